@@ -5,19 +5,26 @@ synthetic catalogue (BASELINE.json configs[2]; configs[3] when --gpus > 1).
 A step = one query = one fused streaming pass over the catalogue (row-sharded
 over the ranks when N > 1, merged with ONE all-gather of 100 packed keys per
 rank) + the device merge.  The catalogue is resident in HBM before the timed
-region; results stay on the device (800 B of keys per query).  Outside the
-timed region the same line carries `microbatch` (12 queries per exact pass) and
-`batched` (BASELINE configs[4]'s 1024-query batches on the matrix-core path,
-with its compute roofline).
+region; results stay on the device (800 B of keys per query).
+
+A plain run sets up, warms up, times ONE region of exactly --steps steps and
+prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype,
+ms_per_step and the run's configuration.  --dump-outputs DIR also writes what
+the last timed step computed (its top-N rows and scores) as DIR/*.npy.
+
+--full adds, outside the timed region, everything else the benchmark measures
+and checks: the timed region repeated (`value` = the median of --repeats
+regions), `roofline` (scan kernel vs the 8 TB/s HBM peak, HIP events in an
+untimed pass of the same stream), latency, `microbatch` (12 queries per exact
+pass), `batched` (BASELINE configs[4]'s 1024-query batches on the matrix-core
+path, with its compute roofline), the stream over the fp32 rows, read probes,
+the `clustered` and `config0` objects, `cpu_baseline` (the oracle on the host
+cores, N=1 only, bounded sample) and the results checked against the oracle.
 
   python bench.py --gpus 1 --steps 300 --warmup 30
+  python bench.py --gpus 1 --steps 300 --warmup 30 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
-
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying
-`roofline` (scan kernel vs the 8 TB/s HBM peak, HIP-event timed inside the
-timed region) and `cpu_baseline` (the oracle on this box's host cores,
-N=1 only, bounded sample).
 """
 from __future__ import annotations
 
@@ -52,9 +59,15 @@ def parse_args():
     ap.add_argument("--event-stride", type=int, default=0,
                     help="HIP events around every k-th scan launch of the UNTIMED pass that fills roofline.avg_kernel_ms "
                          "(0 = choose so that 16 launches are timed, 3 in a short run)")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: repeated timed regions, rooflines, latency, the other paths and sizes, "
+                         "probes, the CPU baseline and the check against the oracle (a plain run times ONE region and stops)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (its top-N rows as float64, scores as "
+                         "float32) to DIR/topn_rows.npy and DIR/topn_scores.npy")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the K-step timed region is run this many times back to back (each between barrier + synchronize pairs); "
-                         "`value` is the median run, `value_runs` lists them all")
+                         "`value` is the median run, `value_runs` lists them all (default: 1, or 5 with --full)")
     ap.add_argument("--batch", type=int, default=1024, help="queries per call of the batched (configs[4]) leg")
     ap.add_argument("--no-batched", action="store_true")
     ap.add_argument("--no-c5-shard", action="store_true",
@@ -97,7 +110,26 @@ def parse_args():
     ap.add_argument("--transport", choices=["auto", "peer", "rccl"], default="auto",
                     help="N > 1, single process: how the per-shard key lists meet (default: peer stores where every "
                          "device can map the first one's memory, else one ncclAllGather per rank)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
+
+
+def value_note(runs: int, steps: int, bracket: str) -> str:
+    if runs == 1:
+        return f"one {steps}-step region, {bracket}"
+    return f"median of {runs} back-to-back {steps}-step regions, each {bracket}"
+
+
+def dump_outputs(out_dir, rows, scores) -> None:
+    """--dump-outputs: the last timed step's result as a caller of the timed path receives it — the top-N rows (float64,
+    exact for every row index) and their scores (float32, bit for bit)."""
+    import numpy as np
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "topn_rows.npy", np.asarray(rows).astype(np.float64))
+    np.save(d / "topn_scores.npy", np.asarray(scores).astype(np.float32))
 
 
 def workload_label(n: int, topn: int) -> str:
@@ -283,7 +315,7 @@ def run_node(args, json_fd):
         return dt, last, shard_ms, host_us, st1["exchanges"] - st0["exchanges"]
 
     # the timed region is run `--repeats` times back to back; `value` is the median run (as at N = 1)
-    runs = [timed_stream(events=(i == 0)) for i in range(max(1, args.repeats))]
+    runs = [timed_stream(events=(i == 0 and args.full)) for i in range(max(1, args.repeats))]
     run_times = [r[0] for r in runs]
     mid = sorted(range(len(runs)), key=lambda i: run_times[i])[len(runs) // 2]
     elapsed, last_result, _, host_us, exchanges = runs[mid]
@@ -291,6 +323,46 @@ def run_node(args, json_fd):
     st_headline = node.shard_stats(0)   # which copy of the rows the headline's queries scan
     replica = bool(st_headline.replica_active)
     rows_local = max(info["shard_rows"])
+
+    head = {
+        "metric": metric_label(n, topn), "value": round(args.steps / elapsed, 2), "unit": "queries/s",
+        "n_gpus": 1 if virtual else g, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 5), "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": replica_desc(st_headline)[4],
+        "data": "synthetic",
+        "value_runs": [round(args.steps / t, 1) for t in run_times],
+        "value_note": value_note(len(run_times), args.steps, "between synchronisations of every device"),
+        "config": {
+            "workload": f"{n} synthetic tracks x 12 fp32 features, top-{topn}, "
+                        + ("REPLICATED on " if replicated else "row-sharded over ")
+                        + (f"{g} VIRTUAL {'replicas' if replicated else 'shards'} of one MI355X (orchestration rehearsal)" if virtual else f"{g} MI355X")
+                        + (" (BASELINE configs[3])" if (n == 10_000_000 and topn == 100 and not replicated) else ""),
+            "engine": "ONE process, the product's C-ABI: mi355rec_create_placed (csrc/sharded.hip)",
+            "placement": args.placement,
+            "placement_note": ("every device holds all rows and serves whole windows of the stream, round-robin: no exchange"
+                               if replicated else
+                               "rows split into contiguous blocks, one per device; one exchange + one merge per window (north_star)"),
+            "rows": n, "topn": topn, "shards": g, "virtual_shards": virtual, "devices": devices,
+            "rows_per_shard": rows_local, "queries_per_step": 1,
+            "transport": "peer" if transport == capi.TRANSPORT_PEER else "rccl",
+            "window": args.window,
+            "window_mode": ("streamed: one scan launch per query on the window's replica" if replicated
+                            else "streamed: one scan launch per shard per query"), "exchanges_in_timed_region": exchanges,
+            "rows_by_pointer": node.rows_by_pointer(), "note": node.note(),
+            "merge": "per shard inside the next query's scan launch (streamed); one exchange + one batched merge per window; "
+                     "last window flushed and its result awaited inside the timed region",
+            "seed": args.seed, "generator": "torch.rand(seed) uniform[0,1) on device 0, sharded from host memory",
+        },
+    }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *last_result)   # the last query of the timed stream, as node.wait returned it
+    if not args.full:
+        # a plain run: the headline figure and nothing else
+        node.close()
+        sys.stdout.flush()
+        os.write(json_fd, (json.dumps(head) + "\n").encode())
+        return
 
     # one query alone, end to end, through the synchronous call the C++ Recommender makes
     lat = []
@@ -407,35 +479,7 @@ def run_node(args, json_fd):
     kernel_label = kernel_label.format(targs="true, true") + f" ({replica_label})"
     achieved = alg / (k_ms * 1e-3) / 1e9 if k_ms > 0 else None
     line = {
-        "metric": metric_label(n, topn), "value": round(args.steps / elapsed, 2), "unit": "queries/s",
-        "n_gpus": 1 if virtual else g, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 5), "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": dtype_label,
-        "data": "synthetic",
-        "value_runs": [round(args.steps / t, 1) for t in run_times],
-        "value_note": f"median of {len(run_times)} back-to-back {args.steps}-step regions, each between synchronisations of every device",
-        "config": {
-            "workload": f"{n} synthetic tracks x 12 fp32 features, top-{topn}, "
-                        + ("REPLICATED on " if replicated else "row-sharded over ")
-                        + (f"{g} VIRTUAL {'replicas' if replicated else 'shards'} of one MI355X (orchestration rehearsal)" if virtual else f"{g} MI355X")
-                        + (" (BASELINE configs[3])" if (n == 10_000_000 and topn == 100 and not replicated) else ""),
-            "engine": "ONE process, the product's C-ABI: mi355rec_create_placed (csrc/sharded.hip)",
-            "placement": args.placement,
-            "placement_note": ("every device holds all rows and serves whole windows of the stream, round-robin: no exchange"
-                               if replicated else
-                               "rows split into contiguous blocks, one per device; one exchange + one merge per window (north_star)"),
-            "rows": n, "topn": topn, "shards": g, "virtual_shards": virtual, "devices": devices,
-            "rows_per_shard": rows_local, "queries_per_step": 1,
-            "transport": transport_name(transport),
-            "window": args.window,
-            "window_mode": ("streamed: one scan launch per query on the window's replica" if replicated
-                            else "streamed: one scan launch per shard per query"), "exchanges_in_timed_region": exchanges,
-            "rows_by_pointer": node.rows_by_pointer(), "note": node.note(),
-            "merge": "per shard inside the next query's scan launch (streamed); one exchange + one batched merge per window; "
-                     "last window flushed and its result awaited inside the timed region",
-            "seed": args.seed, "generator": "torch.rand(seed) uniform[0,1) on device 0, sharded from host memory",
-        },
+        **head,
         "p50_ms": round(lat[len(lat) // 2], 4) if lat else None,
         "p99_ms": round(lat[min(len(lat) - 1, int(len(lat) * 0.99))], 4) if lat else None,
         "roofline": {   # (<= 20 scalar keys; per launch of one shard, mean over the shards; every shard's own figures: `per_gpu`)
@@ -550,7 +594,7 @@ def main():
     full = synthetic_catalogue(n, seed=args.seed, device=dev)
     q_vecs = full[torch.tensor(q_rows, device=dev)].cpu().numpy()
     lo, hi = shard_bounds(n, world, rank)
-    feats_host = full.cpu().numpy() if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    feats_host = full.cpu().numpy() if (rank == 0 and world == 1 and args.full and not args.no_cpu_baseline) else None
     if world > 1:
         shard = full[lo:hi].clone()
         del full
@@ -658,10 +702,57 @@ def main():
             dt = float(t.item())
         return dt
 
-    rc_before = lane_counters() if replica else None
+    rc_before = lane_counters() if (replica and args.full) else None
     run_times = [timed_region() for _ in range(max(1, args.repeats))]
-    rc_after = lane_counters() if replica else None
+    rc_after = lane_counters() if (replica and args.full) else None
     elapsed = sorted(run_times)[len(run_times) // 2]
+    value_runs = [round(args.steps / t, 1) for t in run_times]
+    head = {
+        "metric": metric_label(n, topn),
+        "value": round(args.steps / elapsed, 2), "unit": "queries/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 5),
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": replica_desc(st_headline)[4], "data": "synthetic",
+        "value_runs": value_runs,
+        "value_note": value_note(len(run_times), args.steps, "between barrier + synchronize pairs"),
+        "config": {
+            "workload": f"{n} synthetic tracks x 12 fp32 features, top-{topn}, "
+                        + (f"1 MI355X ({workload_label(n, topn)})" if world == 1 else
+                           f"row-sharded across {world} MI355X, one process per GPU, one all-gather of {topn} keys/rank "
+                           + ("(BASELINE configs[3])" if (n == 10_000_000 and topn == 100) else "")),
+            "rows": n, "topn": topn, "rows_per_gpu": hi - lo, "queries_per_step": 1,
+            "lanes": n_lanes if sharded is None else rank_lanes,
+            "lane_streams": ([ln.lane_status() for ln in lanes[1:]] if (sharded is None and n_lanes > 1) else None),
+            "lanes_note": (f"the stream is dealt over {n_lanes} lanes of one handle (mi355rec_create_lane: same rows and replicas, own "
+                           "stream state and HIP stream); `single_lane` (--full) is the same stream through one handle" if n_lanes > 1 else None),
+            "merge": ("inside the next query's scan launch (streamed), last one flushed in the timed region"
+                      if streamed else ("own launch per query" if sharded is None else
+                                        f"local merge streamed; one all-gather + one batched merge per {args.window} queries")),
+            "seed": args.seed, "generator": "torch.rand(seed) uniform[0,1) on device",
+            "host_wait": ("polled completion signals (HSA_ENABLE_INTERRUPT=0, set by bench.py)" if os.environ.get("HSA_ENABLE_INTERRUPT") == "0"
+                          else ("the runtime's default (interrupt-driven)" if os.environ.get("HSA_ENABLE_INTERRUPT") is None
+                                else f"HSA_ENABLE_INTERRUPT={os.environ.get('HSA_ENABLE_INTERRUPT')} (the caller's)")),
+        },
+    }
+    if args.dump_outputs and rank == 0:
+        # the last step of the timed stream: its keys as the caller's ring (streamed), out_keys (one launch per query) or the last
+        # window merged (N > 1) hold them
+        if sharded is not None:
+            last_keys = sharded.window_keys[-1]
+        else:
+            last_keys = ring_of(total_q - 1) if streamed else out_keys
+        dump_outputs(args.dump_outputs, *unpack_keys(last_keys.cpu().numpy()))
+    if not args.full:
+        # a plain run: the headline figure and nothing else
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(head) + "\n").encode())
+        for ln in lanes[1:]:
+            ln.close()
+        eng.close()
+        if world > 1 or force_sharded:
+            dist.destroy_process_group()
+        return
     # ... and the kernel's duration from an UNTIMED pass of the same stream (same lanes, same queries): HIP events around every
     # stride-th scan launch of lane 0, on the stream the kernel is launched on
     stride = args.event_stride if args.event_stride > 0 else max(1, -(-args.steps // (16 if args.steps >= 64 else 3)))
@@ -1102,33 +1193,8 @@ def main():
             survey = {"kernel_us": round(scan_ms * 1e3, 2), "achieved": round(per_launch, 1), "frac": round(per_launch / HBM_PEAK_GBPS, 4)}
         rescored = (round((rc_after["rescored_rows"] - rc_before["rescored_rows"]) / max(1, rc_after["scans"] - rc_before["scans"]), 1)
                     if replica else None)
-        value_runs = [round(args.steps / t, 1) for t in run_times]
         line = {
-            "metric": metric_label(n, topn),
-            "value": round(qps, 2), "unit": "queries/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 5),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": dtype_label, "data": "synthetic",
-            "value_runs": value_runs,
-            "value_note": f"median of {len(run_times)} back-to-back {args.steps}-step regions, each between barrier + synchronize pairs",
-            "config": {
-                "workload": f"{n} synthetic tracks x 12 fp32 features, top-{topn}, "
-                            + (f"1 MI355X ({workload_label(n, topn)})" if world == 1 else
-                               f"row-sharded across {world} MI355X, one process per GPU, one all-gather of {topn} keys/rank "
-                               + ("(BASELINE configs[3])" if (n == 10_000_000 and topn == 100) else "")),
-                "rows": n, "topn": topn, "rows_per_gpu": hi - lo, "queries_per_step": 1,
-                "lanes": n_lanes if sharded is None else rank_lanes,
-                "lane_streams": ([ln.lane_status() for ln in lanes[1:]] if (sharded is None and n_lanes > 1) else None),
-                "lanes_note": (f"the stream is dealt over {n_lanes} lanes of one handle (mi355rec_create_lane: same rows and replicas, own "
-                               "stream state and HIP stream); `single_lane` is the same stream through one handle" if n_lanes > 1 else None),
-                "merge": ("inside the next query's scan launch (streamed), last one flushed in the timed region"
-                          if streamed else ("own launch per query" if sharded is None else
-                                            f"local merge streamed; one all-gather + one batched merge per {args.window} queries")),
-                "seed": args.seed, "generator": "torch.rand(seed) uniform[0,1) on device",
-                "host_wait": ("polled completion signals (HSA_ENABLE_INTERRUPT=0, set by bench.py)" if os.environ.get("HSA_ENABLE_INTERRUPT") == "0"
-                              else ("the runtime's default (interrupt-driven)" if os.environ.get("HSA_ENABLE_INTERRUPT") is None
-                                    else f"HSA_ENABLE_INTERRUPT={os.environ.get('HSA_ENABLE_INTERRUPT')} (the caller's)")),
-            },
+            **head,
             "p50_ms": round(lat[len(lat) // 2], 4) if lat else None,
             "p99_ms": round(lat[min(len(lat) - 1, int(len(lat) * 0.99))], 4) if lat else None,
             # <= 20 SCALAR keys, short strings (the driver's record keeps a bounded number of keys and characters): everything

@@ -233,10 +233,11 @@ def build_oracle(force: bool = False) -> Path:
     target = odir / "liboracle.so"
     if force or _stale(target, [odir / "cosine_oracle.c", odir / "cosine_oracle.h"]):
         _run(["make", "-C", odir, "liboracle.so"])
-    if Path("/root/reference/DataManager.cpp").exists():
-        ref = odir / "_ref" / "libref_dm.so"
-        if force or _stale(ref, [odir / "ref_dm_driver.cpp"]):
-            _run(["make", "-C", odir, "ref"])
+    # (the Makefile's `ref` target builds oracle/_ref only where the reference tree is present AND readable by the user
+    # building: a tree this user may not read counts as absent, whatever was prebuilt is kept)
+    ref = odir / "_ref" / "libref_dm.so"
+    if force or _stale(ref, [odir / "ref_dm_driver.cpp"]):
+        _run(["make", "-C", odir, "ref"])
     return target
 
 

@@ -24,6 +24,12 @@ Provenance of each file:
       recorded outputs (survey_pins.json).
   survey_pins.json
       the reference outputs recorded in SURVEY.md §8(c)/§6.2, verbatim.
+  preprocess_reference_sha256.json
+      SHA-256 and size of the songs_data.bin the REFERENCE's own DataManager
+      (oracle/_ref/libref_dm.so, OMP_NUM_THREADS=1) writes for each generated
+      CSV of tests/test_datamanager.py's side-by-side cases (make_csv: seeded,
+      edge rows, optional BOM), so the drop-in's bytes are pinned to the
+      reference's without the reference present.
 """
 from __future__ import annotations
 
@@ -97,6 +103,41 @@ def make_sample_bin() -> None:
     print("sample bin:", out.stat().st_size, "bytes,", n, "songs,", genres)
 
 
+# (rows, genres, seed, bom): the cases of tests/test_datamanager.py::test_preprocess_matches_reference_code_side_by_side
+PREPROCESS_CASES = [(300, 5, 1, False), (5000, 37, 2, True), (1500, 1, 3, False)]
+
+
+def preprocess_case_key(rows, genres, seed, bom) -> str:
+    return f"{rows}-{genres}-{seed}-{'bom' if bom else 'nobom'}"
+
+
+def make_preprocess_digests() -> None:
+    import hashlib
+    import subprocess
+    import tempfile
+
+    from tests.test_datamanager import make_csv
+
+    ref = ROOT / "oracle" / "_ref" / "libref_dm.so"
+    if not ref.exists():
+        print("oracle/_ref/libref_dm.so missing (reference not present) — keeping committed preprocess digests")
+        return
+    # the reference in its own process, single-threaded (its multi-thread genre ids are nondeterministic)
+    code = ("import ctypes,sys; L=ctypes.CDLL(sys.argv[1]); L.ref_dm_preprocess.argtypes=[ctypes.c_char_p]*2; "
+            "sys.exit(0 if L.ref_dm_preprocess(sys.argv[2].encode(), sys.argv[3].encode())==1 else 1)")
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for case in PREPROCESS_CASES:
+            csv, binf = Path(tmp) / "in.csv", Path(tmp) / "theirs.bin"
+            make_csv(csv, *case)
+            subprocess.run([sys.executable, "-c", code, str(ref), str(csv), str(binf)], check=True, env=env, capture_output=True)
+            data = binf.read_bytes()
+            out[preprocess_case_key(*case)] = {"sha256": hashlib.sha256(data).hexdigest(), "bytes": len(data)}
+    (GOLD / "preprocess_reference_sha256.json").write_text(json.dumps(out, indent=1) + "\n")
+    print("preprocess digests:", out)
+
+
 def make_catalogue() -> None:
     n = 4096
     f = oracle.mt19937_uniform(20251017, n)
@@ -163,3 +204,4 @@ if __name__ == "__main__":
     make_catalogue()
     make_seeded_top100()
     make_pins()
+    make_preprocess_digests()

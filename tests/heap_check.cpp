@@ -9,15 +9,7 @@
 #include <queue>
 #include <vector>
 
-#ifdef HEAP_CHECK_REFERENCE_HEADER
-// Build container only (-I /root/reference): the reference's OWN Recommendation
-// struct and comparator (Recommender.h:12-22), not a restatement.
-#include "Recommender.h"
-typedef Recommendation Rec;
-static inline int rec_idx(const Rec& r) { return r.songIndex; }
-static inline float rec_sim(const Rec& r) { return r.similarity; }
-#else
-// Where /root/reference is absent (the GPU box): the same 3 lines restated.
+// The Recommendation struct and comparator of Recommender.h:12-22, restated.
 struct Rec {
     int songIndex;
     float similarity;
@@ -26,7 +18,6 @@ struct Rec {
 };
 static inline int rec_idx(const Rec& r) { return r.songIndex; }
 static inline float rec_sim(const Rec& r) { return r.similarity; }
-#endif
 
 int main(int argc, char** argv) {
     if (argc < 4) return 2;

@@ -1,18 +1,13 @@
 """songs_data.bin format + CSV preprocessing of the C++ drop-in, pinned against
 files the REFERENCE's own DataManager wrote (tests/golden/, generated through
-oracle/_ref) and, when oracle/_ref is present, against the reference's code
-run side by side on freshly generated CSVs."""
+oracle/_ref) and against the digests of what the reference's code wrote for
+freshly generated CSVs (tests/golden/preprocess_reference_sha256.json)."""
 import ctypes
+import hashlib
 import json
-import os
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
-
-ROOT = Path(__file__).resolve().parents[1]
-REF_LIB = ROOT / "oracle" / "_ref" / "libref_dm.so"
 
 
 @pytest.fixture(scope="module")
@@ -117,22 +112,19 @@ def make_csv(path, rows, genres, seed, bom=False):
     path.write_text("\n".join(lines) + "\n", encoding="utf-8")
 
 
-@pytest.mark.skipif(not REF_LIB.exists(), reason="oracle/_ref not built (reference absent)")
 @pytest.mark.parametrize("rows,genres,seed,bom", [(300, 5, 1, False), (5000, 37, 2, True), (1500, 1, 3, False)])
-def test_preprocess_matches_reference_code_side_by_side(shim, tmp_path, rows, genres, seed, bom):
+def test_preprocess_matches_reference_code_side_by_side(shim, tmp_path, golden_dir, rows, genres, seed, bom):
+    """The reference's DataManager run on the same generated CSV wrote a file of this SHA-256 and size
+    (tests/golden/preprocess_reference_sha256.json, recorded through oracle/_ref by tests/golden/make_fixtures.py)."""
     csv = tmp_path / "in.csv"
     make_csv(csv, rows, genres, seed, bom)
     ours = tmp_path / "ours.bin"
-    theirs = tmp_path / "theirs.bin"
     assert shim.shim_preprocess(str(csv).encode(), str(ours).encode()) == 1
-    # the reference in its own process, single-threaded (its multi-thread genre ids are nondeterministic)
-    code = ("import ctypes,sys; L=ctypes.CDLL(sys.argv[1]); L.ref_dm_preprocess.argtypes=[ctypes.c_char_p]*2; "
-            "sys.exit(0 if L.ref_dm_preprocess(sys.argv[2].encode(), sys.argv[3].encode())==1 else 1)")
-    env = dict(os.environ, OMP_NUM_THREADS="1")
-    subprocess.run(["python3", "-c", code, str(REF_LIB), str(csv), str(theirs)], check=True, env=env,
-                   capture_output=True)
-    assert ours.read_bytes() == theirs.read_bytes()
-    feats, genre, strings, gmap = load_all(shim, theirs)
+    want = json.loads((golden_dir / "preprocess_reference_sha256.json").read_text())
+    want = want[f"{rows}-{genres}-{seed}-{'bom' if bom else 'nobom'}"]
+    data = ours.read_bytes()
+    assert len(data) == want["bytes"] and hashlib.sha256(data).hexdigest() == want["sha256"]
+    feats, genre, strings, gmap = load_all(shim, ours)
     assert feats.min() >= 0.0 and feats.max() <= 1.0 and len(gmap) == genres
 
 

@@ -1,7 +1,7 @@
 # A/B on one box: the runtime's default (interrupt-driven completion signals) against HSA_ENABLE_INTERRUPT=0 (polled), the whole
 # 20-step line twice each way: the headline, the batched legs over lanes, the sorted-catalogue batch.
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-A="--steps 20 --warmup 5 --no-cpu-baseline --no-config0 --latency-queries 300"
+A="--full --steps 20 --warmup 5 --no-cpu-baseline --no-config0 --latency-queries 300"
 for i in 1 2; do
 for E in 1 0; do
 HSA_ENABLE_INTERRUPT=$E python3 bench.py $A 2>/dev/null | python3 -c "

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where a short timed region of bench.py spends its time on the GPU: from a rocprofv3 --kernel-trace CSV of
-  rocprofv3 --kernel-trace --output-format csv -d <dir> -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-config0 --no-clustered --no-batched --no-single-lane --latency-queries 5
+  rocprofv3 --kernel-trace --output-format csv -d <dir> -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-config0 --no-clustered --no-batched --no-single-lane --latency-queries 5
 prints, for every burst of streamed 8-bit scans (bursts are separated by more than 12 us of idle GPU: the fences between the regions), the span from the first
 kernel's start to the last kernel's end, the sum of the kernels' durations per hardware queue, and the timeline of the launches."""
 import csv

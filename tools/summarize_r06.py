@@ -67,12 +67,12 @@ if os.path.exists(f"{root}/bench.json") and newest(f"{root}/trace/**/*kernel_sta
     subprocess.run([sys.executable, "tools/summarize_profiles.py", "r06", f"{root}/trace", f"{root}/fetch", f"{root}/write", f"{root}/bench.json"], check=True)
     p = "profiles/r06_pmc_hbm_traffic.json"
     d = json.load(open(p))
-    d["command"] = ("rocprofv3 --pmc <COUNTER> --output-format csv -- python3 bench.py --lanes 1 --steps 40 --warmup 5 --no-cpu-baseline --no-config0 "
+    d["command"] = ("rocprofv3 --pmc <COUNTER> --output-format csv -- python3 bench.py --full --lanes 1 --steps 40 --warmup 5 --no-cpu-baseline --no-config0 "
                     "--no-clustered --no-single-lane --latency-queries 50 --no-c5-shard   (ONE handle: a launch's bytes are its own; one counter per pass)")
     json.dump(d, open(p, "w"), indent=1)
 if os.path.exists(f"{root}/bench20.json"):
     shutil.copy(f"{root}/bench20.json", "profiles/r06_bench_n1_20steps.json")
-write_csv("profiles/r06_kernel_stats_one_handle.csv", kernel_stats("trace1", "python3 bench.py --lanes 1 (one handle: streamed kernels alone on the chip)"))
+write_csv("profiles/r06_kernel_stats_one_handle.csv", kernel_stats("trace1", "python3 bench.py --full --lanes 1 (one handle: streamed kernels alone on the chip)"))
 
 # ---- PART C
 rows = []
@@ -110,7 +110,7 @@ if a and b:
 # ---- PART D
 if os.path.exists(f"{root}/clustered.json") and os.path.getsize(f"{root}/clustered.json"):
     d = json.load(open(f"{root}/clustered.json"))
-    json.dump({"command": "python bench.py --catalogue clustered-contiguous --steps 100 --warmup 10 --no-cpu-baseline --no-config0 --no-c5-shard --latency-queries 100",
+    json.dump({"command": "python bench.py --full --catalogue clustered-contiguous --steps 100 --warmup 10 --no-cpu-baseline --no-config0 --no-c5-shard --latency-queries 100",
                "clustered": d.get("clustered")}, open("profiles/r06_clustered.json", "w"), indent=1)
     print("profiles/r06_clustered.json")
 if os.path.exists(f"{root}/other_configs.jsonl"):
