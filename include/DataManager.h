@@ -47,6 +47,7 @@ public:
         std::vector<std::string> trackNames;
         std::vector<uint64_t> recordOffsets;    // byte offset of song i in the file
         std::map<int, std::string> genreMap;
+        std::vector<int> genreIds;              // song i's genre id (Song::genre_id): the labels of genre-restricted queries
         // readSong's file handle: created by loadCatalogue (shared by copies of the catalogue), opened on first use
         // and kept (one open per catalogue, not per printed song); the mutex makes readSong safe to call from
         // several threads, on one catalogue or on copies of it

@@ -73,6 +73,14 @@ public:
     const std::vector<float>& lastScores() const;
     bool similarities(int songIndex, std::vector<float>& out);
 
+    // Extension: genre-restricted recommendations.  recommendByIndexInGenres returns the ids of the topN songs most
+    // similar to songIndex among the songs whose genre id is in genreIds (same checks, messages, order and exclusion
+    // as recommendByIndex; lastScores() is filled the same way).  initialize(songs) keeps the songs' genre ids;
+    // after the matrix overload of initialize, setGenreIds gives them (one per song; -1 = no genre).  The labels
+    // reach the engine on the first genre-restricted call.
+    bool setGenreIds(const std::vector<int>& genreIds);
+    std::vector<int> recommendByIndexInGenres(int songIndex, int topN, const std::vector<int>& genreIds);
+
     struct Impl;   // opaque: defined in Recommender.cpp
 
 private:

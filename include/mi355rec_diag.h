@@ -11,6 +11,9 @@
  *     Recommender::calculateSimilarities, Recommender.h:114), and the probes (mi355rec_enqueue_stream_probe*);
  *   - the building blocks the multi-GPU layers are made of: queries by device pointer, mixed batches, the merge-only entry
  *     points (mi355rec_enqueue_merge_keys*), mi355rec_fetch_row, the explicit set-ups of the node handle;
+ *   - LABELS, an extension beyond the reference (which lists "recommendations within genre" among its extensions only):
+ *     rows carry an integer label (a genre id) and a query returns the top-N rows whose label is in a given set
+ *     (mi355rec_set_labels, _query_row_topn_labels, _query_topn_labels, _label_counters and their node-handle twins);
  *   - test hooks, compiled in only with -DMI355REC_TEST_HOOKS (spotify_recommender_amd/build.py builds
  *     libmi355rec_testhooks.so for tests/; the product library does not export them).
  */
@@ -338,6 +341,41 @@ int mi355rec_sharded_stream_stats(const mi355rec_sharded_t* h, int64_t* queries,
  * communicator reports the same count and its own shard index as its rank (ncclCommUserRank).  bench.py --gpus N puts these
  * in its line, so that a first run on a real node answers "did RCCL see N ranks" by itself.  Any pointer may be NULL. */
 int mi355rec_sharded_rccl_ranks(const mi355rec_sharded_t* h, int* comms, int* ranks, int* ranks_agree);
+
+/* LABELS (an extension beyond the reference): label-filtered top-N.
+ * Every row of a handle may carry a label in [0, MI355REC_MAX_LABELS) — a genre id, or any category the caller chooses —
+ * or -1 (unlabelled: never returned by a filtered query).  mi355rec_set_labels builds a copy of the shard's fp32 rows
+ * grouped by label (labels ascending, rows stable inside a label, unlabelled rows last; +52 B per row of device memory:
+ * the 48-B row and its 4-B original index) and the label offsets.  It gathers the rows to the host, sorts them there
+ * and uploads the copy: a one-time cost, O(n), paid by this call.  Calling it again replaces the labels; labels_host ==
+ * NULL drops them; n must be the handle's row count.  A failure (out of memory, a HIP error) leaves the previous labels in
+ * place.  A handle that has lanes (mi355rec_create_lane) refuses it (INVALID_ARG): the labels are shared by the group, and
+ * a lane made afterwards shares them without a copy.
+ * A filtered query has the arithmetic, canonical order (score descending, then row ascending, -0.0 reported as +0.0)
+ * and exclusion of mi355rec_query_row_topn / _query_topn, restricted to the rows whose label is in labels[0..n_labels)
+ * (duplicates allowed): count = min(topn, |selected rows| - [the excluded row is selected]), the rest padded with -1 / 0;
+ * a set whose labels hold no rows answers count 0.  INVALID_ARG (with a message) for n_labels <= 0, a label outside
+ * [0, MI355REC_MAX_LABELS) and a handle without labels.  One launch per query (per round of 1024 above topn 1024) scans
+ * only the selected labels' rows (csrc/labels.hip.h), then the merge.  No asynchronous, streamed or windowed variant.
+ * mi355rec_label_counters: filtered queries since create, and the rows their launches scanned (whole tiles of 512 rows
+ * per selected label).  Either pointer may be NULL.
+ * Node handle: one shard forwards; a replicated placement gives the labels to every replica and a query to one of them;
+ * a row-sharded one gives each shard its slice, runs a query on every shard (by value, the query row excluded by its
+ * global index) and merges the per-shard lists on the host (exact).  If any shard fails, the labels are dropped on
+ * every shard.  The CPU backend (hosts without a device) serves the same calls. */
+#define MI355REC_MAX_LABELS 1024
+int mi355rec_set_labels(mi355rec_t* h, const int32_t* labels_host, int64_t n);
+int mi355rec_query_row_topn_labels(mi355rec_t* h, int64_t local_row, const int32_t* labels, int n_labels, int topn,
+                                   int64_t* out_idx, float* out_score, int* out_count);
+int mi355rec_query_topn_labels(mi355rec_t* h, const float* query12, int64_t exclude_global, const int32_t* labels,
+                               int n_labels, int topn, int64_t* out_idx, float* out_score, int* out_count);
+int mi355rec_label_counters(const mi355rec_t* h, int64_t* queries, int64_t* rows_scanned);
+int mi355rec_sharded_set_labels(mi355rec_sharded_t* h, const int32_t* labels_host, int64_t n);
+int mi355rec_sharded_query_row_topn_labels(mi355rec_sharded_t* h, int64_t global_row, const int32_t* labels, int n_labels,
+                                           int topn, int64_t* out_idx, float* out_score, int* out_count);
+int mi355rec_sharded_query_topn_labels(mi355rec_sharded_t* h, const float* query12, int64_t exclude_global,
+                                       const int32_t* labels, int n_labels, int topn, int64_t* out_idx, float* out_score,
+                                       int* out_count);
 
 #ifdef MI355REC_TEST_HOOKS
 /* TEST HOOK for the cross-workgroup hand-offs of the streamed scans (csrc/replica.hip.h, "hand-offs that fail

@@ -32,6 +32,7 @@ ERR_INVALID_ARG = -1
 ERR_NO_DEVICE = -2
 ERR_HIP = -3
 ERR_OUT_OF_MEMORY = -4
+MAX_LABELS = 1024
 
 
 class Stats(ctypes.Structure):
@@ -147,6 +148,15 @@ SIGNATURES = {
     "mi355rec_sharded_stream_stats": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     "mi355rec_debug_handoff": (c_int, [c_void_p, c_int]),
     "mi355rec_sharded_rccl_ranks": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "mi355rec_set_labels": (c_int, [c_void_p, c_void_p, c_int64]),
+    "mi355rec_query_row_topn_labels": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p, POINTER(c_int)]),
+    "mi355rec_query_topn_labels": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p, POINTER(c_int)]),
+    "mi355rec_label_counters": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),
+    "mi355rec_sharded_set_labels": (c_int, [c_void_p, c_void_p, c_int64]),
+    "mi355rec_sharded_query_row_topn_labels": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                                       POINTER(c_int)]),
+    "mi355rec_sharded_query_topn_labels": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                                   POINTER(c_int)]),
     "mi355rec_pack_key": (c_uint64, [c_float, c_int64]),
     "mi355rec_key_score": (c_float, [c_uint64]),
     "mi355rec_key_row": (c_int64, [c_uint64]),

@@ -293,7 +293,7 @@ namespace {
 
 bool walkBinary(const std::string& binaryPath, std::vector<float>& features, std::vector<std::string>& trackIds,
                 std::vector<std::string>& trackNames, std::vector<uint64_t>* offsets,
-                std::map<int, std::string>* genreMap) {
+                std::map<int, std::string>* genreMap, std::vector<int>* genreIds = nullptr) {
     const int fd = ::open(binaryPath.c_str(), O_RDONLY);
     if (fd < 0) return false;
     struct stat st;
@@ -343,6 +343,7 @@ bool walkBinary(const std::string& binaryPath, std::vector<float>& features, std
         trackIds.resize(numSongs);
         trackNames.resize(numSongs);
         if (offsets) offsets->resize(numSongs);
+        if (genreIds) genreIds->resize(numSongs);
     }
     for (size_t i = 0; ok && i < numSongs; ++i) {
         if (offsets) (*offsets)[i] = static_cast<uint64_t>(p - begin);
@@ -351,6 +352,7 @@ bool walkBinary(const std::string& binaryPath, std::vector<float>& features, std
         takeString(nullptr);  // artists
         int genre = 0;
         take(&genre, sizeof genre);
+        if (genreIds) (*genreIds)[i] = genre;
         take(&features[i * FEATURE_COUNT], FEATURE_COUNT * sizeof(float));
     }
     ::munmap(map, size);
@@ -360,6 +362,7 @@ bool walkBinary(const std::string& binaryPath, std::vector<float>& features, std
         trackNames.clear();
         if (offsets) offsets->clear();
         if (genreMap) genreMap->clear();
+        if (genreIds) genreIds->clear();
     }
     return ok;
 }
@@ -376,7 +379,7 @@ bool DataManager::loadCatalogue(const std::string& binaryPath, Catalogue& out) {
     std::cout << "Loading preprocessed data from: " << binaryPath << std::endl;
     out.path = binaryPath;
     out.reader = std::make_shared<Catalogue::Reader>();   // opened by the first readSong
-    if (!walkBinary(binaryPath, out.features, out.trackIds, out.trackNames, &out.recordOffsets, &out.genreMap)) {
+    if (!walkBinary(binaryPath, out.features, out.trackIds, out.trackNames, &out.recordOffsets, &out.genreMap, &out.genreIds)) {
         std::cerr << "Error: Could not read binary file: " << binaryPath << std::endl;
         return false;
     }

@@ -24,6 +24,11 @@ struct Recommender::Impl {
     std::vector<std::string> lowerNames;
     std::unordered_map<std::string, int> byId;
 
+    // genre ids of the songs (one per song, -1 = none; empty: not known) and whether the engine has them yet: they are
+    // uploaded by the first genre-restricted query, so that initialize costs what it costs without them
+    std::vector<int> genreIds;
+    bool labelsUploaded = false;
+
     std::vector<int64_t> idxBuf;
     std::vector<float> scoreBuf;
     std::vector<float> lastScores;
@@ -65,8 +70,10 @@ bool Recommender::initialize(const std::vector<Song>& songs) {  // Recommender.c
     impl_->lowerNames.reserve(songs.size());
     impl_->byId.clear();
     impl_->byId.reserve(songs.size() * 2);
+    impl_->genreIds.resize(songs.size());
     for (size_t i = 0; i < songs.size(); ++i) {
         std::copy(songs[i].features, songs[i].features + FEATURE_COUNT, matrix.begin() + i * FEATURE_COUNT);
+        impl_->genreIds[i] = songs[i].genre_id;
         impl_->lowerNames.push_back(toLower(songs[i].track_name));
         impl_->byId.emplace(songs[i].track_id, static_cast<int>(i));  // keeps the first
     }
@@ -92,6 +99,7 @@ bool Recommender::initialize(const std::vector<float>& features, const std::vect
         impl_->lowerNames.push_back(toLower(trackNames[i]));
         impl_->byId.emplace(trackIds[i], static_cast<int>(i));
     }
+    impl_->genreIds.clear();
     return startEngine(impl_, features.data(), trackIds.size());
 }
 
@@ -104,6 +112,7 @@ bool startEngine(Recommender::Impl* impl, const float* matrix, size_t n) {
     }
     impl->initialized = false;
     impl->gpuEnabled = false;
+    impl->labelsUploaded = false;
     impl->numSongs = static_cast<int>(n);
     // The reference pins device 0 (Recommender.cu:124).  Here the library places the catalogue itself: one device up
     // to 7.9 M rows, row-sharded over as many as keep 4 M rows per shard beyond that (one process, one stream per
@@ -141,28 +150,84 @@ bool startEngine(Recommender::Impl* impl, const float* matrix, size_t n) {
 
 }  // namespace
 
-std::vector<int> Recommender::recommendByIndex(int songIndex, int topN) {  // Recommender.cu:275-318
-    if (!impl_->initialized) {
+namespace {
+
+// recommendByIndex's checks (Recommender.cu:275-292); false: nothing to ask the engine (the message, if any, is out).
+bool checkQuery(const Recommender::Impl* impl, int songIndex, int& topN) {
+    if (!impl->initialized) {
         std::cerr << "Error: Recommender not initialized" << std::endl;
-        return {};
+        return false;
     }
-    if (songIndex < 0 || songIndex >= impl_->numSongs) {
+    if (songIndex < 0 || songIndex >= impl->numSongs) {
         std::cerr << "Error: Invalid song index: " << songIndex << std::endl;
-        return {};
+        return false;
     }
     if (topN <= 0) {
         std::cerr << "Error: topN must be positive" << std::endl;
-        return {};
+        return false;
     }
     // The reference's heap never holds more than N-1 entries (Recommender.cu:296-305):
     // a larger topN returns N-1 results, and must not size any buffer.
-    if (topN > impl_->numSongs - 1) topN = impl_->numSongs - 1;
-    if (topN == 0) return {};  // a one-song catalogue has nothing to recommend
+    if (topN > impl->numSongs - 1) topN = impl->numSongs - 1;
+    return topN > 0;   // (a one-song catalogue has nothing to recommend)
+}
+
+}  // namespace
+
+std::vector<int> Recommender::recommendByIndex(int songIndex, int topN) {  // Recommender.cu:275-318
+    if (!checkQuery(impl_, songIndex, topN)) return {};
     impl_->idxBuf.assign(static_cast<size_t>(topN), -1);
     impl_->scoreBuf.assign(static_cast<size_t>(topN), 0.0f);
     int count = 0;
     const int rc = mi355rec_sharded_query_row_topn(impl_->engine, songIndex, topN, impl_->idxBuf.data(),
                                                    impl_->scoreBuf.data(), &count);
+    if (rc != MI355REC_OK) {
+        std::cerr << "Error: " << mi355rec_sharded_last_error(impl_->engine) << std::endl;
+        return {};
+    }
+    std::vector<int> results(static_cast<size_t>(count));
+    for (int i = 0; i < count; ++i) results[i] = static_cast<int>(impl_->idxBuf[i]);
+    impl_->lastScores.assign(impl_->scoreBuf.begin(), impl_->scoreBuf.begin() + count);
+    return results;
+}
+
+bool Recommender::setGenreIds(const std::vector<int>& genreIds) {
+    if (!impl_->initialized || genreIds.size() != static_cast<size_t>(impl_->numSongs)) {
+        std::cerr << "Error: one genre id per song is needed" << std::endl;
+        return false;
+    }
+    for (int g : genreIds)
+        if (g < -1 || g >= MI355REC_MAX_LABELS) {
+            std::cerr << "Error: genre id " << g << " out of [-1, " << MI355REC_MAX_LABELS << ")" << std::endl;
+            return false;
+        }
+    impl_->genreIds = genreIds;
+    impl_->labelsUploaded = false;
+    return true;
+}
+
+std::vector<int> Recommender::recommendByIndexInGenres(int songIndex, int topN, const std::vector<int>& genreIds) {
+    if (!checkQuery(impl_, songIndex, topN)) return {};
+    if (genreIds.empty()) {
+        std::cerr << "Error: no genre to recommend from" << std::endl;
+        return {};
+    }
+    if (!impl_->labelsUploaded) {   // the first genre-restricted query hands the songs' genres to the engine
+        if (impl_->genreIds.size() != static_cast<size_t>(impl_->numSongs)) {
+            std::cerr << "Error: the songs' genre ids are not known (setGenreIds)" << std::endl;
+            return {};
+        }
+        if (mi355rec_sharded_set_labels(impl_->engine, impl_->genreIds.data(), impl_->numSongs) != MI355REC_OK) {
+            std::cerr << "Error: " << mi355rec_sharded_last_error(impl_->engine) << std::endl;
+            return {};
+        }
+        impl_->labelsUploaded = true;
+    }
+    impl_->idxBuf.assign(static_cast<size_t>(topN), -1);
+    impl_->scoreBuf.assign(static_cast<size_t>(topN), 0.0f);
+    int count = 0;
+    const int rc = mi355rec_sharded_query_row_topn_labels(impl_->engine, songIndex, genreIds.data(), static_cast<int>(genreIds.size()),
+                                                          topN, impl_->idxBuf.data(), impl_->scoreBuf.data(), &count);
     if (rc != MI355REC_OK) {
         std::cerr << "Error: " << mi355rec_sharded_last_error(impl_->engine) << std::endl;
         return {};

@@ -147,7 +147,28 @@ void scores(const Catalogue* c, const float* q12, float* out_n) {
     for (int64_t i = 0; i < n; ++i) out_n[i] = score(q12, qn, f + i * kDim);
 }
 
+namespace {
+// The rows a filtered query may return: label[row] is in the set (bit l of mask[l / 32]); null = every row.
+struct LabelFilter {
+    const int32_t* label;
+    const uint32_t* mask;
+    inline bool keeps(int64_t i) const {
+        const int32_t l = label[i];
+        return l >= 0 && ((mask[l >> 5] >> (l & 31)) & 1u);
+    }
+};
+
+int topn_impl(const Catalogue* c, const float* q12, int64_t exclude, int topn, int64_t* out_idx, float* out_score,
+              const LabelFilter* filter);
+}  // namespace
+
 int topn(const Catalogue* c, const float* q12, int64_t exclude, int topn, int64_t* out_idx, float* out_score) {
+    return topn_impl(c, q12, exclude, topn, out_idx, out_score, nullptr);
+}
+
+namespace {
+int topn_impl(const Catalogue* c, const float* q12, int64_t exclude, int topn, int64_t* out_idx, float* out_score,
+              const LabelFilter* filter) {
     if (topn <= 0 || c->n <= 0) return 0;
     const float qn = query_norm(q12);
     const float* f = c->feats.data();
@@ -174,9 +195,16 @@ int topn(const Catalogue* c, const float* q12, int64_t exclude, int topn, int64_
             for (int p = p0; p < p1; ++p) {
                 Best& mine = per_part[static_cast<size_t>(p)];
                 const int64_t lo = n * p / parts, hi = n * (p + 1) / parts;
-                for (int64_t i = lo; i < hi; ++i) {
-                    if (i == exclude) continue;   // by index, not by score (Recommender.cu:296)
-                    mine.offer(pack(score(q12, qn, f + i * kDim), static_cast<uint32_t>(i)));
+                if (filter) {   // (the label test only where a set was given: the unfiltered loop is unchanged)
+                    for (int64_t i = lo; i < hi; ++i) {
+                        if (i == exclude || !filter->keeps(i)) continue;
+                        mine.offer(pack(score(q12, qn, f + i * kDim), static_cast<uint32_t>(i)));
+                    }
+                } else {
+                    for (int64_t i = lo; i < hi; ++i) {
+                        if (i == exclude) continue;   // by index, not by score (Recommender.cu:296)
+                        mine.offer(pack(score(q12, qn, f + i * kDim), static_cast<uint32_t>(i)));
+                    }
                 }
                 mine.cut();   // at most cap keys per part from here on
             }
@@ -196,6 +224,7 @@ int topn(const Catalogue* c, const float* q12, int64_t exclude, int topn, int64_
     }
     return static_cast<int>(count);
 }
+}  // namespace
 
 }  // namespace mi355cpu
 
@@ -228,6 +257,8 @@ struct Node {
     std::vector<float> score;
     std::vector<int> counts;              // [kDepth][window]
     int64_t st_queries = 0, st_windows = 0, st_ns = 0;
+    std::vector<int32_t> labels;          // mi355rec_sharded_set_labels: one per row, -1 = unlabelled (empty: none set)
+    bool has_labels = false;
 };
 
 Node* node_create(const float* feats_rowmajor, int64_t n) {
@@ -264,6 +295,69 @@ int node_query(Node* h, const float* q12, int64_t exclude, int topn_asked, int64
         return MI355REC_ERR_OUT_OF_MEMORY;
     }
     for (int i = c; i < topn_asked; ++i) {   // the C-ABI pads with -1 / 0
+        out_idx[i] = -1;
+        if (out_score) out_score[i] = 0.0f;
+    }
+    if (out_count) *out_count = c;
+    return MI355REC_OK;
+}
+
+int node_set_labels(Node* h, const int32_t* labels, int64_t n, const char** why) {
+    if (!labels) {
+        h->labels.clear();
+        h->has_labels = false;
+        return MI355REC_OK;
+    }
+    if (n != rows(h->cat)) {
+        *why = "the label count must equal the catalogue's rows";
+        return MI355REC_ERR_INVALID_ARG;
+    }
+    for (int64_t i = 0; i < n; ++i)
+        if (labels[i] < -1 || labels[i] >= MI355REC_MAX_LABELS) {
+            *why = "a label is out of [-1, MI355REC_MAX_LABELS)";
+            return MI355REC_ERR_INVALID_ARG;
+        }
+    try {
+        h->labels.assign(labels, labels + n);
+    } catch (const std::bad_alloc&) {
+        *why = "out of host memory";
+        return MI355REC_ERR_OUT_OF_MEMORY;   // (assign gives the strong guarantee: the previous labels stay)
+    }
+    h->has_labels = true;
+    return MI355REC_OK;
+}
+
+int node_query_labels(Node* h, const float* q12, int64_t exclude, const int32_t* set, int n_set, int topn_asked,
+                      int64_t* out_idx, float* out_score, int* out_count, const char** why) {
+    if (topn_asked <= 0) {
+        *why = "topn must be positive";
+        return MI355REC_ERR_INVALID_ARG;
+    }
+    if (n_set <= 0 || !set) {
+        *why = "n_labels must be positive";
+        return MI355REC_ERR_INVALID_ARG;
+    }
+    uint32_t mask[MI355REC_MAX_LABELS / 32] = {0};
+    for (int i = 0; i < n_set; ++i) {
+        if (set[i] < 0 || set[i] >= MI355REC_MAX_LABELS) {
+            *why = "a label of the set is out of [0, MI355REC_MAX_LABELS)";
+            return MI355REC_ERR_INVALID_ARG;
+        }
+        mask[set[i] >> 5] |= 1u << (set[i] & 31);
+    }
+    if (!h->has_labels) {
+        *why = "this handle has no labels (mi355rec_sharded_set_labels)";
+        return MI355REC_ERR_INVALID_ARG;
+    }
+    const LabelFilter filter{h->labels.data(), mask};
+    int c = 0;
+    try {
+        c = topn_impl(h->cat, q12, exclude, topn_asked, out_idx, out_score, &filter);
+    } catch (const std::bad_alloc&) {
+        *why = "out of host memory";
+        return MI355REC_ERR_OUT_OF_MEMORY;
+    }
+    for (int i = c; i < topn_asked; ++i) {
         out_idx[i] = -1;
         if (out_score) out_score[i] = 0.0f;
     }

@@ -52,6 +52,11 @@ void node_destroy(Node* h);
 const Catalogue* node_catalogue(const Node* h);
 int node_query(Node* h, const float* q12, int64_t exclude, int topn, int64_t* out_idx, float* out_score, int* out_count,
                const char** why);
+// LABELS (include/mi355rec_diag.h): one label per row (-1 = unlabelled; labels = null drops them), and the query over the
+// rows whose label is in set[0..n_set) — the same loop with a label test, the same canonical order.
+int node_set_labels(Node* h, const int32_t* labels, int64_t n, const char** why);
+int node_query_labels(Node* h, const float* q12, int64_t exclude, const int32_t* set, int n_set, int topn, int64_t* out_idx,
+                      float* out_score, int* out_count, const char** why);
 int node_set_window(Node* h, int window, const char** why);
 int node_enqueue(Node* h, const float* q12, int64_t exclude, int topn, int64_t* ticket, const char** why);
 int node_flush(Node* h);

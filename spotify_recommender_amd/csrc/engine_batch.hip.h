@@ -458,7 +458,9 @@ int ensure_bq_alloc(mi355rec* h) {
                                    hipFuncAttributeMaxDynamicSharedMemorySize,
                                    static_cast<int>(sizeof(float) * grid * 2 * 5 + sizeof(int) * (kBqSelectBlock / 64) * 256)));
     // the tighter bound is only claimed where fp16 subnormals are demonstrably kept
-    hipLaunchKernelGGL(bq_selfcheck_kernel, dim3(1), dim3(64), 0, h->stream, b.qnorm);
+    // (half_selfcheck_kernel, replica.hip.h: its out[0] and out[1] are the matrix-core and conversion checks this verdict
+    // reads; b.qnorm holds kBqMaxQueries floats, room for its four)
+    hipLaunchKernelGGL(half_selfcheck_kernel, dim3(1), dim3(64), 0, h->stream, b.qnorm);
     float chk[2] = {0.0f, 0.0f};
     HIP_TRY(h, hipMemcpyAsync(chk, b.qnorm, sizeof chk, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));

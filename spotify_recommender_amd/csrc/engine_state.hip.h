@@ -89,6 +89,8 @@ struct ReplicaGeom {
 
 }  // namespace
 
+struct mi355rec_labels;   // the label-grouped copy of a shard's rows (engine_labels.hip.h, mi355rec_set_labels)
+
 struct mi355rec {
     int device = 0;
     int64_t n = 0;
@@ -103,11 +105,16 @@ struct mi355rec {
         void* d_half = nullptr;
         void* d_q8 = nullptr;
         float margin_mix = 0.0f, margin_mfma = 0.0f;   // of the replicas above (half_selfcheck_kernel's verdict)
+        mi355rec_labels* labels = nullptr;             // the labels of the group (set before its first lane was made)
     };
     SharedRows* shared = nullptr;
     bool is_lane = false;
     int lane_stream_attempts = 0;   // streams mi355rec_create_lane went through until one overlapped the parent's (0: not tested)
     int lane_overlaps = -1;         // 1: the lane's stream and its parent's run kernels side by side; 0: no such stream was found; -1: not tested
+    // LABELS (mi355rec_set_labels): the rows grouped by label; owned by the handle, or by the group once it has lanes
+    mi355rec_labels* labels = nullptr;
+    int64_t label_queries = 0;          // filtered queries since create ...
+    int64_t label_rows_scanned = 0;     // ... and the rows their launches scanned (whole tiles)
 
     int cus = 0;
     int grid = 0;

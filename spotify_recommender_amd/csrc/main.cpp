@@ -7,6 +7,7 @@
 //   recommender --preprocess <csv>
 //   recommender --song "<name>" [-n N]
 //   recommender --id "<track_id>" [-n N]
+//   ... either query mode with one or more --genre NAME: recommendations only from those genres (extension)
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -51,7 +52,51 @@ static void printSong(const Song& s, std::map<int, std::string>& genres, const c
 // flattens it again (main.cpp:50-60, Recommender.cu:109,162-167).  Here the file is
 // walked once (DataManager::loadCatalogue): the feature matrix goes to the engine as
 // it is, and only the handful of songs that are PRINTED are read back in full.
-static bool recommendationMode(const std::string& query, bool isTrackId, int topN) {  // main.cpp:46-131
+static std::string lowered(std::string s) {
+    std::transform(s.begin(), s.end(), s.begin(), ::tolower);
+    return s;
+}
+
+// --genre: the songs whose genre is one of `genres` (names matched case-insensitively), ranked as recommendByIndex
+// ranks the whole catalogue; the query song is found by the engine's rules (exact id / exact name, then substring).
+static bool genreRecommendations(Recommender& recommender, const DataManager::Catalogue& catalogue, const std::string& query,
+                                 bool isTrackId, int topN, const std::vector<std::string>& genres, std::vector<int>& recs) {
+    std::vector<int> ids;
+    for (const std::string& name : genres) {
+        int id = -1;
+        for (const auto& g : catalogue.genreMap)
+            if (lowered(g.second) == lowered(name)) { id = g.first; break; }
+        if (id < 0) {
+            std::cerr << "Error: Unknown genre '" << name << "'" << std::endl;
+            return false;
+        }
+        ids.push_back(id);
+    }
+    int index = -1;
+    if (isTrackId) {
+        for (size_t i = 0; i < catalogue.size() && index < 0; ++i)
+            if (catalogue.trackIds[i] == query) index = static_cast<int>(i);
+    } else {
+        const std::string needle = lowered(query);
+        for (size_t i = 0; i < catalogue.size() && index < 0; ++i)
+            if (lowered(catalogue.trackNames[i]) == needle) index = static_cast<int>(i);
+        for (size_t i = 0; i < catalogue.size() && index < 0; ++i)
+            if (lowered(catalogue.trackNames[i]).find(needle) != std::string::npos) index = static_cast<int>(i);
+    }
+    if (index < 0) {
+        std::cerr << "Error: Song with " << (isTrackId ? "track_id" : "name") << " '" << query << "' not found" << std::endl;
+        return true;   // (no recommendations: the caller says so)
+    }
+    std::cout << "Restricted to genres:";
+    for (const std::string& name : genres) std::cout << " " << name;
+    std::cout << std::endl;
+    if (!recommender.setGenreIds(catalogue.genreIds)) return true;
+    recs = recommender.recommendByIndexInGenres(index, topN, ids);
+    return true;
+}
+
+static bool recommendationMode(const std::string& query, bool isTrackId, int topN,
+                               const std::vector<std::string>& genres) {  // main.cpp:46-131
     std::cout << "=== RECOMMENDATION MODE ===" << std::endl;
     DataManager::Catalogue catalogue;
     if (!DataManager::loadCatalogue(kBinaryDataFile, catalogue)) {
@@ -69,12 +114,14 @@ static bool recommendationMode(const std::string& query, bool isTrackId, int top
     int queryIndex = -1;
     if (isTrackId) {
         std::cout << "\nSearching for track ID: " << query << std::endl;
-        recs = recommender.recommend(query, topN);
+        if (genres.empty()) recs = recommender.recommend(query, topN);
+        else if (!genreRecommendations(recommender, catalogue, query, true, topN, genres, recs)) return false;
         for (size_t i = 0; i < catalogue.size(); ++i)
             if (catalogue.trackIds[i] == query) { queryIndex = static_cast<int>(i); break; }
     } else {
         std::cout << "\nSearching for song: " << query << std::endl;
-        recs = recommender.recommendByName(query, topN);
+        if (genres.empty()) recs = recommender.recommendByName(query, topN);
+        else if (!genreRecommendations(recommender, catalogue, query, false, topN, genres, recs)) return false;
         // The reference finds the song it DISPLAYS with a single exact-or-substring
         // pass (main.cpp:85-95), not the engine's exact-then-substring rule; kept.
         std::string needle = query;
@@ -145,7 +192,16 @@ int main(int argc, char* argv[]) {
                 break;
             }
         }
-        return recommendationMode(argv[2], mode == "--id", topN) ? 0 : 1;
+        std::vector<std::string> genres;   // --genre NAME, any number of times
+        for (int i = 3; i < argc; ++i) {
+            if (std::strcmp(argv[i], "--genre") != 0) continue;
+            if (i + 1 >= argc) {
+                std::cerr << "Error: --genre needs a genre name" << std::endl;
+                return 1;
+            }
+            genres.push_back(argv[++i]);
+        }
+        return recommendationMode(argv[2], mode == "--id", topN, genres) ? 0 : 1;
     }
     std::cerr << "Error: Unknown mode '" << mode << "'" << std::endl;
     usage(argv[0]);

@@ -3,6 +3,7 @@
 // of this one translation unit).  Replaces the reference's Recommender internals (Recommender.cu:100-318) behind
 // include/Recommender.h.  No CPU fallback anywhere in this file.
 #include "engine_batch.hip.h"
+#include "engine_labels.hip.h"
 
 extern "C" {
 
@@ -89,6 +90,7 @@ void mi355rec_destroy(mi355rec_t* h) {
     if (h->d_mstream_ctl) (void)hipFree(h->d_mstream_ctl);
     for (hipEvent_t e : h->ev_pass) (void)hipEventDestroy(e);
     if (h->owned_feats && !h->shared) (void)hipFree(h->owned_feats);
+    if (!h->shared) free_labels(h->labels);
     if (h->d_block_lists) (void)hipFree(h->d_block_lists);
     if (h->d_lone_ctr) (void)hipFree(h->d_lone_ctr);
     {
@@ -115,6 +117,7 @@ void mi355rec_destroy(mi355rec_t* h) {
         void* bufs[] = {h->shared->owned_feats, h->shared->d_half, h->shared->d_q8};
         for (void* b : bufs)
             if (b) (void)hipFree(b);
+        free_labels(h->shared->labels);
         delete h->shared;
     }
     delete h;
@@ -215,6 +218,7 @@ int mi355rec_create_lane(mi355rec_t* parent, mi355rec_t** out) {
         group->d_q8 = parent->d_q8;
         group->margin_mix = parent->margin_mix;
         group->margin_mfma = parent->margin_mfma;
+        group->labels = parent->labels;   // (a lane made after mi355rec_set_labels shares them: nothing is copied)
     }
     parent->shared->refs.fetch_add(1);
     lane->shared = parent->shared;

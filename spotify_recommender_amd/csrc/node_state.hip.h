@@ -23,6 +23,12 @@
 #include "cpu_backend.h"
 #include "mi355rec_diag.h"
 
+namespace mi355node {
+// mi355rec_set_labels for a handle whose group of lanes the caller has to itself (engine_labels.hip.h): the replicas of a
+// replicated placement that share a device are lanes of the first one there.
+int set_group_labels(mi355rec_t* h, const int32_t* labels_host, int64_t n);
+}  // namespace mi355node
+
 namespace {
 
 thread_local std::string g_sharded_error;

@@ -120,7 +120,7 @@ __device__ __forceinline__ float half_dot(const uint32_t (&qh)[6], uint32_t a0, 
 // The bound is 1.0e-3 (kBqMargin) when they are kept and 1.5e-3 (kBqMarginFlush) when a unit flushes them
 // (batched.hip.h, "Margin").  Three places matter: v_cvt_pk_f16_f32 when the replica is built (out[1]: fp16(3e-6)
 // converted back), v_fma_mix_f32's fp16 operands in the single-query scan (out[2], out[3]: a subnormal on the row
-// side, on the query side, times 1.0) and the matrix core in the multi-query pass (out[0], as bq_selfcheck_kernel).
+// side, on the query side, times 1.0) and the matrix core in the multi-query pass (out[0]; out[0] and out[1] are also the batched path's check, ensure_bq_alloc).
 // One wave; the host compares with the exact values.
 __global__ void half_selfcheck_kernel(float* out) {
     const int lane = threadIdx.x;

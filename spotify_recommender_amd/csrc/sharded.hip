@@ -506,6 +506,128 @@ int mi355rec_sharded_query_row_topn(mi355rec_sharded_t* h, int64_t global_row, i
     return MI355REC_OK;
 }
 
+// ---- LABELS (include/mi355rec_diag.h) ---------------------------------------------------------------------------------
+int mi355rec_sharded_set_labels(mi355rec_sharded_t* h, const int32_t* labels_host, int64_t n) {
+    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    if (labels_host && n != h->n)
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "%lld labels for a catalogue of %lld rows", (long long)n, (long long)h->n);
+    if (h->cpu) {
+        const char* why = nullptr;
+        return cpu_result(h, mi355cpu::node_set_labels(h->cpu, labels_host, n, &why), why);
+    }
+    DeviceRestore restore;
+    int rc = drain_workers(h);   // the caller's thread drives every shard itself
+    if (rc) return rc;
+    for (size_t r = 0; r < h->shards.size(); ++r) {
+        Shard& s = h->shards[r];
+        bool lane = false;   // a replica on a device that already holds one is a lane of it: it shares that one's labels
+        for (size_t p = 0; p < r && h->replicated && !lane; ++p) lane = h->shards[p].device == s.device;
+        if (lane) continue;
+        S_HIP(h, hipSetDevice(s.device));
+        rc = mi355node::set_group_labels(s.engine, labels_host ? labels_host + s.lo : nullptr, s.hi - s.lo);
+        if (rc != MI355REC_OK) {   // all or nothing: no shard keeps labels the others do not have
+            const std::string why = mi355rec_last_error(s.engine);
+            for (Shard& o : h->shards)
+                if (hipSetDevice(o.device) == hipSuccess) (void)mi355node::set_group_labels(o.engine, nullptr, 0);
+            return sfail(h, rc, "shard on device %d: %s (the labels were dropped on every shard)", s.device, why.c_str());
+        }
+    }
+    return MI355REC_OK;
+}
+
+namespace {
+// A filtered query on a ROW-SHARDED catalogue: the query by value on every shard (the query row excluded by its global index),
+// the per-shard lists merged on the host by key — exact, since every shard's list holds its best min(topn, rows) keys.
+int sharded_labels_by_value(mi355rec_sharded_t* h, const float* q, int64_t exclude_global, const int32_t* labels, int n_labels,
+                            int topn, int64_t* out_idx, float* out_score, int* out_count) {
+    std::vector<mi355rec_key_t> keys;
+    std::vector<int64_t> idx;
+    std::vector<float> sc;
+    try {
+        idx.resize(static_cast<size_t>(topn));
+        sc.resize(static_cast<size_t>(topn));
+        keys.reserve(static_cast<size_t>(topn) * h->shards.size());
+    } catch (const std::bad_alloc&) {
+        return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for %d results per shard", topn);
+    }
+    for (Shard& s : h->shards) {
+        if (s.hi <= s.lo) continue;
+        S_HIP(h, hipSetDevice(s.device));
+        int c = 0;
+        const int rc = mi355rec_query_topn_labels(s.engine, q, exclude_global, labels, n_labels, topn, idx.data(), sc.data(), &c);
+        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", s.device, mi355rec_last_error(s.engine));
+        for (int i = 0; i < c; ++i) keys.push_back(mi355rec_pack_key(sc[static_cast<size_t>(i)], idx[static_cast<size_t>(i)]));
+    }
+    const size_t count = keys.size() < static_cast<size_t>(topn) ? keys.size() : static_cast<size_t>(topn);
+    std::partial_sort(keys.begin(), keys.begin() + count, keys.end(), std::greater<mi355rec_key_t>());
+    for (size_t i = 0; i < static_cast<size_t>(topn); ++i) {
+        out_idx[i] = i < count ? mi355rec_key_row(keys[i]) : -1;
+        if (out_score) out_score[i] = i < count ? mi355rec_key_score(keys[i]) : 0.0f;
+    }
+    if (out_count) *out_count = static_cast<int>(count);
+    return MI355REC_OK;
+}
+}  // namespace
+
+int mi355rec_sharded_query_topn_labels(mi355rec_sharded_t* h, const float* query12, int64_t exclude_global, const int32_t* labels,
+                                       int n_labels, int topn, int64_t* out_idx, float* out_score, int* out_count) {
+    if (!h || !query12 || !out_idx) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    if (topn <= 0) return sfail(h, MI355REC_ERR_INVALID_ARG, "topn must be positive, got %d", topn);
+    if (h->cpu) {
+        const char* why = nullptr;
+        return cpu_result(h, mi355cpu::node_query_labels(h->cpu, query12, exclude_global, labels, n_labels, topn, out_idx, out_score,
+                                                         out_count, &why), why);
+    }
+    DeviceRestore restore;
+    if (h->shards.size() == 1 || h->replicated) {   // one handle holds the whole catalogue
+        Shard* s = &h->shards[0];
+        if (h->replicated) {
+            const int rc = take_replica(h, &s);
+            if (rc) return rc;
+        } else {
+            S_HIP(h, hipSetDevice(s->device));
+        }
+        const int rc = mi355rec_query_topn_labels(s->engine, query12, exclude_global, labels, n_labels, topn, out_idx, out_score, out_count);
+        return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s->engine));
+    }
+    const int rc = drain_workers(h);
+    if (rc) return rc;
+    return sharded_labels_by_value(h, query12, exclude_global, labels, n_labels, topn, out_idx, out_score, out_count);
+}
+
+int mi355rec_sharded_query_row_topn_labels(mi355rec_sharded_t* h, int64_t global_row, const int32_t* labels, int n_labels, int topn,
+                                           int64_t* out_idx, float* out_score, int* out_count) {
+    if (!h || !out_idx) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    if (global_row < 0 || global_row >= h->n)
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "Invalid song index: %lld", (long long)global_row);
+    if (topn <= 0) return sfail(h, MI355REC_ERR_INVALID_ARG, "topn must be positive, got %d", topn);
+    if (h->cpu) {
+        const char* why = nullptr;
+        return cpu_result(h, mi355cpu::node_query_labels(h->cpu, mi355cpu::row(mi355cpu::node_catalogue(h->cpu), global_row), global_row,
+                                                         labels, n_labels, topn, out_idx, out_score, out_count, &why), why);
+    }
+    DeviceRestore restore;
+    if (h->shards.size() == 1 || h->replicated) {   // one handle holds the whole catalogue (row_base 0)
+        Shard* s = &h->shards[0];
+        if (h->replicated) {
+            const int rc = take_replica(h, &s);
+            if (rc) return rc;
+        } else {
+            S_HIP(h, hipSetDevice(s->device));
+        }
+        const int rc = mi355rec_query_row_topn_labels(s->engine, global_row, labels, n_labels, topn, out_idx, out_score, out_count);
+        return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s->engine));
+    }
+    int rc = drain_workers(h);
+    if (rc) return rc;
+    const Shard* own = owner_of(h, global_row);
+    float q[MI355REC_DIM];
+    S_HIP(h, hipSetDevice(own->device));
+    rc = mi355rec_fetch_row(own->engine, global_row - own->lo, q);
+    if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
+    return sharded_labels_by_value(h, q, global_row, labels, n_labels, topn, out_idx, out_score, out_count);
+}
+
 int mi355rec_sharded_scores_row(mi355rec_sharded_t* h, int64_t global_row, float* out_host) {
     if (!h || !out_host) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     if (global_row < 0 || global_row >= h->n)

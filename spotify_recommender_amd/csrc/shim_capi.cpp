@@ -168,6 +168,14 @@ int64_t shim_recommend_by_name(void* h, const char* name, int topn, int* out, fl
     Catalogue* c = static_cast<Catalogue*>(h);
     return giveBack(c, c->rec.recommendByName(name, topn), out, scores, cap);
 }
+// Recommender::recommendByIndexInGenres; genre_ids (one per song, may be null) goes to setGenreIds first.
+int64_t shim_recommend_by_index_in_genres(void* h, int idx, int topn, const int* genres, int n_genres, const int* genre_ids,
+                                          int* out, float* scores, int64_t cap) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    if (genre_ids && !c->rec.setGenreIds(std::vector<int>(genre_ids, genre_ids + c->rec.getSongCount()))) return -1;
+    return giveBack(c, c->rec.recommendByIndexInGenres(idx, topn, std::vector<int>(genres, genres + (n_genres > 0 ? n_genres : 0))),
+                    out, scores, cap);
+}
 int shim_similarities(void* h, int idx, float* out_n) {
     Catalogue* c = static_cast<Catalogue*>(h);
     std::vector<float> v;

@@ -20,6 +20,23 @@ def _np_f32(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.float32))
 
 
+def _np_labels(labels) -> np.ndarray:
+    """A label array or set (int32, contiguous): one label per row for set_labels, the wanted labels for a query."""
+    return np.ascontiguousarray(np.asarray(list(labels) if isinstance(labels, (set, frozenset)) else labels, dtype=np.int32).reshape(-1))
+
+
+def _labels_query(fn, h, check, head, labels, topn: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Runs one filtered query entry point: fn(h, *head, labels, n_labels, topn, idx, score, &count)."""
+    lab = _np_labels(labels)
+    n_out = max(int(topn), 1)
+    idx = np.empty(n_out, dtype=np.int64)
+    score = np.empty(n_out, dtype=np.float32)
+    count = ctypes.c_int(0)
+    check(fn(h, *head, lab.ctypes.data_as(ctypes.c_void_p), int(lab.size), int(topn), idx.ctypes.data_as(ctypes.c_void_p),
+             score.ctypes.data_as(ctypes.c_void_p), ctypes.byref(count)))
+    return idx[:count.value].copy(), score[:count.value].copy()
+
+
 class CosineEngine:
     """One row shard of the N x 12 fp32 catalogue resident on one MI355X.
 
@@ -335,6 +352,30 @@ class CosineEngine:
         capi.check(self._lib.mi355rec_stats(self._h, ctypes.byref(st)), self._h)
         return st
 
+    # ---- LABELS (include/mi355rec_diag.h): label-filtered top-N ----
+    def set_labels(self, labels) -> None:
+        """One label per row in [0, capi.MAX_LABELS), -1 = unlabelled; None drops the labels."""
+        if labels is None:
+            capi.check(self._lib.mi355rec_set_labels(self._h, None, 0), self._h)
+            return
+        lab = _np_labels(labels)
+        capi.check(self._lib.mi355rec_set_labels(self._h, lab.ctypes.data_as(ctypes.c_void_p), int(lab.size)), self._h)
+
+    def query_row_topn_labels(self, local_row: int, labels, topn: int) -> Tuple[np.ndarray, np.ndarray]:
+        """The best `topn` rows whose label is in `labels`, the query row excluded."""
+        return _labels_query(self._lib.mi355rec_query_row_topn_labels, self._h, lambda rc: capi.check(rc, self._h),
+                             (int(local_row),), labels, topn)
+
+    def query_topn_labels(self, query, exclude_global: int, labels, topn: int) -> Tuple[np.ndarray, np.ndarray]:
+        q = _np_f32(query).reshape(capi.DIM)
+        return _labels_query(self._lib.mi355rec_query_topn_labels, self._h, lambda rc: capi.check(rc, self._h),
+                             (q.ctypes.data_as(ctypes.c_void_p), int(exclude_global)), labels, topn)
+
+    def label_counters(self) -> dict:
+        q, r = ctypes.c_int64(0), ctypes.c_int64(0)
+        capi.check(self._lib.mi355rec_label_counters(self._h, ctypes.byref(q), ctypes.byref(r)), self._h)
+        return {"queries": q.value, "rows_scanned": r.value}
+
 
 class NodeEngine:
     """The catalogue on the GPUs of one node driven by ONE process (mi355rec_create_placed): what the C++
@@ -432,6 +473,23 @@ class NodeEngine:
             idx.ctypes.data_as(ctypes.c_void_p), score.ctypes.data_as(ctypes.c_void_p),
             counts.ctypes.data_as(ctypes.c_void_p)))
         return idx, score, counts
+
+    # ---- LABELS (include/mi355rec_diag.h): label-filtered top-N over the whole node ----
+    def set_labels(self, labels) -> None:
+        """One label per row in [0, capi.MAX_LABELS), -1 = unlabelled; None drops the labels."""
+        if labels is None:
+            self._check(self._lib.mi355rec_sharded_set_labels(self._h, None, 0))
+            return
+        lab = _np_labels(labels)
+        self._check(self._lib.mi355rec_sharded_set_labels(self._h, lab.ctypes.data_as(ctypes.c_void_p), int(lab.size)))
+
+    def query_row_topn_labels(self, global_row: int, labels, topn: int) -> Tuple[np.ndarray, np.ndarray]:
+        return _labels_query(self._lib.mi355rec_sharded_query_row_topn_labels, self._h, self._check, (int(global_row),), labels, topn)
+
+    def query_topn_labels(self, query, exclude_global: int, labels, topn: int) -> Tuple[np.ndarray, np.ndarray]:
+        q = _np_f32(query).reshape(capi.DIM)
+        return _labels_query(self._lib.mi355rec_sharded_query_topn_labels, self._h, self._check,
+                             (q.ctypes.data_as(ctypes.c_void_p), int(exclude_global)), labels, topn)
 
     def scores_row(self, global_row: int) -> np.ndarray:
         out = np.empty(self.rows, dtype=np.float32)
