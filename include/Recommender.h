@@ -81,6 +81,12 @@ public:
     bool setGenreIds(const std::vector<int>& genreIds);
     std::vector<int> recommendByIndexInGenres(int songIndex, int topN, const std::vector<int>& genreIds);
 
+    // Extension: playlist recommendations.  recommendForPlaylist returns the ids of the topN songs whose mean similarity
+    // to the songs of songIndices (1 to 32 of them, duplicates counting twice) is the highest, the playlist's songs and
+    // alsoExclude (up to 1024 ids) left out; same messages and {} on bad input as recommendByIndex, lastScores() filled.
+    // topN is capped at the songs that can be returned; above 1024 it is refused.
+    std::vector<int> recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<int>& alsoExclude = {});
+
     struct Impl;   // opaque: defined in Recommender.cpp
 
 private:

@@ -14,6 +14,8 @@
  *   - LABELS, an extension beyond the reference (which lists "recommendations within genre" among its extensions only):
  *     rows carry an integer label (a genre id) and a query returns the top-N rows whose label is in a given set
  *     (mi355rec_set_labels, _query_row_topn_labels, _query_topn_labels, _label_counters and their node-handle twins);
+ *   - PLAYLISTS, a further extension: the top-N rows by the mean of their scores against up to 32 songs, with an exclusion
+ *     list (mi355rec_query_mean_topn, _query_playlist_topn, _playlist_counters and their node-handle twins);
  *   - test hooks, compiled in only with -DMI355REC_TEST_HOOKS (spotify_recommender_amd/build.py builds
  *     libmi355rec_testhooks.so for tests/; the product library does not export them).
  */
@@ -376,6 +378,39 @@ int mi355rec_sharded_query_row_topn_labels(mi355rec_sharded_t* h, int64_t global
 int mi355rec_sharded_query_topn_labels(mi355rec_sharded_t* h, const float* query12, int64_t exclude_global,
                                        const int32_t* labels, int n_labels, int topn, int64_t* out_idx, float* out_score,
                                        int* out_count);
+
+/* PLAYLISTS (an extension beyond the reference): "what goes with this playlist".
+ * Members are K query vectors q_0 .. q_{K-1}, 1 <= K <= MI355REC_MAX_PLAYLIST, given by value (queries: K x 12 floats on the
+ * host) or as rows of the catalogue; duplicates count with their multiplicity.  Every row x scores
+ *     score(x) = fl( fl(...fl(c_0 + c_1) + ... + c_{K-1}) / (float)K ),   c_k = the score mi355rec_query_topn gives x for q_k,
+ * summed in fp32 in member order with one IEEE divide: for K = 1 exactly the single query's score.  The excluded set is
+ * the union of the member rows (by-row calls) and exclude_global[0..n_exclude) (global row ids, any order, duplicates
+ * allowed, n_exclude <= MI355REC_MAX_EXCLUDE).  Results are in the canonical order of every other route (score
+ * descending, then row ascending, -0.0 reported as +0.0); count = min(topn, rows - |distinct excluded rows|), the rest
+ * padded with -1 / 0.  Version 1 answers in ONE round: topn <= 1024.
+ * INVALID_ARG (with a message) for K outside [1, 32], topn <= 0 or > 1024, a member row outside the catalogue (local
+ * rows of the handle; global rows of a node handle), an excluded id < 0 (on a node handle: outside the catalogue),
+ * n_exclude outside [0, 1024] and a NULL list with n_exclude > 0.  On a single handle an excluded id of another shard's
+ * rows matches nothing.
+ * Synchronous, like the label calls: one launch (csrc/playlist.hip.h: a pre-filter over the 8-bit replica with a derived
+ * error bound, K exact chains per surviving row) and the merge.  No set-up: lanes and node handles answer at once.
+ * mi355rec_playlist_counters: playlist queries since create, and the rows whose K exact chains were computed (the
+ * pre-filter's survivors, the rows of each workgroup's starting bound, every row where the pre-filter is off).  Either
+ * pointer may be NULL.
+ * Node handle: one shard forwards; a replicated placement asks one replica; a row-sharded one fetches the member rows
+ * (mi355rec_fetch_row), asks every shard by value with the whole exclusion list (the members' global rows added) and
+ * merges the per-shard lists on the host (exact).  The CPU backend (hosts without a device) serves the same calls. */
+#define MI355REC_MAX_PLAYLIST 32
+#define MI355REC_MAX_EXCLUDE 1024
+int mi355rec_query_mean_topn(mi355rec_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude, int topn,
+                             int64_t* out_idx, float* out_score, int* out_count);
+int mi355rec_query_playlist_topn(mi355rec_t* h, const int64_t* local_rows, int k, const int64_t* exclude_global, int n_exclude,
+                                 int topn, int64_t* out_idx, float* out_score, int* out_count);
+int mi355rec_playlist_counters(const mi355rec_t* h, int64_t* queries, int64_t* rows_exact);
+int mi355rec_sharded_query_mean_topn(mi355rec_sharded_t* h, const float* queries, int k, const int64_t* exclude_global,
+                                     int n_exclude, int topn, int64_t* out_idx, float* out_score, int* out_count);
+int mi355rec_sharded_query_playlist_topn(mi355rec_sharded_t* h, const int64_t* global_rows, int k, const int64_t* exclude_global,
+                                         int n_exclude, int topn, int64_t* out_idx, float* out_score, int* out_count);
 
 #ifdef MI355REC_TEST_HOOKS
 /* TEST HOOK for the cross-workgroup hand-offs of the streamed scans (csrc/replica.hip.h, "hand-offs that fail

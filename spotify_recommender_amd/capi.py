@@ -33,6 +33,8 @@ ERR_NO_DEVICE = -2
 ERR_HIP = -3
 ERR_OUT_OF_MEMORY = -4
 MAX_LABELS = 1024
+MAX_PLAYLIST = 32
+MAX_EXCLUDE = 1024
 
 
 class Stats(ctypes.Structure):
@@ -157,6 +159,13 @@ SIGNATURES = {
                                                        POINTER(c_int)]),
     "mi355rec_sharded_query_topn_labels": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                                    POINTER(c_int)]),
+    "mi355rec_query_mean_topn": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, POINTER(c_int)]),
+    "mi355rec_query_playlist_topn": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, POINTER(c_int)]),
+    "mi355rec_playlist_counters": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),
+    "mi355rec_sharded_query_mean_topn": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                                 POINTER(c_int)]),
+    "mi355rec_sharded_query_playlist_topn": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                                     POINTER(c_int)]),
     "mi355rec_pack_key": (c_uint64, [c_float, c_int64]),
     "mi355rec_key_score": (c_float, [c_uint64]),
     "mi355rec_key_row": (c_int64, [c_uint64]),

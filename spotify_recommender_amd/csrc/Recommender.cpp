@@ -238,6 +238,46 @@ std::vector<int> Recommender::recommendByIndexInGenres(int songIndex, int topN, 
     return results;
 }
 
+std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<int>& alsoExclude) {
+    if (!impl_->initialized) {
+        std::cerr << "Error: Recommender not initialized" << std::endl;
+        return {};
+    }
+    if (songIndices.empty() || songIndices.size() > MI355REC_MAX_PLAYLIST) {
+        std::cerr << "Error: a playlist holds 1 to " << MI355REC_MAX_PLAYLIST << " songs" << std::endl;
+        return {};
+    }
+    if (alsoExclude.size() > MI355REC_MAX_EXCLUDE) {
+        std::cerr << "Error: at most " << MI355REC_MAX_EXCLUDE << " songs can be excluded" << std::endl;
+        return {};
+    }
+    std::vector<int64_t> rows(songIndices.begin(), songIndices.end()), excl(alsoExclude.begin(), alsoExclude.end());
+    for (const std::vector<int64_t>* v : {&rows, &excl})
+        for (int64_t i : *v)
+            if (i < 0 || i >= impl_->numSongs) {
+                std::cerr << "Error: Invalid song index: " << i << std::endl;
+                return {};
+            }
+    if (topN <= 0) {
+        std::cerr << "Error: topN must be positive" << std::endl;
+        return {};
+    }
+    if (topN > impl_->numSongs) topN = impl_->numSongs;   // (the engine pads past what it can return; no buffer beyond the songs)
+    impl_->idxBuf.assign(static_cast<size_t>(topN), -1);
+    impl_->scoreBuf.assign(static_cast<size_t>(topN), 0.0f);
+    int count = 0;
+    const int rc = mi355rec_sharded_query_playlist_topn(impl_->engine, rows.data(), static_cast<int>(rows.size()), excl.data(),
+                                                        static_cast<int>(excl.size()), topN, impl_->idxBuf.data(), impl_->scoreBuf.data(), &count);
+    if (rc != MI355REC_OK) {
+        std::cerr << "Error: " << mi355rec_sharded_last_error(impl_->engine) << std::endl;
+        return {};
+    }
+    std::vector<int> results(static_cast<size_t>(count));
+    for (int i = 0; i < count; ++i) results[i] = static_cast<int>(impl_->idxBuf[i]);
+    impl_->lastScores.assign(impl_->scoreBuf.begin(), impl_->scoreBuf.begin() + count);
+    return results;
+}
+
 std::vector<int> Recommender::recommend(const std::string& trackId, int topN) {  // :356-363
     const auto it = impl_->byId.find(trackId);
     if (it == impl_->byId.end()) {

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <vector>
 
@@ -362,6 +363,45 @@ int node_query_labels(Node* h, const float* q12, int64_t exclude, const int32_t*
         if (out_score) out_score[i] = 0.0f;
     }
     if (out_count) *out_count = c;
+    return MI355REC_OK;
+}
+
+int node_query_mean(Node* h, const float* members, int k, const int64_t* exclude, int n_exclude, int topn_asked, int64_t* out_idx,
+                    float* out_score, int* out_count, const char** why) {
+    const Catalogue* c = h->cat;
+    const int64_t n = c->n;
+    std::vector<float> qn(static_cast<size_t>(k));
+    for (int m = 0; m < k; ++m) qn[static_cast<size_t>(m)] = query_norm(members + m * kDim);
+    std::vector<uint64_t> keys;
+    std::vector<int64_t> excl;
+    try {
+        excl.assign(exclude, exclude + n_exclude);
+        keys.resize(static_cast<size_t>(n));
+    } catch (const std::bad_alloc&) {
+        *why = "out of host memory";
+        return MI355REC_ERR_OUT_OF_MEMORY;
+    }
+    std::sort(excl.begin(), excl.end());
+    excl.erase(std::unique(excl.begin(), excl.end()), excl.end());
+    const float* f = c->feats.data();
+    const float kf = static_cast<float>(k);
+    // score(x) = fl(fl(...fl(c_0 + c_1) + ... + c_{k-1}) / k): fp32, member order, one divide
+#pragma omp parallel for schedule(static) num_threads(c->threads)
+    for (int64_t i = 0; i < n; ++i) {
+        float sum = score(members, qn[0], f + i * kDim);
+        for (int m = 1; m < k; ++m) sum = sum + score(members + m * kDim, qn[static_cast<size_t>(m)], f + i * kDim);
+        keys[static_cast<size_t>(i)] = pack(sum / kf, static_cast<uint32_t>(i));
+    }
+    for (int64_t e : excl)
+        if (e >= 0 && e < n) keys[static_cast<size_t>(e)] = 0;   // (a real key is never 0: its low half is ~row)
+    const int64_t avail = n - static_cast<int64_t>(std::count_if(excl.begin(), excl.end(), [n](int64_t e) { return e >= 0 && e < n; }));
+    const int count = static_cast<int>(topn_asked < avail ? topn_asked : avail);
+    std::partial_sort(keys.begin(), keys.begin() + count, keys.end(), std::greater<uint64_t>());
+    for (int i = 0; i < topn_asked; ++i) {
+        out_idx[i] = i < count ? static_cast<int64_t>(~static_cast<uint32_t>(keys[static_cast<size_t>(i)])) : -1;
+        if (out_score) out_score[i] = i < count ? unordered(static_cast<uint32_t>(keys[static_cast<size_t>(i)] >> 32)) + 0.0f : 0.0f;
+    }
+    if (out_count) *out_count = count;
     return MI355REC_OK;
 }
 

@@ -1,0 +1,193 @@
+// engine_playlist.hip.h — PLAYLISTS on the single-device handle (include/mi355rec_diag.h, "PLAYLISTS"): the top-N rows by
+// the mean of their scores against up to 32 member queries, an exclusion list left out.  One playlist_scan_kernel launch
+// (playlist.hip.h), then the merge of merge.hip.h into the handle's pinned result slots and completion word, as
+// sync_label_query does.  No state beyond a small per-handle buffer for the call's inputs, allocated by the first call.
+// (Part of mi355rec.hip's translation unit, included after engine_labels.hip.h.)
+#pragma once
+
+#include <algorithm>
+
+#include "engine_labels.hip.h"
+#include "playlist.hip.h"
+
+// What the first playlist call of a handle allocates.
+struct mi355rec_playlist {
+    PlaylistBuf* d_buf = nullptr;           // the call's members / member rows and excluded ids on the device ...
+    PlaylistBuf* h_buf = nullptr;           // ... staged here (pinned)
+    unsigned long long* d_exact = nullptr;  // rows whose K chains were computed, since the first call (mi355rec_playlist_counters)
+    int grid_cap = 1;                       // workgroups of a launch at most (occupancy x CUs, and the handle's list slots)
+};
+
+namespace {
+
+constexpr int kPlMinTilesPerWg = 8;   // with the pre-filter: a workgroup scans >= 8 tiles (its anchor bound paid for, its own threshold tight)
+
+void free_playlist(mi355rec_playlist* P) {
+    if (!P) return;
+    if (P->d_buf) (void)hipFree(P->d_buf);
+    if (P->d_exact) (void)hipFree(P->d_exact);
+    if (P->h_buf) (void)hipHostFree(P->h_buf);
+    delete P;
+}
+
+int ensure_playlist(mi355rec* h) {
+    if (h->playlist) return MI355REC_OK;
+    mi355rec_playlist* P = new (std::nothrow) mi355rec_playlist();
+    if (!P) return fail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for the playlist buffers");
+    auto failed = [&](hipError_t e, const char* what) {
+        free_playlist(P);
+        return fail(h, e == hipErrorOutOfMemory ? MI355REC_ERR_OUT_OF_MEMORY : MI355REC_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+    };
+    hipError_t e;
+    if ((e = hipMalloc(&P->d_buf, sizeof(PlaylistBuf))) != hipSuccess) return failed(e, "hipMalloc(playlist buffer)");
+    if ((e = hipHostMalloc(&P->h_buf, sizeof(PlaylistBuf), hipHostMallocDefault)) != hipSuccess) return failed(e, "hipHostMalloc(playlist buffer)");
+    if ((e = hipMalloc(&P->d_exact, sizeof(unsigned long long))) != hipSuccess) return failed(e, "hipMalloc(playlist counter)");
+    if ((e = hipMemset(P->d_exact, 0, sizeof(unsigned long long))) != hipSuccess) return failed(e, "hipMemset(playlist counter)");
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, playlist_scan_kernel, PlaylistCfg::kBlock, 0) != hipSuccess || occ < 1) occ = 1;
+    (void)hipGetLastError();
+    int lists = h->grid > h->hg.grid ? h->grid : h->hg.grid;   // d_block_lists holds this many lists of kMaxTopK keys (create)
+    if (h->qg.grid > lists) lists = h->qg.grid;
+    P->grid_cap = h->cus * occ;
+    if (P->grid_cap > lists) P->grid_cap = lists;
+    if (P->grid_cap > kMergeMaxLists) P->grid_cap = kMergeMaxLists;
+    if (P->grid_cap < 1) P->grid_cap = 1;
+    h->playlist = P;
+    return MI355REC_OK;
+}
+
+// One playlist query, synchronously.  members: k x 12 floats on the host, or null with `local_rows` (k rows of this shard,
+// excluded by their global ids).  exclude_global[0..n_exclude): global ids, any order, duplicates allowed; ids of other
+// shards match nothing here.
+int sync_playlist_query(mi355rec* h, const float* members, const int64_t* local_rows, int k, const int64_t* exclude_global,
+                        int n_exclude, int topn, int64_t* out_idx, float* out_score, int* out_count, int max_exclude = kMaxExclude) {
+    if (!out_idx) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    if (k < 1 || k > kMaxPlaylist) return fail(h, MI355REC_ERR_INVALID_ARG, "playlist of %d songs: 1 to %d are supported", k, kMaxPlaylist);
+    if (!members && !local_rows) return fail(h, MI355REC_ERR_INVALID_ARG, "null playlist");
+    if (topn <= 0 || topn > kMaxTopK)
+        return fail(h, MI355REC_ERR_INVALID_ARG, "topn %d out of [1, %d] (a playlist query has one round)", topn, kMaxTopK);
+    if (n_exclude < 0 || n_exclude > max_exclude)
+        return fail(h, MI355REC_ERR_INVALID_ARG, "n_exclude %d out of [0, %d]", n_exclude, max_exclude);
+    if (n_exclude > 0 && !exclude_global) return fail(h, MI355REC_ERR_INVALID_ARG, "null exclusion list with n_exclude %d", n_exclude);
+    for (int i = 0; i < n_exclude; ++i)
+        if (exclude_global[i] < 0 || exclude_global[i] > static_cast<int64_t>(UINT32_MAX))
+            return fail(h, MI355REC_ERR_INVALID_ARG, "excluded row %lld out of the catalogue", (long long)exclude_global[i]);
+    if (local_rows)
+        for (int m = 0; m < k; ++m)
+            if (local_rows[m] < 0 || local_rows[m] >= h->n)
+                return fail(h, MI355REC_ERR_INVALID_ARG, "Invalid song index: %lld", (long long)local_rows[m]);
+    DeviceGuard guard(h->device);
+    int rc = ensure_playlist(h);
+    if (rc) return rc;
+    mi355rec_playlist* P = h->playlist;
+    PlaylistBuf* b = P->h_buf;
+    // the excluded rows of this shard: sorted, distinct, as uint32 global ids
+    int n_excl = 0;
+    for (int i = 0; i < n_exclude; ++i)
+        if (exclude_global[i] >= h->row_base && exclude_global[i] < h->row_base + h->n) b->excl[n_excl++] = static_cast<uint32_t>(exclude_global[i]);
+    if (local_rows)
+        for (int m = 0; m < k; ++m) b->excl[n_excl++] = static_cast<uint32_t>(h->row_base + local_rows[m]);
+    std::sort(b->excl, b->excl + n_excl);
+    n_excl = static_cast<int>(std::unique(b->excl, b->excl + n_excl) - b->excl);
+    ++h->playlist_queries;
+    const int64_t avail = h->n - n_excl;
+    const int eff = static_cast<int64_t>(topn) < avail ? topn : static_cast<int>(avail);
+    if (eff <= 0) {   // nothing left to return: nothing to launch
+        for (int i = 0; i < topn; ++i) {
+            out_idx[i] = -1;
+            if (out_score) out_score[i] = 0.0f;
+        }
+        if (out_count) *out_count = 0;
+        return MI355REC_OK;
+    }
+    PlaylistArg arg;
+    arg.k = k;
+    arg.n_excl = n_excl;
+    arg.by_row = local_rows ? 1 : 0;
+    if (local_rows) std::memcpy(b->rows, local_rows, sizeof(int64_t) * static_cast<size_t>(k));
+    else std::memcpy(b->members, members, sizeof(float) * kDim * static_cast<size_t>(k));
+    rc = ensure_slots(h, static_cast<size_t>(eff));
+    if (rc) return rc;
+    rc = sync_api_begin(h);
+    if (rc) return rc;
+    b->shared_thr = 0ull;
+    // (the staging buffer is free: the previous call on this handle has completed)
+    const size_t bytes = offsetof(PlaylistBuf, excl) + sizeof(uint32_t) * static_cast<size_t>(n_excl);
+    HIP_TRY(h, hipMemcpyAsync(P->d_buf, b, bytes, hipMemcpyHostToDevice, h->stream));
+    const uint4* q8 = use_q8(h) ? h->d_q8 : nullptr;
+    const int64_t tiles = ((h->n + 3) / 4 + PlaylistCfg::kBlock - 1) / PlaylistCfg::kBlock;
+    int64_t want_grid = q8 ? (tiles + kPlMinTilesPerWg - 1) / kPlMinTilesPerWg : tiles;
+    if (want_grid > P->grid_cap) want_grid = P->grid_cap;
+    if (want_grid < 1) want_grid = 1;
+    const int grid = static_cast<int>(want_grid);
+    const bool direct = eff <= kDirectResultSlots;
+    const uint32_t want = direct ? (++h->done_seq ? h->done_seq : ++h->done_seq) : 0u;   // never 0
+    LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, playlist_scan_kernel, dim3(grid), dim3(PlaylistCfg::kBlock),
+                 h->stream, h->d_feats, q8, h->n, h->row_base, static_cast<const PlaylistBuf*>(P->d_buf), arg,
+                 static_cast<const float*>(h->d_anchor), eff, h->d_block_lists, P->d_exact,
+                 reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr)));
+    HIP_TRY(h, hipGetLastError());
+    rc = enqueue_merge(h, h->d_block_lists, grid, eff, eff, h->d_keys, direct ? h->hd_idx : h->d_idx, direct ? h->hd_score : h->d_score,
+                       h->stream, want);
+    if (rc) return rc;
+    if (direct) {
+        rc = wait_done(h, want);
+        if (rc) return rc;
+    } else {
+        HIP_TRY(h, hipMemcpyAsync(h->h_idx, h->d_idx, eff * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->h_score, h->d_score, eff * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    int c = 0;
+    while (c < eff && h->h_idx[c] >= 0) ++c;
+    std::memcpy(out_idx, h->h_idx, static_cast<size_t>(eff) * sizeof(int64_t));
+    if (out_score) std::memcpy(out_score, h->h_score, static_cast<size_t>(eff) * sizeof(float));
+    for (int i = eff; i < topn; ++i) {
+        out_idx[i] = -1;
+        if (out_score) out_score[i] = 0.0f;
+    }
+    if (out_count) *out_count = c;
+    return MI355REC_OK;
+}
+
+}  // namespace
+
+namespace mi355node {
+int query_mean_topn(mi355rec_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude, int topn,
+                    int64_t* out_idx, float* out_score, int* out_count) {
+    if (!h || !queries) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    return sync_playlist_query(h, queries, nullptr, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count, kPlExcludeCap);
+}
+}  // namespace mi355node
+
+extern "C" {
+
+int mi355rec_query_mean_topn(mi355rec_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude, int topn,
+                             int64_t* out_idx, float* out_score, int* out_count) {
+    if (!h || !queries) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    return sync_playlist_query(h, queries, nullptr, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count);
+}
+
+int mi355rec_query_playlist_topn(mi355rec_t* h, const int64_t* local_rows, int k, const int64_t* exclude_global, int n_exclude,
+                                 int topn, int64_t* out_idx, float* out_score, int* out_count) {
+    if (!h || !local_rows) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    return sync_playlist_query(h, nullptr, local_rows, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count);
+}
+
+int mi355rec_playlist_counters(const mi355rec_t* h, int64_t* queries, int64_t* rows_exact) {
+    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    if (queries) *queries = h->playlist_queries;
+    if (rows_exact) {
+        unsigned long long v = 0;
+        if (h->playlist) {
+            DeviceGuard guard(h->device);
+            // (the calls are synchronous: the counter is settled; a blocking copy orders after them anyway)
+            const hipError_t e = hipMemcpy(&v, h->playlist->d_exact, sizeof v, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) return fail(const_cast<mi355rec_t*>(h), MI355REC_ERR_HIP, "reading the playlist counter: %s", hipGetErrorString(e));
+        }
+        *rows_exact = static_cast<int64_t>(v);
+    }
+    return MI355REC_OK;
+}
+
+}  // extern "C"

@@ -48,13 +48,9 @@ void enqueue_half_seed(mi355rec* h, int kind, const float* qptr, const QueryArg&
     if (kind == kQ8) {
         const int extra = nbhd_applies(h, exclude_global) ? 1 : 0;
         if (h->qg.seed_grid + extra <= 0) return;
-#define SEED_Q8(EXACT)                                                                                                     \
-    hipLaunchKernelGGL((seed_q8_kernel<EXACT>), dim3(h->qg.seed_grid + extra), dim3(kHalfSeedBlock), 0, s, h->d_feats, h->d_q8, \
-                       h->n, h->qg.seed_stride, h->row_base, qa, qptr, exclude_global, seed_buf, epoch, h->qg.seed_grid, topn, \
-                       static_cast<const float*>(h->d_anchor))
-        if (q8_exact_sample(h)) SEED_Q8(true);
-        else SEED_Q8(false);
-#undef SEED_Q8
+        hipLaunchKernelGGL(seed_q8_kernel, dim3(h->qg.seed_grid + extra), dim3(kHalfSeedBlock), 0, s, h->d_feats, h->d_q8, h->n,
+                           h->qg.seed_stride, h->row_base, qa, qptr, exclude_global, seed_buf, epoch, h->qg.seed_grid, topn,
+                           static_cast<const float*>(h->d_anchor), q8_exact_sample(h));
         return;
     }
 #ifdef MI355REC_EXPERIMENTS

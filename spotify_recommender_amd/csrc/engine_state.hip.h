@@ -90,6 +90,7 @@ struct ReplicaGeom {
 }  // namespace
 
 struct mi355rec_labels;   // the label-grouped copy of a shard's rows (engine_labels.hip.h, mi355rec_set_labels)
+struct mi355rec_playlist;   // the buffers of the playlist calls (engine_playlist.hip.h)
 
 struct mi355rec {
     int device = 0;
@@ -115,6 +116,9 @@ struct mi355rec {
     mi355rec_labels* labels = nullptr;
     int64_t label_queries = 0;          // filtered queries since create ...
     int64_t label_rows_scanned = 0;     // ... and the rows their launches scanned (whole tiles)
+    // PLAYLISTS (mi355rec_query_mean_topn / _query_playlist_topn): allocated by the first call, owned by the handle (lanes have their own)
+    mi355rec_playlist* playlist = nullptr;
+    int64_t playlist_queries = 0;
 
     int cus = 0;
     int grid = 0;

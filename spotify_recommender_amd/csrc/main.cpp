@@ -8,6 +8,7 @@
 //   recommender --song "<name>" [-n N]
 //   recommender --id "<track_id>" [-n N]
 //   ... either query mode with one or more --genre NAME: recommendations only from those genres (extension)
+//   recommender --playlist "<track_id>,<track_id>,..." [-n N]: what goes with a playlist of up to 32 songs (extension)
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -159,6 +160,73 @@ static bool recommendationMode(const std::string& query, bool isTrackId, int top
     return true;
 }
 
+// --playlist: the songs most similar on average to the playlist's (exact track ids, the first row of an id as for --id),
+// the playlist's own songs never among them.
+static bool playlistMode(const std::string& list, int topN) {
+    std::cout << "=== PLAYLIST MODE ===" << std::endl;
+    std::vector<std::string> ids;
+    for (size_t start = 0; start <= list.size();) {
+        size_t end = list.find(',', start);
+        if (end == std::string::npos) end = list.size();
+        if (end > start) ids.push_back(list.substr(start, end - start));
+        start = end + 1;
+    }
+    if (ids.empty()) {
+        std::cerr << "Error: the playlist names no track" << std::endl;
+        return false;
+    }
+    DataManager::Catalogue catalogue;
+    if (!DataManager::loadCatalogue(kBinaryDataFile, catalogue)) {
+        std::cerr << "Failed to load data. Have you run preprocessing?" << std::endl;
+        return false;
+    }
+    std::vector<int> members;
+    for (const std::string& id : ids) {
+        int index = -1;
+        for (size_t i = 0; i < catalogue.size() && index < 0; ++i)
+            if (catalogue.trackIds[i] == id) index = static_cast<int>(i);
+        if (index < 0) {
+            std::cerr << "Error: Song with track_id '" << id << "' not found" << std::endl;
+            return false;
+        }
+        members.push_back(index);
+    }
+    Recommender recommender;
+    if (!recommender.initialize(catalogue.features, catalogue.trackIds, catalogue.trackNames)) {
+        std::cerr << "Failed to initialize recommender" << std::endl;
+        return false;
+    }
+    std::map<int, std::string>& genreMap = catalogue.genreMap;
+    const std::vector<int> recs = recommender.recommendForPlaylist(members, topN);
+    if (recs.empty()) {
+        std::cerr << "No recommendations found. Please check the query." << std::endl;
+        return false;
+    }
+    Song song;
+    std::cout << "\n----------------------------------------------\nPlaylist (" << members.size() << " songs):" << std::endl;
+    for (size_t i = 0; i < members.size(); ++i) {
+        if (!DataManager::readSong(catalogue, static_cast<size_t>(members[i]), song)) {
+            std::cerr << "Error: could not read song " << members[i] << " from " << catalogue.path << std::endl;
+            return false;
+        }
+        std::cout << "  " << (i + 1) << ". \"" << song.track_name << "\"" << std::endl;
+        printSong(song, genreMap, "     ");
+    }
+    std::cout << "----------------------------------------------" << std::endl;
+    std::cout << "\nTop " << recs.size() << " Recommendations:\n" << std::endl;
+    for (size_t i = 0; i < recs.size(); ++i) {
+        if (!DataManager::readSong(catalogue, static_cast<size_t>(recs[i]), song)) {
+            std::cerr << "Error: could not read song " << recs[i] << " from " << catalogue.path << std::endl;
+            return false;
+        }
+        std::cout << (i + 1) << ". \"" << song.track_name << "\"" << std::endl;
+        printSong(song, genreMap, "   ");
+        if (i + 1 < recs.size()) std::cout << std::endl;
+    }
+    std::cout << "\nRecommendation complete!" << std::endl;
+    return true;
+}
+
 int main(int argc, char* argv[]) {
     std::cout << "== High-Performance Music Recommendation Engine ==\n"
               << "==   MI355X-native (HIP / gfx950) cosine top-N  ==\n" << std::endl;
@@ -202,6 +270,24 @@ int main(int argc, char* argv[]) {
             genres.push_back(argv[++i]);
         }
         return recommendationMode(argv[2], mode == "--id", topN, genres) ? 0 : 1;
+    }
+    if (mode == "--playlist") {
+        if (argc < 3) {
+            std::cerr << "Error: --playlist needs a comma-separated list of track IDs" << std::endl;
+            return 1;
+        }
+        int topN = 10;
+        for (int i = 3; i < argc - 1; ++i) {
+            if (std::strcmp(argv[i], "-n") == 0) {
+                topN = std::atoi(argv[i + 1]);
+                if (topN <= 0) {
+                    std::cerr << "Error: Invalid value for -n (must be positive)" << std::endl;
+                    return 1;
+                }
+                break;
+            }
+        }
+        return playlistMode(argv[2], topN) ? 0 : 1;
     }
     std::cerr << "Error: Unknown mode '" << mode << "'" << std::endl;
     usage(argv[0]);

@@ -4,6 +4,7 @@
 // include/Recommender.h.  No CPU fallback anywhere in this file.
 #include "engine_batch.hip.h"
 #include "engine_labels.hip.h"
+#include "engine_playlist.hip.h"
 
 extern "C" {
 
@@ -91,6 +92,7 @@ void mi355rec_destroy(mi355rec_t* h) {
     for (hipEvent_t e : h->ev_pass) (void)hipEventDestroy(e);
     if (h->owned_feats && !h->shared) (void)hipFree(h->owned_feats);
     if (!h->shared) free_labels(h->labels);
+    free_playlist(h->playlist);
     if (h->d_block_lists) (void)hipFree(h->d_block_lists);
     if (h->d_lone_ctr) (void)hipFree(h->d_lone_ctr);
     {

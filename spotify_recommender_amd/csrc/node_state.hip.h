@@ -27,6 +27,10 @@ namespace mi355node {
 // mi355rec_set_labels for a handle whose group of lanes the caller has to itself (engine_labels.hip.h): the replicas of a
 // replicated placement that share a device are lanes of the first one there.
 int set_group_labels(mi355rec_t* h, const int32_t* labels_host, int64_t n);
+// mi355rec_query_mean_topn with up to MI355REC_MAX_EXCLUDE + MI355REC_MAX_PLAYLIST excluded ids (engine_playlist.hip.h): the
+// row-sharded node adds the members' global rows to the caller's list.
+int query_mean_topn(mi355rec_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude, int topn,
+                    int64_t* out_idx, float* out_score, int* out_count);
 }  // namespace mi355node
 
 namespace {

@@ -1,0 +1,320 @@
+// playlist.hip.h — the PLAYLIST scan (gfx950 only): the top-N rows by the MEAN of their scores against K <= 32 member
+// queries q_0 .. q_{K-1}, a set of excluded rows left out (engine_playlist.hip.h, include/mi355rec_diag.h "PLAYLISTS").
+//
+// Contract, per row x (bit for bit):
+//     c_k(x)   = cosine_score(q_k, |q_k|, x)                           (core.hip.h: the reference's chain)
+//     score(x) = fl( fl(...fl(c_0 + c_1) + ... + c_{K-1}) / (float)K )   (fp32, member order, one IEEE divide)
+// keys packed with the global row (ties break as in every other route), the excluded rows never listed.
+//
+// PRE-FILTER.  With u^_k = q_k / |q_k| the mean of the LINEAR cosines is u . x^ with u = (sum_k u^_k) / K: one dot product,
+// so one pass over the 8-bit replica (replica_q8.hip.h) bounds the mean of a row.  The replica's query is w = u / |u|
+// (q8_query on u: approx = D / (127 S) with |approx - w . x^| <= M, M = the q8 margin of w — row residual, query digits
+// and slack, tests/test_q8_margin.py), and a row is ruled out iff
+//     |u| approx < T - margin_mean,       margin_mean = |u| M + kPlChainErr + (2K + 32) kPlUlp,
+// T the workgroup's threshold score.  Why that holds, for a valid row x (|x|^2 in [kBqMinNorm2, kBqMaxNorm2]) and members
+// whose norms all lie in [kBqMinNorm, kBqMaxNorm] (then every den of the chain exceeds 1e-8 and no sum overflows):
+//   * u . x^ = |u| (w . x^) <= |u| (approx + M)                                    (the q8 bound of the query w)
+//   * |c_k - u^_k . x^| <= kPlChainErr: a 12-term fp32 dot and norm, two sqrtf, a product and a divide, < 30 ulp of 1
+//     (1.8e-6), doubled; the clamp to [-1, 1] only moves c_k towards the real cosine;
+//   * the roundings, each a few ulp (2^-24 = kPlUlp) of a quantity of size <= 1 after scaling by 1 / K: the K-term sum
+//     ((K + 1) / 2 ulp), the divide (1), u itself (fp32 in the kernel: u_j = fl(sum_k fl(q_kj / |q_k|)) / K in member
+//     order, |q_k| the chain's own norm: 8 ulp per term, K - 1 for the sum, 1 for the divide, so |(u~ - u) . x^| <=
+//     (K + 8) ulp), |u| in fp32 (9 ulp of |u| |approx + M| <= 1.02 |u|) and the fp32 quotient of the cutoff below (4) —
+//     (2K + 32) ulp covers their sum, 1.5 K + 23, with room.
+// So score(x) <= |u| approx + margin_mean, and a row with |u| approx < T - margin_mean scores below T.  In the kernel
+// the test is the replica's INTEGER compare D < q8_threshold((T - margin_mean) / |u|).  tests/test_playlist_margin.py
+// checks the bound with a numpy model of this arithmetic against the oracle, and that it is not vacuous.
+// The pre-filter is OFF for the whole query (every row takes the K chains) when the handle has no 8-bit replica, when
+// |u| < kPlMinMeanNorm or is not finite (members that cancel, zero members) or when a member's norm lies outside
+// [kBqMinNorm, kBqMaxNorm]; rows whose first byte is 0x80 (the replica's special rows) always take the K chains.
+//
+// STARTING THRESHOLD.  The rule: the k-th best key among ANY k or more distinct, not excluded rows bounds the k-th best key
+// of the answer from below, so a workgroup may start from it.  Every workgroup ranks the handle's 4096-row anchor table
+// (handoff.hip.h) by u, reads the best kPlBoundRows of those rows FROM THE MATRIX (the table may be stale for a borrowed
+// matrix: it only chooses rows), scores them with the K chains, drops the excluded ones (the LDS list below) and starts
+// from the topk-th best of the rest (0 when fewer than topk remain, or topk > kPlBoundRows).  All workgroups read the same
+// rows: they are L2-resident after the first.
+// The same rule makes every workgroup's own threshold (the topk-th best key of the rows IT has kept) a bound for all of
+// them: a workgroup that raises its threshold publishes it (atomicMax on PlaylistBuf::shared_thr, reset by the host's
+// copy of the call's inputs) and every workgroup takes the published maximum once per tile.  Monotone and valid whenever
+// it is read, so no ordering is needed; on a catalogue of clusters the workgroups that hold the members' cluster lend
+// their threshold to all the others.
+//
+// EXCLUSION.  The excluded global ids (members and the caller's list, sorted and deduplicated on the host, at most
+// kPlExcludeCap) sit in LDS as uint32; only a key that already beats the workgroup's threshold is looked up (binary
+// search), so the hot loop does not change.
+//
+// Tiles of 2048 rows (one quad of four rows per lane, the replica's packing) are dealt round-robin over the workgroups;
+// without a replica the same tiles are read from the fp32 rows, every row exact (a runtime branch, not a second
+// instantiation).  Selection, compaction and the per-workgroup lists are label_scan_kernel's; the merge of merge.hip.h
+// follows.
+#pragma once
+
+#include "replica_q8.hip.h"
+
+#pragma clang fp contract(off)
+
+namespace mi355 {
+
+constexpr int kMaxPlaylist = 32;                            // MI355REC_MAX_PLAYLIST
+constexpr int kMaxExclude = 1024;                           // MI355REC_MAX_EXCLUDE
+constexpr int kPlExcludeCap = kMaxExclude + kMaxPlaylist;   // the caller's ids and the members' rows
+constexpr int kPlBoundRows = 256;                           // anchor rows a workgroup scores for its starting threshold
+constexpr float kPlChainErr = 4e-6f;                        // |c_k - u^_k . x^| (see above)
+constexpr float kPlUlp = 5.9604645e-8f;                     // 2^-24
+constexpr float kPlMinMeanNorm = 1e-3f;                     // |u| below this: the pre-filter is off
+using PlaylistCfg = Q8Cfg<512, 4, 1>;                       // kBlock, kMinWaves (two workgroups per CU); tiles of 2048 rows
+
+// One call's inputs on the device (written by the host before the launch).
+struct PlaylistBuf {
+    float members[kMaxPlaylist][kDim];
+    int64_t rows[kMaxPlaylist];
+    unsigned long long shared_thr;   // the best threshold any workgroup of the launch has found (0 from the host)
+    uint32_t excl[kPlExcludeCap];   // sorted, distinct global ids (only those of this shard)
+};
+
+struct PlaylistArg {
+    int k;            // members
+    int n_excl;       // entries of PlaylistBuf::excl
+    int by_row;       // 1: member m is the shard's row PlaylistBuf::rows[m]; 0: PlaylistBuf::members[m]
+};
+
+// cosine_score with the row's norm sqrtf(sum f_j^2) taken once for all members: the same operations in the same order.
+__device__ __forceinline__ float cosine_with_norm(const float* __restrict__ q, float qn, const Row& r, float rn) {
+    const float f[kDim] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.c.x, r.c.y, r.c.z, r.c.w};
+    float dot = 0.0f;
+#pragma unroll
+    for (int j = 0; j < kDim; ++j) dot = dot + q[j] * f[j];
+    const float den = rn * qn;
+    float s = 0.0f;
+    if (den > 1e-8f) {
+        const float t = dot / den;
+        const float m = (t < 1.0f) ? t : 1.0f;
+        s = (-1.0f < m) ? m : -1.0f;
+    }
+    return s;
+}
+
+// The contract's score of one row: members (LDS) in order, one fp32 sum, one divide.
+__device__ __forceinline__ float playlist_mean(const float (*__restrict__ mem)[kDim], const float* __restrict__ qn, int k, const Row& r) {
+    float nrm = 0.0f;
+    {
+        const float f[kDim] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.c.x, r.c.y, r.c.z, r.c.w};
+#pragma unroll
+        for (int j = 0; j < kDim; ++j) nrm = nrm + f[j] * f[j];
+    }
+    const float rn = sqrtf(nrm);
+    float sum = cosine_with_norm(mem[0], qn[0], r, rn);
+    for (int m = 1; m < k; ++m) sum = sum + cosine_with_norm(mem[m], qn[m], r, rn);
+    return sum / static_cast<float>(k);
+}
+
+__device__ __forceinline__ bool playlist_excluded(const uint32_t* s_excl, int n_excl, uint32_t g) {
+    int lo = 0, hi = n_excl;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (s_excl[mid] < g) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < n_excl && s_excl[lo] == g;
+}
+
+// q8: the handle's 8-bit replica, or null (every row exact).  anchors: the anchor table, or null (no starting threshold).
+// rows_exact: += the rows whose K chains this launch computed.
+__global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void playlist_scan_kernel(
+    const float* __restrict__ feats, const uint4* __restrict__ q8, int64_t n, int64_t row_base, const PlaylistBuf* __restrict__ buf,
+    PlaylistArg arg, const float* __restrict__ anchors, int topk, uint64_t* __restrict__ block_lists,
+    unsigned long long* __restrict__ rows_exact, unsigned long long* __restrict__ shared_thr /* &buf->shared_thr */) {
+    constexpr int kBlock = PlaylistCfg::kBlock;
+    static_assert(PlaylistCfg::kCandCap >= kAnchorRows / 2 && PlaylistCfg::kCandCap * 2 >= kPlBoundRows, "LDS reuse below");
+    __shared__ uint64_t s_cand[PlaylistCfg::kCandCap];
+    __shared__ SelectSmem s_sel;
+    __shared__ int s_count;
+    __shared__ int s_ok;
+    __shared__ int s_exact;
+    __shared__ unsigned long long s_shared;
+    __shared__ float s_mem[kMaxPlaylist][kDim];
+    __shared__ float s_qn[kMaxPlaylist];
+    __shared__ float s_u[kDim];
+    __shared__ uint32_t s_excl[kPlExcludeCap];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int k = arg.k;
+    const int n_excl = arg.n_excl;
+
+    // ---- members and excluded ids into LDS; the members' norms and whether the bound can be claimed for them
+    for (int i = tid; i < k * kDim; i += kBlock)
+        s_mem[i / kDim][i % kDim] = arg.by_row ? feats[buf->rows[i / kDim] * kDim + i % kDim] : buf->members[i / kDim][i % kDim];
+    for (int i = tid; i < n_excl; i += kBlock) s_excl[i] = buf->excl[i];
+    if (tid == 0) {
+        s_count = 0;
+        s_ok = 1;
+        s_exact = 0;
+    }
+    __syncthreads();
+    if (tid < k) {
+        float q[kDim];
+#pragma unroll
+        for (int j = 0; j < kDim; ++j) q[j] = s_mem[tid][j];
+        const float qn = query_norm(q);
+        s_qn[tid] = qn;
+        if (!(qn >= kBqMinNorm && qn <= kBqMaxNorm)) s_ok = 0;   // (false for NaN too; every writer writes 0)
+    }
+    __syncthreads();
+    if (tid < kDim) {   // u: the mean of the members' unit vectors (only used where every |q_k| is in range)
+        float sum = s_mem[0][tid] / s_qn[0];
+        for (int m = 1; m < k; ++m) sum = sum + s_mem[m][tid] / s_qn[m];
+        s_u[tid] = sum / static_cast<float>(k);
+    }
+    __syncthreads();
+    float u[kDim];
+#pragma unroll
+    for (int j = 0; j < kDim; ++j) u[j] = s_u[j];
+    const float un = query_norm(u);
+    const Q8Query hq = q8_query(u, un);
+    const bool prefilter = q8 != nullptr && s_ok != 0 && hq.ok && un >= kPlMinMeanNorm;   // uniform (false for a NaN |u|)
+    const float margin_mean = un * hq.margin + kPlChainErr + static_cast<float>(2 * k + 32) * kPlUlp;
+    int n_exact = 0;   // rows whose K chains this thread computed
+    uint64_t thr = 0;
+
+    // ---- the starting threshold: the best kPlBoundRows anchors by u, scored exactly (see the rule above)
+    const int n_anchor = n < kAnchorRows ? static_cast<int>(n) : kAnchorRows;   // (anchor i is row i below kAnchorRows rows)
+    if (prefilter && anchors && topk <= kPlBoundRows && n_anchor >= kPlBoundRows) {   // uniform
+        constexpr int kPer = kAnchorRows / kBlock;
+        uint64_t mine[kPer];
+#pragma unroll
+        for (int r = 0; r < kPer; ++r) {
+            const int i = r * kBlock + tid;
+            const Row a = load_row(anchors, static_cast<int64_t>(i));
+            mine[r] = i < n_anchor ? pack_key(cosine_score(u, un, a), static_cast<uint32_t>(i)) : 0ull;
+        }
+        const uint64_t t = block_select_threshold<kBlock, kPer>(mine, kPlBoundRows, true, 0, s_sel);
+        int* const s_pick = reinterpret_cast<int*>(s_cand);
+#pragma unroll
+        for (int r = 0; r < kPer; ++r) {   // (uniform loop) exactly kPlBoundRows keys are >= t
+            const bool keep = mine[r] != 0ull && mine[r] >= t;
+            const uint64_t who = __ballot(keep);
+            int base = 0;
+            if (lane == 0 && who) base = atomicAdd(&s_count, __popcll(who));
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (keep) s_pick[base + lanes_below(who)] = r * kBlock + tid;
+        }
+        __syncthreads();
+        const int picked = s_count;
+        uint64_t key = 0ull;
+        if (tid < picked) {
+            const int64_t row = anchor_row(n, s_pick[tid]);
+            const Row x = load_row(feats, row);   // from the matrix
+            const float m = playlist_mean(s_mem, s_qn, k, x);
+            ++n_exact;
+            const uint32_t g = static_cast<uint32_t>(row_base + row);
+            key = playlist_excluded(s_excl, n_excl, g) ? 0ull : pack_key(m, g);
+        }
+        const uint64_t have = __ballot(key != 0ull);
+        __syncthreads();   // (every thread has read s_count and s_pick)
+        if (tid == 0) s_count = 0;
+        __syncthreads();
+        if (lane == 0 && have) atomicAdd(&s_count, __popcll(have));
+        __syncthreads();
+        const int usable = s_count;
+        __syncthreads();
+        if (tid == 0) s_count = 0;
+        if (usable >= topk) {   // uniform
+            const uint64_t one[1] = {key};
+            thr = block_select_threshold<kBlock, 1>(one, topk, true, 0, s_sel) - 1ull;   // keys >= the topk-th pass
+            if (tid == 0) atomicMax(shared_thr, static_cast<unsigned long long>(thr));
+        }
+        __syncthreads();
+    }
+
+    // ---- the scan
+    const int64_t n_quads = (n + 3) >> 2;
+    const int64_t tiles = (n_quads + kBlock - 1) / kBlock;
+    int cut_d = static_cast<int>(0x80000000u);   // every row is a candidate until a threshold exists
+    auto refresh_cut = [&]() {
+        if (prefilter && thr != 0ull) {   // uniform
+            const float t = ordered_to_score(static_cast<uint32_t>(thr >> 32));
+            cut_d = q8_threshold((t - margin_mean) / un);
+        }
+    };
+    refresh_cut();
+    int compact_at = 2 * topk > 256 ? 2 * topk : 256;
+    if (compact_at > kCandLimit) compact_at = kCandLimit;
+
+    auto load_q8 = [&](HalfTile& d, int64_t t) {
+        int64_t quad = t * kBlock + tid;
+        quad = quad < n_quads ? quad : n_quads - 1;
+        const uint4* p = q8 + quad * 3;
+        d.t0 = p[0];
+        d.t1 = p[1];
+        d.t2 = p[2];
+    };
+    HalfTile cur;
+    cur.t0 = cur.t1 = cur.t2 = make_uint4(0u, 0u, 0u, 0u);
+    if (prefilter) load_q8(cur, blockIdx.x);
+
+    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {   // uniform
+        HalfTile nxt = cur;
+        if (prefilter) load_q8(nxt, t + gridDim.x);   // the next tile is in flight while this one is scored
+        const int64_t quad = t * kBlock + tid;
+        const int64_t r0 = quad * 4;
+        uint32_t mask = 0u;
+        if (quad < n_quads) {
+            const int64_t left = n - r0;
+            mask = left >= 4 ? 0xfu : (1u << static_cast<int>(left)) - 1u;
+        }
+        if (prefilter) {   // uniform
+            int a[4];
+            bool special[4];
+            q8_dot4(hq, cur, a, special);
+#pragma unroll
+            for (int u4 = 0; u4 < 4; ++u4)
+                if (!(special[u4] || a[u4] >= cut_d)) mask &= ~(1u << u4);
+        }
+        while (__ballot(mask != 0u)) {   // uniform
+            const bool have = mask != 0u;
+            const int64_t r = have ? r0 + __builtin_ctz(mask) : 0;
+            const Row x = load_row(feats, r);
+            const float m = playlist_mean(s_mem, s_qn, k, x);
+            n_exact += have ? 1 : 0;
+            const uint32_t g = static_cast<uint32_t>(row_base + r);
+            const uint64_t key = have ? pack_key(m, g) : 0ull;
+            bool pass = key > thr;
+            if (pass && n_excl > 0) pass = !playlist_excluded(s_excl, n_excl, g);
+            const uint64_t ballot = __ballot(pass);
+            if (ballot) {
+                int base = 0;
+                if (lane == 0) base = atomicAdd(&s_count, __popcll(ballot));
+                base = __builtin_amdgcn_readfirstlane(base);
+                if (pass) s_cand[base + lanes_below(ballot)] = key;
+            }
+            mask &= mask - 1u;
+        }
+        // two barriers: every wave reads the count before any wave appends again (scan_kernel)
+        __syncthreads();
+        const int c = s_count;
+        if (tid == 0) s_shared = __hip_atomic_load(shared_thr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        const uint64_t published = s_shared;
+        if (c >= compact_at) {
+            const uint64_t local_thr = compact_candidates<kBlock, PlaylistCfg::kCandPerThread>(s_cand, &s_count, topk, false, s_sel);
+            if (local_thr > thr && local_thr > published && tid == 0) atomicMax(shared_thr, static_cast<unsigned long long>(local_thr));
+            if (local_thr > thr) thr = local_thr;
+        }
+        if (published > thr) thr = published;
+        refresh_cut();
+        cur = nxt;
+    }
+
+    const int wave_exact = wave_inclusive_scan(n_exact);
+    if (lane == 63 && wave_exact) atomicAdd(&s_exact, wave_exact);
+    __syncthreads();
+    if (tid == 0 && rows_exact && s_exact) atomicAdd(rows_exact, static_cast<unsigned long long>(s_exact));
+    if (s_count > kRankCountMax && s_count > topk)   // uniform
+        compact_candidates<kBlock, PlaylistCfg::kCandPerThread>(s_cand, &s_count, topk, false, s_sel);
+    __syncthreads();
+    block_rank_and_store<kBlock>(s_cand, s_count, block_lists + static_cast<int64_t>(blockIdx.x) * topk, topk);
+}
+
+}  // namespace mi355

@@ -197,7 +197,7 @@ __device__ __forceinline__ Q8Region q8_region_load(const uint4* __restrict__ q8,
 // (one 48 B fetch per wave, all lanes the same address): an exact score v of a real row needs only ONE margin in
 // the cutoff (approx < v - margin => exact < v), where the approximate maximum needed two.  At top-100 over
 // 10 M rows that is the difference between ~28 000 and ~10 000 rows sent to the exact chain per query.
-// (kExact = false keeps the approximate maximum and skips the fetch: small shards, where the riders' extra round
+// (exact = false keeps the approximate maximum and skips the fetch: small shards, where the riders' extra round
 // trip is on the critical path of the launch and a few hundred more candidates are not.)
 struct Q8Pick {
     int64_t row;     // wave-uniform: local row of the wave's best usable row
@@ -233,11 +233,10 @@ __device__ __forceinline__ Q8Pick q8_region_pick(const Q8Region& s, const Q8Quer
     return p;
 }
 
-template <bool kExact>
 __device__ __forceinline__ void q8_region_store(const Q8Pick& p, const Row& row, const float (&q)[kDim], float qn,
-                                                unsigned long long* __restrict__ seed_vals, uint32_t epoch, int64_t g) {
+                                                unsigned long long* __restrict__ seed_vals, uint32_t epoch, int64_t g, bool exact) {
     uint32_t v = p.top;
-    if constexpr (kExact) {
+    if (exact) {   // (uniform)
         const float exact = cosine_score(q, qn, row);
         v = p.any ? score_to_ordered(exact) : 0u;
     }
@@ -259,13 +258,13 @@ __device__ __forceinline__ void q8_load_query(const float* __restrict__ query_pt
 }
 
 // One workgroup per region (single queries; the first query of a stream) and, when the grid has one more workgroup
-// than regions, the neighbourhood of the excluded row (handoff.hip.h) by that last one.
-template <bool kExact>
+// than regions, the neighbourhood of the excluded row (handoff.hip.h) by that last one.  `exact`: the sample values are
+// EXACT scores (q8_region_store) — a kernel argument, not a template parameter: both kinds share one kernel.
 __global__ __launch_bounds__(kHalfSeedBlock) void seed_q8_kernel(
     const float* __restrict__ feats, const uint4* __restrict__ q8, int64_t n, int64_t stride_rows, int64_t row_base, QueryArg qarg,
     const float* __restrict__ query_ptr /* null: the query is qarg.q */, int64_t exclude_global,
     unsigned long long* __restrict__ seed_vals, uint32_t epoch, int regions, int topk,
-    const float* __restrict__ anchors /* the handle's anchor table (handoff.hip.h), or null */) {
+    const float* __restrict__ anchors /* the handle's anchor table (handoff.hip.h), or null */, bool exact) {
     if (static_cast<int>(blockIdx.x) >= regions) {   // uniform
         // (1024 rows: this workgroup is the last one out of the sample launch of a query alone, and the scan subtracts a margin
         // of ~0.01 from whatever bound it is given — the 10th percentile of the neighbourhood serves it as well as the 5th)
@@ -283,8 +282,8 @@ __global__ __launch_bounds__(kHalfSeedBlock) void seed_q8_kernel(
     const Q8Pick p = q8_region_pick(s, hq, n, row_base, exclude_global);
     Row row;
     row.a = row.b = row.c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if constexpr (kExact) row = load_row(feats, p.row);
-    q8_region_store<kExact>(p, row, q, qn, seed_vals, epoch, blockIdx.x);
+    if (exact) row = load_row(feats, p.row);   // (uniform)
+    q8_region_store(p, row, q, qn, seed_vals, epoch, blockIdx.x, exact);
 }
 
 // The seed riders of a streamed launch (handoff.hip.h, NextSeed): four regions per memory round trip.
@@ -321,7 +320,7 @@ __device__ __forceinline__ Q8Query q8_seed_rider(const float* __restrict__ feats
 #pragma unroll
             for (int u = 0; u < kAhead; ++u) {
                 const int g = g0 + u * next.n_wgs;
-                if (g < next.regions && g >= next.debug_skip) q8_region_store<true>(pick[u], best[u], q, qn, out, next.epoch, g);   // uniform
+                if (g < next.regions && g >= next.debug_skip) q8_region_store(pick[u], best[u], q, qn, out, next.epoch, g, true);   // uniform
             }
         } else {
             Row none;
@@ -329,7 +328,7 @@ __device__ __forceinline__ Q8Query q8_seed_rider(const float* __restrict__ feats
 #pragma unroll
             for (int u = 0; u < kAhead; ++u) {
                 const int g = g0 + u * next.n_wgs;
-                if (g < next.regions && g >= next.debug_skip) q8_region_store<false>(pick[u], none, q, qn, out, next.epoch, g);   // uniform
+                if (g < next.regions && g >= next.debug_skip) q8_region_store(pick[u], none, q, qn, out, next.epoch, g, false);   // uniform
             }
         }
     }

@@ -628,6 +628,119 @@ int mi355rec_sharded_query_row_topn_labels(mi355rec_sharded_t* h, int64_t global
     return sharded_labels_by_value(h, q, global_row, labels, n_labels, topn, out_idx, out_score, out_count);
 }
 
+// ---- PLAYLISTS (include/mi355rec_diag.h) ------------------------------------------------------------------------------
+namespace {
+// The node-level checks of both playlist calls (the catalogue's global rows are known here).
+int check_playlist(mi355rec_sharded_t* h, const void* members, int k, const int64_t* exclude_global, int n_exclude, int topn,
+                   int64_t* out_idx) {
+    if (!h || !members || !out_idx) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    if (k < 1 || k > MI355REC_MAX_PLAYLIST)
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "playlist of %d songs: 1 to %d are supported", k, MI355REC_MAX_PLAYLIST);
+    if (topn <= 0 || topn > MI355REC_MAX_TOPN_FAST)
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "topn %d out of [1, %d] (a playlist query has one round)", topn, MI355REC_MAX_TOPN_FAST);
+    if (n_exclude < 0 || n_exclude > MI355REC_MAX_EXCLUDE)
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "n_exclude %d out of [0, %d]", n_exclude, MI355REC_MAX_EXCLUDE);
+    if (n_exclude > 0 && !exclude_global) return sfail(h, MI355REC_ERR_INVALID_ARG, "null exclusion list with n_exclude %d", n_exclude);
+    for (int i = 0; i < n_exclude; ++i)
+        if (exclude_global[i] < 0 || exclude_global[i] >= h->n)
+            return sfail(h, MI355REC_ERR_INVALID_ARG, "excluded row %lld out of the catalogue", (long long)exclude_global[i]);
+    return MI355REC_OK;
+}
+
+// members (k x 12, by value) and the excluded global ids: the CPU backend, one handle, or every shard and a host merge.
+int sharded_mean(mi355rec_sharded_t* h, const float* members, int k, const int64_t* excl, int n_excl, int topn, int64_t* out_idx,
+                 float* out_score, int* out_count) {
+    if (h->cpu) {
+        const char* why = nullptr;
+        return cpu_result(h, mi355cpu::node_query_mean(h->cpu, members, k, excl, n_excl, topn, out_idx, out_score, out_count, &why), why);
+    }
+    DeviceRestore restore;
+    if (h->shards.size() == 1 || h->replicated) {   // one handle holds the whole catalogue (row_base 0)
+        Shard* s = &h->shards[0];
+        if (h->replicated) {
+            const int rc = take_replica(h, &s);
+            if (rc) return rc;
+        } else {
+            S_HIP(h, hipSetDevice(s->device));
+        }
+        const int rc = mi355node::query_mean_topn(s->engine, members, k, excl, n_excl, topn, out_idx, out_score, out_count);
+        return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s->engine));
+    }
+    const int drc = drain_workers(h);
+    if (drc) return drc;
+    std::vector<mi355rec_key_t> keys;
+    std::vector<int64_t> idx;
+    std::vector<float> sc;
+    try {
+        idx.resize(static_cast<size_t>(topn));
+        sc.resize(static_cast<size_t>(topn));
+        keys.reserve(static_cast<size_t>(topn) * h->shards.size());
+    } catch (const std::bad_alloc&) {
+        return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for %d results per shard", topn);
+    }
+    for (Shard& s : h->shards) {   // every shard gets the whole list and matches the ids of its own rows
+        if (s.hi <= s.lo) continue;
+        S_HIP(h, hipSetDevice(s.device));
+        int c = 0;
+        const int rc = mi355node::query_mean_topn(s.engine, members, k, excl, n_excl, topn, idx.data(), sc.data(), &c);
+        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", s.device, mi355rec_last_error(s.engine));
+        for (int i = 0; i < c; ++i) keys.push_back(mi355rec_pack_key(sc[static_cast<size_t>(i)], idx[static_cast<size_t>(i)]));
+    }
+    const size_t count = keys.size() < static_cast<size_t>(topn) ? keys.size() : static_cast<size_t>(topn);
+    std::partial_sort(keys.begin(), keys.begin() + count, keys.end(), std::greater<mi355rec_key_t>());
+    for (size_t i = 0; i < static_cast<size_t>(topn); ++i) {
+        out_idx[i] = i < count ? mi355rec_key_row(keys[i]) : -1;
+        if (out_score) out_score[i] = i < count ? mi355rec_key_score(keys[i]) : 0.0f;
+    }
+    if (out_count) *out_count = static_cast<int>(count);
+    return MI355REC_OK;
+}
+}  // namespace
+
+int mi355rec_sharded_query_mean_topn(mi355rec_sharded_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude,
+                                     int topn, int64_t* out_idx, float* out_score, int* out_count) {
+    const int rc = check_playlist(h, queries, k, exclude_global, n_exclude, topn, out_idx);
+    if (rc) return rc;
+    return sharded_mean(h, queries, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count);
+}
+
+int mi355rec_sharded_query_playlist_topn(mi355rec_sharded_t* h, const int64_t* global_rows, int k, const int64_t* exclude_global,
+                                         int n_exclude, int topn, int64_t* out_idx, float* out_score, int* out_count) {
+    int rc = check_playlist(h, global_rows, k, exclude_global, n_exclude, topn, out_idx);
+    if (rc) return rc;
+    for (int m = 0; m < k; ++m)
+        if (global_rows[m] < 0 || global_rows[m] >= h->n)
+            return sfail(h, MI355REC_ERR_INVALID_ARG, "Invalid song index: %lld", (long long)global_rows[m]);
+    if (!h->cpu && h->shards.size() == 1 && !h->replicated) {   // one handle: its own by-row call (the members stay on the device)
+        DeviceRestore restore;
+        Shard& s = h->shards[0];
+        S_HIP(h, hipSetDevice(s.device));
+        rc = mi355rec_query_playlist_topn(s.engine, global_rows, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count);
+        return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s.engine));
+    }
+    // the members by value (fetched once) and their rows added to the exclusion list
+    float members[MI355REC_MAX_PLAYLIST * MI355REC_DIM];
+    int64_t excl[MI355REC_MAX_EXCLUDE + MI355REC_MAX_PLAYLIST];
+    for (int i = 0; i < n_exclude; ++i) excl[i] = exclude_global[i];
+    for (int m = 0; m < k; ++m) {
+        excl[n_exclude + m] = global_rows[m];
+        if (h->cpu) {
+            std::memcpy(members + m * MI355REC_DIM, mi355cpu::row(mi355cpu::node_catalogue(h->cpu), global_rows[m]), sizeof(float) * MI355REC_DIM);
+            continue;
+        }
+        if (m == 0) {
+            rc = drain_workers(h);
+            if (rc) return rc;
+        }
+        DeviceRestore restore;
+        const Shard* own = owner_of(h, global_rows[m]);
+        S_HIP(h, hipSetDevice(own->device));
+        rc = mi355rec_fetch_row(own->engine, global_rows[m] - own->lo, members + m * MI355REC_DIM);
+        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
+    }
+    return sharded_mean(h, members, k, excl, n_exclude + k, topn, out_idx, out_score, out_count);
+}
+
 int mi355rec_sharded_scores_row(mi355rec_sharded_t* h, int64_t global_row, float* out_host) {
     if (!h || !out_host) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     if (global_row < 0 || global_row >= h->n)

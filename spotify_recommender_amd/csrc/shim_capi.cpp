@@ -176,6 +176,14 @@ int64_t shim_recommend_by_index_in_genres(void* h, int idx, int topn, const int*
     return giveBack(c, c->rec.recommendByIndexInGenres(idx, topn, std::vector<int>(genres, genres + (n_genres > 0 ? n_genres : 0))),
                     out, scores, cap);
 }
+// Recommender::recommendForPlaylist.
+int64_t shim_recommend_for_playlist(void* h, const int* songs, int n_songs, int topn, const int* exclude, int n_exclude, int* out,
+                                    float* scores, int64_t cap) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    return giveBack(c, c->rec.recommendForPlaylist(std::vector<int>(songs, songs + (n_songs > 0 ? n_songs : 0)), topn,
+                                                   std::vector<int>(exclude, exclude + (n_exclude > 0 ? n_exclude : 0))),
+                    out, scores, cap);
+}
 int shim_similarities(void* h, int idx, float* out_n) {
     Catalogue* c = static_cast<Catalogue*>(h);
     std::vector<float> v;

@@ -37,6 +37,28 @@ def _labels_query(fn, h, check, head, labels, topn: int) -> Tuple[np.ndarray, np
     return idx[:count.value].copy(), score[:count.value].copy()
 
 
+def _playlist_query(fn, h, check, members, exclude, topn: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Runs one playlist entry point: fn(h, members, k, exclude, n_exclude, topn, idx, score, &count).  `members` is a
+    (k, 12) float32 array (by value) or a 1-D int64 array of rows (by row)."""
+    k = int(members.shape[0])
+    ex = np.ascontiguousarray(np.asarray([] if exclude is None else list(exclude), dtype=np.int64).reshape(-1))
+    n_out = max(int(topn), 1)
+    idx = np.empty(n_out, dtype=np.int64)
+    score = np.empty(n_out, dtype=np.float32)
+    count = ctypes.c_int(0)
+    check(fn(h, members.ctypes.data_as(ctypes.c_void_p), k, ex.ctypes.data_as(ctypes.c_void_p) if ex.size else None, int(ex.size),
+             int(topn), idx.ctypes.data_as(ctypes.c_void_p), score.ctypes.data_as(ctypes.c_void_p), ctypes.byref(count)))
+    return idx[:count.value].copy(), score[:count.value].copy()
+
+
+def _np_members(queries) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(queries, dtype=np.float32).reshape(-1, capi.DIM))
+
+
+def _np_rows(rows) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(list(rows), dtype=np.int64).reshape(-1))
+
+
 class CosineEngine:
     """One row shard of the N x 12 fp32 catalogue resident on one MI355X.
 
@@ -377,6 +399,23 @@ class CosineEngine:
         return {"queries": q.value, "rows_scanned": r.value}
 
 
+    # ---- PLAYLISTS (include/mi355rec_diag.h): top-N by the mean score against up to 32 songs ----
+    def query_mean_topn(self, queries, topn: int, exclude=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The best `topn` rows by the mean of their scores against the rows of `queries` (k x 12); `exclude`: global ids."""
+        return _playlist_query(self._lib.mi355rec_query_mean_topn, self._h, lambda rc: capi.check(rc, self._h),
+                               _np_members(queries), exclude, topn)
+
+    def query_playlist_topn(self, local_rows, topn: int, exclude=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The same for members given as rows of this handle; the members are never returned."""
+        return _playlist_query(self._lib.mi355rec_query_playlist_topn, self._h, lambda rc: capi.check(rc, self._h),
+                               _np_rows(local_rows), exclude, topn)
+
+    def playlist_counters(self) -> dict:
+        q, r = ctypes.c_int64(0), ctypes.c_int64(0)
+        capi.check(self._lib.mi355rec_playlist_counters(self._h, ctypes.byref(q), ctypes.byref(r)), self._h)
+        return {"queries": q.value, "rows_exact": r.value}
+
+
 class NodeEngine:
     """The catalogue on the GPUs of one node driven by ONE process (mi355rec_create_placed): what the C++
     Recommender shim uses.  `placement`: capi.PLACEMENT_SHARDED (rows split over the devices; the default),
@@ -490,6 +529,14 @@ class NodeEngine:
         q = _np_f32(query).reshape(capi.DIM)
         return _labels_query(self._lib.mi355rec_sharded_query_topn_labels, self._h, self._check,
                              (q.ctypes.data_as(ctypes.c_void_p), int(exclude_global)), labels, topn)
+
+    # ---- PLAYLISTS (include/mi355rec_diag.h) over the whole node ----
+    def query_mean_topn(self, queries, topn: int, exclude=None) -> Tuple[np.ndarray, np.ndarray]:
+        return _playlist_query(self._lib.mi355rec_sharded_query_mean_topn, self._h, self._check, _np_members(queries), exclude, topn)
+
+    def query_playlist_topn(self, global_rows, topn: int, exclude=None) -> Tuple[np.ndarray, np.ndarray]:
+        return _playlist_query(self._lib.mi355rec_sharded_query_playlist_topn, self._h, self._check, _np_rows(global_rows), exclude,
+                               topn)
 
     def scores_row(self, global_row: int) -> np.ndarray:
         out = np.empty(self.rows, dtype=np.float32)
