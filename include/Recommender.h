@@ -87,6 +87,21 @@ public:
     // topN is capped at the songs that can be returned; above 1024 it is refused.
     std::vector<int> recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<int>& alsoExclude = {});
 
+    // Extension: feature-range filters.  Only songs whose feature `feature` (0..11 in Song.h order: danceability, energy,
+    // key, loudness, mode, speechiness, acousticness, instrumentalness, liveness, valence, tempo, genre id) lies in
+    // [lo, hi] are returned, in the units of the matrix (songs_data.bin: normalised to [0, 1]).  Several ranges on one
+    // feature intersect; an empty range list filters nothing.  recommendByIndexWhere is recommendByIndex among the songs that
+    // pass every range (same checks, messages and lastScores(); topN above 1024 is refused); the overload of
+    // recommendForPlaylist does the same for a playlist.  A feature outside 0..11, a NaN bound, lo > hi or ranges on one
+    // feature that do not overlap give {} and a message.
+    struct FeatureRange {
+        int feature;
+        float lo, hi;
+    };
+    std::vector<int> recommendByIndexWhere(int songIndex, int topN, const std::vector<FeatureRange>& where);
+    std::vector<int> recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<FeatureRange>& where,
+                                          const std::vector<int>& alsoExclude);
+
     struct Impl;   // opaque: defined in Recommender.cpp
 
 private:

@@ -16,6 +16,8 @@
  *     (mi355rec_set_labels, _query_row_topn_labels, _query_topn_labels, _label_counters and their node-handle twins);
  *   - PLAYLISTS, a further extension: the top-N rows by the mean of their scores against up to 32 songs, with an exclusion
  *     list (mi355rec_query_mean_topn, _query_playlist_topn, _playlist_counters and their node-handle twins);
+ *   - FEATURE FILTERS, on the playlist calls: only rows whose audio features lie within given bounds are returned
+ *     (mi355rec_query_mean_topn_where, _query_playlist_topn_where and their node-handle twins);
  *   - test hooks, compiled in only with -DMI355REC_TEST_HOOKS (spotify_recommender_amd/build.py builds
  *     libmi355rec_testhooks.so for tests/; the product library does not export them).
  */
@@ -411,6 +413,41 @@ int mi355rec_sharded_query_mean_topn(mi355rec_sharded_t* h, const float* queries
                                      int n_exclude, int topn, int64_t* out_idx, float* out_score, int* out_count);
 int mi355rec_sharded_query_playlist_topn(mi355rec_sharded_t* h, const int64_t* global_rows, int k, const int64_t* exclude_global,
                                          int n_exclude, int topn, int64_t* out_idx, float* out_score, int* out_count);
+
+/* FEATURE FILTERS (an extension beyond the reference): "songs like these, but only high-energy".
+ * A row x passes the filter iff, for every feature j whose bit is set in `active` (j < MI355REC_DIM),
+ *     lo[j] <= x[j] && x[j] <= hi[j]      (IEEE compares on the stored fp32 feature)
+ * so a NaN feature fails any active bound, -0.0 equals +0.0 and +-inf bounds are allowed.  The features are the catalogue's
+ * 12 columns (Song.h: danceability, energy, key, loudness, mode, speechiness, acousticness, instrumentalness, liveness,
+ * valence, tempo, genre id), in whatever units the matrix holds (the drop-in's songs_data.bin: min-max normalised to [0, 1]).
+ * The _where calls are the playlist calls above with a filter: they return the top-N of the rows that pass, are not excluded
+ * and are not members (by-row calls), with the playlist call's scores bit for bit and the canonical order;
+ * count = min(topn, |admissible rows|), the rest padded with -1 / 0; topn <= 1024.  A filtered SINGLE query is the K = 1
+ * form (a one-song playlist is exactly the single query): there are no separate single-query entry points.
+ * A NULL filter or active == 0 is exactly the unfiltered call (same results, same launch).
+ * INVALID_ARG (with a message): the playlist calls' cases, and a bit of `active` at or above MI355REC_DIM, a NaN bound or
+ * lo[j] > hi[j] on an active feature.
+ * mi355rec_playlist_counters counts filtered calls too; their rows_exact is every row read from the fp32 matrix, the rows
+ * the filter then rejected included (rejected rows never take the K chains).
+ * Device: the filter is tested inside playlist_scan_kernel on each fp32 row it reads (csrc/playlist.hip.h, "FEATURE
+ * FILTER"), with no set-up: lanes and node handles answer at once.  Node handles as for the playlist calls: a row-sharded
+ * one asks every shard by value with the filter and merges on the host.  The CPU backend serves the same calls. */
+typedef struct {
+    uint32_t active; /* bit j (j < 12): feature j is constrained; higher bits: INVALID_ARG */
+    float lo[12];    /* a row x passes iff, for every active j,  lo[j] <= x[j] && x[j] <= hi[j]  (IEEE compares) */
+    float hi[12];
+} mi355rec_filter_t;
+int mi355rec_query_mean_topn_where(mi355rec_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude,
+                                   const mi355rec_filter_t* filter, int topn, int64_t* out_idx, float* out_score, int* out_count);
+int mi355rec_query_playlist_topn_where(mi355rec_t* h, const int64_t* local_rows, int k, const int64_t* exclude_global,
+                                       int n_exclude, const mi355rec_filter_t* filter, int topn, int64_t* out_idx, float* out_score,
+                                       int* out_count);
+int mi355rec_sharded_query_mean_topn_where(mi355rec_sharded_t* h, const float* queries, int k, const int64_t* exclude_global,
+                                           int n_exclude, const mi355rec_filter_t* filter, int topn, int64_t* out_idx,
+                                           float* out_score, int* out_count);
+int mi355rec_sharded_query_playlist_topn_where(mi355rec_sharded_t* h, const int64_t* global_rows, int k,
+                                               const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
+                                               int topn, int64_t* out_idx, float* out_score, int* out_count);
 
 #ifdef MI355REC_TEST_HOOKS
 /* TEST HOOK for the cross-workgroup hand-offs of the streamed scans (csrc/replica.hip.h, "hand-offs that fail

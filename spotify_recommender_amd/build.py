@@ -219,7 +219,7 @@ def build_shim(force: bool = False) -> Path:
     build_engine(force)
     common = ["g++", "-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", f"-I{INCLUDE}"]
     link = [f"-L{PKG}", "-lmi355rec", "-Wl,-rpath,$ORIGIN"]
-    if force or _stale(LIB_SHIM, deps + [LIB_ENGINE]):
+    if force or _stale(LIB_SHIM, deps + [CSRC / "shim_capi.cpp", LIB_ENGINE]):
         _run([*common, "-shared", "-o", LIB_SHIM, *srcs, CSRC / "shim_capi.cpp", *link])
     main_cpp = CSRC / "main.cpp"
     if main_cpp.exists() and (force or _stale(BIN_CLI, deps + [main_cpp, LIB_SHIM])):

@@ -35,6 +35,14 @@ ERR_OUT_OF_MEMORY = -4
 MAX_LABELS = 1024
 MAX_PLAYLIST = 32
 MAX_EXCLUDE = 1024
+# FEATURE FILTERS: the catalogue's columns in matrix order (Song.h); `where=` mappings take a name or an index.
+FEATURE_NAMES = ("danceability", "energy", "key", "loudness", "mode", "speechiness", "acousticness", "instrumentalness",
+                 "liveness", "valence", "tempo", "genre_id")
+
+
+class Filter(ctypes.Structure):
+    """mi355rec_filter_t (include/mi355rec_diag.h, FEATURE FILTERS)."""
+    _fields_ = [("active", c_uint32), ("lo", c_float * DIM), ("hi", c_float * DIM)]
 
 
 class Stats(ctypes.Structure):
@@ -166,6 +174,14 @@ SIGNATURES = {
                                                  POINTER(c_int)]),
     "mi355rec_sharded_query_playlist_topn": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                                      POINTER(c_int)]),
+    "mi355rec_query_mean_topn_where": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                               POINTER(c_int)]),
+    "mi355rec_query_playlist_topn_where": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                                   POINTER(c_int)]),
+    "mi355rec_sharded_query_mean_topn_where": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                                       c_void_p, POINTER(c_int)]),
+    "mi355rec_sharded_query_playlist_topn_where": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                                           c_void_p, POINTER(c_int)]),
     "mi355rec_pack_key": (c_uint64, [c_float, c_int64]),
     "mi355rec_key_score": (c_float, [c_uint64]),
     "mi355rec_key_row": (c_int64, [c_uint64]),

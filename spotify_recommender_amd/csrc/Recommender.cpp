@@ -238,8 +238,41 @@ std::vector<int> Recommender::recommendByIndexInGenres(int songIndex, int topN, 
     return results;
 }
 
-std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<int>& alsoExclude) {
-    if (!impl_->initialized) {
+namespace {
+
+// The ranges as one mi355rec_filter_t (ranges on one feature intersected); false, with a message, when they cannot be.
+bool makeFilter(const std::vector<Recommender::FeatureRange>& where, mi355rec_filter_t& f) {
+    f.active = 0;
+    for (const Recommender::FeatureRange& r : where) {
+        if (r.feature < 0 || r.feature >= MI355REC_DIM) {
+            std::cerr << "Error: feature index " << r.feature << " out of [0, " << MI355REC_DIM << ")" << std::endl;
+            return false;
+        }
+        if (!(r.lo <= r.hi)) {   // (NaN too)
+            std::cerr << "Error: invalid range [" << r.lo << ", " << r.hi << "] on feature " << r.feature << std::endl;
+            return false;
+        }
+        const uint32_t bit = 1u << r.feature;
+        if (!(f.active & bit)) {
+            f.active |= bit;
+            f.lo[r.feature] = r.lo;
+            f.hi[r.feature] = r.hi;
+            continue;
+        }
+        f.lo[r.feature] = std::max(f.lo[r.feature], r.lo);
+        f.hi[r.feature] = std::min(f.hi[r.feature], r.hi);
+        if (f.lo[r.feature] > f.hi[r.feature]) {
+            std::cerr << "Error: the ranges on feature " << r.feature << " do not overlap" << std::endl;
+            return false;
+        }
+    }
+    return true;
+}
+
+// recommendForPlaylist with a filter (null: the unfiltered entry point).
+std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& songIndices, int topN, const std::vector<int>& alsoExclude,
+                               const mi355rec_filter_t* filter) {
+    if (!impl->initialized) {
         std::cerr << "Error: Recommender not initialized" << std::endl;
         return {};
     }
@@ -254,7 +287,7 @@ std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songI
     std::vector<int64_t> rows(songIndices.begin(), songIndices.end()), excl(alsoExclude.begin(), alsoExclude.end());
     for (const std::vector<int64_t>* v : {&rows, &excl})
         for (int64_t i : *v)
-            if (i < 0 || i >= impl_->numSongs) {
+            if (i < 0 || i >= impl->numSongs) {
                 std::cerr << "Error: Invalid song index: " << i << std::endl;
                 return {};
             }
@@ -262,20 +295,44 @@ std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songI
         std::cerr << "Error: topN must be positive" << std::endl;
         return {};
     }
-    if (topN > impl_->numSongs) topN = impl_->numSongs;   // (the engine pads past what it can return; no buffer beyond the songs)
-    impl_->idxBuf.assign(static_cast<size_t>(topN), -1);
-    impl_->scoreBuf.assign(static_cast<size_t>(topN), 0.0f);
+    if (topN > impl->numSongs) topN = impl->numSongs;   // (the engine pads past what it can return; no buffer beyond the songs)
+    impl->idxBuf.assign(static_cast<size_t>(topN), -1);
+    impl->scoreBuf.assign(static_cast<size_t>(topN), 0.0f);
     int count = 0;
-    const int rc = mi355rec_sharded_query_playlist_topn(impl_->engine, rows.data(), static_cast<int>(rows.size()), excl.data(),
-                                                        static_cast<int>(excl.size()), topN, impl_->idxBuf.data(), impl_->scoreBuf.data(), &count);
+    const int rc = filter ? mi355rec_sharded_query_playlist_topn_where(impl->engine, rows.data(), static_cast<int>(rows.size()), excl.data(),
+                                                                       static_cast<int>(excl.size()), filter, topN, impl->idxBuf.data(),
+                                                                       impl->scoreBuf.data(), &count)
+                          : mi355rec_sharded_query_playlist_topn(impl->engine, rows.data(), static_cast<int>(rows.size()), excl.data(),
+                                                                 static_cast<int>(excl.size()), topN, impl->idxBuf.data(),
+                                                                 impl->scoreBuf.data(), &count);
     if (rc != MI355REC_OK) {
-        std::cerr << "Error: " << mi355rec_sharded_last_error(impl_->engine) << std::endl;
+        std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
         return {};
     }
     std::vector<int> results(static_cast<size_t>(count));
-    for (int i = 0; i < count; ++i) results[i] = static_cast<int>(impl_->idxBuf[i]);
-    impl_->lastScores.assign(impl_->scoreBuf.begin(), impl_->scoreBuf.begin() + count);
+    for (int i = 0; i < count; ++i) results[i] = static_cast<int>(impl->idxBuf[i]);
+    impl->lastScores.assign(impl->scoreBuf.begin(), impl->scoreBuf.begin() + count);
     return results;
+}
+
+}  // namespace
+
+std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<int>& alsoExclude) {
+    return playlistQuery(impl_, songIndices, topN, alsoExclude, nullptr);
+}
+
+std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<FeatureRange>& where,
+                                                   const std::vector<int>& alsoExclude) {
+    mi355rec_filter_t f;
+    if (!makeFilter(where, f)) return {};
+    return playlistQuery(impl_, songIndices, topN, alsoExclude, &f);
+}
+
+std::vector<int> Recommender::recommendByIndexWhere(int songIndex, int topN, const std::vector<FeatureRange>& where) {
+    if (!checkQuery(impl_, songIndex, topN)) return {};
+    mi355rec_filter_t f;
+    if (!makeFilter(where, f)) return {};
+    return playlistQuery(impl_, {songIndex}, topN, {}, &f);
 }
 
 std::vector<int> Recommender::recommend(const std::string& trackId, int topN) {  // :356-363

@@ -1,5 +1,6 @@
 // cpu_backend.cpp — see cpu_backend.h.  Own code; arithmetic contract: Recommender.cu:256-273, selection: :293-315.
 #include "cpu_backend.h"
+#include "filter_check.h"
 
 #include <omp.h>
 
@@ -367,7 +368,7 @@ int node_query_labels(Node* h, const float* q12, int64_t exclude, const int32_t*
 }
 
 int node_query_mean(Node* h, const float* members, int k, const int64_t* exclude, int n_exclude, int topn_asked, int64_t* out_idx,
-                    float* out_score, int* out_count, const char** why) {
+                    float* out_score, int* out_count, const char** why, const mi355rec_filter_t* filter) {
     const Catalogue* c = h->cat;
     const int64_t n = c->n;
     std::vector<float> qn(static_cast<size_t>(k));
@@ -394,7 +395,15 @@ int node_query_mean(Node* h, const float* members, int k, const int64_t* exclude
     }
     for (int64_t e : excl)
         if (e >= 0 && e < n) keys[static_cast<size_t>(e)] = 0;   // (a real key is never 0: its low half is ~row)
-    const int64_t avail = n - static_cast<int64_t>(std::count_if(excl.begin(), excl.end(), [n](int64_t e) { return e >= 0 && e < n; }));
+    int64_t avail = n - static_cast<int64_t>(std::count_if(excl.begin(), excl.end(), [n](int64_t e) { return e >= 0 && e < n; }));
+    if (filter && filter->active) {   // the rows failing the filter go like excluded ones
+        avail = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            uint64_t& key = keys[static_cast<size_t>(i)];
+            if (key != 0 && !mi355filter::pass(filter, f + i * kDim)) key = 0;
+            avail += key != 0;
+        }
+    }
     const int count = static_cast<int>(topn_asked < avail ? topn_asked : avail);
     std::partial_sort(keys.begin(), keys.begin() + count, keys.end(), std::greater<uint64_t>());
     for (int i = 0; i < topn_asked; ++i) {

@@ -17,6 +17,8 @@
 
 #include <cstdint>
 
+#include "mi355rec_diag.h"
+
 namespace mi355cpu {
 
 struct Catalogue;
@@ -58,9 +60,10 @@ int node_set_labels(Node* h, const int32_t* labels, int64_t n, const char** why)
 int node_query_labels(Node* h, const float* q12, int64_t exclude, const int32_t* set, int n_set, int topn, int64_t* out_idx,
                       float* out_score, int* out_count, const char** why);
 // PLAYLISTS (include/mi355rec_diag.h): the top-N rows by the mean of their scores against members[0..k) (k x 12), the
-// rows of exclude[0..n_exclude) (global ids, validated by the caller) left out.
+// rows of exclude[0..n_exclude) (global ids, validated by the caller) left out; filter: null, or a feature filter (checked
+// by the caller, include/mi355rec_diag.h "FEATURE FILTERS") that every returned row passes.
 int node_query_mean(Node* h, const float* members, int k, const int64_t* exclude, int n_exclude, int topn, int64_t* out_idx,
-                    float* out_score, int* out_count, const char** why);
+                    float* out_score, int* out_count, const char** why, const mi355rec_filter_t* filter = nullptr);
 int node_set_window(Node* h, int window, const char** why);
 int node_enqueue(Node* h, const float* q12, int64_t exclude, int topn, int64_t* ticket, const char** why);
 int node_flush(Node* h);

@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "engine_labels.hip.h"
+#include "filter_check.h"
 #include "playlist.hip.h"
 
 // What the first playlist call of a handle allocates.
@@ -58,9 +59,11 @@ int ensure_playlist(mi355rec* h) {
 
 // One playlist query, synchronously.  members: k x 12 floats on the host, or null with `local_rows` (k rows of this shard,
 // excluded by their global ids).  exclude_global[0..n_exclude): global ids, any order, duplicates allowed; ids of other
-// shards match nothing here.
+// shards match nothing here.  filter: null, or the feature filter (include/mi355rec_diag.h, "FEATURE FILTERS"); null and
+// active == 0 launch exactly the unfiltered call.
 int sync_playlist_query(mi355rec* h, const float* members, const int64_t* local_rows, int k, const int64_t* exclude_global,
-                        int n_exclude, int topn, int64_t* out_idx, float* out_score, int* out_count, int max_exclude = kMaxExclude) {
+                        int n_exclude, int topn, int64_t* out_idx, float* out_score, int* out_count, int max_exclude = kMaxExclude,
+                        const mi355rec_filter_t* filter = nullptr) {
     if (!out_idx) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     if (k < 1 || k > kMaxPlaylist) return fail(h, MI355REC_ERR_INVALID_ARG, "playlist of %d songs: 1 to %d are supported", k, kMaxPlaylist);
     if (!members && !local_rows) return fail(h, MI355REC_ERR_INVALID_ARG, "null playlist");
@@ -76,6 +79,10 @@ int sync_playlist_query(mi355rec* h, const float* members, const int64_t* local_
         for (int m = 0; m < k; ++m)
             if (local_rows[m] < 0 || local_rows[m] >= h->n)
                 return fail(h, MI355REC_ERR_INVALID_ARG, "Invalid song index: %lld", (long long)local_rows[m]);
+    if (filter) {
+        char why[128];
+        if (mi355filter::invalid(filter, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    }
     DeviceGuard guard(h->device);
     int rc = ensure_playlist(h);
     if (rc) return rc;
@@ -104,6 +111,11 @@ int sync_playlist_query(mi355rec* h, const float* members, const int64_t* local_
     arg.k = k;
     arg.n_excl = n_excl;
     arg.by_row = local_rows ? 1 : 0;
+    arg.active = filter ? filter->active : 0u;
+    if (arg.active) {
+        std::memcpy(b->lo, filter->lo, sizeof b->lo);
+        std::memcpy(b->hi, filter->hi, sizeof b->hi);
+    }
     if (local_rows) std::memcpy(b->rows, local_rows, sizeof(int64_t) * static_cast<size_t>(k));
     else std::memcpy(b->members, members, sizeof(float) * kDim * static_cast<size_t>(k));
     rc = ensure_slots(h, static_cast<size_t>(eff));
@@ -154,9 +166,10 @@ int sync_playlist_query(mi355rec* h, const float* members, const int64_t* local_
 
 namespace mi355node {
 int query_mean_topn(mi355rec_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude, int topn,
-                    int64_t* out_idx, float* out_score, int* out_count) {
+                    int64_t* out_idx, float* out_score, int* out_count, const mi355rec_filter_t* filter) {
     if (!h || !queries) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    return sync_playlist_query(h, queries, nullptr, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count, kPlExcludeCap);
+    return sync_playlist_query(h, queries, nullptr, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count, kPlExcludeCap,
+                               filter);
 }
 }  // namespace mi355node
 
@@ -172,6 +185,21 @@ int mi355rec_query_playlist_topn(mi355rec_t* h, const int64_t* local_rows, int k
                                  int topn, int64_t* out_idx, float* out_score, int* out_count) {
     if (!h || !local_rows) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     return sync_playlist_query(h, nullptr, local_rows, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count);
+}
+
+int mi355rec_query_mean_topn_where(mi355rec_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude,
+                                   const mi355rec_filter_t* filter, int topn, int64_t* out_idx, float* out_score, int* out_count) {
+    if (!h || !queries) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    return sync_playlist_query(h, queries, nullptr, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count, kMaxExclude,
+                               filter);
+}
+
+int mi355rec_query_playlist_topn_where(mi355rec_t* h, const int64_t* local_rows, int k, const int64_t* exclude_global,
+                                       int n_exclude, const mi355rec_filter_t* filter, int topn, int64_t* out_idx, float* out_score,
+                                       int* out_count) {
+    if (!h || !local_rows) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    return sync_playlist_query(h, nullptr, local_rows, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count, kMaxExclude,
+                               filter);
 }
 
 int mi355rec_playlist_counters(const mi355rec_t* h, int64_t* queries, int64_t* rows_exact) {

@@ -9,6 +9,8 @@
 //   recommender --id "<track_id>" [-n N]
 //   ... either query mode with one or more --genre NAME: recommendations only from those genres (extension)
 //   recommender --playlist "<track_id>,<track_id>,..." [-n N]: what goes with a playlist of up to 32 songs (extension)
+//   ... --song, --id and --playlist with one or more --where NAME=LO:HI: only songs whose feature NAME lies in [LO, HI]
+//       (normalised units; extension; not with --genre)
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -30,7 +32,48 @@ static void usage(const char* prog) {
               << "2. Recommendation Mode (by song name):\n   " << prog << " --song \"Song Name\" [-n N]\n"
               << "   Returns top N similar songs (default N=10).\n\n"
               << "3. Recommendation Mode (by track ID):\n   " << prog << " --id \"track_id\" [-n N]\n"
-              << "   Returns top N similar songs (default N=10).\n" << std::endl;
+              << "   Returns top N similar songs (default N=10).\n\n"
+              << "Filter (extension): --where NAME=LO:HI, repeatable, with --song, --id or --playlist (not with --genre):\n"
+              << "   only songs whose feature NAME lies in [LO, HI].  NAME is a CSV feature column (danceability, energy, key, loudness,\n"
+              << "   mode, speechiness, acousticness, instrumentalness, liveness, valence, tempo); LO and HI are in the\n"
+              << "   normalised [0, 1] units songs_data.bin holds (min-max over the CSV), not raw BPM or dB.\n" << std::endl;
+}
+
+// --where NAME=LO:HI, any number of times from argv[first]: the ranges (feature indices in Song.h order).  false, with a
+// message, on a malformed option or an unknown NAME.
+static bool parseWhere(int argc, char* argv[], int first, std::vector<Recommender::FeatureRange>& ranges) {
+    static const char* const kNames[] = {"danceability", "energy", "key", "loudness", "mode", "speechiness",
+                                         "acousticness", "instrumentalness", "liveness", "valence", "tempo"};
+    for (int i = first; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--where") != 0) continue;
+        if (i + 1 >= argc) {
+            std::cerr << "Error: --where needs NAME=LO:HI" << std::endl;
+            return false;
+        }
+        const std::string arg = argv[++i];
+        const size_t eq = arg.find('='), colon = arg.find(':', eq == std::string::npos ? 0 : eq);
+        if (eq == std::string::npos || colon == std::string::npos) {
+            std::cerr << "Error: --where '" << arg << "': expected NAME=LO:HI" << std::endl;
+            return false;
+        }
+        const std::string name = arg.substr(0, eq), lo = arg.substr(eq + 1, colon - eq - 1), hi = arg.substr(colon + 1);
+        int feature = -1;
+        for (int j = 0; j < 11; ++j)
+            if (name == kNames[j]) feature = j;
+        if (feature < 0) {
+            std::cerr << "Error: --where: unknown feature '" << name << "'" << std::endl;
+            return false;
+        }
+        char* end1 = nullptr;
+        char* end2 = nullptr;
+        const float l = std::strtof(lo.c_str(), &end1), h = std::strtof(hi.c_str(), &end2);
+        if (lo.empty() || hi.empty() || *end1 != '\0' || *end2 != '\0') {
+            std::cerr << "Error: --where '" << arg << "': LO and HI must be numbers" << std::endl;
+            return false;
+        }
+        ranges.push_back({feature, l, h});
+    }
+    return true;
 }
 
 static bool preprocessMode(const std::string& csvPath) {  // main.cpp:33-44
@@ -58,6 +101,33 @@ static std::string lowered(std::string s) {
     return s;
 }
 
+// The query song's row by the engine's rules (exact id / exact name, then substring); -1 if none.
+static int findQuery(const DataManager::Catalogue& catalogue, const std::string& query, bool isTrackId) {
+    int index = -1;
+    if (isTrackId) {
+        for (size_t i = 0; i < catalogue.size() && index < 0; ++i)
+            if (catalogue.trackIds[i] == query) index = static_cast<int>(i);
+    } else {
+        const std::string needle = lowered(query);
+        for (size_t i = 0; i < catalogue.size() && index < 0; ++i)
+            if (lowered(catalogue.trackNames[i]) == needle) index = static_cast<int>(i);
+        for (size_t i = 0; i < catalogue.size() && index < 0; ++i)
+            if (lowered(catalogue.trackNames[i]).find(needle) != std::string::npos) index = static_cast<int>(i);
+    }
+    return index;
+}
+
+// --where: the songs within every range, ranked as recommendByIndex ranks the whole catalogue.
+static void whereRecommendations(Recommender& recommender, const DataManager::Catalogue& catalogue, const std::string& query,
+                                 bool isTrackId, int topN, const std::vector<Recommender::FeatureRange>& ranges, std::vector<int>& recs) {
+    const int index = findQuery(catalogue, query, isTrackId);
+    if (index < 0) {
+        std::cerr << "Error: Song with " << (isTrackId ? "track_id" : "name") << " '" << query << "' not found" << std::endl;
+        return;   // (no recommendations: the caller says so)
+    }
+    recs = recommender.recommendByIndexWhere(index, topN, ranges);
+}
+
 // --genre: the songs whose genre is one of `genres` (names matched case-insensitively), ranked as recommendByIndex
 // ranks the whole catalogue; the query song is found by the engine's rules (exact id / exact name, then substring).
 static bool genreRecommendations(Recommender& recommender, const DataManager::Catalogue& catalogue, const std::string& query,
@@ -73,17 +143,7 @@ static bool genreRecommendations(Recommender& recommender, const DataManager::Ca
         }
         ids.push_back(id);
     }
-    int index = -1;
-    if (isTrackId) {
-        for (size_t i = 0; i < catalogue.size() && index < 0; ++i)
-            if (catalogue.trackIds[i] == query) index = static_cast<int>(i);
-    } else {
-        const std::string needle = lowered(query);
-        for (size_t i = 0; i < catalogue.size() && index < 0; ++i)
-            if (lowered(catalogue.trackNames[i]) == needle) index = static_cast<int>(i);
-        for (size_t i = 0; i < catalogue.size() && index < 0; ++i)
-            if (lowered(catalogue.trackNames[i]).find(needle) != std::string::npos) index = static_cast<int>(i);
-    }
+    const int index = findQuery(catalogue, query, isTrackId);
     if (index < 0) {
         std::cerr << "Error: Song with " << (isTrackId ? "track_id" : "name") << " '" << query << "' not found" << std::endl;
         return true;   // (no recommendations: the caller says so)
@@ -96,8 +156,8 @@ static bool genreRecommendations(Recommender& recommender, const DataManager::Ca
     return true;
 }
 
-static bool recommendationMode(const std::string& query, bool isTrackId, int topN,
-                               const std::vector<std::string>& genres) {  // main.cpp:46-131
+static bool recommendationMode(const std::string& query, bool isTrackId, int topN, const std::vector<std::string>& genres,
+                               const std::vector<Recommender::FeatureRange>& ranges) {  // main.cpp:46-131
     std::cout << "=== RECOMMENDATION MODE ===" << std::endl;
     DataManager::Catalogue catalogue;
     if (!DataManager::loadCatalogue(kBinaryDataFile, catalogue)) {
@@ -115,13 +175,15 @@ static bool recommendationMode(const std::string& query, bool isTrackId, int top
     int queryIndex = -1;
     if (isTrackId) {
         std::cout << "\nSearching for track ID: " << query << std::endl;
-        if (genres.empty()) recs = recommender.recommend(query, topN);
+        if (!ranges.empty()) whereRecommendations(recommender, catalogue, query, true, topN, ranges, recs);
+        else if (genres.empty()) recs = recommender.recommend(query, topN);
         else if (!genreRecommendations(recommender, catalogue, query, true, topN, genres, recs)) return false;
         for (size_t i = 0; i < catalogue.size(); ++i)
             if (catalogue.trackIds[i] == query) { queryIndex = static_cast<int>(i); break; }
     } else {
         std::cout << "\nSearching for song: " << query << std::endl;
-        if (genres.empty()) recs = recommender.recommendByName(query, topN);
+        if (!ranges.empty()) whereRecommendations(recommender, catalogue, query, false, topN, ranges, recs);
+        else if (genres.empty()) recs = recommender.recommendByName(query, topN);
         else if (!genreRecommendations(recommender, catalogue, query, false, topN, genres, recs)) return false;
         // The reference finds the song it DISPLAYS with a single exact-or-substring
         // pass (main.cpp:85-95), not the engine's exact-then-substring rule; kept.
@@ -162,7 +224,7 @@ static bool recommendationMode(const std::string& query, bool isTrackId, int top
 
 // --playlist: the songs most similar on average to the playlist's (exact track ids, the first row of an id as for --id),
 // the playlist's own songs never among them.
-static bool playlistMode(const std::string& list, int topN) {
+static bool playlistMode(const std::string& list, int topN, const std::vector<Recommender::FeatureRange>& ranges) {
     std::cout << "=== PLAYLIST MODE ===" << std::endl;
     std::vector<std::string> ids;
     for (size_t start = 0; start <= list.size();) {
@@ -197,7 +259,8 @@ static bool playlistMode(const std::string& list, int topN) {
         return false;
     }
     std::map<int, std::string>& genreMap = catalogue.genreMap;
-    const std::vector<int> recs = recommender.recommendForPlaylist(members, topN);
+    const std::vector<int> recs = ranges.empty() ? recommender.recommendForPlaylist(members, topN)
+                                                 : recommender.recommendForPlaylist(members, topN, ranges, {});
     if (recs.empty()) {
         std::cerr << "No recommendations found. Please check the query." << std::endl;
         return false;
@@ -269,7 +332,13 @@ int main(int argc, char* argv[]) {
             }
             genres.push_back(argv[++i]);
         }
-        return recommendationMode(argv[2], mode == "--id", topN, genres) ? 0 : 1;
+        std::vector<Recommender::FeatureRange> ranges;
+        if (!parseWhere(argc, argv, 3, ranges)) return 1;
+        if (!ranges.empty() && !genres.empty()) {
+            std::cerr << "Error: --where cannot be combined with --genre" << std::endl;
+            return 1;
+        }
+        return recommendationMode(argv[2], mode == "--id", topN, genres, ranges) ? 0 : 1;
     }
     if (mode == "--playlist") {
         if (argc < 3) {
@@ -287,7 +356,9 @@ int main(int argc, char* argv[]) {
                 break;
             }
         }
-        return playlistMode(argv[2], topN) ? 0 : 1;
+        std::vector<Recommender::FeatureRange> ranges;
+        if (!parseWhere(argc, argv, 3, ranges)) return 1;
+        return playlistMode(argv[2], topN, ranges) ? 0 : 1;
     }
     std::cerr << "Error: Unknown mode '" << mode << "'" << std::endl;
     usage(argv[0]);

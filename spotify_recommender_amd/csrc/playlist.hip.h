@@ -40,6 +40,20 @@
 // it is read, so no ordering is needed; on a catalogue of clusters the workgroups that hold the members' cluster lend
 // their threshold to all the others.
 //
+// FEATURE FILTER (include/mi355rec_diag.h, "FEATURE FILTERS").  PlaylistArg::active (bit j: feature j constrained) and
+// PlaylistBuf::lo / hi: a row x is admissible iff lo[j] <= x[j] && x[j] <= hi[j] for every active j, on the fp32 row of the
+// matrix (IEEE compares: a NaN feature fails).  The 8-bit replica only rules rows out by similarity, so the pre-filter,
+// its margin and the bound above are unchanged; the predicate is applied where an fp32 row is read:
+//   * anchors: the anchor table's copy only CHOOSES the rows (rows failing the filter there are not picked); the rows read
+//     from the matrix that fail are dropped like excluded ones, so the starting threshold is the topk-th best key among
+//     admissible rows;
+//   * scan: a lane whose quad still holds rows (after the pre-filter, or every row on the exact path and for 0x80 rows)
+//     requests the quad's four fp32 rows together, drops the held ones that fail, and only then runs the K chains on the
+//     rest: a rejected row costs one load and a few compares.
+// So keys are only ever formed for admissible rows, and the rule above (the k-th best among ANY k admissible, not excluded
+// rows bounds the answer) keeps every workgroup's threshold and the shared atomicMax valid.  rows_exact then counts every
+// row read from the fp32 matrix (rejected ones included).  active == 0 takes none of these branches (uniform tests).
+//
 // EXCLUSION.  The excluded global ids (members and the caller's list, sorted and deduplicated on the host, at most
 // kPlExcludeCap) sit in LDS as uint32; only a key that already beats the workgroup's threshold is looked up (binary
 // search), so the hot loop does not change.
@@ -69,6 +83,8 @@ using PlaylistCfg = Q8Cfg<512, 4, 1>;                       // kBlock, kMinWaves
 struct PlaylistBuf {
     float members[kMaxPlaylist][kDim];
     int64_t rows[kMaxPlaylist];
+    float lo[kDim];                  // the feature filter's bounds (read only where PlaylistArg::active has bit j)
+    float hi[kDim];
     unsigned long long shared_thr;   // the best threshold any workgroup of the launch has found (0 from the host)
     uint32_t excl[kPlExcludeCap];   // sorted, distinct global ids (only those of this shard)
 };
@@ -77,7 +93,18 @@ struct PlaylistArg {
     int k;            // members
     int n_excl;       // entries of PlaylistBuf::excl
     int by_row;       // 1: member m is the shard's row PlaylistBuf::rows[m]; 0: PlaylistBuf::members[m]
+    uint32_t active;  // the feature filter: bit j (j < kDim) constrains feature j; 0: no filter
 };
+
+// The feature filter's predicate on one fp32 row (active: uniform; unrolled, so no feature is indexed at run time).
+__device__ __forceinline__ bool filter_pass(const Row& r, uint32_t active, const float* __restrict__ lo, const float* __restrict__ hi) {
+    const float f[kDim] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.c.x, r.c.y, r.c.z, r.c.w};
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < kDim; ++j)
+        if (active & (1u << j)) ok = ok && lo[j] <= f[j] && f[j] <= hi[j];   // (false for a NaN feature)
+    return ok;
+}
 
 // cosine_score with the row's norm sqrtf(sum f_j^2) taken once for all members: the same operations in the same order.
 __device__ __forceinline__ float cosine_with_norm(const float* __restrict__ q, float qn, const Row& r, float rn) {
@@ -120,7 +147,7 @@ __device__ __forceinline__ bool playlist_excluded(const uint32_t* s_excl, int n_
 }
 
 // q8: the handle's 8-bit replica, or null (every row exact).  anchors: the anchor table, or null (no starting threshold).
-// rows_exact: += the rows whose K chains this launch computed.
+// rows_exact: += the rows whose K chains this launch computed; with a filter, every fp32 row read (rejected ones included).
 __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void playlist_scan_kernel(
     const float* __restrict__ feats, const uint4* __restrict__ q8, int64_t n, int64_t row_base, const PlaylistBuf* __restrict__ buf,
     PlaylistArg arg, const float* __restrict__ anchors, int topk, uint64_t* __restrict__ block_lists,
@@ -142,6 +169,9 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     const int lane = tid & 63;
     const int k = arg.k;
     const int n_excl = arg.n_excl;
+    const uint32_t active = arg.active;
+    const float* const f_lo = buf->lo;
+    const float* const f_hi = buf->hi;
 
     // ---- members and excluded ids into LDS; the members' norms and whether the bound can be claimed for them
     for (int i = tid; i < k * kDim; i += kBlock)
@@ -188,11 +218,26 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
             const int i = r * kBlock + tid;
             const Row a = load_row(anchors, static_cast<int64_t>(i));
             mine[r] = i < n_anchor ? pack_key(cosine_score(u, un, a), static_cast<uint32_t>(i)) : 0ull;
+            if (active && !filter_pass(a, active, f_lo, f_hi)) mine[r] = 0ull;   // (only chooses: re-checked on the matrix's row)
         }
-        const uint64_t t = block_select_threshold<kBlock, kPer>(mine, kPlBoundRows, true, 0, s_sel);
+        int n_cand = kPlBoundRows;   // anchors left to choose from: all of them without a filter
+        if (active) {   // uniform
+#pragma unroll
+            for (int r = 0; r < kPer; ++r) {
+                const uint64_t have = __ballot(mine[r] != 0ull);
+                if (lane == 0 && have) atomicAdd(&s_count, __popcll(have));
+            }
+            __syncthreads();
+            n_cand = s_count;
+            __syncthreads();
+            if (tid == 0) s_count = 0;
+            __syncthreads();
+        }
+        // (fewer than kPlBoundRows candidates: keep them all)
+        const uint64_t t = n_cand >= kPlBoundRows ? block_select_threshold<kBlock, kPer>(mine, kPlBoundRows, true, 0, s_sel) : 1ull;
         int* const s_pick = reinterpret_cast<int*>(s_cand);
 #pragma unroll
-        for (int r = 0; r < kPer; ++r) {   // (uniform loop) exactly kPlBoundRows keys are >= t
+        for (int r = 0; r < kPer; ++r) {   // (uniform loop) exactly kPlBoundRows keys are >= t, or all n_cand < kPlBoundRows
             const bool keep = mine[r] != 0ull && mine[r] >= t;
             const uint64_t who = __ballot(keep);
             int base = 0;
@@ -209,7 +254,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
             const float m = playlist_mean(s_mem, s_qn, k, x);
             ++n_exact;
             const uint32_t g = static_cast<uint32_t>(row_base + row);
-            key = playlist_excluded(s_excl, n_excl, g) ? 0ull : pack_key(m, g);
+            key = playlist_excluded(s_excl, n_excl, g) || (active && !filter_pass(x, active, f_lo, f_hi)) ? 0ull : pack_key(m, g);
         }
         const uint64_t have = __ballot(key != 0ull);
         __syncthreads();   // (every thread has read s_count and s_pick)
@@ -272,12 +317,24 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
             for (int u4 = 0; u4 < 4; ++u4)
                 if (!(special[u4] || a[u4] >= cut_d)) mask &= ~(1u << u4);
         }
+        if (active && mask != 0u) {   // (active uniform) the filter on the fp32 rows left, before any chain
+            // the quad's four rows are requested together (one memory round trip, not four); rows past n read row n - 1
+            Row x[4];
+#pragma unroll
+            for (int u4 = 0; u4 < 4; ++u4) x[u4] = load_row(feats, r0 + u4 < n ? r0 + u4 : n - 1);
+#pragma unroll
+            for (int u4 = 0; u4 < 4; ++u4)
+                if (mask & (1u << u4)) {
+                    ++n_exact;
+                    if (!filter_pass(x[u4], active, f_lo, f_hi)) mask &= ~(1u << u4);
+                }
+        }
         while (__ballot(mask != 0u)) {   // uniform
             const bool have = mask != 0u;
             const int64_t r = have ? r0 + __builtin_ctz(mask) : 0;
             const Row x = load_row(feats, r);
             const float m = playlist_mean(s_mem, s_qn, k, x);
-            n_exact += have ? 1 : 0;
+            n_exact += (have && !active) ? 1 : 0;   // (with a filter every row read was counted above)
             const uint32_t g = static_cast<uint32_t>(row_base + r);
             const uint64_t key = have ? pack_key(m, g) : 0ull;
             bool pass = key > thr;

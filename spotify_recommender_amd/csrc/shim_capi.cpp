@@ -184,6 +184,26 @@ int64_t shim_recommend_for_playlist(void* h, const int* songs, int n_songs, int 
                                                    std::vector<int>(exclude, exclude + (n_exclude > 0 ? n_exclude : 0))),
                     out, scores, cap);
 }
+// Recommender::recommendByIndexWhere and the filtered recommendForPlaylist: n_ranges ranges (features[i], lo[i], hi[i]).
+static std::vector<Recommender::FeatureRange> ranges(const int* features, const float* lo, const float* hi, int n_ranges) {
+    std::vector<Recommender::FeatureRange> r;
+    for (int i = 0; i < n_ranges; ++i) r.push_back({features[i], lo[i], hi[i]});
+    return r;
+}
+int64_t shim_recommend_by_index_where(void* h, int idx, int topn, const int* features, const float* lo, const float* hi, int n_ranges,
+                                      int* out, float* scores, int64_t cap) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    return giveBack(c, c->rec.recommendByIndexWhere(idx, topn, ranges(features, lo, hi, n_ranges)), out, scores, cap);
+}
+int64_t shim_recommend_for_playlist_where(void* h, const int* songs, int n_songs, int topn, const int* features, const float* lo,
+                                          const float* hi, int n_ranges, const int* exclude, int n_exclude, int* out, float* scores,
+                                          int64_t cap) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    return giveBack(c, c->rec.recommendForPlaylist(std::vector<int>(songs, songs + (n_songs > 0 ? n_songs : 0)), topn,
+                                                   ranges(features, lo, hi, n_ranges),
+                                                   std::vector<int>(exclude, exclude + (n_exclude > 0 ? n_exclude : 0))),
+                    out, scores, cap);
+}
 int shim_similarities(void* h, int idx, float* out_n) {
     Catalogue* c = static_cast<Catalogue*>(h);
     std::vector<float> v;

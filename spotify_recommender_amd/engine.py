@@ -51,6 +51,38 @@ def _playlist_query(fn, h, check, members, exclude, topn: int) -> Tuple[np.ndarr
     return idx[:count.value].copy(), score[:count.value].copy()
 
 
+def make_filter(where) -> capi.Filter:
+    """mi355rec_filter_t from a `where=` mapping {feature index (0..11) or name (capi.FEATURE_NAMES): (lo, hi)}: a row passes
+    iff lo <= x[j] <= hi for every named feature (the stored fp32 values, e.g. [0, 1] for the drop-in's normalised
+    catalogue).  A feature named twice (by index and by name) keeps the intersection of its ranges; an empty intersection
+    is passed on as lo > hi, which the library refuses."""
+    f = capi.Filter()
+    for j in range(capi.DIM):
+        f.lo[j], f.hi[j] = -np.inf, np.inf
+    for key, rng in dict(where).items():
+        if isinstance(key, str):
+            if key.lower() not in capi.FEATURE_NAMES:
+                raise ValueError(f"unknown feature {key!r}: one of {', '.join(capi.FEATURE_NAMES)}")
+            j = capi.FEATURE_NAMES.index(key.lower())
+        else:
+            j = int(key)
+            if not 0 <= j < capi.DIM:
+                raise ValueError(f"feature index {j} out of [0, {capi.DIM})")
+        lo, hi = (float(np.float32(v)) for v in rng)
+        if f.active & (1 << j):
+            lo, hi = max(lo, f.lo[j]), min(hi, f.hi[j])
+        f.active |= 1 << j
+        f.lo[j], f.hi[j] = lo, hi
+    return f
+
+
+def _where_query(fn, h, check, members, exclude, where, topn: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Runs one filtered playlist entry point: fn(h, members, k, exclude, n_exclude, &filter, topn, idx, score, &count)."""
+    flt = make_filter(where)
+    return _playlist_query(lambda h_, m, k, e, n_e, *rest: fn(h_, m, k, e, n_e, ctypes.byref(flt), *rest), h, check, members,
+                           exclude, topn)
+
+
 def _np_members(queries) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(queries, dtype=np.float32).reshape(-1, capi.DIM))
 
@@ -400,15 +432,22 @@ class CosineEngine:
 
 
     # ---- PLAYLISTS (include/mi355rec_diag.h): top-N by the mean score against up to 32 songs ----
-    def query_mean_topn(self, queries, topn: int, exclude=None) -> Tuple[np.ndarray, np.ndarray]:
-        """The best `topn` rows by the mean of their scores against the rows of `queries` (k x 12); `exclude`: global ids."""
-        return _playlist_query(self._lib.mi355rec_query_mean_topn, self._h, lambda rc: capi.check(rc, self._h),
-                               _np_members(queries), exclude, topn)
+    def query_mean_topn(self, queries, topn: int, exclude=None, where=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The best `topn` rows by the mean of their scores against the rows of `queries` (k x 12); `exclude`: global ids.
+        `where`: {feature index or name: (lo, hi)}, only rows within every range are returned (FEATURE FILTERS; a
+        filtered single query is k = 1); None calls the unfiltered entry point."""
+        check = lambda rc: capi.check(rc, self._h)   # noqa: E731
+        if where is not None:
+            return _where_query(self._lib.mi355rec_query_mean_topn_where, self._h, check, _np_members(queries), exclude, where, topn)
+        return _playlist_query(self._lib.mi355rec_query_mean_topn, self._h, check, _np_members(queries), exclude, topn)
 
-    def query_playlist_topn(self, local_rows, topn: int, exclude=None) -> Tuple[np.ndarray, np.ndarray]:
+    def query_playlist_topn(self, local_rows, topn: int, exclude=None, where=None) -> Tuple[np.ndarray, np.ndarray]:
         """The same for members given as rows of this handle; the members are never returned."""
-        return _playlist_query(self._lib.mi355rec_query_playlist_topn, self._h, lambda rc: capi.check(rc, self._h),
-                               _np_rows(local_rows), exclude, topn)
+        check = lambda rc: capi.check(rc, self._h)   # noqa: E731
+        if where is not None:
+            return _where_query(self._lib.mi355rec_query_playlist_topn_where, self._h, check, _np_rows(local_rows), exclude, where,
+                                topn)
+        return _playlist_query(self._lib.mi355rec_query_playlist_topn, self._h, check, _np_rows(local_rows), exclude, topn)
 
     def playlist_counters(self) -> dict:
         q, r = ctypes.c_int64(0), ctypes.c_int64(0)
@@ -531,10 +570,16 @@ class NodeEngine:
                              (q.ctypes.data_as(ctypes.c_void_p), int(exclude_global)), labels, topn)
 
     # ---- PLAYLISTS (include/mi355rec_diag.h) over the whole node ----
-    def query_mean_topn(self, queries, topn: int, exclude=None) -> Tuple[np.ndarray, np.ndarray]:
+    def query_mean_topn(self, queries, topn: int, exclude=None, where=None) -> Tuple[np.ndarray, np.ndarray]:
+        if where is not None:
+            return _where_query(self._lib.mi355rec_sharded_query_mean_topn_where, self._h, self._check, _np_members(queries), exclude,
+                                where, topn)
         return _playlist_query(self._lib.mi355rec_sharded_query_mean_topn, self._h, self._check, _np_members(queries), exclude, topn)
 
-    def query_playlist_topn(self, global_rows, topn: int, exclude=None) -> Tuple[np.ndarray, np.ndarray]:
+    def query_playlist_topn(self, global_rows, topn: int, exclude=None, where=None) -> Tuple[np.ndarray, np.ndarray]:
+        if where is not None:
+            return _where_query(self._lib.mi355rec_sharded_query_playlist_topn_where, self._h, self._check, _np_rows(global_rows),
+                                exclude, where, topn)
         return _playlist_query(self._lib.mi355rec_sharded_query_playlist_topn, self._h, self._check, _np_rows(global_rows), exclude,
                                topn)
 
