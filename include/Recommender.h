@@ -102,6 +102,19 @@ public:
     std::vector<int> recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<FeatureRange>& where,
                                           const std::vector<int>& alsoExclude);
 
+    // Extension: weighted playlists (likes and dislikes).  The overload of recommendForPlaylist takes one weight per song of
+    // songIndices, of any sign: a song's similarity counts w times, a negative weight pushes results away from that song,
+    // and the score is sum(w_k * similarity_k) / sum(|w_k|), in [-1, 1] (lastScores()).  The playlist's songs are never
+    // returned, whatever their weight.  `where` and `alsoExclude` as above (both may be empty).  A weight list whose length
+    // differs from the songs', a NaN or infinite weight, |w| > 1e6 or weights that are all zero give {} and a message.
+    // recommendForTaste is the common case: the liked songs at weight +1, the disliked ones at -dislikeWeight
+    // (dislikeWeight >= 0; liked.size() + disliked.size() <= 32, at least one liked song).
+    std::vector<int> recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
+                                          const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude);
+    std::vector<int> recommendForTaste(const std::vector<int>& liked, const std::vector<int>& disliked, int topN,
+                                       float dislikeWeight = 0.5f, const std::vector<FeatureRange>& where = {},
+                                       const std::vector<int>& alsoExclude = {});
+
     struct Impl;   // opaque: defined in Recommender.cpp
 
 private:

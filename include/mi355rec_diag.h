@@ -18,6 +18,8 @@
  *     list (mi355rec_query_mean_topn, _query_playlist_topn, _playlist_counters and their node-handle twins);
  *   - FEATURE FILTERS, on the playlist calls: only rows whose audio features lie within given bounds are returned
  *     (mi355rec_query_mean_topn_where, _query_playlist_topn_where and their node-handle twins);
+ *   - WEIGHTED PLAYLISTS: a signed weight per member, likes and dislikes
+ *     (mi355rec_query_mean_topn_weighted, _query_playlist_topn_weighted and their node-handle twins);
  *   - test hooks, compiled in only with -DMI355REC_TEST_HOOKS (spotify_recommender_amd/build.py builds
  *     libmi355rec_testhooks.so for tests/; the product library does not export them).
  */
@@ -448,6 +450,37 @@ int mi355rec_sharded_query_mean_topn_where(mi355rec_sharded_t* h, const float* q
 int mi355rec_sharded_query_playlist_topn_where(mi355rec_sharded_t* h, const int64_t* global_rows, int k,
                                                const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
                                                int topn, int64_t* out_idx, float* out_score, int* out_count);
+
+/* WEIGHTED PLAYLISTS (an extension beyond the reference): "more like these, less like those", recency weights, one seed
+ * song coloured by others.  The _weighted calls are the _where calls above plus `weights`: k floats on the host, one per
+ * member, of any sign.  With c_k the score mi355rec_query_topn gives a row for member k (bit for bit),
+ *     W        = fl(...fl(|w_0| + |w_1|) + ... + |w_{k-1}|)                                   (fp32, member order)
+ *     score(x) = fl( fl(...fl( fl(w_0 c_0) + fl(w_1 c_1) ) + ... + fl(w_{k-1} c_{k-1}) ) / W )
+ * in fp32, member order, multiply then add (never fused), one IEEE divide; scores lie in [-1, 1].  Everything else is the
+ * playlist contract: canonical order (score descending, then row ascending, -0.0 reported as +0.0), member rows excluded
+ * on by-row calls WHATEVER their weight (zero and negative weights too), up to MI355REC_MAX_EXCLUDE further ids, the
+ * optional filter, count = min(topn, |admissible rows|), topn <= 1024.
+ * Two identities follow: all weights 1.0f give the playlist call's result bit for bit (fl(1 c) = c, W = k exactly), and
+ * scaling every weight by one power of two changes neither ids nor score bits while nothing over- or underflows.
+ * weights == NULL is exactly the _where call with the same other arguments (same results, same launch).
+ * INVALID_ARG (with a message): the playlist and filter cases, and a weight that is NaN or infinite, |w_k| > 1e6, or
+ * W < 1e-6 (all weights zero included).  mi355rec_playlist_counters counts weighted calls too.
+ * Device: the same playlist_scan_kernel launch (csrc/playlist.hip.h); the 8-bit pre-filter works on the weighted mean
+ * direction u = (sum_k w_k q_k / |q_k|) / W and switches itself off when |u| < 1e-3 (likes and dislikes that cancel): every
+ * row then takes the k exact chains.  Dislikes shrink |u| and let fewer rows be ruled out.  Node handles
+ * as for the playlist calls; the CPU backend serves the same calls with the same arithmetic. */
+int mi355rec_query_mean_topn_weighted(mi355rec_t* h, const float* queries, const float* weights, int k, const int64_t* exclude_global,
+                                      int n_exclude, const mi355rec_filter_t* filter, int topn, int64_t* out_idx, float* out_score,
+                                      int* out_count);
+int mi355rec_query_playlist_topn_weighted(mi355rec_t* h, const int64_t* local_rows, const float* weights, int k,
+                                          const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter, int topn,
+                                          int64_t* out_idx, float* out_score, int* out_count);
+int mi355rec_sharded_query_mean_topn_weighted(mi355rec_sharded_t* h, const float* queries, const float* weights, int k,
+                                              const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
+                                              int topn, int64_t* out_idx, float* out_score, int* out_count);
+int mi355rec_sharded_query_playlist_topn_weighted(mi355rec_sharded_t* h, const int64_t* global_rows, const float* weights, int k,
+                                                  const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
+                                                  int topn, int64_t* out_idx, float* out_score, int* out_count);
 
 #ifdef MI355REC_TEST_HOOKS
 /* TEST HOOK for the cross-workgroup hand-offs of the streamed scans (csrc/replica.hip.h, "hand-offs that fail

@@ -23,7 +23,7 @@ HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc
 OFFLOAD_ARCH = "gfx950"
 
 ENGINE_SOURCES = [CSRC / "mi355rec.hip", CSRC / "sharded.hip"]
-ENGINE_DEPS = ENGINE_SOURCES + sorted(CSRC.glob("*.hip.h")) + [INCLUDE / "mi355rec.h", INCLUDE / "mi355rec_diag.h"]
+ENGINE_DEPS = ENGINE_SOURCES + sorted(CSRC.glob("*.h")) + [INCLUDE / "mi355rec.h", INCLUDE / "mi355rec_diag.h"]
 
 # -ffp-contract=off: the parity contract is sequential multiply-then-add with no
 # FMA contraction (Recommender.cu:264-269 compiled by the reference Makefile:9).
@@ -145,6 +145,7 @@ def check_no_scratch(lib: Path = LIB_ENGINE, tolerate=()) -> int:
 
 CPU_BACKEND_SRC = CSRC / "cpu_backend.cpp"
 CPU_BACKEND_OBJ = PKG / "cpu_backend.o"
+CPU_BACKEND_DEPS = [CPU_BACKEND_SRC, CSRC / "cpu_backend.h", CSRC / "filter_check.h", CSRC / "weights_check.h"]
 # The CPU backend (hosts without a HIP device) is plain C++ + OpenMP, compiled by g++ with the reference's own fp
 # behaviour (Makefile:9: -O3, no -march, no -ffast-math; -ffp-contract=off keeps multiply and add apart) and
 # linked into the engine library.
@@ -153,7 +154,7 @@ CPU_BACKEND_FLAGS = ["-std=c++17", "-O3", "-fopenmp", "-ffp-contract=off", "-fPI
 
 def build_engine(force: bool = False) -> Path:
     """Compile the HIP engine for gfx950 (cross-compiles without a GPU)."""
-    if force or _stale(LIB_ENGINE, ENGINE_DEPS + [CPU_BACKEND_SRC, CSRC / "cpu_backend.h"]):
+    if force or _stale(LIB_ENGINE, ENGINE_DEPS + CPU_BACKEND_DEPS):
         _run(["g++", *CPU_BACKEND_FLAGS, "-c", CPU_BACKEND_SRC, "-o", CPU_BACKEND_OBJ])
         # (the object goes in through the linker: hipcc would take a bare .o behind .hip sources for HIP source)
         _run([HIPCC, *HIP_FLAGS, "-o", LIB_ENGINE, *ENGINE_SOURCES, f"-Wl,{CPU_BACKEND_OBJ}", "-lgomp"])
@@ -172,8 +173,8 @@ def build_engine_variant(out: Path, defines, force: bool = False, tolerate=()) -
     """Another build of the engine library with extra -D flags (never the product library): the MI355REC_EXPERIMENTS build
     keeps the routes that were moved out of the product (the fp16 single-query scan, the 8-bit front end of the
     multi-query pass) compiling, scratch-free and — tests/test_gpu_experiments.py — right."""
-    if force or _stale(out, ENGINE_DEPS + [CPU_BACKEND_SRC, CSRC / "cpu_backend.h"]):
-        if _stale(CPU_BACKEND_OBJ, [CPU_BACKEND_SRC, CSRC / "cpu_backend.h"]):
+    if force or _stale(out, ENGINE_DEPS + CPU_BACKEND_DEPS):
+        if _stale(CPU_BACKEND_OBJ, CPU_BACKEND_DEPS):
             _run(["g++", *CPU_BACKEND_FLAGS, "-c", CPU_BACKEND_SRC, "-o", CPU_BACKEND_OBJ])
         _run([HIPCC, *HIP_FLAGS, *[f"-D{d}" for d in defines], "-o", out, *ENGINE_SOURCES, f"-Wl,{CPU_BACKEND_OBJ}", "-lgomp"])
         try:

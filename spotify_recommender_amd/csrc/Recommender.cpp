@@ -269,9 +269,10 @@ bool makeFilter(const std::vector<Recommender::FeatureRange>& where, mi355rec_fi
     return true;
 }
 
-// recommendForPlaylist with a filter (null: the unfiltered entry point).
+// recommendForPlaylist with a filter (null: the unfiltered entry point) and weights (null: the entry points without them;
+// else one per song, the caller has checked the length).
 std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& songIndices, int topN, const std::vector<int>& alsoExclude,
-                               const mi355rec_filter_t* filter) {
+                               const mi355rec_filter_t* filter, const float* weights = nullptr) {
     if (!impl->initialized) {
         std::cerr << "Error: Recommender not initialized" << std::endl;
         return {};
@@ -299,7 +300,10 @@ std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& 
     impl->idxBuf.assign(static_cast<size_t>(topN), -1);
     impl->scoreBuf.assign(static_cast<size_t>(topN), 0.0f);
     int count = 0;
-    const int rc = filter ? mi355rec_sharded_query_playlist_topn_where(impl->engine, rows.data(), static_cast<int>(rows.size()), excl.data(),
+    const int rc = weights ? mi355rec_sharded_query_playlist_topn_weighted(impl->engine, rows.data(), weights, static_cast<int>(rows.size()),
+                                                                           excl.data(), static_cast<int>(excl.size()), filter, topN,
+                                                                           impl->idxBuf.data(), impl->scoreBuf.data(), &count)
+                   : filter ? mi355rec_sharded_query_playlist_topn_where(impl->engine, rows.data(), static_cast<int>(rows.size()), excl.data(),
                                                                        static_cast<int>(excl.size()), filter, topN, impl->idxBuf.data(),
                                                                        impl->scoreBuf.data(), &count)
                           : mi355rec_sharded_query_playlist_topn(impl->engine, rows.data(), static_cast<int>(rows.size()), excl.data(),
@@ -326,6 +330,35 @@ std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songI
     mi355rec_filter_t f;
     if (!makeFilter(where, f)) return {};
     return playlistQuery(impl_, songIndices, topN, alsoExclude, &f);
+}
+
+std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
+                                                   const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude) {
+    if (weights.size() != songIndices.size()) {
+        std::cerr << "Error: " << weights.size() << " weights for " << songIndices.size() << " songs (one weight per song)" << std::endl;
+        return {};
+    }
+    mi355rec_filter_t f;
+    if (!makeFilter(where, f)) return {};
+    return playlistQuery(impl_, songIndices, topN, alsoExclude, where.empty() ? nullptr : &f, weights.data());
+}
+
+std::vector<int> Recommender::recommendForTaste(const std::vector<int>& liked, const std::vector<int>& disliked, int topN,
+                                                float dislikeWeight, const std::vector<FeatureRange>& where,
+                                                const std::vector<int>& alsoExclude) {
+    if (liked.empty()) {
+        std::cerr << "Error: at least one liked song is needed" << std::endl;
+        return {};
+    }
+    if (!(dislikeWeight >= 0.0f)) {   // (NaN too)
+        std::cerr << "Error: dislikeWeight must be >= 0" << std::endl;
+        return {};
+    }
+    std::vector<int> songs(liked);
+    songs.insert(songs.end(), disliked.begin(), disliked.end());
+    std::vector<float> weights(liked.size(), 1.0f);
+    weights.insert(weights.end(), disliked.size(), -dislikeWeight);
+    return recommendForPlaylist(songs, topN, weights, where, alsoExclude);
 }
 
 std::vector<int> Recommender::recommendByIndexWhere(int songIndex, int topN, const std::vector<FeatureRange>& where) {

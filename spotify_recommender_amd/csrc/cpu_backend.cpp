@@ -1,6 +1,7 @@
 // cpu_backend.cpp — see cpu_backend.h.  Own code; arithmetic contract: Recommender.cu:256-273, selection: :293-315.
 #include "cpu_backend.h"
 #include "filter_check.h"
+#include "weights_check.h"
 
 #include <omp.h>
 
@@ -368,7 +369,7 @@ int node_query_labels(Node* h, const float* q12, int64_t exclude, const int32_t*
 }
 
 int node_query_mean(Node* h, const float* members, int k, const int64_t* exclude, int n_exclude, int topn_asked, int64_t* out_idx,
-                    float* out_score, int* out_count, const char** why, const mi355rec_filter_t* filter) {
+                    float* out_score, int* out_count, const char** why, const mi355rec_filter_t* filter, const float* weights) {
     const Catalogue* c = h->cat;
     const int64_t n = c->n;
     std::vector<float> qn(static_cast<size_t>(k));
@@ -385,13 +386,20 @@ int node_query_mean(Node* h, const float* members, int k, const int64_t* exclude
     std::sort(excl.begin(), excl.end());
     excl.erase(std::unique(excl.begin(), excl.end()), excl.end());
     const float* f = c->feats.data();
-    const float kf = static_cast<float>(k);
-    // score(x) = fl(fl(...fl(c_0 + c_1) + ... + c_{k-1}) / k): fp32, member order, one divide
+    // score(x) = fl(fl(...fl(fl(w_0 c_0) + fl(w_1 c_1)) + ... + fl(w_{k-1} c_{k-1})) / W), W = fl(sum |w_k|): fp32, member order,
+    // multiply then add (this file is built with -ffp-contract=off), one divide.  No weights: every w_k = 1 and W = k, the
+    // plain mean bit for bit.
+    std::vector<float> w(static_cast<size_t>(k), 1.0f);
+    if (weights) w.assign(weights, weights + k);
+    const float wsum = weights ? mi355weights::sum_abs(weights, k) : static_cast<float>(k);
 #pragma omp parallel for schedule(static) num_threads(c->threads)
     for (int64_t i = 0; i < n; ++i) {
-        float sum = score(members, qn[0], f + i * kDim);
-        for (int m = 1; m < k; ++m) sum = sum + score(members + m * kDim, qn[static_cast<size_t>(m)], f + i * kDim);
-        keys[static_cast<size_t>(i)] = pack(sum / kf, static_cast<uint32_t>(i));
+        float sum = w[0] * score(members, qn[0], f + i * kDim);
+        for (int m = 1; m < k; ++m) {
+            const float term = w[static_cast<size_t>(m)] * score(members + m * kDim, qn[static_cast<size_t>(m)], f + i * kDim);
+            sum = sum + term;
+        }
+        keys[static_cast<size_t>(i)] = pack(sum / wsum, static_cast<uint32_t>(i));
     }
     for (int64_t e : excl)
         if (e >= 0 && e < n) keys[static_cast<size_t>(e)] = 0;   // (a real key is never 0: its low half is ~row)

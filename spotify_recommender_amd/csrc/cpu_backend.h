@@ -61,9 +61,11 @@ int node_query_labels(Node* h, const float* q12, int64_t exclude, const int32_t*
                       float* out_score, int* out_count, const char** why);
 // PLAYLISTS (include/mi355rec_diag.h): the top-N rows by the mean of their scores against members[0..k) (k x 12), the
 // rows of exclude[0..n_exclude) (global ids, validated by the caller) left out; filter: null, or a feature filter (checked
-// by the caller, include/mi355rec_diag.h "FEATURE FILTERS") that every returned row passes.
+// by the caller, include/mi355rec_diag.h "FEATURE FILTERS") that every returned row passes; weights: null (the plain mean),
+// or k signed weights checked by the caller ("WEIGHTED PLAYLISTS": score = fl(sum_k fl(w_k c_k)) / fl(sum_k |w_k|)).
 int node_query_mean(Node* h, const float* members, int k, const int64_t* exclude, int n_exclude, int topn, int64_t* out_idx,
-                    float* out_score, int* out_count, const char** why, const mi355rec_filter_t* filter = nullptr);
+                    float* out_score, int* out_count, const char** why, const mi355rec_filter_t* filter = nullptr,
+                    const float* weights = nullptr);
 int node_set_window(Node* h, int window, const char** why);
 int node_enqueue(Node* h, const float* q12, int64_t exclude, int topn, int64_t* ticket, const char** why);
 int node_flush(Node* h);

@@ -10,6 +10,7 @@
 #include "engine_labels.hip.h"
 #include "filter_check.h"
 #include "playlist.hip.h"
+#include "weights_check.h"
 
 // What the first playlist call of a handle allocates.
 struct mi355rec_playlist {
@@ -60,10 +61,11 @@ int ensure_playlist(mi355rec* h) {
 // One playlist query, synchronously.  members: k x 12 floats on the host, or null with `local_rows` (k rows of this shard,
 // excluded by their global ids).  exclude_global[0..n_exclude): global ids, any order, duplicates allowed; ids of other
 // shards match nothing here.  filter: null, or the feature filter (include/mi355rec_diag.h, "FEATURE FILTERS"); null and
-// active == 0 launch exactly the unfiltered call.
+// active == 0 launch exactly the unfiltered call.  weights: null, or k signed weights (include/mi355rec_diag.h, "WEIGHTED
+// PLAYLISTS"); null launches the same kernel with every weight 1.0f and W = k, which is the plain mean bit for bit.
 int sync_playlist_query(mi355rec* h, const float* members, const int64_t* local_rows, int k, const int64_t* exclude_global,
                         int n_exclude, int topn, int64_t* out_idx, float* out_score, int* out_count, int max_exclude = kMaxExclude,
-                        const mi355rec_filter_t* filter = nullptr) {
+                        const mi355rec_filter_t* filter = nullptr, const float* weights = nullptr) {
     if (!out_idx) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     if (k < 1 || k > kMaxPlaylist) return fail(h, MI355REC_ERR_INVALID_ARG, "playlist of %d songs: 1 to %d are supported", k, kMaxPlaylist);
     if (!members && !local_rows) return fail(h, MI355REC_ERR_INVALID_ARG, "null playlist");
@@ -82,6 +84,10 @@ int sync_playlist_query(mi355rec* h, const float* members, const int64_t* local_
     if (filter) {
         char why[128];
         if (mi355filter::invalid(filter, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    }
+    if (weights) {
+        char why[128];
+        if (mi355weights::invalid(weights, k, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
     }
     DeviceGuard guard(h->device);
     int rc = ensure_playlist(h);
@@ -112,6 +118,8 @@ int sync_playlist_query(mi355rec* h, const float* members, const int64_t* local_
     arg.n_excl = n_excl;
     arg.by_row = local_rows ? 1 : 0;
     arg.active = filter ? filter->active : 0u;
+    arg.wsum = weights ? mi355weights::sum_abs(weights, k) : static_cast<float>(k);
+    for (int m = 0; m < k; ++m) b->weights[m] = weights ? weights[m] : 1.0f;
     if (arg.active) {
         std::memcpy(b->lo, filter->lo, sizeof b->lo);
         std::memcpy(b->hi, filter->hi, sizeof b->hi);
@@ -166,10 +174,10 @@ int sync_playlist_query(mi355rec* h, const float* members, const int64_t* local_
 
 namespace mi355node {
 int query_mean_topn(mi355rec_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude, int topn,
-                    int64_t* out_idx, float* out_score, int* out_count, const mi355rec_filter_t* filter) {
+                    int64_t* out_idx, float* out_score, int* out_count, const mi355rec_filter_t* filter, const float* weights) {
     if (!h || !queries) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     return sync_playlist_query(h, queries, nullptr, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count, kPlExcludeCap,
-                               filter);
+                               filter, weights);
 }
 }  // namespace mi355node
 
@@ -200,6 +208,22 @@ int mi355rec_query_playlist_topn_where(mi355rec_t* h, const int64_t* local_rows,
     if (!h || !local_rows) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     return sync_playlist_query(h, nullptr, local_rows, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count, kMaxExclude,
                                filter);
+}
+
+int mi355rec_query_mean_topn_weighted(mi355rec_t* h, const float* queries, const float* weights, int k, const int64_t* exclude_global,
+                                      int n_exclude, const mi355rec_filter_t* filter, int topn, int64_t* out_idx, float* out_score,
+                                      int* out_count) {
+    if (!h || !queries) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    return sync_playlist_query(h, queries, nullptr, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count, kMaxExclude,
+                               filter, weights);
+}
+
+int mi355rec_query_playlist_topn_weighted(mi355rec_t* h, const int64_t* local_rows, const float* weights, int k,
+                                          const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter, int topn,
+                                          int64_t* out_idx, float* out_score, int* out_count) {
+    if (!h || !local_rows) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    return sync_playlist_query(h, nullptr, local_rows, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count, kMaxExclude,
+                               filter, weights);
 }
 
 int mi355rec_playlist_counters(const mi355rec_t* h, int64_t* queries, int64_t* rows_exact) {

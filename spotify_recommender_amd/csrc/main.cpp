@@ -11,6 +11,8 @@
 //   recommender --playlist "<track_id>,<track_id>,..." [-n N]: what goes with a playlist of up to 32 songs (extension)
 //   ... --song, --id and --playlist with one or more --where NAME=LO:HI: only songs whose feature NAME lies in [LO, HI]
 //       (normalised units; extension; not with --genre)
+//   ... --playlist with --dislike "<track_id>,..." [--dislike-weight W] [--weights "w,w,..."]: weighted playlists (extension):
+//       the disliked songs push results away (weight -W, default 0.5), --weights gives the playlist's songs their own weights
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -36,7 +38,10 @@ static void usage(const char* prog) {
               << "Filter (extension): --where NAME=LO:HI, repeatable, with --song, --id or --playlist (not with --genre):\n"
               << "   only songs whose feature NAME lies in [LO, HI].  NAME is a CSV feature column (danceability, energy, key, loudness,\n"
               << "   mode, speechiness, acousticness, instrumentalness, liveness, valence, tempo); LO and HI are in the\n"
-              << "   normalised [0, 1] units songs_data.bin holds (min-max over the CSV), not raw BPM or dB.\n" << std::endl;
+              << "   normalised [0, 1] units songs_data.bin holds (min-max over the CSV), not raw BPM or dB.\n\n"
+              << "Weighted playlists (extension): " << prog << " --playlist \"id,id,...\" [--dislike \"id,...\"] [--dislike-weight W]\n"
+              << "   [--weights \"w,w,...\"]: songs like the playlist's and unlike the disliked ones (each counts -W, default 0.5);\n"
+              << "   --weights gives one weight per playlist song (default 1 each).  Usable with --where.\n" << std::endl;
 }
 
 // --where NAME=LO:HI, any number of times from argv[first]: the ranges (feature indices in Song.h order).  false, with a
@@ -224,15 +229,65 @@ static bool recommendationMode(const std::string& query, bool isTrackId, int top
 
 // --playlist: the songs most similar on average to the playlist's (exact track ids, the first row of an id as for --id),
 // the playlist's own songs never among them.
-static bool playlistMode(const std::string& list, int topN, const std::vector<Recommender::FeatureRange>& ranges) {
-    std::cout << "=== PLAYLIST MODE ===" << std::endl;
-    std::vector<std::string> ids;
+// The non-empty fields of a comma-separated list.
+static std::vector<std::string> splitList(const std::string& list) {
+    std::vector<std::string> items;
     for (size_t start = 0; start <= list.size();) {
         size_t end = list.find(',', start);
         if (end == std::string::npos) end = list.size();
-        if (end > start) ids.push_back(list.substr(start, end - start));
+        if (end > start) items.push_back(list.substr(start, end - start));
         start = end + 1;
     }
+    return items;
+}
+
+// --dislike / --dislike-weight / --weights of a --playlist call (weighted playlists).
+struct Taste {
+    bool weighted = false;            // any of the three options was given
+    std::vector<std::string> dislike;
+    float dislikeWeight = 0.5f;
+    bool haveWeights = false;
+    std::vector<float> weights;       // of the playlist's songs
+};
+
+// false, with a message, on a malformed option.
+static bool parseTaste(int argc, char* argv[], int first, Taste& taste) {
+    for (int i = first; i < argc; ++i) {
+        const bool dislike = std::strcmp(argv[i], "--dislike") == 0, dw = std::strcmp(argv[i], "--dislike-weight") == 0,
+                   weights = std::strcmp(argv[i], "--weights") == 0;
+        if (!dislike && !dw && !weights) continue;
+        if (i + 1 >= argc) {
+            std::cerr << "Error: " << argv[i] << " needs a value" << std::endl;
+            return false;
+        }
+        const std::string arg = argv[++i];
+        taste.weighted = true;
+        if (dislike) {
+            for (const std::string& id : splitList(arg)) taste.dislike.push_back(id);
+            continue;
+        }
+        for (const std::string& field : dw ? std::vector<std::string>{arg} : splitList(arg)) {
+            char* end = nullptr;
+            const float v = std::strtof(field.c_str(), &end);
+            if (field.empty() || *end != '\0') {
+                std::cerr << "Error: " << argv[i - 1] << " '" << arg << "': not a number: '" << field << "'" << std::endl;
+                return false;
+            }
+            if (dw) taste.dislikeWeight = v;
+            else taste.weights.push_back(v);
+        }
+        if (weights) taste.haveWeights = true;
+        if (dw && !(taste.dislikeWeight >= 0.0f)) {
+            std::cerr << "Error: --dislike-weight must be >= 0" << std::endl;
+            return false;
+        }
+    }
+    return true;
+}
+
+static bool playlistMode(const std::string& list, int topN, const std::vector<Recommender::FeatureRange>& ranges, const Taste& taste) {
+    std::cout << "=== PLAYLIST MODE ===" << std::endl;
+    std::vector<std::string> ids = splitList(list);
     if (ids.empty()) {
         std::cerr << "Error: the playlist names no track" << std::endl;
         return false;
@@ -242,6 +297,14 @@ static bool playlistMode(const std::string& list, int topN, const std::vector<Re
         std::cerr << "Failed to load data. Have you run preprocessing?" << std::endl;
         return false;
     }
+    if (taste.haveWeights && taste.weights.size() != ids.size()) {
+        std::cerr << "Error: --weights names " << taste.weights.size() << " weights for " << ids.size() << " playlist songs" << std::endl;
+        return false;
+    }
+    const size_t liked = ids.size();
+    ids.insert(ids.end(), taste.dislike.begin(), taste.dislike.end());
+    std::vector<float> weights = taste.haveWeights ? taste.weights : std::vector<float>(liked, 1.0f);
+    weights.insert(weights.end(), taste.dislike.size(), -taste.dislikeWeight);
     std::vector<int> members;
     for (const std::string& id : ids) {
         int index = -1;
@@ -259,8 +322,9 @@ static bool playlistMode(const std::string& list, int topN, const std::vector<Re
         return false;
     }
     std::map<int, std::string>& genreMap = catalogue.genreMap;
-    const std::vector<int> recs = ranges.empty() ? recommender.recommendForPlaylist(members, topN)
-                                                 : recommender.recommendForPlaylist(members, topN, ranges, {});
+    const std::vector<int> recs = taste.weighted  ? recommender.recommendForPlaylist(members, topN, weights, ranges, {})
+                                  : ranges.empty() ? recommender.recommendForPlaylist(members, topN)
+                                                   : recommender.recommendForPlaylist(members, topN, ranges, {});
     if (recs.empty()) {
         std::cerr << "No recommendations found. Please check the query." << std::endl;
         return false;
@@ -272,7 +336,9 @@ static bool playlistMode(const std::string& list, int topN, const std::vector<Re
             std::cerr << "Error: could not read song " << members[i] << " from " << catalogue.path << std::endl;
             return false;
         }
-        std::cout << "  " << (i + 1) << ". \"" << song.track_name << "\"" << std::endl;
+        std::cout << "  " << (i + 1) << ". \"" << song.track_name << "\"";
+        if (taste.weighted) std::cout << "  (weight " << weights[i] << ")";
+        std::cout << std::endl;
         printSong(song, genreMap, "     ");
     }
     std::cout << "----------------------------------------------" << std::endl;
@@ -358,7 +424,9 @@ int main(int argc, char* argv[]) {
         }
         std::vector<Recommender::FeatureRange> ranges;
         if (!parseWhere(argc, argv, 3, ranges)) return 1;
-        return playlistMode(argv[2], topN, ranges) ? 0 : 1;
+        Taste taste;
+        if (!parseTaste(argc, argv, 3, taste)) return 1;
+        return playlistMode(argv[2], topN, ranges, taste) ? 0 : 1;
     }
     std::cerr << "Error: Unknown mode '" << mode << "'" << std::endl;
     usage(argv[0]);

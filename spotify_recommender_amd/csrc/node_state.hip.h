@@ -29,9 +29,10 @@ namespace mi355node {
 int set_group_labels(mi355rec_t* h, const int32_t* labels_host, int64_t n);
 // mi355rec_query_mean_topn with up to MI355REC_MAX_EXCLUDE + MI355REC_MAX_PLAYLIST excluded ids (engine_playlist.hip.h): the
 // row-sharded node adds the members' global rows to the caller's list.
-// filter: null, or a checked feature filter (include/mi355rec_diag.h, "FEATURE FILTERS").
+// filter: null, or a checked feature filter (include/mi355rec_diag.h, "FEATURE FILTERS"); weights: null, or k weights
+// ("WEIGHTED PLAYLISTS").
 int query_mean_topn(mi355rec_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude, int topn,
-                    int64_t* out_idx, float* out_score, int* out_count, const mi355rec_filter_t* filter);
+                    int64_t* out_idx, float* out_score, int* out_count, const mi355rec_filter_t* filter, const float* weights);
 }  // namespace mi355node
 
 namespace {

@@ -1,32 +1,51 @@
-// playlist.hip.h — the PLAYLIST scan (gfx950 only): the top-N rows by the MEAN of their scores against K <= 32 member
-// queries q_0 .. q_{K-1}, a set of excluded rows left out (engine_playlist.hip.h, include/mi355rec_diag.h "PLAYLISTS").
+// playlist.hip.h — the PLAYLIST scan (gfx950 only): the top-N rows by the WEIGHTED MEAN of their scores against K <= 32
+// member queries q_0 .. q_{K-1} with signed weights w_0 .. w_{K-1}, a set of excluded rows left out (engine_playlist.hip.h,
+// include/mi355rec_diag.h "PLAYLISTS" and "WEIGHTED PLAYLISTS").
 //
 // Contract, per row x (bit for bit):
 //     c_k(x)   = cosine_score(q_k, |q_k|, x)                           (core.hip.h: the reference's chain)
-//     score(x) = fl( fl(...fl(c_0 + c_1) + ... + c_{K-1}) / (float)K )   (fp32, member order, one IEEE divide)
-// keys packed with the global row (ties break as in every other route), the excluded rows never listed.
+//     W        = fl(...fl(|w_0| + |w_1|) + ... + |w_{K-1}|)            (fp32, member order; the host's sum, PlaylistArg::wsum)
+//     score(x) = fl( fl(...fl( fl(w_0 c_0) + fl(w_1 c_1) ) + ... + fl(w_{K-1} c_{K-1}) ) / W )
+// fp32, member order, multiply THEN add (never fused: fp contract is off below), one IEEE divide.  Keys are packed with the
+// global row (ties break as in every other route), the excluded rows never listed.  An unweighted call is the call with
+// every weight 1.0f: fl(1 c) = c and W = K exactly, so it is the plain mean fl(fl(c_0 + ... + c_{K-1}) / K) bit for bit and
+// there is ONE code path.  Scores may be negative (dislikes): a key of any score is non-zero, thresholds are KEYS and 0
+// means "no threshold yet", so nothing below assumes score >= 0.
 //
-// PRE-FILTER.  With u^_k = q_k / |q_k| the mean of the LINEAR cosines is u . x^ with u = (sum_k u^_k) / K: one dot product,
-// so one pass over the 8-bit replica (replica_q8.hip.h) bounds the mean of a row.  The replica's query is w = u / |u|
-// (q8_query on u: approx = D / (127 S) with |approx - w . x^| <= M, M = the q8 margin of w — row residual, query digits
-// and slack, tests/test_q8_margin.py), and a row is ruled out iff
-//     |u| approx < T - margin_mean,       margin_mean = |u| M + kPlChainErr + (2K + 32) kPlUlp,
-// T the workgroup's threshold score.  Why that holds, for a valid row x (|x|^2 in [kBqMinNorm2, kBqMaxNorm2]) and members
-// whose norms all lie in [kBqMinNorm, kBqMaxNorm] (then every den of the chain exceeds 1e-8 and no sum overflows):
-//   * u . x^ = |u| (w . x^) <= |u| (approx + M)                                    (the q8 bound of the query w)
-//   * |c_k - u^_k . x^| <= kPlChainErr: a 12-term fp32 dot and norm, two sqrtf, a product and a divide, < 30 ulp of 1
-//     (1.8e-6), doubled; the clamp to [-1, 1] only moves c_k towards the real cosine;
-//   * the roundings, each a few ulp (2^-24 = kPlUlp) of a quantity of size <= 1 after scaling by 1 / K: the K-term sum
-//     ((K + 1) / 2 ulp), the divide (1), u itself (fp32 in the kernel: u_j = fl(sum_k fl(q_kj / |q_k|)) / K in member
-//     order, |q_k| the chain's own norm: 8 ulp per term, K - 1 for the sum, 1 for the divide, so |(u~ - u) . x^| <=
-//     (K + 8) ulp), |u| in fp32 (9 ulp of |u| |approx + M| <= 1.02 |u|) and the fp32 quotient of the cutoff below (4) —
-//     (2K + 32) ulp covers their sum, 1.5 K + 23, with room.
-// So score(x) <= |u| approx + margin_mean, and a row with |u| approx < T - margin_mean scores below T.  In the kernel
-// the test is the replica's INTEGER compare D < q8_threshold((T - margin_mean) / |u|).  tests/test_playlist_margin.py
-// checks the bound with a numpy model of this arithmetic against the oracle, and that it is not vacuous.
+// PRE-FILTER.  With u^_k = q_k / |q_k| the weighted mean of the LINEAR cosines is u . x^ with u = (sum_k w_k u^_k) / W: one
+// dot product, so one pass over the 8-bit replica (replica_q8.hip.h) bounds the score of a row.  The replica's query is
+// v = u / |u| (q8_query on u: approx = D / (127 S) with |approx - v . x^| <= M, M = the q8 margin of v — row residual,
+// query digits and slack, tests/test_q8_margin.py), and a row is ruled out iff
+//     |u| approx < T - margin_mean,       margin_mean = |u| M + kPlChainErr + (3K + 32) kPlUlp,
+// T the workgroup's threshold score.  Why that holds, for a valid row x (|x|^2 in [kBqMinNorm2, kBqMaxNorm2]), members
+// whose norms all lie in [kBqMinNorm, kBqMaxNorm] (then every den of the chain exceeds 1e-8 and no sum overflows) and
+// weights the host has checked (finite, |w_k| <= 1e6, W >= 1e-6: no product or sum over- or underflows to matter).
+// Write a_k = |w_k| / W with W the fp32 sum above, which BOTH the score and u divide by, so its own rounding only shows in
+// sum_k a_k <= 1 + (K - 1) ulp (ulp = 2^-24 = kPlUlp, relative):
+//   * u . x^ = |u| (v . x^) <= |u| (approx + M)                                    (the q8 bound of the query v)
+//   * |c_k - u^_k . x^| <= kPlChainErr / 2: a 12-term fp32 dot and norm, two sqrtf, a product and a divide, < 30 ulp of 1
+//     (1.8e-6); the clamp to [-1, 1] only moves c_k towards the real cosine.  Weighted: sum_k a_k 1.8e-6 <= 1.8e-6 (1 + 32
+//     ulp), inside kPlChainErr = 4e-6 as before (the doubling is the room);
+//   * the roundings, each a few ulp of a quantity of size <= 1 after scaling by 1 / W:
+//       - the score: K multiplies, each 1 ulp of |w_k c_k| (sum_k a_k |c_k| <= 1 ulp by weight; K ulp counted, one each),
+//         the K - 1 adds (a partial sum is at most sum |w_k| = W, where the unweighted sum had i <= K at step i: K - 1 ulp,
+//         not (K + 1) / 2), the divide (1): at most 2K ulp;
+//       - u itself (fp32 in the kernel: u_j = fl(sum_k fl(w_k fl(q_kj / |q_k|))) / W in member order, |q_k| the chain's own
+//         norm): 8 ulp per term by weight for the norm and the quotient, 1 for the multiply, K - 1 for the sum, 1 for the
+//         divide, so |(u~ - u) . x^| <= (K + 9) ulp;
+//       - |u| in fp32 (9 ulp of |u| |approx + M| <= 1.02 |u|) and the fp32 quotient of the cutoff below (4);
+//       - the K - 1 ulp by which sum a_k may exceed 1, times terms of size <= 1: under 1 ulp of the above, 1 counted;
+//     2K + (K + 9) + 9 + 4 + 1 = 3K + 23: (3K + 32) ulp covers it with room.  For all weights 1 this is K ulp (at most
+//     1.9e-6) above the (2K + 32) the unweighted kernel used; |u| M is 1e-3 and more.
+// So score(x) <= |u| approx + margin_mean, and a row with |u| approx < T - margin_mean scores below T — for T of either
+// sign.  In the kernel the test is the replica's INTEGER compare D < q8_threshold((T - margin_mean) / |u|) (a quotient
+// below -2 means no cutoff).  tests/test_playlist_margin.py (unweighted) and tests/test_weighted_margin.py (positive,
+// signed and likes-and-dislikes weights) check the bound with a numpy model of this arithmetic against the oracle, and
+// that it is not vacuous.
 // The pre-filter is OFF for the whole query (every row takes the K chains) when the handle has no 8-bit replica, when
-// |u| < kPlMinMeanNorm or is not finite (members that cancel, zero members) or when a member's norm lies outside
-// [kBqMinNorm, kBqMaxNorm]; rows whose first byte is 0x80 (the replica's special rows) always take the K chains.
+// |u| < kPlMinMeanNorm or is not finite (members that cancel — likes against dislikes —, zero members) or when a member's
+// norm lies outside [kBqMinNorm, kBqMaxNorm]; rows whose first byte is 0x80 (the replica's special rows) always take the K
+// chains.  Dislikes shrink |u|: the cutoff (T - margin_mean) / |u| falls and more rows take the chains.
 //
 // STARTING THRESHOLD.  The rule: the k-th best key among ANY k or more distinct, not excluded rows bounds the k-th best key
 // of the answer from below, so a workgroup may start from it.  Every workgroup ranks the handle's 4096-row anchor table
@@ -85,6 +104,7 @@ struct PlaylistBuf {
     int64_t rows[kMaxPlaylist];
     float lo[kDim];                  // the feature filter's bounds (read only where PlaylistArg::active has bit j)
     float hi[kDim];
+    float weights[kMaxPlaylist];     // w_k, checked by the host (1.0f each for an unweighted call)
     unsigned long long shared_thr;   // the best threshold any workgroup of the launch has found (0 from the host)
     uint32_t excl[kPlExcludeCap];   // sorted, distinct global ids (only those of this shard)
 };
@@ -94,6 +114,7 @@ struct PlaylistArg {
     int n_excl;       // entries of PlaylistBuf::excl
     int by_row;       // 1: member m is the shard's row PlaylistBuf::rows[m]; 0: PlaylistBuf::members[m]
     uint32_t active;  // the feature filter: bit j (j < kDim) constrains feature j; 0: no filter
+    float wsum;       // W = fl(sum_k |w_k|) in member order (the host's fp32 sum; K for an unweighted call)
 };
 
 // The feature filter's predicate on one fp32 row (active: uniform; unrolled, so no feature is indexed at run time).
@@ -122,8 +143,9 @@ __device__ __forceinline__ float cosine_with_norm(const float* __restrict__ q, f
     return s;
 }
 
-// The contract's score of one row: members (LDS) in order, one fp32 sum, one divide.
-__device__ __forceinline__ float playlist_mean(const float (*__restrict__ mem)[kDim], const float* __restrict__ qn, int k, const Row& r) {
+// The contract's score of one row: members and weights (LDS) in order, multiply then add in fp32, one divide by W.
+__device__ __forceinline__ float playlist_mean(const float (*__restrict__ mem)[kDim], const float* __restrict__ qn,
+                                               const float* __restrict__ w, float wsum, int k, const Row& r) {
     float nrm = 0.0f;
     {
         const float f[kDim] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.c.x, r.c.y, r.c.z, r.c.w};
@@ -131,9 +153,9 @@ __device__ __forceinline__ float playlist_mean(const float (*__restrict__ mem)[k
         for (int j = 0; j < kDim; ++j) nrm = nrm + f[j] * f[j];
     }
     const float rn = sqrtf(nrm);
-    float sum = cosine_with_norm(mem[0], qn[0], r, rn);
-    for (int m = 1; m < k; ++m) sum = sum + cosine_with_norm(mem[m], qn[m], r, rn);
-    return sum / static_cast<float>(k);
+    float sum = w[0] * cosine_with_norm(mem[0], qn[0], r, rn);
+    for (int m = 1; m < k; ++m) sum = sum + w[m] * cosine_with_norm(mem[m], qn[m], r, rn);
+    return sum / wsum;
 }
 
 __device__ __forceinline__ bool playlist_excluded(const uint32_t* s_excl, int n_excl, uint32_t g) {
@@ -162,6 +184,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     __shared__ unsigned long long s_shared;
     __shared__ float s_mem[kMaxPlaylist][kDim];
     __shared__ float s_qn[kMaxPlaylist];
+    __shared__ float s_w[kMaxPlaylist];
     __shared__ float s_u[kDim];
     __shared__ uint32_t s_excl[kPlExcludeCap];
 
@@ -170,6 +193,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     const int k = arg.k;
     const int n_excl = arg.n_excl;
     const uint32_t active = arg.active;
+    const float wsum = arg.wsum;
     const float* const f_lo = buf->lo;
     const float* const f_hi = buf->hi;
 
@@ -189,13 +213,14 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
         for (int j = 0; j < kDim; ++j) q[j] = s_mem[tid][j];
         const float qn = query_norm(q);
         s_qn[tid] = qn;
+        s_w[tid] = buf->weights[tid];
         if (!(qn >= kBqMinNorm && qn <= kBqMaxNorm)) s_ok = 0;   // (false for NaN too; every writer writes 0)
     }
     __syncthreads();
-    if (tid < kDim) {   // u: the mean of the members' unit vectors (only used where every |q_k| is in range)
-        float sum = s_mem[0][tid] / s_qn[0];
-        for (int m = 1; m < k; ++m) sum = sum + s_mem[m][tid] / s_qn[m];
-        s_u[tid] = sum / static_cast<float>(k);
+    if (tid < kDim) {   // u: the weighted mean of the members' unit vectors (only used where every |q_k| is in range)
+        float sum = s_w[0] * (s_mem[0][tid] / s_qn[0]);
+        for (int m = 1; m < k; ++m) sum = sum + s_w[m] * (s_mem[m][tid] / s_qn[m]);
+        s_u[tid] = sum / wsum;
     }
     __syncthreads();
     float u[kDim];
@@ -204,7 +229,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     const float un = query_norm(u);
     const Q8Query hq = q8_query(u, un);
     const bool prefilter = q8 != nullptr && s_ok != 0 && hq.ok && un >= kPlMinMeanNorm;   // uniform (false for a NaN |u|)
-    const float margin_mean = un * hq.margin + kPlChainErr + static_cast<float>(2 * k + 32) * kPlUlp;
+    const float margin_mean = un * hq.margin + kPlChainErr + static_cast<float>(3 * k + 32) * kPlUlp;
     int n_exact = 0;   // rows whose K chains this thread computed
     uint64_t thr = 0;
 
@@ -251,7 +276,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
         if (tid < picked) {
             const int64_t row = anchor_row(n, s_pick[tid]);
             const Row x = load_row(feats, row);   // from the matrix
-            const float m = playlist_mean(s_mem, s_qn, k, x);
+            const float m = playlist_mean(s_mem, s_qn, s_w, wsum, k, x);
             ++n_exact;
             const uint32_t g = static_cast<uint32_t>(row_base + row);
             key = playlist_excluded(s_excl, n_excl, g) || (active && !filter_pass(x, active, f_lo, f_hi)) ? 0ull : pack_key(m, g);
@@ -333,7 +358,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
             const bool have = mask != 0u;
             const int64_t r = have ? r0 + __builtin_ctz(mask) : 0;
             const Row x = load_row(feats, r);
-            const float m = playlist_mean(s_mem, s_qn, k, x);
+            const float m = playlist_mean(s_mem, s_qn, s_w, wsum, k, x);
             n_exact += (have && !active) ? 1 : 0;   // (with a filter every row read was counted above)
             const uint32_t g = static_cast<uint32_t>(row_base + r);
             const uint64_t key = have ? pack_key(m, g) : 0ull;

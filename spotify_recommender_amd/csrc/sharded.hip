@@ -54,6 +54,7 @@
 // A "shard" of a replicated handle is a full replica (lo = 0, hi = n).
 #include "filter_check.h"
 #include "node_stream.hip.h"
+#include "weights_check.h"
 
 extern "C" {
 
@@ -655,14 +656,21 @@ int check_filter(mi355rec_sharded_t* h, const mi355rec_filter_t* filter) {
     return MI355REC_OK;
 }
 
+// The weights' checks (WEIGHTED PLAYLISTS; null: unweighted; k already checked).
+int check_weights(mi355rec_sharded_t* h, const float* weights, int k) {
+    char why[128];
+    if (weights && mi355weights::invalid(weights, k, why, sizeof why)) return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    return MI355REC_OK;
+}
+
 // members (k x 12, by value) and the excluded global ids: the CPU backend, one handle, or every shard and a host merge.
-// filter: null or checked; every shard gets it.
+// filter, weights: null or checked; every shard gets them.
 int sharded_mean(mi355rec_sharded_t* h, const float* members, int k, const int64_t* excl, int n_excl, int topn, int64_t* out_idx,
-                 float* out_score, int* out_count, const mi355rec_filter_t* filter = nullptr) {
+                 float* out_score, int* out_count, const mi355rec_filter_t* filter = nullptr, const float* weights = nullptr) {
     if (h->cpu) {
         const char* why = nullptr;
-        return cpu_result(h, mi355cpu::node_query_mean(h->cpu, members, k, excl, n_excl, topn, out_idx, out_score, out_count, &why, filter),
-                          why);
+        return cpu_result(
+            h, mi355cpu::node_query_mean(h->cpu, members, k, excl, n_excl, topn, out_idx, out_score, out_count, &why, filter, weights), why);
     }
     DeviceRestore restore;
     if (h->shards.size() == 1 || h->replicated) {   // one handle holds the whole catalogue (row_base 0)
@@ -673,7 +681,7 @@ int sharded_mean(mi355rec_sharded_t* h, const float* members, int k, const int64
         } else {
             S_HIP(h, hipSetDevice(s->device));
         }
-        const int rc = mi355node::query_mean_topn(s->engine, members, k, excl, n_excl, topn, out_idx, out_score, out_count, filter);
+        const int rc = mi355node::query_mean_topn(s->engine, members, k, excl, n_excl, topn, out_idx, out_score, out_count, filter, weights);
         return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s->engine));
     }
     const int drc = drain_workers(h);
@@ -692,7 +700,7 @@ int sharded_mean(mi355rec_sharded_t* h, const float* members, int k, const int64
         if (s.hi <= s.lo) continue;
         S_HIP(h, hipSetDevice(s.device));
         int c = 0;
-        const int rc = mi355node::query_mean_topn(s.engine, members, k, excl, n_excl, topn, idx.data(), sc.data(), &c, filter);
+        const int rc = mi355node::query_mean_topn(s.engine, members, k, excl, n_excl, topn, idx.data(), sc.data(), &c, filter, weights);
         if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", s.device, mi355rec_last_error(s.engine));
         for (int i = 0; i < c; ++i) keys.push_back(mi355rec_pack_key(sc[static_cast<size_t>(i)], idx[static_cast<size_t>(i)]));
     }
@@ -729,21 +737,41 @@ int mi355rec_sharded_query_playlist_topn(mi355rec_sharded_t* h, const int64_t* g
                                                       out_count);
 }
 
+int mi355rec_sharded_query_mean_topn_weighted(mi355rec_sharded_t* h, const float* queries, const float* weights, int k,
+                                              const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
+                                              int topn, int64_t* out_idx, float* out_score, int* out_count) {
+    int rc = check_playlist(h, queries, k, exclude_global, n_exclude, topn, out_idx);
+    if (!rc) rc = check_filter(h, filter);
+    if (!rc) rc = check_weights(h, weights, k);
+    if (rc) return rc;
+    return sharded_mean(h, queries, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count, filter, weights);
+}
+
 int mi355rec_sharded_query_playlist_topn_where(mi355rec_sharded_t* h, const int64_t* global_rows, int k,
                                                const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
                                                int topn, int64_t* out_idx, float* out_score, int* out_count) {
+    return mi355rec_sharded_query_playlist_topn_weighted(h, global_rows, nullptr, k, exclude_global, n_exclude, filter, topn, out_idx,
+                                                         out_score, out_count);
+}
+
+int mi355rec_sharded_query_playlist_topn_weighted(mi355rec_sharded_t* h, const int64_t* global_rows, const float* weights, int k,
+                                                  const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
+                                                  int topn, int64_t* out_idx, float* out_score, int* out_count) {
     int rc = check_playlist(h, global_rows, k, exclude_global, n_exclude, topn, out_idx);
     if (rc) return rc;
     for (int m = 0; m < k; ++m)
         if (global_rows[m] < 0 || global_rows[m] >= h->n)
             return sfail(h, MI355REC_ERR_INVALID_ARG, "Invalid song index: %lld", (long long)global_rows[m]);
     rc = check_filter(h, filter);
+    if (!rc) rc = check_weights(h, weights, k);
     if (rc) return rc;
     if (!h->cpu && h->shards.size() == 1 && !h->replicated) {   // one handle: its own by-row call (the members stay on the device)
         DeviceRestore restore;
         Shard& s = h->shards[0];
         S_HIP(h, hipSetDevice(s.device));
-        rc = filter ? mi355rec_query_playlist_topn_where(s.engine, global_rows, k, exclude_global, n_exclude, filter, topn, out_idx,
+        rc = weights ? mi355rec_query_playlist_topn_weighted(s.engine, global_rows, weights, k, exclude_global, n_exclude, filter, topn,
+                                                             out_idx, out_score, out_count)
+             : filter ? mi355rec_query_playlist_topn_where(s.engine, global_rows, k, exclude_global, n_exclude, filter, topn, out_idx,
                                                          out_score, out_count)
                     : mi355rec_query_playlist_topn(s.engine, global_rows, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count);
         return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s.engine));
@@ -768,7 +796,7 @@ int mi355rec_sharded_query_playlist_topn_where(mi355rec_sharded_t* h, const int6
         rc = mi355rec_fetch_row(own->engine, global_rows[m] - own->lo, members + m * MI355REC_DIM);
         if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
     }
-    return sharded_mean(h, members, k, excl, n_exclude + k, topn, out_idx, out_score, out_count, filter);
+    return sharded_mean(h, members, k, excl, n_exclude + k, topn, out_idx, out_score, out_count, filter, weights);
 }
 
 int mi355rec_sharded_scores_row(mi355rec_sharded_t* h, int64_t global_row, float* out_host) {

@@ -204,6 +204,26 @@ int64_t shim_recommend_for_playlist_where(void* h, const int* songs, int n_songs
                                                    std::vector<int>(exclude, exclude + (n_exclude > 0 ? n_exclude : 0))),
                     out, scores, cap);
 }
+// The weighted recommendForPlaylist (n_weights weights for n_songs songs: a length that differs is refused by the class) and
+// recommendForTaste.
+int64_t shim_recommend_for_playlist_weighted(void* h, const int* songs, int n_songs, const float* weights, int n_weights, int topn,
+                                             const int* features, const float* lo, const float* hi, int n_ranges, const int* exclude,
+                                             int n_exclude, int* out, float* scores, int64_t cap) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    return giveBack(c, c->rec.recommendForPlaylist(std::vector<int>(songs, songs + (n_songs > 0 ? n_songs : 0)), topn,
+                                                   std::vector<float>(weights, weights + (n_weights > 0 ? n_weights : 0)),
+                                                   ranges(features, lo, hi, n_ranges),
+                                                   std::vector<int>(exclude, exclude + (n_exclude > 0 ? n_exclude : 0))),
+                    out, scores, cap);
+}
+int64_t shim_recommend_for_taste(void* h, const int* liked, int n_liked, const int* disliked, int n_disliked, int topn,
+                                 float dislike_weight, int* out, float* scores, int64_t cap) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    return giveBack(c, c->rec.recommendForTaste(std::vector<int>(liked, liked + (n_liked > 0 ? n_liked : 0)),
+                                                std::vector<int>(disliked, disliked + (n_disliked > 0 ? n_disliked : 0)), topn,
+                                                dislike_weight),
+                    out, scores, cap);
+}
 int shim_similarities(void* h, int idx, float* out_n) {
     Catalogue* c = static_cast<Catalogue*>(h);
     std::vector<float> v;

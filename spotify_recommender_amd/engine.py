@@ -83,6 +83,17 @@ def _where_query(fn, h, check, members, exclude, where, topn: int) -> Tuple[np.n
                            exclude, topn)
 
 
+def _weighted_query(fn, h, check, members, weights, exclude, where, topn: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Runs one weighted playlist entry point: fn(h, members, weights, k, exclude, n_exclude, filter or NULL, topn, idx, score,
+    &count).  `weights`: one float per member, any sign (WEIGHTED PLAYLISTS)."""
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+    if w.size != members.shape[0]:
+        raise ValueError(f"{w.size} weights for {members.shape[0]} songs: one weight per song")
+    flt = ctypes.byref(make_filter(where)) if where is not None else None
+    return _playlist_query(lambda h_, m, k, e, n_e, *rest: fn(h_, m, w.ctypes.data_as(ctypes.c_void_p), k, e, n_e, flt, *rest), h,
+                           check, members, exclude, topn)
+
+
 def _np_members(queries) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(queries, dtype=np.float32).reshape(-1, capi.DIM))
 
@@ -432,18 +443,26 @@ class CosineEngine:
 
 
     # ---- PLAYLISTS (include/mi355rec_diag.h): top-N by the mean score against up to 32 songs ----
-    def query_mean_topn(self, queries, topn: int, exclude=None, where=None) -> Tuple[np.ndarray, np.ndarray]:
+    def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None) -> Tuple[np.ndarray, np.ndarray]:
         """The best `topn` rows by the mean of their scores against the rows of `queries` (k x 12); `exclude`: global ids.
         `where`: {feature index or name: (lo, hi)}, only rows within every range are returned (FEATURE FILTERS; a
-        filtered single query is k = 1); None calls the unfiltered entry point."""
+        filtered single query is k = 1); None calls the unfiltered entry point.
+        `weights`: one signed float per member (WEIGHTED PLAYLISTS: score = sum w_k c_k / sum |w_k|, a negative weight is
+        a dislike); None calls the entry point used without it."""
         check = lambda rc: capi.check(rc, self._h)   # noqa: E731
+        if weights is not None:
+            return _weighted_query(self._lib.mi355rec_query_mean_topn_weighted, self._h, check, _np_members(queries), weights,
+                                   exclude, where, topn)
         if where is not None:
             return _where_query(self._lib.mi355rec_query_mean_topn_where, self._h, check, _np_members(queries), exclude, where, topn)
         return _playlist_query(self._lib.mi355rec_query_mean_topn, self._h, check, _np_members(queries), exclude, topn)
 
-    def query_playlist_topn(self, local_rows, topn: int, exclude=None, where=None) -> Tuple[np.ndarray, np.ndarray]:
-        """The same for members given as rows of this handle; the members are never returned."""
+    def query_playlist_topn(self, local_rows, topn: int, exclude=None, where=None, weights=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The same for members given as rows of this handle; the members are never returned (whatever their weight)."""
         check = lambda rc: capi.check(rc, self._h)   # noqa: E731
+        if weights is not None:
+            return _weighted_query(self._lib.mi355rec_query_playlist_topn_weighted, self._h, check, _np_rows(local_rows), weights,
+                                   exclude, where, topn)
         if where is not None:
             return _where_query(self._lib.mi355rec_query_playlist_topn_where, self._h, check, _np_rows(local_rows), exclude, where,
                                 topn)
@@ -570,13 +589,19 @@ class NodeEngine:
                              (q.ctypes.data_as(ctypes.c_void_p), int(exclude_global)), labels, topn)
 
     # ---- PLAYLISTS (include/mi355rec_diag.h) over the whole node ----
-    def query_mean_topn(self, queries, topn: int, exclude=None, where=None) -> Tuple[np.ndarray, np.ndarray]:
+    def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None) -> Tuple[np.ndarray, np.ndarray]:
+        if weights is not None:
+            return _weighted_query(self._lib.mi355rec_sharded_query_mean_topn_weighted, self._h, self._check, _np_members(queries),
+                                   weights, exclude, where, topn)
         if where is not None:
             return _where_query(self._lib.mi355rec_sharded_query_mean_topn_where, self._h, self._check, _np_members(queries), exclude,
                                 where, topn)
         return _playlist_query(self._lib.mi355rec_sharded_query_mean_topn, self._h, self._check, _np_members(queries), exclude, topn)
 
-    def query_playlist_topn(self, global_rows, topn: int, exclude=None, where=None) -> Tuple[np.ndarray, np.ndarray]:
+    def query_playlist_topn(self, global_rows, topn: int, exclude=None, where=None, weights=None) -> Tuple[np.ndarray, np.ndarray]:
+        if weights is not None:
+            return _weighted_query(self._lib.mi355rec_sharded_query_playlist_topn_weighted, self._h, self._check,
+                                   _np_rows(global_rows), weights, exclude, where, topn)
         if where is not None:
             return _where_query(self._lib.mi355rec_sharded_query_playlist_topn_where, self._h, self._check, _np_rows(global_rows),
                                 exclude, where, topn)
