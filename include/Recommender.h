@@ -115,6 +115,20 @@ public:
                                        float dislikeWeight = 0.5f, const std::vector<FeatureRange>& where = {},
                                        const std::vector<int>& alsoExclude = {});
 
+    // Extension: diversified recommendations (maximal marginal relevance).  The `pool` most similar songs are found as
+    // above; topN of them are then picked one by one, each pick maximising
+    //     lambda * similarity - (1 - lambda) * (its largest similarity to a song already picked),
+    // so lambda = 1 is the plain result and smaller values spread the results out (0.7 is a usual choice).  The ids come
+    // in pick order; lastScores() holds their similarity (the relevance, not the mmr value).  pool = 0 means
+    // min(1024, max(topN, 4 * topN)); otherwise topN <= pool <= 1024.  recommendDiverse is recommendByIndex diversified
+    // (same checks and messages; `where` as in recommendByIndexWhere); the overload of recommendForPlaylist takes weights
+    // (empty: none), `where` and alsoExclude (both may be empty) as above.  lambda NaN or outside [0, 1], a pool below topN
+    // or above 1024 give {} and a message.
+    std::vector<int> recommendDiverse(int songIndex, int topN, float lambda, int pool = 0, const std::vector<FeatureRange>& where = {});
+    std::vector<int> recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
+                                          const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude, float lambda,
+                                          int pool = 0);
+
     struct Impl;   // opaque: defined in Recommender.cpp
 
 private:

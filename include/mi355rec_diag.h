@@ -20,6 +20,8 @@
  *     (mi355rec_query_mean_topn_where, _query_playlist_topn_where and their node-handle twins);
  *   - WEIGHTED PLAYLISTS: a signed weight per member, likes and dislikes
  *     (mi355rec_query_mean_topn_weighted, _query_playlist_topn_weighted and their node-handle twins);
+ *   - DIVERSIFIED TOP-N: the weighted playlist call's top-`pool`, re-ranked by maximal marginal relevance over the 12
+ *     features (mi355rec_query_mean_topn_diverse, _query_playlist_topn_diverse, their node-handle twins, mi355rec_fetch_rows);
  *   - test hooks, compiled in only with -DMI355REC_TEST_HOOKS (spotify_recommender_amd/build.py builds
  *     libmi355rec_testhooks.so for tests/; the product library does not export them).
  */
@@ -284,6 +286,9 @@ int mi355rec_set_timing(mi355rec_t* h, int enabled);
 
 /* The 12 features of one resident row, copied back to the host (48 bytes). */
 int mi355rec_fetch_row(mi355rec_t* h, int64_t local_row, float* out12_host);
+/* The features of `count` resident rows, copied back to the host in the order asked (count x 12 floats): ids in any order,
+ * duplicates allowed.  One gather launch and one copy per 1024 rows, not a copy per row. */
+int mi355rec_fetch_rows(mi355rec_t* h, const int64_t* local_rows, int64_t count, float* out_host);
 
 /* ---- the node handle (mi355rec.h: mi355rec_create_placed): set-up variants, controls, statistics ---- */
 
@@ -481,6 +486,48 @@ int mi355rec_sharded_query_mean_topn_weighted(mi355rec_sharded_t* h, const float
 int mi355rec_sharded_query_playlist_topn_weighted(mi355rec_sharded_t* h, const int64_t* global_rows, const float* weights, int k,
                                                   const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
                                                   int topn, int64_t* out_idx, float* out_score, int* out_count);
+
+/* DIVERSIFIED TOP-N (an extension beyond the reference): results that are spread out, not ten variations of one song.
+ * Maximal marginal relevance over the data the handle already holds, the 12 features.  The _diverse calls are the _weighted
+ * calls above (weights and filter may be NULL; a single query is k = 1) plus `lambda`, `pool` and `out_mmr`:
+ *   - the POOL is what the _weighted call returns for the same members, weights, exclusion list and filter with topn = pool:
+ *     P' = min(pool, |admissible rows|) rows in canonical order; pool row i has relevance rel_i, that call's score bit for bit;
+ *   - c(i, p) is the score mi355rec_query_topn gives row i (the scanned row) for a query vector equal to row p's 12 stored
+ *     features: the exact sequential chain, never NaN;
+ *   - mu = fl(1 - lambda), once; pen_i starts at +0.0f; after a row p is picked every unpicked row i takes
+ *     pen_i = c(i, p) if c(i, p) > pen_i (IEEE >), else keeps pen_i;
+ *   - mmr_i = fl( fl(lambda rel_i) - fl(mu pen_i) ): fp32, multiply, round, subtract, round, never fused;
+ *   - each step picks the unpicked pool row with the largest mmr_i (IEEE >); a tie goes to the earlier pool position (the
+ *     higher relevance, then the lower row id), so the first pick is pool row 0; min(topn, P') picks.
+ * out_idx[t] is the row picked at step t (pick order), out_score[t] its relevance (the similarity a user understands; -0.0
+ * reported as +0.0), out_mmr[t] (may be NULL) the mmr value it was picked with; padding -1 / 0 / 0;
+ * *out_count = min(topn, P').
+ * Identities, bit for bit: lambda = 1.0f gives the _weighted call's top-N for any pool >= topn, with out_mmr == out_score;
+ * pool == topn gives a permutation of the _weighted call's top-N; the result does not depend on shard count, placement, lane
+ * or replica mode.
+ * INVALID_ARG (with a message): every case of the weighted, filter and playlist calls; lambda NaN or outside [0, 1];
+ * pool < topn or pool > MI355REC_MAX_TOPN_FAST (so topn <= 1024).  mi355rec_playlist_counters counts these calls too.
+ * Device: the playlist scan and its merge leave the pool's keys on the device; mmr_rerank_kernel (csrc/diverse.hip.h), one
+ * workgroup with the pool's rows in LDS, picks serially and stores the results into the handle's pinned result slots with
+ * the completion word: one wait per call, no set-up, lanes and node handles answer at once.
+ * Node handle: one shard forwards, a replicated placement asks one replica; a row-sharded one takes the pool from its
+ * weighted path (per-shard lists merged on the host), gathers the pool rows' features from their owning shards
+ * (mi355rec_fetch_rows) and runs the same kernel on its first shard's device over the pool passed by value.  The CPU
+ * backend serves the same calls with the same arithmetic. */
+int mi355rec_query_mean_topn_diverse(mi355rec_t* h, const float* queries, const float* weights, int k, const int64_t* exclude_global,
+                                     int n_exclude, const mi355rec_filter_t* filter, float lambda, int pool, int topn, int64_t* out_idx,
+                                     float* out_score, float* out_mmr, int* out_count);
+int mi355rec_query_playlist_topn_diverse(mi355rec_t* h, const int64_t* local_rows, const float* weights, int k,
+                                         const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter, float lambda,
+                                         int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr, int* out_count);
+int mi355rec_sharded_query_mean_topn_diverse(mi355rec_sharded_t* h, const float* queries, const float* weights, int k,
+                                             const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
+                                             float lambda, int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
+                                             int* out_count);
+int mi355rec_sharded_query_playlist_topn_diverse(mi355rec_sharded_t* h, const int64_t* global_rows, const float* weights, int k,
+                                                 const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
+                                                 float lambda, int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
+                                                 int* out_count);
 
 #ifdef MI355REC_TEST_HOOKS
 /* TEST HOOK for the cross-workgroup hand-offs of the streamed scans (csrc/replica.hip.h, "hand-offs that fail

@@ -269,10 +269,17 @@ bool makeFilter(const std::vector<Recommender::FeatureRange>& where, mi355rec_fi
     return true;
 }
 
+// lambda and pool of a diversified call (DIVERSIFIED TOP-N; pool 0: min(1024, max(topN, 4 topN)), the Python default).
+struct Diverse {
+    float lambda;
+    int pool;
+};
+
 // recommendForPlaylist with a filter (null: the unfiltered entry point) and weights (null: the entry points without them;
-// else one per song, the caller has checked the length).
+// else one per song, the caller has checked the length); diverse: null, or the diversified entry point (weights and filter
+// may then be null).
 std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& songIndices, int topN, const std::vector<int>& alsoExclude,
-                               const mi355rec_filter_t* filter, const float* weights = nullptr) {
+                               const mi355rec_filter_t* filter, const float* weights = nullptr, const Diverse* diverse = nullptr) {
     if (!impl->initialized) {
         std::cerr << "Error: Recommender not initialized" << std::endl;
         return {};
@@ -300,7 +307,20 @@ std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& 
     impl->idxBuf.assign(static_cast<size_t>(topN), -1);
     impl->scoreBuf.assign(static_cast<size_t>(topN), 0.0f);
     int count = 0;
-    const int rc = weights ? mi355rec_sharded_query_playlist_topn_weighted(impl->engine, rows.data(), weights, static_cast<int>(rows.size()),
+    int pool = 0;
+    if (diverse) {
+        pool = diverse->pool;
+        if (pool == 0) pool = std::min(MI355REC_MAX_TOPN_FAST, std::max(topN, 4 * std::min(topN, MI355REC_MAX_TOPN_FAST)));
+        if (pool < 0) {
+            std::cerr << "Error: pool must be positive (or 0 for the default)" << std::endl;
+            return {};
+        }
+    }
+    const int rc = diverse ? mi355rec_sharded_query_playlist_topn_diverse(impl->engine, rows.data(), weights, static_cast<int>(rows.size()),
+                                                                          excl.data(), static_cast<int>(excl.size()), filter, diverse->lambda,
+                                                                          pool, topN, impl->idxBuf.data(), impl->scoreBuf.data(), nullptr,
+                                                                          &count)
+                   : weights ? mi355rec_sharded_query_playlist_topn_weighted(impl->engine, rows.data(), weights, static_cast<int>(rows.size()),
                                                                            excl.data(), static_cast<int>(excl.size()), filter, topN,
                                                                            impl->idxBuf.data(), impl->scoreBuf.data(), &count)
                    : filter ? mi355rec_sharded_query_playlist_topn_where(impl->engine, rows.data(), static_cast<int>(rows.size()), excl.data(),
@@ -341,6 +361,24 @@ std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songI
     mi355rec_filter_t f;
     if (!makeFilter(where, f)) return {};
     return playlistQuery(impl_, songIndices, topN, alsoExclude, where.empty() ? nullptr : &f, weights.data());
+}
+
+std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
+                                                   const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude, float lambda,
+                                                   int pool) {
+    if (!weights.empty() && weights.size() != songIndices.size()) {
+        std::cerr << "Error: " << weights.size() << " weights for " << songIndices.size() << " songs (one weight per song, or none)" << std::endl;
+        return {};
+    }
+    mi355rec_filter_t f;
+    if (!makeFilter(where, f)) return {};
+    const Diverse d{lambda, pool};
+    return playlistQuery(impl_, songIndices, topN, alsoExclude, where.empty() ? nullptr : &f, weights.empty() ? nullptr : weights.data(), &d);
+}
+
+std::vector<int> Recommender::recommendDiverse(int songIndex, int topN, float lambda, int pool, const std::vector<FeatureRange>& where) {
+    if (!checkQuery(impl_, songIndex, topN)) return {};
+    return recommendForPlaylist({songIndex}, topN, {}, where, {}, lambda, pool);
 }
 
 std::vector<int> Recommender::recommendForTaste(const std::vector<int>& liked, const std::vector<int>& disliked, int topN,

@@ -422,6 +422,65 @@ int node_query_mean(Node* h, const float* members, int k, const int64_t* exclude
     return MI355REC_OK;
 }
 
+// DIVERSIFIED TOP-N (include/mi355rec_diag.h): the pool is node_query_mean's top-`pool`; then the greedy picks, a plain loop
+// over P' <= 1024 rows.  mmr = fl(fl(lambda rel) - fl(mu pen)): multiply, round, subtract, round (-ffp-contract=off).
+int node_query_mean_diverse(Node* h, const float* members, int k, const int64_t* exclude, int n_exclude, const mi355rec_filter_t* filter,
+                            const float* weights, float lambda, int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
+                            int* out_count, const char** why) {
+    std::vector<int64_t> pidx;
+    std::vector<float> prel, pen, qn;
+    std::vector<char> picked;
+    try {
+        pidx.resize(static_cast<size_t>(pool));
+        prel.resize(static_cast<size_t>(pool));
+        pen.assign(static_cast<size_t>(pool), 0.0f);
+        qn.resize(static_cast<size_t>(pool));
+        picked.assign(static_cast<size_t>(pool), 0);
+    } catch (const std::bad_alloc&) {
+        *why = "out of host memory";
+        return MI355REC_ERR_OUT_OF_MEMORY;
+    }
+    int p_eff = 0;
+    const int rc = node_query_mean(h, members, k, exclude, n_exclude, pool, pidx.data(), prel.data(), &p_eff, why, filter, weights);
+    if (rc != MI355REC_OK) return rc;
+    const float* f = h->cat->feats.data();
+    const float mu = 1.0f - lambda;
+    const int picks = topn < p_eff ? topn : p_eff;
+    for (int i = 0; i < p_eff; ++i) qn[static_cast<size_t>(i)] = query_norm(f + pidx[static_cast<size_t>(i)] * kDim);
+    for (int t = 0; t < topn; ++t) {
+        if (t >= picks) {
+            out_idx[t] = -1;
+            if (out_score) out_score[t] = 0.0f;
+            if (out_mmr) out_mmr[t] = 0.0f;
+            continue;
+        }
+        int best = -1;
+        float best_mmr = 0.0f;
+        for (int i = 0; i < p_eff; ++i) {
+            if (picked[static_cast<size_t>(i)]) continue;
+            const float a = lambda * prel[static_cast<size_t>(i)];
+            const float b = mu * pen[static_cast<size_t>(i)];
+            const float mmr = a - b;
+            if (best < 0 || mmr > best_mmr) {   // IEEE >: a tie stays with the earlier pool position
+                best = i;
+                best_mmr = mmr;
+            }
+        }
+        picked[static_cast<size_t>(best)] = 1;
+        out_idx[t] = pidx[static_cast<size_t>(best)];
+        if (out_score) out_score[t] = prel[static_cast<size_t>(best)];
+        if (out_mmr) out_mmr[t] = best_mmr;
+        const float* q = f + pidx[static_cast<size_t>(best)] * kDim;
+        for (int i = 0; i < p_eff; ++i) {
+            if (picked[static_cast<size_t>(i)]) continue;
+            const float c = score(q, qn[static_cast<size_t>(best)], f + pidx[static_cast<size_t>(i)] * kDim);   // row i scanned, row p the query
+            if (c > pen[static_cast<size_t>(i)]) pen[static_cast<size_t>(i)] = c;
+        }
+    }
+    if (out_count) *out_count = picks;
+    return MI355REC_OK;
+}
+
 int node_set_window(Node* h, int window, const char** why) {
     if (window < 1 || window > kMaxWindow) {
         *why = "window out of range";

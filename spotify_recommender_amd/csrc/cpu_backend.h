@@ -66,6 +66,11 @@ int node_query_labels(Node* h, const float* q12, int64_t exclude, const int32_t*
 int node_query_mean(Node* h, const float* members, int k, const int64_t* exclude, int n_exclude, int topn, int64_t* out_idx,
                     float* out_score, int* out_count, const char** why, const mi355rec_filter_t* filter = nullptr,
                     const float* weights = nullptr);
+// DIVERSIFIED TOP-N (include/mi355rec_diag.h): the top-`pool` of node_query_mean re-ranked by maximal marginal relevance;
+// lambda in [0, 1] and topn <= pool <= 1024 are checked by the caller.  out_score and out_mmr may be null.
+int node_query_mean_diverse(Node* h, const float* members, int k, const int64_t* exclude, int n_exclude, const mi355rec_filter_t* filter,
+                            const float* weights, float lambda, int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
+                            int* out_count, const char** why);
 int node_set_window(Node* h, int window, const char** why);
 int node_enqueue(Node* h, const float* q12, int64_t exclude, int topn, int64_t* ticket, const char** why);
 int node_flush(Node* h);

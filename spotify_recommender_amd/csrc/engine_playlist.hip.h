@@ -18,6 +18,10 @@ struct mi355rec_playlist {
     PlaylistBuf* h_buf = nullptr;           // ... staged here (pinned)
     unsigned long long* d_exact = nullptr;  // rows whose K chains were computed, since the first call (mi355rec_playlist_counters)
     int grid_cap = 1;                       // workgroups of a launch at most (occupancy x CUs, and the handle's list slots)
+    // DIVERSIFIED TOP-N (engine_diverse.hip.h), allocated by the first such call:
+    float* h_mmr = nullptr;                 // the picks' mmr values: pinned, mapped, written by mmr_rerank_kernel itself ...
+    float* hd_mmr = nullptr;                // ... at this device-side address
+    float* d_rows = nullptr;                // kMaxTopK rows: a pool passed by value, or the rows mi355rec_fetch_rows gathers
 };
 
 namespace {
@@ -29,6 +33,8 @@ void free_playlist(mi355rec_playlist* P) {
     if (P->d_buf) (void)hipFree(P->d_buf);
     if (P->d_exact) (void)hipFree(P->d_exact);
     if (P->h_buf) (void)hipHostFree(P->h_buf);
+    if (P->h_mmr) (void)hipHostFree(P->h_mmr);
+    if (P->d_rows) (void)hipFree(P->d_rows);
     delete P;
 }
 
@@ -63,9 +69,16 @@ int ensure_playlist(mi355rec* h) {
 // shards match nothing here.  filter: null, or the feature filter (include/mi355rec_diag.h, "FEATURE FILTERS"); null and
 // active == 0 launch exactly the unfiltered call.  weights: null, or k signed weights (include/mi355rec_diag.h, "WEIGHTED
 // PLAYLISTS"); null launches the same kernel with every weight 1.0f and W = k, which is the plain mean bit for bit.
-int sync_playlist_query(mi355rec* h, const float* members, const int64_t* local_rows, int k, const int64_t* exclude_global,
-                        int n_exclude, int topn, int64_t* out_idx, float* out_score, int* out_count, int max_exclude = kMaxExclude,
-                        const mi355rec_filter_t* filter = nullptr, const float* weights = nullptr) {
+//
+// playlist_launch is the call up to and including its scan launch: the checks, the staging and playlist_scan_kernel, which
+// leaves `*grid` lists of `*eff` = min(topn, rows left after the exclusion list) keys in h->d_block_lists.  *eff == 0: nothing
+// is left to return and nothing was launched.  What follows the scan is the caller's: sync_playlist_query merges into the
+// result slots; the diversified calls (engine_diverse.hip.h) merge, re-rank and wait once.
+int playlist_launch(mi355rec* h, const float* members, const int64_t* local_rows, int k, const int64_t* exclude_global, int n_exclude,
+                    int topn, const int64_t* out_idx, int max_exclude, const mi355rec_filter_t* filter, const float* weights, int* eff_out,
+                    int* grid_out) {
+    *eff_out = 0;
+    *grid_out = 0;
     if (!out_idx) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     if (k < 1 || k > kMaxPlaylist) return fail(h, MI355REC_ERR_INVALID_ARG, "playlist of %d songs: 1 to %d are supported", k, kMaxPlaylist);
     if (!members && !local_rows) return fail(h, MI355REC_ERR_INVALID_ARG, "null playlist");
@@ -105,14 +118,7 @@ int sync_playlist_query(mi355rec* h, const float* members, const int64_t* local_
     ++h->playlist_queries;
     const int64_t avail = h->n - n_excl;
     const int eff = static_cast<int64_t>(topn) < avail ? topn : static_cast<int>(avail);
-    if (eff <= 0) {   // nothing left to return: nothing to launch
-        for (int i = 0; i < topn; ++i) {
-            out_idx[i] = -1;
-            if (out_score) out_score[i] = 0.0f;
-        }
-        if (out_count) *out_count = 0;
-        return MI355REC_OK;
-    }
+    if (eff <= 0) return MI355REC_OK;   // nothing left to return: nothing to launch
     PlaylistArg arg;
     arg.k = k;
     arg.n_excl = n_excl;
@@ -140,13 +146,34 @@ int sync_playlist_query(mi355rec* h, const float* members, const int64_t* local_
     if (want_grid > P->grid_cap) want_grid = P->grid_cap;
     if (want_grid < 1) want_grid = 1;
     const int grid = static_cast<int>(want_grid);
-    const bool direct = eff <= kDirectResultSlots;
-    const uint32_t want = direct ? (++h->done_seq ? h->done_seq : ++h->done_seq) : 0u;   // never 0
     LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, playlist_scan_kernel, dim3(grid), dim3(PlaylistCfg::kBlock),
                  h->stream, h->d_feats, q8, h->n, h->row_base, static_cast<const PlaylistBuf*>(P->d_buf), arg,
                  static_cast<const float*>(h->d_anchor), eff, h->d_block_lists, P->d_exact,
                  reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr)));
     HIP_TRY(h, hipGetLastError());
+    *eff_out = eff;
+    *grid_out = grid;
+    return MI355REC_OK;
+}
+
+int sync_playlist_query(mi355rec* h, const float* members, const int64_t* local_rows, int k, const int64_t* exclude_global,
+                        int n_exclude, int topn, int64_t* out_idx, float* out_score, int* out_count, int max_exclude = kMaxExclude,
+                        const mi355rec_filter_t* filter = nullptr, const float* weights = nullptr) {
+    if (!h) return MI355REC_ERR_INVALID_ARG;
+    DeviceGuard guard(h->device);
+    int eff = 0, grid = 0;
+    int rc = playlist_launch(h, members, local_rows, k, exclude_global, n_exclude, topn, out_idx, max_exclude, filter, weights, &eff, &grid);
+    if (rc) return rc;
+    if (eff <= 0) {
+        for (int i = 0; i < topn; ++i) {
+            out_idx[i] = -1;
+            if (out_score) out_score[i] = 0.0f;
+        }
+        if (out_count) *out_count = 0;
+        return MI355REC_OK;
+    }
+    const bool direct = eff <= kDirectResultSlots;
+    const uint32_t want = direct ? (++h->done_seq ? h->done_seq : ++h->done_seq) : 0u;   // never 0
     rc = enqueue_merge(h, h->d_block_lists, grid, eff, eff, h->d_keys, direct ? h->hd_idx : h->d_idx, direct ? h->hd_score : h->d_score,
                        h->stream, want);
     if (rc) return rc;

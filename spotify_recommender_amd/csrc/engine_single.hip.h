@@ -232,14 +232,10 @@ int enqueue_scan(mi355rec* h, const float* qptr, const float* query12,
 int enqueue_merge(mi355rec* h, const uint64_t* lists, int n_lists, int list_len, int topn,
                   uint64_t* out_keys, int64_t* out_idx, float* out_score, hipStream_t s, uint32_t notify = 0) {
     const int slot = timing_begin(h, h->ev_merge, h->n_merge_pairs, h->merge_launches, s);
-    if (notify) {   // the host polls h->h_done for this value (mi355rec_query_row_topn)
-        hipLaunchKernelGGL(merge_notify_kernel, dim3(1), dim3(kMergeBlock), 0, s, lists, n_lists, list_len,
-                           static_cast<int64_t>(list_len), topn, out_keys, out_idx, out_score, h->hd_done, notify);
-    } else {
-        hipLaunchKernelGGL(merge_kernel, dim3(1), dim3(kMergeBlock), 0, s, lists, n_lists, list_len,
-                           static_cast<int64_t>(list_len), static_cast<int64_t>(0), topn, out_keys, out_idx, out_score,
-                           static_cast<int64_t>(0));
-    }
+    // notify: the host polls h->h_done for this value (mi355rec_query_row_topn); 0: no completion word
+    hipLaunchKernelGGL(merge_kernel, dim3(1), dim3(kMergeBlock), 0, s, lists, n_lists, list_len,
+                       static_cast<int64_t>(list_len), static_cast<int64_t>(0), topn, out_keys, out_idx, out_score,
+                       static_cast<int64_t>(0), notify ? h->hd_done : static_cast<uint32_t*>(nullptr), notify);
     timing_end(h, h->ev_merge, h->n_merge_pairs, slot, s);
     HIP_TRY(h, hipGetLastError());
     return MI355REC_OK;

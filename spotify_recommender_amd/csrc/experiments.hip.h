@@ -42,7 +42,7 @@ __device__ unsigned long long g_phase_clock[1024 * 8];   // [workgroup][phase]
     do {                                                                                                         \
         if ((threadIdx.x & 63) == 0 && blockIdx.x < 1023) atomicMax(&g_phase_clock[blockIdx.x * 8 + (i)], wall_clock64()); \
     } while (0)
-// phases of ONE merge (merge_body in the workgroup with blockIdx.x == 0: merge_notify_kernel), kept in row 1023
+// phases of ONE merge (merge_body in the workgroup with blockIdx.x == 0: the notifying merge_kernel launch), kept in row 1023
 #define MI355REC_MPHASE(i)                                                                       \
     do {                                                                                         \
         if (threadIdx.x == 0 && blockIdx.x == 0) g_phase_clock[1023 * 8 + (i)] = wall_clock64(); \

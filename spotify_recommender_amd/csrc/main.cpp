@@ -11,6 +11,8 @@
 //   recommender --playlist "<track_id>,<track_id>,..." [-n N]: what goes with a playlist of up to 32 songs (extension)
 //   ... --song, --id and --playlist with one or more --where NAME=LO:HI: only songs whose feature NAME lies in [LO, HI]
 //       (normalised units; extension; not with --genre)
+//   ... --song, --id and --playlist with --diverse LAMBDA [--pool P]: diversified results (maximal marginal relevance over the
+//       P most similar songs; extension; usable with --where, --dislike, --weights; not with --genre)
 //   ... --playlist with --dislike "<track_id>,..." [--dislike-weight W] [--weights "w,w,..."]: weighted playlists (extension):
 //       the disliked songs push results away (weight -W, default 0.5), --weights gives the playlist's songs their own weights
 #include <algorithm>
@@ -41,7 +43,10 @@ static void usage(const char* prog) {
               << "   normalised [0, 1] units songs_data.bin holds (min-max over the CSV), not raw BPM or dB.\n\n"
               << "Weighted playlists (extension): " << prog << " --playlist \"id,id,...\" [--dislike \"id,...\"] [--dislike-weight W]\n"
               << "   [--weights \"w,w,...\"]: songs like the playlist's and unlike the disliked ones (each counts -W, default 0.5);\n"
-              << "   --weights gives one weight per playlist song (default 1 each).  Usable with --where.\n" << std::endl;
+              << "   --weights gives one weight per playlist song (default 1 each).  Usable with --where.\n"
+              << "Diversified results (extension): --diverse LAMBDA [--pool P], with --song, --id or --playlist (and --where, --dislike,\n"
+              << "   --weights; not with --genre): picks from the P most similar songs (default 4 x N, at most 1024), each pick\n"
+              << "   weighing similarity (LAMBDA in [0, 1]; 1 = the plain result) against likeness to the songs already picked.\n" << std::endl;
 }
 
 // --where NAME=LO:HI, any number of times from argv[first]: the ranges (feature indices in Song.h order).  false, with a
@@ -95,6 +100,53 @@ static void printSong(const Song& s, std::map<int, std::string>& genres, const c
     std::cout << indent << "Artist: " << s.artists << "\n"
               << indent << "Genre:  " << genres[s.genre_id] << "\n"
               << indent << "ID:     " << s.track_id << std::endl;
+}
+
+// --diverse LAMBDA [--pool P] (diversified results).
+struct DiverseOpt {
+    bool on = false;
+    float lambda = 1.0f;
+    int pool = 0;   // 0: the default, min(1024, 4 x N)
+};
+
+// false, with a message, on a malformed or out-of-range option.
+static bool parseDiverse(int argc, char* argv[], int first, int topN, DiverseOpt& dv) {
+    bool havePool = false;
+    for (int i = first; i < argc; ++i) {
+        const bool diverse = std::strcmp(argv[i], "--diverse") == 0, pool = std::strcmp(argv[i], "--pool") == 0;
+        if (!diverse && !pool) continue;
+        if (i + 1 >= argc) {
+            std::cerr << "Error: " << argv[i] << " needs a value" << std::endl;
+            return false;
+        }
+        const std::string arg = argv[++i];
+        char* end = nullptr;
+        if (diverse) {
+            dv.on = true;
+            dv.lambda = std::strtof(arg.c_str(), &end);
+            if (arg.empty() || *end != '\0' || !(dv.lambda >= 0.0f && dv.lambda <= 1.0f)) {   // (NaN too)
+                std::cerr << "Error: --diverse '" << arg << "': LAMBDA must be a number in [0, 1]" << std::endl;
+                return false;
+            }
+        } else {
+            havePool = true;
+            const long v = std::strtol(arg.c_str(), &end, 10);
+            if (arg.empty() || *end != '\0' || v < 1 || v > 1024) {
+                std::cerr << "Error: --pool '" << arg << "': P must be an integer in [1, " << 1024 << "]" << std::endl;
+                return false;
+            }
+            dv.pool = static_cast<int>(v);
+        }
+    }
+    if (havePool && !dv.on) {
+        std::cerr << "Error: --pool needs --diverse LAMBDA" << std::endl;
+        return false;
+    }
+    if (havePool && dv.pool < topN) {
+        std::cerr << "Error: --pool " << dv.pool << " is below -n " << topN << " (picks are made from the pool)" << std::endl;
+        return false;
+    }
+    return true;
 }
 
 // The reference loads every Song, deep-copies the vector into the recommender and
@@ -161,8 +213,21 @@ static bool genreRecommendations(Recommender& recommender, const DataManager::Ca
     return true;
 }
 
+// --diverse: recommendByIndex (or its --where form) diversified.
+static void diverseRecommendations(Recommender& recommender, const DataManager::Catalogue& catalogue, const std::string& query,
+                                   bool isTrackId, int topN, const std::vector<Recommender::FeatureRange>& ranges, const DiverseOpt& dv,
+                                   std::vector<int>& recs) {
+    const int index = findQuery(catalogue, query, isTrackId);
+    if (index < 0) {
+        std::cerr << "Error: Song with " << (isTrackId ? "track_id" : "name") << " '" << query << "' not found" << std::endl;
+        return;   // (no recommendations: the caller says so)
+    }
+    std::cout << "Diversified: lambda " << dv.lambda << std::endl;
+    recs = recommender.recommendDiverse(index, topN, dv.lambda, dv.pool, ranges);
+}
+
 static bool recommendationMode(const std::string& query, bool isTrackId, int topN, const std::vector<std::string>& genres,
-                               const std::vector<Recommender::FeatureRange>& ranges) {  // main.cpp:46-131
+                               const std::vector<Recommender::FeatureRange>& ranges, const DiverseOpt& dv) {  // main.cpp:46-131
     std::cout << "=== RECOMMENDATION MODE ===" << std::endl;
     DataManager::Catalogue catalogue;
     if (!DataManager::loadCatalogue(kBinaryDataFile, catalogue)) {
@@ -180,14 +245,16 @@ static bool recommendationMode(const std::string& query, bool isTrackId, int top
     int queryIndex = -1;
     if (isTrackId) {
         std::cout << "\nSearching for track ID: " << query << std::endl;
-        if (!ranges.empty()) whereRecommendations(recommender, catalogue, query, true, topN, ranges, recs);
+        if (dv.on) diverseRecommendations(recommender, catalogue, query, true, topN, ranges, dv, recs);
+        else if (!ranges.empty()) whereRecommendations(recommender, catalogue, query, true, topN, ranges, recs);
         else if (genres.empty()) recs = recommender.recommend(query, topN);
         else if (!genreRecommendations(recommender, catalogue, query, true, topN, genres, recs)) return false;
         for (size_t i = 0; i < catalogue.size(); ++i)
             if (catalogue.trackIds[i] == query) { queryIndex = static_cast<int>(i); break; }
     } else {
         std::cout << "\nSearching for song: " << query << std::endl;
-        if (!ranges.empty()) whereRecommendations(recommender, catalogue, query, false, topN, ranges, recs);
+        if (dv.on) diverseRecommendations(recommender, catalogue, query, false, topN, ranges, dv, recs);
+        else if (!ranges.empty()) whereRecommendations(recommender, catalogue, query, false, topN, ranges, recs);
         else if (genres.empty()) recs = recommender.recommendByName(query, topN);
         else if (!genreRecommendations(recommender, catalogue, query, false, topN, genres, recs)) return false;
         // The reference finds the song it DISPLAYS with a single exact-or-substring
@@ -285,7 +352,8 @@ static bool parseTaste(int argc, char* argv[], int first, Taste& taste) {
     return true;
 }
 
-static bool playlistMode(const std::string& list, int topN, const std::vector<Recommender::FeatureRange>& ranges, const Taste& taste) {
+static bool playlistMode(const std::string& list, int topN, const std::vector<Recommender::FeatureRange>& ranges, const Taste& taste,
+                         const DiverseOpt& dv) {
     std::cout << "=== PLAYLIST MODE ===" << std::endl;
     std::vector<std::string> ids = splitList(list);
     if (ids.empty()) {
@@ -322,7 +390,10 @@ static bool playlistMode(const std::string& list, int topN, const std::vector<Re
         return false;
     }
     std::map<int, std::string>& genreMap = catalogue.genreMap;
-    const std::vector<int> recs = taste.weighted  ? recommender.recommendForPlaylist(members, topN, weights, ranges, {})
+    if (dv.on) std::cout << "Diversified: lambda " << dv.lambda << std::endl;
+    const std::vector<int> recs = dv.on           ? recommender.recommendForPlaylist(members, topN, taste.weighted ? weights : std::vector<float>(),
+                                                                                     ranges, {}, dv.lambda, dv.pool)
+                                  : taste.weighted ? recommender.recommendForPlaylist(members, topN, weights, ranges, {})
                                   : ranges.empty() ? recommender.recommendForPlaylist(members, topN)
                                                    : recommender.recommendForPlaylist(members, topN, ranges, {});
     if (recs.empty()) {
@@ -404,7 +475,13 @@ int main(int argc, char* argv[]) {
             std::cerr << "Error: --where cannot be combined with --genre" << std::endl;
             return 1;
         }
-        return recommendationMode(argv[2], mode == "--id", topN, genres, ranges) ? 0 : 1;
+        DiverseOpt dv;
+        if (!parseDiverse(argc, argv, 3, topN, dv)) return 1;
+        if (dv.on && !genres.empty()) {
+            std::cerr << "Error: --diverse cannot be combined with --genre" << std::endl;
+            return 1;
+        }
+        return recommendationMode(argv[2], mode == "--id", topN, genres, ranges, dv) ? 0 : 1;
     }
     if (mode == "--playlist") {
         if (argc < 3) {
@@ -426,7 +503,9 @@ int main(int argc, char* argv[]) {
         if (!parseWhere(argc, argv, 3, ranges)) return 1;
         Taste taste;
         if (!parseTaste(argc, argv, 3, taste)) return 1;
-        return playlistMode(argv[2], topN, ranges, taste) ? 0 : 1;
+        DiverseOpt dv;
+        if (!parseDiverse(argc, argv, 3, topN, dv)) return 1;
+        return playlistMode(argv[2], topN, ranges, taste, dv) ? 0 : 1;
     }
     std::cerr << "Error: Unknown mode '" << mode << "'" << std::endl;
     usage(argv[0]);

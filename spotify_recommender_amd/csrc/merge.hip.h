@@ -155,7 +155,7 @@ __device__ __forceinline__ void merge_body(
         // Small input (e.g. one list of topn keys per rank after the all-gather):
         // take every key in one load phase; the select / rank below does the rest.
         // (one LDS atomic per wave instead of one per key; measured on the 326 top-10 lists of a 1 M-row scan: no
-        // difference, 9.1 vs 9.3 us for the whole merge_notify_kernel — the merge is latency, not atomics)
+        // difference, 9.1 vs 9.3 us for the whole notifying merge launch — the merge is latency, not atomics)
         first = list_len;
         for (int64_t i0 = 0; i0 < total_keys; i0 += kThreads) {   // uniform trip count: every lane takes part in the ballot
             const int64_t i = i0 + tid;
@@ -446,7 +446,7 @@ __device__ __forceinline__ void merge_body(
 // separate 1024-thread merge kernel beats the last workgroup of the scan) the scan is the last one: every workgroup
 // stores its list through to device scope and counts itself out (two levels: eight group counters, then one, so
 // that no counter sees more than ~100 arrivals); the workgroup that finds itself last merges all lists — read
-// past its L2 — into the caller's buffers and, like merge_notify_kernel, raises the completion word the host
+// past its L2 — into the caller's buffers and, like merge_kernel's notifying form, raises the completion word the host
 // polls.  No fences under the scanners (see scan_q8_kernel's seed riders for what those cost) and no spinning:
 // every workgroup leaves after one atomic or two.
 struct LoneTail {
@@ -501,31 +501,25 @@ __device__ __forceinline__ void lone_tail(MergeSmem& msm, int* s_flag, const uin
 
 // ---- merge kernels (the merge body itself is defined above the streaming scan) ------
 
+// done_word: null, or — for a caller that WAITS ON THE HOST (mi355rec_query_row_topn; one workgroup) — the completion
+// word: out_idx / out_score are then device-visible addresses of pinned host memory, and after them the workgroup stores
+// `done_value` to *done_word (pinned host memory as well), so the host can poll one word instead of going through
+// hipStreamSynchronize's completion path (~3 us of a 60 us query).  (One kernel with a uniform branch at its end, where
+// there were two with one body: the library keeps to sixty kernels.)
 __global__ __launch_bounds__(kMergeBlock) void merge_kernel(
     const uint64_t* __restrict__ lists_base, int n_lists, int list_len, int64_t list_stride,
     int64_t lists_query_stride, int topk, uint64_t* __restrict__ out_keys_base,
     int64_t* __restrict__ out_idx_base, float* __restrict__ out_score_base,
-    int64_t out_query_stride) {
+    int64_t out_query_stride, uint32_t* done_word, uint32_t done_value) {
     __shared__ MergeSmemT<kMergeBlock, kMergeMaxLists, kMergeSurvCap> sm;
     merge_body(sm, lists_base, n_lists, list_len, list_stride, lists_query_stride, topk, out_keys_base, out_idx_base,
                out_score_base, out_query_stride, blockIdx.x, blockIdx.x);
-}
-
-// The same merge for a caller that WAITS ON THE HOST (mi355rec_query_row_topn): out_idx / out_score are
-// device-visible addresses of pinned host memory, and after them the workgroup stores `done_value` to
-// *done_word (pinned host memory as well), so the host can poll one word instead of going through
-// hipStreamSynchronize's completion path (~3 us of a 60 us query).
-__global__ __launch_bounds__(kMergeBlock) void merge_notify_kernel(
-    const uint64_t* __restrict__ lists_base, int n_lists, int list_len, int64_t list_stride, int topk,
-    uint64_t* __restrict__ out_keys_base, int64_t* __restrict__ out_idx_base, float* __restrict__ out_score_base,
-    uint32_t* done_word, uint32_t done_value) {
-    __shared__ MergeSmemT<kMergeBlock, kMergeMaxLists, kMergeSurvCap> sm;
-    merge_body(sm, lists_base, n_lists, list_len, list_stride, static_cast<int64_t>(0), topk, out_keys_base, out_idx_base,
-               out_score_base, static_cast<int64_t>(0), static_cast<int64_t>(0), static_cast<int64_t>(0));
-    // the waves that stored results order their stores before ... (the others have nothing to release: a system-scope
-    // fence is an L2 write-back per wave, and sixteen of them queue up)
-    if (static_cast<int>(threadIdx.x) < ((topk + 63) & ~63)) __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(done_word, done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // ... the word
+    if (done_word) {   // uniform
+        // the waves that stored results order their stores before ... (the others have nothing to release: a system-scope
+        // fence is an L2 write-back per wave, and sixteen of them queue up)
+        if (static_cast<int>(threadIdx.x) < ((topk + 63) & ~63)) __threadfence_system();
+        __syncthreads();
+        if (threadIdx.x == 0) __hip_atomic_store(done_word, done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // ... the word
+    }
 }
 }  // namespace mi355

@@ -5,6 +5,7 @@
 #include "engine_batch.hip.h"
 #include "engine_labels.hip.h"
 #include "engine_playlist.hip.h"
+#include "engine_diverse.hip.h"
 
 extern "C" {
 
@@ -810,7 +811,7 @@ int mi355rec_enqueue_merge_keys_batch(mi355rec_t* h, const mi355rec_key_t* lists
     const int slot = timing_begin(h, h->ev_merge, h->n_merge_pairs, h->merge_launches, s);
     hipLaunchKernelGGL(merge_kernel, dim3(batch), dim3(kMergeBlock), 0, s, lists_dev, n_lists, list_len,
                        list_stride, query_stride, topn, out_keys_dev, out_idx_dev, out_score_dev,
-                       static_cast<int64_t>(topn));
+                       static_cast<int64_t>(topn), static_cast<uint32_t*>(nullptr), 0u);
     timing_end(h, h->ev_merge, h->n_merge_pairs, slot, s);
     HIP_TRY(h, hipGetLastError());
     return MI355REC_OK;

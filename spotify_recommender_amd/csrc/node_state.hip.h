@@ -33,6 +33,13 @@ int set_group_labels(mi355rec_t* h, const int32_t* labels_host, int64_t n);
 // ("WEIGHTED PLAYLISTS").
 int query_mean_topn(mi355rec_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude, int topn,
                     int64_t* out_idx, float* out_score, int* out_count, const mi355rec_filter_t* filter, const float* weights);
+// mi355rec_query_mean_topn_diverse with the same longer exclusion list (engine_diverse.hip.h), and the re-rank alone over a
+// pool passed by value: `count` (<= 1024) pool rows in canonical order, their global ids, scores and features (count x 12).
+int query_mean_topn_diverse(mi355rec_t* h, const float* queries, const float* weights, int k, const int64_t* exclude_global, int n_exclude,
+                            const mi355rec_filter_t* filter, float lambda, int pool, int topn, int64_t* out_idx, float* out_score,
+                            float* out_mmr, int* out_count);
+int rerank_pool(mi355rec_t* h, const int64_t* pool_idx, const float* pool_score, const float* pool_rows, int count, float lambda, int topn,
+                int64_t* out_idx, float* out_score, float* out_mmr, int* out_count);
 }  // namespace mi355node
 
 namespace {

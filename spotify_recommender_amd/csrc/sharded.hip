@@ -52,6 +52,8 @@
 //               stream by itself, round-robin: no exchange, no merge across devices, queries/s scale with the
 //               devices for any catalogue that fits one.  Synchronous calls go to the replicas in turn.
 // A "shard" of a replicated handle is a full replica (lo = 0, hi = n).
+#include <cmath>
+
 #include "filter_check.h"
 #include "node_stream.hip.h"
 #include "weights_check.h"
@@ -797,6 +799,154 @@ int mi355rec_sharded_query_playlist_topn_weighted(mi355rec_sharded_t* h, const i
         if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
     }
     return sharded_mean(h, members, k, excl, n_exclude + k, topn, out_idx, out_score, out_count, filter, weights);
+}
+
+// ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h) -------------------------------------------------------------------------
+namespace {
+// lambda and pool (check_playlist has seen topn = pool).
+int check_diverse(mi355rec_sharded_t* h, float lambda, int pool, int topn) {
+    if (std::isnan(lambda) || lambda < 0.0f || lambda > 1.0f)
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "lambda %g out of [0, 1]", static_cast<double>(lambda));
+    if (topn <= 0) return sfail(h, MI355REC_ERR_INVALID_ARG, "topn must be positive, got %d", topn);
+    if (pool < topn || pool > MI355REC_MAX_TOPN_FAST)
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "pool %d out of [topn = %d, %d]", pool, topn, MI355REC_MAX_TOPN_FAST);
+    return MI355REC_OK;
+}
+
+// members by value and the excluded global ids, all checked: the CPU backend, one handle, or — row-sharded — the pool from
+// sharded_mean, its rows gathered from their shards (one mi355rec_fetch_rows per shard that owns any) and the re-rank on the
+// first shard's device over the pool passed by value.
+int sharded_diverse(mi355rec_sharded_t* h, const float* members, const float* weights, int k, const int64_t* excl, int n_excl,
+                    const mi355rec_filter_t* filter, float lambda, int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
+                    int* out_count) {
+    if (h->cpu) {
+        const char* why = nullptr;
+        return cpu_result(h, mi355cpu::node_query_mean_diverse(h->cpu, members, k, excl, n_excl, filter, weights, lambda, pool, topn, out_idx,
+                                                              out_score, out_mmr, out_count, &why), why);
+    }
+    DeviceRestore restore;
+    if (h->shards.size() == 1 || h->replicated) {   // one handle holds the whole catalogue (row_base 0)
+        Shard* s = &h->shards[0];
+        if (h->replicated) {
+            const int rc = take_replica(h, &s);
+            if (rc) return rc;
+        } else {
+            S_HIP(h, hipSetDevice(s->device));
+        }
+        const int rc = mi355node::query_mean_topn_diverse(s->engine, members, weights, k, excl, n_excl, filter, lambda, pool, topn, out_idx,
+                                                          out_score, out_mmr, out_count);
+        return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s->engine));
+    }
+    std::vector<int64_t> pidx, local;
+    std::vector<float> prel, rows, part;
+    std::vector<int> where;
+    try {
+        pidx.resize(static_cast<size_t>(pool));
+        prel.resize(static_cast<size_t>(pool));
+        rows.resize(static_cast<size_t>(pool) * MI355REC_DIM);
+        part.resize(static_cast<size_t>(pool) * MI355REC_DIM);
+        local.reserve(static_cast<size_t>(pool));
+        where.reserve(static_cast<size_t>(pool));
+    } catch (const std::bad_alloc&) {
+        return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for a pool of %d rows", pool);
+    }
+    int p_eff = 0;
+    int rc = sharded_mean(h, members, k, excl, n_excl, pool, pidx.data(), prel.data(), &p_eff, filter, weights);
+    if (rc) return rc;
+    if (p_eff <= 0) {
+        for (int i = 0; i < topn; ++i) {
+            out_idx[i] = -1;
+            if (out_score) out_score[i] = 0.0f;
+            if (out_mmr) out_mmr[i] = 0.0f;
+        }
+        if (out_count) *out_count = 0;
+        return MI355REC_OK;
+    }
+    for (Shard& s : h->shards) {
+        if (s.hi <= s.lo) continue;
+        local.clear();
+        where.clear();
+        for (int i = 0; i < p_eff; ++i)
+            if (pidx[static_cast<size_t>(i)] >= s.lo && pidx[static_cast<size_t>(i)] < s.hi) {
+                local.push_back(pidx[static_cast<size_t>(i)] - s.lo);
+                where.push_back(i);
+            }
+        if (local.empty()) continue;
+        S_HIP(h, hipSetDevice(s.device));
+        rc = mi355rec_fetch_rows(s.engine, local.data(), static_cast<int64_t>(local.size()), part.data());
+        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", s.device, mi355rec_last_error(s.engine));
+        for (size_t j = 0; j < where.size(); ++j)
+            std::memcpy(rows.data() + static_cast<size_t>(where[j]) * MI355REC_DIM, part.data() + j * MI355REC_DIM, sizeof(float) * MI355REC_DIM);
+    }
+    Shard* first = nullptr;
+    for (Shard& s : h->shards)
+        if (s.hi > s.lo) {
+            first = &s;
+            break;
+        }
+    S_HIP(h, hipSetDevice(first->device));
+    rc = mi355node::rerank_pool(first->engine, pidx.data(), prel.data(), rows.data(), p_eff, lambda, topn, out_idx, out_score, out_mmr, out_count);
+    return rc == MI355REC_OK ? rc : sfail(h, rc, "shard on device %d: %s", first->device, mi355rec_last_error(first->engine));
+}
+}  // namespace
+
+int mi355rec_sharded_query_mean_topn_diverse(mi355rec_sharded_t* h, const float* queries, const float* weights, int k,
+                                             const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
+                                             float lambda, int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
+                                             int* out_count) {
+    if (!h || !queries || !out_idx) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    int rc = check_diverse(h, lambda, pool, topn);
+    if (!rc) rc = check_playlist(h, queries, k, exclude_global, n_exclude, pool, out_idx);
+    if (!rc) rc = check_filter(h, filter);
+    if (!rc) rc = check_weights(h, weights, k);
+    if (rc) return rc;
+    return sharded_diverse(h, queries, weights, k, exclude_global, n_exclude, filter, lambda, pool, topn, out_idx, out_score, out_mmr,
+                           out_count);
+}
+
+int mi355rec_sharded_query_playlist_topn_diverse(mi355rec_sharded_t* h, const int64_t* global_rows, const float* weights, int k,
+                                                 const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
+                                                 float lambda, int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
+                                                 int* out_count) {
+    if (!h || !global_rows || !out_idx) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    int rc = check_diverse(h, lambda, pool, topn);
+    if (!rc) rc = check_playlist(h, global_rows, k, exclude_global, n_exclude, pool, out_idx);
+    if (rc) return rc;
+    for (int m = 0; m < k; ++m)
+        if (global_rows[m] < 0 || global_rows[m] >= h->n)
+            return sfail(h, MI355REC_ERR_INVALID_ARG, "Invalid song index: %lld", (long long)global_rows[m]);
+    rc = check_filter(h, filter);
+    if (!rc) rc = check_weights(h, weights, k);
+    if (rc) return rc;
+    if (!h->cpu && h->shards.size() == 1 && !h->replicated) {   // one handle: its own by-row call (the members stay on the device)
+        DeviceRestore restore;
+        Shard& s = h->shards[0];
+        S_HIP(h, hipSetDevice(s.device));
+        rc = mi355rec_query_playlist_topn_diverse(s.engine, global_rows, weights, k, exclude_global, n_exclude, filter, lambda, pool, topn,
+                                                  out_idx, out_score, out_mmr, out_count);
+        return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s.engine));
+    }
+    // the members by value (fetched once) and their rows added to the exclusion list
+    float members[MI355REC_MAX_PLAYLIST * MI355REC_DIM];
+    int64_t excl[MI355REC_MAX_EXCLUDE + MI355REC_MAX_PLAYLIST];
+    for (int i = 0; i < n_exclude; ++i) excl[i] = exclude_global[i];
+    for (int m = 0; m < k; ++m) {
+        excl[n_exclude + m] = global_rows[m];
+        if (h->cpu) {
+            std::memcpy(members + m * MI355REC_DIM, mi355cpu::row(mi355cpu::node_catalogue(h->cpu), global_rows[m]), sizeof(float) * MI355REC_DIM);
+            continue;
+        }
+        if (m == 0) {
+            rc = drain_workers(h);
+            if (rc) return rc;
+        }
+        DeviceRestore restore;
+        const Shard* own = owner_of(h, global_rows[m]);
+        S_HIP(h, hipSetDevice(own->device));
+        rc = mi355rec_fetch_row(own->engine, global_rows[m] - own->lo, members + m * MI355REC_DIM);
+        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
+    }
+    return sharded_diverse(h, members, weights, k, excl, n_exclude + k, filter, lambda, pool, topn, out_idx, out_score, out_mmr, out_count);
 }
 
 int mi355rec_sharded_scores_row(mi355rec_sharded_t* h, int64_t global_row, float* out_host) {

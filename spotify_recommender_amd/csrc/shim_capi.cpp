@@ -224,6 +224,22 @@ int64_t shim_recommend_for_taste(void* h, const int* liked, int n_liked, const i
                                                 dislike_weight),
                     out, scores, cap);
 }
+// recommendDiverse and the diversified recommendForPlaylist (n_weights 0: no weights).
+int64_t shim_recommend_diverse(void* h, int song, int topn, float lambda, int pool, const int* features, const float* lo, const float* hi,
+                               int n_ranges, int* out, float* scores, int64_t cap) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    return giveBack(c, c->rec.recommendDiverse(song, topn, lambda, pool, ranges(features, lo, hi, n_ranges)), out, scores, cap);
+}
+int64_t shim_recommend_for_playlist_diverse(void* h, const int* songs, int n_songs, const float* weights, int n_weights, int topn,
+                                            const int* features, const float* lo, const float* hi, int n_ranges, const int* exclude,
+                                            int n_exclude, float lambda, int pool, int* out, float* scores, int64_t cap) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    return giveBack(c, c->rec.recommendForPlaylist(std::vector<int>(songs, songs + (n_songs > 0 ? n_songs : 0)), topn,
+                                                   std::vector<float>(weights, weights + (n_weights > 0 ? n_weights : 0)),
+                                                   ranges(features, lo, hi, n_ranges),
+                                                   std::vector<int>(exclude, exclude + (n_exclude > 0 ? n_exclude : 0)), lambda, pool),
+                    out, scores, cap);
+}
 int shim_similarities(void* h, int idx, float* out_n) {
     Catalogue* c = static_cast<Catalogue*>(h);
     std::vector<float> v;

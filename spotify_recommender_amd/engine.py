@@ -94,6 +94,32 @@ def _weighted_query(fn, h, check, members, weights, exclude, where, topn: int) -
                            check, members, exclude, topn)
 
 
+def _diverse_query(fn, h, check, members, weights, exclude, where, lam, pool, topn: int, return_mmr: bool):
+    """Runs one diversified entry point (DIVERSIFIED TOP-N): fn(h, members, weights or NULL, k, exclude, n_exclude, filter or
+    NULL, lambda, pool, topn, idx, score, mmr, &count).  `lam` in [0, 1] (1: relevance only); `pool`: how many of the most
+    relevant rows the picks are made from, None = min(1024, max(topn, 4 * topn)).  Results come in pick order; the scores are
+    the relevance; with return_mmr a third array holds the mmr value of each pick."""
+    if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)):
+        raise ValueError(f"lam must be a number in [0, 1], got {lam!r}")
+    if pool is None:
+        pool = min(1024, max(int(topn), 4 * int(topn)))
+    elif isinstance(pool, bool) or not isinstance(pool, (int, np.integer)):
+        raise ValueError(f"pool must be an integer or None, got {pool!r}")
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+        if w.size != members.shape[0]:
+            raise ValueError(f"{w.size} weights for {members.shape[0]} songs: one weight per song")
+    flt = ctypes.byref(make_filter(where)) if where is not None else None
+    mmr = np.zeros(max(int(topn), 1), dtype=np.float32)
+    wp = w.ctypes.data_as(ctypes.c_void_p) if w is not None else None
+    idx, score = _playlist_query(
+        lambda h_, m, k, e, n_e, topn_, i_, s_, c_: fn(h_, m, wp, k, e, n_e, flt, ctypes.c_float(float(lam)), int(pool), topn_, i_, s_,
+                                                       mmr.ctypes.data_as(ctypes.c_void_p), c_),
+        h, check, members, exclude, topn)
+    return (idx, score, mmr[:idx.size].copy()) if return_mmr else (idx, score)
+
+
 def _np_members(queries) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(queries, dtype=np.float32).reshape(-1, capi.DIM))
 
@@ -468,6 +494,27 @@ class CosineEngine:
                                 topn)
         return _playlist_query(self._lib.mi355rec_query_playlist_topn, self._h, check, _np_rows(local_rows), exclude, topn)
 
+    # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h): MMR picks from the top-`pool` of the weighted playlist call ----
+    def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False):
+        """`topn` rows picked greedily from the `pool` most relevant (query_mean_topn's order): each pick maximises
+        lam * relevance - (1 - lam) * (its largest similarity to a row already picked).  Pick order; scores = relevance."""
+        return _diverse_query(self._lib.mi355rec_query_mean_topn_diverse, self._h, lambda rc: capi.check(rc, self._h),
+                              _np_members(queries), weights, exclude, where, lam, pool, topn, return_mmr)
+
+    def query_playlist_topn_diverse(self, local_rows, topn: int, lam, pool=None, exclude=None, where=None, weights=None,
+                                    return_mmr=False):
+        """The same for members given as rows of this handle (never returned)."""
+        return _diverse_query(self._lib.mi355rec_query_playlist_topn_diverse, self._h, lambda rc: capi.check(rc, self._h),
+                              _np_rows(local_rows), weights, exclude, where, lam, pool, topn, return_mmr)
+
+    def fetch_rows(self, local_rows) -> np.ndarray:
+        """The features of the listed rows (any order, duplicates allowed), gathered on the device: (len, 12) float32."""
+        rows = _np_rows(local_rows)
+        out = np.empty((rows.size, capi.DIM), dtype=np.float32)
+        capi.check(self._lib.mi355rec_fetch_rows(self._h, rows.ctypes.data_as(ctypes.c_void_p), int(rows.size),
+                                                 out.ctypes.data_as(ctypes.c_void_p)), self._h)
+        return out
+
     def playlist_counters(self) -> dict:
         q, r = ctypes.c_int64(0), ctypes.c_int64(0)
         capi.check(self._lib.mi355rec_playlist_counters(self._h, ctypes.byref(q), ctypes.byref(r)), self._h)
@@ -607,6 +654,16 @@ class NodeEngine:
                                 exclude, where, topn)
         return _playlist_query(self._lib.mi355rec_sharded_query_playlist_topn, self._h, self._check, _np_rows(global_rows), exclude,
                                topn)
+
+    # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h) over the whole node ----
+    def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False):
+        return _diverse_query(self._lib.mi355rec_sharded_query_mean_topn_diverse, self._h, self._check, _np_members(queries), weights,
+                              exclude, where, lam, pool, topn, return_mmr)
+
+    def query_playlist_topn_diverse(self, global_rows, topn: int, lam, pool=None, exclude=None, where=None, weights=None,
+                                    return_mmr=False):
+        return _diverse_query(self._lib.mi355rec_sharded_query_playlist_topn_diverse, self._h, self._check, _np_rows(global_rows),
+                              weights, exclude, where, lam, pool, topn, return_mmr)
 
     def scores_row(self, global_row: int) -> np.ndarray:
         out = np.empty(self.rows, dtype=np.float32)

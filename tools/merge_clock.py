@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Where the merge launch of a query alone spends its time (merge_notify_kernel; a -DMI355REC_PHASE_CLOCK build, --lib):
+"""Where the merge launch of a query alone spends its time (merge_kernel with a completion word; a -DMI355REC_PHASE_CLOCK build, --lib):
   python3 tools/merge_clock.py --lib gpurun_out/q8/libmi355rec_phase.so --rows 1000000 --topn 10"""
 import argparse, ctypes, json, sys
 from pathlib import Path
