@@ -13,8 +13,10 @@ from tests.parity import assert_topn_matches
 pytestmark = pytest.mark.gpu
 
 
-def make_catalogue(rng, rows):
-    kind = rng.integers(0, 7)
+def make_catalogue(rng, rows, kind=None):
+    """One of seven kinds of catalogue: drawn from `rng`, or the `kind` asked for (tests/playlist_sweep_cases.py)."""
+    if kind is None:
+        kind = rng.integers(0, 7)
     if kind == 0:
         f = rng.random((rows, 12), dtype=np.float32)
     elif kind == 1:   # few distinct values per feature -> massive exact ties
