@@ -129,6 +129,23 @@ public:
                                           const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude, float lambda,
                                           int pool = 0);
 
+    // Extension: at most maxPerArtist results per artist (group caps).  initialize(songs) derives one group id per song from
+    // Song::artists: the key is the bytes before the first ';' (the primary artist of the CSV's artists column), matched
+    // exactly; an empty key means no group (the song is never capped).  After the matrix overload of initialize,
+    // setGroupIds gives the ids (one per song; >= 0 a group, -1 none); artistGroupIds derives them from artists strings
+    // the same way.  The groups reach the engine on the first capped call.  recommendByIndexCapped is recommendDiverse
+    // with the cap (lambda = 1: the most similar songs in order, those beyond an artist's cap skipped); pool = 0 means
+    // min(1024, max(topN, 8 * topN)).  Fewer than topN results come back when the pool holds no more eligible songs: raise
+    // pool.  The overload of recommendForPlaylist takes the cap after pool.  maxPerArtist < 1 or unknown groups give {} and
+    // a message; everything else as for the diversified forms.
+    static std::vector<int> artistGroupIds(const std::vector<std::string>& artists);
+    bool setGroupIds(const std::vector<int>& groupIds);
+    std::vector<int> recommendByIndexCapped(int songIndex, int topN, int maxPerArtist, float lambda = 1.0f, int pool = 0,
+                                            const std::vector<FeatureRange>& where = {});
+    std::vector<int> recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
+                                          const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude, float lambda,
+                                          int pool, int maxPerArtist);
+
     struct Impl;   // opaque: defined in Recommender.cpp
 
 private:

@@ -22,6 +22,8 @@
  *     (mi355rec_query_mean_topn_weighted, _query_playlist_topn_weighted and their node-handle twins);
  *   - DIVERSIFIED TOP-N: the weighted playlist call's top-`pool`, re-ranked by maximal marginal relevance over the 12
  *     features (mi355rec_query_mean_topn_diverse, _query_playlist_topn_diverse, their node-handle twins, mi355rec_fetch_rows);
+ *   - group caps: "at most M results per artist" inside the same re-rank (mi355rec_set_groups, the _capped calls and their
+ *     node-handle twins);
  *   - test hooks, compiled in only with -DMI355REC_TEST_HOOKS (spotify_recommender_amd/build.py builds
  *     libmi355rec_testhooks.so for tests/; the product library does not export them).
  */
@@ -528,6 +530,53 @@ int mi355rec_sharded_query_playlist_topn_diverse(mi355rec_sharded_t* h, const in
                                                  const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
                                                  float lambda, int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
                                                  int* out_count);
+
+/* GROUP CAPS (an extension beyond the reference): "at most two per artist".
+ * mi355rec_set_groups gives every row of the handle one int32 (n must be the handle's row count): a value >= 0 is a group id
+ * (only equality matters: ids have no upper limit and need not be dense), -1 means ungrouped (never capped), any other
+ * negative value is INVALID_ARG.  NULL drops the groups, a second call replaces them, a failed call leaves the previous ones.
+ * Device cost: 4 B per row, a plain array in local row order; no copy of the rows is made.  Lanes share the array as they
+ * share labels: a handle that has lanes refuses the call, a lane made afterwards shares the groups without a copy.
+ * The _capped calls are the _diverse calls above (weights, filter and out_mmr may be NULL; a single query is k = 1) plus
+ * `max_per_group` and `out_pool_rows` (may be NULL).  The pool, rel, c(i, p), mu, pen, mmr and the tie rule are those of the
+ * _diverse calls bit for bit; with g_i the group of pool row i,
+ *   - an unpicked pool row is ELIGIBLE at a step iff g_i == -1 or fewer than max_per_group already-picked rows have group g_i;
+ *   - each step picks the eligible row with the largest mmr_i (IEEE >, a tie goes to the earlier pool position); pen is
+ *     updated after every pick; the loop ends after topn picks or when no row is eligible;
+ *   - *out_count = the number of picks, possibly below min(topn, P'); padding -1 / 0 / 0;
+ *   - *out_pool_rows = P'.  count < topn with P' == pool: the pool ran out, raise `pool`; with P' < pool: the catalogue has
+ *     no more.
+ * Identities, bit for bit (ids, scores, mmr): max_per_group >= topn, or every group -1, gives the _diverse result;
+ * lambda = 1.0f gives the walk of the pool in canonical order that takes a row iff it is ungrouped or fewer than
+ * max_per_group earlier-taken rows share its group (the pool rows whose rank inside their group is below max_per_group, the
+ * first topn of them), with out_mmr == out_score; no group id >= 0 occurs more than max_per_group times in any result; the
+ * result does not depend on shard count, placement, lane or replica mode.
+ * INVALID_ARG (with a message): every case of the _diverse calls; max_per_group < 1; a handle without groups.
+ * mi355rec_playlist_counters counts these calls too.
+ * Device: the launches of the _diverse call; mmr_rerank_kernel takes the groups and the cap as two more arguments.  In the
+ * serial loop a thread counts the picks of its own group and retires at the cap; lambda == 1.0f takes a loop-free path
+ * (rank in group, prefix sum over the kept rows) with the same result.
+ * Node handle: one shard forwards mi355rec_sharded_set_groups and the calls; a replicated placement gives every replica the
+ * whole array (a failure drops the groups on every replica); a row-sharded one keeps the host copy in the node handle and
+ * passes the pool's groups to the re-rank by value, next to the pool's rows.  The CPU backend keeps a host copy and serves
+ * the same calls with the same arithmetic. */
+int mi355rec_set_groups(mi355rec_t* h, const int32_t* groups_host, int64_t n);
+int mi355rec_sharded_set_groups(mi355rec_sharded_t* h, const int32_t* groups_host, int64_t n);
+int mi355rec_query_mean_topn_capped(mi355rec_t* h, const float* queries, const float* weights, int k, const int64_t* exclude_global,
+                                    int n_exclude, const mi355rec_filter_t* filter, float lambda, int pool, int max_per_group, int topn,
+                                    int64_t* out_idx, float* out_score, float* out_mmr, int* out_count, int* out_pool_rows);
+int mi355rec_query_playlist_topn_capped(mi355rec_t* h, const int64_t* local_rows, const float* weights, int k,
+                                        const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter, float lambda,
+                                        int pool, int max_per_group, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
+                                        int* out_count, int* out_pool_rows);
+int mi355rec_sharded_query_mean_topn_capped(mi355rec_sharded_t* h, const float* queries, const float* weights, int k,
+                                            const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
+                                            float lambda, int pool, int max_per_group, int topn, int64_t* out_idx, float* out_score,
+                                            float* out_mmr, int* out_count, int* out_pool_rows);
+int mi355rec_sharded_query_playlist_topn_capped(mi355rec_sharded_t* h, const int64_t* global_rows, const float* weights, int k,
+                                                const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
+                                                float lambda, int pool, int max_per_group, int topn, int64_t* out_idx, float* out_score,
+                                                float* out_mmr, int* out_count, int* out_pool_rows);
 
 #ifdef MI355REC_TEST_HOOKS
 /* TEST HOOK for the cross-workgroup hand-offs of the streamed scans (csrc/replica.hip.h, "hand-offs that fail

@@ -199,6 +199,16 @@ SIGNATURES = {
     "mi355rec_sharded_query_playlist_topn_diverse": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_float,
                                                              c_int, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_int)]),
     "mi355rec_fetch_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "mi355rec_set_groups": (c_int, [c_void_p, c_void_p, c_int64]),
+    "mi355rec_sharded_set_groups": (c_int, [c_void_p, c_void_p, c_int64]),
+    "mi355rec_query_mean_topn_capped": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_float, c_int, c_int, c_int,
+        c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "mi355rec_query_playlist_topn_capped": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_float, c_int, c_int, c_int,
+        c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "mi355rec_sharded_query_mean_topn_capped": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_float, c_int, c_int, c_int,
+        c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "mi355rec_sharded_query_playlist_topn_capped": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_float, c_int, c_int, c_int,
+        c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]),
     "mi355rec_pack_key": (c_uint64, [c_float, c_int64]),
     "mi355rec_key_score": (c_float, [c_uint64]),
     "mi355rec_key_row": (c_int64, [c_uint64]),

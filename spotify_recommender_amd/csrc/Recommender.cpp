@@ -29,6 +29,10 @@ struct Recommender::Impl {
     std::vector<int> genreIds;
     bool labelsUploaded = false;
 
+    // group ids of the songs (one per song, -1 = none; empty: not known): uploaded by the first capped query, likewise
+    std::vector<int> groupIds;
+    bool groupsUploaded = false;
+
     std::vector<int64_t> idxBuf;
     std::vector<float> scoreBuf;
     std::vector<float> lastScores;
@@ -71,6 +75,12 @@ bool Recommender::initialize(const std::vector<Song>& songs) {  // Recommender.c
     impl_->byId.clear();
     impl_->byId.reserve(songs.size() * 2);
     impl_->genreIds.resize(songs.size());
+    {
+        std::vector<std::string> artists;
+        artists.reserve(songs.size());
+        for (const Song& s : songs) artists.push_back(s.artists);
+        impl_->groupIds = artistGroupIds(artists);
+    }
     for (size_t i = 0; i < songs.size(); ++i) {
         std::copy(songs[i].features, songs[i].features + FEATURE_COUNT, matrix.begin() + i * FEATURE_COUNT);
         impl_->genreIds[i] = songs[i].genre_id;
@@ -100,6 +110,7 @@ bool Recommender::initialize(const std::vector<float>& features, const std::vect
         impl_->byId.emplace(trackIds[i], static_cast<int>(i));
     }
     impl_->genreIds.clear();
+    impl_->groupIds.clear();
     return startEngine(impl_, features.data(), trackIds.size());
 }
 
@@ -113,6 +124,7 @@ bool startEngine(Recommender::Impl* impl, const float* matrix, size_t n) {
     impl->initialized = false;
     impl->gpuEnabled = false;
     impl->labelsUploaded = false;
+    impl->groupsUploaded = false;
     impl->numSongs = static_cast<int>(n);
     // The reference pins device 0 (Recommender.cu:124).  Here the library places the catalogue itself: one device up
     // to 7.9 M rows, row-sharded over as many as keep 4 M rows per shard beyond that (one process, one stream per
@@ -189,6 +201,32 @@ std::vector<int> Recommender::recommendByIndex(int songIndex, int topN) {  // Re
     for (int i = 0; i < count; ++i) results[i] = static_cast<int>(impl_->idxBuf[i]);
     impl_->lastScores.assign(impl_->scoreBuf.begin(), impl_->scoreBuf.begin() + count);
     return results;
+}
+
+std::vector<int> Recommender::artistGroupIds(const std::vector<std::string>& artists) {
+    std::vector<int> ids(artists.size(), -1);
+    std::unordered_map<std::string, int> seen;   // primary artist -> id, in order of first appearance
+    for (size_t i = 0; i < artists.size(); ++i) {
+        const std::string key = artists[i].substr(0, artists[i].find(';'));
+        if (key.empty()) continue;
+        ids[i] = seen.emplace(key, static_cast<int>(seen.size())).first->second;
+    }
+    return ids;
+}
+
+bool Recommender::setGroupIds(const std::vector<int>& groupIds) {
+    if (!impl_->initialized || groupIds.size() != static_cast<size_t>(impl_->numSongs)) {
+        std::cerr << "Error: one group id per song is needed" << std::endl;
+        return false;
+    }
+    for (int g : groupIds)
+        if (g < -1) {
+            std::cerr << "Error: group id " << g << ": a group id is >= 0, or -1 for no group" << std::endl;
+            return false;
+        }
+    impl_->groupIds = groupIds;
+    impl_->groupsUploaded = false;
+    return true;
 }
 
 bool Recommender::setGenreIds(const std::vector<int>& genreIds) {
@@ -273,6 +311,8 @@ bool makeFilter(const std::vector<Recommender::FeatureRange>& where, mi355rec_fi
 struct Diverse {
     float lambda;
     int pool;
+    int maxPerGroup = 0;   // > 0: the capped entry point (GROUP CAPS; pool 0: min(1024, max(topN, 8 topN)))
+    bool capped = false;
 };
 
 // recommendForPlaylist with a filter (null: the unfiltered entry point) and weights (null: the entry points without them;
@@ -310,13 +350,36 @@ std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& 
     int pool = 0;
     if (diverse) {
         pool = diverse->pool;
-        if (pool == 0) pool = std::min(MI355REC_MAX_TOPN_FAST, std::max(topN, 4 * std::min(topN, MI355REC_MAX_TOPN_FAST)));
+        if (pool == 0)
+            pool = std::min(MI355REC_MAX_TOPN_FAST, std::max(topN, (diverse->capped ? 8 : 4) * std::min(topN, MI355REC_MAX_TOPN_FAST)));
         if (pool < 0) {
             std::cerr << "Error: pool must be positive (or 0 for the default)" << std::endl;
             return {};
         }
     }
-    const int rc = diverse ? mi355rec_sharded_query_playlist_topn_diverse(impl->engine, rows.data(), weights, static_cast<int>(rows.size()),
+    if (diverse && diverse->capped) {
+        if (diverse->maxPerGroup < 1) {
+            std::cerr << "Error: maxPerArtist must be positive" << std::endl;
+            return {};
+        }
+        if (!impl->groupsUploaded) {   // the first capped query hands the songs' groups to the engine
+            if (impl->groupIds.size() != static_cast<size_t>(impl->numSongs)) {
+                std::cerr << "Error: the songs' group ids are not known (setGroupIds)" << std::endl;
+                return {};
+            }
+            if (mi355rec_sharded_set_groups(impl->engine, impl->groupIds.data(), impl->numSongs) != MI355REC_OK) {
+                std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
+                return {};
+            }
+            impl->groupsUploaded = true;
+        }
+    }
+    const int rc = diverse && diverse->capped
+                       ? mi355rec_sharded_query_playlist_topn_capped(impl->engine, rows.data(), weights, static_cast<int>(rows.size()),
+                                                                     excl.data(), static_cast<int>(excl.size()), filter, diverse->lambda,
+                                                                     pool, diverse->maxPerGroup, topN, impl->idxBuf.data(),
+                                                                     impl->scoreBuf.data(), nullptr, &count, nullptr)
+                   : diverse ? mi355rec_sharded_query_playlist_topn_diverse(impl->engine, rows.data(), weights, static_cast<int>(rows.size()),
                                                                           excl.data(), static_cast<int>(excl.size()), filter, diverse->lambda,
                                                                           pool, topN, impl->idxBuf.data(), impl->scoreBuf.data(), nullptr,
                                                                           &count)
@@ -374,6 +437,25 @@ std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songI
     if (!makeFilter(where, f)) return {};
     const Diverse d{lambda, pool};
     return playlistQuery(impl_, songIndices, topN, alsoExclude, where.empty() ? nullptr : &f, weights.empty() ? nullptr : weights.data(), &d);
+}
+
+std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
+                                                   const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude, float lambda,
+                                                   int pool, int maxPerArtist) {
+    if (!weights.empty() && weights.size() != songIndices.size()) {
+        std::cerr << "Error: " << weights.size() << " weights for " << songIndices.size() << " songs (one weight per song, or none)" << std::endl;
+        return {};
+    }
+    mi355rec_filter_t f;
+    if (!makeFilter(where, f)) return {};
+    const Diverse d{lambda, pool, maxPerArtist, true};
+    return playlistQuery(impl_, songIndices, topN, alsoExclude, where.empty() ? nullptr : &f, weights.empty() ? nullptr : weights.data(), &d);
+}
+
+std::vector<int> Recommender::recommendByIndexCapped(int songIndex, int topN, int maxPerArtist, float lambda, int pool,
+                                                     const std::vector<FeatureRange>& where) {
+    if (!checkQuery(impl_, songIndex, topN)) return {};
+    return recommendForPlaylist({songIndex}, topN, {}, where, {}, lambda, pool, maxPerArtist);
 }
 
 std::vector<int> Recommender::recommendDiverse(int songIndex, int topN, float lambda, int pool, const std::vector<FeatureRange>& where) {

@@ -262,6 +262,8 @@ struct Node {
     int64_t st_queries = 0, st_windows = 0, st_ns = 0;
     std::vector<int32_t> labels;          // mi355rec_sharded_set_labels: one per row, -1 = unlabelled (empty: none set)
     bool has_labels = false;
+    std::vector<int32_t> groups;          // mi355rec_sharded_set_groups: one per row, -1 = ungrouped
+    bool has_groups = false;
 };
 
 Node* node_create(const float* feats_rowmajor, int64_t n) {
@@ -327,6 +329,31 @@ int node_set_labels(Node* h, const int32_t* labels, int64_t n, const char** why)
         return MI355REC_ERR_OUT_OF_MEMORY;   // (assign gives the strong guarantee: the previous labels stay)
     }
     h->has_labels = true;
+    return MI355REC_OK;
+}
+
+int node_set_groups(Node* h, const int32_t* groups, int64_t n, const char** why) {
+    if (!groups) {
+        h->groups.clear();
+        h->has_groups = false;
+        return MI355REC_OK;
+    }
+    if (n != rows(h->cat)) {
+        *why = "the group count must equal the catalogue's rows";
+        return MI355REC_ERR_INVALID_ARG;
+    }
+    for (int64_t i = 0; i < n; ++i)
+        if (groups[i] < -1) {
+            *why = "a group id is >= 0, or -1 for no group";
+            return MI355REC_ERR_INVALID_ARG;
+        }
+    try {
+        h->groups.assign(groups, groups + n);
+    } catch (const std::bad_alloc&) {
+        *why = "out of host memory";
+        return MI355REC_ERR_OUT_OF_MEMORY;   // (the previous groups stay)
+    }
+    h->has_groups = true;
     return MI355REC_OK;
 }
 
@@ -426,11 +453,19 @@ int node_query_mean(Node* h, const float* members, int k, const int64_t* exclude
 // over P' <= 1024 rows.  mmr = fl(fl(lambda rel) - fl(mu pen)): multiply, round, subtract, round (-ffp-contract=off).
 int node_query_mean_diverse(Node* h, const float* members, int k, const int64_t* exclude, int n_exclude, const mi355rec_filter_t* filter,
                             const float* weights, float lambda, int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
-                            int* out_count, const char** why) {
+                            int* out_count, const char** why, int max_per_group, int* out_pool_rows) {
+    const bool capped = max_per_group > 0;   // GROUP CAPS
+    if (out_pool_rows) *out_pool_rows = 0;
+    if (capped && !h->has_groups) {
+        *why = "this handle has no groups (mi355rec_sharded_set_groups)";
+        return MI355REC_ERR_INVALID_ARG;
+    }
     std::vector<int64_t> pidx;
     std::vector<float> prel, pen, qn;
     std::vector<char> picked;
+    std::vector<int> seen;   // per pool row: the picked rows of its group so far
     try {
+        if (capped) seen.assign(static_cast<size_t>(pool), 0);
         pidx.resize(static_cast<size_t>(pool));
         prel.resize(static_cast<size_t>(pool));
         pen.assign(static_cast<size_t>(pool), 0.0f);
@@ -443,9 +478,11 @@ int node_query_mean_diverse(Node* h, const float* members, int k, const int64_t*
     int p_eff = 0;
     const int rc = node_query_mean(h, members, k, exclude, n_exclude, pool, pidx.data(), prel.data(), &p_eff, why, filter, weights);
     if (rc != MI355REC_OK) return rc;
+    if (out_pool_rows) *out_pool_rows = p_eff;
     const float* f = h->cat->feats.data();
     const float mu = 1.0f - lambda;
-    const int picks = topn < p_eff ? topn : p_eff;
+    int picks = topn < p_eff ? topn : p_eff;   // (capped: at most so many)
+    auto group_of = [&](int i) { return h->groups[static_cast<size_t>(pidx[static_cast<size_t>(i)])]; };
     for (int i = 0; i < p_eff; ++i) qn[static_cast<size_t>(i)] = query_norm(f + pidx[static_cast<size_t>(i)] * kDim);
     for (int t = 0; t < topn; ++t) {
         if (t >= picks) {
@@ -458,6 +495,7 @@ int node_query_mean_diverse(Node* h, const float* members, int k, const int64_t*
         float best_mmr = 0.0f;
         for (int i = 0; i < p_eff; ++i) {
             if (picked[static_cast<size_t>(i)]) continue;
+            if (capped && group_of(i) >= 0 && seen[static_cast<size_t>(i)] >= max_per_group) continue;   // not eligible
             const float a = lambda * prel[static_cast<size_t>(i)];
             const float b = mu * pen[static_cast<size_t>(i)];
             const float mmr = a - b;
@@ -466,7 +504,14 @@ int node_query_mean_diverse(Node* h, const float* members, int k, const int64_t*
                 best_mmr = mmr;
             }
         }
+        if (best < 0) {   // (capped only) nothing is eligible: the loop ends, the rest is padding
+            picks = t;
+            --t;
+            continue;
+        }
         picked[static_cast<size_t>(best)] = 1;
+        if (capped && group_of(best) >= 0)
+            for (int i = 0; i < p_eff; ++i) seen[static_cast<size_t>(i)] += group_of(i) == group_of(best);
         out_idx[t] = pidx[static_cast<size_t>(best)];
         if (out_score) out_score[t] = prel[static_cast<size_t>(best)];
         if (out_mmr) out_mmr[t] = best_mmr;

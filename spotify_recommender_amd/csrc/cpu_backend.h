@@ -70,7 +70,11 @@ int node_query_mean(Node* h, const float* members, int k, const int64_t* exclude
 // lambda in [0, 1] and topn <= pool <= 1024 are checked by the caller.  out_score and out_mmr may be null.
 int node_query_mean_diverse(Node* h, const float* members, int k, const int64_t* exclude, int n_exclude, const mi355rec_filter_t* filter,
                             const float* weights, float lambda, int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
-                            int* out_count, const char** why);
+                            int* out_count, const char** why, int max_per_group = 0, int* out_pool_rows = nullptr);
+// GROUP CAPS (include/mi355rec_diag.h): one group id per row (>= 0, or -1 = never capped; null drops them).  A positive
+// max_per_group above makes node_query_mean_diverse the capped call: a row is eligible while fewer than max_per_group picked
+// rows share its group; the loop ends when nothing is eligible; *out_pool_rows = P'.
+int node_set_groups(Node* h, const int32_t* groups, int64_t n, const char** why);
 int node_set_window(Node* h, int window, const char** why);
 int node_enqueue(Node* h, const float* q12, int64_t exclude, int topn, int64_t* ticket, const char** why);
 int node_flush(Node* h);

@@ -16,7 +16,15 @@
 //   staged   rows[i] is pool row i, passed by value (a row-sharded node gathers the pool from its shards first);
 //   rows_out the gather alone: row i of the listed keys is stored to rows_out[i] and nothing is ranked
 //            (mi355rec_fetch_rows).
-// 104 B of kernel arguments, no scratch: nothing is indexed dynamically in registers.
+//
+// GROUP CAPS (include/mi355rec_diag.h, "GROUP CAPS"): groups != null adds "at most max_per_group picks per group id >= 0".
+// Thread i keeps its row's group and the number of picked rows of that group in registers; the groups also sit in LDS, so
+// the winner's group is one more broadcast read next to its features; a thread whose count reaches the cap retires.  A
+// step in which no wave has a live lane leaves every wave key 0 and ends the loop for all threads at once: the number of
+// picks is known only at run time.  lambda == 1.0f with groups takes no loop at all (mmr_i = rel_i and the picks are the
+// pool in order): rank inside the group by broadcast reads of the earlier positions' groups, keep the rows whose rank is
+// below the cap, a workgroup-wide prefix sum over the kept rows (ballot, popcount, wave totals in LDS) gives the slot.
+// 128 B of kernel arguments, no scratch: nothing is indexed dynamically in registers.
 #pragma once
 
 #include "core.hip.h"
@@ -34,15 +42,19 @@ struct MmrSmem {
     float pick_mmr[kMmrBlockMax];
     unsigned short pick_pos[kMmrBlockMax];
     uint64_t wave_key[2][kMmrWavesMax];
+    alignas(16) int grp[kMmrBlockMax];     // the pool rows' groups (GROUP CAPS; -1 where there is no row), read as int4
     int first_empty;
 };
+static_assert(sizeof(MmrSmem) <= 64 * 1024, "mmr_rerank_kernel's LDS is static: 64 KB at most");
 
 // keys[0..pool): sorted pool keys (score image << 32 | ~global row), 0-padded.  rows: this shard's matrix (n rows from global
-// row `row_base`), or — staged != 0 — `pool` rows in pool order.  Launch: 1 workgroup of (pool rounded up to 64) threads.
+// row `row_base`), or — staged != 0 — `pool` rows in pool order.  groups: null, or one int32 per row of `rows` (so, staged,
+// the pool's groups in pool order).  out_pool_rows: null, or where P' goes.  Launch: 1 workgroup of (pool rounded up to 64) threads.
 __global__ __launch_bounds__(kMmrBlockMax) void mmr_rerank_kernel(
     const uint64_t* __restrict__ keys, const float* __restrict__ rows, int64_t n, int64_t row_base, int staged, int pool, int topn,
     float lambda, float mu, int64_t* __restrict__ out_idx, float* __restrict__ out_score, float* __restrict__ out_mmr,
-    float* __restrict__ rows_out, uint32_t* done_word, uint32_t done_value) {
+    float* __restrict__ rows_out, uint32_t* done_word, uint32_t done_value, const int32_t* __restrict__ groups, int max_per_group,
+    int* __restrict__ out_pool_rows) {
     __shared__ MmrSmem sm;
     const int tid = static_cast<int>(threadIdx.x);
     const int lane = tid & 63;
@@ -75,15 +87,54 @@ __global__ __launch_bounds__(kMmrBlockMax) void mmr_rerank_kernel(
 #pragma unroll
     for (int j = 0; j < kDim; ++j) sm.feat[j][tid] = f[j];
     sm.qn[tid] = query_norm(f);
+    const bool capped = groups != nullptr;                // uniform
+    const int g = capped && have ? groups[local] : -1;
+    if (capped) sm.grp[tid] = g;
     __syncthreads();
     const int p_eff = sm.first_empty;                     // P'
-    const int picks = topn < p_eff ? topn : p_eff;
+    int picks = topn < p_eff ? topn : p_eff;              // (capped: at most so many)
     bool live = tid < p_eff;
+    if (tid == 0 && out_pool_rows) *out_pool_rows = p_eff;
     const float rel = ordered_to_score(static_cast<uint32_t>(key >> 32));   // (-0.0 is +0.0 in the image already)
+    const bool in_order = capped && lambda == 1.0f;       // uniform: the picks are the pool in order, no loop
+    if (in_order) {
+        // rank inside the group: the earlier pool positions of the same group (every position below a live one holds a row)
+        int rank = 0;
+        if (live && g >= 0) {
+            const int4* g4 = reinterpret_cast<const int4*>(sm.grp);
+            for (int j = 0; j < tid; j += 4) {   // (one address per wave: a broadcast; the trip count differs by lane)
+                const int4 v = g4[j >> 2];
+                rank += (v.x == g) + (j + 1 < tid && v.y == g) + (j + 2 < tid && v.z == g) + (j + 3 < tid && v.w == g);
+            }
+        }
+        const bool keep = live && (g < 0 || rank < max_per_group);
+        const uint64_t kept = __ballot(keep);
+        if (lane == 0) sm.wave_key[0][wave] = static_cast<uint64_t>(__popcll(kept));
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int w = 0; w < n_waves; ++w) {
+            const int c = static_cast<int>(sm.wave_key[0][w]);
+            before += w < wave ? c : 0;
+            total += c;
+        }
+        const int slot = before + __popcll(kept & ((1ull << lane) - 1ull));
+        picks = topn < total ? topn : total;
+        if (keep && slot < topn) {
+            out_idx[slot] = static_cast<int64_t>(static_cast<uint32_t>(~static_cast<uint32_t>(key)));
+            out_score[slot] = rel;
+            if (out_mmr) out_mmr[slot] = rel;   // fl(fl(1 rel) - fl(0 pen)) = rel
+        }
+        for (int t = picks + tid; t < topn; t += static_cast<int>(blockDim.x)) {
+            out_idx[t] = -1;
+            out_score[t] = 0.0f;
+            if (out_mmr) out_mmr[t] = 0.0f;
+        }
+    }
     const float a = lambda * rel;
     float pen = 0.0f;
+    int seen = 0;
 
-    for (int t = 0; t < picks; ++t) {   // uniform trip count: every lane takes part in the DPP steps and the barrier
+    for (int t = 0; !in_order && t < picks; ++t) {   // uniform trip count: every lane takes part in the DPP steps and the barrier
         const float b = mu * pen;
         const float mmr = a - b;
         const uint32_t img = live ? score_to_ordered(mmr) : 0u;   // (an image of a finite score is never 0)
@@ -99,11 +150,19 @@ __global__ __launch_bounds__(kMmrBlockMax) void mmr_rerank_kernel(
             const uint64_t k = sm.wave_key[t & 1][w];
             best = k > best ? k : best;
         }
+        if (best == 0ull) {   // uniform (capped only): no row is eligible any more
+            picks = t;
+            break;
+        }
         const int p = kMmrBlockMax - 1 - static_cast<int>(static_cast<uint32_t>(best));
         if (tid == p) {
             live = false;
             sm.pick_pos[t] = static_cast<unsigned short>(p);
             sm.pick_mmr[t] = mmr;
+        }
+        if (capped) {   // uniform
+            const int gp = sm.grp[p];
+            if (gp >= 0 && g == gp && ++seen >= max_per_group) live = false;
         }
         if (t + 1 < picks) {   // uniform
             float q[kDim];
@@ -114,7 +173,7 @@ __global__ __launch_bounds__(kMmrBlockMax) void mmr_rerank_kernel(
         }
     }
     __syncthreads();
-    for (int t = tid; t < topn; t += static_cast<int>(blockDim.x)) {
+    for (int t = tid; !in_order && t < topn; t += static_cast<int>(blockDim.x)) {
         const bool got = t < picks;
         const uint64_t k = got ? keys[sm.pick_pos[t]] : 0ull;
         out_idx[t] = got ? static_cast<int64_t>(static_cast<uint32_t>(~static_cast<uint32_t>(k))) : -1;
@@ -122,7 +181,7 @@ __global__ __launch_bounds__(kMmrBlockMax) void mmr_rerank_kernel(
         if (out_mmr) out_mmr[t] = got ? sm.pick_mmr[t] : 0.0f;
     }
     if (done_word) {   // uniform
-        if (tid < ((topn + 63) & ~63)) __threadfence_system();   // the waves that stored results order them before ...
+        if (in_order || tid < ((topn + 63) & ~63)) __threadfence_system();   // the waves that stored results order them before ...
         __syncthreads();
         if (tid == 0) __hip_atomic_store(done_word, done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // ... the word
     }

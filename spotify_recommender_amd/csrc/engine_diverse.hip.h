@@ -15,6 +15,9 @@
 namespace {
 
 // lambda and pool (the other arguments are the playlist call's, checked there with topn = pool).
+// The groups a handle answers from (its own, or its group's of lanes).
+const int32_t* groups_of(const mi355rec* h) { return h->shared ? h->shared->d_groups : h->d_groups; }
+
 int check_diverse(mi355rec* h, float lambda, int pool, int topn) {
     if (std::isnan(lambda) || lambda < 0.0f || lambda > 1.0f)
         return fail(h, MI355REC_ERR_INVALID_ARG, "lambda %g out of [0, 1]", static_cast<double>(lambda));
@@ -29,11 +32,14 @@ int ensure_diverse(mi355rec* h) {
     const int rc = ensure_playlist(h);
     if (rc) return rc;
     mi355rec_playlist* P = h->playlist;
-    if (!P->h_mmr) {
-        HIP_TRY(h, hipHostMalloc(&P->h_mmr, sizeof(float) * kMaxTopK, hipHostMallocMapped));
+    if (!P->h_mmr) {   // (one word more: P' of a capped call)
+        HIP_TRY(h, hipHostMalloc(&P->h_mmr, sizeof(float) * kMaxTopK + sizeof(int), hipHostMallocMapped));
         HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void**>(&P->hd_mmr), P->h_mmr, 0));
+        P->h_pool_rows = reinterpret_cast<int*>(P->h_mmr + kMaxTopK);
+        P->hd_pool_rows = reinterpret_cast<int*>(P->hd_mmr + kMaxTopK);
     }
     if (!P->d_rows) HIP_TRY(h, hipMalloc(&P->d_rows, sizeof(float) * kDim * kMaxTopK));
+    if (!P->d_pool_groups) HIP_TRY(h, hipMalloc(&P->d_pool_groups, sizeof(int32_t) * kMaxTopK));
     return MI355REC_OK;
 }
 
@@ -46,19 +52,21 @@ void pad_diverse(int from, int topn, int64_t* out_idx, float* out_score, float* 
 }
 
 // The re-rank of the `pool` keys in h->d_keys on h->stream, the wait and the results.  rows: the handle's matrix, or
-// (staged) the pool's rows in pool order.
+// (staged) the pool's rows in pool order.  groups: null, or (GROUP CAPS) the device array that goes with `rows`.
 int rerank_and_wait(mi355rec* h, const float* rows, bool staged, int pool, float lambda, int topn, int64_t* out_idx, float* out_score,
-                    float* out_mmr, int* out_count) {
+                    float* out_mmr, int* out_count, const int32_t* groups = nullptr, int max_per_group = 0, int* out_pool_rows = nullptr) {
     mi355rec_playlist* P = h->playlist;
     const float mu = 1.0f - lambda;
     const uint32_t want = ++h->done_seq ? h->done_seq : ++h->done_seq;   // never 0
     const int block = (pool + 63) & ~63;
     hipLaunchKernelGGL(mmr_rerank_kernel, dim3(1), dim3(block), 0, h->stream, static_cast<const uint64_t*>(h->d_keys), rows, h->n,
                        h->row_base, staged ? 1 : 0, pool, topn, lambda, mu, h->hd_idx, h->hd_score, P->hd_mmr,
-                       static_cast<float*>(nullptr), h->hd_done, want);
+                       static_cast<float*>(nullptr), h->hd_done, want, groups, max_per_group,
+                       groups ? P->hd_pool_rows : static_cast<int*>(nullptr));
     HIP_TRY(h, hipGetLastError());
     const int rc = wait_done(h, want);
     if (rc) return rc;
+    if (out_pool_rows) *out_pool_rows = groups ? *P->h_pool_rows : 0;
     int c = 0;
     while (c < topn && h->h_idx[c] >= 0) ++c;
     std::memcpy(out_idx, h->h_idx, static_cast<size_t>(topn) * sizeof(int64_t));
@@ -70,10 +78,18 @@ int rerank_and_wait(mi355rec* h, const float* rows, bool staged, int pool, float
 
 int sync_diverse_query(mi355rec* h, const float* members, const int64_t* local_rows, const float* weights, int k,
                        const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter, float lambda, int pool, int topn,
-                       int64_t* out_idx, float* out_score, float* out_mmr, int* out_count, int max_exclude = kMaxExclude) {
+                       int64_t* out_idx, float* out_score, float* out_mmr, int* out_count, int max_exclude = kMaxExclude,
+                       bool capped = false, int max_per_group = 0, int* out_pool_rows = nullptr) {
     if (!out_idx) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     int rc = check_diverse(h, lambda, pool, topn);
     if (rc) return rc;
+    const int32_t* groups = nullptr;
+    if (capped) {   // GROUP CAPS: the same launches, two more arguments to the re-rank
+        if (max_per_group < 1) return fail(h, MI355REC_ERR_INVALID_ARG, "max_per_group must be positive, got %d", max_per_group);
+        groups = groups_of(h);
+        if (!groups) return fail(h, MI355REC_ERR_INVALID_ARG, "this handle has no groups (mi355rec_set_groups)");
+        if (out_pool_rows) *out_pool_rows = 0;
+    }
     DeviceGuard guard(h->device);
     int eff = 0, grid = 0;
     rc = playlist_launch(h, members, local_rows, k, exclude_global, n_exclude, pool, out_idx, max_exclude, filter, weights, &eff, &grid);
@@ -87,7 +103,41 @@ int sync_diverse_query(mi355rec* h, const float* members, const int64_t* local_r
     if (rc) return rc;
     rc = enqueue_merge(h, h->d_block_lists, grid, eff, eff, h->d_keys, nullptr, nullptr, h->stream);
     if (rc) return rc;
-    return rerank_and_wait(h, h->d_feats, false, eff, lambda, topn, out_idx, out_score, out_mmr, out_count);
+    return rerank_and_wait(h, h->d_feats, false, eff, lambda, topn, out_idx, out_score, out_mmr, out_count, groups, max_per_group,
+                           out_pool_rows);
+}
+
+// `group_ok`: as for the labels (engine_labels.hip.h): the node handle may replace the groups under its own lanes.
+int set_groups_common(mi355rec* h, const int32_t* groups_host, int64_t n, bool group_ok) {
+    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    if (!group_ok && h->shared && (h->is_lane || h->shared->refs.load() > 1))
+        return fail(h, MI355REC_ERR_INVALID_ARG, "the handle has lanes: set the groups before the first lane is made");
+    int32_t* fresh = nullptr;
+    DeviceGuard guard(h->device);
+    if (groups_host) {
+        if (n != h->n) return fail(h, MI355REC_ERR_INVALID_ARG, "%lld groups for a handle of %lld rows", (long long)n, (long long)h->n);
+        for (int64_t i = 0; i < n; ++i)
+            if (groups_host[i] < -1)
+                return fail(h, MI355REC_ERR_INVALID_ARG, "group %d of row %lld: a group id is >= 0, or -1 for no group",
+                            static_cast<int>(groups_host[i]), (long long)i);
+        // (an empty shard keeps a one-word array: "has groups" is a non-null pointer)
+        hipError_t e = hipMalloc(&fresh, sizeof(int32_t) * static_cast<size_t>(n > 0 ? n : 1));
+        if (e == hipSuccess && n > 0) e = hipMemcpy(fresh, groups_host, sizeof(int32_t) * static_cast<size_t>(n), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {   // the previous groups stay
+            if (fresh) (void)hipFree(fresh);
+            (void)hipGetLastError();
+            return fail(h, e == hipErrorOutOfMemory ? MI355REC_ERR_OUT_OF_MEMORY : MI355REC_ERR_HIP, "the groups (%lld rows): %s",
+                        (long long)n, hipGetErrorString(e));
+        }
+    }
+    int32_t* old = const_cast<int32_t*>(groups_of(h));
+    if (old) {
+        (void)hipStreamSynchronize(h->stream);   // (only the synchronous calls on this stream read them)
+        (void)hipFree(old);
+    }
+    h->d_groups = fresh;
+    if (h->shared) h->shared->d_groups = fresh;
+    return MI355REC_OK;
 }
 
 }  // namespace
@@ -101,11 +151,24 @@ int query_mean_topn_diverse(mi355rec_t* h, const float* queries, const float* we
                               out_mmr, out_count, kPlExcludeCap);
 }
 
+int query_mean_topn_capped(mi355rec_t* h, const float* queries, const float* weights, int k, const int64_t* exclude_global, int n_exclude,
+                           const mi355rec_filter_t* filter, float lambda, int pool, int max_per_group, int topn, int64_t* out_idx,
+                           float* out_score, float* out_mmr, int* out_count, int* out_pool_rows) {
+    if (!h || !queries) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    return sync_diverse_query(h, queries, nullptr, weights, k, exclude_global, n_exclude, filter, lambda, pool, topn, out_idx, out_score,
+                              out_mmr, out_count, kPlExcludeCap, true, max_per_group, out_pool_rows);
+}
+
+int set_group_groups(mi355rec_t* h, const int32_t* groups_host, int64_t n) { return set_groups_common(h, groups_host, n, true); }
+
 int rerank_pool(mi355rec_t* h, const int64_t* pool_idx, const float* pool_score, const float* pool_rows, int count, float lambda, int topn,
-                int64_t* out_idx, float* out_score, float* out_mmr, int* out_count) {
+                int64_t* out_idx, float* out_score, float* out_mmr, int* out_count, const int32_t* pool_groups, int max_per_group,
+                int* out_pool_rows) {
     if (!h || !pool_idx || !pool_score || !pool_rows || !out_idx) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     if (count < 1 || count > kMaxTopK || topn < 1 || topn > kMaxTopK)
         return fail(h, MI355REC_ERR_INVALID_ARG, "a pool of %d rows, topn %d: 1 to %d are supported", count, topn, kMaxTopK);
+    if (pool_groups && max_per_group < 1)
+        return fail(h, MI355REC_ERR_INVALID_ARG, "max_per_group must be positive, got %d", max_per_group);
     DeviceGuard guard(h->device);
     int rc = ensure_diverse(h);
     if (!rc) rc = ensure_slots(h, static_cast<size_t>(kMaxTopK));
@@ -117,7 +180,11 @@ int rerank_pool(mi355rec_t* h, const int64_t* pool_idx, const float* pool_score,
     HIP_TRY(h, hipMemcpyAsync(h->d_keys, keys, sizeof(uint64_t) * static_cast<size_t>(count), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->playlist->d_rows, pool_rows, sizeof(float) * kDim * static_cast<size_t>(count), hipMemcpyHostToDevice,
                               h->stream));
-    return rerank_and_wait(h, h->playlist->d_rows, true, count, lambda, topn, out_idx, out_score, out_mmr, out_count);
+    if (pool_groups)
+        HIP_TRY(h, hipMemcpyAsync(h->playlist->d_pool_groups, pool_groups, sizeof(int32_t) * static_cast<size_t>(count),
+                                  hipMemcpyHostToDevice, h->stream));
+    return rerank_and_wait(h, h->playlist->d_rows, true, count, lambda, topn, out_idx, out_score, out_mmr, out_count,
+                           pool_groups ? h->playlist->d_pool_groups : nullptr, max_per_group, out_pool_rows);
 }
 }  // namespace mi355node
 
@@ -137,6 +204,25 @@ int mi355rec_query_playlist_topn_diverse(mi355rec_t* h, const int64_t* local_row
     if (!h || !local_rows) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     return sync_diverse_query(h, nullptr, local_rows, weights, k, exclude_global, n_exclude, filter, lambda, pool, topn, out_idx, out_score,
                               out_mmr, out_count);
+}
+
+int mi355rec_set_groups(mi355rec_t* h, const int32_t* groups_host, int64_t n) { return set_groups_common(h, groups_host, n, false); }
+
+int mi355rec_query_mean_topn_capped(mi355rec_t* h, const float* queries, const float* weights, int k, const int64_t* exclude_global,
+                                    int n_exclude, const mi355rec_filter_t* filter, float lambda, int pool, int max_per_group, int topn,
+                                    int64_t* out_idx, float* out_score, float* out_mmr, int* out_count, int* out_pool_rows) {
+    if (!h || !queries) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    return sync_diverse_query(h, queries, nullptr, weights, k, exclude_global, n_exclude, filter, lambda, pool, topn, out_idx, out_score,
+                              out_mmr, out_count, kMaxExclude, true, max_per_group, out_pool_rows);
+}
+
+int mi355rec_query_playlist_topn_capped(mi355rec_t* h, const int64_t* local_rows, const float* weights, int k,
+                                        const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter, float lambda,
+                                        int pool, int max_per_group, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
+                                        int* out_count, int* out_pool_rows) {
+    if (!h || !local_rows) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    return sync_diverse_query(h, nullptr, local_rows, weights, k, exclude_global, n_exclude, filter, lambda, pool, topn, out_idx, out_score,
+                              out_mmr, out_count, kMaxExclude, true, max_per_group, out_pool_rows);
 }
 
 int mi355rec_fetch_rows(mi355rec_t* h, const int64_t* local_rows, int64_t count, float* out_host) {
@@ -159,7 +245,7 @@ int mi355rec_fetch_rows(mi355rec_t* h, const int64_t* local_rows, int64_t count,
         hipLaunchKernelGGL(mmr_rerank_kernel, dim3(1), dim3((c + 63) & ~63), 0, h->stream, static_cast<const uint64_t*>(h->d_keys),
                            static_cast<const float*>(h->d_feats), h->n, h->row_base, 0, c, 0, 0.0f, 0.0f, static_cast<int64_t*>(nullptr),
                            static_cast<float*>(nullptr), static_cast<float*>(nullptr), h->playlist->d_rows,
-                           static_cast<uint32_t*>(nullptr), 0u);
+                           static_cast<uint32_t*>(nullptr), 0u, static_cast<const int32_t*>(nullptr), 0, static_cast<int*>(nullptr));
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipMemcpyAsync(out_host + done * kDim, h->playlist->d_rows, sizeof(float) * kDim * static_cast<size_t>(c),
                                   hipMemcpyDeviceToHost, h->stream));

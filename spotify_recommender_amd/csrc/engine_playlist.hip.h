@@ -22,6 +22,10 @@ struct mi355rec_playlist {
     float* h_mmr = nullptr;                 // the picks' mmr values: pinned, mapped, written by mmr_rerank_kernel itself ...
     float* hd_mmr = nullptr;                // ... at this device-side address
     float* d_rows = nullptr;                // kMaxTopK rows: a pool passed by value, or the rows mi355rec_fetch_rows gathers
+    // GROUP CAPS (engine_diverse.hip.h):
+    int* h_pool_rows = nullptr;             // P' of the last capped call: one more word of the pinned h_mmr allocation ...
+    int* hd_pool_rows = nullptr;            // ... at this device-side address
+    int32_t* d_pool_groups = nullptr;       // kMaxTopK groups: those of a pool passed by value, in pool order
 };
 
 namespace {
@@ -35,6 +39,7 @@ void free_playlist(mi355rec_playlist* P) {
     if (P->h_buf) (void)hipHostFree(P->h_buf);
     if (P->h_mmr) (void)hipHostFree(P->h_mmr);
     if (P->d_rows) (void)hipFree(P->d_rows);
+    if (P->d_pool_groups) (void)hipFree(P->d_pool_groups);
     delete P;
 }
 

@@ -107,6 +107,7 @@ struct mi355rec {
         void* d_q8 = nullptr;
         float margin_mix = 0.0f, margin_mfma = 0.0f;   // of the replicas above (half_selfcheck_kernel's verdict)
         mi355rec_labels* labels = nullptr;             // the labels of the group (set before its first lane was made)
+        int32_t* d_groups = nullptr;                   // the group ids of the group's rows (mi355rec_set_groups), likewise
     };
     SharedRows* shared = nullptr;
     bool is_lane = false;
@@ -116,6 +117,8 @@ struct mi355rec {
     mi355rec_labels* labels = nullptr;
     int64_t label_queries = 0;          // filtered queries since create ...
     int64_t label_rows_scanned = 0;     // ... and the rows their launches scanned (whole tiles)
+    // GROUP CAPS (mi355rec_set_groups): one int32 per row in local row order, -1 = ungrouped; owned like the labels
+    int32_t* d_groups = nullptr;
     // PLAYLISTS (mi355rec_query_mean_topn / _query_playlist_topn): allocated by the first call, owned by the handle (lanes have their own)
     mi355rec_playlist* playlist = nullptr;
     int64_t playlist_queries = 0;

@@ -13,6 +13,8 @@
 //       (normalised units; extension; not with --genre)
 //   ... --song, --id and --playlist with --diverse LAMBDA [--pool P]: diversified results (maximal marginal relevance over the
 //       P most similar songs; extension; usable with --where, --dislike, --weights; not with --genre)
+//   ... --song, --id and --playlist with --max-per-artist M: at most M results per primary artist (extension; combines with
+//       --where, --dislike, --weights, --diverse and --pool; not with --genre)
 //   ... --playlist with --dislike "<track_id>,..." [--dislike-weight W] [--weights "w,w,..."]: weighted playlists (extension):
 //       the disliked songs push results away (weight -W, default 0.5), --weights gives the playlist's songs their own weights
 #include <algorithm>
@@ -46,7 +48,10 @@ static void usage(const char* prog) {
               << "   --weights gives one weight per playlist song (default 1 each).  Usable with --where.\n"
               << "Diversified results (extension): --diverse LAMBDA [--pool P], with --song, --id or --playlist (and --where, --dislike,\n"
               << "   --weights; not with --genre): picks from the P most similar songs (default 4 x N, at most 1024), each pick\n"
-              << "   weighing similarity (LAMBDA in [0, 1]; 1 = the plain result) against likeness to the songs already picked.\n" << std::endl;
+              << "   weighing similarity (LAMBDA in [0, 1]; 1 = the plain result) against likeness to the songs already picked.\n"
+              << "Artist cap (extension): --max-per-artist M, with --song, --id or --playlist (and --where, --dislike, --weights,\n"
+              << "   --diverse, --pool; not with --genre): at most M results by one primary artist (the artists field up to its\n"
+              << "   first ';').  Results come from the P most similar songs (--pool; default 8 x N, at most 1024).\n" << std::endl;
 }
 
 // --where NAME=LO:HI, any number of times from argv[first]: the ranges (feature indices in Song.h order).  false, with a
@@ -107,14 +112,16 @@ struct DiverseOpt {
     bool on = false;
     float lambda = 1.0f;
     int pool = 0;   // 0: the default, min(1024, 4 x N)
+    int maxPerArtist = 0;   // --max-per-artist M (0: not given); the default pool is then min(1024, 8 x N)
 };
 
 // false, with a message, on a malformed or out-of-range option.
 static bool parseDiverse(int argc, char* argv[], int first, int topN, DiverseOpt& dv) {
     bool havePool = false;
     for (int i = first; i < argc; ++i) {
-        const bool diverse = std::strcmp(argv[i], "--diverse") == 0, pool = std::strcmp(argv[i], "--pool") == 0;
-        if (!diverse && !pool) continue;
+        const bool diverse = std::strcmp(argv[i], "--diverse") == 0, pool = std::strcmp(argv[i], "--pool") == 0,
+                   cap = std::strcmp(argv[i], "--max-per-artist") == 0;
+        if (!diverse && !pool && !cap) continue;
         if (i + 1 >= argc) {
             std::cerr << "Error: " << argv[i] << " needs a value" << std::endl;
             return false;
@@ -128,6 +135,13 @@ static bool parseDiverse(int argc, char* argv[], int first, int topN, DiverseOpt
                 std::cerr << "Error: --diverse '" << arg << "': LAMBDA must be a number in [0, 1]" << std::endl;
                 return false;
             }
+        } else if (cap) {
+            const long v = std::strtol(arg.c_str(), &end, 10);
+            if (arg.empty() || *end != '\0' || v < 1 || v > 1024) {
+                std::cerr << "Error: --max-per-artist '" << arg << "': M must be an integer in [1, " << 1024 << "]" << std::endl;
+                return false;
+            }
+            dv.maxPerArtist = static_cast<int>(v);
         } else {
             havePool = true;
             const long v = std::strtol(arg.c_str(), &end, 10);
@@ -138,8 +152,9 @@ static bool parseDiverse(int argc, char* argv[], int first, int topN, DiverseOpt
             dv.pool = static_cast<int>(v);
         }
     }
+    if (dv.maxPerArtist > 0) dv.on = true;   // (without --diverse: lambda 1, the plain order with the cap)
     if (havePool && !dv.on) {
-        std::cerr << "Error: --pool needs --diverse LAMBDA" << std::endl;
+        std::cerr << "Error: --pool needs --diverse LAMBDA or --max-per-artist M" << std::endl;
         return false;
     }
     if (havePool && dv.pool < topN) {
@@ -213,6 +228,20 @@ static bool genreRecommendations(Recommender& recommender, const DataManager::Ca
     return true;
 }
 
+// --max-per-artist: the group ids of the catalogue's songs (their primary artists, read back from the file) to the recommender.
+static bool capByArtist(Recommender& recommender, const DataManager::Catalogue& catalogue) {
+    std::vector<std::string> artists(catalogue.size());
+    Song song;
+    for (size_t i = 0; i < catalogue.size(); ++i) {
+        if (!DataManager::readSong(catalogue, i, song)) {
+            std::cerr << "Error: could not read song " << i << " from " << catalogue.path << std::endl;
+            return false;
+        }
+        artists[i] = song.artists;
+    }
+    return recommender.setGroupIds(Recommender::artistGroupIds(artists));
+}
+
 // --diverse: recommendByIndex (or its --where form) diversified.
 static void diverseRecommendations(Recommender& recommender, const DataManager::Catalogue& catalogue, const std::string& query,
                                    bool isTrackId, int topN, const std::vector<Recommender::FeatureRange>& ranges, const DiverseOpt& dv,
@@ -221,6 +250,14 @@ static void diverseRecommendations(Recommender& recommender, const DataManager::
     if (index < 0) {
         std::cerr << "Error: Song with " << (isTrackId ? "track_id" : "name") << " '" << query << "' not found" << std::endl;
         return;   // (no recommendations: the caller says so)
+    }
+    if (dv.maxPerArtist > 0) {
+        if (!capByArtist(recommender, catalogue)) return;
+        std::cout << "At most " << dv.maxPerArtist << " per artist";
+        if (dv.lambda < 1.0f) std::cout << "; diversified: lambda " << dv.lambda;
+        std::cout << std::endl;
+        recs = recommender.recommendByIndexCapped(index, topN, dv.maxPerArtist, dv.lambda, dv.pool, ranges);
+        return;
     }
     std::cout << "Diversified: lambda " << dv.lambda << std::endl;
     recs = recommender.recommendDiverse(index, topN, dv.lambda, dv.pool, ranges);
@@ -390,8 +427,15 @@ static bool playlistMode(const std::string& list, int topN, const std::vector<Re
         return false;
     }
     std::map<int, std::string>& genreMap = catalogue.genreMap;
-    if (dv.on) std::cout << "Diversified: lambda " << dv.lambda << std::endl;
-    const std::vector<int> recs = dv.on           ? recommender.recommendForPlaylist(members, topN, taste.weighted ? weights : std::vector<float>(),
+    if (dv.maxPerArtist > 0) {
+        if (!capByArtist(recommender, catalogue)) return false;
+        std::cout << "At most " << dv.maxPerArtist << " per artist" << std::endl;
+    }
+    if (dv.on && (dv.maxPerArtist == 0 || dv.lambda < 1.0f)) std::cout << "Diversified: lambda " << dv.lambda << std::endl;
+    const std::vector<int> recs = dv.maxPerArtist > 0
+                                      ? recommender.recommendForPlaylist(members, topN, taste.weighted ? weights : std::vector<float>(), ranges,
+                                                                         {}, dv.lambda, dv.pool, dv.maxPerArtist)
+                                  : dv.on         ? recommender.recommendForPlaylist(members, topN, taste.weighted ? weights : std::vector<float>(),
                                                                                      ranges, {}, dv.lambda, dv.pool)
                                   : taste.weighted ? recommender.recommendForPlaylist(members, topN, weights, ranges, {})
                                   : ranges.empty() ? recommender.recommendForPlaylist(members, topN)
@@ -478,7 +522,7 @@ int main(int argc, char* argv[]) {
         DiverseOpt dv;
         if (!parseDiverse(argc, argv, 3, topN, dv)) return 1;
         if (dv.on && !genres.empty()) {
-            std::cerr << "Error: --diverse cannot be combined with --genre" << std::endl;
+            std::cerr << "Error: " << (dv.maxPerArtist > 0 ? "--max-per-artist" : "--diverse") << " cannot be combined with --genre" << std::endl;
             return 1;
         }
         return recommendationMode(argv[2], mode == "--id", topN, genres, ranges, dv) ? 0 : 1;

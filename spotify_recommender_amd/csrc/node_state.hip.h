@@ -38,8 +38,16 @@ int query_mean_topn(mi355rec_t* h, const float* queries, int k, const int64_t* e
 int query_mean_topn_diverse(mi355rec_t* h, const float* queries, const float* weights, int k, const int64_t* exclude_global, int n_exclude,
                             const mi355rec_filter_t* filter, float lambda, int pool, int topn, int64_t* out_idx, float* out_score,
                             float* out_mmr, int* out_count);
+// GROUP CAPS: pool_groups (null: no cap) are the pool rows' groups in pool order, max_per_group the cap, *out_pool_rows = P'.
 int rerank_pool(mi355rec_t* h, const int64_t* pool_idx, const float* pool_score, const float* pool_rows, int count, float lambda, int topn,
-                int64_t* out_idx, float* out_score, float* out_mmr, int* out_count);
+                int64_t* out_idx, float* out_score, float* out_mmr, int* out_count, const int32_t* pool_groups = nullptr,
+                int max_per_group = 0, int* out_pool_rows = nullptr);
+// mi355rec_query_mean_topn_capped with the longer exclusion list, and mi355rec_set_groups for a handle whose group of lanes
+// the caller has to itself (as set_group_labels).
+int query_mean_topn_capped(mi355rec_t* h, const float* queries, const float* weights, int k, const int64_t* exclude_global, int n_exclude,
+                           const mi355rec_filter_t* filter, float lambda, int pool, int max_per_group, int topn, int64_t* out_idx,
+                           float* out_score, float* out_mmr, int* out_count, int* out_pool_rows);
+int set_group_groups(mi355rec_t* h, const int32_t* groups_host, int64_t n);
 }  // namespace mi355node
 
 namespace {
@@ -199,6 +207,10 @@ struct mi355rec_sharded {
     float* hd_score = nullptr;
     bool peer_rows = true;              // every shard's device can read every other shard's rows
     bool batched_windows = true;        // mi355rec_sharded_set_window_mode
+    // GROUP CAPS (mi355rec_sharded_set_groups) on a ROW-SHARDED placement: the node keeps the host copy and hands the pool's
+    // groups to the re-rank by value; one shard and a replicated placement give the array to their engines instead.
+    std::vector<int32_t> groups;
+    bool has_groups = false;
     bool replicated = false;            // every "shard" holds all rows (mi355rec_create_placed, MI355REC_PLACEMENT_REPLICATED)
     int next_replica = 0;               // whose turn the next synchronous call is (replicated)
     std::vector<hipEvent_t> r_merged;   // replicated: [kStreamDepth][replicas] "this window's results are in host memory",

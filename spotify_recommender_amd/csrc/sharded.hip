@@ -539,6 +539,53 @@ int mi355rec_sharded_set_labels(mi355rec_sharded_t* h, const int32_t* labels_hos
     return MI355REC_OK;
 }
 
+// ---- GROUP CAPS (include/mi355rec_diag.h) -----------------------------------------------------------------------------
+int mi355rec_sharded_set_groups(mi355rec_sharded_t* h, const int32_t* groups_host, int64_t n) {
+    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    if (groups_host && n != h->n)
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "%lld groups for a catalogue of %lld rows", (long long)n, (long long)h->n);
+    if (h->cpu) {
+        const char* why = nullptr;
+        return cpu_result(h, mi355cpu::node_set_groups(h->cpu, groups_host, n, &why), why);
+    }
+    for (int64_t i = 0; groups_host && i < n; ++i)
+        if (groups_host[i] < -1)
+            return sfail(h, MI355REC_ERR_INVALID_ARG, "group %d of row %lld: a group id is >= 0, or -1 for no group",
+                         static_cast<int>(groups_host[i]), (long long)i);
+    DeviceRestore restore;
+    int rc = drain_workers(h);   // the caller's thread drives every shard itself
+    if (rc) return rc;
+    if (h->shards.size() > 1 && !h->replicated) {   // row-sharded: the host copy alone
+        if (!groups_host) {
+            h->groups.clear();
+            h->has_groups = false;
+            return MI355REC_OK;
+        }
+        try {
+            h->groups.assign(groups_host, groups_host + n);   // (the strong guarantee: the previous groups stay)
+        } catch (const std::bad_alloc&) {
+            return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for the groups (%lld rows)", (long long)n);
+        }
+        h->has_groups = true;
+        return MI355REC_OK;
+    }
+    for (size_t r = 0; r < h->shards.size(); ++r) {
+        Shard& s = h->shards[r];
+        bool lane = false;   // a replica on a device that already holds one is a lane of it: it shares that one's groups
+        for (size_t p = 0; p < r && h->replicated && !lane; ++p) lane = h->shards[p].device == s.device;
+        if (lane) continue;
+        S_HIP(h, hipSetDevice(s.device));
+        rc = mi355node::set_group_groups(s.engine, groups_host ? groups_host + s.lo : nullptr, s.hi - s.lo);
+        if (rc != MI355REC_OK) {   // all or nothing: no replica keeps groups the others do not have
+            const std::string why = mi355rec_last_error(s.engine);
+            for (Shard& o : h->shards)
+                if (hipSetDevice(o.device) == hipSuccess) (void)mi355node::set_group_groups(o.engine, nullptr, 0);
+            return sfail(h, rc, "shard on device %d: %s (the groups were dropped on every shard)", s.device, why.c_str());
+        }
+    }
+    return MI355REC_OK;
+}
+
 namespace {
 // A filtered query on a ROW-SHARDED catalogue: the query by value on every shard (the query row excluded by its global index),
 // the per-shard lists merged on the host by key — exact, since every shard's list holds its best min(topn, rows) keys.
@@ -818,11 +865,13 @@ int check_diverse(mi355rec_sharded_t* h, float lambda, int pool, int topn) {
 // first shard's device over the pool passed by value.
 int sharded_diverse(mi355rec_sharded_t* h, const float* members, const float* weights, int k, const int64_t* excl, int n_excl,
                     const mi355rec_filter_t* filter, float lambda, int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
-                    int* out_count) {
+                    int* out_count, int max_per_group = 0, int* out_pool_rows = nullptr) {
+    const bool capped = max_per_group > 0;   // GROUP CAPS (checked by the caller)
+    if (out_pool_rows) *out_pool_rows = 0;
     if (h->cpu) {
         const char* why = nullptr;
         return cpu_result(h, mi355cpu::node_query_mean_diverse(h->cpu, members, k, excl, n_excl, filter, weights, lambda, pool, topn, out_idx,
-                                                              out_score, out_mmr, out_count, &why), why);
+                                                              out_score, out_mmr, out_count, &why, max_per_group, out_pool_rows), why);
     }
     DeviceRestore restore;
     if (h->shards.size() == 1 || h->replicated) {   // one handle holds the whole catalogue (row_base 0)
@@ -833,14 +882,19 @@ int sharded_diverse(mi355rec_sharded_t* h, const float* members, const float* we
         } else {
             S_HIP(h, hipSetDevice(s->device));
         }
-        const int rc = mi355node::query_mean_topn_diverse(s->engine, members, weights, k, excl, n_excl, filter, lambda, pool, topn, out_idx,
-                                                          out_score, out_mmr, out_count);
+        const int rc = capped ? mi355node::query_mean_topn_capped(s->engine, members, weights, k, excl, n_excl, filter, lambda, pool,
+                                                                  max_per_group, topn, out_idx, out_score, out_mmr, out_count, out_pool_rows)
+                              : mi355node::query_mean_topn_diverse(s->engine, members, weights, k, excl, n_excl, filter, lambda, pool, topn,
+                                                                   out_idx, out_score, out_mmr, out_count);
         return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s->engine));
     }
+    if (capped && !h->has_groups) return sfail(h, MI355REC_ERR_INVALID_ARG, "this handle has no groups (mi355rec_sharded_set_groups)");
     std::vector<int64_t> pidx, local;
     std::vector<float> prel, rows, part;
     std::vector<int> where;
+    std::vector<int32_t> pgroups;
     try {
+        if (capped) pgroups.resize(static_cast<size_t>(pool));
         pidx.resize(static_cast<size_t>(pool));
         prel.resize(static_cast<size_t>(pool));
         rows.resize(static_cast<size_t>(pool) * MI355REC_DIM);
@@ -885,7 +939,9 @@ int sharded_diverse(mi355rec_sharded_t* h, const float* members, const float* we
             break;
         }
     S_HIP(h, hipSetDevice(first->device));
-    rc = mi355node::rerank_pool(first->engine, pidx.data(), prel.data(), rows.data(), p_eff, lambda, topn, out_idx, out_score, out_mmr, out_count);
+    for (int i = 0; capped && i < p_eff; ++i) pgroups[static_cast<size_t>(i)] = h->groups[static_cast<size_t>(pidx[static_cast<size_t>(i)])];
+    rc = mi355node::rerank_pool(first->engine, pidx.data(), prel.data(), rows.data(), p_eff, lambda, topn, out_idx, out_score, out_mmr, out_count,
+                                capped ? pgroups.data() : nullptr, max_per_group, out_pool_rows);
     return rc == MI355REC_OK ? rc : sfail(h, rc, "shard on device %d: %s", first->device, mi355rec_last_error(first->engine));
 }
 }  // namespace
@@ -947,6 +1003,69 @@ int mi355rec_sharded_query_playlist_topn_diverse(mi355rec_sharded_t* h, const in
         if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
     }
     return sharded_diverse(h, members, weights, k, excl, n_exclude + k, filter, lambda, pool, topn, out_idx, out_score, out_mmr, out_count);
+}
+
+// GROUP CAPS (include/mi355rec_diag.h): the diversified calls above with the cap; the groups are checked where they live.
+int mi355rec_sharded_query_mean_topn_capped(mi355rec_sharded_t* h, const float* queries, const float* weights, int k,
+                                             const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
+                                             float lambda, int pool, int max_per_group, int topn, int64_t* out_idx, float* out_score,
+                                            float* out_mmr, int* out_count, int* out_pool_rows) {
+    if (!h || !queries || !out_idx) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    int rc = check_diverse(h, lambda, pool, topn);
+    if (!rc && max_per_group < 1) rc = sfail(h, MI355REC_ERR_INVALID_ARG, "max_per_group must be positive, got %d", max_per_group);
+    if (!rc) rc = check_playlist(h, queries, k, exclude_global, n_exclude, pool, out_idx);
+    if (!rc) rc = check_filter(h, filter);
+    if (!rc) rc = check_weights(h, weights, k);
+    if (rc) return rc;
+    return sharded_diverse(h, queries, weights, k, exclude_global, n_exclude, filter, lambda, pool, topn, out_idx, out_score, out_mmr,
+                           out_count, max_per_group, out_pool_rows);
+}
+
+int mi355rec_sharded_query_playlist_topn_capped(mi355rec_sharded_t* h, const int64_t* global_rows, const float* weights, int k,
+                                                 const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
+                                                 float lambda, int pool, int max_per_group, int topn, int64_t* out_idx, float* out_score,
+                                                float* out_mmr, int* out_count, int* out_pool_rows) {
+    if (!h || !global_rows || !out_idx) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    int rc = check_diverse(h, lambda, pool, topn);
+    if (!rc && max_per_group < 1) rc = sfail(h, MI355REC_ERR_INVALID_ARG, "max_per_group must be positive, got %d", max_per_group);
+    if (!rc) rc = check_playlist(h, global_rows, k, exclude_global, n_exclude, pool, out_idx);
+    if (rc) return rc;
+    for (int m = 0; m < k; ++m)
+        if (global_rows[m] < 0 || global_rows[m] >= h->n)
+            return sfail(h, MI355REC_ERR_INVALID_ARG, "Invalid song index: %lld", (long long)global_rows[m]);
+    rc = check_filter(h, filter);
+    if (!rc) rc = check_weights(h, weights, k);
+    if (rc) return rc;
+    if (!h->cpu && h->shards.size() == 1 && !h->replicated) {   // one handle: its own by-row call (the members stay on the device)
+        DeviceRestore restore;
+        Shard& s = h->shards[0];
+        S_HIP(h, hipSetDevice(s.device));
+        rc = mi355rec_query_playlist_topn_capped(s.engine, global_rows, weights, k, exclude_global, n_exclude, filter, lambda, pool,
+                                                 max_per_group, topn, out_idx, out_score, out_mmr, out_count, out_pool_rows);
+        return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s.engine));
+    }
+    // the members by value (fetched once) and their rows added to the exclusion list
+    float members[MI355REC_MAX_PLAYLIST * MI355REC_DIM];
+    int64_t excl[MI355REC_MAX_EXCLUDE + MI355REC_MAX_PLAYLIST];
+    for (int i = 0; i < n_exclude; ++i) excl[i] = exclude_global[i];
+    for (int m = 0; m < k; ++m) {
+        excl[n_exclude + m] = global_rows[m];
+        if (h->cpu) {
+            std::memcpy(members + m * MI355REC_DIM, mi355cpu::row(mi355cpu::node_catalogue(h->cpu), global_rows[m]), sizeof(float) * MI355REC_DIM);
+            continue;
+        }
+        if (m == 0) {
+            rc = drain_workers(h);
+            if (rc) return rc;
+        }
+        DeviceRestore restore;
+        const Shard* own = owner_of(h, global_rows[m]);
+        S_HIP(h, hipSetDevice(own->device));
+        rc = mi355rec_fetch_row(own->engine, global_rows[m] - own->lo, members + m * MI355REC_DIM);
+        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
+    }
+    return sharded_diverse(h, members, weights, k, excl, n_exclude + k, filter, lambda, pool, topn, out_idx, out_score, out_mmr, out_count,
+                           max_per_group, out_pool_rows);
 }
 
 int mi355rec_sharded_scores_row(mi355rec_sharded_t* h, int64_t global_row, float* out_host) {

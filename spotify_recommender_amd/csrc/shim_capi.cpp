@@ -240,6 +240,34 @@ int64_t shim_recommend_for_playlist_diverse(void* h, const int* songs, int n_son
                                                    std::vector<int>(exclude, exclude + (n_exclude > 0 ? n_exclude : 0)), lambda, pool),
                     out, scores, cap);
 }
+// recommendByIndexCapped and the capped recommendForPlaylist; group_ids (one per song, may be null) goes to setGroupIds first,
+// null keeps the groups initialize derived from the songs' artists.  shim_song_group: that derivation for song i.
+int64_t shim_recommend_capped(void* h, int song, int topn, int max_per_artist, float lambda, int pool, const int* features, const float* lo,
+                              const float* hi, int n_ranges, const int* group_ids, int* out, float* scores, int64_t cap) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    if (group_ids && !c->rec.setGroupIds(std::vector<int>(group_ids, group_ids + c->rec.getSongCount()))) return -1;
+    return giveBack(c, c->rec.recommendByIndexCapped(song, topn, max_per_artist, lambda, pool, ranges(features, lo, hi, n_ranges)), out,
+                    scores, cap);
+}
+int64_t shim_recommend_for_playlist_capped(void* h, const int* songs, int n_songs, const float* weights, int n_weights, int topn,
+                                           const int* features, const float* lo, const float* hi, int n_ranges, const int* exclude,
+                                           int n_exclude, float lambda, int pool, int max_per_artist, int* out, float* scores, int64_t cap) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    return giveBack(c, c->rec.recommendForPlaylist(std::vector<int>(songs, songs + (n_songs > 0 ? n_songs : 0)), topn,
+                                                   std::vector<float>(weights, weights + (n_weights > 0 ? n_weights : 0)),
+                                                   ranges(features, lo, hi, n_ranges),
+                                                   std::vector<int>(exclude, exclude + (n_exclude > 0 ? n_exclude : 0)), lambda, pool,
+                                                   max_per_artist),
+                    out, scores, cap);
+}
+int shim_artist_groups(void* h, int* out_n) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    std::vector<std::string> artists;
+    for (const Song& s : c->songs) artists.push_back(s.artists);
+    const std::vector<int> g = Recommender::artistGroupIds(artists);
+    for (size_t i = 0; i < g.size(); ++i) out_n[i] = g[i];
+    return 1;
+}
 int shim_similarities(void* h, int idx, float* out_n) {
     Catalogue* c = static_cast<Catalogue*>(h);
     std::vector<float> v;

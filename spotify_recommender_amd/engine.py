@@ -120,6 +120,30 @@ def _diverse_query(fn, h, check, members, weights, exclude, where, lam, pool, to
     return (idx, score, mmr[:idx.size].copy()) if return_mmr else (idx, score)
 
 
+def _capped_query(fn, h, check, members, weights, exclude, where, lam, pool, max_per_group, topn: int, return_mmr: bool,
+                  return_pool_rows: bool):
+    """Runs one capped entry point (GROUP CAPS): the diversified call's arguments with max_per_group after pool and &pool_rows
+    last.  `lam` = 1.0: relevance order with at most `max_per_group` results per group; `pool` None = min(1024, max(topn,
+    8 * topn)).  Returns (ids, scores[, mmr][, pool_rows]): fewer than `topn` ids with pool_rows == pool means the pool ran
+    out (raise `pool`), with pool_rows < pool that the catalogue has no more."""
+    if pool is None:
+        pool = min(1024, max(int(topn), 8 * int(topn)))
+    if isinstance(max_per_group, bool) or not isinstance(max_per_group, (int, np.integer)):
+        raise ValueError(f"max_per_group must be an integer, got {max_per_group!r}")
+    pool_rows = ctypes.c_int(0)
+    out = _diverse_query(lambda *a: fn(*a[:9], int(max_per_group), *a[9:], ctypes.byref(pool_rows)), h, check, members, weights,
+                         exclude, where, lam, pool, topn, return_mmr)
+    return out + (pool_rows.value,) if return_pool_rows else out
+
+
+def _np_groups(groups) -> np.ndarray:
+    """One group id per row (int32, contiguous): >= 0 a group, -1 ungrouped."""
+    g = np.asarray(groups)
+    if g.dtype.kind not in "iu" or (g.size and (g.min() < -(2 ** 31) or g.max() > 2 ** 31 - 1)):
+        raise ValueError("groups must be integers that fit int32")
+    return np.ascontiguousarray(g.astype(np.int32).reshape(-1))
+
+
 def _np_members(queries) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(queries, dtype=np.float32).reshape(-1, capi.DIM))
 
@@ -507,6 +531,25 @@ class CosineEngine:
         return _diverse_query(self._lib.mi355rec_query_playlist_topn_diverse, self._h, lambda rc: capi.check(rc, self._h),
                               _np_rows(local_rows), weights, exclude, where, lam, pool, topn, return_mmr)
 
+    def set_groups(self, groups) -> None:
+        """One group id per row (GROUP CAPS): >= 0 a group (an artist, say), -1 = never capped; None drops the groups."""
+        if groups is None:
+            capi.check(self._lib.mi355rec_set_groups(self._h, None, 0), self._h)
+            return
+        g = _np_groups(groups)
+        capi.check(self._lib.mi355rec_set_groups(self._h, g.ctypes.data_as(ctypes.c_void_p), int(g.size)), self._h)
+
+    def query_mean_topn_capped(self, queries, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
+                               weights=None, return_mmr=False, return_pool_rows=False):
+        """query_mean_topn_diverse with at most `max_per_group` results per group of set_groups (GROUP CAPS)."""
+        return _capped_query(self._lib.mi355rec_query_mean_topn_capped, self._h, lambda rc: capi.check(rc, self._h),
+                             _np_members(queries), weights, exclude, where, lam, pool, max_per_group, topn, return_mmr, return_pool_rows)
+
+    def query_playlist_topn_capped(self, local_rows, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
+                                   weights=None, return_mmr=False, return_pool_rows=False):
+        return _capped_query(self._lib.mi355rec_query_playlist_topn_capped, self._h, lambda rc: capi.check(rc, self._h),
+                             _np_rows(local_rows), weights, exclude, where, lam, pool, max_per_group, topn, return_mmr, return_pool_rows)
+
     def fetch_rows(self, local_rows) -> np.ndarray:
         """The features of the listed rows (any order, duplicates allowed), gathered on the device: (len, 12) float32."""
         rows = _np_rows(local_rows)
@@ -656,6 +699,24 @@ class NodeEngine:
                                topn)
 
     # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h) over the whole node ----
+    def set_groups(self, groups) -> None:
+        """One group id per row (GROUP CAPS): >= 0 a group, -1 = never capped; None drops the groups."""
+        if groups is None:
+            self._check(self._lib.mi355rec_sharded_set_groups(self._h, None, 0))
+            return
+        g = _np_groups(groups)
+        self._check(self._lib.mi355rec_sharded_set_groups(self._h, g.ctypes.data_as(ctypes.c_void_p), int(g.size)))
+
+    def query_mean_topn_capped(self, queries, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
+                               weights=None, return_mmr=False, return_pool_rows=False):
+        return _capped_query(self._lib.mi355rec_sharded_query_mean_topn_capped, self._h, self._check, _np_members(queries), weights,
+                             exclude, where, lam, pool, max_per_group, topn, return_mmr, return_pool_rows)
+
+    def query_playlist_topn_capped(self, global_rows, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
+                                   weights=None, return_mmr=False, return_pool_rows=False):
+        return _capped_query(self._lib.mi355rec_sharded_query_playlist_topn_capped, self._h, self._check, _np_rows(global_rows),
+                             weights, exclude, where, lam, pool, max_per_group, topn, return_mmr, return_pool_rows)
+
     def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False):
         return _diverse_query(self._lib.mi355rec_sharded_query_mean_topn_diverse, self._h, self._check, _np_members(queries), weights,
                               exclude, where, lam, pool, topn, return_mmr)
