@@ -374,24 +374,18 @@ std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& 
             impl->groupsUploaded = true;
         }
     }
-    const int rc = diverse && diverse->capped
-                       ? mi355rec_sharded_query_playlist_topn_capped(impl->engine, rows.data(), weights, static_cast<int>(rows.size()),
-                                                                     excl.data(), static_cast<int>(excl.size()), filter, diverse->lambda,
-                                                                     pool, diverse->maxPerGroup, topN, impl->idxBuf.data(),
-                                                                     impl->scoreBuf.data(), nullptr, &count, nullptr)
-                   : diverse ? mi355rec_sharded_query_playlist_topn_diverse(impl->engine, rows.data(), weights, static_cast<int>(rows.size()),
-                                                                          excl.data(), static_cast<int>(excl.size()), filter, diverse->lambda,
-                                                                          pool, topN, impl->idxBuf.data(), impl->scoreBuf.data(), nullptr,
-                                                                          &count)
-                   : weights ? mi355rec_sharded_query_playlist_topn_weighted(impl->engine, rows.data(), weights, static_cast<int>(rows.size()),
-                                                                           excl.data(), static_cast<int>(excl.size()), filter, topN,
-                                                                           impl->idxBuf.data(), impl->scoreBuf.data(), &count)
-                   : filter ? mi355rec_sharded_query_playlist_topn_where(impl->engine, rows.data(), static_cast<int>(rows.size()), excl.data(),
-                                                                       static_cast<int>(excl.size()), filter, topN, impl->idxBuf.data(),
-                                                                       impl->scoreBuf.data(), &count)
-                          : mi355rec_sharded_query_playlist_topn(impl->engine, rows.data(), static_cast<int>(rows.size()), excl.data(),
-                                                                 static_cast<int>(excl.size()), topN, impl->idxBuf.data(),
-                                                                 impl->scoreBuf.data(), &count);
+    // (the _playlist_topn and _where entry points are the _weighted one with null weights / a null filter)
+    const int k = static_cast<int>(rows.size()), nExcl = static_cast<int>(excl.size());
+    int64_t* const idx = impl->idxBuf.data();
+    float* const score = impl->scoreBuf.data();
+    const int rc =
+        diverse && diverse->capped
+            ? mi355rec_sharded_query_playlist_topn_capped(impl->engine, rows.data(), weights, k, excl.data(), nExcl, filter, diverse->lambda,
+                                                          pool, diverse->maxPerGroup, topN, idx, score, nullptr, &count, nullptr)
+        : diverse ? mi355rec_sharded_query_playlist_topn_diverse(impl->engine, rows.data(), weights, k, excl.data(), nExcl, filter,
+                                                                 diverse->lambda, pool, topN, idx, score, nullptr, &count)
+                  : mi355rec_sharded_query_playlist_topn_weighted(impl->engine, rows.data(), weights, k, excl.data(), nExcl, filter, topN, idx,
+                                                                  score, &count);
     if (rc != MI355REC_OK) {
         std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
         return {};
@@ -400,6 +394,22 @@ std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& 
     for (int i = 0; i < count; ++i) results[i] = static_cast<int>(impl->idxBuf[i]);
     impl->lastScores.assign(impl->scoreBuf.begin(), impl->scoreBuf.begin() + count);
     return results;
+}
+
+// The recommendForPlaylist overloads that take weights (one per song; orNone: or none at all) and ranges: the length check,
+// the filter (none for no ranges) and the query.
+std::vector<int> weightedPlaylistQuery(Recommender::Impl* impl, const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
+                                       bool orNone, const std::vector<Recommender::FeatureRange>& where, const std::vector<int>& alsoExclude,
+                                       const Diverse* diverse = nullptr) {
+    if (!(orNone && weights.empty()) && weights.size() != songIndices.size()) {
+        std::cerr << "Error: " << weights.size() << " weights for " << songIndices.size() << " songs (one weight per song"
+                  << (orNone ? ", or none" : "") << ")" << std::endl;
+        return {};
+    }
+    mi355rec_filter_t f;
+    if (!makeFilter(where, f)) return {};
+    return playlistQuery(impl, songIndices, topN, alsoExclude, where.empty() ? nullptr : &f, weights.empty() ? nullptr : weights.data(),
+                         diverse);
 }
 
 }  // namespace
@@ -417,39 +427,21 @@ std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songI
 
 std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
                                                    const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude) {
-    if (weights.size() != songIndices.size()) {
-        std::cerr << "Error: " << weights.size() << " weights for " << songIndices.size() << " songs (one weight per song)" << std::endl;
-        return {};
-    }
-    mi355rec_filter_t f;
-    if (!makeFilter(where, f)) return {};
-    return playlistQuery(impl_, songIndices, topN, alsoExclude, where.empty() ? nullptr : &f, weights.data());
+    return weightedPlaylistQuery(impl_, songIndices, topN, weights, false, where, alsoExclude);
 }
 
 std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
                                                    const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude, float lambda,
                                                    int pool) {
-    if (!weights.empty() && weights.size() != songIndices.size()) {
-        std::cerr << "Error: " << weights.size() << " weights for " << songIndices.size() << " songs (one weight per song, or none)" << std::endl;
-        return {};
-    }
-    mi355rec_filter_t f;
-    if (!makeFilter(where, f)) return {};
     const Diverse d{lambda, pool};
-    return playlistQuery(impl_, songIndices, topN, alsoExclude, where.empty() ? nullptr : &f, weights.empty() ? nullptr : weights.data(), &d);
+    return weightedPlaylistQuery(impl_, songIndices, topN, weights, true, where, alsoExclude, &d);
 }
 
 std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
                                                    const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude, float lambda,
                                                    int pool, int maxPerArtist) {
-    if (!weights.empty() && weights.size() != songIndices.size()) {
-        std::cerr << "Error: " << weights.size() << " weights for " << songIndices.size() << " songs (one weight per song, or none)" << std::endl;
-        return {};
-    }
-    mi355rec_filter_t f;
-    if (!makeFilter(where, f)) return {};
     const Diverse d{lambda, pool, maxPerArtist, true};
-    return playlistQuery(impl_, songIndices, topN, alsoExclude, where.empty() ? nullptr : &f, weights.empty() ? nullptr : weights.data(), &d);
+    return weightedPlaylistQuery(impl_, songIndices, topN, weights, true, where, alsoExclude, &d);
 }
 
 std::vector<int> Recommender::recommendByIndexCapped(int songIndex, int topN, int maxPerArtist, float lambda, int pool,

@@ -1,7 +1,5 @@
 // cpu_backend.cpp — see cpu_backend.h.  Own code; arithmetic contract: Recommender.cu:256-273, selection: :293-315.
 #include "cpu_backend.h"
-#include "filter_check.h"
-#include "weights_check.h"
 
 #include <omp.h>
 
@@ -299,11 +297,7 @@ int node_query(Node* h, const float* q12, int64_t exclude, int topn_asked, int64
         *why = "out of host memory";
         return MI355REC_ERR_OUT_OF_MEMORY;
     }
-    for (int i = c; i < topn_asked; ++i) {   // the C-ABI pads with -1 / 0
-        out_idx[i] = -1;
-        if (out_score) out_score[i] = 0.0f;
-    }
-    if (out_count) *out_count = c;
+    mi355playlist::pad({out_idx, out_score, nullptr, out_count, nullptr}, c, topn_asked, c);   // the C-ABI pads with -1 / 0
     return MI355REC_OK;
 }
 
@@ -387,16 +381,15 @@ int node_query_labels(Node* h, const float* q12, int64_t exclude, const int32_t*
         *why = "out of host memory";
         return MI355REC_ERR_OUT_OF_MEMORY;
     }
-    for (int i = c; i < topn_asked; ++i) {
-        out_idx[i] = -1;
-        if (out_score) out_score[i] = 0.0f;
-    }
-    if (out_count) *out_count = c;
+    mi355playlist::pad({out_idx, out_score, nullptr, out_count, nullptr}, c, topn_asked, c);
     return MI355REC_OK;
 }
 
-int node_query_mean(Node* h, const float* members, int k, const int64_t* exclude, int n_exclude, int topn_asked, int64_t* out_idx,
-                    float* out_score, int* out_count, const char** why, const mi355rec_filter_t* filter, const float* weights) {
+int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlist::Outputs& out, const char** why) {
+    const float* members = r.members;
+    const float* weights = r.weights;
+    const mi355rec_filter_t* filter = r.filter;
+    const int k = r.k, topn_asked = r.topn;
     const Catalogue* c = h->cat;
     const int64_t n = c->n;
     std::vector<float> qn(static_cast<size_t>(k));
@@ -404,7 +397,7 @@ int node_query_mean(Node* h, const float* members, int k, const int64_t* exclude
     std::vector<uint64_t> keys;
     std::vector<int64_t> excl;
     try {
-        excl.assign(exclude, exclude + n_exclude);
+        excl.assign(r.exclude, r.exclude + r.n_exclude);
         keys.resize(static_cast<size_t>(n));
     } catch (const std::bad_alloc&) {
         *why = "out of host memory";
@@ -441,21 +434,21 @@ int node_query_mean(Node* h, const float* members, int k, const int64_t* exclude
     }
     const int count = static_cast<int>(topn_asked < avail ? topn_asked : avail);
     std::partial_sort(keys.begin(), keys.begin() + count, keys.end(), std::greater<uint64_t>());
-    for (int i = 0; i < topn_asked; ++i) {
-        out_idx[i] = i < count ? static_cast<int64_t>(~static_cast<uint32_t>(keys[static_cast<size_t>(i)])) : -1;
-        if (out_score) out_score[i] = i < count ? unordered(static_cast<uint32_t>(keys[static_cast<size_t>(i)] >> 32)) + 0.0f : 0.0f;
+    for (int i = 0; i < count; ++i) {
+        out.idx[i] = static_cast<int64_t>(~static_cast<uint32_t>(keys[static_cast<size_t>(i)]));
+        if (out.score) out.score[i] = unordered(static_cast<uint32_t>(keys[static_cast<size_t>(i)] >> 32)) + 0.0f;
     }
-    if (out_count) *out_count = count;
+    mi355playlist::pad(out, count, topn_asked, count);
     return MI355REC_OK;
 }
 
 // DIVERSIFIED TOP-N (include/mi355rec_diag.h): the pool is node_query_mean's top-`pool`; then the greedy picks, a plain loop
 // over P' <= 1024 rows.  mmr = fl(fl(lambda rel) - fl(mu pen)): multiply, round, subtract, round (-ffp-contract=off).
-int node_query_mean_diverse(Node* h, const float* members, int k, const int64_t* exclude, int n_exclude, const mi355rec_filter_t* filter,
-                            const float* weights, float lambda, int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
-                            int* out_count, const char** why, int max_per_group, int* out_pool_rows) {
-    const bool capped = max_per_group > 0;   // GROUP CAPS
-    if (out_pool_rows) *out_pool_rows = 0;
+int node_query_mean_diverse(Node* h, const mi355playlist::Request& r, const mi355playlist::Outputs& out, const char** why) {
+    const bool capped = r.capped;   // GROUP CAPS
+    const float lambda = r.lambda;
+    const int pool = r.pool, topn = r.topn, max_per_group = r.max_per_group;
+    if (out.pool_rows) *out.pool_rows = 0;
     if (capped && !h->has_groups) {
         *why = "this handle has no groups (mi355rec_sharded_set_groups)";
         return MI355REC_ERR_INVALID_ARG;
@@ -476,9 +469,9 @@ int node_query_mean_diverse(Node* h, const float* members, int k, const int64_t*
         return MI355REC_ERR_OUT_OF_MEMORY;
     }
     int p_eff = 0;
-    const int rc = node_query_mean(h, members, k, exclude, n_exclude, pool, pidx.data(), prel.data(), &p_eff, why, filter, weights);
+    const int rc = node_query_mean(h, r.pool_call(), {pidx.data(), prel.data(), nullptr, &p_eff, nullptr}, why);
     if (rc != MI355REC_OK) return rc;
-    if (out_pool_rows) *out_pool_rows = p_eff;
+    if (out.pool_rows) *out.pool_rows = p_eff;
     const float* f = h->cat->feats.data();
     const float mu = 1.0f - lambda;
     int picks = topn < p_eff ? topn : p_eff;   // (capped: at most so many)
@@ -486,9 +479,9 @@ int node_query_mean_diverse(Node* h, const float* members, int k, const int64_t*
     for (int i = 0; i < p_eff; ++i) qn[static_cast<size_t>(i)] = query_norm(f + pidx[static_cast<size_t>(i)] * kDim);
     for (int t = 0; t < topn; ++t) {
         if (t >= picks) {
-            out_idx[t] = -1;
-            if (out_score) out_score[t] = 0.0f;
-            if (out_mmr) out_mmr[t] = 0.0f;
+            out.idx[t] = -1;
+            if (out.score) out.score[t] = 0.0f;
+            if (out.mmr) out.mmr[t] = 0.0f;
             continue;
         }
         int best = -1;
@@ -512,9 +505,9 @@ int node_query_mean_diverse(Node* h, const float* members, int k, const int64_t*
         picked[static_cast<size_t>(best)] = 1;
         if (capped && group_of(best) >= 0)
             for (int i = 0; i < p_eff; ++i) seen[static_cast<size_t>(i)] += group_of(i) == group_of(best);
-        out_idx[t] = pidx[static_cast<size_t>(best)];
-        if (out_score) out_score[t] = prel[static_cast<size_t>(best)];
-        if (out_mmr) out_mmr[t] = best_mmr;
+        out.idx[t] = pidx[static_cast<size_t>(best)];
+        if (out.score) out.score[t] = prel[static_cast<size_t>(best)];
+        if (out.mmr) out.mmr[t] = best_mmr;
         const float* q = f + pidx[static_cast<size_t>(best)] * kDim;
         for (int i = 0; i < p_eff; ++i) {
             if (picked[static_cast<size_t>(i)]) continue;
@@ -522,7 +515,7 @@ int node_query_mean_diverse(Node* h, const float* members, int k, const int64_t*
             if (c > pen[static_cast<size_t>(i)]) pen[static_cast<size_t>(i)] = c;
         }
     }
-    if (out_count) *out_count = picks;
+    if (out.count) *out.count = picks;
     return MI355REC_OK;
 }
 

@@ -18,6 +18,7 @@
 #include <cstdint>
 
 #include "mi355rec_diag.h"
+#include "playlist_request.h"
 
 namespace mi355cpu {
 
@@ -59,20 +60,17 @@ int node_query(Node* h, const float* q12, int64_t exclude, int topn, int64_t* ou
 int node_set_labels(Node* h, const int32_t* labels, int64_t n, const char** why);
 int node_query_labels(Node* h, const float* q12, int64_t exclude, const int32_t* set, int n_set, int topn, int64_t* out_idx,
                       float* out_score, int* out_count, const char** why);
-// PLAYLISTS (include/mi355rec_diag.h): the top-N rows by the mean of their scores against members[0..k) (k x 12), the
-// rows of exclude[0..n_exclude) (global ids, validated by the caller) left out; filter: null, or a feature filter (checked
-// by the caller, include/mi355rec_diag.h "FEATURE FILTERS") that every returned row passes; weights: null (the plain mean),
-// or k signed weights checked by the caller ("WEIGHTED PLAYLISTS": score = fl(sum_k fl(w_k c_k)) / fl(sum_k |w_k|)).
-int node_query_mean(Node* h, const float* members, int k, const int64_t* exclude, int n_exclude, int topn, int64_t* out_idx,
-                    float* out_score, int* out_count, const char** why, const mi355rec_filter_t* filter = nullptr,
-                    const float* weights = nullptr);
-// DIVERSIFIED TOP-N (include/mi355rec_diag.h): the top-`pool` of node_query_mean re-ranked by maximal marginal relevance;
-// lambda in [0, 1] and topn <= pool <= 1024 are checked by the caller.  out_score and out_mmr may be null.
-int node_query_mean_diverse(Node* h, const float* members, int k, const int64_t* exclude, int n_exclude, const mi355rec_filter_t* filter,
-                            const float* weights, float lambda, int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
-                            int* out_count, const char** why, int max_per_group = 0, int* out_pool_rows = nullptr);
-// GROUP CAPS (include/mi355rec_diag.h): one group id per row (>= 0, or -1 = never capped; null drops them).  A positive
-// max_per_group above makes node_query_mean_diverse the capped call: a row is eligible while fewer than max_per_group picked
+// PLAYLISTS (include/mi355rec_diag.h): the top-N rows by the mean of their scores against r.members[0..k) (k x 12, by value:
+// the caller has resolved rows), the rows of r.exclude[0..n_exclude) (global ids) left out; r.filter: null, or a feature filter
+// ("FEATURE FILTERS") that every returned row passes; r.weights: null (the plain mean), or k signed weights ("WEIGHTED
+// PLAYLISTS": score = fl(sum_k fl(w_k c_k)) / fl(sum_k |w_k|)).  The request has been checked by the caller
+// (playlist_request.h); the diversified fields are not read.
+int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlist::Outputs& out, const char** why);
+// DIVERSIFIED TOP-N (include/mi355rec_diag.h): the top-`pool` of node_query_mean re-ranked by maximal marginal relevance.
+// out.score and out.mmr may be null.
+int node_query_mean_diverse(Node* h, const mi355playlist::Request& r, const mi355playlist::Outputs& out, const char** why);
+// GROUP CAPS (include/mi355rec_diag.h): one group id per row (>= 0, or -1 = never capped; null drops them).  A capped
+// request makes node_query_mean_diverse the capped call: a row is eligible while fewer than max_per_group picked
 // rows share its group; the loop ends when nothing is eligible; *out_pool_rows = P'.
 int node_set_groups(Node* h, const int32_t* groups, int64_t n, const char** why);
 int node_set_window(Node* h, int window, const char** why);

@@ -1,10 +1,11 @@
 // engine_diverse.hip.h — DIVERSIFIED TOP-N on the single-device handle (include/mi355rec_diag.h, "DIVERSIFIED TOP-N"): the
-// weighted playlist call's top-`pool`, re-ranked by maximal marginal relevance.  The scan launch of the playlist call
-// (playlist_launch, engine_playlist.hip.h), the merge into h->d_keys (no ids or scores are unpacked: the pool never leaves
-// the device), then mmr_rerank_kernel (diverse.hip.h) on the same stream, which stores the picks into the handle's pinned
-// result slots and raises the completion word: the host waits once.  Also here: a pool passed by value (what a row-sharded
-// node does after gathering the pool's rows from its shards) and mi355rec_fetch_rows, both launches of the same kernel.
-// (Part of mi355rec.hip's translation unit, included after engine_playlist.hip.h.)
+// weighted playlist call's top-`pool`, re-ranked by maximal marginal relevance.  What sync_playlist_query
+// (engine_playlist.hip.h) does for a diversified request: the scan launch of the playlist call, the merge into h->d_keys (no
+// ids or scores are unpacked: the pool never leaves the device), then mmr_rerank_kernel (diverse.hip.h) on the same stream,
+// which stores the picks into the handle's pinned result slots and raises the completion word: the host waits once.  Here:
+// that request's checks, the re-rank and the wait, the _diverse and _capped entry points, a pool passed by value (what a
+// row-sharded node does after gathering the pool's rows from its shards) and mi355rec_fetch_rows, both launches of the same
+// kernel.  (Part of mi355rec.hip's translation unit, included after engine_playlist.hip.h.)
 #pragma once
 
 #include <cmath>
@@ -14,16 +15,14 @@
 
 namespace {
 
-// lambda and pool (the other arguments are the playlist call's, checked there with topn = pool).
 // The groups a handle answers from (its own, or its group's of lanes).
 const int32_t* groups_of(const mi355rec* h) { return h->shared ? h->shared->d_groups : h->d_groups; }
 
-int check_diverse(mi355rec* h, float lambda, int pool, int topn) {
-    if (std::isnan(lambda) || lambda < 0.0f || lambda > 1.0f)
-        return fail(h, MI355REC_ERR_INVALID_ARG, "lambda %g out of [0, 1]", static_cast<double>(lambda));
-    if (topn <= 0) return fail(h, MI355REC_ERR_INVALID_ARG, "topn must be positive, got %d", topn);
-    if (pool < topn || pool > kMaxTopK)
-        return fail(h, MI355REC_ERR_INVALID_ARG, "pool %d out of [topn = %d, %d]", pool, topn, kMaxTopK);
+// lambda, topn, pool and the cap (the other arguments are the playlist call's, checked by playlist_launch with topn = pool).
+int check_diverse(mi355rec* h, const Request& r) {
+    char why[128];
+    if (mi355playlist::invalid_diverse(r, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    if (r.capped && !groups_of(h)) return fail(h, MI355REC_ERR_INVALID_ARG, "this handle has no groups (mi355rec_set_groups)");
     return MI355REC_OK;
 }
 
@@ -43,68 +42,32 @@ int ensure_diverse(mi355rec* h) {
     return MI355REC_OK;
 }
 
-void pad_diverse(int from, int topn, int64_t* out_idx, float* out_score, float* out_mmr) {
-    for (int i = from; i < topn; ++i) {
-        out_idx[i] = -1;
-        if (out_score) out_score[i] = 0.0f;
-        if (out_mmr) out_mmr[i] = 0.0f;
-    }
-}
-
-// The re-rank of the `pool` keys in h->d_keys on h->stream, the wait and the results.  rows: the handle's matrix, or
-// (staged) the pool's rows in pool order.  groups: null, or (GROUP CAPS) the device array that goes with `rows`.
-int rerank_and_wait(mi355rec* h, const float* rows, bool staged, int pool, float lambda, int topn, int64_t* out_idx, float* out_score,
-                    float* out_mmr, int* out_count, const int32_t* groups = nullptr, int max_per_group = 0, int* out_pool_rows = nullptr) {
+// The re-rank of the `pool` keys in h->d_keys on h->stream, the wait and the results; of `r`: lambda, topn and the cap.
+// Over the handle's matrix and (GROUP CAPS: the same launch, two more arguments) its groups, or — staged — over the pool's
+// rows and groups in pool order, copied to the playlist state by the caller.
+int rerank_and_wait(mi355rec* h, const Request& r, const Outputs& out, int pool, bool staged) {
     mi355rec_playlist* P = h->playlist;
-    const float mu = 1.0f - lambda;
+    const float* rows = staged ? P->d_rows : h->d_feats;
+    const int32_t* groups = !r.capped ? nullptr : staged ? P->d_pool_groups : groups_of(h);
+    const int topn = r.topn;
+    const float mu = 1.0f - r.lambda;
     const uint32_t want = ++h->done_seq ? h->done_seq : ++h->done_seq;   // never 0
     const int block = (pool + 63) & ~63;
     hipLaunchKernelGGL(mmr_rerank_kernel, dim3(1), dim3(block), 0, h->stream, static_cast<const uint64_t*>(h->d_keys), rows, h->n,
-                       h->row_base, staged ? 1 : 0, pool, topn, lambda, mu, h->hd_idx, h->hd_score, P->hd_mmr,
-                       static_cast<float*>(nullptr), h->hd_done, want, groups, max_per_group,
+                       h->row_base, staged ? 1 : 0, pool, topn, r.lambda, mu, h->hd_idx, h->hd_score, P->hd_mmr,
+                       static_cast<float*>(nullptr), h->hd_done, want, groups, r.max_per_group,
                        groups ? P->hd_pool_rows : static_cast<int*>(nullptr));
     HIP_TRY(h, hipGetLastError());
     const int rc = wait_done(h, want);
     if (rc) return rc;
-    if (out_pool_rows) *out_pool_rows = groups ? *P->h_pool_rows : 0;
+    if (out.pool_rows) *out.pool_rows = groups ? *P->h_pool_rows : 0;
     int c = 0;
     while (c < topn && h->h_idx[c] >= 0) ++c;
-    std::memcpy(out_idx, h->h_idx, static_cast<size_t>(topn) * sizeof(int64_t));
-    if (out_score) std::memcpy(out_score, h->h_score, static_cast<size_t>(topn) * sizeof(float));
-    if (out_mmr) std::memcpy(out_mmr, P->h_mmr, static_cast<size_t>(topn) * sizeof(float));
-    if (out_count) *out_count = c;
+    std::memcpy(out.idx, h->h_idx, static_cast<size_t>(topn) * sizeof(int64_t));
+    if (out.score) std::memcpy(out.score, h->h_score, static_cast<size_t>(topn) * sizeof(float));
+    if (out.mmr) std::memcpy(out.mmr, P->h_mmr, static_cast<size_t>(topn) * sizeof(float));
+    if (out.count) *out.count = c;
     return MI355REC_OK;
-}
-
-int sync_diverse_query(mi355rec* h, const float* members, const int64_t* local_rows, const float* weights, int k,
-                       const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter, float lambda, int pool, int topn,
-                       int64_t* out_idx, float* out_score, float* out_mmr, int* out_count, int max_exclude = kMaxExclude,
-                       bool capped = false, int max_per_group = 0, int* out_pool_rows = nullptr) {
-    if (!out_idx) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    int rc = check_diverse(h, lambda, pool, topn);
-    if (rc) return rc;
-    const int32_t* groups = nullptr;
-    if (capped) {   // GROUP CAPS: the same launches, two more arguments to the re-rank
-        if (max_per_group < 1) return fail(h, MI355REC_ERR_INVALID_ARG, "max_per_group must be positive, got %d", max_per_group);
-        groups = groups_of(h);
-        if (!groups) return fail(h, MI355REC_ERR_INVALID_ARG, "this handle has no groups (mi355rec_set_groups)");
-        if (out_pool_rows) *out_pool_rows = 0;
-    }
-    DeviceGuard guard(h->device);
-    int eff = 0, grid = 0;
-    rc = playlist_launch(h, members, local_rows, k, exclude_global, n_exclude, pool, out_idx, max_exclude, filter, weights, &eff, &grid);
-    if (rc) return rc;
-    if (eff <= 0) {
-        pad_diverse(0, topn, out_idx, out_score, out_mmr);
-        if (out_count) *out_count = 0;
-        return MI355REC_OK;
-    }
-    rc = ensure_diverse(h);
-    if (rc) return rc;
-    rc = enqueue_merge(h, h->d_block_lists, grid, eff, eff, h->d_keys, nullptr, nullptr, h->stream);
-    if (rc) return rc;
-    return rerank_and_wait(h, h->d_feats, false, eff, lambda, topn, out_idx, out_score, out_mmr, out_count, groups, max_per_group,
-                           out_pool_rows);
 }
 
 // `group_ok`: as for the labels (engine_labels.hip.h): the node handle may replace the groups under its own lanes.
@@ -143,22 +106,6 @@ int set_groups_common(mi355rec* h, const int32_t* groups_host, int64_t n, bool g
 }  // namespace
 
 namespace mi355node {
-int query_mean_topn_diverse(mi355rec_t* h, const float* queries, const float* weights, int k, const int64_t* exclude_global, int n_exclude,
-                            const mi355rec_filter_t* filter, float lambda, int pool, int topn, int64_t* out_idx, float* out_score,
-                            float* out_mmr, int* out_count) {
-    if (!h || !queries) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    return sync_diverse_query(h, queries, nullptr, weights, k, exclude_global, n_exclude, filter, lambda, pool, topn, out_idx, out_score,
-                              out_mmr, out_count, kPlExcludeCap);
-}
-
-int query_mean_topn_capped(mi355rec_t* h, const float* queries, const float* weights, int k, const int64_t* exclude_global, int n_exclude,
-                           const mi355rec_filter_t* filter, float lambda, int pool, int max_per_group, int topn, int64_t* out_idx,
-                           float* out_score, float* out_mmr, int* out_count, int* out_pool_rows) {
-    if (!h || !queries) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    return sync_diverse_query(h, queries, nullptr, weights, k, exclude_global, n_exclude, filter, lambda, pool, topn, out_idx, out_score,
-                              out_mmr, out_count, kPlExcludeCap, true, max_per_group, out_pool_rows);
-}
-
 int set_group_groups(mi355rec_t* h, const int32_t* groups_host, int64_t n) { return set_groups_common(h, groups_host, n, true); }
 
 int rerank_pool(mi355rec_t* h, const int64_t* pool_idx, const float* pool_score, const float* pool_rows, int count, float lambda, int topn,
@@ -183,8 +130,12 @@ int rerank_pool(mi355rec_t* h, const int64_t* pool_idx, const float* pool_score,
     if (pool_groups)
         HIP_TRY(h, hipMemcpyAsync(h->playlist->d_pool_groups, pool_groups, sizeof(int32_t) * static_cast<size_t>(count),
                                   hipMemcpyHostToDevice, h->stream));
-    return rerank_and_wait(h, h->playlist->d_rows, true, count, lambda, topn, out_idx, out_score, out_mmr, out_count,
-                           pool_groups ? h->playlist->d_pool_groups : nullptr, max_per_group, out_pool_rows);
+    Request r;   // (what the re-rank reads of a request)
+    r.lambda = lambda;
+    r.topn = topn;
+    r.capped = pool_groups != nullptr;
+    r.max_per_group = max_per_group;
+    return rerank_and_wait(h, r, {out_idx, out_score, out_mmr, out_count, out_pool_rows}, count, true);
 }
 }  // namespace mi355node
 
@@ -193,17 +144,15 @@ extern "C" {
 int mi355rec_query_mean_topn_diverse(mi355rec_t* h, const float* queries, const float* weights, int k, const int64_t* exclude_global,
                                      int n_exclude, const mi355rec_filter_t* filter, float lambda, int pool, int topn, int64_t* out_idx,
                                      float* out_score, float* out_mmr, int* out_count) {
-    if (!h || !queries) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    return sync_diverse_query(h, queries, nullptr, weights, k, exclude_global, n_exclude, filter, lambda, pool, topn, out_idx, out_score,
-                              out_mmr, out_count);
+    return sync_playlist_query(h, request(queries, nullptr, weights, k, exclude_global, n_exclude, filter, topn).diversified(lambda, pool),
+                               {out_idx, out_score, out_mmr, out_count, nullptr});
 }
 
 int mi355rec_query_playlist_topn_diverse(mi355rec_t* h, const int64_t* local_rows, const float* weights, int k,
                                          const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter, float lambda,
                                          int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr, int* out_count) {
-    if (!h || !local_rows) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    return sync_diverse_query(h, nullptr, local_rows, weights, k, exclude_global, n_exclude, filter, lambda, pool, topn, out_idx, out_score,
-                              out_mmr, out_count);
+    return sync_playlist_query(h, request(nullptr, local_rows, weights, k, exclude_global, n_exclude, filter, topn).diversified(lambda, pool),
+                               {out_idx, out_score, out_mmr, out_count, nullptr});
 }
 
 int mi355rec_set_groups(mi355rec_t* h, const int32_t* groups_host, int64_t n) { return set_groups_common(h, groups_host, n, false); }
@@ -211,18 +160,18 @@ int mi355rec_set_groups(mi355rec_t* h, const int32_t* groups_host, int64_t n) { 
 int mi355rec_query_mean_topn_capped(mi355rec_t* h, const float* queries, const float* weights, int k, const int64_t* exclude_global,
                                     int n_exclude, const mi355rec_filter_t* filter, float lambda, int pool, int max_per_group, int topn,
                                     int64_t* out_idx, float* out_score, float* out_mmr, int* out_count, int* out_pool_rows) {
-    if (!h || !queries) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    return sync_diverse_query(h, queries, nullptr, weights, k, exclude_global, n_exclude, filter, lambda, pool, topn, out_idx, out_score,
-                              out_mmr, out_count, kMaxExclude, true, max_per_group, out_pool_rows);
+    return sync_playlist_query(
+        h, request(queries, nullptr, weights, k, exclude_global, n_exclude, filter, topn).diversified(lambda, pool).capped_at(max_per_group),
+        {out_idx, out_score, out_mmr, out_count, out_pool_rows});
 }
 
 int mi355rec_query_playlist_topn_capped(mi355rec_t* h, const int64_t* local_rows, const float* weights, int k,
                                         const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter, float lambda,
                                         int pool, int max_per_group, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
                                         int* out_count, int* out_pool_rows) {
-    if (!h || !local_rows) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    return sync_diverse_query(h, nullptr, local_rows, weights, k, exclude_global, n_exclude, filter, lambda, pool, topn, out_idx, out_score,
-                              out_mmr, out_count, kMaxExclude, true, max_per_group, out_pool_rows);
+    return sync_playlist_query(
+        h, request(nullptr, local_rows, weights, k, exclude_global, n_exclude, filter, topn).diversified(lambda, pool).capped_at(max_per_group),
+        {out_idx, out_score, out_mmr, out_count, out_pool_rows});
 }
 
 int mi355rec_fetch_rows(mi355rec_t* h, const int64_t* local_rows, int64_t count, float* out_host) {

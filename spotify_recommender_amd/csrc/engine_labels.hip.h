@@ -8,6 +8,7 @@
 
 #include "engine_batch.hip.h"
 #include "labels.hip.h"
+#include "playlist_request.h"
 
 // What mi355rec_set_labels leaves on the device, and the offsets again on the host (they size a query's grid).
 struct mi355rec_labels {
@@ -129,11 +130,7 @@ int sync_label_query(mi355rec* h, const float* qptr, const float* query12, int64
     ++h->label_queries;
     const int eff = static_cast<int64_t>(topn) < selected ? topn : static_cast<int>(selected);
     if (eff == 0) {   // nothing selected: nothing to launch
-        for (int i = 0; i < topn; ++i) {
-            out_idx[i] = -1;
-            if (out_score) out_score[i] = 0.0f;
-        }
-        if (out_count) *out_count = 0;
+        mi355playlist::pad({out_idx, out_score, nullptr, out_count, nullptr}, 0, topn, 0);
         return MI355REC_OK;
     }
     DeviceGuard guard(h->device);
@@ -175,11 +172,7 @@ int sync_label_query(mi355rec* h, const float* qptr, const float* query12, int64
     while (c < eff && h->h_idx[c] >= 0) ++c;
     std::memcpy(out_idx, h->h_idx, static_cast<size_t>(eff) * sizeof(int64_t));
     if (out_score) std::memcpy(out_score, h->h_score, static_cast<size_t>(eff) * sizeof(float));
-    for (int i = eff; i < topn; ++i) {
-        out_idx[i] = -1;
-        if (out_score) out_score[i] = 0.0f;
-    }
-    if (out_count) *out_count = c;
+    mi355playlist::pad({out_idx, out_score, nullptr, out_count, nullptr}, eff, topn, c);
     return MI355REC_OK;
 }
 

@@ -2,15 +2,16 @@
 // the mean of their scores against up to 32 member queries, an exclusion list left out.  One playlist_scan_kernel launch
 // (playlist.hip.h), then the merge of merge.hip.h into the handle's pinned result slots and completion word, as
 // sync_label_query does.  No state beyond a small per-handle buffer for the call's inputs, allocated by the first call.
+// Every call of the family (filtered, weighted, diversified, capped; by value or by row) is one mi355playlist::Request
+// (playlist_request.h) through sync_playlist_query; the exported functions only fill it.
 // (Part of mi355rec.hip's translation unit, included after engine_labels.hip.h.)
 #pragma once
 
 #include <algorithm>
 
 #include "engine_labels.hip.h"
-#include "filter_check.h"
 #include "playlist.hip.h"
-#include "weights_check.h"
+#include "playlist_request.h"
 
 // What the first playlist call of a handle allocates.
 struct mi355rec_playlist {
@@ -29,6 +30,10 @@ struct mi355rec_playlist {
 };
 
 namespace {
+
+using mi355playlist::Outputs;
+using mi355playlist::Request;
+using mi355playlist::request;
 
 constexpr int kPlMinTilesPerWg = 8;   // with the pre-filter: a workgroup scans >= 8 tiles (its anchor bound paid for, its own threshold tight)
 
@@ -69,44 +74,24 @@ int ensure_playlist(mi355rec* h) {
     return MI355REC_OK;
 }
 
-// One playlist query, synchronously.  members: k x 12 floats on the host, or null with `local_rows` (k rows of this shard,
-// excluded by their global ids).  exclude_global[0..n_exclude): global ids, any order, duplicates allowed; ids of other
-// shards match nothing here.  filter: null, or the feature filter (include/mi355rec_diag.h, "FEATURE FILTERS"); null and
-// active == 0 launch exactly the unfiltered call.  weights: null, or k signed weights (include/mi355rec_diag.h, "WEIGHTED
-// PLAYLISTS"); null launches the same kernel with every weight 1.0f and W = k, which is the plain mean bit for bit.
+// One call of the playlist family (playlist_request.h), synchronously.  r.members: k x 12 floats on the host, or null with
+// r.rows (k rows of this shard, excluded by their global ids).  r.exclude[0..n_exclude): global ids, any order, duplicates
+// allowed; ids of other shards match nothing here.  r.filter: null, or the feature filter (include/mi355rec_diag.h, "FEATURE
+// FILTERS"); null and active == 0 launch exactly the unfiltered call.  r.weights: null, or k signed weights
+// (include/mi355rec_diag.h, "WEIGHTED PLAYLISTS"); null launches the same kernel with every weight 1.0f and W = k, which is the
+// plain mean bit for bit.
 //
 // playlist_launch is the call up to and including its scan launch: the checks, the staging and playlist_scan_kernel, which
-// leaves `*grid` lists of `*eff` = min(topn, rows left after the exclusion list) keys in h->d_block_lists.  *eff == 0: nothing
-// is left to return and nothing was launched.  What follows the scan is the caller's: sync_playlist_query merges into the
-// result slots; the diversified calls (engine_diverse.hip.h) merge, re-rank and wait once.
-int playlist_launch(mi355rec* h, const float* members, const int64_t* local_rows, int k, const int64_t* exclude_global, int n_exclude,
-                    int topn, const int64_t* out_idx, int max_exclude, const mi355rec_filter_t* filter, const float* weights, int* eff_out,
-                    int* grid_out) {
+// leaves `*grid` lists of `*eff` = min(r.scan_topn(), rows left after the exclusion list) keys in h->d_block_lists.  *eff == 0:
+// nothing is left to return and nothing was launched.  What follows the scan is sync_playlist_query's: the plain call merges
+// into the result slots; the diversified one merges, re-ranks and waits once (engine_diverse.hip.h).
+int playlist_launch(mi355rec* h, const Request& r, int max_exclude, int* eff_out, int* grid_out) {
     *eff_out = 0;
     *grid_out = 0;
-    if (!out_idx) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    if (k < 1 || k > kMaxPlaylist) return fail(h, MI355REC_ERR_INVALID_ARG, "playlist of %d songs: 1 to %d are supported", k, kMaxPlaylist);
-    if (!members && !local_rows) return fail(h, MI355REC_ERR_INVALID_ARG, "null playlist");
-    if (topn <= 0 || topn > kMaxTopK)
-        return fail(h, MI355REC_ERR_INVALID_ARG, "topn %d out of [1, %d] (a playlist query has one round)", topn, kMaxTopK);
-    if (n_exclude < 0 || n_exclude > max_exclude)
-        return fail(h, MI355REC_ERR_INVALID_ARG, "n_exclude %d out of [0, %d]", n_exclude, max_exclude);
-    if (n_exclude > 0 && !exclude_global) return fail(h, MI355REC_ERR_INVALID_ARG, "null exclusion list with n_exclude %d", n_exclude);
-    for (int i = 0; i < n_exclude; ++i)
-        if (exclude_global[i] < 0 || exclude_global[i] > static_cast<int64_t>(UINT32_MAX))
-            return fail(h, MI355REC_ERR_INVALID_ARG, "excluded row %lld out of the catalogue", (long long)exclude_global[i]);
-    if (local_rows)
-        for (int m = 0; m < k; ++m)
-            if (local_rows[m] < 0 || local_rows[m] >= h->n)
-                return fail(h, MI355REC_ERR_INVALID_ARG, "Invalid song index: %lld", (long long)local_rows[m]);
-    if (filter) {
-        char why[128];
-        if (mi355filter::invalid(filter, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    }
-    if (weights) {
-        char why[128];
-        if (mi355weights::invalid(weights, k, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    }
+    char why[128];
+    if (mi355playlist::invalid_playlist(r, h->n, static_cast<int64_t>(UINT32_MAX) + 1, max_exclude, why, sizeof why))
+        return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    const int k = r.k;
     DeviceGuard guard(h->device);
     int rc = ensure_playlist(h);
     if (rc) return rc;
@@ -114,29 +99,29 @@ int playlist_launch(mi355rec* h, const float* members, const int64_t* local_rows
     PlaylistBuf* b = P->h_buf;
     // the excluded rows of this shard: sorted, distinct, as uint32 global ids
     int n_excl = 0;
-    for (int i = 0; i < n_exclude; ++i)
-        if (exclude_global[i] >= h->row_base && exclude_global[i] < h->row_base + h->n) b->excl[n_excl++] = static_cast<uint32_t>(exclude_global[i]);
-    if (local_rows)
-        for (int m = 0; m < k; ++m) b->excl[n_excl++] = static_cast<uint32_t>(h->row_base + local_rows[m]);
+    for (int i = 0; i < r.n_exclude; ++i)
+        if (r.exclude[i] >= h->row_base && r.exclude[i] < h->row_base + h->n) b->excl[n_excl++] = static_cast<uint32_t>(r.exclude[i]);
+    if (r.rows)
+        for (int m = 0; m < k; ++m) b->excl[n_excl++] = static_cast<uint32_t>(h->row_base + r.rows[m]);
     std::sort(b->excl, b->excl + n_excl);
     n_excl = static_cast<int>(std::unique(b->excl, b->excl + n_excl) - b->excl);
     ++h->playlist_queries;
     const int64_t avail = h->n - n_excl;
-    const int eff = static_cast<int64_t>(topn) < avail ? topn : static_cast<int>(avail);
+    const int eff = static_cast<int64_t>(r.scan_topn()) < avail ? r.scan_topn() : static_cast<int>(avail);
     if (eff <= 0) return MI355REC_OK;   // nothing left to return: nothing to launch
     PlaylistArg arg;
     arg.k = k;
     arg.n_excl = n_excl;
-    arg.by_row = local_rows ? 1 : 0;
-    arg.active = filter ? filter->active : 0u;
-    arg.wsum = weights ? mi355weights::sum_abs(weights, k) : static_cast<float>(k);
-    for (int m = 0; m < k; ++m) b->weights[m] = weights ? weights[m] : 1.0f;
+    arg.by_row = r.rows ? 1 : 0;
+    arg.active = r.filter ? r.filter->active : 0u;
+    arg.wsum = r.weights ? mi355weights::sum_abs(r.weights, k) : static_cast<float>(k);
+    for (int m = 0; m < k; ++m) b->weights[m] = r.weights ? r.weights[m] : 1.0f;
     if (arg.active) {
-        std::memcpy(b->lo, filter->lo, sizeof b->lo);
-        std::memcpy(b->hi, filter->hi, sizeof b->hi);
+        std::memcpy(b->lo, r.filter->lo, sizeof b->lo);
+        std::memcpy(b->hi, r.filter->hi, sizeof b->hi);
     }
-    if (local_rows) std::memcpy(b->rows, local_rows, sizeof(int64_t) * static_cast<size_t>(k));
-    else std::memcpy(b->members, members, sizeof(float) * kDim * static_cast<size_t>(k));
+    if (r.rows) std::memcpy(b->rows, r.rows, sizeof(int64_t) * static_cast<size_t>(k));
+    else std::memcpy(b->members, r.members, sizeof(float) * kDim * static_cast<size_t>(k));
     rc = ensure_slots(h, static_cast<size_t>(eff));
     if (rc) return rc;
     rc = sync_api_begin(h);
@@ -161,21 +146,31 @@ int playlist_launch(mi355rec* h, const float* members, const int64_t* local_rows
     return MI355REC_OK;
 }
 
-int sync_playlist_query(mi355rec* h, const float* members, const int64_t* local_rows, int k, const int64_t* exclude_global,
-                        int n_exclude, int topn, int64_t* out_idx, float* out_score, int* out_count, int max_exclude = kMaxExclude,
-                        const mi355rec_filter_t* filter = nullptr, const float* weights = nullptr) {
-    if (!h) return MI355REC_ERR_INVALID_ARG;
+// (engine_diverse.hip.h, included after this file: what a diversified call adds to the path)
+int check_diverse(mi355rec* h, const Request& r);
+int ensure_diverse(mi355rec* h);
+int rerank_and_wait(mi355rec* h, const Request& r, const Outputs& out, int pool, bool staged);
+
+// The one synchronous path of the family.  max_exclude: kMaxExclude for the exported calls, kPlExcludeCap for the node's.
+int sync_playlist_query(mi355rec* h, const Request& r, const Outputs& out, int max_exclude = kMaxExclude) {
+    if (!h || !(r.members || r.rows) || !out.idx) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    int rc = r.diverse ? check_diverse(h, r) : MI355REC_OK;
+    if (rc) return rc;
+    if (out.pool_rows) *out.pool_rows = 0;
     DeviceGuard guard(h->device);
     int eff = 0, grid = 0;
-    int rc = playlist_launch(h, members, local_rows, k, exclude_global, n_exclude, topn, out_idx, max_exclude, filter, weights, &eff, &grid);
+    rc = playlist_launch(h, r, max_exclude, &eff, &grid);
     if (rc) return rc;
     if (eff <= 0) {
-        for (int i = 0; i < topn; ++i) {
-            out_idx[i] = -1;
-            if (out_score) out_score[i] = 0.0f;
-        }
-        if (out_count) *out_count = 0;
+        mi355playlist::pad(out, 0, r.topn, 0);
         return MI355REC_OK;
+    }
+    if (r.diverse) {   // the pool never leaves the device: no ids or scores are unpacked, the re-rank stores the picks
+        rc = ensure_diverse(h);
+        if (rc) return rc;
+        rc = enqueue_merge(h, h->d_block_lists, grid, eff, eff, h->d_keys, nullptr, nullptr, h->stream);
+        if (rc) return rc;
+        return rerank_and_wait(h, r, out, eff, false);
     }
     const bool direct = eff <= kDirectResultSlots;
     const uint32_t want = direct ? (++h->done_seq ? h->done_seq : ++h->done_seq) : 0u;   // never 0
@@ -192,24 +187,17 @@ int sync_playlist_query(mi355rec* h, const float* members, const int64_t* local_
     }
     int c = 0;
     while (c < eff && h->h_idx[c] >= 0) ++c;
-    std::memcpy(out_idx, h->h_idx, static_cast<size_t>(eff) * sizeof(int64_t));
-    if (out_score) std::memcpy(out_score, h->h_score, static_cast<size_t>(eff) * sizeof(float));
-    for (int i = eff; i < topn; ++i) {
-        out_idx[i] = -1;
-        if (out_score) out_score[i] = 0.0f;
-    }
-    if (out_count) *out_count = c;
+    std::memcpy(out.idx, h->h_idx, static_cast<size_t>(eff) * sizeof(int64_t));
+    if (out.score) std::memcpy(out.score, h->h_score, static_cast<size_t>(eff) * sizeof(float));
+    mi355playlist::pad(out, eff, r.topn, c);
     return MI355REC_OK;
 }
 
 }  // namespace
 
 namespace mi355node {
-int query_mean_topn(mi355rec_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude, int topn,
-                    int64_t* out_idx, float* out_score, int* out_count, const mi355rec_filter_t* filter, const float* weights) {
-    if (!h || !queries) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    return sync_playlist_query(h, queries, nullptr, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count, kPlExcludeCap,
-                               filter, weights);
+int query_playlist(mi355rec_t* h, const mi355playlist::Request& r, const mi355playlist::Outputs& out) {
+    return sync_playlist_query(h, r, out, kPlExcludeCap);
 }
 }  // namespace mi355node
 
@@ -217,45 +205,41 @@ extern "C" {
 
 int mi355rec_query_mean_topn(mi355rec_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude, int topn,
                              int64_t* out_idx, float* out_score, int* out_count) {
-    if (!h || !queries) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    return sync_playlist_query(h, queries, nullptr, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count);
+    return sync_playlist_query(h, request(queries, nullptr, nullptr, k, exclude_global, n_exclude, nullptr, topn),
+                               {out_idx, out_score, nullptr, out_count, nullptr});
 }
 
 int mi355rec_query_playlist_topn(mi355rec_t* h, const int64_t* local_rows, int k, const int64_t* exclude_global, int n_exclude,
                                  int topn, int64_t* out_idx, float* out_score, int* out_count) {
-    if (!h || !local_rows) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    return sync_playlist_query(h, nullptr, local_rows, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count);
+    return sync_playlist_query(h, request(nullptr, local_rows, nullptr, k, exclude_global, n_exclude, nullptr, topn),
+                               {out_idx, out_score, nullptr, out_count, nullptr});
 }
 
 int mi355rec_query_mean_topn_where(mi355rec_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude,
                                    const mi355rec_filter_t* filter, int topn, int64_t* out_idx, float* out_score, int* out_count) {
-    if (!h || !queries) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    return sync_playlist_query(h, queries, nullptr, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count, kMaxExclude,
-                               filter);
+    return sync_playlist_query(h, request(queries, nullptr, nullptr, k, exclude_global, n_exclude, filter, topn),
+                               {out_idx, out_score, nullptr, out_count, nullptr});
 }
 
 int mi355rec_query_playlist_topn_where(mi355rec_t* h, const int64_t* local_rows, int k, const int64_t* exclude_global,
                                        int n_exclude, const mi355rec_filter_t* filter, int topn, int64_t* out_idx, float* out_score,
                                        int* out_count) {
-    if (!h || !local_rows) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    return sync_playlist_query(h, nullptr, local_rows, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count, kMaxExclude,
-                               filter);
+    return sync_playlist_query(h, request(nullptr, local_rows, nullptr, k, exclude_global, n_exclude, filter, topn),
+                               {out_idx, out_score, nullptr, out_count, nullptr});
 }
 
 int mi355rec_query_mean_topn_weighted(mi355rec_t* h, const float* queries, const float* weights, int k, const int64_t* exclude_global,
                                       int n_exclude, const mi355rec_filter_t* filter, int topn, int64_t* out_idx, float* out_score,
                                       int* out_count) {
-    if (!h || !queries) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    return sync_playlist_query(h, queries, nullptr, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count, kMaxExclude,
-                               filter, weights);
+    return sync_playlist_query(h, request(queries, nullptr, weights, k, exclude_global, n_exclude, filter, topn),
+                               {out_idx, out_score, nullptr, out_count, nullptr});
 }
 
 int mi355rec_query_playlist_topn_weighted(mi355rec_t* h, const int64_t* local_rows, const float* weights, int k,
                                           const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter, int topn,
                                           int64_t* out_idx, float* out_score, int* out_count) {
-    if (!h || !local_rows) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    return sync_playlist_query(h, nullptr, local_rows, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count, kMaxExclude,
-                               filter, weights);
+    return sync_playlist_query(h, request(nullptr, local_rows, weights, k, exclude_global, n_exclude, filter, topn),
+                               {out_idx, out_score, nullptr, out_count, nullptr});
 }
 
 int mi355rec_playlist_counters(const mi355rec_t* h, int64_t* queries, int64_t* rows_exact) {

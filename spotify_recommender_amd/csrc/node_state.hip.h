@@ -22,31 +22,23 @@
 
 #include "cpu_backend.h"
 #include "mi355rec_diag.h"
+#include "playlist_request.h"
 
 namespace mi355node {
 // mi355rec_set_labels for a handle whose group of lanes the caller has to itself (engine_labels.hip.h): the replicas of a
 // replicated placement that share a device are lanes of the first one there.
 int set_group_labels(mi355rec_t* h, const int32_t* labels_host, int64_t n);
-// mi355rec_query_mean_topn with up to MI355REC_MAX_EXCLUDE + MI355REC_MAX_PLAYLIST excluded ids (engine_playlist.hip.h): the
-// row-sharded node adds the members' global rows to the caller's list.
-// filter: null, or a checked feature filter (include/mi355rec_diag.h, "FEATURE FILTERS"); weights: null, or k weights
-// ("WEIGHTED PLAYLISTS").
-int query_mean_topn(mi355rec_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude, int topn,
-                    int64_t* out_idx, float* out_score, int* out_count, const mi355rec_filter_t* filter, const float* weights);
-// mi355rec_query_mean_topn_diverse with the same longer exclusion list (engine_diverse.hip.h), and the re-rank alone over a
-// pool passed by value: `count` (<= 1024) pool rows in canonical order, their global ids, scores and features (count x 12).
-int query_mean_topn_diverse(mi355rec_t* h, const float* queries, const float* weights, int k, const int64_t* exclude_global, int n_exclude,
-                            const mi355rec_filter_t* filter, float lambda, int pool, int topn, int64_t* out_idx, float* out_score,
-                            float* out_mmr, int* out_count);
+// One call of the playlist family (playlist_request.h) on a shard's handle: what the exported mi355rec_query_mean_topn* /
+// _playlist_topn* calls run, with up to MI355REC_MAX_EXCLUDE + MI355REC_MAX_PLAYLIST excluded ids (engine_playlist.hip.h):
+// the row-sharded node adds the members' global rows to the caller's list.
+int query_playlist(mi355rec_t* h, const mi355playlist::Request& r, const mi355playlist::Outputs& out);
+// The re-rank alone over a pool passed by value (engine_diverse.hip.h): `count` (<= 1024) pool rows in canonical order, their
+// global ids, scores and features (count x 12).
 // GROUP CAPS: pool_groups (null: no cap) are the pool rows' groups in pool order, max_per_group the cap, *out_pool_rows = P'.
 int rerank_pool(mi355rec_t* h, const int64_t* pool_idx, const float* pool_score, const float* pool_rows, int count, float lambda, int topn,
                 int64_t* out_idx, float* out_score, float* out_mmr, int* out_count, const int32_t* pool_groups = nullptr,
                 int max_per_group = 0, int* out_pool_rows = nullptr);
-// mi355rec_query_mean_topn_capped with the longer exclusion list, and mi355rec_set_groups for a handle whose group of lanes
-// the caller has to itself (as set_group_labels).
-int query_mean_topn_capped(mi355rec_t* h, const float* queries, const float* weights, int k, const int64_t* exclude_global, int n_exclude,
-                           const mi355rec_filter_t* filter, float lambda, int pool, int max_per_group, int topn, int64_t* out_idx,
-                           float* out_score, float* out_mmr, int* out_count, int* out_pool_rows);
+// mi355rec_set_groups for a handle whose group of lanes the caller has to itself (as set_group_labels).
 int set_group_groups(mi355rec_t* h, const int32_t* groups_host, int64_t n);
 }  // namespace mi355node
 
@@ -715,6 +707,53 @@ int take_replica(mi355rec_sharded* h, Shard** out) {
     if (rc) return rc;
     S_HIP(h, hipSetDevice(h->shards[r].device));
     *out = &h->shards[r];
+    return MI355REC_OK;
+}
+
+// "One handle holds the whole catalogue" (one shard, or replicas: row_base 0): `call` on that handle's engine — the only
+// shard's, or the replica whose turn it is — and its error as the node's.  The caller holds a DeviceRestore.
+template <class Call>
+int on_whole_catalogue(mi355rec_sharded_t* h, Call&& call) {
+    Shard* s = &h->shards[0];
+    if (h->replicated) {
+        const int rc = take_replica(h, &s);
+        if (rc) return rc;
+    } else {
+        S_HIP(h, hipSetDevice(s->device));
+    }
+    const int rc = call(s->engine);
+    return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s->engine));
+}
+
+// A query on a ROW-SHARDED catalogue (the workers drained): call(engine, idx, score, count) asks a shard for its top-`topn`,
+// the per-shard lists are merged on the host by key — exact, since every shard's list holds its best min(topn, rows) keys.
+template <class Call>
+int merge_over_shards(mi355rec_sharded_t* h, int topn, const mi355playlist::Outputs& out, Call&& call) {
+    std::vector<mi355rec_key_t> keys;
+    std::vector<int64_t> idx;
+    std::vector<float> sc;
+    try {
+        idx.resize(static_cast<size_t>(topn));
+        sc.resize(static_cast<size_t>(topn));
+        keys.reserve(static_cast<size_t>(topn) * h->shards.size());
+    } catch (const std::bad_alloc&) {
+        return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for %d results per shard", topn);
+    }
+    for (Shard& s : h->shards) {
+        if (s.hi <= s.lo) continue;
+        S_HIP(h, hipSetDevice(s.device));
+        int c = 0;
+        const int rc = call(s.engine, idx.data(), sc.data(), &c);
+        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", s.device, mi355rec_last_error(s.engine));
+        for (int i = 0; i < c; ++i) keys.push_back(mi355rec_pack_key(sc[static_cast<size_t>(i)], idx[static_cast<size_t>(i)]));
+    }
+    const size_t count = keys.size() < static_cast<size_t>(topn) ? keys.size() : static_cast<size_t>(topn);
+    std::partial_sort(keys.begin(), keys.begin() + count, keys.end(), std::greater<mi355rec_key_t>());
+    for (size_t i = 0; i < count; ++i) {
+        out.idx[i] = mi355rec_key_row(keys[i]);
+        if (out.score) out.score[i] = mi355rec_key_score(keys[i]);
+    }
+    mi355playlist::pad(out, static_cast<int>(count), topn, static_cast<int>(count));
     return MI355REC_OK;
 }
 

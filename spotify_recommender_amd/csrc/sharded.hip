@@ -54,9 +54,7 @@
 // A "shard" of a replicated handle is a full replica (lo = 0, hi = n).
 #include <cmath>
 
-#include "filter_check.h"
 #include "node_stream.hip.h"
-#include "weights_check.h"
 
 extern "C" {
 
@@ -587,36 +585,13 @@ int mi355rec_sharded_set_groups(mi355rec_sharded_t* h, const int32_t* groups_hos
 }
 
 namespace {
-// A filtered query on a ROW-SHARDED catalogue: the query by value on every shard (the query row excluded by its global index),
-// the per-shard lists merged on the host by key — exact, since every shard's list holds its best min(topn, rows) keys.
+// A filtered query on a row-sharded catalogue: the query by value on every shard (the query row excluded by its global index).
 int sharded_labels_by_value(mi355rec_sharded_t* h, const float* q, int64_t exclude_global, const int32_t* labels, int n_labels,
                             int topn, int64_t* out_idx, float* out_score, int* out_count) {
-    std::vector<mi355rec_key_t> keys;
-    std::vector<int64_t> idx;
-    std::vector<float> sc;
-    try {
-        idx.resize(static_cast<size_t>(topn));
-        sc.resize(static_cast<size_t>(topn));
-        keys.reserve(static_cast<size_t>(topn) * h->shards.size());
-    } catch (const std::bad_alloc&) {
-        return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for %d results per shard", topn);
-    }
-    for (Shard& s : h->shards) {
-        if (s.hi <= s.lo) continue;
-        S_HIP(h, hipSetDevice(s.device));
-        int c = 0;
-        const int rc = mi355rec_query_topn_labels(s.engine, q, exclude_global, labels, n_labels, topn, idx.data(), sc.data(), &c);
-        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", s.device, mi355rec_last_error(s.engine));
-        for (int i = 0; i < c; ++i) keys.push_back(mi355rec_pack_key(sc[static_cast<size_t>(i)], idx[static_cast<size_t>(i)]));
-    }
-    const size_t count = keys.size() < static_cast<size_t>(topn) ? keys.size() : static_cast<size_t>(topn);
-    std::partial_sort(keys.begin(), keys.begin() + count, keys.end(), std::greater<mi355rec_key_t>());
-    for (size_t i = 0; i < static_cast<size_t>(topn); ++i) {
-        out_idx[i] = i < count ? mi355rec_key_row(keys[i]) : -1;
-        if (out_score) out_score[i] = i < count ? mi355rec_key_score(keys[i]) : 0.0f;
-    }
-    if (out_count) *out_count = static_cast<int>(count);
-    return MI355REC_OK;
+    return merge_over_shards(h, topn, {out_idx, out_score, nullptr, out_count, nullptr},
+                             [&](mi355rec_t* e, int64_t* idx, float* sc, int* c) {
+                                 return mi355rec_query_topn_labels(e, q, exclude_global, labels, n_labels, topn, idx, sc, c);
+                             });
 }
 }  // namespace
 
@@ -630,17 +605,10 @@ int mi355rec_sharded_query_topn_labels(mi355rec_sharded_t* h, const float* query
                                                          out_count, &why), why);
     }
     DeviceRestore restore;
-    if (h->shards.size() == 1 || h->replicated) {   // one handle holds the whole catalogue
-        Shard* s = &h->shards[0];
-        if (h->replicated) {
-            const int rc = take_replica(h, &s);
-            if (rc) return rc;
-        } else {
-            S_HIP(h, hipSetDevice(s->device));
-        }
-        const int rc = mi355rec_query_topn_labels(s->engine, query12, exclude_global, labels, n_labels, topn, out_idx, out_score, out_count);
-        return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s->engine));
-    }
+    if (h->shards.size() == 1 || h->replicated)
+        return on_whole_catalogue(h, [&](mi355rec_t* e) {
+            return mi355rec_query_topn_labels(e, query12, exclude_global, labels, n_labels, topn, out_idx, out_score, out_count);
+        });
     const int rc = drain_workers(h);
     if (rc) return rc;
     return sharded_labels_by_value(h, query12, exclude_global, labels, n_labels, topn, out_idx, out_score, out_count);
@@ -658,17 +626,10 @@ int mi355rec_sharded_query_row_topn_labels(mi355rec_sharded_t* h, int64_t global
                                                          labels, n_labels, topn, out_idx, out_score, out_count, &why), why);
     }
     DeviceRestore restore;
-    if (h->shards.size() == 1 || h->replicated) {   // one handle holds the whole catalogue (row_base 0)
-        Shard* s = &h->shards[0];
-        if (h->replicated) {
-            const int rc = take_replica(h, &s);
-            if (rc) return rc;
-        } else {
-            S_HIP(h, hipSetDevice(s->device));
-        }
-        const int rc = mi355rec_query_row_topn_labels(s->engine, global_row, labels, n_labels, topn, out_idx, out_score, out_count);
-        return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s->engine));
-    }
+    if (h->shards.size() == 1 || h->replicated)
+        return on_whole_catalogue(h, [&](mi355rec_t* e) {
+            return mi355rec_query_row_topn_labels(e, global_row, labels, n_labels, topn, out_idx, out_score, out_count);
+        });
     int rc = drain_workers(h);
     if (rc) return rc;
     const Shard* own = owner_of(h, global_row);
@@ -679,222 +640,24 @@ int mi355rec_sharded_query_row_topn_labels(mi355rec_sharded_t* h, int64_t global
     return sharded_labels_by_value(h, q, global_row, labels, n_labels, topn, out_idx, out_score, out_count);
 }
 
-// ---- PLAYLISTS (include/mi355rec_diag.h) ------------------------------------------------------------------------------
+// ---- PLAYLISTS, FEATURE FILTERS, WEIGHTED PLAYLISTS, DIVERSIFIED TOP-N, GROUP CAPS (include/mi355rec_diag.h) -----------------
 namespace {
-// The node-level checks of both playlist calls (the catalogue's global rows are known here).
-int check_playlist(mi355rec_sharded_t* h, const void* members, int k, const int64_t* exclude_global, int n_exclude, int topn,
-                   int64_t* out_idx) {
-    if (!h || !members || !out_idx) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    if (k < 1 || k > MI355REC_MAX_PLAYLIST)
-        return sfail(h, MI355REC_ERR_INVALID_ARG, "playlist of %d songs: 1 to %d are supported", k, MI355REC_MAX_PLAYLIST);
-    if (topn <= 0 || topn > MI355REC_MAX_TOPN_FAST)
-        return sfail(h, MI355REC_ERR_INVALID_ARG, "topn %d out of [1, %d] (a playlist query has one round)", topn, MI355REC_MAX_TOPN_FAST);
-    if (n_exclude < 0 || n_exclude > MI355REC_MAX_EXCLUDE)
-        return sfail(h, MI355REC_ERR_INVALID_ARG, "n_exclude %d out of [0, %d]", n_exclude, MI355REC_MAX_EXCLUDE);
-    if (n_exclude > 0 && !exclude_global) return sfail(h, MI355REC_ERR_INVALID_ARG, "null exclusion list with n_exclude %d", n_exclude);
-    for (int i = 0; i < n_exclude; ++i)
-        if (exclude_global[i] < 0 || exclude_global[i] >= h->n)
-            return sfail(h, MI355REC_ERR_INVALID_ARG, "excluded row %lld out of the catalogue", (long long)exclude_global[i]);
-    return MI355REC_OK;
-}
+using mi355playlist::Outputs;
+using mi355playlist::Request;
+using mi355playlist::request;
 
-// The feature filter's checks (FEATURE FILTERS; null: no filter).
-int check_filter(mi355rec_sharded_t* h, const mi355rec_filter_t* filter) {
-    char why[128];
-    if (filter && mi355filter::invalid(filter, why, sizeof why)) return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    return MI355REC_OK;
-}
-
-// The weights' checks (WEIGHTED PLAYLISTS; null: unweighted; k already checked).
-int check_weights(mi355rec_sharded_t* h, const float* weights, int k) {
-    char why[128];
-    if (weights && mi355weights::invalid(weights, k, why, sizeof why)) return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    return MI355REC_OK;
-}
-
-// members (k x 12, by value) and the excluded global ids: the CPU backend, one handle, or every shard and a host merge.
-// filter, weights: null or checked; every shard gets them.
-int sharded_mean(mi355rec_sharded_t* h, const float* members, int k, const int64_t* excl, int n_excl, int topn, int64_t* out_idx,
-                 float* out_score, int* out_count, const mi355rec_filter_t* filter = nullptr, const float* weights = nullptr) {
-    if (h->cpu) {
-        const char* why = nullptr;
-        return cpu_result(
-            h, mi355cpu::node_query_mean(h->cpu, members, k, excl, n_excl, topn, out_idx, out_score, out_count, &why, filter, weights), why);
-    }
-    DeviceRestore restore;
-    if (h->shards.size() == 1 || h->replicated) {   // one handle holds the whole catalogue (row_base 0)
-        Shard* s = &h->shards[0];
-        if (h->replicated) {
-            const int rc = take_replica(h, &s);
-            if (rc) return rc;
-        } else {
-            S_HIP(h, hipSetDevice(s->device));
-        }
-        const int rc = mi355node::query_mean_topn(s->engine, members, k, excl, n_excl, topn, out_idx, out_score, out_count, filter, weights);
-        return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s->engine));
-    }
-    const int drc = drain_workers(h);
-    if (drc) return drc;
-    std::vector<mi355rec_key_t> keys;
-    std::vector<int64_t> idx;
-    std::vector<float> sc;
-    try {
-        idx.resize(static_cast<size_t>(topn));
-        sc.resize(static_cast<size_t>(topn));
-        keys.reserve(static_cast<size_t>(topn) * h->shards.size());
-    } catch (const std::bad_alloc&) {
-        return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for %d results per shard", topn);
-    }
-    for (Shard& s : h->shards) {   // every shard gets the whole list and matches the ids of its own rows
-        if (s.hi <= s.lo) continue;
-        S_HIP(h, hipSetDevice(s.device));
-        int c = 0;
-        const int rc = mi355node::query_mean_topn(s.engine, members, k, excl, n_excl, topn, idx.data(), sc.data(), &c, filter, weights);
-        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", s.device, mi355rec_last_error(s.engine));
-        for (int i = 0; i < c; ++i) keys.push_back(mi355rec_pack_key(sc[static_cast<size_t>(i)], idx[static_cast<size_t>(i)]));
-    }
-    const size_t count = keys.size() < static_cast<size_t>(topn) ? keys.size() : static_cast<size_t>(topn);
-    std::partial_sort(keys.begin(), keys.begin() + count, keys.end(), std::greater<mi355rec_key_t>());
-    for (size_t i = 0; i < static_cast<size_t>(topn); ++i) {
-        out_idx[i] = i < count ? mi355rec_key_row(keys[i]) : -1;
-        if (out_score) out_score[i] = i < count ? mi355rec_key_score(keys[i]) : 0.0f;
-    }
-    if (out_count) *out_count = static_cast<int>(count);
-    return MI355REC_OK;
-}
-}  // namespace
-
-int mi355rec_sharded_query_mean_topn(mi355rec_sharded_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude,
-                                     int topn, int64_t* out_idx, float* out_score, int* out_count) {
-    const int rc = check_playlist(h, queries, k, exclude_global, n_exclude, topn, out_idx);
-    if (rc) return rc;
-    return sharded_mean(h, queries, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count);
-}
-
-int mi355rec_sharded_query_mean_topn_where(mi355rec_sharded_t* h, const float* queries, int k, const int64_t* exclude_global,
-                                           int n_exclude, const mi355rec_filter_t* filter, int topn, int64_t* out_idx,
-                                           float* out_score, int* out_count) {
-    int rc = check_playlist(h, queries, k, exclude_global, n_exclude, topn, out_idx);
-    if (!rc) rc = check_filter(h, filter);
-    if (rc) return rc;
-    return sharded_mean(h, queries, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count, filter);
-}
-
-int mi355rec_sharded_query_playlist_topn(mi355rec_sharded_t* h, const int64_t* global_rows, int k, const int64_t* exclude_global,
-                                         int n_exclude, int topn, int64_t* out_idx, float* out_score, int* out_count) {
-    return mi355rec_sharded_query_playlist_topn_where(h, global_rows, k, exclude_global, n_exclude, nullptr, topn, out_idx, out_score,
-                                                      out_count);
-}
-
-int mi355rec_sharded_query_mean_topn_weighted(mi355rec_sharded_t* h, const float* queries, const float* weights, int k,
-                                              const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
-                                              int topn, int64_t* out_idx, float* out_score, int* out_count) {
-    int rc = check_playlist(h, queries, k, exclude_global, n_exclude, topn, out_idx);
-    if (!rc) rc = check_filter(h, filter);
-    if (!rc) rc = check_weights(h, weights, k);
-    if (rc) return rc;
-    return sharded_mean(h, queries, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count, filter, weights);
-}
-
-int mi355rec_sharded_query_playlist_topn_where(mi355rec_sharded_t* h, const int64_t* global_rows, int k,
-                                               const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
-                                               int topn, int64_t* out_idx, float* out_score, int* out_count) {
-    return mi355rec_sharded_query_playlist_topn_weighted(h, global_rows, nullptr, k, exclude_global, n_exclude, filter, topn, out_idx,
-                                                         out_score, out_count);
-}
-
-int mi355rec_sharded_query_playlist_topn_weighted(mi355rec_sharded_t* h, const int64_t* global_rows, const float* weights, int k,
-                                                  const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
-                                                  int topn, int64_t* out_idx, float* out_score, int* out_count) {
-    int rc = check_playlist(h, global_rows, k, exclude_global, n_exclude, topn, out_idx);
-    if (rc) return rc;
-    for (int m = 0; m < k; ++m)
-        if (global_rows[m] < 0 || global_rows[m] >= h->n)
-            return sfail(h, MI355REC_ERR_INVALID_ARG, "Invalid song index: %lld", (long long)global_rows[m]);
-    rc = check_filter(h, filter);
-    if (!rc) rc = check_weights(h, weights, k);
-    if (rc) return rc;
-    if (!h->cpu && h->shards.size() == 1 && !h->replicated) {   // one handle: its own by-row call (the members stay on the device)
-        DeviceRestore restore;
-        Shard& s = h->shards[0];
-        S_HIP(h, hipSetDevice(s.device));
-        rc = weights ? mi355rec_query_playlist_topn_weighted(s.engine, global_rows, weights, k, exclude_global, n_exclude, filter, topn,
-                                                             out_idx, out_score, out_count)
-             : filter ? mi355rec_query_playlist_topn_where(s.engine, global_rows, k, exclude_global, n_exclude, filter, topn, out_idx,
-                                                         out_score, out_count)
-                    : mi355rec_query_playlist_topn(s.engine, global_rows, k, exclude_global, n_exclude, topn, out_idx, out_score, out_count);
-        return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s.engine));
-    }
-    // the members by value (fetched once) and their rows added to the exclusion list
-    float members[MI355REC_MAX_PLAYLIST * MI355REC_DIM];
-    int64_t excl[MI355REC_MAX_EXCLUDE + MI355REC_MAX_PLAYLIST];
-    for (int i = 0; i < n_exclude; ++i) excl[i] = exclude_global[i];
-    for (int m = 0; m < k; ++m) {
-        excl[n_exclude + m] = global_rows[m];
-        if (h->cpu) {
-            std::memcpy(members + m * MI355REC_DIM, mi355cpu::row(mi355cpu::node_catalogue(h->cpu), global_rows[m]), sizeof(float) * MI355REC_DIM);
-            continue;
-        }
-        if (m == 0) {
-            rc = drain_workers(h);
-            if (rc) return rc;
-        }
-        DeviceRestore restore;
-        const Shard* own = owner_of(h, global_rows[m]);
-        S_HIP(h, hipSetDevice(own->device));
-        rc = mi355rec_fetch_row(own->engine, global_rows[m] - own->lo, members + m * MI355REC_DIM);
-        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
-    }
-    return sharded_mean(h, members, k, excl, n_exclude + k, topn, out_idx, out_score, out_count, filter, weights);
-}
-
-// ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h) -------------------------------------------------------------------------
-namespace {
-// lambda and pool (check_playlist has seen topn = pool).
-int check_diverse(mi355rec_sharded_t* h, float lambda, int pool, int topn) {
-    if (std::isnan(lambda) || lambda < 0.0f || lambda > 1.0f)
-        return sfail(h, MI355REC_ERR_INVALID_ARG, "lambda %g out of [0, 1]", static_cast<double>(lambda));
-    if (topn <= 0) return sfail(h, MI355REC_ERR_INVALID_ARG, "topn must be positive, got %d", topn);
-    if (pool < topn || pool > MI355REC_MAX_TOPN_FAST)
-        return sfail(h, MI355REC_ERR_INVALID_ARG, "pool %d out of [topn = %d, %d]", pool, topn, MI355REC_MAX_TOPN_FAST);
-    return MI355REC_OK;
-}
-
-// members by value and the excluded global ids, all checked: the CPU backend, one handle, or — row-sharded — the pool from
-// sharded_mean, its rows gathered from their shards (one mi355rec_fetch_rows per shard that owns any) and the re-rank on the
+// The diversified call on a ROW-SHARDED catalogue (members by value, all checked): the pool from every shard's mean call merged
+// on the host, its rows gathered from their shards (one mi355rec_fetch_rows per shard that owns any) and the re-rank on the
 // first shard's device over the pool passed by value.
-int sharded_diverse(mi355rec_sharded_t* h, const float* members, const float* weights, int k, const int64_t* excl, int n_excl,
-                    const mi355rec_filter_t* filter, float lambda, int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
-                    int* out_count, int max_per_group = 0, int* out_pool_rows = nullptr) {
-    const bool capped = max_per_group > 0;   // GROUP CAPS (checked by the caller)
-    if (out_pool_rows) *out_pool_rows = 0;
-    if (h->cpu) {
-        const char* why = nullptr;
-        return cpu_result(h, mi355cpu::node_query_mean_diverse(h->cpu, members, k, excl, n_excl, filter, weights, lambda, pool, topn, out_idx,
-                                                              out_score, out_mmr, out_count, &why, max_per_group, out_pool_rows), why);
-    }
-    DeviceRestore restore;
-    if (h->shards.size() == 1 || h->replicated) {   // one handle holds the whole catalogue (row_base 0)
-        Shard* s = &h->shards[0];
-        if (h->replicated) {
-            const int rc = take_replica(h, &s);
-            if (rc) return rc;
-        } else {
-            S_HIP(h, hipSetDevice(s->device));
-        }
-        const int rc = capped ? mi355node::query_mean_topn_capped(s->engine, members, weights, k, excl, n_excl, filter, lambda, pool,
-                                                                  max_per_group, topn, out_idx, out_score, out_mmr, out_count, out_pool_rows)
-                              : mi355node::query_mean_topn_diverse(s->engine, members, weights, k, excl, n_excl, filter, lambda, pool, topn,
-                                                                   out_idx, out_score, out_mmr, out_count);
-        return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s->engine));
-    }
-    if (capped && !h->has_groups) return sfail(h, MI355REC_ERR_INVALID_ARG, "this handle has no groups (mi355rec_sharded_set_groups)");
+int diverse_over_shards(mi355rec_sharded_t* h, const Request& r, const Outputs& out) {
+    const int pool = r.pool;
+    if (r.capped && !h->has_groups) return sfail(h, MI355REC_ERR_INVALID_ARG, "this handle has no groups (mi355rec_sharded_set_groups)");
     std::vector<int64_t> pidx, local;
     std::vector<float> prel, rows, part;
     std::vector<int> where;
     std::vector<int32_t> pgroups;
     try {
-        if (capped) pgroups.resize(static_cast<size_t>(pool));
+        if (r.capped) pgroups.resize(static_cast<size_t>(pool));
         pidx.resize(static_cast<size_t>(pool));
         prel.resize(static_cast<size_t>(pool));
         rows.resize(static_cast<size_t>(pool) * MI355REC_DIM);
@@ -905,15 +668,16 @@ int sharded_diverse(mi355rec_sharded_t* h, const float* members, const float* we
         return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for a pool of %d rows", pool);
     }
     int p_eff = 0;
-    int rc = sharded_mean(h, members, k, excl, n_excl, pool, pidx.data(), prel.data(), &p_eff, filter, weights);
+    int rc = drain_workers(h);
+    if (rc) return rc;
+    const Request mean = r.pool_call();
+    rc = merge_over_shards(h, pool, {pidx.data(), prel.data(), nullptr, &p_eff, nullptr},
+                           [&](mi355rec_t* e, int64_t* idx, float* sc, int* c) {
+                               return mi355node::query_playlist(e, mean, {idx, sc, nullptr, c, nullptr});
+                           });
     if (rc) return rc;
     if (p_eff <= 0) {
-        for (int i = 0; i < topn; ++i) {
-            out_idx[i] = -1;
-            if (out_score) out_score[i] = 0.0f;
-            if (out_mmr) out_mmr[i] = 0.0f;
-        }
-        if (out_count) *out_count = 0;
+        mi355playlist::pad(out, 0, r.topn, 0);
         return MI355REC_OK;
     }
     for (Shard& s : h->shards) {
@@ -939,70 +703,121 @@ int sharded_diverse(mi355rec_sharded_t* h, const float* members, const float* we
             break;
         }
     S_HIP(h, hipSetDevice(first->device));
-    for (int i = 0; capped && i < p_eff; ++i) pgroups[static_cast<size_t>(i)] = h->groups[static_cast<size_t>(pidx[static_cast<size_t>(i)])];
-    rc = mi355node::rerank_pool(first->engine, pidx.data(), prel.data(), rows.data(), p_eff, lambda, topn, out_idx, out_score, out_mmr, out_count,
-                                capped ? pgroups.data() : nullptr, max_per_group, out_pool_rows);
+    for (int i = 0; r.capped && i < p_eff; ++i) pgroups[static_cast<size_t>(i)] = h->groups[static_cast<size_t>(pidx[static_cast<size_t>(i)])];
+    rc = mi355node::rerank_pool(first->engine, pidx.data(), prel.data(), rows.data(), p_eff, r.lambda, r.topn, out.idx, out.score, out.mmr,
+                                out.count, r.capped ? pgroups.data() : nullptr, r.max_per_group, out.pool_rows);
     return rc == MI355REC_OK ? rc : sfail(h, rc, "shard on device %d: %s", first->device, mi355rec_last_error(first->engine));
 }
+
+// Every call of the family on the node handle: the checks (the catalogue's global rows are known here), the members of a
+// by-row call by value where no single handle can read them, then the CPU backend, the one handle that holds the whole
+// catalogue, or every shard and a host merge.
+int sharded_playlist(mi355rec_sharded_t* h, Request r, const Outputs& out) {
+    if (!h || !(r.members || r.rows) || !out.idx) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    char why[128];
+    if ((r.diverse && mi355playlist::invalid_diverse(r, why, sizeof why)) ||
+        mi355playlist::invalid_playlist(r, h->n, h->n, MI355REC_MAX_EXCLUDE, why, sizeof why))
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    if (out.pool_rows) *out.pool_rows = 0;
+    // By row, one handle (row_base 0) takes its own by-row call below: the members stay on the device.  Otherwise the members
+    // go by value (fetched once) and their rows are added to the exclusion list.
+    float members[MI355REC_MAX_PLAYLIST * MI355REC_DIM];
+    int64_t excl[MI355REC_MAX_EXCLUDE + MI355REC_MAX_PLAYLIST];
+    if (r.rows && (h->cpu || h->shards.size() > 1 || h->replicated)) {
+        for (int i = 0; i < r.n_exclude; ++i) excl[i] = r.exclude[i];
+        for (int m = 0; m < r.k; ++m) {
+            excl[r.n_exclude + m] = r.rows[m];
+            if (h->cpu) {
+                std::memcpy(members + m * MI355REC_DIM, mi355cpu::row(mi355cpu::node_catalogue(h->cpu), r.rows[m]), sizeof(float) * MI355REC_DIM);
+                continue;
+            }
+            if (m == 0) {
+                const int rc = drain_workers(h);
+                if (rc) return rc;
+            }
+            DeviceRestore restore;
+            const Shard* own = owner_of(h, r.rows[m]);
+            S_HIP(h, hipSetDevice(own->device));
+            const int rc = mi355rec_fetch_row(own->engine, r.rows[m] - own->lo, members + m * MI355REC_DIM);
+            if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
+        }
+        r.members = members;
+        r.rows = nullptr;
+        r.exclude = excl;
+        r.n_exclude += r.k;
+    }
+    if (h->cpu) {
+        const char* cpu_why = nullptr;
+        return cpu_result(h, r.diverse ? mi355cpu::node_query_mean_diverse(h->cpu, r, out, &cpu_why)
+                                       : mi355cpu::node_query_mean(h->cpu, r, out, &cpu_why), cpu_why);
+    }
+    DeviceRestore restore;
+    if (h->shards.size() == 1 || h->replicated)
+        return on_whole_catalogue(h, [&](mi355rec_t* e) { return mi355node::query_playlist(e, r, out); });
+    if (r.diverse) return diverse_over_shards(h, r, out);
+    const int rc = drain_workers(h);
+    if (rc) return rc;
+    // every shard gets the whole exclusion list and matches the ids of its own rows
+    return merge_over_shards(h, r.topn, out, [&](mi355rec_t* e, int64_t* idx, float* sc, int* c) {
+        return mi355node::query_playlist(e, r, {idx, sc, nullptr, c, nullptr});
+    });
+}
 }  // namespace
+
+int mi355rec_sharded_query_mean_topn(mi355rec_sharded_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude,
+                                     int topn, int64_t* out_idx, float* out_score, int* out_count) {
+    return sharded_playlist(h, request(queries, nullptr, nullptr, k, exclude_global, n_exclude, nullptr, topn),
+                            {out_idx, out_score, nullptr, out_count, nullptr});
+}
+
+int mi355rec_sharded_query_mean_topn_where(mi355rec_sharded_t* h, const float* queries, int k, const int64_t* exclude_global,
+                                           int n_exclude, const mi355rec_filter_t* filter, int topn, int64_t* out_idx,
+                                           float* out_score, int* out_count) {
+    return sharded_playlist(h, request(queries, nullptr, nullptr, k, exclude_global, n_exclude, filter, topn),
+                            {out_idx, out_score, nullptr, out_count, nullptr});
+}
+
+int mi355rec_sharded_query_mean_topn_weighted(mi355rec_sharded_t* h, const float* queries, const float* weights, int k,
+                                              const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
+                                              int topn, int64_t* out_idx, float* out_score, int* out_count) {
+    return sharded_playlist(h, request(queries, nullptr, weights, k, exclude_global, n_exclude, filter, topn),
+                            {out_idx, out_score, nullptr, out_count, nullptr});
+}
+
+int mi355rec_sharded_query_playlist_topn(mi355rec_sharded_t* h, const int64_t* global_rows, int k, const int64_t* exclude_global,
+                                         int n_exclude, int topn, int64_t* out_idx, float* out_score, int* out_count) {
+    return sharded_playlist(h, request(nullptr, global_rows, nullptr, k, exclude_global, n_exclude, nullptr, topn),
+                            {out_idx, out_score, nullptr, out_count, nullptr});
+}
+
+int mi355rec_sharded_query_playlist_topn_where(mi355rec_sharded_t* h, const int64_t* global_rows, int k,
+                                               const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
+                                               int topn, int64_t* out_idx, float* out_score, int* out_count) {
+    return sharded_playlist(h, request(nullptr, global_rows, nullptr, k, exclude_global, n_exclude, filter, topn),
+                            {out_idx, out_score, nullptr, out_count, nullptr});
+}
+
+int mi355rec_sharded_query_playlist_topn_weighted(mi355rec_sharded_t* h, const int64_t* global_rows, const float* weights, int k,
+                                                  const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
+                                                  int topn, int64_t* out_idx, float* out_score, int* out_count) {
+    return sharded_playlist(h, request(nullptr, global_rows, weights, k, exclude_global, n_exclude, filter, topn),
+                            {out_idx, out_score, nullptr, out_count, nullptr});
+}
 
 int mi355rec_sharded_query_mean_topn_diverse(mi355rec_sharded_t* h, const float* queries, const float* weights, int k,
                                              const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
                                              float lambda, int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
                                              int* out_count) {
-    if (!h || !queries || !out_idx) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    int rc = check_diverse(h, lambda, pool, topn);
-    if (!rc) rc = check_playlist(h, queries, k, exclude_global, n_exclude, pool, out_idx);
-    if (!rc) rc = check_filter(h, filter);
-    if (!rc) rc = check_weights(h, weights, k);
-    if (rc) return rc;
-    return sharded_diverse(h, queries, weights, k, exclude_global, n_exclude, filter, lambda, pool, topn, out_idx, out_score, out_mmr,
-                           out_count);
+    return sharded_playlist(h, request(queries, nullptr, weights, k, exclude_global, n_exclude, filter, topn).diversified(lambda, pool),
+                            {out_idx, out_score, out_mmr, out_count, nullptr});
 }
 
 int mi355rec_sharded_query_playlist_topn_diverse(mi355rec_sharded_t* h, const int64_t* global_rows, const float* weights, int k,
                                                  const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
                                                  float lambda, int pool, int topn, int64_t* out_idx, float* out_score, float* out_mmr,
                                                  int* out_count) {
-    if (!h || !global_rows || !out_idx) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    int rc = check_diverse(h, lambda, pool, topn);
-    if (!rc) rc = check_playlist(h, global_rows, k, exclude_global, n_exclude, pool, out_idx);
-    if (rc) return rc;
-    for (int m = 0; m < k; ++m)
-        if (global_rows[m] < 0 || global_rows[m] >= h->n)
-            return sfail(h, MI355REC_ERR_INVALID_ARG, "Invalid song index: %lld", (long long)global_rows[m]);
-    rc = check_filter(h, filter);
-    if (!rc) rc = check_weights(h, weights, k);
-    if (rc) return rc;
-    if (!h->cpu && h->shards.size() == 1 && !h->replicated) {   // one handle: its own by-row call (the members stay on the device)
-        DeviceRestore restore;
-        Shard& s = h->shards[0];
-        S_HIP(h, hipSetDevice(s.device));
-        rc = mi355rec_query_playlist_topn_diverse(s.engine, global_rows, weights, k, exclude_global, n_exclude, filter, lambda, pool, topn,
-                                                  out_idx, out_score, out_mmr, out_count);
-        return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s.engine));
-    }
-    // the members by value (fetched once) and their rows added to the exclusion list
-    float members[MI355REC_MAX_PLAYLIST * MI355REC_DIM];
-    int64_t excl[MI355REC_MAX_EXCLUDE + MI355REC_MAX_PLAYLIST];
-    for (int i = 0; i < n_exclude; ++i) excl[i] = exclude_global[i];
-    for (int m = 0; m < k; ++m) {
-        excl[n_exclude + m] = global_rows[m];
-        if (h->cpu) {
-            std::memcpy(members + m * MI355REC_DIM, mi355cpu::row(mi355cpu::node_catalogue(h->cpu), global_rows[m]), sizeof(float) * MI355REC_DIM);
-            continue;
-        }
-        if (m == 0) {
-            rc = drain_workers(h);
-            if (rc) return rc;
-        }
-        DeviceRestore restore;
-        const Shard* own = owner_of(h, global_rows[m]);
-        S_HIP(h, hipSetDevice(own->device));
-        rc = mi355rec_fetch_row(own->engine, global_rows[m] - own->lo, members + m * MI355REC_DIM);
-        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
-    }
-    return sharded_diverse(h, members, weights, k, excl, n_exclude + k, filter, lambda, pool, topn, out_idx, out_score, out_mmr, out_count);
+    return sharded_playlist(h, request(nullptr, global_rows, weights, k, exclude_global, n_exclude, filter, topn).diversified(lambda, pool),
+                            {out_idx, out_score, out_mmr, out_count, nullptr});
 }
 
 // GROUP CAPS (include/mi355rec_diag.h): the diversified calls above with the cap; the groups are checked where they live.
@@ -1010,62 +825,18 @@ int mi355rec_sharded_query_mean_topn_capped(mi355rec_sharded_t* h, const float* 
                                              const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
                                              float lambda, int pool, int max_per_group, int topn, int64_t* out_idx, float* out_score,
                                             float* out_mmr, int* out_count, int* out_pool_rows) {
-    if (!h || !queries || !out_idx) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    int rc = check_diverse(h, lambda, pool, topn);
-    if (!rc && max_per_group < 1) rc = sfail(h, MI355REC_ERR_INVALID_ARG, "max_per_group must be positive, got %d", max_per_group);
-    if (!rc) rc = check_playlist(h, queries, k, exclude_global, n_exclude, pool, out_idx);
-    if (!rc) rc = check_filter(h, filter);
-    if (!rc) rc = check_weights(h, weights, k);
-    if (rc) return rc;
-    return sharded_diverse(h, queries, weights, k, exclude_global, n_exclude, filter, lambda, pool, topn, out_idx, out_score, out_mmr,
-                           out_count, max_per_group, out_pool_rows);
+    return sharded_playlist(
+        h, request(queries, nullptr, weights, k, exclude_global, n_exclude, filter, topn).diversified(lambda, pool).capped_at(max_per_group),
+        {out_idx, out_score, out_mmr, out_count, out_pool_rows});
 }
 
 int mi355rec_sharded_query_playlist_topn_capped(mi355rec_sharded_t* h, const int64_t* global_rows, const float* weights, int k,
                                                  const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
                                                  float lambda, int pool, int max_per_group, int topn, int64_t* out_idx, float* out_score,
                                                 float* out_mmr, int* out_count, int* out_pool_rows) {
-    if (!h || !global_rows || !out_idx) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    int rc = check_diverse(h, lambda, pool, topn);
-    if (!rc && max_per_group < 1) rc = sfail(h, MI355REC_ERR_INVALID_ARG, "max_per_group must be positive, got %d", max_per_group);
-    if (!rc) rc = check_playlist(h, global_rows, k, exclude_global, n_exclude, pool, out_idx);
-    if (rc) return rc;
-    for (int m = 0; m < k; ++m)
-        if (global_rows[m] < 0 || global_rows[m] >= h->n)
-            return sfail(h, MI355REC_ERR_INVALID_ARG, "Invalid song index: %lld", (long long)global_rows[m]);
-    rc = check_filter(h, filter);
-    if (!rc) rc = check_weights(h, weights, k);
-    if (rc) return rc;
-    if (!h->cpu && h->shards.size() == 1 && !h->replicated) {   // one handle: its own by-row call (the members stay on the device)
-        DeviceRestore restore;
-        Shard& s = h->shards[0];
-        S_HIP(h, hipSetDevice(s.device));
-        rc = mi355rec_query_playlist_topn_capped(s.engine, global_rows, weights, k, exclude_global, n_exclude, filter, lambda, pool,
-                                                 max_per_group, topn, out_idx, out_score, out_mmr, out_count, out_pool_rows);
-        return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s.engine));
-    }
-    // the members by value (fetched once) and their rows added to the exclusion list
-    float members[MI355REC_MAX_PLAYLIST * MI355REC_DIM];
-    int64_t excl[MI355REC_MAX_EXCLUDE + MI355REC_MAX_PLAYLIST];
-    for (int i = 0; i < n_exclude; ++i) excl[i] = exclude_global[i];
-    for (int m = 0; m < k; ++m) {
-        excl[n_exclude + m] = global_rows[m];
-        if (h->cpu) {
-            std::memcpy(members + m * MI355REC_DIM, mi355cpu::row(mi355cpu::node_catalogue(h->cpu), global_rows[m]), sizeof(float) * MI355REC_DIM);
-            continue;
-        }
-        if (m == 0) {
-            rc = drain_workers(h);
-            if (rc) return rc;
-        }
-        DeviceRestore restore;
-        const Shard* own = owner_of(h, global_rows[m]);
-        S_HIP(h, hipSetDevice(own->device));
-        rc = mi355rec_fetch_row(own->engine, global_rows[m] - own->lo, members + m * MI355REC_DIM);
-        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
-    }
-    return sharded_diverse(h, members, weights, k, excl, n_exclude + k, filter, lambda, pool, topn, out_idx, out_score, out_mmr, out_count,
-                           max_per_group, out_pool_rows);
+    return sharded_playlist(
+        h, request(nullptr, global_rows, weights, k, exclude_global, n_exclude, filter, topn).diversified(lambda, pool).capped_at(max_per_group),
+        {out_idx, out_score, out_mmr, out_count, out_pool_rows});
 }
 
 int mi355rec_sharded_scores_row(mi355rec_sharded_t* h, int64_t global_row, float* out_host) {

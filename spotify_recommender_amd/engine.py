@@ -37,20 +37,6 @@ def _labels_query(fn, h, check, head, labels, topn: int) -> Tuple[np.ndarray, np
     return idx[:count.value].copy(), score[:count.value].copy()
 
 
-def _playlist_query(fn, h, check, members, exclude, topn: int) -> Tuple[np.ndarray, np.ndarray]:
-    """Runs one playlist entry point: fn(h, members, k, exclude, n_exclude, topn, idx, score, &count).  `members` is a
-    (k, 12) float32 array (by value) or a 1-D int64 array of rows (by row)."""
-    k = int(members.shape[0])
-    ex = np.ascontiguousarray(np.asarray([] if exclude is None else list(exclude), dtype=np.int64).reshape(-1))
-    n_out = max(int(topn), 1)
-    idx = np.empty(n_out, dtype=np.int64)
-    score = np.empty(n_out, dtype=np.float32)
-    count = ctypes.c_int(0)
-    check(fn(h, members.ctypes.data_as(ctypes.c_void_p), k, ex.ctypes.data_as(ctypes.c_void_p) if ex.size else None, int(ex.size),
-             int(topn), idx.ctypes.data_as(ctypes.c_void_p), score.ctypes.data_as(ctypes.c_void_p), ctypes.byref(count)))
-    return idx[:count.value].copy(), score[:count.value].copy()
-
-
 def make_filter(where) -> capi.Filter:
     """mi355rec_filter_t from a `where=` mapping {feature index (0..11) or name (capi.FEATURE_NAMES): (lo, hi)}: a row passes
     iff lo <= x[j] <= hi for every named feature (the stored fp32 values, e.g. [0, 1] for the drop-in's normalised
@@ -76,64 +62,79 @@ def make_filter(where) -> capi.Filter:
     return f
 
 
-def _where_query(fn, h, check, members, exclude, where, topn: int) -> Tuple[np.ndarray, np.ndarray]:
-    """Runs one filtered playlist entry point: fn(h, members, k, exclude, n_exclude, &filter, topn, idx, score, &count)."""
-    flt = make_filter(where)
-    return _playlist_query(lambda h_, m, k, e, n_e, *rest: fn(h_, m, k, e, n_e, ctypes.byref(flt), *rest), h, check, members,
-                           exclude, topn)
+_PLAYLIST_LEVELS = ("", "_where", "_weighted", "_diverse", "_capped")   # each level's entry point takes the previous one's arguments and its own
 
 
-def _weighted_query(fn, h, check, members, weights, exclude, where, topn: int) -> Tuple[np.ndarray, np.ndarray]:
-    """Runs one weighted playlist entry point: fn(h, members, weights, k, exclude, n_exclude, filter or NULL, topn, idx, score,
-    &count).  `weights`: one float per member, any sign (WEIGHTED PLAYLISTS)."""
-    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
-    if w.size != members.shape[0]:
-        raise ValueError(f"{w.size} weights for {members.shape[0]} songs: one weight per song")
-    flt = ctypes.byref(make_filter(where)) if where is not None else None
-    return _playlist_query(lambda h_, m, k, e, n_e, *rest: fn(h_, m, w.ctypes.data_as(ctypes.c_void_p), k, e, n_e, flt, *rest), h,
-                           check, members, exclude, topn)
+def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=None, where=None, weights=None, level: str = None,
+                     lam=None, pool=None, max_per_group=None, return_mmr: bool = False, return_pool_rows: bool = False):
+    """Runs one entry point of the playlist family: `prefix`query_{mean|playlist}_topn`level`.  `members` is a (k, 12) float32
+    array (by value: mean) or a 1-D int64 array of rows (by row: playlist).  `level` None: the lowest that takes the
+    arguments given ("" plain, "_where" with a filter, "_weighted" with weights); "_diverse" and "_capped" are asked for.
+    The C argument list, in order: h, members, [weights or NULL: from _weighted on], k, exclude, n_exclude, [filter or NULL:
+    from _where on], [lambda, pool: from _diverse on], [max_per_group: _capped], topn, idx, score, [mmr: from _diverse on],
+    &count, [&pool_rows: _capped].
 
-
-def _diverse_query(fn, h, check, members, weights, exclude, where, lam, pool, topn: int, return_mmr: bool):
-    """Runs one diversified entry point (DIVERSIFIED TOP-N): fn(h, members, weights or NULL, k, exclude, n_exclude, filter or
-    NULL, lambda, pool, topn, idx, score, mmr, &count).  `lam` in [0, 1] (1: relevance only); `pool`: how many of the most
-    relevant rows the picks are made from, None = min(1024, max(topn, 4 * topn)).  Results come in pick order; the scores are
-    the relevance; with return_mmr a third array holds the mmr value of each pick."""
-    if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)):
-        raise ValueError(f"lam must be a number in [0, 1], got {lam!r}")
-    if pool is None:
-        pool = min(1024, max(int(topn), 4 * int(topn)))
-    elif isinstance(pool, bool) or not isinstance(pool, (int, np.integer)):
-        raise ValueError(f"pool must be an integer or None, got {pool!r}")
+    `where`: FEATURE FILTERS (make_filter).  `weights`: one float per member, any sign (WEIGHTED PLAYLISTS).
+    DIVERSIFIED TOP-N: `lam` in [0, 1] (1: relevance only); `pool`: how many of the most relevant rows the picks are made
+    from, None = min(1024, max(topn, 4 * topn)) (8 * topn capped).  Results come in pick order; the scores are the relevance;
+    with return_mmr a third array holds the mmr value of each pick.
+    GROUP CAPS: `lam` = 1.0 is relevance order with at most `max_per_group` results per group.  With return_pool_rows the last
+    element is pool_rows: fewer than `topn` ids with pool_rows == pool means the pool ran out (raise `pool`), with
+    pool_rows < pool that the catalogue has no more."""
+    if level is None:
+        level = "_weighted" if weights is not None else "_where" if where is not None else ""
+    rank = _PLAYLIST_LEVELS.index(level)
+    diverse, capped = rank >= 3, rank == 4
+    if capped and (isinstance(max_per_group, bool) or not isinstance(max_per_group, (int, np.integer))):
+        raise ValueError(f"max_per_group must be an integer, got {max_per_group!r}")
+    if diverse:
+        if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)):
+            raise ValueError(f"lam must be a number in [0, 1], got {lam!r}")
+        if pool is None:
+            pool = min(1024, max(int(topn), (8 if capped else 4) * int(topn)))
+        elif isinstance(pool, bool) or not isinstance(pool, (int, np.integer)):
+            raise ValueError(f"pool must be an integer or None, got {pool!r}")
+    k = int(members.shape[0])
     w = None
     if weights is not None:
         w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
-        if w.size != members.shape[0]:
-            raise ValueError(f"{w.size} weights for {members.shape[0]} songs: one weight per song")
-    flt = ctypes.byref(make_filter(where)) if where is not None else None
-    mmr = np.zeros(max(int(topn), 1), dtype=np.float32)
-    wp = w.ctypes.data_as(ctypes.c_void_p) if w is not None else None
-    idx, score = _playlist_query(
-        lambda h_, m, k, e, n_e, topn_, i_, s_, c_: fn(h_, m, wp, k, e, n_e, flt, ctypes.c_float(float(lam)), int(pool), topn_, i_, s_,
-                                                       mmr.ctypes.data_as(ctypes.c_void_p), c_),
-        h, check, members, exclude, topn)
-    return (idx, score, mmr[:idx.size].copy()) if return_mmr else (idx, score)
+        if w.size != k:
+            raise ValueError(f"{w.size} weights for {k} songs: one weight per song")
+    flt = make_filter(where) if where is not None else None
+    ex = np.ascontiguousarray(np.asarray([] if exclude is None else list(exclude), dtype=np.int64).reshape(-1))
+    n_out = max(int(topn), 1)
+    idx = np.empty(n_out, dtype=np.int64)
+    score = np.empty(n_out, dtype=np.float32)
+    mmr = np.zeros(n_out, dtype=np.float32)
+    count, pool_rows = ctypes.c_int(0), ctypes.c_int(0)
 
+    def ptr(a):
+        return a.ctypes.data_as(ctypes.c_void_p)
 
-def _capped_query(fn, h, check, members, weights, exclude, where, lam, pool, max_per_group, topn: int, return_mmr: bool,
-                  return_pool_rows: bool):
-    """Runs one capped entry point (GROUP CAPS): the diversified call's arguments with max_per_group after pool and &pool_rows
-    last.  `lam` = 1.0: relevance order with at most `max_per_group` results per group; `pool` None = min(1024, max(topn,
-    8 * topn)).  Returns (ids, scores[, mmr][, pool_rows]): fewer than `topn` ids with pool_rows == pool means the pool ran
-    out (raise `pool`), with pool_rows < pool that the catalogue has no more."""
-    if pool is None:
-        pool = min(1024, max(int(topn), 8 * int(topn)))
-    if isinstance(max_per_group, bool) or not isinstance(max_per_group, (int, np.integer)):
-        raise ValueError(f"max_per_group must be an integer, got {max_per_group!r}")
-    pool_rows = ctypes.c_int(0)
-    out = _diverse_query(lambda *a: fn(*a[:9], int(max_per_group), *a[9:], ctypes.byref(pool_rows)), h, check, members, weights,
-                         exclude, where, lam, pool, topn, return_mmr)
-    return out + (pool_rows.value,) if return_pool_rows else out
+    args = [h, ptr(members)]
+    if rank >= 2:
+        args.append(ptr(w) if w is not None else None)
+    args += [k, ptr(ex) if ex.size else None, int(ex.size)]
+    if rank >= 1:
+        args.append(ctypes.byref(flt) if flt is not None else None)
+    if diverse:
+        args += [ctypes.c_float(float(lam)), int(pool)]
+    if capped:
+        args.append(int(max_per_group))
+    args += [int(topn), ptr(idx), ptr(score)]
+    if diverse:
+        args.append(ptr(mmr))
+    args.append(ctypes.byref(count))
+    if capped:
+        args.append(ctypes.byref(pool_rows))
+    by = "playlist" if members.dtype == np.int64 else "mean"
+    check(getattr(lib, f"{prefix}query_{by}_topn{level}")(*args))
+    out = (idx[:count.value].copy(), score[:count.value].copy())
+    if return_mmr:
+        out += (mmr[:count.value].copy(),)
+    if return_pool_rows:
+        out += (pool_rows.value,)
+    return out
 
 
 def _np_groups(groups) -> np.ndarray:
@@ -499,37 +500,26 @@ class CosineEngine:
         filtered single query is k = 1); None calls the unfiltered entry point.
         `weights`: one signed float per member (WEIGHTED PLAYLISTS: score = sum w_k c_k / sum |w_k|, a negative weight is
         a dislike); None calls the entry point used without it."""
-        check = lambda rc: capi.check(rc, self._h)   # noqa: E731
-        if weights is not None:
-            return _weighted_query(self._lib.mi355rec_query_mean_topn_weighted, self._h, check, _np_members(queries), weights,
-                                   exclude, where, topn)
-        if where is not None:
-            return _where_query(self._lib.mi355rec_query_mean_topn_where, self._h, check, _np_members(queries), exclude, where, topn)
-        return _playlist_query(self._lib.mi355rec_query_mean_topn, self._h, check, _np_members(queries), exclude, topn)
+        return self._playlist(_np_members(queries), topn, exclude, where, weights)
 
     def query_playlist_topn(self, local_rows, topn: int, exclude=None, where=None, weights=None) -> Tuple[np.ndarray, np.ndarray]:
         """The same for members given as rows of this handle; the members are never returned (whatever their weight)."""
-        check = lambda rc: capi.check(rc, self._h)   # noqa: E731
-        if weights is not None:
-            return _weighted_query(self._lib.mi355rec_query_playlist_topn_weighted, self._h, check, _np_rows(local_rows), weights,
-                                   exclude, where, topn)
-        if where is not None:
-            return _where_query(self._lib.mi355rec_query_playlist_topn_where, self._h, check, _np_rows(local_rows), exclude, where,
-                                topn)
-        return _playlist_query(self._lib.mi355rec_query_playlist_topn, self._h, check, _np_rows(local_rows), exclude, topn)
+        return self._playlist(_np_rows(local_rows), topn, exclude, where, weights)
+
+    def _playlist(self, members, topn, exclude, where, weights, level=None, **more):
+        return _playlist_family(self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), members, topn, exclude, where,
+                                weights, level, **more)
 
     # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h): MMR picks from the top-`pool` of the weighted playlist call ----
     def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False):
         """`topn` rows picked greedily from the `pool` most relevant (query_mean_topn's order): each pick maximises
         lam * relevance - (1 - lam) * (its largest similarity to a row already picked).  Pick order; scores = relevance."""
-        return _diverse_query(self._lib.mi355rec_query_mean_topn_diverse, self._h, lambda rc: capi.check(rc, self._h),
-                              _np_members(queries), weights, exclude, where, lam, pool, topn, return_mmr)
+        return self._playlist(_np_members(queries), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr)
 
     def query_playlist_topn_diverse(self, local_rows, topn: int, lam, pool=None, exclude=None, where=None, weights=None,
                                     return_mmr=False):
         """The same for members given as rows of this handle (never returned)."""
-        return _diverse_query(self._lib.mi355rec_query_playlist_topn_diverse, self._h, lambda rc: capi.check(rc, self._h),
-                              _np_rows(local_rows), weights, exclude, where, lam, pool, topn, return_mmr)
+        return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr)
 
     def set_groups(self, groups) -> None:
         """One group id per row (GROUP CAPS): >= 0 a group (an artist, say), -1 = never capped; None drops the groups."""
@@ -542,13 +532,13 @@ class CosineEngine:
     def query_mean_topn_capped(self, queries, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
                                weights=None, return_mmr=False, return_pool_rows=False):
         """query_mean_topn_diverse with at most `max_per_group` results per group of set_groups (GROUP CAPS)."""
-        return _capped_query(self._lib.mi355rec_query_mean_topn_capped, self._h, lambda rc: capi.check(rc, self._h),
-                             _np_members(queries), weights, exclude, where, lam, pool, max_per_group, topn, return_mmr, return_pool_rows)
+        return self._playlist(_np_members(queries), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
+                              max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows)
 
     def query_playlist_topn_capped(self, local_rows, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
                                    weights=None, return_mmr=False, return_pool_rows=False):
-        return _capped_query(self._lib.mi355rec_query_playlist_topn_capped, self._h, lambda rc: capi.check(rc, self._h),
-                             _np_rows(local_rows), weights, exclude, where, lam, pool, max_per_group, topn, return_mmr, return_pool_rows)
+        return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
+                              max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows)
 
     def fetch_rows(self, local_rows) -> np.ndarray:
         """The features of the listed rows (any order, duplicates allowed), gathered on the device: (len, 12) float32."""
@@ -680,23 +670,14 @@ class NodeEngine:
 
     # ---- PLAYLISTS (include/mi355rec_diag.h) over the whole node ----
     def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None) -> Tuple[np.ndarray, np.ndarray]:
-        if weights is not None:
-            return _weighted_query(self._lib.mi355rec_sharded_query_mean_topn_weighted, self._h, self._check, _np_members(queries),
-                                   weights, exclude, where, topn)
-        if where is not None:
-            return _where_query(self._lib.mi355rec_sharded_query_mean_topn_where, self._h, self._check, _np_members(queries), exclude,
-                                where, topn)
-        return _playlist_query(self._lib.mi355rec_sharded_query_mean_topn, self._h, self._check, _np_members(queries), exclude, topn)
+        return self._playlist(_np_members(queries), topn, exclude, where, weights)
 
     def query_playlist_topn(self, global_rows, topn: int, exclude=None, where=None, weights=None) -> Tuple[np.ndarray, np.ndarray]:
-        if weights is not None:
-            return _weighted_query(self._lib.mi355rec_sharded_query_playlist_topn_weighted, self._h, self._check,
-                                   _np_rows(global_rows), weights, exclude, where, topn)
-        if where is not None:
-            return _where_query(self._lib.mi355rec_sharded_query_playlist_topn_where, self._h, self._check, _np_rows(global_rows),
-                                exclude, where, topn)
-        return _playlist_query(self._lib.mi355rec_sharded_query_playlist_topn, self._h, self._check, _np_rows(global_rows), exclude,
-                               topn)
+        return self._playlist(_np_rows(global_rows), topn, exclude, where, weights)
+
+    def _playlist(self, members, topn, exclude, where, weights, level=None, **more):
+        return _playlist_family(self._lib, "mi355rec_sharded_", self._h, self._check, members, topn, exclude, where, weights, level,
+                                **more)
 
     # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h) over the whole node ----
     def set_groups(self, groups) -> None:
@@ -709,22 +690,20 @@ class NodeEngine:
 
     def query_mean_topn_capped(self, queries, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
                                weights=None, return_mmr=False, return_pool_rows=False):
-        return _capped_query(self._lib.mi355rec_sharded_query_mean_topn_capped, self._h, self._check, _np_members(queries), weights,
-                             exclude, where, lam, pool, max_per_group, topn, return_mmr, return_pool_rows)
+        return self._playlist(_np_members(queries), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
+                              max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows)
 
     def query_playlist_topn_capped(self, global_rows, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
                                    weights=None, return_mmr=False, return_pool_rows=False):
-        return _capped_query(self._lib.mi355rec_sharded_query_playlist_topn_capped, self._h, self._check, _np_rows(global_rows),
-                             weights, exclude, where, lam, pool, max_per_group, topn, return_mmr, return_pool_rows)
+        return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
+                              max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows)
 
     def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False):
-        return _diverse_query(self._lib.mi355rec_sharded_query_mean_topn_diverse, self._h, self._check, _np_members(queries), weights,
-                              exclude, where, lam, pool, topn, return_mmr)
+        return self._playlist(_np_members(queries), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr)
 
     def query_playlist_topn_diverse(self, global_rows, topn: int, lam, pool=None, exclude=None, where=None, weights=None,
                                     return_mmr=False):
-        return _diverse_query(self._lib.mi355rec_sharded_query_playlist_topn_diverse, self._h, self._check, _np_rows(global_rows),
-                              weights, exclude, where, lam, pool, topn, return_mmr)
+        return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr)
 
     def scores_row(self, global_row: int) -> np.ndarray:
         out = np.empty(self.rows, dtype=np.float32)
