@@ -86,8 +86,8 @@ bool multi_front_q8(const mi355rec* h, int nq) {
 }
 
 bool half_multi_ok(const mi355rec* h, int topn) {
-    return h->d_half && h->replica_mode != MI355REC_REPLICA_OFF && topn <= kMultiMaxTopK && h->hg.seed_grid > 0 &&
-           h->hg.seed_grid * kHalfSeedWaves >= topn;
+    return h->d_half && h->replica_mode != MI355REC_REPLICA_OFF && topn <= kMultiMaxTopK && h->geom[kFp16].seed_grid > 0 &&
+           h->geom[kFp16].seed_grid * kHalfSeedWaves >= topn;
 }
 
 void fill_half_multi_arg(HalfMultiArg& arg, const mi355rec* h, const float* queries, const float* const* qptrs, const int64_t* exclude,
@@ -117,13 +117,13 @@ int hm_sample_log2(const mi355rec* h, int nq, bool riding) {
     int l = nq >= 12 ? 2 : nq >= 5 ? 1 : 0;
     if (riding && l > 1) l = 1;
     MI355REC_EXP_INT(l, "MI355REC_EXP_SAMPLE_LOG2", 0, 3);
-    while (l > 0 && (static_cast<int64_t>(1024) << l) > h->hg.seed_stride) --l;
+    while (l > 0 && (static_cast<int64_t>(1024) << l) > h->geom[kFp16].seed_stride) --l;
     return l;
 }
 
 int enqueue_half_multi(mi355rec* h, const float* queries, const float* const* qptrs, const int64_t* exclude, int count,
                        int topn, uint64_t* out_keys, int64_t* out_idx, float* out_score, hipStream_t s) {
-    const int n_seed = h->hg.seed_grid * kHalfSeedWaves;
+    const int n_seed = h->geom[kFp16].seed_grid * kHalfSeedWaves;
     HmRide no_ride;
     std::memset(&no_ride, 0, sizeof no_ride);
     HalfMultiArg arg;
@@ -134,11 +134,11 @@ int enqueue_half_multi(mi355rec* h, const float* queries, const float* const* qp
         // the sample launch's last workgroup selects the cutoffs; the pass reads them (stream order)
         const unsigned long long* const cuts = h->d_half_mcuts;
         // (+ one workgroup per query for its neighbourhood's bound: handoff.hip.h)
-        hipLaunchKernelGGL(seed_half_multi_kernel, dim3(h->hg.seed_grid + nq), dim3(kHmBlock), 0, s, h->d_feats, h->d_half, h->n, h->row_base,
-                           h->hg.seed_stride, arg, nq, h->hg.seed_grid, h->d_half_mseed, epoch, hm_sample_log2(h, nq, false), h->d_half_mctl,
+        hipLaunchKernelGGL(seed_half_multi_kernel, dim3(h->geom[kFp16].seed_grid + nq), dim3(kHmBlock), 0, s, h->d_feats, h->d_half, h->n, h->row_base,
+                           h->geom[kFp16].seed_stride, arg, nq, h->geom[kFp16].seed_grid, h->d_half_mseed, epoch, hm_sample_log2(h, nq, false), h->d_half_mctl,
                            h->half_mctl_done + (h->dbg_no_last ? 0x40000000u : 0u), h->d_half_mcuts, topn, h->dbg_skip_regions);
         HIP_TRY(h, hipGetLastError());
-        h->half_mctl_done += static_cast<unsigned>(h->hg.seed_grid);
+        h->half_mctl_done += static_cast<unsigned>(h->geom[kFp16].seed_grid);
         h->dbg_no_last = false;   // (test hooks of mi355rec_debug_handoff: they apply to ONE sampling launch)
         h->dbg_skip_regions = 0;
         ++h->half_scans;
@@ -146,22 +146,22 @@ int enqueue_half_multi(mi355rec* h, const float* queries, const float* const* qp
         if (multi_front_q8(h, nq)) {   // rows from the 8-bit replica through the integer matrix core (replica_multi.hip.h)
             ++h->q8_scans;
             ++h->routes.multi_q8;
-            LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_half_multi_kernel<false, true>), dim3(h->hg.grid),
+            LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_half_multi_kernel<false, true>), dim3(h->geom[kFp16].grid),
                          dim3(kHmBlock), s, h->d_feats, h->d_half, reinterpret_cast<const uint32_t*>(h->d_q8), h->n, h->row_base, arg, nq,
                          g0, topn, h->d_block_lists, h->d_half_mseed, n_seed, h->d_half_rescored, no_ride, arg, cuts, epoch);
         } else
 #endif
         {
             ++h->routes.multi_fp16;
-            LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_half_multi_kernel<false, false>), dim3(h->hg.grid),
+            LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_half_multi_kernel<false, false>), dim3(h->geom[kFp16].grid),
                          dim3(kHmBlock), s, h->d_feats, h->d_half, static_cast<const uint32_t*>(nullptr), h->n, h->row_base, arg, nq,
                          g0, topn, h->d_block_lists, h->d_half_mseed, n_seed, h->d_half_rescored, no_ride, arg, cuts, epoch);
         }
     }
     HIP_TRY(h, hipGetLastError());
     const int slot = timing_begin(h, h->ev_merge, h->n_merge_pairs, h->merge_launches, s);
-    hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(kMergeBlock), 0, s, h->d_block_lists, h->hg.grid, topn,
-                       static_cast<int64_t>(topn), static_cast<int64_t>(h->hg.grid) * topn, topn, out_keys, out_idx, out_score,
+    hipLaunchKernelGGL(merge_kernel, dim3(count), dim3(kMergeBlock), 0, s, h->d_block_lists, h->geom[kFp16].grid, topn,
+                       static_cast<int64_t>(topn), static_cast<int64_t>(h->geom[kFp16].grid) * topn, topn, out_keys, out_idx, out_score,
                        static_cast<int64_t>(topn), static_cast<uint32_t*>(nullptr), 0u);
     timing_end(h, h->ev_merge, h->n_merge_pairs, slot, s);
     HIP_TRY(h, hipGetLastError());
@@ -183,7 +183,7 @@ constexpr int kHmNbhdPerWg = 4;     // queries of the next batch one neighbourho
 
 int ensure_mstream(mi355rec* h) {
     if (h->mstream_ready) return MI355REC_OK;
-    const size_t list_bytes = sizeof(uint64_t) * static_cast<size_t>(kHmQueries) * h->hg.grid * kMultiMaxTopK;
+    const size_t list_bytes = sizeof(uint64_t) * static_cast<size_t>(kHmQueries) * h->geom[kFp16].grid * kMultiMaxTopK;
     const size_t seed_bytes = sizeof(unsigned long long) * static_cast<size_t>(kHmSampleSlots);
     hipError_t e = hipSuccess;
     for (int i = 0; i < 2 && e == hipSuccess; ++i) {
@@ -233,7 +233,7 @@ int launch_mstash(mi355rec* h, hipStream_t s, const HalfMultiArg* next, int next
         ride.sample_log2 = hm_sample_log2(h, next_nq, true);
         ride.seed_wgs = kHmRiders << ride.sample_log2;
         MI355REC_EXP_INT(ride.seed_wgs, "MI355REC_EXP_RIDERS", 1, 512);
-        if (ride.seed_wgs > h->hg.seed_grid) ride.seed_wgs = h->hg.seed_grid;
+        if (ride.seed_wgs > h->geom[kFp16].seed_grid) ride.seed_wgs = h->geom[kFp16].seed_grid;
         // (a query that excludes no row of this shard looks for its anchor first — handoff.hip.h, nbhd_anchor: two more round
         // trips per query — so a workgroup takes half as many of a batch that holds such queries)
         bool anchors = false;
@@ -242,8 +242,8 @@ int launch_mstash(mi355rec* h, hipStream_t s, const HalfMultiArg* next, int next
         const int per_wg = anchors ? (kHmNbhdPerWg + 1) / 2 : kHmNbhdPerWg;
         ride.nb_wgs = (next_nq + per_wg - 1) / per_wg;
         ride.next_queries = next_nq;
-        ride.regions = h->hg.seed_grid;
-        ride.stride_rows = h->hg.seed_stride;
+        ride.regions = h->geom[kFp16].seed_grid;
+        ride.stride_rows = h->geom[kFp16].seed_stride;
         ride.next_seed_vals = h->d_mstream_seed[next_buf];
         ride.next_ctl = h->d_mstream_ctl + next_buf;
         ride.next_cuts = h->d_mstream_cuts + next_buf * kHmQueries;
@@ -258,7 +258,7 @@ int launch_mstash(mi355rec* h, hipStream_t s, const HalfMultiArg* next, int next
     const unsigned long long* cuts_ready = st.cuts_ready ? h->d_mstream_cuts + st.seed_buf * kHmQueries : nullptr;
     // the launch stays within one resident wave of workgroups: the riders and mergers take scanner slots
     const int others = ride.merge_wgs + ride.seed_wgs + ride.nb_wgs;
-    int scanners = h->hg.grid - others;
+    int scanners = h->geom[kFp16].grid - others;
     if (scanners < 1) scanners = 1;
     ++h->half_scans;
 #ifdef MI355REC_EXPERIMENTS
@@ -269,7 +269,7 @@ int launch_mstash(mi355rec* h, hipStream_t s, const HalfMultiArg* next, int next
                      dim3(scanners + others), dim3(kHmBlock), s, h->d_feats, h->d_half,
                      reinterpret_cast<const uint32_t*>(h->d_q8), h->n, h->row_base,
                      st.arg, st.nq, 0, st.topn, h->d_mstream_lists[buf], h->d_mstream_seed[st.seed_buf],
-                     h->hg.seed_grid * kHalfSeedWaves, h->d_half_rescored, ride, next ? *next : st.arg, cuts_ready, st.epoch);
+                     h->geom[kFp16].seed_grid * kHalfSeedWaves, h->d_half_rescored, ride, next ? *next : st.arg, cuts_ready, st.epoch);
     } else
 #endif
     {
@@ -278,7 +278,7 @@ int launch_mstash(mi355rec* h, hipStream_t s, const HalfMultiArg* next, int next
                      dim3(scanners + others), dim3(kHmBlock), s, h->d_feats, h->d_half,
                      static_cast<const uint32_t*>(nullptr), h->n, h->row_base,
                      st.arg, st.nq, 0, st.topn, h->d_mstream_lists[buf], h->d_mstream_seed[st.seed_buf],
-                     h->hg.seed_grid * kHalfSeedWaves, h->d_half_rescored, ride, next ? *next : st.arg, cuts_ready, st.epoch);
+                     h->geom[kFp16].seed_grid * kHalfSeedWaves, h->d_half_rescored, ride, next ? *next : st.arg, cuts_ready, st.epoch);
     }
     HIP_TRY(h, hipGetLastError());
     if (next) h->mctl_done[next_buf] += static_cast<unsigned>(ride.seed_wgs);   // (the books move once the launch has been accepted)
@@ -323,17 +323,17 @@ int enqueue_mstream(mi355rec* h, const float* queries, const float* const* qptrs
         seed_buf = 1 - h->mstash.seed_buf;
         rc = launch_mstash(h, s, &arg, nq, topn, seed_buf, epoch);   // its riders take THIS batch's sample (and select its cutoffs)
         if (rc) return rc;
-        cuts_ready = h->hg.seed_grid > 0;   // (launch_mstash gave the launch seed riders)
+        cuts_ready = h->geom[kFp16].seed_grid > 0;   // (launch_mstash gave the launch seed riders)
     } else {   // the head of a stream: a sample launch of its own
-        hipLaunchKernelGGL(seed_half_multi_kernel, dim3(h->hg.seed_grid + nq), dim3(kHmBlock), 0, s, h->d_feats, h->d_half, h->n, h->row_base,
-                           h->hg.seed_stride, arg, nq, h->hg.seed_grid, h->d_mstream_seed[seed_buf], epoch, hm_sample_log2(h, nq, false),
+        hipLaunchKernelGGL(seed_half_multi_kernel, dim3(h->geom[kFp16].seed_grid + nq), dim3(kHmBlock), 0, s, h->d_feats, h->d_half, h->n, h->row_base,
+                           h->geom[kFp16].seed_stride, arg, nq, h->geom[kFp16].seed_grid, h->d_mstream_seed[seed_buf], epoch, hm_sample_log2(h, nq, false),
                            h->d_mstream_ctl + seed_buf, h->mctl_done[seed_buf] + (h->dbg_no_last ? 0x40000000u : 0u),
                            h->d_mstream_cuts + seed_buf * kHmQueries, topn, h->dbg_skip_regions);
         HIP_TRY(h, hipGetLastError());
-        h->mctl_done[seed_buf] += static_cast<unsigned>(h->hg.seed_grid);
+        h->mctl_done[seed_buf] += static_cast<unsigned>(h->geom[kFp16].seed_grid);
         h->dbg_no_last = false;
         h->dbg_skip_regions = 0;
-        cuts_ready = h->hg.seed_grid > 0;
+        cuts_ready = h->geom[kFp16].seed_grid > 0;
     }
     auto& st = h->mstash;
     st.has = true;

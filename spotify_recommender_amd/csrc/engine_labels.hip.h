@@ -64,7 +64,7 @@ int build_labels(mi355rec* h, const int32_t* labels, mi355rec_labels** out) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, label_scan_kernel, LabelScanCfg::kBlock, 0) != hipSuccess || occ < 1) occ = 1;
     (void)hipGetLastError();
     L->grid_cap = h->cus * occ;
-    if (L->grid_cap > h->grid) L->grid_cap = h->grid;   // d_block_lists holds h->grid lists of kMaxTopK keys
+    if (L->grid_cap > h->geom[kFp32].grid) L->grid_cap = h->geom[kFp32].grid;   // d_block_lists holds at least that many lists of kMaxTopK keys
     if (L->grid_cap < 1) L->grid_cap = 1;
     auto failed = [&](hipError_t e, const char* what) {
         free_labels(L);

@@ -64,8 +64,7 @@ int ensure_playlist(mi355rec* h) {
     int occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, playlist_scan_kernel, PlaylistCfg::kBlock, 0) != hipSuccess || occ < 1) occ = 1;
     (void)hipGetLastError();
-    int lists = h->grid > h->hg.grid ? h->grid : h->hg.grid;   // d_block_lists holds this many lists of kMaxTopK keys (create)
-    if (h->qg.grid > lists) lists = h->qg.grid;
+    const int lists = most(h, &ScanGeom::grid);   // d_block_lists holds this many lists of kMaxTopK keys (create)
     P->grid_cap = h->cus * occ;
     if (P->grid_cap > lists) P->grid_cap = lists;
     if (P->grid_cap > kMergeMaxLists) P->grid_cap = kMergeMaxLists;

@@ -6,6 +6,8 @@
 
 #include "engine_state.hip.h"
 
+#include <type_traits>
+
 namespace {
 
 int flush_mstream(mi355rec* h, hipStream_t s);   // (engine_batch.hip.h: a stream of BATCHES on the handle is closed before a single query joins)
@@ -25,13 +27,9 @@ int single_kind(const mi355rec* h, const uint64_t* upper_dev) {
     return use_q8(h) ? kQ8 : kFp16;
 }
 
-// Streamed launches over the 8-bit replica: the last seed rider out turns the sample into the next launch's
-// cutoff (saves a ~4 us select in every workgroup of that launch).  The riders then take sample + select
-// (~10 us) in all, so only where the scanners run longer than that.
-bool q8_hoists(const mi355rec* h) { return h->qg.riders > 0 && h->qg.r_iters >= 5; }
 // The sample holds EXACT scores of its rows (one margin in the cutoff instead of two: a third of the candidates)
 // where the extra fetch per sampled wave is not on the launch's critical path.
-bool q8_exact_sample(const mi355rec* h) { return h->qg.iters >= 3; }
+bool q8_exact_sample(const mi355rec* h) { return h->geom[kQ8].iters >= 3; }
 
 // Does a neighbourhood give the scan a bound (handoff.hip.h)?  Around the row the query excludes when that is a row of THIS
 // shard, else (a query by value, a row of another shard) around the query's anchor — on every shard large enough to have one.
@@ -40,61 +38,183 @@ bool nbhd_applies(const mi355rec* h, int64_t exclude_global) {
     return h->n >= kNbhdRows;
 }
 
-// The sample launch of a query ALONE over a replica (the first query of a stream as well): the sampled regions and,
-// when the excluded row is a row of this shard, one more workgroup for its neighbourhood.  The values are tagged with
-// `epoch`, which the scan that reads them is given as well.
-void enqueue_half_seed(mi355rec* h, int kind, const float* qptr, const QueryArg& qa, int64_t exclude_global, int topn,
-                       unsigned long long* seed_buf, uint32_t epoch, hipStream_t s) {
-    if (kind == kQ8) {
-        const int extra = nbhd_applies(h, exclude_global) ? 1 : 0;
-        if (h->qg.seed_grid + extra <= 0) return;
-        hipLaunchKernelGGL(seed_q8_kernel, dim3(h->qg.seed_grid + extra), dim3(kHalfSeedBlock), 0, s, h->d_feats, h->d_q8, h->n,
-                           h->qg.seed_stride, h->row_base, qa, qptr, exclude_global, seed_buf, epoch, h->qg.seed_grid, topn,
-                           static_cast<const float*>(h->d_anchor), q8_exact_sample(h));
-        return;
-    }
-#ifdef MI355REC_EXPERIMENTS
-    if (h->hg.seed_grid <= 0) return;
-    uint32_t* const seed_out = reinterpret_cast<uint32_t*>(seed_buf);   // the fp16 scan's plain values
-    if (qptr) {
-        hipLaunchKernelGGL((seed_half_kernel<true>), dim3(h->hg.seed_grid), dim3(kHalfSeedBlock), 0, s, h->d_feats, h->d_half,
-                           h->n, h->hg.seed_stride, h->row_base, qa, qptr, exclude_global, seed_out);
-    } else {
-        hipLaunchKernelGGL((seed_half_kernel<false>), dim3(h->hg.seed_grid), dim3(kHalfSeedBlock), 0, s, h->d_feats, h->d_half,
-                           h->n, h->hg.seed_stride, h->row_base, qa, kNoQueryPtr, exclude_global, seed_out);
-    }
-#endif
+// Every kernel that takes a query exists twice: kQueryFromRow reads the 12 floats from `qptr` (a resident row, or any
+// other device-readable address), the other takes them by value in its QueryArg / NextSeed and is handed kNoQueryPtr.
+// fn(std::true_type or std::false_type, the pointer argument) launches the one that serves this query.
+template <typename Fn>
+void by_query_form(const float* qptr, Fn&& fn) {
+    if (qptr) fn(std::true_type(), qptr);
+    else fn(std::false_type(), kNoQueryPtr);
 }
 
-// The same for a query alone over the fp32 rows (kernels.hip.h, seed_f32_kernel): the regions' last workgroup leaves the
-// bound in `ctl`, the neighbourhood workgroup its own in seed_buf[kNbhdSlot].  `*ctl_done` is what ctl->done holds (the
-// counter is never reset).  Returns whether a sample (hence a bound in `ctl`) was enqueued.
-bool enqueue_f32_seed(mi355rec* h, const float* qptr, const float* query12, int64_t exclude_global, int topn,
-                      unsigned long long* seed_buf, SeedCtl* ctl, unsigned* ctl_done, uint32_t epoch, hipStream_t s) {
+// ---- the arguments every scan launch is assembled from --------------------------------------------------------------
+QueryArg make_query_arg(const mi355rec* h, const float* qptr, const float* query12) {
+    QueryArg qa;
+    std::memset(&qa, 0, sizeof qa);
+    qa.margin = h->margin_mix;
+    if (!qptr) std::memcpy(qa.q, query12, sizeof qa.q);
+    return qa;
+}
+
+// A launch with no merge of a query before riding in it, none of its own lists at its tail, nothing for a query after.
+PrevMerge no_prev_merge() { return PrevMerge{nullptr, 0, 0, nullptr}; }
+LoneTail no_lone_tail() { return LoneTail{nullptr, nullptr, nullptr, nullptr, nullptr, 0u, {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}}; }
+NextSeed no_next_seed() {
     NextSeed sd;
     std::memset(&sd, 0, sizeof sd);
+    return sd;
+}
+
+// What a launch takes for the query AFTER the one it scans for (handoff.hip.h) — or, in a sample launch of its own,
+// for the query itself: `wgs` workgroups sample the regions of `kind` rows into `out` and (`nbhd`) one more takes the
+// query's neighbourhood.  ctl != null: the last of the `wgs` to arrive leaves the bound there; its arrival counter
+// counts up from `ctl_done` and is never reset.  The test hooks of mi355rec_debug_handoff apply to ONE sampling
+// launch: this one.
+NextSeed make_next_seed(mi355rec* h, int kind, int wgs, bool nbhd, const float* qptr, const float* query12, int64_t exclude_global,
+                        int topn, uint32_t epoch, unsigned long long* out, SeedCtl* ctl, unsigned ctl_done) {
+    const ScanGeom& g = h->geom[kind];
+    NextSeed sd = no_next_seed();
     sd.anchors = h->d_anchor;
     sd.query_ptr = qptr;
     if (!qptr) std::memcpy(sd.q, query12, sizeof sd.q);
     sd.exclude_global = exclude_global;
-    sd.out = seed_buf;
-    sd.regions = h->fg.seed_grid;
-    sd.n_wgs = h->fg.seed_grid;
-    sd.stride_rows = h->fg.seed_stride;
-    sd.ctl = sd.regions > 0 ? ctl : nullptr;
+    sd.out = out;
+    sd.n_wgs = wgs;
+    sd.nbhd = nbhd ? 1 : 0;   // (it stores its slot even when the excluded row is not of this shard)
+    sd.regions = g.seed_grid;
+    sd.stride_rows = g.seed_stride;
+    sd.ctl = wgs > 0 ? ctl : nullptr;
     sd.topk = topn;
+    sd.exact = kind == kQ8 && q8_exact_sample(h);
     sd.epoch = epoch;
-    sd.done_base = *ctl_done + (h->dbg_no_last ? 0x40000000u : 0u);
+    if (sd.ctl) sd.done_base = ctl_done + (h->dbg_no_last ? 0x40000000u : 0u);
     sd.debug_skip = h->dbg_skip_regions;
-    sd.nbhd = nbhd_applies(h, exclude_global) ? 1 : 0;
-    if (sd.regions + sd.nbhd <= 0) return false;
-    hipLaunchKernelGGL(seed_f32_kernel, dim3(sd.regions + sd.nbhd), dim3(kHalfSeedBlock), 0, s, h->d_feats, h->n, h->row_base, sd);
-    if (sd.regions > 0) {
-        *ctl_done += static_cast<unsigned>(sd.regions);
-        h->dbg_no_last = false;   // (test hooks of mi355rec_debug_handoff: they apply to ONE sampling launch)
-        h->dbg_skip_regions = 0;
+    h->dbg_no_last = false;
+    h->dbg_skip_regions = 0;
+    return sd;
+}
+
+// The sample launch of a query ALONE over a replica (the first query of a stream as well): the sampled regions and,
+// when the excluded row is a row of this shard, one more workgroup for its neighbourhood.  The values are tagged with
+// `epoch`, which the scan that reads them is given as well.
+void enqueue_half_seed(mi355rec* h, int kind, const float* qptr, const float* query12, int64_t exclude_global, int topn,
+                       unsigned long long* seed_buf, uint32_t epoch, hipStream_t s) {
+    const ScanGeom& g = h->geom[kind];
+    const QueryArg qa = make_query_arg(h, qptr, query12);
+    if (kind == kQ8) {
+        const int extra = nbhd_applies(h, exclude_global) ? 1 : 0;
+        if (g.seed_grid + extra <= 0) return;
+        hipLaunchKernelGGL(seed_q8_kernel, dim3(g.seed_grid + extra), dim3(kHalfSeedBlock), 0, s, h->d_feats, h->d_q8, h->n,
+                           g.seed_stride, h->row_base, qa, qptr, exclude_global, seed_buf, epoch, g.seed_grid, topn,
+                           static_cast<const float*>(h->d_anchor), q8_exact_sample(h));
+        return;
     }
-    return sd.regions > 0;
+#ifdef MI355REC_EXPERIMENTS
+    if (g.seed_grid <= 0) return;
+    by_query_form(qptr, [&](auto from_row, const float* qp) {
+        hipLaunchKernelGGL((seed_half_kernel<decltype(from_row)::value>), dim3(g.seed_grid), dim3(kHalfSeedBlock), 0, s, h->d_feats,
+                           h->d_half, h->n, g.seed_stride, h->row_base, qa, qp, exclude_global,
+                           reinterpret_cast<uint32_t*>(seed_buf));   // (the fp16 scan's plain values)
+    });
+#endif
+}
+
+// The same for a query alone over the fp32 rows (kernels.hip.h, seed_f32_kernel): one workgroup per region, the last
+// to arrive leaves the bound in `ctl`, the neighbourhood workgroup its own in seed_buf[kNbhdSlot].  `*ctl_done` is what
+// ctl->done holds (the counter is never reset).  Returns whether a sample (hence a bound in `ctl`) was enqueued.
+bool enqueue_f32_seed(mi355rec* h, const float* qptr, const float* query12, int64_t exclude_global, int topn,
+                      unsigned long long* seed_buf, SeedCtl* ctl, unsigned* ctl_done, uint32_t epoch, hipStream_t s) {
+    const int regions = h->geom[kFp32].seed_grid;
+    const int nbhd = nbhd_applies(h, exclude_global) ? 1 : 0;
+    if (regions + nbhd <= 0) return false;
+    const NextSeed sd = make_next_seed(h, kFp32, regions, nbhd != 0, qptr, query12, exclude_global, topn, epoch, seed_buf, ctl, *ctl_done);
+    hipLaunchKernelGGL(seed_f32_kernel, dim3(regions + nbhd), dim3(kHalfSeedBlock), 0, s, h->d_feats, h->n, h->row_base, sd);
+    *ctl_done += static_cast<unsigned>(regions);
+    return regions > 0;
+}
+
+// ---- one scan launch ------------------------------------------------------------------------------------------------
+// What the launch of a query alone, its lone-fused form and the launch of a streamed query differ in; the rest is the
+// kind's own (launch_scan).
+struct ScanLaunch {
+    int kind = kFp32;                           // which rows it streams
+    bool streamed = false;                      // one workgroup behind the scanners merges `prev`, and `next` may ask for more
+    int grid = 0;                               // workgroups in all ...
+    int iters = 0;                              // ... and the tiles of a scanning one
+    uint64_t* lists = nullptr;                  // one list per scanning workgroup
+    unsigned long long* sample = nullptr;       // the query's sample values (null: fp32 rows without a sample) ...
+    const unsigned long long* bound = nullptr;  // ... the launch-wide bound, where somebody has made one of them already ...
+    uint32_t epoch = 0u;                        // ... and the tag of both
+    const uint64_t* upper = nullptr;            // fp32 rows: a later round of topn > 1024 keeps keys below this one
+    PrevMerge prev = no_prev_merge();
+    NextSeed next = no_next_seed();
+    LoneTail tail = no_lone_tail();             // 8-bit replica, counters != null: the launch merges its own lists (merge.hip.h, lone_tail)
+};
+
+// Launches it and, once the launch is known to have been accepted, moves the books: a refused launch leaves host and
+// device counters in step.
+int launch_scan(mi355rec* h, const ScanLaunch& L, const float* qptr, const float* query12, int64_t exclude_global, int topn,
+                hipStream_t s) {
+    const QueryArg qa = make_query_arg(h, qptr, query12);
+    const dim3 grid(static_cast<unsigned>(L.grid));
+    const bool fused = L.tail.counters != nullptr;
+    if (L.kind == kQ8) {
+        const int n_seed = h->geom[kQ8].seed_grid * kHalfSeedWaves;
+        const int q8_seeds = q8_exact_sample(h) ? -n_seed : n_seed;   // (negative: exact values)
+        by_query_form(qptr, [&](auto from_row, const float* qp) {
+            constexpr bool kRow = decltype(from_row)::value;
+            auto launch = [&](auto kernel) {
+                LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, kernel, grid, dim3(Q8Config::kBlock), s,
+                             h->d_feats, h->d_q8, h->n, L.iters, h->row_base, qa, qp, exclude_global, topn, L.lists, L.sample,
+                             q8_seeds, h->d_half_rescored, L.prev, L.next, L.bound, L.tail, L.epoch);
+            };
+            if (L.streamed) launch(scan_q8_kernel<Q8Config, kRow, true>);
+            else if (fused) launch(scan_q8_kernel<Q8Config, kRow, false, true>);
+            else launch(scan_q8_kernel<Q8Config, kRow, false>);
+        });
+#ifdef MI355REC_EXPERIMENTS
+    } else if (L.kind == kFp16) {
+        const int n_seed = h->geom[kFp16].seed_grid * kHalfSeedWaves;
+        by_query_form(qptr, [&](auto from_row, const float* qp) {
+            constexpr bool kRow = decltype(from_row)::value;
+            auto launch = [&](auto kernel) {
+                LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, kernel, grid, dim3(HalfConfig::kBlock), s,
+                             h->d_feats, h->d_half, h->n, L.iters, h->row_base, qa, qp, exclude_global, topn, L.lists,
+                             reinterpret_cast<uint32_t*>(L.sample), n_seed, h->d_half_rescored, L.prev, L.next);   // (plain sample values)
+            };
+            if (L.streamed) launch(scan_half_kernel<HalfConfig, kRow, true>);
+            else launch(scan_half_kernel<HalfConfig, kRow, false>);
+        });
+#endif
+    } else {
+        by_query_form(qptr, [&](auto from_row, const float* qp) {
+            constexpr bool kRow = decltype(from_row)::value;
+            auto launch = [&](auto kernel) {   // (rows_per_block = 0: tiles dealt round-robin)
+                LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, kernel, grid, dim3(kScanBlock), s,
+                             h->d_feats, h->n, static_cast<int64_t>(0), L.iters, h->row_base, qa, qp, exclude_global, topn, L.lists,
+                             static_cast<float*>(nullptr), L.upper, L.prev, L.bound, L.sample, L.epoch, L.next);
+            };
+            if (L.streamed) launch(scan_kernel<ScanConfig, kRow, false, 0, true>);
+            else launch(scan_kernel<ScanConfig, kRow, false>);
+        });
+    }
+    HIP_TRY(h, hipGetLastError());
+    if (L.kind == kFp32) {
+        ++h->routes.fp32;
+        return MI355REC_OK;
+    }
+    ++h->half_scans;
+    if (L.kind == kFp16) {
+        ++h->routes.fp16;
+        return MI355REC_OK;
+    }
+    ++h->q8_scans;
+    ++(fused ? h->routes.q8_lone : h->routes.q8);
+    if (fused) {   // the arrival counters of the launch's tail count up and are never reset
+        for (unsigned g = 0; g < 8u; ++g) h->lone_base[g] += lone_tail_members(grid.x, g);
+        h->lone_base[8] += lone_tail_groups(grid.x);
+    }
+    return MI355REC_OK;
 }
 
 // Enqueue the scan for one query.  qptr != null: the kernel reads the query's 12 floats from there
@@ -114,119 +234,32 @@ constexpr int64_t kF32LoneSeedMinRows = 4000000;
 int enqueue_scan(mi355rec* h, const float* qptr, const float* query12,
                  int64_t exclude_global, int topn, const uint64_t* upper_dev, hipStream_t s, int* n_lists,
                  const LoneTail* lone = nullptr, bool* fused = nullptr) {
-    QueryArg qa;
-    std::memset(&qa, 0, sizeof qa);
-    qa.margin = h->margin_mix;
-    if (!qptr) std::memcpy(qa.q, query12, sizeof qa.q);
-    const PrevMerge none{nullptr, 0, 0, nullptr};
-    const LoneTail no_tail{nullptr, nullptr, nullptr, nullptr, nullptr, 0u, {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}};
-    NextSeed no_next;
-    std::memset(&no_next, 0, sizeof no_next);
     if (fused) *fused = false;
-    const int kind = single_kind(h, upper_dev);
-    if (kind == kQ8) {
-        ++h->half_scans;
-        *n_lists = h->qg.grid;
-        ++h->q8_scans;
-        const uint32_t epoch = next_epoch(h);
-        enqueue_half_seed(h, kQ8, qptr, qa, exclude_global, topn, h->d_half_seed, epoch, s);
-        const int q8_seeds = (q8_exact_sample(h) ? -1 : 1) * h->qg.seed_grid * kHalfSeedWaves;   // (negative: exact values)
-        const unsigned long long* const no_cutoff = nullptr;
-        if (lone && h->n >= kLoneFusedMinRows) {
-            ++h->routes.q8_lone;
-            // the arrival counters of the launch's tail count up and are never reset: this launch starts from ...
-            LoneTail tail = *lone;
-            const unsigned grid = static_cast<unsigned>(h->qg.grid);
-            for (unsigned g = 0; g < 8u; ++g) tail.base[g] = h->lone_base[g];
-            tail.base[8] = h->lone_base[8];
-            if (qptr) {
-                LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_q8_kernel<Q8Config, true, false, true>),
-                             dim3(h->qg.grid), dim3(Q8Config::kBlock), s,
-                             h->d_feats, h->d_q8, h->n, h->qg.iters, h->row_base, qa, qptr, exclude_global, topn,
-                             h->d_block_lists, h->d_half_seed, q8_seeds, h->d_half_rescored, none, no_next,
-                             no_cutoff, tail, epoch);
-            } else {
-                LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_q8_kernel<Q8Config, false, false, true>),
-                             dim3(h->qg.grid), dim3(Q8Config::kBlock), s,
-                             h->d_feats, h->d_q8, h->n, h->qg.iters, h->row_base, qa, kNoQueryPtr, exclude_global, topn,
-                             h->d_block_lists, h->d_half_seed, q8_seeds, h->d_half_rescored, none, no_next,
-                             no_cutoff, tail, epoch);
-            }
-            HIP_TRY(h, hipGetLastError());
-            // (the books move only once the launch is known to have been accepted: a refused launch leaves host and
-            // device counters in step)
-            for (unsigned g = 0; g < 8u; ++g) h->lone_base[g] += lone_tail_members(grid, g);
-            h->lone_base[8] += lone_tail_groups(grid);
-            *fused = true;
-            return MI355REC_OK;
+    ScanLaunch L;
+    L.kind = single_kind(h, upper_dev);
+    L.grid = *n_lists = h->geom[L.kind].grid;
+    L.iters = h->geom[L.kind].iters;
+    L.lists = h->d_block_lists;
+    L.upper = upper_dev;
+    if (L.kind != kFp32) {
+        if (L.kind == kQ8) L.epoch = next_epoch(h);
+        L.sample = h->d_half_seed;
+        enqueue_half_seed(h, L.kind, qptr, query12, exclude_global, topn, h->d_half_seed, L.epoch, s);
+        if (L.kind == kQ8 && lone && h->n >= kLoneFusedMinRows) {
+            L.tail = *lone;   // ... whose arrival counters start this launch from
+            for (unsigned g = 0; g < 9u; ++g) L.tail.base[g] = h->lone_base[g];
         }
-        ++h->routes.q8;
-        if (qptr) {
-            LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_q8_kernel<Q8Config, true, false>),
-                         dim3(h->qg.grid), dim3(Q8Config::kBlock), s,
-                         h->d_feats, h->d_q8, h->n, h->qg.iters, h->row_base, qa, qptr, exclude_global, topn,
-                         h->d_block_lists, h->d_half_seed, q8_seeds, h->d_half_rescored, none, no_next,
-                         no_cutoff, no_tail, epoch);
-        } else {
-            LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_q8_kernel<Q8Config, false, false>),
-                         dim3(h->qg.grid), dim3(Q8Config::kBlock), s,
-                         h->d_feats, h->d_q8, h->n, h->qg.iters, h->row_base, qa, kNoQueryPtr, exclude_global, topn,
-                         h->d_block_lists, h->d_half_seed, q8_seeds, h->d_half_rescored, none, no_next,
-                         no_cutoff, no_tail, epoch);
-        }
-        HIP_TRY(h, hipGetLastError());
-        return MI355REC_OK;
+    } else if (!upper_dev && h->n >= kF32LoneSeedMinRows) {
+        // The launch-wide bound (kernels.hip.h): on shards where ~5 us are worth it, and never for the later rounds of
+        // topn > 1024 (they look for keys BELOW the round before: a lower bound on the best keys says nothing there).
+        L.epoch = next_epoch(h);
+        if (enqueue_f32_seed(h, qptr, query12, exclude_global, topn, h->d_half_seed, h->d_lone_ctl, &h->lone_ctl_done, L.epoch, s))
+            L.bound = &h->d_lone_ctl->cutoff;
+        L.sample = h->d_half_seed;
     }
-#ifdef MI355REC_EXPERIMENTS
-    if (kind == kFp16) {
-        ++h->half_scans;
-        *n_lists = h->hg.grid;
-        ++h->routes.fp16;
-        uint32_t* const half_seed = reinterpret_cast<uint32_t*>(h->d_half_seed);   // (the fp16 scan's plain sample values)
-        enqueue_half_seed(h, kFp16, qptr, qa, exclude_global, topn, h->d_half_seed, 0u, s);
-        if (qptr) {
-            LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_half_kernel<HalfConfig, true, false>),
-                         dim3(h->hg.grid), dim3(HalfConfig::kBlock), s,
-                         h->d_feats, h->d_half, h->n, h->hg.iters, h->row_base, qa, qptr, exclude_global, topn,
-                         h->d_block_lists, half_seed, h->hg.seed_grid * kHalfSeedWaves, h->d_half_rescored, none, no_next);
-        } else {
-            LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_half_kernel<HalfConfig, false, false>),
-                         dim3(h->hg.grid), dim3(HalfConfig::kBlock), s,
-                         h->d_feats, h->d_half, h->n, h->hg.iters, h->row_base, qa, kNoQueryPtr, exclude_global,
-                         topn, h->d_block_lists, half_seed, h->hg.seed_grid * kHalfSeedWaves, h->d_half_rescored, none, no_next);
-        }
-        HIP_TRY(h, hipGetLastError());
-        return MI355REC_OK;
-    }
-#endif
-    *n_lists = h->grid;
-    ++h->routes.fp32;
-    // The launch-wide bound (kernels.hip.h): on shards where ~5 us are worth it, and never for the later rounds of
-    // topn > 1024 (they look for keys BELOW the round before: a lower bound on the best keys says nothing there).
-    const unsigned long long* bound = nullptr;
-    const unsigned long long* sample = nullptr;
-    uint32_t epoch = 0u;
-    if (!upper_dev && h->n >= kF32LoneSeedMinRows) {
-        epoch = next_epoch(h);
-        if (enqueue_f32_seed(h, qptr, query12, exclude_global, topn, h->d_half_seed, h->d_lone_ctl, &h->lone_ctl_done, epoch, s))
-            bound = &h->d_lone_ctl->cutoff;
-        sample = h->d_half_seed;
-    }
-    if (qptr) {
-        LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_kernel<ScanConfig, true, false>),
-                     dim3(h->grid), dim3(kScanBlock), s,
-                     h->d_feats, h->n, h->rows_per_block, h->iters, h->row_base, qa,
-                     qptr, exclude_global, topn, h->d_block_lists,
-                     static_cast<float*>(nullptr), upper_dev, none, bound, sample, epoch, no_next);
-    } else {
-        LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_kernel<ScanConfig, false, false>),
-                     dim3(h->grid), dim3(kScanBlock), s,
-                     h->d_feats, h->n, h->rows_per_block, h->iters, h->row_base, qa,
-                     kNoQueryPtr, exclude_global, topn, h->d_block_lists,
-                     static_cast<float*>(nullptr), upper_dev, none, bound, sample, epoch, no_next);
-    }
-    HIP_TRY(h, hipGetLastError());
-    return MI355REC_OK;
+    const int rc = launch_scan(h, L, qptr, query12, exclude_global, topn, s);
+    if (rc == MI355REC_OK && fused) *fused = L.tail.counters != nullptr;
+    return rc;
 }
 
 int enqueue_merge(mi355rec* h, const uint64_t* lists, int n_lists, int list_len, int topn,
@@ -325,11 +358,16 @@ int ensure_streamed(mi355rec* h) {
 }
 
 int ensure_streamed_alloc(mi355rec* h) {
-    int most = h->sgrid > h->hg.sgrid ? h->sgrid : h->hg.sgrid;
-    if (h->qg.sgrid > most) most = h->qg.sgrid;
-    for (int i = 0; i < 2; ++i)
-        HIP_TRY(h, hipMalloc(&h->d_stream_lists[i], sizeof(uint64_t) * static_cast<size_t>(most) * kMaxTopK));
+    const size_t words = static_cast<size_t>(most(h, &ScanGeom::sgrid)) * kMaxTopK;
+    for (int i = 0; i < 2; ++i) HIP_TRY(h, hipMalloc(&h->d_stream_lists[i], sizeof(uint64_t) * words));
     return MI355REC_OK;
+}
+
+// The merge of the streamed query whose lists wait for it, in a launch of its own.
+int merge_pending(mi355rec* h, hipStream_t s) {
+    h->pending = false;
+    return enqueue_merge(h, h->d_stream_lists[h->pending_buf], h->pending_lists, h->pending_topn, h->pending_topn,
+                         h->pending_out, nullptr, nullptr, s);
 }
 
 int launch_stashed(mi355rec* h, hipStream_t s, bool with_next, const float* next_ptr, const float* next_q,
@@ -340,145 +378,46 @@ int flush_streamed(mi355rec* h, hipStream_t s) {
         const int rc = launch_stashed(h, s, false, nullptr, nullptr, -1, 0, 0, 0u);
         if (rc) return rc;
     }
-    if (!h->pending) return MI355REC_OK;
-    h->pending = false;
-    return enqueue_merge(h, h->d_stream_lists[h->pending_buf], h->pending_lists, h->pending_topn, h->pending_topn,
-                         h->pending_out, nullptr, nullptr, s);
+    return h->pending ? merge_pending(h, s) : MI355REC_OK;
 }
-
-// How many seed riders a streamed launch over `kind` rows carries for the NEXT query, and whether their last one
-// leaves that query's bound (cutoff) in d_stream_ctl.
-int stream_riders(const mi355rec* h, int kind) { return kind == kFp32 ? h->fg.riders : (kind == kQ8 ? h->qg.riders : h->hg.riders); }
-bool stream_hoists(const mi355rec* h, int kind) {
-    return kind == kFp32 ? h->fg.riders > 0 : (kind == kQ8 ? q8_hoists(h) : false);
-}
-// ... and whether the launch has a workgroup for the next query's neighbourhood at all.
-bool stream_nbhd(const mi355rec* h, int kind) { return kind == kFp32 ? h->fg.nbhd != 0 : (kind == kQ8 ? h->qg.riders > 0 : false); }
 
 // Launches the stashed streamed query: scanners + the riding merger of the query before it + (with_next) the seed
-// riders and the neighbourhood workgroup of the query after it.
+// riders and the neighbourhood workgroup of the query after it, where the launch over its kind of rows has them
+// (ScanGeom: riders, nbhd; hoists: their last one leaves that query's bound in d_stream_ctl).
 int launch_stashed(mi355rec* h, hipStream_t s, bool with_next, const float* next_ptr, const float* next_q,
                    int64_t next_exclude, int next_topn, int next_buf, uint32_t next_epoch_tag) {
     auto& st = h->stashed;
+    const ScanGeom& g = h->geom[st.kind];
     // The fp32 scan's riding merger keeps 2048 survivors; with ~770 lists and topN near 1000 about
     // 2.2 topN keys survive its first cut, and an overflow drops into the exact radix select over all
     // keys in global memory (correct, ~1 ms).  Such a query's merge gets its own launch instead.
     if (st.kind == kFp32 && h->pending && h->pending_topn > kRideTopnMax) {
-        h->pending = false;
-        const int rc = enqueue_merge(h, h->d_stream_lists[h->pending_buf], h->pending_lists, h->pending_topn, h->pending_topn,
-                                     h->pending_out, nullptr, nullptr, s);
+        const int rc = merge_pending(h, s);
         if (rc) return rc;
     }
+    ScanLaunch L;
+    L.kind = st.kind;
+    L.streamed = true;
     const int buf = h->pending ? 1 - h->pending_buf : 0;
-    PrevMerge prev{nullptr, 0, 0, nullptr};
-    if (h->pending) prev = PrevMerge{h->d_stream_lists[h->pending_buf], h->pending_lists, h->pending_topn, h->pending_out};
-    NextSeed next;
-    std::memset(&next, 0, sizeof next);
-    next.anchors = h->d_anchor;
-    next.query_ptr = nullptr;
-    next.exclude_global = -1;
-    int scanners, iters;
-    if (st.kind == kFp32) {
-        scanners = h->sgrid;
-        iters = h->siters;
-    } else {
-        const ReplicaGeom& g = st.kind == kQ8 ? h->qg : h->hg;
-        scanners = g.sgrid;
-        iters = g.siters;
+    if (h->pending) L.prev = PrevMerge{h->d_stream_lists[h->pending_buf], h->pending_lists, h->pending_topn, h->pending_out};
+    int scanners = g.sgrid;
+    L.iters = g.siters;
+    if (with_next && (g.riders > 0 || g.nbhd)) {
+        scanners = g.r_scan;
+        L.iters = g.r_iters;
+        L.next = make_next_seed(h, st.kind, g.riders, g.nbhd, next_ptr, next_q, next_exclude, next_topn, next_epoch_tag,
+                                h->d_stream_seed[next_buf], g.hoists ? h->d_stream_ctl + next_buf : nullptr, h->ctl_done[next_buf]);
     }
-    unsigned riders_arriving = 0u;
-    if (with_next && (stream_riders(h, st.kind) > 0 || stream_nbhd(h, st.kind))) {
-        next.query_ptr = next_ptr;
-        if (!next_ptr) std::memcpy(next.q, next_q, sizeof next.q);
-        next.exclude_global = next_exclude;
-        next.out = h->d_stream_seed[next_buf];
-        next.n_wgs = stream_riders(h, st.kind);
-        next.nbhd = stream_nbhd(h, st.kind) ? 1 : 0;   // (it stores its slot even when the excluded row is not of this shard)
-        if (st.kind == kFp32) {
-            next.regions = h->fg.seed_grid;
-            next.stride_rows = h->fg.seed_stride;
-            scanners = h->fg.r_scan;
-            iters = h->fg.r_iters;
-        } else {
-            const ReplicaGeom& g = st.kind == kQ8 ? h->qg : h->hg;
-            next.regions = g.seed_grid;
-            next.stride_rows = g.seed_stride;
-            scanners = g.r_scan;
-            iters = g.r_iters;
-        }
-        next.ctl = (next.n_wgs > 0 && stream_hoists(h, st.kind)) ? h->d_stream_ctl + next_buf : nullptr;
-        next.topk = next_topn;
-        next.exact = st.kind == kQ8 && q8_exact_sample(h);
-        next.epoch = next_epoch_tag;
-        if (next.ctl) {   // the riders' arrival counter counts up and is never reset: this launch's riders start from ...
-            next.done_base = h->ctl_done[next_buf] + (h->dbg_no_last ? 0x40000000u : 0u);
-            riders_arriving = static_cast<unsigned>(next.n_wgs);
-        }
-        next.debug_skip = h->dbg_skip_regions;
-        h->dbg_no_last = false;
-        h->dbg_skip_regions = 0;
-    }
-    QueryArg qa;
-    std::memset(&qa, 0, sizeof qa);
-    qa.margin = h->margin_mix;
-    if (!st.qptr) std::memcpy(qa.q, st.q, sizeof qa.q);
-    const dim3 grid(static_cast<unsigned>(scanners + 1 + next.n_wgs + next.nbhd));
-    unsigned long long* const my_seed = h->d_stream_seed[st.seed_buf];
-    const unsigned long long* ready = st.cutoff_ready ? &h->d_stream_ctl[st.seed_buf].cutoff : nullptr;
-    if (st.kind == kQ8) {
-        ++h->half_scans;
-        ++h->q8_scans;
-        ++h->routes.q8;
-        const int n_seed = h->qg.seed_grid * kHalfSeedWaves;
-        const int q8_seeds = q8_exact_sample(h) ? -n_seed : n_seed;   // (negative: exact values)
-        const LoneTail no_tail{nullptr, nullptr, nullptr, nullptr, nullptr, 0u, {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}};
-        if (st.qptr) {
-            LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_q8_kernel<Q8Config, true, true>),
-                         grid, dim3(Q8Config::kBlock), s,
-                         h->d_feats, h->d_q8, h->n, iters, h->row_base, qa, st.qptr, st.exclude, st.topn,
-                         h->d_stream_lists[buf], my_seed, q8_seeds, h->d_half_rescored, prev, next, ready, no_tail, st.epoch);
-        } else {
-            LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_q8_kernel<Q8Config, false, true>),
-                         grid, dim3(Q8Config::kBlock), s,
-                         h->d_feats, h->d_q8, h->n, iters, h->row_base, qa, kNoQueryPtr, st.exclude, st.topn,
-                         h->d_stream_lists[buf], my_seed, q8_seeds, h->d_half_rescored, prev, next, ready, no_tail, st.epoch);
-        }
-#ifdef MI355REC_EXPERIMENTS
-    } else if (st.kind == kFp16) {
-        ++h->half_scans;
-        ++h->routes.fp16;
-        const int n_seed = h->hg.seed_grid * kHalfSeedWaves;
-        if (st.qptr) {
-            LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_half_kernel<HalfConfig, true, true>),
-                         grid, dim3(HalfConfig::kBlock), s,
-                         h->d_feats, h->d_half, h->n, iters, h->row_base, qa, st.qptr, st.exclude, st.topn,
-                         h->d_stream_lists[buf], reinterpret_cast<uint32_t*>(my_seed), n_seed, h->d_half_rescored, prev, next);
-        } else {
-            LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_half_kernel<HalfConfig, false, true>),
-                         grid, dim3(HalfConfig::kBlock), s,
-                         h->d_feats, h->d_half, h->n, iters, h->row_base, qa, kNoQueryPtr, st.exclude, st.topn,
-                         h->d_stream_lists[buf], reinterpret_cast<uint32_t*>(my_seed), n_seed, h->d_half_rescored, prev, next);
-        }
-#endif
-    } else {
-        ++h->routes.fp32;
-        if (st.qptr) {
-            LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_kernel<ScanConfig, true, false, 0, true>),
-                         grid, dim3(kScanBlock), s,
-                         h->d_feats, h->n, static_cast<int64_t>(0), iters, h->row_base, qa, st.qptr,
-                         st.exclude, st.topn, h->d_stream_lists[buf], static_cast<float*>(nullptr),
-                         static_cast<const uint64_t*>(nullptr), prev, ready, my_seed, st.epoch, next);
-        } else {
-            LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, (scan_kernel<ScanConfig, false, false, 0, true>),
-                         grid, dim3(kScanBlock), s,
-                         h->d_feats, h->n, static_cast<int64_t>(0), iters, h->row_base, qa, kNoQueryPtr,
-                         st.exclude, st.topn, h->d_stream_lists[buf], static_cast<float*>(nullptr),
-                         static_cast<const uint64_t*>(nullptr), prev, ready, my_seed, st.epoch, next);
-        }
-    }
-    HIP_TRY(h, hipGetLastError());
-    // (the books move only once the launch is known to have been accepted)
-    if (riders_arriving) h->ctl_done[next_buf] += riders_arriving;
+    L.grid = scanners + 1 + L.next.n_wgs + L.next.nbhd;
+    L.lists = h->d_stream_lists[buf];
+    L.sample = h->d_stream_seed[st.seed_buf];
+    L.bound = st.cutoff_ready ? &h->d_stream_ctl[st.seed_buf].cutoff : nullptr;
+    L.epoch = st.epoch;
+    const int rc = launch_scan(h, L, st.qptr, st.q, st.exclude, st.topn, s);
+    if (rc) return rc;
+    // (the books move only once the launch is known to have been accepted; the riders' arrival counter counts up
+    // and is never reset)
+    if (L.next.ctl) h->ctl_done[next_buf] += static_cast<unsigned>(L.next.n_wgs);
     h->pending = true;
     h->pending_buf = buf;
     h->pending_topn = st.topn;
@@ -509,23 +448,19 @@ int enqueue_streamed(mi355rec* h, const float* qptr, const float* query12, int64
         // the riders of a launch sample the rows that launch scans: a change of rows (mi355rec_set_replica) between two
         // calls costs the next query a sample launch of its own
         const bool same = h->stashed.kind == kind;
-        sampled = same && stream_riders(h, kind) > 0;
-        nbhd_taken = same && stream_nbhd(h, kind);
+        sampled = same && h->geom[kind].riders > 0;
+        nbhd_taken = same && h->geom[kind].nbhd;
         rc = launch_stashed(h, s, same, qptr, query12, exclude_global, topn, seed_buf, epoch);
         if (rc) return rc;
     }
-    bool bound_ready = sampled && stream_hoists(h, kind);
+    bool bound_ready = sampled && h->geom[kind].hoists;
     if (!sampled) {   // first query of a stream, or a shard too small to spare riders
         if (kind == kFp32) {
             if (h->n >= kF32LoneSeedMinRows)
                 bound_ready = enqueue_f32_seed(h, qptr, query12, exclude_global, topn, h->d_stream_seed[seed_buf], h->d_stream_ctl + seed_buf,
                                                &h->ctl_done[seed_buf], epoch, s);
         } else if (!nbhd_taken) {
-            QueryArg qa;
-            std::memset(&qa, 0, sizeof qa);
-            qa.margin = h->margin_mix;
-            if (!qptr) std::memcpy(qa.q, query12, sizeof qa.q);
-            enqueue_half_seed(h, kind, qptr, qa, exclude_global, topn, h->d_stream_seed[seed_buf], epoch, s);
+            enqueue_half_seed(h, kind, qptr, query12, exclude_global, topn, h->d_stream_seed[seed_buf], epoch, s);
         }
         HIP_TRY(h, hipGetLastError());
     }

@@ -66,25 +66,19 @@ constexpr int64_t kF32SampleMinRows = 2000000;  // below this a fp32 scan is a d
 constexpr int kFp32 = 0, kFp16 = 1, kQ8 = 2;    // which rows a single-query scan streams (mi355rec::Stashed::kind)
 const float* const kNoQueryPtr = nullptr;   // kernel argument of the variants that take the query by value
 
-// Launch geometry of a single-query scan over a replica of the catalogue (fp16: replica.hip.h,
-// 8-bit: replica_q8.hip.h).
-// The sample of the fp32 rows (handoff.hip.h, f32_sample_regions) that gives the fp32 scan its launch-wide bound, and
-// the geometry of a streamed fp32 launch that carries the NEXT query's seed riders and neighbourhood workgroup.
-struct F32Geom {
-    int seed_grid = 0;                  // sampled regions of kHalfSeedBlock rows (0: the shard is too small to be worth a sample) ...
+// Launch geometry of a single-query scan over one kind of rows (fp32: plan_grid; fp16 replica, replica.hip.h, and
+// 8-bit replica, replica_q8.hip.h: plan_replica), mi355rec::geom[kind].  A streamed launch has one workgroup that
+// merges the query before and, where it can spare them, carries the NEXT query's sample (seed riders over the
+// regions of handoff.hip.h) and neighbourhood workgroup.
+struct ScanGeom {
+    int grid = 0, iters = 0;            // plain launch
+    int sgrid = 0, siters = 0;          // streamed launch that carries nothing for the next query (one more workgroup is the merger)
+    int seed_grid = 0;                  // sampled regions (0: the shard is too small to be worth a sample) ...
     int64_t seed_stride = 0;            // ... and the rows between their starts
     int riders = 0;                     // seed riders of a streamed launch (0: none)
-    int nbhd = 0;                       // 1: a streamed launch also carries the next query's neighbourhood workgroup
-    int r_scan = 0, r_iters = 0;        // its scanners and their tiles
-};
-
-struct ReplicaGeom {
-    int grid = 0, iters = 0;            // plain launch
-    int sgrid = 0, siters = 0;          // streamed launch without seed riders (one more workgroup is the merger)
-    int seed_grid = 0;                  // sampled regions ...
-    int64_t seed_stride = 0;            // ... and the rows between their starts
-    int riders = 0;                     // seed riders of a streamed launch
-    int r_scan = 0, r_iters = 0;        // its scanners and their tiles
+    bool nbhd = false;                  // a streamed launch also carries the next query's neighbourhood workgroup
+    bool hoists = false;                // the last rider out leaves the next query's bound (cutoff) in d_stream_ctl
+    int r_scan = 0, r_iters = 0;        // scanners of a streamed launch with riders or a neighbourhood workgroup, and their tiles
 };
 
 }  // namespace
@@ -124,9 +118,7 @@ struct mi355rec {
     int64_t playlist_queries = 0;
 
     int cus = 0;
-    int grid = 0;
-    int64_t rows_per_block = 0;
-    int iters = 0;
+    ScanGeom geom[3];                   // by the kind of rows a single-query scan streams: kFp32, kFp16, kQ8
     // geometry of the multi-query pass (scan_multi_kernel)
     int mgrid = 0;
     int64_t mrows_per_block = 0;
@@ -136,13 +128,11 @@ struct mi355rec {
     // streamed single queries (mi355rec_enqueue_*_streamed): the merge of query k rides in
     // the scan launch of query k + 1; two more list buffers alternate
     uint64_t* d_stream_lists[2] = {nullptr, nullptr};
-    int sgrid = 0, siters = 0;          // scanning workgroups of a streamed launch (one slot is the merger's)
-    F32Geom fg;                         // the fp32 scan's sample and riders
     bool streamed_ready = false;        // both list buffers exist
     bool pending = false;               // a streamed query's lists wait for their merge
     int pending_buf = 0, pending_topn = 0;
     uint64_t* pending_out = nullptr;
-    // fp16 replica of the catalogue (replica.hip.h) and the geometry of the scan over it
+    // fp16 replica of the catalogue (replica.hip.h)
     uint4* d_half = nullptr;            // ((n + 1) / 2) pairs of rows x 48 B
     // sample maxima: 8 bytes per entry — epoch-tagged values (8-bit scan, multi-query pass: replica.hip.h, "hand-offs
     // that fail safe"); the fp16 single-query scan uses the same buffers as plain uint32_t[]
@@ -172,10 +162,8 @@ struct mi355rec {
     struct Routes {
         int64_t fp32 = 0, fp16 = 0, q8 = 0, q8_lone = 0, multi_fp32 = 0, multi_fp16 = 0, multi_q8 = 0, mfma_two_pass = 0;
     } routes;
-    ReplicaGeom hg;                     // geometry of the scan over the fp16 replica ...
     uint4* d_q8 = nullptr;              // 8-bit replica (replica_q8.hip.h): ((n + 3) / 4) quads of rows x 48 B
     float* d_anchor = nullptr;          // the anchor table (handoff.hip.h, nbhd_anchor): kAnchorRows rows x 48 B, a copy made at create
-    ReplicaGeom qg;                     // ... and over the 8-bit one
     int replica_mode = 0;               // MI355REC_REPLICA_AUTO / _OFF / _ON
     bool replica_allowed = true;        // false: created with MI355REC_CREATE_NO_REPLICA
     float replica_build_ms = 0.f;
@@ -356,54 +344,62 @@ int order_stream(mi355rec* h, hipStream_t s) {
     return MI355REC_OK;
 }
 
+// The largest of a launch size over the three kinds of rows (what sizes the list buffers they share).
+int most(const mi355rec* h, int ScanGeom::*field) {
+    int m = 0;
+    for (const ScanGeom& g : h->geom)
+        if (g.*field > m) m = g.*field;
+    return m;
+}
+
 // Synchronous host API: runs on the handle's private stream, after any
 // asynchronous work the caller enqueued through this handle.
 int sync_api_begin(mi355rec* h) { return order_stream(h, h->stream); }
 
-// Single-query scan: tiles of kScanTileRows rows are dealt round-robin over the
-// resident workgroups (rows_per_block = 0 selects that mapping in the kernel), so
+// Single-query scan over the fp32 rows: tiles of kScanTileRows rows are dealt round-robin over the
+// resident workgroups (the kernel's rows_per_block argument is 0: that mapping), so
 // the chip reads one moving window of the matrix — 3 % faster than a contiguous
 // block of rows per workgroup (measured, tools/kbench.hip).
 void plan_grid(mi355rec* h, int blocks_per_cu) {
+    ScanGeom& f = h->geom[kFp32];
+    f = ScanGeom();
     int64_t max_blocks = static_cast<int64_t>(h->cus) * blocks_per_cu;
     if (max_blocks > kMergeMaxLists) max_blocks = kMergeMaxLists;
     MI355REC_EXP_INT(max_blocks, "MI355REC_EXP_FP32_GRID", 1, max_blocks - 1);   // (tools/lat_exp.sh: fewer lists for the merge)
     const int64_t tiles = (h->n + kScanTileRows - 1) / kScanTileRows;
-    h->grid = static_cast<int>(tiles < max_blocks ? tiles : max_blocks);
-    h->rows_per_block = 0;
-    h->iters = static_cast<int>((tiles + h->grid - 1) / h->grid);
+    f.grid = static_cast<int>(tiles < max_blocks ? tiles : max_blocks);
+    f.iters = static_cast<int>((tiles + f.grid - 1) / f.grid);
     // a streamed launch: one workgroup is the merger of the query before ...
-    int g = h->grid > 1 ? h->grid - 1 : 1;
+    int g = f.grid > 1 ? f.grid - 1 : 1;
     if (g > kRideMaxLists - 1) g = kRideMaxLists - 1;
     MI355REC_EXP_INT(g, "MI355REC_EXP_SGRID", 1, g - 1);
     if (tiles < g) g = static_cast<int>(tiles);
-    h->sgrid = g;
-    h->siters = static_cast<int>((tiles + g - 1) / g);
+    f.sgrid = g;
+    f.siters = static_cast<int>((tiles + g - 1) / g);
     // ... and, where the launch can spare them, a few are the NEXT query's seed riders and its neighbourhood workgroup
     // (handoff.hip.h): a rider takes two regions per memory round trip (~2.5 us) and should be done well before the
     // scanners (~3 us per tile each) are; sized as if it took four, which still leaves it under half of the launch
     // (10 M rows: 11 riders x 12 round trips = 30 of 80 us).
-    F32Geom& f = h->fg;
-    f = F32Geom();
-    f.r_scan = h->sgrid;
-    f.r_iters = h->siters;
+    f.r_scan = f.sgrid;
+    f.r_iters = f.siters;
     int64_t sg = h->n / kHalfSeedBlock;
     if (sg > kHalfSeedMaxGrid) sg = kHalfSeedMaxGrid;
     if (h->n >= kF32SampleMinRows && sg >= 64) {
         f.seed_grid = static_cast<int>(sg);
         f.seed_stride = h->n / sg;
     }
-    if (h->grid >= 16 && h->grid == max_blocks && h->n >= kNbhdRows) {
-        f.nbhd = 1;
+    if (f.grid >= 16 && f.grid == max_blocks && h->n >= kNbhdRows) {
+        f.nbhd = true;
         if (f.seed_grid > 0) {
-            int rounds = static_cast<int>(h->siters * 3.0 / 12.0);
+            int rounds = static_cast<int>(f.siters * 3.0 / 12.0);
             if (rounds < 1) rounds = 1;
             int riders = (f.seed_grid + 4 * rounds - 1) / (4 * rounds);
-            if (riders > h->grid / 16) riders = h->grid / 16;
-            MI355REC_EXP_INT(riders, "MI355REC_EXP_F32_RIDERS", 0, h->grid / 4);
+            if (riders > f.grid / 16) riders = f.grid / 16;
+            MI355REC_EXP_INT(riders, "MI355REC_EXP_F32_RIDERS", 0, f.grid / 4);
             f.riders = riders;
         }
-        f.r_scan = h->grid - 1 - f.riders - f.nbhd;
+        f.hoists = f.riders > 0;
+        f.r_scan = f.grid - 2 - f.riders;   // (the merger, and the next query's neighbourhood workgroup)
         if (f.r_scan > kRideMaxLists - 1) f.r_scan = kRideMaxLists - 1;
         f.r_iters = static_cast<int>((tiles + f.r_scan - 1) / f.r_scan);
     }
@@ -427,8 +423,8 @@ void plan_multi_grid(mi355rec* h, int blocks_per_cu) {
 // Scan over a replica: tiles of `tile_rows` rows dealt round-robin; the seed kernel samples
 // `tile_rows` rows of up to 256 evenly spaced regions (>= tile_rows apart, so no row is sampled
 // twice; starts are multiples of `align` rows, the replica's packing unit).
-ReplicaGeom plan_replica(const mi355rec* h, int occ, int tile_rows, int align, double us_per_tile) {
-    ReplicaGeom g;
+ScanGeom plan_replica(const mi355rec* h, int occ, int tile_rows, int align, double us_per_tile) {
+    ScanGeom g;
     if (occ < 1) occ = 1;
     if (occ > 3) occ = 3;
     int64_t max_blocks = static_cast<int64_t>(h->cus) * occ;
@@ -467,6 +463,12 @@ ReplicaGeom plan_replica(const mi355rec* h, int occ, int tile_rows, int align, d
                 g.seed_grid = static_cast<int>(sg);
                 g.seed_stride = (h->n / sg) / align * align;
             }
+            // Over the 8-bit replica (plan_half_grid: not the fp16 one) the launch has the neighbourhood workgroup its
+            // riders left room for, and the last rider out turns the sample into the next launch's cutoff (saves a
+            // ~4 us select in every workgroup of that launch).  The riders then take sample + select (~10 us) in
+            // all, so only where the scanners run longer than that.
+            g.nbhd = true;
+            g.hoists = g.r_iters >= 5;
         }
     }
     return g;
@@ -477,9 +479,10 @@ void plan_half_grid(mi355rec* h) {
     // the fp16 replica: the multi-query pass's workgroups and sampled regions (experiment builds: also the single-query scan's)
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, scan_half_multi_kernel<false, false>, kHmBlock, 0) != hipSuccess) occ = 1;
     MI355REC_EXP_INT(occ, "MI355REC_EXP_HOCC", 1, 4);
-    h->hg = plan_replica(h, occ, HalfConfig::kTileRows, 2, 2.1);
+    h->geom[kFp16] = plan_replica(h, occ, HalfConfig::kTileRows, 2, 2.1);
+    h->geom[kFp16].nbhd = h->geom[kFp16].hoists = false;   // (its riders only take the sample; r_scan still leaves the slot)
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, scan_q8_kernel<Q8Config, true, false>, Q8Config::kBlock, 0) != hipSuccess) occ = 1;
-    h->qg = plan_replica(h, occ, Q8Config::kTileRows, 4, 2.1);
+    h->geom[kQ8] = plan_replica(h, occ, Q8Config::kTileRows, 4, 2.1);
 }
 
 void free_replica(mi355rec* h) {
@@ -628,7 +631,7 @@ int create_common(const float* feats, bool on_device, int64_t n, int dim, int de
         plan_multi_grid(h, mocc);
         plan_half_grid(h);
     } else {
-        h->grid = h->mgrid = 1;  // sizes the (unused) scratch; no scan is ever launched
+        h->geom[kFp32].grid = h->mgrid = 1;  // sizes the (unused) scratch; no scan is ever launched
     }
 
     int rc = MI355REC_OK;
@@ -655,10 +658,8 @@ int create_common(const float* feats, bool on_device, int64_t n, int dim, int de
         h->d_feats = h->owned_feats;
     }
 
-    int single_lists = h->grid > h->hg.grid ? h->grid : h->hg.grid;
-    if (h->qg.grid > single_lists) single_lists = h->qg.grid;
-    size_t list_words = static_cast<size_t>(single_lists) * kMaxTopK;
-    const size_t multi_words = static_cast<size_t>(h->mgrid > h->hg.grid ? h->mgrid : h->hg.grid) * kMultiChain * kMultiMaxTopK;
+    size_t list_words = static_cast<size_t>(most(h, &ScanGeom::grid)) * kMaxTopK;
+    const size_t multi_words = static_cast<size_t>(h->mgrid > h->geom[kFp16].grid ? h->mgrid : h->geom[kFp16].grid) * kMultiChain * kMultiMaxTopK;
     if (multi_words > list_words) list_words = multi_words;
     if ((e = hipMalloc(&h->d_block_lists, sizeof(uint64_t) * list_words)) != hipSuccess)
         return cleanup(MI355REC_ERR_OUT_OF_MEMORY, "hipMalloc(block lists)", e);

@@ -296,7 +296,7 @@ int mi355rec_stats(const mi355rec_t* hc, mi355rec_stats_t* out) {
     out->row_base = h->row_base;
     out->device = h->device;
     out->compute_units = h->cus;
-    out->grid_blocks = h->grid;
+    out->grid_blocks = h->geom[kFp32].grid;
     out->block_threads = kScanBlock;
     out->bytes_per_query = h->n * kDim * static_cast<int64_t>(sizeof(float));
     out->last_scan_ms = h->last_scan_ms;
@@ -306,7 +306,7 @@ int mi355rec_stats(const mi355rec_t* hc, mi355rec_stats_t* out) {
     out->batched_margin = h->bq.ready ? h->bq.margin : 0.0f;
     out->replica_bytes_per_query = h->d_half ? ((h->n + 1) / 2) * 48 : 0;
     out->replica_active = use_half(h, nullptr) ? 1 : 0;
-    out->replica_grid_blocks = h->d_half ? (use_q8(h) ? h->qg.grid : h->hg.grid) : 0;
+    out->replica_grid_blocks = h->d_half ? h->geom[use_q8(h) ? kQ8 : kFp16].grid : 0;
     out->replica_build_ms = h->replica_build_ms;
     out->replica_margin_single = h->d_half ? h->margin_mix : 0.0f;
     out->replica_margin_multi = h->d_half ? h->margin_mfma : 0.0f;
@@ -350,30 +350,46 @@ int mi355rec_stats_sized(const mi355rec_t* h, void* out, size_t out_size, size_t
 
 // ---- asynchronous device API -------------------------------------------------
 
+namespace {
+
+// What every mi355rec_enqueue_* call does once its own arguments have been looked at (null, then the row index): topn
+// (allow_rounds: topn > 1024 is served in rounds), the handle's device for the length of the call, and the caller's
+// stream ordered behind the handle's last one.  rc != 0: the call returns it.
+struct EnqueueCall {
+    DeviceGuard guard;
+    hipStream_t s;
+    int rc;
+    EnqueueCall(mi355rec* h, int topn, bool allow_rounds, void* stream)
+        : guard(h->device), s(static_cast<hipStream_t>(stream)), rc(check_topn(h, topn, allow_rounds)) {
+        if (!rc) rc = order_stream(h, s);
+    }
+};
+
+// An EMPTY shard answers with all-empty lists at once (it still takes part in the merge).
+static int answer_empty(mi355rec* h, mi355rec_key_t* out_keys_dev, size_t slots, hipStream_t s) {
+    HIP_TRY(h, hipMemsetAsync(out_keys_dev, 0, sizeof(uint64_t) * slots, s));
+    return MI355REC_OK;
+}
+
+}  // namespace
+
 int mi355rec_enqueue_row_keys(mi355rec_t* h, int64_t local_row, int topn,
                               mi355rec_key_t* out_keys_dev, void* stream) {
     if (!h || !out_keys_dev) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     if (local_row < 0 || local_row >= h->n)
         return fail(h, MI355REC_ERR_INVALID_ARG, "Invalid song index: %lld", (long long)local_row);
-    int rc = check_topn(h, topn, true);
-    if (rc) return rc;
-    DeviceGuard guard(h->device);
-    rc = order_stream(h, static_cast<hipStream_t>(stream));
-    if (rc) return rc;
+    EnqueueCall call(h, topn, true, stream);
+    if (call.rc) return call.rc;
     return enqueue_query(h, h->d_feats + local_row * kDim, nullptr, h->row_base + local_row, topn, out_keys_dev, nullptr,
-                         nullptr, static_cast<hipStream_t>(stream));
+                         nullptr, call.s);
 }
 
 int mi355rec_enqueue_query_keys(mi355rec_t* h, const float* query12, int64_t exclude_global,
                                 int topn, mi355rec_key_t* out_keys_dev, void* stream) {
     if (!h || !out_keys_dev || !query12) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    int rc = check_topn(h, topn, true);
-    if (rc) return rc;
-    DeviceGuard guard(h->device);
-    rc = order_stream(h, static_cast<hipStream_t>(stream));
-    if (rc) return rc;
-    return enqueue_query(h, nullptr, query12, exclude_global, topn, out_keys_dev, nullptr, nullptr,
-                         static_cast<hipStream_t>(stream));
+    EnqueueCall call(h, topn, true, stream);
+    if (call.rc) return call.rc;
+    return enqueue_query(h, nullptr, query12, exclude_global, topn, out_keys_dev, nullptr, nullptr, call.s);
 }
 
 int mi355rec_enqueue_row_keys_streamed(mi355rec_t* h, int64_t local_row, int topn, mi355rec_key_t* out_keys_dev,
@@ -381,29 +397,18 @@ int mi355rec_enqueue_row_keys_streamed(mi355rec_t* h, int64_t local_row, int top
     if (!h || !out_keys_dev) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     if (local_row < 0 || local_row >= h->n)
         return fail(h, MI355REC_ERR_INVALID_ARG, "Invalid song index: %lld", (long long)local_row);
-    int rc = check_topn(h, topn, false);
-    if (rc) return rc;
-    DeviceGuard guard(h->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = order_stream(h, s);
-    if (rc) return rc;
-    return enqueue_streamed(h, h->d_feats + local_row * kDim, nullptr, h->row_base + local_row, topn, out_keys_dev, s);
+    EnqueueCall call(h, topn, false, stream);
+    if (call.rc) return call.rc;
+    return enqueue_streamed(h, h->d_feats + local_row * kDim, nullptr, h->row_base + local_row, topn, out_keys_dev, call.s);
 }
 
 int mi355rec_enqueue_query_keys_streamed(mi355rec_t* h, const float* query12, int64_t exclude_global, int topn,
                                          mi355rec_key_t* out_keys_dev, void* stream) {
     if (!h || !out_keys_dev || !query12) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    int rc = check_topn(h, topn, false);
-    if (rc) return rc;
-    DeviceGuard guard(h->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = order_stream(h, s);
-    if (rc) return rc;
-    if (h->n < 1) {   // an EMPTY shard answers with an all-empty list at once (it still takes part in the merge)
-        HIP_TRY(h, hipMemsetAsync(out_keys_dev, 0, sizeof(uint64_t) * static_cast<size_t>(topn), s));
-        return MI355REC_OK;
-    }
-    return enqueue_streamed(h, nullptr, query12, exclude_global, topn, out_keys_dev, s);
+    EnqueueCall call(h, topn, false, stream);
+    if (call.rc) return call.rc;
+    if (h->n < 1) return answer_empty(h, out_keys_dev, static_cast<size_t>(topn), call.s);
+    return enqueue_streamed(h, nullptr, query12, exclude_global, topn, out_keys_dev, call.s);
 }
 
 int mi355rec_enqueue_batch_keys_streamed(mi355rec_t* h, const float* queries, const int64_t* exclude_global, int batch,
@@ -424,13 +429,10 @@ int mi355rec_enqueue_batch_mixed_keys_streamed(mi355rec_t* h, const float* queri
         if (query_ptrs_dev) return mi355rec_enqueue_batch_mixed_keys(h, queries, query_ptrs_dev, exclude_global, batch, topn, out_keys_dev, stream);
         return mi355rec_enqueue_batch_keys(h, queries, exclude_global, batch, topn, out_keys_dev, stream);
     }
-    int rc = check_topn(h, topn, false);
-    if (rc) return rc;
-    DeviceGuard guard(h->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = order_stream(h, s);
-    if (rc) return rc;
-    rc = flush_streamed(h, s);   // a stream of SINGLE queries on this handle is closed first
+    EnqueueCall call(h, topn, false, stream);
+    if (call.rc) return call.rc;
+    hipStream_t s = call.s;
+    int rc = flush_streamed(h, s);   // a stream of SINGLE queries on this handle is closed first
     if (rc) return rc;
     for (int g0 = 0; g0 < batch; g0 += kHmQueries) {
         const int nq = batch - g0 < kHmQueries ? batch - g0 : kHmQueries;
@@ -451,16 +453,11 @@ int mi355rec_enqueue_batch_mixed_keys(mi355rec_t* h, const float* queries, const
                                       void* stream) {
     if (!h || !out_keys_dev || (!queries && !query_ptrs_dev)) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     if (batch < 1) return fail(h, MI355REC_ERR_INVALID_ARG, "batch must be positive");
-    int rc = check_topn(h, topn, false);
-    if (rc) return rc;
-    DeviceGuard guard(h->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = order_stream(h, s);
-    if (rc) return rc;
-    if (h->n < 1) {   // an empty shard answers with all-empty lists
-        HIP_TRY(h, hipMemsetAsync(out_keys_dev, 0, sizeof(uint64_t) * static_cast<size_t>(batch) * topn, s));
-        return MI355REC_OK;
-    }
+    EnqueueCall call(h, topn, false, stream);
+    if (call.rc) return call.rc;
+    hipStream_t s = call.s;
+    int rc = MI355REC_OK;
+    if (h->n < 1) return answer_empty(h, out_keys_dev, static_cast<size_t>(batch) * topn, s);
     if (batch >= 2 && mi355rec_batch_pointers_ok(h, topn) && h->batch_path != MI355REC_BATCH_MULTI) {
         for (int b = 0; b < batch; b += kMultiChain) {
             const int count = batch - b < kMultiChain ? batch - b : kMultiChain;
@@ -496,30 +493,19 @@ int mi355rec_row_ptr(mi355rec_t* h, int64_t local_row, const float** out_dev) {
 int mi355rec_enqueue_ptr_keys(mi355rec_t* h, const float* query12_dev, int64_t exclude_global, int topn,
                               mi355rec_key_t* out_keys_dev, int64_t* out_idx_dev, float* out_score_dev, void* stream) {
     if (!h || !out_keys_dev || !query12_dev) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    int rc = check_topn(h, topn, true);
-    if (rc) return rc;
-    DeviceGuard guard(h->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = order_stream(h, s);
-    if (rc) return rc;
+    EnqueueCall call(h, topn, true, stream);
+    if (call.rc) return call.rc;
     return enqueue_query(h, h->n > 0 ? query12_dev : nullptr, query12_dev, exclude_global, topn, out_keys_dev, out_idx_dev,
-                         out_score_dev, s);
+                         out_score_dev, call.s);
 }
 
 int mi355rec_enqueue_ptr_keys_streamed(mi355rec_t* h, const float* query12_dev, int64_t exclude_global, int topn,
                                        mi355rec_key_t* out_keys_dev, void* stream) {
     if (!h || !out_keys_dev || !query12_dev) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
-    int rc = check_topn(h, topn, false);
-    if (rc) return rc;
-    DeviceGuard guard(h->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = order_stream(h, s);
-    if (rc) return rc;
-    if (h->n < 1) {
-        HIP_TRY(h, hipMemsetAsync(out_keys_dev, 0, sizeof(uint64_t) * static_cast<size_t>(topn), s));
-        return MI355REC_OK;
-    }
-    return enqueue_streamed(h, query12_dev, nullptr, exclude_global, topn, out_keys_dev, s);
+    EnqueueCall call(h, topn, false, stream);
+    if (call.rc) return call.rc;
+    if (h->n < 1) return answer_empty(h, out_keys_dev, static_cast<size_t>(topn), call.s);
+    return enqueue_streamed(h, query12_dev, nullptr, exclude_global, topn, out_keys_dev, call.s);
 }
 
 int mi355rec_enqueue_flush(mi355rec_t* h, void* stream) {
@@ -537,13 +523,9 @@ int mi355rec_enqueue_batch_keys(mi355rec_t* h, const float* queries, const int64
                                 int batch, int topn, mi355rec_key_t* out_keys_dev, void* stream) {
     if (!h || !queries || !out_keys_dev) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     if (batch < 1) return fail(h, MI355REC_ERR_INVALID_ARG, "batch must be positive");
-    int rc = check_topn(h, topn, true);
-    if (rc) return rc;
-    DeviceGuard guard(h->device);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = order_stream(h, s);
-    if (rc) return rc;
-    return enqueue_batch(h, queries, exclude_global, batch, topn, out_keys_dev, nullptr, nullptr, s);
+    EnqueueCall call(h, topn, true, stream);
+    if (call.rc) return call.rc;
+    return enqueue_batch(h, queries, exclude_global, batch, topn, out_keys_dev, nullptr, nullptr, call.s);
 }
 
 int mi355rec_enqueue_batch_keys_dev(mi355rec_t* h, const float* queries_dev, const int64_t* exclude_global_dev,
@@ -830,25 +812,16 @@ int mi355rec_enqueue_scores(mi355rec_t* h, int64_t local_row, const float* query
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc = order_stream(h, s);
     if (rc) return rc;
-    QueryArg qa;
-    std::memset(&qa, 0, sizeof qa);
-    qa.margin = h->margin_mix;
-    NextSeed no_next;
-    std::memset(&no_next, 0, sizeof no_next);
-    if (local_row >= 0) {
-        hipLaunchKernelGGL((scan_kernel<ScanConfig, true, true>), dim3(h->grid), dim3(kScanBlock), 0, s, h->d_feats,
-                           h->n, h->rows_per_block, h->iters, h->row_base, qa, h->d_feats + local_row * kDim,
+    const float* const qrow = local_row >= 0 ? h->d_feats + local_row * kDim : nullptr;
+    const QueryArg qa = make_query_arg(h, qrow, query12);
+    const ScanGeom& g = h->geom[kFp32];
+    by_query_form(qrow, [&](auto from_row, const float* qp) {
+        hipLaunchKernelGGL((scan_kernel<ScanConfig, decltype(from_row)::value, true>), dim3(g.grid), dim3(kScanBlock), 0, s, h->d_feats,
+                           h->n, static_cast<int64_t>(0), g.iters, h->row_base, qa, qp,
                            static_cast<int64_t>(-1), 1, static_cast<uint64_t*>(nullptr), out_scores_dev,
-                           static_cast<const uint64_t*>(nullptr), PrevMerge{nullptr, 0, 0, nullptr},
-                           static_cast<const unsigned long long*>(nullptr), static_cast<const unsigned long long*>(nullptr), 0u, no_next);
-    } else {
-        std::memcpy(qa.q, query12, sizeof qa.q);
-        hipLaunchKernelGGL((scan_kernel<ScanConfig, false, true>), dim3(h->grid), dim3(kScanBlock), 0, s, h->d_feats,
-                           h->n, h->rows_per_block, h->iters, h->row_base, qa, kNoQueryPtr,
-                           static_cast<int64_t>(-1), 1, static_cast<uint64_t*>(nullptr), out_scores_dev,
-                           static_cast<const uint64_t*>(nullptr), PrevMerge{nullptr, 0, 0, nullptr},
-                           static_cast<const unsigned long long*>(nullptr), static_cast<const unsigned long long*>(nullptr), 0u, no_next);
-    }
+                           static_cast<const uint64_t*>(nullptr), no_prev_merge(),
+                           static_cast<const unsigned long long*>(nullptr), static_cast<const unsigned long long*>(nullptr), 0u, no_next_seed());
+    });
     HIP_TRY(h, hipGetLastError());
     return MI355REC_OK;
 }
