@@ -138,13 +138,19 @@ public:
     // min(1024, max(topN, 8 * topN)).  Fewer than topN results come back when the pool holds no more eligible songs: raise
     // pool.  The overload of recommendForPlaylist takes the cap after pool.  maxPerArtist < 1 or unknown groups give {} and
     // a message; everything else as for the diversified forms.
+    // Extension: the whole family within genres.  This most general overload of recommendForPlaylist takes, last, the genre
+    // ids the results must come from (as recommendByIndexInGenres: the songs' genres are those of initialize(songs) or
+    // setGenreIds; the playlist's own songs may belong to any genre).  Empty: no restriction, the call as before (maxPerArtist
+    // < 1 stays an error there).  With genre ids this overload is the whole family, so maxPerArtist = 0 is accepted and asks
+    // for no cap: the diversified call, and with lambda = 1 the plain top-N within the genres (no pool, no re-rank).  A single song within
+    // genres with a filter, diversity or a cap is the one-song playlist {songIndex}.
     static std::vector<int> artistGroupIds(const std::vector<std::string>& artists);
     bool setGroupIds(const std::vector<int>& groupIds);
     std::vector<int> recommendByIndexCapped(int songIndex, int topN, int maxPerArtist, float lambda = 1.0f, int pool = 0,
                                             const std::vector<FeatureRange>& where = {});
     std::vector<int> recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
                                           const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude, float lambda,
-                                          int pool, int maxPerArtist);
+                                          int pool, int maxPerArtist, const std::vector<int>& genreIds = {});
 
     struct Impl;   // opaque: defined in Recommender.cpp
 

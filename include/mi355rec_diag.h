@@ -24,6 +24,8 @@
  *     features (mi355rec_query_mean_topn_diverse, _query_playlist_topn_diverse, their node-handle twins, mi355rec_fetch_rows);
  *   - group caps: "at most M results per artist" inside the same re-rank (mi355rec_set_groups, the _capped calls and their
  *     node-handle twins);
+ *   - PLAYLIST REQUESTS: the whole playlist family as one call that takes a struct, and the only one that takes a label set
+ *     (mi355rec_query_playlist_request and its node-handle twin);
  *   - test hooks, compiled in only with -DMI355REC_TEST_HOOKS (spotify_recommender_amd/build.py builds
  *     libmi355rec_testhooks.so for tests/; the product library does not export them).
  */
@@ -358,8 +360,8 @@ int mi355rec_sharded_rccl_ranks(const mi355rec_sharded_t* h, int* comms, int* ra
 /* LABELS (an extension beyond the reference): label-filtered top-N.
  * Every row of a handle may carry a label in [0, MI355REC_MAX_LABELS) — a genre id, or any category the caller chooses —
  * or -1 (unlabelled: never returned by a filtered query).  mi355rec_set_labels builds a copy of the shard's fp32 rows
- * grouped by label (labels ascending, rows stable inside a label, unlabelled rows last; +52 B per row of device memory:
- * the 48-B row and its 4-B original index) and the label offsets.  It gathers the rows to the host, sorts them there
+ * grouped by label (labels ascending, rows stable inside a label, unlabelled rows last; +54 B per row of device memory:
+ * the 48-B row, its 4-B original index and its label in row order as int16, what PLAYLIST REQUESTS read) and the label offsets.  It gathers the rows to the host, sorts them there
  * and uploads the copy: a one-time cost, O(n), paid by this call.  Calling it again replaces the labels; labels_host ==
  * NULL drops them; n must be the handle's row count.  A failure (out of memory, a HIP error) leaves the previous labels in
  * place.  A handle that has lanes (mi355rec_create_lane) refuses it (INVALID_ARG): the labels are shared by the group, and
@@ -577,6 +579,69 @@ int mi355rec_sharded_query_playlist_topn_capped(mi355rec_sharded_t* h, const int
                                                 const int64_t* exclude_global, int n_exclude, const mi355rec_filter_t* filter,
                                                 float lambda, int pool, int max_per_group, int topn, int64_t* out_idx, float* out_score,
                                                 float* out_mmr, int* out_count, int* out_pool_rows);
+
+/* PLAYLIST REQUESTS: the playlist family as ONE call, and the family within LABELS ("what goes with this playlist, in rock
+ * and indie, high-energy only, at most two per artist").
+ * mi355rec_playlist_query_t describes one call of the family: every entry point of PLAYLISTS, FEATURE FILTERS, WEIGHTED
+ * PLAYLISTS, DIVERSIFIED TOP-N and GROUP CAPS above is the special case that sets the fields it takes as arguments and leaves
+ * the others zero (same checks, same launches, same results bit for bit).  The struct carries its own size as its first
+ * field, as mi355rec_stats_sized does: set size = sizeof(mi355rec_playlist_query_t) of the header you compiled with.  The
+ * struct only ever grows at its end; a shorter one from an older caller is read as "later fields zero"; a size of 0 (below
+ * the size field itself), one that ends inside a field, or one larger than this library knows is INVALID_ARG.
+ *   members / rows   exactly one is non-NULL: k x 12 floats by value, or k rows of the handle (local rows of a single handle,
+ *                    global rows of a node handle; never returned);
+ *   weights          NULL, or k signed weights;           exclude_global / n_exclude   as in the playlist calls;
+ *   filter           NULL, or the feature filter;         topn   results asked for;
+ *   labels/n_labels  NULL / 0 (every row), or the label set, see below;
+ *   flags            MI355REC_PQ_DIVERSE: lambda and pool are read (the _diverse call); MI355REC_PQ_CAPPED (with _DIVERSE only):
+ *                    max_per_group is read (the _capped call).  Unknown bits: INVALID_ARG.
+ * mi355rec_playlist_result_t: out_idx (topn slots) is required; out_score (topn), out_mmr (topn; written by diversified calls
+ * only), out_count and out_pool_rows (P' of a capped call, else 0) may each be NULL.
+ * THE LABEL SET.  labels[0..n_labels): values in [0, MI355REC_MAX_LABELS), duplicates allowed.  With a label set a row is
+ * admissible iff its label (mi355rec_set_labels) is in the set, it passes the feature filter if there is one, and it is
+ * neither excluded nor a member row.  Rows labelled -1 are never admissible; members and excluded ids need not lie in the
+ * selected labels.  Everything else is unchanged bit for bit: scores, weights, canonical order, MMR picks, caps, ties.
+ * count = min(topn, |admissible rows|), the rest padded with -1 / 0; a set whose labels hold no rows answers count 0 without a
+ * launch; the pool of a diversified or capped call is the top-`pool` of the admissible rows.  labels == NULL with n_labels == 0
+ * is exactly the call without labels (same launch, same results).  k = 1 by row with a label set returns the ids and score
+ * bits of mi355rec_query_row_topn_labels.
+ * INVALID_ARG (with a message): everything the family refuses; n_labels < 0; n_labels > 0 with NULL labels; labels non-NULL
+ * with n_labels == 0; a label out of range; a label set on a handle without labels.
+ * Device: mi355rec_set_labels also keeps the labels in row order (int16, 2 B per row); playlist_scan_kernel tests a row's
+ * label against the set before anything else is done with the row (csrc/playlist.hip.h, "LABEL SET"): one pass over the
+ * whole catalogue, +2 B on the 8-bit replica's 12 B per row, whatever the selection.
+ * Node handle: one shard forwards; a replicated placement asks one replica; a row-sharded one forwards the label set to
+ * every shard (each holds its slice's labels from mi355rec_sharded_set_labels) and merges on the host.  The CPU backend
+ * serves the same calls. */
+#define MI355REC_PQ_DIVERSE 1u
+#define MI355REC_PQ_CAPPED 2u
+typedef struct {
+    uint32_t size;                    /* sizeof(mi355rec_playlist_query_t) of the caller's header */
+    uint32_t flags;                   /* MI355REC_PQ_* */
+    const float* members;             /* k x 12 floats (host), or NULL with ... */
+    const int64_t* rows;              /* ... k rows of the handle */
+    const float* weights;             /* NULL, or k signed weights */
+    const int64_t* exclude_global;    /* n_exclude global ids, or NULL */
+    const mi355rec_filter_t* filter;  /* NULL, or the feature filter */
+    const int32_t* labels;            /* NULL, or n_labels labels */
+    int32_t k;
+    int32_t n_exclude;
+    int32_t n_labels;
+    int32_t topn;
+    float lambda;                     /* MI355REC_PQ_DIVERSE */
+    int32_t pool;                     /* MI355REC_PQ_DIVERSE */
+    int32_t max_per_group;            /* MI355REC_PQ_CAPPED */
+} mi355rec_playlist_query_t;
+typedef struct {
+    int64_t* out_idx;                 /* topn slots; required */
+    float* out_score;                 /* topn slots, or NULL */
+    float* out_mmr;                   /* topn slots, or NULL (diversified calls) */
+    int* out_count;                   /* or NULL */
+    int* out_pool_rows;               /* or NULL (capped calls: P') */
+} mi355rec_playlist_result_t;
+int mi355rec_query_playlist_request(mi355rec_t* h, const mi355rec_playlist_query_t* query, const mi355rec_playlist_result_t* result);
+int mi355rec_sharded_query_playlist_request(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
+                                            const mi355rec_playlist_result_t* result);
 
 #ifdef MI355REC_TEST_HOOKS
 /* TEST HOOK for the cross-workgroup hand-offs of the streamed scans (csrc/replica.hip.h, "hand-offs that fail

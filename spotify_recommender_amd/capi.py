@@ -45,6 +45,23 @@ class Filter(ctypes.Structure):
     _fields_ = [("active", c_uint32), ("lo", c_float * DIM), ("hi", c_float * DIM)]
 
 
+PQ_DIVERSE, PQ_CAPPED = 1, 2
+
+
+class PlaylistQuery(ctypes.Structure):
+    """mi355rec_playlist_query_t (include/mi355rec_diag.h, PLAYLIST REQUESTS); `size` is sizeof of this struct."""
+    _fields_ = [("size", c_uint32), ("flags", c_uint32), ("members", c_void_p), ("rows", c_void_p), ("weights", c_void_p),
+                ("exclude_global", c_void_p), ("filter", POINTER(Filter)), ("labels", c_void_p), ("k", c_int32),
+                ("n_exclude", c_int32), ("n_labels", c_int32), ("topn", c_int32), ("lambda_", c_float), ("pool", c_int32),
+                ("max_per_group", c_int32)]
+
+
+class PlaylistResult(ctypes.Structure):
+    """mi355rec_playlist_result_t: every pointer but out_idx may be NULL."""
+    _fields_ = [("out_idx", c_void_p), ("out_score", c_void_p), ("out_mmr", c_void_p), ("out_count", POINTER(c_int)),
+                ("out_pool_rows", POINTER(c_int))]
+
+
 class Stats(ctypes.Structure):
     _fields_ = [
         ("rows", c_int64),
@@ -209,6 +226,8 @@ SIGNATURES = {
         c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]),
     "mi355rec_sharded_query_playlist_topn_capped": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_float, c_int, c_int, c_int,
         c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "mi355rec_query_playlist_request": (c_int, [c_void_p, POINTER(PlaylistQuery), POINTER(PlaylistResult)]),
+    "mi355rec_sharded_query_playlist_request": (c_int, [c_void_p, POINTER(PlaylistQuery), POINTER(PlaylistResult)]),
     "mi355rec_pack_key": (c_uint64, [c_float, c_int64]),
     "mi355rec_key_score": (c_float, [c_uint64]),
     "mi355rec_key_row": (c_int64, [c_uint64]),

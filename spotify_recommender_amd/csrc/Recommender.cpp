@@ -244,23 +244,30 @@ bool Recommender::setGenreIds(const std::vector<int>& genreIds) {
     return true;
 }
 
+namespace {
+// The first genre-restricted query hands the songs' genres to the engine.
+bool uploadLabels(Recommender::Impl* impl) {
+    if (impl->labelsUploaded) return true;
+    if (impl->genreIds.size() != static_cast<size_t>(impl->numSongs)) {
+        std::cerr << "Error: the songs' genre ids are not known (setGenreIds)" << std::endl;
+        return false;
+    }
+    if (mi355rec_sharded_set_labels(impl->engine, impl->genreIds.data(), impl->numSongs) != MI355REC_OK) {
+        std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
+        return false;
+    }
+    impl->labelsUploaded = true;
+    return true;
+}
+}  // namespace
+
 std::vector<int> Recommender::recommendByIndexInGenres(int songIndex, int topN, const std::vector<int>& genreIds) {
     if (!checkQuery(impl_, songIndex, topN)) return {};
     if (genreIds.empty()) {
         std::cerr << "Error: no genre to recommend from" << std::endl;
         return {};
     }
-    if (!impl_->labelsUploaded) {   // the first genre-restricted query hands the songs' genres to the engine
-        if (impl_->genreIds.size() != static_cast<size_t>(impl_->numSongs)) {
-            std::cerr << "Error: the songs' genre ids are not known (setGenreIds)" << std::endl;
-            return {};
-        }
-        if (mi355rec_sharded_set_labels(impl_->engine, impl_->genreIds.data(), impl_->numSongs) != MI355REC_OK) {
-            std::cerr << "Error: " << mi355rec_sharded_last_error(impl_->engine) << std::endl;
-            return {};
-        }
-        impl_->labelsUploaded = true;
-    }
+    if (!uploadLabels(impl_)) return {};
     impl_->idxBuf.assign(static_cast<size_t>(topN), -1);
     impl_->scoreBuf.assign(static_cast<size_t>(topN), 0.0f);
     int count = 0;
@@ -317,9 +324,10 @@ struct Diverse {
 
 // recommendForPlaylist with a filter (null: the unfiltered entry point) and weights (null: the entry points without them;
 // else one per song, the caller has checked the length); diverse: null, or the diversified entry point (weights and filter
-// may then be null).
+// may then be null).  genres: null or empty, or the genre ids the results come from (the request call, PLAYLIST REQUESTS).
 std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& songIndices, int topN, const std::vector<int>& alsoExclude,
-                               const mi355rec_filter_t* filter, const float* weights = nullptr, const Diverse* diverse = nullptr) {
+                               const mi355rec_filter_t* filter, const float* weights = nullptr, const Diverse* diverse = nullptr,
+                               const std::vector<int>* genres = nullptr) {
     if (!impl->initialized) {
         std::cerr << "Error: Recommender not initialized" << std::endl;
         return {};
@@ -378,14 +386,41 @@ std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& 
     const int k = static_cast<int>(rows.size()), nExcl = static_cast<int>(excl.size());
     int64_t* const idx = impl->idxBuf.data();
     float* const score = impl->scoreBuf.data();
-    const int rc =
-        diverse && diverse->capped
-            ? mi355rec_sharded_query_playlist_topn_capped(impl->engine, rows.data(), weights, k, excl.data(), nExcl, filter, diverse->lambda,
-                                                          pool, diverse->maxPerGroup, topN, idx, score, nullptr, &count, nullptr)
-        : diverse ? mi355rec_sharded_query_playlist_topn_diverse(impl->engine, rows.data(), weights, k, excl.data(), nExcl, filter,
-                                                                 diverse->lambda, pool, topN, idx, score, nullptr, &count)
-                  : mi355rec_sharded_query_playlist_topn_weighted(impl->engine, rows.data(), weights, k, excl.data(), nExcl, filter, topN, idx,
-                                                                  score, &count);
+    int rc;
+    if (genres && !genres->empty()) {
+        if (!uploadLabels(impl)) return {};
+        mi355rec_playlist_query_t q{};
+        q.size = sizeof q;
+        q.flags = (diverse ? MI355REC_PQ_DIVERSE : 0u) | (diverse && diverse->capped ? MI355REC_PQ_CAPPED : 0u);
+        q.rows = rows.data();
+        q.k = k;
+        q.weights = weights;
+        q.exclude_global = excl.data();
+        q.n_exclude = nExcl;
+        q.filter = filter;
+        q.labels = genres->data();
+        q.n_labels = static_cast<int32_t>(genres->size());
+        q.topn = topN;
+        if (diverse) {
+            q.lambda = diverse->lambda;
+            q.pool = pool;
+            q.max_per_group = diverse->maxPerGroup;
+        }
+        mi355rec_playlist_result_t res{};
+        res.out_idx = idx;
+        res.out_score = score;
+        res.out_count = &count;
+        rc = mi355rec_sharded_query_playlist_request(impl->engine, &q, &res);
+    } else if (diverse && diverse->capped) {
+        rc = mi355rec_sharded_query_playlist_topn_capped(impl->engine, rows.data(), weights, k, excl.data(), nExcl, filter, diverse->lambda,
+                                                         pool, diverse->maxPerGroup, topN, idx, score, nullptr, &count, nullptr);
+    } else if (diverse) {
+        rc = mi355rec_sharded_query_playlist_topn_diverse(impl->engine, rows.data(), weights, k, excl.data(), nExcl, filter, diverse->lambda,
+                                                          pool, topN, idx, score, nullptr, &count);
+    } else {
+        rc = mi355rec_sharded_query_playlist_topn_weighted(impl->engine, rows.data(), weights, k, excl.data(), nExcl, filter, topN, idx, score,
+                                                           &count);
+    }
     if (rc != MI355REC_OK) {
         std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
         return {};
@@ -400,7 +435,7 @@ std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& 
 // the filter (none for no ranges) and the query.
 std::vector<int> weightedPlaylistQuery(Recommender::Impl* impl, const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
                                        bool orNone, const std::vector<Recommender::FeatureRange>& where, const std::vector<int>& alsoExclude,
-                                       const Diverse* diverse = nullptr) {
+                                       const Diverse* diverse = nullptr, const std::vector<int>* genres = nullptr) {
     if (!(orNone && weights.empty()) && weights.size() != songIndices.size()) {
         std::cerr << "Error: " << weights.size() << " weights for " << songIndices.size() << " songs (one weight per song"
                   << (orNone ? ", or none" : "") << ")" << std::endl;
@@ -409,7 +444,7 @@ std::vector<int> weightedPlaylistQuery(Recommender::Impl* impl, const std::vecto
     mi355rec_filter_t f;
     if (!makeFilter(where, f)) return {};
     return playlistQuery(impl, songIndices, topN, alsoExclude, where.empty() ? nullptr : &f, weights.empty() ? nullptr : weights.data(),
-                         diverse);
+                         diverse, genres);
 }
 
 }  // namespace
@@ -439,9 +474,13 @@ std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songI
 
 std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
                                                    const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude, float lambda,
-                                                   int pool, int maxPerArtist) {
-    const Diverse d{lambda, pool, maxPerArtist, true};
-    return weightedPlaylistQuery(impl_, songIndices, topN, weights, true, where, alsoExclude, &d);
+                                                   int pool, int maxPerArtist, const std::vector<int>& genreIds) {
+    // Within genres maxPerArtist 0 asks for no cap: the diversified call, and with lambda 1, whose picks are the pool's first
+    // topN in order for any pool, the plain request (no pool, no re-rank launch).
+    const bool uncapped = maxPerArtist == 0 && !genreIds.empty();
+    const Diverse d{lambda, pool, maxPerArtist, !uncapped};
+    return weightedPlaylistQuery(impl_, songIndices, topN, weights, true, where, alsoExclude, uncapped && lambda == 1.0f ? nullptr : &d,
+                                 &genreIds);
 }
 
 std::vector<int> Recommender::recommendByIndexCapped(int songIndex, int topN, int maxPerArtist, float lambda, int pool,

@@ -390,6 +390,10 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
     const float* weights = r.weights;
     const mi355rec_filter_t* filter = r.filter;
     const int k = r.k, topn_asked = r.topn;
+    if (r.n_labels > 0 && !h->has_labels) {   // "PLAYLIST REQUESTS": a label set needs labels
+        *why = "this handle has no labels (mi355rec_sharded_set_labels)";
+        return MI355REC_ERR_INVALID_ARG;
+    }
     const Catalogue* c = h->cat;
     const int64_t n = c->n;
     std::vector<float> qn(static_cast<size_t>(k));
@@ -429,6 +433,17 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
         for (int64_t i = 0; i < n; ++i) {
             uint64_t& key = keys[static_cast<size_t>(i)];
             if (key != 0 && !mi355filter::pass(filter, f + i * kDim)) key = 0;
+            avail += key != 0;
+        }
+    }
+    if (r.n_labels > 0) {   // ... and so do the rows whose label is not in the set (-1: never)
+        uint32_t mask[MI355REC_MAX_LABELS / 32];
+        mi355playlist::label_bits(r, mask);
+        const LabelFilter in_set{h->labels.data(), mask};
+        avail = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            uint64_t& key = keys[static_cast<size_t>(i)];
+            if (key != 0 && !in_set.keeps(i)) key = 0;
             avail += key != 0;
         }
     }

@@ -1,5 +1,5 @@
 // engine_labels.hip.h — LABELS on the single-device handle (include/mi355rec_diag.h, "LABELS"): the label-grouped copy of
-// the shard's rows that mi355rec_set_labels builds, and the synchronous filtered query over it (labels.hip.h, then the
+// the shard's rows that mi355rec_set_labels builds (and the labels in row order for the playlist calls), and the synchronous filtered query over it (labels.hip.h, then the
 // merge of merge.hip.h into the handle's pinned result slots and completion word, as sync_single_query does).
 // (Part of mi355rec.hip's translation unit, included after engine_batch.hip.h.)
 #pragma once
@@ -15,6 +15,8 @@ struct mi355rec_labels {
     float* d_feats = nullptr;     // [n][12]: the rows, grouped by label (ascending), stable inside a label, unlabelled last
     uint32_t* d_rows = nullptr;   // [n]: the shard-local row of each sorted position
     int64_t* d_off = nullptr;     // [kMaxLabels + 1]: label l holds positions [d_off[l], d_off[l + 1])
+    int16_t* d_row_labels = nullptr;   // [ceil(n / 4) * 4]: the labels in ROW order, the last quad padded with -1 (what a playlist
+                                       // call with a label set reads, playlist.hip.h "LABEL SET": 2 B per row)
     std::vector<int64_t> off;     // the same offsets on the host
     int grid_cap = 1;             // workgroups of a filtered launch at most (occupancy x CUs, and the handle's list slots)
     float build_ms = 0.0f;        // wall time of the mi355rec_set_labels call that built it
@@ -24,7 +26,7 @@ namespace {
 
 void free_labels(mi355rec_labels* L) {
     if (!L) return;
-    void* bufs[] = {L->d_feats, L->d_rows, L->d_off};
+    void* bufs[] = {L->d_feats, L->d_rows, L->d_off, L->d_row_labels};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete L;
@@ -42,11 +44,14 @@ int build_labels(mi355rec* h, const int32_t* labels, mi355rec_labels** out) {
     if (!L) return fail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for the labels");
     std::vector<float> rows, sorted;
     std::vector<uint32_t> order;
+    std::vector<int16_t> in_row_order;
+    const size_t n_padded = (n + 3) / 4 * 4;
     try {   // (no exception may cross the C-ABI)
         L->off.assign(kMaxLabels + 2, 0);
         rows.resize(n * kDim);
         sorted.resize(n * kDim);
         order.resize(n);
+        in_row_order.assign(n_padded, static_cast<int16_t>(-1));
     } catch (const std::bad_alloc&) {
         free_labels(L);
         return fail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for the labels (%lld rows)", (long long)h->n);
@@ -60,6 +65,7 @@ int build_labels(mi355rec* h, const int32_t* labels, mi355rec_labels** out) {
         for (size_t i = 0; i < n; ++i) order[next[labels[i] < 0 ? kMaxLabels : labels[i]]++] = static_cast<uint32_t>(i);
     }
     off.resize(kMaxLabels + 1);   // (the end of the unlabelled bucket is n)
+    for (size_t i = 0; i < n; ++i) in_row_order[i] = static_cast<int16_t>(labels[i] < 0 ? -1 : labels[i]);   // (kMaxLabels fits int16)
     int occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, label_scan_kernel, LabelScanCfg::kBlock, 0) != hipSuccess || occ < 1) occ = 1;
     (void)hipGetLastError();
@@ -85,6 +91,9 @@ int build_labels(mi355rec* h, const int32_t* labels, mi355rec_labels** out) {
             return failed(e, "hipMemcpy(label-grouped rows H2D)");
         if ((e = hipMemcpy(L->d_rows, order.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice)) != hipSuccess)
             return failed(e, "hipMemcpy(label row ids H2D)");
+        if ((e = hipMalloc(&L->d_row_labels, sizeof(int16_t) * n_padded)) != hipSuccess) return failed(e, "hipMalloc(labels in row order)");
+        if ((e = hipMemcpy(L->d_row_labels, in_row_order.data(), sizeof(int16_t) * n_padded, hipMemcpyHostToDevice)) != hipSuccess)
+            return failed(e, "hipMemcpy(labels in row order H2D)");
     }
     if ((e = hipMemcpy(L->d_off, off.data(), sizeof(int64_t) * (kMaxLabels + 1), hipMemcpyHostToDevice)) != hipSuccess)
         return failed(e, "hipMemcpy(label offsets H2D)");

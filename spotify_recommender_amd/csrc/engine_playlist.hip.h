@@ -78,7 +78,8 @@ int ensure_playlist(mi355rec* h) {
 // allowed; ids of other shards match nothing here.  r.filter: null, or the feature filter (include/mi355rec_diag.h, "FEATURE
 // FILTERS"); null and active == 0 launch exactly the unfiltered call.  r.weights: null, or k signed weights
 // (include/mi355rec_diag.h, "WEIGHTED PLAYLISTS"); null launches the same kernel with every weight 1.0f and W = k, which is the
-// plain mean bit for bit.
+// plain mean bit for bit.  r.labels: null, or the label set (include/mi355rec_diag.h, "PLAYLIST REQUESTS"): only rows whose label
+// (mi355rec_set_labels) is in it are admissible; null launches exactly the call without labels.
 //
 // playlist_launch is the call up to and including its scan launch: the checks, the staging and playlist_scan_kernel, which
 // leaves `*grid` lists of `*eff` = min(r.scan_topn(), rows left after the exclusion list) keys in h->d_block_lists.  *eff == 0:
@@ -104,8 +105,20 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, int* eff_out
         for (int m = 0; m < k; ++m) b->excl[n_excl++] = static_cast<uint32_t>(h->row_base + r.rows[m]);
     std::sort(b->excl, b->excl + n_excl);
     n_excl = static_cast<int>(std::unique(b->excl, b->excl + n_excl) - b->excl);
+    int64_t avail = h->n - n_excl;
+    // the label set ("PLAYLIST REQUESTS"): at most the selected rows are left (host offsets); nothing selected: no launch
+    const mi355rec_labels* L = nullptr;
+    if (r.n_labels > 0) {
+        L = labels_of(h);
+        if (!L) return fail(h, MI355REC_ERR_INVALID_ARG, "this handle has no labels (mi355rec_set_labels)");
+        LabelMask mask;
+        int64_t selected = 0, label_tiles = 0;
+        rc = label_mask(h, L, r.labels, r.n_labels, &mask, &selected, &label_tiles);
+        if (rc) return rc;
+        std::memcpy(b->label_mask, mask.w, sizeof b->label_mask);
+        if (selected < avail) avail = selected;
+    }
     ++h->playlist_queries;
-    const int64_t avail = h->n - n_excl;
     const int eff = static_cast<int64_t>(r.scan_topn()) < avail ? r.scan_topn() : static_cast<int>(avail);
     if (eff <= 0) return MI355REC_OK;   // nothing left to return: nothing to launch
     PlaylistArg arg;
@@ -114,6 +127,7 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, int* eff_out
     arg.by_row = r.rows ? 1 : 0;
     arg.active = r.filter ? r.filter->active : 0u;
     arg.wsum = r.weights ? mi355weights::sum_abs(r.weights, k) : static_cast<float>(k);
+    arg.labelled = L ? 1 : 0;
     for (int m = 0; m < k; ++m) b->weights[m] = r.weights ? r.weights[m] : 1.0f;
     if (arg.active) {
         std::memcpy(b->lo, r.filter->lo, sizeof b->lo);
@@ -138,7 +152,8 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, int* eff_out
     LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, playlist_scan_kernel, dim3(grid), dim3(PlaylistCfg::kBlock),
                  h->stream, h->d_feats, q8, h->n, h->row_base, static_cast<const PlaylistBuf*>(P->d_buf), arg,
                  static_cast<const float*>(h->d_anchor), eff, h->d_block_lists, P->d_exact,
-                 reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr)));
+                 reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr)),
+                 reinterpret_cast<const uint2*>(L ? L->d_row_labels : nullptr));
     HIP_TRY(h, hipGetLastError());
     *eff_out = eff;
     *grid_out = grid;
@@ -239,6 +254,17 @@ int mi355rec_query_playlist_topn_weighted(mi355rec_t* h, const int64_t* local_ro
                                           int64_t* out_idx, float* out_score, int* out_count) {
     return sync_playlist_query(h, request(nullptr, local_rows, weights, k, exclude_global, n_exclude, filter, topn),
                                {out_idx, out_score, nullptr, out_count, nullptr});
+}
+
+// "PLAYLIST REQUESTS": the family's one call; every entry point above (and engine_diverse.hip.h's) is a special case of it.
+int mi355rec_query_playlist_request(mi355rec_t* h, const mi355rec_playlist_query_t* query, const mi355rec_playlist_result_t* result) {
+    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    mi355rec_playlist_query_t full;
+    Request r;
+    Outputs out;
+    char why[128];
+    if (mi355playlist::from_query(query, result, &full, &r, &out, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    return sync_playlist_query(h, r, out);
 }
 
 int mi355rec_playlist_counters(const mi355rec_t* h, int64_t* queries, int64_t* rows_exact) {

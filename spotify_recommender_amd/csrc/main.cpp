@@ -9,12 +9,14 @@
 //   recommender --id "<track_id>" [-n N]
 //   ... either query mode with one or more --genre NAME: recommendations only from those genres (extension)
 //   recommender --playlist "<track_id>,<track_id>,..." [-n N]: what goes with a playlist of up to 32 songs (extension)
+//   ... --playlist with one or more --genre NAME: only songs of those genres, together with any of --where, --dislike,
+//       --weights, --diverse, --pool and --max-per-artist (extension); for one song, --playlist <one id> --genre ...
 //   ... --song, --id and --playlist with one or more --where NAME=LO:HI: only songs whose feature NAME lies in [LO, HI]
-//       (normalised units; extension; not with --genre)
+//       (normalised units; extension; with --genre in the --playlist mode only)
 //   ... --song, --id and --playlist with --diverse LAMBDA [--pool P]: diversified results (maximal marginal relevance over the
-//       P most similar songs; extension; usable with --where, --dislike, --weights; not with --genre)
+//       P most similar songs; extension; usable with --where, --dislike, --weights; with --genre in the --playlist mode only)
 //   ... --song, --id and --playlist with --max-per-artist M: at most M results per primary artist (extension; combines with
-//       --where, --dislike, --weights, --diverse and --pool; not with --genre)
+//       --where, --dislike, --weights, --diverse and --pool; with --genre in the --playlist mode only)
 //   ... --playlist with --dislike "<track_id>,..." [--dislike-weight W] [--weights "w,w,..."]: weighted playlists (extension):
 //       the disliked songs push results away (weight -W, default 0.5), --weights gives the playlist's songs their own weights
 #include <algorithm>
@@ -39,7 +41,7 @@ static void usage(const char* prog) {
               << "   Returns top N similar songs (default N=10).\n\n"
               << "3. Recommendation Mode (by track ID):\n   " << prog << " --id \"track_id\" [-n N]\n"
               << "   Returns top N similar songs (default N=10).\n\n"
-              << "Filter (extension): --where NAME=LO:HI, repeatable, with --song, --id or --playlist (not with --genre):\n"
+              << "Filter (extension): --where NAME=LO:HI, repeatable, with --song, --id or --playlist (with --genre: --playlist only):\n"
               << "   only songs whose feature NAME lies in [LO, HI].  NAME is a CSV feature column (danceability, energy, key, loudness,\n"
               << "   mode, speechiness, acousticness, instrumentalness, liveness, valence, tempo); LO and HI are in the\n"
               << "   normalised [0, 1] units songs_data.bin holds (min-max over the CSV), not raw BPM or dB.\n\n"
@@ -47,11 +49,15 @@ static void usage(const char* prog) {
               << "   [--weights \"w,w,...\"]: songs like the playlist's and unlike the disliked ones (each counts -W, default 0.5);\n"
               << "   --weights gives one weight per playlist song (default 1 each).  Usable with --where.\n"
               << "Diversified results (extension): --diverse LAMBDA [--pool P], with --song, --id or --playlist (and --where, --dislike,\n"
-              << "   --weights; not with --genre): picks from the P most similar songs (default 4 x N, at most 1024), each pick\n"
+              << "   --weights; with --genre: --playlist only): picks from the P most similar songs (default 4 x N, at most 1024), each pick\n"
               << "   weighing similarity (LAMBDA in [0, 1]; 1 = the plain result) against likeness to the songs already picked.\n"
               << "Artist cap (extension): --max-per-artist M, with --song, --id or --playlist (and --where, --dislike, --weights,\n"
-              << "   --diverse, --pool; not with --genre): at most M results by one primary artist (the artists field up to its\n"
-              << "   first ';').  Results come from the P most similar songs (--pool; default 8 x N, at most 1024).\n" << std::endl;
+              << "   --diverse, --pool; with --genre: --playlist only): at most M results by one primary artist (the artists field up to its\n"
+              << "   first ';').  Results come from the P most similar songs (--pool; default 8 x N, at most 1024).\n"
+              << "Playlists within genres (extension): " << prog << " --playlist \"id,id,...\" --genre NAME [--genre NAME ...]\n"
+              << "   with any of --where, --dislike, --weights, --diverse, --pool, --max-per-artist: only songs of those genres.\n"
+              << "   With --song / --id, --genre does not combine with --where, --diverse or --max-per-artist: use\n"
+              << "   --playlist <one id> --genre ... for those combinations.\n" << std::endl;
 }
 
 // --where NAME=LO:HI, any number of times from argv[first]: the ranges (feature indices in Song.h order).  false, with a
@@ -200,11 +206,8 @@ static void whereRecommendations(Recommender& recommender, const DataManager::Ca
     recs = recommender.recommendByIndexWhere(index, topN, ranges);
 }
 
-// --genre: the songs whose genre is one of `genres` (names matched case-insensitively), ranked as recommendByIndex
-// ranks the whole catalogue; the query song is found by the engine's rules (exact id / exact name, then substring).
-static bool genreRecommendations(Recommender& recommender, const DataManager::Catalogue& catalogue, const std::string& query,
-                                 bool isTrackId, int topN, const std::vector<std::string>& genres, std::vector<int>& recs) {
-    std::vector<int> ids;
+// The ids of the genres named (case-insensitively); false, with a message, for an unknown one.
+static bool genreIdsOf(const DataManager::Catalogue& catalogue, const std::vector<std::string>& genres, std::vector<int>& ids) {
     for (const std::string& name : genres) {
         int id = -1;
         for (const auto& g : catalogue.genreMap)
@@ -215,6 +218,15 @@ static bool genreRecommendations(Recommender& recommender, const DataManager::Ca
         }
         ids.push_back(id);
     }
+    return true;
+}
+
+// --genre: the songs whose genre is one of `genres` (names matched case-insensitively), ranked as recommendByIndex
+// ranks the whole catalogue; the query song is found by the engine's rules (exact id / exact name, then substring).
+static bool genreRecommendations(Recommender& recommender, const DataManager::Catalogue& catalogue, const std::string& query,
+                                 bool isTrackId, int topN, const std::vector<std::string>& genres, std::vector<int>& recs) {
+    std::vector<int> ids;
+    if (!genreIdsOf(catalogue, genres, ids)) return false;
     const int index = findQuery(catalogue, query, isTrackId);
     if (index < 0) {
         std::cerr << "Error: Song with " << (isTrackId ? "track_id" : "name") << " '" << query << "' not found" << std::endl;
@@ -390,7 +402,7 @@ static bool parseTaste(int argc, char* argv[], int first, Taste& taste) {
 }
 
 static bool playlistMode(const std::string& list, int topN, const std::vector<Recommender::FeatureRange>& ranges, const Taste& taste,
-                         const DiverseOpt& dv) {
+                         const DiverseOpt& dv, const std::vector<std::string>& genres) {
     std::cout << "=== PLAYLIST MODE ===" << std::endl;
     std::vector<std::string> ids = splitList(list);
     if (ids.empty()) {
@@ -406,6 +418,8 @@ static bool playlistMode(const std::string& list, int topN, const std::vector<Re
         std::cerr << "Error: --weights names " << taste.weights.size() << " weights for " << ids.size() << " playlist songs" << std::endl;
         return false;
     }
+    std::vector<int> genreIds;   // --genre: only songs of these genres are recommended (the playlist's own may be of any)
+    if (!genreIdsOf(catalogue, genres, genreIds)) return false;
     const size_t liked = ids.size();
     ids.insert(ids.end(), taste.dislike.begin(), taste.dislike.end());
     std::vector<float> weights = taste.haveWeights ? taste.weights : std::vector<float>(liked, 1.0f);
@@ -432,7 +446,17 @@ static bool playlistMode(const std::string& list, int topN, const std::vector<Re
         std::cout << "At most " << dv.maxPerArtist << " per artist" << std::endl;
     }
     if (dv.on && (dv.maxPerArtist == 0 || dv.lambda < 1.0f)) std::cout << "Diversified: lambda " << dv.lambda << std::endl;
-    const std::vector<int> recs = dv.maxPerArtist > 0
+    if (!genreIds.empty()) {
+        std::cout << "Restricted to genres:";
+        for (const std::string& name : genres) std::cout << " " << name;
+        std::cout << std::endl;
+        if (!recommender.setGenreIds(catalogue.genreIds)) return false;
+    }
+    const std::vector<int> recs = !genreIds.empty()   // (the general overload: lambda 1 without a cap is the plain request)
+                                      ? recommender.recommendForPlaylist(members, topN, taste.weighted ? weights : std::vector<float>(), ranges,
+                                                                         {}, dv.on ? dv.lambda : 1.0f, dv.on ? dv.pool : 0, dv.maxPerArtist,
+                                                                         genreIds)
+                                  : dv.maxPerArtist > 0
                                       ? recommender.recommendForPlaylist(members, topN, taste.weighted ? weights : std::vector<float>(), ranges,
                                                                          {}, dv.lambda, dv.pool, dv.maxPerArtist)
                                   : dv.on         ? recommender.recommendForPlaylist(members, topN, taste.weighted ? weights : std::vector<float>(),
@@ -549,7 +573,16 @@ int main(int argc, char* argv[]) {
         if (!parseTaste(argc, argv, 3, taste)) return 1;
         DiverseOpt dv;
         if (!parseDiverse(argc, argv, 3, topN, dv)) return 1;
-        return playlistMode(argv[2], topN, ranges, taste, dv) ? 0 : 1;
+        std::vector<std::string> genres;   // --genre NAME, any number of times
+        for (int i = 3; i < argc; ++i) {
+            if (std::strcmp(argv[i], "--genre") != 0) continue;
+            if (i + 1 >= argc) {
+                std::cerr << "Error: --genre needs a genre name" << std::endl;
+                return 1;
+            }
+            genres.push_back(argv[++i]);
+        }
+        return playlistMode(argv[2], topN, ranges, taste, dv, genres) ? 0 : 1;
     }
     std::cerr << "Error: Unknown mode '" << mode << "'" << std::endl;
     usage(argv[0]);

@@ -73,6 +73,21 @@
 // rows bounds the answer) keeps every workgroup's threshold and the shared atomicMax valid.  rows_exact then counts every
 // row read from the fp32 matrix (rejected ones included).  active == 0 takes none of these branches (uniform tests).
 //
+// LABEL SET (include/mi355rec_diag.h, "PLAYLIST REQUESTS").  PlaylistArg::labelled (uniform), PlaylistBuf::label_mask (bit l:
+// label l is selected) and `labels`, the shard's labels in row order as int16 (engine_labels.hip.h: four to a quad, the last
+// quad padded with -1): a row is admissible only if its label is >= 0 and selected.  The test needs no fp32 row, so it comes
+// FIRST: per tile a lane loads its quad's four labels as one 8-byte load (the quad clamped as load_q8 clamps it, issued
+// with the next tile's replica load) and clears the mask bit of every row that fails, before the 8-bit dot products, the
+// filter's fp32 loads and any chain — on the exact path too.  A row rejected by its label never reads an fp32 row and
+// rows_exact does not count it.  The pre-filter, its margin and the argument of tests/test_playlist_margin.py do not change:
+// the replica still only rules rows out by similarity, of the rows the label test has left.
+//   * anchors: anchors whose row (anchor_row(n, i)) is not selected are not chosen; the rows then read from the matrix are
+//     checked again, as the filter does, so the starting threshold is the topk-th best key among admissible rows;
+//   * scan: as above.
+// So keys are only ever formed for admissible rows here as well, and the rule (the k-th best among ANY k admissible, not
+// excluded rows bounds the answer) keeps every workgroup's threshold and the shared atomicMax valid.  labelled == 0 takes
+// none of these branches (uniform tests) and never reads `labels`.
+//
 // EXCLUSION.  The excluded global ids (members and the caller's list, sorted and deduplicated on the host, at most
 // kPlExcludeCap) sit in LDS as uint32; only a key that already beats the workgroup's threshold is looked up (binary
 // search), so the hot loop does not change.
@@ -83,6 +98,7 @@
 // follows.
 #pragma once
 
+#include "labels.hip.h"
 #include "replica_q8.hip.h"
 
 #pragma clang fp contract(off)
@@ -106,6 +122,7 @@ struct PlaylistBuf {
     float hi[kDim];
     float weights[kMaxPlaylist];     // w_k, checked by the host (1.0f each for an unweighted call)
     unsigned long long shared_thr;   // the best threshold any workgroup of the launch has found (0 from the host)
+    uint32_t label_mask[kMaxLabels / 32];   // the label set (read only where PlaylistArg::labelled): bit l = label l is selected
     uint32_t excl[kPlExcludeCap];   // sorted, distinct global ids (only those of this shard)
 };
 
@@ -115,7 +132,13 @@ struct PlaylistArg {
     int by_row;       // 1: member m is the shard's row PlaylistBuf::rows[m]; 0: PlaylistBuf::members[m]
     uint32_t active;  // the feature filter: bit j (j < kDim) constrains feature j; 0: no filter
     float wsum;       // W = fl(sum_k |w_k|) in member order (the host's fp32 sum; K for an unweighted call)
+    int labelled;     // 1: only rows whose label is in PlaylistBuf::label_mask are admissible; 0: no label set
 };
+
+// Is label l (int16 of the row-order array: -1 = unlabelled or padding) in the set?
+__device__ __forceinline__ bool label_selected(const uint32_t* s_lmask, int l) {
+    return l >= 0 && ((s_lmask[(l & (kMaxLabels - 1)) >> 5] >> (l & 31)) & 1u) != 0u;
+}
 
 // The feature filter's predicate on one fp32 row (active: uniform; unrolled, so no feature is indexed at run time).
 __device__ __forceinline__ bool filter_pass(const Row& r, uint32_t active, const float* __restrict__ lo, const float* __restrict__ hi) {
@@ -170,10 +193,12 @@ __device__ __forceinline__ bool playlist_excluded(const uint32_t* s_excl, int n_
 
 // q8: the handle's 8-bit replica, or null (every row exact).  anchors: the anchor table, or null (no starting threshold).
 // rows_exact: += the rows whose K chains this launch computed; with a filter, every fp32 row read (rejected ones included).
+// labels: the shard's labels in row order, four int16 to a quad (read only where arg.labelled).
 __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void playlist_scan_kernel(
     const float* __restrict__ feats, const uint4* __restrict__ q8, int64_t n, int64_t row_base, const PlaylistBuf* __restrict__ buf,
     PlaylistArg arg, const float* __restrict__ anchors, int topk, uint64_t* __restrict__ block_lists,
-    unsigned long long* __restrict__ rows_exact, unsigned long long* __restrict__ shared_thr /* &buf->shared_thr */) {
+    unsigned long long* __restrict__ rows_exact, unsigned long long* __restrict__ shared_thr /* &buf->shared_thr */,
+    const uint2* __restrict__ labels) {
     constexpr int kBlock = PlaylistCfg::kBlock;
     static_assert(PlaylistCfg::kCandCap >= kAnchorRows / 2 && PlaylistCfg::kCandCap * 2 >= kPlBoundRows, "LDS reuse below");
     __shared__ uint64_t s_cand[PlaylistCfg::kCandCap];
@@ -187,6 +212,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     __shared__ float s_w[kMaxPlaylist];
     __shared__ float s_u[kDim];
     __shared__ uint32_t s_excl[kPlExcludeCap];
+    __shared__ uint32_t s_lmask[kMaxLabels / 32];
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -194,6 +220,8 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     const int n_excl = arg.n_excl;
     const uint32_t active = arg.active;
     const float wsum = arg.wsum;
+    const bool labelled = arg.labelled != 0;
+    const int16_t* const row_label = reinterpret_cast<const int16_t*>(labels);
     const float* const f_lo = buf->lo;
     const float* const f_hi = buf->hi;
 
@@ -201,6 +229,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     for (int i = tid; i < k * kDim; i += kBlock)
         s_mem[i / kDim][i % kDim] = arg.by_row ? feats[buf->rows[i / kDim] * kDim + i % kDim] : buf->members[i / kDim][i % kDim];
     for (int i = tid; i < n_excl; i += kBlock) s_excl[i] = buf->excl[i];
+    if (labelled && tid < kMaxLabels / 32) s_lmask[tid] = buf->label_mask[tid];
     if (tid == 0) {
         s_count = 0;
         s_ok = 1;
@@ -244,9 +273,10 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
             const Row a = load_row(anchors, static_cast<int64_t>(i));
             mine[r] = i < n_anchor ? pack_key(cosine_score(u, un, a), static_cast<uint32_t>(i)) : 0ull;
             if (active && !filter_pass(a, active, f_lo, f_hi)) mine[r] = 0ull;   // (only chooses: re-checked on the matrix's row)
+            if (labelled && i < n_anchor && !label_selected(s_lmask, row_label[anchor_row(n, i)])) mine[r] = 0ull;
         }
         int n_cand = kPlBoundRows;   // anchors left to choose from: all of them without a filter
-        if (active) {   // uniform
+        if (active || labelled) {   // uniform
 #pragma unroll
             for (int r = 0; r < kPer; ++r) {
                 const uint64_t have = __ballot(mine[r] != 0ull);
@@ -279,7 +309,10 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
             const float m = playlist_mean(s_mem, s_qn, s_w, wsum, k, x);
             ++n_exact;
             const uint32_t g = static_cast<uint32_t>(row_base + row);
-            key = playlist_excluded(s_excl, n_excl, g) || (active && !filter_pass(x, active, f_lo, f_hi)) ? 0ull : pack_key(m, g);
+            key = playlist_excluded(s_excl, n_excl, g) || (active && !filter_pass(x, active, f_lo, f_hi)) ||
+                          (labelled && !label_selected(s_lmask, row_label[row]))
+                      ? 0ull
+                      : pack_key(m, g);
         }
         const uint64_t have = __ballot(key != 0ull);
         __syncthreads();   // (every thread has read s_count and s_pick)
@@ -320,19 +353,35 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
         d.t1 = p[1];
         d.t2 = p[2];
     };
+    auto load_labels = [&](int64_t t) {   // the quad's four labels, 8 bytes (the quad clamped as in load_q8)
+        int64_t quad = t * kBlock + tid;
+        quad = quad < n_quads ? quad : n_quads - 1;
+        return labels[quad];
+    };
     HalfTile cur;
     cur.t0 = cur.t1 = cur.t2 = make_uint4(0u, 0u, 0u, 0u);
     if (prefilter) load_q8(cur, blockIdx.x);
+    uint2 lab_cur = make_uint2(0u, 0u);
+    if (labelled) lab_cur = load_labels(blockIdx.x);
 
     for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {   // uniform
         HalfTile nxt = cur;
         if (prefilter) load_q8(nxt, t + gridDim.x);   // the next tile is in flight while this one is scored
+        uint2 lab_nxt = lab_cur;
+        if (labelled) lab_nxt = load_labels(t + gridDim.x);   // (uniform) ... and so are its labels
         const int64_t quad = t * kBlock + tid;
         const int64_t r0 = quad * 4;
         uint32_t mask = 0u;
         if (quad < n_quads) {
             const int64_t left = n - r0;
             mask = left >= 4 ? 0xfu : (1u << static_cast<int>(left)) - 1u;
+        }
+        if (labelled) {   // (uniform) the label test first: it needs nothing but the label
+            const int l4[4] = {static_cast<int16_t>(lab_cur.x & 0xffffu), static_cast<int16_t>(lab_cur.x >> 16),
+                               static_cast<int16_t>(lab_cur.y & 0xffffu), static_cast<int16_t>(lab_cur.y >> 16)};
+#pragma unroll
+            for (int u4 = 0; u4 < 4; ++u4)
+                if (!label_selected(s_lmask, l4[u4])) mask &= ~(1u << u4);
         }
         if (prefilter) {   // uniform
             int a[4];
@@ -387,6 +436,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
         if (published > thr) thr = published;
         refresh_cut();
         cur = nxt;
+        lab_cur = lab_nxt;
     }
 
     const int wave_exact = wave_inclusive_scan(n_exact);

@@ -1,12 +1,16 @@
 // playlist_request.h — ONE description of a call of the playlist family (include/mi355rec_diag.h: "PLAYLISTS", "FEATURE
 // FILTERS", "WEIGHTED PLAYLISTS", "DIVERSIFIED TOP-N", "GROUP CAPS"), its outputs and its argument checks, shared by the single
 // handle (engine_playlist.hip.h), the node handle (sharded.hip) and the CPU backend.  Every exported entry point of the
-// family fills a Request and an Outputs and takes the one path of its handle type; neither struct is part of the C-ABI.
+// family fills a Request and an Outputs and takes the one path of its handle type.  Neither struct is part of the C-ABI; the
+// C-ABI's own request ("PLAYLIST REQUESTS": mi355rec_playlist_query_t, the only call that takes a label set) is converted
+// to them by from_query below.
 #pragma once
 
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 
 #include "filter_check.h"
 #include "mi355rec_diag.h"
@@ -22,6 +26,8 @@ struct Request {
     const int64_t* exclude = nullptr;           // n_exclude global ids, any order, duplicates allowed
     int n_exclude = 0;
     const mi355rec_filter_t* filter = nullptr;  // null, or the feature filter
+    const int32_t* labels = nullptr;            // null (every row), or n_labels labels in [0, MI355REC_MAX_LABELS): only rows
+    int n_labels = 0;                           // ... whose label is in the set are admissible ("PLAYLIST REQUESTS")
     int topn = 0;
     bool diverse = false;                       // the top-`pool` re-ranked by maximal marginal relevance with `lambda`
     float lambda = 1.0f;
@@ -144,6 +150,74 @@ inline bool invalid_playlist(const Request& r, int64_t n_rows, int64_t exclude_e
             }
     if (r.filter && mi355filter::invalid(r.filter, msg, cap)) return true;
     if (r.weights && mi355weights::invalid(r.weights, r.k, msg, cap)) return true;
+    // the label set: the messages of the label calls (engine_labels.hip.h, label_mask)
+    if (r.n_labels < 0 || (r.labels && r.n_labels == 0)) {
+        std::snprintf(msg, cap, "n_labels must be positive, got %d", r.n_labels);
+        return true;
+    }
+    if (r.n_labels > 0 && !r.labels) {
+        std::snprintf(msg, cap, "null label set");
+        return true;
+    }
+    for (int i = 0; i < r.n_labels; ++i)
+        if (r.labels[i] < 0 || r.labels[i] >= MI355REC_MAX_LABELS) {
+            std::snprintf(msg, cap, "label %d out of [0, %d)", static_cast<int>(r.labels[i]), MI355REC_MAX_LABELS);
+            return true;
+        }
+    return false;
+}
+
+// The label set of a checked request as a mask: bit l of mask[l / 32] (MI355REC_MAX_LABELS / 32 words).
+inline void label_bits(const Request& r, uint32_t* mask) {
+    for (int w = 0; w < MI355REC_MAX_LABELS / 32; ++w) mask[w] = 0u;
+    for (int i = 0; i < r.n_labels; ++i) mask[r.labels[i] >> 5] |= 1u << (r.labels[i] & 31);
+}
+
+// The C-ABI's request (include/mi355rec_diag.h, "PLAYLIST REQUESTS") as the Request and Outputs every layer below takes.
+// q->size says how much of the struct the caller knows: a shorter one is read as "later fields zero"; 0, or more than this
+// library knows, is refused.  True when the structs cannot be used; then msg[0..cap) says why.
+inline bool from_query(const mi355rec_playlist_query_t* q, const mi355rec_playlist_result_t* res, mi355rec_playlist_query_t* full,
+                       Request* r, Outputs* out, char* msg, size_t cap) {
+    if (!q || !res) {
+        std::snprintf(msg, cap, "null argument");
+        return true;
+    }
+    // (a struct that ends inside a field would hand over half a pointer: only sizes that end where a field ends)
+    static const size_t ends[] = {offsetof(mi355rec_playlist_query_t, flags),          offsetof(mi355rec_playlist_query_t, members),
+                                  offsetof(mi355rec_playlist_query_t, rows),           offsetof(mi355rec_playlist_query_t, weights),
+                                  offsetof(mi355rec_playlist_query_t, exclude_global), offsetof(mi355rec_playlist_query_t, filter),
+                                  offsetof(mi355rec_playlist_query_t, labels),         offsetof(mi355rec_playlist_query_t, k),
+                                  offsetof(mi355rec_playlist_query_t, n_exclude),      offsetof(mi355rec_playlist_query_t, n_labels),
+                                  offsetof(mi355rec_playlist_query_t, topn),           offsetof(mi355rec_playlist_query_t, lambda),
+                                  offsetof(mi355rec_playlist_query_t, pool),           offsetof(mi355rec_playlist_query_t, max_per_group),
+                                  offsetof(mi355rec_playlist_query_t, max_per_group) + sizeof(int32_t), sizeof(mi355rec_playlist_query_t)};
+    bool known = false;
+    for (size_t e : ends) known = known || q->size == e;
+    if (!known) {
+        std::snprintf(msg, cap, "playlist query of size %u: not the end of a field of the %u bytes this library reads",
+                      static_cast<unsigned>(q->size), static_cast<unsigned>(sizeof *full));
+        return true;
+    }
+    std::memset(full, 0, sizeof *full);
+    std::memcpy(full, q, q->size);
+    if (full->flags & ~static_cast<uint32_t>(MI355REC_PQ_DIVERSE | MI355REC_PQ_CAPPED)) {
+        std::snprintf(msg, cap, "unknown flags 0x%x in a playlist query", static_cast<unsigned>(full->flags));
+        return true;
+    }
+    if ((full->flags & MI355REC_PQ_CAPPED) && !(full->flags & MI355REC_PQ_DIVERSE)) {
+        std::snprintf(msg, cap, "MI355REC_PQ_CAPPED needs MI355REC_PQ_DIVERSE");
+        return true;
+    }
+    if (full->members && full->rows) {
+        std::snprintf(msg, cap, "members by value and by row in one playlist query");
+        return true;
+    }
+    *r = request(full->members, full->rows, full->weights, full->k, full->exclude_global, full->n_exclude, full->filter, full->topn);
+    r->labels = full->labels;
+    r->n_labels = full->n_labels;
+    if (full->flags & MI355REC_PQ_DIVERSE) *r = r->diversified(full->lambda, full->pool);
+    if (full->flags & MI355REC_PQ_CAPPED) *r = r->capped_at(full->max_per_group);
+    *out = {res->out_idx, res->out_score, r->diverse ? res->out_mmr : nullptr, res->out_count, res->out_pool_rows};
     return false;
 }
 

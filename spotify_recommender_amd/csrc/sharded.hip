@@ -839,6 +839,19 @@ int mi355rec_sharded_query_playlist_topn_capped(mi355rec_sharded_t* h, const int
         {out_idx, out_score, out_mmr, out_count, out_pool_rows});
 }
 
+// PLAYLIST REQUESTS (include/mi355rec_diag.h): the family's one call on the node handle; the label set travels in the Request
+// (one handle takes it as it is, a row-sharded catalogue hands it to every shard with that shard's slice of the labels).
+int mi355rec_sharded_query_playlist_request(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
+                                            const mi355rec_playlist_result_t* result) {
+    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    mi355rec_playlist_query_t full;
+    Request r;
+    Outputs out;
+    char why[128];
+    if (mi355playlist::from_query(query, result, &full, &r, &out, why, sizeof why)) return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    return sharded_playlist(h, r, out);
+}
+
 int mi355rec_sharded_scores_row(mi355rec_sharded_t* h, int64_t global_row, float* out_host) {
     if (!h || !out_host) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     if (global_row < 0 || global_row >= h->n)

@@ -66,7 +66,7 @@ _PLAYLIST_LEVELS = ("", "_where", "_weighted", "_diverse", "_capped")   # each l
 
 
 def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=None, where=None, weights=None, level: str = None,
-                     lam=None, pool=None, max_per_group=None, return_mmr: bool = False, return_pool_rows: bool = False):
+                     lam=None, pool=None, max_per_group=None, return_mmr: bool = False, return_pool_rows: bool = False, labels=None):
     """Runs one entry point of the playlist family: `prefix`query_{mean|playlist}_topn`level`.  `members` is a (k, 12) float32
     array (by value: mean) or a 1-D int64 array of rows (by row: playlist).  `level` None: the lowest that takes the
     arguments given ("" plain, "_where" with a filter, "_weighted" with weights); "_diverse" and "_capped" are asked for.
@@ -80,7 +80,10 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
     with return_mmr a third array holds the mmr value of each pick.
     GROUP CAPS: `lam` = 1.0 is relevance order with at most `max_per_group` results per group.  With return_pool_rows the last
     element is pool_rows: fewer than `topn` ids with pool_rows == pool means the pool ran out (raise `pool`), with
-    pool_rows < pool that the catalogue has no more."""
+    pool_rows < pool that the catalogue has no more.
+    PLAYLIST REQUESTS: `labels`, a set of labels (set_labels), restricts the answer (and a diversified call's pool) to rows whose
+    label is in it; the call then goes through `prefix`query_playlist_request, the family's one struct-taking entry point.
+    None takes exactly the entry point described above."""
     if level is None:
         level = "_weighted" if weights is not None else "_where" if where is not None else ""
     rank = _PLAYLIST_LEVELS.index(level)
@@ -128,7 +131,26 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
     if capped:
         args.append(ctypes.byref(pool_rows))
     by = "playlist" if members.dtype == np.int64 else "mean"
-    check(getattr(lib, f"{prefix}query_{by}_topn{level}")(*args))
+    if labels is not None:
+        lab = _np_labels(labels)
+        q = capi.PlaylistQuery()
+        q.size = ctypes.sizeof(capi.PlaylistQuery)
+        q.flags = (capi.PQ_DIVERSE if diverse else 0) | (capi.PQ_CAPPED if capped else 0)
+        q.members, q.rows = (None, ptr(members)) if by == "playlist" else (ptr(members), None)
+        q.weights = ptr(w) if w is not None else None
+        q.exclude_global, q.n_exclude = (ptr(ex) if ex.size else None), int(ex.size)
+        q.filter = ctypes.pointer(flt) if flt is not None else None
+        q.labels, q.n_labels = ptr(lab), int(lab.size)   # (an empty set stays a non-NULL pointer: the library refuses it)
+        q.k, q.topn = k, int(topn)
+        if diverse:
+            q.lambda_, q.pool = float(lam), int(pool)
+        if capped:
+            q.max_per_group = int(max_per_group)
+        res = capi.PlaylistResult(ptr(idx), ptr(score), ptr(mmr) if diverse else None, ctypes.pointer(count),
+                                  ctypes.pointer(pool_rows))
+        check(getattr(lib, f"{prefix}query_playlist_request")(h, ctypes.byref(q), ctypes.byref(res)))
+    else:
+        check(getattr(lib, f"{prefix}query_{by}_topn{level}")(*args))
     out = (idx[:count.value].copy(), score[:count.value].copy())
     if return_mmr:
         out += (mmr[:count.value].copy(),)
@@ -494,32 +516,34 @@ class CosineEngine:
 
 
     # ---- PLAYLISTS (include/mi355rec_diag.h): top-N by the mean score against up to 32 songs ----
-    def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None) -> Tuple[np.ndarray, np.ndarray]:
+    def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
         """The best `topn` rows by the mean of their scores against the rows of `queries` (k x 12); `exclude`: global ids.
         `where`: {feature index or name: (lo, hi)}, only rows within every range are returned (FEATURE FILTERS; a
         filtered single query is k = 1); None calls the unfiltered entry point.
         `weights`: one signed float per member (WEIGHTED PLAYLISTS: score = sum w_k c_k / sum |w_k|, a negative weight is
         a dislike); None calls the entry point used without it."""
-        return self._playlist(_np_members(queries), topn, exclude, where, weights)
+        return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels)
 
-    def query_playlist_topn(self, local_rows, topn: int, exclude=None, where=None, weights=None) -> Tuple[np.ndarray, np.ndarray]:
+    def query_playlist_topn(self, local_rows, topn: int, exclude=None, where=None, weights=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
         """The same for members given as rows of this handle; the members are never returned (whatever their weight)."""
-        return self._playlist(_np_rows(local_rows), topn, exclude, where, weights)
+        return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, labels=labels)
 
-    def _playlist(self, members, topn, exclude, where, weights, level=None, **more):
+    def _playlist(self, members, topn, exclude, where, weights, level=None, labels=None, **more):
         return _playlist_family(self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), members, topn, exclude, where,
-                                weights, level, **more)
+                                weights, level, labels=labels, **more)
 
     # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h): MMR picks from the top-`pool` of the weighted playlist call ----
-    def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False):
+    def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False, labels=None):
         """`topn` rows picked greedily from the `pool` most relevant (query_mean_topn's order): each pick maximises
         lam * relevance - (1 - lam) * (its largest similarity to a row already picked).  Pick order; scores = relevance."""
-        return self._playlist(_np_members(queries), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr)
+        return self._playlist(_np_members(queries), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr,
+                              labels=labels)
 
     def query_playlist_topn_diverse(self, local_rows, topn: int, lam, pool=None, exclude=None, where=None, weights=None,
-                                    return_mmr=False):
+                                    return_mmr=False, labels=None):
         """The same for members given as rows of this handle (never returned)."""
-        return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr)
+        return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr,
+                              labels=labels)
 
     def set_groups(self, groups) -> None:
         """One group id per row (GROUP CAPS): >= 0 a group (an artist, say), -1 = never capped; None drops the groups."""
@@ -530,15 +554,17 @@ class CosineEngine:
         capi.check(self._lib.mi355rec_set_groups(self._h, g.ctypes.data_as(ctypes.c_void_p), int(g.size)), self._h)
 
     def query_mean_topn_capped(self, queries, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
-                               weights=None, return_mmr=False, return_pool_rows=False):
+                               weights=None, return_mmr=False, return_pool_rows=False, labels=None):
         """query_mean_topn_diverse with at most `max_per_group` results per group of set_groups (GROUP CAPS)."""
         return self._playlist(_np_members(queries), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
-                              max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows)
+                              max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows,
+                              labels=labels)
 
     def query_playlist_topn_capped(self, local_rows, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
-                                   weights=None, return_mmr=False, return_pool_rows=False):
+                                   weights=None, return_mmr=False, return_pool_rows=False, labels=None):
         return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
-                              max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows)
+                              max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows,
+                              labels=labels)
 
     def fetch_rows(self, local_rows) -> np.ndarray:
         """The features of the listed rows (any order, duplicates allowed), gathered on the device: (len, 12) float32."""
@@ -669,15 +695,15 @@ class NodeEngine:
                              (q.ctypes.data_as(ctypes.c_void_p), int(exclude_global)), labels, topn)
 
     # ---- PLAYLISTS (include/mi355rec_diag.h) over the whole node ----
-    def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None) -> Tuple[np.ndarray, np.ndarray]:
-        return self._playlist(_np_members(queries), topn, exclude, where, weights)
+    def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
+        return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels)
 
-    def query_playlist_topn(self, global_rows, topn: int, exclude=None, where=None, weights=None) -> Tuple[np.ndarray, np.ndarray]:
-        return self._playlist(_np_rows(global_rows), topn, exclude, where, weights)
+    def query_playlist_topn(self, global_rows, topn: int, exclude=None, where=None, weights=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
+        return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, labels=labels)
 
-    def _playlist(self, members, topn, exclude, where, weights, level=None, **more):
+    def _playlist(self, members, topn, exclude, where, weights, level=None, labels=None, **more):
         return _playlist_family(self._lib, "mi355rec_sharded_", self._h, self._check, members, topn, exclude, where, weights, level,
-                                **more)
+                                labels=labels, **more)
 
     # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h) over the whole node ----
     def set_groups(self, groups) -> None:
@@ -689,21 +715,25 @@ class NodeEngine:
         self._check(self._lib.mi355rec_sharded_set_groups(self._h, g.ctypes.data_as(ctypes.c_void_p), int(g.size)))
 
     def query_mean_topn_capped(self, queries, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
-                               weights=None, return_mmr=False, return_pool_rows=False):
+                               weights=None, return_mmr=False, return_pool_rows=False, labels=None):
         return self._playlist(_np_members(queries), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
-                              max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows)
+                              max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows,
+                              labels=labels)
 
     def query_playlist_topn_capped(self, global_rows, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
-                                   weights=None, return_mmr=False, return_pool_rows=False):
+                                   weights=None, return_mmr=False, return_pool_rows=False, labels=None):
         return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
-                              max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows)
+                              max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows,
+                              labels=labels)
 
-    def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False):
-        return self._playlist(_np_members(queries), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr)
+    def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False, labels=None):
+        return self._playlist(_np_members(queries), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr,
+                              labels=labels)
 
     def query_playlist_topn_diverse(self, global_rows, topn: int, lam, pool=None, exclude=None, where=None, weights=None,
-                                    return_mmr=False):
-        return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr)
+                                    return_mmr=False, labels=None):
+        return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr,
+                              labels=labels)
 
     def scores_row(self, global_row: int) -> np.ndarray:
         out = np.empty(self.rows, dtype=np.float32)
