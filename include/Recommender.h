@@ -144,13 +144,19 @@ public:
     // < 1 stays an error there).  With genre ids this overload is the whole family, so maxPerArtist = 0 is accepted and asks
     // for no cap: the diversified call, and with lambda = 1 the plain top-N within the genres (no pool, no re-rank).  A single song within
     // genres with a filter, diversity or a cap is the one-song playlist {songIndex}.
+    // Extension: row priors.  setPriors gives every song one float in [-1, 1] (popularity, freshness, an editorial boost; one
+    // per song, every value finite); the last argument of the general overload, priorWeight, then ranks by
+    // similarity + priorWeight * prior (|priorWeight| <= 4; negative demotes; lastScores() holds the blended values).
+    // priorWeight = 0 (the default) is the call as before.  Like genre ids, a prior weight makes the general overload the whole
+    // family: maxPerArtist = 0 then asks for no cap.  The priors reach the engine on the first call that uses them.
+    bool setPriors(const std::vector<float>& priors);
     static std::vector<int> artistGroupIds(const std::vector<std::string>& artists);
     bool setGroupIds(const std::vector<int>& groupIds);
     std::vector<int> recommendByIndexCapped(int songIndex, int topN, int maxPerArtist, float lambda = 1.0f, int pool = 0,
                                             const std::vector<FeatureRange>& where = {});
     std::vector<int> recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
                                           const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude, float lambda,
-                                          int pool, int maxPerArtist, const std::vector<int>& genreIds = {});
+                                          int pool, int maxPerArtist, const std::vector<int>& genreIds = {}, float priorWeight = 0.0f);
 
     struct Impl;   // opaque: defined in Recommender.cpp
 

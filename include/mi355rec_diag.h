@@ -26,6 +26,8 @@
  *     node-handle twins);
  *   - PLAYLIST REQUESTS: the whole playlist family as one call that takes a struct, and the only one that takes a label set
  *     (mi355rec_query_playlist_request and its node-handle twin);
+ *   - ROW PRIORS: a per-row prior (popularity, freshness, a boost or a demotion) blended into the request's ranking value
+ *     (mi355rec_set_priors, MI355REC_PQ_PRIOR and prior_weight of the request, and the node-handle twin);
  *   - test hooks, compiled in only with -DMI355REC_TEST_HOOKS (spotify_recommender_amd/build.py builds
  *     libmi355rec_testhooks.so for tests/; the product library does not export them).
  */
@@ -594,7 +596,8 @@ int mi355rec_sharded_query_playlist_topn_capped(mi355rec_sharded_t* h, const int
  *   filter           NULL, or the feature filter;         topn   results asked for;
  *   labels/n_labels  NULL / 0 (every row), or the label set, see below;
  *   flags            MI355REC_PQ_DIVERSE: lambda and pool are read (the _diverse call); MI355REC_PQ_CAPPED (with _DIVERSE only):
- *                    max_per_group is read (the _capped call).  Unknown bits: INVALID_ARG.
+ *                    max_per_group is read (the _capped call); MI355REC_PQ_PRIOR: prior_weight is read (ROW PRIORS below).
+ *                    Unknown bits (8 and above): INVALID_ARG.
  * mi355rec_playlist_result_t: out_idx (topn slots) is required; out_score (topn), out_mmr (topn; written by diversified calls
  * only), out_count and out_pool_rows (P' of a capped call, else 0) may each be NULL.
  * THE LABEL SET.  labels[0..n_labels): values in [0, MI355REC_MAX_LABELS), duplicates allowed.  With a label set a row is
@@ -615,6 +618,7 @@ int mi355rec_sharded_query_playlist_topn_capped(mi355rec_sharded_t* h, const int
  * serves the same calls. */
 #define MI355REC_PQ_DIVERSE 1u
 #define MI355REC_PQ_CAPPED 2u
+#define MI355REC_PQ_PRIOR 4u          /* ROW PRIORS below: prior_weight is read */
 typedef struct {
     uint32_t size;                    /* sizeof(mi355rec_playlist_query_t) of the caller's header */
     uint32_t flags;                   /* MI355REC_PQ_* */
@@ -631,6 +635,7 @@ typedef struct {
     float lambda;                     /* MI355REC_PQ_DIVERSE */
     int32_t pool;                     /* MI355REC_PQ_DIVERSE */
     int32_t max_per_group;            /* MI355REC_PQ_CAPPED */
+    float prior_weight;               /* MI355REC_PQ_PRIOR (offset 84, the tail padding of older headers: sizeof stays 88) */
 } mi355rec_playlist_query_t;
 typedef struct {
     int64_t* out_idx;                 /* topn slots; required */
@@ -642,6 +647,38 @@ typedef struct {
 int mi355rec_query_playlist_request(mi355rec_t* h, const mi355rec_playlist_query_t* query, const mi355rec_playlist_result_t* result);
 int mi355rec_sharded_query_playlist_request(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
                                             const mi355rec_playlist_result_t* result);
+
+/* ROW PRIORS (an extension beyond the reference, which drops the dataset's `popularity` column): a per-row prior blended
+ * into the ranking of the playlist request — popularity, freshness, an editorial boost, or a demotion (a negative weight:
+ * "surface obscure tracks").
+ * mi355rec_set_priors gives every row of the handle one fp32 (n must be the handle's row count).  Every value must be finite
+ * with |p| <= 1; otherwise the call is INVALID_ARG with a message naming the first bad row.  NULL drops the priors, a second
+ * call replaces them, a failed call leaves the previous ones.  Device cost: 4 B per row, a plain array in local row order,
+ * padded to a whole quad of four rows (one 16-byte load serves a lane's quad).  Lanes share the array as they share groups: a
+ * handle that has lanes refuses the call, a lane made afterwards shares the priors without a copy.
+ * THE CALL is mi355rec_query_playlist_request with MI355REC_PQ_PRIOR set and prior_weight = beta.  The field lies at offset
+ * 84, in what was the struct's tail padding (sizeof stays 88), and an older caller's padding bytes are garbage: it is read
+ * ONLY when the flag is set.  With the flag set the struct's `size` must cover the field, beta must be finite with
+ * |beta| <= MI355REC_MAX_PRIOR_WEIGHT, and the handle must have priors; otherwise INVALID_ARG with a message.  The twenty
+ * older entry points are unchanged.
+ * RANKING VALUE.  With s(x) the score the same request gives row x without the flag,
+ *     v(x) = fl( s(x) + fl(beta p(x)) )         fp32, multiply then add, never fused.
+ * Keys are packed from v; out_score reports v (-0.0 as +0.0); the canonical order is v descending, then row ascending; the
+ * pool of a diversified or capped call is the top-`pool` by v and rel_i = v.  Admissibility (exclusion, members, filter, label
+ * set), counts and padding are unchanged.
+ * Identities, bit for bit: the flag with beta = 0.0f is the call without the flag (same launch, same ids and score bits); all
+ * priors +0.0f is no prior; the result does not depend on shard count, placement, lane or replica mode.
+ * Device: a uniform runtime branch of playlist_scan_kernel (csrc/playlist.hip.h, "ROW PRIORS"): the priors stream with the
+ * 8-bit replica (+4 B on its 12 B per row) and enter the pre-filter's integer cut PER ROW; the exact chains add the prior with
+ * the two operations above.  Calls without a prior take none of the new branches and never read the array.
+ * Node handle: one shard forwards; a replicated placement gives every replica the whole array (a failure drops the priors on
+ * every replica); a row-sharded one gives each shard its slice and merges the shards' keys on the host as before, which is
+ * exact because keys carry v.  The CPU backend keeps a host copy and uses the same two operations.
+ * Not served: priors on the single-query, streamed, batched and label-only routes; multiplicative blends; a separate
+ * similarity output. */
+#define MI355REC_MAX_PRIOR_WEIGHT 4.0f
+int mi355rec_set_priors(mi355rec_t* h, const float* priors_host, int64_t n);
+int mi355rec_sharded_set_priors(mi355rec_sharded_t* h, const float* priors_host, int64_t n);
 
 #ifdef MI355REC_TEST_HOOKS
 /* TEST HOOK for the cross-workgroup hand-offs of the streamed scans (csrc/replica.hip.h, "hand-offs that fail

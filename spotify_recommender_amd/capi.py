@@ -45,7 +45,8 @@ class Filter(ctypes.Structure):
     _fields_ = [("active", c_uint32), ("lo", c_float * DIM), ("hi", c_float * DIM)]
 
 
-PQ_DIVERSE, PQ_CAPPED = 1, 2
+PQ_DIVERSE, PQ_CAPPED, PQ_PRIOR = 1, 2, 4
+MAX_PRIOR_WEIGHT = 4.0
 
 
 class PlaylistQuery(ctypes.Structure):
@@ -53,7 +54,7 @@ class PlaylistQuery(ctypes.Structure):
     _fields_ = [("size", c_uint32), ("flags", c_uint32), ("members", c_void_p), ("rows", c_void_p), ("weights", c_void_p),
                 ("exclude_global", c_void_p), ("filter", POINTER(Filter)), ("labels", c_void_p), ("k", c_int32),
                 ("n_exclude", c_int32), ("n_labels", c_int32), ("topn", c_int32), ("lambda_", c_float), ("pool", c_int32),
-                ("max_per_group", c_int32)]
+                ("max_per_group", c_int32), ("prior_weight", c_float)]
 
 
 class PlaylistResult(ctypes.Structure):
@@ -226,6 +227,8 @@ SIGNATURES = {
         c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]),
     "mi355rec_sharded_query_playlist_topn_capped": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_float, c_int, c_int, c_int,
         c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "mi355rec_set_priors": (c_int, [c_void_p, c_void_p, c_int64]),
+    "mi355rec_sharded_set_priors": (c_int, [c_void_p, c_void_p, c_int64]),
     "mi355rec_query_playlist_request": (c_int, [c_void_p, POINTER(PlaylistQuery), POINTER(PlaylistResult)]),
     "mi355rec_sharded_query_playlist_request": (c_int, [c_void_p, POINTER(PlaylistQuery), POINTER(PlaylistResult)]),
     "mi355rec_pack_key": (c_uint64, [c_float, c_int64]),

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cmath>
 #include <iostream>
 #include <unordered_map>
 
@@ -31,6 +32,8 @@ struct Recommender::Impl {
 
     // group ids of the songs (one per song, -1 = none; empty: not known): uploaded by the first capped query, likewise
     std::vector<int> groupIds;
+    std::vector<float> priors;       // setPriors: one per song (empty: none)
+    bool priorsUploaded = false;
     bool groupsUploaded = false;
 
     std::vector<int64_t> idxBuf;
@@ -229,6 +232,21 @@ bool Recommender::setGroupIds(const std::vector<int>& groupIds) {
     return true;
 }
 
+bool Recommender::setPriors(const std::vector<float>& priors) {
+    if (!impl_->initialized || priors.size() != static_cast<size_t>(impl_->numSongs)) {
+        std::cerr << "Error: one prior per song is needed" << std::endl;
+        return false;
+    }
+    for (size_t i = 0; i < priors.size(); ++i)
+        if (!(std::fabs(priors[i]) <= 1.0f)) {   // (NaN too)
+            std::cerr << "Error: prior " << priors[i] << " of song " << i << ": a prior is finite with |p| <= 1" << std::endl;
+            return false;
+        }
+    impl_->priors = priors;
+    impl_->priorsUploaded = false;
+    return true;
+}
+
 bool Recommender::setGenreIds(const std::vector<int>& genreIds) {
     if (!impl_->initialized || genreIds.size() != static_cast<size_t>(impl_->numSongs)) {
         std::cerr << "Error: one genre id per song is needed" << std::endl;
@@ -327,7 +345,7 @@ struct Diverse {
 // may then be null).  genres: null or empty, or the genre ids the results come from (the request call, PLAYLIST REQUESTS).
 std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& songIndices, int topN, const std::vector<int>& alsoExclude,
                                const mi355rec_filter_t* filter, const float* weights = nullptr, const Diverse* diverse = nullptr,
-                               const std::vector<int>* genres = nullptr) {
+                               const std::vector<int>* genres = nullptr, float priorWeight = 0.0f) {
     if (!impl->initialized) {
         std::cerr << "Error: Recommender not initialized" << std::endl;
         return {};
@@ -387,19 +405,35 @@ std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& 
     int64_t* const idx = impl->idxBuf.data();
     float* const score = impl->scoreBuf.data();
     int rc;
-    if (genres && !genres->empty()) {
-        if (!uploadLabels(impl)) return {};
+    const bool withGenres = genres && !genres->empty(), withPrior = priorWeight != 0.0f;   // (NaN: the engine refuses it)
+    if (withPrior && !impl->priorsUploaded) {   // the first call with a prior weight hands the songs' priors to the engine
+        if (impl->priors.size() != static_cast<size_t>(impl->numSongs)) {
+            std::cerr << "Error: the songs' priors are not known (setPriors)" << std::endl;
+            return {};
+        }
+        if (mi355rec_sharded_set_priors(impl->engine, impl->priors.data(), impl->numSongs) != MI355REC_OK) {
+            std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
+            return {};
+        }
+        impl->priorsUploaded = true;
+    }
+    if (withGenres || withPrior) {
+        if (withGenres && !uploadLabels(impl)) return {};
         mi355rec_playlist_query_t q{};
         q.size = sizeof q;
-        q.flags = (diverse ? MI355REC_PQ_DIVERSE : 0u) | (diverse && diverse->capped ? MI355REC_PQ_CAPPED : 0u);
+        q.flags = (diverse ? MI355REC_PQ_DIVERSE : 0u) | (diverse && diverse->capped ? MI355REC_PQ_CAPPED : 0u) |
+                  (withPrior ? MI355REC_PQ_PRIOR : 0u);
+        q.prior_weight = priorWeight;
         q.rows = rows.data();
         q.k = k;
         q.weights = weights;
         q.exclude_global = excl.data();
         q.n_exclude = nExcl;
         q.filter = filter;
-        q.labels = genres->data();
-        q.n_labels = static_cast<int32_t>(genres->size());
+        if (withGenres) {
+            q.labels = genres->data();
+            q.n_labels = static_cast<int32_t>(genres->size());
+        }
         q.topn = topN;
         if (diverse) {
             q.lambda = diverse->lambda;
@@ -435,7 +469,7 @@ std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& 
 // the filter (none for no ranges) and the query.
 std::vector<int> weightedPlaylistQuery(Recommender::Impl* impl, const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
                                        bool orNone, const std::vector<Recommender::FeatureRange>& where, const std::vector<int>& alsoExclude,
-                                       const Diverse* diverse = nullptr, const std::vector<int>* genres = nullptr) {
+                                       const Diverse* diverse = nullptr, const std::vector<int>* genres = nullptr, float priorWeight = 0.0f) {
     if (!(orNone && weights.empty()) && weights.size() != songIndices.size()) {
         std::cerr << "Error: " << weights.size() << " weights for " << songIndices.size() << " songs (one weight per song"
                   << (orNone ? ", or none" : "") << ")" << std::endl;
@@ -444,7 +478,7 @@ std::vector<int> weightedPlaylistQuery(Recommender::Impl* impl, const std::vecto
     mi355rec_filter_t f;
     if (!makeFilter(where, f)) return {};
     return playlistQuery(impl, songIndices, topN, alsoExclude, where.empty() ? nullptr : &f, weights.empty() ? nullptr : weights.data(),
-                         diverse, genres);
+                         diverse, genres, priorWeight);
 }
 
 }  // namespace
@@ -474,13 +508,13 @@ std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songI
 
 std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
                                                    const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude, float lambda,
-                                                   int pool, int maxPerArtist, const std::vector<int>& genreIds) {
-    // Within genres maxPerArtist 0 asks for no cap: the diversified call, and with lambda 1, whose picks are the pool's first
-    // topN in order for any pool, the plain request (no pool, no re-rank launch).
-    const bool uncapped = maxPerArtist == 0 && !genreIds.empty();
+                                                   int pool, int maxPerArtist, const std::vector<int>& genreIds, float priorWeight) {
+    // Within genres (or with a prior weight) maxPerArtist 0 asks for no cap: the diversified call, and with lambda 1, whose
+    // picks are the pool's first topN in order for any pool, the plain request (no pool, no re-rank launch).
+    const bool uncapped = maxPerArtist == 0 && (!genreIds.empty() || priorWeight != 0.0f);
     const Diverse d{lambda, pool, maxPerArtist, !uncapped};
     return weightedPlaylistQuery(impl_, songIndices, topN, weights, true, where, alsoExclude, uncapped && lambda == 1.0f ? nullptr : &d,
-                                 &genreIds);
+                                 &genreIds, priorWeight);
 }
 
 std::vector<int> Recommender::recommendByIndexCapped(int songIndex, int topN, int maxPerArtist, float lambda, int pool,

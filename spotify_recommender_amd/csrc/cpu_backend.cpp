@@ -262,6 +262,8 @@ struct Node {
     bool has_labels = false;
     std::vector<int32_t> groups;          // mi355rec_sharded_set_groups: one per row, -1 = ungrouped
     bool has_groups = false;
+    std::vector<float> priors;            // mi355rec_sharded_set_priors: one per row
+    bool has_priors = false;
 };
 
 Node* node_create(const float* feats_rowmajor, int64_t n) {
@@ -351,6 +353,26 @@ int node_set_groups(Node* h, const int32_t* groups, int64_t n, const char** why)
     return MI355REC_OK;
 }
 
+int node_set_priors(Node* h, const float* priors, int64_t n, const char** why) {
+    if (!priors) {
+        h->priors.clear();
+        h->has_priors = false;
+        return MI355REC_OK;
+    }
+    if (n != rows(h->cat)) {
+        *why = "the prior count must equal the catalogue's rows";
+        return MI355REC_ERR_INVALID_ARG;
+    }
+    try {
+        h->priors.assign(priors, priors + n);
+    } catch (const std::bad_alloc&) {
+        *why = "out of host memory";
+        return MI355REC_ERR_OUT_OF_MEMORY;   // (the previous priors stay)
+    }
+    h->has_priors = true;
+    return MI355REC_OK;
+}
+
 int node_query_labels(Node* h, const float* q12, int64_t exclude, const int32_t* set, int n_set, int topn_asked,
                       int64_t* out_idx, float* out_score, int* out_count, const char** why) {
     if (topn_asked <= 0) {
@@ -394,6 +416,14 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
         *why = "this handle has no labels (mi355rec_sharded_set_labels)";
         return MI355REC_ERR_INVALID_ARG;
     }
+    if (r.prior && !h->has_priors) {   // "ROW PRIORS"
+        *why = "this handle has no priors (mi355rec_sharded_set_priors)";
+        return MI355REC_ERR_INVALID_ARG;
+    }
+    // v = fl(score + fl(beta p)): multiply, round, add, round (-ffp-contract=off); beta == 0 is the call without a prior
+    const bool prior = r.prior && r.prior_weight != 0.0f;
+    const float beta = r.prior_weight;
+    const float* pri = prior ? h->priors.data() : nullptr;
     const Catalogue* c = h->cat;
     const int64_t n = c->n;
     std::vector<float> qn(static_cast<size_t>(k));
@@ -423,7 +453,12 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
             const float term = w[static_cast<size_t>(m)] * score(members + m * kDim, qn[static_cast<size_t>(m)], f + i * kDim);
             sum = sum + term;
         }
-        keys[static_cast<size_t>(i)] = pack(sum / wsum, static_cast<uint32_t>(i));
+        float v = sum / wsum;
+        if (prior) {
+            const float b = beta * pri[i];
+            v = v + b;
+        }
+        keys[static_cast<size_t>(i)] = pack(v, static_cast<uint32_t>(i));
     }
     for (int64_t e : excl)
         if (e >= 0 && e < n) keys[static_cast<size_t>(e)] = 0;   // (a real key is never 0: its low half is ~row)

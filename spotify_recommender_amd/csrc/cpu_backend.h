@@ -73,6 +73,8 @@ int node_query_mean_diverse(Node* h, const mi355playlist::Request& r, const mi35
 // request makes node_query_mean_diverse the capped call: a row is eligible while fewer than max_per_group picked
 // rows share its group; the loop ends when nothing is eligible; *out_pool_rows = P'.
 int node_set_groups(Node* h, const int32_t* groups, int64_t n, const char** why);
+// ROW PRIORS: one fp32 per row, already checked by the caller (finite, |p| <= 1); null drops them.
+int node_set_priors(Node* h, const float* priors, int64_t n, const char** why);
 int node_set_window(Node* h, int window, const char** why);
 int node_enqueue(Node* h, const float* q12, int64_t exclude, int topn, int64_t* ticket, const char** why);
 int node_flush(Node* h);

@@ -35,6 +35,45 @@ using mi355playlist::Outputs;
 using mi355playlist::Request;
 using mi355playlist::request;
 
+// The priors a handle answers from (its own, or its group's of lanes): "ROW PRIORS".
+const float* priors_of(const mi355rec* h) { return h->shared ? h->shared->d_priors : h->d_priors; }
+
+// mi355rec_set_priors.  `group_ok`: as for the labels and the groups: the node handle may replace the priors under its own
+// lanes.  The device array is padded with +0.0f to a whole quad (playlist_scan_kernel loads a quad's four priors at once).
+int set_priors_common(mi355rec* h, const float* priors_host, int64_t n, bool group_ok) {
+    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    if (!group_ok && h->shared && (h->is_lane || h->shared->refs.load() > 1))
+        return fail(h, MI355REC_ERR_INVALID_ARG, "the handle has lanes: set the priors before the first lane is made");
+    float* fresh = nullptr;
+    DeviceGuard guard(h->device);
+    if (priors_host) {
+        if (n != h->n) return fail(h, MI355REC_ERR_INVALID_ARG, "%lld priors for a handle of %lld rows", (long long)n, (long long)h->n);
+        const int64_t bad = mi355playlist::first_bad_prior(priors_host, n);
+        if (bad >= 0)
+            return fail(h, MI355REC_ERR_INVALID_ARG, "prior %g of row %lld: a prior is finite with |p| <= 1",
+                        static_cast<double>(priors_host[bad]), (long long)bad);
+        // (an empty shard keeps a one-quad array: "has priors" is a non-null pointer)
+        const size_t padded = static_cast<size_t>(n > 0 ? (n + 3) / 4 * 4 : 4);
+        hipError_t e = hipMalloc(&fresh, sizeof(float) * padded);
+        if (e == hipSuccess) e = hipMemset(fresh, 0, sizeof(float) * padded);
+        if (e == hipSuccess && n > 0) e = hipMemcpy(fresh, priors_host, sizeof(float) * static_cast<size_t>(n), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {   // the previous priors stay
+            if (fresh) (void)hipFree(fresh);
+            (void)hipGetLastError();
+            return fail(h, e == hipErrorOutOfMemory ? MI355REC_ERR_OUT_OF_MEMORY : MI355REC_ERR_HIP, "the priors (%lld rows): %s",
+                        (long long)n, hipGetErrorString(e));
+        }
+    }
+    float* old = const_cast<float*>(priors_of(h));
+    if (old) {
+        (void)hipStreamSynchronize(h->stream);   // (only the synchronous calls on this stream read them)
+        (void)hipFree(old);
+    }
+    h->d_priors = fresh;
+    if (h->shared) h->shared->d_priors = fresh;
+    return MI355REC_OK;
+}
+
 constexpr int kPlMinTilesPerWg = 8;   // with the pre-filter: a workgroup scans >= 8 tiles (its anchor bound paid for, its own threshold tight)
 
 void free_playlist(mi355rec_playlist* P) {
@@ -118,6 +157,13 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, int* eff_out
         std::memcpy(b->label_mask, mask.w, sizeof b->label_mask);
         if (selected < avail) avail = selected;
     }
+    // the prior ("ROW PRIORS"): checked whenever the request carries one; beta == 0 then launches exactly the call without it
+    const float* pri = nullptr;
+    if (r.prior) {
+        pri = priors_of(h);
+        if (!pri) return fail(h, MI355REC_ERR_INVALID_ARG, "this handle has no priors (mi355rec_set_priors)");
+        if (r.prior_weight == 0.0f) pri = nullptr;
+    }
     ++h->playlist_queries;
     const int eff = static_cast<int64_t>(r.scan_topn()) < avail ? r.scan_topn() : static_cast<int>(avail);
     if (eff <= 0) return MI355REC_OK;   // nothing left to return: nothing to launch
@@ -128,6 +174,8 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, int* eff_out
     arg.active = r.filter ? r.filter->active : 0u;
     arg.wsum = r.weights ? mi355weights::sum_abs(r.weights, k) : static_cast<float>(k);
     arg.labelled = L ? 1 : 0;
+    arg.prior = pri ? 1 : 0;
+    arg.prior_weight = pri ? r.prior_weight : 0.0f;
     for (int m = 0; m < k; ++m) b->weights[m] = r.weights ? r.weights[m] : 1.0f;
     if (arg.active) {
         std::memcpy(b->lo, r.filter->lo, sizeof b->lo);
@@ -153,7 +201,7 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, int* eff_out
                  h->stream, h->d_feats, q8, h->n, h->row_base, static_cast<const PlaylistBuf*>(P->d_buf), arg,
                  static_cast<const float*>(h->d_anchor), eff, h->d_block_lists, P->d_exact,
                  reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr)),
-                 reinterpret_cast<const uint2*>(L ? L->d_row_labels : nullptr));
+                 reinterpret_cast<const uint2*>(L ? L->d_row_labels : nullptr), reinterpret_cast<const float4*>(pri));
     HIP_TRY(h, hipGetLastError());
     *eff_out = eff;
     *grid_out = grid;
@@ -213,6 +261,7 @@ namespace mi355node {
 int query_playlist(mi355rec_t* h, const mi355playlist::Request& r, const mi355playlist::Outputs& out) {
     return sync_playlist_query(h, r, out, kPlExcludeCap);
 }
+int set_group_priors(mi355rec_t* h, const float* priors_host, int64_t n) { return set_priors_common(h, priors_host, n, true); }
 }  // namespace mi355node
 
 extern "C" {
@@ -266,6 +315,9 @@ int mi355rec_query_playlist_request(mi355rec_t* h, const mi355rec_playlist_query
     if (mi355playlist::from_query(query, result, &full, &r, &out, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
     return sync_playlist_query(h, r, out);
 }
+
+// "ROW PRIORS"
+int mi355rec_set_priors(mi355rec_t* h, const float* priors_host, int64_t n) { return set_priors_common(h, priors_host, n, false); }
 
 int mi355rec_playlist_counters(const mi355rec_t* h, int64_t* queries, int64_t* rows_exact) {
     if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");

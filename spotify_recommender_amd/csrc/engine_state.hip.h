@@ -102,6 +102,7 @@ struct mi355rec {
         float margin_mix = 0.0f, margin_mfma = 0.0f;   // of the replicas above (half_selfcheck_kernel's verdict)
         mi355rec_labels* labels = nullptr;             // the labels of the group (set before its first lane was made)
         int32_t* d_groups = nullptr;                   // the group ids of the group's rows (mi355rec_set_groups), likewise
+        float* d_priors = nullptr;                     // the priors of the group's rows (mi355rec_set_priors), likewise
     };
     SharedRows* shared = nullptr;
     bool is_lane = false;
@@ -113,6 +114,8 @@ struct mi355rec {
     int64_t label_rows_scanned = 0;     // ... and the rows their launches scanned (whole tiles)
     // GROUP CAPS (mi355rec_set_groups): one int32 per row in local row order, -1 = ungrouped; owned like the labels
     int32_t* d_groups = nullptr;
+    // ROW PRIORS (mi355rec_set_priors): one fp32 per row in local row order, padded to a whole quad; owned like the labels
+    float* d_priors = nullptr;
     // PLAYLISTS (mi355rec_query_mean_topn / _query_playlist_topn): allocated by the first call, owned by the handle (lanes have their own)
     mi355rec_playlist* playlist = nullptr;
     int64_t playlist_queries = 0;

@@ -17,11 +17,14 @@
 //       P most similar songs; extension; usable with --where, --dislike, --weights; with --genre in the --playlist mode only)
 //   ... --song, --id and --playlist with --max-per-artist M: at most M results per primary artist (extension; combines with
 //       --where, --dislike, --weights, --diverse and --pool; with --genre in the --playlist mode only)
+//   ... --playlist with --priors FILE --prior-weight BETA: rank by similarity + BETA x prior (extension; FILE holds one float in
+//       [-1, 1] per line, in catalogue order; usable with every other option of the --playlist mode)
 //   ... --playlist with --dislike "<track_id>,..." [--dislike-weight W] [--weights "w,w,..."]: weighted playlists (extension):
 //       the disliked songs push results away (weight -W, default 0.5), --weights gives the playlist's songs their own weights
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
 #include <map>
 #include <string>
@@ -57,7 +60,10 @@ static void usage(const char* prog) {
               << "Playlists within genres (extension): " << prog << " --playlist \"id,id,...\" --genre NAME [--genre NAME ...]\n"
               << "   with any of --where, --dislike, --weights, --diverse, --pool, --max-per-artist: only songs of those genres.\n"
               << "   With --song / --id, --genre does not combine with --where, --diverse or --max-per-artist: use\n"
-              << "   --playlist <one id> --genre ... for those combinations.\n" << std::endl;
+              << "   --playlist <one id> --genre ... for those combinations.\n"
+              << "Row priors (extension): " << prog << " --playlist \"id,id,...\" --priors FILE --prior-weight BETA, with any other\n"
+              << "   --playlist option: ranks by similarity + BETA x prior (BETA in [-4, 4]; negative demotes).  FILE holds one number in\n"
+              << "   [-1, 1] per line, one line per song in the order of songs_data.bin (a popularity column scaled to [0, 1], say).\n" << std::endl;
 }
 
 // --where NAME=LO:HI, any number of times from argv[first]: the ranges (feature indices in Song.h order).  false, with a
@@ -401,8 +407,74 @@ static bool parseTaste(int argc, char* argv[], int first, Taste& taste) {
     return true;
 }
 
+// --priors FILE --prior-weight BETA of a --playlist call (row priors).
+struct PriorOpt {
+    bool on = false;
+    std::string file;
+    float weight = 0.0f;
+};
+
+// false, with a message, on a malformed option or one without the other.
+static bool parsePrior(int argc, char* argv[], int first, PriorOpt& pr) {
+    bool haveWeight = false;
+    for (int i = first; i < argc; ++i) {
+        const bool file = std::strcmp(argv[i], "--priors") == 0, weight = std::strcmp(argv[i], "--prior-weight") == 0;
+        if (!file && !weight) continue;
+        if (i + 1 >= argc) {
+            std::cerr << "Error: " << argv[i] << " needs a value" << std::endl;
+            return false;
+        }
+        const std::string arg = argv[++i];
+        if (file) {
+            pr.file = arg;
+            continue;
+        }
+        char* end = nullptr;
+        pr.weight = std::strtof(arg.c_str(), &end);
+        haveWeight = true;
+        if (arg.empty() || *end != '\0' || !(pr.weight >= -4.0f && pr.weight <= 4.0f)) {   // (NaN too)
+            std::cerr << "Error: --prior-weight '" << arg << "': BETA must be a number in [-4, 4]" << std::endl;
+            return false;
+        }
+    }
+    if (haveWeight != !pr.file.empty()) {
+        std::cerr << "Error: --priors FILE and --prior-weight BETA go together" << std::endl;
+        return false;
+    }
+    pr.on = haveWeight;
+    return true;
+}
+
+// The priors file: one number per line (blank lines skipped), `songs` of them.  false, with a message, otherwise.
+static bool readPriors(const std::string& path, size_t songs, std::vector<float>& priors) {
+    std::ifstream in(path);
+    if (!in) {
+        std::cerr << "Error: cannot open the priors file '" << path << "'" << std::endl;
+        return false;
+    }
+    std::string line;
+    for (size_t lineNo = 1; std::getline(in, line); ++lineNo) {
+        const size_t a = line.find_first_not_of(" \t\r");
+        if (a == std::string::npos) continue;
+        const std::string field = line.substr(a, line.find_last_not_of(" \t\r") - a + 1);
+        char* end = nullptr;
+        const float v = std::strtof(field.c_str(), &end);
+        if (*end != '\0') {
+            std::cerr << "Error: " << path << " line " << lineNo << ": not a number: '" << field << "'" << std::endl;
+            return false;
+        }
+        priors.push_back(v);
+    }
+    if (priors.size() != songs) {
+        std::cerr << "Error: " << path << " holds " << priors.size() << " priors for " << songs << " songs (one per line, in catalogue order)"
+                  << std::endl;
+        return false;
+    }
+    return true;
+}
+
 static bool playlistMode(const std::string& list, int topN, const std::vector<Recommender::FeatureRange>& ranges, const Taste& taste,
-                         const DiverseOpt& dv, const std::vector<std::string>& genres) {
+                         const DiverseOpt& dv, const std::vector<std::string>& genres, const PriorOpt& pr) {
     std::cout << "=== PLAYLIST MODE ===" << std::endl;
     std::vector<std::string> ids = splitList(list);
     if (ids.empty()) {
@@ -452,10 +524,16 @@ static bool playlistMode(const std::string& list, int topN, const std::vector<Re
         std::cout << std::endl;
         if (!recommender.setGenreIds(catalogue.genreIds)) return false;
     }
-    const std::vector<int> recs = !genreIds.empty()   // (the general overload: lambda 1 without a cap is the plain request)
+    if (pr.on) {
+        std::vector<float> priors;
+        if (!readPriors(pr.file, catalogue.size(), priors) || !recommender.setPriors(priors)) return false;
+        std::cout << "Prior weight: " << pr.weight << " (" << pr.file << ")" << std::endl;
+    }
+    const bool blended = pr.on && pr.weight != 0.0f;   // (BETA 0 is the call without a prior)
+    const std::vector<int> recs = !genreIds.empty() || blended   // (the general overload: lambda 1 without a cap is the plain request)
                                       ? recommender.recommendForPlaylist(members, topN, taste.weighted ? weights : std::vector<float>(), ranges,
                                                                          {}, dv.on ? dv.lambda : 1.0f, dv.on ? dv.pool : 0, dv.maxPerArtist,
-                                                                         genreIds)
+                                                                         genreIds, blended ? pr.weight : 0.0f)
                                   : dv.maxPerArtist > 0
                                       ? recommender.recommendForPlaylist(members, topN, taste.weighted ? weights : std::vector<float>(), ranges,
                                                                          {}, dv.lambda, dv.pool, dv.maxPerArtist)
@@ -582,7 +660,9 @@ int main(int argc, char* argv[]) {
             }
             genres.push_back(argv[++i]);
         }
-        return playlistMode(argv[2], topN, ranges, taste, dv, genres) ? 0 : 1;
+        PriorOpt pr;
+        if (!parsePrior(argc, argv, 3, pr)) return 1;
+        return playlistMode(argv[2], topN, ranges, taste, dv, genres, pr) ? 0 : 1;
     }
     std::cerr << "Error: Unknown mode '" << mode << "'" << std::endl;
     usage(argv[0]);

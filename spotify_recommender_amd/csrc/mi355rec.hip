@@ -94,6 +94,7 @@ void mi355rec_destroy(mi355rec_t* h) {
     if (h->owned_feats && !h->shared) (void)hipFree(h->owned_feats);
     if (!h->shared) free_labels(h->labels);
     if (!h->shared && h->d_groups) (void)hipFree(h->d_groups);
+    if (!h->shared && h->d_priors) (void)hipFree(h->d_priors);
     free_playlist(h->playlist);
     if (h->d_block_lists) (void)hipFree(h->d_block_lists);
     if (h->d_lone_ctr) (void)hipFree(h->d_lone_ctr);
@@ -123,6 +124,7 @@ void mi355rec_destroy(mi355rec_t* h) {
             if (b) (void)hipFree(b);
         free_labels(h->shared->labels);
         if (h->shared->d_groups) (void)hipFree(h->shared->d_groups);
+        if (h->shared->d_priors) (void)hipFree(h->shared->d_priors);
         delete h->shared;
     }
     delete h;
@@ -225,6 +227,7 @@ int mi355rec_create_lane(mi355rec_t* parent, mi355rec_t** out) {
         group->margin_mfma = parent->margin_mfma;
         group->labels = parent->labels;   // (a lane made after mi355rec_set_labels shares them: nothing is copied)
         group->d_groups = parent->d_groups;   // (mi355rec_set_groups: likewise)
+        group->d_priors = parent->d_priors;   // (mi355rec_set_priors: likewise)
     }
     parent->shared->refs.fetch_add(1);
     lane->shared = parent->shared;

@@ -40,6 +40,8 @@ int rerank_pool(mi355rec_t* h, const int64_t* pool_idx, const float* pool_score,
                 int max_per_group = 0, int* out_pool_rows = nullptr);
 // mi355rec_set_groups for a handle whose group of lanes the caller has to itself (as set_group_labels).
 int set_group_groups(mi355rec_t* h, const int32_t* groups_host, int64_t n);
+// mi355rec_set_priors for a handle whose group of lanes the caller has to itself (as set_group_labels).
+int set_group_priors(mi355rec_t* h, const float* priors_host, int64_t n);
 }  // namespace mi355node
 
 namespace {
@@ -203,6 +205,9 @@ struct mi355rec_sharded {
     // groups to the re-rank by value; one shard and a replicated placement give the array to their engines instead.
     std::vector<int32_t> groups;
     bool has_groups = false;
+    // ROW PRIORS (mi355rec_sharded_set_priors): the engines hold the arrays (every replica the whole one, every shard of a
+    // row-sharded placement its slice); the node only remembers that they do.
+    bool has_priors = false;
     bool replicated = false;            // every "shard" holds all rows (mi355rec_create_placed, MI355REC_PLACEMENT_REPLICATED)
     int next_replica = 0;               // whose turn the next synchronous call is (replicated)
     std::vector<hipEvent_t> r_merged;   // replicated: [kStreamDepth][replicas] "this window's results are in host memory",

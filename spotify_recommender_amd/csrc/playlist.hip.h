@@ -88,6 +88,44 @@
 // excluded rows bounds the answer) keeps every workgroup's threshold and the shared atomicMax valid.  labelled == 0 takes
 // none of these branches (uniform tests) and never reads `labels`.
 //
+// ROW PRIORS (include/mi355rec_diag.h, "ROW PRIORS").  PlaylistArg::prior (uniform), PlaylistArg::prior_weight = beta and
+// `priors`, one fp32 p(x) per row in local row order (|p| <= 1, |beta| <= 4: checked by the host; the array is padded to whole
+// quads).  The ranking value of a row is
+//     v(x) = fl( score(x) + fl(beta p(x)) )                              (fp32, multiply THEN add: fp contract is off)
+// and every key, every workgroup threshold and shared_thr is a key of v.  The rule above (the k-th best among ANY k admissible
+// rows bounds the answer) does not care what the ranking value is, so the thresholds stay valid.
+//   * exact path, 0x80 rows, survivors of the pre-filter: the chain loop reloads the row's prior (4 B, an L2 hit: four priors
+//     are not kept live across the loop) and forms v with exactly those two operations;
+//   * anchors: the anchor table still only CHOOSES rows (by similarity alone); the rows read from the matrix get their prior
+//     added before the starting threshold is taken, so that threshold is a key of v;
+//   * pre-filter: per tile a lane loads its quad's four priors as one 16-byte load (the quad clamped as load_q8 clamps it,
+//     issued with the next tile's replica load) and a row is ruled out iff
+//         |u| approx < T - margin_prior - fl(beta p(x)),       margin_prior = margin_mean + kPlPriorUlps kPlUlp,
+//     T the threshold's v.  The test is an integer compare D < cut(x) against a PER-ROW cut (one launch-wide max(beta p) would
+//     send 2 - 95 % of the rows to the chains).  With S = 127 * 32000 / |u| (kQ8DotScale / |u|):
+//         base = fl( fl( fl(T - margin_prior) / |u| ) kQ8DotScale )      (refreshed whenever the threshold moves; -inf: none yet)
+//         bs   = fl( fl(beta kQ8DotScale) / |u| )                        (once per launch)
+//         cut(x) = int( clamp( fl(base - fl(p(x) bs)), -2^30, 2^30 ) ) - 1
+//     one multiply, one subtract, one clamp and one convert per row.  The clamp comes AFTER the subtraction, on the float:
+//     base and p bs may each be huge (|u| down to 1e-3: 2e10) while their difference is what matters; |D| < 4.2e6, so a cut
+//     clamped at +-2^30 decides as the unclamped one does and the convert cannot overflow.  The int conversion truncates
+//     towards zero (off by < 1 upwards for a negative value): the - 1 puts the cut at or below the float again.  T may lie
+//     anywhere in [-5, 5] now, so q8_threshold's clamp of the quotient at +-2 (right for |T| <= 1: it only ever lowers a cut
+//     that rules every row out anyway) is NOT used here: with beta p = 4 and T = 4.5 it would leave a cut of -2 |u| and no
+//     row ruled out.
+//     Why margin_prior suffices: score(x) <= |u| approx + margin_mean (above), b = fl(beta p(x)) is the very value v adds, and
+//     in units of the score (a D-unit is |u| / kQ8DotScale) with ulp = 2^-24 relative:
+//       - v = fl(score + b): one rounding of a sum of magnitude <= 5: 5 ulp;
+//       - base against (T - margin_prior) kQ8DotScale / |u|: a subtract, a divide, a multiply of a quantity <= 5.01: 16 ulp;
+//       - fl(p bs) against b kQ8DotScale / |u|: beta kQ8DotScale, the divide, the product, and b's own rounding, of a
+//         quantity <= 4: 16 ulp;
+//       - the subtraction base - p bs: one rounding of a difference whose operands are <= 5.01 and 4: 10 ulp;
+//     47 ulp: kPlPriorUlps = 96 covers it with room (5.7e-6; |u| M is 1e-5 and more).  So a row with D < cut(x) has
+//     v(x) < T.  tests/test_prior_margin.py checks this with a numpy model of exactly this arithmetic against the oracle (beta
+//     = +-4, +-2^-20, 0.25; p = +-1, 0, tiny, skewed; |u| near 1e-3; T negative and above 1) and that the bound is not
+//     vacuous (at most 5 % of 65 537 rows survive at the true threshold; the real-number model gives 1.21 %).
+// prior == 0 takes none of these branches (uniform tests) and never reads `priors`.
+//
 // EXCLUSION.  The excluded global ids (members and the caller's list, sorted and deduplicated on the host, at most
 // kPlExcludeCap) sit in LDS as uint32; only a key that already beats the workgroup's threshold is looked up (binary
 // search), so the hot loop does not change.
@@ -112,6 +150,8 @@ constexpr int kPlBoundRows = 256;                           // anchor rows a wor
 constexpr float kPlChainErr = 4e-6f;                        // |c_k - u^_k . x^| (see above)
 constexpr float kPlUlp = 5.9604645e-8f;                     // 2^-24
 constexpr float kPlMinMeanNorm = 1e-3f;                     // |u| below this: the pre-filter is off
+constexpr float kPlPriorUlps = 96.0f;                       // margin_prior - margin_mean, in kPlUlp (see ROW PRIORS above)
+constexpr float kPlCutClamp = 1073741824.0f;                // 2^30: a per-row cut beyond it decides as the clamped one (|D| < 4.2e6)
 using PlaylistCfg = Q8Cfg<512, 4, 1>;                       // kBlock, kMinWaves (two workgroups per CU); tiles of 2048 rows
 
 // One call's inputs on the device (written by the host before the launch).
@@ -133,6 +173,8 @@ struct PlaylistArg {
     uint32_t active;  // the feature filter: bit j (j < kDim) constrains feature j; 0: no filter
     float wsum;       // W = fl(sum_k |w_k|) in member order (the host's fp32 sum; K for an unweighted call)
     int labelled;     // 1: only rows whose label is in PlaylistBuf::label_mask are admissible; 0: no label set
+    float prior_weight;   // beta (read only where `prior`): v = fl(score + fl(beta p(x)))
+    int prior;        // 1: rank by v, p from the kernel's `priors`; 0: rank by the score alone (`priors` is never read)
 };
 
 // Is label l (int16 of the row-order array: -1 = unlabelled or padding) in the set?
@@ -194,11 +236,12 @@ __device__ __forceinline__ bool playlist_excluded(const uint32_t* s_excl, int n_
 // q8: the handle's 8-bit replica, or null (every row exact).  anchors: the anchor table, or null (no starting threshold).
 // rows_exact: += the rows whose K chains this launch computed; with a filter, every fp32 row read (rejected ones included).
 // labels: the shard's labels in row order, four int16 to a quad (read only where arg.labelled).
+// priors: the shard's priors in row order, four fp32 to a quad (read only where arg.prior).
 __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void playlist_scan_kernel(
     const float* __restrict__ feats, const uint4* __restrict__ q8, int64_t n, int64_t row_base, const PlaylistBuf* __restrict__ buf,
     PlaylistArg arg, const float* __restrict__ anchors, int topk, uint64_t* __restrict__ block_lists,
     unsigned long long* __restrict__ rows_exact, unsigned long long* __restrict__ shared_thr /* &buf->shared_thr */,
-    const uint2* __restrict__ labels) {
+    const uint2* __restrict__ labels, const float4* __restrict__ priors) {
     constexpr int kBlock = PlaylistCfg::kBlock;
     static_assert(PlaylistCfg::kCandCap >= kAnchorRows / 2 && PlaylistCfg::kCandCap * 2 >= kPlBoundRows, "LDS reuse below");
     __shared__ uint64_t s_cand[PlaylistCfg::kCandCap];
@@ -222,6 +265,9 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     const float wsum = arg.wsum;
     const bool labelled = arg.labelled != 0;
     const int16_t* const row_label = reinterpret_cast<const int16_t*>(labels);
+    const bool prior = arg.prior != 0;
+    const float beta = arg.prior_weight;
+    const float* const row_prior = reinterpret_cast<const float*>(priors);
     const float* const f_lo = buf->lo;
     const float* const f_hi = buf->hi;
 
@@ -259,6 +305,8 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     const Q8Query hq = q8_query(u, un);
     const bool prefilter = q8 != nullptr && s_ok != 0 && hq.ok && un >= kPlMinMeanNorm;   // uniform (false for a NaN |u|)
     const float margin_mean = un * hq.margin + kPlChainErr + static_cast<float>(3 * k + 32) * kPlUlp;
+    const float margin_prior = margin_mean + kPlPriorUlps * kPlUlp;
+    const float prior_scale = (beta * kQ8DotScale) / un;   // bs (only used where prior && prefilter: |u| >= kPlMinMeanNorm then)
     int n_exact = 0;   // rows whose K chains this thread computed
     uint64_t thr = 0;
 
@@ -306,7 +354,8 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
         if (tid < picked) {
             const int64_t row = anchor_row(n, s_pick[tid]);
             const Row x = load_row(feats, row);   // from the matrix
-            const float m = playlist_mean(s_mem, s_qn, s_w, wsum, k, x);
+            float m = playlist_mean(s_mem, s_qn, s_w, wsum, k, x);
+            if (prior) m = m + beta * row_prior[row];   // (uniform) v: multiply, round, add, round
             ++n_exact;
             const uint32_t g = static_cast<uint32_t>(row_base + row);
             key = playlist_excluded(s_excl, n_excl, g) || (active && !filter_pass(x, active, f_lo, f_hi)) ||
@@ -341,7 +390,15 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
             cut_d = q8_threshold((t - margin_mean) / un);
         }
     };
-    refresh_cut();
+    float cut_base = -__builtin_inff();   // ROW PRIORS: the part of the per-row cut that moves with the threshold (-inf: no threshold yet)
+    auto refresh_prior_cut = [&]() {
+        if (thr != 0ull) {   // uniform
+            const float t = ordered_to_score(static_cast<uint32_t>(thr >> 32));
+            cut_base = ((t - margin_prior) / un) * kQ8DotScale;
+        }
+    };
+    if (prior && prefilter) refresh_prior_cut();   // uniform
+    else refresh_cut();
     int compact_at = 2 * topk > 256 ? 2 * topk : 256;
     if (compact_at > kCandLimit) compact_at = kCandLimit;
 
@@ -358,17 +415,26 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
         quad = quad < n_quads ? quad : n_quads - 1;
         return labels[quad];
     };
+    auto load_priors = [&](int64_t t) {   // the quad's four priors, 16 bytes (the quad clamped as in load_q8)
+        int64_t quad = t * kBlock + tid;
+        quad = quad < n_quads ? quad : n_quads - 1;
+        return priors[quad];
+    };
     HalfTile cur;
     cur.t0 = cur.t1 = cur.t2 = make_uint4(0u, 0u, 0u, 0u);
     if (prefilter) load_q8(cur, blockIdx.x);
     uint2 lab_cur = make_uint2(0u, 0u);
     if (labelled) lab_cur = load_labels(blockIdx.x);
+    float4 pri_cur = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (prior && prefilter) pri_cur = load_priors(blockIdx.x);   // (the exact path reloads a row's prior in the chain loop)
 
     for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {   // uniform
         HalfTile nxt = cur;
         if (prefilter) load_q8(nxt, t + gridDim.x);   // the next tile is in flight while this one is scored
         uint2 lab_nxt = lab_cur;
         if (labelled) lab_nxt = load_labels(t + gridDim.x);   // (uniform) ... and so are its labels
+        float4 pri_nxt = pri_cur;
+        if (prior && prefilter) pri_nxt = load_priors(t + gridDim.x);   // (uniform) ... and its priors
         const int64_t quad = t * kBlock + tid;
         const int64_t r0 = quad * 4;
         uint32_t mask = 0u;
@@ -387,9 +453,19 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
             int a[4];
             bool special[4];
             q8_dot4(hq, cur, a, special);
+            if (!prior) {   // uniform
 #pragma unroll
-            for (int u4 = 0; u4 < 4; ++u4)
-                if (!(special[u4] || a[u4] >= cut_d)) mask &= ~(1u << u4);
+                for (int u4 = 0; u4 < 4; ++u4)
+                    if (!(special[u4] || a[u4] >= cut_d)) mask &= ~(1u << u4);
+            } else {   // the per-row cut (ROW PRIORS above): multiply, subtract, clamp, convert
+                const float p4[4] = {pri_cur.x, pri_cur.y, pri_cur.z, pri_cur.w};
+#pragma unroll
+                for (int u4 = 0; u4 < 4; ++u4) {
+                    const float c = cut_base - p4[u4] * prior_scale;
+                    const int cut = static_cast<int>(__builtin_fminf(__builtin_fmaxf(c, -kPlCutClamp), kPlCutClamp)) - 1;
+                    if (!(special[u4] || a[u4] >= cut)) mask &= ~(1u << u4);
+                }
+            }
         }
         if (active && mask != 0u) {   // (active uniform) the filter on the fp32 rows left, before any chain
             // the quad's four rows are requested together (one memory round trip, not four); rows past n read row n - 1
@@ -407,7 +483,8 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
             const bool have = mask != 0u;
             const int64_t r = have ? r0 + __builtin_ctz(mask) : 0;
             const Row x = load_row(feats, r);
-            const float m = playlist_mean(s_mem, s_qn, s_w, wsum, k, x);
+            float m = playlist_mean(s_mem, s_qn, s_w, wsum, k, x);
+            if (prior) m = m + beta * row_prior[r];   // (uniform) v; the prior reloaded: an L2 hit (the tile's load brought its line)
             n_exact += (have && !active) ? 1 : 0;   // (with a filter every row read was counted above)
             const uint32_t g = static_cast<uint32_t>(row_base + r);
             const uint64_t key = have ? pack_key(m, g) : 0ull;
@@ -434,9 +511,11 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
             if (local_thr > thr) thr = local_thr;
         }
         if (published > thr) thr = published;
-        refresh_cut();
+        if (prior && prefilter) refresh_prior_cut();   // uniform
+        else refresh_cut();
         cur = nxt;
         lab_cur = lab_nxt;
+        pri_cur = pri_nxt;
     }
 
     const int wave_exact = wave_inclusive_scan(n_exact);

@@ -34,6 +34,8 @@ struct Request {
     int pool = 0;
     bool capped = false;                        // (diverse only) at most max_per_group picks per group ...
     int max_per_group = 0;                      // ... >= 1 then; 0 in every call that is not capped
+    bool prior = false;                         // rank by v = fl(score + fl(prior_weight p(x))), p the handle's priors ("ROW PRIORS")
+    float prior_weight = 0.0f;                  // ... beta, finite, |beta| <= MI355REC_MAX_PRIOR_WEIGHT; 0.0f is the call without a prior
 
     int scan_topn() const { return diverse ? pool : topn; }   // what the scan selects
     // The same call diversified, and (of a diversified one) capped: what the _diverse and _capped entry points add.
@@ -49,6 +51,12 @@ struct Request {
         Request r = *this;
         r.diverse = r.capped = false;
         r.topn = pool;
+        return r;
+    }
+    Request with_prior(float weight) const {
+        Request r = *this;
+        r.prior = true;
+        r.prior_weight = weight;
         return r;
     }
     Request capped_at(int max_per_group_) const {
@@ -164,7 +172,19 @@ inline bool invalid_playlist(const Request& r, int64_t n_rows, int64_t exclude_e
             std::snprintf(msg, cap, "label %d out of [0, %d)", static_cast<int>(r.labels[i]), MI355REC_MAX_LABELS);
             return true;
         }
+    if (r.prior && !(std::fabs(r.prior_weight) <= MI355REC_MAX_PRIOR_WEIGHT)) {   // (false for NaN)
+        std::snprintf(msg, cap, "prior_weight %g out of [-%g, %g]", static_cast<double>(r.prior_weight),
+                      static_cast<double>(MI355REC_MAX_PRIOR_WEIGHT), static_cast<double>(MI355REC_MAX_PRIOR_WEIGHT));
+        return true;
+    }
     return false;
+}
+
+// The first row whose prior cannot be used (not finite, or |p| > 1), or -1 ("ROW PRIORS": mi355rec_set_priors).
+inline int64_t first_bad_prior(const float* priors, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (!(std::fabs(priors[i]) <= 1.0f)) return i;   // (false for NaN)
+    return -1;
 }
 
 // The label set of a checked request as a mask: bit l of mask[l / 32] (MI355REC_MAX_LABELS / 32 words).
@@ -190,7 +210,10 @@ inline bool from_query(const mi355rec_playlist_query_t* q, const mi355rec_playli
                                   offsetof(mi355rec_playlist_query_t, n_exclude),      offsetof(mi355rec_playlist_query_t, n_labels),
                                   offsetof(mi355rec_playlist_query_t, topn),           offsetof(mi355rec_playlist_query_t, lambda),
                                   offsetof(mi355rec_playlist_query_t, pool),           offsetof(mi355rec_playlist_query_t, max_per_group),
-                                  offsetof(mi355rec_playlist_query_t, max_per_group) + sizeof(int32_t), sizeof(mi355rec_playlist_query_t)};
+                                  offsetof(mi355rec_playlist_query_t, prior_weight), sizeof(mi355rec_playlist_query_t)};
+    static_assert(offsetof(mi355rec_playlist_query_t, prior_weight) == offsetof(mi355rec_playlist_query_t, max_per_group) + sizeof(int32_t) &&
+                      offsetof(mi355rec_playlist_query_t, prior_weight) == 84 && sizeof(mi355rec_playlist_query_t) == 88,
+                  "prior_weight fills the tail padding: the struct ends where the field ends");
     bool known = false;
     for (size_t e : ends) known = known || q->size == e;
     if (!known) {
@@ -200,12 +223,19 @@ inline bool from_query(const mi355rec_playlist_query_t* q, const mi355rec_playli
     }
     std::memset(full, 0, sizeof *full);
     std::memcpy(full, q, q->size);
-    if (full->flags & ~static_cast<uint32_t>(MI355REC_PQ_DIVERSE | MI355REC_PQ_CAPPED)) {
+    if (full->flags & ~static_cast<uint32_t>(MI355REC_PQ_DIVERSE | MI355REC_PQ_CAPPED | MI355REC_PQ_PRIOR)) {
         std::snprintf(msg, cap, "unknown flags 0x%x in a playlist query", static_cast<unsigned>(full->flags));
         return true;
     }
     if ((full->flags & MI355REC_PQ_CAPPED) && !(full->flags & MI355REC_PQ_DIVERSE)) {
         std::snprintf(msg, cap, "MI355REC_PQ_CAPPED needs MI355REC_PQ_DIVERSE");
+        return true;
+    }
+    // prior_weight lies in what was tail padding: an older caller's bytes there are garbage, so it is read only with the flag,
+    // and only from a struct whose size covers it
+    if ((full->flags & MI355REC_PQ_PRIOR) && q->size < offsetof(mi355rec_playlist_query_t, prior_weight) + sizeof(float)) {
+        std::snprintf(msg, cap, "MI355REC_PQ_PRIOR in a playlist query of size %u: prior_weight ends at %u", static_cast<unsigned>(q->size),
+                      static_cast<unsigned>(offsetof(mi355rec_playlist_query_t, prior_weight) + sizeof(float)));
         return true;
     }
     if (full->members && full->rows) {
@@ -217,6 +247,7 @@ inline bool from_query(const mi355rec_playlist_query_t* q, const mi355rec_playli
     r->n_labels = full->n_labels;
     if (full->flags & MI355REC_PQ_DIVERSE) *r = r->diversified(full->lambda, full->pool);
     if (full->flags & MI355REC_PQ_CAPPED) *r = r->capped_at(full->max_per_group);
+    if (full->flags & MI355REC_PQ_PRIOR) *r = r->with_prior(full->prior_weight);
     *out = {res->out_idx, res->out_score, r->diverse ? res->out_mmr : nullptr, res->out_count, res->out_pool_rows};
     return false;
 }

@@ -584,6 +584,42 @@ int mi355rec_sharded_set_groups(mi355rec_sharded_t* h, const int32_t* groups_hos
     return MI355REC_OK;
 }
 
+// ---- ROW PRIORS (include/mi355rec_diag.h) -----------------------------------------------------------------------------
+int mi355rec_sharded_set_priors(mi355rec_sharded_t* h, const float* priors_host, int64_t n) {
+    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    if (priors_host && n != h->n)
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "%lld priors for a catalogue of %lld rows", (long long)n, (long long)h->n);
+    const int64_t bad = priors_host ? mi355playlist::first_bad_prior(priors_host, n) : -1;
+    if (bad >= 0)
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "prior %g of row %lld: a prior is finite with |p| <= 1",
+                     static_cast<double>(priors_host[bad]), (long long)bad);
+    if (h->cpu) {
+        const char* why = nullptr;
+        return cpu_result(h, mi355cpu::node_set_priors(h->cpu, priors_host, n, &why), why);
+    }
+    DeviceRestore restore;
+    int rc = drain_workers(h);   // the caller's thread drives every shard itself
+    if (rc) return rc;
+    // every replica the whole array, every shard of a row-sharded placement its slice (each scans its own rows' priors)
+    for (size_t r = 0; r < h->shards.size(); ++r) {
+        Shard& s = h->shards[r];
+        bool lane = false;   // a replica on a device that already holds one is a lane of it: it shares that one's priors
+        for (size_t p = 0; p < r && h->replicated && !lane; ++p) lane = h->shards[p].device == s.device;
+        if (lane) continue;
+        S_HIP(h, hipSetDevice(s.device));
+        rc = mi355node::set_group_priors(s.engine, priors_host ? priors_host + s.lo : nullptr, s.hi - s.lo);
+        if (rc != MI355REC_OK) {   // all or nothing: no shard keeps priors the others do not have
+            const std::string why = mi355rec_last_error(s.engine);
+            for (Shard& o : h->shards)
+                if (hipSetDevice(o.device) == hipSuccess) (void)mi355node::set_group_priors(o.engine, nullptr, 0);
+            h->has_priors = false;
+            return sfail(h, rc, "shard on device %d: %s (the priors were dropped on every shard)", s.device, why.c_str());
+        }
+    }
+    h->has_priors = priors_host != nullptr;
+    return MI355REC_OK;
+}
+
 namespace {
 // A filtered query on a row-sharded catalogue: the query by value on every shard (the query row excluded by its global index).
 int sharded_labels_by_value(mi355rec_sharded_t* h, const float* q, int64_t exclude_global, const int32_t* labels, int n_labels,
@@ -718,6 +754,8 @@ int sharded_playlist(mi355rec_sharded_t* h, Request r, const Outputs& out) {
     if ((r.diverse && mi355playlist::invalid_diverse(r, why, sizeof why)) ||
         mi355playlist::invalid_playlist(r, h->n, h->n, MI355REC_MAX_EXCLUDE, why, sizeof why))
         return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    if (r.prior && !h->cpu && !h->has_priors)
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "this handle has no priors (mi355rec_sharded_set_priors)");
     if (out.pool_rows) *out.pool_rows = 0;
     // By row, one handle (row_base 0) takes its own by-row call below: the members stay on the device.  Otherwise the members
     // go by value (fetched once) and their rows are added to the exclusion list.

@@ -66,7 +66,8 @@ _PLAYLIST_LEVELS = ("", "_where", "_weighted", "_diverse", "_capped")   # each l
 
 
 def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=None, where=None, weights=None, level: str = None,
-                     lam=None, pool=None, max_per_group=None, return_mmr: bool = False, return_pool_rows: bool = False, labels=None):
+                     lam=None, pool=None, max_per_group=None, return_mmr: bool = False, return_pool_rows: bool = False, labels=None,
+                     prior_weight=None):
     """Runs one entry point of the playlist family: `prefix`query_{mean|playlist}_topn`level`.  `members` is a (k, 12) float32
     array (by value: mean) or a 1-D int64 array of rows (by row: playlist).  `level` None: the lowest that takes the
     arguments given ("" plain, "_where" with a filter, "_weighted" with weights); "_diverse" and "_capped" are asked for.
@@ -83,7 +84,11 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
     pool_rows < pool that the catalogue has no more.
     PLAYLIST REQUESTS: `labels`, a set of labels (set_labels), restricts the answer (and a diversified call's pool) to rows whose
     label is in it; the call then goes through `prefix`query_playlist_request, the family's one struct-taking entry point.
-    None takes exactly the entry point described above."""
+    None takes exactly the entry point described above.
+    ROW PRIORS: `prior_weight` = beta ranks by score + beta * prior (set_priors; |beta| <= capi.MAX_PRIOR_WEIGHT, negative demotes);
+    the call goes through the request as well, the returned scores are the blended values.  None takes the entry point used today."""
+    if prior_weight is not None and (isinstance(prior_weight, bool) or not isinstance(prior_weight, (int, float, np.integer, np.floating))):
+        raise ValueError(f"prior_weight must be a number or None, got {prior_weight!r}")
     if level is None:
         level = "_weighted" if weights is not None else "_where" if where is not None else ""
     rank = _PLAYLIST_LEVELS.index(level)
@@ -131,16 +136,20 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
     if capped:
         args.append(ctypes.byref(pool_rows))
     by = "playlist" if members.dtype == np.int64 else "mean"
-    if labels is not None:
-        lab = _np_labels(labels)
+    if labels is not None or prior_weight is not None:
         q = capi.PlaylistQuery()
         q.size = ctypes.sizeof(capi.PlaylistQuery)
         q.flags = (capi.PQ_DIVERSE if diverse else 0) | (capi.PQ_CAPPED if capped else 0)
+        if prior_weight is not None:
+            q.flags |= capi.PQ_PRIOR
+            q.prior_weight = float(prior_weight)
         q.members, q.rows = (None, ptr(members)) if by == "playlist" else (ptr(members), None)
         q.weights = ptr(w) if w is not None else None
         q.exclude_global, q.n_exclude = (ptr(ex) if ex.size else None), int(ex.size)
         q.filter = ctypes.pointer(flt) if flt is not None else None
-        q.labels, q.n_labels = ptr(lab), int(lab.size)   # (an empty set stays a non-NULL pointer: the library refuses it)
+        if labels is not None:
+            lab = _np_labels(labels)
+            q.labels, q.n_labels = ptr(lab), int(lab.size)   # (an empty set stays a non-NULL pointer: the library refuses it)
         q.k, q.topn = k, int(topn)
         if diverse:
             q.lambda_, q.pool = float(lam), int(pool)
@@ -157,6 +166,11 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
     if return_pool_rows:
         out += (pool_rows.value,)
     return out
+
+
+def _np_priors(priors) -> np.ndarray:
+    """One prior per row (float32, contiguous); the library checks the values."""
+    return np.ascontiguousarray(np.asarray(priors, dtype=np.float32).reshape(-1))
 
 
 def _np_groups(groups) -> np.ndarray:
@@ -516,34 +530,34 @@ class CosineEngine:
 
 
     # ---- PLAYLISTS (include/mi355rec_diag.h): top-N by the mean score against up to 32 songs ----
-    def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
+    def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None) -> Tuple[np.ndarray, np.ndarray]:
         """The best `topn` rows by the mean of their scores against the rows of `queries` (k x 12); `exclude`: global ids.
         `where`: {feature index or name: (lo, hi)}, only rows within every range are returned (FEATURE FILTERS; a
         filtered single query is k = 1); None calls the unfiltered entry point.
         `weights`: one signed float per member (WEIGHTED PLAYLISTS: score = sum w_k c_k / sum |w_k|, a negative weight is
         a dislike); None calls the entry point used without it."""
-        return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels)
+        return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight)
 
-    def query_playlist_topn(self, local_rows, topn: int, exclude=None, where=None, weights=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
+    def query_playlist_topn(self, local_rows, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None) -> Tuple[np.ndarray, np.ndarray]:
         """The same for members given as rows of this handle; the members are never returned (whatever their weight)."""
-        return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, labels=labels)
+        return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight)
 
     def _playlist(self, members, topn, exclude, where, weights, level=None, labels=None, **more):
         return _playlist_family(self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), members, topn, exclude, where,
                                 weights, level, labels=labels, **more)
 
     # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h): MMR picks from the top-`pool` of the weighted playlist call ----
-    def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False, labels=None):
+    def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False, labels=None, prior_weight=None):
         """`topn` rows picked greedily from the `pool` most relevant (query_mean_topn's order): each pick maximises
         lam * relevance - (1 - lam) * (its largest similarity to a row already picked).  Pick order; scores = relevance."""
         return self._playlist(_np_members(queries), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr,
-                              labels=labels)
+                              labels=labels, prior_weight=prior_weight)
 
     def query_playlist_topn_diverse(self, local_rows, topn: int, lam, pool=None, exclude=None, where=None, weights=None,
-                                    return_mmr=False, labels=None):
+                                    return_mmr=False, labels=None, prior_weight=None):
         """The same for members given as rows of this handle (never returned)."""
         return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr,
-                              labels=labels)
+                              labels=labels, prior_weight=prior_weight)
 
     def set_groups(self, groups) -> None:
         """One group id per row (GROUP CAPS): >= 0 a group (an artist, say), -1 = never capped; None drops the groups."""
@@ -553,18 +567,26 @@ class CosineEngine:
         g = _np_groups(groups)
         capi.check(self._lib.mi355rec_set_groups(self._h, g.ctypes.data_as(ctypes.c_void_p), int(g.size)), self._h)
 
+    def set_priors(self, priors) -> None:
+        """One float per row in [-1, 1] (ROW PRIORS: popularity, freshness, a boost); None drops the priors."""
+        if priors is None:
+            capi.check(self._lib.mi355rec_set_priors(self._h, None, 0), self._h)
+            return
+        p = _np_priors(priors)
+        capi.check(self._lib.mi355rec_set_priors(self._h, p.ctypes.data_as(ctypes.c_void_p), int(p.size)), self._h)
+
     def query_mean_topn_capped(self, queries, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
-                               weights=None, return_mmr=False, return_pool_rows=False, labels=None):
+                               weights=None, return_mmr=False, return_pool_rows=False, labels=None, prior_weight=None):
         """query_mean_topn_diverse with at most `max_per_group` results per group of set_groups (GROUP CAPS)."""
         return self._playlist(_np_members(queries), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
                               max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows,
-                              labels=labels)
+                              labels=labels, prior_weight=prior_weight)
 
     def query_playlist_topn_capped(self, local_rows, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
-                                   weights=None, return_mmr=False, return_pool_rows=False, labels=None):
+                                   weights=None, return_mmr=False, return_pool_rows=False, labels=None, prior_weight=None):
         return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
                               max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows,
-                              labels=labels)
+                              labels=labels, prior_weight=prior_weight)
 
     def fetch_rows(self, local_rows) -> np.ndarray:
         """The features of the listed rows (any order, duplicates allowed), gathered on the device: (len, 12) float32."""
@@ -695,11 +717,11 @@ class NodeEngine:
                              (q.ctypes.data_as(ctypes.c_void_p), int(exclude_global)), labels, topn)
 
     # ---- PLAYLISTS (include/mi355rec_diag.h) over the whole node ----
-    def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
-        return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels)
+    def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None) -> Tuple[np.ndarray, np.ndarray]:
+        return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight)
 
-    def query_playlist_topn(self, global_rows, topn: int, exclude=None, where=None, weights=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
-        return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, labels=labels)
+    def query_playlist_topn(self, global_rows, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None) -> Tuple[np.ndarray, np.ndarray]:
+        return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight)
 
     def _playlist(self, members, topn, exclude, where, weights, level=None, labels=None, **more):
         return _playlist_family(self._lib, "mi355rec_sharded_", self._h, self._check, members, topn, exclude, where, weights, level,
@@ -714,26 +736,34 @@ class NodeEngine:
         g = _np_groups(groups)
         self._check(self._lib.mi355rec_sharded_set_groups(self._h, g.ctypes.data_as(ctypes.c_void_p), int(g.size)))
 
+    def set_priors(self, priors) -> None:
+        """One float per row in [-1, 1] (ROW PRIORS); None drops the priors."""
+        if priors is None:
+            self._check(self._lib.mi355rec_sharded_set_priors(self._h, None, 0))
+            return
+        p = _np_priors(priors)
+        self._check(self._lib.mi355rec_sharded_set_priors(self._h, p.ctypes.data_as(ctypes.c_void_p), int(p.size)))
+
     def query_mean_topn_capped(self, queries, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
-                               weights=None, return_mmr=False, return_pool_rows=False, labels=None):
+                               weights=None, return_mmr=False, return_pool_rows=False, labels=None, prior_weight=None):
         return self._playlist(_np_members(queries), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
                               max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows,
-                              labels=labels)
+                              labels=labels, prior_weight=prior_weight)
 
     def query_playlist_topn_capped(self, global_rows, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
-                                   weights=None, return_mmr=False, return_pool_rows=False, labels=None):
+                                   weights=None, return_mmr=False, return_pool_rows=False, labels=None, prior_weight=None):
         return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
                               max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows,
-                              labels=labels)
+                              labels=labels, prior_weight=prior_weight)
 
-    def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False, labels=None):
+    def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False, labels=None, prior_weight=None):
         return self._playlist(_np_members(queries), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr,
-                              labels=labels)
+                              labels=labels, prior_weight=prior_weight)
 
     def query_playlist_topn_diverse(self, global_rows, topn: int, lam, pool=None, exclude=None, where=None, weights=None,
-                                    return_mmr=False, labels=None):
+                                    return_mmr=False, labels=None, prior_weight=None):
         return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr,
-                              labels=labels)
+                              labels=labels, prior_weight=prior_weight)
 
     def scores_row(self, global_row: int) -> np.ndarray:
         out = np.empty(self.rows, dtype=np.float32)
