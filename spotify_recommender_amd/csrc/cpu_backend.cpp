@@ -303,74 +303,51 @@ int node_query(Node* h, const float* q12, int64_t exclude, int topn_asked, int64
     return MI355REC_OK;
 }
 
-int node_set_labels(Node* h, const int32_t* labels, int64_t n, const char** why) {
-    if (!labels) {
-        h->labels.clear();
-        h->has_labels = false;
+namespace {
+// One per-row attribute of the node: null clears it; otherwise the count must be the catalogue's rows and no value may be
+// bad (bad_value(v): what is wrong with v, or null); assign gives the strong guarantee, so the previous values stay on failure.
+template <class T, class BadValue>
+int node_set_side(Node* h, std::vector<T>& dst, bool& has, const T* src, int64_t n, const char* bad_count, BadValue bad_value,
+                  const char** why) {
+    if (!src) {
+        dst.clear();
+        has = false;
         return MI355REC_OK;
     }
     if (n != rows(h->cat)) {
-        *why = "the label count must equal the catalogue's rows";
+        *why = bad_count;
         return MI355REC_ERR_INVALID_ARG;
     }
     for (int64_t i = 0; i < n; ++i)
-        if (labels[i] < -1 || labels[i] >= MI355REC_MAX_LABELS) {
-            *why = "a label is out of [-1, MI355REC_MAX_LABELS)";
+        if (const char* bad = bad_value(src[i])) {
+            *why = bad;
             return MI355REC_ERR_INVALID_ARG;
         }
     try {
-        h->labels.assign(labels, labels + n);
+        dst.assign(src, src + n);
     } catch (const std::bad_alloc&) {
         *why = "out of host memory";
-        return MI355REC_ERR_OUT_OF_MEMORY;   // (assign gives the strong guarantee: the previous labels stay)
+        return MI355REC_ERR_OUT_OF_MEMORY;
     }
-    h->has_labels = true;
+    has = true;
     return MI355REC_OK;
+}
+}  // namespace
+
+int node_set_labels(Node* h, const int32_t* labels, int64_t n, const char** why) {
+    return node_set_side(h, h->labels, h->has_labels, labels, n, "the label count must equal the catalogue's rows",
+                         [](int32_t l) { return l < -1 || l >= MI355REC_MAX_LABELS ? "a label is out of [-1, MI355REC_MAX_LABELS)" : nullptr; }, why);
 }
 
 int node_set_groups(Node* h, const int32_t* groups, int64_t n, const char** why) {
-    if (!groups) {
-        h->groups.clear();
-        h->has_groups = false;
-        return MI355REC_OK;
-    }
-    if (n != rows(h->cat)) {
-        *why = "the group count must equal the catalogue's rows";
-        return MI355REC_ERR_INVALID_ARG;
-    }
-    for (int64_t i = 0; i < n; ++i)
-        if (groups[i] < -1) {
-            *why = "a group id is >= 0, or -1 for no group";
-            return MI355REC_ERR_INVALID_ARG;
-        }
-    try {
-        h->groups.assign(groups, groups + n);
-    } catch (const std::bad_alloc&) {
-        *why = "out of host memory";
-        return MI355REC_ERR_OUT_OF_MEMORY;   // (the previous groups stay)
-    }
-    h->has_groups = true;
-    return MI355REC_OK;
+    return node_set_side(h, h->groups, h->has_groups, groups, n, "the group count must equal the catalogue's rows",
+                         [](int32_t g) { return g < -1 ? "a group id is >= 0, or -1 for no group" : nullptr; }, why);
 }
 
+// (the node handle has checked the values: mi355rec_sharded_set_priors)
 int node_set_priors(Node* h, const float* priors, int64_t n, const char** why) {
-    if (!priors) {
-        h->priors.clear();
-        h->has_priors = false;
-        return MI355REC_OK;
-    }
-    if (n != rows(h->cat)) {
-        *why = "the prior count must equal the catalogue's rows";
-        return MI355REC_ERR_INVALID_ARG;
-    }
-    try {
-        h->priors.assign(priors, priors + n);
-    } catch (const std::bad_alloc&) {
-        *why = "out of host memory";
-        return MI355REC_ERR_OUT_OF_MEMORY;   // (the previous priors stay)
-    }
-    h->has_priors = true;
-    return MI355REC_OK;
+    return node_set_side(h, h->priors, h->has_priors, priors, n, "the prior count must equal the catalogue's rows",
+                         [](float) { return static_cast<const char*>(nullptr); }, why);
 }
 
 int node_query_labels(Node* h, const float* q12, int64_t exclude, const int32_t* set, int n_set, int topn_asked,

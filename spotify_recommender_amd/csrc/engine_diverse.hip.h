@@ -2,8 +2,9 @@
 // weighted playlist call's top-`pool`, re-ranked by maximal marginal relevance.  What sync_playlist_query
 // (engine_playlist.hip.h) does for a diversified request: the scan launch of the playlist call, the merge into h->d_keys (no
 // ids or scores are unpacked: the pool never leaves the device), then mmr_rerank_kernel (diverse.hip.h) on the same stream,
-// which stores the picks into the handle's pinned result slots and raises the completion word: the host waits once.  Here:
-// that request's checks, the re-rank and the wait, the _diverse and _capped entry points, a pool passed by value (what a
+// which stores the picks into the handle's pinned result slots and raises the completion word: the host waits once
+// (sync_finish, engine_sync.hip.h; the slots were begun by playlist_launch).  Here: that request's checks, the re-rank and
+// its extra outputs (mmr, P'), mi355rec_set_groups, the _diverse and _capped entry points, a pool passed by value (what a
 // row-sharded node does after gathering the pool's rows from its shards) and mi355rec_fetch_rows, both launches of the same
 // kernel.  (Part of mi355rec.hip's translation unit, included after engine_playlist.hip.h.)
 #pragma once
@@ -15,14 +16,11 @@
 
 namespace {
 
-// The groups a handle answers from (its own, or its group's of lanes).
-const int32_t* groups_of(const mi355rec* h) { return h->shared ? h->shared->d_groups : h->d_groups; }
-
 // lambda, topn, pool and the cap (the other arguments are the playlist call's, checked by playlist_launch with topn = pool).
 int check_diverse(mi355rec* h, const Request& r) {
     char why[128];
     if (mi355playlist::invalid_diverse(r, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    if (r.capped && !groups_of(h)) return fail(h, MI355REC_ERR_INVALID_ARG, "this handle has no groups (mi355rec_set_groups)");
+    if (r.capped && !h->side->d_groups) return fail(h, MI355REC_ERR_INVALID_ARG, "this handle has no groups (mi355rec_set_groups)");
     return MI355REC_OK;
 }
 
@@ -44,63 +42,44 @@ int ensure_diverse(mi355rec* h) {
 
 // The re-rank of the `pool` keys in h->d_keys on h->stream, the wait and the results; of `r`: lambda, topn and the cap.
 // Over the handle's matrix and (GROUP CAPS: the same launch, two more arguments) its groups, or — staged — over the pool's
-// rows and groups in pool order, copied to the playlist state by the caller.
-int rerank_and_wait(mi355rec* h, const Request& r, const Outputs& out, int pool, bool staged) {
+// rows and groups in pool order, copied to the playlist state by the caller.  The kernel itself stores the picks into the
+// pinned slots and raises ss.want; beyond sync_finish only the extra outputs (mmr, P') are this function's.
+int rerank_and_wait(mi355rec* h, const Request& r, const Outputs& out, SyncSlots ss, int pool, bool staged) {
     mi355rec_playlist* P = h->playlist;
     const float* rows = staged ? P->d_rows : h->d_feats;
-    const int32_t* groups = !r.capped ? nullptr : staged ? P->d_pool_groups : groups_of(h);
+    const int32_t* groups = !r.capped ? nullptr : staged ? P->d_pool_groups : h->side->d_groups;
     const int topn = r.topn;
     const float mu = 1.0f - r.lambda;
-    const uint32_t want = ++h->done_seq ? h->done_seq : ++h->done_seq;   // never 0
     const int block = (pool + 63) & ~63;
     hipLaunchKernelGGL(mmr_rerank_kernel, dim3(1), dim3(block), 0, h->stream, static_cast<const uint64_t*>(h->d_keys), rows, h->n,
-                       h->row_base, staged ? 1 : 0, pool, topn, r.lambda, mu, h->hd_idx, h->hd_score, P->hd_mmr,
-                       static_cast<float*>(nullptr), h->hd_done, want, groups, r.max_per_group,
+                       h->row_base, staged ? 1 : 0, pool, topn, r.lambda, mu, ss.idx, ss.score, P->hd_mmr,
+                       static_cast<float*>(nullptr), h->hd_done, ss.want, groups, r.max_per_group,
                        groups ? P->hd_pool_rows : static_cast<int*>(nullptr));
     HIP_TRY(h, hipGetLastError());
-    const int rc = wait_done(h, want);
+    ss.eff = topn;   // (the slots were begun for the pool; its topn picks are the call's results)
+    const int rc = sync_finish(h, ss, topn, out.idx, out.score, out.count);
     if (rc) return rc;
     if (out.pool_rows) *out.pool_rows = groups ? *P->h_pool_rows : 0;
-    int c = 0;
-    while (c < topn && h->h_idx[c] >= 0) ++c;
-    std::memcpy(out.idx, h->h_idx, static_cast<size_t>(topn) * sizeof(int64_t));
-    if (out.score) std::memcpy(out.score, h->h_score, static_cast<size_t>(topn) * sizeof(float));
     if (out.mmr) std::memcpy(out.mmr, P->h_mmr, static_cast<size_t>(topn) * sizeof(float));
-    if (out.count) *out.count = c;
     return MI355REC_OK;
 }
 
-// `group_ok`: as for the labels (engine_labels.hip.h): the node handle may replace the groups under its own lanes.
+// mi355rec_set_groups: the groups' own checks and upload (replace_side, engine_labels.hip.h, does the rest).
 int set_groups_common(mi355rec* h, const int32_t* groups_host, int64_t n, bool group_ok) {
-    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    if (!group_ok && h->shared && (h->is_lane || h->shared->refs.load() > 1))
-        return fail(h, MI355REC_ERR_INVALID_ARG, "the handle has lanes: set the groups before the first lane is made");
-    int32_t* fresh = nullptr;
-    DeviceGuard guard(h->device);
-    if (groups_host) {
+    return replace_side(h, &RowSide::d_groups, "groups", group_ok, groups_host != nullptr, [&](int32_t** fresh) {
         if (n != h->n) return fail(h, MI355REC_ERR_INVALID_ARG, "%lld groups for a handle of %lld rows", (long long)n, (long long)h->n);
         for (int64_t i = 0; i < n; ++i)
             if (groups_host[i] < -1)
                 return fail(h, MI355REC_ERR_INVALID_ARG, "group %d of row %lld: a group id is >= 0, or -1 for no group",
                             static_cast<int>(groups_host[i]), (long long)i);
         // (an empty shard keeps a one-word array: "has groups" is a non-null pointer)
-        hipError_t e = hipMalloc(&fresh, sizeof(int32_t) * static_cast<size_t>(n > 0 ? n : 1));
-        if (e == hipSuccess && n > 0) e = hipMemcpy(fresh, groups_host, sizeof(int32_t) * static_cast<size_t>(n), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {   // the previous groups stay
-            if (fresh) (void)hipFree(fresh);
-            (void)hipGetLastError();
-            return fail(h, e == hipErrorOutOfMemory ? MI355REC_ERR_OUT_OF_MEMORY : MI355REC_ERR_HIP, "the groups (%lld rows): %s",
-                        (long long)n, hipGetErrorString(e));
-        }
-    }
-    int32_t* old = const_cast<int32_t*>(groups_of(h));
-    if (old) {
-        (void)hipStreamSynchronize(h->stream);   // (only the synchronous calls on this stream read them)
-        (void)hipFree(old);
-    }
-    h->d_groups = fresh;
-    if (h->shared) h->shared->d_groups = fresh;
-    return MI355REC_OK;
+        hipError_t e = hipMalloc(fresh, sizeof(int32_t) * static_cast<size_t>(n > 0 ? n : 1));
+        if (e == hipSuccess && n > 0) e = hipMemcpy(*fresh, groups_host, sizeof(int32_t) * static_cast<size_t>(n), hipMemcpyHostToDevice);
+        if (e == hipSuccess) return static_cast<int>(MI355REC_OK);
+        if (*fresh) (void)hipFree(*fresh);
+        return fail(h, e == hipErrorOutOfMemory ? MI355REC_ERR_OUT_OF_MEMORY : MI355REC_ERR_HIP, "the groups (%lld rows): %s",
+                    (long long)n, hipGetErrorString(e));
+    });
 }
 
 }  // namespace
@@ -117,9 +96,9 @@ int rerank_pool(mi355rec_t* h, const int64_t* pool_idx, const float* pool_score,
     if (pool_groups && max_per_group < 1)
         return fail(h, MI355REC_ERR_INVALID_ARG, "max_per_group must be positive, got %d", max_per_group);
     DeviceGuard guard(h->device);
+    SyncSlots ss;
     int rc = ensure_diverse(h);
-    if (!rc) rc = ensure_slots(h, static_cast<size_t>(kMaxTopK));
-    if (!rc) rc = sync_api_begin(h);
+    if (!rc) rc = sync_begin(h, kMaxTopK, 1, true, &ss);   // (slots for any pool and topn this call takes)
     if (rc) return rc;
     uint64_t keys[kMaxTopK];
     for (int i = 0; i < count; ++i) keys[i] = pack_key(pool_score[i], static_cast<uint32_t>(pool_idx[i]));
@@ -135,7 +114,7 @@ int rerank_pool(mi355rec_t* h, const int64_t* pool_idx, const float* pool_score,
     r.topn = topn;
     r.capped = pool_groups != nullptr;
     r.max_per_group = max_per_group;
-    return rerank_and_wait(h, r, {out_idx, out_score, out_mmr, out_count, out_pool_rows}, count, true);
+    return rerank_and_wait(h, r, {out_idx, out_score, out_mmr, out_count, out_pool_rows}, ss, count, true);
 }
 }  // namespace mi355node
 
@@ -182,9 +161,9 @@ int mi355rec_fetch_rows(mi355rec_t* h, const int64_t* local_rows, int64_t count,
             return fail(h, MI355REC_ERR_INVALID_ARG, "Invalid song index: %lld", (long long)local_rows[i]);
     if (count == 0) return MI355REC_OK;
     DeviceGuard guard(h->device);
+    SyncSlots ss;   // (only h->d_keys of the slots is used; never notifies: each round waits for the stream)
     int rc = ensure_diverse(h);
-    if (!rc) rc = ensure_slots(h, static_cast<size_t>(kMaxTopK));
-    if (!rc) rc = sync_api_begin(h);
+    if (!rc) rc = sync_begin(h, kMaxTopK, 1, false, &ss);
     if (rc) return rc;
     uint64_t keys[kMaxTopK];
     for (int64_t done = 0; done < count; done += kMaxTopK) {   // one gather launch and one copy back per 1024 rows

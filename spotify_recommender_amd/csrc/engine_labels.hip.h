@@ -1,12 +1,14 @@
 // engine_labels.hip.h — LABELS on the single-device handle (include/mi355rec_diag.h, "LABELS"): the label-grouped copy of
-// the shard's rows that mi355rec_set_labels builds (and the labels in row order for the playlist calls), and the synchronous filtered query over it (labels.hip.h, then the
-// merge of merge.hip.h into the handle's pinned result slots and completion word, as sync_single_query does).
-// (Part of mi355rec.hip's translation unit, included after engine_batch.hip.h.)
+// the shard's rows that mi355rec_set_labels builds (and the labels in row order for the playlist calls), and the synchronous
+// filtered query over it (labels.hip.h, then the merge of merge.hip.h, between sync_begin and sync_finish of
+// engine_sync.hip.h).  Also the owner's side of the PER-ROW SIDE DATA (RowSide, engine_state.hip.h): free_side, and
+// replace_side, which the setters of labels, groups and priors share.
+// (Part of mi355rec.hip's translation unit, included after engine_sync.hip.h.)
 #pragma once
 
 #include <chrono>
 
-#include "engine_batch.hip.h"
+#include "engine_sync.hip.h"
 #include "labels.hip.h"
 #include "playlist_request.h"
 
@@ -32,8 +34,40 @@ void free_labels(mi355rec_labels* L) {
     delete L;
 }
 
-// The labels a handle answers from (its own, or its group's).
-mi355rec_labels* labels_of(const mi355rec* h) { return h->shared ? h->shared->labels : h->labels; }
+// Frees what a RowSide holds and leaves it empty: the one place the side data is freed.
+void free_side(RowSide& s) {
+    free_labels(s.labels);
+    if (s.d_groups) (void)hipFree(s.d_groups);
+    if (s.d_priors) (void)hipFree(s.d_priors);
+    s = RowSide();
+}
+
+// What the three setters share: `field` of the side data `h` answers from is replaced by what `build` makes (`set`), or
+// dropped (!set).  A handle with lanes refuses, unless `group_ok`: the side data may be replaced under a group of lanes only
+// for a caller that knows no member of the group is in use meanwhile (the node handle, whose workers are idle and whose
+// replicas on one device are lanes of the first).  build(&fresh) validates and uploads; where it fails the previous value
+// stays.  The old value is freed once the handle's stream has drained (only the synchronous calls on it read side data).
+template <class T, class Build>
+int replace_side(mi355rec* h, T* RowSide::*field, const char* noun, bool group_ok, bool set, Build build) {
+    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    if (!group_ok && h->shared && (h->is_lane || h->shared->refs.load() > 1))
+        return fail(h, MI355REC_ERR_INVALID_ARG, "the handle has lanes: set the %s before the first lane is made", noun);
+    DeviceGuard guard(h->device);
+    T* fresh = nullptr;
+    if (set) {
+        const int rc = build(&fresh);
+        if (rc != MI355REC_OK) {
+            (void)hipGetLastError();   // (a failed upload leaves no HIP error behind)
+            return rc;
+        }
+    }
+    RowSide old;
+    old.*field = h->side->*field;
+    if (old.*field) (void)hipStreamSynchronize(h->stream);
+    free_side(old);
+    h->side->*field = fresh;
+    return MI355REC_OK;
+}
 
 // Builds the label-grouped copy: the rows come back to the host (the handle may have been made from a device pointer),
 // are placed by a counting sort and go up again.  Nothing of the handle is touched until everything has succeeded.
@@ -124,13 +158,13 @@ int label_mask(mi355rec* h, const mi355rec_labels* L, const int32_t* labels, int
     return MI355REC_OK;
 }
 
-// One filtered query, synchronously (sync_single_query's pattern): rounds of kMaxTopK keys, each one label_scan_kernel
-// launch + one merge; a single-round query's merge stores the results and the completion word in pinned host memory.
+// One filtered query, synchronously (engine_sync.hip.h): rounds of kMaxTopK keys, each one label_scan_kernel launch + one
+// merge; a single-round query's merge stores the results and the completion word in pinned host memory.
 int sync_label_query(mi355rec* h, const float* qptr, const float* query12, int64_t exclude_global, const int32_t* labels,
                      int n_labels, int topn, int64_t* out_idx, float* out_score, int* out_count) {
     int rc = check_topn(h, topn, true);
     if (rc) return rc;
-    const mi355rec_labels* L = labels_of(h);
+    const mi355rec_labels* L = h->side->labels;
     if (!L) return fail(h, MI355REC_ERR_INVALID_ARG, "this handle has no labels (mi355rec_set_labels)");
     LabelMask mask;
     int64_t selected = 0, tiles = 0;
@@ -143,15 +177,9 @@ int sync_label_query(mi355rec* h, const float* qptr, const float* query12, int64
         return MI355REC_OK;
     }
     DeviceGuard guard(h->device);
-    rc = ensure_slots(h, static_cast<size_t>(eff));
+    SyncSlots ss;
+    rc = sync_begin(h, eff, 1, true, &ss);
     if (rc) return rc;
-    rc = sync_api_begin(h);
-    if (rc) return rc;
-    const bool direct = eff <= kDirectResultSlots;
-    const bool notify = direct && eff <= kMaxTopK;
-    const uint32_t want = notify ? (++h->done_seq ? h->done_seq : ++h->done_seq) : 0u;   // never 0
-    int64_t* const r_idx = direct ? h->hd_idx : h->d_idx;
-    float* const r_score = direct ? h->hd_score : h->d_score;
     QueryArg qa;
     std::memset(&qa, 0, sizeof qa);
     if (!qptr) std::memcpy(qa.q, query12, sizeof qa.q);
@@ -164,60 +192,26 @@ int sync_label_query(mi355rec* h, const float* qptr, const float* query12, int64
                      h->d_block_lists, upper);
         HIP_TRY(h, hipGetLastError());
         h->label_rows_scanned += tiles * LabelScanCfg::kTileRows;
-        rc = enqueue_merge(h, h->d_block_lists, grid, k, k, h->d_keys + done, r_idx + done, r_score + done, h->stream, notify ? want : 0u);
+        rc = enqueue_merge(h, h->d_block_lists, grid, k, k, h->d_keys + done, ss.idx + done, ss.score + done, h->stream, ss.want);
         if (rc) return rc;
     }
-    if (!direct) {
-        HIP_TRY(h, hipMemcpyAsync(h->h_idx, h->d_idx, eff * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->h_score, h->d_score, eff * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    }
-    if (notify) {
-        rc = wait_done(h, want);
-        if (rc) return rc;
-    } else {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    int c = 0;
-    while (c < eff && h->h_idx[c] >= 0) ++c;
-    std::memcpy(out_idx, h->h_idx, static_cast<size_t>(eff) * sizeof(int64_t));
-    if (out_score) std::memcpy(out_score, h->h_score, static_cast<size_t>(eff) * sizeof(float));
-    mi355playlist::pad({out_idx, out_score, nullptr, out_count, nullptr}, eff, topn, c);
-    return MI355REC_OK;
+    return sync_finish(h, ss, topn, out_idx, out_score, out_count);
 }
 
-}  // namespace
-
-namespace {
-
-// `group_ok`: the labels may be replaced under a group of lanes — only for a caller that knows no member of the group is in
-// use meanwhile (the node handle, whose workers are idle and whose replicas on one device are lanes of the first).
+// mi355rec_set_labels: the labels' own checks and build (replace_side does the rest).
 int set_labels_common(mi355rec* h, const int32_t* labels_host, int64_t n, bool group_ok) {
-    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    if (!group_ok && h->shared && (h->is_lane || h->shared->refs.load() > 1))
-        return fail(h, MI355REC_ERR_INVALID_ARG, "the handle has lanes: set the labels before the first lane is made");
-    mi355rec_labels* fresh = nullptr;
-    if (labels_host) {
+    return replace_side(h, &RowSide::labels, "labels", group_ok, labels_host != nullptr, [&](mi355rec_labels** fresh) {
         if (n != h->n) return fail(h, MI355REC_ERR_INVALID_ARG, "%lld labels for a handle of %lld rows", (long long)n, (long long)h->n);
         for (int64_t i = 0; i < n; ++i)
             if (labels_host[i] < -1 || labels_host[i] >= kMaxLabels)
                 return fail(h, MI355REC_ERR_INVALID_ARG, "label %d of row %lld out of [-1, %d)", static_cast<int>(labels_host[i]),
                             (long long)i, kMaxLabels);
-        DeviceGuard guard(h->device);
         const auto t0 = std::chrono::steady_clock::now();
-        const int rc = build_labels(h, labels_host, &fresh);
-        if (rc != MI355REC_OK) {
-            (void)hipGetLastError();
-            return rc;   // the previous labels stay
-        }
-        fresh->build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    DeviceGuard guard(h->device);
-    mi355rec_labels* old = labels_of(h);
-    if (old) (void)hipStreamSynchronize(h->stream);   // (only the synchronous calls on this stream read them)
-    free_labels(old);
-    h->labels = fresh;
-    if (h->shared) h->shared->labels = fresh;
-    return MI355REC_OK;
+        const int rc = build_labels(h, labels_host, fresh);
+        if (rc == MI355REC_OK)
+            (*fresh)->build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return rc;
+    });
 }
 
 }  // namespace

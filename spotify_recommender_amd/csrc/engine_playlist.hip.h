@@ -1,7 +1,7 @@
 // engine_playlist.hip.h — PLAYLISTS on the single-device handle (include/mi355rec_diag.h, "PLAYLISTS"): the top-N rows by
 // the mean of their scores against up to 32 member queries, an exclusion list left out.  One playlist_scan_kernel launch
-// (playlist.hip.h), then the merge of merge.hip.h into the handle's pinned result slots and completion word, as
-// sync_label_query does.  No state beyond a small per-handle buffer for the call's inputs, allocated by the first call.
+// (playlist.hip.h), then the merge of merge.hip.h into the handle's pinned result slots and completion word, between
+// sync_begin and sync_finish (engine_sync.hip.h) as sync_label_query does.  No state beyond a small per-handle buffer for the call's inputs, allocated by the first call.
 // Every call of the family (filtered, weighted, diversified, capped; by value or by row) is one mi355playlist::Request
 // (playlist_request.h) through sync_playlist_query; the exported functions only fill it.
 // (Part of mi355rec.hip's translation unit, included after engine_labels.hip.h.)
@@ -35,18 +35,10 @@ using mi355playlist::Outputs;
 using mi355playlist::Request;
 using mi355playlist::request;
 
-// The priors a handle answers from (its own, or its group's of lanes): "ROW PRIORS".
-const float* priors_of(const mi355rec* h) { return h->shared ? h->shared->d_priors : h->d_priors; }
-
-// mi355rec_set_priors.  `group_ok`: as for the labels and the groups: the node handle may replace the priors under its own
-// lanes.  The device array is padded with +0.0f to a whole quad (playlist_scan_kernel loads a quad's four priors at once).
+// mi355rec_set_priors: the priors' own checks and upload (replace_side, engine_labels.hip.h, does the rest).  The device
+// array is padded with +0.0f to a whole quad (playlist_scan_kernel loads a quad's four priors at once).
 int set_priors_common(mi355rec* h, const float* priors_host, int64_t n, bool group_ok) {
-    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    if (!group_ok && h->shared && (h->is_lane || h->shared->refs.load() > 1))
-        return fail(h, MI355REC_ERR_INVALID_ARG, "the handle has lanes: set the priors before the first lane is made");
-    float* fresh = nullptr;
-    DeviceGuard guard(h->device);
-    if (priors_host) {
+    return replace_side(h, &RowSide::d_priors, "priors", group_ok, priors_host != nullptr, [&](float** fresh) {
         if (n != h->n) return fail(h, MI355REC_ERR_INVALID_ARG, "%lld priors for a handle of %lld rows", (long long)n, (long long)h->n);
         const int64_t bad = mi355playlist::first_bad_prior(priors_host, n);
         if (bad >= 0)
@@ -54,24 +46,14 @@ int set_priors_common(mi355rec* h, const float* priors_host, int64_t n, bool gro
                         static_cast<double>(priors_host[bad]), (long long)bad);
         // (an empty shard keeps a one-quad array: "has priors" is a non-null pointer)
         const size_t padded = static_cast<size_t>(n > 0 ? (n + 3) / 4 * 4 : 4);
-        hipError_t e = hipMalloc(&fresh, sizeof(float) * padded);
-        if (e == hipSuccess) e = hipMemset(fresh, 0, sizeof(float) * padded);
-        if (e == hipSuccess && n > 0) e = hipMemcpy(fresh, priors_host, sizeof(float) * static_cast<size_t>(n), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {   // the previous priors stay
-            if (fresh) (void)hipFree(fresh);
-            (void)hipGetLastError();
-            return fail(h, e == hipErrorOutOfMemory ? MI355REC_ERR_OUT_OF_MEMORY : MI355REC_ERR_HIP, "the priors (%lld rows): %s",
-                        (long long)n, hipGetErrorString(e));
-        }
-    }
-    float* old = const_cast<float*>(priors_of(h));
-    if (old) {
-        (void)hipStreamSynchronize(h->stream);   // (only the synchronous calls on this stream read them)
-        (void)hipFree(old);
-    }
-    h->d_priors = fresh;
-    if (h->shared) h->shared->d_priors = fresh;
-    return MI355REC_OK;
+        hipError_t e = hipMalloc(fresh, sizeof(float) * padded);
+        if (e == hipSuccess) e = hipMemset(*fresh, 0, sizeof(float) * padded);
+        if (e == hipSuccess && n > 0) e = hipMemcpy(*fresh, priors_host, sizeof(float) * static_cast<size_t>(n), hipMemcpyHostToDevice);
+        if (e == hipSuccess) return static_cast<int>(MI355REC_OK);
+        if (*fresh) (void)hipFree(*fresh);
+        return fail(h, e == hipErrorOutOfMemory ? MI355REC_ERR_OUT_OF_MEMORY : MI355REC_ERR_HIP, "the priors (%lld rows): %s",
+                    (long long)n, hipGetErrorString(e));
+    });
 }
 
 constexpr int kPlMinTilesPerWg = 8;   // with the pre-filter: a workgroup scans >= 8 tiles (its anchor bound paid for, its own threshold tight)
@@ -120,12 +102,13 @@ int ensure_playlist(mi355rec* h) {
 // plain mean bit for bit.  r.labels: null, or the label set (include/mi355rec_diag.h, "PLAYLIST REQUESTS"): only rows whose label
 // (mi355rec_set_labels) is in it are admissible; null launches exactly the call without labels.
 //
-// playlist_launch is the call up to and including its scan launch: the checks, the staging and playlist_scan_kernel, which
-// leaves `*grid` lists of `*eff` = min(r.scan_topn(), rows left after the exclusion list) keys in h->d_block_lists.  *eff == 0:
-// nothing is left to return and nothing was launched.  What follows the scan is sync_playlist_query's: the plain call merges
-// into the result slots; the diversified one merges, re-ranks and waits once (engine_diverse.hip.h).
-int playlist_launch(mi355rec* h, const Request& r, int max_exclude, int* eff_out, int* grid_out) {
-    *eff_out = 0;
+// playlist_launch is the call up to and including its scan launch: the checks, sync_begin (engine_sync.hip.h), the staging
+// and playlist_scan_kernel, which leaves `*grid` lists of `ss->eff` = min(r.scan_topn(), rows left after the exclusion list)
+// keys in h->d_block_lists.  ss->eff == 0: nothing is left to return and nothing was begun or launched.  What follows the
+// scan is sync_playlist_query's: the plain call merges into the result slots; the diversified one merges, re-ranks and waits
+// once (engine_diverse.hip.h).
+int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* ss, int* grid_out) {
+    *ss = SyncSlots();
     *grid_out = 0;
     char why[128];
     if (mi355playlist::invalid_playlist(r, h->n, static_cast<int64_t>(UINT32_MAX) + 1, max_exclude, why, sizeof why))
@@ -148,7 +131,7 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, int* eff_out
     // the label set ("PLAYLIST REQUESTS"): at most the selected rows are left (host offsets); nothing selected: no launch
     const mi355rec_labels* L = nullptr;
     if (r.n_labels > 0) {
-        L = labels_of(h);
+        L = h->side->labels;
         if (!L) return fail(h, MI355REC_ERR_INVALID_ARG, "this handle has no labels (mi355rec_set_labels)");
         LabelMask mask;
         int64_t selected = 0, label_tiles = 0;
@@ -160,7 +143,7 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, int* eff_out
     // the prior ("ROW PRIORS"): checked whenever the request carries one; beta == 0 then launches exactly the call without it
     const float* pri = nullptr;
     if (r.prior) {
-        pri = priors_of(h);
+        pri = h->side->d_priors;
         if (!pri) return fail(h, MI355REC_ERR_INVALID_ARG, "this handle has no priors (mi355rec_set_priors)");
         if (r.prior_weight == 0.0f) pri = nullptr;
     }
@@ -183,9 +166,7 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, int* eff_out
     }
     if (r.rows) std::memcpy(b->rows, r.rows, sizeof(int64_t) * static_cast<size_t>(k));
     else std::memcpy(b->members, r.members, sizeof(float) * kDim * static_cast<size_t>(k));
-    rc = ensure_slots(h, static_cast<size_t>(eff));
-    if (rc) return rc;
-    rc = sync_api_begin(h);
+    rc = sync_begin(h, eff, 1, true, ss);
     if (rc) return rc;
     b->shared_thr = 0ull;
     // (the staging buffer is free: the previous call on this handle has completed)
@@ -203,7 +184,6 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, int* eff_out
                  reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr)),
                  reinterpret_cast<const uint2*>(L ? L->d_row_labels : nullptr), reinterpret_cast<const float4*>(pri));
     HIP_TRY(h, hipGetLastError());
-    *eff_out = eff;
     *grid_out = grid;
     return MI355REC_OK;
 }
@@ -211,7 +191,7 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, int* eff_out
 // (engine_diverse.hip.h, included after this file: what a diversified call adds to the path)
 int check_diverse(mi355rec* h, const Request& r);
 int ensure_diverse(mi355rec* h);
-int rerank_and_wait(mi355rec* h, const Request& r, const Outputs& out, int pool, bool staged);
+int rerank_and_wait(mi355rec* h, const Request& r, const Outputs& out, SyncSlots ss, int pool, bool staged);
 
 // The one synchronous path of the family.  max_exclude: kMaxExclude for the exported calls, kPlExcludeCap for the node's.
 int sync_playlist_query(mi355rec* h, const Request& r, const Outputs& out, int max_exclude = kMaxExclude) {
@@ -220,39 +200,27 @@ int sync_playlist_query(mi355rec* h, const Request& r, const Outputs& out, int m
     if (rc) return rc;
     if (out.pool_rows) *out.pool_rows = 0;
     DeviceGuard guard(h->device);
-    int eff = 0, grid = 0;
-    rc = playlist_launch(h, r, max_exclude, &eff, &grid);
+    SyncSlots ss;
+    int grid = 0;
+    rc = playlist_launch(h, r, max_exclude, &ss, &grid);
     if (rc) return rc;
+    const int eff = ss.eff;
     if (eff <= 0) {
         mi355playlist::pad(out, 0, r.topn, 0);
         return MI355REC_OK;
     }
+    // one round: the results always fit the pinned slots and the call's last launch raises the completion word
+    static_assert(kMaxTopK <= kDirectResultSlots, "a playlist call has no copy-back branch");
     if (r.diverse) {   // the pool never leaves the device: no ids or scores are unpacked, the re-rank stores the picks
         rc = ensure_diverse(h);
         if (rc) return rc;
         rc = enqueue_merge(h, h->d_block_lists, grid, eff, eff, h->d_keys, nullptr, nullptr, h->stream);
         if (rc) return rc;
-        return rerank_and_wait(h, r, out, eff, false);
+        return rerank_and_wait(h, r, out, ss, eff, false);
     }
-    const bool direct = eff <= kDirectResultSlots;
-    const uint32_t want = direct ? (++h->done_seq ? h->done_seq : ++h->done_seq) : 0u;   // never 0
-    rc = enqueue_merge(h, h->d_block_lists, grid, eff, eff, h->d_keys, direct ? h->hd_idx : h->d_idx, direct ? h->hd_score : h->d_score,
-                       h->stream, want);
+    rc = enqueue_merge(h, h->d_block_lists, grid, eff, eff, h->d_keys, ss.idx, ss.score, h->stream, ss.want);
     if (rc) return rc;
-    if (direct) {
-        rc = wait_done(h, want);
-        if (rc) return rc;
-    } else {
-        HIP_TRY(h, hipMemcpyAsync(h->h_idx, h->d_idx, eff * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->h_score, h->d_score, eff * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    int c = 0;
-    while (c < eff && h->h_idx[c] >= 0) ++c;
-    std::memcpy(out.idx, h->h_idx, static_cast<size_t>(eff) * sizeof(int64_t));
-    if (out.score) std::memcpy(out.score, h->h_score, static_cast<size_t>(eff) * sizeof(float));
-    mi355playlist::pad(out, eff, r.topn, c);
-    return MI355REC_OK;
+    return sync_finish(h, ss, r.topn, out.idx, out.score, out.count);
 }
 
 }  // namespace

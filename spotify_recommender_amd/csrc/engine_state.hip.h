@@ -1,6 +1,7 @@
 // engine_state.hip.h — the single-device handle behind the C-ABI (include/mi355rec.h): what it owns on the device, how its
 // launch geometries are planned, how it is created and how its launches are timed.  Part of ONE translation unit
-// (mi355rec.hip includes engine_state, engine_single, engine_batch in this order); no CPU fallback anywhere in it.
+// (mi355rec.hip includes engine_state, engine_single, engine_batch, engine_sync, then the engine_labels / _playlist /
+// _diverse features in this order); no CPU fallback anywhere in it.
 //
 // Host side of the drop-in boundary: owns the device-resident catalogue shard (replaces Recommender::initialize's
 // cudaMalloc / cudaMemcpy, Recommender.cu:155-168).
@@ -86,6 +87,15 @@ struct ScanGeom {
 struct mi355rec_labels;   // the label-grouped copy of a shard's rows (engine_labels.hip.h, mi355rec_set_labels)
 struct mi355rec_playlist;   // the buffers of the playlist calls (engine_playlist.hip.h)
 
+// PER-ROW SIDE DATA: what the setters leave beside the rows (engine_labels.hip.h: free_side, replace_side).  It has ONE
+// owner: the handle (mi355rec::own_side), or, once the handle has lanes, the group (SharedRows::side); every member
+// answers from mi355rec::side, which points at the owner's.
+struct RowSide {
+    mi355rec_labels* labels = nullptr;   // mi355rec_set_labels: the rows grouped by label
+    int32_t* d_groups = nullptr;         // mi355rec_set_groups: one int32 per row in local row order, -1 = ungrouped
+    float* d_priors = nullptr;           // mi355rec_set_priors: one fp32 per row in local row order, padded to a whole quad
+};
+
 struct mi355rec {
     int device = 0;
     int64_t n = 0;
@@ -93,29 +103,26 @@ struct mi355rec {
     const float* d_feats = nullptr;
     float* owned_feats = nullptr;
     // LANES (mi355rec_create_lane): further handles over the SAME rows and replicas, each with its own stream state.  Once a
-    // lane exists the rows the first handle owned and both replicas belong to the group: freed by whoever is destroyed last.
+    // lane exists the rows the first handle owned, both replicas and the per-row side data belong to the group: freed by
+    // whoever is destroyed last.
     struct SharedRows {
         std::atomic<int> refs{1};
         void* owned_feats = nullptr;
         void* d_half = nullptr;
         void* d_q8 = nullptr;
         float margin_mix = 0.0f, margin_mfma = 0.0f;   // of the replicas above (half_selfcheck_kernel's verdict)
-        mi355rec_labels* labels = nullptr;             // the labels of the group (set before its first lane was made)
-        int32_t* d_groups = nullptr;                   // the group ids of the group's rows (mi355rec_set_groups), likewise
-        float* d_priors = nullptr;                     // the priors of the group's rows (mi355rec_set_priors), likewise
+        RowSide side;                                  // what the first handle's setters had left when its first lane was made
     };
     SharedRows* shared = nullptr;
     bool is_lane = false;
     int lane_stream_attempts = 0;   // streams mi355rec_create_lane went through until one overlapped the parent's (0: not tested)
     int lane_overlaps = -1;         // 1: the lane's stream and its parent's run kernels side by side; 0: no such stream was found; -1: not tested
-    // LABELS (mi355rec_set_labels): the rows grouped by label; owned by the handle, or by the group once it has lanes
-    mi355rec_labels* labels = nullptr;
+    // LABELS, GROUP CAPS, ROW PRIORS: the handle's own side data (empty once the group owns it), and the one it answers
+    // from: &own_side, or &shared->side from the first lane on (a lane's always)
+    RowSide own_side;
+    RowSide* side = &own_side;
     int64_t label_queries = 0;          // filtered queries since create ...
     int64_t label_rows_scanned = 0;     // ... and the rows their launches scanned (whole tiles)
-    // GROUP CAPS (mi355rec_set_groups): one int32 per row in local row order, -1 = ungrouped; owned like the labels
-    int32_t* d_groups = nullptr;
-    // ROW PRIORS (mi355rec_set_priors): one fp32 per row in local row order, padded to a whole quad; owned like the labels
-    float* d_priors = nullptr;
     // PLAYLISTS (mi355rec_query_mean_topn / _query_playlist_topn): allocated by the first call, owned by the handle (lanes have their own)
     mi355rec_playlist* playlist = nullptr;
     int64_t playlist_queries = 0;

@@ -1,8 +1,9 @@
 // mi355rec.hip — the C-ABI (include/mi355rec.h) over the gfx950 kernels: every entry point validates its arguments, picks
-// the device and the stream order, and hands over to the engine (engine_state / engine_single / engine_batch .hip.h, all part
+// the device and the stream order, and hands over to the engine (engine_state / engine_single / engine_batch / engine_sync .hip.h, all part
 // of this one translation unit).  Replaces the reference's Recommender internals (Recommender.cu:100-318) behind
 // include/Recommender.h.  No CPU fallback anywhere in this file.
 #include "engine_batch.hip.h"
+#include "engine_sync.hip.h"
 #include "engine_labels.hip.h"
 #include "engine_playlist.hip.h"
 #include "engine_diverse.hip.h"
@@ -92,9 +93,7 @@ void mi355rec_destroy(mi355rec_t* h) {
     if (h->d_mstream_ctl) (void)hipFree(h->d_mstream_ctl);
     for (hipEvent_t e : h->ev_pass) (void)hipEventDestroy(e);
     if (h->owned_feats && !h->shared) (void)hipFree(h->owned_feats);
-    if (!h->shared) free_labels(h->labels);
-    if (!h->shared && h->d_groups) (void)hipFree(h->d_groups);
-    if (!h->shared && h->d_priors) (void)hipFree(h->d_priors);
+    if (!h->shared) free_side(h->own_side);
     free_playlist(h->playlist);
     if (h->d_block_lists) (void)hipFree(h->d_block_lists);
     if (h->d_lone_ctr) (void)hipFree(h->d_lone_ctr);
@@ -122,9 +121,7 @@ void mi355rec_destroy(mi355rec_t* h) {
         void* bufs[] = {h->shared->owned_feats, h->shared->d_half, h->shared->d_q8};
         for (void* b : bufs)
             if (b) (void)hipFree(b);
-        free_labels(h->shared->labels);
-        if (h->shared->d_groups) (void)hipFree(h->shared->d_groups);
-        if (h->shared->d_priors) (void)hipFree(h->shared->d_priors);
+        free_side(h->shared->side);
         delete h->shared;
     }
     delete h;
@@ -225,12 +222,13 @@ int mi355rec_create_lane(mi355rec_t* parent, mi355rec_t** out) {
         group->d_q8 = parent->d_q8;
         group->margin_mix = parent->margin_mix;
         group->margin_mfma = parent->margin_mfma;
-        group->labels = parent->labels;   // (a lane made after mi355rec_set_labels shares them: nothing is copied)
-        group->d_groups = parent->d_groups;   // (mi355rec_set_groups: likewise)
-        group->d_priors = parent->d_priors;   // (mi355rec_set_priors: likewise)
+        group->side = parent->own_side;   // (labels, groups, priors: a lane made after their setters shares them, nothing is copied)
+        parent->own_side = RowSide();
+        parent->side = &group->side;
     }
     parent->shared->refs.fetch_add(1);
     lane->shared = parent->shared;
+    lane->side = &parent->shared->side;
     lane->d_half = parent->d_half;
     lane->d_q8 = parent->d_q8;
     lane->margin_mix = parent->margin_mix;
@@ -903,38 +901,12 @@ int mi355rec_query_batch_topn(mi355rec_t* h, const float* queries, int batch,
     DeviceGuard guard(h->device);
     // internal lists are `eff` long: a shard of n rows cannot return more
     const int eff = static_cast<int64_t>(topn) < h->n ? topn : static_cast<int>(h->n);
-    const size_t cnt = static_cast<size_t>(batch) * eff;
-    rc = ensure_slots(h, cnt);
+    SyncSlots ss;
+    rc = sync_begin(h, eff, batch, false, &ss);   // (never notifies: enqueue_batch's launches raise no completion word)
     if (rc) return rc;
-    rc = sync_api_begin(h);
+    rc = enqueue_batch(h, queries, exclude_global, batch, eff, h->d_keys, ss.idx, ss.score, h->stream);
     if (rc) return rc;
-    const bool direct = cnt <= static_cast<size_t>(kDirectResultSlots);
-    rc = enqueue_batch(h, queries, exclude_global, batch, eff, h->d_keys, direct ? h->hd_idx : h->d_idx,
-                       direct ? h->hd_score : h->d_score, h->stream);
-    if (rc) return rc;
-    if (!direct) {
-        HIP_TRY(h, hipMemcpyAsync(h->h_idx, h->d_idx, cnt * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->h_score, h->d_score, cnt * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (int b = 0; b < batch; ++b) {
-        const int64_t* src_i = h->h_idx + static_cast<size_t>(b) * eff;
-        const float* src_s = h->h_score + static_cast<size_t>(b) * eff;
-        int64_t* dst_i = out_idx + static_cast<size_t>(b) * topn;
-        std::memcpy(dst_i, src_i, static_cast<size_t>(eff) * sizeof(int64_t));
-        for (int i = eff; i < topn; ++i) dst_i[i] = -1;
-        if (out_score) {
-            float* dst_s = out_score + static_cast<size_t>(b) * topn;
-            std::memcpy(dst_s, src_s, static_cast<size_t>(eff) * sizeof(float));
-            for (int i = eff; i < topn; ++i) dst_s[i] = 0.0f;
-        }
-        if (out_count) {
-            int c = 0;
-            while (c < eff && src_i[c] >= 0) ++c;
-            out_count[b] = c;
-        }
-    }
-    return MI355REC_OK;
+    return sync_finish(h, ss, topn, out_idx, out_score, out_count);
 }
 
 namespace {
@@ -947,42 +919,16 @@ int sync_single_query(mi355rec_t* h, const float* qptr, const float* query12, in
     int rc = check_topn(h, topn, true);
     if (rc) return rc;
     DeviceGuard guard(h->device);
-    // device / pinned slots are sized by what the shard can return, not by topn
+    // device / pinned slots are sized by what the shard can return, not by topn.  Small results go straight into the pinned
+    // host buffers from the merge kernel (zero-copy stores over PCIe: no D2H copy launches on the latency path); one round
+    // (eff <= 1024) also stores a completion word there, and the host spins on the word.
     const int eff = static_cast<int64_t>(topn) < h->n ? topn : static_cast<int>(h->n);
-    rc = ensure_slots(h, static_cast<size_t>(eff));
+    SyncSlots ss;
+    rc = sync_begin(h, eff, 1, true, &ss);
     if (rc) return rc;
-    rc = sync_api_begin(h);
+    rc = enqueue_query(h, qptr, query12, exclude_global, eff, h->d_keys, ss.idx, ss.score, h->stream, ss.want);
     if (rc) return rc;
-    // Small results go straight into the pinned host buffers from the merge kernel
-    // (zero-copy stores over PCIe: no D2H copy launches on the latency path).
-    const bool direct = eff <= kDirectResultSlots;
-    // one round (eff <= 1024): the merge kernel stores the results AND a completion word in pinned host
-    // memory; the host spins on the word
-    const bool notify = direct && eff <= kMaxTopK && eff > 0;
-    const uint32_t want = notify ? (++h->done_seq ? h->done_seq : ++h->done_seq) : 0u;   // never 0
-    rc = enqueue_query(h, qptr, query12, exclude_global, eff, h->d_keys, direct ? h->hd_idx : h->d_idx,
-                       direct ? h->hd_score : h->d_score, h->stream, want);
-    if (rc) return rc;
-    if (!direct) {
-        HIP_TRY(h, hipMemcpyAsync(h->h_idx, h->d_idx, eff * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->h_score, h->d_score, eff * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    }
-    if (notify) {
-        rc = wait_done(h, want);
-        if (rc) return rc;
-    } else {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    int c = 0;
-    while (c < eff && h->h_idx[c] >= 0) ++c;
-    std::memcpy(out_idx, h->h_idx, static_cast<size_t>(eff) * sizeof(int64_t));
-    if (out_score) std::memcpy(out_score, h->h_score, static_cast<size_t>(eff) * sizeof(float));
-    for (int i = eff; i < topn; ++i) {
-        out_idx[i] = -1;
-        if (out_score) out_score[i] = 0.0f;
-    }
-    if (out_count) *out_count = c;
-    return MI355REC_OK;
+    return sync_finish(h, ss, topn, out_idx, out_score, out_count);
 }
 }  // namespace
 

@@ -237,6 +237,33 @@ int create_on(const float* feats_host, int64_t n, int dim, const int* devices, i
     return MI355REC_OK;
 }
 
+// ---- PER-ROW SIDE DATA: labels, groups, priors (the setters below) ----
+// One attribute on every shard that owns side data, all or nothing.  The caller's thread drives every shard itself (the
+// workers are drained first); a replica on a device that already holds one is a lane of it and shares that one's side data,
+// so it is skipped.  set_shard(engine, shard) sets the attribute from the shard's slice, set_shard(engine, nullptr) drops it:
+// where one shard fails it is dropped on every shard, so that none keeps what the others do not have.
+template <class SetShard>
+int set_on_every_shard(mi355rec_sharded_t* h, const char* noun, SetShard set_shard) {
+    DeviceRestore restore;
+    int rc = drain_workers(h);
+    if (rc) return rc;
+    for (size_t r = 0; r < h->shards.size(); ++r) {
+        Shard& s = h->shards[r];
+        bool lane = false;
+        for (size_t p = 0; p < r && h->replicated && !lane; ++p) lane = h->shards[p].device == s.device;
+        if (lane) continue;
+        S_HIP(h, hipSetDevice(s.device));
+        rc = set_shard(s.engine, &s);
+        if (rc != MI355REC_OK) {
+            const std::string why = mi355rec_last_error(s.engine);
+            for (Shard& o : h->shards)
+                if (hipSetDevice(o.device) == hipSuccess) (void)set_shard(o.engine, nullptr);
+            return sfail(h, rc, "shard on device %d: %s (the %s were dropped on every shard)", s.device, why.c_str(), noun);
+        }
+    }
+    return MI355REC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -517,24 +544,9 @@ int mi355rec_sharded_set_labels(mi355rec_sharded_t* h, const int32_t* labels_hos
         const char* why = nullptr;
         return cpu_result(h, mi355cpu::node_set_labels(h->cpu, labels_host, n, &why), why);
     }
-    DeviceRestore restore;
-    int rc = drain_workers(h);   // the caller's thread drives every shard itself
-    if (rc) return rc;
-    for (size_t r = 0; r < h->shards.size(); ++r) {
-        Shard& s = h->shards[r];
-        bool lane = false;   // a replica on a device that already holds one is a lane of it: it shares that one's labels
-        for (size_t p = 0; p < r && h->replicated && !lane; ++p) lane = h->shards[p].device == s.device;
-        if (lane) continue;
-        S_HIP(h, hipSetDevice(s.device));
-        rc = mi355node::set_group_labels(s.engine, labels_host ? labels_host + s.lo : nullptr, s.hi - s.lo);
-        if (rc != MI355REC_OK) {   // all or nothing: no shard keeps labels the others do not have
-            const std::string why = mi355rec_last_error(s.engine);
-            for (Shard& o : h->shards)
-                if (hipSetDevice(o.device) == hipSuccess) (void)mi355node::set_group_labels(o.engine, nullptr, 0);
-            return sfail(h, rc, "shard on device %d: %s (the labels were dropped on every shard)", s.device, why.c_str());
-        }
-    }
-    return MI355REC_OK;
+    return set_on_every_shard(h, "labels", [&](mi355rec_t* e, const Shard* s) {
+        return s && labels_host ? mi355node::set_group_labels(e, labels_host + s->lo, s->hi - s->lo) : mi355node::set_group_labels(e, nullptr, 0);
+    });
 }
 
 // ---- GROUP CAPS (include/mi355rec_diag.h) -----------------------------------------------------------------------------
@@ -550,10 +562,10 @@ int mi355rec_sharded_set_groups(mi355rec_sharded_t* h, const int32_t* groups_hos
         if (groups_host[i] < -1)
             return sfail(h, MI355REC_ERR_INVALID_ARG, "group %d of row %lld: a group id is >= 0, or -1 for no group",
                          static_cast<int>(groups_host[i]), (long long)i);
-    DeviceRestore restore;
-    int rc = drain_workers(h);   // the caller's thread drives every shard itself
-    if (rc) return rc;
     if (h->shards.size() > 1 && !h->replicated) {   // row-sharded: the host copy alone
+        DeviceRestore restore;
+        const int rc = drain_workers(h);
+        if (rc) return rc;
         if (!groups_host) {
             h->groups.clear();
             h->has_groups = false;
@@ -567,21 +579,9 @@ int mi355rec_sharded_set_groups(mi355rec_sharded_t* h, const int32_t* groups_hos
         h->has_groups = true;
         return MI355REC_OK;
     }
-    for (size_t r = 0; r < h->shards.size(); ++r) {
-        Shard& s = h->shards[r];
-        bool lane = false;   // a replica on a device that already holds one is a lane of it: it shares that one's groups
-        for (size_t p = 0; p < r && h->replicated && !lane; ++p) lane = h->shards[p].device == s.device;
-        if (lane) continue;
-        S_HIP(h, hipSetDevice(s.device));
-        rc = mi355node::set_group_groups(s.engine, groups_host ? groups_host + s.lo : nullptr, s.hi - s.lo);
-        if (rc != MI355REC_OK) {   // all or nothing: no replica keeps groups the others do not have
-            const std::string why = mi355rec_last_error(s.engine);
-            for (Shard& o : h->shards)
-                if (hipSetDevice(o.device) == hipSuccess) (void)mi355node::set_group_groups(o.engine, nullptr, 0);
-            return sfail(h, rc, "shard on device %d: %s (the groups were dropped on every shard)", s.device, why.c_str());
-        }
-    }
-    return MI355REC_OK;
+    return set_on_every_shard(h, "groups", [&](mi355rec_t* e, const Shard* s) {
+        return s && groups_host ? mi355node::set_group_groups(e, groups_host + s->lo, s->hi - s->lo) : mi355node::set_group_groups(e, nullptr, 0);
+    });
 }
 
 // ---- ROW PRIORS (include/mi355rec_diag.h) -----------------------------------------------------------------------------
@@ -597,27 +597,13 @@ int mi355rec_sharded_set_priors(mi355rec_sharded_t* h, const float* priors_host,
         const char* why = nullptr;
         return cpu_result(h, mi355cpu::node_set_priors(h->cpu, priors_host, n, &why), why);
     }
-    DeviceRestore restore;
-    int rc = drain_workers(h);   // the caller's thread drives every shard itself
-    if (rc) return rc;
     // every replica the whole array, every shard of a row-sharded placement its slice (each scans its own rows' priors)
-    for (size_t r = 0; r < h->shards.size(); ++r) {
-        Shard& s = h->shards[r];
-        bool lane = false;   // a replica on a device that already holds one is a lane of it: it shares that one's priors
-        for (size_t p = 0; p < r && h->replicated && !lane; ++p) lane = h->shards[p].device == s.device;
-        if (lane) continue;
-        S_HIP(h, hipSetDevice(s.device));
-        rc = mi355node::set_group_priors(s.engine, priors_host ? priors_host + s.lo : nullptr, s.hi - s.lo);
-        if (rc != MI355REC_OK) {   // all or nothing: no shard keeps priors the others do not have
-            const std::string why = mi355rec_last_error(s.engine);
-            for (Shard& o : h->shards)
-                if (hipSetDevice(o.device) == hipSuccess) (void)mi355node::set_group_priors(o.engine, nullptr, 0);
-            h->has_priors = false;
-            return sfail(h, rc, "shard on device %d: %s (the priors were dropped on every shard)", s.device, why.c_str());
-        }
-    }
-    h->has_priors = priors_host != nullptr;
-    return MI355REC_OK;
+    const int rc = set_on_every_shard(h, "priors", [&](mi355rec_t* e, const Shard* s) {
+        if (!s) h->has_priors = false;   // (dropped on every shard after one failed)
+        return s && priors_host ? mi355node::set_group_priors(e, priors_host + s->lo, s->hi - s->lo) : mi355node::set_group_priors(e, nullptr, 0);
+    });
+    if (rc == MI355REC_OK) h->has_priors = priors_host != nullptr;
+    return rc;
 }
 
 namespace {
