@@ -158,6 +158,16 @@ public:
                                           const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude, float lambda,
                                           int pool, int maxPerArtist, const std::vector<int>& genreIds = {}, float priorWeight = 0.0f);
 
+    // Extension: nearest songs by Euclidean distance (the reference's "Additional Metrics: Euclidean").  recommendNearest
+    // returns the ids of the topN songs NEAREST to the songs of songIndices (1 to 32; never returned themselves) over the 12
+    // features of the matrix, nearest first; lastScores() holds the DISTANCES (ascending): for one song the Euclidean distance,
+    // for several the root-mean-square distance to them, which ranks as the distance to their centroid does.  Cosine ignores
+    // magnitude; on the min-max normalised matrix of songs_data.bin the distance does not.  `where` and `genreIds` as above
+    // (both may be empty).  Weights, diversity, caps and priors are not served with this metric.  Same messages and {} on bad
+    // input as recommendForPlaylist.
+    std::vector<int> recommendNearest(const std::vector<int>& songIndices, int topN, const std::vector<FeatureRange>& where = {},
+                                      const std::vector<int>& genreIds = {});
+
     struct Impl;   // opaque: defined in Recommender.cpp
 
 private:

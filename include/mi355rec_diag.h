@@ -28,6 +28,8 @@
  *     (mi355rec_query_playlist_request and its node-handle twin);
  *   - ROW PRIORS: a per-row prior (popularity, freshness, a boost or a demotion) blended into the request's ranking value
  *     (mi355rec_set_priors, MI355REC_PQ_PRIOR and prior_weight of the request, and the node-handle twin);
+ *   - DISTANCE REQUESTS: the nearest rows by Euclidean distance to up to 32 members, with the playlist request's exclusion
+ *     list, feature filter and label set (mi355rec_query_distance_request and its node-handle twin);
  *   - test hooks, compiled in only with -DMI355REC_TEST_HOOKS (spotify_recommender_amd/build.py builds
  *     libmi355rec_testhooks.so for tests/; the product library does not export them).
  */
@@ -679,6 +681,61 @@ int mi355rec_sharded_query_playlist_request(mi355rec_sharded_t* h, const mi355re
 #define MI355REC_MAX_PRIOR_WEIGHT 4.0f
 int mi355rec_set_priors(mi355rec_t* h, const float* priors_host, int64_t n);
 int mi355rec_sharded_set_priors(mi355rec_sharded_t* h, const float* priors_host, int64_t n);
+
+/* DISTANCE REQUESTS (an extension the reference lists as "Additional Metrics: Euclidean"): the top-N rows NEAREST to up to 32
+ * members by Euclidean distance over the 12 features.  Cosine ignores magnitude; on a catalogue normalised per feature (what
+ * DataManager writes) the distance is a different and meaningful notion of "sounds like this".
+ * The playlist request's struct is frozen, so the metric has its own struct and entry points.  mi355rec_distance_query_t carries
+ * its own size under the rules of mi355rec_playlist_query_t: a shorter struct that ends where a field ends is read as "later
+ * fields zero"; a size of 0, one that ends inside a field, or one larger than this library knows is INVALID_ARG.
+ *   members / rows   exactly one is non-NULL: k x 12 floats by value, or k rows of the handle (local rows of a single handle,
+ *                    global rows of a node handle; never returned); 1 <= k <= MI355REC_MAX_PLAYLIST;
+ *   exclude_global / n_exclude, filter, labels / n_labels   as in the playlist request;
+ *   topn             in [1, MI355REC_MAX_TOPN_FAST];       flags   must be 0.
+ * mi355rec_distance_result_t: out_idx (topn slots) is required; out_distance (topn) and out_count may be NULL.
+ * RANKING VALUE, per row x, bit for bit (fp32, subtract, multiply THEN add, never fused; members in order):
+ *     d2_k(x) = acc after j = 0..11 of:  t = fl(q_kj - x_j);  acc = fl(acc + fl(t * t))          (acc starts at 0.0f)
+ *     m(x)    = fl( fl(...fl(d2_0 + d2_1) + ... + d2_{k-1}) / (float)k )                         (k = 1: m = d2_0)
+ * Rows are ranked by m ascending, then row ascending (keys are packed from -m, so every selection and merge of the playlist
+ * family serves them unchanged).  out_distance = sqrtf(m), taken on the host: for k = 1 the Euclidean distance, for k > 1 the
+ * root-mean-square distance to the members — as a RANKING that is the distance to their centroid.
+ * A row is admissible iff m(x) is finite (a row or member holding NaN or inf, or a sum that overflows, is never listed), it is
+ * neither excluded nor a member row, it passes the feature filter if there is one and its label is in the label set if there
+ * is one.  count = min(topn, |admissible rows|), the rest padded with -1 / 0.0f.
+ * INVALID_ARG (with a message): flags != 0; both or neither of members and rows; a bad size; everything the playlist request
+ * refuses for the fields the two share (same limits, same messages).
+ * Device: a uniform runtime branch of playlist_scan_kernel (csrc/playlist.hip.h, "DISTANCE"): no new kernel.  With the 8-bit
+ * replica the scan streams 12 + 4 B per row: the replica's dot product with the members' centroid and the row's norm (a
+ * 4 B/row array the handle's first distance request builds, q8_build_kernel's second output) bound m(x) from below, a per-row
+ * integer cut rules rows out and only the survivors take the k chains on the fp32 rows.  The results are the same with the
+ * replica on and off, bit for bit.  On a catalogue that is one tight cluster, or that has one dominant unnormalised feature,
+ * the bound rules little out and the call runs at the exact path's speed.  mi355rec_playlist_counters counts these calls
+ * and the rows whose chains they computed as it counts the others.
+ * Node handle: one shard forwards; a replicated placement asks one replica; a row-sharded one fetches members given by row,
+ * forwards the request to every shard and merges the shards' keys on the host, which is exact because keys carry -m.  The CPU
+ * backend serves the same call with the same chain.
+ * Not served: weights, diversified and capped calls, priors (there is no field for them). */
+typedef struct {
+    uint32_t size;                    /* sizeof(mi355rec_distance_query_t) of the caller's header */
+    uint32_t flags;                   /* must be 0 */
+    const float* members;             /* k x 12 floats (host), or NULL with ... */
+    const int64_t* rows;              /* ... k rows of the handle */
+    const int64_t* exclude_global;    /* n_exclude global ids, or NULL */
+    const mi355rec_filter_t* filter;  /* NULL, or the feature filter */
+    const int32_t* labels;            /* NULL, or n_labels labels */
+    int32_t k;
+    int32_t n_exclude;
+    int32_t n_labels;
+    int32_t topn;
+} mi355rec_distance_query_t;
+typedef struct {
+    int64_t* out_idx;                 /* topn slots; required */
+    float* out_distance;              /* topn slots, or NULL */
+    int* out_count;                   /* or NULL */
+} mi355rec_distance_result_t;
+int mi355rec_query_distance_request(mi355rec_t* h, const mi355rec_distance_query_t* query, const mi355rec_distance_result_t* result);
+int mi355rec_sharded_query_distance_request(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
+                                            const mi355rec_distance_result_t* result);
 
 #ifdef MI355REC_TEST_HOOKS
 /* TEST HOOK for the cross-workgroup hand-offs of the streamed scans (csrc/replica.hip.h, "hand-offs that fail

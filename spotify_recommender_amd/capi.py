@@ -63,6 +63,18 @@ class PlaylistResult(ctypes.Structure):
                 ("out_pool_rows", POINTER(c_int))]
 
 
+class DistanceQuery(ctypes.Structure):
+    """mi355rec_distance_query_t (include/mi355rec_diag.h, DISTANCE REQUESTS); `size` is sizeof of this struct, flags 0."""
+    _fields_ = [("size", c_uint32), ("flags", c_uint32), ("members", c_void_p), ("rows", c_void_p), ("exclude_global", c_void_p),
+                ("filter", POINTER(Filter)), ("labels", c_void_p), ("k", c_int32), ("n_exclude", c_int32), ("n_labels", c_int32),
+                ("topn", c_int32)]
+
+
+class DistanceResult(ctypes.Structure):
+    """mi355rec_distance_result_t: every pointer but out_idx may be NULL."""
+    _fields_ = [("out_idx", c_void_p), ("out_distance", c_void_p), ("out_count", POINTER(c_int))]
+
+
 class Stats(ctypes.Structure):
     _fields_ = [
         ("rows", c_int64),
@@ -231,6 +243,8 @@ SIGNATURES = {
     "mi355rec_sharded_set_priors": (c_int, [c_void_p, c_void_p, c_int64]),
     "mi355rec_query_playlist_request": (c_int, [c_void_p, POINTER(PlaylistQuery), POINTER(PlaylistResult)]),
     "mi355rec_sharded_query_playlist_request": (c_int, [c_void_p, POINTER(PlaylistQuery), POINTER(PlaylistResult)]),
+    "mi355rec_query_distance_request": (c_int, [c_void_p, POINTER(DistanceQuery), POINTER(DistanceResult)]),
+    "mi355rec_sharded_query_distance_request": (c_int, [c_void_p, POINTER(DistanceQuery), POINTER(DistanceResult)]),
     "mi355rec_pack_key": (c_uint64, [c_float, c_int64]),
     "mi355rec_key_score": (c_float, [c_uint64]),
     "mi355rec_key_row": (c_int64, [c_uint64]),

@@ -517,6 +517,58 @@ std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songI
                                  &genreIds, priorWeight);
 }
 
+std::vector<int> Recommender::recommendNearest(const std::vector<int>& songIndices, int topN, const std::vector<FeatureRange>& where,
+                                               const std::vector<int>& genreIds) {
+    Impl* impl = impl_;
+    if (!impl->initialized) {
+        std::cerr << "Error: Recommender not initialized" << std::endl;
+        return {};
+    }
+    if (songIndices.empty() || songIndices.size() > MI355REC_MAX_PLAYLIST) {
+        std::cerr << "Error: a playlist holds 1 to " << MI355REC_MAX_PLAYLIST << " songs" << std::endl;
+        return {};
+    }
+    std::vector<int64_t> rows(songIndices.begin(), songIndices.end());
+    for (int64_t i : rows)
+        if (i < 0 || i >= impl->numSongs) {
+            std::cerr << "Error: Invalid song index: " << i << std::endl;
+            return {};
+        }
+    if (topN <= 0) {
+        std::cerr << "Error: topN must be positive" << std::endl;
+        return {};
+    }
+    if (topN > impl->numSongs) topN = impl->numSongs;
+    mi355rec_filter_t f;
+    if (!makeFilter(where, f)) return {};
+    if (!genreIds.empty() && !uploadLabels(impl)) return {};
+    impl->idxBuf.assign(static_cast<size_t>(topN), -1);
+    impl->scoreBuf.assign(static_cast<size_t>(topN), 0.0f);
+    int count = 0;
+    mi355rec_distance_query_t q{};
+    q.size = sizeof q;
+    q.rows = rows.data();
+    q.k = static_cast<int32_t>(rows.size());
+    q.filter = where.empty() ? nullptr : &f;
+    if (!genreIds.empty()) {
+        q.labels = genreIds.data();
+        q.n_labels = static_cast<int32_t>(genreIds.size());
+    }
+    q.topn = topN;
+    mi355rec_distance_result_t res{};
+    res.out_idx = impl->idxBuf.data();
+    res.out_distance = impl->scoreBuf.data();
+    res.out_count = &count;
+    if (mi355rec_sharded_query_distance_request(impl->engine, &q, &res) != MI355REC_OK) {
+        std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
+        return {};
+    }
+    std::vector<int> results(static_cast<size_t>(count));
+    for (int i = 0; i < count; ++i) results[i] = static_cast<int>(impl->idxBuf[i]);
+    impl->lastScores.assign(impl->scoreBuf.begin(), impl->scoreBuf.begin() + count);
+    return results;
+}
+
 std::vector<int> Recommender::recommendByIndexCapped(int songIndex, int topN, int maxPerArtist, float lambda, int pool,
                                                      const std::vector<FeatureRange>& where) {
     if (!checkQuery(impl_, songIndex, topN)) return {};

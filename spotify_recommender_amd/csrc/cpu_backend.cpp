@@ -423,8 +423,26 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
     std::vector<float> w(static_cast<size_t>(k), 1.0f);
     if (weights) w.assign(weights, weights + k);
     const float wsum = weights ? mi355weights::sum_abs(weights, k) : static_cast<float>(k);
+    // "DISTANCE REQUESTS": m(x) = fl(fl(d2_0 + ... + d2_{k-1}) / k), d2_k the sequential fp32 sum of fl(t * t), t = fl(q_kj - x_j);
+    // keys carry -m, a row whose m is not finite gets no key (it is not admissible).
+    const bool dist = r.metric == mi355playlist::kDistance;
 #pragma omp parallel for schedule(static) num_threads(c->threads)
     for (int64_t i = 0; i < n; ++i) {
+        if (dist) {
+            float sum = 0.0f;
+            for (int m = 0; m < k; ++m) {
+                float acc = 0.0f;
+                for (int j = 0; j < kDim; ++j) {
+                    const float t = members[m * kDim + j] - f[i * kDim + j];
+                    const float sq = t * t;
+                    acc = acc + sq;
+                }
+                sum = m == 0 ? acc : sum + acc;
+            }
+            const float mean = sum / static_cast<float>(k);
+            keys[static_cast<size_t>(i)] = std::isfinite(mean) ? pack(-mean, static_cast<uint32_t>(i)) : 0;
+            continue;
+        }
         float sum = w[0] * score(members, qn[0], f + i * kDim);
         for (int m = 1; m < k; ++m) {
             const float term = w[static_cast<size_t>(m)] * score(members + m * kDim, qn[static_cast<size_t>(m)], f + i * kDim);
@@ -440,6 +458,7 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
     for (int64_t e : excl)
         if (e >= 0 && e < n) keys[static_cast<size_t>(e)] = 0;   // (a real key is never 0: its low half is ~row)
     int64_t avail = n - static_cast<int64_t>(std::count_if(excl.begin(), excl.end(), [n](int64_t e) { return e >= 0 && e < n; }));
+    if (dist) avail = static_cast<int64_t>(std::count_if(keys.begin(), keys.end(), [](uint64_t key) { return key != 0; }));
     if (filter && filter->active) {   // the rows failing the filter go like excluded ones
         avail = 0;
         for (int64_t i = 0; i < n; ++i) {
@@ -466,6 +485,7 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
         if (out.score) out.score[i] = unordered(static_cast<uint32_t>(keys[static_cast<size_t>(i)] >> 32)) + 0.0f;
     }
     mi355playlist::pad(out, count, topn_asked, count);
+    if (r.report_distance) mi355playlist::scores_to_distances(out, topn_asked);
     return MI355REC_OK;
 }
 

@@ -27,6 +27,12 @@ struct mi355rec_playlist {
     int* h_pool_rows = nullptr;             // P' of the last capped call: one more word of the pinned h_mmr allocation ...
     int* hd_pool_rows = nullptr;            // ... at this device-side address
     int32_t* d_pool_groups = nullptr;       // kMaxTopK groups: those of a pool passed by value, in pool order
+    // DISTANCE REQUESTS (playlist.hip.h, "DISTANCE"): |x| of every row in local row order, padded to a whole quad, 4 B per row.
+    // Built by the handle's first distance request that scans the 8-bit replica (q8_build_kernel with a null replica pointer, on
+    // the handle's stream) and dropped by mi355rec_rebuild_replica: a snapshot of the rows, as the replica is.  It belongs to
+    // THIS handle, not to RowSide: a lane builds and holds its own, so no lane ever builds under another lane's launch.
+    float* d_norms = nullptr;
+    bool norms_built = false;               // the build has been enqueued on the handle's stream: only then may a scan read d_norms
 };
 
 namespace {
@@ -66,6 +72,7 @@ void free_playlist(mi355rec_playlist* P) {
     if (P->h_mmr) (void)hipHostFree(P->h_mmr);
     if (P->d_rows) (void)hipFree(P->d_rows);
     if (P->d_pool_groups) (void)hipFree(P->d_pool_groups);
+    if (P->d_norms) (void)hipFree(P->d_norms);
     delete P;
 }
 
@@ -159,6 +166,7 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     arg.labelled = L ? 1 : 0;
     arg.prior = pri ? 1 : 0;
     arg.prior_weight = pri ? r.prior_weight : 0.0f;
+    arg.metric = r.metric == mi355playlist::kDistance ? kPlDistance : kPlCosine;
     for (int m = 0; m < k; ++m) b->weights[m] = r.weights ? r.weights[m] : 1.0f;
     if (arg.active) {
         std::memcpy(b->lo, r.filter->lo, sizeof b->lo);
@@ -166,13 +174,32 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     }
     if (r.rows) std::memcpy(b->rows, r.rows, sizeof(int64_t) * static_cast<size_t>(k));
     else std::memcpy(b->members, r.members, sizeof(float) * kDim * static_cast<size_t>(k));
+    // "DISTANCE REQUESTS": the rows' norms, once per handle (and per rebuild).  Allocated before the call is begun: a failure
+    // here leaves nothing begun and nothing staged.
+    const uint4* q8 = use_q8(h) ? h->d_q8 : nullptr;
+    const int64_t n_quads4 = (h->n + 3) / 4 * 4;
+    const bool fresh_norms = q8 && arg.metric == kPlDistance && !P->norms_built;
+    if (fresh_norms && !P->d_norms) {   // (an earlier call that failed before its build was enqueued has left the allocation)
+        const hipError_t e = hipMalloc(&P->d_norms, sizeof(float) * static_cast<size_t>(n_quads4));
+        if (e != hipSuccess) {
+            P->d_norms = nullptr;
+            (void)hipGetLastError();
+            return fail(h, e == hipErrorOutOfMemory ? MI355REC_ERR_OUT_OF_MEMORY : MI355REC_ERR_HIP, "the row norms (%lld rows): %s",
+                        (long long)h->n, hipGetErrorString(e));
+        }
+    }
     rc = sync_begin(h, eff, 1, true, ss);
     if (rc) return rc;
     b->shared_thr = 0ull;
     // (the staging buffer is free: the previous call on this handle has completed)
     const size_t bytes = offsetof(PlaylistBuf, excl) + sizeof(uint32_t) * static_cast<size_t>(n_excl);
     HIP_TRY(h, hipMemcpyAsync(P->d_buf, b, bytes, hipMemcpyHostToDevice, h->stream));
-    const uint4* q8 = use_q8(h) ? h->d_q8 : nullptr;
+    if (fresh_norms) {   // (on the handle's stream, ahead of the scan that reads them)
+        hipLaunchKernelGGL(q8_build_kernel, dim3(static_cast<unsigned>((n_quads4 + 255) / 256)), dim3(256), 0, h->stream, h->d_feats, h->n,
+                           n_quads4, static_cast<uint32_t*>(nullptr), P->d_norms);
+        HIP_TRY(h, hipGetLastError());
+        P->norms_built = true;   // (only now: every exit above leaves an array that the next request builds)
+    }
     const int64_t tiles = ((h->n + 3) / 4 + PlaylistCfg::kBlock - 1) / PlaylistCfg::kBlock;
     int64_t want_grid = q8 ? (tiles + kPlMinTilesPerWg - 1) / kPlMinTilesPerWg : tiles;
     if (want_grid > P->grid_cap) want_grid = P->grid_cap;
@@ -182,7 +209,8 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
                  h->stream, h->d_feats, q8, h->n, h->row_base, static_cast<const PlaylistBuf*>(P->d_buf), arg,
                  static_cast<const float*>(h->d_anchor), eff, h->d_block_lists, P->d_exact,
                  reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr)),
-                 reinterpret_cast<const uint2*>(L ? L->d_row_labels : nullptr), reinterpret_cast<const float4*>(pri));
+                 reinterpret_cast<const uint2*>(L ? L->d_row_labels : nullptr), reinterpret_cast<const float4*>(pri),
+                 reinterpret_cast<const float4*>(arg.metric == kPlDistance && q8 ? P->d_norms : nullptr));
     HIP_TRY(h, hipGetLastError());
     *grid_out = grid;
     return MI355REC_OK;
@@ -220,7 +248,9 @@ int sync_playlist_query(mi355rec* h, const Request& r, const Outputs& out, int m
     }
     rc = enqueue_merge(h, h->d_block_lists, grid, eff, eff, h->d_keys, ss.idx, ss.score, h->stream, ss.want);
     if (rc) return rc;
-    return sync_finish(h, ss, r.topn, out.idx, out.score, out.count);
+    rc = sync_finish(h, ss, r.topn, out.idx, out.score, out.count);
+    if (rc == MI355REC_OK && r.report_distance) mi355playlist::scores_to_distances(out, r.topn);   // "DISTANCE REQUESTS": -m to sqrtf(m)
+    return rc;
 }
 
 }  // namespace
@@ -284,8 +314,32 @@ int mi355rec_query_playlist_request(mi355rec_t* h, const mi355rec_playlist_query
     return sync_playlist_query(h, r, out);
 }
 
+// "DISTANCE REQUESTS": the same Request with metric = kDistance through the same path.
+int mi355rec_query_distance_request(mi355rec_t* h, const mi355rec_distance_query_t* query, const mi355rec_distance_result_t* result) {
+    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    mi355rec_distance_query_t full;
+    Request r;
+    Outputs out;
+    char why[160];
+    if (mi355playlist::from_distance_query(query, result, &full, &r, &out, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    return sync_playlist_query(h, r, out);
+}
+
 // "ROW PRIORS"
 int mi355rec_set_priors(mi355rec_t* h, const float* priors_host, int64_t n) { return set_priors_common(h, priors_host, n, false); }
+
+}  // extern "C"
+
+// mi355rec_rebuild_replica (mi355rec.hip): the norms are a snapshot of the rows too; the next distance request builds them again.
+// (The caller has drained the handle's stream.)
+static void drop_distance_norms(mi355rec* h) {
+    if (!h->playlist || !h->playlist->d_norms) return;
+    (void)hipFree(h->playlist->d_norms);
+    h->playlist->d_norms = nullptr;
+    h->playlist->norms_built = false;
+}
+
+extern "C" {
 
 int mi355rec_playlist_counters(const mi355rec_t* h, int64_t* queries, int64_t* rows_exact) {
     if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");

@@ -559,7 +559,7 @@ int build_replica_inner(mi355rec* h) {
                        h->d_feats, h->n, n_padded, reinterpret_cast<uint2*>(h->d_half));
     const int64_t n_quads4 = (h->n + 3) / 4 * 4;
     hipLaunchKernelGGL(q8_build_kernel, dim3(static_cast<unsigned>((n_quads4 + 255) / 256)), dim3(256), 0, h->stream,
-                       h->d_feats, h->n, n_quads4, reinterpret_cast<uint32_t*>(h->d_q8));
+                       h->d_feats, h->n, n_quads4, reinterpret_cast<uint32_t*>(h->d_q8), static_cast<float*>(nullptr));
     if (timed) (void)hipEventRecord(b, h->stream);
     const hipError_t e = hipStreamSynchronize(h->stream);
     if (timed && e == hipSuccess) (void)hipEventElapsedTime(&h->replica_build_ms, a, b);

@@ -19,6 +19,8 @@
 //       --where, --dislike, --weights, --diverse and --pool; with --genre in the --playlist mode only)
 //   ... --playlist with --priors FILE --prior-weight BETA: rank by similarity + BETA x prior (extension; FILE holds one float in
 //       [-1, 1] per line, in catalogue order; usable with every other option of the --playlist mode)
+//   ... --song, --id and --playlist with --metric euclidean: the NEAREST songs by Euclidean distance over the 12 features instead
+//       of the most similar by cosine (extension; with --genre and --where; distances are printed)
 //   ... --playlist with --dislike "<track_id>,..." [--dislike-weight W] [--weights "w,w,..."]: weighted playlists (extension):
 //       the disliked songs push results away (weight -W, default 0.5), --weights gives the playlist's songs their own weights
 #include <algorithm>
@@ -63,7 +65,11 @@ static void usage(const char* prog) {
               << "   --playlist <one id> --genre ... for those combinations.\n"
               << "Row priors (extension): " << prog << " --playlist \"id,id,...\" --priors FILE --prior-weight BETA, with any other\n"
               << "   --playlist option: ranks by similarity + BETA x prior (BETA in [-4, 4]; negative demotes).  FILE holds one number in\n"
-              << "   [-1, 1] per line, one line per song in the order of songs_data.bin (a popularity column scaled to [0, 1], say).\n" << std::endl;
+              << "   [-1, 1] per line, one line per song in the order of songs_data.bin (a popularity column scaled to [0, 1], say).\n"
+              << "Euclidean metric (extension): --metric euclidean, with --song, --id or --playlist (and --genre, --where): the nearest\n"
+              << "   songs by distance over the 12 normalised features (for a playlist: the root-mean-square distance to its songs).\n"
+              << "   Cosine ignores how large the features are; the distance does not.  Not with --diverse, --weights, --dislike,\n"
+              << "   --priors or --max-per-artist.  --metric cosine is the default.\n" << std::endl;
 }
 
 // --where NAME=LO:HI, any number of times from argv[first]: the ranges (feature indices in Song.h order).  false, with a
@@ -573,6 +579,103 @@ static bool playlistMode(const std::string& list, int topN, const std::vector<Re
     return true;
 }
 
+// --metric NAME from argv[first]: euclidean = true for "euclidean", false for "cosine" or no option.  false (the return
+// value), with a message, for another name, or for euclidean beside an option it is not served with.
+static bool parseMetric(int argc, char* argv[], int first, bool& euclidean) {
+    euclidean = false;
+    for (int i = first; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--metric") != 0) continue;
+        if (i + 1 >= argc) {
+            std::cerr << "Error: --metric needs a name (cosine or euclidean)" << std::endl;
+            return false;
+        }
+        const std::string name = argv[++i];
+        if (name != "cosine" && name != "euclidean") {
+            std::cerr << "Error: --metric '" << name << "': cosine or euclidean" << std::endl;
+            return false;
+        }
+        euclidean = name == "euclidean";
+    }
+    if (!euclidean) return true;
+    for (int i = first; i < argc; ++i)
+        for (const char* no : {"--diverse", "--pool", "--weights", "--dislike", "--dislike-weight", "--priors", "--prior-weight", "--max-per-artist"})
+            if (std::strcmp(argv[i], no) == 0) {
+                std::cerr << "Error: --metric euclidean cannot be combined with " << no
+                          << " (distance requests take --genre and --where only)" << std::endl;
+                return false;
+            }
+    return true;
+}
+
+// --metric euclidean: the songs nearest to one song (--song / --id) or to a playlist's songs, with their distances.
+static bool nearestMode(const std::string& query, bool isPlaylist, bool isTrackId, int topN,
+                        const std::vector<Recommender::FeatureRange>& ranges, const std::vector<std::string>& genres) {
+    std::cout << "=== NEAREST MODE (Euclidean distance) ===" << std::endl;
+    DataManager::Catalogue catalogue;
+    if (!DataManager::loadCatalogue(kBinaryDataFile, catalogue)) {
+        std::cerr << "Failed to load data. Have you run preprocessing?" << std::endl;
+        return false;
+    }
+    std::vector<int> genreIds;
+    if (!genreIdsOf(catalogue, genres, genreIds)) return false;
+    std::vector<int> members;
+    const std::vector<std::string> names = isPlaylist ? splitList(query) : std::vector<std::string>{query};
+    if (names.empty()) {
+        std::cerr << "Error: the playlist names no track" << std::endl;
+        return false;
+    }
+    for (const std::string& name : names) {
+        const int index = findQuery(catalogue, name, isPlaylist || isTrackId);
+        if (index < 0) {
+            std::cerr << "Error: Song with " << (isPlaylist || isTrackId ? "track_id" : "name") << " '" << name << "' not found" << std::endl;
+            return false;
+        }
+        members.push_back(index);
+    }
+    Recommender recommender;
+    if (!recommender.initialize(catalogue.features, catalogue.trackIds, catalogue.trackNames)) {
+        std::cerr << "Failed to initialize recommender" << std::endl;
+        return false;
+    }
+    if (!genreIds.empty()) {
+        std::cout << "Restricted to genres:";
+        for (const std::string& name : genres) std::cout << " " << name;
+        std::cout << std::endl;
+        if (!recommender.setGenreIds(catalogue.genreIds)) return false;
+    }
+    const std::vector<int> recs = recommender.recommendNearest(members, topN, ranges, genreIds);
+    if (recs.empty()) {
+        std::cerr << "No recommendations found. Please check the query." << std::endl;
+        return false;
+    }
+    const std::vector<float> distances = recommender.lastScores();
+    std::map<int, std::string>& genreMap = catalogue.genreMap;
+    Song song;
+    std::cout << "\n----------------------------------------------\n" << (isPlaylist ? "Playlist" : "Query") << " (" << members.size()
+              << (members.size() == 1 ? " song):" : " songs):") << std::endl;
+    for (size_t i = 0; i < members.size(); ++i) {
+        if (!DataManager::readSong(catalogue, static_cast<size_t>(members[i]), song)) {
+            std::cerr << "Error: could not read song " << members[i] << " from " << catalogue.path << std::endl;
+            return false;
+        }
+        std::cout << "  " << (i + 1) << ". \"" << song.track_name << "\"" << std::endl;
+        printSong(song, genreMap, "     ");
+    }
+    std::cout << "----------------------------------------------" << std::endl;
+    std::cout << "\nTop " << recs.size() << " Recommendations:\n" << std::endl;
+    for (size_t i = 0; i < recs.size(); ++i) {
+        if (!DataManager::readSong(catalogue, static_cast<size_t>(recs[i]), song)) {
+            std::cerr << "Error: could not read song " << recs[i] << " from " << catalogue.path << std::endl;
+            return false;
+        }
+        std::cout << (i + 1) << ". \"" << song.track_name << "\"  (distance " << distances[i] << ")" << std::endl;
+        printSong(song, genreMap, "   ");
+        if (i + 1 < recs.size()) std::cout << std::endl;
+    }
+    std::cout << "\nRecommendation complete!" << std::endl;
+    return true;
+}
+
 int main(int argc, char* argv[]) {
     std::cout << "== High-Performance Music Recommendation Engine ==\n"
               << "==   MI355X-native (HIP / gfx950) cosine top-N  ==\n" << std::endl;
@@ -617,6 +720,9 @@ int main(int argc, char* argv[]) {
         }
         std::vector<Recommender::FeatureRange> ranges;
         if (!parseWhere(argc, argv, 3, ranges)) return 1;
+        bool euclidean = false;
+        if (!parseMetric(argc, argv, 3, euclidean)) return 1;
+        if (euclidean) return nearestMode(argv[2], false, mode == "--id", topN, ranges, genres) ? 0 : 1;
         if (!ranges.empty() && !genres.empty()) {
             std::cerr << "Error: --where cannot be combined with --genre" << std::endl;
             return 1;
@@ -647,6 +753,20 @@ int main(int argc, char* argv[]) {
         }
         std::vector<Recommender::FeatureRange> ranges;
         if (!parseWhere(argc, argv, 3, ranges)) return 1;
+        bool euclidean = false;
+        if (!parseMetric(argc, argv, 3, euclidean)) return 1;
+        if (euclidean) {
+            std::vector<std::string> in_genres;
+            for (int i = 3; i < argc; ++i) {
+                if (std::strcmp(argv[i], "--genre") != 0) continue;
+                if (i + 1 >= argc) {
+                    std::cerr << "Error: --genre needs a genre name" << std::endl;
+                    return 1;
+                }
+                in_genres.push_back(argv[++i]);
+            }
+            return nearestMode(argv[2], true, true, topN, ranges, in_genres) ? 0 : 1;
+        }
         Taste taste;
         if (!parseTaste(argc, argv, 3, taste)) return 1;
         DiverseOpt dv;

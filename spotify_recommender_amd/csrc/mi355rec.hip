@@ -756,7 +756,8 @@ int mi355rec_rebuild_replica(mi355rec_t* h) {
     if (rc) return rc;
     rc = build_anchors(h);   // (the other snapshot of the rows)
     if (rc) return rc;
-    rc = build_replica(h);
+    rc = build_replica(h);   // (synchronises the handle's stream)
+    drop_distance_norms(h);   // "DISTANCE REQUESTS": the third snapshot of the rows; the next such request takes it again
     if (rc == MI355REC_OK && h->shared) {   // published to the group
         h->shared->d_half = h->d_half;
         h->shared->d_q8 = h->d_q8;

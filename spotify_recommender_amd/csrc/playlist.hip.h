@@ -126,6 +126,68 @@
 //     vacuous (at most 5 % of 65 537 rows survive at the true threshold; the real-number model gives 1.21 %).
 // prior == 0 takes none of these branches (uniform tests) and never reads `priors`.
 //
+// DISTANCE (include/mi355rec_diag.h, "DISTANCE REQUESTS").  PlaylistArg::metric == kPlDistance (uniform): the ranking value of
+// a row is the MEAN SQUARED EUCLIDEAN DISTANCE to the members, smaller is better:
+//     d2_k(x) = acc after j = 0..11 of:  t = fl(q_kj - x_j);  acc = fl(acc + fl(t * t))        (acc starts at 0.0f)
+//     m(x)    = fl( fl(...fl(d2_0 + d2_1) + ... + d2_{K-1}) / (float)K )                       (member order; K = 1: m = d2_0)
+// fp32, subtract, multiply THEN add (fp contract is off), one IEEE divide (by 1.0f for K = 1: exact).  Every key, every
+// workgroup threshold and shared_thr is a key of -m: pack_key orders by score descending, so the best keys are the nearest
+// rows, ties break by global row ascending as everywhere, and m = +0.0 packs as a score of +0.0 (score_to_ordered maps -0.0
+// there).  The rule above (the k-th best key among ANY k admissible rows bounds the answer) does not care what the ranking
+// value is, so selection, compaction, the per-workgroup lists, the shared atomicMax and the merge are unchanged.  The host
+// reports sqrtf(m) (engine_playlist.hip.h); the weights, W and the priors are never read.
+//   * a row whose m is not finite (NaN or inf: hostile features or members, an overflowing sum) forms NO key: it is not
+//     admissible, like a row the filter rejects;
+//   * the K chains (playlist_sqdist) replace playlist_mean where a key is formed; exclusion lookup, filter and the label
+//     test first are as above;
+//   * PRE-FILTER.  Let c = (1/K) sum_k q_k be the centroid and Q2 = (1/K) sum_k |q_k|^2.  In real numbers
+//         m(x) = |x|^2 - 2 x . c + Q2 = |x|^2 - 2 |x| |c| (x^ . c^) + Q2.
+//     The replica is queried with v = c / |c| (q8_query on c: approx = D / (127 S), |approx - x^ . v| <= M), so
+//         L(x) = |x|^2 - 2 |x| |c| (approx + M) + Q2 <= m(x),
+//     and a row is ruled out iff L(x) - slack > T, T the threshold's m (T = -score of the threshold key, exact), with
+//     slack = eps G(x), G(x) = |x|^2 + Q2 + 2 |x| |c| (an upper bound of m: features may be far from [0, 1], so the slack
+//     is RELATIVE) and eps = (4K + 128) 2^-24.  Solved for D, with s = |x| as stored (below) and S2c = 127 S / (2 |c|):
+//         q2e  = fl(Q2 (1 - eps)),  a1 = fl(S2c (1 - eps)),  c0 = fl(127 S (M + eps))        (once per launch)
+//         b(T) = fl( fl(q2e - T) S2c )                                (refreshed whenever the threshold moves; -inf: none yet)
+//         cut(x) = int( clamp( fl( fl( fl(a1 s) + fl(b rcp(s)) ) - c0 ), -2^30, 2^30 ) ) - 1
+//     and the test is the integer compare D < cut(x): a reciprocal (v_rcp_f32, one ulp), two multiplies, an add, a subtract,
+//     the clamp and the convert per row.  The clamp comes after the arithmetic, on the float, as for the priors; a product
+//     that overflows saturates with the right sign (b -> -inf for a huge T: no row is ruled out; b r -> +inf only where
+//     Q2 / (|x| |c|) is beyond 1e30 while T is not: such a row is 1e15 thresholds away); a NaN (only from rows that are not
+//     claimed, below) is dropped by fmaxf and leaves -2^30.  The launch refuses the pre-filter where q2e S2c is not finite.
+//     Why eps suffices, with u = 2^-24 relative, P = s^2 + Q2, Z = 2 s |c|, for a row the bound is claimed for:
+//       - the chain: every term of m is non-negative, so the fp32 value is within (15 + K) u of m itself (subtract 1,
+//         square 3, twelve adds 11 more; K - 1 adds and a divide), and m <= G;
+//       - c in fp32: K - 1 adds and a divide per component, |(c~ - c) . x| <= K u |x| sqrt(Q2) <= K u P / 2, twice in m: K u P;
+//       - Q2 in fp32: 13 u per |q_k|^2, K - 1 adds, a divide, the product with (1 - eps): (K + 15) u Q2;
+//       - s against |x| (q8_build_kernel: the sequential sum, 13 u, halved by sqrtf, and its rounding): 7.5 u, so s^2 is
+//         15 u of |x|^2, and s |c| (|c| = query_norm(c): 7.5 u more) is 16 u of Z, times |approx + M| <= 1.03: 17 u Z;
+//       - the cut's own arithmetic (S2c 3, a1 2, c0 3, the difference q2e - T and its product 2, rcp 2, two products 2, the
+//         add and the subtract 2: kappa = 16 roundings, each relative to one of s/(2|c|), (Q2 + T)/(2 s |c|), M + eps), in
+//         units of m: kappa u (P + T + Z).  T <= 2 (P + Z) wherever a row can be ruled out at all (the cut is below
+//         -(1 + M) 127 S <= D beyond that), so this is at most 3 kappa u (P + Z);
+//       - the conversion truncates towards zero and the - 1 puts the cut at or below the float.
+//     (15 + K) + K + (K + 15) + 17 + 3 kappa = 3K + 95 <= 4K + 128.  So D < cut(x) implies m~(x) > T: the row's key lies below
+//     the threshold whatever its row id.  eps is 1.5e-5 at most; M is 1e-2.  tests/test_distance_margin.py checks this with a
+//     numpy model of exactly this arithmetic (and the reciprocal one ulp off either way) against tests/distance_oracle.py:
+//     uniform, tied, duplicated, signed wide, one dominant feature, norms at the edges of the valid range; K = 1, 3, 32; tiny
+//     centroids; T at the true threshold, 0 and far above — and that the bound is not vacuous (at the true top-10 threshold of
+//     65 537 uniform rows at most 1 % survive; 0.04 - 0.15 % measured on the model).
+//     On a catalogue whose rows all lie within M |x| |c| of each other (one tight cluster) or with one dominant unnormalised
+//     feature the bound rules little out and the call runs at the exact path's speed: it stays correct.
+//   * PER-ROW NORMS.  `norms`: s(x) = sqrtf of the sequential fp32 sum of squares, one fp32 per row in local row order, padded
+//     to whole quads (q8_build_kernel's second output, launched with a null replica pointer by the handle's first distance
+//     request; engine_playlist.hip.h says who owns it).  Per tile a lane loads its quad's four norms as one 16-byte load, with
+//     the next tile's replica load, in the registers the priors' load uses (a distance request has no prior).
+//   * the pre-filter is OFF for the launch (every row takes the chains) when the handle has no 8-bit replica, when a member's
+//     norm or |c| lies outside [kBqMinNorm, kBqMaxNorm] or is not finite, when q8_query says not ok, or when q2e S2c
+//     overflows.  Rows whose first byte is 0x80 always take the chains, and so do rows whose stored norm is zero or outside
+//     [kBqMinNorm, kBqMaxNorm] (the replica's own validity test uses a fused sum: the two may disagree at the edge).
+//   * STARTING THRESHOLD.  The rule above holds for any ranking value: the anchor table's copy is ranked by the chain's d2
+//     against c (anchors whose d2 is not finite are not chosen), the best kPlBoundRows are read from the matrix and scored
+//     with the K chains, and the topk-th best admissible one starts the threshold.
+// metric == kPlCosine takes none of these branches (uniform tests).
+//
 // EXCLUSION.  The excluded global ids (members and the caller's list, sorted and deduplicated on the host, at most
 // kPlExcludeCap) sit in LDS as uint32; only a key that already beats the workgroup's threshold is looked up (binary
 // search), so the hot loop does not change.
@@ -151,6 +213,7 @@ constexpr float kPlChainErr = 4e-6f;                        // |c_k - u^_k . x^|
 constexpr float kPlUlp = 5.9604645e-8f;                     // 2^-24
 constexpr float kPlMinMeanNorm = 1e-3f;                     // |u| below this: the pre-filter is off
 constexpr float kPlPriorUlps = 96.0f;                       // margin_prior - margin_mean, in kPlUlp (see ROW PRIORS above)
+constexpr int kPlCosine = 0, kPlDistance = 1;               // PlaylistArg::metric (mi355playlist::Metric)
 constexpr float kPlCutClamp = 1073741824.0f;                // 2^30: a per-row cut beyond it decides as the clamped one (|D| < 4.2e6)
 using PlaylistCfg = Q8Cfg<512, 4, 1>;                       // kBlock, kMinWaves (two workgroups per CU); tiles of 2048 rows
 
@@ -175,6 +238,7 @@ struct PlaylistArg {
     int labelled;     // 1: only rows whose label is in PlaylistBuf::label_mask are admissible; 0: no label set
     float prior_weight;   // beta (read only where `prior`): v = fl(score + fl(beta p(x)))
     int prior;        // 1: rank by v, p from the kernel's `priors`; 0: rank by the score alone (`priors` is never read)
+    int metric;       // kPlCosine, or kPlDistance: rank by -m(x), the mean squared distance to the members (DISTANCE above)
 };
 
 // Is label l (int16 of the row-order array: -1 = unlabelled or padding) in the set?
@@ -223,6 +287,42 @@ __device__ __forceinline__ float playlist_mean(const float (*__restrict__ mem)[k
     return sum / wsum;
 }
 
+// DISTANCE: sum_j q_j^2, sequential fp32 (what query_norm takes the root of).
+__device__ __forceinline__ float playlist_sqnorm(const float (&q)[kDim]) {
+    float s = 0.0f;
+#pragma unroll
+    for (int j = 0; j < kDim; ++j) s = s + q[j] * q[j];
+    return s;
+}
+
+// DISTANCE: the contract's chain d2 of one row against one vector in registers (the anchors against the centroid).
+__device__ __forceinline__ float row_sqdist(const float (&q)[kDim], const Row& r) {
+    const float f[kDim] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.c.x, r.c.y, r.c.z, r.c.w};
+    float acc = 0.0f;
+#pragma unroll
+    for (int j = 0; j < kDim; ++j) {
+        const float t = q[j] - f[j];
+        acc = acc + t * t;
+    }
+    return acc;
+}
+
+// DISTANCE: m(x), the contract's mean squared distance of one row to the members (LDS) in order.
+__device__ __forceinline__ float playlist_sqdist(const float (*__restrict__ mem)[kDim], int k, const Row& r) {
+    const float f[kDim] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.c.x, r.c.y, r.c.z, r.c.w};
+    float sum = 0.0f;
+    for (int m = 0; m < k; ++m) {
+        float acc = 0.0f;
+#pragma unroll
+        for (int j = 0; j < kDim; ++j) {
+            const float t = mem[m][j] - f[j];
+            acc = acc + t * t;
+        }
+        sum = m == 0 ? acc : sum + acc;
+    }
+    return sum / static_cast<float>(k);
+}
+
 __device__ __forceinline__ bool playlist_excluded(const uint32_t* s_excl, int n_excl, uint32_t g) {
     int lo = 0, hi = n_excl;
     while (lo < hi) {
@@ -237,11 +337,12 @@ __device__ __forceinline__ bool playlist_excluded(const uint32_t* s_excl, int n_
 // rows_exact: += the rows whose K chains this launch computed; with a filter, every fp32 row read (rejected ones included).
 // labels: the shard's labels in row order, four int16 to a quad (read only where arg.labelled).
 // priors: the shard's priors in row order, four fp32 to a quad (read only where arg.prior).
+// norms: DISTANCE: the rows' norms in row order, four fp32 to a quad, or null (no pre-filter for this metric then).
 __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void playlist_scan_kernel(
     const float* __restrict__ feats, const uint4* __restrict__ q8, int64_t n, int64_t row_base, const PlaylistBuf* __restrict__ buf,
     PlaylistArg arg, const float* __restrict__ anchors, int topk, uint64_t* __restrict__ block_lists,
     unsigned long long* __restrict__ rows_exact, unsigned long long* __restrict__ shared_thr /* &buf->shared_thr */,
-    const uint2* __restrict__ labels, const float4* __restrict__ priors) {
+    const uint2* __restrict__ labels, const float4* __restrict__ priors, const float4* __restrict__ norms) {
     constexpr int kBlock = PlaylistCfg::kBlock;
     static_assert(PlaylistCfg::kCandCap >= kAnchorRows / 2 && PlaylistCfg::kCandCap * 2 >= kPlBoundRows, "LDS reuse below");
     __shared__ uint64_t s_cand[PlaylistCfg::kCandCap];
@@ -268,6 +369,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     const bool prior = arg.prior != 0;
     const float beta = arg.prior_weight;
     const float* const row_prior = reinterpret_cast<const float*>(priors);
+    const bool dist = arg.metric == kPlDistance;
     const float* const f_lo = buf->lo;
     const float* const f_hi = buf->hi;
 
@@ -288,14 +390,20 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
         for (int j = 0; j < kDim; ++j) q[j] = s_mem[tid][j];
         const float qn = query_norm(q);
         s_qn[tid] = qn;
-        s_w[tid] = buf->weights[tid];
+        s_w[tid] = dist ? playlist_sqnorm(q) : buf->weights[tid];   // (DISTANCE: |q_k|^2 for Q2; the weights are never read)
         if (!(qn >= kBqMinNorm && qn <= kBqMaxNorm)) s_ok = 0;   // (false for NaN too; every writer writes 0)
     }
     __syncthreads();
     if (tid < kDim) {   // u: the weighted mean of the members' unit vectors (only used where every |q_k| is in range)
-        float sum = s_w[0] * (s_mem[0][tid] / s_qn[0]);
-        for (int m = 1; m < k; ++m) sum = sum + s_w[m] * (s_mem[m][tid] / s_qn[m]);
-        s_u[tid] = sum / wsum;
+        if (dist) {   // (uniform) DISTANCE: u is the centroid c = fl(fl(q_0j + ... + q_{K-1}j) / K)
+            float sum = s_mem[0][tid];
+            for (int m = 1; m < k; ++m) sum = sum + s_mem[m][tid];
+            s_u[tid] = sum / static_cast<float>(k);
+        } else {
+            float sum = s_w[0] * (s_mem[0][tid] / s_qn[0]);
+            for (int m = 1; m < k; ++m) sum = sum + s_w[m] * (s_mem[m][tid] / s_qn[m]);
+            s_u[tid] = sum / wsum;
+        }
     }
     __syncthreads();
     float u[kDim];
@@ -303,10 +411,24 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     for (int j = 0; j < kDim; ++j) u[j] = s_u[j];
     const float un = query_norm(u);
     const Q8Query hq = q8_query(u, un);
-    const bool prefilter = q8 != nullptr && s_ok != 0 && hq.ok && un >= kPlMinMeanNorm;   // uniform (false for a NaN |u|)
+    // DISTANCE: the launch's constants of the per-row cut (see above); q2e * s2c must be finite or the cut could overflow upwards
+    float dist_q2e = 0.0f, dist_s2c = 0.0f, dist_c0 = 0.0f;
+    if (dist) {   // uniform
+        float q2 = s_w[0];
+        for (int m = 1; m < k; ++m) q2 = q2 + s_w[m];
+        const float eps = static_cast<float>(4 * k + 128) * kPlUlp;
+        dist_q2e = (q2 / static_cast<float>(k)) * (1.0f - eps);
+        dist_s2c = kQ8DotScale / (2.0f * un);
+        dist_c0 = kQ8DotScale * (hq.margin + eps);
+    }
+    const float dist_a1 = dist_s2c * (1.0f - static_cast<float>(4 * k + 128) * kPlUlp);
+    const bool prefilter = q8 != nullptr && s_ok != 0 && hq.ok &&
+                           (dist ? norms != nullptr && dist_q2e * dist_s2c < __builtin_inff() : un >= kPlMinMeanNorm);   // uniform (false for NaN)
     const float margin_mean = un * hq.margin + kPlChainErr + static_cast<float>(3 * k + 32) * kPlUlp;
     const float margin_prior = margin_mean + kPlPriorUlps * kPlUlp;
     const float prior_scale = (beta * kQ8DotScale) / un;   // bs (only used where prior && prefilter: |u| >= kPlMinMeanNorm then)
+    const bool side = (prior || dist) && prefilter;          // a 4 B/row side array streams with the replica: the priors, or the norms
+    const float4* const side4 = dist ? norms : priors;
     int n_exact = 0;   // rows whose K chains this thread computed
     uint64_t thr = 0;
 
@@ -319,12 +441,17 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
         for (int r = 0; r < kPer; ++r) {
             const int i = r * kBlock + tid;
             const Row a = load_row(anchors, static_cast<int64_t>(i));
-            mine[r] = i < n_anchor ? pack_key(cosine_score(u, un, a), static_cast<uint32_t>(i)) : 0ull;
+            if (dist) {   // (uniform) DISTANCE: the anchors nearest to the centroid; a distance that is not finite is no candidate
+                const float d = row_sqdist(u, a);
+                mine[r] = i < n_anchor && d < __builtin_inff() ? pack_key(-d, static_cast<uint32_t>(i)) : 0ull;
+            } else {
+                mine[r] = i < n_anchor ? pack_key(cosine_score(u, un, a), static_cast<uint32_t>(i)) : 0ull;
+            }
             if (active && !filter_pass(a, active, f_lo, f_hi)) mine[r] = 0ull;   // (only chooses: re-checked on the matrix's row)
             if (labelled && i < n_anchor && !label_selected(s_lmask, row_label[anchor_row(n, i)])) mine[r] = 0ull;
         }
         int n_cand = kPlBoundRows;   // anchors left to choose from: all of them without a filter
-        if (active || labelled) {   // uniform
+        if (active || labelled || dist) {   // uniform
 #pragma unroll
             for (int r = 0; r < kPer; ++r) {
                 const uint64_t have = __ballot(mine[r] != 0ull);
@@ -354,11 +481,19 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
         if (tid < picked) {
             const int64_t row = anchor_row(n, s_pick[tid]);
             const Row x = load_row(feats, row);   // from the matrix
-            float m = playlist_mean(s_mem, s_qn, s_w, wsum, k, x);
+            float m;
+            bool finite = true;
+            if (dist) {   // uniform
+                const float d = playlist_sqdist(s_mem, k, x);
+                finite = d < __builtin_inff();
+                m = -d;
+            } else {
+                m = playlist_mean(s_mem, s_qn, s_w, wsum, k, x);
+            }
             if (prior) m = m + beta * row_prior[row];   // (uniform) v: multiply, round, add, round
             ++n_exact;
             const uint32_t g = static_cast<uint32_t>(row_base + row);
-            key = playlist_excluded(s_excl, n_excl, g) || (active && !filter_pass(x, active, f_lo, f_hi)) ||
+            key = !finite || playlist_excluded(s_excl, n_excl, g) || (active && !filter_pass(x, active, f_lo, f_hi)) ||
                           (labelled && !label_selected(s_lmask, row_label[row]))
                       ? 0ull
                       : pack_key(m, g);
@@ -394,10 +529,11 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     auto refresh_prior_cut = [&]() {
         if (thr != 0ull) {   // uniform
             const float t = ordered_to_score(static_cast<uint32_t>(thr >> 32));
-            cut_base = ((t - margin_prior) / un) * kQ8DotScale;
+            if (dist) cut_base = (dist_q2e - (0.0f - t)) * dist_s2c;   // (uniform) DISTANCE: b(T), T = -t the threshold's m
+            else cut_base = ((t - margin_prior) / un) * kQ8DotScale;
         }
     };
-    if (prior && prefilter) refresh_prior_cut();   // uniform
+    if (side) refresh_prior_cut();   // uniform
     else refresh_cut();
     int compact_at = 2 * topk > 256 ? 2 * topk : 256;
     if (compact_at > kCandLimit) compact_at = kCandLimit;
@@ -415,10 +551,10 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
         quad = quad < n_quads ? quad : n_quads - 1;
         return labels[quad];
     };
-    auto load_priors = [&](int64_t t) {   // the quad's four priors, 16 bytes (the quad clamped as in load_q8)
+    auto load_priors = [&](int64_t t) {   // the quad's four priors (DISTANCE: norms), 16 bytes (the quad clamped as in load_q8)
         int64_t quad = t * kBlock + tid;
         quad = quad < n_quads ? quad : n_quads - 1;
-        return priors[quad];
+        return side4[quad];
     };
     HalfTile cur;
     cur.t0 = cur.t1 = cur.t2 = make_uint4(0u, 0u, 0u, 0u);
@@ -426,7 +562,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     uint2 lab_cur = make_uint2(0u, 0u);
     if (labelled) lab_cur = load_labels(blockIdx.x);
     float4 pri_cur = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (prior && prefilter) pri_cur = load_priors(blockIdx.x);   // (the exact path reloads a row's prior in the chain loop)
+    if (side) pri_cur = load_priors(blockIdx.x);   // (the exact path reloads a row's prior in the chain loop)
 
     for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {   // uniform
         HalfTile nxt = cur;
@@ -434,7 +570,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
         uint2 lab_nxt = lab_cur;
         if (labelled) lab_nxt = load_labels(t + gridDim.x);   // (uniform) ... and so are its labels
         float4 pri_nxt = pri_cur;
-        if (prior && prefilter) pri_nxt = load_priors(t + gridDim.x);   // (uniform) ... and its priors
+        if (side) pri_nxt = load_priors(t + gridDim.x);   // (uniform) ... and its priors (DISTANCE: norms)
         const int64_t quad = t * kBlock + tid;
         const int64_t r0 = quad * 4;
         uint32_t mask = 0u;
@@ -453,7 +589,17 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
             int a[4];
             bool special[4];
             q8_dot4(hq, cur, a, special);
-            if (!prior) {   // uniform
+            if (dist) {   // (uniform) DISTANCE: the per-row cut a1 s + b(T) / s - c0: reciprocal, two multiplies, add, subtract, clamp, convert
+                const float s4[4] = {pri_cur.x, pri_cur.y, pri_cur.z, pri_cur.w};
+#pragma unroll
+                for (int u4 = 0; u4 < 4; ++u4) {
+                    const float sn = s4[u4];
+                    const float c = (dist_a1 * sn + cut_base * __builtin_amdgcn_rcpf(sn)) - dist_c0;
+                    const int cut = static_cast<int>(__builtin_fminf(__builtin_fmaxf(c, -kPlCutClamp), kPlCutClamp)) - 1;
+                    const bool claimed = sn >= kBqMinNorm && sn <= kBqMaxNorm;   // (false for a zero, tiny, huge or NaN norm: always exact)
+                    if (!(special[u4] || !claimed || a[u4] >= cut)) mask &= ~(1u << u4);
+                }
+            } else if (!prior) {   // uniform
 #pragma unroll
                 for (int u4 = 0; u4 < 4; ++u4)
                     if (!(special[u4] || a[u4] >= cut_d)) mask &= ~(1u << u4);
@@ -483,11 +629,19 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
             const bool have = mask != 0u;
             const int64_t r = have ? r0 + __builtin_ctz(mask) : 0;
             const Row x = load_row(feats, r);
-            float m = playlist_mean(s_mem, s_qn, s_w, wsum, k, x);
+            float m;
+            bool finite = true;
+            if (dist) {   // (uniform) DISTANCE: the key carries -m; a row whose m is not finite forms no key
+                const float d = playlist_sqdist(s_mem, k, x);
+                finite = d < __builtin_inff();   // (false for NaN)
+                m = -d;
+            } else {
+                m = playlist_mean(s_mem, s_qn, s_w, wsum, k, x);
+            }
             if (prior) m = m + beta * row_prior[r];   // (uniform) v; the prior reloaded: an L2 hit (the tile's load brought its line)
             n_exact += (have && !active) ? 1 : 0;   // (with a filter every row read was counted above)
             const uint32_t g = static_cast<uint32_t>(row_base + r);
-            const uint64_t key = have ? pack_key(m, g) : 0ull;
+            const uint64_t key = have && finite ? pack_key(m, g) : 0ull;
             bool pass = key > thr;
             if (pass && n_excl > 0) pass = !playlist_excluded(s_excl, n_excl, g);
             const uint64_t ballot = __ballot(pass);
@@ -511,7 +665,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
             if (local_thr > thr) thr = local_thr;
         }
         if (published > thr) thr = published;
-        if (prior && prefilter) refresh_prior_cut();   // uniform
+        if (side) refresh_prior_cut();   // uniform
         else refresh_cut();
         cur = nxt;
         lab_cur = lab_nxt;

@@ -3,7 +3,8 @@
 // handle (engine_playlist.hip.h), the node handle (sharded.hip) and the CPU backend.  Every exported entry point of the
 // family fills a Request and an Outputs and takes the one path of its handle type.  Neither struct is part of the C-ABI; the
 // C-ABI's own request ("PLAYLIST REQUESTS": mi355rec_playlist_query_t, the only call that takes a label set) is converted
-// to them by from_query below.
+// to them by from_query below, and the distance request ("DISTANCE REQUESTS": mi355rec_distance_query_t, the same Request with
+// metric = kDistance) by from_distance_query.
 #pragma once
 
 #include <cmath>
@@ -17,6 +18,8 @@
 #include "weights_check.h"
 
 namespace mi355playlist {
+
+enum Metric { kCosine = 0, kDistance = 1 };
 
 struct Request {
     const float* members = nullptr;             // k x 12 floats by value, or null with ...
@@ -36,6 +39,10 @@ struct Request {
     int max_per_group = 0;                      // ... >= 1 then; 0 in every call that is not capped
     bool prior = false;                         // rank by v = fl(score + fl(prior_weight p(x))), p the handle's priors ("ROW PRIORS")
     float prior_weight = 0.0f;                  // ... beta, finite, |beta| <= MI355REC_MAX_PRIOR_WEIGHT; 0.0f is the call without a prior
+    int metric = kCosine;                       // kDistance ("DISTANCE REQUESTS"): rank by m(x), the mean squared distance to the
+                                                // ... members, ascending; keys and scores carry -m
+    bool report_distance = false;               // (kDistance) the score output holds sqrtf(m); false: -m itself, what a node
+                                                // ... handle's merge over shards compares
 
     int scan_topn() const { return diverse ? pool : topn; }   // what the scan selects
     // The same call diversified, and (of a diversified one) capped: what the _diverse and _capped entry points add.
@@ -193,6 +200,13 @@ inline void label_bits(const Request& r, uint32_t* mask) {
     for (int i = 0; i < r.n_labels; ++i) mask[r.labels[i] >> 5] |= 1u << (r.labels[i] & 31);
 }
 
+// "DISTANCE REQUESTS": out.score[0..count) holds -m (the key's score, +0.0 for m = 0); the reported distance is sqrtf(m).
+// (0.0f - s, not -s: the distance of m = 0 is +0.0f.)
+inline void scores_to_distances(const Outputs& out, int topn) {
+    if (!out.score) return;
+    for (int i = 0; i < topn && out.idx[i] >= 0; ++i) out.score[i] = std::sqrt(0.0f - out.score[i]);
+}
+
 // The C-ABI's request (include/mi355rec_diag.h, "PLAYLIST REQUESTS") as the Request and Outputs every layer below takes.
 // q->size says how much of the struct the caller knows: a shorter one is read as "later fields zero"; 0, or more than this
 // library knows, is refused.  True when the structs cannot be used; then msg[0..cap) says why.
@@ -249,6 +263,54 @@ inline bool from_query(const mi355rec_playlist_query_t* q, const mi355rec_playli
     if (full->flags & MI355REC_PQ_CAPPED) *r = r->capped_at(full->max_per_group);
     if (full->flags & MI355REC_PQ_PRIOR) *r = r->with_prior(full->prior_weight);
     *out = {res->out_idx, res->out_score, r->diverse ? res->out_mmr : nullptr, res->out_count, res->out_pool_rows};
+    return false;
+}
+
+// The C-ABI's distance request (include/mi355rec_diag.h, "DISTANCE REQUESTS") as the same Request (metric = kDistance) and
+// Outputs: the size rules of from_query, flags must be 0.  True when the structs cannot be used; then msg[0..cap) says why.
+inline bool from_distance_query(const mi355rec_distance_query_t* q, const mi355rec_distance_result_t* res, mi355rec_distance_query_t* full,
+                                Request* r, Outputs* out, char* msg, size_t cap) {
+    if (!q || !res) {
+        std::snprintf(msg, cap, "null argument");
+        return true;
+    }
+    static const size_t ends[] = {offsetof(mi355rec_distance_query_t, flags),          offsetof(mi355rec_distance_query_t, members),
+                                  offsetof(mi355rec_distance_query_t, rows),           offsetof(mi355rec_distance_query_t, exclude_global),
+                                  offsetof(mi355rec_distance_query_t, filter),         offsetof(mi355rec_distance_query_t, labels),
+                                  offsetof(mi355rec_distance_query_t, k),              offsetof(mi355rec_distance_query_t, n_exclude),
+                                  offsetof(mi355rec_distance_query_t, n_labels),       offsetof(mi355rec_distance_query_t, topn),
+                                  sizeof(mi355rec_distance_query_t)};
+    static_assert(sizeof(mi355rec_distance_query_t) == offsetof(mi355rec_distance_query_t, topn) + sizeof(int32_t) &&
+                      sizeof(mi355rec_distance_query_t) == 64,
+                  "no tail padding: the struct ends where its last field ends");
+    bool known = false;
+    for (size_t e : ends) known = known || q->size == e;
+    if (!known) {
+        std::snprintf(msg, cap, "distance query of size %u: not the end of a field of the %u bytes this library reads",
+                      static_cast<unsigned>(q->size), static_cast<unsigned>(sizeof *full));
+        return true;
+    }
+    std::memset(full, 0, sizeof *full);
+    std::memcpy(full, q, q->size);
+    if (full->flags != 0u) {
+        std::snprintf(msg, cap, "flags 0x%x in a distance query: must be 0 (weights, diversified and capped calls and priors are not served)",
+                      static_cast<unsigned>(full->flags));
+        return true;
+    }
+    if (full->members && full->rows) {
+        std::snprintf(msg, cap, "members by value and by row in one distance query");
+        return true;
+    }
+    if (!full->members && !full->rows) {
+        std::snprintf(msg, cap, "a distance query needs members by value or by row");
+        return true;
+    }
+    *r = request(full->members, full->rows, nullptr, full->k, full->exclude_global, full->n_exclude, full->filter, full->topn);
+    r->labels = full->labels;
+    r->n_labels = full->n_labels;
+    r->metric = kDistance;
+    r->report_distance = true;
+    *out = {res->out_idx, res->out_distance, nullptr, res->out_count, nullptr};
     return false;
 }
 

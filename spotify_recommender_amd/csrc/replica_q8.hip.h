@@ -61,14 +61,23 @@ constexpr uint32_t kQ8Special = 0x80u;       // first byte of a row the bound is
 
 // ---- building the replica ---------------------------------------------------------------------------
 // One thread per row; rows [n, n_padded) (n_padded a multiple of 4) are padding and hold the special marker.
+// q8 and norms may each be null (uniform tests): the replica is stored only where q8 is given; where norms is given,
+// norms[row] = sqrtf of the SEQUENTIAL fp32 sum of squares (multiply, round, add, round: what query_norm computes; 0.0f for
+// the padding) — the per-row norms of the distance requests (playlist.hip.h, "DISTANCE"), 4 B per row in local row order.
 __global__ __launch_bounds__(256) void q8_build_kernel(const float* __restrict__ feats, int64_t n, int64_t n_padded,
-                                                       uint32_t* __restrict__ q8) {
+                                                       uint32_t* __restrict__ q8, float* __restrict__ norms) {
     const int64_t row = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (row >= n_padded) return;
     uint32_t d0 = 0x80808080u, d1 = 0x80808080u, d2 = 0x80808080u;   // special
+    float seq = 0.0f;
     if (row < n) {
         const float4* p = reinterpret_cast<const float4*>(feats) + row * 3;
         const float4 a = p[0], b = p[1], c = p[2];
+        if (norms) {   // uniform
+            const float f[kDim] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
+#pragma unroll
+            for (int j = 0; j < kDim; ++j) seq = seq + f[j] * f[j];
+        }
         // the normalisation of the fp16 replica and of the batched passes (replica_build_kernel)
         float tot = a.x * a.x;
         tot = __builtin_fmaf(a.y, a.y, tot);
@@ -95,10 +104,13 @@ __global__ __launch_bounds__(256) void q8_build_kernel(const float* __restrict__
             d2 = q(c.x) | (q(c.y) << 8) | (q(c.z) << 16) | (q(c.w) << 24);
         }
     }
-    uint32_t* dst = q8 + row * 3;
-    dst[0] = d0;
-    dst[1] = d1;
-    dst[2] = d2;
+    if (q8) {   // uniform
+        uint32_t* dst = q8 + row * 3;
+        dst[0] = d0;
+        dst[1] = d1;
+        dst[2] = d2;
+    }
+    if (norms) norms[row] = sqrtf(seq);   // uniform
 }
 
 // ---- the query ------------------------------------------------------------------------------------------

@@ -781,10 +781,15 @@ int sharded_playlist(mi355rec_sharded_t* h, Request r, const Outputs& out) {
     if (r.diverse) return diverse_over_shards(h, r, out);
     const int rc = drain_workers(h);
     if (rc) return rc;
-    // every shard gets the whole exclusion list and matches the ids of its own rows
-    return merge_over_shards(h, r.topn, out, [&](mi355rec_t* e, int64_t* idx, float* sc, int* c) {
+    // every shard gets the whole exclusion list and matches the ids of its own rows ("DISTANCE REQUESTS": the shards answer
+    // with -m, what the merge's keys compare; the distances are taken from the merged list)
+    const bool report_distance = r.report_distance;
+    r.report_distance = false;
+    const int merged = merge_over_shards(h, r.topn, out, [&](mi355rec_t* e, int64_t* idx, float* sc, int* c) {
         return mi355node::query_playlist(e, r, {idx, sc, nullptr, c, nullptr});
     });
+    if (merged == MI355REC_OK && report_distance) mi355playlist::scores_to_distances(out, r.topn);
+    return merged;
 }
 }  // namespace
 
@@ -873,6 +878,18 @@ int mi355rec_sharded_query_playlist_request(mi355rec_sharded_t* h, const mi355re
     Outputs out;
     char why[128];
     if (mi355playlist::from_query(query, result, &full, &r, &out, why, sizeof why)) return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    return sharded_playlist(h, r, out);
+}
+
+// DISTANCE REQUESTS (include/mi355rec_diag.h): the same Request with metric = kDistance through sharded_playlist.
+int mi355rec_sharded_query_distance_request(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
+                                            const mi355rec_distance_result_t* result) {
+    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    mi355rec_distance_query_t full;
+    Request r;
+    Outputs out;
+    char why[160];
+    if (mi355playlist::from_distance_query(query, result, &full, &r, &out, why, sizeof why)) return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
     return sharded_playlist(h, r, out);
 }
 

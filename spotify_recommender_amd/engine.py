@@ -168,6 +168,35 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
     return out
 
 
+def _distance_request(lib, prefix: str, h, check, members, topn: int, exclude=None, where=None, labels=None):
+    """One DISTANCE REQUEST (`prefix`query_distance_request): the `topn` rows nearest to the members by Euclidean distance.
+    `members` is a (k, 12) float32 array (by value) or a 1-D int64 array of rows (never returned).  `exclude`, `where` and
+    `labels` are the playlist request's.  Returns (ids, distances): nearest first, ties by row; for k > 1 a distance is the
+    root-mean-square distance to the members."""
+    flt = make_filter(where) if where is not None else None
+    ex = np.ascontiguousarray(np.asarray([] if exclude is None else list(exclude), dtype=np.int64).reshape(-1))
+    n_out = max(int(topn), 1)
+    idx = np.empty(n_out, dtype=np.int64)
+    dist = np.empty(n_out, dtype=np.float32)
+    count = ctypes.c_int(0)
+
+    def ptr(a):
+        return a.ctypes.data_as(ctypes.c_void_p)
+
+    q = capi.DistanceQuery()
+    q.size = ctypes.sizeof(capi.DistanceQuery)
+    q.members, q.rows = (None, ptr(members)) if members.dtype == np.int64 else (ptr(members), None)
+    q.exclude_global, q.n_exclude = (ptr(ex) if ex.size else None), int(ex.size)
+    q.filter = ctypes.pointer(flt) if flt is not None else None
+    if labels is not None:
+        lab = _np_labels(labels)
+        q.labels, q.n_labels = ptr(lab), int(lab.size)   # (an empty set stays a non-NULL pointer: the library refuses it)
+    q.k, q.topn = int(members.shape[0]), int(topn)
+    res = capi.DistanceResult(ptr(idx), ptr(dist), ctypes.pointer(count))
+    check(getattr(lib, f"{prefix}query_distance_request")(h, ctypes.byref(q), ctypes.byref(res)))
+    return idx[:count.value].copy(), dist[:count.value].copy()
+
+
 def _np_priors(priors) -> np.ndarray:
     """One prior per row (float32, contiguous); the library checks the values."""
     return np.ascontiguousarray(np.asarray(priors, dtype=np.float32).reshape(-1))
@@ -546,6 +575,19 @@ class CosineEngine:
         return _playlist_family(self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), members, topn, exclude, where,
                                 weights, level, labels=labels, **more)
 
+    # ---- DISTANCE REQUESTS (include/mi355rec_diag.h): the nearest rows by Euclidean distance ----
+    def query_nearest(self, members, topn: int, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The `topn` rows nearest to the rows of `members` (k x 12) by Euclidean distance over the 12 features: (ids,
+        distances), nearest first.  k > 1: the root-mean-square distance to the members (as a ranking: the distance to their
+        centroid).  `exclude`, `where`, `labels`: as in query_mean_topn."""
+        return _distance_request(self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), _np_members(members), topn,
+                                 exclude, where, labels)
+
+    def query_nearest_rows(self, rows, topn: int, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The same for members given as rows of this handle; the members are never returned."""
+        return _distance_request(self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), _np_rows(rows), topn,
+                                 exclude, where, labels)
+
     # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h): MMR picks from the top-`pool` of the weighted playlist call ----
     def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False, labels=None, prior_weight=None):
         """`topn` rows picked greedily from the `pool` most relevant (query_mean_topn's order): each pick maximises
@@ -726,6 +768,15 @@ class NodeEngine:
     def _playlist(self, members, topn, exclude, where, weights, level=None, labels=None, **more):
         return _playlist_family(self._lib, "mi355rec_sharded_", self._h, self._check, members, topn, exclude, where, weights, level,
                                 labels=labels, **more)
+
+    # ---- DISTANCE REQUESTS (include/mi355rec_diag.h) over the whole node ----
+    def query_nearest(self, members, topn: int, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The `topn` rows nearest to the rows of `members` (k x 12) by Euclidean distance: (ids, distances)."""
+        return _distance_request(self._lib, "mi355rec_sharded_", self._h, self._check, _np_members(members), topn, exclude, where, labels)
+
+    def query_nearest_rows(self, rows, topn: int, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The same for members given as global rows (never returned)."""
+        return _distance_request(self._lib, "mi355rec_sharded_", self._h, self._check, _np_rows(rows), topn, exclude, where, labels)
 
     # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h) over the whole node ----
     def set_groups(self, groups) -> None:
