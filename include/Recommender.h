@@ -168,6 +168,15 @@ public:
     std::vector<int> recommendNearest(const std::vector<int>& songIndices, int topN, const std::vector<FeatureRange>& where = {},
                                       const std::vector<int>& genreIds = {});
 
+    // Extension: feature scales (include/mi355rec_diag.h, "FEATURE SCALES").  recommendScaled is the playlist recommendation
+    // (euclidean = false: lastScores() holds the scaled cosine means, best first) or recommendNearest (euclidean = true:
+    // lastScores() holds the distances) with every feature j of the songs multiplied by scales[j] first: 12 non-negative
+    // factors in Song.h order, 0 ignores a feature, 2 makes it count double; an empty vector is the unscaled call.  `where`
+    // still tests the stored features.  Same messages and {} on bad input as recommendNearest; the engine refuses scales that
+    // are negative, not finite, above 1024 or all zero.
+    std::vector<int> recommendScaled(const std::vector<int>& songIndices, int topN, const std::vector<float>& scales, bool euclidean,
+                                     const std::vector<FeatureRange>& where = {}, const std::vector<int>& genreIds = {});
+
     struct Impl;   // opaque: defined in Recommender.cpp
 
 private:

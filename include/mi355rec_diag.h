@@ -30,6 +30,8 @@
  *     (mi355rec_set_priors, MI355REC_PQ_PRIOR and prior_weight of the request, and the node-handle twin);
  *   - DISTANCE REQUESTS: the nearest rows by Euclidean distance to up to 32 members, with the playlist request's exclusion
  *     list, feature filter and label set (mi355rec_query_distance_request and its node-handle twin);
+ *   - FEATURE SCALES: 12 non-negative per-request factors that weigh or ignore features in the playlist and distance requests
+ *     (mi355rec_query_playlist_request_scaled, mi355rec_query_distance_request_scaled and their node-handle twins);
  *   - test hooks, compiled in only with -DMI355REC_TEST_HOOKS (spotify_recommender_amd/build.py builds
  *     libmi355rec_testhooks.so for tests/; the product library does not export them).
  */
@@ -736,6 +738,53 @@ typedef struct {
 int mi355rec_query_distance_request(mi355rec_t* h, const mi355rec_distance_query_t* query, const mi355rec_distance_result_t* result);
 int mi355rec_sharded_query_distance_request(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
                                             const mi355rec_distance_result_t* result);
+
+/* FEATURE SCALES: which features count, and how much.  Every ranking above compares all 12 columns at equal weight; key, mode
+ * and the genre id are categorical codes on which cosine and Euclidean geometry mean little, and one dominant unnormalised
+ * feature decides a distance by itself.  A scaled request takes 12 host floats a_0 .. a_11, one per column in Song.h order, beside
+ * the request's struct (both structs are frozen at 88 and 64 bytes, so the scales travel in four entry points of their own).
+ * DEFINITION, bit for bit: with x'_j = fl(a_j x_j) for every row and q'_kj = fl(a_j q_kj) for every member (ONE fp32 multiply
+ * each), the scaled request returns exactly what the unscaled request of the same struct returns for the members q' on a
+ * catalogue whose rows are x'.  The chains, member order, member weights and W, canonical order, ties, -0.0 -> +0.0, counts and
+ * padding are unchanged.  Members given by row are scaled from the stored row, members given by value from the vector the caller
+ * passed.  The reported score is the scaled cosine mean; out_distance is sqrtf(m') and a row is admissible for the distance
+ * metric iff m' is finite.  fl(0 * NaN) is NaN and fl(0 * inf) is NaN: a zero scale does NOT hide a NaN or an inf in that column
+ * (a cosine chain then answers as it does for any NaN row; a distance request never lists the row).  The feature filter tests
+ * the STORED x, never x'.  Exclusion, member rows and label sets are unchanged.
+ * ARGUMENTS: feature_scales == NULL is exactly the unscaled call (same launch, same results).  Otherwise every a_j is finite with
+ * 0 <= a_j <= MI355REC_MAX_FEATURE_SCALE (-0.0f counts as 0), at least one a_j > 0, and the playlist struct's flags must be 0.
+ * Every other check and message is the unscaled request's.  Anything else is INVALID_ARG with a message that names the feature
+ * index and its value, or the refused flag.
+ * IDENTITIES (tests/test_scaled_cpu.py, tests/test_gpu_scaled.py):
+ *   - all scales 1.0f: the unscaled request's ids and score bits (the host routes it to the unscaled launch);
+ *   - scales in {0, 1}: the request on the catalogue with those columns zeroed;
+ *   - every scale times one power of two: the same cosine ids and score bits, distances times exactly that factor, as long as
+ *     nothing overflows, underflows or crosses the chain's den > 1e-8 rule;
+ *   - the result does not depend on shard count, placement, lane or replica mode.
+ * Device: a uniform runtime branch of playlist_scan_kernel (csrc/playlist.hip.h, "FEATURE SCALES"): no new kernel; calls without
+ * scales take none of its branches.  A loaded row is scaled once (12 multiplies), then the unscaled chains run.  With the 8-bit
+ * replica a scaled COSINE request keeps a pre-filter: the replica's dot product bounds the numerator and the row's own bytes
+ * bound |Abar x^| (Abar = the scales over their maximum), a per-row integer cut rules rows out.  It is on for a_max in
+ * [2^-10, 8] and members whose scaled norms are in range; rows with too little mass on the kept features take the chains.  With
+ * one feature kept every cosine is +-1 and every row takes the chains.  A scaled DISTANCE request runs on the exact path (every
+ * row takes the chains; the stored norms are those of the unscaled rows).
+ * Measured on one MI355X at 10 M uniform rows, top-100, K = 1 (tools/run_scaled.py, profiles/r15_scaled.json): the cosine request
+ * 91.4 us per call without scales, 111.9 us with key, mode and genre id at 0, 116.5 us with the scales [2,1,.5,0,1,1,3,1,.25,1,1,0];
+ * K = 10: 132.9, 170.2 and 186.8 us.  The distance request 92.8 us without scales, 184.6 us scaled (212.4 us at K = 10).
+ * Node handle: one shard forwards; a replicated placement asks one replica; a row-sharded one fetches members given by row
+ * UNSCALED and forwards them by value with the scales, so each shard's fl(a_j x_j) is the by-row value; keys merge as before.
+ * The CPU backend serves the same calls with the same two steps.
+ * Not served: diversified and capped calls with scales; priors with scales; the re-rank's c(i,p) on scaled features; scales on
+ * the single-query, streamed, batched and label-only routes; negative scales; a pre-filter for scaled distance requests. */
+#define MI355REC_MAX_FEATURE_SCALE 1024.0f
+int mi355rec_query_playlist_request_scaled(mi355rec_t* h, const mi355rec_playlist_query_t* query, const float* feature_scales,
+                                           const mi355rec_playlist_result_t* result);
+int mi355rec_query_distance_request_scaled(mi355rec_t* h, const mi355rec_distance_query_t* query, const float* feature_scales,
+                                           const mi355rec_distance_result_t* result);
+int mi355rec_sharded_query_playlist_request_scaled(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
+                                                   const float* feature_scales, const mi355rec_playlist_result_t* result);
+int mi355rec_sharded_query_distance_request_scaled(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
+                                                   const float* feature_scales, const mi355rec_distance_result_t* result);
 
 #ifdef MI355REC_TEST_HOOKS
 /* TEST HOOK for the cross-workgroup hand-offs of the streamed scans (csrc/replica.hip.h, "hand-offs that fail

@@ -47,6 +47,7 @@ class Filter(ctypes.Structure):
 
 PQ_DIVERSE, PQ_CAPPED, PQ_PRIOR = 1, 2, 4
 MAX_PRIOR_WEIGHT = 4.0
+MAX_FEATURE_SCALE = 1024.0   # MI355REC_MAX_FEATURE_SCALE (FEATURE SCALES)
 
 
 class PlaylistQuery(ctypes.Structure):
@@ -245,6 +246,11 @@ SIGNATURES = {
     "mi355rec_sharded_query_playlist_request": (c_int, [c_void_p, POINTER(PlaylistQuery), POINTER(PlaylistResult)]),
     "mi355rec_query_distance_request": (c_int, [c_void_p, POINTER(DistanceQuery), POINTER(DistanceResult)]),
     "mi355rec_sharded_query_distance_request": (c_int, [c_void_p, POINTER(DistanceQuery), POINTER(DistanceResult)]),
+    # FEATURE SCALES: the two requests with 12 per-feature factors (NULL: the unscaled call)
+    "mi355rec_query_playlist_request_scaled": (c_int, [c_void_p, POINTER(PlaylistQuery), c_void_p, POINTER(PlaylistResult)]),
+    "mi355rec_query_distance_request_scaled": (c_int, [c_void_p, POINTER(DistanceQuery), c_void_p, POINTER(DistanceResult)]),
+    "mi355rec_sharded_query_playlist_request_scaled": (c_int, [c_void_p, POINTER(PlaylistQuery), c_void_p, POINTER(PlaylistResult)]),
+    "mi355rec_sharded_query_distance_request_scaled": (c_int, [c_void_p, POINTER(DistanceQuery), c_void_p, POINTER(DistanceResult)]),
     "mi355rec_pack_key": (c_uint64, [c_float, c_int64]),
     "mi355rec_key_score": (c_float, [c_uint64]),
     "mi355rec_key_row": (c_int64, [c_uint64]),

@@ -519,6 +519,11 @@ std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songI
 
 std::vector<int> Recommender::recommendNearest(const std::vector<int>& songIndices, int topN, const std::vector<FeatureRange>& where,
                                                const std::vector<int>& genreIds) {
+    return recommendScaled(songIndices, topN, {}, true, where, genreIds);
+}
+
+std::vector<int> Recommender::recommendScaled(const std::vector<int>& songIndices, int topN, const std::vector<float>& scales, bool euclidean,
+                                              const std::vector<FeatureRange>& where, const std::vector<int>& genreIds) {
     Impl* impl = impl_;
     if (!impl->initialized) {
         std::cerr << "Error: Recommender not initialized" << std::endl;
@@ -538,6 +543,10 @@ std::vector<int> Recommender::recommendNearest(const std::vector<int>& songIndic
         std::cerr << "Error: topN must be positive" << std::endl;
         return {};
     }
+    if (!scales.empty() && scales.size() != MI355REC_DIM) {
+        std::cerr << "Error: " << scales.size() << " feature scales: one per feature, " << MI355REC_DIM << " in all" << std::endl;
+        return {};
+    }
     if (topN > impl->numSongs) topN = impl->numSongs;
     mi355rec_filter_t f;
     if (!makeFilter(where, f)) return {};
@@ -545,6 +554,31 @@ std::vector<int> Recommender::recommendNearest(const std::vector<int>& songIndic
     impl->idxBuf.assign(static_cast<size_t>(topN), -1);
     impl->scoreBuf.assign(static_cast<size_t>(topN), 0.0f);
     int count = 0;
+    const float* const a = scales.empty() ? nullptr : scales.data();
+    if (!euclidean) {   // the playlist request by row: the members are never returned
+        mi355rec_playlist_query_t pq{};
+        pq.size = sizeof pq;
+        pq.rows = rows.data();
+        pq.k = static_cast<int32_t>(rows.size());
+        pq.filter = where.empty() ? nullptr : &f;
+        if (!genreIds.empty()) {
+            pq.labels = genreIds.data();
+            pq.n_labels = static_cast<int32_t>(genreIds.size());
+        }
+        pq.topn = topN;
+        mi355rec_playlist_result_t pres{};
+        pres.out_idx = impl->idxBuf.data();
+        pres.out_score = impl->scoreBuf.data();
+        pres.out_count = &count;
+        if (mi355rec_sharded_query_playlist_request_scaled(impl->engine, &pq, a, &pres) != MI355REC_OK) {
+            std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
+            return {};
+        }
+        std::vector<int> results(static_cast<size_t>(count));
+        for (int i = 0; i < count; ++i) results[i] = static_cast<int>(impl->idxBuf[i]);
+        impl->lastScores.assign(impl->scoreBuf.begin(), impl->scoreBuf.begin() + count);
+        return results;
+    }
     mi355rec_distance_query_t q{};
     q.size = sizeof q;
     q.rows = rows.data();
@@ -559,7 +593,7 @@ std::vector<int> Recommender::recommendNearest(const std::vector<int>& songIndic
     res.out_idx = impl->idxBuf.data();
     res.out_distance = impl->scoreBuf.data();
     res.out_count = &count;
-    if (mi355rec_sharded_query_distance_request(impl->engine, &q, &res) != MI355REC_OK) {
+    if (mi355rec_sharded_query_distance_request_scaled(impl->engine, &q, a, &res) != MI355REC_OK) {
         std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
         return {};
     }

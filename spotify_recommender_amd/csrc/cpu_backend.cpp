@@ -426,14 +426,36 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
     // "DISTANCE REQUESTS": m(x) = fl(fl(d2_0 + ... + d2_{k-1}) / k), d2_k the sequential fp32 sum of fl(t * t), t = fl(q_kj - x_j);
     // keys carry -m, a row whose m is not finite gets no key (it is not admissible).
     const bool dist = r.metric == mi355playlist::kDistance;
+    // "FEATURE SCALES": two steps, as on the device: members and rows scaled with one fp32 multiply per feature, then the chains
+    // above on the scaled values.  The filter below tests the stored rows f.
+    const float* const a = r.scales;
+    std::vector<float> scaled_members;
+    if (a) {
+        try {
+            scaled_members.assign(members, members + static_cast<size_t>(k) * kDim);
+        } catch (const std::bad_alloc&) {
+            *why = "out of host memory";
+            return MI355REC_ERR_OUT_OF_MEMORY;
+        }
+        for (int m = 0; m < k; ++m)
+            for (int j = 0; j < kDim; ++j) scaled_members[static_cast<size_t>(m * kDim + j)] = a[j] * members[m * kDim + j];
+        members = scaled_members.data();
+        for (int m = 0; m < k; ++m) qn[static_cast<size_t>(m)] = query_norm(members + m * kDim);
+    }
 #pragma omp parallel for schedule(static) num_threads(c->threads)
     for (int64_t i = 0; i < n; ++i) {
+        float xs[kDim];
+        const float* x = f + i * kDim;   // the row the chains read: the stored one, or its scaled copy
+        if (a) {
+            for (int j = 0; j < kDim; ++j) xs[j] = a[j] * x[j];
+            x = xs;
+        }
         if (dist) {
             float sum = 0.0f;
             for (int m = 0; m < k; ++m) {
                 float acc = 0.0f;
                 for (int j = 0; j < kDim; ++j) {
-                    const float t = members[m * kDim + j] - f[i * kDim + j];
+                    const float t = members[m * kDim + j] - x[j];
                     const float sq = t * t;
                     acc = acc + sq;
                 }
@@ -443,9 +465,9 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
             keys[static_cast<size_t>(i)] = std::isfinite(mean) ? pack(-mean, static_cast<uint32_t>(i)) : 0;
             continue;
         }
-        float sum = w[0] * score(members, qn[0], f + i * kDim);
+        float sum = w[0] * score(members, qn[0], x);
         for (int m = 1; m < k; ++m) {
-            const float term = w[static_cast<size_t>(m)] * score(members + m * kDim, qn[static_cast<size_t>(m)], f + i * kDim);
+            const float term = w[static_cast<size_t>(m)] * score(members + m * kDim, qn[static_cast<size_t>(m)], x);
             sum = sum + term;
         }
         float v = sum / wsum;

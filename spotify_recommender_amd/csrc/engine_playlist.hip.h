@@ -167,6 +167,8 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     arg.prior = pri ? 1 : 0;
     arg.prior_weight = pri ? r.prior_weight : 0.0f;
     arg.metric = r.metric == mi355playlist::kDistance ? kPlDistance : kPlCosine;
+    arg.scaled = r.scales ? 1 : 0;   // "FEATURE SCALES" (every scale 1.0f has become null scales: the unscaled launch)
+    for (int j = 0; j < kDim; ++j) b->scales[j] = r.scales ? r.scales[j] : 1.0f;
     for (int m = 0; m < k; ++m) b->weights[m] = r.weights ? r.weights[m] : 1.0f;
     if (arg.active) {
         std::memcpy(b->lo, r.filter->lo, sizeof b->lo);
@@ -178,7 +180,9 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     // here leaves nothing begun and nothing staged.
     const uint4* q8 = use_q8(h) ? h->d_q8 : nullptr;
     const int64_t n_quads4 = (h->n + 3) / 4 * 4;
-    const bool fresh_norms = q8 && arg.metric == kPlDistance && !P->norms_built;
+    // (a scaled distance request takes the exact path: the norms are those of the unscaled rows, it is launched with null norms)
+    const bool scan_norms = q8 && arg.metric == kPlDistance && !arg.scaled;
+    const bool fresh_norms = scan_norms && !P->norms_built;
     if (fresh_norms && !P->d_norms) {   // (an earlier call that failed before its build was enqueued has left the allocation)
         const hipError_t e = hipMalloc(&P->d_norms, sizeof(float) * static_cast<size_t>(n_quads4));
         if (e != hipSuccess) {
@@ -210,7 +214,7 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
                  static_cast<const float*>(h->d_anchor), eff, h->d_block_lists, P->d_exact,
                  reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr)),
                  reinterpret_cast<const uint2*>(L ? L->d_row_labels : nullptr), reinterpret_cast<const float4*>(pri),
-                 reinterpret_cast<const float4*>(arg.metric == kPlDistance && q8 ? P->d_norms : nullptr));
+                 reinterpret_cast<const float4*>(scan_norms ? P->d_norms : nullptr));
     HIP_TRY(h, hipGetLastError());
     *grid_out = grid;
     return MI355REC_OK;
@@ -304,25 +308,38 @@ int mi355rec_query_playlist_topn_weighted(mi355rec_t* h, const int64_t* local_ro
 }
 
 // "PLAYLIST REQUESTS": the family's one call; every entry point above (and engine_diverse.hip.h's) is a special case of it.
-int mi355rec_query_playlist_request(mi355rec_t* h, const mi355rec_playlist_query_t* query, const mi355rec_playlist_result_t* result) {
+// ("FEATURE SCALES": the request with null scales is the NULL-scales case of the one path below.)
+int mi355rec_query_playlist_request_scaled(mi355rec_t* h, const mi355rec_playlist_query_t* query, const float* feature_scales,
+                                           const mi355rec_playlist_result_t* result) {
     if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
     mi355rec_playlist_query_t full;
     Request r;
     Outputs out;
-    char why[128];
-    if (mi355playlist::from_query(query, result, &full, &r, &out, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    char why[160];
+    if (mi355playlist::from_query_scaled(query, feature_scales, result, &full, &r, &out, why, sizeof why))
+        return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
     return sync_playlist_query(h, r, out);
 }
 
+int mi355rec_query_playlist_request(mi355rec_t* h, const mi355rec_playlist_query_t* query, const mi355rec_playlist_result_t* result) {
+    return mi355rec_query_playlist_request_scaled(h, query, nullptr, result);
+}
+
 // "DISTANCE REQUESTS": the same Request with metric = kDistance through the same path.
-int mi355rec_query_distance_request(mi355rec_t* h, const mi355rec_distance_query_t* query, const mi355rec_distance_result_t* result) {
+int mi355rec_query_distance_request_scaled(mi355rec_t* h, const mi355rec_distance_query_t* query, const float* feature_scales,
+                                           const mi355rec_distance_result_t* result) {
     if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
     mi355rec_distance_query_t full;
     Request r;
     Outputs out;
     char why[160];
-    if (mi355playlist::from_distance_query(query, result, &full, &r, &out, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    if (mi355playlist::from_distance_query_scaled(query, feature_scales, result, &full, &r, &out, why, sizeof why))
+        return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
     return sync_playlist_query(h, r, out);
+}
+
+int mi355rec_query_distance_request(mi355rec_t* h, const mi355rec_distance_query_t* query, const mi355rec_distance_result_t* result) {
+    return mi355rec_query_distance_request_scaled(h, query, nullptr, result);
 }
 
 // "ROW PRIORS"

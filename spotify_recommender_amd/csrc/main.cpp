@@ -21,6 +21,8 @@
 //       [-1, 1] per line, in catalogue order; usable with every other option of the --playlist mode)
 //   ... --song, --id and --playlist with --metric euclidean: the NEAREST songs by Euclidean distance over the 12 features instead
 //       of the most similar by cosine (extension; with --genre and --where; distances are printed)
+//   ... --song, --id and --playlist with one or more --scale NAME=S: feature NAME counts S times (0: ignored) in the similarity or
+//       the distance (extension; under both metrics, with --genre and --where)
 //   ... --playlist with --dislike "<track_id>,..." [--dislike-weight W] [--weights "w,w,..."]: weighted playlists (extension):
 //       the disliked songs push results away (weight -W, default 0.5), --weights gives the playlist's songs their own weights
 #include <algorithm>
@@ -69,7 +71,12 @@ static void usage(const char* prog) {
               << "Euclidean metric (extension): --metric euclidean, with --song, --id or --playlist (and --genre, --where): the nearest\n"
               << "   songs by distance over the 12 normalised features (for a playlist: the root-mean-square distance to its songs).\n"
               << "   Cosine ignores how large the features are; the distance does not.  Not with --diverse, --weights, --dislike,\n"
-              << "   --priors or --max-per-artist.  --metric cosine is the default.\n" << std::endl;
+              << "   --priors or --max-per-artist.  --metric cosine is the default.\n"
+              << "Feature scales (extension): --scale NAME=S, repeatable, with --song, --id or --playlist, under both metrics (and\n"
+              << "   --genre, --where): every song's feature NAME is multiplied by S (0 to 1024) before songs are compared, so S = 0\n"
+              << "   ignores the feature and S = 2 makes it count double; features not named keep 1.  NAME is one of --where's names or\n"
+              << "   genre (the numeric genre id).  --where still tests the stored values.  Not with --diverse, --pool,\n"
+              << "   --max-per-artist, --priors, --weights or --dislike.\n" << std::endl;
 }
 
 // --where NAME=LO:HI, any number of times from argv[first]: the ranges (feature indices in Song.h order).  false, with a
@@ -106,6 +113,56 @@ static bool parseWhere(int argc, char* argv[], int first, std::vector<Recommende
         }
         ranges.push_back({feature, l, h});
     }
+    return true;
+}
+
+// --scale NAME=S, any number of times from argv[first]: scales = 12 factors in Song.h order (1 where not named), or empty when the
+// option is not given.  false, with a message, on a malformed option, an unknown NAME or an option --scale is not served with.
+static bool parseScale(int argc, char* argv[], int first, std::vector<float>& scales) {
+    static const char* const kNames[] = {"danceability", "energy", "key", "loudness", "mode", "speechiness",
+                                         "acousticness", "instrumentalness", "liveness", "valence", "tempo", "genre"};
+    scales.clear();
+    for (int i = first; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--scale") != 0) continue;
+        if (i + 1 >= argc) {
+            std::cerr << "Error: --scale needs NAME=S" << std::endl;
+            return false;
+        }
+        const std::string arg = argv[++i];
+        const size_t eq = arg.find('=');
+        if (eq == std::string::npos) {
+            std::cerr << "Error: --scale '" << arg << "': expected NAME=S" << std::endl;
+            return false;
+        }
+        const std::string name = arg.substr(0, eq), value = arg.substr(eq + 1);
+        int feature = -1;
+        for (int j = 0; j < 12; ++j)
+            if (name == kNames[j]) feature = j;
+        if (feature < 0) {
+            std::cerr << "Error: --scale: unknown feature '" << name << "'" << std::endl;
+            return false;
+        }
+        char* end = nullptr;
+        const float v = std::strtof(value.c_str(), &end);
+        if (value.empty() || *end != '\0') {
+            std::cerr << "Error: --scale '" << arg << "': S must be a number" << std::endl;
+            return false;
+        }
+        if (scales.empty()) scales.assign(12, 1.0f);
+        scales[static_cast<size_t>(feature)] = v;
+    }
+    if (scales.empty()) return true;
+    for (int i = first; i < argc; ++i)
+        for (const char* no : {"--diverse", "--pool", "--weights", "--dislike", "--dislike-weight", "--priors", "--prior-weight", "--max-per-artist"})
+            if (std::strcmp(argv[i], no) == 0) {
+                std::cerr << "Error: --scale cannot be combined with " << no << " (scaled requests take --metric, --genre and --where only)"
+                          << std::endl;
+                return false;
+            }
+    std::cout << "Feature scales:";
+    for (int j = 0; j < 12; ++j)
+        if (scales[static_cast<size_t>(j)] != 1.0f) std::cout << " " << kNames[j] << "=" << scales[static_cast<size_t>(j)];
+    std::cout << std::endl;
     return true;
 }
 
@@ -607,10 +664,12 @@ static bool parseMetric(int argc, char* argv[], int first, bool& euclidean) {
     return true;
 }
 
-// --metric euclidean: the songs nearest to one song (--song / --id) or to a playlist's songs, with their distances.
+// --metric euclidean: the songs nearest to one song (--song / --id) or to a playlist's songs, with their distances; with
+// --scale (scales not empty) under either metric: the same over the scaled features, cosine printing its scores.
 static bool nearestMode(const std::string& query, bool isPlaylist, bool isTrackId, int topN,
-                        const std::vector<Recommender::FeatureRange>& ranges, const std::vector<std::string>& genres) {
-    std::cout << "=== NEAREST MODE (Euclidean distance) ===" << std::endl;
+                        const std::vector<Recommender::FeatureRange>& ranges, const std::vector<std::string>& genres,
+                        bool euclidean = true, const std::vector<float>& scales = {}) {
+    std::cout << (euclidean ? "=== NEAREST MODE (Euclidean distance) ===" : "=== SCALED MODE (cosine over scaled features) ===") << std::endl;
     DataManager::Catalogue catalogue;
     if (!DataManager::loadCatalogue(kBinaryDataFile, catalogue)) {
         std::cerr << "Failed to load data. Have you run preprocessing?" << std::endl;
@@ -643,7 +702,7 @@ static bool nearestMode(const std::string& query, bool isPlaylist, bool isTrackI
         std::cout << std::endl;
         if (!recommender.setGenreIds(catalogue.genreIds)) return false;
     }
-    const std::vector<int> recs = recommender.recommendNearest(members, topN, ranges, genreIds);
+    const std::vector<int> recs = recommender.recommendScaled(members, topN, scales, euclidean, ranges, genreIds);
     if (recs.empty()) {
         std::cerr << "No recommendations found. Please check the query." << std::endl;
         return false;
@@ -668,7 +727,7 @@ static bool nearestMode(const std::string& query, bool isPlaylist, bool isTrackI
             std::cerr << "Error: could not read song " << recs[i] << " from " << catalogue.path << std::endl;
             return false;
         }
-        std::cout << (i + 1) << ". \"" << song.track_name << "\"  (distance " << distances[i] << ")" << std::endl;
+        std::cout << (i + 1) << ". \"" << song.track_name << "\"  (" << (euclidean ? "distance " : "score ") << distances[i] << ")" << std::endl;
         printSong(song, genreMap, "   ");
         if (i + 1 < recs.size()) std::cout << std::endl;
     }
@@ -722,7 +781,9 @@ int main(int argc, char* argv[]) {
         if (!parseWhere(argc, argv, 3, ranges)) return 1;
         bool euclidean = false;
         if (!parseMetric(argc, argv, 3, euclidean)) return 1;
-        if (euclidean) return nearestMode(argv[2], false, mode == "--id", topN, ranges, genres) ? 0 : 1;
+        std::vector<float> scales;
+        if (!parseScale(argc, argv, 3, scales)) return 1;
+        if (euclidean || !scales.empty()) return nearestMode(argv[2], false, mode == "--id", topN, ranges, genres, euclidean, scales) ? 0 : 1;
         if (!ranges.empty() && !genres.empty()) {
             std::cerr << "Error: --where cannot be combined with --genre" << std::endl;
             return 1;
@@ -755,7 +816,9 @@ int main(int argc, char* argv[]) {
         if (!parseWhere(argc, argv, 3, ranges)) return 1;
         bool euclidean = false;
         if (!parseMetric(argc, argv, 3, euclidean)) return 1;
-        if (euclidean) {
+        std::vector<float> scales;
+        if (!parseScale(argc, argv, 3, scales)) return 1;
+        if (euclidean || !scales.empty()) {
             std::vector<std::string> in_genres;
             for (int i = 3; i < argc; ++i) {
                 if (std::strcmp(argv[i], "--genre") != 0) continue;
@@ -765,7 +828,7 @@ int main(int argc, char* argv[]) {
                 }
                 in_genres.push_back(argv[++i]);
             }
-            return nearestMode(argv[2], true, true, topN, ranges, in_genres) ? 0 : 1;
+            return nearestMode(argv[2], true, true, topN, ranges, in_genres, euclidean, scales) ? 0 : 1;
         }
         Taste taste;
         if (!parseTaste(argc, argv, 3, taste)) return 1;

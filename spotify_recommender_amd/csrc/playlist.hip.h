@@ -188,6 +188,77 @@
 //     with the K chains, and the topk-th best admissible one starts the threshold.
 // metric == kPlCosine takes none of these branches (uniform tests).
 //
+// FEATURE SCALES (include/mi355rec_diag.h, "FEATURE SCALES").  PlaylistArg::scaled (uniform) and PlaylistBuf::scales = a_0 .. a_11
+// (finite, 0 <= a_j <= 1024, not all zero: checked by the host; in LDS as s_scale).  The request is the unscaled request of
+// either metric on rows x'_j = fl(a_j x_j) and members q'_kj = fl(a_j q_kj), one fp32 multiply each:
+//   * members: scaled once in the prologue as they enter LDS (a member given by row after its row is read), so the members'
+//     norms, u, the centroid and Q2 are those of the scaled members with no further change;
+//   * exact chains (the exact path, 0x80 rows, survivors of the pre-filter, the anchor rows read from the matrix): the loaded
+//     Row is scaled once (scale_row: 12 multiplies, not once per member), then playlist_mean / playlist_sqdist run unchanged;
+//   * the feature filter tests the row BEFORE it is scaled (the stored x); labels and exclusion do not read features;
+//   * anchors: the table's copy is scaled and ranked by u (by the chain's d2 for the distance metric).  It only chooses rows, and
+//     the rule (the k-th best key among ANY k admissible rows bounds the answer) holds for any ranking value, so the shared
+//     atomicMax, selection and merge are unchanged;
+//   * DISTANCE with scales runs on the exact path: the host passes null `norms` (they are the unscaled rows' norms).
+//   * PRE-FILTER, cosine metric.  Write a_max = max_j a_j, abar_j = fl(a_j / a_max) (the fp32 values, in LDS as s_abar; Abar their
+//     diagonal matrix), u = the weighted mean of the scaled members' unit vectors as above (fp32: s_u), x^ = x / |x| and
+//         ubar = Abar u,   bn = |ubar| <= |u| <= 1,   g(x) = |Abar x^| in [0, 1].
+//     A cosine does not change when its row is multiplied by a_max, so in real numbers score(x) = (ubar . x^) / g(x): the numerator
+//     is the existing machinery (q8_query on ubar: ubar . x^ <= bn (approx + M)) and the denominator comes from the row's own
+//     replica bytes k_j = round(127 x^_j): with gk(x) = |Abar k| / 127,
+//         | gk - g | <= |Abar (k / 127 - x^)| <= |abar|_2 / 254 =: e        (each byte within 1/254 of x^_j; e <= sqrt(12) / 254),
+//         L(x) = gk - e <= g(x) <= U(x) = gk + e.
+//     With Tm = T - margin_scaled, T the workgroup's threshold score, a row is ruled out iff
+//         bn (approx + M) < Tm F(x),     F = L if Tm >= 0, U otherwise.
+//     Why that is sound (L > 0 below): for Tm >= 0, either bn (approx + M) >= 0 and score <= bn (approx + M) / L < Tm, or it is
+//     negative and score <= bn (approx + M) / U < 0 <= Tm; for Tm < 0 the left side is negative and score <= (that) / U < Tm.
+//     As the kernel's integer compare D < cut(x), in the style of the prior's and the distance's cuts:
+//         base(T) = fl( fl( fl(T - margin_scaled) / bn ) kQ8DotScale )          (refreshed whenever the threshold moves; -inf: none yet)
+//         (fmul, fadd) = (1 - 16 ulp, -e~) for Tm >= 0,  (1 + 16 ulp, +e~) otherwise,   e~ = fl( fl(|abar| 1.001 / 254) + 8 ulp )
+//         gk = fl( v_sqrt( seq sum_j fl( fl(abar_j k_j)^2 ) ) fl(1 / 127) ),    F = fl( fl(gk fmul) + fadd )
+//         cut(x) = int( clamp( fl( fl(base F) - c0 ), -2^30, 2^30 ) ) - 1,      c0 = fl( kQ8DotScale fl(M + 16 ulp) )
+//     row by row from the lane's quad (scaled_code_norm: per byte a conversion, a multiply, a square, an add into ONE accumulator;
+//     no four-row temporaries), the clamp after the arithmetic on the float and the - 1 after the truncation, as above.
+//     The roundings, ulp = 2^-24 relative (kPlUlp):
+//       - the scaling: x'_j = a_max abar_j x_j (1 + d), |d| <= 2 ulp (the product, and abar_j against a_j / a_max), so the real
+//         cosines of the fp32 rows x' and members q' (fixed fp32 vectors: u is defined from them) are within 4 ulp of
+//         (Abar u . x^) / g: numerator and denominator each move by at most 2 ulp of g.  5 counted.  A product a_j x_j that
+//         underflows is off by < 2^-149, nothing beside |x'| >= 1e-9 (below);
+//       - the chains on x': kPlChainErr and 2K ulp for the score's own roundings, as in PRE-FILTER above;
+//       - u in fp32 ((K + 9) ulp by weight, as above) and ubar_j = fl(abar_j u_j) (1 more): |(ubar~ - ubar) . x^| <= (K + 10) ulp g,
+//         so (K + 10) ulp of the score after the division by g;
+//       - bn in fp32 (query_norm: 8 ulp) multiplies bn (approx + M) / g <= |u| + 2 bn M / g <= 1 + 2 * 0.0137 * 64 < 2.8 for the
+//         rows the bound is claimed for (g >= 2^-6, below): 22 ulp;
+//       - fl(T - margin_scaled): one rounding of a quantity <= 1.01, 1 ulp, on the safe side once counted;
+//       5 + 2K + (K + 10) + 22 + 1 = 3K + 38: margin_scaled = kPlChainErr + (3K + kPlScaleUlps) ulp with kPlScaleUlps = 64.
+//       - gk: the byte conversion is exact, then 3 roundings per term and 12 terms (16 ulp of the sum, 8 of its root), v_sqrt_f32
+//         (1), the product with fl(1 / 127) (1.5): under 11 ulp, kPlScaleGkUlps = 16 is the factor (1 -+ 16 ulp) of F;
+//       - e~: |abar| by query_norm (8 ulp), the replica's own normalisation (v_rsq_f32: a byte may sit 4e-5 of a step off) and the
+//         fused against the sequential row norm are inside the factor 1.001; the 8 ulp added cover the two roundings of F;
+//       - the cut's own arithmetic (the quotient by bn, the product with kQ8DotScale, the product with F, the subtraction of c0,
+//         c0's two roundings: 6 roundings of quantities <= 1.05 kQ8DotScale wherever the compare is not already decided — beyond
+//         |base F| > 1.03 kQ8DotScale every row, or none, is ruled out whatever a relative 2^-22 does): kPlScaleCutUlps = 16 in c0.
+//     THE CHAIN'S den > 1e-8 RULE.  A valid replica row only guarantees |x| >= kBqMinNorm = 1.005e-4, and |x'| = a_max |x| g(x) may
+//     be far smaller: where den = |x'| |q'_k| <= 1e-8 the chain returns 0, which is ABOVE a negative real cosine and above the
+//     bound.  So the bound is claimed only for rows with L(x) >= l_floor = max(kPlScaleFloor, den_floor),
+//         den_floor = fl( 2e-4 / fl(a_max min_k |q'_k|) ):   |x'| |q'_k| >= a_max kBqMinNorm l_floor min |q'_k| >= 2e-8
+//     (twice the rule's 1e-8: the room for every rounding in it), tested as gk >= gk_min = fl( fl(l_floor + e~) (1 + 64 ulp) ).
+//     kPlScaleFloor = 2^-6 also bounds the amplification 1 / g used above.  Rows below the floor (no mass on the kept features: a
+//     zero row has gk = 0) take the chains.  den_floor > 0.5 switches the pre-filter off for the launch.
+//     OVERFLOW AND UNDERFLOW.  The pre-filter is on only for a_max in [kPlScaleMinMax, kPlScaleMaxMax] = [2^-10, 8]: a claimed row
+//     has |x'| <= 8 kBqMaxNorm = 8e18, so its sum of squares stays below 6.4e37 (at a_max = 1024 it would overflow and the chain
+//     would answer 1.0 for such a row), and |x'| >= 2^-10 * 1.005e-4 * 2^-6 > 1e-9, so no square that matters underflows.  The
+//     scaled members' norms must lie in [kBqMinNorm, kBqMaxNorm] as before (s_ok is taken on q'), bn must be finite and at least
+//     kPlMinMeanNorm, and q8_query must say ok.  Otherwise, and without a replica, every row takes the chains.
+//     With one feature kept every cosine is +-1 and nearly every row survives: correct, and as slow as the exact path.
+//     tests/test_scaled_margin.py checks the bound with a numpy model of exactly this arithmetic (the square root one ulp off
+//     either way) against tests/scaled_oracle.py — every named scale set, a_max at both ends of the range and just outside it,
+//     K = 1, 3, 32, plain, positive, signed and likes-and-dislikes weights, T at the true top-10 threshold, 0 and negative,
+//     uniform and signed rows, rows with no mass on the kept features or at the floor, rows and members with norms at the edges of
+//     the valid range — and that it is not vacuous (at the true top-10 threshold of 65 537 uniform rows at most 5 % survive for
+//     K = 1, 3, 32; the model measures 0.3 - 1.5 %).
+// scaled == 0 takes none of these branches (uniform tests) and never reads PlaylistBuf::scales.
+//
 // EXCLUSION.  The excluded global ids (members and the caller's list, sorted and deduplicated on the host, at most
 // kPlExcludeCap) sit in LDS as uint32; only a key that already beats the workgroup's threshold is looked up (binary
 // search), so the hot loop does not change.
@@ -215,6 +286,14 @@ constexpr float kPlMinMeanNorm = 1e-3f;                     // |u| below this: t
 constexpr float kPlPriorUlps = 96.0f;                       // margin_prior - margin_mean, in kPlUlp (see ROW PRIORS above)
 constexpr int kPlCosine = 0, kPlDistance = 1;               // PlaylistArg::metric (mi355playlist::Metric)
 constexpr float kPlCutClamp = 1073741824.0f;                // 2^30: a per-row cut beyond it decides as the clamped one (|D| < 4.2e6)
+// FEATURE SCALES (see above)
+constexpr float kPlScaleMinMax = 0.0009765625f;             // 2^-10: the pre-filter of a scaled launch is on only for a_max in ...
+constexpr float kPlScaleMaxMax = 8.0f;                      // ... [2^-10, 8] (no square of a scaled valid row over- or underflows)
+constexpr float kPlScaleFloor = 0.015625f;                  // 2^-6: rows whose L(x) is below this (or below the den floor) take the chains
+constexpr float kPlScaleStep = 1.001f / 254.0f;             // e / |abar|: half a byte step, the replica's rsq offset inside the 1.001
+constexpr float kPlScaleGkUlps = 16.0f;                     // |Abar k| / 127 in fp32: within this many ulp (relative) of the real value
+constexpr float kPlScaleUlps = 64.0f;                       // margin_scaled - kPlChainErr - 3K ulp, in kPlUlp
+constexpr float kPlScaleCutUlps = 16.0f;                    // the cut's own arithmetic, in kPlUlp of approx
 using PlaylistCfg = Q8Cfg<512, 4, 1>;                       // kBlock, kMinWaves (two workgroups per CU); tiles of 2048 rows
 
 // One call's inputs on the device (written by the host before the launch).
@@ -224,6 +303,7 @@ struct PlaylistBuf {
     float lo[kDim];                  // the feature filter's bounds (read only where PlaylistArg::active has bit j)
     float hi[kDim];
     float weights[kMaxPlaylist];     // w_k, checked by the host (1.0f each for an unweighted call)
+    float scales[kDim];              // FEATURE SCALES a_j, checked by the host (read only where PlaylistArg::scaled)
     unsigned long long shared_thr;   // the best threshold any workgroup of the launch has found (0 from the host)
     uint32_t label_mask[kMaxLabels / 32];   // the label set (read only where PlaylistArg::labelled): bit l = label l is selected
     uint32_t excl[kPlExcludeCap];   // sorted, distinct global ids (only those of this shard)
@@ -239,6 +319,7 @@ struct PlaylistArg {
     float prior_weight;   // beta (read only where `prior`): v = fl(score + fl(beta p(x)))
     int prior;        // 1: rank by v, p from the kernel's `priors`; 0: rank by the score alone (`priors` is never read)
     int metric;       // kPlCosine, or kPlDistance: rank by -m(x), the mean squared distance to the members (DISTANCE above)
+    int scaled;       // 1: rows and members are multiplied by PlaylistBuf::scales before the chains (FEATURE SCALES above); 0: never read
 };
 
 // Is label l (int16 of the row-order array: -1 = unlabelled or padding) in the set?
@@ -254,6 +335,26 @@ __device__ __forceinline__ bool filter_pass(const Row& r, uint32_t active, const
     for (int j = 0; j < kDim; ++j)
         if (active & (1u << j)) ok = ok && lo[j] <= f[j] && f[j] <= hi[j];   // (false for a NaN feature)
     return ok;
+}
+
+// FEATURE SCALES: x'_j = fl(a_j x_j), one multiply per feature (a: LDS).
+__device__ __forceinline__ void scale_row(Row& r, const float* __restrict__ a) {
+    r.a = make_float4(a[0] * r.a.x, a[1] * r.a.y, a[2] * r.a.z, a[3] * r.a.w);
+    r.b = make_float4(a[4] * r.b.x, a[5] * r.b.y, a[6] * r.b.z, a[7] * r.b.w);
+    r.c = make_float4(a[8] * r.c.x, a[9] * r.c.y, a[10] * r.c.z, a[11] * r.c.w);
+}
+
+// FEATURE SCALES: |Abar k| / 127 of one replica row (3 dwords, byte j = k_j), abar in LDS: per byte a conversion, a multiply,
+// a square and an add into one accumulator (fp contract is off), then the hardware's square root (one ulp) and one multiply.
+__device__ __forceinline__ float scaled_code_norm(uint32_t d0, uint32_t d1, uint32_t d2, const float* __restrict__ abar) {
+    const uint32_t d[3] = {d0, d1, d2};
+    float acc = 0.0f;
+#pragma unroll
+    for (int j = 0; j < kDim; ++j) {
+        const float p = abar[j] * static_cast<float>(static_cast<int>(static_cast<int8_t>(d[j >> 2] >> (8 * (j & 3)))));
+        acc = acc + p * p;
+    }
+    return __builtin_amdgcn_sqrtf(acc) * (1.0f / 127.0f);
 }
 
 // cosine_score with the row's norm sqrtf(sum f_j^2) taken once for all members: the same operations in the same order.
@@ -357,6 +458,8 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     __shared__ float s_u[kDim];
     __shared__ uint32_t s_excl[kPlExcludeCap];
     __shared__ uint32_t s_lmask[kMaxLabels / 32];
+    __shared__ __attribute__((aligned(16))) float s_scale[kDim];   // FEATURE SCALES: a_j ...
+    __shared__ __attribute__((aligned(16))) float s_abar[kDim];    // ... and a_j / a_max (both only where arg.scaled)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -370,12 +473,25 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     const float beta = arg.prior_weight;
     const float* const row_prior = reinterpret_cast<const float*>(priors);
     const bool dist = arg.metric == kPlDistance;
+    const bool scaled = arg.scaled != 0;
     const float* const f_lo = buf->lo;
     const float* const f_hi = buf->hi;
 
     // ---- members and excluded ids into LDS; the members' norms and whether the bound can be claimed for them
-    for (int i = tid; i < k * kDim; i += kBlock)
-        s_mem[i / kDim][i % kDim] = arg.by_row ? feats[buf->rows[i / kDim] * kDim + i % kDim] : buf->members[i / kDim][i % kDim];
+    for (int i = tid; i < k * kDim; i += kBlock) {
+        const float q = arg.by_row ? feats[buf->rows[i / kDim] * kDim + i % kDim] : buf->members[i / kDim][i % kDim];
+        s_mem[i / kDim][i % kDim] = scaled ? buf->scales[i % kDim] * q : q;   // (uniform) FEATURE SCALES: q'_kj = fl(a_j q_kj)
+    }
+    float a_max = 1.0f;
+    if (scaled) {   // uniform
+        a_max = buf->scales[0];
+#pragma unroll
+        for (int j = 1; j < kDim; ++j) a_max = __builtin_fmaxf(a_max, buf->scales[j]);
+        if (tid < kDim) {
+            s_scale[tid] = buf->scales[tid];
+            s_abar[tid] = buf->scales[tid] / a_max;   // (the host has checked a_max > 0)
+        }
+    }
     for (int i = tid; i < n_excl; i += kBlock) s_excl[i] = buf->excl[i];
     if (labelled && tid < kMaxLabels / 32) s_lmask[tid] = buf->label_mask[tid];
     if (tid == 0) {
@@ -410,7 +526,31 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
 #pragma unroll
     for (int j = 0; j < kDim; ++j) u[j] = s_u[j];
     const float un = query_norm(u);
-    const Q8Query hq = q8_query(u, un);
+    // FEATURE SCALES: u (the mean in the scaled space) ranks the scaled anchors; the replica holds UNSCALED rows, so its query is
+    // ubar = Abar u and bn = |ubar| takes |u|'s place in the cut (unscaled: ubar = u, bn = un)
+    float bn = un, scale_e = 0.0f, scale_gk_min = __builtin_inff();
+    float uq[kDim];
+#pragma unroll
+    for (int j = 0; j < kDim; ++j) uq[j] = u[j];
+    if (scaled) {   // uniform
+        float ab[kDim];
+        float qn_min = s_qn[0];
+        for (int m = 1; m < k; ++m) qn_min = __builtin_fminf(qn_min, s_qn[m]);
+#pragma unroll
+        for (int j = 0; j < kDim; ++j) {
+            ab[j] = s_abar[j];
+            uq[j] = ab[j] * u[j];
+        }
+        bn = query_norm(uq);
+        scale_e = query_norm(ab) * kPlScaleStep + 8.0f * kPlUlp;
+        // rows with L(x) below the floor take the chains: the fixed floor, and the one that keeps every den of the chain above
+        // 1e-8 (|x'| >= a_max kBqMinNorm L, times the smallest scaled member norm: 2e-8 asked for)
+        const float den_floor = 2e-4f / (a_max * qn_min);
+        const float l_floor = __builtin_fmaxf(kPlScaleFloor, den_floor);
+        scale_gk_min = (l_floor + scale_e) * (1.0f + 4.0f * kPlScaleGkUlps * kPlUlp);
+        if (!(den_floor <= 0.5f && a_max >= kPlScaleMinMax && a_max <= kPlScaleMaxMax)) bn = 0.0f;   // (the pre-filter is off below)
+    }
+    const Q8Query hq = q8_query(uq, bn);
     // DISTANCE: the launch's constants of the per-row cut (see above); q2e * s2c must be finite or the cut could overflow upwards
     float dist_q2e = 0.0f, dist_s2c = 0.0f, dist_c0 = 0.0f;
     if (dist) {   // uniform
@@ -423,8 +563,13 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     }
     const float dist_a1 = dist_s2c * (1.0f - static_cast<float>(4 * k + 128) * kPlUlp);
     const bool prefilter = q8 != nullptr && s_ok != 0 && hq.ok &&
-                           (dist ? norms != nullptr && dist_q2e * dist_s2c < __builtin_inff() : un >= kPlMinMeanNorm);   // uniform (false for NaN)
+                           (dist ? norms != nullptr && dist_q2e * dist_s2c < __builtin_inff() : bn >= kPlMinMeanNorm);   // uniform (false for NaN)
     const float margin_mean = un * hq.margin + kPlChainErr + static_cast<float>(3 * k + 32) * kPlUlp;
+    // FEATURE SCALES: the replica's margin M is not part of margin_scaled: it sits in the cut's constant c0, beside the per-row factor
+    const float margin_scaled = kPlChainErr + (static_cast<float>(3 * k) + kPlScaleUlps) * kPlUlp;
+    const float scale_c0 = kQ8DotScale * (hq.margin + kPlScaleCutUlps * kPlUlp);
+    const bool scaled_cut = scaled && prefilter;   // uniform: the per-row cut of FEATURE SCALES (never with a prior or a distance)
+    float scale_fmul = 1.0f, scale_fadd = 0.0f;   // F(x) = fl(fl(gk fmul) + fadd): L(x) or U(x), by the sign of T - margin_scaled
     const float margin_prior = margin_mean + kPlPriorUlps * kPlUlp;
     const float prior_scale = (beta * kQ8DotScale) / un;   // bs (only used where prior && prefilter: |u| >= kPlMinMeanNorm then)
     const bool side = (prior || dist) && prefilter;          // a 4 B/row side array streams with the replica: the priors, or the norms
@@ -440,14 +585,16 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
 #pragma unroll
         for (int r = 0; r < kPer; ++r) {
             const int i = r * kBlock + tid;
-            const Row a = load_row(anchors, static_cast<int64_t>(i));
+            Row a = load_row(anchors, static_cast<int64_t>(i));
+            const bool a_pass = !active || filter_pass(a, active, f_lo, f_hi);   // (the filter tests the stored values)
+            if (scaled) scale_row(a, s_scale);   // (uniform)
             if (dist) {   // (uniform) DISTANCE: the anchors nearest to the centroid; a distance that is not finite is no candidate
                 const float d = row_sqdist(u, a);
                 mine[r] = i < n_anchor && d < __builtin_inff() ? pack_key(-d, static_cast<uint32_t>(i)) : 0ull;
             } else {
                 mine[r] = i < n_anchor ? pack_key(cosine_score(u, un, a), static_cast<uint32_t>(i)) : 0ull;
             }
-            if (active && !filter_pass(a, active, f_lo, f_hi)) mine[r] = 0ull;   // (only chooses: re-checked on the matrix's row)
+            if (!a_pass) mine[r] = 0ull;   // (only chooses: re-checked on the matrix's row)
             if (labelled && i < n_anchor && !label_selected(s_lmask, row_label[anchor_row(n, i)])) mine[r] = 0ull;
         }
         int n_cand = kPlBoundRows;   // anchors left to choose from: all of them without a filter
@@ -480,7 +627,9 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
         uint64_t key = 0ull;
         if (tid < picked) {
             const int64_t row = anchor_row(n, s_pick[tid]);
-            const Row x = load_row(feats, row);   // from the matrix
+            Row x = load_row(feats, row);   // from the matrix
+            const bool x_pass = !active || filter_pass(x, active, f_lo, f_hi);   // (the filter tests the stored row)
+            if (scaled) scale_row(x, s_scale);   // (uniform)
             float m;
             bool finite = true;
             if (dist) {   // uniform
@@ -493,7 +642,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
             if (prior) m = m + beta * row_prior[row];   // (uniform) v: multiply, round, add, round
             ++n_exact;
             const uint32_t g = static_cast<uint32_t>(row_base + row);
-            key = !finite || playlist_excluded(s_excl, n_excl, g) || (active && !filter_pass(x, active, f_lo, f_hi)) ||
+            key = !finite || playlist_excluded(s_excl, n_excl, g) || !x_pass ||
                           (labelled && !label_selected(s_lmask, row_label[row]))
                       ? 0ull
                       : pack_key(m, g);
@@ -529,11 +678,19 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     auto refresh_prior_cut = [&]() {
         if (thr != 0ull) {   // uniform
             const float t = ordered_to_score(static_cast<uint32_t>(thr >> 32));
-            if (dist) cut_base = (dist_q2e - (0.0f - t)) * dist_s2c;   // (uniform) DISTANCE: b(T), T = -t the threshold's m
-            else cut_base = ((t - margin_prior) / un) * kQ8DotScale;
+            if (dist) {   // (uniform) DISTANCE: b(T), T = -t the threshold's m
+                cut_base = (dist_q2e - (0.0f - t)) * dist_s2c;
+            } else if (scaled_cut) {   // (uniform) FEATURE SCALES: base(T), and L or U as the factor by its sign
+                const float tm = t - margin_scaled;
+                cut_base = (tm / bn) * kQ8DotScale;
+                scale_fmul = tm >= 0.0f ? 1.0f - kPlScaleGkUlps * kPlUlp : 1.0f + kPlScaleGkUlps * kPlUlp;
+                scale_fadd = tm >= 0.0f ? -scale_e : scale_e;
+            } else {
+                cut_base = ((t - margin_prior) / un) * kQ8DotScale;
+            }
         }
     };
-    if (side) refresh_prior_cut();   // uniform
+    if (side || scaled_cut) refresh_prior_cut();   // uniform
     else refresh_cut();
     int compact_at = 2 * topk > 256 ? 2 * topk : 256;
     if (compact_at > kCandLimit) compact_at = kCandLimit;
@@ -599,6 +756,17 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
                     const bool claimed = sn >= kBqMinNorm && sn <= kBqMaxNorm;   // (false for a zero, tiny, huge or NaN norm: always exact)
                     if (!(special[u4] || !claimed || a[u4] >= cut)) mask &= ~(1u << u4);
                 }
+            } else if (scaled_cut) {   // (uniform) FEATURE SCALES: the per-row cut base(T) F(x) - c0, row by row from the row's own bytes
+                const uint32_t w[12] = {cur.t0.x, cur.t0.y, cur.t0.z, cur.t0.w, cur.t1.x, cur.t1.y,
+                                        cur.t1.z, cur.t1.w, cur.t2.x, cur.t2.y, cur.t2.z, cur.t2.w};
+#pragma unroll
+                for (int u4 = 0; u4 < 4; ++u4) {
+                    const float gk = scaled_code_norm(w[3 * u4], w[3 * u4 + 1], w[3 * u4 + 2], s_abar);
+                    const float c = cut_base * (gk * scale_fmul + scale_fadd) - scale_c0;
+                    const int cut = static_cast<int>(__builtin_fminf(__builtin_fmaxf(c, -kPlCutClamp), kPlCutClamp)) - 1;
+                    const bool claimed = gk >= scale_gk_min;   // (L(x) at or above the floor; false for an all-zero row)
+                    if (!(special[u4] || !claimed || a[u4] >= cut)) mask &= ~(1u << u4);
+                }
             } else if (!prior) {   // uniform
 #pragma unroll
                 for (int u4 = 0; u4 < 4; ++u4)
@@ -628,7 +796,8 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
         while (__ballot(mask != 0u)) {   // uniform
             const bool have = mask != 0u;
             const int64_t r = have ? r0 + __builtin_ctz(mask) : 0;
-            const Row x = load_row(feats, r);
+            Row x = load_row(feats, r);
+            if (scaled) scale_row(x, s_scale);   // (uniform) FEATURE SCALES: once per row, then the chains unchanged
             float m;
             bool finite = true;
             if (dist) {   // (uniform) DISTANCE: the key carries -m; a row whose m is not finite forms no key
@@ -665,7 +834,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
             if (local_thr > thr) thr = local_thr;
         }
         if (published > thr) thr = published;
-        if (side) refresh_prior_cut();   // uniform
+        if (side || scaled_cut) refresh_prior_cut();   // uniform
         else refresh_cut();
         cur = nxt;
         lab_cur = lab_nxt;

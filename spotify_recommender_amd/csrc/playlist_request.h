@@ -43,6 +43,8 @@ struct Request {
                                                 // ... members, ascending; keys and scores carry -m
     bool report_distance = false;               // (kDistance) the score output holds sqrtf(m); false: -m itself, what a node
                                                 // ... handle's merge over shards compares
+    const float* scales = nullptr;              // null, or 12 checked feature scales a_j ("FEATURE SCALES"): the call is the same
+                                                // ... call on rows fl(a_j x_j) with members fl(a_j q_kj); the filter tests x itself
 
     int scan_topn() const { return diverse ? pool : topn; }   // what the scan selects
     // The same call diversified, and (of a diversified one) capped: what the _diverse and _capped entry points add.
@@ -266,6 +268,53 @@ inline bool from_query(const mi355rec_playlist_query_t* q, const mi355rec_playli
     return false;
 }
 
+// "FEATURE SCALES": true when the 12 scales cannot be used (each finite, 0 <= a_j <= MI355REC_MAX_FEATURE_SCALE, -0.0f is 0; at
+// least one > 0); then msg[0..cap) names the feature and its value.
+inline bool invalid_scales(const float* a, char* msg, size_t cap) {
+    bool any = false;
+    for (int j = 0; j < MI355REC_DIM; ++j) {
+        if (!(a[j] >= 0.0f && a[j] <= MI355REC_MAX_FEATURE_SCALE)) {   // (false for NaN)
+            std::snprintf(msg, cap, "feature scale %d is %g: a scale is finite and in [0, %g]", j, static_cast<double>(a[j]),
+                          static_cast<double>(MI355REC_MAX_FEATURE_SCALE));
+            return true;
+        }
+        any = any || a[j] > 0.0f;
+    }
+    if (!any) {
+        std::snprintf(msg, cap, "every feature scale is 0: at least one must be positive");
+        return true;
+    }
+    return false;
+}
+
+// The scales of a checked request as the launch takes them: null when there are none or every one is 1.0f (fl(1 x) = x: the
+// unscaled call bit for bit, so it takes the unscaled launch).
+inline const float* effective_scales(const float* a) {
+    if (!a) return nullptr;
+    for (int j = 0; j < MI355REC_DIM; ++j)
+        if (a[j] != 1.0f) return a;
+    return nullptr;
+}
+
+// from_query with the scales of the _scaled entry points: null scales are from_query itself; otherwise every check of from_query
+// first (its messages), then flags must be 0 and the scales usable.
+inline bool from_query_scaled(const mi355rec_playlist_query_t* q, const float* scales, const mi355rec_playlist_result_t* res,
+                              mi355rec_playlist_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
+    if (from_query(q, res, full, r, out, msg, cap)) return true;
+    if (!scales) return false;
+    static const struct { uint32_t bit; const char* name; } refused[] = {{MI355REC_PQ_DIVERSE, "MI355REC_PQ_DIVERSE"},
+                                                                         {MI355REC_PQ_CAPPED, "MI355REC_PQ_CAPPED"},
+                                                                         {MI355REC_PQ_PRIOR, "MI355REC_PQ_PRIOR"}};
+    for (const auto& f : refused)
+        if (full->flags & f.bit) {
+            std::snprintf(msg, cap, "%s with feature scales: flags must be 0 (diversified and capped calls and priors are not served)", f.name);
+            return true;
+        }
+    if (invalid_scales(scales, msg, cap)) return true;
+    r->scales = effective_scales(scales);
+    return false;
+}
+
 // The C-ABI's distance request (include/mi355rec_diag.h, "DISTANCE REQUESTS") as the same Request (metric = kDistance) and
 // Outputs: the size rules of from_query, flags must be 0.  True when the structs cannot be used; then msg[0..cap) says why.
 inline bool from_distance_query(const mi355rec_distance_query_t* q, const mi355rec_distance_result_t* res, mi355rec_distance_query_t* full,
@@ -311,6 +360,16 @@ inline bool from_distance_query(const mi355rec_distance_query_t* q, const mi355r
     r->metric = kDistance;
     r->report_distance = true;
     *out = {res->out_idx, res->out_distance, nullptr, res->out_count, nullptr};
+    return false;
+}
+
+// from_distance_query with the scales of the _scaled entry points (null: from_distance_query itself).
+inline bool from_distance_query_scaled(const mi355rec_distance_query_t* q, const float* scales, const mi355rec_distance_result_t* res,
+                                       mi355rec_distance_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
+    if (from_distance_query(q, res, full, r, out, msg, cap)) return true;
+    if (!scales) return false;
+    if (invalid_scales(scales, msg, cap)) return true;
+    r->scales = effective_scales(scales);
     return false;
 }
 

@@ -870,27 +870,42 @@ int mi355rec_sharded_query_playlist_topn_capped(mi355rec_sharded_t* h, const int
 
 // PLAYLIST REQUESTS (include/mi355rec_diag.h): the family's one call on the node handle; the label set travels in the Request
 // (one handle takes it as it is, a row-sharded catalogue hands it to every shard with that shard's slice of the labels).
-int mi355rec_sharded_query_playlist_request(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
-                                            const mi355rec_playlist_result_t* result) {
+// FEATURE SCALES: the scales travel in the Request.  One handle takes it as it is; a row-sharded catalogue has fetched the
+// members given by row UNSCALED (sharded_playlist) and forwards them by value with the scales, so every shard's fl(a_j x_j) is
+// the by-row value.
+int mi355rec_sharded_query_playlist_request_scaled(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
+                                                   const float* feature_scales, const mi355rec_playlist_result_t* result) {
     if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
     mi355rec_playlist_query_t full;
     Request r;
     Outputs out;
-    char why[128];
-    if (mi355playlist::from_query(query, result, &full, &r, &out, why, sizeof why)) return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    char why[160];
+    if (mi355playlist::from_query_scaled(query, feature_scales, result, &full, &r, &out, why, sizeof why))
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
     return sharded_playlist(h, r, out);
 }
 
+int mi355rec_sharded_query_playlist_request(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
+                                            const mi355rec_playlist_result_t* result) {
+    return mi355rec_sharded_query_playlist_request_scaled(h, query, nullptr, result);
+}
+
 // DISTANCE REQUESTS (include/mi355rec_diag.h): the same Request with metric = kDistance through sharded_playlist.
-int mi355rec_sharded_query_distance_request(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
-                                            const mi355rec_distance_result_t* result) {
+int mi355rec_sharded_query_distance_request_scaled(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
+                                                   const float* feature_scales, const mi355rec_distance_result_t* result) {
     if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
     mi355rec_distance_query_t full;
     Request r;
     Outputs out;
     char why[160];
-    if (mi355playlist::from_distance_query(query, result, &full, &r, &out, why, sizeof why)) return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    if (mi355playlist::from_distance_query_scaled(query, feature_scales, result, &full, &r, &out, why, sizeof why))
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
     return sharded_playlist(h, r, out);
+}
+
+int mi355rec_sharded_query_distance_request(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
+                                            const mi355rec_distance_result_t* result) {
+    return mi355rec_sharded_query_distance_request_scaled(h, query, nullptr, result);
 }
 
 int mi355rec_sharded_scores_row(mi355rec_sharded_t* h, int64_t global_row, float* out_host) {

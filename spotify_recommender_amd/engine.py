@@ -62,12 +62,35 @@ def make_filter(where) -> capi.Filter:
     return f
 
 
+def make_scales(scales) -> np.ndarray:
+    """The 12 float32 FEATURE SCALES (include/mi355rec_diag.h) from a `scales=` argument: a sequence of 12 floats, or a mapping
+    {feature index (0..11) or name (capi.FEATURE_NAMES): scale} with every feature it does not name at 1.0.  The library checks
+    the values (finite, in [0, capi.MAX_FEATURE_SCALE], not all zero)."""
+    if isinstance(scales, dict) or hasattr(scales, "items"):
+        a = np.ones(capi.DIM, dtype=np.float32)
+        for key, v in dict(scales).items():
+            if isinstance(key, str):
+                if key.lower() not in capi.FEATURE_NAMES:
+                    raise ValueError(f"unknown feature {key!r}: one of {', '.join(capi.FEATURE_NAMES)}")
+                j = capi.FEATURE_NAMES.index(key.lower())
+            else:
+                j = int(key)
+                if not 0 <= j < capi.DIM:
+                    raise ValueError(f"feature index {j} out of [0, {capi.DIM})")
+            a[j] = np.float32(v)
+        return a
+    a = np.ascontiguousarray(np.asarray(scales, dtype=np.float32).reshape(-1))
+    if a.size != capi.DIM:
+        raise ValueError(f"{a.size} scales: one per feature, {capi.DIM} in all")
+    return a
+
+
 _PLAYLIST_LEVELS = ("", "_where", "_weighted", "_diverse", "_capped")   # each level's entry point takes the previous one's arguments and its own
 
 
 def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=None, where=None, weights=None, level: str = None,
                      lam=None, pool=None, max_per_group=None, return_mmr: bool = False, return_pool_rows: bool = False, labels=None,
-                     prior_weight=None):
+                     prior_weight=None, scales=None):
     """Runs one entry point of the playlist family: `prefix`query_{mean|playlist}_topn`level`.  `members` is a (k, 12) float32
     array (by value: mean) or a 1-D int64 array of rows (by row: playlist).  `level` None: the lowest that takes the
     arguments given ("" plain, "_where" with a filter, "_weighted" with weights); "_diverse" and "_capped" are asked for.
@@ -86,7 +109,9 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
     label is in it; the call then goes through `prefix`query_playlist_request, the family's one struct-taking entry point.
     None takes exactly the entry point described above.
     ROW PRIORS: `prior_weight` = beta ranks by score + beta * prior (set_priors; |beta| <= capi.MAX_PRIOR_WEIGHT, negative demotes);
-    the call goes through the request as well, the returned scores are the blended values.  None takes the entry point used today."""
+    the call goes through the request as well, the returned scores are the blended values.  None takes the entry point used today.
+    FEATURE SCALES: `scales` (make_scales) weighs or ignores features; the call goes through `prefix`query_playlist_request_scaled,
+    which refuses diversified and capped calls and priors.  None takes the entry point used today."""
     if prior_weight is not None and (isinstance(prior_weight, bool) or not isinstance(prior_weight, (int, float, np.integer, np.floating))):
         raise ValueError(f"prior_weight must be a number or None, got {prior_weight!r}")
     if level is None:
@@ -136,7 +161,8 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
     if capped:
         args.append(ctypes.byref(pool_rows))
     by = "playlist" if members.dtype == np.int64 else "mean"
-    if labels is not None or prior_weight is not None:
+    a = make_scales(scales) if scales is not None else None
+    if labels is not None or prior_weight is not None or a is not None:
         q = capi.PlaylistQuery()
         q.size = ctypes.sizeof(capi.PlaylistQuery)
         q.flags = (capi.PQ_DIVERSE if diverse else 0) | (capi.PQ_CAPPED if capped else 0)
@@ -157,7 +183,10 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
             q.max_per_group = int(max_per_group)
         res = capi.PlaylistResult(ptr(idx), ptr(score), ptr(mmr) if diverse else None, ctypes.pointer(count),
                                   ctypes.pointer(pool_rows))
-        check(getattr(lib, f"{prefix}query_playlist_request")(h, ctypes.byref(q), ctypes.byref(res)))
+        if a is not None:
+            check(getattr(lib, f"{prefix}query_playlist_request_scaled")(h, ctypes.byref(q), ptr(a), ctypes.byref(res)))
+        else:
+            check(getattr(lib, f"{prefix}query_playlist_request")(h, ctypes.byref(q), ctypes.byref(res)))
     else:
         check(getattr(lib, f"{prefix}query_{by}_topn{level}")(*args))
     out = (idx[:count.value].copy(), score[:count.value].copy())
@@ -168,11 +197,11 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
     return out
 
 
-def _distance_request(lib, prefix: str, h, check, members, topn: int, exclude=None, where=None, labels=None):
+def _distance_request(lib, prefix: str, h, check, members, topn: int, exclude=None, where=None, labels=None, scales=None):
     """One DISTANCE REQUEST (`prefix`query_distance_request): the `topn` rows nearest to the members by Euclidean distance.
     `members` is a (k, 12) float32 array (by value) or a 1-D int64 array of rows (never returned).  `exclude`, `where` and
     `labels` are the playlist request's.  Returns (ids, distances): nearest first, ties by row; for k > 1 a distance is the
-    root-mean-square distance to the members."""
+    root-mean-square distance to the members.  `scales` (make_scales): FEATURE SCALES, through `prefix`query_distance_request_scaled."""
     flt = make_filter(where) if where is not None else None
     ex = np.ascontiguousarray(np.asarray([] if exclude is None else list(exclude), dtype=np.int64).reshape(-1))
     n_out = max(int(topn), 1)
@@ -193,7 +222,11 @@ def _distance_request(lib, prefix: str, h, check, members, topn: int, exclude=No
         q.labels, q.n_labels = ptr(lab), int(lab.size)   # (an empty set stays a non-NULL pointer: the library refuses it)
     q.k, q.topn = int(members.shape[0]), int(topn)
     res = capi.DistanceResult(ptr(idx), ptr(dist), ctypes.pointer(count))
-    check(getattr(lib, f"{prefix}query_distance_request")(h, ctypes.byref(q), ctypes.byref(res)))
+    if scales is not None:
+        a = make_scales(scales)
+        check(getattr(lib, f"{prefix}query_distance_request_scaled")(h, ctypes.byref(q), ptr(a), ctypes.byref(res)))
+    else:
+        check(getattr(lib, f"{prefix}query_distance_request")(h, ctypes.byref(q), ctypes.byref(res)))
     return idx[:count.value].copy(), dist[:count.value].copy()
 
 
@@ -559,17 +592,21 @@ class CosineEngine:
 
 
     # ---- PLAYLISTS (include/mi355rec_diag.h): top-N by the mean score against up to 32 songs ----
-    def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None) -> Tuple[np.ndarray, np.ndarray]:
+    def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None,
+                        scales=None) -> Tuple[np.ndarray, np.ndarray]:
         """The best `topn` rows by the mean of their scores against the rows of `queries` (k x 12); `exclude`: global ids.
         `where`: {feature index or name: (lo, hi)}, only rows within every range are returned (FEATURE FILTERS; a
         filtered single query is k = 1); None calls the unfiltered entry point.
         `weights`: one signed float per member (WEIGHTED PLAYLISTS: score = sum w_k c_k / sum |w_k|, a negative weight is
-        a dislike); None calls the entry point used without it."""
-        return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight)
+        a dislike); None calls the entry point used without it.
+        `scales`: FEATURE SCALES, 12 floats or {feature index or name: scale} (unnamed features 1.0): rows and members are
+        multiplied feature by feature before the scores are taken (0 ignores a feature); not with prior_weight."""
+        return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales)
 
-    def query_playlist_topn(self, local_rows, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None) -> Tuple[np.ndarray, np.ndarray]:
+    def query_playlist_topn(self, local_rows, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None,
+                            scales=None) -> Tuple[np.ndarray, np.ndarray]:
         """The same for members given as rows of this handle; the members are never returned (whatever their weight)."""
-        return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight)
+        return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales)
 
     def _playlist(self, members, topn, exclude, where, weights, level=None, labels=None, **more):
         return _playlist_family(self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), members, topn, exclude, where,
@@ -587,6 +624,17 @@ class CosineEngine:
         """The same for members given as rows of this handle; the members are never returned."""
         return _distance_request(self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), _np_rows(rows), topn,
                                  exclude, where, labels)
+
+    def query_nearest_scaled(self, members, topn: int, scales, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
+        """query_nearest with FEATURE SCALES (`scales` as in query_mean_topn): the distances are taken between the scaled
+        members and the scaled rows; the filter still tests the stored rows."""
+        return _distance_request(self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), _np_members(members), topn,
+                                 exclude, where, labels, scales)
+
+    def query_nearest_rows_scaled(self, rows, topn: int, scales, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
+        """query_nearest_rows with FEATURE SCALES."""
+        return _distance_request(self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), _np_rows(rows), topn,
+                                 exclude, where, labels, scales)
 
     # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h): MMR picks from the top-`pool` of the weighted playlist call ----
     def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False, labels=None, prior_weight=None):
@@ -759,11 +807,13 @@ class NodeEngine:
                              (q.ctypes.data_as(ctypes.c_void_p), int(exclude_global)), labels, topn)
 
     # ---- PLAYLISTS (include/mi355rec_diag.h) over the whole node ----
-    def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None) -> Tuple[np.ndarray, np.ndarray]:
-        return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight)
+    def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None,
+                        scales=None) -> Tuple[np.ndarray, np.ndarray]:
+        return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales)
 
-    def query_playlist_topn(self, global_rows, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None) -> Tuple[np.ndarray, np.ndarray]:
-        return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight)
+    def query_playlist_topn(self, global_rows, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None,
+                            scales=None) -> Tuple[np.ndarray, np.ndarray]:
+        return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales)
 
     def _playlist(self, members, topn, exclude, where, weights, level=None, labels=None, **more):
         return _playlist_family(self._lib, "mi355rec_sharded_", self._h, self._check, members, topn, exclude, where, weights, level,
@@ -777,6 +827,15 @@ class NodeEngine:
     def query_nearest_rows(self, rows, topn: int, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
         """The same for members given as global rows (never returned)."""
         return _distance_request(self._lib, "mi355rec_sharded_", self._h, self._check, _np_rows(rows), topn, exclude, where, labels)
+
+    def query_nearest_scaled(self, members, topn: int, scales, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
+        """query_nearest with FEATURE SCALES (12 floats or {feature index or name: scale})."""
+        return _distance_request(self._lib, "mi355rec_sharded_", self._h, self._check, _np_members(members), topn, exclude, where, labels,
+                                 scales)
+
+    def query_nearest_rows_scaled(self, rows, topn: int, scales, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
+        """query_nearest_rows with FEATURE SCALES."""
+        return _distance_request(self._lib, "mi355rec_sharded_", self._h, self._check, _np_rows(rows), topn, exclude, where, labels, scales)
 
     # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h) over the whole node ----
     def set_groups(self, groups) -> None:
