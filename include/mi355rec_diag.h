@@ -411,7 +411,7 @@ int mi355rec_sharded_query_topn_labels(mi355rec_sharded_t* h, const float* query
  * rows of the handle; global rows of a node handle), an excluded id < 0 (on a node handle: outside the catalogue),
  * n_exclude outside [0, 1024] and a NULL list with n_exclude > 0.  On a single handle an excluded id of another shard's
  * rows matches nothing.
- * Synchronous, like the label calls: one launch (csrc/playlist.hip.h: a pre-filter over the 8-bit replica with a derived
+ * Synchronous, like the label calls: one launch (csrc/playlist.hip.h; csrc/playlist_cut.hip.h: a pre-filter over the 8-bit replica with a derived
  * error bound, K exact chains per surviving row) and the merge.  No set-up: lanes and node handles answer at once.
  * mi355rec_playlist_counters: playlist queries since create, and the rows whose K exact chains were computed (the
  * pre-filter's survivors, the rows of each workgroup's starting bound, every row where the pre-filter is off).  Either
@@ -480,7 +480,7 @@ int mi355rec_sharded_query_playlist_topn_where(mi355rec_sharded_t* h, const int6
  * weights == NULL is exactly the _where call with the same other arguments (same results, same launch).
  * INVALID_ARG (with a message): the playlist and filter cases, and a weight that is NaN or infinite, |w_k| > 1e6, or
  * W < 1e-6 (all weights zero included).  mi355rec_playlist_counters counts weighted calls too.
- * Device: the same playlist_scan_kernel launch (csrc/playlist.hip.h); the 8-bit pre-filter works on the weighted mean
+ * Device: the same playlist_scan_kernel launch (csrc/playlist.hip.h); the 8-bit pre-filter (csrc/playlist_cut.hip.h, "PLAIN") works on the weighted mean
  * direction u = (sum_k w_k q_k / |q_k|) / W and switches itself off when |u| < 1e-3 (likes and dislikes that cancel): every
  * row then takes the k exact chains.  Dislikes shrink |u| and let fewer rows be ruled out.  Node handles
  * as for the playlist calls; the CPU backend serves the same calls with the same arithmetic. */
@@ -672,7 +672,7 @@ int mi355rec_sharded_query_playlist_request(mi355rec_sharded_t* h, const mi355re
  * set), counts and padding are unchanged.
  * Identities, bit for bit: the flag with beta = 0.0f is the call without the flag (same launch, same ids and score bits); all
  * priors +0.0f is no prior; the result does not depend on shard count, placement, lane or replica mode.
- * Device: a uniform runtime branch of playlist_scan_kernel (csrc/playlist.hip.h, "ROW PRIORS"): the priors stream with the
+ * Device: a uniform runtime branch of playlist_scan_kernel (csrc/playlist.hip.h, "ROW PRIORS"; its cut: csrc/playlist_cut.hip.h, "PRIOR"): the priors stream with the
  * 8-bit replica (+4 B on its 12 B per row) and enter the pre-filter's integer cut PER ROW; the exact chains add the prior with
  * the two operations above.  Calls without a prior take none of the new branches and never read the array.
  * Node handle: one shard forwards; a replicated placement gives every replica the whole array (a failure drops the priors on
@@ -706,7 +706,7 @@ int mi355rec_sharded_set_priors(mi355rec_sharded_t* h, const float* priors_host,
  * is one.  count = min(topn, |admissible rows|), the rest padded with -1 / 0.0f.
  * INVALID_ARG (with a message): flags != 0; both or neither of members and rows; a bad size; everything the playlist request
  * refuses for the fields the two share (same limits, same messages).
- * Device: a uniform runtime branch of playlist_scan_kernel (csrc/playlist.hip.h, "DISTANCE"): no new kernel.  With the 8-bit
+ * Device: a uniform runtime branch of playlist_scan_kernel (csrc/playlist.hip.h, "DISTANCE"; its cut: csrc/playlist_cut.hip.h, "DISTANCE"): no new kernel.  With the 8-bit
  * replica the scan streams 12 + 4 B per row: the replica's dot product with the members' centroid and the row's norm (a
  * 4 B/row array the handle's first distance request builds, q8_build_kernel's second output) bound m(x) from below, a per-row
  * integer cut rules rows out and only the survivors take the k chains on the fp32 rows.  The results are the same with the
@@ -761,7 +761,7 @@ int mi355rec_sharded_query_distance_request(mi355rec_sharded_t* h, const mi355re
  *   - every scale times one power of two: the same cosine ids and score bits, distances times exactly that factor, as long as
  *     nothing overflows, underflows or crosses the chain's den > 1e-8 rule;
  *   - the result does not depend on shard count, placement, lane or replica mode.
- * Device: a uniform runtime branch of playlist_scan_kernel (csrc/playlist.hip.h, "FEATURE SCALES"): no new kernel; calls without
+ * Device: a uniform runtime branch of playlist_scan_kernel (csrc/playlist.hip.h, "FEATURE SCALES"; its cut: csrc/playlist_cut.hip.h, "SCALED"): no new kernel; calls without
  * scales take none of its branches.  A loaded row is scaled once (12 multiplies), then the unscaled chains run.  With the 8-bit
  * replica a scaled COSINE request keeps a pre-filter: the replica's dot product bounds the numerator and the row's own bytes
  * bound |Abar x^| (Abar = the scales over their maximum), a per-row integer cut rules rows out.  It is on for a_max in

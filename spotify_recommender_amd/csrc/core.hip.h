@@ -77,6 +77,13 @@ struct Row {
     float4 a, b, c;
 };
 
+// The row's twelve features in order (registers: every index below is a compile-time constant after unrolling).
+__device__ __forceinline__ void row_features(const Row& r, float (&f)[kDim]) {
+    f[0] = r.a.x, f[1] = r.a.y, f[2] = r.a.z, f[3] = r.a.w;
+    f[4] = r.b.x, f[5] = r.b.y, f[6] = r.b.z, f[7] = r.b.w;
+    f[8] = r.c.x, f[9] = r.c.y, f[10] = r.c.z, f[11] = r.c.w;
+}
+
 __device__ __forceinline__ float query_norm(const float (&q)[kDim]) {
     float qn = 0.0f;  // Recommender.cu:259-261
 #pragma unroll
@@ -86,8 +93,8 @@ __device__ __forceinline__ float query_norm(const float (&q)[kDim]) {
 
 __device__ __forceinline__ float cosine_score(const float (&q)[kDim], float qn,
                                               const Row& r) {
-    const float f[kDim] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y,
-                           r.b.z, r.b.w, r.c.x, r.c.y, r.c.z, r.c.w};
+    float f[kDim];
+    row_features(r, f);
     float dot = 0.0f;  // Recommender.cu:264-269
     float nrm = 0.0f;
 #pragma unroll
@@ -128,8 +135,8 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float approx_cosine(const float (&q)[kDim], float inv_qn, const Row& r) {
-    const float f[kDim] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y,
-                           r.b.z, r.b.w, r.c.x, r.c.y, r.c.z, r.c.w};
+    float f[kDim];
+    row_features(r, f);
     v2f d = {0.0f, 0.0f};
     v2f m = {0.0f, 0.0f};
 #pragma unroll

@@ -83,7 +83,8 @@ __global__ __launch_bounds__(kMmrBlockMax) void mmr_rerank_kernel(
     if (tid == 0) sm.first_empty = pool < static_cast<int>(blockDim.x) ? pool : static_cast<int>(blockDim.x);
     __syncthreads();
     if (!have && tid < pool) atomicMin(&sm.first_empty, tid);
-    const float f[kDim] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.c.x, r.c.y, r.c.z, r.c.w};
+    float f[kDim];
+    row_features(r, f);
 #pragma unroll
     for (int j = 0; j < kDim; ++j) sm.feat[j][tid] = f[j];
     sm.qn[tid] = query_norm(f);

@@ -1,4 +1,4 @@
-"""The pre-filter of the DISTANCE REQUESTS (csrc/playlist.hip.h, "DISTANCE"), checked on the CPU with a numpy model of exactly
+"""The pre-filter of the DISTANCE REQUESTS (csrc/playlist_cut.hip.h, "DISTANCE"), checked on the CPU with a numpy model of exactly
 the kernel's arithmetic against tests/distance_oracle.py:
 
     c_j  = fl( fl(q_0j + ... + q_{K-1}j) / K ),  |c| = sqrtf(seq sum c_j^2)            (fp32, member order)
@@ -15,74 +15,9 @@ neighbours.  No row with m(x) <= T may ever be ruled out; and the bound is not v
 import numpy as np
 
 from tests.distance_oracle import mean_sqdist
+from tests.playlist_cut_model import DistanceCut as Model, stored_norms
 from tests.playlist_sweep_cases import catalogue_of_kind
-from tests.test_q8_margin import DOT_SCALE, S, q8_codes
-
-ULP = np.float32(2.0 ** -24)
-CLAMP = np.float32(2.0 ** 30)
-MIN_NORM, MAX_NORM = np.float32(1.005e-4), np.float32(1e18)
-
-
-def seq_sqnorm(v):
-    """Sequential fp32 sum of squares over the last axis (multiply, round, add, round)."""
-    v = np.asarray(v, np.float32)
-    acc = np.zeros(v.shape[:-1], np.float32)
-    with np.errstate(all="ignore"):
-        for j in range(v.shape[-1]):
-            acc = (acc + (v[..., j] * v[..., j]).astype(np.float32)).astype(np.float32)
-    return acc
-
-
-def stored_norms(feats):
-    """q8_build_kernel's second output."""
-    with np.errstate(all="ignore"):
-        return np.sqrt(seq_sqnorm(feats)).astype(np.float32)
-
-
-class Model:
-    """The launch's constants, or ok == False where the kernel switches the pre-filter off for the launch."""
-
-    def __init__(self, codes, members):
-        q = np.ascontiguousarray(members, np.float32).reshape(-1, 12)
-        k = q.shape[0]
-        with np.errstate(all="ignore"):
-            q2k = seq_sqnorm(q)
-            qn = np.sqrt(q2k).astype(np.float32)
-            c = q[0].copy()
-            for m in range(1, k):
-                c = (c + q[m]).astype(np.float32)
-            c = (c / np.float32(k)).astype(np.float32)
-            cn = np.float32(np.sqrt(seq_sqnorm(c)))
-            self.ok = bool(np.all((qn >= MIN_NORM) & (qn <= MAX_NORM)) and MIN_NORM <= cn <= MAX_NORM)
-            if not self.ok:
-                return
-            chat = (c * (np.float32(1) / cn)).astype(np.float32)                         # q8_query: q[j] * inv * S
-            Q = np.clip(np.rint((chat * np.float32(S)).astype(np.float32)), -S, S).astype(np.int64)
-            self.D = codes @ Q
-            margin = np.float32(np.float32(np.abs(Q).sum()) * np.float32(np.float32(1.0 / 254.0) / np.float32(S)) * np.float32(1 + 1e-5)
-                                + np.float32(3.4642 * 0.5 / S) + np.float32(3e-5))
-            q2 = q2k[0]
-            for m in range(1, k):
-                q2 = np.float32(q2 + q2k[m])
-            eps = np.float32(np.float32(4 * k + 128) * ULP)
-            self.q2e = np.float32(np.float32(q2 / np.float32(k)) * np.float32(np.float32(1) - eps))
-            self.s2c = np.float32(DOT_SCALE / np.float32(np.float32(2) * cn))
-            self.c0 = np.float32(DOT_SCALE * np.float32(margin + eps))
-            self.a1 = np.float32(self.s2c * np.float32(np.float32(1) - eps))
-            self.ok = bool(np.isfinite(np.float32(self.q2e * self.s2c)))
-            self.cn, self.margin = cn, margin
-
-    def ruled_out(self, valid, s, T, rcp_ulps=0):
-        with np.errstate(all="ignore"):
-            b = np.float32(np.float32(self.q2e - np.float32(T)) * self.s2c)
-            r = (np.float32(1) / s).astype(np.float32)
-            for _ in range(abs(rcp_ulps)):
-                r = np.nextafter(r, np.float32(np.inf if rcp_ulps > 0 else -np.inf))
-            c = (((self.a1 * s).astype(np.float32) + (b * r).astype(np.float32)).astype(np.float32) - self.c0).astype(np.float32)
-            c = np.where(np.isnan(c), -CLAMP, np.clip(c, -CLAMP, CLAMP))                  # (fmaxf / fminf drop a NaN)
-            cut = np.trunc(c).astype(np.int64) - 1
-            claimed = (s >= MIN_NORM) & (s <= MAX_NORM)
-            return valid & claimed & (self.D < cut)
+from tests.test_q8_margin import q8_codes
 
 
 def catalogues(n):

@@ -1,4 +1,4 @@
-"""The error bound of the playlist pre-filter (csrc/playlist.hip.h), checked on the CPU with a numpy model of exactly that
+"""The error bound of the playlist pre-filter (csrc/playlist_cut.hip.h, "PLAIN"), checked on the CPU with a numpy model of exactly that
 arithmetic against the oracle's exact mean scores:
 
     |q_k| = the chain's fp32 norm,  u_j = fl(sum_k fl(q_kj / |q_k|)) / K   (fp32, member order),  |u| in fp32
@@ -11,47 +11,10 @@ vacuous, and that the integer cutoff the kernel derives from a threshold T never
 import numpy as np
 
 from oracle import oracle
+from tests.playlist_cut_model import unweighted_model as model
 from tests.playlist_oracle import mean_scores
 from tests.test_batched_margin import catalogues
-from tests.test_q8_margin import DOT_SCALE, q8_codes, q8_digits, q8_threshold
-
-ULP = np.float32(2.0 ** -24)
-
-
-def fp32_norm(v):
-    s = np.float32(0)
-    for x in np.asarray(v, np.float32):
-        s = np.float32(s + np.float32(x * x))
-    return np.float32(np.sqrt(s))
-
-
-def mean_direction(members):
-    """(u, |u|, ok) as the kernel computes them; ok: the bound may be claimed for this playlist."""
-    members = np.asarray(members, np.float32)
-    qn = [fp32_norm(q) for q in members]
-    ok = all(np.float32(1.005e-4) <= n <= np.float32(1e18) for n in qn)
-    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        u = (members[0] / qn[0]).astype(np.float32)
-        for q, n in zip(members[1:], qn[1:]):
-            u = (u + (q / n).astype(np.float32)).astype(np.float32)
-        u = (u / np.float32(len(members))).astype(np.float32)
-    un = fp32_norm(u)
-    return u, un, bool(ok and np.isfinite(un) and un >= np.float32(1e-3))
-
-
-def model(rows, members):
-    """(D, valid, |u|, margin_mean) or None where the kernel turns the pre-filter off."""
-    u, un, ok = mean_direction(members)
-    if not ok:
-        return None
-    k, valid = q8_codes(rows)
-    Q, h, l, qok = q8_digits(u)
-    if not qok:
-        return None
-    D = k @ Q
-    M = np.float32(np.abs(Q).sum()) * np.float32(1 / 254.0 / 32000) * np.float32(1 + 1e-5) + np.float32(3.4642 * 0.5 / 32000) + np.float32(3e-5)
-    mm = np.float32(un * M + np.float32(4e-6) + np.float32(2 * len(members) + 32) * ULP)
-    return D, valid, un, float(mm)
+from tests.test_q8_margin import DOT_SCALE, q8_threshold
 
 
 def playlists(rng, f):

@@ -1,7 +1,7 @@
-"""The per-row cut of the playlist pre-filter with ROW PRIORS (csrc/playlist.hip.h, "ROW PRIORS"), checked on the CPU with a
+"""The per-row cut of the playlist pre-filter with ROW PRIORS (csrc/playlist_cut.hip.h, "PRIOR"), checked on the CPU with a
 numpy model of exactly the kernel's arithmetic against the oracle's exact ranking values:
 
-    margin_prior = margin_mean + 96 * 2^-24                                   (margin_mean: tests/test_weighted_margin.model)
+    margin_prior = margin_mean + 96 * 2^-24                                   (margin_mean: tests/playlist_cut_model.model)
     base   = fl( fl( fl(T - margin_prior) / |u| ) * 127 S )                   (fp32; S = 32000)
     bs     = fl( fl(beta * 127 S) / |u| )
     cut(x) = int( clamp( fl(base - fl(p(x) bs)), -2^30, 2^30 ) ) - 1          (the conversion truncates towards zero)
@@ -13,26 +13,10 @@ uniform rows at most 5 % of the rows survive (the real-number model of the desig
 max(beta p) would let 2 - 95 % through)."""
 import numpy as np
 
+from tests.playlist_cut_model import model, ruled_out
 from tests.prior_oracle import blended, prior_kinds
-from tests.test_playlist_margin import ULP
-from tests.test_q8_margin import DOT_SCALE, q8_codes
-from tests.test_weighted_margin import model
+from tests.test_q8_margin import q8_codes
 from tests.weighted_oracle import weighted_scores
-
-PRIOR_ULPS = np.float32(96.0)
-CLAMP = np.float32(2.0 ** 30)
-
-
-def ruled_out(D, valid, un, margin_mean, T, beta, priors):
-    """The rows the kernel's per-row cut rules out at threshold T (float32 arithmetic, operation for operation)."""
-    un = np.float32(un)
-    mp = np.float32(np.float32(margin_mean) + PRIOR_ULPS * ULP)
-    with np.errstate(over="ignore"):
-        base = np.float32(np.float32(np.float32(np.float32(T) - mp) / un) * DOT_SCALE)
-        bs = np.float32(np.float32(np.float32(beta) * DOT_SCALE) / un)
-        c = (base - (np.asarray(priors, np.float32) * bs).astype(np.float32)).astype(np.float32)
-    cut = np.trunc(np.clip(c, -CLAMP, CLAMP)).astype(np.int64) - 1
-    return valid & (D < cut)
 
 
 def hostile_priors(rng, n):

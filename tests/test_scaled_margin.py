@@ -1,4 +1,4 @@
-"""The pre-filter of the scaled cosine requests (csrc/playlist.hip.h, "FEATURE SCALES"), checked on the CPU with a numpy model of
+"""The pre-filter of the scaled cosine requests (csrc/playlist_cut.hip.h, "SCALED"), checked on the CPU with a numpy model of
 exactly the kernel's fp32 arithmetic against tests/scaled_oracle.py:
 
     q'_kj = fl(a_j q_kj),  |q'_k| = sqrtf(seq sum),  u_j = fl( fl(sum_k fl(w_k fl(q'_kj / |q'_k|))) / W )      (member order)
@@ -17,86 +17,13 @@ No row whose oracle score reaches T may ever be ruled out; and the bound is not 
 import numpy as np
 import pytest
 
+from tests.playlist_cut_model import F32, ScaledCut as Model
 from tests.scaled_oracle import DROP3, EDGE, GENERAL, ONE, ONES, cosine_scores
-from tests.test_distance_margin import seq_sqnorm
-from tests.test_q8_margin import DOT_SCALE, S, q8_codes
-from tests.weighted_oracle import weight_kinds, weight_sum
+from tests.test_q8_margin import q8_codes
+from tests.weighted_oracle import weight_kinds
 
-F32 = np.float32
-ULP = F32(2.0 ** -24)
-CLAMP = F32(2.0 ** 30)
-MIN_NORM, MAX_NORM = F32(1.005e-4), F32(1e18)
-A_MIN, A_MAX = F32(2.0 ** -10), F32(8.0)
-FLOOR = F32(2.0 ** -6)
-STEP = F32(F32(1.001) / F32(254.0))
 THREE = np.zeros(12, F32)
 THREE[[0, 1, 9]] = 1                                          # three features kept: danceability, energy, valence
-
-
-def norm(v):
-    with np.errstate(all="ignore"):
-        return np.sqrt(seq_sqnorm(v)).astype(F32)
-
-
-class Model:
-    """The launch's constants, or ok == False where the kernel switches the pre-filter off for the launch."""
-
-    def __init__(self, codes, members, weights, a):
-        a = np.asarray(a, F32)
-        q = (np.ascontiguousarray(members, F32).reshape(-1, 12) * a).astype(F32)
-        k = q.shape[0]
-        w = np.ones(k, F32) if weights is None else np.asarray(weights, F32)
-        wsum = F32(k) if weights is None else weight_sum(w)
-        self.ok = False
-        with np.errstate(all="ignore"):
-            qn = norm(q)
-            if not np.all((qn >= MIN_NORM) & (qn <= MAX_NORM)):
-                return
-            u = (w[0] * (q[0] / qn[0]).astype(F32)).astype(F32)
-            for m in range(1, k):
-                u = (u + (w[m] * (q[m] / qn[m]).astype(F32)).astype(F32)).astype(F32)
-            u = (u / wsum).astype(F32)
-            a_max = a.max()
-            self.ab = (a / a_max).astype(F32)
-            uq = (self.ab * u).astype(F32)
-            bn = F32(norm(uq))
-            self.e = F32(F32(norm(self.ab) * STEP) + F32(8.0) * ULP)
-            den_floor = F32(F32(2e-4) / F32(a_max * qn.min()))
-            l_floor = max(FLOOR, den_floor)
-            self.gk_min = F32(F32(l_floor + self.e) * F32(F32(1) + F32(64) * ULP))
-            if not (den_floor <= F32(0.5) and A_MIN <= a_max <= A_MAX):
-                return
-            if not (MIN_NORM <= bn <= MAX_NORM and bn >= F32(1e-3)):
-                return
-            inv = F32(F32(1) / bn)
-            Q = np.clip(np.rint(((uq * inv).astype(F32) * F32(S)).astype(F32)), -S, S).astype(np.int64)
-            self.D = codes @ Q
-            self.margin = F32(F32(np.abs(Q).sum()) * F32(F32(1.0 / 254.0) / F32(S)) * F32(1 + 1e-5) + F32(3.4642 * 0.5 / S) + F32(3e-5))
-            self.margin_scaled = F32(F32(4e-6) + F32(F32(3 * k) + F32(64)) * ULP)
-            self.c0 = F32(DOT_SCALE * F32(self.margin + F32(16) * ULP))
-            self.bn = bn
-            acc = np.zeros(codes.shape[0], F32)
-            for j in range(12):
-                p = (self.ab[j] * codes[:, j].astype(F32)).astype(F32)
-                acc = (acc + (p * p).astype(F32)).astype(F32)
-            self.root = np.sqrt(acc).astype(F32)
-            self.ok = True
-
-    def ruled_out(self, valid, T, sqrt_ulps=0):
-        with np.errstate(all="ignore"):
-            root = self.root
-            for _ in range(abs(sqrt_ulps)):
-                root = np.nextafter(root, F32(np.inf if sqrt_ulps > 0 else -np.inf))
-            gk = (root * F32(F32(1) / F32(127))).astype(F32)
-            tm = F32(F32(T) - self.margin_scaled)
-            base = F32(F32(tm / self.bn) * DOT_SCALE)
-            fmul = F32(F32(1) - F32(16) * ULP) if tm >= 0 else F32(F32(1) + F32(16) * ULP)
-            fadd = -self.e if tm >= 0 else self.e
-            f = ((gk * fmul).astype(F32) + fadd).astype(F32)
-            c = ((base * f).astype(F32) - self.c0).astype(F32)
-            c = np.where(np.isnan(c), -CLAMP, np.clip(c, -CLAMP, CLAMP))
-            cut = np.trunc(c).astype(np.int64) - 1
-            return valid & (gk >= self.gk_min) & (self.D < cut)
 
 
 def scale_sets():

@@ -1,4 +1,4 @@
-"""The error bound of the WEIGHTED playlist pre-filter (csrc/playlist.hip.h), checked on the CPU with a numpy model of
+"""The error bound of the WEIGHTED playlist pre-filter (csrc/playlist_cut.hip.h, "PLAIN"), checked on the CPU with a numpy model of
 exactly that arithmetic against the weighted oracle's exact scores:
 
     |q_k| = the chain's fp32 norm,  W = fl(sum_k |w_k|),  u_j = fl(sum_k fl(w_k fl(q_kj / |q_k|))) / W   (fp32, member order)
@@ -12,42 +12,12 @@ cannot pass by claiming nothing.  It also checks that the bound is not vacuous a
 threshold T (of either sign) never rules out a row whose score is >= T."""
 import numpy as np
 
+from tests.playlist_cut_model import model, weighted_direction
 from tests.test_batched_margin import catalogues
-from tests.test_playlist_margin import ULP, fp32_norm
-from tests.test_q8_margin import DOT_SCALE, q8_codes, q8_digits, q8_threshold
+from tests.test_q8_margin import DOT_SCALE, q8_codes, q8_threshold
 from tests.weighted_oracle import weight_kinds, weight_sum, weighted_scores
 
 KS = (1, 2, 5, 10, 32)
-
-
-def weighted_direction(members, weights):
-    """(u, |u|, ok) as the kernel computes them; ok: the bound may be claimed for this playlist."""
-    members = np.asarray(members, np.float32)
-    w = np.asarray(weights, np.float32)
-    W = weight_sum(w)
-    qn = [fp32_norm(q) for q in members]
-    ok = all(np.float32(1.005e-4) <= n <= np.float32(1e18) for n in qn)
-    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        u = (w[0] * (members[0] / qn[0]).astype(np.float32)).astype(np.float32)
-        for q, n, wk in zip(members[1:], qn[1:], w[1:]):
-            u = (u + (wk * (q / n).astype(np.float32)).astype(np.float32)).astype(np.float32)
-        u = (u / W).astype(np.float32)
-    un = fp32_norm(u)
-    return u, un, bool(ok and np.isfinite(un) and un >= np.float32(1e-3))
-
-
-def model(codes, valid, members, weights):
-    """(D, |u|, margin_mean), or None where the kernel turns the pre-filter off."""
-    u, un, ok = weighted_direction(members, weights)
-    if not ok:
-        return None
-    Q, h, l, qok = q8_digits(u)
-    if not qok:
-        return None
-    D = codes @ Q
-    M = np.float32(np.abs(Q).sum()) * np.float32(1 / 254.0 / 32000) * np.float32(1 + 1e-5) + np.float32(3.4642 * 0.5 / 32000) + np.float32(3e-5)
-    mm = np.float32(un * M + np.float32(4e-6) + np.float32(3 * len(members) + 32) * ULP)
-    return D, un, float(mm)
 
 
 def test_weighted_prefilter_error_stays_inside_the_margin_and_the_cutoff_is_safe():
@@ -97,7 +67,7 @@ def test_weighted_prefilter_error_stays_inside_the_margin_and_the_cutoff_is_safe
 def test_all_ones_is_the_unweighted_model_and_scores():
     """Identity 1 in the model: weights of 1.0 give the unweighted kernel's u bit for bit and the plain mean's scores."""
     from tests.playlist_oracle import mean_scores
-    from tests.test_playlist_margin import mean_direction
+    from tests.playlist_cut_model import mean_direction
     rng = np.random.default_rng(6)
     for name, f in catalogues(rng, 5_000):
         f = np.ascontiguousarray(f, dtype=np.float32)

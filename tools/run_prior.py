@@ -12,8 +12,6 @@ Prints one JSON document and writes it to --out.
 the path this change must not slow down.)"""
 import argparse
 import json
-import os
-import subprocess
 import sys
 import time
 from pathlib import Path
@@ -59,38 +57,10 @@ def catalogues(n, rng, only_uniform=False):
     yield "genre_contiguous", np.ascontiguousarray(np.clip(f, 0.0, 1.0), dtype=np.float32)
 
 
-def no_prior_only(a):
-    """One child of --ab: the request without a prior, K = 1 and 10, with whichever library MI355REC_LIB names."""
-    from spotify_recommender_amd import CosineEngine
-    n, topn = a.rows, a.topn
-    rng = np.random.default_rng(7)
-    feats = next(catalogues(n, rng, True))[1]
-    res = {}
-    with CosineEngine(feats) as eng:
-        for k in (1, 10):
-            lists = [rng.choice(n, size=k, replace=False) for _ in range(a.calls)]
-            res[f"k{k}"] = timed(lambda rows: eng.query_playlist_topn(rows, topn), lists)["p50_us"]
-    print("AB " + json.dumps(res))
-
-
 def ab(a):
-    env_b = dict(os.environ)
-    env_a = dict(os.environ, MI355REC_LIB=str(Path(a.ab).resolve()), MI355REC_CAPI_LENIENT="1")
-    cmd = [sys.executable, __file__, "--no-prior-only", "--rows", str(a.rows), "--calls", str(a.calls), "--topn", str(a.topn)]
-    runs = {"this": [], "parent": []}
-    for _ in range(a.rounds):
-        for name, env in (("this", env_b), ("parent", env_a)):
-            p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
-            if p.returncode != 0:
-                raise SystemExit(f"A/B child ({name}) failed with {p.returncode}:\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
-            runs[name].append(json.loads([l for l in p.stdout.splitlines() if l.startswith("AB ")][-1][3:]))
-    out = {"rows": a.rows, "topn": a.topn, "rounds": a.rounds, "order": "this, parent, this, parent, ...", "runs": runs}
-    for k in ("k1", "k10"):
-        mine, theirs = [r[k] for r in runs["this"]], [r[k] for r in runs["parent"]]
-        b, p = float(np.median(mine)), float(np.median(theirs))
-        out[f"{k}_p50_us"] = {"this": round(b, 1), "parent": round(p, 1), "ratio": round(b / p, 3),
-                              "parent_spread": round((max(theirs) - min(theirs)) / p, 3)}
-    return out
+    """The plain request, K = 1 and 10, on this tree and with the library a.ab in alternating child processes (tools/playlist_ab.py)."""
+    from tools.playlist_ab import PLAIN, run
+    return run(a.ab, a.rows, a.calls, a.topn, a.rounds, PLAIN)
 
 
 def main():
@@ -100,11 +70,8 @@ def main():
     ap.add_argument("--topn", type=int, default=100)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--ab", default="")
-    ap.add_argument("--no-prior-only", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    if a.no_prior_only:
-        return no_prior_only(a)
     if a.ab:
         out = ab(a)
     else:

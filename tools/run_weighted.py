@@ -13,8 +13,6 @@ Prints one JSON document and writes it to --out.
 (--profile: fewer calls, the uniform catalogue only, no A/B.)"""
 import argparse
 import json
-import os
-import subprocess
 import sys
 from pathlib import Path
 
@@ -34,38 +32,10 @@ def mean_norm(members, w):
     return float(np.linalg.norm(u))
 
 
-def unweighted_only(a):
-    """One child of --ab: the unweighted K = 1 / K = 10 playlist calls with whichever library MI355REC_LIB names."""
-    from spotify_recommender_amd import CosineEngine
-    n, topn = a.rows, a.topn
-    rng = np.random.default_rng(7)
-    data = catalogue(n)
-    res = {}
-    with CosineEngine(data) as eng:
-        for k in (1, 10):
-            lists = [rng.choice(n, size=k, replace=False) for _ in range(a.calls)]
-            res[f"k{k}"] = timed(lambda rows: eng.query_playlist_topn(rows, topn), lists)["p50_us"]
-    print("AB " + json.dumps(res))
-
-
 def ab(a):
-    env_b = dict(os.environ)
-    env_a = dict(os.environ, MI355REC_LIB=str(Path(a.ab).resolve()), MI355REC_CAPI_LENIENT="1")
-    cmd = [sys.executable, __file__, "--unweighted-only", "--rows", str(a.rows), "--calls", str(a.calls), "--topn", str(a.topn)]
-    runs = {"this": [], "parent": []}
-    for _ in range(a.rounds):
-        for name, env in (("this", env_b), ("parent", env_a)):
-            p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
-            if p.returncode != 0:
-                raise SystemExit(f"A/B child ({name}) failed with {p.returncode}:\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
-            runs[name].append(json.loads([l for l in p.stdout.splitlines() if l.startswith("AB ")][-1][3:]))
-    out = {"rounds": a.rounds, "order": "this, parent, this, parent, ...", "runs": runs}
-    for k in ("k1", "k10"):
-        b = float(np.median([r[k] for r in runs["this"]]))
-        p = float(np.median([r[k] for r in runs["parent"]]))
-        out[f"{k}_p50_us"] = {"this": round(b, 1), "parent": round(p, 1), "ratio": round(b / p, 3)}
-    out["within_3pct"] = all(out[f"{k}_p50_us"]["ratio"] <= 1.03 for k in ("k1", "k10"))
-    return out
+    """The plain request, K = 1 and 10, on this tree and with the library a.ab in alternating child processes (tools/playlist_ab.py)."""
+    from tools.playlist_ab import PLAIN, run
+    return run(a.ab, a.rows, a.calls, a.topn, a.rounds, PLAIN)
 
 
 def measure(eng, host, topn, lists, weights):
@@ -115,11 +85,8 @@ def main():
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--ab", default="")
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--unweighted-only", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    if a.unweighted_only:
-        return unweighted_only(a)
     import torch
     from spotify_recommender_amd import CosineEngine
     from spotify_recommender_amd.synth import clustered_catalogue
