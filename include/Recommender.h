@@ -177,6 +177,17 @@ public:
     std::vector<int> recommendScaled(const std::vector<int>& songIndices, int topN, const std::vector<float>& scales, bool euclidean,
                                      const std::vector<FeatureRange>& where = {}, const std::vector<int>& genreIds = {});
 
+    // Extension: row sets (include/mi355rec_diag.h, "ROW SETS").  setRowSet gives the songs a listener has already heard
+    // (only = false: they are never returned) or the candidates to rank within (only = true: only they are returned); any
+    // number of them, duplicates allowed, where alsoExclude holds at most 1024.  The set applies to every recommendForPlaylist,
+    // recommendNearest and recommendScaled call, and to the single-song forms that are one-song playlists (recommendByIndexWhere,
+    // recommendDiverse, recommendByIndexCapped), until clearRowSet() or the next setRowSet, beside everything those calls take; it
+    // costs one bit per song on the host and on every device.  recommend(), recommendByIndex() and recommendByName() (the
+    // reference's own single-query path) are unchanged.  An index outside the songs gives false and a message, and the set as
+    // it was.
+    bool setRowSet(const std::vector<int>& songIndices, bool only = false);
+    void clearRowSet();
+
     struct Impl;   // opaque: defined in Recommender.cpp
 
 private:

@@ -32,6 +32,8 @@
  *     list, feature filter and label set (mi355rec_query_distance_request and its node-handle twin);
  *   - FEATURE SCALES: 12 non-negative per-request factors that weigh or ignore features in the playlist and distance requests
  *     (mi355rec_query_playlist_request_scaled, mi355rec_query_distance_request_scaled and their node-handle twins);
+ *   - ROW SETS: one bit per row, to leave out a listening history or to rank within a candidate set, passed to the playlist and
+ *     distance requests in a self-sized struct of extras (mi355rec_rowset_*, mi355rec_query_*_request_ext and the node-handle twins);
  *   - test hooks, compiled in only with -DMI355REC_TEST_HOOKS (spotify_recommender_amd/build.py builds
  *     libmi355rec_testhooks.so for tests/; the product library does not export them).
  */
@@ -785,6 +787,70 @@ int mi355rec_sharded_query_playlist_request_scaled(mi355rec_sharded_t* h, const 
                                                    const float* feature_scales, const mi355rec_playlist_result_t* result);
 int mi355rec_sharded_query_distance_request_scaled(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
                                                    const float* feature_scales, const mi355rec_distance_result_t* result);
+
+/* ROW SETS: exclude a listening history, or rank only within a candidate set.  exclude_global holds at most MI355REC_MAX_EXCLUDE
+ * ids (they sit in LDS and are looked up after a row's chains have run); a history is 10^4 .. 10^5 tracks, and a candidate set (the
+ * tracks licensed in a market, the output of a collaborative-filtering stage) is per request and arbitrary, which labels are not.
+ * Both are ONE BIT PER ROW on the device: n / 8 bytes on the host and on every device copy (1.25 MB at 10 M rows).
+ * A set is made once from global ids, may grow (mi355rec_rowset_add), and is passed to a request in mi355rec_request_ext_t, a
+ * self-sized struct of per-request extras beside the frozen request structs: later extras extend it, not the entry points.
+ * CONTRACT, bit for bit.  A row is admissible iff it was admissible without the set (not excluded, not a member row, passes the
+ * filter, label in the label set, distance finite) AND (MI355REC_ROWSET_EXCLUDE: it is not in the set; MI355REC_ROWSET_ONLY: it is).
+ * Everything else is the request without the set: chains, weights, priors, scales, order, ties, -0.0 -> +0.0, count = min(topn,
+ * admissible rows), padding; the pool of a diversified or capped call is the top-`pool` of the admissible rows.  Members may lie
+ * inside or outside the set and are never returned.  A set goes with every flag of the playlist request; with feature_scales the
+ * playlist flags must be 0, as for the _scaled call.
+ * IDENTITIES (tests/test_rowset_cpu.py, tests/test_gpu_rowset.py):
+ *   - ext == NULL, or both of its pointers NULL: the plain request (same launch, same ids and bits); scales only: the _scaled call;
+ *   - EXCLUDE with |S| <= MI355REC_MAX_EXCLUDE: the request with S appended to exclude_global; EXCLUDE with an empty set (and ONLY
+ *     with every row): the plain request, launched as such;
+ *   - ONLY with an empty set, EXCLUDE with every row: count 0, nothing is launched;
+ *   - the result does not depend on replica mode, lane, shard count or placement.
+ * IDS: duplicates allowed, any order.  Single handle: 0 <= id < 2^32 as for exclude_global, ids outside [row_base, row_base + n)
+ * match nothing.  Node handle: 0 <= id < n.  A negative or too large id (named in the message), n_ids < 0, or a NULL list with
+ * n_ids > 0 is INVALID_ARG; n_ids == 0 makes an empty set.  A failed mi355rec_rowset_add leaves the set unchanged.  Errors of create
+ * are the handle's last error, those of add are mi355rec_last_global_error().
+ * OWNERSHIP: a set belongs to the handle it was made on and may be used on it and on its lanes (same rows, same device); a node
+ * handle's set on that node handle only; anything else is INVALID_ARG ("row set of another handle").  Sets are destroyed BEFORE
+ * their handle.  Requests only read a set, so requests on different lanes may share one at the same time; mi355rec_rowset_add or
+ * _destroy concurrent with a request that uses the set is the caller's error.
+ * mi355rec_rowset_count: the distinct rows of the handle in the set.  create and add copy to the device synchronously before they
+ * return; add uploads the whole bitmap of every copy again.
+ * Device (csrc/playlist.hip.h, "ROW SETS"): no new kernel and no second instantiation: a uniform branch of playlist_scan_kernel.
+ * Per tile a lane reads its quad's four bits and clears the rows the set rejects BEFORE the label test, the 8-bit dot products, the
+ * filter's fp32 loads and any chain, on the exact path too: a rejected row costs one bit and mi355rec_playlist_counters' rows_exact
+ * does not count it.  A request without a set reads nothing new.  A row-sharded node gives every shard its slice of the bitmap, a
+ * replicated one every replica the whole; the CPU backend tests the host bitmap.  The call always makes one pass over the catalogue.
+ * Measured on one MI355X at 10 M uniform rows, top-100, replica on, K = 1 by row (tools/run_rowset.py, profiles/r17_rowset.json; p50
+ * per call): the cosine request 92.2 us without a set, 100.4 us with a set that rejects nothing returnable, 100.5 us with 20 000
+ * random ids excluded, 101.2 us within a random half, 83.9 us within a random 1 %; K = 10: 134.6, 142.5, 142.5, 138.4, 118.8 us; the
+ * distance request, K = 1: 94.8, 98.2, 98.1, 96.7, 81.5 us.  Calls without a set are within the parent build's own spread
+ * (profiles/r17_rowset_ab.json).
+ * Not served: sets on the single-query, streamed, batched and label-only routes; two sets in one request; removing ids; set
+ * algebra; a gather path that scores only the listed rows of a tiny ONLY set. */
+typedef struct mi355rec_rowset mi355rec_rowset_t;
+int mi355rec_rowset_create(mi355rec_t* h, const int64_t* global_ids, int64_t n_ids, mi355rec_rowset_t** out);
+int mi355rec_sharded_rowset_create(mi355rec_sharded_t* h, const int64_t* global_ids, int64_t n_ids, mi355rec_rowset_t** out);
+int mi355rec_rowset_add(mi355rec_rowset_t* s, const int64_t* global_ids, int64_t n_ids);
+int64_t mi355rec_rowset_count(const mi355rec_rowset_t* s);
+void mi355rec_rowset_destroy(mi355rec_rowset_t* s);   /* NULL is fine */
+
+#define MI355REC_ROWSET_EXCLUDE 0u   /* rows IN the set are not admissible ("seen") */
+#define MI355REC_ROWSET_ONLY 1u      /* rows NOT in the set are not admissible ("candidates") */
+typedef struct {
+    uint32_t size;                     /* sizeof of the caller's header; the size rules of mi355rec_playlist_query_t */
+    uint32_t rowset_mode;              /* MI355REC_ROWSET_*; read only where rowset != NULL; other values INVALID_ARG */
+    const float* feature_scales;       /* NULL, or 12 scales: exactly the _scaled call's argument */
+    const mi355rec_rowset_t* rowset;   /* NULL, or the set */
+} mi355rec_request_ext_t;              /* 24 bytes */
+int mi355rec_query_playlist_request_ext(mi355rec_t* h, const mi355rec_playlist_query_t* query, const mi355rec_request_ext_t* ext,
+                                        const mi355rec_playlist_result_t* result);
+int mi355rec_query_distance_request_ext(mi355rec_t* h, const mi355rec_distance_query_t* query, const mi355rec_request_ext_t* ext,
+                                        const mi355rec_distance_result_t* result);
+int mi355rec_sharded_query_playlist_request_ext(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
+                                                const mi355rec_request_ext_t* ext, const mi355rec_playlist_result_t* result);
+int mi355rec_sharded_query_distance_request_ext(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
+                                                const mi355rec_request_ext_t* ext, const mi355rec_distance_result_t* result);
 
 #ifdef MI355REC_TEST_HOOKS
 /* TEST HOOK for the cross-workgroup hand-offs of the streamed scans (csrc/replica.hip.h, "hand-offs that fail

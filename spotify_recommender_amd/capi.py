@@ -76,6 +76,15 @@ class DistanceResult(ctypes.Structure):
     _fields_ = [("out_idx", c_void_p), ("out_distance", c_void_p), ("out_count", POINTER(c_int))]
 
 
+ROWSET_EXCLUDE, ROWSET_ONLY = 0, 1   # MI355REC_ROWSET_* (ROW SETS)
+
+
+class RequestExt(ctypes.Structure):
+    """mi355rec_request_ext_t (include/mi355rec_diag.h, ROW SETS): the per-request extras beside the two request structs; `size` is
+    sizeof of this struct (24).  feature_scales: NULL or 12 floats; rowset: NULL or a mi355rec_rowset_t*."""
+    _fields_ = [("size", c_uint32), ("rowset_mode", c_uint32), ("feature_scales", c_void_p), ("rowset", c_void_p)]
+
+
 class Stats(ctypes.Structure):
     _fields_ = [
         ("rows", c_int64),
@@ -251,6 +260,16 @@ SIGNATURES = {
     "mi355rec_query_distance_request_scaled": (c_int, [c_void_p, POINTER(DistanceQuery), c_void_p, POINTER(DistanceResult)]),
     "mi355rec_sharded_query_playlist_request_scaled": (c_int, [c_void_p, POINTER(PlaylistQuery), c_void_p, POINTER(PlaylistResult)]),
     "mi355rec_sharded_query_distance_request_scaled": (c_int, [c_void_p, POINTER(DistanceQuery), c_void_p, POINTER(DistanceResult)]),
+    # ROW SETS: one bit per row (a listening history, a candidate set), and the requests with their per-request extras
+    "mi355rec_rowset_create": (c_int, [c_void_p, c_void_p, c_int64, POINTER(c_void_p)]),
+    "mi355rec_sharded_rowset_create": (c_int, [c_void_p, c_void_p, c_int64, POINTER(c_void_p)]),
+    "mi355rec_rowset_add": (c_int, [c_void_p, c_void_p, c_int64]),
+    "mi355rec_rowset_count": (c_int64, [c_void_p]),
+    "mi355rec_rowset_destroy": (None, [c_void_p]),
+    "mi355rec_query_playlist_request_ext": (c_int, [c_void_p, POINTER(PlaylistQuery), POINTER(RequestExt), POINTER(PlaylistResult)]),
+    "mi355rec_query_distance_request_ext": (c_int, [c_void_p, POINTER(DistanceQuery), POINTER(RequestExt), POINTER(DistanceResult)]),
+    "mi355rec_sharded_query_playlist_request_ext": (c_int, [c_void_p, POINTER(PlaylistQuery), POINTER(RequestExt), POINTER(PlaylistResult)]),
+    "mi355rec_sharded_query_distance_request_ext": (c_int, [c_void_p, POINTER(DistanceQuery), POINTER(RequestExt), POINTER(DistanceResult)]),
     "mi355rec_pack_key": (c_uint64, [c_float, c_int64]),
     "mi355rec_key_score": (c_float, [c_uint64]),
     "mi355rec_key_row": (c_int64, [c_uint64]),

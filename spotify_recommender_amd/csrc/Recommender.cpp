@@ -36,6 +36,10 @@ struct Recommender::Impl {
     bool priorsUploaded = false;
     bool groupsUploaded = false;
 
+    // setRowSet: the engine's set (null: none) and its mode; destroyed before the engine
+    mi355rec_rowset_t* rowSet = nullptr;
+    bool rowSetOnly = false;
+
     std::vector<int64_t> idxBuf;
     std::vector<float> scoreBuf;
     std::vector<float> lastScores;
@@ -54,6 +58,7 @@ std::string toLower(const std::string& str) {  // Recommender.cu:329-334
 Recommender::Recommender() : impl_(new Impl()) {}
 
 Recommender::~Recommender() {  // Recommender.cu:86-98
+    mi355rec_rowset_destroy(impl_->rowSet);
     if (impl_->engine) mi355rec_sharded_destroy(impl_->engine);
     delete impl_;
 }
@@ -247,6 +252,42 @@ bool Recommender::setPriors(const std::vector<float>& priors) {
     return true;
 }
 
+bool Recommender::setRowSet(const std::vector<int>& songIndices, bool only) {
+    if (!impl_->initialized) {
+        std::cerr << "Error: Recommender not initialized" << std::endl;
+        return false;
+    }
+    const std::vector<int64_t> ids(songIndices.begin(), songIndices.end());
+    mi355rec_rowset_t* fresh = nullptr;
+    if (mi355rec_sharded_rowset_create(impl_->engine, ids.data(), static_cast<int64_t>(ids.size()), &fresh) != MI355REC_OK) {
+        std::cerr << "Error: " << mi355rec_sharded_last_error(impl_->engine) << std::endl;
+        return false;
+    }
+    mi355rec_rowset_destroy(impl_->rowSet);
+    impl_->rowSet = fresh;
+    impl_->rowSetOnly = only;
+    return true;
+}
+
+void Recommender::clearRowSet() {
+    mi355rec_rowset_destroy(impl_->rowSet);
+    impl_->rowSet = nullptr;
+    impl_->rowSetOnly = false;
+}
+
+namespace {
+// The per-request extras of a call: the scales (null: none) and the row set of setRowSet (none: a null pointer; an ext of
+// two null pointers is the plain request).
+mi355rec_request_ext_t requestExt(const Recommender::Impl* impl, const float* scales) {
+    mi355rec_request_ext_t ext{};
+    ext.size = sizeof ext;
+    ext.rowset_mode = impl->rowSetOnly ? MI355REC_ROWSET_ONLY : MI355REC_ROWSET_EXCLUDE;
+    ext.feature_scales = scales;
+    ext.rowset = impl->rowSet;
+    return ext;
+}
+}  // namespace
+
 bool Recommender::setGenreIds(const std::vector<int>& genreIds) {
     if (!impl_->initialized || genreIds.size() != static_cast<size_t>(impl_->numSongs)) {
         std::cerr << "Error: one genre id per song is needed" << std::endl;
@@ -417,7 +458,7 @@ std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& 
         }
         impl->priorsUploaded = true;
     }
-    if (withGenres || withPrior) {
+    if (withGenres || withPrior || impl->rowSet) {   // (a row set travels beside the request: ROW SETS)
         if (withGenres && !uploadLabels(impl)) return {};
         mi355rec_playlist_query_t q{};
         q.size = sizeof q;
@@ -444,7 +485,8 @@ std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& 
         res.out_idx = idx;
         res.out_score = score;
         res.out_count = &count;
-        rc = mi355rec_sharded_query_playlist_request(impl->engine, &q, &res);
+        const mi355rec_request_ext_t ext = requestExt(impl, nullptr);
+        rc = mi355rec_sharded_query_playlist_request_ext(impl->engine, &q, &ext, &res);
     } else if (diverse && diverse->capped) {
         rc = mi355rec_sharded_query_playlist_topn_capped(impl->engine, rows.data(), weights, k, excl.data(), nExcl, filter, diverse->lambda,
                                                          pool, diverse->maxPerGroup, topN, idx, score, nullptr, &count, nullptr);
@@ -554,7 +596,7 @@ std::vector<int> Recommender::recommendScaled(const std::vector<int>& songIndice
     impl->idxBuf.assign(static_cast<size_t>(topN), -1);
     impl->scoreBuf.assign(static_cast<size_t>(topN), 0.0f);
     int count = 0;
-    const float* const a = scales.empty() ? nullptr : scales.data();
+    const mi355rec_request_ext_t ext = requestExt(impl, scales.empty() ? nullptr : scales.data());
     if (!euclidean) {   // the playlist request by row: the members are never returned
         mi355rec_playlist_query_t pq{};
         pq.size = sizeof pq;
@@ -570,7 +612,7 @@ std::vector<int> Recommender::recommendScaled(const std::vector<int>& songIndice
         pres.out_idx = impl->idxBuf.data();
         pres.out_score = impl->scoreBuf.data();
         pres.out_count = &count;
-        if (mi355rec_sharded_query_playlist_request_scaled(impl->engine, &pq, a, &pres) != MI355REC_OK) {
+        if (mi355rec_sharded_query_playlist_request_ext(impl->engine, &pq, &ext, &pres) != MI355REC_OK) {
             std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
             return {};
         }
@@ -593,7 +635,7 @@ std::vector<int> Recommender::recommendScaled(const std::vector<int>& songIndice
     res.out_idx = impl->idxBuf.data();
     res.out_distance = impl->scoreBuf.data();
     res.out_count = &count;
-    if (mi355rec_sharded_query_distance_request_scaled(impl->engine, &q, a, &res) != MI355REC_OK) {
+    if (mi355rec_sharded_query_distance_request_ext(impl->engine, &q, &ext, &res) != MI355REC_OK) {
         std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
         return {};
     }

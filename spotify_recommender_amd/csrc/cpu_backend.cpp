@@ -233,6 +233,7 @@ int topn_impl(const Catalogue* c, const float* q12, int64_t exclude, int topn, i
 #include <chrono>
 
 #include "mi355rec_diag.h"
+#include "rowset.h"
 
 namespace mi355cpu {
 
@@ -497,6 +498,14 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
         for (int64_t i = 0; i < n; ++i) {
             uint64_t& key = keys[static_cast<size_t>(i)];
             if (key != 0 && !in_set.keeps(i)) key = 0;
+            avail += key != 0;
+        }
+    }
+    if (r.rowset) {   // "ROW SETS": ... and the rows the set does not admit (rowset.h: the host bitmap, global rows)
+        avail = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            uint64_t& key = keys[static_cast<size_t>(i)];
+            if (key != 0 && !mi355rowset::admits(r.rowset, r.rowset_only, i)) key = 0;
             avail += key != 0;
         }
     }

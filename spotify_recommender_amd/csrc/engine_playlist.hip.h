@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "engine_labels.hip.h"
+#include "engine_rowset.hip.h"
 #include "playlist.hip.h"
 #include "playlist_request.h"
 
@@ -147,6 +148,16 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
         std::memcpy(b->label_mask, mask.w, sizeof b->label_mask);
         if (selected < avail) avail = selected;
     }
+    // the row set ("ROW SETS"): this handle's copy of the bitmap; at most the rows it admits are left (an upper bound, as `selected`
+    // is).  A set that rejects no row of this shard launches exactly the call without it.
+    const uint8_t* set_bits = nullptr;
+    if (r.rowset) {
+        const mi355rowset::Part* part = rowset_part(h, r.rowset);
+        if (!part) return fail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
+        const int64_t admitted = r.rowset_only ? part->count : h->n - part->count;
+        if (admitted < avail) avail = admitted;
+        if (admitted < h->n) set_bits = part->d_bits;
+    }
     // the prior ("ROW PRIORS"): checked whenever the request carries one; beta == 0 then launches exactly the call without it
     const float* pri = nullptr;
     if (r.prior) {
@@ -167,6 +178,8 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     arg.prior = pri ? 1 : 0;
     arg.prior_weight = pri ? r.prior_weight : 0.0f;
     arg.metric = r.metric == mi355playlist::kDistance ? kPlDistance : kPlCosine;
+    arg.rowset = set_bits;
+    arg.rowset_flip = set_bits && !r.rowset_only ? 0xfu : 0u;   // EXCLUDE: a set bit clears the row; ONLY: a clear bit does
     arg.scaled = r.scales ? 1 : 0;   // "FEATURE SCALES" (every scale 1.0f has become null scales: the unscaled launch)
     for (int j = 0; j < kDim; ++j) b->scales[j] = r.scales ? r.scales[j] : 1.0f;
     for (int m = 0; m < k; ++m) b->weights[m] = r.weights ? r.weights[m] : 1.0f;
@@ -308,38 +321,51 @@ int mi355rec_query_playlist_topn_weighted(mi355rec_t* h, const int64_t* local_ro
 }
 
 // "PLAYLIST REQUESTS": the family's one call; every entry point above (and engine_diverse.hip.h's) is a special case of it.
-// ("FEATURE SCALES": the request with null scales is the NULL-scales case of the one path below.)
-int mi355rec_query_playlist_request_scaled(mi355rec_t* h, const mi355rec_playlist_query_t* query, const float* feature_scales,
-                                           const mi355rec_playlist_result_t* result) {
+// "ROW SETS": the request with its per-request extras; the plain and the _scaled entry points are special cases of THIS one path.
+int mi355rec_query_playlist_request_ext(mi355rec_t* h, const mi355rec_playlist_query_t* query, const mi355rec_request_ext_t* ext,
+                                        const mi355rec_playlist_result_t* result) {
     if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
     mi355rec_playlist_query_t full;
     Request r;
     Outputs out;
     char why[160];
-    if (mi355playlist::from_query_scaled(query, feature_scales, result, &full, &r, &out, why, sizeof why))
-        return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    if (mi355playlist::from_query_ext(query, ext, result, &full, &r, &out, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    if (r.rowset && r.rowset->node) return fail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
     return sync_playlist_query(h, r, out);
 }
 
+int mi355rec_query_playlist_request_scaled(mi355rec_t* h, const mi355rec_playlist_query_t* query, const float* feature_scales,
+                                           const mi355rec_playlist_result_t* result) {
+    const mi355rec_request_ext_t ext = mi355playlist::scales_only_ext(feature_scales);
+    return mi355rec_query_playlist_request_ext(h, query, &ext, result);
+}
+
 int mi355rec_query_playlist_request(mi355rec_t* h, const mi355rec_playlist_query_t* query, const mi355rec_playlist_result_t* result) {
-    return mi355rec_query_playlist_request_scaled(h, query, nullptr, result);
+    return mi355rec_query_playlist_request_ext(h, query, nullptr, result);
 }
 
 // "DISTANCE REQUESTS": the same Request with metric = kDistance through the same path.
-int mi355rec_query_distance_request_scaled(mi355rec_t* h, const mi355rec_distance_query_t* query, const float* feature_scales,
-                                           const mi355rec_distance_result_t* result) {
+int mi355rec_query_distance_request_ext(mi355rec_t* h, const mi355rec_distance_query_t* query, const mi355rec_request_ext_t* ext,
+                                        const mi355rec_distance_result_t* result) {
     if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
     mi355rec_distance_query_t full;
     Request r;
     Outputs out;
     char why[160];
-    if (mi355playlist::from_distance_query_scaled(query, feature_scales, result, &full, &r, &out, why, sizeof why))
+    if (mi355playlist::from_distance_query_ext(query, ext, result, &full, &r, &out, why, sizeof why))
         return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    if (r.rowset && r.rowset->node) return fail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
     return sync_playlist_query(h, r, out);
 }
 
+int mi355rec_query_distance_request_scaled(mi355rec_t* h, const mi355rec_distance_query_t* query, const float* feature_scales,
+                                           const mi355rec_distance_result_t* result) {
+    const mi355rec_request_ext_t ext = mi355playlist::scales_only_ext(feature_scales);
+    return mi355rec_query_distance_request_ext(h, query, &ext, result);
+}
+
 int mi355rec_query_distance_request(mi355rec_t* h, const mi355rec_distance_query_t* query, const mi355rec_distance_result_t* result) {
-    return mi355rec_query_distance_request_scaled(h, query, nullptr, result);
+    return mi355rec_query_distance_request_ext(h, query, nullptr, result);
 }
 
 // "ROW PRIORS"

@@ -23,6 +23,9 @@
 //       of the most similar by cosine (extension; with --genre and --where; distances are printed)
 //   ... --song, --id and --playlist with one or more --scale NAME=S: feature NAME counts S times (0: ignored) in the similarity or
 //       the distance (extension; under both metrics, with --genre and --where)
+//   ... --song, --id and --playlist with --seen FILE or --only FILE (track ids, one per line): the listed songs are never recommended
+//       (--seen: a listening history of any length) or only the listed songs are ranked (--only: a candidate set); extension, beside
+//       every other option of those modes; --song / --id then run as the one-song playlist (not with --genre there)
 //   ... --playlist with --dislike "<track_id>,..." [--dislike-weight W] [--weights "w,w,..."]: weighted playlists (extension):
 //       the disliked songs push results away (weight -W, default 0.5), --weights gives the playlist's songs their own weights
 #include <algorithm>
@@ -32,6 +35,7 @@
 #include <iostream>
 #include <map>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "DataManager.h"
@@ -76,7 +80,12 @@ static void usage(const char* prog) {
               << "   --genre, --where): every song's feature NAME is multiplied by S (0 to 1024) before songs are compared, so S = 0\n"
               << "   ignores the feature and S = 2 makes it count double; features not named keep 1.  NAME is one of --where's names or\n"
               << "   genre (the numeric genre id).  --where still tests the stored values.  Not with --diverse, --pool,\n"
-              << "   --max-per-artist, --priors, --weights or --dislike.\n" << std::endl;
+              << "   --max-per-artist, --priors, --weights or --dislike.\n"
+              << "Row sets (extension): --seen FILE or --only FILE (not both), with --song, --id or --playlist and every other option of\n"
+              << "   those modes: FILE holds track ids, one per line.  --seen: those songs are never recommended (a listening history, of\n"
+              << "   any length).  --only: only those songs are ranked (a candidate set).  Lines that name no song of the catalogue are\n"
+              << "   skipped and counted.  With --song / --id (the one-song playlist) not together with --genre: use --playlist <one id>.\n"
+              << std::endl;
 }
 
 // --where NAME=LO:HI, any number of times from argv[first]: the ranges (feature indices in Song.h order).  false, with a
@@ -239,6 +248,32 @@ static bool parseDiverse(int argc, char* argv[], int first, int topN, DiverseOpt
     return true;
 }
 
+// --seen FILE / --only FILE from argv[first] (row sets): what main() found, for the modes below.
+struct RowSetOpt {
+    bool on = false, only = false;
+    std::string file;
+};
+static RowSetOpt g_rowSet;
+
+static bool parseRowSet(int argc, char* argv[], int first, RowSetOpt& rs) {
+    for (int i = first; i < argc; ++i) {
+        const bool seen = std::strcmp(argv[i], "--seen") == 0, only = std::strcmp(argv[i], "--only") == 0;
+        if (!seen && !only) continue;
+        if (i + 1 >= argc) {
+            std::cerr << "Error: " << argv[i] << " needs a file of track ids (one per line)" << std::endl;
+            return false;
+        }
+        if (rs.on) {
+            std::cerr << "Error: --seen and --only cannot be combined, and each is given once (a request takes one row set)" << std::endl;
+            return false;
+        }
+        rs.on = true;
+        rs.only = only;
+        rs.file = argv[++i];
+    }
+    return true;
+}
+
 // The reference loads every Song, deep-copies the vector into the recommender and
 // flattens it again (main.cpp:50-60, Recommender.cu:109,162-167).  Here the file is
 // walked once (DataManager::loadCatalogue): the feature matrix goes to the engine as
@@ -262,6 +297,35 @@ static int findQuery(const DataManager::Catalogue& catalogue, const std::string&
             if (lowered(catalogue.trackNames[i]).find(needle) != std::string::npos) index = static_cast<int>(i);
     }
     return index;
+}
+
+// --seen / --only: the file's track ids (one per line, blank lines skipped, the first row of an id as for --id) to the recommender
+// as its row set.  A line that names no song of the catalogue is skipped; how many were is said on stderr (a history normally
+// holds tracks the catalogue lacks).  false, with a message, when the file cannot be read or the set is refused.
+static bool applyRowSet(Recommender& recommender, const DataManager::Catalogue& catalogue) {
+    if (!g_rowSet.on) return true;
+    std::ifstream in(g_rowSet.file);
+    if (!in) {
+        std::cerr << "Error: cannot open the row set file '" << g_rowSet.file << "'" << std::endl;
+        return false;
+    }
+    std::unordered_map<std::string, int> byId;
+    for (size_t i = 0; i < catalogue.size(); ++i) byId.emplace(catalogue.trackIds[i], static_cast<int>(i));   // (the first row of an id)
+    std::vector<int> rows;
+    size_t skipped = 0;
+    std::string line;
+    while (std::getline(in, line)) {
+        const size_t a = line.find_first_not_of(" \t\r");
+        if (a == std::string::npos) continue;
+        const auto hit = byId.find(line.substr(a, line.find_last_not_of(" \t\r") - a + 1));
+        if (hit == byId.end()) ++skipped;
+        else rows.push_back(hit->second);
+    }
+    std::cerr << "Row set (" << (g_rowSet.only ? "--only" : "--seen") << " " << g_rowSet.file << "): " << rows.size() << " tracks, " << skipped
+              << " lines skipped (not in the catalogue)" << std::endl;
+    if (!recommender.setRowSet(rows, g_rowSet.only)) return false;
+    std::cout << (g_rowSet.only ? "Only among " : "Leaving out ") << rows.size() << " listed songs" << std::endl;
+    return true;
 }
 
 // --where: the songs within every range, ranked as recommendByIndex ranks the whole catalogue.
@@ -357,6 +421,7 @@ static bool recommendationMode(const std::string& query, bool isTrackId, int top
         std::cerr << "Failed to initialize recommender" << std::endl;
         return false;
     }
+    if (!applyRowSet(recommender, catalogue)) return false;
     std::map<int, std::string>& genreMap = catalogue.genreMap;
 
     std::vector<int> recs;
@@ -364,7 +429,7 @@ static bool recommendationMode(const std::string& query, bool isTrackId, int top
     if (isTrackId) {
         std::cout << "\nSearching for track ID: " << query << std::endl;
         if (dv.on) diverseRecommendations(recommender, catalogue, query, true, topN, ranges, dv, recs);
-        else if (!ranges.empty()) whereRecommendations(recommender, catalogue, query, true, topN, ranges, recs);
+        else if (!ranges.empty() || g_rowSet.on) whereRecommendations(recommender, catalogue, query, true, topN, ranges, recs);   // (a row set: the one-song playlist)
         else if (genres.empty()) recs = recommender.recommend(query, topN);
         else if (!genreRecommendations(recommender, catalogue, query, true, topN, genres, recs)) return false;
         for (size_t i = 0; i < catalogue.size(); ++i)
@@ -372,7 +437,7 @@ static bool recommendationMode(const std::string& query, bool isTrackId, int top
     } else {
         std::cout << "\nSearching for song: " << query << std::endl;
         if (dv.on) diverseRecommendations(recommender, catalogue, query, false, topN, ranges, dv, recs);
-        else if (!ranges.empty()) whereRecommendations(recommender, catalogue, query, false, topN, ranges, recs);
+        else if (!ranges.empty() || g_rowSet.on) whereRecommendations(recommender, catalogue, query, false, topN, ranges, recs);
         else if (genres.empty()) recs = recommender.recommendByName(query, topN);
         else if (!genreRecommendations(recommender, catalogue, query, false, topN, genres, recs)) return false;
         // The reference finds the song it DISPLAYS with a single exact-or-substring
@@ -575,6 +640,7 @@ static bool playlistMode(const std::string& list, int topN, const std::vector<Re
         std::cerr << "Failed to initialize recommender" << std::endl;
         return false;
     }
+    if (!applyRowSet(recommender, catalogue)) return false;
     std::map<int, std::string>& genreMap = catalogue.genreMap;
     if (dv.maxPerArtist > 0) {
         if (!capByArtist(recommender, catalogue)) return false;
@@ -696,6 +762,7 @@ static bool nearestMode(const std::string& query, bool isPlaylist, bool isTrackI
         std::cerr << "Failed to initialize recommender" << std::endl;
         return false;
     }
+    if (!applyRowSet(recommender, catalogue)) return false;
     if (!genreIds.empty()) {
         std::cout << "Restricted to genres:";
         for (const std::string& name : genres) std::cout << " " << name;
@@ -779,6 +846,7 @@ int main(int argc, char* argv[]) {
         }
         std::vector<Recommender::FeatureRange> ranges;
         if (!parseWhere(argc, argv, 3, ranges)) return 1;
+        if (!parseRowSet(argc, argv, 3, g_rowSet)) return 1;
         bool euclidean = false;
         if (!parseMetric(argc, argv, 3, euclidean)) return 1;
         std::vector<float> scales;
@@ -786,6 +854,11 @@ int main(int argc, char* argv[]) {
         if (euclidean || !scales.empty()) return nearestMode(argv[2], false, mode == "--id", topN, ranges, genres, euclidean, scales) ? 0 : 1;
         if (!ranges.empty() && !genres.empty()) {
             std::cerr << "Error: --where cannot be combined with --genre" << std::endl;
+            return 1;
+        }
+        if (g_rowSet.on && !genres.empty()) {
+            std::cerr << "Error: " << (g_rowSet.only ? "--only" : "--seen") << " cannot be combined with --genre here: use --playlist <one id> --genre ..."
+                      << std::endl;
             return 1;
         }
         DiverseOpt dv;
@@ -814,6 +887,7 @@ int main(int argc, char* argv[]) {
         }
         std::vector<Recommender::FeatureRange> ranges;
         if (!parseWhere(argc, argv, 3, ranges)) return 1;
+        if (!parseRowSet(argc, argv, 3, g_rowSet)) return 1;
         bool euclidean = false;
         if (!parseMetric(argc, argv, 3, euclidean)) return 1;
         std::vector<float> scales;

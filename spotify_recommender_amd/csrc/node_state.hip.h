@@ -23,6 +23,7 @@
 #include "cpu_backend.h"
 #include "mi355rec_diag.h"
 #include "playlist_request.h"
+#include "rowset.h"
 
 namespace mi355node {
 // mi355rec_set_labels for a handle whose group of lanes the caller has to itself (engine_labels.hip.h): the replicas of a
@@ -42,6 +43,8 @@ int rerank_pool(mi355rec_t* h, const int64_t* pool_idx, const float* pool_score,
 int set_group_groups(mi355rec_t* h, const int32_t* groups_host, int64_t n);
 // mi355rec_set_priors for a handle whose group of lanes the caller has to itself (as set_group_labels).
 int set_group_priors(mi355rec_t* h, const float* priors_host, int64_t n);
+// ROW SETS (engine_rowset.hip.h): a device copy of rows [lo, hi) of the set's bitmap beside the rows of `e`; why[0..cap) on failure.
+int rowset_attach(mi355rec_rowset* s, mi355rec_t* e, int64_t lo, int64_t hi, char* why, size_t cap);
 }  // namespace mi355node
 
 namespace {

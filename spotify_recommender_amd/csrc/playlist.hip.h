@@ -113,6 +113,23 @@
 //     row's own replica bytes).
 // scaled == 0 takes none of these branches (uniform tests) and never reads PlaylistBuf::scales.
 //
+// ROW SETS (include/mi355rec_diag.h, "ROW SETS").  PlaylistArg::rowset (uniform; null: no set), the shard's bitmap built on the host
+// (rowset.h, engine_rowset.hip.h): bit i & 7 of byte i / 8 is local row i, the bits past the last row are 0; and PlaylistArg::rowset_flip:
+// 0xf when rows IN the set are not admissible (EXCLUDE), 0 when rows NOT in it are not (ONLY), so (nibble ^ flip) & 0xf is a quad's
+// admissible mask.  Like the label test it needs no fp32 row, so it comes FIRST:
+//   * scan: per tile a lane takes the nibble of its quad (byte quad >> 1, shift (quad & 1) * 4, the quad clamped by playlist_tile_quad)
+//     and ANDs it into `mask` before the label test, the 8-bit dot products, the filter's fp32 loads and any chain, on the exact path
+//     and for the replica's 0x80 rows too.  A row the set rejects never reads an fp32 row and rows_exact does not count it.  The byte is
+//     loaded at the top of the tile iteration, not with the next tile's replica load: measured both ways at 128 VGPRs and no scratch
+//     (docs/LAB_NOTES.md): the prefetched form takes about 2 us off a K = 1 call with a set at 10 M rows and was not shown to leave
+//     the calls without a set alone, which this form does;
+//   * anchors: the rows read from the matrix are tested again, beside playlist_excluded, the filter and the label, so the starting
+//     threshold stays the topk-th best key among admissible rows (the anchor table's copy still only chooses rows, by similarity).
+// So keys are only ever formed for admissible rows, and the rule (the k-th best among ANY k admissible rows bounds the answer) keeps
+// every workgroup's threshold and the shared atomicMax valid.  The pre-filter, its margins and playlist_cut.hip.h do not change: the
+// replica still only rules rows out by similarity, among the rows the set has left.  rowset == null takes none of these branches
+// (uniform tests) and reads nothing new.
+//
 // EXCLUSION.  The excluded global ids (members and the caller's list, sorted and deduplicated on the host, at most
 // kPlExcludeCap) sit in LDS as uint32; only a key that already beats the workgroup's threshold is looked up (binary
 // search), so the hot loop does not change.
@@ -161,6 +178,8 @@ struct PlaylistArg {
     int prior;        // 1: rank by v, p from the kernel's `priors`; 0: rank by the score alone (`priors` is never read)
     int metric;       // kPlCosine, or kPlDistance: rank by -m(x), the mean squared distance to the members (DISTANCE above)
     int scaled;       // 1: rows and members are multiplied by PlaylistBuf::scales before the chains (FEATURE SCALES above); 0: never read
+    const uint8_t* rowset;   // ROW SETS above: the shard's bitmap, bit i of byte i / 8 is local row i (padding bits 0); null: no set
+    uint32_t rowset_flip;    // ... 0xf: rows IN the set are not admissible (EXCLUDE); 0: rows NOT in it are not (ONLY)
 };
 
 // Is label l (int16 of the row-order array: -1 = unlabelled or padding) in the set?
@@ -237,6 +256,11 @@ __device__ __forceinline__ float playlist_sqdist(const float (*__restrict__ mem)
     return sum / static_cast<float>(k);
 }
 
+// ROW SETS: does the set admit local row `row`?  (bits: non-null)
+__device__ __forceinline__ bool rowset_admits(const uint8_t* __restrict__ bits, uint32_t flip, int64_t row) {
+    return (((static_cast<uint32_t>(bits[row >> 3]) >> (row & 7)) ^ flip) & 1u) != 0u;
+}
+
 __device__ __forceinline__ bool playlist_excluded(const uint32_t* s_excl, int n_excl, uint32_t g) {
     int lo = 0, hi = n_excl;
     while (lo < hi) {
@@ -275,6 +299,8 @@ struct PlaylistCtx {
     const float* row_prior;     // the rows' priors one by one
     const float4* side4;        // a quad's four SIDE values: the rows' priors, or (DISTANCE) their stored norms; null: none were passed
     const uint4* q8;            // (never read with the cut off)
+    const uint8_t* rowset;      // ROW SETS: the bitmap, or null
+    uint32_t flip;
     int tid, lane;
 };
 
@@ -410,7 +436,7 @@ __device__ __forceinline__ uint64_t playlist_anchor_bound(const PlaylistCtx& c, 
         const uint64_t row_key = playlist_row_key(c, sm, x, row);
         ++n_exact;
         key = playlist_excluded(sm.excl, c.n_excl, static_cast<uint32_t>(c.row_base + row)) || !x_pass ||
-                      (c.labelled && !label_selected(sm.lmask, c.row_label[row]))
+                      (c.labelled && !label_selected(sm.lmask, c.row_label[row])) || (c.rowset && !rowset_admits(c.rowset, c.flip, row))
                   ? 0ull
                   : row_key;
     }
@@ -473,7 +499,11 @@ __device__ __forceinline__ void playlist_scan_tiles(const PlaylistCtx& c, const 
         const int64_t r0 = quad * 4;
         const int64_t left = quad < n_quads ? n - r0 : 0;   // rows of the quad inside the shard
         uint32_t mask = left >= 4 ? 0xfu : (1u << static_cast<int>(left)) - 1u;
-        if (c.labelled) {   // (uniform) the label test first: it needs nothing but the label
+        if (c.rowset) {   // (uniform) ROW SETS: the quad's nibble, before anything else is done with its rows
+            const int64_t q = playlist_tile_quad(t, tid, n_quads);
+            mask &= ((static_cast<uint32_t>(c.rowset[q >> 1]) >> ((static_cast<uint32_t>(q) & 1u) * 4u)) ^ c.flip) & 0xfu;
+        }
+        if (c.labelled) {   // (uniform) the label test: it needs nothing but the label
             const int l4[4] = {static_cast<int16_t>(cur.labels.x & 0xffffu), static_cast<int16_t>(cur.labels.x >> 16),
                                static_cast<int16_t>(cur.labels.y & 0xffffu), static_cast<int16_t>(cur.labels.y >> 16)};
 #pragma unroll
@@ -556,7 +586,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     const int tid = threadIdx.x;
     const PlaylistCtx c = {feats, anchors, n, row_base, buf, shared_thr, arg.k, arg.n_excl, topk, arg.active, arg.wsum, arg.prior_weight,
                            arg.by_row != 0, arg.labelled != 0, arg.prior != 0, dist, arg.scaled != 0, reinterpret_cast<const int16_t*>(labels), labels,
-                           reinterpret_cast<const float*>(priors), dist ? norms : priors, q8, tid, tid & 63};
+                           reinterpret_cast<const float*>(priors), dist ? norms : priors, q8, arg.rowset, arg.rowset_flip, tid, tid & 63};
     float u[kDim], un;
     PlaylistCut cut;
     const Q8Query hq = playlist_prologue(c, sm, u, un, cut);

@@ -45,6 +45,8 @@ struct Request {
                                                 // ... handle's merge over shards compares
     const float* scales = nullptr;              // null, or 12 checked feature scales a_j ("FEATURE SCALES"): the call is the same
                                                 // ... call on rows fl(a_j x_j) with members fl(a_j q_kj); the filter tests x itself
+    const mi355rec_rowset_t* rowset = nullptr;  // null, or the row set ("ROW SETS", rowset.h): with rowset_only only its rows are
+    bool rowset_only = false;                   // ... admissible, without it only the others
 
     int scan_topn() const { return diverse ? pool : topn; }   // what the scan selects
     // The same call diversified, and (of a diversified one) capped: what the _diverse and _capped entry points add.
@@ -296,23 +298,69 @@ inline const float* effective_scales(const float* a) {
     return nullptr;
 }
 
-// from_query with the scales of the _scaled entry points: null scales are from_query itself; otherwise every check of from_query
-// first (its messages), then flags must be 0 and the scales usable.
-inline bool from_query_scaled(const mi355rec_playlist_query_t* q, const float* scales, const mi355rec_playlist_result_t* res,
-                              mi355rec_playlist_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
-    if (from_query(q, res, full, r, out, msg, cap)) return true;
-    if (!scales) return false;
-    static const struct { uint32_t bit; const char* name; } refused[] = {{MI355REC_PQ_DIVERSE, "MI355REC_PQ_DIVERSE"},
-                                                                         {MI355REC_PQ_CAPPED, "MI355REC_PQ_CAPPED"},
-                                                                         {MI355REC_PQ_PRIOR, "MI355REC_PQ_PRIOR"}};
-    for (const auto& f : refused)
-        if (full->flags & f.bit) {
-            std::snprintf(msg, cap, "%s with feature scales: flags must be 0 (diversified and capped calls and priors are not served)", f.name);
-            return true;
-        }
-    if (invalid_scales(scales, msg, cap)) return true;
-    r->scales = effective_scales(scales);
+// "ROW SETS": the per-request extras (mi355rec_request_ext_t) as this library reads them.  ext->size follows the size rules of
+// from_query: a shorter struct that ends where a field ends is read as "later fields zero"; 0, an end inside a field, or more than
+// this library knows is refused.  A null ext is the ext with every field zero.  True when it cannot be used; then msg says why.
+inline bool from_ext(const mi355rec_request_ext_t* ext, mi355rec_request_ext_t* full, char* msg, size_t cap) {
+    std::memset(full, 0, sizeof *full);
+    if (!ext) return false;
+    static const size_t ends[] = {offsetof(mi355rec_request_ext_t, rowset_mode), offsetof(mi355rec_request_ext_t, feature_scales),
+                                  offsetof(mi355rec_request_ext_t, rowset), sizeof(mi355rec_request_ext_t)};
+    static_assert(sizeof(mi355rec_request_ext_t) == 24 && offsetof(mi355rec_request_ext_t, rowset) == 16, "the struct ends where its last field ends");
+    bool known = false;
+    for (size_t e : ends) known = known || ext->size == e;
+    if (!known) {
+        std::snprintf(msg, cap, "request ext of size %u: not the end of a field of the %u bytes this library reads",
+                      static_cast<unsigned>(ext->size), static_cast<unsigned>(sizeof *full));
+        return true;
+    }
+    std::memcpy(full, ext, ext->size);
+    if (full->rowset && full->rowset_mode != MI355REC_ROWSET_EXCLUDE && full->rowset_mode != MI355REC_ROWSET_ONLY) {
+        std::snprintf(msg, cap, "rowset_mode %u: MI355REC_ROWSET_EXCLUDE (0) or MI355REC_ROWSET_ONLY (1)", static_cast<unsigned>(full->rowset_mode));
+        return true;
+    }
     return false;
+}
+
+// The extras of a checked ext into the Request (the scales checked here: invalid_scales' messages).
+inline bool apply_ext(const mi355rec_request_ext_t& ext, Request* r, char* msg, size_t cap) {
+    if (ext.feature_scales) {
+        if (invalid_scales(ext.feature_scales, msg, cap)) return true;
+        r->scales = effective_scales(ext.feature_scales);
+    }
+    r->rowset = ext.rowset;
+    r->rowset_only = ext.rowset && ext.rowset_mode == MI355REC_ROWSET_ONLY;
+    return false;
+}
+
+// from_query with the extras of the _ext entry points (the _scaled ones pass an ext that holds their scales): every check of
+// from_query first (its messages), then the ext's own; with scales, flags must be 0 and the scales usable.  A null ext, or one whose
+// pointers are null, is from_query itself.
+inline bool from_query_ext(const mi355rec_playlist_query_t* q, const mi355rec_request_ext_t* ext, const mi355rec_playlist_result_t* res,
+                           mi355rec_playlist_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
+    if (from_query(q, res, full, r, out, msg, cap)) return true;
+    mi355rec_request_ext_t x;
+    if (from_ext(ext, &x, msg, cap)) return true;
+    if (x.feature_scales) {
+        static const struct { uint32_t bit; const char* name; } refused[] = {{MI355REC_PQ_DIVERSE, "MI355REC_PQ_DIVERSE"},
+                                                                             {MI355REC_PQ_CAPPED, "MI355REC_PQ_CAPPED"},
+                                                                             {MI355REC_PQ_PRIOR, "MI355REC_PQ_PRIOR"}};
+        for (const auto& f : refused)
+            if (full->flags & f.bit) {
+                std::snprintf(msg, cap, "%s with feature scales: flags must be 0 (diversified and capped calls and priors are not served)", f.name);
+                return true;
+            }
+    }
+    return apply_ext(x, r, msg, cap);
+}
+
+// The ext a _scaled entry point passes on: its scales and nothing else.
+inline mi355rec_request_ext_t scales_only_ext(const float* scales) {
+    mi355rec_request_ext_t x;
+    std::memset(&x, 0, sizeof x);
+    x.size = static_cast<uint32_t>(sizeof x);
+    x.feature_scales = scales;
+    return x;
 }
 
 // The C-ABI's distance request (include/mi355rec_diag.h, "DISTANCE REQUESTS") as the same Request (metric = kDistance) and
@@ -363,14 +411,13 @@ inline bool from_distance_query(const mi355rec_distance_query_t* q, const mi355r
     return false;
 }
 
-// from_distance_query with the scales of the _scaled entry points (null: from_distance_query itself).
-inline bool from_distance_query_scaled(const mi355rec_distance_query_t* q, const float* scales, const mi355rec_distance_result_t* res,
-                                       mi355rec_distance_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
+// from_distance_query with the extras of the _ext entry points (null, or null pointers: from_distance_query itself).
+inline bool from_distance_query_ext(const mi355rec_distance_query_t* q, const mi355rec_request_ext_t* ext, const mi355rec_distance_result_t* res,
+                                    mi355rec_distance_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
     if (from_distance_query(q, res, full, r, out, msg, cap)) return true;
-    if (!scales) return false;
-    if (invalid_scales(scales, msg, cap)) return true;
-    r->scales = effective_scales(scales);
-    return false;
+    mi355rec_request_ext_t x;
+    if (from_ext(ext, &x, msg, cap)) return true;
+    return apply_ext(x, r, msg, cap);
 }
 
 }  // namespace mi355playlist

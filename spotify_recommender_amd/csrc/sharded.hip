@@ -742,6 +742,7 @@ int sharded_playlist(mi355rec_sharded_t* h, Request r, const Outputs& out) {
         return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
     if (r.prior && !h->cpu && !h->has_priors)
         return sfail(h, MI355REC_ERR_INVALID_ARG, "this handle has no priors (mi355rec_sharded_set_priors)");
+    if (r.rowset && r.rowset->node != h) return sfail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
     if (out.pool_rows) *out.pool_rows = 0;
     // By row, one handle (row_base 0) takes its own by-row call below: the members stay on the device.  Otherwise the members
     // go by value (fetched once) and their rows are added to the exclusion list.
@@ -873,39 +874,85 @@ int mi355rec_sharded_query_playlist_topn_capped(mi355rec_sharded_t* h, const int
 // FEATURE SCALES: the scales travel in the Request.  One handle takes it as it is; a row-sharded catalogue has fetched the
 // members given by row UNSCALED (sharded_playlist) and forwards them by value with the scales, so every shard's fl(a_j x_j) is
 // the by-row value.
-int mi355rec_sharded_query_playlist_request_scaled(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
-                                                   const float* feature_scales, const mi355rec_playlist_result_t* result) {
+// ROW SETS: the set travels in the Request as well (sharded_playlist checks that it is this node's); every shard's scan finds its
+// own copy of the bitmap (engine_playlist.hip.h), the CPU backend tests the host bitmap.
+int mi355rec_sharded_query_playlist_request_ext(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
+                                                const mi355rec_request_ext_t* ext, const mi355rec_playlist_result_t* result) {
     if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
     mi355rec_playlist_query_t full;
     Request r;
     Outputs out;
     char why[160];
-    if (mi355playlist::from_query_scaled(query, feature_scales, result, &full, &r, &out, why, sizeof why))
-        return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    if (mi355playlist::from_query_ext(query, ext, result, &full, &r, &out, why, sizeof why)) return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
     return sharded_playlist(h, r, out);
+}
+
+int mi355rec_sharded_query_playlist_request_scaled(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
+                                                   const float* feature_scales, const mi355rec_playlist_result_t* result) {
+    const mi355rec_request_ext_t ext = mi355playlist::scales_only_ext(feature_scales);
+    return mi355rec_sharded_query_playlist_request_ext(h, query, &ext, result);
 }
 
 int mi355rec_sharded_query_playlist_request(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
                                             const mi355rec_playlist_result_t* result) {
-    return mi355rec_sharded_query_playlist_request_scaled(h, query, nullptr, result);
+    return mi355rec_sharded_query_playlist_request_ext(h, query, nullptr, result);
 }
 
 // DISTANCE REQUESTS (include/mi355rec_diag.h): the same Request with metric = kDistance through sharded_playlist.
-int mi355rec_sharded_query_distance_request_scaled(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
-                                                   const float* feature_scales, const mi355rec_distance_result_t* result) {
+int mi355rec_sharded_query_distance_request_ext(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
+                                                const mi355rec_request_ext_t* ext, const mi355rec_distance_result_t* result) {
     if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
     mi355rec_distance_query_t full;
     Request r;
     Outputs out;
     char why[160];
-    if (mi355playlist::from_distance_query_scaled(query, feature_scales, result, &full, &r, &out, why, sizeof why))
+    if (mi355playlist::from_distance_query_ext(query, ext, result, &full, &r, &out, why, sizeof why))
         return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
     return sharded_playlist(h, r, out);
 }
 
+int mi355rec_sharded_query_distance_request_scaled(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
+                                                   const float* feature_scales, const mi355rec_distance_result_t* result) {
+    const mi355rec_request_ext_t ext = mi355playlist::scales_only_ext(feature_scales);
+    return mi355rec_sharded_query_distance_request_ext(h, query, &ext, result);
+}
+
 int mi355rec_sharded_query_distance_request(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
                                             const mi355rec_distance_result_t* result) {
-    return mi355rec_sharded_query_distance_request_scaled(h, query, nullptr, result);
+    return mi355rec_sharded_query_distance_request_ext(h, query, nullptr, result);
+}
+
+// ROW SETS (include/mi355rec_diag.h): the global host bitmap, and a device copy beside every engine's rows: a row-sharded placement
+// gives each shard the slice [lo, hi) (lo is in general no multiple of 8: rowset.h slices by bit), a replicated one and a single
+// shard the whole bitmap.  mi355rec_rowset_add (engine_rowset.hip.h) refreshes every copy.
+int mi355rec_sharded_rowset_create(mi355rec_sharded_t* h, const int64_t* global_ids, int64_t n_ids, mi355rec_rowset_t** out) {
+    if (!h || !out) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    char why[160];
+    if (mi355rowset::invalid_ids(global_ids, n_ids, h->n, why, sizeof why)) return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    mi355rec_rowset* s = new (std::nothrow) mi355rec_rowset();
+    if (!s) return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for a row set");
+    s->node = h;
+    try {
+        s->bits.reset(0, h->n);
+    } catch (const std::bad_alloc&) {
+        delete s;
+        return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for a row set of %lld rows", (long long)h->n);
+    }
+    s->bits.add(global_ids, n_ids);
+    if (!h->cpu) {
+        DeviceRestore restore;
+        for (Shard& sh : h->shards) {
+            if (sh.hi <= sh.lo) continue;
+            const int rc = mi355node::rowset_attach(s, sh.engine, sh.lo, sh.hi, why, sizeof why);
+            if (rc != MI355REC_OK) {
+                mi355rec_rowset_destroy(s);
+                return sfail(h, rc, "shard on device %d: %s", sh.device, why);
+            }
+        }
+    }
+    *out = s;
+    return MI355REC_OK;
 }
 
 int mi355rec_sharded_scores_row(mi355rec_sharded_t* h, int64_t global_row, float* out_host) {

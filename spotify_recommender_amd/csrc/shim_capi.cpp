@@ -176,6 +176,15 @@ int64_t shim_recommend_by_index_in_genres(void* h, int idx, int topn, const int*
     return giveBack(c, c->rec.recommendByIndexInGenres(idx, topn, std::vector<int>(genres, genres + (n_genres > 0 ? n_genres : 0))),
                     out, scores, cap);
 }
+// Recommender::setRowSet (n_songs < 0: clearRowSet).
+int shim_set_row_set(void* h, const int* songs, int n_songs, int only) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    if (n_songs < 0) {
+        c->rec.clearRowSet();
+        return 1;
+    }
+    return c->rec.setRowSet(std::vector<int>(songs, songs + n_songs), only != 0) ? 1 : 0;
+}
 // Recommender::recommendForPlaylist.
 int64_t shim_recommend_for_playlist(void* h, const int* songs, int n_songs, int topn, const int* exclude, int n_exclude, int* out,
                                     float* scores, int64_t cap) {

@@ -9,6 +9,7 @@ per-workgroup lists.  No arithmetic happens in Python.
 from __future__ import annotations
 
 import ctypes
+import weakref
 from typing import Optional, Tuple
 
 import numpy as np
@@ -90,7 +91,7 @@ _PLAYLIST_LEVELS = ("", "_where", "_weighted", "_diverse", "_capped")   # each l
 
 def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=None, where=None, weights=None, level: str = None,
                      lam=None, pool=None, max_per_group=None, return_mmr: bool = False, return_pool_rows: bool = False, labels=None,
-                     prior_weight=None, scales=None):
+                     prior_weight=None, scales=None, rowset=None):
     """Runs one entry point of the playlist family: `prefix`query_{mean|playlist}_topn`level`.  `members` is a (k, 12) float32
     array (by value: mean) or a 1-D int64 array of rows (by row: playlist).  `level` None: the lowest that takes the
     arguments given ("" plain, "_where" with a filter, "_weighted" with weights); "_diverse" and "_capped" are asked for.
@@ -111,7 +112,9 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
     ROW PRIORS: `prior_weight` = beta ranks by score + beta * prior (set_priors; |beta| <= capi.MAX_PRIOR_WEIGHT, negative demotes);
     the call goes through the request as well, the returned scores are the blended values.  None takes the entry point used today.
     FEATURE SCALES: `scales` (make_scales) weighs or ignores features; the call goes through `prefix`query_playlist_request_scaled,
-    which refuses diversified and capped calls and priors.  None takes the entry point used today."""
+    which refuses diversified and capped calls and priors.  None takes the entry point used today.
+    ROW SETS: `rowset` = (the set's pointer, capi.ROWSET_EXCLUDE or capi.ROWSET_ONLY); the call goes through
+    `prefix`query_playlist_request_ext.  None takes the entry point used today."""
     if prior_weight is not None and (isinstance(prior_weight, bool) or not isinstance(prior_weight, (int, float, np.integer, np.floating))):
         raise ValueError(f"prior_weight must be a number or None, got {prior_weight!r}")
     if level is None:
@@ -162,7 +165,7 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
         args.append(ctypes.byref(pool_rows))
     by = "playlist" if members.dtype == np.int64 else "mean"
     a = make_scales(scales) if scales is not None else None
-    if labels is not None or prior_weight is not None or a is not None:
+    if labels is not None or prior_weight is not None or a is not None or rowset is not None:
         q = capi.PlaylistQuery()
         q.size = ctypes.sizeof(capi.PlaylistQuery)
         q.flags = (capi.PQ_DIVERSE if diverse else 0) | (capi.PQ_CAPPED if capped else 0)
@@ -183,7 +186,10 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
             q.max_per_group = int(max_per_group)
         res = capi.PlaylistResult(ptr(idx), ptr(score), ptr(mmr) if diverse else None, ctypes.pointer(count),
                                   ctypes.pointer(pool_rows))
-        if a is not None:
+        if rowset is not None:
+            ext = capi.RequestExt(ctypes.sizeof(capi.RequestExt), int(rowset[1]), ptr(a) if a is not None else None, rowset[0])
+            check(getattr(lib, f"{prefix}query_playlist_request_ext")(h, ctypes.byref(q), ctypes.byref(ext), ctypes.byref(res)))
+        elif a is not None:
             check(getattr(lib, f"{prefix}query_playlist_request_scaled")(h, ctypes.byref(q), ptr(a), ctypes.byref(res)))
         else:
             check(getattr(lib, f"{prefix}query_playlist_request")(h, ctypes.byref(q), ctypes.byref(res)))
@@ -197,11 +203,12 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
     return out
 
 
-def _distance_request(lib, prefix: str, h, check, members, topn: int, exclude=None, where=None, labels=None, scales=None):
+def _distance_request(lib, prefix: str, h, check, members, topn: int, exclude=None, where=None, labels=None, scales=None, rowset=None):
     """One DISTANCE REQUEST (`prefix`query_distance_request): the `topn` rows nearest to the members by Euclidean distance.
     `members` is a (k, 12) float32 array (by value) or a 1-D int64 array of rows (never returned).  `exclude`, `where` and
     `labels` are the playlist request's.  Returns (ids, distances): nearest first, ties by row; for k > 1 a distance is the
-    root-mean-square distance to the members.  `scales` (make_scales): FEATURE SCALES, through `prefix`query_distance_request_scaled."""
+    root-mean-square distance to the members.  `scales` (make_scales): FEATURE SCALES, through `prefix`query_distance_request_scaled.
+    `rowset` = (pointer, mode): ROW SETS, through `prefix`query_distance_request_ext."""
     flt = make_filter(where) if where is not None else None
     ex = np.ascontiguousarray(np.asarray([] if exclude is None else list(exclude), dtype=np.int64).reshape(-1))
     n_out = max(int(topn), 1)
@@ -222,7 +229,11 @@ def _distance_request(lib, prefix: str, h, check, members, topn: int, exclude=No
         q.labels, q.n_labels = ptr(lab), int(lab.size)   # (an empty set stays a non-NULL pointer: the library refuses it)
     q.k, q.topn = int(members.shape[0]), int(topn)
     res = capi.DistanceResult(ptr(idx), ptr(dist), ctypes.pointer(count))
-    if scales is not None:
+    if rowset is not None:
+        a = make_scales(scales) if scales is not None else None
+        ext = capi.RequestExt(ctypes.sizeof(capi.RequestExt), int(rowset[1]), ptr(a) if a is not None else None, rowset[0])
+        check(getattr(lib, f"{prefix}query_distance_request_ext")(h, ctypes.byref(q), ctypes.byref(ext), ctypes.byref(res)))
+    elif scales is not None:
         a = make_scales(scales)
         check(getattr(lib, f"{prefix}query_distance_request_scaled")(h, ctypes.byref(q), ptr(a), ctypes.byref(res)))
     else:
@@ -251,7 +262,89 @@ def _np_rows(rows) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(list(rows), dtype=np.int64).reshape(-1))
 
 
-class CosineEngine:
+class RowSet:
+    """ROW SETS (include/mi355rec_diag.h): one bit per row of the engine it was made on (CosineEngine.row_set / NodeEngine.row_set),
+    n / 8 bytes on the host and on every device copy.  Pass it as `seen=` (its rows are left out) or `only=` (only its rows are
+    ranked).  It may grow (add); close() frees it, and the engine closes the sets it still has before it closes itself.  add or
+    close while another thread runs a request with the set is the caller's error."""
+
+    def __init__(self, owner, ids, create):
+        self._lib = owner._lib
+        self._owner = owner
+        self._p = ctypes.c_void_p()
+        a = _np_ids(ids)
+        owner._set_check(create(owner._h, a.ctypes.data_as(ctypes.c_void_p) if a.size else None, int(a.size), ctypes.byref(self._p)))
+        owner._sets.add(self)
+
+    def _ptr(self):
+        if not self._p:
+            raise ValueError("this row set is closed")
+        return self._p
+
+    def add(self, ids) -> None:
+        """Adds global ids (duplicates and ids already in the set are fine); a refused list leaves the set unchanged."""
+        a = _np_ids(ids)
+        rc = self._lib.mi355rec_rowset_add(self._ptr(), a.ctypes.data_as(ctypes.c_void_p) if a.size else None, int(a.size))
+        if rc != capi.OK:
+            raise capi.Mi355Error(rc, (self._lib.mi355rec_last_global_error() or b"").decode("utf-8", "replace"))
+
+    @property
+    def count(self) -> int:
+        """The distinct rows of the engine in the set."""
+        return int(self._lib.mi355rec_rowset_count(self._ptr()))
+
+    def close(self) -> None:
+        if getattr(self, "_p", None) is not None and self._p:
+            self._lib.mi355rec_rowset_destroy(self._p)
+            self._p = ctypes.c_void_p()
+            self._owner._sets.discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _np_ids(ids) -> np.ndarray:
+    """Global ids of a row set (int64, contiguous); the library checks the values."""
+    return np.ascontiguousarray(np.asarray([] if ids is None else ids, dtype=np.int64).reshape(-1))
+
+
+class _RowSets:
+    """What both engines share for ROW SETS: the sets they own, and `seen=` / `only=` resolved to (pointer, mode)."""
+
+    @property
+    def _sets(self):
+        if "_row_sets" not in self.__dict__:
+            self.__dict__["_row_sets"] = weakref.WeakSet()
+        return self.__dict__["_row_sets"]
+
+    def _close_sets(self) -> None:
+        for s in list(self.__dict__.get("_row_sets", ())):
+            s.close()
+
+    def _with_set(self, seen, only, call):
+        """call(rowset) with rowset = None, or (pointer, mode) of `seen` / `only`: a RowSet, or a plain id sequence, for which a
+        temporary set is made and destroyed."""
+        if seen is not None and only is not None:
+            raise ValueError("seen= and only= are mutually exclusive: a request takes one row set")
+        src, mode = (seen, capi.ROWSET_EXCLUDE) if seen is not None else (only, capi.ROWSET_ONLY)
+        if src is None:
+            return call(None)
+        if isinstance(src, RowSet):
+            return call((src._ptr(), mode))
+        with self.row_set(src) as tmp:
+            return call((tmp._ptr(), mode))
+
+
+class CosineEngine(_RowSets):
     """One row shard of the N x 12 fp32 catalogue resident on one MI355X.
 
     Replaces the reference's device state (d_features / d_queryFeature /
@@ -322,8 +415,17 @@ class CosineEngine:
         return torch.cuda.ExternalStream(int(self._lib.mi355rec_own_stream(self._h)), device=self.device)
 
     # -- lifetime ---------------------------------------------------------
+    def row_set(self, ids) -> RowSet:
+        """A ROW SET of this handle from global ids (0 <= id < 2**32; ids of other shards match nothing), usable on this engine
+        and its lanes as `seen=` or `only=`."""
+        return RowSet(self, ids, self._lib.mi355rec_rowset_create)
+
+    def _set_check(self, rc: int) -> None:
+        capi.check(rc, self._h)
+
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h:
+            self._close_sets()
             self._lib.mi355rec_destroy(self._h)
             self._h = ctypes.c_void_p()
         self._keepalive = None
@@ -593,24 +695,29 @@ class CosineEngine:
 
     # ---- PLAYLISTS (include/mi355rec_diag.h): top-N by the mean score against up to 32 songs ----
     def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None,
-                        scales=None) -> Tuple[np.ndarray, np.ndarray]:
+                        scales=None, seen=None, only=None) -> Tuple[np.ndarray, np.ndarray]:
         """The best `topn` rows by the mean of their scores against the rows of `queries` (k x 12); `exclude`: global ids.
         `where`: {feature index or name: (lo, hi)}, only rows within every range are returned (FEATURE FILTERS; a
         filtered single query is k = 1); None calls the unfiltered entry point.
         `weights`: one signed float per member (WEIGHTED PLAYLISTS: score = sum w_k c_k / sum |w_k|, a negative weight is
         a dislike); None calls the entry point used without it.
         `scales`: FEATURE SCALES, 12 floats or {feature index or name: scale} (unnamed features 1.0): rows and members are
-        multiplied feature by feature before the scores are taken (0 ignores a feature); not with prior_weight."""
-        return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales)
+        multiplied feature by feature before the scores are taken (0 ignores a feature); not with prior_weight.
+        `seen` / `only`: ROW SETS, a RowSet (row_set) or a plain sequence of global ids: the rows of `seen` are never returned (a
+        listening history of any length); with `only`, only its rows are ranked (a candidate set).  Mutually exclusive."""
+        return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales,
+                              seen=seen, only=only)
 
     def query_playlist_topn(self, local_rows, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None,
-                            scales=None) -> Tuple[np.ndarray, np.ndarray]:
+                            scales=None, seen=None, only=None) -> Tuple[np.ndarray, np.ndarray]:
         """The same for members given as rows of this handle; the members are never returned (whatever their weight)."""
-        return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales)
+        return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales,
+                              seen=seen, only=only)
 
-    def _playlist(self, members, topn, exclude, where, weights, level=None, labels=None, **more):
-        return _playlist_family(self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), members, topn, exclude, where,
-                                weights, level, labels=labels, **more)
+    def _playlist(self, members, topn, exclude, where, weights, level=None, labels=None, seen=None, only=None, **more):
+        return self._with_set(seen, only, lambda rowset: _playlist_family(
+            self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), members, topn, exclude, where, weights, level,
+            labels=labels, rowset=rowset, **more))
 
     # ---- DISTANCE REQUESTS (include/mi355rec_diag.h): the nearest rows by Euclidean distance ----
     def query_nearest(self, members, topn: int, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
@@ -625,29 +732,35 @@ class CosineEngine:
         return _distance_request(self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), _np_rows(rows), topn,
                                  exclude, where, labels)
 
-    def query_nearest_scaled(self, members, topn: int, scales, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
-        """query_nearest with FEATURE SCALES (`scales` as in query_mean_topn): the distances are taken between the scaled
-        members and the scaled rows; the filter still tests the stored rows."""
-        return _distance_request(self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), _np_members(members), topn,
-                                 exclude, where, labels, scales)
+    def query_nearest_scaled(self, members, topn: int, scales, exclude=None, where=None, labels=None, seen=None,
+                             only=None) -> Tuple[np.ndarray, np.ndarray]:
+        """query_nearest with FEATURE SCALES (`scales` as in query_mean_topn; None: none): the distances are taken between the
+        scaled members and the scaled rows; the filter still tests the stored rows.  `seen` / `only`: ROW SETS, as in
+        query_mean_topn (query_nearest itself keeps its parameter list)."""
+        return self._nearest(_np_members(members), topn, scales, exclude, where, labels, seen, only)
 
-    def query_nearest_rows_scaled(self, rows, topn: int, scales, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
-        """query_nearest_rows with FEATURE SCALES."""
-        return _distance_request(self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), _np_rows(rows), topn,
-                                 exclude, where, labels, scales)
+    def query_nearest_rows_scaled(self, rows, topn: int, scales, exclude=None, where=None, labels=None, seen=None,
+                                  only=None) -> Tuple[np.ndarray, np.ndarray]:
+        """query_nearest_rows with FEATURE SCALES and ROW SETS."""
+        return self._nearest(_np_rows(rows), topn, scales, exclude, where, labels, seen, only)
+
+    def _nearest(self, members, topn, scales, exclude, where, labels, seen, only):
+        return self._with_set(seen, only, lambda rowset: _distance_request(
+            self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), members, topn, exclude, where, labels, scales, rowset))
 
     # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h): MMR picks from the top-`pool` of the weighted playlist call ----
-    def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False, labels=None, prior_weight=None):
+    def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False,
+                                labels=None, prior_weight=None, seen=None, only=None):
         """`topn` rows picked greedily from the `pool` most relevant (query_mean_topn's order): each pick maximises
         lam * relevance - (1 - lam) * (its largest similarity to a row already picked).  Pick order; scores = relevance."""
         return self._playlist(_np_members(queries), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr,
-                              labels=labels, prior_weight=prior_weight)
+                              labels=labels, prior_weight=prior_weight, seen=seen, only=only)
 
     def query_playlist_topn_diverse(self, local_rows, topn: int, lam, pool=None, exclude=None, where=None, weights=None,
-                                    return_mmr=False, labels=None, prior_weight=None):
+                                    return_mmr=False, labels=None, prior_weight=None, seen=None, only=None):
         """The same for members given as rows of this handle (never returned)."""
         return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr,
-                              labels=labels, prior_weight=prior_weight)
+                              labels=labels, prior_weight=prior_weight, seen=seen, only=only)
 
     def set_groups(self, groups) -> None:
         """One group id per row (GROUP CAPS): >= 0 a group (an artist, say), -1 = never capped; None drops the groups."""
@@ -666,17 +779,19 @@ class CosineEngine:
         capi.check(self._lib.mi355rec_set_priors(self._h, p.ctypes.data_as(ctypes.c_void_p), int(p.size)), self._h)
 
     def query_mean_topn_capped(self, queries, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
-                               weights=None, return_mmr=False, return_pool_rows=False, labels=None, prior_weight=None):
+                               weights=None, return_mmr=False, return_pool_rows=False, labels=None, prior_weight=None,
+                               seen=None, only=None):
         """query_mean_topn_diverse with at most `max_per_group` results per group of set_groups (GROUP CAPS)."""
         return self._playlist(_np_members(queries), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
                               max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows,
-                              labels=labels, prior_weight=prior_weight)
+                              labels=labels, prior_weight=prior_weight, seen=seen, only=only)
 
     def query_playlist_topn_capped(self, local_rows, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
-                                   weights=None, return_mmr=False, return_pool_rows=False, labels=None, prior_weight=None):
+                                   weights=None, return_mmr=False, return_pool_rows=False, labels=None, prior_weight=None,
+                                   seen=None, only=None):
         return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
                               max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows,
-                              labels=labels, prior_weight=prior_weight)
+                              labels=labels, prior_weight=prior_weight, seen=seen, only=only)
 
     def fetch_rows(self, local_rows) -> np.ndarray:
         """The features of the listed rows (any order, duplicates allowed), gathered on the device: (len, 12) float32."""
@@ -692,7 +807,7 @@ class CosineEngine:
         return {"queries": q.value, "rows_exact": r.value}
 
 
-class NodeEngine:
+class NodeEngine(_RowSets):
     """The catalogue on the GPUs of one node driven by ONE process (mi355rec_create_placed): what the C++
     Recommender shim uses.  `placement`: capi.PLACEMENT_SHARDED (rows split over the devices; the default),
     PLACEMENT_REPLICATED (every device holds all rows and serves whole windows of the stream).
@@ -721,8 +836,16 @@ class NodeEngine:
         if rc != capi.OK:
             raise capi.Mi355Error(rc, (self._lib.mi355rec_sharded_last_error(self._h) or b"").decode("utf-8", "replace"))
 
+    def row_set(self, ids) -> RowSet:
+        """A ROW SET of this node handle from global ids (0 <= id < rows), usable on it as `seen=` or `only=`."""
+        return RowSet(self, ids, self._lib.mi355rec_sharded_rowset_create)
+
+    def _set_check(self, rc: int) -> None:
+        self._check(rc)
+
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h:
+            self._close_sets()
             self._lib.mi355rec_sharded_destroy(self._h)
             self._h = ctypes.c_void_p()
 
@@ -808,16 +931,19 @@ class NodeEngine:
 
     # ---- PLAYLISTS (include/mi355rec_diag.h) over the whole node ----
     def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None,
-                        scales=None) -> Tuple[np.ndarray, np.ndarray]:
-        return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales)
+                        scales=None, seen=None, only=None) -> Tuple[np.ndarray, np.ndarray]:
+        return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales,
+                              seen=seen, only=only)
 
     def query_playlist_topn(self, global_rows, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None,
-                            scales=None) -> Tuple[np.ndarray, np.ndarray]:
-        return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales)
+                            scales=None, seen=None, only=None) -> Tuple[np.ndarray, np.ndarray]:
+        return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales,
+                              seen=seen, only=only)
 
-    def _playlist(self, members, topn, exclude, where, weights, level=None, labels=None, **more):
-        return _playlist_family(self._lib, "mi355rec_sharded_", self._h, self._check, members, topn, exclude, where, weights, level,
-                                labels=labels, **more)
+    def _playlist(self, members, topn, exclude, where, weights, level=None, labels=None, seen=None, only=None, **more):
+        return self._with_set(seen, only, lambda rowset: _playlist_family(
+            self._lib, "mi355rec_sharded_", self._h, self._check, members, topn, exclude, where, weights, level, labels=labels,
+            rowset=rowset, **more))
 
     # ---- DISTANCE REQUESTS (include/mi355rec_diag.h) over the whole node ----
     def query_nearest(self, members, topn: int, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
@@ -828,14 +954,19 @@ class NodeEngine:
         """The same for members given as global rows (never returned)."""
         return _distance_request(self._lib, "mi355rec_sharded_", self._h, self._check, _np_rows(rows), topn, exclude, where, labels)
 
-    def query_nearest_scaled(self, members, topn: int, scales, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
-        """query_nearest with FEATURE SCALES (12 floats or {feature index or name: scale})."""
-        return _distance_request(self._lib, "mi355rec_sharded_", self._h, self._check, _np_members(members), topn, exclude, where, labels,
-                                 scales)
+    def query_nearest_scaled(self, members, topn: int, scales, exclude=None, where=None, labels=None, seen=None,
+                             only=None) -> Tuple[np.ndarray, np.ndarray]:
+        """query_nearest with FEATURE SCALES (12 floats or {feature index or name: scale}; None: none) and ROW SETS."""
+        return self._nearest(_np_members(members), topn, scales, exclude, where, labels, seen, only)
 
-    def query_nearest_rows_scaled(self, rows, topn: int, scales, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
-        """query_nearest_rows with FEATURE SCALES."""
-        return _distance_request(self._lib, "mi355rec_sharded_", self._h, self._check, _np_rows(rows), topn, exclude, where, labels, scales)
+    def query_nearest_rows_scaled(self, rows, topn: int, scales, exclude=None, where=None, labels=None, seen=None,
+                                  only=None) -> Tuple[np.ndarray, np.ndarray]:
+        """query_nearest_rows with FEATURE SCALES and ROW SETS."""
+        return self._nearest(_np_rows(rows), topn, scales, exclude, where, labels, seen, only)
+
+    def _nearest(self, members, topn, scales, exclude, where, labels, seen, only):
+        return self._with_set(seen, only, lambda rowset: _distance_request(
+            self._lib, "mi355rec_sharded_", self._h, self._check, members, topn, exclude, where, labels, scales, rowset))
 
     # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h) over the whole node ----
     def set_groups(self, groups) -> None:
@@ -855,25 +986,28 @@ class NodeEngine:
         self._check(self._lib.mi355rec_sharded_set_priors(self._h, p.ctypes.data_as(ctypes.c_void_p), int(p.size)))
 
     def query_mean_topn_capped(self, queries, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
-                               weights=None, return_mmr=False, return_pool_rows=False, labels=None, prior_weight=None):
+                               weights=None, return_mmr=False, return_pool_rows=False, labels=None, prior_weight=None,
+                               seen=None, only=None):
         return self._playlist(_np_members(queries), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
                               max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows,
-                              labels=labels, prior_weight=prior_weight)
+                              labels=labels, prior_weight=prior_weight, seen=seen, only=only)
 
     def query_playlist_topn_capped(self, global_rows, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
-                                   weights=None, return_mmr=False, return_pool_rows=False, labels=None, prior_weight=None):
+                                   weights=None, return_mmr=False, return_pool_rows=False, labels=None, prior_weight=None,
+                                   seen=None, only=None):
         return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
                               max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows,
-                              labels=labels, prior_weight=prior_weight)
+                              labels=labels, prior_weight=prior_weight, seen=seen, only=only)
 
-    def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False, labels=None, prior_weight=None):
+    def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False,
+                                labels=None, prior_weight=None, seen=None, only=None):
         return self._playlist(_np_members(queries), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr,
-                              labels=labels, prior_weight=prior_weight)
+                              labels=labels, prior_weight=prior_weight, seen=seen, only=only)
 
     def query_playlist_topn_diverse(self, global_rows, topn: int, lam, pool=None, exclude=None, where=None, weights=None,
-                                    return_mmr=False, labels=None, prior_weight=None):
+                                    return_mmr=False, labels=None, prior_weight=None, seen=None, only=None):
         return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr,
-                              labels=labels, prior_weight=prior_weight)
+                              labels=labels, prior_weight=prior_weight, seen=seen, only=only)
 
     def scores_row(self, global_row: int) -> np.ndarray:
         out = np.empty(self.rows, dtype=np.float32)
