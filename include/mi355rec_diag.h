@@ -155,6 +155,46 @@ int mi355rec_rebuild_replica(mi355rec_t* h);
  * the exact chain.  Either pointer may be NULL. */
 int mi355rec_replica_counters(mi355rec_t* h, int64_t* scans, int64_t* rescored_rows);
 
+/* THE CUTOFF SAMPLE of a single query over the 8-bit replica (csrc/replica_q8.hip.h).  Every such query starts from a lower
+ * bound of its topn-th score, taken from the exact scores of a sample of rows.
+ *   STRIDED:  256 evenly spaced regions of 2048 rows (5 % of a 10 M-row shard, 6.3 MB per query), one value per 256 rows;
+ *   BUCKETED: built once beside the replica — up to 1024 strided regions (a fifth of the rows) grouped by direction (the
+ *             nearest of as many centroid rows) and kept as a contiguous copy in that order; a query reads the 32 regions
+ *             whose buckets lie nearest to it (0.8 MB), one value per 64 rows.  +16 B per base row of device memory (32 MB
+ *             at 10 M rows) and the build time mi355rec_bucket_sample_info reports.  INVALID_ARG where the handle has no
+ *             such structure: shards whose 8-bit scan does not take exact sample values (under ~2.1 M rows on a 256-CU
+ *             device) or created without a replica;
+ *   AUTO (default): BUCKETED for topn <= 128 on shards of at least MI355REC_SAMPLE_AUTO_MIN_ROWS rows that have the
+ *             structure, for the queries of a stream whose sample rides in the launch before; STRIDED otherwise — also for
+ *             a query alone and the first of a stream, whose sample launch is on the critical path (5.4 us strided, 14.3
+ *             bucketed) (measured, two lanes, top-100 / top-10 in us per query, strided -> bucketed:
+ *             2.5 M rows 7.92 -> 8.0 / 7.22 -> 7.15, 4 M 8.35 -> 8.61 / 8.18 -> 8.44, 5 M 9.5 -> 9.23 / 9.2 -> 9.46,
+ *             6 M 10.92 -> 10.35 / 10.35 -> 10.33, 7.5 M 13.17 -> 12.42 / 12.5 -> 12.03, 10 M 16.5 -> 15.75 / 16.17 -> 15.75).
+ * Either way the sample only places the bound: results are those of the exact chain, bit for bit.  The mode belongs to the
+ * handle (a lane has its own) and applies from the next query's sample on; a node handle's shards each decide for themselves. */
+#define MI355REC_SAMPLE_AUTO 0
+#define MI355REC_SAMPLE_STRIDED 1
+#define MI355REC_SAMPLE_BUCKETED 2
+#define MI355REC_SAMPLE_AUTO_MIN_ROWS 6000000
+int mi355rec_set_sample(mi355rec_t* h, int mode);
+typedef struct {
+    int64_t base_rows;        /* rows of the base (0: the handle has no bucketed sample)                          */
+    int32_t regions;          /* 2048-row regions of the ordered base                                            */
+    int32_t centroids;        /* buckets: centroid i is local row i * centroid_stride + centroid_stride / 2      */
+    int64_t bytes;            /* device memory of the structure                                                   */
+    int64_t stride_rows;      /* base region g is local rows [g * stride_rows, g * stride_rows + 2048)            */
+    int64_t centroid_stride;
+    int32_t picks;            /* regions a query reads                                                            */
+    int32_t mode;             /* MI355REC_SAMPLE_AUTO / _STRIDED / _BUCKETED as set                               */
+    int32_t last_used;        /* _STRIDED or _BUCKETED: what the last query over the 8-bit replica took; 0: none yet */
+    float build_ms;           /* host wall time of building it (inside create / mi355rec_rebuild_replica)         */
+} mi355rec_bucket_sample_info_t;
+int mi355rec_bucket_sample_info(const mi355rec_t* h, mi355rec_bucket_sample_info_t* out);
+/* Copies the structure to the host: rows_out[regions * 2048] = the local row of every entry in (bucket, row) order (-1:
+ * padding), region_tab_out[regions * 2] = the buckets of each region's first and last entry.  Either may be NULL.
+ * INVALID_ARG where the handle has none.  Synchronises the handle's stream. */
+int mi355rec_bucket_sample_rows(mi355rec_t* h, int32_t* rows_out, int32_t* region_tab_out);
+
 /* What mi355rec_create_lane found when it chose the lane's stream: it times a small kernel on the parent's stream alone and
  * on both streams at once, and replaces the lane's stream (each new stream is bound to the next hardware queue) until the pair
  * runs side by side.  *stream_attempts = streams tried (0 on a handle that is not a lane); *overlaps_parent = 1 side by side,
@@ -861,8 +901,8 @@ int mi355rec_sharded_query_distance_request_ext(mi355rec_sharded_t* h, const mi3
  *                   overwritten with the most hostile values an EARLIER query could have left (a perfect score, a
  *                   cutoff of +1.0) under the epochs of the last queries;
  *   DROP_STORES     the next sampling launch (the seed riders of a streamed launch, or the sample launch of a batch on
- *                   its own / at the head of a stream) does not store the first half of its regions (whoever selects
- *                   the cutoffs then reads whatever was there before);
+ *                   its own / at the head of a stream) does not store the first half of its regions — riders that take the
+ *                   BUCKETED sample store nothing at all — (whoever selects the cutoffs then reads whatever was there before);
  *   NO_LAST_RIDER   the next sampling launch is told a wrong arrival count, so none of its workgroups selects a cutoff
  *                   (the pass behind it then finds whatever cutoff was there before).
  * Never needed in production and NOT in the product library: declared and compiled only with -DMI355REC_TEST_HOOKS

@@ -20,6 +20,8 @@ DIM = 12
 MAX_TOPN_FAST = 1024
 BATCH_AUTO, BATCH_MULTI, BATCH_MFMA, BATCH_HALF, BATCH_Q8, BATCH_MFMA_NOSKIP = 0, 1, 2, 3, 4, 5
 REPLICA_AUTO, REPLICA_OFF, REPLICA_ON, REPLICA_FP16 = 0, 1, 2, 3
+SAMPLE_AUTO, SAMPLE_STRIDED, SAMPLE_BUCKETED = 0, 1, 2   # mi355rec_set_sample
+SAMPLE_AUTO_MIN_ROWS = 6_000_000
 TRANSPORT_PEER, TRANSPORT_RCCL = 1, 2
 PLACEMENT_AUTO, PLACEMENT_SHARDED, PLACEMENT_REPLICATED, PLACEMENT_CPU = 0, 1, 2, 3
 CREATE_NO_REPLICA = 1
@@ -83,6 +85,11 @@ class RequestExt(ctypes.Structure):
     """mi355rec_request_ext_t (include/mi355rec_diag.h, ROW SETS): the per-request extras beside the two request structs; `size` is
     sizeof of this struct (24).  feature_scales: NULL or 12 floats; rowset: NULL or a mi355rec_rowset_t*."""
     _fields_ = [("size", c_uint32), ("rowset_mode", c_uint32), ("feature_scales", c_void_p), ("rowset", c_void_p)]
+
+
+class BucketSampleInfo(ctypes.Structure):   # mi355rec_bucket_sample_info_t
+    _fields_ = [("base_rows", c_int64), ("regions", c_int32), ("centroids", c_int32), ("bytes", c_int64), ("stride_rows", c_int64),
+                ("centroid_stride", c_int64), ("picks", c_int32), ("mode", c_int32), ("last_used", c_int32), ("build_ms", c_float)]
 
 
 class Stats(ctypes.Structure):
@@ -157,6 +164,9 @@ SIGNATURES = {
     "mi355rec_set_replica": (c_int, [c_void_p, c_int]),
     "mi355rec_rebuild_replica": (c_int, [c_void_p]),
     "mi355rec_replica_counters": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),
+    "mi355rec_set_sample": (c_int, [c_void_p, c_int]),
+    "mi355rec_bucket_sample_info": (c_int, [c_void_p, c_void_p]),
+    "mi355rec_bucket_sample_rows": (c_int, [c_void_p, c_void_p, c_void_p]),
     "mi355rec_batched_last_counters": (c_int, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64),
                                                POINTER(c_int32)]),
     "mi355rec_batched_pass2_pairs": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),

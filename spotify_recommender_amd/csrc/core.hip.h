@@ -209,6 +209,22 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t x) {
 
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t x) { return ~wave_max_u32(~x); }
 
+// The same per DPP ROW: the max over the 16 lanes a lane shares its row with, returned in every lane of that row.
+__device__ __forceinline__ uint32_t row16_max_u32(uint32_t x) {
+    auto mx = [](uint32_t a, uint32_t b) { return a > b ? a : b; };
+    x = mx(x, static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), 0x111, 0xf, 0xf, true)));
+    x = mx(x, static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), 0x112, 0xf, 0xf, true)));
+    x = mx(x, static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), 0x114, 0xf, 0xf, true)));
+    x = mx(x, static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), 0x118, 0xf, 0xf, true)));
+    // (lane 15 of every row holds the row's max: four scalar reads, one select per lane)
+    const uint32_t r0 = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), 15));
+    const uint32_t r1 = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), 31));
+    const uint32_t r2 = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), 47));
+    const uint32_t r3 = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), 63));
+    const unsigned row = (threadIdx.x & 63u) >> 4;
+    return row == 0u ? r0 : (row == 1u ? r1 : (row == 2u ? r2 : r3));
+}
+
 // Every thread of the workgroup calls this with its share of the keys in
 // registers (0 = empty slot; keys are unique).  Precondition: at least `need`
 // non-empty keys in total, need >= 1.  Returns T with |{key >= T}| >= need;

@@ -31,6 +31,40 @@ int single_kind(const mi355rec* h, const uint64_t* upper_dev) {
 // where the extra fetch per sampled wave is not on the launch's critical path.
 bool q8_exact_sample(const mi355rec* h) { return h->geom[kQ8].iters >= 3; }
 
+// Which sample the next query over `kind` rows takes (mi355rec_set_sample): the bucketed one (replica_q8.hip.h) where the handle
+// has the structure and was told to, or — AUTO — for topn <= 128 on shards of MI355REC_SAMPLE_AUTO_MIN_ROWS rows and more
+// where the sample is CARRIED by the riders of the launch before.  (Only top-10 and top-100 were modelled: 1024 values of
+// which the topn-th is wanted.  A sample launch of its own — a query alone, the first of a stream — is on the query's critical
+// path, and there the strided sample's one round trip in 256 workgroups beats the bucketed one's chain of four in eight:
+// 5.4 against 14.3 us, 42.0 against 48.4 us for a lone query at 10 M rows.)
+constexpr int kBucketAutoMaxTopn = 128;
+bool use_bucket(const mi355rec* h, int kind, int topn, bool carried) {
+    if (kind != kQ8 || !h->bsample.rows || !q8_exact_sample(h) || h->sample_mode == MI355REC_SAMPLE_STRIDED) return false;
+    if (h->sample_mode == MI355REC_SAMPLE_BUCKETED) return true;
+    return carried && topn <= kBucketAutoMaxTopn && h->n >= MI355REC_SAMPLE_AUTO_MIN_ROWS;
+}
+BucketSample bucket_arg(const mi355rec* h) {
+    const BucketBufs& b = h->bsample;
+    BucketSample bs;
+    std::memset(&bs, 0, sizeof bs);
+    bs.q8 = static_cast<const uint4*>(b.q8);
+    bs.rows = b.rows;
+    bs.centroids = b.centroids;
+    bs.region_tab = reinterpret_cast<const int2*>(b.region_tab);
+    bs.regions = b.regions;
+    bs.n_centroids = b.n_centroids;
+    bs.picks = b.regions < kBucketPicks ? b.regions : kBucketPicks;
+    return bs;
+}
+// The geometry of a streamed launch over `kind` rows whose riders take the next query's sample, bucketed or not.
+const ScanGeom& stream_geom(const mi355rec* h, int kind, bool next_bucketed) { return next_bucketed ? h->geom_bucket : h->geom[kind]; }
+// How many sample values a scan over the 8-bit replica selects from, negative where they are exact scores (scan_q8_kernel).
+int q8_seed_count(const mi355rec* h, bool bucketed) {
+    if (bucketed) return -(kBucketPicks * kBucketGroups);
+    const int n_seed = h->geom[kQ8].seed_grid * kHalfSeedWaves;
+    return q8_exact_sample(h) ? -n_seed : n_seed;
+}
+
 // Does a neighbourhood give the scan a bound (handoff.hip.h)?  Around the row the query excludes when that is a row of THIS
 // shard, else (a query by value, a row of another shard) around the query's anchor — on every shard large enough to have one.
 bool nbhd_applies(const mi355rec* h, int64_t exclude_global) {
@@ -71,7 +105,7 @@ NextSeed no_next_seed() {
 // counts up from `ctl_done` and is never reset.  The test hooks of mi355rec_debug_handoff apply to ONE sampling
 // launch: this one.
 NextSeed make_next_seed(mi355rec* h, int kind, int wgs, bool nbhd, const float* qptr, const float* query12, int64_t exclude_global,
-                        int topn, uint32_t epoch, unsigned long long* out, SeedCtl* ctl, unsigned ctl_done) {
+                        int topn, uint32_t epoch, unsigned long long* out, SeedCtl* ctl, unsigned ctl_done, bool bucketed = false) {
     const ScanGeom& g = h->geom[kind];
     NextSeed sd = no_next_seed();
     sd.anchors = h->d_anchor;
@@ -86,6 +120,7 @@ NextSeed make_next_seed(mi355rec* h, int kind, int wgs, bool nbhd, const float* 
     sd.ctl = wgs > 0 ? ctl : nullptr;
     sd.topk = topn;
     sd.exact = kind == kQ8 && q8_exact_sample(h);
+    if (bucketed) sd.bucket = bucket_arg(h);   // (its values are exact scores: use_bucket)
     sd.epoch = epoch;
     if (sd.ctl) sd.done_base = ctl_done + (h->dbg_no_last ? 0x40000000u : 0u);
     sd.debug_skip = h->dbg_skip_regions;
@@ -98,15 +133,22 @@ NextSeed make_next_seed(mi355rec* h, int kind, int wgs, bool nbhd, const float* 
 // when the excluded row is a row of this shard, one more workgroup for its neighbourhood.  The values are tagged with
 // `epoch`, which the scan that reads them is given as well.
 void enqueue_half_seed(mi355rec* h, int kind, const float* qptr, const float* query12, int64_t exclude_global, int topn,
-                       unsigned long long* seed_buf, uint32_t epoch, hipStream_t s) {
+                       unsigned long long* seed_buf, uint32_t epoch, hipStream_t s, bool bucketed = false) {
     const ScanGeom& g = h->geom[kind];
     const QueryArg qa = make_query_arg(h, qptr, query12);
     if (kind == kQ8) {
         const int extra = nbhd_applies(h, exclude_global) ? 1 : 0;
-        if (g.seed_grid + extra <= 0) return;
-        hipLaunchKernelGGL(seed_q8_kernel, dim3(g.seed_grid + extra), dim3(kHalfSeedBlock), 0, s, h->d_feats, h->d_q8, h->n,
-                           g.seed_stride, h->row_base, qa, qptr, exclude_global, seed_buf, epoch, g.seed_grid, topn,
-                           static_cast<const float*>(h->d_anchor), q8_exact_sample(h));
+        BucketSample bs;
+        std::memset(&bs, 0, sizeof bs);
+        int wgs = g.seed_grid;
+        if (bucketed) {   // a handful of workgroups share its regions, kBucketAhead each per round trip
+            bs = bucket_arg(h);
+            wgs = (bs.picks + kBucketAhead - 1) / kBucketAhead;
+        }
+        if (wgs + extra <= 0) return;
+        hipLaunchKernelGGL(seed_q8_kernel, dim3(wgs + extra), dim3(kHalfSeedBlock), 0, s, h->d_feats, h->d_q8, h->n,
+                           g.seed_stride, h->row_base, qa, qptr, exclude_global, seed_buf, epoch, wgs, topn,
+                           static_cast<const float*>(h->d_anchor), q8_exact_sample(h), bs);
         return;
     }
 #ifdef MI355REC_EXPERIMENTS
@@ -138,6 +180,7 @@ bool enqueue_f32_seed(mi355rec* h, const float* qptr, const float* query12, int6
 // kind's own (launch_scan).
 struct ScanLaunch {
     int kind = kFp32;                           // which rows it streams
+    bool bucketed = false;                      // 8-bit replica: the query's sample is the bucketed one (what `sample` holds)
     bool streamed = false;                      // one workgroup behind the scanners merges `prev`, and `next` may ask for more
     int grid = 0;                               // workgroups in all ...
     int iters = 0;                              // ... and the tiles of a scanning one
@@ -159,8 +202,7 @@ int launch_scan(mi355rec* h, const ScanLaunch& L, const float* qptr, const float
     const dim3 grid(static_cast<unsigned>(L.grid));
     const bool fused = L.tail.counters != nullptr;
     if (L.kind == kQ8) {
-        const int n_seed = h->geom[kQ8].seed_grid * kHalfSeedWaves;
-        const int q8_seeds = q8_exact_sample(h) ? -n_seed : n_seed;   // (negative: exact values)
+        const int q8_seeds = q8_seed_count(h, L.bucketed);   // (negative: exact values)
         by_query_form(qptr, [&](auto from_row, const float* qp) {
             constexpr bool kRow = decltype(from_row)::value;
             auto launch = [&](auto kernel) {
@@ -244,7 +286,9 @@ int enqueue_scan(mi355rec* h, const float* qptr, const float* query12,
     if (L.kind != kFp32) {
         if (L.kind == kQ8) L.epoch = next_epoch(h);
         L.sample = h->d_half_seed;
-        enqueue_half_seed(h, L.kind, qptr, query12, exclude_global, topn, h->d_half_seed, L.epoch, s);
+        L.bucketed = use_bucket(h, L.kind, topn, false);
+        if (L.kind == kQ8) h->last_sample = L.bucketed ? MI355REC_SAMPLE_BUCKETED : MI355REC_SAMPLE_STRIDED;
+        enqueue_half_seed(h, L.kind, qptr, query12, exclude_global, topn, h->d_half_seed, L.epoch, s, L.bucketed);
         if (L.kind == kQ8 && lone && h->n >= kLoneFusedMinRows) {
             L.tail = *lone;   // ... whose arrival counters start this launch from
             for (unsigned g = 0; g < 9u; ++g) L.tail.base[g] = h->lone_base[g];
@@ -387,7 +431,8 @@ int flush_streamed(mi355rec* h, hipStream_t s) {
 int launch_stashed(mi355rec* h, hipStream_t s, bool with_next, const float* next_ptr, const float* next_q,
                    int64_t next_exclude, int next_topn, int next_buf, uint32_t next_epoch_tag) {
     auto& st = h->stashed;
-    const ScanGeom& g = h->geom[st.kind];
+    const bool next_bucketed = with_next && use_bucket(h, st.kind, next_topn, h->geom_bucket.riders > 0);
+    const ScanGeom& g = stream_geom(h, st.kind, next_bucketed);
     // The fp32 scan's riding merger keeps 2048 survivors; with ~770 lists and topN near 1000 about
     // 2.2 topN keys survive its first cut, and an overflow drops into the exact radix select over all
     // keys in global memory (correct, ~1 ms).  Such a query's merge gets its own launch instead.
@@ -406,13 +451,15 @@ int launch_stashed(mi355rec* h, hipStream_t s, bool with_next, const float* next
         scanners = g.r_scan;
         L.iters = g.r_iters;
         L.next = make_next_seed(h, st.kind, g.riders, g.nbhd, next_ptr, next_q, next_exclude, next_topn, next_epoch_tag,
-                                h->d_stream_seed[next_buf], g.hoists ? h->d_stream_ctl + next_buf : nullptr, h->ctl_done[next_buf]);
+                                h->d_stream_seed[next_buf], g.hoists ? h->d_stream_ctl + next_buf : nullptr, h->ctl_done[next_buf],
+                                next_bucketed);
     }
     L.grid = scanners + 1 + L.next.n_wgs + L.next.nbhd;
     L.lists = h->d_stream_lists[buf];
     L.sample = h->d_stream_seed[st.seed_buf];
     L.bound = st.cutoff_ready ? &h->d_stream_ctl[st.seed_buf].cutoff : nullptr;
     L.epoch = st.epoch;
+    L.bucketed = st.bucketed;
     const int rc = launch_scan(h, L, st.qptr, st.q, st.exclude, st.topn, s);
     if (rc) return rc;
     // (the books move only once the launch is known to have been accepted; the riders' arrival counter counts up
@@ -443,24 +490,28 @@ int enqueue_streamed(mi355rec* h, const float* qptr, const float* query12, int64
     int seed_buf = 0;
     bool sampled = false, nbhd_taken = false;
     const uint32_t epoch = next_epoch(h);   // the tag of this query's sample values and bound
+    // (carried: the launch of the stashed query has riders for this one — what launch_stashed decides by as well)
+    const bool bucketed = use_bucket(h, kind, topn, h->stashed.has && h->stashed.kind == kind && h->geom_bucket.riders > 0);
+    const ScanGeom& ng = stream_geom(h, kind, bucketed);   // of the launch that carries THIS query's sample
+    if (kind == kQ8) h->last_sample = bucketed ? MI355REC_SAMPLE_BUCKETED : MI355REC_SAMPLE_STRIDED;
     if (h->stashed.has) {
         seed_buf = 1 - h->stashed.seed_buf;
         // the riders of a launch sample the rows that launch scans: a change of rows (mi355rec_set_replica) between two
         // calls costs the next query a sample launch of its own
         const bool same = h->stashed.kind == kind;
-        sampled = same && h->geom[kind].riders > 0;
-        nbhd_taken = same && h->geom[kind].nbhd;
+        sampled = same && ng.riders > 0;
+        nbhd_taken = same && ng.nbhd;
         rc = launch_stashed(h, s, same, qptr, query12, exclude_global, topn, seed_buf, epoch);
         if (rc) return rc;
     }
-    bool bound_ready = sampled && h->geom[kind].hoists;
+    bool bound_ready = sampled && ng.hoists;
     if (!sampled) {   // first query of a stream, or a shard too small to spare riders
         if (kind == kFp32) {
             if (h->n >= kF32LoneSeedMinRows)
                 bound_ready = enqueue_f32_seed(h, qptr, query12, exclude_global, topn, h->d_stream_seed[seed_buf], h->d_stream_ctl + seed_buf,
                                                &h->ctl_done[seed_buf], epoch, s);
         } else if (!nbhd_taken) {
-            enqueue_half_seed(h, kind, qptr, query12, exclude_global, topn, h->d_stream_seed[seed_buf], epoch, s);
+            enqueue_half_seed(h, kind, qptr, query12, exclude_global, topn, h->d_stream_seed[seed_buf], epoch, s, bucketed);
         }
         HIP_TRY(h, hipGetLastError());
     }
@@ -474,6 +525,7 @@ int enqueue_streamed(mi355rec* h, const float* qptr, const float* query12, int64
     st.seed_buf = seed_buf;
     st.epoch = epoch;
     st.kind = kind;
+    st.bucketed = bucketed;
     st.cutoff_ready = bound_ready;
     return MI355REC_OK;
 }

@@ -20,12 +20,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <atomic>
+#include <chrono>
 #include <new>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "batched.hip.h"
+#include "bucket_sample.h"
 #include "kernels.hip.h"
 #include "replica.hip.h"
 #include "replica_q8.hip.h"
@@ -84,6 +86,23 @@ struct ScanGeom {
 
 }  // namespace
 
+// The bucketed sample of the 8-bit scan (replica_q8.hip.h, "the bucketed sample"): built beside the 8-bit replica, shared by a
+// group of lanes and freed like d_q8.  rows == null: the handle has none.
+struct BucketBufs {
+    void* q8 = nullptr;           // regions x 2048 x 12 B: the base rows' replica entries in (bucket, row) order
+    int32_t* rows = nullptr;      // regions x 2048 local rows (-1: padding)
+    float* centroids = nullptr;   // n_centroids x 12 floats
+    int32_t* region_tab = nullptr;   // regions x (first bucket, last bucket)
+    int regions = 0, n_centroids = 0;
+    int64_t base_rows = 0;        // real entries
+    int64_t stride = 0;           // rows between the starts of the base's strided regions
+    int64_t centroid_stride = 0;  // centroid i is local row i * centroid_stride + centroid_stride / 2
+    float build_ms = 0.f;         // host wall time of building it (assignment, sort, gather)
+    int64_t bytes() const {
+        return rows ? static_cast<int64_t>(regions) * 2048 * (12 + 4) + static_cast<int64_t>(n_centroids) * 48 + static_cast<int64_t>(regions) * 8 : 0;
+    }
+};
+
 struct mi355rec_labels;   // the label-grouped copy of a shard's rows (engine_labels.hip.h, mi355rec_set_labels)
 struct mi355rec_playlist;   // the buffers of the playlist calls (engine_playlist.hip.h)
 
@@ -110,6 +129,7 @@ struct mi355rec {
         void* owned_feats = nullptr;
         void* d_half = nullptr;
         void* d_q8 = nullptr;
+        BucketBufs bsample;                            // the bucketed sample that goes with d_q8
         float margin_mix = 0.0f, margin_mfma = 0.0f;   // of the replicas above (half_selfcheck_kernel's verdict)
         RowSide side;                                  // what the first handle's setters had left when its first lane was made
     };
@@ -129,6 +149,10 @@ struct mi355rec {
 
     int cus = 0;
     ScanGeom geom[3];                   // by the kind of rows a single-query scan streams: kFp32, kFp16, kQ8
+    ScanGeom geom_bucket;               // kQ8's, for a streamed launch whose riders take the BUCKETED sample (fewer riders)
+    BucketBufs bsample;                 // the bucketed sample (a group of lanes shares it, like d_q8)
+    int sample_mode = 0;                // MI355REC_SAMPLE_AUTO / _STRIDED / _BUCKETED (mi355rec_set_sample)
+    int last_sample = 0;                // which sample the last query over the 8-bit replica took (0: none yet)
     // geometry of the multi-query pass (scan_multi_kernel)
     int mgrid = 0;
     int64_t mrows_per_block = 0;
@@ -194,6 +218,7 @@ struct mi355rec {
         uint32_t epoch = 0;             // the tag of its sample values and of its cutoff
         int kind = 0;                   // which rows its scan streams — and its sample was taken over: kFp32, kFp16 (experiment builds), kQ8
         bool cutoff_ready = false;      // ... by riders, whose last one left the launch-wide cutoff / bound in d_stream_ctl
+        bool bucketed = false;          // 8-bit replica: its sample is the bucketed one (replica_q8.hip.h)
     } stashed;
     unsigned long long* d_stream_seed[2] = {nullptr, nullptr};
     SeedCtl* d_stream_ctl = nullptr;    // [2]: rider count and finished cutoff beside each of d_stream_seed (8-bit replica)
@@ -493,6 +518,26 @@ void plan_half_grid(mi355rec* h) {
     h->geom[kFp16].nbhd = h->geom[kFp16].hoists = false;   // (its riders only take the sample; r_scan still leaves the slot)
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, scan_q8_kernel<Q8Config, true, false>, Q8Config::kBlock, 0) != hipSuccess) occ = 1;
     h->geom[kQ8] = plan_replica(h, occ, Q8Config::kTileRows, 4, 2.1);
+    // The bucketed sample (replica_q8.hip.h) is kBucketPicks regions, four per rider in flight: a handful of riders, one
+    // round each, and the workgroups that frees go to the scanners.
+    ScanGeom& b = h->geom_bucket;
+    b = h->geom[kQ8];
+    if (b.riders > 0) {
+        int riders = (kBucketPicks + kBucketAhead - 1) / kBucketAhead;
+        if (riders > b.riders) riders = b.riders;
+        const int64_t tiles = (h->n + Q8Config::kTileRows - 1) / Q8Config::kTileRows;
+        b.riders = riders;
+        b.r_scan = b.grid - 2 - riders;
+        b.r_iters = static_cast<int>((tiles + b.r_scan - 1) / b.r_scan);
+        b.hoists = b.r_iters >= 5;
+    }
+}
+
+void free_bucket_bufs(BucketBufs& b) {
+    void* bufs[] = {b.q8, b.rows, b.centroids, b.region_tab};
+    for (void* p : bufs)
+        if (p) (void)hipFree(p);
+    b = BucketBufs();
 }
 
 void free_replica(mi355rec* h) {
@@ -509,6 +554,8 @@ void free_replica(mi355rec* h) {
     h->d_q8 = nullptr;
     h->d_half_mseed = nullptr;
     h->d_half_rescored = nullptr;
+    if (!(h->shared && h->shared->bsample.rows == h->bsample.rows)) free_bucket_bufs(h->bsample);
+    h->bsample = BucketBufs();
 }
 
 // The per-handle state that goes with a replica (sample values, cutoffs and arrival counters of the multi-query pass,
@@ -536,6 +583,7 @@ int alloc_replica_state(mi355rec* h) {
 // nothing: after a failure the handle has NO replica (d_half and everything keyed on it is null)
 // and keeps serving from the fp32 rows.
 int build_replica_inner(mi355rec* h);
+int build_bucket_sample(mi355rec* h);
 int build_replica(mi355rec* h) {
     const int rc = build_replica_inner(h);
     if (rc != MI355REC_OK) {
@@ -559,7 +607,8 @@ int build_replica_inner(mi355rec* h) {
                        h->d_feats, h->n, n_padded, reinterpret_cast<uint2*>(h->d_half));
     const int64_t n_quads4 = (h->n + 3) / 4 * 4;
     hipLaunchKernelGGL(q8_build_kernel, dim3(static_cast<unsigned>((n_quads4 + 255) / 256)), dim3(256), 0, h->stream,
-                       h->d_feats, h->n, n_quads4, reinterpret_cast<uint32_t*>(h->d_q8), static_cast<float*>(nullptr));
+                       h->d_feats, h->n, n_quads4, reinterpret_cast<uint32_t*>(h->d_q8), static_cast<float*>(nullptr),
+                       static_cast<const int32_t*>(nullptr), static_cast<const float*>(nullptr), 0, static_cast<int32_t*>(nullptr));
     if (timed) (void)hipEventRecord(b, h->stream);
     const hipError_t e = hipStreamSynchronize(h->stream);
     if (timed && e == hipSuccess) (void)hipEventElapsedTime(&h->replica_build_ms, a, b);
@@ -576,6 +625,67 @@ int build_replica_inner(mi355rec* h) {
     const bool cvt_kept = chk[1] > 2.9e-6f && chk[1] < 3.1e-6f;
     h->margin_mfma = (cvt_kept && chk[0] == 9.5367431640625e-07f) ? kBqMargin : kBqMarginFlush;
     h->margin_mix = (cvt_kept && chk[2] == 9.5367431640625e-07f && chk[3] == 9.5367431640625e-07f) ? kBqMargin : kBqMarginFlush;
+    if (build_bucket_sample(h) != MI355REC_OK) {   // optional: without it every query takes the strided sample
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(h->stream);
+        free_bucket_bufs(h->bsample);
+        if (h->sample_mode == MI355REC_SAMPLE_BUCKETED) h->sample_mode = MI355REC_SAMPLE_AUTO;
+    }
+    return MI355REC_OK;
+}
+
+// The bucketed sample of the 8-bit scan (replica_q8.hip.h, "the bucketed sample"), built from the rows and the 8-bit replica
+// on the handle's stream; a snapshot like them (mi355rec_rebuild_replica builds it again).  Not built where the 8-bit scan's
+// exact sample is not used (q8_exact_sample: the bucketed values are exact scores) or the base would be under
+// kBucketMinRegions regions: h->bsample stays empty and the call succeeds.
+constexpr int kBucketMinRegions = 64;
+bool q8_exact_sample(const mi355rec* h);
+int build_bucket_sample(mi355rec* h) {
+    free_bucket_bufs(h->bsample);
+    if (!h->d_q8 || !q8_exact_sample(h) || h->n > 0x7fffffffll) return MI355REC_OK;
+    int64_t regions = h->n / (5 * static_cast<int64_t>(kBucketRegionRows));
+    if (regions > kBucketMaxRegions) regions = kBucketMaxRegions;
+    if (regions < kBucketMinRegions) return MI355REC_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    BucketBufs& b = h->bsample;
+    const int64_t stride = (h->n / regions) / 4 * 4;   // >= 5 x 2048 - 3: no row is in two regions, every region is whole
+    const int64_t n_base = regions * kBucketRegionRows;
+    const int n_cent = static_cast<int>(regions);
+    const int64_t cstride = h->n / n_cent;
+    HIP_TRY(h, hipMalloc(&b.centroids, sizeof(float) * kDim * static_cast<size_t>(n_cent)));
+    HIP_TRY(h, hipMalloc(&b.rows, sizeof(int32_t) * static_cast<size_t>(n_base)));
+    HIP_TRY(h, hipMalloc(&b.region_tab, sizeof(int32_t) * 2 * static_cast<size_t>(regions)));
+    HIP_TRY(h, hipMalloc(&b.q8, static_cast<size_t>(n_base) * 12));
+    // the centroids: one strided copy, as the anchor table's (build_anchors)
+    HIP_TRY(h, hipMemcpy2DAsync(b.centroids, sizeof(float) * kDim, h->d_feats + (cstride >> 1) * kDim, sizeof(float) * kDim * static_cast<size_t>(cstride),
+                                sizeof(float) * kDim, static_cast<size_t>(n_cent), hipMemcpyDeviceToDevice, h->stream));
+    // the assignment (q8_build_kernel's third job), into b.rows for the moment; the base's row list rests in b.q8 meanwhile
+    std::vector<int32_t> bucket(static_cast<size_t>(n_base)), base(static_cast<size_t>(n_base));
+    for (int64_t e = 0; e < n_base; ++e) base[static_cast<size_t>(e)] = static_cast<int32_t>((e >> 11) * stride + (e & 2047));
+    HIP_TRY(h, hipMemcpyAsync(b.q8, base.data(), sizeof(int32_t) * static_cast<size_t>(n_base), hipMemcpyHostToDevice, h->stream));
+    const dim3 build_grid(static_cast<unsigned>((n_base + 255) / 256));
+    hipLaunchKernelGGL(q8_build_kernel, build_grid, dim3(256), 0, h->stream, h->d_feats, h->n, n_base, static_cast<uint32_t*>(nullptr),
+                       static_cast<float*>(nullptr), static_cast<const int32_t*>(b.q8), static_cast<const float*>(b.centroids), n_cent, b.rows);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(bucket.data(), b.rows, sizeof(int32_t) * static_cast<size_t>(n_base), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    BucketOrder order;
+    if (!bucket_sample_sort(base.data(), bucket.data(), n_base, n_cent, order) || order.regions != regions)
+        return fail(h, MI355REC_ERR_HIP, "the bucket assignment of the sample is out of range");
+    HIP_TRY(h, hipMemcpyAsync(b.rows, order.rows.data(), sizeof(int32_t) * static_cast<size_t>(n_base), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(b.region_tab, order.region_tab.data(), sizeof(int32_t) * 2 * static_cast<size_t>(regions), hipMemcpyHostToDevice, h->stream));
+    // the rows' replica entries in that order, from the rows themselves (q8_build_kernel's second job: what the replica holds)
+    hipLaunchKernelGGL(q8_build_kernel, build_grid, dim3(256), 0, h->stream, h->d_feats, h->n, n_base, static_cast<uint32_t*>(b.q8),
+                       static_cast<float*>(nullptr), static_cast<const int32_t*>(b.rows), static_cast<const float*>(nullptr), 0,
+                       static_cast<int32_t*>(nullptr));
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // (the host vectors above are read until here)
+    b.regions = static_cast<int>(regions);
+    b.n_centroids = n_cent;
+    b.base_rows = n_base;
+    b.stride = stride;
+    b.centroid_stride = cstride;
+    b.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return MI355REC_OK;
 }
 

@@ -67,6 +67,19 @@ struct SeedCtl {
     unsigned long long cutoff;   // tag_value(epoch, bits of a float): what the last rider made of the sample for the next launch
 };
 
+// The DIRECTION-BUCKETED sample of the 8-bit scan (replica_q8.hip.h, "the bucketed sample"): what a handle built beside
+// its 8-bit replica.  rows == null: the query takes the strided sample.
+struct BucketSample {
+    const uint4* q8;             // the base rows' 12 B replica entries in (bucket, row) order: regions x 2048 rows, 48 B per four
+    const int32_t* rows;         // the local row of every entry (-1: padding of the last region)
+    const float* centroids;      // n_centroids x 12 floats: the catalogue rows the buckets are named after
+    const int2* region_tab;      // per region: the buckets of its first and of its last entry
+    int regions;                 // <= kBucketMaxRegions
+    int n_centroids;             // <= kBucketMaxRegions
+    int picks;                   // regions a query samples: <= kBucketPicks
+    int pad;
+};
+
 // What a streamed launch carries for the NEXT query: after the scanners and the merger come next.n_wgs "seed riders"
 // that take its sample and, with next.nbhd, one more workgroup (the LAST of the grid) for its neighbourhood.  They are
 // resident from the start like everybody else — the host launches that many scanners fewer.
@@ -89,6 +102,7 @@ struct NextSeed {
     int debug_skip;            // test hook (0 in the product): the riders do NOT store regions below this one
     int nbhd;                  // 1: the grid's last workgroup computes the next query's neighbourhood bound into out[kNbhdSlot]
     const float* anchors;      // the handle's anchor table (nbhd_anchor), or null
+    BucketSample bucket;       // 8-bit replica, bucket.rows != null: the riders take the bucketed sample (n_wgs riders share bucket.picks regions)
 };
 
 // ---- selecting from <= 2048 sample values ----------------------------------------------------------------------

@@ -121,6 +121,7 @@ void mi355rec_destroy(mi355rec_t* h) {
         void* bufs[] = {h->shared->owned_feats, h->shared->d_half, h->shared->d_q8};
         for (void* b : bufs)
             if (b) (void)hipFree(b);
+        free_bucket_bufs(h->shared->bsample);
         free_side(h->shared->side);
         delete h->shared;
     }
@@ -220,6 +221,7 @@ int mi355rec_create_lane(mi355rec_t* parent, mi355rec_t** out) {
         group->owned_feats = parent->owned_feats;
         group->d_half = parent->d_half;
         group->d_q8 = parent->d_q8;
+        group->bsample = parent->bsample;
         group->margin_mix = parent->margin_mix;
         group->margin_mfma = parent->margin_mfma;
         group->side = parent->own_side;   // (labels, groups, priors: a lane made after their setters shares them, nothing is copied)
@@ -231,6 +233,8 @@ int mi355rec_create_lane(mi355rec_t* parent, mi355rec_t** out) {
     lane->side = &parent->shared->side;
     lane->d_half = parent->d_half;
     lane->d_q8 = parent->d_q8;
+    lane->bsample = parent->bsample;
+    lane->sample_mode = parent->sample_mode;
     lane->margin_mix = parent->margin_mix;
     lane->margin_mfma = parent->margin_mfma;
     lane->replica_build_ms = 0.f;
@@ -631,6 +635,7 @@ int adopt_group_replica(mi355rec* h) {
     }
     h->d_half = static_cast<decltype(h->d_half)>(h->shared->d_half);
     h->d_q8 = static_cast<decltype(h->d_q8)>(h->shared->d_q8);
+    h->bsample = h->shared->bsample;
     h->margin_mix = h->shared->margin_mix;
     h->margin_mfma = h->shared->margin_mfma;
     return MI355REC_OK;
@@ -659,6 +664,45 @@ int mi355rec_set_replica(mi355rec_t* h, int mode) {
         preallocate_stream_state(h);
     }
     h->replica_mode = mode;
+    return MI355REC_OK;
+}
+
+int mi355rec_set_sample(mi355rec_t* h, int mode) {
+    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    if (mode != MI355REC_SAMPLE_AUTO && mode != MI355REC_SAMPLE_STRIDED && mode != MI355REC_SAMPLE_BUCKETED)
+        return fail(h, MI355REC_ERR_INVALID_ARG, "unknown sample mode %d", mode);
+    if (mode == MI355REC_SAMPLE_BUCKETED && !h->bsample.rows)
+        return fail(h, MI355REC_ERR_INVALID_ARG, "this handle has no bucketed sample (mi355rec_bucket_sample_info)");
+    h->sample_mode = mode;
+    return MI355REC_OK;
+}
+
+int mi355rec_bucket_sample_info(const mi355rec_t* h, mi355rec_bucket_sample_info_t* out) {
+    if (!h || !out) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null argument");
+    std::memset(out, 0, sizeof *out);
+    const BucketBufs& b = h->bsample;
+    out->mode = h->sample_mode;
+    out->last_used = h->last_sample;
+    if (!b.rows) return MI355REC_OK;
+    out->base_rows = b.base_rows;
+    out->regions = b.regions;
+    out->centroids = b.n_centroids;
+    out->bytes = b.bytes();
+    out->stride_rows = b.stride;
+    out->centroid_stride = b.centroid_stride;
+    out->picks = b.regions < kBucketPicks ? b.regions : kBucketPicks;
+    out->build_ms = b.build_ms;
+    return MI355REC_OK;
+}
+
+int mi355rec_bucket_sample_rows(mi355rec_t* h, int32_t* rows_out, int32_t* region_tab_out) {
+    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    const BucketBufs& b = h->bsample;
+    if (!b.rows) return fail(h, MI355REC_ERR_INVALID_ARG, "this handle has no bucketed sample (mi355rec_bucket_sample_info)");
+    DeviceGuard guard(h->device);
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (rows_out) HIP_TRY(h, hipMemcpy(rows_out, b.rows, sizeof(int32_t) * static_cast<size_t>(b.regions) * kBucketRegionRows, hipMemcpyDeviceToHost));
+    if (region_tab_out) HIP_TRY(h, hipMemcpy(region_tab_out, b.region_tab, sizeof(int32_t) * 2 * static_cast<size_t>(b.regions), hipMemcpyDeviceToHost));
     return MI355REC_OK;
 }
 
@@ -761,6 +805,7 @@ int mi355rec_rebuild_replica(mi355rec_t* h) {
     if (rc == MI355REC_OK && h->shared) {   // published to the group
         h->shared->d_half = h->d_half;
         h->shared->d_q8 = h->d_q8;
+        h->shared->bsample = h->bsample;
         h->shared->margin_mix = h->margin_mix;
         h->shared->margin_mfma = h->margin_mfma;
     }

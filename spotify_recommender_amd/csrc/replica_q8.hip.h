@@ -30,7 +30,10 @@
 //     EXACT score of the row with the largest approx (q8_region_pick / q8_region_store); v = the topk-th largest of
 //     those <= 2048 exact scores, cutoff = v - margin (ONE margin: v is the exact score of a real row; shards too
 //     small to afford the extra fetch keep approximate sample values and two margins); workgroup-local thresholds
-//     tighten it whenever a local list fills.
+//     tighten it whenever a local list fills;
+//   * ... or, where the handle was told to (mi355rec_set_sample), from the BUCKETED sample: a fifth of the rows grouped by
+//     direction once, beside the replica, of which a query reads 32 regions whose buckets lie nearest to it — 0.8 MB instead of 6.3 MB,
+//     one exact score per 64 rows ("the bucketed sample" below).  Half the candidates of the strided sample at 10 M rows.
 // With a margin twelve times the fp16 replica's, ~0.1 % of the rows (~9 000 of 10 M at top-100) go to the exact
 // chain instead of 0.05 % — 0.6 MB of random 48 B fetches beside 120 MB of stream.
 //
@@ -64,15 +67,56 @@ constexpr uint32_t kQ8Special = 0x80u;       // first byte of a row the bound is
 // q8 and norms may each be null (uniform tests): the replica is stored only where q8 is given; where norms is given,
 // norms[row] = sqrtf of the SEQUENTIAL fp32 sum of squares (multiply, round, add, round: what query_norm computes; 0.0f for
 // the padding) — the per-row norms of the distance requests (playlist.hip.h, "DISTANCE"), 4 B per row in local row order.
+// The same kernel builds what the BUCKETED SAMPLE keeps beside the replica ("the bucketed sample" below; one kernel, not
+// three: the library's kernel count is capped):
+//   * pick != null: thread e works on local row pick[e] instead of row e (outside [0, n): padding) and stores at index e —
+//     the base rows' entries in sample order;
+//   * centroids != null: bucket[e] = the centroid with the largest dot product row . c / |c| (the row's own norm scales
+//     every candidate alike): a sequential fma chain in feature order and centroid order, so deterministic, and a tie
+//     keeps the LOWER centroid (strict >).  A centroid whose norm is zero or not finite counts as score 0.
 __global__ __launch_bounds__(256) void q8_build_kernel(const float* __restrict__ feats, int64_t n, int64_t n_padded,
-                                                       uint32_t* __restrict__ q8, float* __restrict__ norms) {
-    const int64_t row = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (row >= n_padded) return;
+                                                       uint32_t* __restrict__ q8, float* __restrict__ norms,
+                                                       const int32_t* __restrict__ pick, const float* __restrict__ centroids,
+                                                       int n_centroids, int32_t* __restrict__ bucket) {
+    __shared__ float s_inv[1024];
+    if (centroids) {   // uniform
+        n_centroids = n_centroids < 1024 ? n_centroids : 1024;
+        for (int c = threadIdx.x; c < n_centroids; c += blockDim.x) {
+            float tot = 0.0f;
+            for (int j = 0; j < kDim; ++j) tot = __builtin_fmaf(centroids[c * kDim + j], centroids[c * kDim + j], tot);
+            const float inv = 1.0f / sqrtf(tot);
+            s_inv[c] = (tot > 0.0f && inv == inv && inv < 3.0e38f) ? inv : 0.0f;
+        }
+        __syncthreads();
+    }
+    const int64_t slot = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (slot >= n_padded) return;
+    int64_t row = slot;
+    if (pick) {   // uniform
+        row = pick[slot];
+        row = row >= 0 ? row : n;   // (padding)
+    }
     uint32_t d0 = 0x80808080u, d1 = 0x80808080u, d2 = 0x80808080u;   // special
     float seq = 0.0f;
     if (row < n) {
         const float4* p = reinterpret_cast<const float4*>(feats) + row * 3;
         const float4 a = p[0], b = p[1], c = p[2];
+        if (centroids) {   // uniform
+            const float f[kDim] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
+            float best = -__builtin_inff();
+            int best_c = 0;
+            for (int k = 0; k < n_centroids; ++k) {   // (uniform addresses: scalar loads)
+                float dot = 0.0f;
+#pragma unroll
+                for (int j = 0; j < kDim; ++j) dot = __builtin_fmaf(f[j], centroids[k * kDim + j], dot);
+                const float v = dot * s_inv[k];
+                if (v > best) {
+                    best = v;
+                    best_c = k;
+                }
+            }
+            bucket[slot] = best_c;
+        }
         if (norms) {   // uniform
             const float f[kDim] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
 #pragma unroll
@@ -103,14 +147,16 @@ __global__ __launch_bounds__(256) void q8_build_kernel(const float* __restrict__
             d1 = q(b.x) | (q(b.y) << 8) | (q(b.z) << 16) | (q(b.w) << 24);
             d2 = q(c.x) | (q(c.y) << 8) | (q(c.z) << 16) | (q(c.w) << 24);
         }
+    } else if (centroids) {   // uniform
+        bucket[slot] = 0;     // (padding: any bucket in range)
     }
     if (q8) {   // uniform
-        uint32_t* dst = q8 + row * 3;
+        uint32_t* dst = q8 + slot * 3;
         dst[0] = d0;
         dst[1] = d1;
         dst[2] = d2;
     }
-    if (norms) norms[row] = sqrtf(seq);   // uniform
+    if (norms) norms[slot] = sqrtf(seq);   // uniform
 }
 
 // ---- the query ------------------------------------------------------------------------------------------
@@ -269,6 +315,175 @@ __device__ __forceinline__ void q8_load_query(const float* __restrict__ query_pt
     }
 }
 
+// ---- the bucketed sample ------------------------------------------------------------------------------------------
+// The strided sample reads 256 regions x 2048 rows (5 % of a 10 M-row catalogue, 6.3 MB) for EVERY query and keeps the
+// best row of each 256-row wave tile, wherever the query points.  Which rows are worth looking at depends on the query's
+// direction, and the catalogue does not change between queries — so the grouping is done once, beside the replica
+// (engine_state.hip.h, build_bucket_sample): a BASE of up to 1024 strided regions (a fifth of the rows) is assigned, row by
+// row, to the nearest of as many CENTROIDS (strided catalogue rows, largest normalised dot product, ties to the lower
+// centroid), ordered by (bucket, row) on the host (bucket_sample.h) and kept as a contiguous copy of the rows' 12 B
+// entries + their local row numbers + the bucket range of every 2048-row region of that order.  A query then
+//   1. scores the centroids (exact chain, <= 2 per thread), gives every region the best centroid score of its bucket
+//      range (its first kBucketSpanMax - 1 buckets and its last: a longer range only happens where buckets are nearly empty) and
+//      takes the regions whose score reaches the picks-th best one, the first `picks` of them in region order;
+//   2. reads those `picks` <= 32 regions (0.79 MB instead of 6.3), riders taking every n_wgs-th of them.  The selection
+//      returns the lower edge of a histogram bin, so a few more than `picks` regions can reach it: kept are the first
+//      `picks` in region order, all of them within one bin (2.4e-4) of the picks-th best score — not the best by rank;
+//   3. takes one value per 64 rows of a region — the 16 lanes of a DPP row x 4 rows per lane: the lane that holds the
+//      row's best approximate score looks its row up (BucketSample::rows), fetches it from the CURRENT fp32 matrix and
+//      stores cosine_score() of it — up to 32 x 32 = 1024 values at out[rank * 32 + tid / 16].
+// Every rider redoes 1.: the same arithmetic on the same table gives the same ranking, so the riders' shares are
+// disjoint without a hand-off between them.  What decides RESULTS is only that every value is the exact score of a
+// real, distinct, eligible row of this shard: entries are distinct rows (a permutation of the base), padding holds the
+// special marker and row -1, the excluded row and rows outside [0, n) yield nothing, an invalid query yields nothing.
+// Poorly chosen regions (a stale copy after rows changed in place, a degenerate centroid) only loosen the bound.
+constexpr int kBucketMaxRegions = 1024;   // regions of the base, and centroids
+constexpr int kBucketPicks = 32;          // regions a query reads
+constexpr int kBucketGroups = kHalfSeedBlock / 16;   // values per region: one per DPP row of 16 lanes
+constexpr int kBucketSpanMax = 8;         // buckets of a region's range that are looked at: the first 7 and the last (a loop over
+                                          // the whole range was 64 dependent LDS reads in some thread of every rider: ~3 us)
+constexpr int kBucketAhead = 4;           // regions of a rider in flight
+constexpr int kBucketScratch = kBucketMaxRegions + kSelScratch + kBucketPicks + 8 + 1;   // ints of LDS scratch
+static_assert(kBucketPicks * kBucketGroups <= kHalfSeedPerThread * kHalfSeedBlock, "the values fit the sample buffer's selection");
+
+// Called by all kHalfSeedBlock threads of sampling workgroup `rider` of `n_wgs`.  `s`: kBucketScratch ints of LDS nobody
+// else is using, `sel`: the selection's histogram.  drop (test hook): nothing is stored.
+__device__ __forceinline__ Q8Query q8_bucket_sample(const float* __restrict__ feats, const BucketSample& bs, int64_t n, int64_t row_base,
+                                                    const float* __restrict__ query_ptr, const float (&by_value)[kDim],
+                                                    int64_t exclude_global, unsigned long long* __restrict__ out, uint32_t epoch,
+                                                    int rider, int n_wgs, bool drop, int* s, SelectSmem& sel) {
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    uint32_t* const s_cent = reinterpret_cast<uint32_t*>(s);   // [kBucketMaxRegions] centroid scores, ordered
+    int* const s_bins = s + kBucketMaxRegions;                  // [kSelScratch] the selection's scratch
+    int* const s_pick = s_bins + kSelScratch;                   // [kBucketPicks] the regions to read (-1: none)
+    int* const s_wave = s_pick + kBucketPicks;                  // [8] per-wave counts of the prefix sum
+    int* const s_count = s_wave + 8;                            // [1] the selection's counter
+    const int n_cent = bs.n_centroids < kBucketMaxRegions ? bs.n_centroids : kBucketMaxRegions;
+    const int n_reg = bs.regions < kBucketMaxRegions ? bs.regions : kBucketMaxRegions;
+    const int picks = bs.picks < kBucketPicks ? (bs.picks < n_reg ? bs.picks : n_reg) : (kBucketPicks < n_reg ? kBucketPicks : n_reg);
+    // what needs nothing of the query is requested before it (two dependent scalar loads and a norm)
+    Row cent[2];
+    int2 tab[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int i = tid + u * kHalfSeedBlock;
+        cent[u] = load_row(bs.centroids, static_cast<int64_t>(i < n_cent ? i : 0));
+        tab[u] = bs.region_tab[i < n_reg ? i : 0];
+    }
+    float q[kDim];
+    q8_load_query(query_ptr, by_value, q);
+    const float qn = query_norm(q);
+    const Q8Query hq = q8_query(q, qn);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int i = tid + u * kHalfSeedBlock;
+        if (i < n_cent) s_cent[i] = score_to_ordered(cosine_score(q, qn, cent[u]));
+    }
+    if (tid < kBucketPicks) s_pick[tid] = -1;
+    if (tid == 0) *s_count = 0;
+    __syncthreads();
+    uint32_t best_of[2];   // the region's best centroid score, ordered (0: no such region)
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int g = tid + u * kHalfSeedBlock;
+        best_of[u] = 0u;
+        if (g < n_reg) {
+            int first = tab[u].x < 0 ? 0 : (tab[u].x < n_cent ? tab[u].x : n_cent - 1);
+            int last = tab[u].y < first ? first : (tab[u].y < n_cent ? tab[u].y : n_cent - 1);
+            uint32_t m = 0u;
+#pragma unroll
+            for (int i = 0; i < kBucketSpanMax; ++i) {   // (independent reads, clamped to the range: all in flight at once)
+                const uint32_t c = s_cent[first + i < last ? first + i : last];
+                m = c > m ? c : m;
+            }
+            best_of[u] = m;
+        }
+    }
+    // The regions to read: those whose score reaches the picks-th best score (handoff.hip.h, kth_of_values: one histogram
+    // pass; ranking all pairs by counting was built first and cost the riders 14 us at 976 regions), the first `picks` of
+    // them in region order — a block-wide prefix sum, the same in every rider.
+    const float vth = kth_of_values<kHalfSeedBlock, 2>(best_of, n_reg, picks, s_count, sel, s_bins);
+    const uint32_t need = vth > -__builtin_inff() ? score_to_ordered(vth) : 1u;   // (-inf: fewer scored regions than picks: all of them)
+    const int chosen0 = best_of[0] != 0u && best_of[0] >= need, chosen1 = best_of[1] != 0u && best_of[1] >= need;
+    const int incl = wave_inclusive_scan(chosen0 | (chosen1 << 16));
+    __syncthreads();   // (kth_of_values is done with its scratch)
+    if (lane == 63) s_wave[tid >> 6] = incl;
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int w = 0; w < kHalfSeedBlock / 64; ++w) {   // (uniform reads)
+        const int t = s_wave[w];
+        before += w < (tid >> 6) ? t : 0;
+        total += t;
+    }
+    const int slot0 = ((before + incl) & 0xffff) - chosen0;
+    const int slot1 = (total & 0xffff) + ((before + incl) >> 16) - chosen1;   // regions 512 .. 1023 come after regions 0 .. 511
+    if (chosen0 && slot0 < picks) s_pick[slot0] = tid;
+    if (chosen1 && slot1 < picks) s_pick[slot1] = tid + kHalfSeedBlock;
+    __syncthreads();
+    for (int k0 = rider; k0 < picks; k0 += kBucketAhead * n_wgs) {
+        HalfTile t[kBucketAhead];
+        bool live[kBucketAhead];
+        int4 ids[kBucketAhead];
+#pragma unroll
+        for (int u = 0; u < kBucketAhead; ++u) {
+            const int k = k0 + u * n_wgs;
+            int g = s_pick[k < picks ? k : rider];
+            live[u] = k < picks && g >= 0 && g < n_reg;   // uniform
+            g = live[u] ? g : 0;
+            const uint4* p = bs.q8 + (static_cast<int64_t>(g) * kHalfSeedBlock + tid) * 3;
+            t[u].t0 = p[0];
+            t[u].t1 = p[1];
+            t[u].t2 = p[2];
+            // (the lane's four row numbers ride along: looked up after the pick they would be one more dependent round trip)
+            ids[u] = reinterpret_cast<const int4*>(bs.rows)[static_cast<int64_t>(g) * kHalfSeedBlock + tid];
+        }
+        int32_t idx[kBucketAhead];
+        bool mine[kBucketAhead];
+#pragma unroll
+        for (int u = 0; u < kBucketAhead; ++u) {
+            int a[4];
+            bool special[4];
+            q8_dot4(hq, t[u], a, special);
+            uint32_t v = 0u;
+            int best = 0;
+            const int id4[4] = {ids[u].x, ids[u].y, ids[u].z, ids[u].w};
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                // (as q8_region_pick: padding, a row number outside the shard and the excluded row are left out BEFORE the
+                // group's best is chosen, so such a group still yields its best eligible row)
+                const bool use = hq.ok && !special[r] && id4[r] >= 0 && static_cast<int64_t>(id4[r]) < n &&
+                                 row_base + id4[r] != exclude_global;
+                const uint32_t w = use ? score_to_ordered(q8_approx(hq, a[r])) : 0u;
+                best = w > v ? r : best;
+                v = w > v ? w : v;
+            }
+            const uint32_t top = row16_max_u32(v);
+            const uint64_t holders = __ballot(v == top && v != 0u);
+            const uint32_t in_row = static_cast<uint32_t>(holders >> (lane & 48)) & 0xffffu;
+            mine[u] = in_row != 0u && static_cast<int>(__builtin_ctz(in_row)) == (lane & 15);   // the row's first holder
+            idx[u] = best == 0 ? id4[0] : (best == 1 ? id4[1] : (best == 2 ? id4[2] : id4[3]));
+        }
+        Row rows[kBucketAhead];
+        bool ok[kBucketAhead];
+#pragma unroll
+        for (int u = 0; u < kBucketAhead; ++u) {
+            ok[u] = mine[u] && idx[u] >= 0 && static_cast<int64_t>(idx[u]) < n && row_base + idx[u] != exclude_global;
+            rows[u] = load_row(feats, ok[u] ? static_cast<int64_t>(idx[u]) : static_cast<int64_t>(0));
+        }
+#pragma unroll
+        for (int u = 0; u < kBucketAhead; ++u) {
+            const int k = k0 + u * n_wgs;
+            const float exact = cosine_score(q, qn, rows[u]);
+            // written THROUGH to device scope, under the query's epoch (q8_region_store)
+            if (ok[u] && live[u] && !drop)
+                __hip_atomic_store(&out[k * kBucketGroups + (tid >> 4)], tag_value(epoch, score_to_ordered(exact)), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    return hq;
+}
+
 // One workgroup per region (single queries; the first query of a stream) and, when the grid has one more workgroup
 // than regions, the neighbourhood of the excluded row (handoff.hip.h) by that last one.  `exact`: the sample values are
 // EXACT scores (q8_region_store) — a kernel argument, not a template parameter: both kinds share one kernel.
@@ -276,12 +491,20 @@ __global__ __launch_bounds__(kHalfSeedBlock) void seed_q8_kernel(
     const float* __restrict__ feats, const uint4* __restrict__ q8, int64_t n, int64_t stride_rows, int64_t row_base, QueryArg qarg,
     const float* __restrict__ query_ptr /* null: the query is qarg.q */, int64_t exclude_global,
     unsigned long long* __restrict__ seed_vals, uint32_t epoch, int regions, int topk,
-    const float* __restrict__ anchors /* the handle's anchor table (handoff.hip.h), or null */, bool exact) {
+    const float* __restrict__ anchors /* the handle's anchor table (handoff.hip.h), or null */, bool exact,
+    BucketSample bucket /* rows != null: `regions` workgroups share the bucketed sample's regions instead */) {
     if (static_cast<int>(blockIdx.x) >= regions) {   // uniform
         // (1024 rows: this workgroup is the last one out of the sample launch of a query alone, and the scan subtracts a margin
         // of ~0.01 from whatever bound it is given — the 10th percentile of the neighbourhood serves it as well as the 5th)
         __shared__ int s_scratch[Nbhd<kHalfSeedBlock, 1024>::kScratch];
         nbhd_to_slot<kHalfSeedBlock, 1024>(feats, n, row_base, query_ptr, qarg.q, exclude_global, topk, epoch, seed_vals, s_scratch, anchors);
+        return;
+    }
+    if (bucket.rows) {   // uniform
+        __shared__ int s_bucket[kBucketScratch];
+        __shared__ SelectSmem s_bucket_sel;
+        (void)q8_bucket_sample(feats, bucket, n, row_base, query_ptr, qarg.q, exclude_global, seed_vals, epoch,
+                               static_cast<int>(blockIdx.x), regions, false, s_bucket, s_bucket_sel);
         return;
     }
     // the region's rows are requested FIRST: they need nothing of the query, whose 12 floats sit behind two dependent
@@ -374,7 +597,8 @@ using DefaultQ8Cfg = Q8Cfg<512, 4, 2>;
 
 // kWithMerge (streamed queries): workgroups [0, S) scan, workgroup S merges the PREVIOUS streamed query, the next
 // next.n_wgs workgroups are seed riders for the NEXT one and (next.nbhd) the last of the grid takes that query's
-// neighbourhood (handoff.hip.h); S = gridDim.x - 1 - next.n_wgs - next.nbhd.
+// neighbourhood (handoff.hip.h); S = gridDim.x - 1 - next.n_wgs - next.nbhd.  Those are the roles' VIRTUAL ids (`vb`): in
+// hardware the 1 + n_wgs + nbhd workgroups that do not scan hold the FIRST block ids, so that they are dispatched first.
 // Slot kNbhdSlot of `seed_vals` holds, under this query's epoch, the neighbourhood's EXACT bound v (0: none): keys below
 // it are dropped at once and v - margin is one more lower bound on the cutoff — what keeps a catalogue sorted by genre
 // (the query's cluster in ONE sampled region at most) from scanning with another cluster's cutoff.
@@ -400,27 +624,41 @@ __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel(
     __shared__ int s_lone_flag;
     HalfScanSmemT<Cfg>* sm;
     unsigned nblocks = gridDim.x;   // scanning workgroups
+    unsigned vb = blockIdx.x;       // this workgroup's place among them (and, kWithMerge, behind them: see below)
     MI355REC_PHASE(0);
     if constexpr (kWithMerge) {
-        nblocks = gridDim.x - 1u - static_cast<unsigned>(next.n_wgs) - static_cast<unsigned>(next.nbhd);
-        if (blockIdx.x >= nblocks) {
-            if (blockIdx.x == nblocks) {
+        // The workgroups that do not scan take the FIRST block ids — they are dispatched first: at the end of the grid they
+        // only got their slots once workgroups of the launch before had finished, and a rider's chain of dependent round
+        // trips, started that late, was the last thing to finish in the launch.  `vb` is the id every role is told by.
+        const unsigned extra = 1u + static_cast<unsigned>(next.n_wgs) + static_cast<unsigned>(next.nbhd);
+        nblocks = gridDim.x - extra;
+        vb = blockIdx.x >= extra ? blockIdx.x - extra : nblocks + blockIdx.x;
+        if (vb >= nblocks) {
+            if (vb == nblocks) {
                 if (prev.lists)
                     merge_body(s_mem.merge, prev.lists, prev.n_lists, prev.topk, static_cast<int64_t>(prev.topk),
                                static_cast<int64_t>(0), prev.topk, prev.out_keys, static_cast<int64_t*>(nullptr),
                                static_cast<float*>(nullptr), static_cast<int64_t>(0), static_cast<int64_t>(0),
                                static_cast<int64_t>(0));
-            } else if (next.nbhd && blockIdx.x == gridDim.x - 1u) {   // the next query's neighbourhood: read by the NEXT launch
+            } else if (next.nbhd && vb == gridDim.x - 1u) {   // the next query's neighbourhood: read by the NEXT launch
                 nbhd_to_slot<kBlock>(feats, n, row_base, next.query_ptr, next.q, next.exclude_global, next.topk, next.epoch,
                                      static_cast<unsigned long long*>(next.out), reinterpret_cast<int*>(s_mem.scan.cand), next.anchors);
             } else {
-                const Q8Query nq = q8_seed_rider(feats, q8, n, row_base, next, static_cast<int>(blockIdx.x - nblocks - 1u));
+                static_assert(kBlock == kHalfSeedBlock && sizeof(s_mem.scan.cand) >= sizeof(int) * kBucketScratch, "the riders' geometry");
+                const int rider = static_cast<int>(vb - nblocks - 1u);
+                const bool bucketed = next.bucket.rows != nullptr;   // uniform
+                // (DROP_STORES, the test hook: the bucketed riders drop every store)
+                const Q8Query nq = bucketed ? q8_bucket_sample(feats, next.bucket, n, row_base, next.query_ptr, next.q, next.exclude_global,
+                                                               static_cast<unsigned long long*>(next.out), next.epoch, rider, next.n_wgs,
+                                                               next.debug_skip > 0, reinterpret_cast<int*>(s_mem.scan.cand), s_mem.scan.sel)
+                                            : q8_seed_rider(feats, q8, n, row_base, next, rider);
+                const int n_vals = bucketed ? kBucketPicks * kBucketGroups : next.regions * kHalfSeedWaves;
                 // Last rider out turns the sample into the cutoff (handoff.hip.h, sample_arrive_and_select: no device-wide
                 // fence under the scanners).  Values and cutoff carry the next query's epoch and the counter is never reset.
                 if (next.ctl) {   // uniform; null: nobody reads the sample inside this launch (small shards: the next launch selects)
                     float v;
                     if (sample_arrive_and_select<kBlock>(next.ctl, next.done_base, static_cast<unsigned>(next.n_wgs),
-                                                         static_cast<const unsigned long long*>(next.out), next.regions * kHalfSeedWaves,
+                                                         static_cast<const unsigned long long*>(next.out), n_vals,
                                                          next.topk, next.epoch, &s_mem.scan.count, &s_mem.scan.seeds, s_mem.scan.sel,
                                                          reinterpret_cast<int*>(s_mem.scan.cand), v)) {
                         // one margin below an EXACT score of a real row, two below an approximate one
@@ -447,7 +685,7 @@ __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel(
     SelectSmem& s_sel = sm->sel;
     int& s_count = sm->count;
 
-    const unsigned bid = blockIdx.x;
+    const unsigned bid = vb;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
 

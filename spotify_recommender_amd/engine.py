@@ -618,6 +618,25 @@ class CosineEngine(_RowSets):
         capi.check(self._lib.mi355rec_replica_counters(self._h, ctypes.byref(scans), ctypes.byref(rows)), self._h)
         return {"scans": int(scans.value), "rescored_rows": int(rows.value)}
 
+    def set_sample(self, mode: int) -> None:
+        """capi.SAMPLE_AUTO / SAMPLE_STRIDED / SAMPLE_BUCKETED: which cutoff sample single queries over the 8-bit replica take."""
+        capi.check(self._lib.mi355rec_set_sample(self._h, int(mode)), self._h)
+
+    def bucket_sample_info(self) -> dict:
+        """The bucketed sample of the handle (base_rows 0: it has none), the mode set and what the last query took."""
+        info = capi.BucketSampleInfo()
+        capi.check(self._lib.mi355rec_bucket_sample_info(self._h, ctypes.byref(info)), self._h)
+        return {name: getattr(info, name) for name, _ in info._fields_}
+
+    def bucket_sample_rows(self):
+        """(sample_rows int32[regions * 2048], region_tab int32[regions, 2]) copied to the host."""
+        info = self.bucket_sample_info()
+        rows = np.empty(info["regions"] * 2048, dtype=np.int32)
+        tab = np.empty((info["regions"], 2), dtype=np.int32)
+        capi.check(self._lib.mi355rec_bucket_sample_rows(self._h, rows.ctypes.data_as(ctypes.c_void_p),
+                                                         tab.ctypes.data_as(ctypes.c_void_p)), self._h)
+        return rows, tab
+
     def debug_handoff(self, flags: int) -> None:
         """Test hook (capi.DEBUG_HANDOFF_*): poison / drop the cross-workgroup hand-offs of the streamed scans."""
         capi.check(self._lib.mi355rec_debug_handoff(self._h, int(flags)), self._h)
