@@ -188,6 +188,13 @@ public:
     bool setRowSet(const std::vector<int>& songIndices, bool only = false);
     void clearRowSet();
 
+    // Extension: in-place updates (include/mi355rec_diag.h, "ROW UPDATES").  updateSongs gives the songs at `indices` (distinct,
+    // inside the catalogue) new features: 12 floats per song in Song.h order, features[12 * i ..] for indices[i].  Every later
+    // recommendation answers as if the catalogue had been initialised with the new features; ids, names, genre ids, groups,
+    // priors and the row set stay as they are.  A wrong length, an index outside the songs or one named twice give false and a
+    // message, and the catalogue as it was.  An empty list succeeds.
+    bool updateSongs(const std::vector<int>& indices, const std::vector<float>& features);
+
     struct Impl;   // opaque: defined in Recommender.cpp
 
 private:

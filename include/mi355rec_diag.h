@@ -34,6 +34,8 @@
  *     (mi355rec_query_playlist_request_scaled, mi355rec_query_distance_request_scaled and their node-handle twins);
  *   - ROW SETS: one bit per row, to leave out a listening history or to rank within a candidate set, passed to the playlist and
  *     distance requests in a self-sized struct of extras (mi355rec_rowset_*, mi355rec_query_*_request_ext and the node-handle twins);
+ *   - ROW UPDATES: rows of the catalogue change in place and every route answers as a freshly created handle would
+ *     (mi355rec_update_rows, _update_info, _replica_entries and the node-handle twin);
  *   - test hooks, compiled in only with -DMI355REC_TEST_HOOKS (spotify_recommender_amd/build.py builds
  *     libmi355rec_testhooks.so for tests/; the product library does not export them).
  */
@@ -891,6 +893,66 @@ int mi355rec_sharded_query_playlist_request_ext(mi355rec_sharded_t* h, const mi3
                                                 const mi355rec_request_ext_t* ext, const mi355rec_playlist_result_t* result);
 int mi355rec_sharded_query_distance_request_ext(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
                                                 const mi355rec_request_ext_t* ext, const mi355rec_distance_result_t* result);
+
+/* ROW UPDATES (the reference lists "Real-time Updates: Incremental index updates" among its extensions): songs are re-analysed
+ * and corrected every day, and a changed row should not cost a rebuild of everything the handle keeps beside the rows.
+ * mi355rec_update_rows changes `count` rows in place and returns once the update has been applied (synchronous, a set-up call
+ * like the setters).  From then on every route of the handle and of every lane of its group answers exactly as a handle freshly
+ * created from the updated matrix would: ids, order, score and distance bits.
+ *   feats_host != NULL: count x 12 floats, row i for local_rows[i]; the matrix must be the library's own (mi355rec_create).  The rows
+ *                       are written and everything derived from them is redone.
+ *   feats_host == NULL: the caller has already changed those rows of the matrix (the borrowed matrix of mi355rec_create_device —
+ *                       the writes complete before the call — or an owned one): only what is derived from them is redone.
+ * What is exact afterwards, where the handle has it: the fp32 row, its entry in the fp16 and in the 8-bit replica, its norm
+ * (distance requests) and its slot in the label-grouped copy of mi355rec_set_labels.  Priors, groups, row labels and row sets do
+ * not depend on the features and stay.  Any fp32 values are accepted: zero, tiny, huge, infinite and NaN rows take the replicas'
+ * special encodings, as at create.  Two snapshots only ever PLACE a bound and may stay stale without changing a result: the
+ * anchor table (the caller's is recopied, a lane's is not) and the bucketed sample.  A stale one costs candidates, not
+ * correctness: mi355rec_update_info_t::rows_since_snapshot counts the rows updated since the replicas were last built from all
+ * rows (create, mi355rec_rebuild_replica: they reset it) and is the cue for an eventual rebuild.
+ * INVALID_ARG (with a message), checked before anything is written: host rows on a borrowed matrix; a row outside [0, n); a row
+ * named twice (two threads would race on one row); another lane of the group with a streamed query or batch open.
+ * count == 0 succeeds and changes nothing.  An error AFTER the checks (a HIP error, out of memory; on a node handle, a failure on
+ * one shard after others succeeded) may leave the update applied in part: repeating it with the same rows and features is safe.
+ * LANES: the rows and the replicas are the group's, so an update through any member serves all of them.  Two rules: flush every
+ * lane first (mi355rec_enqueue_flush: a stashed or pending streamed query carries a cutoff taken from the old rows; the caller's
+ * own are completed by the call, another member's make it fail), and let no other thread use the group during the call.  What
+ * the members have enqueued need not have finished: before its first write the call waits for every other member's own stream and
+ * for the stream each was last used on, so work enqueued before the call is answered from the old rows, whole.  The
+ * norms of the distance requests belong to each handle: the caller's are rewritten, the other members drop theirs and build
+ * them again on their next distance request.
+ * Device: no new kernel.  The update is a further job of q8_build_kernel (csrc/replica_q8.hip.h): thread e reads staged row e and
+ * stores the row and its entries at row local_rows[e], through the packers the builders themselves call.  Rows are staged through
+ * a pinned buffer of at most 65 536 rows; a larger update goes in chunks.
+ * Node handle: feats_host is required (the node owns its rows; NULL is INVALID_ARG).  The open window is closed and the workers
+ * are drained first; tickets waited for earlier stay readable.  A row-sharded placement gives each shard the rows it owns, a
+ * replicated one applies the update once per device, the CPU backend rewrites its host matrix.
+ * mi355rec_update_info: out->size = sizeof(mi355rec_update_info_t) of the caller's header on entry; no more than that is written.
+ * mi355rec_replica_entries copies the stored entries of the given rows (any order, duplicates allowed) to the host: 24 B per row
+ * of the fp16 replica, 12 B of the 8-bit one, and the norm where the handle has built norms (out_norms is left alone
+ * otherwise).  Any out pointer may be NULL.  INVALID_ARG on a handle without replicas.  For tests: an updated handle against a
+ * fresh one, byte for byte.
+ * Measured on one MI355X at 10 M uniform rows with the replicas (tools/run_update_rows.py, profiles/r18_update_rows.json; host wall
+ * time around the synchronous call, medians of five alternating runs): 1 row 0.06 ms, 1 000 rows 0.085 ms, 100 000 rows 0.50 ms,
+ * 1 000 000 rows 4.5 ms (0.07 / 0.09 / 0.83 / 7.4 ms with labels set); beside it mi355rec_rebuild_replica 13.8 ms and destroying and
+ * creating the handle again from host memory 65 ms (429 ms with the labels set again).  Staleness, streamed top-100 queries by row:
+ * 21.88 us per query and 5 164 rows to the exact chain fresh, 21.90 us / 5 209 rows with 1 % of the rows updated, 21.97 us / 5 621
+ * with 10 %, 21.87 us / 5 152 after mi355rec_rebuild_replica.  bench.py's headline against the parent commit, three alternating
+ * runs each: 55 588 / 55 853 / 55 120 queries/s beside the parent's 54 936 ... 56 679 (profiles/r18_update_rows_ab.json).
+ * Not served: appending or deleting rows (a deleted song is a row set); per-row updates of priors, labels or groups; an
+ * incremental refresh of the bucketed sample; updates inside a running stream. */
+typedef struct {
+    uint32_t size;                /* in: sizeof of the caller's header                                           */
+    float last_ms;                /* host wall time of the last mi355rec_update_rows call on this handle          */
+    int64_t calls;                /* update calls on this handle that changed something, since create            */
+    int64_t rows;                 /* rows they updated                                                           */
+    int64_t rows_since_snapshot;  /* rows updated (through any lane of the group) since the replicas, the bucketed sample
+                                     and the anchor tables were last built from all rows                          */
+} mi355rec_update_info_t;         /* 32 bytes */
+int mi355rec_update_rows(mi355rec_t* h, const int64_t* local_rows, int64_t count, const float* feats_host);
+int mi355rec_sharded_update_rows(mi355rec_sharded_t* h, const int64_t* global_rows, int64_t count, const float* feats_host);
+int mi355rec_update_info(const mi355rec_t* h, mi355rec_update_info_t* out);
+int mi355rec_replica_entries(mi355rec_t* h, const int64_t* local_rows, int64_t count, void* out_half, void* out_q8, float* out_norms);
 
 #ifdef MI355REC_TEST_HOOKS
 /* TEST HOOK for the cross-workgroup hand-offs of the streamed scans (csrc/replica.hip.h, "hand-offs that fail

@@ -92,6 +92,10 @@ class BucketSampleInfo(ctypes.Structure):   # mi355rec_bucket_sample_info_t
                 ("centroid_stride", c_int64), ("picks", c_int32), ("mode", c_int32), ("last_used", c_int32), ("build_ms", c_float)]
 
 
+class UpdateInfo(ctypes.Structure):   # mi355rec_update_info_t (size = sizeof of this struct, 32, on entry)
+    _fields_ = [("size", c_uint32), ("last_ms", c_float), ("calls", c_int64), ("rows", c_int64), ("rows_since_snapshot", c_int64)]
+
+
 class Stats(ctypes.Structure):
     _fields_ = [
         ("rows", c_int64),
@@ -280,6 +284,11 @@ SIGNATURES = {
     "mi355rec_query_distance_request_ext": (c_int, [c_void_p, POINTER(DistanceQuery), POINTER(RequestExt), POINTER(DistanceResult)]),
     "mi355rec_sharded_query_playlist_request_ext": (c_int, [c_void_p, POINTER(PlaylistQuery), POINTER(RequestExt), POINTER(PlaylistResult)]),
     "mi355rec_sharded_query_distance_request_ext": (c_int, [c_void_p, POINTER(DistanceQuery), POINTER(RequestExt), POINTER(DistanceResult)]),
+    # ROW UPDATES: rows change in place, every route answers as a freshly created handle would
+    "mi355rec_update_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "mi355rec_sharded_update_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "mi355rec_update_info": (c_int, [c_void_p, POINTER(UpdateInfo)]),
+    "mi355rec_replica_entries": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "mi355rec_pack_key": (c_uint64, [c_float, c_int64]),
     "mi355rec_key_score": (c_float, [c_uint64]),
     "mi355rec_key_row": (c_int64, [c_uint64]),

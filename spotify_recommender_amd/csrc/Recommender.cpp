@@ -252,6 +252,23 @@ bool Recommender::setPriors(const std::vector<float>& priors) {
     return true;
 }
 
+bool Recommender::updateSongs(const std::vector<int>& indices, const std::vector<float>& features) {
+    if (!impl_->initialized) {
+        std::cerr << "Error: Recommender not initialized" << std::endl;
+        return false;
+    }
+    if (features.size() != indices.size() * static_cast<size_t>(MI355REC_DIM)) {
+        std::cerr << "Error: " << MI355REC_DIM << " features per updated song are needed" << std::endl;
+        return false;
+    }
+    const std::vector<int64_t> rows(indices.begin(), indices.end());
+    if (mi355rec_sharded_update_rows(impl_->engine, rows.data(), static_cast<int64_t>(rows.size()), features.data()) != MI355REC_OK) {
+        std::cerr << "Error: " << mi355rec_sharded_last_error(impl_->engine) << std::endl;
+        return false;
+    }
+    return true;
+}
+
 bool Recommender::setRowSet(const std::vector<int>& songIndices, bool only) {
     if (!impl_->initialized) {
         std::cerr << "Error: Recommender not initialized" << std::endl;

@@ -351,6 +351,17 @@ int node_set_priors(Node* h, const float* priors, int64_t n, const char** why) {
                          [](float) { return static_cast<const char*>(nullptr); }, why);
 }
 
+int node_update_rows(Node* h, const int64_t* rows, int64_t count, const float* feats, const char** why) {
+    if (count < 0 || (count > 0 && (!rows || !feats))) {
+        *why = "null rows / negative count";
+        return MI355REC_ERR_INVALID_ARG;
+    }
+    float* dst = h->cat->feats.data();
+    for (int64_t i = 0; i < count; ++i)
+        std::memcpy(dst + static_cast<size_t>(rows[i]) * kDim, feats + static_cast<size_t>(i) * kDim, sizeof(float) * kDim);
+    return MI355REC_OK;
+}
+
 int node_query_labels(Node* h, const float* q12, int64_t exclude, const int32_t* set, int n_set, int topn_asked,
                       int64_t* out_idx, float* out_score, int* out_count, const char** why) {
     if (topn_asked <= 0) {

@@ -75,6 +75,10 @@ int node_query_mean_diverse(Node* h, const mi355playlist::Request& r, const mi35
 int node_set_groups(Node* h, const int32_t* groups, int64_t n, const char** why);
 // ROW PRIORS: one fp32 per row, already checked by the caller (finite, |p| <= 1); null drops them.
 int node_set_priors(Node* h, const float* priors, int64_t n, const char** why);
+// ROW UPDATES: rows[0..count) (checked by the caller: inside the catalogue, no duplicates) take feats[i * 12 ..].  The backend
+// derives nothing from a row ahead of a query, so the host matrix is all there is to rewrite; results already computed
+// (tickets of the stream) stay what they were.
+int node_update_rows(Node* h, const int64_t* rows, int64_t count, const float* feats, const char** why);
 int node_set_window(Node* h, int window, const char** why);
 int node_enqueue(Node* h, const float* q12, int64_t exclude, int topn, int64_t* ticket, const char** why);
 int node_flush(Node* h);

@@ -20,6 +20,7 @@ struct mi355rec_labels {
     int16_t* d_row_labels = nullptr;   // [ceil(n / 4) * 4]: the labels in ROW order, the last quad padded with -1 (what a playlist
                                        // call with a label set reads, playlist.hip.h "LABEL SET": 2 B per row)
     std::vector<int64_t> off;     // the same offsets on the host
+    std::vector<uint32_t> pos_of_row;   // the inverse of d_rows, on the host: made by the first mi355rec_update_rows (engine_update.hip.h)
     int grid_cap = 1;             // workgroups of a filtered launch at most (occupancy x CUs, and the handle's list slots)
     float build_ms = 0.0f;        // wall time of the mi355rec_set_labels call that built it
 };

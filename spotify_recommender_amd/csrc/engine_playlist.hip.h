@@ -214,7 +214,8 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     if (fresh_norms) {   // (on the handle's stream, ahead of the scan that reads them)
         hipLaunchKernelGGL(q8_build_kernel, dim3(static_cast<unsigned>((n_quads4 + 255) / 256)), dim3(256), 0, h->stream, h->d_feats, h->n,
                            n_quads4, static_cast<uint32_t*>(nullptr), P->d_norms, static_cast<const int32_t*>(nullptr),
-                           static_cast<const float*>(nullptr), 0, static_cast<int32_t*>(nullptr));
+                           static_cast<const float*>(nullptr), 0, static_cast<int32_t*>(nullptr),
+                           static_cast<const int64_t*>(nullptr), static_cast<const int64_t*>(nullptr), static_cast<uint2*>(nullptr), static_cast<float*>(nullptr));
         HIP_TRY(h, hipGetLastError());
         P->norms_built = true;   // (only now: every exit above leaves an array that the next request builds)
     }

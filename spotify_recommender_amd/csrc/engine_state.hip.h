@@ -132,6 +132,9 @@ struct mi355rec {
         BucketBufs bsample;                            // the bucketed sample that goes with d_q8
         float margin_mix = 0.0f, margin_mfma = 0.0f;   // of the replicas above (half_selfcheck_kernel's verdict)
         RowSide side;                                  // what the first handle's setters had left when its first lane was made
+        // every handle of the group, the first one included: kept by mi355rec_create_lane and mi355rec_destroy, never on the query
+        // path.  What mi355rec_update_rows asks whether another member has a streamed query open (engine_update.hip.h).
+        std::vector<mi355rec*> members;
     };
     SharedRows* shared = nullptr;
     bool is_lane = false;
@@ -319,6 +322,17 @@ struct mi355rec {
         int last_count = 0;              // queries of the last chunk (what the diagnostics cover)
     } bq;
     int batch_path = 0;               // MI355REC_BATCH_AUTO / _MULTI / _MFMA
+
+    // ROW UPDATES (mi355rec_update_rows, engine_update.hip.h): the counters of mi355rec_update_info and the staging of a call,
+    // allocated by the first update that needs it and grown up to mi355update::kStageRows rows
+    struct Update {
+        int64_t calls = 0, rows = 0;
+        int64_t rows_since_snapshot = 0;   // rows updated since the replicas and the bucketed sample were last built from all rows
+        float last_ms = 0.f;
+        int64_t cap = 0;                   // rows the two buffers below hold
+        char* h_stage = nullptr;           // pinned: cap rows x 48 B, cap row ids, cap sorted positions (int64 each)
+        char* d_stage = nullptr;           // the same on the device
+    } upd;
 
     // optional HIP-event timing of the enqueued kernels
     bool timing = false;
@@ -586,6 +600,11 @@ int build_replica_inner(mi355rec* h);
 int build_bucket_sample(mi355rec* h);
 int build_replica(mi355rec* h) {
     const int rc = build_replica_inner(h);
+    if (rc == MI355REC_OK) {   // every snapshot of the rows is fresh: the count of mi355rec_update_info starts again
+        h->upd.rows_since_snapshot = 0;
+        if (h->shared)
+            for (mi355rec* m : h->shared->members) m->upd.rows_since_snapshot = 0;
+    }
     if (rc != MI355REC_OK) {
         (void)hipStreamSynchronize(h->stream);
         free_replica(h);
@@ -608,7 +627,8 @@ int build_replica_inner(mi355rec* h) {
     const int64_t n_quads4 = (h->n + 3) / 4 * 4;
     hipLaunchKernelGGL(q8_build_kernel, dim3(static_cast<unsigned>((n_quads4 + 255) / 256)), dim3(256), 0, h->stream,
                        h->d_feats, h->n, n_quads4, reinterpret_cast<uint32_t*>(h->d_q8), static_cast<float*>(nullptr),
-                       static_cast<const int32_t*>(nullptr), static_cast<const float*>(nullptr), 0, static_cast<int32_t*>(nullptr));
+                       static_cast<const int32_t*>(nullptr), static_cast<const float*>(nullptr), 0, static_cast<int32_t*>(nullptr),
+                       static_cast<const int64_t*>(nullptr), static_cast<const int64_t*>(nullptr), static_cast<uint2*>(nullptr), static_cast<float*>(nullptr));
     if (timed) (void)hipEventRecord(b, h->stream);
     const hipError_t e = hipStreamSynchronize(h->stream);
     if (timed && e == hipSuccess) (void)hipEventElapsedTime(&h->replica_build_ms, a, b);
@@ -665,7 +685,8 @@ int build_bucket_sample(mi355rec* h) {
     HIP_TRY(h, hipMemcpyAsync(b.q8, base.data(), sizeof(int32_t) * static_cast<size_t>(n_base), hipMemcpyHostToDevice, h->stream));
     const dim3 build_grid(static_cast<unsigned>((n_base + 255) / 256));
     hipLaunchKernelGGL(q8_build_kernel, build_grid, dim3(256), 0, h->stream, h->d_feats, h->n, n_base, static_cast<uint32_t*>(nullptr),
-                       static_cast<float*>(nullptr), static_cast<const int32_t*>(b.q8), static_cast<const float*>(b.centroids), n_cent, b.rows);
+                       static_cast<float*>(nullptr), static_cast<const int32_t*>(b.q8), static_cast<const float*>(b.centroids), n_cent, b.rows,
+                       static_cast<const int64_t*>(nullptr), static_cast<const int64_t*>(nullptr), static_cast<uint2*>(nullptr), static_cast<float*>(nullptr));
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(bucket.data(), b.rows, sizeof(int32_t) * static_cast<size_t>(n_base), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -677,7 +698,8 @@ int build_bucket_sample(mi355rec* h) {
     // the rows' replica entries in that order, from the rows themselves (q8_build_kernel's second job: what the replica holds)
     hipLaunchKernelGGL(q8_build_kernel, build_grid, dim3(256), 0, h->stream, h->d_feats, h->n, n_base, static_cast<uint32_t*>(b.q8),
                        static_cast<float*>(nullptr), static_cast<const int32_t*>(b.rows), static_cast<const float*>(nullptr), 0,
-                       static_cast<int32_t*>(nullptr));
+                       static_cast<int32_t*>(nullptr),
+                       static_cast<const int64_t*>(nullptr), static_cast<const int64_t*>(nullptr), static_cast<uint2*>(nullptr), static_cast<float*>(nullptr));
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));   // (the host vectors above are read until here)
     b.regions = static_cast<int>(regions);

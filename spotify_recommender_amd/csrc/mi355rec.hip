@@ -7,6 +7,7 @@
 #include "engine_labels.hip.h"
 #include "engine_playlist.hip.h"
 #include "engine_diverse.hip.h"
+#include "engine_update.hip.h"
 
 extern "C" {
 
@@ -117,6 +118,16 @@ void mi355rec_destroy(mi355rec_t* h) {
     if (h->h_done) (void)hipHostFree(h->h_done);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     if (h->order_ev) (void)hipEventDestroy(h->order_ev);
+    if (h->upd.h_stage) (void)hipHostFree(h->upd.h_stage);
+    if (h->upd.d_stage) (void)hipFree(h->upd.d_stage);
+    if (h->shared) {
+        std::vector<mi355rec*>& m = h->shared->members;
+        for (size_t i = 0; i < m.size(); ++i)
+            if (m[i] == h) {
+                m.erase(m.begin() + static_cast<std::ptrdiff_t>(i));
+                break;
+            }
+    }
     if (h->shared && h->shared->refs.fetch_sub(1) == 1) {   // the last of a group of lanes: the rows and the replicas go with it
         void* bufs[] = {h->shared->owned_feats, h->shared->d_half, h->shared->d_q8};
         for (void* b : bufs)
@@ -213,6 +224,15 @@ int mi355rec_create_lane(mi355rec_t* parent, mi355rec_t** out) {
     }
     if (!parent->shared) {   // from now on the group owns what the parent owned
         mi355rec::SharedRows* group = new (std::nothrow) mi355rec::SharedRows();   // (no exception may cross the C-ABI)
+        if (group) {
+            try {
+                group->members.reserve(8);
+                group->members.push_back(parent);
+            } catch (const std::bad_alloc&) {
+                delete group;
+                group = nullptr;
+            }
+        }
         if (!group) {
             mi355rec_destroy(lane);
             return fail(parent, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for the lane group");
@@ -228,8 +248,15 @@ int mi355rec_create_lane(mi355rec_t* parent, mi355rec_t** out) {
         parent->own_side = RowSide();
         parent->side = &group->side;
     }
+    try {
+        parent->shared->members.push_back(lane);   // (the group's registry: mi355rec_update_rows, engine_update.hip.h)
+    } catch (const std::bad_alloc&) {
+        mi355rec_destroy(lane);   // (it is no member yet: lane->shared is null)
+        return fail(parent, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for the lane group");
+    }
     parent->shared->refs.fetch_add(1);
     lane->shared = parent->shared;
+    lane->upd.rows_since_snapshot = parent->upd.rows_since_snapshot;
     lane->side = &parent->shared->side;
     lane->d_half = parent->d_half;
     lane->d_q8 = parent->d_q8;

@@ -23,6 +23,7 @@
 #include "cpu_backend.h"
 #include "mi355rec_diag.h"
 #include "playlist_request.h"
+#include "rows_update.h"
 #include "rowset.h"
 
 namespace mi355node {
@@ -278,11 +279,7 @@ int cpu_result(mi355rec_sharded* h, int rc, const char* why) {
 }
 
 // balanced contiguous blocks: the first n % g shards hold one row more
-void bounds(int64_t n, int g, int r, int64_t& lo, int64_t& hi) {
-    const int64_t per = n / g, rem = n % g;
-    lo = r * per + (r < rem ? r : rem);
-    hi = lo + per + (r < rem ? 1 : 0);
-}
+void bounds(int64_t n, int g, int r, int64_t& lo, int64_t& hi) { mi355update::shard_bounds(n, g, r, lo, hi); }
 
 int drain_workers(mi355rec_sharded* h);
 

@@ -46,42 +46,57 @@ constexpr uint32_t kHalfNaN2 = kBqNaN2;        // two fp16 quiet NaNs: "always s
 // (the sampling geometry — kHalfSeedBlock, kHalfSeedWaves, kHalfSeedMaxGrid — and the hand-off types live in handoff.hip.h)
 
 // ---- building the replica ---------------------------------------------------------
+// The two packers below are what BOTH builders call (replica_build_kernel here, q8_build_kernel in replica_q8.hip.h, whose
+// update job rewrites single entries in place): an updated entry is the rebuilt entry by construction.
+
+// |row|^2 as every normalisation of a stored row takes it: one product, then eleven fmas in feature order (the batched
+// passes' chain, bq_pass_kernel, so one bound covers them all).
+__device__ __forceinline__ float replica_norm2(const float4& a, const float4& b, const float4& c) {
+    float tot = a.x * a.x;
+    tot = __builtin_fmaf(a.y, a.y, tot);
+    tot = __builtin_fmaf(a.z, a.z, tot);
+    tot = __builtin_fmaf(a.w, a.w, tot);
+    tot = __builtin_fmaf(b.x, b.x, tot);
+    tot = __builtin_fmaf(b.y, b.y, tot);
+    tot = __builtin_fmaf(b.z, b.z, tot);
+    tot = __builtin_fmaf(b.w, b.w, tot);
+    tot = __builtin_fmaf(c.x, c.x, tot);
+    tot = __builtin_fmaf(c.y, c.y, tot);
+    tot = __builtin_fmaf(c.z, c.z, tot);
+    tot = __builtin_fmaf(c.w, c.w, tot);
+    return tot;
+}
+
+// The fp16 entry of a row (six fp16 pairs; tot = replica_norm2 of it): normalised, all zero for a zero row, NaN for every
+// other row the bound is not claimed for.
+__device__ __forceinline__ void half_pack_row(const float4& a, const float4& b, const float4& c, float tot, uint32_t (&p)[6]) {
+    p[0] = p[1] = p[2] = p[3] = p[4] = p[5] = kHalfNaN2;
+    const bool valid = tot >= kBqMinNorm2 && tot <= kBqMaxNorm2;
+    if (valid) {
+        const float inv = __builtin_amdgcn_rsqf(tot);
+        p[0] = bq_pack_h2(a.x * inv, a.y * inv); p[1] = bq_pack_h2(a.z * inv, a.w * inv);
+        p[2] = bq_pack_h2(b.x * inv, b.y * inv); p[3] = bq_pack_h2(b.z * inv, b.w * inv);
+        p[4] = bq_pack_h2(c.x * inv, c.y * inv); p[5] = bq_pack_h2(c.z * inv, c.w * inv);
+    } else if (tot == 0.0f) {
+        p[0] = p[1] = p[2] = p[3] = p[4] = p[5] = 0u;
+    }
+}
+
 // One thread per row; rows [n, n_padded) (n_padded even) are padding and hold NaN.
 __global__ __launch_bounds__(256) void replica_build_kernel(const float* __restrict__ feats, int64_t n, int64_t n_padded,
                                                             uint2* __restrict__ half) {
     const int64_t row = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (row >= n_padded) return;
-    uint32_t p0 = kHalfNaN2, p1 = kHalfNaN2, p2 = kHalfNaN2, p3 = kHalfNaN2, p4 = kHalfNaN2, p5 = kHalfNaN2;
+    uint32_t p[6] = {kHalfNaN2, kHalfNaN2, kHalfNaN2, kHalfNaN2, kHalfNaN2, kHalfNaN2};
     if (row < n) {
-        const float4* p = reinterpret_cast<const float4*>(feats) + row * 3;
-        const float4 a = p[0], b = p[1], c = p[2];
-        // the same normalisation as the batched passes (bq_pass_kernel), so one bound covers both
-        float tot = a.x * a.x;
-        tot = __builtin_fmaf(a.y, a.y, tot);
-        tot = __builtin_fmaf(a.z, a.z, tot);
-        tot = __builtin_fmaf(a.w, a.w, tot);
-        tot = __builtin_fmaf(b.x, b.x, tot);
-        tot = __builtin_fmaf(b.y, b.y, tot);
-        tot = __builtin_fmaf(b.z, b.z, tot);
-        tot = __builtin_fmaf(b.w, b.w, tot);
-        tot = __builtin_fmaf(c.x, c.x, tot);
-        tot = __builtin_fmaf(c.y, c.y, tot);
-        tot = __builtin_fmaf(c.z, c.z, tot);
-        tot = __builtin_fmaf(c.w, c.w, tot);
-        const bool valid = tot >= kBqMinNorm2 && tot <= kBqMaxNorm2;
-        if (valid) {
-            const float inv = __builtin_amdgcn_rsqf(tot);
-            p0 = bq_pack_h2(a.x * inv, a.y * inv); p1 = bq_pack_h2(a.z * inv, a.w * inv);
-            p2 = bq_pack_h2(b.x * inv, b.y * inv); p3 = bq_pack_h2(b.z * inv, b.w * inv);
-            p4 = bq_pack_h2(c.x * inv, c.y * inv); p5 = bq_pack_h2(c.z * inv, c.w * inv);
-        } else if (tot == 0.0f) {
-            p0 = p1 = p2 = p3 = p4 = p5 = 0u;
-        }
+        const float4* src = reinterpret_cast<const float4*>(feats) + row * 3;
+        const float4 a = src[0], b = src[1], c = src[2];
+        half_pack_row(a, b, c, replica_norm2(a, b, c), p);
     }
     uint2* dst = half + row * 3;
-    dst[0] = make_uint2(p0, p1);
-    dst[1] = make_uint2(p2, p3);
-    dst[2] = make_uint2(p4, p5);
+    dst[0] = make_uint2(p[0], p[1]);
+    dst[1] = make_uint2(p[2], p[3]);
+    dst[2] = make_uint2(p[4], p[5]);
 }
 
 // ---- the query in fp16 --------------------------------------------------------------

@@ -74,10 +74,36 @@ constexpr uint32_t kQ8Special = 0x80u;       // first byte of a row the bound is
 //   * centroids != null: bucket[e] = the centroid with the largest dot product row . c / |c| (the row's own norm scales
 //     every candidate alike): a sequential fma chain in feature order and centroid order, so deterministic, and a tie
 //     keeps the LOWER centroid (strict >).  A centroid whose norm is zero or not finite counts as score 0.
+//   * upd_dst != null — the UPDATE job (mi355rec_update_rows, engine_update.hip.h): thread e reads source row upd_src[e] (row e
+//     where upd_src is null: the staged rows of the call) of `feats`, which holds n rows, and stores at row upd_dst[e] instead of
+//     slot e: the 8-bit entry, the fp16 entry (half), the norm and the fp32 row itself (rows_out), each where its pointer is
+//     given.  n_padded is the number of rows of the call; padding is never written.  The label-grouped copy is the same job
+//     with only rows_out and upd_dst = the rows' sorted positions.  half and rows_out are null in every other job.
+
+// The 8-bit entry of a row (three dwords; tot = replica_norm2 of it): left as it is — the special marker — unless the row is
+// valid or exactly zero.
+__device__ __forceinline__ void q8_pack_row(const float4& a, const float4& b, const float4& c, float tot, uint32_t& d0, uint32_t& d1,
+                                            uint32_t& d2) {
+    const bool valid = tot >= kBqMinNorm2 && tot <= kBqMaxNorm2;
+    if (valid || tot == 0.0f) {
+        const float inv = valid ? __builtin_amdgcn_rsqf(tot) * 127.0f : 0.0f;
+        auto q = [&](float x) {   // round to nearest; |x * inv| <= 127 (1 + 1e-6); two's complement byte
+            int k = static_cast<int>(__builtin_rintf(x * inv));
+            k = k > 127 ? 127 : (k < -127 ? -127 : k);
+            return static_cast<uint32_t>(k) & 0xffu;
+        };
+        d0 = q(a.x) | (q(a.y) << 8) | (q(a.z) << 16) | (q(a.w) << 24);
+        d1 = q(b.x) | (q(b.y) << 8) | (q(b.z) << 16) | (q(b.w) << 24);
+        d2 = q(c.x) | (q(c.y) << 8) | (q(c.z) << 16) | (q(c.w) << 24);
+    }
+}
+
 __global__ __launch_bounds__(256) void q8_build_kernel(const float* __restrict__ feats, int64_t n, int64_t n_padded,
                                                        uint32_t* __restrict__ q8, float* __restrict__ norms,
                                                        const int32_t* __restrict__ pick, const float* __restrict__ centroids,
-                                                       int n_centroids, int32_t* __restrict__ bucket) {
+                                                       int n_centroids, int32_t* __restrict__ bucket,
+                                                       const int64_t* __restrict__ upd_src, const int64_t* __restrict__ upd_dst,
+                                                       uint2* __restrict__ half, float* __restrict__ rows_out) {
     __shared__ float s_inv[1024];
     if (centroids) {   // uniform
         n_centroids = n_centroids < 1024 ? n_centroids : 1024;
@@ -91,16 +117,28 @@ __global__ __launch_bounds__(256) void q8_build_kernel(const float* __restrict__
     }
     const int64_t slot = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (slot >= n_padded) return;
-    int64_t row = slot;
+    int64_t row = slot, out = slot;
     if (pick) {   // uniform
         row = pick[slot];
         row = row >= 0 ? row : n;   // (padding)
     }
+    if (upd_dst) {   // uniform: the update job
+        row = upd_src ? upd_src[slot] : slot;
+        out = upd_dst[slot];
+        if (row < 0 || row >= n) return;   // (the host has checked the list: an update never writes padding)
+    }
     uint32_t d0 = 0x80808080u, d1 = 0x80808080u, d2 = 0x80808080u;   // special
+    uint32_t hp[6] = {kHalfNaN2, kHalfNaN2, kHalfNaN2, kHalfNaN2, kHalfNaN2, kHalfNaN2};
     float seq = 0.0f;
     if (row < n) {
         const float4* p = reinterpret_cast<const float4*>(feats) + row * 3;
         const float4 a = p[0], b = p[1], c = p[2];
+        if (rows_out) {   // uniform
+            float4* dst = reinterpret_cast<float4*>(rows_out) + out * 3;
+            dst[0] = a;
+            dst[1] = b;
+            dst[2] = c;
+        }
         if (centroids) {   // uniform
             const float f[kDim] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
             float best = -__builtin_inff();
@@ -122,41 +160,26 @@ __global__ __launch_bounds__(256) void q8_build_kernel(const float* __restrict__
 #pragma unroll
             for (int j = 0; j < kDim; ++j) seq = seq + f[j] * f[j];
         }
-        // the normalisation of the fp16 replica and of the batched passes (replica_build_kernel)
-        float tot = a.x * a.x;
-        tot = __builtin_fmaf(a.y, a.y, tot);
-        tot = __builtin_fmaf(a.z, a.z, tot);
-        tot = __builtin_fmaf(a.w, a.w, tot);
-        tot = __builtin_fmaf(b.x, b.x, tot);
-        tot = __builtin_fmaf(b.y, b.y, tot);
-        tot = __builtin_fmaf(b.z, b.z, tot);
-        tot = __builtin_fmaf(b.w, b.w, tot);
-        tot = __builtin_fmaf(c.x, c.x, tot);
-        tot = __builtin_fmaf(c.y, c.y, tot);
-        tot = __builtin_fmaf(c.z, c.z, tot);
-        tot = __builtin_fmaf(c.w, c.w, tot);
-        const bool valid = tot >= kBqMinNorm2 && tot <= kBqMaxNorm2;
-        if (valid || tot == 0.0f) {
-            const float inv = valid ? __builtin_amdgcn_rsqf(tot) * 127.0f : 0.0f;
-            auto q = [&](float x) {   // round to nearest; |x * inv| <= 127 (1 + 1e-6); two's complement byte
-                int k = static_cast<int>(__builtin_rintf(x * inv));
-                k = k > 127 ? 127 : (k < -127 ? -127 : k);
-                return static_cast<uint32_t>(k) & 0xffu;
-            };
-            d0 = q(a.x) | (q(a.y) << 8) | (q(a.z) << 16) | (q(a.w) << 24);
-            d1 = q(b.x) | (q(b.y) << 8) | (q(b.z) << 16) | (q(b.w) << 24);
-            d2 = q(c.x) | (q(c.y) << 8) | (q(c.z) << 16) | (q(c.w) << 24);
-        }
+        // the normalisation of the fp16 replica and of the batched passes (replica_norm2, replica.hip.h)
+        const float tot = replica_norm2(a, b, c);
+        q8_pack_row(a, b, c, tot, d0, d1, d2);
+        if (half) half_pack_row(a, b, c, tot, hp);   // uniform
     } else if (centroids) {   // uniform
         bucket[slot] = 0;     // (padding: any bucket in range)
     }
     if (q8) {   // uniform
-        uint32_t* dst = q8 + slot * 3;
+        uint32_t* dst = q8 + out * 3;
         dst[0] = d0;
         dst[1] = d1;
         dst[2] = d2;
     }
-    if (norms) norms[slot] = sqrtf(seq);   // uniform
+    if (half) {   // uniform
+        uint2* dst = half + out * 3;
+        dst[0] = make_uint2(hp[0], hp[1]);
+        dst[1] = make_uint2(hp[2], hp[3]);
+        dst[2] = make_uint2(hp[4], hp[5]);
+    }
+    if (norms) norms[out] = sqrtf(seq);   // uniform
 }
 
 // ---- the query ------------------------------------------------------------------------------------------

@@ -955,6 +955,75 @@ int mi355rec_sharded_rowset_create(mi355rec_sharded_t* h, const int64_t* global_
     return MI355REC_OK;
 }
 
+// ROW UPDATES (include/mi355rec_diag.h): the node handle owns its rows, so an update always brings them.  The open window is closed
+// and the workers are drained first (tickets already waited for stay readable: their results are in host memory); then the
+// caller's thread drives the engines itself.  Row-sharded: every shard gets the rows it owns, made local.  Replicated: every
+// device once — a replica on a device that already holds one is a lane of it and shares its rows and replicas.
+int mi355rec_sharded_update_rows(mi355rec_sharded_t* h, const int64_t* global_rows, int64_t count, const float* feats_host) {
+    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    if (count < 0 || (count > 0 && !global_rows)) return sfail(h, MI355REC_ERR_INVALID_ARG, "null rows / negative count");
+    if (count == 0) return MI355REC_OK;
+    if (!feats_host) return sfail(h, MI355REC_ERR_INVALID_ARG, "a node handle owns its rows: an update brings them (feats_host is NULL)");
+    std::vector<mi355update::ShardPart> parts;
+    std::vector<float> rows;
+    try {
+        int64_t at = 0;
+        const mi355update::Bad bad = mi355update::check_rows(global_rows, count, h->n, &at);
+        if (bad != mi355update::kFine) {
+            char why[160];
+            mi355update::describe(bad, global_rows, at, h->n, why, sizeof why);
+            return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+        }
+        if (!h->cpu && !h->replicated && h->shards.size() > 1) {
+            std::vector<int64_t> lo(h->shards.size());
+            for (size_t r = 0; r < h->shards.size(); ++r) lo[r] = h->shards[r].lo;
+            mi355update::split_by_shard(global_rows, count, lo.data(), static_cast<int>(lo.size()), parts);
+        }
+    } catch (const std::bad_alloc&) {
+        return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for an update of %lld rows", (long long)count);
+    }
+    if (h->cpu) {
+        const char* why = nullptr;
+        return cpu_result(h, mi355cpu::node_update_rows(h->cpu, global_rows, count, feats_host, &why), why);
+    }
+    DeviceRestore restore;
+    int rc = stream_flush(h);
+    if (rc) return rc;
+    rc = drain_workers(h);
+    if (rc) return rc;
+    // (the workers have only ENQUEUED the window's scans: every shard's stream is drained before a row is written, as ensure_stream
+    // does before it replaces the stream's buffers — the engines wait for their lanes' streams again themselves)
+    for (Shard& s : h->shards) {
+        S_HIP(h, hipSetDevice(s.device));
+        S_HIP(h, hipStreamSynchronize(s.stream));
+    }
+    // A failure on one shard leaves the shards before it updated: the update may have been applied in part, and repeating it
+    // (the same rows, the same features) is safe.
+    for (size_t r = 0; r < h->shards.size(); ++r) {
+        Shard& s = h->shards[r];
+        if (s.hi == s.lo) continue;
+        S_HIP(h, hipSetDevice(s.device));
+        if (parts.empty()) {   // one shard, or replicas: the whole list, once per device
+            bool lane = false;
+            for (size_t p = 0; p < r && !lane; ++p) lane = h->shards[p].device == s.device;
+            if (lane) continue;
+            S_ENG(h, s, mi355rec_update_rows(s.engine, global_rows, count, feats_host));
+            continue;
+        }
+        const mi355update::ShardPart& part = parts[r];
+        if (part.local.empty()) continue;
+        try {
+            rows.resize(part.local.size() * MI355REC_DIM);
+        } catch (const std::bad_alloc&) {
+            return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for an update of %lld rows", (long long)count);
+        }
+        for (size_t i = 0; i < part.at.size(); ++i)
+            std::memcpy(&rows[i * MI355REC_DIM], feats_host + static_cast<size_t>(part.at[i]) * MI355REC_DIM, sizeof(float) * MI355REC_DIM);
+        S_ENG(h, s, mi355rec_update_rows(s.engine, part.local.data(), static_cast<int64_t>(part.local.size()), rows.data()));
+    }
+    return MI355REC_OK;
+}
+
 int mi355rec_sharded_scores_row(mi355rec_sharded_t* h, int64_t global_row, float* out_host) {
     if (!h || !out_host) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     if (global_row < 0 || global_row >= h->n)

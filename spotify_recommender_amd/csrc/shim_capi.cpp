@@ -185,6 +185,12 @@ int shim_set_row_set(void* h, const int* songs, int n_songs, int only) {
     }
     return c->rec.setRowSet(std::vector<int>(songs, songs + n_songs), only != 0) ? 1 : 0;
 }
+// Recommender::updateSongs (n_features floats for n_songs songs: a length that differs is refused by the class).
+int shim_update_songs(void* h, const int* songs, int n_songs, const float* features, int64_t n_features) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    return c->rec.updateSongs(std::vector<int>(songs, songs + (n_songs > 0 ? n_songs : 0)),
+                              std::vector<float>(features, features + (n_features > 0 ? n_features : 0))) ? 1 : 0;
+}
 // Recommender::recommendForPlaylist.
 int64_t shim_recommend_for_playlist(void* h, const int* songs, int n_songs, int topn, const int* exclude, int n_exclude, int* out,
                                     float* scores, int64_t cap) {

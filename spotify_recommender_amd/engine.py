@@ -645,6 +645,55 @@ class CosineEngine(_RowSets):
         """After overwriting a borrowed catalogue in place (synchronous)."""
         capi.check(self._lib.mi355rec_rebuild_replica(self._h), self._h)
 
+    # -- ROW UPDATES ------------------------------------------------------------
+    def update_rows(self, local_rows, feats=None) -> None:
+        """Rows change in place (mi355rec_update_rows): afterwards every route of this handle and of its lanes answers as a handle
+        freshly created from the updated matrix would.  local_rows: distinct rows of this handle; feats: [len(local_rows), 12]
+        float32, or None when the caller has already written those rows of the torch tensor the engine was created over.
+        Over such a tensor, feats is written into the tensor here (the engine borrows it), then the derived data is redone; the
+        library is asked first, so a refused update leaves the tensor as it was (update_info counts that path as two calls).
+        Flush every lane first (enqueue_flush) and let no other thread use the group meanwhile."""
+        rows = np.ascontiguousarray(np.asarray(local_rows, dtype=np.int64).reshape(-1))
+        rows_p = rows.ctypes.data_as(ctypes.c_void_p) if rows.size else None
+        if feats is not None:
+            arr = _np_f32(feats.detach().cpu().numpy() if hasattr(feats, "detach") else feats).reshape(-1, capi.DIM)
+            if arr.shape[0] != rows.size:
+                raise ValueError(f"{arr.shape[0]} feature rows for {rows.size} row ids")
+            if self._keepalive is None:
+                capi.check(self._lib.mi355rec_update_rows(self._h, rows_p, rows.size, arr.ctypes.data_as(ctypes.c_void_p)), self._h)
+                return
+            # The library is asked FIRST, with NULL rows and the tensor as it is (in effect a no-op: it redoes the entries of
+            # unchanged rows): whatever it refuses (a row out of range or named twice, another lane with a streamed query open) is
+            # refused before the tensor is written.
+            import torch
+            t = self._keepalive
+            torch.cuda.synchronize(t.device)
+            capi.check(self._lib.mi355rec_update_rows(self._h, rows_p, rows.size, None), self._h)
+            t[torch.from_numpy(rows).to(t.device)] = torch.from_numpy(arr).to(t.device)
+        if self._keepalive is not None:
+            import torch
+            torch.cuda.synchronize(self._keepalive.device)   # the tensor's writes are done before the library reads the rows
+        capi.check(self._lib.mi355rec_update_rows(self._h, rows_p, rows.size, None), self._h)
+
+    def update_info(self) -> dict:
+        """{"calls", "rows", "rows_since_snapshot", "last_ms"} (mi355rec_update_info): rows_since_snapshot is the cue for an eventual
+        rebuild_replica, which refreshes the bucketed sample and the anchor tables and resets it."""
+        info = capi.UpdateInfo()
+        info.size = ctypes.sizeof(capi.UpdateInfo)
+        capi.check(self._lib.mi355rec_update_info(self._h, ctypes.byref(info)), self._h)
+        return {"calls": info.calls, "rows": info.rows, "rows_since_snapshot": info.rows_since_snapshot, "last_ms": info.last_ms}
+
+    def replica_entries(self, local_rows):
+        """The stored replica entries of the given rows (mi355rec_replica_entries): (fp16 [k, 24] uint8, 8-bit [k, 12] uint8,
+        norms [k] float32 — NaN-filled where the handle has built no norms).  For tests: an updated handle against a fresh one."""
+        rows = np.ascontiguousarray(np.asarray(local_rows, dtype=np.int64).reshape(-1))
+        half = np.zeros((rows.size, 24), dtype=np.uint8)
+        q8 = np.zeros((rows.size, 12), dtype=np.uint8)
+        norms = np.full(rows.size, np.nan, dtype=np.float32)
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+        capi.check(self._lib.mi355rec_replica_entries(self._h, ptr(rows), rows.size, ptr(half), ptr(q8), ptr(norms)), self._h)
+        return half, q8, norms
+
     def set_batch_path(self, path: int) -> None:
         """capi.BATCH_AUTO / BATCH_MULTI / BATCH_MFMA (tests, A/B measurements)."""
         capi.check(self._lib.mi355rec_set_batch_path(self._h, int(path)), self._h)
@@ -1027,6 +1076,17 @@ class NodeEngine(_RowSets):
                                     return_mmr=False, labels=None, prior_weight=None, seen=None, only=None):
         return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr,
                               labels=labels, prior_weight=prior_weight, seen=seen, only=only)
+
+    def update_rows(self, global_rows, feats) -> None:
+        """Rows change in place on every shard or replica that holds them (mi355rec_sharded_update_rows); the node owns its rows, so
+        feats ([len(global_rows), 12] float32) is required.  Closes the open window and drains the workers first."""
+        rows = np.ascontiguousarray(np.asarray(global_rows, dtype=np.int64).reshape(-1))
+        arr = None if feats is None else _np_f32(feats).reshape(-1, capi.DIM)
+        if arr is not None and arr.shape[0] != rows.size:
+            raise ValueError(f"{arr.shape[0]} feature rows for {rows.size} row ids")
+        self._check(self._lib.mi355rec_sharded_update_rows(
+            self._h, rows.ctypes.data_as(ctypes.c_void_p) if rows.size else None, rows.size,
+            None if arr is None else arr.ctypes.data_as(ctypes.c_void_p)))
 
     def scores_row(self, global_row: int) -> np.ndarray:
         out = np.empty(self.rows, dtype=np.float32)
