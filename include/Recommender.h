@@ -188,6 +188,30 @@ public:
     bool setRowSet(const std::vector<int>& songIndices, bool only = false);
     void clearRowSet();
 
+    // Extension: one description of a request.  Every method above that takes a playlist (and recommendByIndexWhere,
+    // recommendDiverse, recommendByIndexCapped, which take the one-song playlist) fills a Query and runs it through
+    // recommendQuery; a caller may do so itself and combine what no overload combines (scales with alsoExclude, say).  The
+    // fields mean what the parameters of those methods mean; messages and {} on bad input are theirs.  maxPerArtist = 0 asks
+    // for no cap; a cap without `diverse` is the plain order with the cap (lambda stays 1); `diverse` with lambda = 1 within genres
+    // or with a prior weight is the plain request (the same result without a pool).  With euclidean set, lastScores()
+    // holds distances, and weights, diverse, maxPerArtist and priorWeight are refused.  The row set of setRowSet applies.
+    struct Query {
+        std::vector<int> songs;            // 1 to 32
+        std::vector<float> weights;        // one per song, or none
+        std::vector<FeatureRange> where;
+        std::vector<int> alsoExclude;      // up to 1024
+        std::vector<int> genreIds;         // empty: every genre
+        bool diverse = false;              // re-rank the `pool` best by maximal marginal relevance with `lambda`
+        float lambda = 1.0f;
+        int pool = 0;                      // 0: min(1024, 4 * topN), with a cap 8 * topN
+        int maxPerArtist = 0;
+        float priorWeight = 0.0f;
+        std::vector<float> scales;         // 12, or none
+        bool euclidean = false;
+        int topN = 10;
+    };
+    std::vector<int> recommendQuery(const Query& query);
+
     // Extension: in-place updates (include/mi355rec_diag.h, "ROW UPDATES").  updateSongs gives the songs at `indices` (distinct,
     // inside the catalogue) new features: 12 floats per song in Song.h order, features[12 * i ..] for indices[i].  Every later
     // recommendation answers as if the catalogue had been initialised with the new features; ids, names, genre ids, groups,

@@ -11,6 +11,17 @@
 
 #include "mi355rec_diag.h"   // (the core + mi355rec_sharded_note / _placement for the messages)
 
+namespace {
+// A per-song array that the engine is handed by the first call that needs it (initialize costs what it costs without it): the
+// values (one per song; empty: not known) and whether THIS engine has them yet.
+template <class T>
+struct PerSong {
+    std::vector<T> values;
+    bool uploaded = false;
+    void set(const std::vector<T>& v) { values = v, uploaded = false; }
+};
+}  // namespace
+
 struct Recommender::Impl {
     bool initialized = false;
     bool gpuEnabled = false;
@@ -25,20 +36,18 @@ struct Recommender::Impl {
     std::vector<std::string> lowerNames;
     std::unordered_map<std::string, int> byId;
 
-    // genre ids of the songs (one per song, -1 = none; empty: not known) and whether the engine has them yet: they are
-    // uploaded by the first genre-restricted query, so that initialize costs what it costs without them
-    std::vector<int> genreIds;
-    bool labelsUploaded = false;
+    PerSong<int> genres;     // genre ids (-1 = none): the first genre-restricted query uploads them
+    PerSong<int> groups;     // group ids (-1 = none): the first capped query
+    PerSong<float> priors;   // setPriors: the first query with a prior weight
 
-    // group ids of the songs (one per song, -1 = none; empty: not known): uploaded by the first capped query, likewise
-    std::vector<int> groupIds;
-    std::vector<float> priors;       // setPriors: one per song (empty: none)
-    bool priorsUploaded = false;
-    bool groupsUploaded = false;
-
-    // setRowSet: the engine's set (null: none) and its mode; destroyed before the engine
+    // setRowSet: the engine's set (null: none) and its mode.  It belongs to `engine`: dropRowSet before the engine goes.
     mi355rec_rowset_t* rowSet = nullptr;
     bool rowSetOnly = false;
+    void dropRowSet() {
+        mi355rec_rowset_destroy(rowSet);
+        rowSet = nullptr;
+        rowSetOnly = false;
+    }
 
     std::vector<int64_t> idxBuf;
     std::vector<float> scoreBuf;
@@ -58,7 +67,7 @@ std::string toLower(const std::string& str) {  // Recommender.cu:329-334
 Recommender::Recommender() : impl_(new Impl()) {}
 
 Recommender::~Recommender() {  // Recommender.cu:86-98
-    mi355rec_rowset_destroy(impl_->rowSet);
+    impl_->dropRowSet();
     if (impl_->engine) mi355rec_sharded_destroy(impl_->engine);
     delete impl_;
 }
@@ -82,16 +91,16 @@ bool Recommender::initialize(const std::vector<Song>& songs) {  // Recommender.c
     impl_->lowerNames.reserve(songs.size());
     impl_->byId.clear();
     impl_->byId.reserve(songs.size() * 2);
-    impl_->genreIds.resize(songs.size());
+    impl_->genres.values.resize(songs.size());
     {
         std::vector<std::string> artists;
         artists.reserve(songs.size());
         for (const Song& s : songs) artists.push_back(s.artists);
-        impl_->groupIds = artistGroupIds(artists);
+        impl_->groups.values = artistGroupIds(artists);
     }
     for (size_t i = 0; i < songs.size(); ++i) {
         std::copy(songs[i].features, songs[i].features + FEATURE_COUNT, matrix.begin() + i * FEATURE_COUNT);
-        impl_->genreIds[i] = songs[i].genre_id;
+        impl_->genres.values[i] = songs[i].genre_id;
         impl_->lowerNames.push_back(toLower(songs[i].track_name));
         impl_->byId.emplace(songs[i].track_id, static_cast<int>(i));  // keeps the first
     }
@@ -117,22 +126,22 @@ bool Recommender::initialize(const std::vector<float>& features, const std::vect
         impl_->lowerNames.push_back(toLower(trackNames[i]));
         impl_->byId.emplace(trackIds[i], static_cast<int>(i));
     }
-    impl_->genreIds.clear();
-    impl_->groupIds.clear();
+    impl_->genres.values.clear();
+    impl_->groups.values.clear();
     return startEngine(impl_, features.data(), trackIds.size());
 }
 
 namespace {
 
 bool startEngine(Recommender::Impl* impl, const float* matrix, size_t n) {
+    impl->dropRowSet();   // (a set is the engine's that made it: after a re-initialisation the class holds none)
     if (impl->engine) {
         mi355rec_sharded_destroy(impl->engine);
         impl->engine = nullptr;
     }
     impl->initialized = false;
     impl->gpuEnabled = false;
-    impl->labelsUploaded = false;
-    impl->groupsUploaded = false;
+    impl->genres.uploaded = impl->groups.uploaded = impl->priors.uploaded = false;   // (the new engine has none of them)
     impl->numSongs = static_cast<int>(n);
     // The reference pins device 0 (Recommender.cu:124).  Here the library places the catalogue itself: one device up
     // to 7.9 M rows, row-sharded over as many as keep 4 M rows per shard beyond that (one process, one stream per
@@ -232,8 +241,7 @@ bool Recommender::setGroupIds(const std::vector<int>& groupIds) {
             std::cerr << "Error: group id " << g << ": a group id is >= 0, or -1 for no group" << std::endl;
             return false;
         }
-    impl_->groupIds = groupIds;
-    impl_->groupsUploaded = false;
+    impl_->groups.set(groupIds);
     return true;
 }
 
@@ -247,8 +255,7 @@ bool Recommender::setPriors(const std::vector<float>& priors) {
             std::cerr << "Error: prior " << priors[i] << " of song " << i << ": a prior is finite with |p| <= 1" << std::endl;
             return false;
         }
-    impl_->priors = priors;
-    impl_->priorsUploaded = false;
+    impl_->priors.set(priors);
     return true;
 }
 
@@ -280,21 +287,17 @@ bool Recommender::setRowSet(const std::vector<int>& songIndices, bool only) {
         std::cerr << "Error: " << mi355rec_sharded_last_error(impl_->engine) << std::endl;
         return false;
     }
-    mi355rec_rowset_destroy(impl_->rowSet);
+    impl_->dropRowSet();
     impl_->rowSet = fresh;
     impl_->rowSetOnly = only;
     return true;
 }
 
-void Recommender::clearRowSet() {
-    mi355rec_rowset_destroy(impl_->rowSet);
-    impl_->rowSet = nullptr;
-    impl_->rowSetOnly = false;
-}
+void Recommender::clearRowSet() { impl_->dropRowSet(); }
 
 namespace {
-// The per-request extras of a call: the scales (null: none) and the row set of setRowSet (none: a null pointer; an ext of
-// two null pointers is the plain request).
+// The per-request extras of a call (FEATURE SCALES, ROW SETS): the scales (null: none) and the row set of setRowSet (none: a null
+// pointer; an ext of two null pointers is the plain request).
 mi355rec_request_ext_t requestExt(const Recommender::Impl* impl, const float* scales) {
     mi355rec_request_ext_t ext{};
     ext.size = sizeof ext;
@@ -315,26 +318,31 @@ bool Recommender::setGenreIds(const std::vector<int>& genreIds) {
             std::cerr << "Error: genre id " << g << " out of [-1, " << MI355REC_MAX_LABELS << ")" << std::endl;
             return false;
         }
-    impl_->genreIds = genreIds;
-    impl_->labelsUploaded = false;
+    impl_->genres.set(genreIds);
     return true;
 }
 
 namespace {
-// The first genre-restricted query hands the songs' genres to the engine.
-bool uploadLabels(Recommender::Impl* impl) {
-    if (impl->labelsUploaded) return true;
-    if (impl->genreIds.size() != static_cast<size_t>(impl->numSongs)) {
-        std::cerr << "Error: the songs' genre ids are not known (setGenreIds)" << std::endl;
+// The first query that needs a per-song array hands it to the engine through `set`; what / setter: for the message when the
+// array is not known.
+template <class T>
+bool ensureUploaded(Recommender::Impl* impl, PerSong<T>& a, int (*set)(mi355rec_sharded_t*, const T*, int64_t), const char* what,
+                    const char* setter) {
+    if (a.uploaded) return true;
+    if (a.values.size() != static_cast<size_t>(impl->numSongs)) {
+        std::cerr << "Error: the songs' " << what << " are not known (" << setter << ")" << std::endl;
         return false;
     }
-    if (mi355rec_sharded_set_labels(impl->engine, impl->genreIds.data(), impl->numSongs) != MI355REC_OK) {
+    if (set(impl->engine, a.values.data(), impl->numSongs) != MI355REC_OK) {
         std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
         return false;
     }
-    impl->labelsUploaded = true;
+    a.uploaded = true;
     return true;
 }
+bool ensureGenres(Recommender::Impl* impl) { return ensureUploaded(impl, impl->genres, mi355rec_sharded_set_labels, "genre ids", "setGenreIds"); }
+bool ensureGroups(Recommender::Impl* impl) { return ensureUploaded(impl, impl->groups, mi355rec_sharded_set_groups, "group ids", "setGroupIds"); }
+bool ensurePriors(Recommender::Impl* impl) { return ensureUploaded(impl, impl->priors, mi355rec_sharded_set_priors, "priors", "setPriors"); }
 }  // namespace
 
 std::vector<int> Recommender::recommendByIndexInGenres(int songIndex, int topN, const std::vector<int>& genreIds) {
@@ -343,7 +351,7 @@ std::vector<int> Recommender::recommendByIndexInGenres(int songIndex, int topN, 
         std::cerr << "Error: no genre to recommend from" << std::endl;
         return {};
     }
-    if (!uploadLabels(impl_)) return {};
+    if (!ensureGenres(impl_)) return {};
     impl_->idxBuf.assign(static_cast<size_t>(topN), -1);
     impl_->scoreBuf.assign(static_cast<size_t>(topN), 0.0f);
     int count = 0;
@@ -390,129 +398,113 @@ bool makeFilter(const std::vector<Recommender::FeatureRange>& where, mi355rec_fi
     return true;
 }
 
-// lambda and pool of a diversified call (DIVERSIFIED TOP-N; pool 0: min(1024, max(topN, 4 topN)), the Python default).
-struct Diverse {
-    float lambda;
-    int pool;
-    int maxPerGroup = 0;   // > 0: the capped entry point (GROUP CAPS; pool 0: min(1024, max(topN, 8 topN)))
-    bool capped = false;
-};
-
-// recommendForPlaylist with a filter (null: the unfiltered entry point) and weights (null: the entry points without them;
-// else one per song, the caller has checked the length); diverse: null, or the diversified entry point (weights and filter
-// may then be null).  genres: null or empty, or the genre ids the results come from (the request call, PLAYLIST REQUESTS).
-std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& songIndices, int topN, const std::vector<int>& alsoExclude,
-                               const mi355rec_filter_t* filter, const float* weights = nullptr, const Diverse* diverse = nullptr,
-                               const std::vector<int>* genres = nullptr, float priorWeight = 0.0f) {
+// Recommender::recommendQuery: every call that reaches the playlist request or the distance request, and the one place that does.
+// rangesLast: `where` is looked at after the songs, topN and the scales instead of first (recommendScaled's order of messages).
+std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, bool rangesLast) {
+    if (!q.weights.empty() && q.weights.size() != q.songs.size()) {
+        std::cerr << "Error: " << q.weights.size() << " weights for " << q.songs.size() << " songs (one weight per song, or none)" << std::endl;
+        return {};
+    }
+    mi355rec_filter_t f;
+    if (!rangesLast && !makeFilter(q.where, f)) return {};
     if (!impl->initialized) {
         std::cerr << "Error: Recommender not initialized" << std::endl;
         return {};
     }
-    if (songIndices.empty() || songIndices.size() > MI355REC_MAX_PLAYLIST) {
+    if (q.songs.empty() || q.songs.size() > MI355REC_MAX_PLAYLIST) {
         std::cerr << "Error: a playlist holds 1 to " << MI355REC_MAX_PLAYLIST << " songs" << std::endl;
         return {};
     }
-    if (alsoExclude.size() > MI355REC_MAX_EXCLUDE) {
+    if (q.alsoExclude.size() > MI355REC_MAX_EXCLUDE) {
         std::cerr << "Error: at most " << MI355REC_MAX_EXCLUDE << " songs can be excluded" << std::endl;
         return {};
     }
-    std::vector<int64_t> rows(songIndices.begin(), songIndices.end()), excl(alsoExclude.begin(), alsoExclude.end());
+    const std::vector<int64_t> rows(q.songs.begin(), q.songs.end()), excl(q.alsoExclude.begin(), q.alsoExclude.end());
     for (const std::vector<int64_t>* v : {&rows, &excl})
         for (int64_t i : *v)
             if (i < 0 || i >= impl->numSongs) {
                 std::cerr << "Error: Invalid song index: " << i << std::endl;
                 return {};
             }
+    int topN = q.topN;
     if (topN <= 0) {
         std::cerr << "Error: topN must be positive" << std::endl;
         return {};
     }
+    if (!q.scales.empty() && q.scales.size() != MI355REC_DIM) {
+        std::cerr << "Error: " << q.scales.size() << " feature scales: one per feature, " << MI355REC_DIM << " in all" << std::endl;
+        return {};
+    }
     if (topN > impl->numSongs) topN = impl->numSongs;   // (the engine pads past what it can return; no buffer beyond the songs)
-    impl->idxBuf.assign(static_cast<size_t>(topN), -1);
-    impl->scoreBuf.assign(static_cast<size_t>(topN), 0.0f);
-    int count = 0;
+    if (rangesLast && !makeFilter(q.where, f)) return {};
+    const bool capped = q.maxPerArtist != 0, withPrior = q.priorWeight != 0.0f;   // (a NaN weight: the engine refuses it)
+    // Within genres or with a prior weight, lambda 1 without a cap is the plain request: its picks are the pool's first topN in
+    // order for any pool, so no pool is taken and no re-rank launched (the diversified overload without either keeps its launch).
+    const bool plainOrder = q.lambda == 1.0f && (!q.genreIds.empty() || withPrior);
+    const bool rerank = capped || (q.diverse && !plainOrder);   // (a cap alone: lambda 1, the plain order with the cap)
+    if (q.euclidean && (!q.weights.empty() || rerank || withPrior)) {
+        std::cerr << "Error: the Euclidean metric takes no weights, diversity, cap or prior weight" << std::endl;
+        return {};
+    }
     int pool = 0;
-    if (diverse) {
-        pool = diverse->pool;
-        if (pool == 0)
-            pool = std::min(MI355REC_MAX_TOPN_FAST, std::max(topN, (diverse->capped ? 8 : 4) * std::min(topN, MI355REC_MAX_TOPN_FAST)));
+    if (rerank) {   // (DIVERSIFIED TOP-N, GROUP CAPS: pool 0 is min(1024, max(topN, 4 topN)), with a cap 8 topN)
+        pool = q.pool ? q.pool : std::min(MI355REC_MAX_TOPN_FAST, std::max(topN, (capped ? 8 : 4) * std::min(topN, MI355REC_MAX_TOPN_FAST)));
         if (pool < 0) {
             std::cerr << "Error: pool must be positive (or 0 for the default)" << std::endl;
             return {};
         }
     }
-    if (diverse && diverse->capped) {
-        if (diverse->maxPerGroup < 1) {
-            std::cerr << "Error: maxPerArtist must be positive" << std::endl;
-            return {};
-        }
-        if (!impl->groupsUploaded) {   // the first capped query hands the songs' groups to the engine
-            if (impl->groupIds.size() != static_cast<size_t>(impl->numSongs)) {
-                std::cerr << "Error: the songs' group ids are not known (setGroupIds)" << std::endl;
-                return {};
-            }
-            if (mi355rec_sharded_set_groups(impl->engine, impl->groupIds.data(), impl->numSongs) != MI355REC_OK) {
-                std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
-                return {};
-            }
-            impl->groupsUploaded = true;
-        }
+    if (q.maxPerArtist < 0) {
+        std::cerr << "Error: maxPerArtist must be positive" << std::endl;
+        return {};
     }
-    // (the _playlist_topn and _where entry points are the _weighted one with null weights / a null filter)
-    const int k = static_cast<int>(rows.size()), nExcl = static_cast<int>(excl.size());
-    int64_t* const idx = impl->idxBuf.data();
-    float* const score = impl->scoreBuf.data();
+    if (capped && !ensureGroups(impl)) return {};
+    if (withPrior && !ensurePriors(impl)) return {};
+    if (!q.genreIds.empty() && !ensureGenres(impl)) return {};
+    impl->idxBuf.assign(static_cast<size_t>(topN), -1);
+    impl->scoreBuf.assign(static_cast<size_t>(topN), 0.0f);
+    int count = 0;
+    const auto shared = [&](auto& r) {   // what mi355rec_playlist_query_t and mi355rec_distance_query_t have in common
+        r.size = sizeof r;
+        r.rows = rows.data();
+        r.k = static_cast<int32_t>(rows.size());
+        r.exclude_global = excl.data();
+        r.n_exclude = static_cast<int32_t>(excl.size());
+        r.filter = q.where.empty() ? nullptr : &f;
+        if (!q.genreIds.empty()) {
+            r.labels = q.genreIds.data();
+            r.n_labels = static_cast<int32_t>(q.genreIds.size());
+        }
+        r.topn = topN;
+    };
+    // (an ext whose two pointers are null is the plain request, and a request without flags the plain playlist call: the launches
+    // are those of the legacy entry points)
+    const mi355rec_request_ext_t ext = requestExt(impl, q.scales.empty() ? nullptr : q.scales.data());
     int rc;
-    const bool withGenres = genres && !genres->empty(), withPrior = priorWeight != 0.0f;   // (NaN: the engine refuses it)
-    if (withPrior && !impl->priorsUploaded) {   // the first call with a prior weight hands the songs' priors to the engine
-        if (impl->priors.size() != static_cast<size_t>(impl->numSongs)) {
-            std::cerr << "Error: the songs' priors are not known (setPriors)" << std::endl;
-            return {};
-        }
-        if (mi355rec_sharded_set_priors(impl->engine, impl->priors.data(), impl->numSongs) != MI355REC_OK) {
-            std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
-            return {};
-        }
-        impl->priorsUploaded = true;
-    }
-    if (withGenres || withPrior || impl->rowSet) {   // (a row set travels beside the request: ROW SETS)
-        if (withGenres && !uploadLabels(impl)) return {};
-        mi355rec_playlist_query_t q{};
-        q.size = sizeof q;
-        q.flags = (diverse ? MI355REC_PQ_DIVERSE : 0u) | (diverse && diverse->capped ? MI355REC_PQ_CAPPED : 0u) |
-                  (withPrior ? MI355REC_PQ_PRIOR : 0u);
-        q.prior_weight = priorWeight;
-        q.rows = rows.data();
-        q.k = k;
-        q.weights = weights;
-        q.exclude_global = excl.data();
-        q.n_exclude = nExcl;
-        q.filter = filter;
-        if (withGenres) {
-            q.labels = genres->data();
-            q.n_labels = static_cast<int32_t>(genres->size());
-        }
-        q.topn = topN;
-        if (diverse) {
-            q.lambda = diverse->lambda;
-            q.pool = pool;
-            q.max_per_group = diverse->maxPerGroup;
+    if (q.euclidean) {
+        mi355rec_distance_query_t d{};
+        shared(d);
+        mi355rec_distance_result_t res{};
+        res.out_idx = impl->idxBuf.data();
+        res.out_distance = impl->scoreBuf.data();
+        res.out_count = &count;
+        rc = mi355rec_sharded_query_distance_request_ext(impl->engine, &d, &ext, &res);
+    } else {
+        mi355rec_playlist_query_t p{};
+        shared(p);
+        p.flags = (rerank ? MI355REC_PQ_DIVERSE : 0u) | (capped ? MI355REC_PQ_CAPPED : 0u) | (withPrior ? MI355REC_PQ_PRIOR : 0u);
+        p.weights = q.weights.empty() ? nullptr : q.weights.data();
+        p.prior_weight = q.priorWeight;
+        if (rerank) {
+            p.lambda = q.lambda;
+            p.pool = pool;
+            p.max_per_group = q.maxPerArtist;
         }
         mi355rec_playlist_result_t res{};
-        res.out_idx = idx;
-        res.out_score = score;
+        res.out_idx = impl->idxBuf.data();
+        res.out_score = impl->scoreBuf.data();
         res.out_count = &count;
-        const mi355rec_request_ext_t ext = requestExt(impl, nullptr);
-        rc = mi355rec_sharded_query_playlist_request_ext(impl->engine, &q, &ext, &res);
-    } else if (diverse && diverse->capped) {
-        rc = mi355rec_sharded_query_playlist_topn_capped(impl->engine, rows.data(), weights, k, excl.data(), nExcl, filter, diverse->lambda,
-                                                         pool, diverse->maxPerGroup, topN, idx, score, nullptr, &count, nullptr);
-    } else if (diverse) {
-        rc = mi355rec_sharded_query_playlist_topn_diverse(impl->engine, rows.data(), weights, k, excl.data(), nExcl, filter, diverse->lambda,
-                                                          pool, topN, idx, score, nullptr, &count);
-    } else {
-        rc = mi355rec_sharded_query_playlist_topn_weighted(impl->engine, rows.data(), weights, k, excl.data(), nExcl, filter, topN, idx, score,
-                                                           &count);
+        rc = mi355rec_sharded_query_playlist_request_ext(impl->engine, &p, &ext, &res);
     }
     if (rc != MI355REC_OK) {
         std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
@@ -524,56 +516,64 @@ std::vector<int> playlistQuery(Recommender::Impl* impl, const std::vector<int>& 
     return results;
 }
 
-// The recommendForPlaylist overloads that take weights (one per song; orNone: or none at all) and ranges: the length check,
-// the filter (none for no ranges) and the query.
-std::vector<int> weightedPlaylistQuery(Recommender::Impl* impl, const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
-                                       bool orNone, const std::vector<Recommender::FeatureRange>& where, const std::vector<int>& alsoExclude,
-                                       const Diverse* diverse = nullptr, const std::vector<int>* genres = nullptr, float priorWeight = 0.0f) {
-    if (!(orNone && weights.empty()) && weights.size() != songIndices.size()) {
-        std::cerr << "Error: " << weights.size() << " weights for " << songIndices.size() << " songs (one weight per song"
-                  << (orNone ? ", or none" : "") << ")" << std::endl;
-        return {};
-    }
-    mi355rec_filter_t f;
-    if (!makeFilter(where, f)) return {};
-    return playlistQuery(impl, songIndices, topN, alsoExclude, where.empty() ? nullptr : &f, weights.empty() ? nullptr : weights.data(),
-                         diverse, genres, priorWeight);
+// What every recommendForPlaylist overload starts its Query from.
+Recommender::Query playlistOf(const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
+                              const std::vector<Recommender::FeatureRange>& where, const std::vector<int>& alsoExclude) {
+    Recommender::Query q;
+    q.songs = songIndices;
+    q.topN = topN;
+    q.weights = weights;
+    q.where = where;
+    q.alsoExclude = alsoExclude;
+    return q;
 }
 
 }  // namespace
 
+std::vector<int> Recommender::recommendQuery(const Query& query) { return runQuery(impl_, query, false); }
+
 std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<int>& alsoExclude) {
-    return playlistQuery(impl_, songIndices, topN, alsoExclude, nullptr);
+    return recommendQuery(playlistOf(songIndices, topN, {}, {}, alsoExclude));
 }
 
 std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<FeatureRange>& where,
                                                    const std::vector<int>& alsoExclude) {
-    mi355rec_filter_t f;
-    if (!makeFilter(where, f)) return {};
-    return playlistQuery(impl_, songIndices, topN, alsoExclude, &f);
+    return recommendQuery(playlistOf(songIndices, topN, {}, where, alsoExclude));
 }
 
 std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
                                                    const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude) {
-    return weightedPlaylistQuery(impl_, songIndices, topN, weights, false, where, alsoExclude);
+    if (weights.size() != songIndices.size()) {   // (this overload alone takes no empty weight list)
+        std::cerr << "Error: " << weights.size() << " weights for " << songIndices.size() << " songs (one weight per song)" << std::endl;
+        return {};
+    }
+    return recommendQuery(playlistOf(songIndices, topN, weights, where, alsoExclude));
 }
 
 std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
                                                    const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude, float lambda,
                                                    int pool) {
-    const Diverse d{lambda, pool};
-    return weightedPlaylistQuery(impl_, songIndices, topN, weights, true, where, alsoExclude, &d);
+    Query q = playlistOf(songIndices, topN, weights, where, alsoExclude);
+    q.diverse = true;
+    q.lambda = lambda;
+    q.pool = pool;
+    return recommendQuery(q);
 }
 
 std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<float>& weights,
                                                    const std::vector<FeatureRange>& where, const std::vector<int>& alsoExclude, float lambda,
                                                    int pool, int maxPerArtist, const std::vector<int>& genreIds, float priorWeight) {
-    // Within genres (or with a prior weight) maxPerArtist 0 asks for no cap: the diversified call, and with lambda 1, whose
-    // picks are the pool's first topN in order for any pool, the plain request (no pool, no re-rank launch).
-    const bool uncapped = maxPerArtist == 0 && (!genreIds.empty() || priorWeight != 0.0f);
-    const Diverse d{lambda, pool, maxPerArtist, !uncapped};
-    return weightedPlaylistQuery(impl_, songIndices, topN, weights, true, where, alsoExclude, uncapped && lambda == 1.0f ? nullptr : &d,
-                                 &genreIds, priorWeight);
+    // Within genres (or with a prior weight) maxPerArtist 0 asks for no cap: the diversified call (with lambda 1 the plain
+    // request: runQuery).  Without either it is refused like every other value below 1.
+    const bool wholeFamily = !genreIds.empty() || priorWeight != 0.0f;
+    Query q = playlistOf(songIndices, topN, weights, where, alsoExclude);
+    q.diverse = true;
+    q.lambda = lambda;
+    q.pool = pool;
+    q.maxPerArtist = maxPerArtist == 0 && !wholeFamily ? -1 : maxPerArtist;
+    q.genreIds = genreIds;
+    q.priorWeight = priorWeight;
+    return recommendQuery(q);
 }
 
 std::vector<int> Recommender::recommendNearest(const std::vector<int>& songIndices, int topN, const std::vector<FeatureRange>& where,
@@ -583,83 +583,11 @@ std::vector<int> Recommender::recommendNearest(const std::vector<int>& songIndic
 
 std::vector<int> Recommender::recommendScaled(const std::vector<int>& songIndices, int topN, const std::vector<float>& scales, bool euclidean,
                                               const std::vector<FeatureRange>& where, const std::vector<int>& genreIds) {
-    Impl* impl = impl_;
-    if (!impl->initialized) {
-        std::cerr << "Error: Recommender not initialized" << std::endl;
-        return {};
-    }
-    if (songIndices.empty() || songIndices.size() > MI355REC_MAX_PLAYLIST) {
-        std::cerr << "Error: a playlist holds 1 to " << MI355REC_MAX_PLAYLIST << " songs" << std::endl;
-        return {};
-    }
-    std::vector<int64_t> rows(songIndices.begin(), songIndices.end());
-    for (int64_t i : rows)
-        if (i < 0 || i >= impl->numSongs) {
-            std::cerr << "Error: Invalid song index: " << i << std::endl;
-            return {};
-        }
-    if (topN <= 0) {
-        std::cerr << "Error: topN must be positive" << std::endl;
-        return {};
-    }
-    if (!scales.empty() && scales.size() != MI355REC_DIM) {
-        std::cerr << "Error: " << scales.size() << " feature scales: one per feature, " << MI355REC_DIM << " in all" << std::endl;
-        return {};
-    }
-    if (topN > impl->numSongs) topN = impl->numSongs;
-    mi355rec_filter_t f;
-    if (!makeFilter(where, f)) return {};
-    if (!genreIds.empty() && !uploadLabels(impl)) return {};
-    impl->idxBuf.assign(static_cast<size_t>(topN), -1);
-    impl->scoreBuf.assign(static_cast<size_t>(topN), 0.0f);
-    int count = 0;
-    const mi355rec_request_ext_t ext = requestExt(impl, scales.empty() ? nullptr : scales.data());
-    if (!euclidean) {   // the playlist request by row: the members are never returned
-        mi355rec_playlist_query_t pq{};
-        pq.size = sizeof pq;
-        pq.rows = rows.data();
-        pq.k = static_cast<int32_t>(rows.size());
-        pq.filter = where.empty() ? nullptr : &f;
-        if (!genreIds.empty()) {
-            pq.labels = genreIds.data();
-            pq.n_labels = static_cast<int32_t>(genreIds.size());
-        }
-        pq.topn = topN;
-        mi355rec_playlist_result_t pres{};
-        pres.out_idx = impl->idxBuf.data();
-        pres.out_score = impl->scoreBuf.data();
-        pres.out_count = &count;
-        if (mi355rec_sharded_query_playlist_request_ext(impl->engine, &pq, &ext, &pres) != MI355REC_OK) {
-            std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
-            return {};
-        }
-        std::vector<int> results(static_cast<size_t>(count));
-        for (int i = 0; i < count; ++i) results[i] = static_cast<int>(impl->idxBuf[i]);
-        impl->lastScores.assign(impl->scoreBuf.begin(), impl->scoreBuf.begin() + count);
-        return results;
-    }
-    mi355rec_distance_query_t q{};
-    q.size = sizeof q;
-    q.rows = rows.data();
-    q.k = static_cast<int32_t>(rows.size());
-    q.filter = where.empty() ? nullptr : &f;
-    if (!genreIds.empty()) {
-        q.labels = genreIds.data();
-        q.n_labels = static_cast<int32_t>(genreIds.size());
-    }
-    q.topn = topN;
-    mi355rec_distance_result_t res{};
-    res.out_idx = impl->idxBuf.data();
-    res.out_distance = impl->scoreBuf.data();
-    res.out_count = &count;
-    if (mi355rec_sharded_query_distance_request_ext(impl->engine, &q, &ext, &res) != MI355REC_OK) {
-        std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
-        return {};
-    }
-    std::vector<int> results(static_cast<size_t>(count));
-    for (int i = 0; i < count; ++i) results[i] = static_cast<int>(impl->idxBuf[i]);
-    impl->lastScores.assign(impl->scoreBuf.begin(), impl->scoreBuf.begin() + count);
-    return results;
+    Query q = playlistOf(songIndices, topN, {}, where, {});
+    q.genreIds = genreIds;
+    q.scales = scales;
+    q.euclidean = euclidean;
+    return runQuery(impl_, q, /*rangesLast=*/true);
 }
 
 std::vector<int> Recommender::recommendByIndexCapped(int songIndex, int topN, int maxPerArtist, float lambda, int pool,
@@ -693,9 +621,7 @@ std::vector<int> Recommender::recommendForTaste(const std::vector<int>& liked, c
 
 std::vector<int> Recommender::recommendByIndexWhere(int songIndex, int topN, const std::vector<FeatureRange>& where) {
     if (!checkQuery(impl_, songIndex, topN)) return {};
-    mi355rec_filter_t f;
-    if (!makeFilter(where, f)) return {};
-    return playlistQuery(impl_, {songIndex}, topN, {}, &f);
+    return recommendForPlaylist({songIndex}, topN, where, {});
 }
 
 std::vector<int> Recommender::recommend(const std::string& trackId, int topN) {  // :356-363

@@ -34,6 +34,7 @@
 #include <fstream>
 #include <iostream>
 #include <map>
+#include <sstream>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -125,11 +126,12 @@ static bool parseWhere(int argc, char* argv[], int first, std::vector<Recommende
     return true;
 }
 
+static const char* const kScaleNames[] = {"danceability", "energy", "key", "loudness", "mode", "speechiness",
+                                          "acousticness", "instrumentalness", "liveness", "valence", "tempo", "genre"};
+
 // --scale NAME=S, any number of times from argv[first]: scales = 12 factors in Song.h order (1 where not named), or empty when the
-// option is not given.  false, with a message, on a malformed option, an unknown NAME or an option --scale is not served with.
+// option is not given.  false, with a message, on a malformed option or an unknown NAME.
 static bool parseScale(int argc, char* argv[], int first, std::vector<float>& scales) {
-    static const char* const kNames[] = {"danceability", "energy", "key", "loudness", "mode", "speechiness",
-                                         "acousticness", "instrumentalness", "liveness", "valence", "tempo", "genre"};
     scales.clear();
     for (int i = first; i < argc; ++i) {
         if (std::strcmp(argv[i], "--scale") != 0) continue;
@@ -146,7 +148,7 @@ static bool parseScale(int argc, char* argv[], int first, std::vector<float>& sc
         const std::string name = arg.substr(0, eq), value = arg.substr(eq + 1);
         int feature = -1;
         for (int j = 0; j < 12; ++j)
-            if (name == kNames[j]) feature = j;
+            if (name == kScaleNames[j]) feature = j;
         if (feature < 0) {
             std::cerr << "Error: --scale: unknown feature '" << name << "'" << std::endl;
             return false;
@@ -160,19 +162,16 @@ static bool parseScale(int argc, char* argv[], int first, std::vector<float>& sc
         if (scales.empty()) scales.assign(12, 1.0f);
         scales[static_cast<size_t>(feature)] = v;
     }
-    if (scales.empty()) return true;
-    for (int i = first; i < argc; ++i)
-        for (const char* no : {"--diverse", "--pool", "--weights", "--dislike", "--dislike-weight", "--priors", "--prior-weight", "--max-per-artist"})
-            if (std::strcmp(argv[i], no) == 0) {
-                std::cerr << "Error: --scale cannot be combined with " << no << " (scaled requests take --metric, --genre and --where only)"
-                          << std::endl;
-                return false;
-            }
+    return true;
+}
+
+// The scales that are not 1, announced (none given: nothing).
+static void printScales(const std::vector<float>& scales) {
+    if (scales.empty()) return;
     std::cout << "Feature scales:";
     for (int j = 0; j < 12; ++j)
-        if (scales[static_cast<size_t>(j)] != 1.0f) std::cout << " " << kNames[j] << "=" << scales[static_cast<size_t>(j)];
+        if (scales[static_cast<size_t>(j)] != 1.0f) std::cout << " " << kScaleNames[j] << "=" << scales[static_cast<size_t>(j)];
     std::cout << std::endl;
-    return true;
 }
 
 static bool preprocessMode(const std::string& csvPath) {  // main.cpp:33-44
@@ -248,12 +247,11 @@ static bool parseDiverse(int argc, char* argv[], int first, int topN, DiverseOpt
     return true;
 }
 
-// --seen FILE / --only FILE from argv[first] (row sets): what main() found, for the modes below.
+// --seen FILE / --only FILE from argv[first] (row sets).
 struct RowSetOpt {
     bool on = false, only = false;
     std::string file;
 };
-static RowSetOpt g_rowSet;
 
 static bool parseRowSet(int argc, char* argv[], int first, RowSetOpt& rs) {
     for (int i = first; i < argc; ++i) {
@@ -302,11 +300,11 @@ static int findQuery(const DataManager::Catalogue& catalogue, const std::string&
 // --seen / --only: the file's track ids (one per line, blank lines skipped, the first row of an id as for --id) to the recommender
 // as its row set.  A line that names no song of the catalogue is skipped; how many were is said on stderr (a history normally
 // holds tracks the catalogue lacks).  false, with a message, when the file cannot be read or the set is refused.
-static bool applyRowSet(Recommender& recommender, const DataManager::Catalogue& catalogue) {
-    if (!g_rowSet.on) return true;
-    std::ifstream in(g_rowSet.file);
+static bool applyRowSet(Recommender& recommender, const DataManager::Catalogue& catalogue, const RowSetOpt& rs) {
+    if (!rs.on) return true;
+    std::ifstream in(rs.file);
     if (!in) {
-        std::cerr << "Error: cannot open the row set file '" << g_rowSet.file << "'" << std::endl;
+        std::cerr << "Error: cannot open the row set file '" << rs.file << "'" << std::endl;
         return false;
     }
     std::unordered_map<std::string, int> byId;
@@ -321,22 +319,11 @@ static bool applyRowSet(Recommender& recommender, const DataManager::Catalogue& 
         if (hit == byId.end()) ++skipped;
         else rows.push_back(hit->second);
     }
-    std::cerr << "Row set (" << (g_rowSet.only ? "--only" : "--seen") << " " << g_rowSet.file << "): " << rows.size() << " tracks, " << skipped
+    std::cerr << "Row set (" << (rs.only ? "--only" : "--seen") << " " << rs.file << "): " << rows.size() << " tracks, " << skipped
               << " lines skipped (not in the catalogue)" << std::endl;
-    if (!recommender.setRowSet(rows, g_rowSet.only)) return false;
-    std::cout << (g_rowSet.only ? "Only among " : "Leaving out ") << rows.size() << " listed songs" << std::endl;
+    if (!recommender.setRowSet(rows, rs.only)) return false;
+    std::cout << (rs.only ? "Only among " : "Leaving out ") << rows.size() << " listed songs" << std::endl;
     return true;
-}
-
-// --where: the songs within every range, ranked as recommendByIndex ranks the whole catalogue.
-static void whereRecommendations(Recommender& recommender, const DataManager::Catalogue& catalogue, const std::string& query,
-                                 bool isTrackId, int topN, const std::vector<Recommender::FeatureRange>& ranges, std::vector<int>& recs) {
-    const int index = findQuery(catalogue, query, isTrackId);
-    if (index < 0) {
-        std::cerr << "Error: Song with " << (isTrackId ? "track_id" : "name") << " '" << query << "' not found" << std::endl;
-        return;   // (no recommendations: the caller says so)
-    }
-    recs = recommender.recommendByIndexWhere(index, topN, ranges);
 }
 
 // The ids of the genres named (case-insensitively); false, with a message, for an unknown one.
@@ -354,25 +341,6 @@ static bool genreIdsOf(const DataManager::Catalogue& catalogue, const std::vecto
     return true;
 }
 
-// --genre: the songs whose genre is one of `genres` (names matched case-insensitively), ranked as recommendByIndex
-// ranks the whole catalogue; the query song is found by the engine's rules (exact id / exact name, then substring).
-static bool genreRecommendations(Recommender& recommender, const DataManager::Catalogue& catalogue, const std::string& query,
-                                 bool isTrackId, int topN, const std::vector<std::string>& genres, std::vector<int>& recs) {
-    std::vector<int> ids;
-    if (!genreIdsOf(catalogue, genres, ids)) return false;
-    const int index = findQuery(catalogue, query, isTrackId);
-    if (index < 0) {
-        std::cerr << "Error: Song with " << (isTrackId ? "track_id" : "name") << " '" << query << "' not found" << std::endl;
-        return true;   // (no recommendations: the caller says so)
-    }
-    std::cout << "Restricted to genres:";
-    for (const std::string& name : genres) std::cout << " " << name;
-    std::cout << std::endl;
-    if (!recommender.setGenreIds(catalogue.genreIds)) return true;
-    recs = recommender.recommendByIndexInGenres(index, topN, ids);
-    return true;
-}
-
 // --max-per-artist: the group ids of the catalogue's songs (their primary artists, read back from the file) to the recommender.
 static bool capByArtist(Recommender& recommender, const DataManager::Catalogue& catalogue) {
     std::vector<std::string> artists(catalogue.size());
@@ -387,98 +355,6 @@ static bool capByArtist(Recommender& recommender, const DataManager::Catalogue& 
     return recommender.setGroupIds(Recommender::artistGroupIds(artists));
 }
 
-// --diverse: recommendByIndex (or its --where form) diversified.
-static void diverseRecommendations(Recommender& recommender, const DataManager::Catalogue& catalogue, const std::string& query,
-                                   bool isTrackId, int topN, const std::vector<Recommender::FeatureRange>& ranges, const DiverseOpt& dv,
-                                   std::vector<int>& recs) {
-    const int index = findQuery(catalogue, query, isTrackId);
-    if (index < 0) {
-        std::cerr << "Error: Song with " << (isTrackId ? "track_id" : "name") << " '" << query << "' not found" << std::endl;
-        return;   // (no recommendations: the caller says so)
-    }
-    if (dv.maxPerArtist > 0) {
-        if (!capByArtist(recommender, catalogue)) return;
-        std::cout << "At most " << dv.maxPerArtist << " per artist";
-        if (dv.lambda < 1.0f) std::cout << "; diversified: lambda " << dv.lambda;
-        std::cout << std::endl;
-        recs = recommender.recommendByIndexCapped(index, topN, dv.maxPerArtist, dv.lambda, dv.pool, ranges);
-        return;
-    }
-    std::cout << "Diversified: lambda " << dv.lambda << std::endl;
-    recs = recommender.recommendDiverse(index, topN, dv.lambda, dv.pool, ranges);
-}
-
-static bool recommendationMode(const std::string& query, bool isTrackId, int topN, const std::vector<std::string>& genres,
-                               const std::vector<Recommender::FeatureRange>& ranges, const DiverseOpt& dv) {  // main.cpp:46-131
-    std::cout << "=== RECOMMENDATION MODE ===" << std::endl;
-    DataManager::Catalogue catalogue;
-    if (!DataManager::loadCatalogue(kBinaryDataFile, catalogue)) {
-        std::cerr << "Failed to load data. Have you run preprocessing?" << std::endl;
-        return false;
-    }
-    Recommender recommender;
-    if (!recommender.initialize(catalogue.features, catalogue.trackIds, catalogue.trackNames)) {
-        std::cerr << "Failed to initialize recommender" << std::endl;
-        return false;
-    }
-    if (!applyRowSet(recommender, catalogue)) return false;
-    std::map<int, std::string>& genreMap = catalogue.genreMap;
-
-    std::vector<int> recs;
-    int queryIndex = -1;
-    if (isTrackId) {
-        std::cout << "\nSearching for track ID: " << query << std::endl;
-        if (dv.on) diverseRecommendations(recommender, catalogue, query, true, topN, ranges, dv, recs);
-        else if (!ranges.empty() || g_rowSet.on) whereRecommendations(recommender, catalogue, query, true, topN, ranges, recs);   // (a row set: the one-song playlist)
-        else if (genres.empty()) recs = recommender.recommend(query, topN);
-        else if (!genreRecommendations(recommender, catalogue, query, true, topN, genres, recs)) return false;
-        for (size_t i = 0; i < catalogue.size(); ++i)
-            if (catalogue.trackIds[i] == query) { queryIndex = static_cast<int>(i); break; }
-    } else {
-        std::cout << "\nSearching for song: " << query << std::endl;
-        if (dv.on) diverseRecommendations(recommender, catalogue, query, false, topN, ranges, dv, recs);
-        else if (!ranges.empty() || g_rowSet.on) whereRecommendations(recommender, catalogue, query, false, topN, ranges, recs);
-        else if (genres.empty()) recs = recommender.recommendByName(query, topN);
-        else if (!genreRecommendations(recommender, catalogue, query, false, topN, genres, recs)) return false;
-        // The reference finds the song it DISPLAYS with a single exact-or-substring
-        // pass (main.cpp:85-95), not the engine's exact-then-substring rule; kept.
-        std::string needle = query;
-        std::transform(needle.begin(), needle.end(), needle.begin(), ::tolower);
-        for (size_t i = 0; i < catalogue.size(); ++i) {
-            std::string name = catalogue.trackNames[i];
-            std::transform(name.begin(), name.end(), name.begin(), ::tolower);
-            if (name == needle || name.find(needle) != std::string::npos) { queryIndex = static_cast<int>(i); break; }
-        }
-    }
-    if (recs.empty()) {
-        std::cerr << "No recommendations found. Please check the query." << std::endl;
-        return false;
-    }
-    Song song;
-    if (queryIndex >= 0 && DataManager::readSong(catalogue, static_cast<size_t>(queryIndex), song)) {
-        std::cout << "\n----------------------------------------------\nQuery Song:\n"
-                  << "  Title:   " << song.track_name << "\n"
-                  << "  Artist:  " << song.artists << "\n"
-                  << "  Genre:   " << genreMap[song.genre_id] << "\n"
-                  << "  ID:      " << song.track_id
-                  << "\n----------------------------------------------" << std::endl;
-    }
-    std::cout << "\nTop " << recs.size() << " Recommendations:\n" << std::endl;
-    for (size_t i = 0; i < recs.size(); ++i) {
-        if (!DataManager::readSong(catalogue, static_cast<size_t>(recs[i]), song)) {
-            std::cerr << "Error: could not read song " << recs[i] << " from " << catalogue.path << std::endl;
-            return false;
-        }
-        std::cout << (i + 1) << ". \"" << song.track_name << "\"" << std::endl;
-        printSong(song, genreMap, "   ");
-        if (i + 1 < recs.size()) std::cout << std::endl;
-    }
-    std::cout << "\nRecommendation complete!" << std::endl;
-    return true;
-}
-
-// --playlist: the songs most similar on average to the playlist's (exact track ids, the first row of an id as for --id),
-// the playlist's own songs never among them.
 // The non-empty fields of a comma-separated list.
 static std::vector<std::string> splitList(const std::string& list) {
     std::vector<std::string> items;
@@ -601,109 +477,8 @@ static bool readPriors(const std::string& path, size_t songs, std::vector<float>
     return true;
 }
 
-static bool playlistMode(const std::string& list, int topN, const std::vector<Recommender::FeatureRange>& ranges, const Taste& taste,
-                         const DiverseOpt& dv, const std::vector<std::string>& genres, const PriorOpt& pr) {
-    std::cout << "=== PLAYLIST MODE ===" << std::endl;
-    std::vector<std::string> ids = splitList(list);
-    if (ids.empty()) {
-        std::cerr << "Error: the playlist names no track" << std::endl;
-        return false;
-    }
-    DataManager::Catalogue catalogue;
-    if (!DataManager::loadCatalogue(kBinaryDataFile, catalogue)) {
-        std::cerr << "Failed to load data. Have you run preprocessing?" << std::endl;
-        return false;
-    }
-    if (taste.haveWeights && taste.weights.size() != ids.size()) {
-        std::cerr << "Error: --weights names " << taste.weights.size() << " weights for " << ids.size() << " playlist songs" << std::endl;
-        return false;
-    }
-    std::vector<int> genreIds;   // --genre: only songs of these genres are recommended (the playlist's own may be of any)
-    if (!genreIdsOf(catalogue, genres, genreIds)) return false;
-    const size_t liked = ids.size();
-    ids.insert(ids.end(), taste.dislike.begin(), taste.dislike.end());
-    std::vector<float> weights = taste.haveWeights ? taste.weights : std::vector<float>(liked, 1.0f);
-    weights.insert(weights.end(), taste.dislike.size(), -taste.dislikeWeight);
-    std::vector<int> members;
-    for (const std::string& id : ids) {
-        int index = -1;
-        for (size_t i = 0; i < catalogue.size() && index < 0; ++i)
-            if (catalogue.trackIds[i] == id) index = static_cast<int>(i);
-        if (index < 0) {
-            std::cerr << "Error: Song with track_id '" << id << "' not found" << std::endl;
-            return false;
-        }
-        members.push_back(index);
-    }
-    Recommender recommender;
-    if (!recommender.initialize(catalogue.features, catalogue.trackIds, catalogue.trackNames)) {
-        std::cerr << "Failed to initialize recommender" << std::endl;
-        return false;
-    }
-    if (!applyRowSet(recommender, catalogue)) return false;
-    std::map<int, std::string>& genreMap = catalogue.genreMap;
-    if (dv.maxPerArtist > 0) {
-        if (!capByArtist(recommender, catalogue)) return false;
-        std::cout << "At most " << dv.maxPerArtist << " per artist" << std::endl;
-    }
-    if (dv.on && (dv.maxPerArtist == 0 || dv.lambda < 1.0f)) std::cout << "Diversified: lambda " << dv.lambda << std::endl;
-    if (!genreIds.empty()) {
-        std::cout << "Restricted to genres:";
-        for (const std::string& name : genres) std::cout << " " << name;
-        std::cout << std::endl;
-        if (!recommender.setGenreIds(catalogue.genreIds)) return false;
-    }
-    if (pr.on) {
-        std::vector<float> priors;
-        if (!readPriors(pr.file, catalogue.size(), priors) || !recommender.setPriors(priors)) return false;
-        std::cout << "Prior weight: " << pr.weight << " (" << pr.file << ")" << std::endl;
-    }
-    const bool blended = pr.on && pr.weight != 0.0f;   // (BETA 0 is the call without a prior)
-    const std::vector<int> recs = !genreIds.empty() || blended   // (the general overload: lambda 1 without a cap is the plain request)
-                                      ? recommender.recommendForPlaylist(members, topN, taste.weighted ? weights : std::vector<float>(), ranges,
-                                                                         {}, dv.on ? dv.lambda : 1.0f, dv.on ? dv.pool : 0, dv.maxPerArtist,
-                                                                         genreIds, blended ? pr.weight : 0.0f)
-                                  : dv.maxPerArtist > 0
-                                      ? recommender.recommendForPlaylist(members, topN, taste.weighted ? weights : std::vector<float>(), ranges,
-                                                                         {}, dv.lambda, dv.pool, dv.maxPerArtist)
-                                  : dv.on         ? recommender.recommendForPlaylist(members, topN, taste.weighted ? weights : std::vector<float>(),
-                                                                                     ranges, {}, dv.lambda, dv.pool)
-                                  : taste.weighted ? recommender.recommendForPlaylist(members, topN, weights, ranges, {})
-                                  : ranges.empty() ? recommender.recommendForPlaylist(members, topN)
-                                                   : recommender.recommendForPlaylist(members, topN, ranges, {});
-    if (recs.empty()) {
-        std::cerr << "No recommendations found. Please check the query." << std::endl;
-        return false;
-    }
-    Song song;
-    std::cout << "\n----------------------------------------------\nPlaylist (" << members.size() << " songs):" << std::endl;
-    for (size_t i = 0; i < members.size(); ++i) {
-        if (!DataManager::readSong(catalogue, static_cast<size_t>(members[i]), song)) {
-            std::cerr << "Error: could not read song " << members[i] << " from " << catalogue.path << std::endl;
-            return false;
-        }
-        std::cout << "  " << (i + 1) << ". \"" << song.track_name << "\"";
-        if (taste.weighted) std::cout << "  (weight " << weights[i] << ")";
-        std::cout << std::endl;
-        printSong(song, genreMap, "     ");
-    }
-    std::cout << "----------------------------------------------" << std::endl;
-    std::cout << "\nTop " << recs.size() << " Recommendations:\n" << std::endl;
-    for (size_t i = 0; i < recs.size(); ++i) {
-        if (!DataManager::readSong(catalogue, static_cast<size_t>(recs[i]), song)) {
-            std::cerr << "Error: could not read song " << recs[i] << " from " << catalogue.path << std::endl;
-            return false;
-        }
-        std::cout << (i + 1) << ". \"" << song.track_name << "\"" << std::endl;
-        printSong(song, genreMap, "   ");
-        if (i + 1 < recs.size()) std::cout << std::endl;
-    }
-    std::cout << "\nRecommendation complete!" << std::endl;
-    return true;
-}
-
 // --metric NAME from argv[first]: euclidean = true for "euclidean", false for "cosine" or no option.  false (the return
-// value), with a message, for another name, or for euclidean beside an option it is not served with.
+// value), with a message, for another name.
 static bool parseMetric(int argc, char* argv[], int first, bool& euclidean) {
     euclidean = false;
     for (int i = first; i < argc; ++i) {
@@ -719,83 +494,294 @@ static bool parseMetric(int argc, char* argv[], int first, bool& euclidean) {
         }
         euclidean = name == "euclidean";
     }
-    if (!euclidean) return true;
-    for (int i = first; i < argc; ++i)
-        for (const char* no : {"--diverse", "--pool", "--weights", "--dislike", "--dislike-weight", "--priors", "--prior-weight", "--max-per-artist"})
-            if (std::strcmp(argv[i], no) == 0) {
-                std::cerr << "Error: --metric euclidean cannot be combined with " << no
-                          << " (distance requests take --genre and --where only)" << std::endl;
-                return false;
-            }
     return true;
 }
 
-// --metric euclidean: the songs nearest to one song (--song / --id) or to a playlist's songs, with their distances; with
-// --scale (scales not empty) under either metric: the same over the scaled features, cosine printing its scores.
-static bool nearestMode(const std::string& query, bool isPlaylist, bool isTrackId, int topN,
-                        const std::vector<Recommender::FeatureRange>& ranges, const std::vector<std::string>& genres,
-                        bool euclidean = true, const std::vector<float>& scales = {}) {
-    std::cout << (euclidean ? "=== NEAREST MODE (Euclidean distance) ===" : "=== SCALED MODE (cosine over scaled features) ===") << std::endl;
+// -n N: the first -n among argv[first .. argc-2] (the reference's rule, main.cpp:169-178: in last position it is not looked at).
+static bool parseTopN(int argc, char* argv[], int first, int& topN) {
+    for (int i = first; i < argc - 1; ++i) {
+        if (std::strcmp(argv[i], "-n") != 0) continue;
+        topN = std::atoi(argv[i + 1]);
+        if (topN <= 0) {
+            std::cerr << "Error: Invalid value for -n (must be positive)" << std::endl;
+            return false;
+        }
+        break;
+    }
+    return true;
+}
+
+// --genre NAME, any number of times from argv[first].
+static bool parseGenres(int argc, char* argv[], int first, std::vector<std::string>& genres) {
+    for (int i = first; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--genre") != 0) continue;
+        if (i + 1 >= argc) {
+            std::cerr << "Error: --genre needs a genre name" << std::endl;
+            return false;
+        }
+        genres.push_back(argv[++i]);
+    }
+    return true;
+}
+
+// Everything a query mode's command line says.
+struct Options {
+    bool playlist = false;     // --playlist (else --song / --id)
+    bool isTrackId = false;    // the query names track ids (--id, --playlist), not a song name
+    std::string query;
+    int topN = 10;
+    std::vector<std::string> genres;
+    std::vector<Recommender::FeatureRange> ranges;
+    RowSetOpt rowSet;
+    bool euclidean = false;
+    std::vector<float> scales;
+    Taste taste;
+    DiverseOpt dv;
+    PriorOpt pr;
+    // a distance or scaled request (its own banner; scores or distances are printed; --song / --id run as the one-song playlist)
+    bool nearest() const { return euclidean || !scales.empty(); }
+};
+
+// What does not combine: the option `given` stands for beside one of `beside` (the first of them in argv stands for %s in `text`).
+// A row is looked at where its `given` has just been parsed (parseOptions), so that a command line with two faults reports the
+// one it always reported.  (--seen beside --only, or either twice, is refused where they are parsed: parseRowSet; --pool without
+// --diverse or a cap in parseDiverse.)
+enum class Given {
+    Euclidean,       // --metric euclidean
+    Scale,           // --scale
+    GenreFiltered,   // --genre under --song / --id by unscaled cosine, beside a filter or a row set ...
+    GenreReranked,   // ... and beside a re-rank: --playlist <one id> and the distance and scaled requests serve those pairs
+};
+struct Refusal {
+    Given given;
+    std::vector<const char*> beside;
+    const char* text;
+};
+static const std::vector<const char*> kRequestOptions = {"--diverse",        "--pool",   "--weights",      "--dislike",
+                                                         "--dislike-weight", "--priors", "--prior-weight", "--max-per-artist"};
+static const Refusal kRefusals[] = {
+    {Given::Euclidean, kRequestOptions, "--metric euclidean cannot be combined with %s (distance requests take --genre and --where only)"},
+    {Given::Scale, kRequestOptions, "--scale cannot be combined with %s (scaled requests take --metric, --genre and --where only)"},
+    {Given::GenreFiltered, {"--where"}, "%s cannot be combined with --genre"},
+    {Given::GenreFiltered, {"--seen", "--only"}, "%s cannot be combined with --genre here: use --playlist <one id> --genre ..."},
+    {Given::GenreReranked, {"--max-per-artist"}, "%s cannot be combined with --genre"},
+    {Given::GenreReranked, {"--diverse"}, "%s cannot be combined with --genre"},
+};
+
+// true, with the message, when `given` holds and the command line has an option that one of its rows refuses beside it.
+static bool refused(int argc, char* argv[], int first, const Options& o, Given given) {
+    const bool genreAlone = !o.playlist && !o.nearest() && !o.genres.empty();
+    if (!(given == Given::Euclidean ? o.euclidean : given == Given::Scale ? !o.scales.empty() : genreAlone)) return false;
+    for (const Refusal& r : kRefusals) {
+        if (r.given != given) continue;
+        for (int i = first; i < argc; ++i)
+            for (const char* other : r.beside)
+                if (std::strcmp(argv[i], other) == 0) {
+                    std::string text = r.text;
+                    std::cerr << "Error: " << text.replace(text.find("%s"), 2, other) << std::endl;
+                    return true;
+                }
+    }
+    return false;
+}
+
+// The options of a query mode from argv[3..], each by its own parser, in the order that decides which malformed option is
+// reported first (--song / --id look at --genre first, --playlist after its other options).  false: the message is out.
+static bool parseOptions(int argc, char* argv[], Options& o) {
+    const int first = 3;
+    o.playlist = std::strcmp(argv[1], "--playlist") == 0;
+    o.isTrackId = std::strcmp(argv[1], "--song") != 0;
+    o.query = argv[2];
+    if (!parseTopN(argc, argv, first, o.topN)) return false;
+    if (!o.playlist && !parseGenres(argc, argv, first, o.genres)) return false;
+    if (!parseWhere(argc, argv, first, o.ranges) || !parseRowSet(argc, argv, first, o.rowSet)) return false;
+    if (!parseMetric(argc, argv, first, o.euclidean) || refused(argc, argv, first, o, Given::Euclidean)) return false;
+    if (!parseScale(argc, argv, first, o.scales) || refused(argc, argv, first, o, Given::Scale)) return false;
+    printScales(o.scales);
+    if (refused(argc, argv, first, o, Given::GenreFiltered)) return false;
+    if (o.playlist && !parseTaste(argc, argv, first, o.taste)) return false;
+    if (!parseDiverse(argc, argv, first, o.topN, o.dv) || refused(argc, argv, first, o, Given::GenreReranked)) return false;
+    return !o.playlist || (parseGenres(argc, argv, first, o.genres) && parsePrior(argc, argv, first, o.pr));
+}
+
+// One recommended (or member) song's lines.
+static bool printEntry(const DataManager::Catalogue& catalogue, std::map<int, std::string>& genreMap, int row, size_t number,
+                       const char* indent, const std::string& suffix) {
+    Song song;
+    if (!DataManager::readSong(catalogue, static_cast<size_t>(row), song)) {
+        std::cerr << "Error: could not read song " << row << " from " << catalogue.path << std::endl;
+        return false;
+    }
+    std::cout << indent << number << ". \"" << song.track_name << "\"" << suffix << std::endl;
+    printSong(song, genreMap, *indent ? "     " : "   ");
+    return true;
+}
+
+// The rows of the songs named (track ids, or a song name by the engine's rules); false, with a message, for one that is not there.
+static bool resolveMembers(const DataManager::Catalogue& catalogue, const std::vector<std::string>& names, bool isTrackId,
+                           std::vector<int>& members) {
+    for (const std::string& name : names) {
+        const int index = findQuery(catalogue, name, isTrackId);
+        if (index < 0) {
+            std::cerr << "Error: Song with " << (isTrackId ? "track_id" : "name") << " '" << name << "' not found" << std::endl;
+            return false;
+        }
+        members.push_back(index);
+    }
+    return true;
+}
+
+// Artist groups, genre ids and priors to the recommender, each announced.  oneLine: --song / --id say cap and lambda on one line.
+static bool handOver(Recommender& recommender, const DataManager::Catalogue& catalogue, const Options& o, bool oneLine,
+                     const std::vector<int>& genreIds) {
+    const DiverseOpt& dv = o.dv;
+    if (dv.maxPerArtist > 0) {
+        if (!capByArtist(recommender, catalogue)) return false;
+        std::cout << "At most " << dv.maxPerArtist << " per artist";
+        if (oneLine && dv.lambda < 1.0f) std::cout << "; diversified: lambda " << dv.lambda;
+        std::cout << std::endl;
+    }
+    if (dv.on && (dv.maxPerArtist == 0 || (!oneLine && dv.lambda < 1.0f))) std::cout << "Diversified: lambda " << dv.lambda << std::endl;
+    if (!genreIds.empty()) {
+        std::cout << "Restricted to genres:";
+        for (const std::string& name : o.genres) std::cout << " " << name;
+        std::cout << std::endl;
+        if (!recommender.setGenreIds(catalogue.genreIds)) return false;
+    }
+    if (o.pr.on) {
+        std::vector<float> priors;
+        if (!readPriors(o.pr.file, catalogue.size(), priors) || !recommender.setPriors(priors)) return false;
+        std::cout << "Prior weight: " << o.pr.weight << " (" << o.pr.file << ")" << std::endl;
+    }
+    return true;
+}
+
+// The "Query Song" block of --song / --id.  The reference finds the song it DISPLAYS with a single exact-or-substring
+// pass (main.cpp:85-95), not the engine's exact-then-substring rule; kept.
+static void printQuerySong(const DataManager::Catalogue& catalogue, std::map<int, std::string>& genreMap, const Options& o) {
+    int shown = -1;
+    const std::string needle = lowered(o.query);
+    for (size_t i = 0; i < catalogue.size() && shown < 0; ++i) {
+        const std::string name = o.isTrackId ? std::string() : lowered(catalogue.trackNames[i]);
+        if (o.isTrackId ? catalogue.trackIds[i] == o.query : name == needle || name.find(needle) != std::string::npos) shown = static_cast<int>(i);
+    }
+    Song s;
+    if (shown < 0 || !DataManager::readSong(catalogue, static_cast<size_t>(shown), s)) return;
+    std::cout << "\n----------------------------------------------\nQuery Song:\n"
+              << "  Title:   " << s.track_name << "\n"
+              << "  Artist:  " << s.artists << "\n"
+              << "  Genre:   " << genreMap[s.genre_id] << "\n"
+              << "  ID:      " << s.track_id
+              << "\n----------------------------------------------" << std::endl;
+}
+
+// The query modes (main.cpp:46-131 and the extensions): load the catalogue, resolve the member songs, initialise, apply the row
+// set, hand over genre ids, artist groups and priors, ask, print.  Three flavours differ in what they print and in when they
+// look their songs up: --song / --id by unscaled cosine ("song": the reference's mode; the song is looked up after initialize
+// and whatever goes wrong from there ends in "No recommendations found"), --playlist, and the distance or scaled request of any.
+static bool queryMode(const Options& o) {
+    const bool nearest = o.nearest(), song = !o.playlist && !nearest;
+    std::cout << (nearest ? (o.euclidean ? "=== NEAREST MODE (Euclidean distance) ===" : "=== SCALED MODE (cosine over scaled features) ===")
+                  : song  ? "=== RECOMMENDATION MODE ==="
+                          : "=== PLAYLIST MODE ===")
+              << std::endl;
+    const auto noRecommendations = [] {
+        std::cerr << "No recommendations found. Please check the query." << std::endl;
+        return false;
+    };
+    const auto namesNoTrack = [] {
+        std::cerr << "Error: the playlist names no track" << std::endl;
+        return false;
+    };
+
+    // 1. the catalogue (--playlist looks at its list before it opens it, a distance or scaled request after)
+    std::vector<std::string> names = o.playlist ? splitList(o.query) : std::vector<std::string>{o.query};
+    if (names.empty() && !nearest) return namesNoTrack();
     DataManager::Catalogue catalogue;
     if (!DataManager::loadCatalogue(kBinaryDataFile, catalogue)) {
         std::cerr << "Failed to load data. Have you run preprocessing?" << std::endl;
         return false;
     }
-    std::vector<int> genreIds;
-    if (!genreIdsOf(catalogue, genres, genreIds)) return false;
-    std::vector<int> members;
-    const std::vector<std::string> names = isPlaylist ? splitList(query) : std::vector<std::string>{query};
-    if (names.empty()) {
-        std::cerr << "Error: the playlist names no track" << std::endl;
+    std::map<int, std::string>& genreMap = catalogue.genreMap;
+
+    // 2. the member songs and their weights (the disliked songs are members with a negative weight)
+    const Taste& taste = o.taste;
+    if (taste.haveWeights && taste.weights.size() != names.size()) {
+        std::cerr << "Error: --weights names " << taste.weights.size() << " weights for " << names.size() << " playlist songs" << std::endl;
         return false;
     }
-    for (const std::string& name : names) {
-        const int index = findQuery(catalogue, name, isPlaylist || isTrackId);
-        if (index < 0) {
-            std::cerr << "Error: Song with " << (isPlaylist || isTrackId ? "track_id" : "name") << " '" << name << "' not found" << std::endl;
-            return false;
-        }
-        members.push_back(index);
-    }
+    std::vector<int> genreIds, members;   // --genre: only songs of these genres are recommended (the members may be of any)
+    if (!song && !genreIdsOf(catalogue, o.genres, genreIds)) return false;
+    if (names.empty()) return namesNoTrack();
+    std::vector<float> weights = taste.haveWeights ? taste.weights : std::vector<float>(names.size(), 1.0f);
+    weights.insert(weights.end(), taste.dislike.size(), -taste.dislikeWeight);
+    names.insert(names.end(), taste.dislike.begin(), taste.dislike.end());
+    if (!song && !resolveMembers(catalogue, names, o.isTrackId, members)) return false;
+
+    // 3. the engine, 4. the row set
     Recommender recommender;
     if (!recommender.initialize(catalogue.features, catalogue.trackIds, catalogue.trackNames)) {
         std::cerr << "Failed to initialize recommender" << std::endl;
         return false;
     }
-    if (!applyRowSet(recommender, catalogue)) return false;
-    if (!genreIds.empty()) {
-        std::cout << "Restricted to genres:";
-        for (const std::string& name : genres) std::cout << " " << name;
-        std::cout << std::endl;
-        if (!recommender.setGenreIds(catalogue.genreIds)) return false;
+    if (!applyRowSet(recommender, catalogue, o.rowSet)) return false;
+
+    // (2. for the song flavour.)  Without an extension option it is the reference's own route: recommend / recommendByName look
+    // the song up themselves; with --genre alone its label-scan form.  Everything else is one Recommender::Query.
+    const bool reference = song && !o.dv.on && o.ranges.empty() && !o.rowSet.on;
+    if (song) {
+        std::cout << "\nSearching for " << (o.isTrackId ? "track ID: " : "song: ") << o.query << std::endl;
+        if (!genreIdsOf(catalogue, o.genres, genreIds)) return false;
+        if ((!reference || !genreIds.empty()) && !resolveMembers(catalogue, names, o.isTrackId, members)) return noRecommendations();
     }
-    const std::vector<int> recs = recommender.recommendScaled(members, topN, scales, euclidean, ranges, genreIds);
-    if (recs.empty()) {
-        std::cerr << "No recommendations found. Please check the query." << std::endl;
-        return false;
+
+    // 5. genre ids, artist groups, priors
+    if (!handOver(recommender, catalogue, o, song, genreIds)) return song ? noRecommendations() : false;
+
+    // 6. the request
+    std::vector<int> recs;
+    if (reference && genreIds.empty()) {
+        recs = o.isTrackId ? recommender.recommend(o.query, o.topN) : recommender.recommendByName(o.query, o.topN);
+    } else if (reference) {
+        recs = recommender.recommendByIndexInGenres(members[0], o.topN, genreIds);
+    } else {
+        Recommender::Query q;
+        q.songs = members;
+        // (--song / --id keep recommendByIndex's clamp: the reference's heap never holds more than N-1 entries)
+        q.topN = song ? std::min(o.topN, static_cast<int>(catalogue.size()) - 1) : o.topN;
+        if (taste.weighted) q.weights = weights;
+        q.where = o.ranges;
+        q.genreIds = genreIds;
+        q.diverse = o.dv.on;
+        q.lambda = o.dv.lambda;
+        q.pool = o.dv.pool;
+        q.maxPerArtist = o.dv.maxPerArtist;
+        q.priorWeight = o.pr.on ? o.pr.weight : 0.0f;   // (BETA 0 is the call without a prior)
+        q.scales = o.scales;
+        q.euclidean = o.euclidean;
+        if (q.topN > 0) recs = recommender.recommendQuery(q);
     }
-    const std::vector<float> distances = recommender.lastScores();
-    std::map<int, std::string>& genreMap = catalogue.genreMap;
-    Song song;
-    std::cout << "\n----------------------------------------------\n" << (isPlaylist ? "Playlist" : "Query") << " (" << members.size()
-              << (members.size() == 1 ? " song):" : " songs):") << std::endl;
-    for (size_t i = 0; i < members.size(); ++i) {
-        if (!DataManager::readSong(catalogue, static_cast<size_t>(members[i]), song)) {
-            std::cerr << "Error: could not read song " << members[i] << " from " << catalogue.path << std::endl;
-            return false;
+    if (recs.empty()) return noRecommendations();
+
+    // 7. the query's block, then the recommendations (a distance or scaled request prints their values)
+    const std::vector<float> values = recommender.lastScores();
+    if (song) {
+        printQuerySong(catalogue, genreMap, o);
+    } else {
+        std::cout << "\n----------------------------------------------\n" << (o.playlist ? "Playlist" : "Query") << " (" << members.size()
+                  << (nearest && members.size() == 1 ? " song):" : " songs):") << std::endl;
+        for (size_t i = 0; i < members.size(); ++i) {
+            std::ostringstream weight;
+            if (taste.weighted) weight << "  (weight " << weights[i] << ")";
+            if (!printEntry(catalogue, genreMap, members[i], i + 1, "  ", weight.str())) return false;
         }
-        std::cout << "  " << (i + 1) << ". \"" << song.track_name << "\"" << std::endl;
-        printSong(song, genreMap, "     ");
+        std::cout << "----------------------------------------------" << std::endl;
     }
-    std::cout << "----------------------------------------------" << std::endl;
     std::cout << "\nTop " << recs.size() << " Recommendations:\n" << std::endl;
     for (size_t i = 0; i < recs.size(); ++i) {
-        if (!DataManager::readSong(catalogue, static_cast<size_t>(recs[i]), song)) {
-            std::cerr << "Error: could not read song " << recs[i] << " from " << catalogue.path << std::endl;
-            return false;
-        }
-        std::cout << (i + 1) << ". \"" << song.track_name << "\"  (" << (euclidean ? "distance " : "score ") << distances[i] << ")" << std::endl;
-        printSong(song, genreMap, "   ");
+        std::ostringstream value;
+        if (nearest) value << "  (" << (o.euclidean ? "distance " : "score ") << values[i] << ")";
+        if (!printEntry(catalogue, genreMap, recs[i], i + 1, "", value.str())) return false;
         if (i + 1 < recs.size()) std::cout << std::endl;
     }
     std::cout << "\nRecommendation complete!" << std::endl;
@@ -818,108 +804,18 @@ int main(int argc, char* argv[]) {
         }
         return preprocessMode(argv[2]) ? 0 : 1;
     }
-    if (mode == "--song" || mode == "--id") {
+    if (mode == "--song" || mode == "--id" || mode == "--playlist") {
+        if (argc < 3 && mode == "--playlist") {
+            std::cerr << "Error: --playlist needs a comma-separated list of track IDs" << std::endl;
+            return 1;
+        }
         if (argc < 3) {
             std::cerr << "Error: Song name or track ID required" << std::endl;
             usage(argv[0]);
             return 1;
         }
-        int topN = 10;
-        for (int i = 3; i < argc - 1; ++i) {  // main.cpp:169-178
-            if (std::strcmp(argv[i], "-n") == 0) {
-                topN = std::atoi(argv[i + 1]);
-                if (topN <= 0) {
-                    std::cerr << "Error: Invalid value for -n (must be positive)" << std::endl;
-                    return 1;
-                }
-                break;
-            }
-        }
-        std::vector<std::string> genres;   // --genre NAME, any number of times
-        for (int i = 3; i < argc; ++i) {
-            if (std::strcmp(argv[i], "--genre") != 0) continue;
-            if (i + 1 >= argc) {
-                std::cerr << "Error: --genre needs a genre name" << std::endl;
-                return 1;
-            }
-            genres.push_back(argv[++i]);
-        }
-        std::vector<Recommender::FeatureRange> ranges;
-        if (!parseWhere(argc, argv, 3, ranges)) return 1;
-        if (!parseRowSet(argc, argv, 3, g_rowSet)) return 1;
-        bool euclidean = false;
-        if (!parseMetric(argc, argv, 3, euclidean)) return 1;
-        std::vector<float> scales;
-        if (!parseScale(argc, argv, 3, scales)) return 1;
-        if (euclidean || !scales.empty()) return nearestMode(argv[2], false, mode == "--id", topN, ranges, genres, euclidean, scales) ? 0 : 1;
-        if (!ranges.empty() && !genres.empty()) {
-            std::cerr << "Error: --where cannot be combined with --genre" << std::endl;
-            return 1;
-        }
-        if (g_rowSet.on && !genres.empty()) {
-            std::cerr << "Error: " << (g_rowSet.only ? "--only" : "--seen") << " cannot be combined with --genre here: use --playlist <one id> --genre ..."
-                      << std::endl;
-            return 1;
-        }
-        DiverseOpt dv;
-        if (!parseDiverse(argc, argv, 3, topN, dv)) return 1;
-        if (dv.on && !genres.empty()) {
-            std::cerr << "Error: " << (dv.maxPerArtist > 0 ? "--max-per-artist" : "--diverse") << " cannot be combined with --genre" << std::endl;
-            return 1;
-        }
-        return recommendationMode(argv[2], mode == "--id", topN, genres, ranges, dv) ? 0 : 1;
-    }
-    if (mode == "--playlist") {
-        if (argc < 3) {
-            std::cerr << "Error: --playlist needs a comma-separated list of track IDs" << std::endl;
-            return 1;
-        }
-        int topN = 10;
-        for (int i = 3; i < argc - 1; ++i) {
-            if (std::strcmp(argv[i], "-n") == 0) {
-                topN = std::atoi(argv[i + 1]);
-                if (topN <= 0) {
-                    std::cerr << "Error: Invalid value for -n (must be positive)" << std::endl;
-                    return 1;
-                }
-                break;
-            }
-        }
-        std::vector<Recommender::FeatureRange> ranges;
-        if (!parseWhere(argc, argv, 3, ranges)) return 1;
-        if (!parseRowSet(argc, argv, 3, g_rowSet)) return 1;
-        bool euclidean = false;
-        if (!parseMetric(argc, argv, 3, euclidean)) return 1;
-        std::vector<float> scales;
-        if (!parseScale(argc, argv, 3, scales)) return 1;
-        if (euclidean || !scales.empty()) {
-            std::vector<std::string> in_genres;
-            for (int i = 3; i < argc; ++i) {
-                if (std::strcmp(argv[i], "--genre") != 0) continue;
-                if (i + 1 >= argc) {
-                    std::cerr << "Error: --genre needs a genre name" << std::endl;
-                    return 1;
-                }
-                in_genres.push_back(argv[++i]);
-            }
-            return nearestMode(argv[2], true, true, topN, ranges, in_genres, euclidean, scales) ? 0 : 1;
-        }
-        Taste taste;
-        if (!parseTaste(argc, argv, 3, taste)) return 1;
-        DiverseOpt dv;
-        if (!parseDiverse(argc, argv, 3, topN, dv)) return 1;
-        std::vector<std::string> genres;   // --genre NAME, any number of times
-        for (int i = 3; i < argc; ++i) {
-            if (std::strcmp(argv[i], "--genre") != 0) continue;
-            if (i + 1 >= argc) {
-                std::cerr << "Error: --genre needs a genre name" << std::endl;
-                return 1;
-            }
-            genres.push_back(argv[++i]);
-        }
-        PriorOpt pr;
-        if (!parsePrior(argc, argv, 3, pr)) return 1;
-        return playlistMode(argv[2], topN, ranges, taste, dv, genres, pr) ? 0 : 1;
+        Options o;
+        return parseOptions(argc, argv, o) && queryMode(o) ? 0 : 1;
     }
     std::cerr << "Error: Unknown mode '" << mode << "'" << std::endl;
     usage(argv[0]);

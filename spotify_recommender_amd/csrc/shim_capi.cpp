@@ -275,6 +275,54 @@ int64_t shim_recommend_for_playlist_capped(void* h, const int* songs, int n_song
                                                    max_per_artist),
                     out, scores, cap);
 }
+// Recommender::setPriors (one per song) and Recommender::recommendQuery, the Query's fields as flat arrays (a count of 0: empty).
+int shim_set_priors(void* h, const float* priors) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    return c->rec.setPriors(std::vector<float>(priors, priors + c->rec.getSongCount())) ? 1 : 0;
+}
+int64_t shim_query(void* h, const int* songs, int n_songs, const float* weights, int n_weights, const int* features, const float* lo,
+                   const float* hi, int n_ranges, const int* exclude, int n_exclude, const int* genres, int n_genres, int diverse,
+                   float lambda, int pool, int max_per_artist, float prior_weight, const float* scales, int n_scales, int euclidean,
+                   int topn, int* out, float* scores, int64_t cap) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    Recommender::Query q;
+    q.songs.assign(songs, songs + n_songs);
+    q.weights.assign(weights, weights + n_weights);
+    q.where = ranges(features, lo, hi, n_ranges);
+    q.alsoExclude.assign(exclude, exclude + n_exclude);
+    q.genreIds.assign(genres, genres + n_genres);
+    q.diverse = diverse != 0;
+    q.lambda = lambda;
+    q.pool = pool;
+    q.maxPerArtist = max_per_artist;
+    q.priorWeight = prior_weight;
+    q.scales.assign(scales, scales + n_scales);
+    q.euclidean = euclidean != 0;
+    q.topN = topn;
+    return giveBack(c, c->rec.recommendQuery(q), out, scores, cap);
+}
+// The most general recommendForPlaylist overload (genre ids and a prior weight last) and recommendScaled (n_scales 0: none;
+// recommendNearest is its euclidean form without scales).
+int64_t shim_recommend_for_playlist_general(void* h, const int* songs, int n_songs, const float* weights, int n_weights, int topn,
+                                            const int* features, const float* lo, const float* hi, int n_ranges, const int* exclude,
+                                            int n_exclude, float lambda, int pool, int max_per_artist, const int* genres, int n_genres,
+                                            float prior_weight, int* out, float* scores, int64_t cap) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    return giveBack(c, c->rec.recommendForPlaylist(std::vector<int>(songs, songs + n_songs), topn, std::vector<float>(weights, weights + n_weights),
+                                                   ranges(features, lo, hi, n_ranges), std::vector<int>(exclude, exclude + n_exclude), lambda,
+                                                   pool, max_per_artist, std::vector<int>(genres, genres + n_genres), prior_weight),
+                    out, scores, cap);
+}
+int64_t shim_recommend_scaled(void* h, const int* songs, int n_songs, int topn, const float* scales, int n_scales, int euclidean,
+                              const int* features, const float* lo, const float* hi, int n_ranges, const int* genres, int n_genres, int* out,
+                              float* scores, int64_t cap) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    const std::vector<int> s(songs, songs + n_songs), g(genres, genres + n_genres);
+    const std::vector<Recommender::FeatureRange> where = ranges(features, lo, hi, n_ranges);
+    return giveBack(c, euclidean && n_scales == 0 ? c->rec.recommendNearest(s, topn, where, g)
+                                                  : c->rec.recommendScaled(s, topn, std::vector<float>(scales, scales + n_scales), euclidean != 0, where, g),
+                    out, scores, cap);
+}
 int shim_artist_groups(void* h, int* out_n) {
     Catalogue* c = static_cast<Catalogue*>(h);
     std::vector<std::string> artists;

@@ -344,13 +344,111 @@ class _RowSets:
             return call((tmp._ptr(), mode))
 
 
-class CosineEngine(_RowSets):
+class _RequestFamily(_RowSets):
+    """What both engines share for the playlist request family and the distance request: the calls that differ between a
+    single handle and a node handle only in the C-ABI's symbol prefix (`_prefix`) and in how a return code is checked
+    (`_check`).  Rows are local rows of a CosineEngine and global rows of a NodeEngine."""
+
+    def _entry(self, name: str):
+        return getattr(self._lib, self._prefix + name)
+
+    def _set_per_row(self, name: str, values, convert) -> None:
+        if values is None:
+            self._check(self._entry(name)(self._h, None, 0))
+            return
+        a = convert(values)
+        self._check(self._entry(name)(self._h, a.ctypes.data_as(ctypes.c_void_p), int(a.size)))
+
+    # ---- LABELS (include/mi355rec_diag.h): label-filtered top-N ----
+    def set_labels(self, labels) -> None:
+        """One label per row in [0, capi.MAX_LABELS), -1 = unlabelled; None drops the labels."""
+        self._set_per_row("set_labels", labels, _np_labels)
+
+    # ---- PLAYLISTS (include/mi355rec_diag.h): top-N by the mean score against up to 32 songs ----
+    def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None,
+                        scales=None, seen=None, only=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The best `topn` rows by the mean of their scores against the rows of `queries` (k x 12); `exclude`: global ids.
+        `where`: {feature index or name: (lo, hi)}, only rows within every range are returned (FEATURE FILTERS; a
+        filtered single query is k = 1); None calls the unfiltered entry point.
+        `weights`: one signed float per member (WEIGHTED PLAYLISTS: score = sum w_k c_k / sum |w_k|, a negative weight is
+        a dislike); None calls the entry point used without it.
+        `scales`: FEATURE SCALES, 12 floats or {feature index or name: scale} (unnamed features 1.0): rows and members are
+        multiplied feature by feature before the scores are taken (0 ignores a feature); not with prior_weight.
+        `seen` / `only`: ROW SETS, a RowSet (row_set) or a plain sequence of global ids: the rows of `seen` are never returned (a
+        listening history of any length); with `only`, only its rows are ranked (a candidate set).  Mutually exclusive.
+        query_playlist_topn is the same for members given as rows of the engine; the members are then never returned
+        (whatever their weight)."""
+        return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales,
+                              seen=seen, only=only)
+
+    def _playlist(self, members, topn, exclude, where, weights, level=None, labels=None, seen=None, only=None, **more):
+        return self._with_set(seen, only, lambda rowset: _playlist_family(
+            self._lib, self._prefix, self._h, self._check, members, topn, exclude, where, weights, level, labels=labels,
+            rowset=rowset, **more))
+
+    # ---- DISTANCE REQUESTS (include/mi355rec_diag.h): the nearest rows by Euclidean distance ----
+    def query_nearest(self, members, topn: int, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The `topn` rows nearest to the rows of `members` (k x 12) by Euclidean distance over the 12 features: (ids,
+        distances), nearest first.  k > 1: the root-mean-square distance to the members (as a ranking: the distance to their
+        centroid).  `exclude`, `where`, `labels`: as in query_mean_topn."""
+        return self._nearest(_np_members(members), topn, None, exclude, where, labels, None, None)
+
+    def query_nearest_rows(self, rows, topn: int, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The same for members given as rows of the engine; the members are never returned."""
+        return self._nearest(_np_rows(rows), topn, None, exclude, where, labels, None, None)
+
+    def query_nearest_scaled(self, members, topn: int, scales, exclude=None, where=None, labels=None, seen=None,
+                             only=None) -> Tuple[np.ndarray, np.ndarray]:
+        """query_nearest with FEATURE SCALES (`scales` as in query_mean_topn; None: none): the distances are taken between the
+        scaled members and the scaled rows; the filter still tests the stored rows.  `seen` / `only`: ROW SETS, as in
+        query_mean_topn (query_nearest itself keeps its parameter list)."""
+        return self._nearest(_np_members(members), topn, scales, exclude, where, labels, seen, only)
+
+    def query_nearest_rows_scaled(self, rows, topn: int, scales, exclude=None, where=None, labels=None, seen=None,
+                                  only=None) -> Tuple[np.ndarray, np.ndarray]:
+        """query_nearest_rows with FEATURE SCALES and ROW SETS."""
+        return self._nearest(_np_rows(rows), topn, scales, exclude, where, labels, seen, only)
+
+    def _nearest(self, members, topn, scales, exclude, where, labels, seen, only):
+        return self._with_set(seen, only, lambda rowset: _distance_request(
+            self._lib, self._prefix, self._h, self._check, members, topn, exclude, where, labels, scales, rowset))
+
+    # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h): MMR picks from the top-`pool` of the weighted playlist call ----
+    def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False,
+                                labels=None, prior_weight=None, seen=None, only=None):
+        """`topn` rows picked greedily from the `pool` most relevant (query_mean_topn's order): each pick maximises
+        lam * relevance - (1 - lam) * (its largest similarity to a row already picked).  Pick order; scores = relevance.
+        query_playlist_topn_diverse is the same for members given as rows of the engine (never returned)."""
+        return self._playlist(_np_members(queries), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr,
+                              labels=labels, prior_weight=prior_weight, seen=seen, only=only)
+
+    def set_groups(self, groups) -> None:
+        """One group id per row (GROUP CAPS): >= 0 a group (an artist, say), -1 = never capped; None drops the groups."""
+        self._set_per_row("set_groups", groups, _np_groups)
+
+    def set_priors(self, priors) -> None:
+        """One float per row in [-1, 1] (ROW PRIORS: popularity, freshness, a boost); None drops the priors."""
+        self._set_per_row("set_priors", priors, _np_priors)
+
+    def query_mean_topn_capped(self, queries, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
+                               weights=None, return_mmr=False, return_pool_rows=False, labels=None, prior_weight=None,
+                               seen=None, only=None):
+        """query_mean_topn_diverse with at most `max_per_group` results per group of set_groups (GROUP CAPS);
+        query_playlist_topn_capped: for members given as rows of the engine."""
+        return self._playlist(_np_members(queries), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
+                              max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows,
+                              labels=labels, prior_weight=prior_weight, seen=seen, only=only)
+
+
+class CosineEngine(_RequestFamily):
     """One row shard of the N x 12 fp32 catalogue resident on one MI355X.
 
     Replaces the reference's device state (d_features / d_queryFeature /
     d_similarities, Recommender.h:91-94) and its per-query pipeline
     (Recommender.cu:184-254 + :293-315).
     """
+
+    _prefix = "mi355rec_"
 
     def __init__(self, feats, device: int = 0, row_base: int = 0, flags: int = 0):
         """flags: capi.CREATE_NO_REPLICA = keep the fp32 rows only (48 B per row resident instead of 84)."""
@@ -420,8 +518,10 @@ class CosineEngine(_RowSets):
         and its lanes as `seen=` or `only=`."""
         return RowSet(self, ids, self._lib.mi355rec_rowset_create)
 
-    def _set_check(self, rc: int) -> None:
+    def _check(self, rc: int) -> None:
         capi.check(rc, self._h)
+
+    _set_check = _check
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h:
@@ -737,14 +837,6 @@ class CosineEngine(_RowSets):
         return st
 
     # ---- LABELS (include/mi355rec_diag.h): label-filtered top-N ----
-    def set_labels(self, labels) -> None:
-        """One label per row in [0, capi.MAX_LABELS), -1 = unlabelled; None drops the labels."""
-        if labels is None:
-            capi.check(self._lib.mi355rec_set_labels(self._h, None, 0), self._h)
-            return
-        lab = _np_labels(labels)
-        capi.check(self._lib.mi355rec_set_labels(self._h, lab.ctypes.data_as(ctypes.c_void_p), int(lab.size)), self._h)
-
     def query_row_topn_labels(self, local_row: int, labels, topn: int) -> Tuple[np.ndarray, np.ndarray]:
         """The best `topn` rows whose label is in `labels`, the query row excluded."""
         return _labels_query(self._lib.mi355rec_query_row_topn_labels, self._h, lambda rc: capi.check(rc, self._h),
@@ -761,97 +853,17 @@ class CosineEngine(_RowSets):
         return {"queries": q.value, "rows_scanned": r.value}
 
 
-    # ---- PLAYLISTS (include/mi355rec_diag.h): top-N by the mean score against up to 32 songs ----
-    def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None,
-                        scales=None, seen=None, only=None) -> Tuple[np.ndarray, np.ndarray]:
-        """The best `topn` rows by the mean of their scores against the rows of `queries` (k x 12); `exclude`: global ids.
-        `where`: {feature index or name: (lo, hi)}, only rows within every range are returned (FEATURE FILTERS; a
-        filtered single query is k = 1); None calls the unfiltered entry point.
-        `weights`: one signed float per member (WEIGHTED PLAYLISTS: score = sum w_k c_k / sum |w_k|, a negative weight is
-        a dislike); None calls the entry point used without it.
-        `scales`: FEATURE SCALES, 12 floats or {feature index or name: scale} (unnamed features 1.0): rows and members are
-        multiplied feature by feature before the scores are taken (0 ignores a feature); not with prior_weight.
-        `seen` / `only`: ROW SETS, a RowSet (row_set) or a plain sequence of global ids: the rows of `seen` are never returned (a
-        listening history of any length); with `only`, only its rows are ranked (a candidate set).  Mutually exclusive."""
-        return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales,
-                              seen=seen, only=only)
-
+    # ---- the by-row forms of the request family (_RequestFamily): the members are rows of this handle ----
     def query_playlist_topn(self, local_rows, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None,
                             scales=None, seen=None, only=None) -> Tuple[np.ndarray, np.ndarray]:
         """The same for members given as rows of this handle; the members are never returned (whatever their weight)."""
         return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales,
                               seen=seen, only=only)
 
-    def _playlist(self, members, topn, exclude, where, weights, level=None, labels=None, seen=None, only=None, **more):
-        return self._with_set(seen, only, lambda rowset: _playlist_family(
-            self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), members, topn, exclude, where, weights, level,
-            labels=labels, rowset=rowset, **more))
-
-    # ---- DISTANCE REQUESTS (include/mi355rec_diag.h): the nearest rows by Euclidean distance ----
-    def query_nearest(self, members, topn: int, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
-        """The `topn` rows nearest to the rows of `members` (k x 12) by Euclidean distance over the 12 features: (ids,
-        distances), nearest first.  k > 1: the root-mean-square distance to the members (as a ranking: the distance to their
-        centroid).  `exclude`, `where`, `labels`: as in query_mean_topn."""
-        return _distance_request(self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), _np_members(members), topn,
-                                 exclude, where, labels)
-
-    def query_nearest_rows(self, rows, topn: int, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
-        """The same for members given as rows of this handle; the members are never returned."""
-        return _distance_request(self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), _np_rows(rows), topn,
-                                 exclude, where, labels)
-
-    def query_nearest_scaled(self, members, topn: int, scales, exclude=None, where=None, labels=None, seen=None,
-                             only=None) -> Tuple[np.ndarray, np.ndarray]:
-        """query_nearest with FEATURE SCALES (`scales` as in query_mean_topn; None: none): the distances are taken between the
-        scaled members and the scaled rows; the filter still tests the stored rows.  `seen` / `only`: ROW SETS, as in
-        query_mean_topn (query_nearest itself keeps its parameter list)."""
-        return self._nearest(_np_members(members), topn, scales, exclude, where, labels, seen, only)
-
-    def query_nearest_rows_scaled(self, rows, topn: int, scales, exclude=None, where=None, labels=None, seen=None,
-                                  only=None) -> Tuple[np.ndarray, np.ndarray]:
-        """query_nearest_rows with FEATURE SCALES and ROW SETS."""
-        return self._nearest(_np_rows(rows), topn, scales, exclude, where, labels, seen, only)
-
-    def _nearest(self, members, topn, scales, exclude, where, labels, seen, only):
-        return self._with_set(seen, only, lambda rowset: _distance_request(
-            self._lib, "mi355rec_", self._h, lambda rc: capi.check(rc, self._h), members, topn, exclude, where, labels, scales, rowset))
-
-    # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h): MMR picks from the top-`pool` of the weighted playlist call ----
-    def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False,
-                                labels=None, prior_weight=None, seen=None, only=None):
-        """`topn` rows picked greedily from the `pool` most relevant (query_mean_topn's order): each pick maximises
-        lam * relevance - (1 - lam) * (its largest similarity to a row already picked).  Pick order; scores = relevance."""
-        return self._playlist(_np_members(queries), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr,
-                              labels=labels, prior_weight=prior_weight, seen=seen, only=only)
-
     def query_playlist_topn_diverse(self, local_rows, topn: int, lam, pool=None, exclude=None, where=None, weights=None,
                                     return_mmr=False, labels=None, prior_weight=None, seen=None, only=None):
         """The same for members given as rows of this handle (never returned)."""
         return self._playlist(_np_rows(local_rows), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr,
-                              labels=labels, prior_weight=prior_weight, seen=seen, only=only)
-
-    def set_groups(self, groups) -> None:
-        """One group id per row (GROUP CAPS): >= 0 a group (an artist, say), -1 = never capped; None drops the groups."""
-        if groups is None:
-            capi.check(self._lib.mi355rec_set_groups(self._h, None, 0), self._h)
-            return
-        g = _np_groups(groups)
-        capi.check(self._lib.mi355rec_set_groups(self._h, g.ctypes.data_as(ctypes.c_void_p), int(g.size)), self._h)
-
-    def set_priors(self, priors) -> None:
-        """One float per row in [-1, 1] (ROW PRIORS: popularity, freshness, a boost); None drops the priors."""
-        if priors is None:
-            capi.check(self._lib.mi355rec_set_priors(self._h, None, 0), self._h)
-            return
-        p = _np_priors(priors)
-        capi.check(self._lib.mi355rec_set_priors(self._h, p.ctypes.data_as(ctypes.c_void_p), int(p.size)), self._h)
-
-    def query_mean_topn_capped(self, queries, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
-                               weights=None, return_mmr=False, return_pool_rows=False, labels=None, prior_weight=None,
-                               seen=None, only=None):
-        """query_mean_topn_diverse with at most `max_per_group` results per group of set_groups (GROUP CAPS)."""
-        return self._playlist(_np_members(queries), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
-                              max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows,
                               labels=labels, prior_weight=prior_weight, seen=seen, only=only)
 
     def query_playlist_topn_capped(self, local_rows, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
@@ -875,12 +887,14 @@ class CosineEngine(_RowSets):
         return {"queries": q.value, "rows_exact": r.value}
 
 
-class NodeEngine(_RowSets):
+class NodeEngine(_RequestFamily):
     """The catalogue on the GPUs of one node driven by ONE process (mi355rec_create_placed): what the C++
     Recommender shim uses.  `placement`: capi.PLACEMENT_SHARDED (rows split over the devices; the default),
     PLACEMENT_REPLICATED (every device holds all rows and serves whole windows of the stream).
     `devices=None` -> devices 0 .. n_devices-1, n_devices = 0 letting the library choose; a list may repeat a
     device (virtual shards / replicas on a one-GPU box)."""
+
+    _prefix = "mi355rec_sharded_"
 
     def __init__(self, feats, devices=None, n_devices: int = 0, placement: int = capi.PLACEMENT_SHARDED):
         self._lib = capi.lib()
@@ -981,14 +995,6 @@ class NodeEngine(_RowSets):
         return idx, score, counts
 
     # ---- LABELS (include/mi355rec_diag.h): label-filtered top-N over the whole node ----
-    def set_labels(self, labels) -> None:
-        """One label per row in [0, capi.MAX_LABELS), -1 = unlabelled; None drops the labels."""
-        if labels is None:
-            self._check(self._lib.mi355rec_sharded_set_labels(self._h, None, 0))
-            return
-        lab = _np_labels(labels)
-        self._check(self._lib.mi355rec_sharded_set_labels(self._h, lab.ctypes.data_as(ctypes.c_void_p), int(lab.size)))
-
     def query_row_topn_labels(self, global_row: int, labels, topn: int) -> Tuple[np.ndarray, np.ndarray]:
         return _labels_query(self._lib.mi355rec_sharded_query_row_topn_labels, self._h, self._check, (int(global_row),), labels, topn)
 
@@ -997,79 +1003,17 @@ class NodeEngine(_RowSets):
         return _labels_query(self._lib.mi355rec_sharded_query_topn_labels, self._h, self._check,
                              (q.ctypes.data_as(ctypes.c_void_p), int(exclude_global)), labels, topn)
 
-    # ---- PLAYLISTS (include/mi355rec_diag.h) over the whole node ----
-    def query_mean_topn(self, queries, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None,
-                        scales=None, seen=None, only=None) -> Tuple[np.ndarray, np.ndarray]:
-        return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales,
-                              seen=seen, only=only)
-
+    # ---- the by-row forms of the request family (_RequestFamily): the members are global rows ----
     def query_playlist_topn(self, global_rows, topn: int, exclude=None, where=None, weights=None, labels=None, prior_weight=None,
                             scales=None, seen=None, only=None) -> Tuple[np.ndarray, np.ndarray]:
         return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales,
                               seen=seen, only=only)
-
-    def _playlist(self, members, topn, exclude, where, weights, level=None, labels=None, seen=None, only=None, **more):
-        return self._with_set(seen, only, lambda rowset: _playlist_family(
-            self._lib, "mi355rec_sharded_", self._h, self._check, members, topn, exclude, where, weights, level, labels=labels,
-            rowset=rowset, **more))
-
-    # ---- DISTANCE REQUESTS (include/mi355rec_diag.h) over the whole node ----
-    def query_nearest(self, members, topn: int, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
-        """The `topn` rows nearest to the rows of `members` (k x 12) by Euclidean distance: (ids, distances)."""
-        return _distance_request(self._lib, "mi355rec_sharded_", self._h, self._check, _np_members(members), topn, exclude, where, labels)
-
-    def query_nearest_rows(self, rows, topn: int, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
-        """The same for members given as global rows (never returned)."""
-        return _distance_request(self._lib, "mi355rec_sharded_", self._h, self._check, _np_rows(rows), topn, exclude, where, labels)
-
-    def query_nearest_scaled(self, members, topn: int, scales, exclude=None, where=None, labels=None, seen=None,
-                             only=None) -> Tuple[np.ndarray, np.ndarray]:
-        """query_nearest with FEATURE SCALES (12 floats or {feature index or name: scale}; None: none) and ROW SETS."""
-        return self._nearest(_np_members(members), topn, scales, exclude, where, labels, seen, only)
-
-    def query_nearest_rows_scaled(self, rows, topn: int, scales, exclude=None, where=None, labels=None, seen=None,
-                                  only=None) -> Tuple[np.ndarray, np.ndarray]:
-        """query_nearest_rows with FEATURE SCALES and ROW SETS."""
-        return self._nearest(_np_rows(rows), topn, scales, exclude, where, labels, seen, only)
-
-    def _nearest(self, members, topn, scales, exclude, where, labels, seen, only):
-        return self._with_set(seen, only, lambda rowset: _distance_request(
-            self._lib, "mi355rec_sharded_", self._h, self._check, members, topn, exclude, where, labels, scales, rowset))
-
-    # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h) over the whole node ----
-    def set_groups(self, groups) -> None:
-        """One group id per row (GROUP CAPS): >= 0 a group, -1 = never capped; None drops the groups."""
-        if groups is None:
-            self._check(self._lib.mi355rec_sharded_set_groups(self._h, None, 0))
-            return
-        g = _np_groups(groups)
-        self._check(self._lib.mi355rec_sharded_set_groups(self._h, g.ctypes.data_as(ctypes.c_void_p), int(g.size)))
-
-    def set_priors(self, priors) -> None:
-        """One float per row in [-1, 1] (ROW PRIORS); None drops the priors."""
-        if priors is None:
-            self._check(self._lib.mi355rec_sharded_set_priors(self._h, None, 0))
-            return
-        p = _np_priors(priors)
-        self._check(self._lib.mi355rec_sharded_set_priors(self._h, p.ctypes.data_as(ctypes.c_void_p), int(p.size)))
-
-    def query_mean_topn_capped(self, queries, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
-                               weights=None, return_mmr=False, return_pool_rows=False, labels=None, prior_weight=None,
-                               seen=None, only=None):
-        return self._playlist(_np_members(queries), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
-                              max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows,
-                              labels=labels, prior_weight=prior_weight, seen=seen, only=only)
 
     def query_playlist_topn_capped(self, global_rows, topn: int, max_per_group: int, lam=1.0, pool=None, exclude=None, where=None,
                                    weights=None, return_mmr=False, return_pool_rows=False, labels=None, prior_weight=None,
                                    seen=None, only=None):
         return self._playlist(_np_rows(global_rows), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
                               max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows,
-                              labels=labels, prior_weight=prior_weight, seen=seen, only=only)
-
-    def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False,
-                                labels=None, prior_weight=None, seen=None, only=None):
-        return self._playlist(_np_members(queries), topn, exclude, where, weights, "_diverse", lam=lam, pool=pool, return_mmr=return_mmr,
                               labels=labels, prior_weight=prior_weight, seen=seen, only=only)
 
     def query_playlist_topn_diverse(self, global_rows, topn: int, lam, pool=None, exclude=None, where=None, weights=None,
