@@ -25,6 +25,7 @@
 #ifndef RECOMMENDER_H
 #define RECOMMENDER_H
 
+#include <cstdint>
 #include <map>
 #include <string>
 #include <vector>
@@ -187,6 +188,15 @@ public:
     // it was.
     bool setRowSet(const std::vector<int>& songIndices, bool only = false);
     void clearRowSet();
+
+    // Extension: candidate lists (include/mi355rec_diag.h, "CANDIDATE LISTS").  setCandidates gives the songs to rank within, the
+    // output of a first stage: any order, duplicates allowed, at most 1 048 576.  Where setRowSet(..., true) keeps one bit per song
+    // and every request reads the whole catalogue, a request with a list reads only the listed songs; the results are the same.  The
+    // list applies to the calls the row set applies to, until clearCandidates() or the next setCandidates, and goes with a row set
+    // (setRowSet(history) and setCandidates(candidates): the candidates not heard yet).  An empty list is a list: nothing is
+    // returned.  An index outside the songs gives false and a message, and the list as it was.
+    bool setCandidates(const std::vector<int64_t>& songIndices);
+    void clearCandidates();
 
     // Extension: one description of a request.  Every method above that takes a playlist (and recommendByIndexWhere,
     // recommendDiverse, recommendByIndexCapped, which take the one-song playlist) fills a Query and runs it through

@@ -869,7 +869,7 @@ int mi355rec_sharded_query_distance_request_scaled(mi355rec_sharded_t* h, const 
  * distance request, K = 1: 94.8, 98.2, 98.1, 96.7, 81.5 us.  Calls without a set are within the parent build's own spread
  * (profiles/r17_rowset_ab.json).
  * Not served: sets on the single-query, streamed, batched and label-only routes; two sets in one request; removing ids; set
- * algebra; a gather path that scores only the listed rows of a tiny ONLY set. */
+ * algebra.  (A request that names its candidates reads only those rows: CANDIDATE LISTS below.) */
 typedef struct mi355rec_rowset mi355rec_rowset_t;
 int mi355rec_rowset_create(mi355rec_t* h, const int64_t* global_ids, int64_t n_ids, mi355rec_rowset_t** out);
 int mi355rec_sharded_rowset_create(mi355rec_sharded_t* h, const int64_t* global_ids, int64_t n_ids, mi355rec_rowset_t** out);
@@ -893,6 +893,59 @@ int mi355rec_sharded_query_playlist_request_ext(mi355rec_sharded_t* h, const mi3
                                                 const mi355rec_request_ext_t* ext, const mi355rec_playlist_result_t* result);
 int mi355rec_sharded_query_distance_request_ext(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
                                                 const mi355rec_request_ext_t* ext, const mi355rec_distance_result_t* result);
+
+/* CANDIDATE LISTS: "rank these few thousand candidates", the second stage of a two-stage recommender (the first stage being
+ * collaborative filtering, a market's licensed tracks, a search hit list).  An ONLY row set serves it with n / 8 bytes of bitmap built
+ * and uploaded per request and one pass over the whole catalogue.  A request may instead carry the LIST itself: n_candidates global
+ * row ids, any order, duplicates allowed.  Only listed rows are admissible; the engine GATHERS exactly those rows, scores them with
+ * the request's own exact chain and selects the top-N.  The list is an argument of four entry points (mi355rec_request_ext_t keeps
+ * its 24 bytes), which otherwise are the _ext calls: ext may be NULL.
+ * CONTRACT, bit for bit.  A request with the list C returns what the same request returns with an ONLY row set made from C and no
+ * list: ids, order, score bits, out_count, out_mmr, out_pool_rows, padding.  Everything else keeps its meaning and its arithmetic:
+ * exclusion list, member rows, filter, label set, prior, weights, MMR, caps, distance, scales.  If ext carries a row set S as well,
+ * both must admit a row: ONLY S ranks within C n S, EXCLUDE S within C \ S (candidates minus a listening history, the common
+ * pairing).  Members may be listed and are never returned.  The result does not depend on replica mode, lane, shard count or
+ * placement.
+ * ARGUMENTS: every check and message of the _ext call comes first, then the list's: n_candidates == 0 is an empty list (count 0,
+ * padded, nothing is launched); a NULL list with n_candidates > 0, n_candidates < 0 and n_candidates > MI355REC_MAX_CANDIDATES
+ * (4 MB of staged ids) are INVALID_ARG.  Single handle: an id below 0 or at or above 2^32 is INVALID_ARG (named in the message, as
+ * for row sets); ids outside [row_base, row_base + n) match nothing.  Node handle: an id below 0 or at or above n is INVALID_ARG.
+ * HOST (csrc/candidates.h): the list is reduced to the shard's sorted, distinct local rows as uint32 (one pass checks the ids on a
+ * single handle, keeps those of the shard and tests whether they already ascend strictly: then nothing is sorted), staged through a pinned buffer of the handle and copied on the
+ * handle's stream ahead of the launch; both buffers grow on demand.  A row-sharded node gives each shard the ids of its range (a
+ * shard with none launches nothing), a replicated one gives the serving replica the whole list, the CPU backend searches the
+ * sorted list per row.
+ * DEVICE (csrc/playlist.hip.h, "CANDIDATE LISTS"): no new kernel and no second instantiation: a uniform branch of
+ * playlist_scan_kernel in place of the anchor bound and the tile scan.  A thread takes two consecutive entries and requests their
+ * rows together (kPlGatherPerThread: a tuning constant of the kernel, no part of this interface); the launch has one workgroup of 512
+ * threads per 1024 rows, up to the handle's grid.  The replica
+ * is never consulted: every listed row that passes the row set and the label test takes the exact chain and counts into
+ * mi355rec_playlist_counters' rows_exact.  A request without a list takes the path it took before.
+ * mi355rec_candidates_counters: requests = requests that took the gather launch (an empty shard list launches nothing and is not
+ * counted); rows_gathered = the distinct in-shard list entries those launches were given.  Either pointer may be NULL.
+ * Measured on one MI355X at 10 M uniform rows, top-100, replica on, K = 1 by row (tools/run_candidates.py,
+ * profiles/r19_candidates.json; p50 per call), the list ascending: 38.2 us at 100 ids, 42.3 at 1 000, 66.5 at 10 000, 139.4 at 100
+ * 000, 796 at 1 000 000, beside 68.3 / 71.7 / 77.0 / 84.6 / 106.7 us with a pre-made ONLY set of the same ids, 299 ... 1 498 us with
+ * an ONLY set made per request and 92.0 us without list or set; a shuffled list adds the host's sort: 3 us at 1 000 ids, 316 us at
+ * 10 000, 4.1 ms at 100 000, 48 ms at 1 000 000.  The gather stops winning over the pre-made ONLY set between 10 000 and 100 000 ids
+ * for an ascending list and between 1 000 and 10 000 for a shuffled one (K = 10 and the distance request alike).
+ * MI355REC_MAX_CANDIDATES bounds the staging buffer; it is no routing threshold.  A thread takes two entries, not four, because the
+ * kernel sits on its register budget: 4 entries per thread need scratch (docs/LAB_NOTES.md).  Requests without a list are within the
+ * parent build's own spread (profiles/r19_candidates_ab.json).
+ * Not served: routing a small ONLY row set to the gather by itself; lists on the single-query, streamed, batched and label-only
+ * routes; a pre-filter for the gather (every listed row takes the exact chain); scores of candidates outside the top-N. */
+#define MI355REC_MAX_CANDIDATES 1048576
+int mi355rec_query_playlist_request_candidates(mi355rec_t* h, const mi355rec_playlist_query_t* query, const mi355rec_request_ext_t* ext,
+                                               const int64_t* candidates, int64_t n_candidates, const mi355rec_playlist_result_t* result);
+int mi355rec_query_distance_request_candidates(mi355rec_t* h, const mi355rec_distance_query_t* query, const mi355rec_request_ext_t* ext,
+                                               const int64_t* candidates, int64_t n_candidates, const mi355rec_distance_result_t* result);
+int mi355rec_sharded_query_playlist_request_candidates(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
+                                                       const mi355rec_request_ext_t* ext, const int64_t* candidates, int64_t n_candidates,
+                                                       const mi355rec_playlist_result_t* result);
+int mi355rec_sharded_query_distance_request_candidates(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
+                                                       const mi355rec_request_ext_t* ext, const int64_t* candidates, int64_t n_candidates,
+                                                       const mi355rec_distance_result_t* result);
+int mi355rec_candidates_counters(const mi355rec_t* h, int64_t* requests, int64_t* rows_gathered);
 
 /* ROW UPDATES (the reference lists "Real-time Updates: Incremental index updates" among its extensions): songs are re-analysed
  * and corrected every day, and a changed row should not cost a rebuild of everything the handle keeps beside the rows.

@@ -146,7 +146,7 @@ def check_no_scratch(lib: Path = LIB_ENGINE, tolerate=()) -> int:
 CPU_BACKEND_SRC = CSRC / "cpu_backend.cpp"
 CPU_BACKEND_OBJ = PKG / "cpu_backend.o"
 CPU_BACKEND_DEPS = [CPU_BACKEND_SRC, CSRC / "cpu_backend.h", CSRC / "filter_check.h", CSRC / "weights_check.h",
-                    CSRC / "playlist_request.h", CSRC / "rowset.h", CSRC / "rows_update.h"]
+                    CSRC / "playlist_request.h", CSRC / "rowset.h", CSRC / "rows_update.h", CSRC / "candidates.h"]
 # The CPU backend (hosts without a HIP device) is plain C++ + OpenMP, compiled by g++ with the reference's own fp
 # behaviour (Makefile:9: -O3, no -march, no -ffast-math; -ffp-contract=off keeps multiply and add apart) and
 # linked into the engine library.

@@ -79,6 +79,7 @@ class DistanceResult(ctypes.Structure):
 
 
 ROWSET_EXCLUDE, ROWSET_ONLY = 0, 1   # MI355REC_ROWSET_* (ROW SETS)
+MAX_CANDIDATES = 1 << 20             # MI355REC_MAX_CANDIDATES (CANDIDATE LISTS)
 
 
 class RequestExt(ctypes.Structure):
@@ -284,6 +285,16 @@ SIGNATURES = {
     "mi355rec_query_distance_request_ext": (c_int, [c_void_p, POINTER(DistanceQuery), POINTER(RequestExt), POINTER(DistanceResult)]),
     "mi355rec_sharded_query_playlist_request_ext": (c_int, [c_void_p, POINTER(PlaylistQuery), POINTER(RequestExt), POINTER(PlaylistResult)]),
     "mi355rec_sharded_query_distance_request_ext": (c_int, [c_void_p, POINTER(DistanceQuery), POINTER(RequestExt), POINTER(DistanceResult)]),
+    # CANDIDATE LISTS: the _ext requests with a list of global ids (c_void_p, c_int64): only the listed rows are gathered and ranked
+    "mi355rec_query_playlist_request_candidates": (c_int, [c_void_p, POINTER(PlaylistQuery), POINTER(RequestExt), c_void_p, c_int64,
+                                                           POINTER(PlaylistResult)]),
+    "mi355rec_query_distance_request_candidates": (c_int, [c_void_p, POINTER(DistanceQuery), POINTER(RequestExt), c_void_p, c_int64,
+                                                           POINTER(DistanceResult)]),
+    "mi355rec_sharded_query_playlist_request_candidates": (c_int, [c_void_p, POINTER(PlaylistQuery), POINTER(RequestExt), c_void_p, c_int64,
+                                                                   POINTER(PlaylistResult)]),
+    "mi355rec_sharded_query_distance_request_candidates": (c_int, [c_void_p, POINTER(DistanceQuery), POINTER(RequestExt), c_void_p, c_int64,
+                                                                   POINTER(DistanceResult)]),
+    "mi355rec_candidates_counters": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),
     # ROW UPDATES: rows change in place, every route answers as a freshly created handle would
     "mi355rec_update_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "mi355rec_sharded_update_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

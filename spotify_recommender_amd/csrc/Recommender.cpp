@@ -43,6 +43,9 @@ struct Recommender::Impl {
     // setRowSet: the engine's set (null: none) and its mode.  It belongs to `engine`: dropRowSet before the engine goes.
     mi355rec_rowset_t* rowSet = nullptr;
     bool rowSetOnly = false;
+    // setCandidates: the candidate list of the requests (hasCandidates: an empty list is a list).
+    std::vector<int64_t> candidates;
+    bool hasCandidates = false;
     void dropRowSet() {
         mi355rec_rowset_destroy(rowSet);
         rowSet = nullptr;
@@ -135,6 +138,8 @@ namespace {
 
 bool startEngine(Recommender::Impl* impl, const float* matrix, size_t n) {
     impl->dropRowSet();   // (a set is the engine's that made it: after a re-initialisation the class holds none)
+    impl->candidates.clear();   // (... and no candidate list: its ids were songs of the catalogue before)
+    impl->hasCandidates = false;
     if (impl->engine) {
         mi355rec_sharded_destroy(impl->engine);
         impl->engine = nullptr;
@@ -294,6 +299,30 @@ bool Recommender::setRowSet(const std::vector<int>& songIndices, bool only) {
 }
 
 void Recommender::clearRowSet() { impl_->dropRowSet(); }
+
+bool Recommender::setCandidates(const std::vector<int64_t>& songIndices) {
+    if (!impl_->initialized) {
+        std::cerr << "Error: Recommender not initialized" << std::endl;
+        return false;
+    }
+    if (songIndices.size() > static_cast<size_t>(MI355REC_MAX_CANDIDATES)) {
+        std::cerr << "Error: " << songIndices.size() << " candidates: at most " << MI355REC_MAX_CANDIDATES << " are taken" << std::endl;
+        return false;
+    }
+    for (int64_t id : songIndices)
+        if (id < 0 || id >= impl_->numSongs) {
+            std::cerr << "Error: candidate list: id " << id << " out of [0, " << impl_->numSongs << ")" << std::endl;
+            return false;
+        }
+    impl_->candidates = songIndices;
+    impl_->hasCandidates = true;
+    return true;
+}
+
+void Recommender::clearCandidates() {
+    impl_->candidates.clear();
+    impl_->hasCandidates = false;
+}
 
 namespace {
 // The per-request extras of a call (FEATURE SCALES, ROW SETS): the scales (null: none) and the row set of setRowSet (none: a null
@@ -488,7 +517,9 @@ std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, 
         res.out_idx = impl->idxBuf.data();
         res.out_distance = impl->scoreBuf.data();
         res.out_count = &count;
-        rc = mi355rec_sharded_query_distance_request_ext(impl->engine, &d, &ext, &res);
+        rc = impl->hasCandidates ? mi355rec_sharded_query_distance_request_candidates(impl->engine, &d, &ext, impl->candidates.data(),
+                                                                                     static_cast<int64_t>(impl->candidates.size()), &res)
+                                 : mi355rec_sharded_query_distance_request_ext(impl->engine, &d, &ext, &res);
     } else {
         mi355rec_playlist_query_t p{};
         shared(p);
@@ -504,7 +535,9 @@ std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, 
         res.out_idx = impl->idxBuf.data();
         res.out_score = impl->scoreBuf.data();
         res.out_count = &count;
-        rc = mi355rec_sharded_query_playlist_request_ext(impl->engine, &p, &ext, &res);
+        rc = impl->hasCandidates ? mi355rec_sharded_query_playlist_request_candidates(impl->engine, &p, &ext, impl->candidates.data(),
+                                                                                     static_cast<int64_t>(impl->candidates.size()), &res)
+                                 : mi355rec_sharded_query_playlist_request_ext(impl->engine, &p, &ext, &res);
     }
     if (rc != MI355REC_OK) {
         std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;

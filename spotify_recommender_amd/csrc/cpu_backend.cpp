@@ -232,6 +232,7 @@ int topn_impl(const Catalogue* c, const float* q12, int64_t exclude, int topn, i
 // ---- the handle: synchronous calls + the ticketed stream ----------------------------------------------------------
 #include <chrono>
 
+#include "candidates.h"
 #include "mi355rec_diag.h"
 #include "rowset.h"
 
@@ -517,6 +518,22 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
         for (int64_t i = 0; i < n; ++i) {
             uint64_t& key = keys[static_cast<size_t>(i)];
             if (key != 0 && !mi355rowset::admits(r.rowset, r.rowset_only, i)) key = 0;
+            avail += key != 0;
+        }
+    }
+    if (r.listed) {   // "CANDIDATE LISTS": ... and the rows that are not listed (candidates.h: the sorted list, searched per row)
+        std::vector<uint32_t> listed;
+        try {
+            listed.resize(static_cast<size_t>(r.n_candidates > 0 ? r.n_candidates : 1));
+        } catch (const std::bad_alloc&) {
+            *why = "out of host memory";
+            return MI355REC_ERR_OUT_OF_MEMORY;
+        }
+        const int64_t n_listed = mi355cand::reduce(r.candidates, r.n_candidates, 0, n, listed.data()).count;
+        avail = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            uint64_t& key = keys[static_cast<size_t>(i)];
+            if (key != 0 && !mi355cand::contains(listed.data(), n_listed, i)) key = 0;
             avail += key != 0;
         }
     }

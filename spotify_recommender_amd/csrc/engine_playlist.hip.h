@@ -9,6 +9,7 @@
 
 #include <algorithm>
 
+#include "candidates.h"
 #include "engine_labels.hip.h"
 #include "engine_rowset.hip.h"
 #include "playlist.hip.h"
@@ -34,6 +35,13 @@ struct mi355rec_playlist {
     // THIS handle, not to RowSide: a lane builds and holds its own, so no lane ever builds under another lane's launch.
     float* d_norms = nullptr;
     bool norms_built = false;               // the build has been enqueued on the handle's stream: only then may a scan read d_norms
+    // CANDIDATE LISTS (playlist.hip.h, "CANDIDATE LISTS"): a request's listed rows of this shard, reduced on the host (candidates.h)
+    // into the pinned h_cand and copied to d_cand on the handle's stream ahead of the launch.  Both hold cand_cap entries and grow on
+    // demand, before the call is begun.
+    uint32_t* h_cand = nullptr;
+    uint32_t* d_cand = nullptr;
+    int64_t cand_cap = 0;
+    int64_t cand_requests = 0, cand_rows = 0;   // mi355rec_candidates_counters
 };
 
 namespace {
@@ -74,6 +82,8 @@ void free_playlist(mi355rec_playlist* P) {
     if (P->d_rows) (void)hipFree(P->d_rows);
     if (P->d_pool_groups) (void)hipFree(P->d_pool_groups);
     if (P->d_norms) (void)hipFree(P->d_norms);
+    if (P->h_cand) (void)hipHostFree(P->h_cand);
+    if (P->d_cand) (void)hipFree(P->d_cand);
     delete P;
 }
 
@@ -100,6 +110,29 @@ int ensure_playlist(mi355rec* h) {
     if (P->grid_cap < 1) P->grid_cap = 1;
     h->playlist = P;
     return MI355REC_OK;
+}
+
+// CANDIDATE LISTS: room for `want` list entries in h_cand and d_cand (the previous call on this handle has completed: nothing reads
+// the old buffers).  A failure leaves the handle without them; the next request allocates again.
+int ensure_candidates(mi355rec* h, mi355rec_playlist* P, int64_t want) {
+    if (want <= P->cand_cap) return MI355REC_OK;
+    int64_t cap = P->cand_cap > 0 ? P->cand_cap : 4096;
+    while (cap < want) cap *= 2;
+    if (P->h_cand) (void)hipHostFree(P->h_cand);
+    if (P->d_cand) (void)hipFree(P->d_cand);
+    P->h_cand = P->d_cand = nullptr;
+    P->cand_cap = 0;
+    hipError_t e = hipHostMalloc(&P->h_cand, sizeof(uint32_t) * static_cast<size_t>(cap), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc(&P->d_cand, sizeof(uint32_t) * static_cast<size_t>(cap));
+    if (e == hipSuccess) {
+        P->cand_cap = cap;
+        return MI355REC_OK;
+    }
+    if (P->h_cand) (void)hipHostFree(P->h_cand);
+    P->h_cand = P->d_cand = nullptr;
+    (void)hipGetLastError();
+    return fail(h, e == hipErrorOutOfMemory ? MI355REC_ERR_OUT_OF_MEMORY : MI355REC_ERR_HIP, "the candidate list (%lld ids): %s", (long long)want,
+                hipGetErrorString(e));
 }
 
 // One call of the playlist family (playlist_request.h), synchronously.  r.members: k x 12 floats on the host, or null with
@@ -158,6 +191,24 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
         if (admitted < avail) avail = admitted;
         if (admitted < h->n) set_bits = part->d_bits;
     }
+    // the candidate list ("CANDIDATE LISTS"): this shard's listed rows, sorted and distinct, into the pinned buffer; at most they
+    // are left.  The launch below then gathers them and reads nothing else of the catalogue.
+    int64_t n_cand = 0;
+    if (r.listed) {
+        if (r.n_candidates > 0) {
+            rc = ensure_candidates(h, P, r.n_candidates);
+            if (rc) return rc;
+            // (one pass over the ids: the range check of a list that comes unchecked, the shard's rows, the ascending test)
+            const mi355cand::Reduced red =
+                mi355cand::reduce(r.candidates, r.n_candidates, h->row_base, h->row_base + h->n, P->h_cand, r.candidates_id_end);
+            if (red.bad >= 0) {
+                mi355cand::bad_id_message(r.candidates[red.bad], r.candidates_id_end, why, sizeof why);
+                return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+            }
+            n_cand = red.count;
+        }
+        if (n_cand < avail) avail = n_cand;
+    }
     // the prior ("ROW PRIORS"): checked whenever the request carries one; beta == 0 then launches exactly the call without it
     const float* pri = nullptr;
     if (r.prior) {
@@ -180,6 +231,8 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     arg.metric = r.metric == mi355playlist::kDistance ? kPlDistance : kPlCosine;
     arg.rowset = set_bits;
     arg.rowset_flip = set_bits && !r.rowset_only ? 0xfu : 0u;   // EXCLUDE: a set bit clears the row; ONLY: a clear bit does
+    arg.cand = r.listed ? P->d_cand : nullptr;   // (eff > 0: the list has an entry)
+    arg.n_cand = n_cand;
     arg.scaled = r.scales ? 1 : 0;   // "FEATURE SCALES" (every scale 1.0f has become null scales: the unscaled launch)
     for (int j = 0; j < kDim; ++j) b->scales[j] = r.scales ? r.scales[j] : 1.0f;
     for (int m = 0; m < k; ++m) b->weights[m] = r.weights ? r.weights[m] : 1.0f;
@@ -191,7 +244,8 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     else std::memcpy(b->members, r.members, sizeof(float) * kDim * static_cast<size_t>(k));
     // "DISTANCE REQUESTS": the rows' norms, once per handle (and per rebuild).  Allocated before the call is begun: a failure
     // here leaves nothing begun and nothing staged.
-    const uint4* q8 = use_q8(h) ? h->d_q8 : nullptr;
+    // (a candidate list gathers: no replica, no anchors, no norms, so the cut is off and every listed row takes the exact chain)
+    const uint4* q8 = !r.listed && use_q8(h) ? h->d_q8 : nullptr;
     const int64_t n_quads4 = (h->n + 3) / 4 * 4;
     // (a scaled distance request takes the exact path: the norms are those of the unscaled rows, it is launched with null norms)
     const bool scan_norms = q8 && arg.metric == kPlDistance && !arg.scaled;
@@ -219,14 +273,20 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
         HIP_TRY(h, hipGetLastError());
         P->norms_built = true;   // (only now: every exit above leaves an array that the next request builds)
     }
+    if (r.listed) {   // (on the handle's stream, ahead of the launch that reads them)
+        HIP_TRY(h, hipMemcpyAsync(P->d_cand, P->h_cand, sizeof(uint32_t) * static_cast<size_t>(n_cand), hipMemcpyHostToDevice, h->stream));
+        ++P->cand_requests;
+        P->cand_rows += n_cand;
+    }
     const int64_t tiles = ((h->n + 3) / 4 + PlaylistCfg::kBlock - 1) / PlaylistCfg::kBlock;
     int64_t want_grid = q8 ? (tiles + kPlMinTilesPerWg - 1) / kPlMinTilesPerWg : tiles;
+    if (r.listed) want_grid = (n_cand + PlaylistCfg::kBlock * kPlGatherPerThread - 1) / (PlaylistCfg::kBlock * kPlGatherPerThread);
     if (want_grid > P->grid_cap) want_grid = P->grid_cap;
     if (want_grid < 1) want_grid = 1;
     const int grid = static_cast<int>(want_grid);
     LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, playlist_scan_kernel, dim3(grid), dim3(PlaylistCfg::kBlock),
                  h->stream, h->d_feats, q8, h->n, h->row_base, static_cast<const PlaylistBuf*>(P->d_buf), arg,
-                 static_cast<const float*>(h->d_anchor), eff, h->d_block_lists, P->d_exact,
+                 static_cast<const float*>(r.listed ? nullptr : h->d_anchor), eff, h->d_block_lists, P->d_exact,
                  reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr)),
                  reinterpret_cast<const uint2*>(L ? L->d_row_labels : nullptr), reinterpret_cast<const float4*>(pri),
                  reinterpret_cast<const float4*>(scan_norms ? P->d_norms : nullptr));
@@ -336,6 +396,25 @@ int mi355rec_query_playlist_request_ext(mi355rec_t* h, const mi355rec_playlist_q
     return sync_playlist_query(h, r, out);
 }
 
+// "CANDIDATE LISTS": the same request with its list; every check of the _ext call first, then the list's own (candidates.h).
+int mi355rec_query_playlist_request_candidates(mi355rec_t* h, const mi355rec_playlist_query_t* query, const mi355rec_request_ext_t* ext,
+                                               const int64_t* candidates, int64_t n_candidates, const mi355rec_playlist_result_t* result) {
+    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    mi355rec_playlist_query_t full;
+    Request r;
+    Outputs out;
+    char why[160];
+    if (mi355playlist::from_query_ext(query, ext, result, &full, &r, &out, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    if (r.rowset && r.rowset->node) return fail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
+    if (mi355cand::invalid_count(candidates, n_candidates, MI355REC_MAX_CANDIDATES, why, sizeof why))
+        return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    r.candidates_id_end = kRowsetIdEnd;   // (the ids are checked in playlist_launch's one pass over them)
+    r.listed = true;
+    r.candidates = candidates;
+    r.n_candidates = n_candidates;
+    return sync_playlist_query(h, r, out);
+}
+
 int mi355rec_query_playlist_request_scaled(mi355rec_t* h, const mi355rec_playlist_query_t* query, const float* feature_scales,
                                            const mi355rec_playlist_result_t* result) {
     const mi355rec_request_ext_t ext = mi355playlist::scales_only_ext(feature_scales);
@@ -357,6 +436,25 @@ int mi355rec_query_distance_request_ext(mi355rec_t* h, const mi355rec_distance_q
     if (mi355playlist::from_distance_query_ext(query, ext, result, &full, &r, &out, why, sizeof why))
         return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
     if (r.rowset && r.rowset->node) return fail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
+    return sync_playlist_query(h, r, out);
+}
+
+int mi355rec_query_distance_request_candidates(mi355rec_t* h, const mi355rec_distance_query_t* query, const mi355rec_request_ext_t* ext,
+                                               const int64_t* candidates, int64_t n_candidates, const mi355rec_distance_result_t* result) {
+    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    mi355rec_distance_query_t full;
+    Request r;
+    Outputs out;
+    char why[160];
+    if (mi355playlist::from_distance_query_ext(query, ext, result, &full, &r, &out, why, sizeof why))
+        return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    if (r.rowset && r.rowset->node) return fail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
+    if (mi355cand::invalid_count(candidates, n_candidates, MI355REC_MAX_CANDIDATES, why, sizeof why))
+        return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    r.candidates_id_end = kRowsetIdEnd;   // (the ids are checked in playlist_launch's one pass over them)
+    r.listed = true;
+    r.candidates = candidates;
+    r.n_candidates = n_candidates;
     return sync_playlist_query(h, r, out);
 }
 
@@ -399,6 +497,14 @@ int mi355rec_playlist_counters(const mi355rec_t* h, int64_t* queries, int64_t* r
         }
         *rows_exact = static_cast<int64_t>(v);
     }
+    return MI355REC_OK;
+}
+
+// "CANDIDATE LISTS": requests that took the gather launch, and the distinct in-shard list entries those launches were given.
+int mi355rec_candidates_counters(const mi355rec_t* h, int64_t* requests, int64_t* rows_gathered) {
+    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    if (requests) *requests = h->playlist ? h->playlist->cand_requests : 0;
+    if (rows_gathered) *rows_gathered = h->playlist ? h->playlist->cand_rows : 0;
     return MI355REC_OK;
 }
 

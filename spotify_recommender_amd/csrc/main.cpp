@@ -23,6 +23,8 @@
 //       of the most similar by cosine (extension; with --genre and --where; distances are printed)
 //   ... --song, --id and --playlist with one or more --scale NAME=S: feature NAME counts S times (0: ignored) in the similarity or
 //       the distance (extension; under both metrics, with --genre and --where)
+//   ... the same modes with --candidates FILE (track ids, one per line, as for --only): only the listed songs are READ and ranked (a
+//       candidate list: the engine gathers them and makes no pass over the catalogue); goes with --seen or --only; extension
 //   ... --song, --id and --playlist with --seen FILE or --only FILE (track ids, one per line): the listed songs are never recommended
 //       (--seen: a listening history of any length) or only the listed songs are ranked (--only: a candidate set); extension, beside
 //       every other option of those modes; --song / --id then run as the one-song playlist (not with --genre there)
@@ -272,6 +274,29 @@ static bool parseRowSet(int argc, char* argv[], int first, RowSetOpt& rs) {
     return true;
 }
 
+// --candidates FILE from argv[first] (candidate lists): the format of --only FILE; goes with --seen or --only.
+struct CandidatesOpt {
+    bool on = false;
+    std::string file;
+};
+
+static bool parseCandidates(int argc, char* argv[], int first, CandidatesOpt& c) {
+    for (int i = first; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--candidates") != 0) continue;
+        if (i + 1 >= argc) {
+            std::cerr << "Error: --candidates needs a file of track ids (one per line)" << std::endl;
+            return false;
+        }
+        if (c.on) {
+            std::cerr << "Error: --candidates is given once (a request takes one candidate list)" << std::endl;
+            return false;
+        }
+        c.on = true;
+        c.file = argv[++i];
+    }
+    return true;
+}
+
 // The reference loads every Song, deep-copies the vector into the recommender and
 // flattens it again (main.cpp:50-60, Recommender.cu:109,162-167).  Here the file is
 // walked once (DataManager::loadCatalogue): the feature matrix goes to the engine as
@@ -297,20 +322,18 @@ static int findQuery(const DataManager::Catalogue& catalogue, const std::string&
     return index;
 }
 
-// --seen / --only: the file's track ids (one per line, blank lines skipped, the first row of an id as for --id) to the recommender
-// as its row set.  A line that names no song of the catalogue is skipped; how many were is said on stderr (a history normally
-// holds tracks the catalogue lacks).  false, with a message, when the file cannot be read or the set is refused.
-static bool applyRowSet(Recommender& recommender, const DataManager::Catalogue& catalogue, const RowSetOpt& rs) {
-    if (!rs.on) return true;
-    std::ifstream in(rs.file);
+// The rows of the track ids in `file` (one per line, blank lines skipped, the first row of an id as for --id) appended to `rows`; a line
+// that names no song of the catalogue is counted in `skipped`.  false, with a message that calls the file `what`, when it cannot be opened.
+static bool readTrackIdFile(const DataManager::Catalogue& catalogue, const std::string& file, const char* what, std::vector<int>& rows,
+                            size_t& skipped) {
+    std::ifstream in(file);
     if (!in) {
-        std::cerr << "Error: cannot open the row set file '" << rs.file << "'" << std::endl;
+        std::cerr << "Error: cannot open the " << what << " file '" << file << "'" << std::endl;
         return false;
     }
     std::unordered_map<std::string, int> byId;
     for (size_t i = 0; i < catalogue.size(); ++i) byId.emplace(catalogue.trackIds[i], static_cast<int>(i));   // (the first row of an id)
-    std::vector<int> rows;
-    size_t skipped = 0;
+    skipped = 0;
     std::string line;
     while (std::getline(in, line)) {
         const size_t a = line.find_first_not_of(" \t\r");
@@ -319,10 +342,35 @@ static bool applyRowSet(Recommender& recommender, const DataManager::Catalogue& 
         if (hit == byId.end()) ++skipped;
         else rows.push_back(hit->second);
     }
+    return true;
+}
+
+// --seen / --only: the file's track ids (one per line, blank lines skipped, the first row of an id as for --id) to the recommender
+// as its row set.  A line that names no song of the catalogue is skipped; how many were is said on stderr (a history normally
+// holds tracks the catalogue lacks).  false, with a message, when the file cannot be read or the set is refused.
+static bool applyRowSet(Recommender& recommender, const DataManager::Catalogue& catalogue, const RowSetOpt& rs) {
+    if (!rs.on) return true;
+    std::vector<int> rows;
+    size_t skipped = 0;
+    if (!readTrackIdFile(catalogue, rs.file, "row set", rows, skipped)) return false;
     std::cerr << "Row set (" << (rs.only ? "--only" : "--seen") << " " << rs.file << "): " << rows.size() << " tracks, " << skipped
               << " lines skipped (not in the catalogue)" << std::endl;
     if (!recommender.setRowSet(rows, rs.only)) return false;
     std::cout << (rs.only ? "Only among " : "Leaving out ") << rows.size() << " listed songs" << std::endl;
+    return true;
+}
+
+// --candidates: the file's track ids (the rules of --only FILE) to the recommender as its candidate list: only they are read and
+// ranked.  false, with a message, when the file cannot be read or the list is refused.
+static bool applyCandidates(Recommender& recommender, const DataManager::Catalogue& catalogue, const CandidatesOpt& c) {
+    if (!c.on) return true;
+    std::vector<int> rows;
+    size_t skipped = 0;
+    if (!readTrackIdFile(catalogue, c.file, "candidate list", rows, skipped)) return false;
+    std::cerr << "Candidate list (--candidates " << c.file << "): " << rows.size() << " tracks, " << skipped
+              << " lines skipped (not in the catalogue)" << std::endl;
+    if (!recommender.setCandidates(std::vector<int64_t>(rows.begin(), rows.end()))) return false;
+    std::cout << "Ranking " << rows.size() << " listed candidates" << std::endl;
     return true;
 }
 
@@ -533,6 +581,7 @@ struct Options {
     std::vector<std::string> genres;
     std::vector<Recommender::FeatureRange> ranges;
     RowSetOpt rowSet;
+    CandidatesOpt candidates;
     bool euclidean = false;
     std::vector<float> scales;
     Taste taste;
@@ -563,7 +612,7 @@ static const Refusal kRefusals[] = {
     {Given::Euclidean, kRequestOptions, "--metric euclidean cannot be combined with %s (distance requests take --genre and --where only)"},
     {Given::Scale, kRequestOptions, "--scale cannot be combined with %s (scaled requests take --metric, --genre and --where only)"},
     {Given::GenreFiltered, {"--where"}, "%s cannot be combined with --genre"},
-    {Given::GenreFiltered, {"--seen", "--only"}, "%s cannot be combined with --genre here: use --playlist <one id> --genre ..."},
+    {Given::GenreFiltered, {"--seen", "--only", "--candidates"}, "%s cannot be combined with --genre here: use --playlist <one id> --genre ..."},
     {Given::GenreReranked, {"--max-per-artist"}, "%s cannot be combined with --genre"},
     {Given::GenreReranked, {"--diverse"}, "%s cannot be combined with --genre"},
 };
@@ -595,6 +644,7 @@ static bool parseOptions(int argc, char* argv[], Options& o) {
     if (!parseTopN(argc, argv, first, o.topN)) return false;
     if (!o.playlist && !parseGenres(argc, argv, first, o.genres)) return false;
     if (!parseWhere(argc, argv, first, o.ranges) || !parseRowSet(argc, argv, first, o.rowSet)) return false;
+    if (!parseCandidates(argc, argv, first, o.candidates)) return false;
     if (!parseMetric(argc, argv, first, o.euclidean) || refused(argc, argv, first, o, Given::Euclidean)) return false;
     if (!parseScale(argc, argv, first, o.scales) || refused(argc, argv, first, o, Given::Scale)) return false;
     printScales(o.scales);
@@ -724,11 +774,11 @@ static bool queryMode(const Options& o) {
         std::cerr << "Failed to initialize recommender" << std::endl;
         return false;
     }
-    if (!applyRowSet(recommender, catalogue, o.rowSet)) return false;
+    if (!applyRowSet(recommender, catalogue, o.rowSet) || !applyCandidates(recommender, catalogue, o.candidates)) return false;
 
     // (2. for the song flavour.)  Without an extension option it is the reference's own route: recommend / recommendByName look
     // the song up themselves; with --genre alone its label-scan form.  Everything else is one Recommender::Query.
-    const bool reference = song && !o.dv.on && o.ranges.empty() && !o.rowSet.on;
+    const bool reference = song && !o.dv.on && o.ranges.empty() && !o.rowSet.on && !o.candidates.on;
     if (song) {
         std::cout << "\nSearching for " << (o.isTrackId ? "track ID: " : "song: ") << o.query << std::endl;
         if (!genreIdsOf(catalogue, o.genres, genreIds)) return false;

@@ -130,6 +130,22 @@
 // replica still only rules rows out by similarity, among the rows the set has left.  rowset == null takes none of these branches
 // (uniform tests) and reads nothing new.
 //
+// CANDIDATE LISTS (include/mi355rec_diag.h, "CANDIDATE LISTS").  PlaylistArg::cand (uniform; null: no list): this shard's listed
+// rows, local, strictly ascending, as uint32 (candidates.h, engine_playlist.hip.h).  The kernel then GATHERS: playlist_gather_rows
+// takes the place of playlist_anchor_bound + playlist_scan_tiles, the prologue before it and the tail after it are shared.  The
+// host launches it with a null replica, null anchors and null norms: the cut is off, the threshold starts at 0 and every listed
+// row takes the exact chain, so the keys are those of the exact path by construction (playlist_row_key).
+//   * workgroup b takes the entries [(b + j gridDim.x) kBlock kPlGatherPerThread, + kBlock kPlGatherPerThread), j = 0, 1, ...; a
+//     thread takes kPlGatherPerThread consecutive entries and requests their fp32 rows TOGETHER (one memory round trip after the
+//     one for the entries, as the filter path requests a quad's four rows); an entry past n_cand re-reads the last one, masked;
+//   * per entry, in the scan's order: the row-set bit, the label (by row: the list knows nothing of quads), the filter on the
+//     stored row, then playlist_row_key, playlist_excluded and the ballot append.  rows_exact counts every entry that reaches the
+//     filter or the chains;
+//   * per iteration the scan's two barriers, compact_candidates at compact_at and the shared_thr exchange: an iteration appends at
+//     most kBlock kPlGatherPerThread <= PlaylistCfg::kTileRows keys, a tile's worth, so the candidate slots cannot overflow.
+// The rows ascend, so neighbouring lanes share cache lines where the list is dense.  cand == null takes none of this (one uniform
+// test in the kernel body) and the scan's loop is untouched.
+//
 // EXCLUSION.  The excluded global ids (members and the caller's list, sorted and deduplicated on the host, at most
 // kPlExcludeCap) sit in LDS as uint32; only a key that already beats the workgroup's threshold is looked up (binary
 // search), so the hot loop does not change.
@@ -180,6 +196,8 @@ struct PlaylistArg {
     int scaled;       // 1: rows and members are multiplied by PlaylistBuf::scales before the chains (FEATURE SCALES above); 0: never read
     const uint8_t* rowset;   // ROW SETS above: the shard's bitmap, bit i of byte i / 8 is local row i (padding bits 0); null: no set
     uint32_t rowset_flip;    // ... 0xf: rows IN the set are not admissible (EXCLUDE); 0: rows NOT in it are not (ONLY)
+    const uint32_t* cand;    // CANDIDATE LISTS above: n_cand > 0 local rows, strictly ascending: only they are read; null: no list
+    int64_t n_cand;
 };
 
 // Is label l (int16 of the row-order array: -1 = unlabelled or padding) in the set?
@@ -562,6 +580,78 @@ __device__ __forceinline__ void playlist_scan_tiles(const PlaylistCtx& c, const 
     }
 }
 
+// ---- CANDIDATE LISTS: the gather, playlist_scan_tiles' sibling: the listed rows `cand[0..n_cand)` of this workgroup, candidates
+// into sm.cand.  The threshold starts at 0; nothing of the cut is read.
+// List entries of a thread per iteration, their rows in flight together.  The kernel sits on its budget
+// of 128 VGPRs without scratch: 4 entries (48 row registers) and 3 spill, 2 fit; what is in flight per CU comes from its 1024 threads.
+constexpr int kPlGatherPerThread = 2;
+__device__ __forceinline__ void playlist_gather_rows(const PlaylistCtx& c, const PlaylistSmem& sm, const uint32_t* __restrict__ cand,
+                                                     int64_t n_cand, int& n_exact) {
+    constexpr int kBlock = PlaylistCfg::kBlock, kPer = kPlGatherPerThread;
+    static_assert(kBlock * kPer <= PlaylistCfg::kTileRows, "an iteration appends at most a tile's worth of keys (kCandCap)");
+    const int tid = c.tid, lane = c.lane;
+    const int64_t chunks = (n_cand + kBlock * kPer - 1) / (kBlock * kPer);
+    uint64_t thr = 0ull;
+    int compact_at = 2 * c.topk > 256 ? 2 * c.topk : 256;
+    if (compact_at > kCandLimit) compact_at = kCandLimit;
+
+    for (int64_t t = blockIdx.x; t < chunks; t += gridDim.x) {   // uniform
+        const int64_t e0 = (t * kBlock + tid) * kPer;
+        uint32_t row[kPer], mask = 0u;
+        Row x[kPer];
+#pragma unroll
+        for (int v = 0; v < kPer; ++v) {
+            row[v] = cand[e0 + v < n_cand ? e0 + v : n_cand - 1];
+            if (e0 + v < n_cand) mask |= 1u << v;
+        }
+#pragma unroll
+        for (int v = 0; v < kPer; ++v) x[v] = load_row(c.feats, static_cast<int64_t>(row[v]));   // requested together
+        if (c.rowset) {   // (uniform) ROW SETS
+#pragma unroll
+            for (int v = 0; v < kPer; ++v)
+                if (!rowset_admits(c.rowset, c.flip, static_cast<int64_t>(row[v]))) mask &= ~(1u << v);
+        }
+        if (c.labelled) {   // (uniform) the label, by row
+#pragma unroll
+            for (int v = 0; v < kPer; ++v)
+                if (!label_selected(sm.lmask, c.row_label[row[v]])) mask &= ~(1u << v);
+        }
+        n_exact += __builtin_popcount(mask);   // every row that reaches the filter or the chains
+        if (c.active) {   // (uniform) the filter on the stored rows
+#pragma unroll
+            for (int v = 0; v < kPer; ++v)
+                if (!filter_pass(x[v], c.active, c.buf->lo, c.buf->hi)) mask &= ~(1u << v);
+        }
+#pragma unroll
+        for (int v = 0; v < kPer; ++v) {   // (uniform) entry v of every thread (unrolled: x[v] is a register, never indexed)
+            const bool have = (mask & (1u << v)) != 0u;
+            const uint64_t row_key = playlist_row_key(c, sm, x[v], static_cast<int64_t>(row[v]));
+            const uint64_t key = have ? row_key : 0ull;
+            bool pass = key > thr;
+            if (pass && c.n_excl > 0) pass = !playlist_excluded(sm.excl, c.n_excl, static_cast<uint32_t>(c.row_base + row[v]));
+            const uint64_t ballot = __ballot(pass);
+            if (ballot) {
+                int base = 0;
+                if (lane == 0) base = atomicAdd(&sm.count, __popcll(ballot));
+                base = __builtin_amdgcn_readfirstlane(base);
+                if (pass) sm.cand[base + lanes_below(ballot)] = key;
+            }
+        }
+        // the scan's two barriers, compaction and threshold exchange
+        __syncthreads();
+        const int count = sm.count;
+        if (tid == 0) sm.shared = __hip_atomic_load(c.shared_thr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        const uint64_t published = sm.shared;
+        if (count >= compact_at) {
+            const uint64_t local_thr = compact_candidates<kBlock, PlaylistCfg::kCandPerThread>(sm.cand, &sm.count, c.topk, false, sm.sel);
+            if (local_thr > thr && local_thr > published && tid == 0) atomicMax(c.shared_thr, static_cast<unsigned long long>(local_thr));
+            if (local_thr > thr) thr = local_thr;
+        }
+        if (published > thr) thr = published;
+    }
+}
+
 // q8: the handle's 8-bit replica, or null (every row exact).  anchors: the anchor table, or null (no starting threshold).
 // rows_exact: += the rows whose K chains this launch computed; with a filter, every fp32 row read (rejected ones included).
 // labels: the shard's labels in row order, four int16 to a quad (read only where arg.labelled).
@@ -591,9 +681,15 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     PlaylistCut cut;
     const Q8Query hq = playlist_prologue(c, sm, u, un, cut);
     int n_exact = 0;   // rows whose K chains this thread computed
-    uint64_t thr = 0ull;
-    if (cut.kind != kPlCutOff) thr = playlist_anchor_bound(c, sm, u, un, n_exact);   // uniform
-    playlist_scan_tiles(c, sm, hq, cut, thr, n_exact);
+    // (uniform) CANDIDATE LISTS: only the listed rows.  Marked unlikely: a non-null pointer test counts as likely, and the register
+    // allocator then weighs the scan's loops below the gather's and moves the kernel's spilled SGPRs into them (docs/LAB_NOTES.md).
+    if (__builtin_expect(arg.cand != nullptr, 0)) {
+        playlist_gather_rows(c, sm, arg.cand, arg.n_cand, n_exact);
+    } else {
+        uint64_t thr = 0ull;
+        if (cut.kind != kPlCutOff) thr = playlist_anchor_bound(c, sm, u, un, n_exact);   // uniform
+        playlist_scan_tiles(c, sm, hq, cut, thr, n_exact);
+    }
 
     const int wave_exact = wave_inclusive_scan(n_exact);
     if (c.lane == 63 && wave_exact) atomicAdd(&sm.exact, wave_exact);

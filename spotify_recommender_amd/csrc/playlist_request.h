@@ -47,6 +47,11 @@ struct Request {
                                                 // ... call on rows fl(a_j x_j) with members fl(a_j q_kj); the filter tests x itself
     const mi355rec_rowset_t* rowset = nullptr;  // null, or the row set ("ROW SETS", rowset.h): with rowset_only only its rows are
     bool rowset_only = false;                   // ... admissible, without it only the others
+    bool listed = false;                        // "CANDIDATE LISTS" (candidates.h): only the n_candidates checked global ids of
+    const int64_t* candidates = nullptr;        // ... `candidates` are admissible (any order, duplicates allowed; n_candidates == 0:
+    int64_t n_candidates = 0;                   // ... no row is), beside whatever else the request asks of a row
+    int64_t candidates_id_end = -1;             // >= 0: the ids are NOT checked yet: each lies in [0, this), or the request is refused
+                                                // ... by the pass that reduces the list (the single handle's own entry points)
 
     int scan_topn() const { return diverse ? pool : topn; }   // what the scan selects
     // The same call diversified, and (of a diversified one) capped: what the _diverse and _capped entry points add.

@@ -54,6 +54,7 @@
 // A "shard" of a replicated handle is a full replica (lo = 0, hi = n).
 #include <cmath>
 
+#include "candidates.h"
 #include "node_stream.hip.h"
 
 extern "C" {
@@ -668,6 +669,27 @@ using mi355playlist::Outputs;
 using mi355playlist::Request;
 using mi355playlist::request;
 
+// CANDIDATE LISTS on a ROW-SHARDED catalogue: the request as the shard of engine `e` takes it, its list cut down to the ids of that
+// shard's range (candidates.h).  A shard with none gets an empty list: its call launches nothing, as one with nothing left to return.
+struct ShardLists {
+    std::vector<int64_t> ids;   // the list of the shard asked for last (the shards are asked one after the other)
+    Request of(const mi355rec_sharded_t* h, const Request& r, const mi355rec_t* e) {
+        if (!r.listed) return r;
+        Request mine = r;
+        for (const Shard& s : h->shards)
+            if (s.engine == e) {
+                try {
+                    mi355cand::split(r.candidates, r.n_candidates, s.lo, s.hi, &ids);
+                } catch (const std::bad_alloc&) {
+                    return r;   // (the whole list: the shard matches the ids of its own rows itself)
+                }
+                mine.candidates = ids.data();
+                mine.n_candidates = static_cast<int64_t>(ids.size());
+            }
+        return mine;
+    }
+};
+
 // The diversified call on a ROW-SHARDED catalogue (members by value, all checked): the pool from every shard's mean call merged
 // on the host, its rows gathered from their shards (one mi355rec_fetch_rows per shard that owns any) and the re-rank on the
 // first shard's device over the pool passed by value.
@@ -693,9 +715,10 @@ int diverse_over_shards(mi355rec_sharded_t* h, const Request& r, const Outputs& 
     int rc = drain_workers(h);
     if (rc) return rc;
     const Request mean = r.pool_call();
+    ShardLists lists;
     rc = merge_over_shards(h, pool, {pidx.data(), prel.data(), nullptr, &p_eff, nullptr},
                            [&](mi355rec_t* e, int64_t* idx, float* sc, int* c) {
-                               return mi355node::query_playlist(e, mean, {idx, sc, nullptr, c, nullptr});
+                               return mi355node::query_playlist(e, lists.of(h, mean, e), {idx, sc, nullptr, c, nullptr});
                            });
     if (rc) return rc;
     if (p_eff <= 0) {
@@ -786,8 +809,9 @@ int sharded_playlist(mi355rec_sharded_t* h, Request r, const Outputs& out) {
     // with -m, what the merge's keys compare; the distances are taken from the merged list)
     const bool report_distance = r.report_distance;
     r.report_distance = false;
+    ShardLists lists;
     const int merged = merge_over_shards(h, r.topn, out, [&](mi355rec_t* e, int64_t* idx, float* sc, int* c) {
-        return mi355node::query_playlist(e, r, {idx, sc, nullptr, c, nullptr});
+        return mi355node::query_playlist(e, lists.of(h, r, e), {idx, sc, nullptr, c, nullptr});
     });
     if (merged == MI355REC_OK && report_distance) mi355playlist::scores_to_distances(out, r.topn);
     return merged;
@@ -920,6 +944,42 @@ int mi355rec_sharded_query_distance_request_scaled(mi355rec_sharded_t* h, const 
 int mi355rec_sharded_query_distance_request(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
                                             const mi355rec_distance_result_t* result) {
     return mi355rec_sharded_query_distance_request_ext(h, query, nullptr, result);
+}
+
+// CANDIDATE LISTS (include/mi355rec_diag.h): the list travels in the Request; its ids are rows of the catalogue.  One handle takes it
+// whole, a row-sharded catalogue cuts it per shard (ShardLists), the CPU backend searches it.
+int mi355rec_sharded_query_playlist_request_candidates(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
+                                                       const mi355rec_request_ext_t* ext, const int64_t* candidates, int64_t n_candidates,
+                                                       const mi355rec_playlist_result_t* result) {
+    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    mi355rec_playlist_query_t full;
+    Request r;
+    Outputs out;
+    char why[160];
+    if (mi355playlist::from_query_ext(query, ext, result, &full, &r, &out, why, sizeof why) ||
+        mi355cand::invalid_list(candidates, n_candidates, MI355REC_MAX_CANDIDATES, h->n, why, sizeof why))
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    r.listed = true;
+    r.candidates = candidates;
+    r.n_candidates = n_candidates;
+    return sharded_playlist(h, r, out);
+}
+
+int mi355rec_sharded_query_distance_request_candidates(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
+                                                       const mi355rec_request_ext_t* ext, const int64_t* candidates, int64_t n_candidates,
+                                                       const mi355rec_distance_result_t* result) {
+    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    mi355rec_distance_query_t full;
+    Request r;
+    Outputs out;
+    char why[160];
+    if (mi355playlist::from_distance_query_ext(query, ext, result, &full, &r, &out, why, sizeof why) ||
+        mi355cand::invalid_list(candidates, n_candidates, MI355REC_MAX_CANDIDATES, h->n, why, sizeof why))
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    r.listed = true;
+    r.candidates = candidates;
+    r.n_candidates = n_candidates;
+    return sharded_playlist(h, r, out);
 }
 
 // ROW SETS (include/mi355rec_diag.h): the global host bitmap, and a device copy beside every engine's rows: a row-sharded placement

@@ -185,6 +185,15 @@ int shim_set_row_set(void* h, const int* songs, int n_songs, int only) {
     }
     return c->rec.setRowSet(std::vector<int>(songs, songs + n_songs), only != 0) ? 1 : 0;
 }
+// Recommender::setCandidates (n_songs < 0: clearCandidates).
+int shim_set_candidates(void* h, const int64_t* songs, int64_t n_songs) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    if (n_songs < 0) {
+        c->rec.clearCandidates();
+        return 1;
+    }
+    return c->rec.setCandidates(std::vector<int64_t>(songs, songs + n_songs)) ? 1 : 0;
+}
 // Recommender::updateSongs (n_features floats for n_songs songs: a length that differs is refused by the class).
 int shim_update_songs(void* h, const int* songs, int n_songs, const float* features, int64_t n_features) {
     Catalogue* c = static_cast<Catalogue*>(h);

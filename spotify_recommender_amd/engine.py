@@ -9,6 +9,7 @@ per-workgroup lists.  No arithmetic happens in Python.
 from __future__ import annotations
 
 import ctypes
+import types
 import weakref
 from typing import Optional, Tuple
 
@@ -91,7 +92,7 @@ _PLAYLIST_LEVELS = ("", "_where", "_weighted", "_diverse", "_capped")   # each l
 
 def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=None, where=None, weights=None, level: str = None,
                      lam=None, pool=None, max_per_group=None, return_mmr: bool = False, return_pool_rows: bool = False, labels=None,
-                     prior_weight=None, scales=None, rowset=None):
+                     prior_weight=None, scales=None, rowset=None, candidates=None):
     """Runs one entry point of the playlist family: `prefix`query_{mean|playlist}_topn`level`.  `members` is a (k, 12) float32
     array (by value: mean) or a 1-D int64 array of rows (by row: playlist).  `level` None: the lowest that takes the
     arguments given ("" plain, "_where" with a filter, "_weighted" with weights); "_diverse" and "_capped" are asked for.
@@ -114,7 +115,10 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
     FEATURE SCALES: `scales` (make_scales) weighs or ignores features; the call goes through `prefix`query_playlist_request_scaled,
     which refuses diversified and capped calls and priors.  None takes the entry point used today.
     ROW SETS: `rowset` = (the set's pointer, capi.ROWSET_EXCLUDE or capi.ROWSET_ONLY); the call goes through
-    `prefix`query_playlist_request_ext.  None takes the entry point used today."""
+    `prefix`query_playlist_request_ext.  None takes the entry point used today.
+    CANDIDATE LISTS: `candidates`, a sequence of global ids (any order, duplicates fine; empty: nothing is returned): only the
+    listed rows are gathered and ranked, through `prefix`query_playlist_request_candidates, with whatever else is asked (a
+    `rowset` too: both must admit a row).  None takes the entry point used today."""
     if prior_weight is not None and (isinstance(prior_weight, bool) or not isinstance(prior_weight, (int, float, np.integer, np.floating))):
         raise ValueError(f"prior_weight must be a number or None, got {prior_weight!r}")
     if level is None:
@@ -165,7 +169,7 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
         args.append(ctypes.byref(pool_rows))
     by = "playlist" if members.dtype == np.int64 else "mean"
     a = make_scales(scales) if scales is not None else None
-    if labels is not None or prior_weight is not None or a is not None or rowset is not None:
+    if labels is not None or prior_weight is not None or a is not None or rowset is not None or candidates is not None:
         q = capi.PlaylistQuery()
         q.size = ctypes.sizeof(capi.PlaylistQuery)
         q.flags = (capi.PQ_DIVERSE if diverse else 0) | (capi.PQ_CAPPED if capped else 0)
@@ -186,8 +190,13 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
             q.max_per_group = int(max_per_group)
         res = capi.PlaylistResult(ptr(idx), ptr(score), ptr(mmr) if diverse else None, ctypes.pointer(count),
                                   ctypes.pointer(pool_rows))
-        if rowset is not None:
-            ext = capi.RequestExt(ctypes.sizeof(capi.RequestExt), int(rowset[1]), ptr(a) if a is not None else None, rowset[0])
+        if candidates is not None:
+            cand = _np_ids(candidates)
+            ext = _request_ext(a, rowset)
+            check(getattr(lib, f"{prefix}query_playlist_request_candidates")(
+                h, ctypes.byref(q), ctypes.byref(ext), ptr(cand) if cand.size else None, int(cand.size), ctypes.byref(res)))
+        elif rowset is not None:
+            ext = _request_ext(a, rowset)
             check(getattr(lib, f"{prefix}query_playlist_request_ext")(h, ctypes.byref(q), ctypes.byref(ext), ctypes.byref(res)))
         elif a is not None:
             check(getattr(lib, f"{prefix}query_playlist_request_scaled")(h, ctypes.byref(q), ptr(a), ctypes.byref(res)))
@@ -203,12 +212,22 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
     return out
 
 
-def _distance_request(lib, prefix: str, h, check, members, topn: int, exclude=None, where=None, labels=None, scales=None, rowset=None):
+def _request_ext(scales, rowset):
+    """capi.RequestExt from checked scales (a float32 array or None) and rowset = (pointer, mode) or None.  (The arrays it points to
+    are the caller's: they outlive the call.)"""
+    return capi.RequestExt(ctypes.sizeof(capi.RequestExt), int(rowset[1]) if rowset is not None else 0,
+                           scales.ctypes.data_as(ctypes.c_void_p) if scales is not None else None,
+                           rowset[0] if rowset is not None else None)
+
+
+def _distance_request(lib, prefix: str, h, check, members, topn: int, exclude=None, where=None, labels=None, scales=None, rowset=None,
+                      candidates=None):
     """One DISTANCE REQUEST (`prefix`query_distance_request): the `topn` rows nearest to the members by Euclidean distance.
     `members` is a (k, 12) float32 array (by value) or a 1-D int64 array of rows (never returned).  `exclude`, `where` and
     `labels` are the playlist request's.  Returns (ids, distances): nearest first, ties by row; for k > 1 a distance is the
     root-mean-square distance to the members.  `scales` (make_scales): FEATURE SCALES, through `prefix`query_distance_request_scaled.
-    `rowset` = (pointer, mode): ROW SETS, through `prefix`query_distance_request_ext."""
+    `rowset` = (pointer, mode): ROW SETS, through `prefix`query_distance_request_ext.  `candidates`: CANDIDATE LISTS, a sequence of
+    global ids, through `prefix`query_distance_request_candidates."""
     flt = make_filter(where) if where is not None else None
     ex = np.ascontiguousarray(np.asarray([] if exclude is None else list(exclude), dtype=np.int64).reshape(-1))
     n_out = max(int(topn), 1)
@@ -229,9 +248,15 @@ def _distance_request(lib, prefix: str, h, check, members, topn: int, exclude=No
         q.labels, q.n_labels = ptr(lab), int(lab.size)   # (an empty set stays a non-NULL pointer: the library refuses it)
     q.k, q.topn = int(members.shape[0]), int(topn)
     res = capi.DistanceResult(ptr(idx), ptr(dist), ctypes.pointer(count))
-    if rowset is not None:
+    if candidates is not None:
         a = make_scales(scales) if scales is not None else None
-        ext = capi.RequestExt(ctypes.sizeof(capi.RequestExt), int(rowset[1]), ptr(a) if a is not None else None, rowset[0])
+        cand = _np_ids(candidates)
+        ext = _request_ext(a, rowset)
+        check(getattr(lib, f"{prefix}query_distance_request_candidates")(
+            h, ctypes.byref(q), ctypes.byref(ext), ptr(cand) if cand.size else None, int(cand.size), ctypes.byref(res)))
+    elif rowset is not None:
+        a = make_scales(scales) if scales is not None else None
+        ext = _request_ext(a, rowset)
         check(getattr(lib, f"{prefix}query_distance_request_ext")(h, ctypes.byref(q), ctypes.byref(ext), ctypes.byref(res)))
     elif scales is not None:
         a = make_scales(scales)
@@ -381,10 +406,11 @@ class _RequestFamily(_RowSets):
         return self._playlist(_np_members(queries), topn, exclude, where, weights, labels=labels, prior_weight=prior_weight, scales=scales,
                               seen=seen, only=only)
 
-    def _playlist(self, members, topn, exclude, where, weights, level=None, labels=None, seen=None, only=None, **more):
+    def _playlist(self, members, topn, exclude, where, weights, level=None, labels=None, seen=None, only=None, candidates=None, **more):
+        """Every playlist method's one way down.  `candidates`: CANDIDATE LISTS, passed by with_candidates' view alone."""
         return self._with_set(seen, only, lambda rowset: _playlist_family(
             self._lib, self._prefix, self._h, self._check, members, topn, exclude, where, weights, level, labels=labels,
-            rowset=rowset, **more))
+            rowset=rowset, candidates=candidates, **more))
 
     # ---- DISTANCE REQUESTS (include/mi355rec_diag.h): the nearest rows by Euclidean distance ----
     def query_nearest(self, members, topn: int, exclude=None, where=None, labels=None) -> Tuple[np.ndarray, np.ndarray]:
@@ -409,9 +435,9 @@ class _RequestFamily(_RowSets):
         """query_nearest_rows with FEATURE SCALES and ROW SETS."""
         return self._nearest(_np_rows(rows), topn, scales, exclude, where, labels, seen, only)
 
-    def _nearest(self, members, topn, scales, exclude, where, labels, seen, only):
+    def _nearest(self, members, topn, scales, exclude, where, labels, seen, only, candidates=None):
         return self._with_set(seen, only, lambda rowset: _distance_request(
-            self._lib, self._prefix, self._h, self._check, members, topn, exclude, where, labels, scales, rowset))
+            self._lib, self._prefix, self._h, self._check, members, topn, exclude, where, labels, scales, rowset, candidates))
 
     # ---- DIVERSIFIED TOP-N (include/mi355rec_diag.h): MMR picks from the top-`pool` of the weighted playlist call ----
     def query_mean_topn_diverse(self, queries, topn: int, lam, pool=None, exclude=None, where=None, weights=None, return_mmr=False,
@@ -438,6 +464,46 @@ class _RequestFamily(_RowSets):
         return self._playlist(_np_members(queries), topn, exclude, where, weights, "_capped", lam=lam, pool=pool,
                               max_per_group=max_per_group, return_mmr=return_mmr, return_pool_rows=return_pool_rows,
                               labels=labels, prior_weight=prior_weight, seen=seen, only=only)
+
+
+class _Listed:
+    """An engine seen through a CANDIDATE LIST (with_candidates): the engine's request-family methods, each ranking within the list.
+    A method of the engine's class runs with THIS object as its self, so its one call down (self._playlist / self._nearest) lands
+    here and goes on to the engine's with the list as an explicit argument.  The engine itself is never written to."""
+
+    def __init__(self, eng, candidates):
+        self._eng, self._ids = eng, _np_ids(candidates)
+
+    def __getattr__(self, name):
+        if not (name.startswith("query_mean_topn") or name.startswith("query_playlist_topn") or name.startswith("query_nearest")):
+            raise AttributeError(f"{name}: a candidate list goes with query_mean_topn*, query_playlist_topn* and query_nearest*")
+        return types.MethodType(getattr(type(self._eng), name), self)
+
+    def _playlist(self, *args, **kwargs):
+        return self._eng._playlist(*args, candidates=self._ids, **kwargs)
+
+    def _nearest(self, *args, **kwargs):
+        return self._eng._nearest(*args, candidates=self._ids, **kwargs)
+
+
+def with_candidates(eng, candidates):
+    """CANDIDATE LISTS (include/mi355rec_diag.h): `eng` (a CosineEngine, a lane or a NodeEngine) restricted to `candidates`, a plain
+    sequence or an int64 array of global ids in any order (duplicates fine, up to capi.MAX_CANDIDATES; empty: nothing is returned).
+    The object returned has the engine's query_mean_topn*, query_playlist_topn* and query_nearest* methods with their own
+    parameters; each gathers and ranks ONLY the listed rows, where an `only=` row set would make a pass over the whole catalogue.
+    It composes with every other argument: with `seen=` the answer lies in the list minus the set (candidates minus a listening
+    history), with `only=` in both.  The result is bit for bit that of `only=candidates`.
+        ids, scores = with_candidates(eng, first_stage_ids).query_playlist_topn(playlist_rows, 100, seen=history)
+    (The engines' own methods keep their parameter lists: tests/test_engine_surface.py records them.)"""
+    return _Listed(eng, candidates)
+
+
+def candidates_counters(eng) -> dict:
+    """mi355rec_candidates_counters of a CosineEngine (or a lane): the requests that took the gather launch and the distinct
+    in-shard list entries those launches were given, since the handle was created."""
+    q, r = ctypes.c_int64(0), ctypes.c_int64(0)
+    capi.check(eng._lib.mi355rec_candidates_counters(eng._h, ctypes.byref(q), ctypes.byref(r)), eng._h)
+    return {"requests": q.value, "rows_gathered": r.value}
 
 
 class CosineEngine(_RequestFamily):
