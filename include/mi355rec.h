@@ -174,7 +174,15 @@ int mi355rec_enqueue_query_keys(mi355rec_t* h, const float* query12,
  * completed; out_keys_dev must stay valid until then — in practice: flush, then
  * synchronise, then read.  A stream of K queries costs K scan launches + ONE merge launch
  * (+ one seed launch) instead of 3 K, which removes the ~10 us one-workgroup merge kernel
- * and the ~5 us seed kernel from every step. */
+ * and the ~5 us seed kernel from every step.
+ * PAIRS: where the handle pairs (mi355rec_set_stream_pairing, include/mi355rec_diag.h; by default on shards of
+ * MI355REC_PAIRING_AUTO_MIN_ROWS rows and more), two consecutive streamed queries over the 8-bit replica that
+ * ask for the same topn <= 128 are served by ONE launch that scores every row against both, and the stream
+ * runs up to THREE calls behind instead of one: call 2k + 1 completes pair k and launches pair k - 1, whose
+ * launch merges pair k - 2.  The contract is the one above, stated without a call count: the keys of streamed
+ * queries are written in CALL ORDER (a buffer given to two queries ends with the later one's keys), and
+ * everything enqueued is written once the work of mi355rec_enqueue_flush on the stream has completed.  A
+ * streamed launch may thus serve two queued queries; each of them is still one full pass' worth of scores. */
 int mi355rec_enqueue_row_keys_streamed(mi355rec_t* h, int64_t local_row, int topn,
                                        mi355rec_key_t* out_keys_dev, void* stream);
 int mi355rec_enqueue_query_keys_streamed(mi355rec_t* h, const float* query12,

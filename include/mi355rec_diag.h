@@ -87,6 +87,8 @@ typedef struct {
     int64_t route_mfma_two_pass; /* chunks (<= 1024 queries) of the two-pass batched matrix-core path              */
     int64_t route_exact_queue;   /* queries that path handed to the exact scan on the device (reading it synchronises) */
     int32_t device_bytes_per_row; /* what the handle keeps resident per row: 48 (fp32) + 24 (fp16 replica) + 12 (8-bit) */
+    int64_t stream_pair_launches; /* streamed launches that served TWO queued queries in one pass over the 8-bit replica
+                                     (mi355rec_set_stream_pairing); each of them still counts twice in route_q8 */
 } mi355rec_stats_t;
 
 /* What this build of the library was compiled with.  The product build returns 0.  The tools/ scripts build
@@ -179,6 +181,24 @@ int mi355rec_replica_counters(mi355rec_t* h, int64_t* scans, int64_t* rescored_r
 #define MI355REC_SAMPLE_BUCKETED 2
 #define MI355REC_SAMPLE_AUTO_MIN_ROWS 6000000
 int mi355rec_set_sample(mi355rec_t* h, int mode);
+
+/* PAIRS OF STREAMED QUERIES.  Two consecutive mi355rec_enqueue_*_streamed calls on a handle that both scan the 8-bit replica
+ * and ask for the same topn <= 128 may be served by ONE pass over the replica: a tile is loaded once and scored against
+ * both queries (csrc/replica_q8.hip.h, scan_q8_kernel_pair).  Everything per query — cutoff, candidates, exact re-scoring,
+ * merge, keys — is what the one-query launch computes, bit for bit; only the bytes streamed per query halve.  The stream
+ * then runs up to three calls behind instead of one (include/mi355rec.h).  A query without a partner (an odd tail at the
+ * flush, another topn, a change of mi355rec_set_replica / _set_sample or a non-streamed call in between) takes the
+ * one-query launch.  The two sample launches of the first pair of a stream take the sample a carried query would take under
+ * mi355rec_set_sample(AUTO) (they are two calls ahead of the pair's launch, not on its critical path).
+ *   AUTO (default): pairs on shards of at least MI355REC_PAIRING_AUTO_MIN_ROWS rows;
+ *   OFF:            never;
+ *   ON:             wherever the two queries qualify.
+ * The mode belongs to the handle; a lane inherits its parent's when it is created.  The shards of a node handle do not pair. */
+#define MI355REC_PAIRING_AUTO 0
+#define MI355REC_PAIRING_OFF 1
+#define MI355REC_PAIRING_ON 2
+#define MI355REC_PAIRING_AUTO_MIN_ROWS 2500000
+int mi355rec_set_stream_pairing(mi355rec_t* h, int mode);
 typedef struct {
     int64_t base_rows;        /* rows of the base (0: the handle has no bucketed sample)                          */
     int32_t regions;          /* 2048-row regions of the ordered base                                            */

@@ -1,7 +1,8 @@
 // engine_single.hip.h — ONE query at a time: which rows its scan streams (fp32, 8-bit replica), the sample / neighbourhood
 // launch in front of a query alone, the scan + merge (replaces calculateSimilarities + the host heap, Recommender.cu:184-254,
 // 293-315), rounds for topn > 1024, the completion word of a synchronous query, and the STREAM of single queries that runs
-// one call behind so that every launch carries the next query's seed riders.  (Part of mi355rec.hip's translation unit.)
+// one call behind so that every launch carries the next query's seed riders — or, where two queued queries share one pass
+// over the 8-bit replica ("pairs"), up to three.  (Part of mi355rec.hip's translation unit.)
 #pragma once
 
 #include "engine_state.hip.h"
@@ -210,7 +211,7 @@ int launch_scan(mi355rec* h, const ScanLaunch& L, const float* qptr, const float
                              h->d_feats, h->d_q8, h->n, L.iters, h->row_base, qa, qp, exclude_global, topn, L.lists, L.sample,
                              q8_seeds, h->d_half_rescored, L.prev, L.next, L.bound, L.tail, L.epoch);
             };
-            if (L.streamed) launch(scan_q8_kernel<Q8Config, kRow, true>);
+            if (L.streamed) launch(scan_q8_kernel<Q8Config, false, true>);   // (one streamed form: it tests qp at run time)
             else if (fused) launch(scan_q8_kernel<Q8Config, kRow, false, true>);
             else launch(scan_q8_kernel<Q8Config, kRow, false>);
         });
@@ -329,8 +330,15 @@ int check_topn(mi355rec* h, int topn, bool allow_rounds) {
 // One query end to end on stream `s`: scan + merge, in rounds of kMaxTopK when
 // topn is larger (round r only sees keys below the last key of round r-1, read
 // from device memory, so the rounds are enqueued back to back without a sync).
+bool pairs_open(const mi355rec* h);
+int flush_streamed(mi355rec* h, hipStream_t s);
 int enqueue_query(mi355rec* h, const float* qptr, const float* query12, int64_t exclude_global,
                   int topn_asked, uint64_t* out_keys, int64_t* out_idx, float* out_score, hipStream_t s, uint32_t notify = 0) {
+    // a non-streamed query between two streamed ones: a pair is not held open across it ("pairs", below)
+    if (pairs_open(h)) {
+        const int rc = flush_streamed(h, s);
+        if (rc) return rc;
+    }
     // A shard of n rows has at most n results (the reference's heap never grows
     // past N-1, Recommender.cu:300): run only the rounds that can produce keys and
     // pad the rest, so an absurd topn costs a memset, not topn/1024 catalogue scans.
@@ -417,7 +425,17 @@ int merge_pending(mi355rec* h, hipStream_t s) {
 int launch_stashed(mi355rec* h, hipStream_t s, bool with_next, const float* next_ptr, const float* next_q,
                    int64_t next_exclude, int next_topn, int next_buf, uint32_t next_epoch_tag);
 
+int drain_pairs(mi355rec* h, hipStream_t s);   // ("pairs", below)
+
+// Everything the stream of single queries still holds is launched and merged: the pairs first (their queries came first), then
+// the one-query path's stashed query and pending merge.  Every call that closes a stream goes through here.
+int flush_single_stream(mi355rec* h, hipStream_t s);
 int flush_streamed(mi355rec* h, hipStream_t s) {
+    const int rc = drain_pairs(h, s);
+    return rc ? rc : flush_single_stream(h, s);
+}
+
+int flush_single_stream(mi355rec* h, hipStream_t s) {
     if (h->stashed.has) {
         const int rc = launch_stashed(h, s, false, nullptr, nullptr, -1, 0, 0, 0u);
         if (rc) return rc;
@@ -474,19 +492,19 @@ int launch_stashed(mi355rec* h, hipStream_t s, bool with_next, const float* next
     return MI355REC_OK;
 }
 
-int enqueue_streamed(mi355rec* h, const float* qptr, const float* query12, int64_t exclude_global, int topn,
-                     uint64_t* out_keys, hipStream_t s) {
-    int rc = ensure_streamed(h);
-    if (rc) return rc;
-    rc = flush_mstream(h, s);   // a stream of BATCHES on this handle is closed first
-    if (rc) return rc;
+// The one-query path: what a streamed query takes that finds no partner ("pairs", below), or whose handle does not pair.
+// accepted_kind >= 0: the rows the query was accepted for when it was called (a first query of a pair that lost its partner:
+// it streams what it would have streamed had it been stashed here at once).
+int enqueue_streamed_single(mi355rec* h, const float* qptr, const float* query12, int64_t exclude_global, int topn,
+                            uint64_t* out_keys, hipStream_t s, int accepted_kind = -1) {
+    int rc = MI355REC_OK;
     if (MI355REC_EXP_FLAG("MI355REC_EXP_RIDE_NOMERGE") && h->pending) {
-        rc = flush_streamed(h, s);
+        rc = flush_single_stream(h, s);
         if (rc) return rc;
     }
     // One call behind: the query of the PREVIOUS call is launched now, and its launch takes the sample and the
     // neighbourhood of this one.  The first query of a stream needs a sample launch of its own.
-    const int kind = single_kind(h, nullptr);
+    const int kind = accepted_kind >= 0 ? accepted_kind : single_kind(h, nullptr);
     int seed_buf = 0;
     bool sampled = false, nbhd_taken = false;
     const uint32_t epoch = next_epoch(h);   // the tag of this query's sample values and bound
@@ -527,6 +545,242 @@ int enqueue_streamed(mi355rec* h, const float* qptr, const float* query12, int64
     st.kind = kind;
     st.bucketed = bucketed;
     st.cutoff_ready = bound_ready;
+    return MI355REC_OK;
+}
+
+// ---- pairs ----------------------------------------------------------------------------------------------------------
+// Two queued single queries each stream the same 8-bit replica; the vector work per query is small beside the stream.  So
+// two CONSECUTIVE streamed queries that both take the 8-bit replica and ask for the same topn <= kPairMaxTopk form a PAIR,
+// and one launch (scan_q8_kernel_pair) scores every tile against both.  Either may be by row, by value or by pointer.
+//
+// The stream then runs up to THREE calls behind: it holds the pair that waits for its launch and the first query of the
+// pair after it.  Call 2k + 1 completes pair k and launches pair k - 1, whose launch carries the two mergers of pair k - 2
+// and the seed riders and neighbourhood workgroups of BOTH queries of pair k (each with its own sample buffer, SeedCtl and
+// epoch; bucketed where use_bucket says so).  The first pair of a stream gets sample launches of its own.  A query that
+// finds no partner — the odd tail at a flush, a change of topn, of the rows single queries stream, of mi355rec_set_replica
+// or mi355rec_set_sample between the two calls, a handle that does not pair — goes through the one-query path above,
+// unchanged.  The two paths are never open at once: whichever a query takes closes the other first, so keys are always
+// written in call order.  All per-QUERY books stay per query; a pair launch counts once in stream_pair_launches.
+bool pairing_on(const mi355rec* h) {
+    if (h->pairing == MI355REC_PAIRING_ON) return true;
+    if (h->pairing == MI355REC_PAIRING_OFF) return false;
+    return h->n >= MI355REC_PAIRING_AUTO_MIN_ROWS;
+}
+bool pairs_open(const mi355rec* h) { return h->pairs.waiting || h->pairs.has_first || h->pairs.pending; }
+
+void free_pairs(mi355rec* h) {
+    auto& P = h->pairs;
+    for (int i = 0; i < 4; ++i) {
+        if (P.lists[i]) (void)hipFree(P.lists[i]);
+        if (P.seed[i]) (void)hipFree(P.seed[i]);
+        P.lists[i] = nullptr;
+        P.seed[i] = nullptr;
+    }
+    if (P.ctl) (void)hipFree(P.ctl);
+    P.ctl = nullptr;
+    P.ready = false;
+}
+
+int ensure_pairs_alloc(mi355rec* h) {
+    auto& P = h->pairs;
+    const size_t words = static_cast<size_t>(h->geom[kQ8].grid > 0 ? h->geom[kQ8].grid : 1) * kPairMaxTopk;
+    for (int i = 0; i < 4; ++i) {
+        HIP_TRY(h, hipMalloc(&P.lists[i], sizeof(uint64_t) * words));
+        HIP_TRY(h, hipMalloc(&P.seed[i], sizeof(unsigned long long) * kSampleSlots));
+        HIP_TRY(h, hipMemset(P.seed[i], 0, sizeof(unsigned long long) * kSampleSlots));
+    }
+    HIP_TRY(h, hipMalloc(&P.ctl, sizeof(SeedCtl) * 4));
+    HIP_TRY(h, hipMemset(P.ctl, 0, sizeof(SeedCtl) * 4));
+    return MI355REC_OK;
+}
+int ensure_pairs(mi355rec* h) {
+    if (h->pairs.ready) return MI355REC_OK;
+    const int rc = ensure_pairs_alloc(h);
+    if (rc != MI355REC_OK) {   // all or nothing
+        free_pairs(h);
+        return rc;
+    }
+    for (unsigned& d : h->pairs.ctl_done) d = 0u;
+    h->pairs.ready = true;
+    return MI355REC_OK;
+}
+
+// The mergers of the pair launched last, in launches of their own and in call order.
+int merge_pair_pending(mi355rec* h, hipStream_t s) {
+    auto& P = h->pairs;
+    P.pending = false;
+    for (int x = 0; x < 2; ++x) {
+        const int rc = enqueue_merge(h, P.lists[2 * P.pending_set + x], P.pending_lists, P.pending_topn, P.pending_topn, P.pending_out[x],
+                                     nullptr, nullptr, s);
+        if (rc) return rc;
+    }
+    return MI355REC_OK;
+}
+
+// Launches the waiting pair: scanners + the two riding mergers of the pair before + (next != null) the seed riders and the
+// neighbourhood workgroups of the two queries of the pair after, where the launch has them (ScanGeom: riders, nbhd, hoists).
+int launch_pair(mi355rec* h, hipStream_t s, const mi355rec::Stashed* next, bool next_bucketed) {
+    auto& P = h->pairs;
+    const mi355rec::Stashed& a = P.wait[0];
+    const mi355rec::Stashed& b = P.wait[1];
+    const int topn = a.topn;
+    // two mergers in one launch write their keys in no particular order: lists that share an output are merged one after the other
+    if (P.pending) {
+        const uint64_t* lo = P.pending_out[0] < P.pending_out[1] ? P.pending_out[0] : P.pending_out[1];
+        const uint64_t* hi = P.pending_out[0] < P.pending_out[1] ? P.pending_out[1] : P.pending_out[0];
+        if (hi < lo + P.pending_topn) {
+            const int rc = merge_pair_pending(h, s);
+            if (rc) return rc;
+        }
+    }
+    const ScanGeom& g = stream_geom(h, kQ8, next != nullptr && next_bucketed);
+    const bool riders = next != nullptr && (g.riders > 0 || g.nbhd);
+    const int extra = 2 + (riders ? 2 * (g.riders + (g.nbhd ? 1 : 0)) : 0);
+    const int64_t tiles = (h->n + Q8PairConfig::kTileRows - 1) / Q8PairConfig::kTileRows;
+    int64_t scanners = g.grid - extra;
+    if (scanners > kRideMaxLists - 1) scanners = kRideMaxLists - 1;
+    if (scanners > tiles) scanners = tiles;
+    if (scanners < 1) scanners = 1;
+    const int iters = static_cast<int>((tiles + scanners - 1) / scanners);
+    const int set = P.pending ? 1 - P.pending_set : 0;
+    Q8PairSide side;
+    std::memset(&side, 0, sizeof side);
+    side.prev[0] = side.prev[1] = no_prev_merge();
+    if (P.pending)
+        for (int x = 0; x < 2; ++x) side.prev[x] = PrevMerge{P.lists[2 * P.pending_set + x], P.pending_lists, P.pending_topn, P.pending_out[x]};
+    if (riders)
+        for (int x = 0; x < 2; ++x)
+            side.next[x] = make_next_seed(h, kQ8, g.riders, g.nbhd, next[x].qptr, next[x].q, next[x].exclude, next[x].topn, next[x].epoch,
+                                          P.seed[next[x].seed_buf], g.hoists ? P.ctl + next[x].seed_buf : nullptr,
+                                          P.ctl_done[next[x].seed_buf], next_bucketed);
+    Q8PairArg arg[2];
+    const mi355rec::Stashed* const q[2] = {&a, &b};
+    for (int x = 0; x < 2; ++x) {
+        std::memset(&arg[x], 0, sizeof arg[x]);
+        arg[x].qarg = make_query_arg(h, q[x]->qptr, q[x]->q);
+        arg[x].query_ptr = q[x]->qptr;
+        arg[x].exclude_global = q[x]->exclude;
+        arg[x].block_lists = P.lists[2 * set + x];
+        arg[x].seed_vals = P.seed[q[x]->seed_buf];
+        arg[x].cutoff_ready = q[x]->cutoff_ready ? &P.ctl[q[x]->seed_buf].cutoff : nullptr;
+        arg[x].n_seed = q8_seed_count(h, q[x]->bucketed);   // (negative: exact values)
+        arg[x].epoch = q[x]->epoch;
+    }
+    const dim3 grid(static_cast<unsigned>(scanners + 2 + 2 * (side.next[0].n_wgs + side.next[0].nbhd)));
+    LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, scan_q8_kernel_pair<Q8PairConfig>, grid, dim3(Q8PairConfig::kBlock), s,
+                 h->d_feats, h->d_q8, h->n, iters, h->row_base, arg[0], arg[1], topn, h->d_half_rescored, side);
+    HIP_TRY(h, hipGetLastError());
+    // (the books move only once the launch is known to have been accepted: per QUERY, as on the one-query path)
+    h->half_scans += 2;
+    h->q8_scans += 2;
+    h->routes.q8 += 2;
+    ++h->stream_pair_launches;
+    for (int x = 0; x < 2; ++x)
+        if (side.next[x].ctl) P.ctl_done[next[x].seed_buf] += static_cast<unsigned>(side.next[x].n_wgs);
+    P.pending = true;
+    P.pending_set = set;
+    P.pending_lists = static_cast<int>(scanners);
+    P.pending_topn = topn;
+    P.pending_out[0] = a.out;
+    P.pending_out[1] = b.out;
+    P.waiting = false;
+    return MI355REC_OK;
+}
+
+// Everything the pairs still hold, in call order: the waiting pair, the mergers, and the first query of an unfinished
+// pair — which found no partner and takes the one-query path (left open: the caller flushes it or streams on).
+int drain_pairs(mi355rec* h, hipStream_t s) {
+    auto& P = h->pairs;
+    if (P.waiting) {
+        const int rc = launch_pair(h, s, nullptr, false);
+        if (rc) return rc;
+    }
+    if (P.pending) {
+        const int rc = merge_pair_pending(h, s);
+        if (rc) return rc;
+    }
+    if (P.has_first) {
+        const mi355rec::Stashed f = P.first;
+        P.has_first = false;
+        return enqueue_streamed_single(h, f.qptr, f.q, f.exclude, f.topn, f.out, s, h->d_q8 ? f.kind : -1);
+    }
+    return MI355REC_OK;
+}
+
+int enqueue_streamed(mi355rec* h, const float* qptr, const float* query12, int64_t exclude_global, int topn,
+                     uint64_t* out_keys, hipStream_t s) {
+    int rc = ensure_streamed(h);
+    if (rc) return rc;
+    rc = flush_mstream(h, s);   // a stream of BATCHES on this handle is closed first
+    if (rc) return rc;
+    auto& P = h->pairs;
+    bool pair = single_kind(h, nullptr) == kQ8 && topn <= kPairMaxTopk && pairing_on(h);
+    if (pair && ensure_pairs(h) != MI355REC_OK) {   // (no room for the pairs' buffers: the one-query path serves)
+        (void)hipGetLastError();
+        pair = false;
+    }
+    // a first query whose partner this one cannot be finds none
+    if (pair && P.has_first && (P.first.topn != topn || P.first_replica_mode != h->replica_mode || P.first_sample_mode != h->sample_mode)) {
+        rc = drain_pairs(h, s);
+        if (rc) return rc;
+    }
+    if (!pair) {
+        if (pairs_open(h)) {
+            rc = drain_pairs(h, s);
+            if (rc) return rc;
+        }
+        return enqueue_streamed_single(h, qptr, query12, exclude_global, topn, out_keys, s);
+    }
+    if (h->stashed.has || h->pending) {
+        rc = flush_single_stream(h, s);
+        if (rc) return rc;
+    }
+    mi355rec::Stashed x;
+    x.has = true;
+    x.qptr = qptr;
+    if (!qptr) std::memcpy(x.q, query12, sizeof x.q);
+    x.exclude = exclude_global;
+    x.topn = topn;
+    x.out = out_keys;
+    x.kind = kQ8;
+    if (!P.has_first) {   // the first of a pair: it waits for its partner without a sample
+        P.first = x;
+        P.has_first = true;
+        P.first_replica_mode = h->replica_mode;
+        P.first_sample_mode = h->sample_mode;
+        return MI355REC_OK;
+    }
+    // The pair is complete: the pair before it is launched now, and its launch takes the samples and the neighbourhoods of
+    // this one.  The first pair of a stream, and a shard too small to spare riders, get sample launches of their own.
+    // (Which sample: what use_bucket gives a CARRIED query — also for the first pair of a stream.  Its sample launches are
+    // not on the pair's critical path as a query alone's is: the pair is launched two calls from now, or by the flush.)
+    const int set = P.waiting ? 1 - (P.wait[0].seed_buf >> 1) : 0;
+    const bool bucketed = use_bucket(h, kQ8, topn, h->geom_bucket.riders > 0);
+    const ScanGeom& ng = stream_geom(h, kQ8, bucketed);   // of the launch that carries THIS pair's samples
+    mi355rec::Stashed nx[2] = {P.first, x};
+    for (int i = 0; i < 2; ++i) {
+        nx[i].seed_buf = 2 * set + i;
+        nx[i].epoch = next_epoch(h);
+        nx[i].bucketed = bucketed;
+    }
+    h->last_sample = bucketed ? MI355REC_SAMPLE_BUCKETED : MI355REC_SAMPLE_STRIDED;
+    bool sampled = false;
+    if (P.waiting) {
+        sampled = ng.riders > 0;
+        rc = launch_pair(h, s, nx, bucketed);
+        if (rc) return rc;
+    }
+    if (!sampled) {
+        for (int i = 0; i < 2; ++i)
+            enqueue_half_seed(h, kQ8, nx[i].qptr, nx[i].q, nx[i].exclude, topn, P.seed[nx[i].seed_buf], nx[i].epoch, s, bucketed);
+        HIP_TRY(h, hipGetLastError());
+    }
+    for (int i = 0; i < 2; ++i) {
+        nx[i].cutoff_ready = sampled && ng.hoists;
+        P.wait[i] = nx[i];
+    }
+    P.waiting = true;
+    P.has_first = false;
     return MI355REC_OK;
 }
 

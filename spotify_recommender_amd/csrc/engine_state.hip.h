@@ -59,6 +59,7 @@ using ScanConfig = DefaultScanCfg;
 using MultiConfig = DefaultMultiCfg;
 using HalfConfig = DefaultHalfCfg;
 using Q8Config = DefaultQ8Cfg;
+using Q8PairConfig = DefaultQ8PairCfg;
 constexpr int kRideTopnMax = 640;   // largest topN whose merge rides in the next fp32 scan launch
 constexpr int64_t kReplicaMinRows = 65536;      // smaller shards are created without a replica (built on demand by set_replica(ON))
 constexpr int64_t kHalfAutoMinRows = 1000000;   // below this a query is launch-bound either way (measured: 11.8 vs
@@ -225,6 +226,28 @@ struct mi355rec {
     } stashed;
     unsigned long long* d_stream_seed[2] = {nullptr, nullptr};
     SeedCtl* d_stream_ctl = nullptr;    // [2]: rider count and finished cutoff beside each of d_stream_seed (8-bit replica)
+    // PAIRS of streamed queries over the 8-bit replica (engine_single.hip.h, "pairs"): two consecutive queries with the same
+    // topn <= kPairMaxTopk share ONE pass over the replica (scan_q8_kernel_pair).  The stream then holds up to three queries
+    // back: the pair that WAITS for its launch (its samples taken or in flight) and the FIRST of the pair after it, which has
+    // no sample yet.  The waiting pair is launched when that next pair is complete, or by the flush; its launch carries the
+    // mergers of the pair before and the riders of the pair after.  Buffers come in two sets of two (set p: [2p], [2p + 1]).
+    int pairing = 0;                    // MI355REC_PAIRING_AUTO / _OFF / _ON (mi355rec_set_stream_pairing)
+    int64_t stream_pair_launches = 0;   // pair launches since create
+    struct Pairs {
+        bool ready = false;             // the buffers below exist
+        uint64_t* lists[4] = {nullptr, nullptr, nullptr, nullptr};             // sgrid x kPairMaxTopk keys each
+        unsigned long long* seed[4] = {nullptr, nullptr, nullptr, nullptr};    // kSampleSlots tagged values each
+        SeedCtl* ctl = nullptr;         // [4] beside them ...
+        unsigned ctl_done[4] = {0u, 0u, 0u, 0u};   // ... and what their arrival counters hold
+        bool waiting = false;           // wait[0], wait[1]: a complete pair whose launch is due
+        Stashed wait[2];
+        bool has_first = false;         // first: the first query of the next pair (no sample yet) ...
+        Stashed first;
+        int first_replica_mode = 0, first_sample_mode = 0;   // ... and the modes it was accepted under
+        bool pending = false;           // the lists of the pair launched last wait for their mergers
+        int pending_set = 0, pending_lists = 0, pending_topn = 0;
+        uint64_t* pending_out[2] = {nullptr, nullptr};
+    } pairs;
     // a STREAM of batches over the replica (mi355rec_enqueue_batch_keys_streamed)
     bool mstream_ready = false;
     uint64_t* d_mstream_lists[2] = {nullptr, nullptr};   // [kHmQueries][hgrid][kMultiMaxTopK], alternating

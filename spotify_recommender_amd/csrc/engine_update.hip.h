@@ -20,7 +20,7 @@ namespace {
 bool owns_matrix(const mi355rec* h) { return h->owned_feats || (h->shared && h->shared->owned_feats); }
 
 // A streamed query or batch that has been accepted and not completed: its sample or cutoff was taken from the rows as they were.
-bool stream_open(const mi355rec* m) { return m->stashed.has || m->pending || m->mstash.has || m->mpending.has; }
+bool stream_open(const mi355rec* m) { return m->stashed.has || m->pending || pairs_open(m) || m->mstash.has || m->mpending.has; }
 
 // The staging of one chunk of `rows` rows (<= mi355update::kStageRows): [ids][sorted positions][rows x 12 floats], packed, in
 // pinned memory and on the device.  The handle's stream is idle when this is called (every chunk waits for its launch).

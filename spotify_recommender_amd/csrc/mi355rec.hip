@@ -45,6 +45,7 @@ void preallocate_stream_state(mi355rec* h) {
     const std::string kept = h->err;
     bool ok = ensure_streamed(h) == MI355REC_OK;
     if (ok && h->d_half) ok = ensure_mstream(h) == MI355REC_OK;
+    if (ok && h->d_q8 && h->pairing != MI355REC_PAIRING_OFF) ok = ensure_pairs(h) == MI355REC_OK;
     if (!ok) {
         (void)hipGetLastError();
         h->err = kept;
@@ -105,6 +106,7 @@ void mi355rec_destroy(mi355rec_t* h) {
     }
     if (h->d_stream_lists[0]) (void)hipFree(h->d_stream_lists[0]);
     if (h->d_stream_lists[1]) (void)hipFree(h->d_stream_lists[1]);
+    free_pairs(h);
     if (h->d_anchor) (void)hipFree(h->d_anchor);
     if (h->d_seed_keys) (void)hipFree(h->d_seed_keys);
     if (h->d_seed_vals) (void)hipFree(h->d_seed_vals);
@@ -210,6 +212,7 @@ int mi355rec_create_lane(mi355rec_t* parent, mi355rec_t** out) {
     // are the lane's too, until it is told otherwise itself
     lane->replica_mode = parent->replica_mode;
     lane->batch_path = parent->batch_path;
+    lane->pairing = parent->pairing;
     if (parent->d_half) {
         const int src = alloc_replica_state(lane);
         if (src != MI355REC_OK) {
@@ -365,6 +368,7 @@ int mi355rec_stats(const mi355rec_t* hc, mi355rec_stats_t* out) {
             out->route_exact_queue = queued;
     }
     out->device_bytes_per_row = 48 + (h->d_half ? 24 : 0) + (h->d_q8 ? 12 : 0);
+    out->stream_pair_launches = h->stream_pair_launches;
     return MI355REC_OK;
 }
 
@@ -704,6 +708,14 @@ int mi355rec_set_sample(mi355rec_t* h, int mode) {
     return MI355REC_OK;
 }
 
+int mi355rec_set_stream_pairing(mi355rec_t* h, int mode) {
+    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    if (mode != MI355REC_PAIRING_AUTO && mode != MI355REC_PAIRING_OFF && mode != MI355REC_PAIRING_ON)
+        return fail(h, MI355REC_ERR_INVALID_ARG, "unknown pairing mode %d", mode);
+    h->pairing = mode;   // (from the next streamed query on: one that waits for a partner it can no longer get takes the one-query path)
+    return MI355REC_OK;
+}
+
 int mi355rec_bucket_sample_info(const mi355rec_t* h, mi355rec_bucket_sample_info_t* out) {
     if (!h || !out) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null argument");
     std::memset(out, 0, sizeof *out);
@@ -763,6 +775,19 @@ int mi355rec_debug_handoff(mi355rec_t* h, int flags) {
             HIP_TRY(h, hipMemcpy(ctl, h->d_stream_ctl, sizeof ctl, hipMemcpyDeviceToHost));
             ctl[0].cutoff = ctl[1].cutoff = stale_cut;   // (the arrival counters stay what they are)
             HIP_TRY(h, hipMemcpy(h->d_stream_ctl, ctl, sizeof ctl, hipMemcpyHostToDevice));
+        }
+        if (h->pairs.ready) {
+            // the pairs' buffers (engine_single.hip.h, "pairs"): TWO epochs are live while a pair waits for its launch (the
+            // last one handed out and the one before), so the stale values carry the three epochs before those
+            std::vector<unsigned long long> older(per);
+            for (size_t i = 0; i < per; ++i)
+                older[i] = (static_cast<unsigned long long>(h->epoch_ctr - 2u - static_cast<uint32_t>(i % 3)) << 32) | one;
+            for (unsigned long long* b : h->pairs.seed)
+                if (b) HIP_TRY(h, hipMemcpy(b, older.data(), sizeof(unsigned long long) * per, hipMemcpyHostToDevice));
+            SeedCtl ctl[4];
+            HIP_TRY(h, hipMemcpy(ctl, h->pairs.ctl, sizeof ctl, hipMemcpyDeviceToHost));
+            for (SeedCtl& c : ctl) c.cutoff = (static_cast<unsigned long long>(h->epoch_ctr - 2u) << 32) | one_bits;
+            HIP_TRY(h, hipMemcpy(h->pairs.ctl, ctl, sizeof ctl, hipMemcpyHostToDevice));
         }
         if (h->d_lone_ctl) {
             SeedCtl ctl;

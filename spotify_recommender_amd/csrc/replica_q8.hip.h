@@ -606,6 +606,51 @@ __device__ __forceinline__ float q8_cutoff_from_sample(const Sample& sample, int
     return exact_values ? v - hq.margin : v - 2.0f * hq.margin;   // (-inf stays -inf)
 }
 
+// ---- the workgroups of a streamed launch that do not scan (scan_q8_kernel, scan_q8_kernel_pair) --------------------------
+// The merger of a query before: its per-workgroup lists into the caller's keys.
+template <typename MergeSmem>
+__device__ __forceinline__ void q8_ride_merge(MergeSmem& sm, const PrevMerge& prev) {
+    if (prev.lists)
+        merge_body(sm, prev.lists, prev.n_lists, prev.topk, static_cast<int64_t>(prev.topk), static_cast<int64_t>(0), prev.topk,
+                   prev.out_keys, static_cast<int64_t*>(nullptr), static_cast<float*>(nullptr), static_cast<int64_t>(0),
+                   static_cast<int64_t>(0), static_cast<int64_t>(0));
+}
+
+// The neighbourhood of a query after (handoff.hip.h): read by the launch that scans for it.
+template <int kBlock>
+__device__ __forceinline__ void q8_ride_nbhd(const float* __restrict__ feats, int64_t n, int64_t row_base, const NextSeed& next,
+                                             int* s_scratch) {
+    nbhd_to_slot<kBlock>(feats, n, row_base, next.query_ptr, next.q, next.exclude_global, next.topk, next.epoch,
+                         static_cast<unsigned long long*>(next.out), s_scratch, next.anchors);
+}
+
+// Seed rider `rider` of next.n_wgs: its share of the sample of a query after, strided or bucketed.  s_scratch: kBucketScratch
+// ints of LDS nobody else is using.
+template <int kBlock>
+__device__ __forceinline__ void q8_ride_sample(const float* __restrict__ feats, const uint4* __restrict__ q8, int64_t n, int64_t row_base,
+                                               const NextSeed& next, int rider, int* s_scratch, int* s_flag, int* s_seeds,
+                                               SelectSmem& s_sel) {
+    const bool bucketed = next.bucket.rows != nullptr;   // uniform
+    // (DROP_STORES, the test hook: the bucketed riders drop every store)
+    const Q8Query nq = bucketed ? q8_bucket_sample(feats, next.bucket, n, row_base, next.query_ptr, next.q, next.exclude_global,
+                                                   static_cast<unsigned long long*>(next.out), next.epoch, rider, next.n_wgs,
+                                                   next.debug_skip > 0, s_scratch, s_sel)
+                                : q8_seed_rider(feats, q8, n, row_base, next, rider);
+    const int n_vals = bucketed ? kBucketPicks * kBucketGroups : next.regions * kHalfSeedWaves;
+    // Last rider out turns the sample into the cutoff (handoff.hip.h, sample_arrive_and_select: no device-wide
+    // fence under the scanners).  Values and cutoff carry the next query's epoch and the counter is never reset.
+    if (next.ctl) {   // uniform; null: nobody reads the sample inside this launch (small shards: the next launch selects)
+        float v;
+        if (sample_arrive_and_select<kBlock>(next.ctl, next.done_base, static_cast<unsigned>(next.n_wgs),
+                                             static_cast<const unsigned long long*>(next.out), n_vals, next.topk, next.epoch, s_flag,
+                                             s_seeds, s_sel, s_scratch, v)) {
+            // one margin below an EXACT score of a real row, two below an approximate one
+            const float c = !nq.ok ? -__builtin_inff() : (next.exact != 0 ? v - nq.margin : v - 2.0f * nq.margin);
+            if (threadIdx.x == 0) next.ctl->cutoff = tag_value(next.epoch, __float_as_uint(c));
+        }
+    }
+}
+
 // ---- the scan ----------------------------------------------------------------------------------------------
 template <int kBlockT, int kMinWavesT, int kDepthT>
 struct Q8Cfg {
@@ -633,6 +678,10 @@ using DefaultQ8Cfg = Q8Cfg<512, 4, 2>;
 //
 // kLoneTail (a lone query whose caller waits on the host): the workgroup that finishes last merges the lists of
 // THIS launch into the caller's buffers and raises the completion word (kernels.hip.h, lone_tail).
+//
+// kQueryFromRow is a compile-time choice for the plain and the lone-tail forms only.  The STREAMED form exists once
+// (<Cfg, false, true>) and takes the run-time test q8_load_query makes anyway — query_ptr, or qarg.q where that is
+// null: its kernel slot went to scan_q8_kernel_pair (the library's kernel count is capped).
 template <typename Cfg, bool kQueryFromRow, bool kWithMerge, bool kLoneTail = false>
 __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel(
     const float* __restrict__ feats, const uint4* __restrict__ q8, int64_t n, int iters, int64_t row_base,
@@ -658,37 +707,13 @@ __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel(
         vb = blockIdx.x >= extra ? blockIdx.x - extra : nblocks + blockIdx.x;
         if (vb >= nblocks) {
             if (vb == nblocks) {
-                if (prev.lists)
-                    merge_body(s_mem.merge, prev.lists, prev.n_lists, prev.topk, static_cast<int64_t>(prev.topk),
-                               static_cast<int64_t>(0), prev.topk, prev.out_keys, static_cast<int64_t*>(nullptr),
-                               static_cast<float*>(nullptr), static_cast<int64_t>(0), static_cast<int64_t>(0),
-                               static_cast<int64_t>(0));
+                q8_ride_merge(s_mem.merge, prev);
             } else if (next.nbhd && vb == gridDim.x - 1u) {   // the next query's neighbourhood: read by the NEXT launch
-                nbhd_to_slot<kBlock>(feats, n, row_base, next.query_ptr, next.q, next.exclude_global, next.topk, next.epoch,
-                                     static_cast<unsigned long long*>(next.out), reinterpret_cast<int*>(s_mem.scan.cand), next.anchors);
+                q8_ride_nbhd<kBlock>(feats, n, row_base, next, reinterpret_cast<int*>(s_mem.scan.cand));
             } else {
                 static_assert(kBlock == kHalfSeedBlock && sizeof(s_mem.scan.cand) >= sizeof(int) * kBucketScratch, "the riders' geometry");
-                const int rider = static_cast<int>(vb - nblocks - 1u);
-                const bool bucketed = next.bucket.rows != nullptr;   // uniform
-                // (DROP_STORES, the test hook: the bucketed riders drop every store)
-                const Q8Query nq = bucketed ? q8_bucket_sample(feats, next.bucket, n, row_base, next.query_ptr, next.q, next.exclude_global,
-                                                               static_cast<unsigned long long*>(next.out), next.epoch, rider, next.n_wgs,
-                                                               next.debug_skip > 0, reinterpret_cast<int*>(s_mem.scan.cand), s_mem.scan.sel)
-                                            : q8_seed_rider(feats, q8, n, row_base, next, rider);
-                const int n_vals = bucketed ? kBucketPicks * kBucketGroups : next.regions * kHalfSeedWaves;
-                // Last rider out turns the sample into the cutoff (handoff.hip.h, sample_arrive_and_select: no device-wide
-                // fence under the scanners).  Values and cutoff carry the next query's epoch and the counter is never reset.
-                if (next.ctl) {   // uniform; null: nobody reads the sample inside this launch (small shards: the next launch selects)
-                    float v;
-                    if (sample_arrive_and_select<kBlock>(next.ctl, next.done_base, static_cast<unsigned>(next.n_wgs),
-                                                         static_cast<const unsigned long long*>(next.out), n_vals,
-                                                         next.topk, next.epoch, &s_mem.scan.count, &s_mem.scan.seeds, s_mem.scan.sel,
-                                                         reinterpret_cast<int*>(s_mem.scan.cand), v)) {
-                        // one margin below an EXACT score of a real row, two below an approximate one
-                        const float c = !nq.ok ? -__builtin_inff() : (next.exact != 0 ? v - nq.margin : v - 2.0f * nq.margin);
-                        if (threadIdx.x == 0) next.ctl->cutoff = tag_value(next.epoch, __float_as_uint(c));
-                    }
-                }
+                q8_ride_sample<kBlock>(feats, q8, n, row_base, next, static_cast<int>(vb - nblocks - 1u), reinterpret_cast<int*>(s_mem.scan.cand),
+                                       &s_mem.scan.count, &s_mem.scan.seeds, s_mem.scan.sel);
             }
             __syncthreads();
             MI355REC_PHASE(5);
@@ -745,7 +770,7 @@ __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel(
 #pragma unroll
     for (int d = 0; d < kDepth - 1; ++d) load_tile(ring[d], d);
     float q[kDim];
-    q8_load_query(kQueryFromRow ? query_ptr : nullptr, qarg.q, q);
+    q8_load_query((kQueryFromRow || kWithMerge) ? query_ptr : nullptr, qarg.q, q);
     const float qn = query_norm(q);
     const Q8Query hq = q8_query(q, qn);
     const Sample sample = sample_finish(sample_raw, epoch);
@@ -885,6 +910,327 @@ __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel(
     if constexpr (kLoneTail) lone_tail(s_mem.merge, &s_lone_flag, block_lists, topk, lone);
     __syncthreads();
     MI355REC_PHASE(4);
+}
+
+// ---- the scan for a PAIR of streamed queries -------------------------------------------------------------------------
+// Two streamed queries queued on a handle each stream the same replica: 120 MB at 10 M rows, against ~50 vector
+// instructions per lane and tile of work.  The pair form is scan_q8_kernel<.., kWithMerge> with TWO queries: a tile is
+// loaded once and q8_dot4 runs against query A and then query B over the same registers.  Everything a query owns it
+// owns here as well — cutoff, cut_d and thr, the candidate list in LDS and its compaction, the rescored count, the
+// per-workgroup output list (the pending fetch slot alone is shared) — and everything after a hit (cosine_score, pack_key,
+// block_rank_and_store) is the single form's, so the keys are the single form's bit for bit.  Both queries ask for the same topk <= kPairMaxTopk: the
+// candidate lists are a quarter of the single form's (compaction starts at max(2 topk, 256) = 256 keys either way).
+//
+// Workgroups, by virtual id: [0, S) scan; S and S + 1 merge the lists of the pair BEFORE (prev[0], prev[1]); then
+// next[0].n_wgs and next[1].n_wgs seed riders and next[0].nbhd + next[1].nbhd neighbourhood workgroups for the two
+// queries of the pair AFTER, each with its own sample buffer, SeedCtl and epoch.  As in the single form they hold the
+// FIRST block ids.
+constexpr int kPairMaxTopk = 128;
+
+// A wave-uniform value the compiler holds in a vector register (whatever float arithmetic or an LDS read produced it), moved
+// to a scalar one: two queries' digits, norms, cutoffs and thresholds are two dozen registers per lane otherwise.
+__device__ __forceinline__ int q8_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ float q8_uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+__device__ __forceinline__ uint64_t q8_uniform(uint64_t v) {
+    const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(static_cast<uint32_t>(v))));
+    const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(static_cast<uint32_t>(v >> 32))));
+    return (static_cast<uint64_t>(hi) << 32) | lo;
+}
+__device__ __forceinline__ Q8Query q8_uniform(const Q8Query& q) {
+    Q8Query r;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        r.hi[j] = q8_uniform(q.hi[j]);
+        r.lo[j] = q8_uniform(q.lo[j]);
+    }
+    r.inv = q.inv;
+    r.margin = q8_uniform(q.margin);
+    r.ok = q8_uniform(q.ok ? 1 : 0) != 0;
+    return r;
+}
+constexpr int kPairCandLimit = 2 * kPairMaxTopk;   // a tile is never entered with more candidates of one query
+
+template <int kBlockT, int kMinWavesT, int kDepthT>
+struct Q8PairCfg {
+    static constexpr int kBlock = kBlockT;
+    static constexpr int kMinWaves = kMinWavesT;
+    static constexpr int kDepth = kDepthT;
+    static constexpr int kTileRows = 4 * kBlockT;
+    static constexpr int kCandCap = kPairCandLimit + kTileRows;
+    static constexpr int kCandPerThread = (kCandCap + kBlockT - 1) / kBlockT;
+};
+using DefaultQ8PairCfg = Q8PairCfg<512, 4, 2>;
+
+template <typename Cfg>
+struct Q8PairSmemT {
+    uint64_t cand[2][Cfg::kCandCap];
+    SelectSmem sel;   // (the two queries select one after the other)
+    int count[2];
+    int seeds[2];
+    int rescored;
+};
+template <typename Cfg>
+union Q8PairOrMergeSmem {
+    Q8PairSmemT<Cfg> scan;
+    MergeSmemT<Cfg::kBlock, kRideMaxLists, kHalfRideSurvCap> merge;
+};
+
+// One query of a pair launch: what scan_q8_kernel takes as separate arguments.
+struct Q8PairArg {
+    QueryArg qarg;
+    const float* query_ptr;                       // null: the query is qarg.q
+    long long exclude_global;
+    uint64_t* block_lists;                        // [scanning workgroups][topk]
+    const unsigned long long* seed_vals;          // tagged with `epoch`
+    const unsigned long long* cutoff_ready;       // tagged; null: select from seed_vals here
+    int n_seed;                                   // negative: |n_seed| EXACT sample values
+    uint32_t epoch;
+};
+
+// What the workgroups of a pair launch that do not scan are given: indexed by a run-time (uniform) 0 / 1, so that every role
+// exists once in the kernel's code and reads the arguments of ITS query from the kernel's argument block.
+struct Q8PairSide {
+    PrevMerge prev[2];   // the lists of the pair before
+    NextSeed next[2];    // the queries of the pair after: the same n_wgs and nbhd in both
+};
+
+template <typename Cfg>
+__global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel_pair(
+    const float* __restrict__ feats, const uint4* __restrict__ q8, int64_t n, int iters, int64_t row_base, Q8PairArg arg_a,
+    Q8PairArg arg_b, int topk, unsigned long long* __restrict__ rescored /* [scanning workgroups] */, Q8PairSide side) {
+    constexpr int kBlock = Cfg::kBlock;
+    __shared__ Q8PairOrMergeSmem<Cfg> s_mem;
+    const unsigned riders = static_cast<unsigned>(side.next[0].n_wgs), nbhds = static_cast<unsigned>(side.next[0].nbhd);
+    const unsigned extra = 2u + 2u * (riders + nbhds);
+    const unsigned nblocks = gridDim.x - extra;   // scanning workgroups
+    const unsigned vb = blockIdx.x >= extra ? blockIdx.x - extra : nblocks + blockIdx.x;
+    if (vb >= nblocks) {
+        static_assert(kBlock == kHalfSeedBlock && sizeof(s_mem.scan.cand) >= sizeof(int) * kBucketScratch &&
+                          sizeof(s_mem.scan.cand) >= sizeof(int) * Nbhd<kBlock>::kScratch, "the riders' geometry");
+        int* const s_scratch = reinterpret_cast<int*>(s_mem.scan.cand);
+        const unsigned e = vb - nblocks;   // uniform
+        if (e < 2u) {
+            q8_ride_merge(s_mem.merge, side.prev[e]);
+        } else if (e < 2u + 2u * riders) {
+            const unsigned which = e - 2u >= riders ? 1u : 0u;
+            q8_ride_sample<kBlock>(feats, q8, n, row_base, side.next[which], static_cast<int>(e - 2u - which * riders), s_scratch,
+                                   &s_mem.scan.count[0], &s_mem.scan.seeds[0], s_mem.scan.sel);
+        } else {
+            q8_ride_nbhd<kBlock>(feats, n, row_base, side.next[e - 2u - 2u * riders], s_scratch);
+        }
+        __syncthreads();
+        return;
+    }
+    Q8PairSmemT<Cfg>* const sm = &s_mem.scan;
+    SelectSmem& s_sel = sm->sel;
+
+    const unsigned bid = vb;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+
+    const int64_t n_quads = (n + 3) >> 2;
+    const int64_t last_quad = n_quads - 1;
+    const int64_t quad_begin = static_cast<int64_t>(bid) * kBlock + tid;
+    const int64_t quad_stride = static_cast<int64_t>(nblocks) * kBlock;
+
+    auto load_tile = [&](HalfTile& dst, int it) {
+        int64_t quad = quad_begin + static_cast<int64_t>(it) * quad_stride;
+        quad = quad < n_quads ? quad : last_quad;   // unconditional prefetch (see scan_kernel)
+        const uint4* p = q8 + quad * 3;
+        dst.t0 = p[0];
+        dst.t1 = p[1];
+        dst.t2 = p[2];
+    };
+
+    // What one query of the pair owns (scan_q8_kernel's locals).
+    struct Mine {
+        float q[kDim];
+        float qn;
+        Q8Query hq;
+        float cutoff;
+        uint64_t thr;
+        int cut_d;
+        int n_rescored;   // wave-uniform
+        uint64_t* s_cand;
+        int* s_count;
+    };
+    Mine A, B;
+    A.s_cand = sm->cand[0];
+    B.s_cand = sm->cand[1];
+    A.s_count = &sm->count[0];
+    B.s_count = &sm->count[1];
+
+    // as the single form: the finished cutoffs — or the sample values — are asked for first, then the tile, then the queries
+    constexpr int kDepth = Cfg::kDepth;
+    const unsigned long long nbhd_raw_a = arg_a.seed_vals[kNbhdSlot], nbhd_raw_b = arg_b.seed_vals[kNbhdSlot];   // (scalar loads)
+    float left_a = 0.0f, left_b = 0.0f;
+    SampleRaw raw_a, raw_b;
+#pragma unroll
+    for (int r = 0; r < kHalfSeedPerThread; ++r) raw_a.t[r] = raw_b.t[r] = 0ull;
+    const int n_sample_a = arg_a.n_seed < 0 ? -arg_a.n_seed : arg_a.n_seed, n_sample_b = arg_b.n_seed < 0 ? -arg_b.n_seed : arg_b.n_seed;
+    if (arg_a.cutoff_ready) left_a = untag_cutoff(*arg_a.cutoff_ready, arg_a.epoch);   // uniform
+    else raw_a = sample_request<kBlock>(arg_a.seed_vals, n_sample_a);
+    if (arg_b.cutoff_ready) left_b = untag_cutoff(*arg_b.cutoff_ready, arg_b.epoch);   // uniform
+    else raw_b = sample_request<kBlock>(arg_b.seed_vals, n_sample_b);
+    HalfTile ring[kDepth];
+#pragma unroll
+    for (int d = 0; d < kDepth - 1; ++d) load_tile(ring[d], d);
+    q8_load_query(arg_a.query_ptr, arg_a.qarg.q, A.q);
+    q8_load_query(arg_b.query_ptr, arg_b.qarg.q, B.q);
+    A.qn = q8_uniform(query_norm(A.q));
+    B.qn = q8_uniform(query_norm(B.q));
+    A.hq = q8_uniform(q8_query(A.q, A.qn));
+    B.hq = q8_uniform(q8_query(B.q, B.qn));
+
+    if (tid == 0) {
+        sm->count[0] = sm->count[1] = 0;
+        sm->seeds[0] = sm->seeds[1] = 0;
+        sm->rescored = 0;
+    }
+    __syncthreads();
+    // ---- the launch-wide cutoffs (while the first tiles are in flight), one query after the other
+    auto start = [&](Mine& m, const Q8PairArg& arg, const SampleRaw& raw, int n_sample, float left, unsigned long long nbhd_raw, int* s_seeds) {
+        if (arg.cutoff_ready) {   // uniform
+            m.cutoff = left;
+        } else {
+            const Sample sample = sample_finish(raw, arg.epoch);
+            m.cutoff = q8_cutoff_from_sample<kBlock>(sample, n_sample, topk, arg.n_seed < 0, m.hq, s_seeds, s_sel, reinterpret_cast<int*>(m.s_cand));
+        }
+        m.thr = 0;
+        if (const uint32_t nbv = untag_value(nbhd_raw, arg.epoch)) {   // uniform: at least topk rows score >= this EXACT bound
+            m.thr = (static_cast<uint64_t>(nbv) << 32) - 1ull;         // (a key AT the bound passes: key > thr)
+            if (m.hq.ok) {
+                const float nb_cut = ordered_to_score(nbv) - m.hq.margin;
+                m.cutoff = nb_cut > m.cutoff ? nb_cut : m.cutoff;
+            }
+        }
+        m.cutoff = q8_uniform(m.cutoff);
+        m.thr = q8_uniform(m.thr);
+        m.cut_d = q8_uniform(q8_threshold(m.cutoff));
+        m.n_rescored = 0;
+    };
+    start(A, arg_a, raw_a, n_sample_a, left_a, nbhd_raw_a, &sm->seeds[0]);
+    __syncthreads();   // (B's selection shares s_sel with A's)
+    start(B, arg_b, raw_b, n_sample_b, left_b, nbhd_raw_b, &sm->seeds[1]);
+    int compact_at = 2 * topk > 256 ? 2 * topk : 256;
+    if (compact_at > kPairCandLimit) compact_at = kPairCandLimit;
+
+    auto append = [&](Mine& m, int64_t exclude_global, bool have, const Row& row, int64_t r) {
+        const float s = cosine_score(m.q, m.qn, row);
+        const int64_t g = row_base + r;
+        uint64_t key = pack_key(s, static_cast<uint32_t>(g));
+        if (g == exclude_global) key = 0;
+        const bool pass = have && key > m.thr;
+        const uint64_t ballot = __ballot(pass);
+        if (ballot) {
+            int base = 0;
+            if (lane == 0) base = atomicAdd(m.s_count, __popcll(ballot));
+            base = __builtin_amdgcn_readfirstlane(base);
+            const int pos = base + lanes_below(ballot);
+            if (pass) m.s_cand[pos] = key;
+        }
+    };
+    // The pending fetch slot (scan_q8_kernel: issued when a candidate row is found, consumed one tile later) is SHARED: one
+    // row per lane, with a bit per query it is a candidate of — a row both queries cannot rule out is fetched once.  A lane's
+    // further candidate rows of the tile, of either query, are scored on the spot (rare).
+    Row pend;
+    pend.a = pend.b = pend.c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    int64_t pend_r = 0;
+    uint32_t pend_for = 0u;   // bit 0: query A, bit 1: query B
+    auto score_row = [&](uint32_t who, const Row& row, int64_t r) {
+        if (__ballot((who & 1u) != 0u)) append(A, arg_a.exclude_global, (who & 1u) != 0u, row, r);
+        if (__ballot((who & 2u) != 0u)) append(B, arg_b.exclude_global, (who & 2u) != 0u, row, r);
+    };
+    auto consume = [&]() {
+        if (__ballot(pend_for != 0u)) score_row(pend_for, pend, pend_r);
+        pend_for = 0u;
+    };
+    auto fetch = [&](uint32_t mask_a, uint32_t mask_b, int64_t r0) {
+        const uint32_t both = mask_a | mask_b;
+        if (!__ballot(both != 0u)) return;   // uniform
+        auto whose = [&](int u) { return ((mask_a >> u) & 1u) | (((mask_b >> u) & 1u) << 1); };
+        // (the books stay per query: every row a query sends to the exact chain counts for that query)
+        auto count = [&](uint32_t who) {
+            A.n_rescored += __popcll(__ballot((who & 1u) != 0u));
+            B.n_rescored += __popcll(__ballot((who & 2u) != 0u));
+        };
+        const int first = both ? __builtin_ctz(both) : 0;
+        pend_r = r0 + first;
+        pend = load_row(feats, both ? pend_r : static_cast<int64_t>(0));   // (lanes without a candidate re-read row 0: one cached line)
+        pend_for = both ? whose(first) : 0u;
+        count(pend_for);
+        uint32_t rest = both & (both - 1u);
+        while (__ballot(rest != 0u)) {   // uniform, rare
+            const int u = rest ? __builtin_ctz(rest) : 0;
+            const uint32_t who = rest ? whose(u) : 0u;
+            count(who);
+            const Row extra = load_row(feats, rest ? r0 + u : static_cast<int64_t>(0));
+            score_row(who, extra, r0 + u);
+            rest &= rest - 1u;
+        }
+    };
+    auto tighten = [&](Mine& m) {
+        const uint64_t local_thr = compact_candidates<kBlock, Cfg::kCandPerThread>(m.s_cand, m.s_count, topk, false, s_sel);
+        if (local_thr > m.thr) {
+            m.thr = q8_uniform(local_thr);
+            if (m.hq.ok) {
+                const float local_cut = ordered_to_score(static_cast<uint32_t>(m.thr >> 32)) - m.hq.margin;
+                m.cutoff = q8_uniform(local_cut > m.cutoff ? local_cut : m.cutoff);
+                m.cut_d = q8_uniform(q8_threshold(m.cutoff));
+            }
+        }
+    };
+
+    auto process_tile = [&](const HalfTile& t, int it) {
+        const int64_t quad = quad_begin + static_cast<int64_t>(it) * quad_stride;
+        const int64_t r0 = quad * 4;
+        uint32_t hit_a = 0u, hit_b = 0u;   // which of the lane's four rows each query cannot rule out
+        {
+            int a[4];
+            bool special[4];
+            q8_dot4(A.hq, t, a, special);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) hit_a |= (special[u] | (a[u] >= A.cut_d)) ? (1u << u) : 0u;
+            q8_dot4(B.hq, t, a, special);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) hit_b |= (special[u] | (a[u] >= B.cut_d)) ? (1u << u) : 0u;
+        }
+        const uint64_t maybe = __ballot((hit_a | hit_b) != 0u);
+        consume();   // the rows fetched while the previous tile was scanned
+        if (maybe) {   // uniform
+            const int64_t left = n - r0;
+            const int valid = quad < n_quads ? (left < 4 ? static_cast<int>(left) : 4) : 0;
+            const uint32_t inside = (1u << valid) - 1u;   // (padding of the last quad, the clamped prefetch past the end)
+            fetch(hit_a & inside, hit_b & inside, r0);
+        }
+        __syncthreads();
+        const int ca = *A.s_count, cb = *B.s_count;
+        __syncthreads();
+        if (ca >= compact_at) tighten(A);   // uniform
+        if (cb >= compact_at) tighten(B);   // uniform
+    };
+
+    for (int it = 0; it < iters; it += kDepth) {
+#pragma unroll
+        for (int sidx = 0; sidx < kDepth; ++sidx) {
+            load_tile(ring[(sidx + kDepth - 1) % kDepth], it + sidx + kDepth - 1);
+            if (it + sidx < iters) process_tile(ring[sidx], it + sidx);  // uniform
+        }
+    }
+    consume();   // the last tile's fetches
+
+    if (lane == 0 && A.n_rescored + B.n_rescored) atomicAdd(&sm->rescored, A.n_rescored + B.n_rescored);
+    __syncthreads();
+    if (tid == 0) rescored[bid] += static_cast<unsigned long long>(sm->rescored);   // launches of a handle are stream-ordered
+    auto finish = [&](Mine& m, uint64_t* block_lists) {
+        if (*m.s_count > kRankCountMax && *m.s_count > topk)  // uniform
+            compact_candidates<kBlock, Cfg::kCandPerThread>(m.s_cand, m.s_count, topk, false, s_sel);
+        __syncthreads();
+        block_rank_and_store<kBlock>(m.s_cand, *m.s_count, block_lists + static_cast<int64_t>(bid) * topk, topk);
+        __syncthreads();
+    };
+    finish(A, arg_a.block_lists);
+    finish(B, arg_b.block_lists);
 }
 
 }  // namespace mi355

@@ -154,6 +154,7 @@ int create_on(const float* feats_host, int64_t n, int dim, const int* devices, i
                                  : mi355rec_create(s.hi > s.lo ? feats_host + s.lo * MI355REC_DIM : nullptr, s.hi - s.lo, dim, s.device,
                                                    s.lo, &s.engine);
         if (rc != MI355REC_OK) return bail(sfail(nullptr, rc, "shard %d on device %d: %s", r, s.device, mi355rec_last_global_error()));
+        (void)mi355rec_set_stream_pairing(s.engine, MI355REC_PAIRING_OFF);   // (a node's windows run one call behind: its shards do not pair)
         // The shard works on the stream its engine was created with: for a lane that is the stream mi355rec_create_lane CHOSE
         // because kernels on it run beside the first replica's (a hardware queue of its own) — a stream made here would be
         // bound to whichever queue is next, possibly the same one.

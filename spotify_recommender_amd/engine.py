@@ -1163,6 +1163,20 @@ class NodeEngine(_RequestFamily):
         return (self._lib.mi355rec_sharded_note(self._h) or b"").decode("utf-8", "replace")
 
 
+# ---- pairs of streamed queries -----------------------------------------------
+
+def set_stream_pairing(engine: "CosineEngine", mode: int) -> None:
+    """capi.PAIRING_AUTO / PAIRING_OFF / PAIRING_ON for `engine` (mi355rec_set_stream_pairing): whether two queued streamed
+    queries over the 8-bit replica that ask for the same topn <= 128 share ONE pass over it.  The stream then runs up to
+    three calls behind instead of one; results are unchanged.  A lane inherits the mode when it is created."""
+    capi.check(engine._lib.mi355rec_set_stream_pairing(engine._h, int(mode)), engine._h)
+
+
+def stream_pair_launches(engine: "CosineEngine") -> int:
+    """Pair launches of `engine` since create (mi355rec_stats_t::stream_pair_launches)."""
+    return int(engine.stats().stream_pair_launches)
+
+
 # ---- packed keys on the host (pure bit manipulation, mirrors kernels.hip.h) ----
 
 def unpack_keys(keys) -> Tuple[np.ndarray, np.ndarray]:
@@ -1227,6 +1241,10 @@ class ShardedEngine:
         self.device = dev
         self._lanes = [local]
         self._lane_streams = [None]
+        # The windowed stream gathers a window a fixed number of calls into the next one: it counts on the rank's streamed
+        # queries running ONE call behind, so the rank's engine does not pair them (its lanes inherit that).
+        if isinstance(local, CosineEngine):
+            set_stream_pairing(local, capi.PAIRING_OFF)
         if int(lanes) > 1 and hasattr(local, "lane"):
             self._lanes = [local] + [local.lane() for _ in range(int(lanes) - 1)]
             self._lane_streams = [ln.own_stream() for ln in self._lanes]
