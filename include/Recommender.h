@@ -222,6 +222,15 @@ public:
     };
     std::vector<int> recommendQuery(const Query& query);
 
+    // Extension: candidate scores (include/mi355rec_diag.h, "CANDIDATE SCORES").  scoreSongs gives what `query` is worth at every
+    // song of songIndices, in their order (duplicates allowed, at most 1 048 576): the score (with euclidean the distance)
+    // recommendQuery would report for that song, bit for bit; for a blender that mixes a first stage's score with this one, or "how
+    // similar is song A to song B".  A song the query can never return (one of query.songs or alsoExclude, outside where or genreIds,
+    // rejected by the row set) gets NaN, and 0 in *admissible (1 otherwise) where that is given.  topN is ignored; diverse and
+    // maxPerArtist are refused with a message and {} (a re-ranked order has no value per song), as is an index outside the songs.
+    // The row set of setRowSet applies; the list of setCandidates does not.  lastScores() is left as it was.
+    std::vector<float> scoreSongs(const Query& query, const std::vector<int64_t>& songIndices, std::vector<char>* admissible = nullptr);
+
     // Extension: in-place updates (include/mi355rec_diag.h, "ROW UPDATES").  updateSongs gives the songs at `indices` (distinct,
     // inside the catalogue) new features: 12 floats per song in Song.h order, features[12 * i ..] for indices[i].  Every later
     // recommendation answers as if the catalogue had been initialised with the new features; ids, names, genre ids, groups,

@@ -953,7 +953,8 @@ int mi355rec_sharded_query_distance_request_ext(mi355rec_sharded_t* h, const mi3
  * kernel sits on its register budget: 4 entries per thread need scratch (docs/LAB_NOTES.md).  Requests without a list are within the
  * parent build's own spread (profiles/r19_candidates_ab.json).
  * Not served: routing a small ONLY row set to the gather by itself; lists on the single-query, streamed, batched and label-only
- * routes; a pre-filter for the gather (every listed row takes the exact chain); scores of candidates outside the top-N. */
+ * routes; a pre-filter for the gather (every listed row takes the exact chain).  (Scores of candidates outside the top-N:
+ * CANDIDATE SCORES below.) */
 #define MI355REC_MAX_CANDIDATES 1048576
 int mi355rec_query_playlist_request_candidates(mi355rec_t* h, const mi355rec_playlist_query_t* query, const mi355rec_request_ext_t* ext,
                                                const int64_t* candidates, int64_t n_candidates, const mi355rec_playlist_result_t* result);
@@ -966,6 +967,45 @@ int mi355rec_sharded_query_distance_request_candidates(mi355rec_sharded_t* h, co
                                                        const mi355rec_request_ext_t* ext, const int64_t* candidates, int64_t n_candidates,
                                                        const mi355rec_distance_result_t* result);
 int mi355rec_candidates_counters(const mi355rec_t* h, int64_t* requests, int64_t* rows_gathered);
+
+/* CANDIDATE SCORES: "how does this request value these candidates", for a blender or re-ranker that mixes the first stage's own
+ * score with the engine's and so needs the value of EVERY candidate, not of the N best.  The calls take what the _candidates calls
+ * take, with two arrays of n_candidates entries in place of the result struct.
+ * CONTRACT, bit for bit, for every i in [0, n_candidates), g = candidates[i]: g is ADMISSIBLE iff the matching _candidates call
+ * with the same query and ext and the one-entry list {g} returns g.  Then out_value[i] holds the bits of that call's out_score[0]
+ * (out_distance[0] = sqrtf(m) for the distance call) and out_admissible[i] is 1.  Otherwise out_value[i] is the quiet NaN
+ * 0x7fc00000 and out_admissible[i] is 0: an excluded id, a member given by row, a row that the row set, the label set or the
+ * filter rejects, a distance that is not finite and, on a single handle, an id outside [row_base, row_base + n).  Output is in
+ * list order; duplicates each get their value; a score of -0.0 reports as +0.0; weights, MI355REC_PQ_PRIOR (the value is v),
+ * feature scales and both row-set modes keep their meaning.  The result does not depend on replica mode, lane, shard count or
+ * placement.
+ * ARGUMENTS: every check and message of the _candidates call first (topn included: one struct serves both calls; topn is otherwise
+ * unused).  Then: MI355REC_PQ_DIVERSE and MI355REC_PQ_CAPPED are INVALID_ARG (a re-ranked order has no per-row value); a NULL
+ * out_value with n_candidates > 0 is INVALID_ARG; out_admissible may be NULL.  n_candidates == 0 returns OK, writes nothing and
+ * launches nothing.
+ * DEVICE (csrc/playlist.hip.h, "CANDIDATE SCORES"): no new kernel: the gather launch with topk == 0 stores the key of entry e of
+ * the shard's sorted, distinct list (or 0) at index e of a per-handle buffer of 8 B per entry, which grows on demand, and selects
+ * nothing; no merge is launched.  The host copies the buffer back through a pinned one on the handle's stream and unpacks it
+ * through the list-order map of csrc/candidates.h.  A scoring launch is a gather launch: it counts into
+ * mi355rec_candidates_counters and rows_exact as the _candidates call with the same list does.
+ * Measured on one MI355X at 10 M uniform rows, K = 1 by row, replica on, the list ascending (tools/run_candidate_scores.py,
+ * profiles/r21_candidate_scores.json; p50 per call beside the _candidates top-100 call on the same list): 32.9 us against 40.2 at
+ * 100 ids, 35.9 / 43.8 at 1 000, 84.3 / 67.2 at 10 000, 281.8 / 140.3 at 100 000, 2 225 / 800 at 1 000 000: faster while the saved
+ * merge launch shows, slower from 10 000 ids, where the host's work per id (the list-order map, the copy back, the unpack) outgrows
+ * it.  Requests without a list and _candidates requests are within the parent build's own spread (profiles/r21_candidate_scores_ab.json).
+ * Not served: scores on the single-query, streamed, batched and label-only routes; per-member scores; asynchronous variants. */
+int mi355rec_score_playlist_request_candidates(mi355rec_t* h, const mi355rec_playlist_query_t* query, const mi355rec_request_ext_t* ext,
+                                               const int64_t* candidates, int64_t n_candidates, float* out_value,
+                                               uint8_t* out_admissible /* may be NULL */);
+int mi355rec_score_distance_request_candidates(mi355rec_t* h, const mi355rec_distance_query_t* query, const mi355rec_request_ext_t* ext,
+                                               const int64_t* candidates, int64_t n_candidates, float* out_distance,
+                                               uint8_t* out_admissible /* may be NULL */);
+int mi355rec_sharded_score_playlist_request_candidates(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
+                                                       const mi355rec_request_ext_t* ext, const int64_t* candidates, int64_t n_candidates,
+                                                       float* out_value, uint8_t* out_admissible /* may be NULL */);
+int mi355rec_sharded_score_distance_request_candidates(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
+                                                       const mi355rec_request_ext_t* ext, const int64_t* candidates, int64_t n_candidates,
+                                                       float* out_distance, uint8_t* out_admissible /* may be NULL */);
 
 /* ROW UPDATES (the reference lists "Real-time Updates: Incremental index updates" among its extensions): songs are re-analysed
  * and corrected every day, and a changed row should not cost a rebuild of everything the handle keeps beside the rows.

@@ -299,6 +299,15 @@ SIGNATURES = {
     "mi355rec_sharded_query_distance_request_candidates": (c_int, [c_void_p, POINTER(DistanceQuery), POINTER(RequestExt), c_void_p, c_int64,
                                                                    POINTER(DistanceResult)]),
     "mi355rec_candidates_counters": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),
+    # CANDIDATE SCORES: the same request and list; every listed row's value (float32) and admissible flag (uint8, may be NULL) in list order
+    "mi355rec_score_playlist_request_candidates": (c_int, [c_void_p, POINTER(PlaylistQuery), POINTER(RequestExt), c_void_p, c_int64,
+                                                           c_void_p, c_void_p]),
+    "mi355rec_score_distance_request_candidates": (c_int, [c_void_p, POINTER(DistanceQuery), POINTER(RequestExt), c_void_p, c_int64,
+                                                           c_void_p, c_void_p]),
+    "mi355rec_sharded_score_playlist_request_candidates": (c_int, [c_void_p, POINTER(PlaylistQuery), POINTER(RequestExt), c_void_p, c_int64,
+                                                                   c_void_p, c_void_p]),
+    "mi355rec_sharded_score_distance_request_candidates": (c_int, [c_void_p, POINTER(DistanceQuery), POINTER(RequestExt), c_void_p, c_int64,
+                                                                   c_void_p, c_void_p]),
     # ROW UPDATES: rows change in place, every route answers as a freshly created handle would
     "mi355rec_update_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "mi355rec_sharded_update_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

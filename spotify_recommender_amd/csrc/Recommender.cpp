@@ -429,7 +429,14 @@ bool makeFilter(const std::vector<Recommender::FeatureRange>& where, mi355rec_fi
 
 // Recommender::recommendQuery: every call that reaches the playlist request or the distance request, and the one place that does.
 // rangesLast: `where` is looked at after the songs, topN and the scales instead of first (recommendScaled's order of messages).
-std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, bool rangesLast) {
+// score (scoreSongs; null: a recommendation): the request's value of every song of score->songs instead of its top-N.
+struct ScoreSongs {
+    const std::vector<int64_t>& songs;
+    std::vector<float> values;
+    std::vector<uint8_t> admissible;
+    bool ok = false;   // the engine has answered: values and admissible hold one entry per song
+};
+std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, bool rangesLast, ScoreSongs* score = nullptr) {
     if (!q.weights.empty() && q.weights.size() != q.songs.size()) {
         std::cerr << "Error: " << q.weights.size() << " weights for " << q.songs.size() << " songs (one weight per song, or none)" << std::endl;
         return {};
@@ -455,7 +462,7 @@ std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, 
                 std::cerr << "Error: Invalid song index: " << i << std::endl;
                 return {};
             }
-    int topN = q.topN;
+    int topN = score ? 1 : q.topN;   // (scoreSongs ignores topN)
     if (topN <= 0) {
         std::cerr << "Error: topN must be positive" << std::endl;
         return {};
@@ -471,6 +478,10 @@ std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, 
     // order for any pool, so no pool is taken and no re-rank launched (the diversified overload without either keeps its launch).
     const bool plainOrder = q.lambda == 1.0f && (!q.genreIds.empty() || withPrior);
     const bool rerank = capped || (q.diverse && !plainOrder);   // (a cap alone: lambda 1, the plain order with the cap)
+    if (score && (q.diverse || capped)) {
+        std::cerr << "Error: scoreSongs takes no diversity and no cap (a re-ranked order has no value per song)" << std::endl;
+        return {};
+    }
     if (q.euclidean && (!q.weights.empty() || rerank || withPrior)) {
         std::cerr << "Error: the Euclidean metric takes no weights, diversity, cap or prior weight" << std::endl;
         return {};
@@ -517,9 +528,12 @@ std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, 
         res.out_idx = impl->idxBuf.data();
         res.out_distance = impl->scoreBuf.data();
         res.out_count = &count;
-        rc = impl->hasCandidates ? mi355rec_sharded_query_distance_request_candidates(impl->engine, &d, &ext, impl->candidates.data(),
-                                                                                     static_cast<int64_t>(impl->candidates.size()), &res)
-                                 : mi355rec_sharded_query_distance_request_ext(impl->engine, &d, &ext, &res);
+        rc = score ? mi355rec_sharded_score_distance_request_candidates(impl->engine, &d, &ext, score->songs.data(),
+                                                                        static_cast<int64_t>(score->songs.size()), score->values.data(),
+                                                                        score->admissible.data())
+             : impl->hasCandidates ? mi355rec_sharded_query_distance_request_candidates(impl->engine, &d, &ext, impl->candidates.data(),
+                                                                                       static_cast<int64_t>(impl->candidates.size()), &res)
+                                   : mi355rec_sharded_query_distance_request_ext(impl->engine, &d, &ext, &res);
     } else {
         mi355rec_playlist_query_t p{};
         shared(p);
@@ -535,12 +549,19 @@ std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, 
         res.out_idx = impl->idxBuf.data();
         res.out_score = impl->scoreBuf.data();
         res.out_count = &count;
-        rc = impl->hasCandidates ? mi355rec_sharded_query_playlist_request_candidates(impl->engine, &p, &ext, impl->candidates.data(),
-                                                                                     static_cast<int64_t>(impl->candidates.size()), &res)
-                                 : mi355rec_sharded_query_playlist_request_ext(impl->engine, &p, &ext, &res);
+        rc = score ? mi355rec_sharded_score_playlist_request_candidates(impl->engine, &p, &ext, score->songs.data(),
+                                                                        static_cast<int64_t>(score->songs.size()), score->values.data(),
+                                                                        score->admissible.data())
+             : impl->hasCandidates ? mi355rec_sharded_query_playlist_request_candidates(impl->engine, &p, &ext, impl->candidates.data(),
+                                                                                       static_cast<int64_t>(impl->candidates.size()), &res)
+                                   : mi355rec_sharded_query_playlist_request_ext(impl->engine, &p, &ext, &res);
     }
     if (rc != MI355REC_OK) {
         std::cerr << "Error: " << mi355rec_sharded_last_error(impl->engine) << std::endl;
+        return {};
+    }
+    if (score) {
+        score->ok = true;
         return {};
     }
     std::vector<int> results(static_cast<size_t>(count));
@@ -564,6 +585,20 @@ Recommender::Query playlistOf(const std::vector<int>& songIndices, int topN, con
 }  // namespace
 
 std::vector<int> Recommender::recommendQuery(const Query& query) { return runQuery(impl_, query, false); }
+
+std::vector<float> Recommender::scoreSongs(const Query& query, const std::vector<int64_t>& songIndices, std::vector<char>* admissible) {
+    if (admissible) admissible->clear();
+    for (int64_t i : songIndices)
+        if (impl_->initialized && (i < 0 || i >= impl_->numSongs)) {
+            std::cerr << "Error: Invalid song index: " << i << std::endl;
+            return {};
+        }
+    ScoreSongs score{songIndices, std::vector<float>(songIndices.size()), std::vector<uint8_t>(songIndices.size())};
+    runQuery(impl_, query, false, &score);
+    if (!score.ok) return {};
+    if (admissible) admissible->assign(score.admissible.begin(), score.admissible.end());
+    return score.values;
+}
 
 std::vector<int> Recommender::recommendForPlaylist(const std::vector<int>& songIndices, int topN, const std::vector<int>& alsoExclude) {
     return recommendQuery(playlistOf(songIndices, topN, {}, {}, alsoExclude));

@@ -84,6 +84,19 @@ inline Reduced reduce(const int64_t* ids, int64_t n, int64_t lo, int64_t hi, uin
     return r;
 }
 
+// CANDIDATE SCORES: from list order to the reduced list.  rows[0..red.count) and `red` are what reduce made of the same ids, lo and hi;
+// pos holds n entries: pos[i] = the index of ids[i] - lo in rows, or -1 when ids[i] is outside [lo, hi).  One pass when the list
+// came strictly ascending (the in-range ids ARE the reduced list, in order), a binary search per id otherwise.
+inline void positions(const int64_t* ids, int64_t n, int64_t lo, int64_t hi, const uint32_t* rows, const Reduced& red, int64_t* pos) {
+    int64_t next = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t id = ids[i];
+        if (id < lo || id >= hi) pos[i] = -1;
+        else if (red.ascending) pos[i] = next++;
+        else pos[i] = std::lower_bound(rows, rows + red.count, static_cast<uint32_t>(id - lo)) - rows;   // (found: reduce kept it)
+    }
+}
+
 // A node handle's checked list for the shard [lo, hi): the ids of that range, global, in list order (duplicates stay: the shard's
 // own reduce drops them).  out is cleared first.
 inline void split(const int64_t* ids, int64_t n, int64_t lo, int64_t hi, std::vector<int64_t>* out) {

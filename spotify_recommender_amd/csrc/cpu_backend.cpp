@@ -397,11 +397,13 @@ int node_query_labels(Node* h, const float* q12, int64_t exclude, const int32_t*
     return MI355REC_OK;
 }
 
-int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlist::Outputs& out, const char** why) {
+// The key of every row of the catalogue under the request, 0 for a row that is not admissible (keys[i]: row i), and how many are:
+// what node_query_mean selects from and node_score_rows reads.
+static int mean_keys(Node* h, const mi355playlist::Request& r, std::vector<uint64_t>& keys, int64_t* admissible, const char** why) {
     const float* members = r.members;
     const float* weights = r.weights;
     const mi355rec_filter_t* filter = r.filter;
-    const int k = r.k, topn_asked = r.topn;
+    const int k = r.k;
     if (r.n_labels > 0 && !h->has_labels) {   // "PLAYLIST REQUESTS": a label set needs labels
         *why = "this handle has no labels (mi355rec_sharded_set_labels)";
         return MI355REC_ERR_INVALID_ARG;
@@ -418,7 +420,6 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
     const int64_t n = c->n;
     std::vector<float> qn(static_cast<size_t>(k));
     for (int m = 0; m < k; ++m) qn[static_cast<size_t>(m)] = query_norm(members + m * kDim);
-    std::vector<uint64_t> keys;
     std::vector<int64_t> excl;
     try {
         excl.assign(r.exclude, r.exclude + r.n_exclude);
@@ -537,6 +538,16 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
             avail += key != 0;
         }
     }
+    *admissible = avail;
+    return MI355REC_OK;
+}
+
+int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlist::Outputs& out, const char** why) {
+    const int topn_asked = r.topn;
+    std::vector<uint64_t> keys;
+    int64_t avail = 0;
+    const int rc = mean_keys(h, r, keys, &avail, why);
+    if (rc) return rc;
     const int count = static_cast<int>(topn_asked < avail ? topn_asked : avail);
     std::partial_sort(keys.begin(), keys.begin() + count, keys.end(), std::greater<uint64_t>());
     for (int i = 0; i < count; ++i) {
@@ -545,6 +556,20 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
     }
     mi355playlist::pad(out, count, topn_asked, count);
     if (r.report_distance) mi355playlist::scores_to_distances(out, topn_asked);
+    return MI355REC_OK;
+}
+
+// CANDIDATE SCORES (include/mi355rec_diag.h): the same keys, read at every listed id in list order (the ids are checked: rows of the catalogue).
+int node_score_rows(Node* h, const mi355playlist::Request& r, const mi355playlist::ScoreOutputs& out, const char** why) {
+    std::vector<uint64_t> keys;
+    int64_t avail = 0;
+    const int rc = mean_keys(h, r, keys, &avail, why);
+    if (rc) return rc;
+    for (int64_t i = 0; i < r.n_candidates; ++i) {
+        const uint64_t key = keys[static_cast<size_t>(r.candidates[i])];
+        if (key) mi355playlist::score_some(r, out, i, unordered(static_cast<uint32_t>(key >> 32)) + 0.0f);
+        else mi355playlist::score_none(out, i);
+    }
     return MI355REC_OK;
 }
 

@@ -66,6 +66,9 @@ int node_query_labels(Node* h, const float* q12, int64_t exclude, const int32_t*
 // PLAYLISTS": score = fl(sum_k fl(w_k c_k)) / fl(sum_k |w_k|)).  The request has been checked by the caller
 // (playlist_request.h); the diversified fields are not read.
 int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlist::Outputs& out, const char** why);
+// CANDIDATE SCORES (include/mi355rec_diag.h): the value of every listed row under the same request (members by value, checked; r.listed
+// with checked ids), in list order, by node_query_mean's own arithmetic.
+int node_score_rows(Node* h, const mi355playlist::Request& r, const mi355playlist::ScoreOutputs& out, const char** why);
 // DIVERSIFIED TOP-N (include/mi355rec_diag.h): the top-`pool` of node_query_mean re-ranked by maximal marginal relevance.
 // out.score and out.mmr may be null.
 int node_query_mean_diverse(Node* h, const mi355playlist::Request& r, const mi355playlist::Outputs& out, const char** why);

@@ -42,6 +42,13 @@ struct mi355rec_playlist {
     uint32_t* d_cand = nullptr;
     int64_t cand_cap = 0;
     int64_t cand_requests = 0, cand_rows = 0;   // mi355rec_candidates_counters
+    // CANDIDATE SCORES (playlist.hip.h, "CANDIDATE SCORES"): the key of every entry of d_cand, stored by the scoring launch, copied back
+    // into the pinned h_cand_keys on the handle's stream.  Both hold cand_key_cap entries and grow with the list's buffers.
+    uint64_t* h_cand_keys = nullptr;
+    uint64_t* d_cand_keys = nullptr;
+    int64_t cand_key_cap = 0;
+    std::vector<int64_t> cand_pos;              // list order -> entry of d_cand (candidates.h, positions) ...
+    int64_t cand_entries = 0;                   // ... of which the scoring launch was given this many
 };
 
 namespace {
@@ -84,6 +91,8 @@ void free_playlist(mi355rec_playlist* P) {
     if (P->d_norms) (void)hipFree(P->d_norms);
     if (P->h_cand) (void)hipHostFree(P->h_cand);
     if (P->d_cand) (void)hipFree(P->d_cand);
+    if (P->h_cand_keys) (void)hipHostFree(P->h_cand_keys);
+    if (P->d_cand_keys) (void)hipFree(P->d_cand_keys);
     delete P;
 }
 
@@ -114,23 +123,32 @@ int ensure_playlist(mi355rec* h) {
 
 // CANDIDATE LISTS: room for `want` list entries in h_cand and d_cand (the previous call on this handle has completed: nothing reads
 // the old buffers).  A failure leaves the handle without them; the next request allocates again.
-int ensure_candidates(mi355rec* h, mi355rec_playlist* P, int64_t want) {
-    if (want <= P->cand_cap) return MI355REC_OK;
-    int64_t cap = P->cand_cap > 0 ? P->cand_cap : 4096;
+// keys: CANDIDATE SCORES: room for `want` keys in h_cand_keys and d_cand_keys as well (8 B per entry, at most 8 MB), under the same rules.
+template <typename T>
+hipError_t grow_candidates(T** host, T** dev, int64_t* have, int64_t want) {
+    if (want <= *have) return hipSuccess;
+    int64_t cap = *have > 0 ? *have : 4096;
     while (cap < want) cap *= 2;
-    if (P->h_cand) (void)hipHostFree(P->h_cand);
-    if (P->d_cand) (void)hipFree(P->d_cand);
-    P->h_cand = P->d_cand = nullptr;
-    P->cand_cap = 0;
-    hipError_t e = hipHostMalloc(&P->h_cand, sizeof(uint32_t) * static_cast<size_t>(cap), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc(&P->d_cand, sizeof(uint32_t) * static_cast<size_t>(cap));
+    if (*host) (void)hipHostFree(*host);
+    if (*dev) (void)hipFree(*dev);
+    *host = *dev = nullptr;
+    *have = 0;
+    hipError_t e = hipHostMalloc(host, sizeof(T) * static_cast<size_t>(cap), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc(dev, sizeof(T) * static_cast<size_t>(cap));
     if (e == hipSuccess) {
-        P->cand_cap = cap;
-        return MI355REC_OK;
+        *have = cap;
+        return hipSuccess;
     }
-    if (P->h_cand) (void)hipHostFree(P->h_cand);
-    P->h_cand = P->d_cand = nullptr;
+    if (*host) (void)hipHostFree(*host);
+    *host = *dev = nullptr;
     (void)hipGetLastError();
+    return e;
+}
+
+int ensure_candidates(mi355rec* h, mi355rec_playlist* P, int64_t want, bool keys = false) {
+    hipError_t e = grow_candidates(&P->h_cand, &P->d_cand, &P->cand_cap, want);
+    if (e == hipSuccess && keys) e = grow_candidates(&P->h_cand_keys, &P->d_cand_keys, &P->cand_key_cap, want);
+    if (e == hipSuccess) return MI355REC_OK;
     return fail(h, e == hipErrorOutOfMemory ? MI355REC_ERR_OUT_OF_MEMORY : MI355REC_ERR_HIP, "the candidate list (%lld ids): %s", (long long)want,
                 hipGetErrorString(e));
 }
@@ -196,7 +214,7 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     int64_t n_cand = 0;
     if (r.listed) {
         if (r.n_candidates > 0) {
-            rc = ensure_candidates(h, P, r.n_candidates);
+            rc = ensure_candidates(h, P, r.n_candidates, r.score);
             if (rc) return rc;
             // (one pass over the ids: the range check of a list that comes unchecked, the shard's rows, the ascending test)
             const mi355cand::Reduced red =
@@ -206,6 +224,11 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
                 return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
             }
             n_cand = red.count;
+            if (r.score) {   // "CANDIDATE SCORES": where each list position finds its entry
+                P->cand_entries = n_cand;
+                P->cand_pos.resize(static_cast<size_t>(r.n_candidates));
+                mi355cand::positions(r.candidates, r.n_candidates, h->row_base, h->row_base + h->n, P->h_cand, red, P->cand_pos.data());
+            }
         }
         if (n_cand < avail) avail = n_cand;
     }
@@ -219,6 +242,8 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     ++h->playlist_queries;
     const int eff = static_cast<int64_t>(r.scan_topn()) < avail ? r.scan_topn() : static_cast<int>(avail);
     if (eff <= 0) return MI355REC_OK;   // nothing left to return: nothing to launch
+    // "CANDIDATE SCORES": the launch selects nothing (topk == 0 is the kernel's score mode) and needs no result slot
+    const int topk = r.score ? 0 : eff;
     PlaylistArg arg;
     arg.k = k;
     arg.n_excl = n_excl;
@@ -259,7 +284,7 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
                         (long long)h->n, hipGetErrorString(e));
         }
     }
-    rc = sync_begin(h, eff, 1, true, ss);
+    rc = sync_begin(h, topk, 1, true, ss);
     if (rc) return rc;
     b->shared_thr = 0ull;
     // (the staging buffer is free: the previous call on this handle has completed)
@@ -286,7 +311,7 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     const int grid = static_cast<int>(want_grid);
     LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, playlist_scan_kernel, dim3(grid), dim3(PlaylistCfg::kBlock),
                  h->stream, h->d_feats, q8, h->n, h->row_base, static_cast<const PlaylistBuf*>(P->d_buf), arg,
-                 static_cast<const float*>(r.listed ? nullptr : h->d_anchor), eff, h->d_block_lists, P->d_exact,
+                 static_cast<const float*>(r.listed ? nullptr : h->d_anchor), topk, r.score ? P->d_cand_keys : h->d_block_lists, P->d_exact,
                  reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr)),
                  reinterpret_cast<const uint2*>(L ? L->d_row_labels : nullptr), reinterpret_cast<const float4*>(pri),
                  reinterpret_cast<const float4*>(scan_norms ? P->d_norms : nullptr));
@@ -332,11 +357,56 @@ int sync_playlist_query(mi355rec* h, const Request& r, const Outputs& out, int m
     return rc;
 }
 
+// "CANDIDATE SCORES": the same request with r.score: the gather launch stores every entry's key and selects nothing, no merge
+// follows; the keys come back through the pinned buffer and are unpacked in list order (P->cand_pos).  No launch (no list entry of
+// this shard, or no row the request could admit): every candidate is inadmissible.
+int sync_playlist_scores(mi355rec* h, const Request& r, const mi355playlist::ScoreOutputs& out, int max_exclude = kMaxExclude) {
+    if (!h || !(r.members || r.rows) || !out.value) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    DeviceGuard guard(h->device);
+    SyncSlots ss;
+    int grid = 0;
+    int rc = playlist_launch(h, r, max_exclude, &ss, &grid);
+    if (rc) return rc;
+    if (grid == 0) {
+        for (int64_t i = 0; i < r.n_candidates; ++i) mi355playlist::score_none(out, i);
+        return MI355REC_OK;
+    }
+    mi355rec_playlist* P = h->playlist;
+    rc = sync_finish_buffer(h, P->h_cand_keys, P->d_cand_keys, sizeof(uint64_t) * static_cast<size_t>(P->cand_entries));
+    if (rc) return rc;
+    for (int64_t i = 0; i < r.n_candidates; ++i) {
+        const uint64_t key = P->cand_pos[static_cast<size_t>(i)] >= 0 ? P->h_cand_keys[P->cand_pos[static_cast<size_t>(i)]] : 0ull;
+        if (key) mi355playlist::score_some(r, out, i, mi355rec_key_score(key));
+        else mi355playlist::score_none(out, i);
+    }
+    return MI355REC_OK;
+}
+
+// The scoring entry points' shared tail: the list's and the call's own checks, then the one path.
+int score_request(mi355rec* h, Request r, const int64_t* candidates, int64_t n_candidates, float* out_value, uint8_t* out_admissible) {
+    char why[160];
+    if (r.rowset && r.rowset->node) return fail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
+    if (mi355cand::invalid_count(candidates, n_candidates, MI355REC_MAX_CANDIDATES, why, sizeof why) ||
+        mi355playlist::invalid_score_request(r, n_candidates, out_value, why, sizeof why))
+        return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    if (mi355playlist::invalid_playlist(r, h->n, static_cast<int64_t>(UINT32_MAX) + 1, kMaxExclude, why, sizeof why))
+        return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    if (n_candidates == 0) return MI355REC_OK;   // nothing to write, nothing to launch
+    r.candidates_id_end = kRowsetIdEnd;   // (the ids are checked in playlist_launch's one pass over them)
+    r.listed = r.score = true;
+    r.candidates = candidates;
+    r.n_candidates = n_candidates;
+    return sync_playlist_scores(h, r, {out_value, out_admissible});
+}
+
 }  // namespace
 
 namespace mi355node {
 int query_playlist(mi355rec_t* h, const mi355playlist::Request& r, const mi355playlist::Outputs& out) {
     return sync_playlist_query(h, r, out, kPlExcludeCap);
+}
+int score_playlist(mi355rec_t* h, const mi355playlist::Request& r, const mi355playlist::ScoreOutputs& out) {
+    return sync_playlist_scores(h, r, out, kPlExcludeCap);
 }
 int set_group_priors(mi355rec_t* h, const float* priors_host, int64_t n) { return set_priors_common(h, priors_host, n, true); }
 }  // namespace mi355node
@@ -456,6 +526,32 @@ int mi355rec_query_distance_request_candidates(mi355rec_t* h, const mi355rec_dis
     r.candidates = candidates;
     r.n_candidates = n_candidates;
     return sync_playlist_query(h, r, out);
+}
+
+// "CANDIDATE SCORES": the _candidates calls' conversion and checks (there is no result struct: an empty one stands in), then score_request.
+int mi355rec_score_playlist_request_candidates(mi355rec_t* h, const mi355rec_playlist_query_t* query, const mi355rec_request_ext_t* ext,
+                                               const int64_t* candidates, int64_t n_candidates, float* out_value, uint8_t* out_admissible) {
+    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    mi355rec_playlist_query_t full;
+    const mi355rec_playlist_result_t none = {};
+    Request r;
+    Outputs out;
+    char why[160];
+    if (mi355playlist::from_query_ext(query, ext, &none, &full, &r, &out, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    return score_request(h, r, candidates, n_candidates, out_value, out_admissible);
+}
+
+int mi355rec_score_distance_request_candidates(mi355rec_t* h, const mi355rec_distance_query_t* query, const mi355rec_request_ext_t* ext,
+                                               const int64_t* candidates, int64_t n_candidates, float* out_distance, uint8_t* out_admissible) {
+    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    mi355rec_distance_query_t full;
+    const mi355rec_distance_result_t none = {};
+    Request r;
+    Outputs out;
+    char why[160];
+    if (mi355playlist::from_distance_query_ext(query, ext, &none, &full, &r, &out, why, sizeof why))
+        return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    return score_request(h, r, candidates, n_candidates, out_distance, out_admissible);
 }
 
 int mi355rec_query_distance_request_scaled(mi355rec_t* h, const mi355rec_distance_query_t* query, const float* feature_scales,

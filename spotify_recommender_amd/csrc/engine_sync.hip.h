@@ -74,4 +74,13 @@ int sync_finish(mi355rec* h, const SyncSlots& ss, int topn, int64_t* out_idx, fl
     return MI355REC_OK;
 }
 
+// The same second half for a call whose result is not a top-N list but `bytes` of a device buffer of its own ("CANDIDATE SCORES": the
+// entries' keys): copied into the caller's pinned `host` on the handle's stream behind the call's launches, then the stream is
+// waited for (such a call never notifies: sync_begin was given eff == 0).
+int sync_finish_buffer(mi355rec* h, void* host, const void* dev, size_t bytes) {
+    HIP_TRY(h, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MI355REC_OK;
+}
+
 }  // namespace

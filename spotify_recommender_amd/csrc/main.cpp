@@ -25,6 +25,12 @@
 //       the distance (extension; under both metrics, with --genre and --where)
 //   ... the same modes with --candidates FILE (track ids, one per line, as for --only): only the listed songs are READ and ranked (a
 //       candidate list: the engine gathers them and makes no pass over the catalogue); goes with --seen or --only; extension
+//   ... the same modes with --score FILE (track ids, one per line, as for --candidates): nothing is recommended; every listed track
+//       is printed in file order with the request's value for it (its score, or its distance under --metric euclidean), or "not
+//       eligible" where the request can never return it (a song of the query, a --seen song, outside --where or --genre); -n is
+//       ignored; "how similar is song A to song B" is --id A --score <file naming B>; goes with --seen, --only, --where, --scale,
+//       --metric and the --playlist mode's weights, genres and priors; not with --candidates, --diverse, --max-per-artist or --pool,
+//       nor with --genre under --song / --id; extension
 //   ... --song, --id and --playlist with --seen FILE or --only FILE (track ids, one per line): the listed songs are never recommended
 //       (--seen: a listening history of any length) or only the listed songs are ranked (--only: a candidate set); extension, beside
 //       every other option of those modes; --song / --id then run as the one-song playlist (not with --genre there)
@@ -294,6 +300,40 @@ static bool parseCandidates(int argc, char* argv[], int first, CandidatesOpt& c)
         c.on = true;
         c.file = argv[++i];
     }
+    return true;
+}
+
+// --score FILE from argv[first] (candidate scores): the format of --candidates FILE.  The listed tracks are not ranked: each is
+// printed with the request's value for it.  Not with --candidates (the file IS the list), nor with a re-rank (--diverse,
+// --max-per-artist, --pool: a re-ranked order has no value per track).
+struct ScoreOpt {
+    bool on = false;
+    std::string file;
+};
+
+static bool parseScore(int argc, char* argv[], int first, ScoreOpt& sc) {
+    for (int i = first; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--score") != 0) continue;
+        if (i + 1 >= argc) {
+            std::cerr << "Error: --score needs a file of track ids (one per line)" << std::endl;
+            return false;
+        }
+        if (sc.on) {
+            std::cerr << "Error: --score is given once (a request scores one list)" << std::endl;
+            return false;
+        }
+        sc.on = true;
+        sc.file = argv[++i];
+    }
+    if (!sc.on) return true;
+    for (int i = first; i < argc; ++i)
+        for (const char* other : {"--candidates", "--diverse", "--max-per-artist", "--pool"})
+            if (std::strcmp(argv[i], other) == 0) {
+                std::cerr << "Error: --score cannot be combined with " << other
+                          << (std::strcmp(other, "--candidates") == 0 ? " (the scored file is the list)" : " (a re-ranked order has no value per track)")
+                          << std::endl;
+                return false;
+            }
     return true;
 }
 
@@ -582,6 +622,7 @@ struct Options {
     std::vector<Recommender::FeatureRange> ranges;
     RowSetOpt rowSet;
     CandidatesOpt candidates;
+    ScoreOpt score;
     bool euclidean = false;
     std::vector<float> scales;
     Taste taste;
@@ -612,7 +653,7 @@ static const Refusal kRefusals[] = {
     {Given::Euclidean, kRequestOptions, "--metric euclidean cannot be combined with %s (distance requests take --genre and --where only)"},
     {Given::Scale, kRequestOptions, "--scale cannot be combined with %s (scaled requests take --metric, --genre and --where only)"},
     {Given::GenreFiltered, {"--where"}, "%s cannot be combined with --genre"},
-    {Given::GenreFiltered, {"--seen", "--only", "--candidates"}, "%s cannot be combined with --genre here: use --playlist <one id> --genre ..."},
+    {Given::GenreFiltered, {"--seen", "--only", "--candidates", "--score"}, "%s cannot be combined with --genre here: use --playlist <one id> --genre ..."},
     {Given::GenreReranked, {"--max-per-artist"}, "%s cannot be combined with --genre"},
     {Given::GenreReranked, {"--diverse"}, "%s cannot be combined with --genre"},
 };
@@ -644,7 +685,7 @@ static bool parseOptions(int argc, char* argv[], Options& o) {
     if (!parseTopN(argc, argv, first, o.topN)) return false;
     if (!o.playlist && !parseGenres(argc, argv, first, o.genres)) return false;
     if (!parseWhere(argc, argv, first, o.ranges) || !parseRowSet(argc, argv, first, o.rowSet)) return false;
-    if (!parseCandidates(argc, argv, first, o.candidates)) return false;
+    if (!parseCandidates(argc, argv, first, o.candidates) || !parseScore(argc, argv, first, o.score)) return false;
     if (!parseMetric(argc, argv, first, o.euclidean) || refused(argc, argv, first, o, Given::Euclidean)) return false;
     if (!parseScale(argc, argv, first, o.scales) || refused(argc, argv, first, o, Given::Scale)) return false;
     printScales(o.scales);
@@ -778,7 +819,7 @@ static bool queryMode(const Options& o) {
 
     // (2. for the song flavour.)  Without an extension option it is the reference's own route: recommend / recommendByName look
     // the song up themselves; with --genre alone its label-scan form.  Everything else is one Recommender::Query.
-    const bool reference = song && !o.dv.on && o.ranges.empty() && !o.rowSet.on && !o.candidates.on;
+    const bool reference = song && !o.dv.on && o.ranges.empty() && !o.rowSet.on && !o.candidates.on && !o.score.on;
     if (song) {
         std::cout << "\nSearching for " << (o.isTrackId ? "track ID: " : "song: ") << o.query << std::endl;
         if (!genreIdsOf(catalogue, o.genres, genreIds)) return false;
@@ -790,6 +831,18 @@ static bool queryMode(const Options& o) {
 
     // 6. the request
     std::vector<int> recs;
+    std::vector<int64_t> listed;   // --score: the file's tracks, and the request's value of each
+    std::vector<float> listedValues;
+    std::vector<char> eligible;
+    if (o.score.on) {
+        std::vector<int> rows;
+        size_t skipped = 0;
+        if (!readTrackIdFile(catalogue, o.score.file, "score list", rows, skipped)) return false;
+        std::cerr << "Score list (--score " << o.score.file << "): " << rows.size() << " tracks, " << skipped
+                  << " lines skipped (not in the catalogue)" << std::endl;
+        listed.assign(rows.begin(), rows.end());
+        std::cout << "Scoring " << listed.size() << " listed tracks" << std::endl;
+    }
     if (reference && genreIds.empty()) {
         recs = o.isTrackId ? recommender.recommend(o.query, o.topN) : recommender.recommendByName(o.query, o.topN);
     } else if (reference) {
@@ -809,9 +862,10 @@ static bool queryMode(const Options& o) {
         q.priorWeight = o.pr.on ? o.pr.weight : 0.0f;   // (BETA 0 is the call without a prior)
         q.scales = o.scales;
         q.euclidean = o.euclidean;
-        if (q.topN > 0) recs = recommender.recommendQuery(q);
+        if (o.score.on) listedValues = recommender.scoreSongs(q, listed, &eligible);
+        else if (q.topN > 0) recs = recommender.recommendQuery(q);
     }
-    if (recs.empty()) return noRecommendations();
+    if (o.score.on ? listedValues.size() != listed.size() || listed.empty() : recs.empty()) return noRecommendations();
 
     // 7. the query's block, then the recommendations (a distance or scaled request prints their values)
     const std::vector<float> values = recommender.lastScores();
@@ -826,6 +880,18 @@ static bool queryMode(const Options& o) {
             if (!printEntry(catalogue, genreMap, members[i], i + 1, "  ", weight.str())) return false;
         }
         std::cout << "----------------------------------------------" << std::endl;
+    }
+    if (o.score.on) {   // --score: the listed tracks in file order, nothing is recommended
+        std::cout << "\nValues of " << listed.size() << " listed tracks:\n" << std::endl;
+        for (size_t i = 0; i < listed.size(); ++i) {
+            std::ostringstream value;
+            if (eligible[i]) value << "  (" << (o.euclidean ? "distance " : "score ") << listedValues[i] << ")";
+            else value << "  (not eligible)";
+            if (!printEntry(catalogue, genreMap, static_cast<int>(listed[i]), i + 1, "", value.str())) return false;
+            if (i + 1 < listed.size()) std::cout << std::endl;
+        }
+        std::cout << "\nScoring complete!" << std::endl;
+        return true;
     }
     std::cout << "\nTop " << recs.size() << " Recommendations:\n" << std::endl;
     for (size_t i = 0; i < recs.size(); ++i) {

@@ -34,6 +34,8 @@ int set_group_labels(mi355rec_t* h, const int32_t* labels_host, int64_t n);
 // _playlist_topn* calls run, with up to MI355REC_MAX_EXCLUDE + MI355REC_MAX_PLAYLIST excluded ids (engine_playlist.hip.h):
 // the row-sharded node adds the members' global rows to the caller's list.
 int query_playlist(mi355rec_t* h, const mi355playlist::Request& r, const mi355playlist::Outputs& out);
+// "CANDIDATE SCORES": the scoring request (r.listed, r.score) on one handle, under the same limit.
+int score_playlist(mi355rec_t* h, const mi355playlist::Request& r, const mi355playlist::ScoreOutputs& out);
 // The re-rank alone over a pool passed by value (engine_diverse.hip.h): `count` (<= 1024) pool rows in canonical order, their
 // global ids, scores and features (count x 12).
 // GROUP CAPS: pool_groups (null: no cap) are the pool rows' groups in pool order, max_per_group the cap, *out_pool_rows = P'.

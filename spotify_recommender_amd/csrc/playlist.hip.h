@@ -146,6 +146,14 @@
 // The rows ascend, so neighbouring lanes share cache lines where the list is dense.  cand == null takes none of this (one uniform
 // test in the kernel body) and the scan's loop is untouched.
 //
+// CANDIDATE SCORES (include/mi355rec_diag.h, "CANDIDATE SCORES").  The gather launched with topk == 0 (uniform) and, as `block_lists`,
+// a buffer of n_cand 64-bit words: the SCORE MODE.  For entry e of the list the thread stores word e: the row's playlist_row_key if
+// the row passed the row-set, label and filter tests, formed a key and is not in the LDS exclusion list, else 0.  The threshold stays
+// 0, so every formed key is looked up in the exclusion list.  Nothing is appended: the ballot, the two barriers, the compaction and
+// the shared_thr exchange are skipped, sm.count stays 0, the tail stores topk = 0 keys per workgroup and the host launches no merge.
+// Entries past n_cand store nothing.  No kernel argument is added (the kernel sits on its register budget): the mode rides on topk,
+// the buffer on block_lists.
+//
 // EXCLUSION.  The excluded global ids (members and the caller's list, sorted and deduplicated on the host, at most
 // kPlExcludeCap) sit in LDS as uint32; only a key that already beats the workgroup's threshold is looked up (binary
 // search), so the hot loop does not change.
@@ -586,11 +594,12 @@ __device__ __forceinline__ void playlist_scan_tiles(const PlaylistCtx& c, const 
 // of 128 VGPRs without scratch: 4 entries (48 row registers) and 3 spill, 2 fit; what is in flight per CU comes from its 1024 threads.
 constexpr int kPlGatherPerThread = 2;
 __device__ __forceinline__ void playlist_gather_rows(const PlaylistCtx& c, const PlaylistSmem& sm, const uint32_t* __restrict__ cand,
-                                                     int64_t n_cand, int& n_exact) {
+                                                     int64_t n_cand, uint64_t* __restrict__ entry_keys, int& n_exact) {
     constexpr int kBlock = PlaylistCfg::kBlock, kPer = kPlGatherPerThread;
     static_assert(kBlock * kPer <= PlaylistCfg::kTileRows, "an iteration appends at most a tile's worth of keys (kCandCap)");
     const int tid = c.tid, lane = c.lane;
     const int64_t chunks = (n_cand + kBlock * kPer - 1) / (kBlock * kPer);
+    const bool score = c.topk == 0;   // (uniform) CANDIDATE SCORES: every entry's key to entry_keys, nothing selected
     uint64_t thr = 0ull;
     int compact_at = 2 * c.topk > 256 ? 2 * c.topk : 256;
     if (compact_at > kCandLimit) compact_at = kCandLimit;
@@ -629,6 +638,10 @@ __device__ __forceinline__ void playlist_gather_rows(const PlaylistCtx& c, const
             const uint64_t key = have ? row_key : 0ull;
             bool pass = key > thr;
             if (pass && c.n_excl > 0) pass = !playlist_excluded(sm.excl, c.n_excl, static_cast<uint32_t>(c.row_base + row[v]));
+            if (score) {   // (uniform) entry e0 + v's word: its key, or 0 (thr stays 0, so every key was looked up in the exclusion list)
+                if (e0 + v < n_cand) entry_keys[e0 + v] = pass ? key : 0ull;
+                continue;
+            }
             const uint64_t ballot = __ballot(pass);
             if (ballot) {
                 int base = 0;
@@ -637,6 +650,7 @@ __device__ __forceinline__ void playlist_gather_rows(const PlaylistCtx& c, const
                 if (pass) sm.cand[base + lanes_below(ballot)] = key;
             }
         }
+        if (score) continue;   // (uniform) nothing was appended: no barrier, no compaction, no threshold
         // the scan's two barriers, compaction and threshold exchange
         __syncthreads();
         const int count = sm.count;
@@ -684,7 +698,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     // (uniform) CANDIDATE LISTS: only the listed rows.  Marked unlikely: a non-null pointer test counts as likely, and the register
     // allocator then weighs the scan's loops below the gather's and moves the kernel's spilled SGPRs into them (docs/LAB_NOTES.md).
     if (__builtin_expect(arg.cand != nullptr, 0)) {
-        playlist_gather_rows(c, sm, arg.cand, arg.n_cand, n_exact);
+        playlist_gather_rows(c, sm, arg.cand, arg.n_cand, block_lists, n_exact);
     } else {
         uint64_t thr = 0ull;
         if (cut.kind != kPlCutOff) thr = playlist_anchor_bound(c, sm, u, un, n_exact);   // uniform

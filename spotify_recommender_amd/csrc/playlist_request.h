@@ -52,6 +52,8 @@ struct Request {
     int64_t n_candidates = 0;                   // ... no row is), beside whatever else the request asks of a row
     int64_t candidates_id_end = -1;             // >= 0: the ids are NOT checked yet: each lies in [0, this), or the request is refused
                                                 // ... by the pass that reduces the list (the single handle's own entry points)
+    bool score = false;                         // "CANDIDATE SCORES" (listed only): the value of EVERY listed row is wanted, in list
+                                                // ... order, and nothing is selected: topn is checked and otherwise unused
 
     int scan_topn() const { return diverse ? pool : topn; }   // what the scan selects
     // The same call diversified, and (of a diversified one) capped: what the _diverse and _capped entry points add.
@@ -214,6 +216,39 @@ inline void label_bits(const Request& r, uint32_t* mask) {
 inline void scores_to_distances(const Outputs& out, int topn) {
     if (!out.score) return;
     for (int i = 0; i < topn && out.idx[i] >= 0; ++i) out.score[i] = std::sqrt(0.0f - out.score[i]);
+}
+
+// "CANDIDATE SCORES": where the values go, in list order: value[i] and (may be null) admissible[i] for candidates[i].
+struct ScoreOutputs {
+    float* value = nullptr;
+    uint8_t* admissible = nullptr;
+};
+
+// ... the entry of a candidate that is not admissible: the quiet NaN 0x7fc00000, flag 0.
+inline void score_none(const ScoreOutputs& out, int64_t i) {
+    const uint32_t nan_bits = 0x7fc00000u;
+    std::memcpy(&out.value[i], &nan_bits, sizeof nan_bits);
+    if (out.admissible) out.admissible[i] = 0;
+}
+
+// ... and of one that is: `s` is the key's score (+0.0 for -0.0 already; -m for a distance request: sqrtf(0.0f - s) is reported).
+inline void score_some(const Request& r, const ScoreOutputs& out, int64_t i, float s) {
+    out.value[i] = r.report_distance ? std::sqrt(0.0f - s) : s;
+    if (out.admissible) out.admissible[i] = 1;
+}
+
+// ... what the scoring calls refuse beyond the _candidates calls' own checks (r: the converted request).  True: msg says why.
+inline bool invalid_score_request(const Request& r, int64_t n_candidates, const float* out_value, char* msg, size_t cap) {
+    if (r.diverse) {
+        std::snprintf(msg, cap, "%s in a candidate scores call: a re-ranked order has no per-row value",
+                      r.capped ? "MI355REC_PQ_CAPPED" : "MI355REC_PQ_DIVERSE");
+        return true;
+    }
+    if (n_candidates > 0 && !out_value) {
+        std::snprintf(msg, cap, "candidate scores: null out_value with n_candidates %lld", static_cast<long long>(n_candidates));
+        return true;
+    }
+    return false;
 }
 
 // The C-ABI's request (include/mi355rec_diag.h, "PLAYLIST REQUESTS") as the Request and Outputs every layer below takes.

@@ -755,6 +755,34 @@ int diverse_over_shards(mi355rec_sharded_t* h, const Request& r, const Outputs& 
     return rc == MI355REC_OK ? rc : sfail(h, rc, "shard on device %d: %s", first->device, mi355rec_last_error(first->engine));
 }
 
+// By row, one handle (row_base 0) takes its own by-row call: the members stay on the device.  Otherwise the members go by value
+// (fetched once into `members`) and their rows are added to the exclusion list (`excl`).  r has been checked.
+int members_by_value(mi355rec_sharded_t* h, Request& r, float* members, int64_t* excl) {
+    if (!(r.rows && (h->cpu || h->shards.size() > 1 || h->replicated))) return MI355REC_OK;
+    for (int i = 0; i < r.n_exclude; ++i) excl[i] = r.exclude[i];
+    for (int m = 0; m < r.k; ++m) {
+        excl[r.n_exclude + m] = r.rows[m];
+        if (h->cpu) {
+            std::memcpy(members + m * MI355REC_DIM, mi355cpu::row(mi355cpu::node_catalogue(h->cpu), r.rows[m]), sizeof(float) * MI355REC_DIM);
+            continue;
+        }
+        if (m == 0) {
+            const int rc = drain_workers(h);
+            if (rc) return rc;
+        }
+        DeviceRestore restore;
+        const Shard* own = owner_of(h, r.rows[m]);
+        S_HIP(h, hipSetDevice(own->device));
+        const int rc = mi355rec_fetch_row(own->engine, r.rows[m] - own->lo, members + m * MI355REC_DIM);
+        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
+    }
+    r.members = members;
+    r.rows = nullptr;
+    r.exclude = excl;
+    r.n_exclude += r.k;
+    return MI355REC_OK;
+}
+
 // Every call of the family on the node handle: the checks (the catalogue's global rows are known here), the members of a
 // by-row call by value where no single handle can read them, then the CPU backend, the one handle that holds the whole
 // catalogue, or every shard and a host merge.
@@ -768,33 +796,10 @@ int sharded_playlist(mi355rec_sharded_t* h, Request r, const Outputs& out) {
         return sfail(h, MI355REC_ERR_INVALID_ARG, "this handle has no priors (mi355rec_sharded_set_priors)");
     if (r.rowset && r.rowset->node != h) return sfail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
     if (out.pool_rows) *out.pool_rows = 0;
-    // By row, one handle (row_base 0) takes its own by-row call below: the members stay on the device.  Otherwise the members
-    // go by value (fetched once) and their rows are added to the exclusion list.
     float members[MI355REC_MAX_PLAYLIST * MI355REC_DIM];
     int64_t excl[MI355REC_MAX_EXCLUDE + MI355REC_MAX_PLAYLIST];
-    if (r.rows && (h->cpu || h->shards.size() > 1 || h->replicated)) {
-        for (int i = 0; i < r.n_exclude; ++i) excl[i] = r.exclude[i];
-        for (int m = 0; m < r.k; ++m) {
-            excl[r.n_exclude + m] = r.rows[m];
-            if (h->cpu) {
-                std::memcpy(members + m * MI355REC_DIM, mi355cpu::row(mi355cpu::node_catalogue(h->cpu), r.rows[m]), sizeof(float) * MI355REC_DIM);
-                continue;
-            }
-            if (m == 0) {
-                const int rc = drain_workers(h);
-                if (rc) return rc;
-            }
-            DeviceRestore restore;
-            const Shard* own = owner_of(h, r.rows[m]);
-            S_HIP(h, hipSetDevice(own->device));
-            const int rc = mi355rec_fetch_row(own->engine, r.rows[m] - own->lo, members + m * MI355REC_DIM);
-            if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
-        }
-        r.members = members;
-        r.rows = nullptr;
-        r.exclude = excl;
-        r.n_exclude += r.k;
-    }
+    const int by_value = members_by_value(h, r, members, excl);
+    if (by_value) return by_value;
     if (h->cpu) {
         const char* cpu_why = nullptr;
         return cpu_result(h, r.diverse ? mi355cpu::node_query_mean_diverse(h->cpu, r, out, &cpu_why)
@@ -816,6 +821,65 @@ int sharded_playlist(mi355rec_sharded_t* h, Request r, const Outputs& out) {
     });
     if (merged == MI355REC_OK && report_distance) mi355playlist::scores_to_distances(out, r.topn);
     return merged;
+}
+
+// CANDIDATE SCORES (include/mi355rec_diag.h) on the node handle: sharded_playlist's checks and member rows, then the CPU backend,
+// the one handle that holds the whole catalogue with the whole list, or every shard that owns listed ids with those ids (a shard
+// with none launches nothing), its values scattered back to the ids' list positions.  (r.listed and r.score are set; the ids are checked.)
+int sharded_scores(mi355rec_sharded_t* h, Request r, const mi355playlist::ScoreOutputs& out) {
+    if (!(r.members || r.rows)) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    char why[160];
+    if (mi355playlist::invalid_score_request(r, r.n_candidates, out.value, why, sizeof why) ||
+        mi355playlist::invalid_playlist(r, h->n, h->n, MI355REC_MAX_EXCLUDE, why, sizeof why))
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    if (r.prior && !h->cpu && !h->has_priors)
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "this handle has no priors (mi355rec_sharded_set_priors)");
+    if (r.rowset && r.rowset->node != h) return sfail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
+    if (r.n_candidates == 0) return MI355REC_OK;   // nothing to write, nothing to launch
+    float members[MI355REC_MAX_PLAYLIST * MI355REC_DIM];
+    int64_t excl[MI355REC_MAX_EXCLUDE + MI355REC_MAX_PLAYLIST];
+    int rc = members_by_value(h, r, members, excl);
+    if (rc) return rc;
+    if (h->cpu) {
+        const char* cpu_why = nullptr;
+        return cpu_result(h, mi355cpu::node_score_rows(h->cpu, r, out, &cpu_why), cpu_why);
+    }
+    DeviceRestore restore;
+    if (h->shards.size() == 1 || h->replicated)
+        return on_whole_catalogue(h, [&](mi355rec_t* e) { return mi355node::score_playlist(e, r, out); });
+    rc = drain_workers(h);
+    if (rc) return rc;
+    std::vector<int64_t> ids, where;
+    std::vector<float> value;
+    std::vector<uint8_t> admissible;
+    for (Shard& s : h->shards) {
+        if (s.hi <= s.lo) continue;
+        try {
+            ids.clear();
+            where.clear();
+            for (int64_t i = 0; i < r.n_candidates; ++i)
+                if (r.candidates[i] >= s.lo && r.candidates[i] < s.hi) {
+                    ids.push_back(r.candidates[i]);
+                    where.push_back(i);
+                }
+            value.resize(ids.size());
+            admissible.resize(ids.size());
+        } catch (const std::bad_alloc&) {
+            return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for a list of %lld candidates", (long long)r.n_candidates);
+        }
+        if (ids.empty()) continue;
+        Request mine = r;
+        mine.candidates = ids.data();
+        mine.n_candidates = static_cast<int64_t>(ids.size());
+        S_HIP(h, hipSetDevice(s.device));
+        rc = mi355node::score_playlist(s.engine, mine, {value.data(), admissible.data()});
+        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", s.device, mi355rec_last_error(s.engine));
+        for (size_t j = 0; j < where.size(); ++j) {
+            out.value[where[j]] = value[j];
+            if (out.admissible) out.admissible[where[j]] = admissible[j];
+        }
+    }
+    return MI355REC_OK;
 }
 }  // namespace
 
@@ -981,6 +1045,43 @@ int mi355rec_sharded_query_distance_request_candidates(mi355rec_sharded_t* h, co
     r.candidates = candidates;
     r.n_candidates = n_candidates;
     return sharded_playlist(h, r, out);
+}
+
+// CANDIDATE SCORES (include/mi355rec_diag.h): the _candidates calls' conversion and checks, then sharded_scores.
+int mi355rec_sharded_score_playlist_request_candidates(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
+                                                       const mi355rec_request_ext_t* ext, const int64_t* candidates, int64_t n_candidates,
+                                                       float* out_value, uint8_t* out_admissible) {
+    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    mi355rec_playlist_query_t full;
+    const mi355rec_playlist_result_t none = {};
+    Request r;
+    Outputs out;
+    char why[160];
+    if (mi355playlist::from_query_ext(query, ext, &none, &full, &r, &out, why, sizeof why) ||
+        mi355cand::invalid_list(candidates, n_candidates, MI355REC_MAX_CANDIDATES, h->n, why, sizeof why))
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    r.listed = r.score = true;
+    r.candidates = candidates;
+    r.n_candidates = n_candidates;
+    return sharded_scores(h, r, {out_value, out_admissible});
+}
+
+int mi355rec_sharded_score_distance_request_candidates(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
+                                                       const mi355rec_request_ext_t* ext, const int64_t* candidates, int64_t n_candidates,
+                                                       float* out_distance, uint8_t* out_admissible) {
+    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    mi355rec_distance_query_t full;
+    const mi355rec_distance_result_t none = {};
+    Request r;
+    Outputs out;
+    char why[160];
+    if (mi355playlist::from_distance_query_ext(query, ext, &none, &full, &r, &out, why, sizeof why) ||
+        mi355cand::invalid_list(candidates, n_candidates, MI355REC_MAX_CANDIDATES, h->n, why, sizeof why))
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    r.listed = r.score = true;
+    r.candidates = candidates;
+    r.n_candidates = n_candidates;
+    return sharded_scores(h, r, {out_distance, out_admissible});
 }
 
 // ROW SETS (include/mi355rec_diag.h): the global host bitmap, and a device copy beside every engine's rows: a row-sharded placement

@@ -194,6 +194,30 @@ int shim_set_candidates(void* h, const int64_t* songs, int64_t n_songs) {
     }
     return c->rec.setCandidates(std::vector<int64_t>(songs, songs + n_songs)) ? 1 : 0;
 }
+// Recommender::scoreSongs of the Query {songs, alsoExclude = exclude, where = the one range on where_feature (< 0: none), euclidean,
+// diverse, maxPerArtist, topN}: the values and flags of the n_listed songs into values / admissible (either may be null); returns how
+// many values the class gave back (0: refused, or an empty list).
+int64_t shim_score_songs(void* h, const int* songs, int n_songs, const int* exclude, int n_exclude, int where_feature, float lo, float hi,
+                         int euclidean, int diverse, int max_per_artist, int topn, const int64_t* listed, int64_t n_listed, float* values,
+                         char* admissible) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    Recommender::Query q;
+    q.songs.assign(songs, songs + (n_songs > 0 ? n_songs : 0));
+    q.alsoExclude.assign(exclude, exclude + (n_exclude > 0 ? n_exclude : 0));
+    if (where_feature >= 0) q.where.push_back({where_feature, lo, hi});
+    q.euclidean = euclidean != 0;
+    q.diverse = diverse != 0;
+    q.lambda = 0.5f;
+    q.maxPerArtist = max_per_artist;
+    q.topN = topn;
+    std::vector<char> flags;
+    const std::vector<float> v = c->rec.scoreSongs(q, std::vector<int64_t>(listed, listed + (n_listed > 0 ? n_listed : 0)), &flags);
+    for (size_t i = 0; i < v.size(); ++i) {
+        if (values) values[i] = v[i];
+        if (admissible) admissible[i] = flags[i];
+    }
+    return static_cast<int64_t>(v.size());
+}
 // Recommender::updateSongs (n_features floats for n_songs songs: a length that differs is refused by the class).
 int shim_update_songs(void* h, const int* songs, int n_songs, const float* features, int64_t n_features) {
     Catalogue* c = static_cast<Catalogue*>(h);

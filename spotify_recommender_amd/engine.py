@@ -498,6 +498,63 @@ def with_candidates(eng, candidates):
     return _Listed(eng, candidates)
 
 
+def candidate_scores(eng, candidates, *, queries=None, rows=None, metric="cosine", exclude=None, where=None, weights=None, labels=None,
+                     prior_weight=None, scales=None, seen=None, only=None) -> Tuple[np.ndarray, np.ndarray]:
+    """CANDIDATE SCORES (include/mi355rec_diag.h): what the request is worth at EVERY listed row, in list order, for a blender that
+    mixes a first stage's score with the engine's.  `eng`: a CosineEngine, a lane or a NodeEngine; `candidates`: global ids, any
+    order, duplicates fine, up to capi.MAX_CANDIDATES.  The request is given as to query_mean_topn / query_playlist_topn
+    (metric="cosine": `queries` k x 12 by value or `rows` of the engine; `weights`, `prior_weight`) or to query_nearest*
+    (metric="distance"), with `exclude`, `where`, `labels`, `scales`, `seen` / `only` as there.
+    Returns (values float32[n], admissible bool[n]): values[i] is bit for bit the score (the distance) the same request's top-N call
+    reports for candidates[i]; where candidates[i] can never be returned (excluded, a member given by row, rejected by the row set,
+    the label set or the filter, a distance that is not finite, an id outside a single handle's rows) it is NaN and the flag is False."""
+    if (queries is None) == (rows is None):
+        raise ValueError("candidate_scores takes queries= (members by value) or rows= (members by row), one of them")
+    if metric not in ("cosine", "distance"):
+        raise ValueError(f"metric {metric!r}: 'cosine' or 'distance'")
+    dist = metric == "distance"
+    if dist and (weights is not None or prior_weight is not None):
+        raise ValueError("a distance request takes no weights and no prior_weight")
+    members = _np_members(queries) if queries is not None else _np_rows(rows)
+    k = int(members.shape[0])
+    cand = _np_ids(candidates)
+    values = np.empty(cand.size, dtype=np.float32)
+    flags = np.empty(cand.size, dtype=np.uint8)
+
+    def ptr(a):
+        return a.ctypes.data_as(ctypes.c_void_p)
+
+    flt = make_filter(where) if where is not None else None
+    ex = np.ascontiguousarray(np.asarray([] if exclude is None else list(exclude), dtype=np.int64).reshape(-1))
+    q = capi.DistanceQuery() if dist else capi.PlaylistQuery()
+    q.size = ctypes.sizeof(type(q))
+    q.members, q.rows = (None, ptr(members)) if members.dtype == np.int64 else (ptr(members), None)
+    q.exclude_global, q.n_exclude = (ptr(ex) if ex.size else None), int(ex.size)
+    q.filter = ctypes.pointer(flt) if flt is not None else None
+    if labels is not None:
+        lab = _np_labels(labels)
+        q.labels, q.n_labels = ptr(lab), int(lab.size)
+    q.k, q.topn = k, 1   # (topn is checked and otherwise unused)
+    if weights is not None:
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+        if w.size != k:
+            raise ValueError(f"{w.size} weights for {k} songs: one weight per song")
+        q.weights = ptr(w)
+    if prior_weight is not None:
+        q.flags |= capi.PQ_PRIOR
+        q.prior_weight = float(prior_weight)
+    a = make_scales(scales) if scales is not None else None
+    entry = getattr(eng._lib, f"{eng._prefix}score_{'distance' if dist else 'playlist'}_request_candidates")
+
+    def call(rowset):
+        ext = _request_ext(a, rowset)
+        eng._check(entry(eng._h, ctypes.byref(q), ctypes.byref(ext), ptr(cand) if cand.size else None, int(cand.size),
+                         ptr(values) if cand.size else None, ptr(flags) if cand.size else None))
+
+    eng._with_set(seen, only, call)
+    return values, flags.astype(bool)
+
+
 def candidates_counters(eng) -> dict:
     """mi355rec_candidates_counters of a CosineEngine (or a lane): the requests that took the gather launch and the distinct
     in-shard list entries those launches were given, since the handle was created."""
