@@ -205,6 +205,10 @@ public:
     // for no cap; a cap without `diverse` is the plain order with the cap (lambda stays 1); `diverse` with lambda = 1 within genres
     // or with a prior weight is the plain request (the same result without a pool).  With euclidean set, lastScores()
     // holds distances, and weights, diverse, maxPerArtist and priorWeight are refused.  The row set of setRowSet applies.
+    // anyOf (include/mi355rec_diag.h, "ANY-OF REQUESTS"): songs rank by their BEST similarity among `songs` ("like any of these")
+    // instead of the mean; lastScores() holds that similarity and lastMatchedSongs() the song of `songs` each result matched.  With
+    // anyOf, weights, diverse, maxPerArtist, priorWeight, scales and euclidean are refused with a message and {}, and so are a set
+    // candidate list (setCandidates) and scoreSongs.  The row set of setRowSet applies.
     struct Query {
         std::vector<int> songs;            // 1 to 32
         std::vector<float> weights;        // one per song, or none
@@ -219,8 +223,12 @@ public:
         std::vector<float> scales;         // 12, or none
         bool euclidean = false;
         int topN = 10;
+        bool anyOf = false;
     };
     std::vector<int> recommendQuery(const Query& query);
+    // Per result of the last recommendQuery with anyOf: the catalogue index of the matched song of query.songs (the first of them
+    // that attains the result's score).  Empty after any other call.
+    const std::vector<int>& lastMatchedSongs() const;
 
     // Extension: candidate scores (include/mi355rec_diag.h, "CANDIDATE SCORES").  scoreSongs gives what `query` is worth at every
     // song of songIndices, in their order (duplicates allowed, at most 1 048 576): the score (with euclidean the distance)

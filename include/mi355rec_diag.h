@@ -36,6 +36,8 @@
  *     distance requests in a self-sized struct of extras (mi355rec_rowset_*, mi355rec_query_*_request_ext and the node-handle twins);
  *   - ROW UPDATES: rows of the catalogue change in place and every route answers as a freshly created handle would
  *     (mi355rec_update_rows, _update_info, _replica_entries and the node-handle twin);
+ *   - ANY-OF REQUESTS: the top-N rows by their best match among up to 32 members, with the matched member's index per result
+ *     (mi355rec_query_anyof_request and its node-handle twin);
  *   - test hooks, compiled in only with -DMI355REC_TEST_HOOKS (spotify_recommender_amd/build.py builds
  *     libmi355rec_testhooks.so for tests/; the product library does not export them).
  */
@@ -1006,6 +1008,65 @@ int mi355rec_sharded_score_playlist_request_candidates(mi355rec_sharded_t* h, co
 int mi355rec_sharded_score_distance_request_candidates(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
                                                        const mi355rec_request_ext_t* ext, const int64_t* candidates, int64_t n_candidates,
                                                        float* out_distance, uint8_t* out_admissible /* may be NULL */);
+
+/* ANY-OF REQUESTS ("multi-interest" retrieval): the top-N rows by their BEST match among up to 32 members ("like any of these"),
+ * and which member each result matched ("because you listened to X").  The mean and the distance requests collapse a playlist
+ * to one point (its mean direction, its centroid); a listener with two tastes gets the songs in between.  This request does not.
+ * mi355rec_anyof_query_t carries its own size under the rules of mi355rec_playlist_query_t.
+ *   members / rows   exactly one is non-NULL: k x 12 floats by value, or k rows of the handle (local rows of a single handle,
+ *                    global rows of a node handle; never returned); 1 <= k <= MI355REC_MAX_PLAYLIST;
+ *   exclude_global / n_exclude, filter, labels / n_labels   as in the playlist request;
+ *   topn             in [1, MI355REC_MAX_TOPN_FAST];       flags   must be 0.
+ * mi355rec_anyof_result_t: out_idx (topn slots) is required; out_score, out_member (topn slots each) and out_count may be NULL.
+ * RANKING VALUE, per row x, bit for bit:
+ *     c_k(x) = the score mi355rec_query_topn gives row x for the query q_k        (never NaN, in [-1, 1])
+ *     v(x) = c_0;  a(x) = 0;   for k = 1 .. K-1:  if (c_k > v) { v = c_k; a = k; }   (IEEE compare: -0.0 does not beat +0.0)
+ * Rows rank by v descending, then row ascending (keys are packed from v: -0.0 reports as +0.0).  out_score[i] = v and
+ * out_member[i] = a of result i: the SMALLEST index into the caller's member list that attains the maximum.
+ * count = min(topn, |admissible rows|); past it the padding is -1 / +0.0f / -1.  Admissibility is the playlist request's (not
+ * excluded, not a member row, the filter, the label set, the row set of `ext`).
+ * ext: may be NULL; its row set is honoured with the _ext calls' ownership checks; a non-NULL feature_scales is INVALID_ARG
+ * ("any-of requests take no feature scales").  There are no _ext or _scaled variants: this one entry point takes ext.
+ * INVALID_ARG (with a message): flags != 0; both or neither of members and rows; a bad size; everything the playlist request
+ * refuses for the fields the two share (same limits, same messages).
+ * Device: anyof_scan_kernel (csrc/anyof.hip.h), the playlist scan's launch geometry.  With the 8-bit replica the row a lane holds
+ * is dotted with every member (6 v_dot4_i32_i8 per member and row) and a row is ruled out only if EVERY member's cut rules it out
+ * (csrc/playlist_cut.hip.h, "ANY"); the survivors take the k chains on the fp32 row.  Replica on and off answer alike, bit for
+ * bit.  out_member costs a second, tiny launch of the same kernel over the merged result rows.  mi355rec_playlist_counters counts
+ * these calls and the rows whose chains they computed (the attribution's rows not included).
+ * Node handle: one shard forwards; a replicated placement asks one replica; a row-sharded one fetches members given by row,
+ * forwards them by value to every shard and merges keys and member indices on the host.  The CPU backend serves the same call.
+ * Measured (MI355X, 10 M uniform rows, top-100, 8-bit replica on; profiles/r22_anyof.json), p50 per call in us,
+ * any-of / any-of with out_member / K one-member playlist requests + host merge / mean playlist request:
+ *     K = 1: 86.1 / 102.1 / 106.2 / 93.7      K = 3: 101.8 / 116.4 / 322.2 / 100.9
+ *     K = 10: 180.5 / 196.8 / 1094.5 / 133.9   K = 32: 435.3 / 456.2 / 3689.3 / 242.8
+ * The request beats the K one-member requests at every K measured; 4 - 6 % of the rows take the chains, as for the mean request
+ * (has the 300-cluster sorted catalogue as well).
+ * Not served: weights, priors, feature scales, MMR and caps; an any-of distance; candidate lists and scores; asynchronous,
+ * streamed or batched variants. */
+typedef struct {
+    uint32_t size;                    /* sizeof(mi355rec_anyof_query_t) of the caller's header */
+    uint32_t flags;                   /* must be 0 */
+    const float* members;             /* k x 12 floats (host), or NULL with ... */
+    const int64_t* rows;              /* ... k rows of the handle */
+    const int64_t* exclude_global;    /* n_exclude global ids, or NULL */
+    const mi355rec_filter_t* filter;  /* NULL, or the feature filter */
+    const int32_t* labels;            /* NULL, or n_labels labels */
+    int32_t k;
+    int32_t n_exclude;
+    int32_t n_labels;
+    int32_t topn;
+} mi355rec_anyof_query_t;             /* 64 bytes */
+typedef struct {
+    int64_t* out_idx;                 /* topn slots; required */
+    float* out_score;                 /* topn slots, or NULL */
+    int32_t* out_member;              /* topn slots, or NULL */
+    int* out_count;                   /* or NULL */
+} mi355rec_anyof_result_t;
+int mi355rec_query_anyof_request(mi355rec_t* h, const mi355rec_anyof_query_t* query, const mi355rec_request_ext_t* ext,
+                                 const mi355rec_anyof_result_t* result);
+int mi355rec_sharded_query_anyof_request(mi355rec_sharded_t* h, const mi355rec_anyof_query_t* query, const mi355rec_request_ext_t* ext,
+                                         const mi355rec_anyof_result_t* result);
 
 /* ROW UPDATES (the reference lists "Real-time Updates: Incremental index updates" among its extensions): songs are re-analysed
  * and corrected every day, and a changed row should not cost a rebuild of everything the handle keeps beside the rows.

@@ -55,6 +55,7 @@ struct Recommender::Impl {
     std::vector<int64_t> idxBuf;
     std::vector<float> scoreBuf;
     std::vector<float> lastScores;
+    std::vector<int> lastMatched;   // Query::anyOf: the matched song of every result of the last such query
 };
 
 namespace {
@@ -486,6 +487,21 @@ std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, 
         std::cerr << "Error: the Euclidean metric takes no weights, diversity, cap or prior weight" << std::endl;
         return {};
     }
+    impl->lastMatched.clear();
+    if (q.anyOf) {   // "ANY-OF REQUESTS": what the request has no field for, and what is not served with it
+        if (!q.weights.empty() || rerank || withPrior || !q.scales.empty() || q.euclidean) {
+            std::cerr << "Error: an any-of query takes no weights, diversity, cap, prior weight, feature scales or Euclidean metric" << std::endl;
+            return {};
+        }
+        if (impl->hasCandidates) {
+            std::cerr << "Error: an any-of query takes no candidate list (clearCandidates first)" << std::endl;
+            return {};
+        }
+        if (score) {
+            std::cerr << "Error: scoreSongs takes no any-of query" << std::endl;
+            return {};
+        }
+    }
     int pool = 0;
     if (rerank) {   // (DIVERSIFIED TOP-N, GROUP CAPS: pool 0 is min(1024, max(topN, 4 topN)), with a cap 8 topN)
         pool = q.pool ? q.pool : std::min(MI355REC_MAX_TOPN_FAST, std::max(topN, (capped ? 8 : 4) * std::min(topN, MI355REC_MAX_TOPN_FAST)));
@@ -521,7 +537,18 @@ std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, 
     // are those of the legacy entry points)
     const mi355rec_request_ext_t ext = requestExt(impl, q.scales.empty() ? nullptr : q.scales.data());
     int rc;
-    if (q.euclidean) {
+    std::vector<int32_t> member;
+    if (q.anyOf) {
+        mi355rec_anyof_query_t a{};
+        shared(a);
+        member.assign(static_cast<size_t>(topN), -1);
+        mi355rec_anyof_result_t res{};
+        res.out_idx = impl->idxBuf.data();
+        res.out_score = impl->scoreBuf.data();
+        res.out_member = member.data();
+        res.out_count = &count;
+        rc = mi355rec_sharded_query_anyof_request(impl->engine, &a, &ext, &res);
+    } else if (q.euclidean) {
         mi355rec_distance_query_t d{};
         shared(d);
         mi355rec_distance_result_t res{};
@@ -567,6 +594,8 @@ std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, 
     std::vector<int> results(static_cast<size_t>(count));
     for (int i = 0; i < count; ++i) results[i] = static_cast<int>(impl->idxBuf[i]);
     impl->lastScores.assign(impl->scoreBuf.begin(), impl->scoreBuf.begin() + count);
+    if (q.anyOf)
+        for (int i = 0; i < count; ++i) impl->lastMatched.push_back(q.songs[static_cast<size_t>(member[static_cast<size_t>(i)])]);
     return results;
 }
 
@@ -730,6 +759,7 @@ bool Recommender::isGPUEnabled() const { return impl_->gpuEnabled; }
 int Recommender::getSongCount() const { return impl_->numSongs; }
 
 const std::vector<float>& Recommender::lastScores() const { return impl_->lastScores; }
+const std::vector<int>& Recommender::lastMatchedSongs() const { return impl_->lastMatched; }
 
 bool Recommender::similarities(int songIndex, std::vector<float>& out) {  // Recommender.cu:184-254
     if (!impl_->initialized || songIndex < 0 || songIndex >= impl_->numSongs) {

@@ -57,7 +57,7 @@
 // accumulation and the reference chain's own rounding.  gfx950 keeps fp16
 // subnormals both in v_cvt_pk_f16_f32 and as MFMA operands (default float mode);
 // this is CHECKED on the device when the path is first used
-// (half_selfcheck_kernel): kBqMargin = 1.0e-3 if they are kept, kBqMarginFlush =
+// (half_selfcheck, replica.hip.h): kBqMargin = 1.0e-3 if they are kept, kBqMarginFlush =
 // 1.5e-3 otherwise.  tests/test_batched_margin.py checks both bounds on hostile
 // data with a numpy model of exactly this arithmetic.
 #pragma once
@@ -95,7 +95,7 @@ constexpr int kBqFinalRows = kBqFinalBlock * 16;     // rows one batch of record
 constexpr int kBqFinalAhead = 3;             // rows a finalize thread keeps in flight (a chunk = two rounds of three)
 constexpr int kBqFinalRecs = 3;              // candidate records a finalize thread takes at a time (768 per workgroup and lot)
 constexpr int kBqPassBlock = 256;            // 4 waves, one per SIMD; 4-5 workgroups per CU
-constexpr float kBqMargin = 1.0e-3f;         // fp16 subnormals kept (verified per device by half_selfcheck_kernel)
+constexpr float kBqMargin = 1.0e-3f;         // fp16 subnormals kept (verified per device by half_selfcheck)
 constexpr float kBqMarginFlush = 1.5e-3f;    // bound if they were flushed
 constexpr float kBqSlack = 4e-6f;            // fp16 hi/lo split of T' and the fused subtraction
 constexpr float kBqMinNorm2 = 1.01e-8f;      // |x| >= 1.005e-4 for rows and queries alike
@@ -127,7 +127,7 @@ __device__ __forceinline__ uint32_t bq_pack_h2(float a, float b) {
 }
 
 // ---- does this device keep fp16 subnormals? ----------------------------------------
-// half_selfcheck_kernel (replica.hip.h) answers it: out[0] = MFMA(2^-20 (an fp16 subnormal) x 1.0), out[1] = fp16(3e-6)
+// half_selfcheck (replica.hip.h) answers it: out[0] = MFMA(2^-20 (an fp16 subnormal) x 1.0), out[1] = fp16(3e-6)
 // converted back: both are non-zero iff neither the conversion nor the matrix core flushes.
 
 // ---- queries -> B fragments -----------------------------------------------------

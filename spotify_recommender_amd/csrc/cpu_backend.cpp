@@ -397,6 +397,21 @@ int node_query_labels(Node* h, const float* q12, int64_t exclude, const int32_t*
     return MI355REC_OK;
 }
 
+// "ANY-OF REQUESTS": v(x) = c_0, a = 0; for k = 1 .. K-1: if (c_k > v) { v = c_k; a = k; } — an IEEE compare, so -0.0 does not beat
+// +0.0 and a is the smallest member index that attains the maximum.  c_k is score() above: the single query's chain.
+static inline float anyof_best(const float* members, const float* qn, int k, const float* x, int* a) {
+    float v = score(members, qn[0], x);
+    *a = 0;
+    for (int m = 1; m < k; ++m) {
+        const float c = score(members + m * kDim, qn[m], x);
+        if (c > v) {
+            v = c;
+            *a = m;
+        }
+    }
+    return v;
+}
+
 // The key of every row of the catalogue under the request, 0 for a row that is not admissible (keys[i]: row i), and how many are:
 // what node_query_mean selects from and node_score_rows reads.
 static int mean_keys(Node* h, const mi355playlist::Request& r, std::vector<uint64_t>& keys, int64_t* admissible, const char** why) {
@@ -440,6 +455,7 @@ static int mean_keys(Node* h, const mi355playlist::Request& r, std::vector<uint6
     // "DISTANCE REQUESTS": m(x) = fl(fl(d2_0 + ... + d2_{k-1}) / k), d2_k the sequential fp32 sum of fl(t * t), t = fl(q_kj - x_j);
     // keys carry -m, a row whose m is not finite gets no key (it is not admissible).
     const bool dist = r.metric == mi355playlist::kDistance;
+    const bool anyof = r.metric == mi355playlist::kAnyOf;
     // "FEATURE SCALES": two steps, as on the device: members and rows scaled with one fp32 multiply per feature, then the chains
     // above on the scaled values.  The filter below tests the stored rows f.
     const float* const a = r.scales;
@@ -477,6 +493,11 @@ static int mean_keys(Node* h, const mi355playlist::Request& r, std::vector<uint6
             }
             const float mean = sum / static_cast<float>(k);
             keys[static_cast<size_t>(i)] = std::isfinite(mean) ? pack(-mean, static_cast<uint32_t>(i)) : 0;
+            continue;
+        }
+        if (anyof) {   // "ANY-OF REQUESTS": v = the best of the members' scores, in member order (the compare chain of anyof_best)
+            int a;
+            keys[static_cast<size_t>(i)] = pack(anyof_best(members, qn.data(), k, x, &a), static_cast<uint32_t>(i));
             continue;
         }
         float sum = w[0] * score(members, qn[0], x);
@@ -553,6 +574,13 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
     for (int i = 0; i < count; ++i) {
         out.idx[i] = static_cast<int64_t>(~static_cast<uint32_t>(keys[static_cast<size_t>(i)]));
         if (out.score) out.score[i] = unordered(static_cast<uint32_t>(keys[static_cast<size_t>(i)] >> 32)) + 0.0f;
+        if (out.member) {   // "ANY-OF REQUESTS": the matched member of a result row: its k chains once more
+            float qn[MI355REC_MAX_PLAYLIST];
+            for (int m = 0; m < r.k; ++m) qn[m] = query_norm(r.members + m * kDim);
+            int a = 0;
+            (void)anyof_best(r.members, qn, r.k, h->cat->feats.data() + out.idx[i] * kDim, &a);
+            out.member[i] = a;
+        }
     }
     mi355playlist::pad(out, count, topn_asked, count);
     if (r.report_distance) mi355playlist::scores_to_distances(out, topn_asked);

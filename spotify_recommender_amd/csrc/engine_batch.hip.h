@@ -458,9 +458,10 @@ int ensure_bq_alloc(mi355rec* h) {
                                    hipFuncAttributeMaxDynamicSharedMemorySize,
                                    static_cast<int>(sizeof(float) * grid * 2 * 5 + sizeof(int) * (kBqSelectBlock / 64) * 256)));
     // the tighter bound is only claimed where fp16 subnormals are demonstrably kept
-    // (half_selfcheck_kernel, replica.hip.h: its out[0] and out[1] are the matrix-core and conversion checks this verdict
+    // (half_selfcheck, replica.hip.h, through replica_build_kernel without rows: its out[0] and out[1] are the matrix-core and conversion checks this verdict
     // reads; b.qnorm holds kBqMaxQueries floats, room for its four)
-    hipLaunchKernelGGL(half_selfcheck_kernel, dim3(1), dim3(64), 0, h->stream, b.qnorm);
+    hipLaunchKernelGGL(replica_build_kernel, dim3(1), dim3(64), 0, h->stream, static_cast<const float*>(nullptr), static_cast<int64_t>(0),
+                       static_cast<int64_t>(0), static_cast<uint2*>(nullptr), b.qnorm);
     float chk[2] = {0.0f, 0.0f};
     HIP_TRY(h, hipMemcpyAsync(chk, b.qnorm, sizeof chk, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));

@@ -3,12 +3,14 @@
 // (playlist.hip.h), then the merge of merge.hip.h into the handle's pinned result slots and completion word, between
 // sync_begin and sync_finish (engine_sync.hip.h) as sync_label_query does.  No state beyond a small per-handle buffer for the call's inputs, allocated by the first call.
 // Every call of the family (filtered, weighted, diversified, capped; by value or by row) is one mi355playlist::Request
-// (playlist_request.h) through sync_playlist_query; the exported functions only fill it.
+// (playlist_request.h) through sync_playlist_query; the exported functions only fill it.  An ANY-OF request (metric kAnyOf) takes the
+// same path with anyof_scan_kernel (anyof.hip.h) at the launch and, where out_member is asked for, its attribution launch after the merge.
 // (Part of mi355rec.hip's translation unit, included after engine_labels.hip.h.)
 #pragma once
 
 #include <algorithm>
 
+#include "anyof.hip.h"
 #include "candidates.h"
 #include "engine_labels.hip.h"
 #include "engine_rowset.hip.h"
@@ -49,6 +51,10 @@ struct mi355rec_playlist {
     int64_t cand_key_cap = 0;
     std::vector<int64_t> cand_pos;              // list order -> entry of d_cand (candidates.h, positions) ...
     int64_t cand_entries = 0;                   // ... of which the scoring launch was given this many
+    // ANY-OF REQUESTS (anyof.hip.h, "ATTRIBUTION"): a(x) of the merged result's rows, stored by the attribution launch, copied back into
+    // the pinned h_member on the handle's stream.  kMaxTopK entries each, allocated with the buffers above.
+    int32_t* d_member = nullptr;
+    int32_t* h_member = nullptr;
 };
 
 namespace {
@@ -93,6 +99,8 @@ void free_playlist(mi355rec_playlist* P) {
     if (P->d_cand) (void)hipFree(P->d_cand);
     if (P->h_cand_keys) (void)hipHostFree(P->h_cand_keys);
     if (P->d_cand_keys) (void)hipFree(P->d_cand_keys);
+    if (P->d_member) (void)hipFree(P->d_member);
+    if (P->h_member) (void)hipHostFree(P->h_member);
     delete P;
 }
 
@@ -109,6 +117,8 @@ int ensure_playlist(mi355rec* h) {
     if ((e = hipHostMalloc(&P->h_buf, sizeof(PlaylistBuf), hipHostMallocDefault)) != hipSuccess) return failed(e, "hipHostMalloc(playlist buffer)");
     if ((e = hipMalloc(&P->d_exact, sizeof(unsigned long long))) != hipSuccess) return failed(e, "hipMalloc(playlist counter)");
     if ((e = hipMemset(P->d_exact, 0, sizeof(unsigned long long))) != hipSuccess) return failed(e, "hipMemset(playlist counter)");
+    if ((e = hipMalloc(&P->d_member, sizeof(int32_t) * kMaxTopK)) != hipSuccess) return failed(e, "hipMalloc(any-of members)");
+    if ((e = hipHostMalloc(&P->h_member, sizeof(int32_t) * kMaxTopK, hipHostMallocDefault)) != hipSuccess) return failed(e, "hipHostMalloc(any-of members)");
     int occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, playlist_scan_kernel, PlaylistCfg::kBlock, 0) != hipSuccess || occ < 1) occ = 1;
     (void)hipGetLastError();
@@ -284,7 +294,9 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
                         (long long)h->n, hipGetErrorString(e));
         }
     }
-    rc = sync_begin(h, topk, 1, true, ss);
+    // "ANY-OF REQUESTS": with out_member the merge is not the call's last launch (the attribution follows): it does not notify
+    const bool anyof = r.metric == mi355playlist::kAnyOf;
+    rc = sync_begin(h, topk, 1, !(anyof && r.attribute), ss);
     if (rc) return rc;
     b->shared_thr = 0ull;
     // (the staging buffer is free: the previous call on this handle has completed)
@@ -309,6 +321,18 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     if (want_grid > P->grid_cap) want_grid = P->grid_cap;
     if (want_grid < 1) want_grid = 1;
     const int grid = static_cast<int>(want_grid);
+    if (anyof) {   // "ANY-OF REQUESTS": its own kernel (anyof.hip.h), this launch's geometry, inputs and lists
+        const AnyofArg any = {k, n_excl, arg.by_row, arg.active, arg.labelled, arg.rowset, arg.rowset_flip, 0};
+        LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, anyof_scan_kernel, dim3(grid), dim3(PlaylistCfg::kBlock), h->stream,
+                     h->d_feats, q8, h->n, h->row_base, static_cast<const PlaylistBuf*>(P->d_buf), any, static_cast<const float*>(h->d_anchor), topk,
+                     h->d_block_lists, P->d_exact,
+                     reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr)),
+                     reinterpret_cast<const uint2*>(L ? L->d_row_labels : nullptr), static_cast<const uint64_t*>(nullptr),
+                     static_cast<int32_t*>(nullptr));
+        HIP_TRY(h, hipGetLastError());
+        *grid_out = grid;
+        return MI355REC_OK;
+    }
     LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, playlist_scan_kernel, dim3(grid), dim3(PlaylistCfg::kBlock),
                  h->stream, h->d_feats, q8, h->n, h->row_base, static_cast<const PlaylistBuf*>(P->d_buf), arg,
                  static_cast<const float*>(r.listed ? nullptr : h->d_anchor), topk, r.score ? P->d_cand_keys : h->d_block_lists, P->d_exact,
@@ -317,6 +341,22 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
                  reinterpret_cast<const float4*>(scan_norms ? P->d_norms : nullptr));
     HIP_TRY(h, hipGetLastError());
     *grid_out = grid;
+    return MI355REC_OK;
+}
+
+// "ANY-OF REQUESTS", ATTRIBUTION (anyof.hip.h): the same kernel once more over the `eff` merged keys in h->d_keys (the call's inputs
+// are still staged in P->d_buf), one thread per result row, then the copy of the member indices into pinned memory: both on the
+// handle's stream, behind the merge.
+int anyof_attribute(mi355rec* h, const Request& r, int eff) {
+    mi355rec_playlist* P = h->playlist;
+    const AnyofArg any = {r.k, 0, r.rows ? 1 : 0, 0u, 0, nullptr, 0u, eff};
+    hipLaunchKernelGGL(anyof_scan_kernel, dim3((eff + PlaylistCfg::kBlock - 1) / PlaylistCfg::kBlock), dim3(PlaylistCfg::kBlock), 0, h->stream,
+                       h->d_feats, static_cast<const uint4*>(nullptr), h->n, h->row_base, static_cast<const PlaylistBuf*>(P->d_buf), any,
+                       static_cast<const float*>(nullptr), 0, static_cast<uint64_t*>(nullptr), static_cast<unsigned long long*>(nullptr),
+                       static_cast<unsigned long long*>(nullptr), static_cast<const uint2*>(nullptr), static_cast<const uint64_t*>(h->d_keys),
+                       P->d_member);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(P->h_member, P->d_member, sizeof(int32_t) * static_cast<size_t>(eff), hipMemcpyDeviceToHost, h->stream));
     return MI355REC_OK;
 }
 
@@ -352,7 +392,13 @@ int sync_playlist_query(mi355rec* h, const Request& r, const Outputs& out, int m
     }
     rc = enqueue_merge(h, h->d_block_lists, grid, eff, eff, h->d_keys, ss.idx, ss.score, h->stream, ss.want);
     if (rc) return rc;
+    if (r.metric == mi355playlist::kAnyOf && r.attribute) {   // "ANY-OF REQUESTS": a(x) of the merged rows, ahead of the copy back
+        rc = anyof_attribute(h, r, eff);
+        if (rc) return rc;
+    }
     rc = sync_finish(h, ss, r.topn, out.idx, out.score, out.count);
+    if (rc == MI355REC_OK && out.member)   // (the stream has been waited for: ss.want == 0 with an attribution)
+        for (int i = 0; i < r.topn; ++i) out.member[i] = i < eff && out.idx[i] >= 0 ? h->playlist->h_member[i] : -1;
     if (rc == MI355REC_OK && r.report_distance) mi355playlist::scores_to_distances(out, r.topn);   // "DISTANCE REQUESTS": -m to sqrtf(m)
     return rc;
 }
@@ -562,6 +608,19 @@ int mi355rec_query_distance_request_scaled(mi355rec_t* h, const mi355rec_distanc
 
 int mi355rec_query_distance_request(mi355rec_t* h, const mi355rec_distance_query_t* query, const mi355rec_distance_result_t* result) {
     return mi355rec_query_distance_request_ext(h, query, nullptr, result);
+}
+
+// "ANY-OF REQUESTS": the same Request with metric = kAnyOf through the same path; its scan is anyof_scan_kernel.
+int mi355rec_query_anyof_request(mi355rec_t* h, const mi355rec_anyof_query_t* query, const mi355rec_request_ext_t* ext,
+                                 const mi355rec_anyof_result_t* result) {
+    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    mi355rec_anyof_query_t full;
+    Request r;
+    Outputs out;
+    char why[160];
+    if (mi355playlist::from_anyof_query(query, ext, result, &full, &r, &out, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    if (r.rowset && r.rowset->node) return fail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
+    return sync_playlist_query(h, r, out);
 }
 
 // "ROW PRIORS"

@@ -131,7 +131,7 @@ struct mi355rec {
         void* d_half = nullptr;
         void* d_q8 = nullptr;
         BucketBufs bsample;                            // the bucketed sample that goes with d_q8
-        float margin_mix = 0.0f, margin_mfma = 0.0f;   // of the replicas above (half_selfcheck_kernel's verdict)
+        float margin_mix = 0.0f, margin_mfma = 0.0f;   // of the replicas above (half_selfcheck's verdict)
         RowSide side;                                  // what the first handle's setters had left when its first lane was made
         // every handle of the group, the first one included: kept by mi355rec_create_lane and mi355rec_destroy, never on the query
         // path.  What mi355rec_update_rows asks whether another member has a streamed query open (engine_update.hip.h).
@@ -646,7 +646,7 @@ int build_replica_inner(mi355rec* h) {
     const bool timed = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess;
     if (timed) (void)hipEventRecord(a, h->stream);
     hipLaunchKernelGGL(replica_build_kernel, dim3(static_cast<unsigned>((n_padded + 255) / 256)), dim3(256), 0, h->stream,
-                       h->d_feats, h->n, n_padded, reinterpret_cast<uint2*>(h->d_half));
+                       h->d_feats, h->n, n_padded, reinterpret_cast<uint2*>(h->d_half), static_cast<float*>(nullptr));
     const int64_t n_quads4 = (h->n + 3) / 4 * 4;
     hipLaunchKernelGGL(q8_build_kernel, dim3(static_cast<unsigned>((n_quads4 + 255) / 256)), dim3(256), 0, h->stream,
                        h->d_feats, h->n, n_quads4, reinterpret_cast<uint32_t*>(h->d_q8), static_cast<float*>(nullptr),
@@ -659,9 +659,10 @@ int build_replica_inner(mi355rec* h) {
     if (b) (void)hipEventDestroy(b);
     HIP_TRY(h, e);
     HIP_TRY(h, hipGetLastError());
-    // which error bound the pre-filters may claim on this device (replica.hip.h, half_selfcheck_kernel)
+    // which error bound the pre-filters may claim on this device (replica.hip.h, half_selfcheck: the builder's first wave, no rows)
     float* scratch = reinterpret_cast<float*>(h->d_half_seed);   // (any scratch of >= 16 bytes will do)
-    hipLaunchKernelGGL(half_selfcheck_kernel, dim3(1), dim3(64), 0, h->stream, scratch);
+    hipLaunchKernelGGL(replica_build_kernel, dim3(1), dim3(64), 0, h->stream, static_cast<const float*>(nullptr), static_cast<int64_t>(0),
+                       static_cast<int64_t>(0), static_cast<uint2*>(nullptr), scratch);
     float chk[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     HIP_TRY(h, hipMemcpyAsync(chk, scratch, sizeof chk, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));

@@ -585,6 +585,30 @@ static bool parseMetric(int argc, char* argv[], int first, bool& euclidean) {
     return true;
 }
 
+// --match NAME from argv[first]: anyOf = true for "any" (ANY-OF REQUESTS: rank by the best-matching playlist song), false for "mean"
+// or no option.  false (the return value), with a message, for another name or without --playlist.
+static bool parseMatch(int argc, char* argv[], int first, bool playlist, bool& anyOf) {
+    anyOf = false;
+    for (int i = first; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--match") != 0) continue;
+        if (i + 1 >= argc) {
+            std::cerr << "Error: --match needs a name (mean or any)" << std::endl;
+            return false;
+        }
+        const std::string name = argv[++i];
+        if (name != "mean" && name != "any") {
+            std::cerr << "Error: --match '" << name << "': mean or any" << std::endl;
+            return false;
+        }
+        if (!playlist) {
+            std::cerr << "Error: --match goes with --playlist" << std::endl;
+            return false;
+        }
+        anyOf = name == "any";
+    }
+    return true;
+}
+
 // -n N: the first -n among argv[first .. argc-2] (the reference's rule, main.cpp:169-178: in last position it is not looked at).
 static bool parseTopN(int argc, char* argv[], int first, int& topN) {
     for (int i = first; i < argc - 1; ++i) {
@@ -624,6 +648,7 @@ struct Options {
     CandidatesOpt candidates;
     ScoreOpt score;
     bool euclidean = false;
+    bool anyOf = false;        // --match any
     std::vector<float> scales;
     Taste taste;
     DiverseOpt dv;
@@ -641,6 +666,7 @@ enum class Given {
     Scale,           // --scale
     GenreFiltered,   // --genre under --song / --id by unscaled cosine, beside a filter or a row set ...
     GenreReranked,   // ... and beside a re-rank: --playlist <one id> and the distance and scaled requests serve those pairs
+    MatchAny,        // --match any
 };
 struct Refusal {
     Given given;
@@ -656,12 +682,15 @@ static const Refusal kRefusals[] = {
     {Given::GenreFiltered, {"--seen", "--only", "--candidates", "--score"}, "%s cannot be combined with --genre here: use --playlist <one id> --genre ..."},
     {Given::GenreReranked, {"--max-per-artist"}, "%s cannot be combined with --genre"},
     {Given::GenreReranked, {"--diverse"}, "%s cannot be combined with --genre"},
+    {Given::MatchAny, kRequestOptions, "--match any cannot be combined with %s (any-of requests take --genre, --where, --seen and --only only)"},
+    {Given::MatchAny, {"--scale", "--candidates", "--score"}, "--match any cannot be combined with %s (any-of requests take --genre, --where, --seen and --only only)"},
 };
 
 // true, with the message, when `given` holds and the command line has an option that one of its rows refuses beside it.
 static bool refused(int argc, char* argv[], int first, const Options& o, Given given) {
     const bool genreAlone = !o.playlist && !o.nearest() && !o.genres.empty();
-    if (!(given == Given::Euclidean ? o.euclidean : given == Given::Scale ? !o.scales.empty() : genreAlone)) return false;
+    if (!(given == Given::Euclidean ? o.euclidean : given == Given::Scale ? !o.scales.empty() : given == Given::MatchAny ? o.anyOf : genreAlone))
+        return false;
     for (const Refusal& r : kRefusals) {
         if (r.given != given) continue;
         for (int i = first; i < argc; ++i)
@@ -687,6 +716,12 @@ static bool parseOptions(int argc, char* argv[], Options& o) {
     if (!parseWhere(argc, argv, first, o.ranges) || !parseRowSet(argc, argv, first, o.rowSet)) return false;
     if (!parseCandidates(argc, argv, first, o.candidates) || !parseScore(argc, argv, first, o.score)) return false;
     if (!parseMetric(argc, argv, first, o.euclidean) || refused(argc, argv, first, o, Given::Euclidean)) return false;
+    if (!parseMatch(argc, argv, first, o.playlist, o.anyOf) || refused(argc, argv, first, o, Given::MatchAny)) return false;
+    if (o.anyOf && o.euclidean) {
+        std::cerr << "Error: --match any cannot be combined with --metric euclidean (any-of requests take --genre, --where, --seen and --only only)"
+                  << std::endl;
+        return false;
+    }
     if (!parseScale(argc, argv, first, o.scales) || refused(argc, argv, first, o, Given::Scale)) return false;
     printScales(o.scales);
     if (refused(argc, argv, first, o, Given::GenreFiltered)) return false;
@@ -862,6 +897,7 @@ static bool queryMode(const Options& o) {
         q.priorWeight = o.pr.on ? o.pr.weight : 0.0f;   // (BETA 0 is the call without a prior)
         q.scales = o.scales;
         q.euclidean = o.euclidean;
+        q.anyOf = o.anyOf;
         if (o.score.on) listedValues = recommender.scoreSongs(q, listed, &eligible);
         else if (q.topN > 0) recs = recommender.recommendQuery(q);
     }
@@ -869,6 +905,7 @@ static bool queryMode(const Options& o) {
 
     // 7. the query's block, then the recommendations (a distance or scaled request prints their values)
     const std::vector<float> values = recommender.lastScores();
+    const std::vector<int> matched = recommender.lastMatchedSongs();   // --match any: the playlist song each recommendation matched
     if (song) {
         printQuerySong(catalogue, genreMap, o);
     } else {
@@ -880,6 +917,7 @@ static bool queryMode(const Options& o) {
             if (!printEntry(catalogue, genreMap, members[i], i + 1, "  ", weight.str())) return false;
         }
         std::cout << "----------------------------------------------" << std::endl;
+        if (o.anyOf) std::cout << "Matching: the best of the playlist's songs (--match any)" << std::endl;
     }
     if (o.score.on) {   // --score: the listed tracks in file order, nothing is recommended
         std::cout << "\nValues of " << listed.size() << " listed tracks:\n" << std::endl;
@@ -897,6 +935,7 @@ static bool queryMode(const Options& o) {
     for (size_t i = 0; i < recs.size(); ++i) {
         std::ostringstream value;
         if (nearest) value << "  (" << (o.euclidean ? "distance " : "score ") << values[i] << ")";
+        if (o.anyOf && i < matched.size()) value << "  (matches \"" << catalogue.trackNames[static_cast<size_t>(matched[i])] << "\")";
         if (!printEntry(catalogue, genreMap, recs[i], i + 1, "", value.str())) return false;
         if (i + 1 < recs.size()) std::cout << std::endl;
     }

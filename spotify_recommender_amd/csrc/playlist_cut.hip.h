@@ -333,4 +333,65 @@ __device__ __forceinline__ void playlist_cut_apply(const PlaylistCut& c, uint32_
         if (!(special[r] || D[r] >= cut[r])) mask &= ~(1u << r);
 }
 
+// ANY (anyof.hip.h, "ANY-OF REQUESTS": the ranking value is v(x) = max_k c_k(x), c_k the cosine of the row with member q_k; this is
+// anyof_scan_kernel's pre-filter, not playlist_scan_kernel's: it has no PlCutKind, the launch either has it for every member or is off).
+//   * one PLAIN cut PER MEMBER.  Member k alone is the PLAIN request with K = 1, w_0 = 1, W = 1: its u is u_k = fl(q_kj / |q_k|)
+//     (fl(1 x) = x and x / 1 = x: the prologue's arithmetic with nothing added), un_k = |u_k| by query_norm, the replica's query is
+//     q8_query(u_k, un_k) with its margin M_k, and
+//         margin_k = un_k M_k + kPlChainErr + (3 * 1 + 32) kPlUlp,      cut_k(T) = q8_threshold( fl( fl(T - margin_k) / un_k ) ),
+//     all through playlist_cut_setup and playlist_cut_plain above with k = 1: the same functions, so PLAIN's proof is this one's.
+//   * the test, per row with its replica bytes in hand: D_k = the integer dot product with member k's digits,
+//         keep = special || OR_k ( D_k >= cut_k ).
+//   * SOUNDNESS, for T the workgroup's threshold score (of either sign).  v(x) >= T needs some k with c_k(x) >= T: v IS one of the
+//     c_k (the compare chain selects, it computes nothing: no rounding is added).  PLAIN at K = 1 shows D_k < cut_k => c_k(x) < T
+//     for a valid row and a member whose norm lies in [kBqMinNorm, kBqMaxNorm].  So a row with D_k < cut_k for EVERY k has every
+//     c_k(x) < T, hence v(x) < T: its key lies below the threshold whatever its row id, and ruling it out loses nothing.
+//   * the cuts are refreshed (every member's, by the first K threads, into LDS) whenever the workgroup's threshold moves; until
+//     there is one every cut is kPlCutNone and every row is kept.
+//   * OFF for the launch (every row takes the chains) when the handle has no replica, when any member's norm lies outside
+//     [kBqMinNorm, kBqMaxNorm] or is not finite, or when any member's q8_query is not ok (playlist_cut_setup's verdict per member;
+//     un_k is 1 within a few ulp, so kPlMinMeanNorm never bites).  Rows whose first replica byte is 0x80 always take the chains.
+//   * tests/test_anyof_margin.py checks this with tests/anyof_cut_model.py (a numpy mirror that calls playlist_cut_model.py's
+//     functions as this calls the ones above) against tests/anyof_oracle.py, and that it is not vacuous.
+// The digits (hi[0..3), lo[0..3)) of one member, its |u_k| and margin_k; true: the cut may be claimed for this member.
+__device__ __forceinline__ bool playlist_cut_any_member(bool usable, const float* __restrict__ q, float qn, int (&digits)[6], float& un,
+                                                        float& margin) {
+    float u[kDim];
+#pragma unroll
+    for (int j = 0; j < kDim; ++j) u[j] = q[j] / qn;
+    un = query_norm(u);
+    PlaylistCut c;
+    const Q8Query hq = playlist_cut_setup(c, usable, false, false, false, false, 0.0f, 1, u, un, 1.0f, nullptr, nullptr, nullptr);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) digits[j] = hq.hi[j], digits[3 + j] = hq.lo[j];
+    margin = c.margin_mean;
+    return c.kind == kPlCutPlain;
+}
+// Member k's integer cut at the threshold score t.
+__device__ __forceinline__ int playlist_cut_any(float un, float margin, float t) {
+    PlaylistCut c;
+    c.un = un, c.margin_mean = margin;
+    return playlist_cut_plain(c, t);
+}
+// Clears the mask bit of every row of a lane's quad that EVERY member's cut rules out.  digits, cut: the k members' (LDS; read at
+// uniform addresses and moved to scalar registers).
+__device__ __forceinline__ void playlist_cut_any_apply(uint32_t& mask, const HalfTile& tile, const int (*__restrict__ digits)[6],
+                                                       const int* __restrict__ cut, int k) {
+    uint32_t keep = 0u;
+    bool special[4];
+    for (int m = 0; m < k; ++m) {   // uniform
+        Q8Query q;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) q.hi[j] = q8_uniform(digits[m][j]), q.lo[j] = q8_uniform(digits[m][3 + j]);
+        const int cut_m = q8_uniform(cut[m]);
+        int D[4];
+        q8_dot4(q, tile, D, special);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) keep |= D[r] >= cut_m ? 1u << r : 0u;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) keep |= special[r] ? 1u << r : 0u;
+    mask &= keep;
+}
+
 }  // namespace mi355

@@ -19,7 +19,7 @@
 
 namespace mi355playlist {
 
-enum Metric { kCosine = 0, kDistance = 1 };
+enum Metric { kCosine = 0, kDistance = 1, kAnyOf = 2 };
 
 struct Request {
     const float* members = nullptr;             // k x 12 floats by value, or null with ...
@@ -41,6 +41,8 @@ struct Request {
     float prior_weight = 0.0f;                  // ... beta, finite, |beta| <= MI355REC_MAX_PRIOR_WEIGHT; 0.0f is the call without a prior
     int metric = kCosine;                       // kDistance ("DISTANCE REQUESTS"): rank by m(x), the mean squared distance to the
                                                 // ... members, ascending; keys and scores carry -m
+                                                // kAnyOf ("ANY-OF REQUESTS"): rank by v(x), the best of the members' cosines
+    bool attribute = false;                     // (kAnyOf) the member index a(x) of every result is wanted (Outputs::member)
     bool report_distance = false;               // (kDistance) the score output holds sqrtf(m); false: -m itself, what a node
                                                 // ... handle's merge over shards compares
     const float* scales = nullptr;              // null, or 12 checked feature scales a_j ("FEATURE SCALES"): the call is the same
@@ -108,6 +110,7 @@ struct Outputs {
     float* mmr = nullptr;       // diverse only
     int* count = nullptr;
     int* pool_rows = nullptr;   // capped only: P'
+    int32_t* member = nullptr;  // "ANY-OF REQUESTS" only: a(x) of every result
 };
 
 // idx / score / mmr [from, topn) padded with -1 / 0.0f / 0.0f, and *count set.
@@ -116,6 +119,7 @@ inline void pad(const Outputs& out, int from, int topn, int count) {
         out.idx[i] = -1;
         if (out.score) out.score[i] = 0.0f;
         if (out.mmr) out.mmr[i] = 0.0f;
+        if (out.member) out.member[i] = -1;
     }
     if (out.count) *out.count = count;
 }
@@ -449,6 +453,59 @@ inline bool from_distance_query(const mi355rec_distance_query_t* q, const mi355r
     r->report_distance = true;
     *out = {res->out_idx, res->out_distance, nullptr, res->out_count, nullptr};
     return false;
+}
+
+// The C-ABI's any-of request (include/mi355rec_diag.h, "ANY-OF REQUESTS") as the same Request (metric = kAnyOf) and Outputs: the
+// size rules of from_query, flags must be 0, no feature scales.  True when the structs cannot be used; then msg[0..cap) says why.
+inline bool from_anyof_query(const mi355rec_anyof_query_t* q, const mi355rec_request_ext_t* ext, const mi355rec_anyof_result_t* res,
+                             mi355rec_anyof_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
+    if (!q || !res) {
+        std::snprintf(msg, cap, "null argument");
+        return true;
+    }
+    static const size_t ends[] = {offsetof(mi355rec_anyof_query_t, flags),          offsetof(mi355rec_anyof_query_t, members),
+                                  offsetof(mi355rec_anyof_query_t, rows),           offsetof(mi355rec_anyof_query_t, exclude_global),
+                                  offsetof(mi355rec_anyof_query_t, filter),         offsetof(mi355rec_anyof_query_t, labels),
+                                  offsetof(mi355rec_anyof_query_t, k),              offsetof(mi355rec_anyof_query_t, n_exclude),
+                                  offsetof(mi355rec_anyof_query_t, n_labels),       offsetof(mi355rec_anyof_query_t, topn),
+                                  sizeof(mi355rec_anyof_query_t)};
+    static_assert(sizeof(mi355rec_anyof_query_t) == offsetof(mi355rec_anyof_query_t, topn) + sizeof(int32_t) && sizeof(mi355rec_anyof_query_t) == 64,
+                  "no tail padding: the struct ends where its last field ends");
+    bool known = false;
+    for (size_t e : ends) known = known || q->size == e;
+    if (!known) {
+        std::snprintf(msg, cap, "any-of query of size %u: not the end of a field of the %u bytes this library reads",
+                      static_cast<unsigned>(q->size), static_cast<unsigned>(sizeof *full));
+        return true;
+    }
+    std::memset(full, 0, sizeof *full);
+    std::memcpy(full, q, q->size);
+    if (full->flags != 0u) {
+        std::snprintf(msg, cap, "flags 0x%x in an any-of query: must be 0 (weights, diversified and capped calls and priors are not served)",
+                      static_cast<unsigned>(full->flags));
+        return true;
+    }
+    if (full->members && full->rows) {
+        std::snprintf(msg, cap, "members by value and by row in one any-of query");
+        return true;
+    }
+    if (!full->members && !full->rows) {
+        std::snprintf(msg, cap, "an any-of query needs members by value or by row");
+        return true;
+    }
+    *r = request(full->members, full->rows, nullptr, full->k, full->exclude_global, full->n_exclude, full->filter, full->topn);
+    r->labels = full->labels;
+    r->n_labels = full->n_labels;
+    r->metric = kAnyOf;
+    r->attribute = res->out_member != nullptr;
+    *out = {res->out_idx, res->out_score, nullptr, res->out_count, nullptr, res->out_member};
+    mi355rec_request_ext_t x;
+    if (from_ext(ext, &x, msg, cap)) return true;
+    if (x.feature_scales) {
+        std::snprintf(msg, cap, "any-of requests take no feature scales");
+        return true;
+    }
+    return apply_ext(x, r, msg, cap);
 }
 
 // from_distance_query with the extras of the _ext entry points (null, or null pointers: from_distance_query itself).

@@ -82,23 +82,6 @@ __device__ __forceinline__ void half_pack_row(const float4& a, const float4& b, 
     }
 }
 
-// One thread per row; rows [n, n_padded) (n_padded even) are padding and hold NaN.
-__global__ __launch_bounds__(256) void replica_build_kernel(const float* __restrict__ feats, int64_t n, int64_t n_padded,
-                                                            uint2* __restrict__ half) {
-    const int64_t row = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (row >= n_padded) return;
-    uint32_t p[6] = {kHalfNaN2, kHalfNaN2, kHalfNaN2, kHalfNaN2, kHalfNaN2, kHalfNaN2};
-    if (row < n) {
-        const float4* src = reinterpret_cast<const float4*>(feats) + row * 3;
-        const float4 a = src[0], b = src[1], c = src[2];
-        half_pack_row(a, b, c, replica_norm2(a, b, c), p);
-    }
-    uint2* dst = half + row * 3;
-    dst[0] = make_uint2(p[0], p[1]);
-    dst[1] = make_uint2(p[2], p[3]);
-    dst[2] = make_uint2(p[4], p[5]);
-}
-
 // ---- the query in fp16 --------------------------------------------------------------
 struct HalfQuery {
     uint32_t h[6];   // fp16 pairs of q / |q| (wave-uniform: scalar registers)
@@ -136,8 +119,9 @@ __device__ __forceinline__ float half_dot(const uint32_t (&qh)[6], uint32_t a0, 
 // (batched.hip.h, "Margin").  Three places matter: v_cvt_pk_f16_f32 when the replica is built (out[1]: fp16(3e-6)
 // converted back), v_fma_mix_f32's fp16 operands in the single-query scan (out[2], out[3]: a subnormal on the row
 // side, on the query side, times 1.0) and the matrix core in the multi-query pass (out[0]; out[0] and out[1] are also the batched path's check, ensure_bq_alloc).
-// One wave; the host compares with the exact values.
-__global__ void half_selfcheck_kernel(float* out) {
+// One wave; the host compares with the exact values.  It rides in replica_build_kernel (below) rather than being a kernel of its own:
+// the library keeps to sixty kernels, and both are create-time work.
+__device__ __forceinline__ void half_selfcheck(float* out) {
     const int lane = threadIdx.x;
     bq_h8 A = {0, 0, 0, 0, 0, 0, 0, 0}, B = {0, 0, 0, 0, 0, 0, 0, 0};
     if (lane < 32) {
@@ -160,6 +144,26 @@ __global__ void half_selfcheck_kernel(float* out) {
         out[2] = row_side;
         out[3] = query_side;
     }
+}
+
+// One thread per row; rows [n, n_padded) (n_padded even) are padding and hold NaN.
+// selfcheck != null (uniform): the first wave of the first workgroup also answers half_selfcheck above into selfcheck[0..4), before
+// its rows (a whole wave, every lane active, as the matrix core needs).  The check alone: one workgroup, n = n_padded = 0.
+__global__ __launch_bounds__(256) void replica_build_kernel(const float* __restrict__ feats, int64_t n, int64_t n_padded,
+                                                            uint2* __restrict__ half, float* __restrict__ selfcheck) {
+    if (selfcheck && blockIdx.x == 0 && threadIdx.x < 64) half_selfcheck(selfcheck);
+    const int64_t row = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (row >= n_padded) return;
+    uint32_t p[6] = {kHalfNaN2, kHalfNaN2, kHalfNaN2, kHalfNaN2, kHalfNaN2, kHalfNaN2};
+    if (row < n) {
+        const float4* src = reinterpret_cast<const float4*>(feats) + row * 3;
+        const float4 a = src[0], b = src[1], c = src[2];
+        half_pack_row(a, b, c, replica_norm2(a, b, c), p);
+    }
+    uint2* dst = half + row * 3;
+    dst[0] = make_uint2(p[0], p[1]);
+    dst[1] = make_uint2(p[2], p[3]);
+    dst[2] = make_uint2(p[4], p[5]);
 }
 
 #ifdef MI355REC_EXPERIMENTS   // the single-query scan over THIS replica is an A/B route of tools builds (single queries stream

@@ -783,6 +783,43 @@ int members_by_value(mi355rec_sharded_t* h, Request& r, float* members, int64_t*
     return MI355REC_OK;
 }
 
+// "ANY-OF REQUESTS" with out_member on a ROW-SHARDED catalogue (members by value, the workers drained): merge_over_shards' merge with
+// each key's member index carried through it (rows are distinct across shards, so the keys are).
+int anyof_over_shards(mi355rec_sharded_t* h, const Request& r, const Outputs& out) {
+    const int topn = r.topn;
+    std::vector<std::pair<mi355rec_key_t, int32_t>> keys;
+    std::vector<int64_t> idx;
+    std::vector<float> sc;
+    std::vector<int32_t> mem;
+    try {
+        idx.resize(static_cast<size_t>(topn));
+        sc.resize(static_cast<size_t>(topn));
+        mem.resize(static_cast<size_t>(topn));
+        keys.reserve(static_cast<size_t>(topn) * h->shards.size());
+    } catch (const std::bad_alloc&) {
+        return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for %d results per shard", topn);
+    }
+    for (Shard& s : h->shards) {
+        if (s.hi <= s.lo) continue;
+        S_HIP(h, hipSetDevice(s.device));
+        int c = 0;
+        const int rc = mi355node::query_playlist(s.engine, r, {idx.data(), sc.data(), nullptr, &c, nullptr, mem.data()});
+        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", s.device, mi355rec_last_error(s.engine));
+        for (int i = 0; i < c; ++i)
+            keys.emplace_back(mi355rec_pack_key(sc[static_cast<size_t>(i)], idx[static_cast<size_t>(i)]), mem[static_cast<size_t>(i)]);
+    }
+    const size_t count = keys.size() < static_cast<size_t>(topn) ? keys.size() : static_cast<size_t>(topn);
+    std::partial_sort(keys.begin(), keys.begin() + count, keys.end(),
+                      [](const std::pair<mi355rec_key_t, int32_t>& a, const std::pair<mi355rec_key_t, int32_t>& b) { return a.first > b.first; });
+    for (size_t i = 0; i < count; ++i) {
+        out.idx[i] = mi355rec_key_row(keys[i].first);
+        if (out.score) out.score[i] = mi355rec_key_score(keys[i].first);
+        out.member[i] = keys[i].second;
+    }
+    mi355playlist::pad(out, static_cast<int>(count), topn, static_cast<int>(count));
+    return MI355REC_OK;
+}
+
 // Every call of the family on the node handle: the checks (the catalogue's global rows are known here), the members of a
 // by-row call by value where no single handle can read them, then the CPU backend, the one handle that holds the whole
 // catalogue, or every shard and a host merge.
@@ -813,6 +850,7 @@ int sharded_playlist(mi355rec_sharded_t* h, Request r, const Outputs& out) {
     if (rc) return rc;
     // every shard gets the whole exclusion list and matches the ids of its own rows ("DISTANCE REQUESTS": the shards answer
     // with -m, what the merge's keys compare; the distances are taken from the merged list)
+    if (r.metric == mi355playlist::kAnyOf && out.member) return anyof_over_shards(h, r, out);
     const bool report_distance = r.report_distance;
     r.report_distance = false;
     ShardLists lists;
@@ -1009,6 +1047,19 @@ int mi355rec_sharded_query_distance_request_scaled(mi355rec_sharded_t* h, const 
 int mi355rec_sharded_query_distance_request(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
                                             const mi355rec_distance_result_t* result) {
     return mi355rec_sharded_query_distance_request_ext(h, query, nullptr, result);
+}
+
+// ANY-OF REQUESTS (include/mi355rec_diag.h): the same Request with metric = kAnyOf through sharded_playlist; a row-sharded catalogue
+// carries each key's member index through its host merge (anyof_over_shards).
+int mi355rec_sharded_query_anyof_request(mi355rec_sharded_t* h, const mi355rec_anyof_query_t* query, const mi355rec_request_ext_t* ext,
+                                         const mi355rec_anyof_result_t* result) {
+    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    mi355rec_anyof_query_t full;
+    Request r;
+    Outputs out;
+    char why[160];
+    if (mi355playlist::from_anyof_query(query, ext, result, &full, &r, &out, why, sizeof why)) return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    return sharded_playlist(h, r, out);
 }
 
 // CANDIDATE LISTS (include/mi355rec_diag.h): the list travels in the Request; its ids are rows of the catalogue.  One handle takes it

@@ -74,7 +74,7 @@ int main(int argc, char** argv) {
     // the same two passes reading the fp16 replica
     uint2* half;
     CK(hipMalloc(&half, (size_t)((n + 1) & ~1ll) * 24));
-    replica_build_kernel<<<(unsigned)((((n + 1) & ~1ll) + 255) / 256), 256>>>(feats, n, (n + 1) & ~1ll, half);
+    replica_build_kernel<<<(unsigned)((((n + 1) & ~1ll) + 255) / 256), 256>>>(feats, n, (n + 1) & ~1ll, half, static_cast<float*>(nullptr));
     CK(hipDeviceSynchronize());
 #define PASSR(COLLECT) [&] { hipLaunchKernelGGL((bq_pass_kernel<NB, COLLECT, 0, true>), dim3(grid), dim3(kBqPassBlock), 0, 0, feats, n, tiles, 1, bfrag, gmax, cand_count, cand_rows, counters, special, static_cast<const uint2*>(half)); }
     report("pass 2 (no hits), fp16 replica", median_ms(PASSR(true), 7));
