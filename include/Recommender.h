@@ -209,6 +209,9 @@ public:
     // instead of the mean; lastScores() holds that similarity and lastMatchedSongs() the song of `songs` each result matched.  With
     // anyOf, weights, diverse, maxPerArtist, priorWeight, scales and euclidean are refused with a message and {}, and so are a set
     // candidate list (setCandidates) and scoreSongs.  The row set of setRowSet applies.
+    // manhattan (include/mi355rec_diag.h, "MANHATTAN REQUESTS"): songs rank by their mean L1 distance to `songs`, nearest first;
+    // lastScores() holds the distances.  With manhattan, weights, diverse, maxPerArtist, priorWeight, scales, euclidean and anyOf are
+    // refused with a message and {}, and so are a set candidate list (setCandidates) and scoreSongs.  The row set of setRowSet applies.
     struct Query {
         std::vector<int> songs;            // 1 to 32
         std::vector<float> weights;        // one per song, or none
@@ -224,6 +227,7 @@ public:
         bool euclidean = false;
         int topN = 10;
         bool anyOf = false;
+        bool manhattan = false;
     };
     std::vector<int> recommendQuery(const Query& query);
     // Per result of the last recommendQuery with anyOf: the catalogue index of the matched song of query.songs (the first of them

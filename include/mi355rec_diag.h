@@ -38,6 +38,8 @@
  *     (mi355rec_update_rows, _update_info, _replica_entries and the node-handle twin);
  *   - ANY-OF REQUESTS: the top-N rows by their best match among up to 32 members, with the matched member's index per result
  *     (mi355rec_query_anyof_request and its node-handle twin);
+ *   - MANHATTAN REQUESTS: the nearest rows by L1 distance to up to 32 members, with the playlist request's exclusion list,
+ *     feature filter, label set and row set (mi355rec_query_manhattan_request and its node-handle twin);
  *   - test hooks, compiled in only with -DMI355REC_TEST_HOOKS (spotify_recommender_amd/build.py builds
  *     libmi355rec_testhooks.so for tests/; the product library does not export them).
  */
@@ -1067,6 +1069,71 @@ int mi355rec_query_anyof_request(mi355rec_t* h, const mi355rec_anyof_query_t* qu
                                  const mi355rec_anyof_result_t* result);
 int mi355rec_sharded_query_anyof_request(mi355rec_sharded_t* h, const mi355rec_anyof_query_t* query, const mi355rec_request_ext_t* ext,
                                          const mi355rec_anyof_result_t* result);
+
+/* MANHATTAN REQUESTS (the reference lists "Additional Metrics: Euclidean, Manhattan distance" among its extensions): the top-N
+ * rows NEAREST by L1 distance to up to 32 members.  Where the distance request squares a coordinate's difference, this one does
+ * not: one badly-off feature does not dominate.  mi355rec_manhattan_query_t has the field list of mi355rec_distance_query_t and
+ * carries its own size under the same rules.
+ *   members / rows   exactly one is non-NULL: k x 12 floats by value, or k rows of the handle (never returned);
+ *                    1 <= k <= MI355REC_MAX_PLAYLIST;
+ *   exclude_global / n_exclude, filter, labels / n_labels   as in the playlist request;
+ *   topn             in [1, MI355REC_MAX_TOPN_FAST];       flags   must be 0.
+ * mi355rec_manhattan_result_t: out_idx (topn slots) is required; out_distance (topn slots) and out_count may be NULL.
+ * RANKING VALUE, per row x, bit for bit in fp32, never fused:
+ *     d1_k(x) = acc after j = 0..11 of:  t = fl(q_kj - x_j);  acc = fl(acc + fabsf(t))              (acc starts at 0.0f)
+ *     m(x)    = fl( fl(...fl(d1_0 + d1_1) + ... + d1_{K-1}) / (float)K )                            (members in order)
+ * Rows rank by m ascending, then row ascending.  Keys are packed from -m as the distance request's are (m = 0 packs as +0.0);
+ * out_distance[i] = m itself (0.0f - score: no root).  A row whose m is not finite forms no key.  Admissibility is the playlist
+ * request's (the row set of `ext`, the label set, the filter, not a member row, not excluded); count = min(topn, |admissible
+ * rows|), past it the padding is -1 / +0.0f.
+ * ext: may be NULL; its row set is honoured with the _ext calls' ownership checks; a non-NULL feature_scales is INVALID_ARG
+ * ("manhattan requests take no feature scales").  There are no _ext or _scaled variants: this one entry point takes ext.
+ * INVALID_ARG (with a message): flags != 0; both or neither of members and rows; a bad size; everything the playlist request
+ * refuses for the fields the two share (same limits, same messages).
+ * Device: manhattan_scan_kernel (csrc/anyof.hip.h, "MANHATTAN": any-of's pieces instantiated for this metric in a kernel of their
+ * own): the playlist scan's launch, the members in LDS.
+ * With the 8-bit replica and the handle's per-row norms (the distance request's: built on first use, dropped by
+ * mi355rec_rebuild_replica, kept exact by mi355rec_update_rows) a row costs 16 B: its bytes times its stored norm give a point
+ * within half a replica step per coordinate of the row, and the PER-MEMBER sum of L1 distances to that point, less 12 half steps,
+ * bounds m from below; a row whose bound exceeds the workgroup's threshold is ruled out, the others take the chains on the fp32
+ * row.  Replica on and off answer alike, bit for bit.  mi355rec_playlist_counters counts these calls and their rows_exact.
+ * Node handle: one shard forwards; a replicated placement asks one replica; a row-sharded one fetches members given by row,
+ * forwards them by value to every shard and merges keys of -m on the host.  The CPU backend runs the same chain.
+ * Measured (MI355X, 10 M uniform rows, top-100, members by row; profiles/r23_manhattan.json, tools/run_manhattan.py), p50 per call
+ * in us, on a handle with the replica / on one without, and the distance and any-of requests with the replica beside it:
+ *     K = 1: 97.2 / 192.5, 97.8, 89.6      K = 3: 113.8 / 195.3, 100.1, 103.8
+ *     K = 10: 184.2 / 212.3, 119.0, 184.0   K = 32: 280.0 / 270.9, 187.7, 434.4
+ * The bound's arithmetic grows with K as the chains' does.  With the bound at every K (profiles/r23_manhattan_cut_every_k.json) it
+ * wins at K = 1, 3, 10 (97.7 / 113.6 / 185.4 us) and loses at K = 32 (416.1 us against 270.9 without a replica), so it is used up
+ * to K = 10: ABOVE THAT THE LAUNCH IS THE EXACT PATH WHATEVER THE HANDLE HOLDS (the K = 32 figure "with the replica" above is the
+ * chains on every row).  3.5 - 4.3 % of the rows take the chains up to K = 10.  Against the parent commit's library
+ * (profiles/r23_manhattan_ab.json) the any-of, playlist and distance requests did not move (five alternating
+ * children a side: no ratio above 1, each inside the parent's own spread).
+ * Not served: weights, priors, feature scales, MMR and caps; candidate lists and candidate scores; asynchronous, streamed and
+ * batched variants; the torch.distributed ShardedEngine; a cheaper cut for large K (per coordinate mean_k |q_kj - t| is convex
+ * and piecewise linear in t: an evaluation that does not touch all K members is the next step). */
+typedef struct {
+    uint32_t size;                    /* sizeof(mi355rec_manhattan_query_t) of the caller's header */
+    uint32_t flags;                   /* must be 0 */
+    const float* members;             /* k x 12 floats (host), or NULL with ... */
+    const int64_t* rows;              /* ... k rows of the handle */
+    const int64_t* exclude_global;    /* n_exclude global ids, or NULL */
+    const mi355rec_filter_t* filter;  /* NULL, or the feature filter */
+    const int32_t* labels;            /* NULL, or n_labels labels */
+    int32_t k;
+    int32_t n_exclude;
+    int32_t n_labels;
+    int32_t topn;
+} mi355rec_manhattan_query_t;         /* 64 bytes */
+typedef struct {
+    int64_t* out_idx;                 /* topn slots; required */
+    float* out_distance;              /* topn slots, or NULL: m(x) */
+    int* out_count;                   /* or NULL */
+} mi355rec_manhattan_result_t;
+int mi355rec_query_manhattan_request(mi355rec_t* h, const mi355rec_manhattan_query_t* query, const mi355rec_request_ext_t* ext,
+                                     const mi355rec_manhattan_result_t* result);
+int mi355rec_sharded_query_manhattan_request(mi355rec_sharded_t* h, const mi355rec_manhattan_query_t* query,
+                                             const mi355rec_request_ext_t* ext, const mi355rec_manhattan_result_t* result);
 
 /* ROW UPDATES (the reference lists "Real-time Updates: Incremental index updates" among its extensions): songs are re-analysed
  * and corrected every day, and a changed row should not cost a rebuild of everything the handle keeps beside the rows.

@@ -92,6 +92,18 @@ class AnyOfResult(ctypes.Structure):
     _fields_ = [("out_idx", c_void_p), ("out_score", c_void_p), ("out_member", c_void_p), ("out_count", POINTER(c_int))]
 
 
+class ManhattanQuery(ctypes.Structure):
+    """mi355rec_manhattan_query_t (include/mi355rec_diag.h, MANHATTAN REQUESTS); `size` is sizeof of this struct, flags 0."""
+    _fields_ = [("size", c_uint32), ("flags", c_uint32), ("members", c_void_p), ("rows", c_void_p), ("exclude_global", c_void_p),
+                ("filter", POINTER(Filter)), ("labels", c_void_p), ("k", c_int32), ("n_exclude", c_int32), ("n_labels", c_int32),
+                ("topn", c_int32)]
+
+
+class ManhattanResult(ctypes.Structure):
+    """mi355rec_manhattan_result_t: every pointer but out_idx may be NULL; out_distance holds m(x)."""
+    _fields_ = [("out_idx", c_void_p), ("out_distance", c_void_p), ("out_count", POINTER(c_int))]
+
+
 ROWSET_EXCLUDE, ROWSET_ONLY = 0, 1   # MI355REC_ROWSET_* (ROW SETS)
 MAX_CANDIDATES = 1 << 20             # MI355REC_MAX_CANDIDATES (CANDIDATE LISTS)
 
@@ -323,6 +335,9 @@ SIGNATURES = {
     # ANY-OF REQUESTS: top-N by the best-matching member, with the matched member's index; one entry point takes the ext
     "mi355rec_query_anyof_request": (c_int, [c_void_p, POINTER(AnyOfQuery), POINTER(RequestExt), POINTER(AnyOfResult)]),
     "mi355rec_sharded_query_anyof_request": (c_int, [c_void_p, POINTER(AnyOfQuery), POINTER(RequestExt), POINTER(AnyOfResult)]),
+    # MANHATTAN REQUESTS: nearest-by-L1 top-N; one entry point takes the ext
+    "mi355rec_query_manhattan_request": (c_int, [c_void_p, POINTER(ManhattanQuery), POINTER(RequestExt), POINTER(ManhattanResult)]),
+    "mi355rec_sharded_query_manhattan_request": (c_int, [c_void_p, POINTER(ManhattanQuery), POINTER(RequestExt), POINTER(ManhattanResult)]),
     # ROW UPDATES: rows change in place, every route answers as a freshly created handle would
     "mi355rec_update_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "mi355rec_sharded_update_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

@@ -502,6 +502,21 @@ std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, 
             return {};
         }
     }
+    if (q.manhattan) {   // "MANHATTAN REQUESTS": what the request has no field for, and what is not served with it
+        if (!q.weights.empty() || rerank || withPrior || !q.scales.empty() || q.euclidean || q.anyOf) {
+            std::cerr << "Error: a Manhattan query takes no weights, diversity, cap, prior weight, feature scales, Euclidean metric or any-of matching"
+                      << std::endl;
+            return {};
+        }
+        if (impl->hasCandidates) {
+            std::cerr << "Error: a Manhattan query takes no candidate list (clearCandidates first)" << std::endl;
+            return {};
+        }
+        if (score) {
+            std::cerr << "Error: scoreSongs takes no Manhattan query" << std::endl;
+            return {};
+        }
+    }
     int pool = 0;
     if (rerank) {   // (DIVERSIFIED TOP-N, GROUP CAPS: pool 0 is min(1024, max(topN, 4 topN)), with a cap 8 topN)
         pool = q.pool ? q.pool : std::min(MI355REC_MAX_TOPN_FAST, std::max(topN, (capped ? 8 : 4) * std::min(topN, MI355REC_MAX_TOPN_FAST)));
@@ -538,7 +553,15 @@ std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, 
     const mi355rec_request_ext_t ext = requestExt(impl, q.scales.empty() ? nullptr : q.scales.data());
     int rc;
     std::vector<int32_t> member;
-    if (q.anyOf) {
+    if (q.manhattan) {
+        mi355rec_manhattan_query_t m{};
+        shared(m);
+        mi355rec_manhattan_result_t res{};
+        res.out_idx = impl->idxBuf.data();
+        res.out_distance = impl->scoreBuf.data();
+        res.out_count = &count;
+        rc = mi355rec_sharded_query_manhattan_request(impl->engine, &m, &ext, &res);
+    } else if (q.anyOf) {
         mi355rec_anyof_query_t a{};
         shared(a);
         member.assign(static_cast<size_t>(topN), -1);

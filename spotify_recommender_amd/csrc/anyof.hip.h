@@ -31,6 +31,20 @@
 //
 // ATTRIBUTION (AnyofArg::n_attr > 0, uniform): the same kernel, launched once more over the merged result: thread i reads key i of
 // `attr_keys`, runs the K chains on that row and stores a(x) to attr_member[i] (-1 for an empty slot).  No second __global__.
+//
+// MANHATTAN (manhattan_scan_kernel, at the end of this file; include/mi355rec_diag.h "MANHATTAN REQUESTS"): a second kernel made of
+// the same pieces.  It ranks by
+//     d1_k(x) = acc after j = 0..11 of:  t = fl(q_kj - x_j);  acc = fl(acc + fabsf(t))       (acc starts at 0.0f)
+//     m(x)    = fl( fl(...fl(d1_0 + d1_1) + ... + d1_{K-1}) / (float)K ),     keys pack_key(-m, global row); m not finite: no key
+// ascending in m, then row ascending.  Every piece below is a template on kL1: anyof_scan_kernel instantiates <false> and is the
+// code it was, manhattan_scan_kernel instantiates <true>; the two share source, not a function.  What differs, in three places:
+// the row key (anyof_row_key: manhattan_value in place of anyof_value), the anchor bound's ranking of the table (the same value; a
+// value that is not finite is no candidate) and the cut (playlist_cut.hip.h, "MANHATTAN": the row's bytes times its stored norm,
+// the PER-MEMBER L1 sum, a float compare; its three constants in LDS, kt refreshed by thread 0 whenever the threshold moves).
+// `norms`: the handle's per-row norms (DISTANCE's), a quad's four loaded with the replica's tile, the next tile's in flight.
+// Everything else (admissibility and its order, the candidate lists, the threshold exchange, rows_exact) is the source any-of
+// runs.  The members' cosine constants (digits, |u_k|, margins) do not exist there.  DESIGN.md 5.4.18 has the registers and why
+// the metric is not a branch of anyof_scan_kernel (it was, and any-of paid 1 % for it).
 #pragma once
 
 #include "playlist.hip.h"
@@ -61,6 +75,7 @@ struct AnyofSmem {
     int (*digits)[6];   // ANY: member k's query digits ...
     float *un, *margin; // ... |u_k| and margin_k ...
     int* cut;           // ... and its integer cut at the workgroup's threshold
+    float* l1;          // MANHATTAN: ce, ke1 and kt of the cut (playlist_cut.hip.h)
 };
 
 struct AnyofCtx {
@@ -77,7 +92,31 @@ struct AnyofCtx {
     const uint8_t* rowset;
     uint32_t flip;
     int tid, lane;
+    const float4* norms4;  // MANHATTAN: a quad's four stored norms; null: none were passed (the cut is off)
 };
+
+// MANHATTAN: m(x) of the contract: the row's features once, K chains against the members in LDS, in order.
+__device__ __forceinline__ float manhattan_value(const float (*__restrict__ mem)[kDim], int k, const Row& r) {
+    float f[kDim];
+    row_features(r, f);
+    float sum = 0.0f;
+    for (int m = 0; m < k; ++m) {
+        float acc = 0.0f;
+#pragma unroll
+        for (int j = 0; j < kDim; ++j) {
+            const float t = mem[m][j] - f[j];
+            acc = acc + __builtin_fabsf(t);
+        }
+        sum = m == 0 ? acc : sum + acc;
+    }
+    return sum / static_cast<float>(k);
+}
+
+// ... as a key on global row g: -m, or 0 where m is not finite (no key).
+__device__ __forceinline__ uint64_t manhattan_key(const float (*__restrict__ mem)[kDim], int k, const Row& r, uint32_t g) {
+    const float d = manhattan_value(mem, k, r);
+    return d < __builtin_inff() ? pack_key(-d, g) : 0ull;   // (false for NaN)
+}
 
 // v(x) and a(x) of the contract: the row's features and norm once, K chains against the members in LDS, the compare chain.
 __device__ __forceinline__ float anyof_value(const float (*__restrict__ mem)[kDim], const float* __restrict__ qn, int k, const Row& r, int& a) {
@@ -94,12 +133,15 @@ __device__ __forceinline__ float anyof_value(const float (*__restrict__ mem)[kDi
 }
 
 // THE key of the fp32 row x at local row `row`: the anchor bound and the scan both call it (bit-identical keys).
+template <bool kL1>
 __device__ __forceinline__ uint64_t anyof_row_key(const AnyofCtx& c, const AnyofSmem& sm, const Row& x, int64_t row) {
+    if constexpr (kL1) return manhattan_key(sm.mem, c.k, x, static_cast<uint32_t>(c.row_base + row));
     int a;
     return pack_key(anyof_value(sm.mem, sm.qn, c.k, x, a), static_cast<uint32_t>(c.row_base + row));
 }
 
 // ---- members and excluded ids into LDS; the members' norms; per member the ANY cut's constants.  Returns whether the cut is on.
+template <bool kL1>
 __device__ __forceinline__ bool anyof_prologue(const AnyofCtx& c, const AnyofSmem& sm, bool by_row) {
     constexpr int kBlock = PlaylistCfg::kBlock;
     const PlaylistBuf* const buf = c.buf;
@@ -110,6 +152,21 @@ __device__ __forceinline__ bool anyof_prologue(const AnyofCtx& c, const AnyofSme
     if (c.labelled && tid < kMaxLabels / 32) sm.lmask[tid] = buf->label_mask[tid];
     if (tid == 0) sm.count = sm.exact = 0, sm.ok = 1;
     __syncthreads();
+    if constexpr (kL1) {   // MANHATTAN: the cut's constants; it is off where a member's norm is not finite or above kBqMaxNorm
+        if (tid < k) {
+            float q[kDim];
+#pragma unroll
+            for (int j = 0; j < kDim; ++j) q[j] = sm.mem[tid][j];
+            if (!(query_norm(q) <= kBqMaxNorm)) sm.ok = 0;   // (false for NaN; every writer writes 0)
+        }
+        if (tid == 0) {
+            sm.l1[0] = 1.0f - playlist_cut_l1_eps(k);
+            sm.l1[1] = static_cast<float>(k) * kL1HalfSteps;
+            sm.l1[2] = __builtin_inff();   // no threshold yet: no row is ruled out
+        }
+        __syncthreads();
+        return c.q8 != nullptr && c.norms4 != nullptr && sm.ok != 0;
+    }
     if (tid < k) {
         float q[kDim];
 #pragma unroll
@@ -133,6 +190,7 @@ __device__ __forceinline__ bool anyof_prologue(const AnyofCtx& c, const AnyofSme
 }
 
 // ---- the starting threshold (STARTING THRESHOLD above).  Returns the threshold key (published too), or 0.
+template <bool kL1>
 __device__ __forceinline__ uint64_t anyof_anchor_bound(const AnyofCtx& c, const AnyofSmem& sm, int& n_exact) {
     constexpr int kBlock = PlaylistCfg::kBlock, kPer = kAnchorRows / kBlock;
     static_assert(PlaylistCfg::kCandCap >= kAnchorRows / 2 && PlaylistCfg::kCandCap * 2 >= kPlBoundRows, "LDS reuse below");
@@ -146,12 +204,13 @@ __device__ __forceinline__ uint64_t anyof_anchor_bound(const AnyofCtx& c, const 
         const int i = r * kBlock + tid;
         const Row a = load_row(c.anchors, static_cast<int64_t>(i));
         int who;
-        mine[r] = i < n_anchor ? pack_key(anyof_value(sm.mem, sm.qn, c.k, a, who), static_cast<uint32_t>(i)) : 0ull;
+        if constexpr (kL1) mine[r] = i < n_anchor ? manhattan_key(sm.mem, c.k, a, static_cast<uint32_t>(i)) : 0ull;   // (not finite: no candidate)
+        else mine[r] = i < n_anchor ? pack_key(anyof_value(sm.mem, sm.qn, c.k, a, who), static_cast<uint32_t>(i)) : 0ull;
         if (c.active && !filter_pass(a, c.active, c.buf->lo, c.buf->hi)) mine[r] = 0ull;   // (only chooses: re-checked on the matrix's row)
         if (c.labelled && i < n_anchor && !label_selected(sm.lmask, c.row_label[anchor_row(n, i)])) mine[r] = 0ull;
     }
     int n_cand = kPlBoundRows;   // anchors left to choose from: all of them without a filter
-    if (c.active || c.labelled) {   // uniform
+    if (c.active || c.labelled || kL1) {   // uniform
 #pragma unroll
         for (int r = 0; r < kPer; ++r) {
             const uint64_t have = __ballot(mine[r] != 0ull);
@@ -182,7 +241,7 @@ __device__ __forceinline__ uint64_t anyof_anchor_bound(const AnyofCtx& c, const 
         const int64_t row = anchor_row(n, s_pick[tid]);
         const Row x = load_row(c.feats, row);   // from the matrix
         const bool x_pass = !c.active || filter_pass(x, c.active, c.buf->lo, c.buf->hi);
-        const uint64_t row_key = anyof_row_key(c, sm, x, row);
+        const uint64_t row_key = anyof_row_key<kL1>(c, sm, x, row);
         ++n_exact;
         key = playlist_excluded(sm.excl, c.n_excl, static_cast<uint32_t>(c.row_base + row)) || !x_pass ||
                       (c.labelled && !label_selected(sm.lmask, c.row_label[row])) || (c.rowset && !rowset_admits(c.rowset, c.flip, row))
@@ -209,11 +268,15 @@ __device__ __forceinline__ uint64_t anyof_anchor_bound(const AnyofCtx& c, const 
 }
 
 // The workgroup's threshold key has moved: every member's cut, by the first K threads (the caller's barrier follows).
+template <bool kL1>
 __device__ __forceinline__ void anyof_cut_refresh(const AnyofCtx& c, const AnyofSmem& sm, uint64_t thr) {
-    if (c.tid < c.k) sm.cut[c.tid] = playlist_cut_any(sm.un[c.tid], sm.margin[c.tid], ordered_to_score(static_cast<uint32_t>(thr >> 32)));
+    if constexpr (kL1) {   // MANHATTAN: kt = fl(K T), T = 0.0f - the threshold's score
+        if (c.tid == 0) sm.l1[2] = static_cast<float>(c.k) * (0.0f - ordered_to_score(static_cast<uint32_t>(thr >> 32)));
+    } else if (c.tid < c.k) sm.cut[c.tid] = playlist_cut_any(sm.un[c.tid], sm.margin[c.tid], ordered_to_score(static_cast<uint32_t>(thr >> 32)));
 }
 
 // ---- the scan: this workgroup's tiles, candidates into sm.cand (thr: the starting threshold key, or 0)
+template <bool kL1>
 __device__ __forceinline__ void anyof_scan_tiles(const AnyofCtx& c, const AnyofSmem& sm, bool cut_on, uint64_t thr, int& n_exact) {
     constexpr int kBlock = PlaylistCfg::kBlock;
     const int tid = c.tid, lane = c.lane;
@@ -221,13 +284,15 @@ __device__ __forceinline__ void anyof_scan_tiles(const AnyofCtx& c, const AnyofS
     int compact_at = 2 * c.topk > 256 ? 2 * c.topk : 256;
     if (compact_at > kCandLimit) compact_at = kCandLimit;
     if (cut_on && thr != 0ull) {   // uniform
-        anyof_cut_refresh(c, sm, thr);
+        anyof_cut_refresh<kL1>(c, sm, thr);
         __syncthreads();
     }
     HalfTile cur = {};
     uint2 cur_labels = make_uint2(0u, 0u);
     if (cut_on) cur = reinterpret_cast<const HalfTile*>(c.q8)[playlist_tile_quad(blockIdx.x, tid, n_quads)];
     if (c.labelled) cur_labels = c.labels4[playlist_tile_quad(blockIdx.x, tid, n_quads)];
+    float4 cur_norms = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (kL1 && cut_on) cur_norms = c.norms4[playlist_tile_quad(blockIdx.x, tid, n_quads)];
 
     for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {   // uniform
         HalfTile nxt = cur;
@@ -235,6 +300,8 @@ __device__ __forceinline__ void anyof_scan_tiles(const AnyofCtx& c, const AnyofS
         // the next tile is in flight while this one is scored (past the last tile: the clamped quad again)
         if (cut_on) nxt = reinterpret_cast<const HalfTile*>(c.q8)[playlist_tile_quad(t + gridDim.x, tid, n_quads)];
         if (c.labelled) nxt_labels = c.labels4[playlist_tile_quad(t + gridDim.x, tid, n_quads)];
+        float4 nxt_norms = cur_norms;
+        if (kL1 && cut_on) nxt_norms = c.norms4[playlist_tile_quad(t + gridDim.x, tid, n_quads)];
         const int64_t quad = t * kBlock + tid;
         const int64_t r0 = quad * 4;
         const int64_t left = quad < n_quads ? n - r0 : 0;   // rows of the quad inside the shard
@@ -250,7 +317,10 @@ __device__ __forceinline__ void anyof_scan_tiles(const AnyofCtx& c, const AnyofS
             for (int u4 = 0; u4 < 4; ++u4)
                 if (!label_selected(sm.lmask, l4[u4])) mask &= ~(1u << u4);
         }
-        if (cut_on && thr != 0ull) playlist_cut_any_apply(mask, cur, sm.digits, sm.cut, c.k);   // (uniform) no threshold: every row is kept
+        if (cut_on && thr != 0ull) {   // (uniform) no threshold: every row is kept
+            if constexpr (kL1) playlist_cut_l1_apply(mask, cur, cur_norms, sm.mem, c.k, sm.l1[0], sm.l1[1], sm.l1[2]);
+            else playlist_cut_any_apply(mask, cur, sm.digits, sm.cut, c.k);
+        }
         if (c.active && mask != 0u) {   // (active uniform) the filter on the fp32 rows left, before any chain
             Row x[4];
 #pragma unroll
@@ -265,7 +335,7 @@ __device__ __forceinline__ void anyof_scan_tiles(const AnyofCtx& c, const AnyofS
         while (__ballot(mask != 0u)) {   // uniform
             const bool have = mask != 0u;
             const int64_t r = have ? r0 + __builtin_ctz(mask) : 0;
-            const uint64_t row_key = anyof_row_key(c, sm, load_row(c.feats, r), r);
+            const uint64_t row_key = anyof_row_key<kL1>(c, sm, load_row(c.feats, r), r);
             n_exact += (have && !c.active) ? 1 : 0;   // (with a filter every row read was counted above)
             const uint64_t key = have ? row_key : 0ull;
             bool pass = key > thr;
@@ -293,12 +363,33 @@ __device__ __forceinline__ void anyof_scan_tiles(const AnyofCtx& c, const AnyofS
         }
         if (published > thr) thr = published;
         if (cut_on && thr != before) {   // (uniform) every wave has left this tile's cut test: the barriers above
-            anyof_cut_refresh(c, sm, thr);
+            anyof_cut_refresh<kL1>(c, sm, thr);
             __syncthreads();
         }
         cur = nxt;
         cur_labels = nxt_labels;
+        cur_norms = nxt_norms;
     }
+}
+
+// ---- one workgroup's scan behind the prologue: the starting threshold, its tiles, the rows_exact count, the ranked list
+template <bool kL1>
+__device__ __forceinline__ void anyof_scan_body(const AnyofCtx& c, const AnyofSmem& sm, bool cut_on, uint64_t* __restrict__ block_lists,
+                                                unsigned long long* __restrict__ rows_exact) {
+    constexpr int kBlock = PlaylistCfg::kBlock;
+    int n_exact = 0;   // rows whose K chains this thread computed
+    uint64_t thr = 0ull;
+    if (cut_on) thr = anyof_anchor_bound<kL1>(c, sm, n_exact);   // uniform
+    anyof_scan_tiles<kL1>(c, sm, cut_on, thr, n_exact);
+
+    const int wave_exact = wave_inclusive_scan(n_exact);
+    if (c.lane == 63 && wave_exact) atomicAdd(&sm.exact, wave_exact);
+    __syncthreads();
+    if (c.tid == 0 && rows_exact && sm.exact) atomicAdd(rows_exact, static_cast<unsigned long long>(sm.exact));
+    if (sm.count > kRankCountMax && sm.count > c.topk)   // uniform
+        compact_candidates<kBlock, PlaylistCfg::kCandPerThread>(sm.cand, &sm.count, c.topk, false, sm.sel);
+    __syncthreads();
+    block_rank_and_store<kBlock>(sm.cand, sm.count, block_lists + static_cast<int64_t>(blockIdx.x) * c.topk, c.topk);
 }
 
 // q8: the handle's 8-bit replica, or null (every row exact).  anchors: the anchor table, or null (no starting threshold).
@@ -319,12 +410,13 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void a
     __shared__ float s_qn[kMaxPlaylist], s_un[kMaxPlaylist], s_margin[kMaxPlaylist];
     __shared__ int s_digits[kMaxPlaylist][6], s_cut[kMaxPlaylist];
     __shared__ uint32_t s_excl[kPlExcludeCap], s_lmask[kMaxLabels / 32];
-    const AnyofSmem sm = {s_cand, s_sel, s_count, s_ok, s_exact, s_shared, s_mem, s_qn, s_excl, s_lmask, s_digits, s_un, s_margin, s_cut};
+    const AnyofSmem sm = {s_cand, s_sel, s_count, s_ok, s_exact, s_shared, s_mem, s_qn, s_excl, s_lmask, s_digits, s_un, s_margin, s_cut, nullptr};
     const int tid = threadIdx.x;
     const bool attribution = arg.n_attr > 0;   // uniform
     const AnyofCtx c = {feats, anchors, n, row_base, buf, shared_thr, arg.k, attribution ? 0 : arg.n_excl, topk, arg.active, arg.labelled != 0,
-                        reinterpret_cast<const int16_t*>(labels), labels, attribution ? nullptr : q8, arg.rowset, arg.rowset_flip, tid, tid & 63};
-    const bool cut_on = anyof_prologue(c, sm, arg.by_row != 0);
+                        reinterpret_cast<const int16_t*>(labels), labels, attribution ? nullptr : q8, arg.rowset, arg.rowset_flip, tid, tid & 63,
+                        nullptr};
+    const bool cut_on = anyof_prologue<false>(c, sm, arg.by_row != 0);
     if (attribution) {   // (uniform) one thread per result: the K chains of its row, a(x) stored
         const int i = static_cast<int>(blockIdx.x) * kBlock + tid;
         if (i < arg.n_attr) {
@@ -338,19 +430,31 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void a
         }
         return;
     }
-    int n_exact = 0;   // rows whose K chains this thread computed
-    uint64_t thr = 0ull;
-    if (cut_on) thr = anyof_anchor_bound(c, sm, n_exact);   // uniform
-    anyof_scan_tiles(c, sm, cut_on, thr, n_exact);
+    anyof_scan_body<false>(c, sm, cut_on, block_lists, rows_exact);
+}
 
-    const int wave_exact = wave_inclusive_scan(n_exact);
-    if (c.lane == 63 && wave_exact) atomicAdd(&sm.exact, wave_exact);
-    __syncthreads();
-    if (tid == 0 && rows_exact && sm.exact) atomicAdd(rows_exact, static_cast<unsigned long long>(sm.exact));
-    if (sm.count > kRankCountMax && sm.count > topk)   // uniform
-        compact_candidates<kBlock, PlaylistCfg::kCandPerThread>(sm.cand, &sm.count, topk, false, sm.sel);
-    __syncthreads();
-    block_rank_and_store<kBlock>(sm.cand, sm.count, block_lists + static_cast<int64_t>(blockIdx.x) * topk, topk);
+// MANHATTAN: the same pieces as their kL1 = true instances, in a kernel of its own (anyof_scan_kernel shares no function, no
+// register allocation and no code layout with it).  The arguments are anyof_scan_kernel's without the attribution's; arg.n_attr is 0.
+// norms: the rows' norms in row order, four fp32 to a quad, or null (no pre-filter then).
+__global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void manhattan_scan_kernel(
+    const float* __restrict__ feats, const uint4* __restrict__ q8, int64_t n, int64_t row_base, const PlaylistBuf* __restrict__ buf,
+    AnyofArg arg, const float* __restrict__ anchors, int topk, uint64_t* __restrict__ block_lists,
+    unsigned long long* __restrict__ rows_exact, unsigned long long* __restrict__ shared_thr /* &buf->shared_thr */,
+    const uint2* __restrict__ labels, const float4* __restrict__ norms) {
+    __shared__ uint64_t s_cand[PlaylistCfg::kCandCap];
+    __shared__ SelectSmem s_sel;
+    __shared__ int s_count, s_ok, s_exact;
+    __shared__ unsigned long long s_shared;
+    __shared__ float s_mem[kMaxPlaylist][kDim];
+    __shared__ float s_l1[4];
+    __shared__ uint32_t s_excl[kPlExcludeCap], s_lmask[kMaxLabels / 32];
+    // (the members' cosine constants are any-of's: never touched by a kL1 instance)
+    const AnyofSmem sm = {s_cand, s_sel, s_count, s_ok, s_exact, s_shared, s_mem, nullptr, s_excl, s_lmask, nullptr, nullptr, nullptr, nullptr, s_l1};
+    const int tid = threadIdx.x;
+    const AnyofCtx c = {feats, anchors, n, row_base, buf, shared_thr, arg.k, arg.n_excl, topk, arg.active, arg.labelled != 0,
+                        reinterpret_cast<const int16_t*>(labels), labels, q8, arg.rowset, arg.rowset_flip, tid, tid & 63, norms};
+    const bool cut_on = anyof_prologue<true>(c, sm, arg.by_row != 0);
+    anyof_scan_body<true>(c, sm, cut_on, block_lists, rows_exact);
 }
 
 }  // namespace mi355

@@ -456,6 +456,9 @@ static int mean_keys(Node* h, const mi355playlist::Request& r, std::vector<uint6
     // keys carry -m, a row whose m is not finite gets no key (it is not admissible).
     const bool dist = r.metric == mi355playlist::kDistance;
     const bool anyof = r.metric == mi355playlist::kAnyOf;
+    // "MANHATTAN REQUESTS": m(x) = fl(fl(d1_0 + ... + d1_{k-1}) / k), d1_k the sequential fp32 sum of fabsf(t), t = fl(q_kj - x_j);
+    // keys carry -m, a row whose m is not finite gets no key (it is not admissible).
+    const bool l1 = r.metric == mi355playlist::kManhattan;
     // "FEATURE SCALES": two steps, as on the device: members and rows scaled with one fp32 multiply per feature, then the chains
     // above on the scaled values.  The filter below tests the stored rows f.
     const float* const a = r.scales;
@@ -495,6 +498,20 @@ static int mean_keys(Node* h, const mi355playlist::Request& r, std::vector<uint6
             keys[static_cast<size_t>(i)] = std::isfinite(mean) ? pack(-mean, static_cast<uint32_t>(i)) : 0;
             continue;
         }
+        if (l1) {
+            float sum = 0.0f;
+            for (int m = 0; m < k; ++m) {
+                float acc = 0.0f;
+                for (int j = 0; j < kDim; ++j) {
+                    const float t = members[m * kDim + j] - x[j];
+                    acc = acc + std::fabs(t);
+                }
+                sum = m == 0 ? acc : sum + acc;
+            }
+            const float mean = sum / static_cast<float>(k);
+            keys[static_cast<size_t>(i)] = std::isfinite(mean) ? pack(-mean, static_cast<uint32_t>(i)) : 0;
+            continue;
+        }
         if (anyof) {   // "ANY-OF REQUESTS": v = the best of the members' scores, in member order (the compare chain of anyof_best)
             int a;
             keys[static_cast<size_t>(i)] = pack(anyof_best(members, qn.data(), k, x, &a), static_cast<uint32_t>(i));
@@ -515,7 +532,7 @@ static int mean_keys(Node* h, const mi355playlist::Request& r, std::vector<uint6
     for (int64_t e : excl)
         if (e >= 0 && e < n) keys[static_cast<size_t>(e)] = 0;   // (a real key is never 0: its low half is ~row)
     int64_t avail = n - static_cast<int64_t>(std::count_if(excl.begin(), excl.end(), [n](int64_t e) { return e >= 0 && e < n; }));
-    if (dist) avail = static_cast<int64_t>(std::count_if(keys.begin(), keys.end(), [](uint64_t key) { return key != 0; }));
+    if (dist || l1) avail = static_cast<int64_t>(std::count_if(keys.begin(), keys.end(), [](uint64_t key) { return key != 0; }));
     if (filter && filter->active) {   // the rows failing the filter go like excluded ones
         avail = 0;
         for (int64_t i = 0; i < n; ++i) {
@@ -583,7 +600,7 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
         }
     }
     mi355playlist::pad(out, count, topn_asked, count);
-    if (r.report_distance) mi355playlist::scores_to_distances(out, topn_asked);
+    if (r.report_distance) mi355playlist::scores_to_distances(out, topn_asked, r.metric);
     return MI355REC_OK;
 }
 

@@ -84,6 +84,14 @@ int set_priors_common(mi355rec* h, const float* priors_host, int64_t n, bool gro
     });
 }
 
+// "MANHATTAN REQUESTS": the most members for which the launch takes the 8-bit pre-filter (playlist_cut.hip.h, "MANHATTAN"): its
+// arithmetic grows with K as the chains' does, only its bytes do not.  Measured on an MI355X at 10 M uniform rows, top-100, with
+// the cut at every K (profiles/r23_manhattan_cut_every_k.json: the experiments build with MI355REC_EXP_L1_CUT_MAX_K=32), p50 on a
+// handle with the replica / on one without: K = 1: 97.7 / 192.9 us, K = 3: 113.6 / 194.8, K = 10: 185.4 / 210.4, K = 32: 416.1 /
+// 270.1 (300-cluster sorted catalogue: 99.5 / 203.1, 109.8 / 201.3, 169.0 / 212.9, 347.9 / 268.9).  Both grow linearly in K
+// (about 10 us and under 3 us per member) and cross near K = 12; K = 10 is the largest K measured at which the cut wins, so it
+// is on up to there.
+constexpr int kL1CutMaxK = 10;
 constexpr int kPlMinTilesPerWg = 8;   // with the pre-filter: a workgroup scans >= 8 tiles (its anchor bound paid for, its own threshold tight)
 
 void free_playlist(mi355rec_playlist* P) {
@@ -281,9 +289,14 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     // here leaves nothing begun and nothing staged.
     // (a candidate list gathers: no replica, no anchors, no norms, so the cut is off and every listed row takes the exact chain)
     const uint4* q8 = !r.listed && use_q8(h) ? h->d_q8 : nullptr;
+    // "MANHATTAN REQUESTS": the same norms; above kL1CutMaxK members the launch gets no replica (the cut loses to the chains there)
+    const bool manhattan = r.metric == mi355playlist::kManhattan;
+    int l1_cut_max_k = kL1CutMaxK;
+    MI355REC_EXP_INT(l1_cut_max_k, "MI355REC_EXP_L1_CUT_MAX_K", 0, MI355REC_MAX_PLAYLIST);   // (experiments build only: tools/run_manhattan.py)
+    if (manhattan && k > l1_cut_max_k) q8 = nullptr;
     const int64_t n_quads4 = (h->n + 3) / 4 * 4;
     // (a scaled distance request takes the exact path: the norms are those of the unscaled rows, it is launched with null norms)
-    const bool scan_norms = q8 && arg.metric == kPlDistance && !arg.scaled;
+    const bool scan_norms = q8 && ((arg.metric == kPlDistance && !arg.scaled) || manhattan);
     const bool fresh_norms = scan_norms && !P->norms_built;
     if (fresh_norms && !P->d_norms) {   // (an earlier call that failed before its build was enqueued has left the allocation)
         const hipError_t e = hipMalloc(&P->d_norms, sizeof(float) * static_cast<size_t>(n_quads4));
@@ -321,6 +334,17 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     if (want_grid > P->grid_cap) want_grid = P->grid_cap;
     if (want_grid < 1) want_grid = 1;
     const int grid = static_cast<int>(want_grid);
+    if (manhattan) {   // "MANHATTAN REQUESTS": its own kernel (anyof.hip.h), this launch's geometry, inputs and lists
+        const AnyofArg any = {k, n_excl, arg.by_row, arg.active, arg.labelled, arg.rowset, arg.rowset_flip, 0};
+        LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, manhattan_scan_kernel, dim3(grid), dim3(PlaylistCfg::kBlock), h->stream,
+                     h->d_feats, q8, h->n, h->row_base, static_cast<const PlaylistBuf*>(P->d_buf), any, static_cast<const float*>(h->d_anchor), topk,
+                     h->d_block_lists, P->d_exact,
+                     reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr)),
+                     reinterpret_cast<const uint2*>(L ? L->d_row_labels : nullptr), reinterpret_cast<const float4*>(scan_norms ? P->d_norms : nullptr));
+        HIP_TRY(h, hipGetLastError());
+        *grid_out = grid;
+        return MI355REC_OK;
+    }
     if (anyof) {   // "ANY-OF REQUESTS": its own kernel (anyof.hip.h), this launch's geometry, inputs and lists
         const AnyofArg any = {k, n_excl, arg.by_row, arg.active, arg.labelled, arg.rowset, arg.rowset_flip, 0};
         LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, anyof_scan_kernel, dim3(grid), dim3(PlaylistCfg::kBlock), h->stream,
@@ -399,7 +423,7 @@ int sync_playlist_query(mi355rec* h, const Request& r, const Outputs& out, int m
     rc = sync_finish(h, ss, r.topn, out.idx, out.score, out.count);
     if (rc == MI355REC_OK && out.member)   // (the stream has been waited for: ss.want == 0 with an attribution)
         for (int i = 0; i < r.topn; ++i) out.member[i] = i < eff && out.idx[i] >= 0 ? h->playlist->h_member[i] : -1;
-    if (rc == MI355REC_OK && r.report_distance) mi355playlist::scores_to_distances(out, r.topn);   // "DISTANCE REQUESTS": -m to sqrtf(m)
+    if (rc == MI355REC_OK && r.report_distance) mi355playlist::scores_to_distances(out, r.topn, r.metric);   // "DISTANCE REQUESTS": -m to sqrtf(m) ("MANHATTAN": to m)
     return rc;
 }
 
@@ -619,6 +643,19 @@ int mi355rec_query_anyof_request(mi355rec_t* h, const mi355rec_anyof_query_t* qu
     Outputs out;
     char why[160];
     if (mi355playlist::from_anyof_query(query, ext, result, &full, &r, &out, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    if (r.rowset && r.rowset->node) return fail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
+    return sync_playlist_query(h, r, out);
+}
+
+// "MANHATTAN REQUESTS": the same Request with metric = kManhattan through the same path; its scan is manhattan_scan_kernel.
+int mi355rec_query_manhattan_request(mi355rec_t* h, const mi355rec_manhattan_query_t* query, const mi355rec_request_ext_t* ext,
+                                     const mi355rec_manhattan_result_t* result) {
+    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    mi355rec_manhattan_query_t full;
+    Request r;
+    Outputs out;
+    char why[160];
+    if (mi355playlist::from_manhattan_query(query, ext, result, &full, &r, &out, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
     if (r.rowset && r.rowset->node) return fail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
     return sync_playlist_query(h, r, out);
 }

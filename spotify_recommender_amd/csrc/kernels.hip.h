@@ -191,6 +191,16 @@ __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_kernel(
         // ANOTHER shard through the peer mapping (sharded.hip), a staged vector.  Wave-uniform: scalar loads.
 #pragma unroll
         for (int j = 0; j < kDim; ++j) q[j] = query_ptr[j];
+    } else if constexpr (kScoresOnly) {
+        // ONE scores-only instance serves both query forms (a uniform run-time choice: the same 12 floats either way, so the
+        // same scores; the top-N instances keep their two forms)
+        if (query_ptr) {
+#pragma unroll
+            for (int j = 0; j < kDim; ++j) q[j] = query_ptr[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < kDim; ++j) q[j] = qarg.q[j];
+        }
     } else {
 #pragma unroll
         for (int j = 0; j < kDim; ++j) q[j] = qarg.q[j];

@@ -21,6 +21,9 @@
 //       [-1, 1] per line, in catalogue order; usable with every other option of the --playlist mode)
 //   ... --song, --id and --playlist with --metric euclidean: the NEAREST songs by Euclidean distance over the 12 features instead
 //       of the most similar by cosine (extension; with --genre and --where; distances are printed)
+//   ... --song, --id and --playlist with --distance manhattan: the NEAREST songs by Manhattan (L1) distance over the 12 features,
+//       for a playlist the mean of the distances to its songs (extension; with --genre, --where, --seen and --only and nothing else;
+//       distances are printed; --metric keeps its two names)
 //   ... --song, --id and --playlist with one or more --scale NAME=S: feature NAME counts S times (0: ignored) in the similarity or
 //       the distance (extension; under both metrics, with --genre and --where)
 //   ... the same modes with --candidates FILE (track ids, one per line, as for --only): only the listed songs are READ and ranked (a
@@ -609,6 +612,26 @@ static bool parseMatch(int argc, char* argv[], int first, bool playlist, bool& a
     return true;
 }
 
+// --distance NAME from argv[first]: manhattan = true for "manhattan" (MANHATTAN REQUESTS: the nearest songs by L1 distance), false
+// without the option.  false (the return value), with a message, for another name.
+static bool parseDistance(int argc, char* argv[], int first, bool& manhattan) {
+    manhattan = false;
+    for (int i = first; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--distance") != 0) continue;
+        if (i + 1 >= argc) {
+            std::cerr << "Error: --distance needs a name (manhattan)" << std::endl;
+            return false;
+        }
+        const std::string name = argv[++i];
+        if (name != "manhattan") {
+            std::cerr << "Error: --distance '" << name << "': manhattan" << std::endl;
+            return false;
+        }
+        manhattan = true;
+    }
+    return true;
+}
+
 // -n N: the first -n among argv[first .. argc-2] (the reference's rule, main.cpp:169-178: in last position it is not looked at).
 static bool parseTopN(int argc, char* argv[], int first, int& topN) {
     for (int i = first; i < argc - 1; ++i) {
@@ -649,12 +672,13 @@ struct Options {
     ScoreOpt score;
     bool euclidean = false;
     bool anyOf = false;        // --match any
+    bool manhattan = false;    // --distance manhattan
     std::vector<float> scales;
     Taste taste;
     DiverseOpt dv;
     PriorOpt pr;
     // a distance or scaled request (its own banner; scores or distances are printed; --song / --id run as the one-song playlist)
-    bool nearest() const { return euclidean || !scales.empty(); }
+    bool nearest() const { return euclidean || manhattan || !scales.empty(); }
 };
 
 // What does not combine: the option `given` stands for beside one of `beside` (the first of them in argv stands for %s in `text`).
@@ -667,6 +691,7 @@ enum class Given {
     GenreFiltered,   // --genre under --song / --id by unscaled cosine, beside a filter or a row set ...
     GenreReranked,   // ... and beside a re-rank: --playlist <one id> and the distance and scaled requests serve those pairs
     MatchAny,        // --match any
+    Manhattan,       // --distance manhattan
 };
 struct Refusal {
     Given given;
@@ -684,12 +709,14 @@ static const Refusal kRefusals[] = {
     {Given::GenreReranked, {"--diverse"}, "%s cannot be combined with --genre"},
     {Given::MatchAny, kRequestOptions, "--match any cannot be combined with %s (any-of requests take --genre, --where, --seen and --only only)"},
     {Given::MatchAny, {"--scale", "--candidates", "--score"}, "--match any cannot be combined with %s (any-of requests take --genre, --where, --seen and --only only)"},
+    {Given::Manhattan, kRequestOptions, "--distance manhattan cannot be combined with %s (Manhattan requests take --genre, --where, --seen and --only only)"},
+    {Given::Manhattan, {"--scale", "--candidates", "--score"}, "--distance manhattan cannot be combined with %s (Manhattan requests take --genre, --where, --seen and --only only)"},
 };
 
 // true, with the message, when `given` holds and the command line has an option that one of its rows refuses beside it.
 static bool refused(int argc, char* argv[], int first, const Options& o, Given given) {
     const bool genreAlone = !o.playlist && !o.nearest() && !o.genres.empty();
-    if (!(given == Given::Euclidean ? o.euclidean : given == Given::Scale ? !o.scales.empty() : given == Given::MatchAny ? o.anyOf : genreAlone))
+    if (!(given == Given::Euclidean ? o.euclidean : given == Given::Scale ? !o.scales.empty() : given == Given::MatchAny ? o.anyOf : given == Given::Manhattan ? o.manhattan : genreAlone))
         return false;
     for (const Refusal& r : kRefusals) {
         if (r.given != given) continue;
@@ -720,6 +747,12 @@ static bool parseOptions(int argc, char* argv[], Options& o) {
     if (o.anyOf && o.euclidean) {
         std::cerr << "Error: --match any cannot be combined with --metric euclidean (any-of requests take --genre, --where, --seen and --only only)"
                   << std::endl;
+        return false;
+    }
+    if (!parseDistance(argc, argv, first, o.manhattan) || refused(argc, argv, first, o, Given::Manhattan)) return false;
+    if (o.manhattan && (o.euclidean || o.anyOf)) {
+        std::cerr << "Error: --distance manhattan cannot be combined with " << (o.euclidean ? "--metric euclidean" : "--match any")
+                  << " (Manhattan requests take --genre, --where, --seen and --only only)" << std::endl;
         return false;
     }
     if (!parseScale(argc, argv, first, o.scales) || refused(argc, argv, first, o, Given::Scale)) return false;
@@ -807,7 +840,9 @@ static void printQuerySong(const DataManager::Catalogue& catalogue, std::map<int
 // and whatever goes wrong from there ends in "No recommendations found"), --playlist, and the distance or scaled request of any.
 static bool queryMode(const Options& o) {
     const bool nearest = o.nearest(), song = !o.playlist && !nearest;
-    std::cout << (nearest ? (o.euclidean ? "=== NEAREST MODE (Euclidean distance) ===" : "=== SCALED MODE (cosine over scaled features) ===")
+    std::cout << (nearest ? (o.manhattan   ? "=== NEAREST MODE (Manhattan distance) ==="
+                             : o.euclidean ? "=== NEAREST MODE (Euclidean distance) ==="
+                                           : "=== SCALED MODE (cosine over scaled features) ===")
                   : song  ? "=== RECOMMENDATION MODE ==="
                           : "=== PLAYLIST MODE ===")
               << std::endl;
@@ -898,6 +933,7 @@ static bool queryMode(const Options& o) {
         q.scales = o.scales;
         q.euclidean = o.euclidean;
         q.anyOf = o.anyOf;
+        q.manhattan = o.manhattan;
         if (o.score.on) listedValues = recommender.scoreSongs(q, listed, &eligible);
         else if (q.topN > 0) recs = recommender.recommendQuery(q);
     }
@@ -934,7 +970,7 @@ static bool queryMode(const Options& o) {
     std::cout << "\nTop " << recs.size() << " Recommendations:\n" << std::endl;
     for (size_t i = 0; i < recs.size(); ++i) {
         std::ostringstream value;
-        if (nearest) value << "  (" << (o.euclidean ? "distance " : "score ") << values[i] << ")";
+        if (nearest) value << "  (" << (o.euclidean || o.manhattan ? "distance " : "score ") << values[i] << ")";
         if (o.anyOf && i < matched.size()) value << "  (matches \"" << catalogue.trackNames[static_cast<size_t>(matched[i])] << "\")";
         if (!printEntry(catalogue, genreMap, recs[i], i + 1, "", value.str())) return false;
         if (i + 1 < recs.size()) std::cout << std::endl;

@@ -914,13 +914,12 @@ int mi355rec_enqueue_scores(mi355rec_t* h, int64_t local_row, const float* query
     const float* const qrow = local_row >= 0 ? h->d_feats + local_row * kDim : nullptr;
     const QueryArg qa = make_query_arg(h, qrow, query12);
     const ScanGeom& g = h->geom[kFp32];
-    by_query_form(qrow, [&](auto from_row, const float* qp) {
-        hipLaunchKernelGGL((scan_kernel<ScanConfig, decltype(from_row)::value, true>), dim3(g.grid), dim3(kScanBlock), 0, s, h->d_feats,
-                           h->n, static_cast<int64_t>(0), g.iters, h->row_base, qa, qp,
-                           static_cast<int64_t>(-1), 1, static_cast<uint64_t*>(nullptr), out_scores_dev,
-                           static_cast<const uint64_t*>(nullptr), no_prev_merge(),
-                           static_cast<const unsigned long long*>(nullptr), static_cast<const unsigned long long*>(nullptr), 0u, no_next_seed());
-    });
+    // (the scores-only scan is ONE kernel for both query forms: it reads the row where `qrow` is given, qa.q otherwise)
+    hipLaunchKernelGGL((scan_kernel<ScanConfig, false, true>), dim3(g.grid), dim3(kScanBlock), 0, s, h->d_feats,
+                       h->n, static_cast<int64_t>(0), g.iters, h->row_base, qa, qrow,
+                       static_cast<int64_t>(-1), 1, static_cast<uint64_t*>(nullptr), out_scores_dev,
+                       static_cast<const uint64_t*>(nullptr), no_prev_merge(),
+                       static_cast<const unsigned long long*>(nullptr), static_cast<const unsigned long long*>(nullptr), 0u, no_next_seed());
     HIP_TRY(h, hipGetLastError());
     return MI355REC_OK;
 }

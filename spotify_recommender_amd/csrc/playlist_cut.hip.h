@@ -394,4 +394,70 @@ __device__ __forceinline__ void playlist_cut_any_apply(uint32_t& mask, const Hal
     mask &= keep;
 }
 
+// MANHATTAN (anyof.hip.h, "MANHATTAN REQUESTS": the ranking value is -m(x), m the mean over the members of the L1 distance to the
+// row; this is the cut of manhattan_scan_kernel: it has no PlCutKind, the launch either has it or is off).
+//   * THE POINT.  A claimed row (below) has replica bytes b_j = rint(127 x_j rsq(|x|^2)) and the stored norm s (q8_build_kernel's
+//     second output, the distance request's).  xt_j = s b_j / 127 lies within half a byte step of x_j:
+//         sum_j |x_j - xt_j| <= 12 (s / 254) (1 + d0),     d0 < 1e-4
+//     (|b_j - 127 x_j / |x| (1 + e1)| <= 1/2 with |e1| < 5e-7 for v_rsq_f32, the fused sum of squares and the product; s against
+//     |x|: 7.5 ulp, DISTANCE above; the two enter as |x| (|e1| + |e2|) sum_j |b_j| / 127 <= 3.5e-6 |x|, which is 8e-5 of 12 s / 254).
+//   * THE BOUND IS PER MEMBER.  |q_kj - x_j| >= |q_kj - xt_j| - |x_j - xt_j| for every member k, so in real numbers
+//         K m(x) >= A(x) - K 12 (s / 254) (1 + d0),        A(x) = sum_k sum_j |q_kj - xt_j|.
+//     The centroid does NOT serve here: sum_j |c_j - xt_j| <= A / K with equality only where every member lies on the same side
+//     of xt in every coordinate; for K > 1 members spread over the catalogue it rules nothing out (DESIGN.md 5.4.18 has the table).
+//   * THE TEST.  With eps = (13K + 64) 2^-24 and T the workgroup's threshold as m (T = 0.0f - score of the threshold key, exact, >= 0):
+//         ce  = fl(1 - eps),   ke1 = fl( (float)K fl(12 * 1.001 / 254) )                       (once per launch)
+//         kt  = fl( (float)K T )                                                              (refreshed whenever the threshold moves)
+//         acc = the fp32 sum, in the order g = 0..2, k = 0..K-1, j = 4g..4g+3, of fabsf( fl(q_kj - fl((float)b_j sc)) ),  sc = fl(s fl(1/127))
+//         ruled out  iff  fl(acc ce) > fl( fl(s ke1) + kt )
+//     a conversion and a multiply per byte, a subtract and an add (the absolute value is an operand modifier) per member and byte.
+//   * WHY eps SUFFICES, u = 2^-24 relative; every quantity below is non-negative, so relative errors stay relative:
+//       - the chain: d1_k is within 13 u of its real value (the subtract 1, twelve adds), the K - 1 adds and the divide K more:
+//         m~ >= m (1 - (K + 14) u) for the fp32 m~ that the key carries;
+//       - acc: every term is fl(q - xtc) with xtc = xt_j (1 + 3 u) (1/127 as fp32, two products), so it is at most
+//         (1 + u) (|q - xt_j| + 3 u |xt_j|), and the 12K sequential adds of non-negative terms add 12K u:
+//         acc <= (1 + (12K + 1) u) (A + 3 u K sum_j |xt_j|),   sum_j |xt_j| <= 3.5 s,  so the second term is under 7e-7 K s:
+//         1.5e-5 of K 12 s / 254, inside the 1.001 with d0 (1e-4 + 1.5e-5 < 1e-3 less the 8 u of ke1's own roundings);
+//       - the test's arithmetic: ce (1), acc ce (1), ke1 (3), s ke1 (1), kt (1), the add (1): 8 u, 10 counted;
+//       (K + 14) + (12K + 1) + 10 = 13K + 25 <= 13K + 64.  So the test implies K m~(x) > K T: the row's key lies below the
+//     threshold whatever its row id.  T = +inf (or K T overflowing) rules no row out; a NaN compares false: the row is kept.
+//   * CLAIMED rows: first byte not 0x80 and s in [kBqMinNorm, kBqMaxNorm] (a zero row has s = 0: it takes the chains, as do
+//     tiny, huge, infinite and NaN rows).  OFF for the launch (every row takes the chains): no replica, no norms, or a member
+//     whose norm is not finite or above kBqMaxNorm (then no term of acc overflows: each is at most 2e18, 384 of them).
+//   * tests/test_manhattan_margin.py checks this with tests/manhattan_cut_model.py (a numpy mirror, operation for operation)
+//     against tests/manhattan_oracle.py, and that it is not vacuous.
+constexpr float kL1HalfSteps = 12.0f * 1.001f / 254.0f;   // 12 half steps of a normalised component, with d0 and acc's second term
+__device__ __forceinline__ float playlist_cut_l1_eps(int k) { return static_cast<float>(13 * k + 64) * kPlUlp; }
+// Clears the mask bit of every row of a lane's quad that the bound rules out.  mem: the k members (LDS, uniform addresses);
+// norms: the quad's four stored norms; ce, ke1, kt: the launch's constants and the threshold's (above).
+__device__ __forceinline__ void playlist_cut_l1_apply(uint32_t& mask, const HalfTile& tile, const float4 norms,
+                                                      const float (*__restrict__ mem)[kDim], int k, float ce, float ke1, float kt) {
+    const uint32_t w[12] = {tile.t0.x, tile.t0.y, tile.t0.z, tile.t0.w, tile.t1.x, tile.t1.y, tile.t1.z, tile.t1.w, tile.t2.x, tile.t2.y, tile.t2.z, tile.t2.w};
+    const float s4[4] = {norms.x, norms.y, norms.z, norms.w};
+    float sc[4], acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sc[r] = s4[r] * (1.0f / 127.0f);
+#pragma unroll
+    for (int g = 0; g < 3; ++g) {   // four features at a time: 16 decoded values live, not 48
+        float xt[4][4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+                xt[r][jj] = static_cast<float>(static_cast<int>(static_cast<int8_t>(w[3 * r + g] >> (8 * jj)))) * sc[r];
+        for (int m = 0; m < k; ++m) {   // uniform
+            const float q4[4] = {mem[m][4 * g], mem[m][4 * g + 1], mem[m][4 * g + 2], mem[m][4 * g + 3]};
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) acc[r] = acc[r] + __builtin_fabsf(q4[jj] - xt[r][jj]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const bool claimed = (w[3 * r] & 0xffu) != kQ8Special && s4[r] >= kBqMinNorm && s4[r] <= kBqMaxNorm;
+        if (claimed && acc[r] * ce > s4[r] * ke1 + kt) mask &= ~(1u << r);
+    }
+}
+
 }  // namespace mi355

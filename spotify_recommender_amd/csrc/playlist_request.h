@@ -4,7 +4,7 @@
 // family fills a Request and an Outputs and takes the one path of its handle type.  Neither struct is part of the C-ABI; the
 // C-ABI's own request ("PLAYLIST REQUESTS": mi355rec_playlist_query_t, the only call that takes a label set) is converted
 // to them by from_query below, and the distance request ("DISTANCE REQUESTS": mi355rec_distance_query_t, the same Request with
-// metric = kDistance) by from_distance_query.
+// metric = kDistance) by from_distance_query, the Manhattan request ("MANHATTAN REQUESTS", metric = kManhattan) by from_manhattan_query.
 #pragma once
 
 #include <cmath>
@@ -19,7 +19,7 @@
 
 namespace mi355playlist {
 
-enum Metric { kCosine = 0, kDistance = 1, kAnyOf = 2 };
+enum Metric { kCosine = 0, kDistance = 1, kAnyOf = 2, kManhattan = 3 };
 
 struct Request {
     const float* members = nullptr;             // k x 12 floats by value, or null with ...
@@ -42,8 +42,11 @@ struct Request {
     int metric = kCosine;                       // kDistance ("DISTANCE REQUESTS"): rank by m(x), the mean squared distance to the
                                                 // ... members, ascending; keys and scores carry -m
                                                 // kAnyOf ("ANY-OF REQUESTS"): rank by v(x), the best of the members' cosines
+                                                // kManhattan ("MANHATTAN REQUESTS"): rank by m(x), the mean L1 distance to the members,
+                                                // ... ascending; keys and scores carry -m
     bool attribute = false;                     // (kAnyOf) the member index a(x) of every result is wanted (Outputs::member)
-    bool report_distance = false;               // (kDistance) the score output holds sqrtf(m); false: -m itself, what a node
+    bool report_distance = false;               // (kDistance, kManhattan) the score output holds sqrtf(m) (kManhattan: m, no root);
+                                                // ... false: -m itself, what a node
                                                 // ... handle's merge over shards compares
     const float* scales = nullptr;              // null, or 12 checked feature scales a_j ("FEATURE SCALES"): the call is the same
                                                 // ... call on rows fl(a_j x_j) with members fl(a_j q_kj); the filter tests x itself
@@ -216,10 +219,13 @@ inline void label_bits(const Request& r, uint32_t* mask) {
 }
 
 // "DISTANCE REQUESTS": out.score[0..count) holds -m (the key's score, +0.0 for m = 0); the reported distance is sqrtf(m).
-// (0.0f - s, not -s: the distance of m = 0 is +0.0f.)
-inline void scores_to_distances(const Outputs& out, int topn) {
+// (0.0f - s, not -s: the distance of m = 0 is +0.0f.)  "MANHATTAN REQUESTS" (metric kManhattan): m itself, there is no root.
+inline void scores_to_distances(const Outputs& out, int topn, int metric = kDistance) {
     if (!out.score) return;
-    for (int i = 0; i < topn && out.idx[i] >= 0; ++i) out.score[i] = std::sqrt(0.0f - out.score[i]);
+    for (int i = 0; i < topn && out.idx[i] >= 0; ++i) {
+        const float m = 0.0f - out.score[i];
+        out.score[i] = metric == kManhattan ? m : std::sqrt(m);
+    }
 }
 
 // "CANDIDATE SCORES": where the values go, in list order: value[i] and (may be null) admissible[i] for candidates[i].
@@ -453,6 +459,61 @@ inline bool from_distance_query(const mi355rec_distance_query_t* q, const mi355r
     r->report_distance = true;
     *out = {res->out_idx, res->out_distance, nullptr, res->out_count, nullptr};
     return false;
+}
+
+// The C-ABI's Manhattan request (include/mi355rec_diag.h, "MANHATTAN REQUESTS") as the same Request (metric = kManhattan) and
+// Outputs: the size rules of from_query, flags must be 0, no feature scales.  True when the structs cannot be used; then
+// msg[0..cap) says why.
+inline bool from_manhattan_query(const mi355rec_manhattan_query_t* q, const mi355rec_request_ext_t* ext, const mi355rec_manhattan_result_t* res,
+                                 mi355rec_manhattan_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
+    if (!q || !res) {
+        std::snprintf(msg, cap, "null argument");
+        return true;
+    }
+    static const size_t ends[] = {offsetof(mi355rec_manhattan_query_t, flags),          offsetof(mi355rec_manhattan_query_t, members),
+                                  offsetof(mi355rec_manhattan_query_t, rows),           offsetof(mi355rec_manhattan_query_t, exclude_global),
+                                  offsetof(mi355rec_manhattan_query_t, filter),         offsetof(mi355rec_manhattan_query_t, labels),
+                                  offsetof(mi355rec_manhattan_query_t, k),              offsetof(mi355rec_manhattan_query_t, n_exclude),
+                                  offsetof(mi355rec_manhattan_query_t, n_labels),       offsetof(mi355rec_manhattan_query_t, topn),
+                                  sizeof(mi355rec_manhattan_query_t)};
+    static_assert(sizeof(mi355rec_manhattan_query_t) == offsetof(mi355rec_manhattan_query_t, topn) + sizeof(int32_t) &&
+                      sizeof(mi355rec_manhattan_query_t) == 64,
+                  "no tail padding: the struct ends where its last field ends");
+    bool known = false;
+    for (size_t e : ends) known = known || q->size == e;
+    if (!known) {
+        std::snprintf(msg, cap, "manhattan query of size %u: not the end of a field of the %u bytes this library reads",
+                      static_cast<unsigned>(q->size), static_cast<unsigned>(sizeof *full));
+        return true;
+    }
+    std::memset(full, 0, sizeof *full);
+    std::memcpy(full, q, q->size);
+    if (full->flags != 0u) {
+        std::snprintf(msg, cap, "flags 0x%x in a manhattan query: must be 0 (weights, diversified and capped calls and priors are not served)",
+                      static_cast<unsigned>(full->flags));
+        return true;
+    }
+    if (full->members && full->rows) {
+        std::snprintf(msg, cap, "members by value and by row in one manhattan query");
+        return true;
+    }
+    if (!full->members && !full->rows) {
+        std::snprintf(msg, cap, "a manhattan query needs members by value or by row");
+        return true;
+    }
+    *r = request(full->members, full->rows, nullptr, full->k, full->exclude_global, full->n_exclude, full->filter, full->topn);
+    r->labels = full->labels;
+    r->n_labels = full->n_labels;
+    r->metric = kManhattan;
+    r->report_distance = true;
+    *out = {res->out_idx, res->out_distance, nullptr, res->out_count, nullptr};
+    mi355rec_request_ext_t x;
+    if (from_ext(ext, &x, msg, cap)) return true;
+    if (x.feature_scales) {
+        std::snprintf(msg, cap, "manhattan requests take no feature scales");
+        return true;
+    }
+    return apply_ext(x, r, msg, cap);
 }
 
 // The C-ABI's any-of request (include/mi355rec_diag.h, "ANY-OF REQUESTS") as the same Request (metric = kAnyOf) and Outputs: the

@@ -857,7 +857,7 @@ int sharded_playlist(mi355rec_sharded_t* h, Request r, const Outputs& out) {
     const int merged = merge_over_shards(h, r.topn, out, [&](mi355rec_t* e, int64_t* idx, float* sc, int* c) {
         return mi355node::query_playlist(e, lists.of(h, r, e), {idx, sc, nullptr, c, nullptr});
     });
-    if (merged == MI355REC_OK && report_distance) mi355playlist::scores_to_distances(out, r.topn);
+    if (merged == MI355REC_OK && report_distance) mi355playlist::scores_to_distances(out, r.topn, r.metric);
     return merged;
 }
 
@@ -1059,6 +1059,19 @@ int mi355rec_sharded_query_anyof_request(mi355rec_sharded_t* h, const mi355rec_a
     Outputs out;
     char why[160];
     if (mi355playlist::from_anyof_query(query, ext, result, &full, &r, &out, why, sizeof why)) return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    return sharded_playlist(h, r, out);
+}
+
+// MANHATTAN REQUESTS (include/mi355rec_diag.h): the same Request with metric = kManhattan through sharded_playlist, as the distance
+// request: the shards answer with -m, what the merge's keys compare, and m is taken from the merged list.
+int mi355rec_sharded_query_manhattan_request(mi355rec_sharded_t* h, const mi355rec_manhattan_query_t* query,
+                                             const mi355rec_request_ext_t* ext, const mi355rec_manhattan_result_t* result) {
+    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    mi355rec_manhattan_query_t full;
+    Request r;
+    Outputs out;
+    char why[160];
+    if (mi355playlist::from_manhattan_query(query, ext, result, &full, &r, &out, why, sizeof why)) return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
     return sharded_playlist(h, r, out);
 }
 

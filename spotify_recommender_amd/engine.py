@@ -598,6 +598,47 @@ def query_anyof(eng, topn, members=None, rows=None, exclude=None, where=None, la
     return idx[:c].copy(), score[:c].copy(), member[:c].copy()
 
 
+def query_manhattan(eng, topn, members=None, rows=None, exclude=None, where=None, labels=None, seen=None, only=None):
+    """MANHATTAN REQUESTS (include/mi355rec_diag.h): the `topn` rows NEAREST by L1 distance to the members (the mean over the
+    members of sum_j |q_kj - x_j|).  `eng`: a CosineEngine, a lane or a NodeEngine; `members` k x 12 by value or `rows` of the
+    engine (never returned), one of them; `exclude`, `where`, `labels`, `seen` / `only` as in query_playlist_topn.
+    Returns (ids int64[c], distances float32[c]), nearest first, ties by id.
+        ids, distances = query_manhattan(eng, 100, rows=playlist_rows, seen=history)
+    (The engines' own methods keep their parameter lists: tests/test_engine_surface.py records them.)"""
+    if (members is None) == (rows is None):
+        raise ValueError("query_manhattan takes members= (by value) or rows= (by row), one of them")
+    m = _np_members(members) if members is not None else _np_rows(rows)
+    n_out = max(int(topn), 1)
+    idx = np.empty(n_out, dtype=np.int64)
+    dist = np.empty(n_out, dtype=np.float32)
+    count = ctypes.c_int(0)
+
+    def ptr(a):
+        return a.ctypes.data_as(ctypes.c_void_p)
+
+    flt = make_filter(where) if where is not None else None
+    ex = np.ascontiguousarray(np.asarray([] if exclude is None else list(exclude), dtype=np.int64).reshape(-1))
+    q = capi.ManhattanQuery()
+    q.size = ctypes.sizeof(capi.ManhattanQuery)
+    q.members, q.rows = (None, ptr(m)) if m.dtype == np.int64 else (ptr(m), None)
+    q.exclude_global, q.n_exclude = (ptr(ex) if ex.size else None), int(ex.size)
+    q.filter = ctypes.pointer(flt) if flt is not None else None
+    if labels is not None:
+        lab = _np_labels(labels)
+        q.labels, q.n_labels = ptr(lab), int(lab.size)   # (an empty set stays a non-NULL pointer: the library refuses it)
+    q.k, q.topn = int(m.shape[0]), int(topn)
+    res = capi.ManhattanResult(ptr(idx), ptr(dist), ctypes.pointer(count))
+    entry = getattr(eng._lib, f"{eng._prefix}query_manhattan_request")
+
+    def call(rowset):
+        ext = _request_ext(None, rowset)
+        eng._check(entry(eng._h, ctypes.byref(q), ctypes.byref(ext) if rowset is not None else None, ctypes.byref(res)))
+
+    eng._with_set(seen, only, call)
+    c = count.value
+    return idx[:c].copy(), dist[:c].copy()
+
+
 def candidates_counters(eng) -> dict:
     """mi355rec_candidates_counters of a CosineEngine (or a lane): the requests that took the gather launch and the distinct
     in-shard list entries those launches were given, since the handle was created."""

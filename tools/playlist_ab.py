@@ -10,6 +10,7 @@ label and filter tests:
     scaled_k10               cosine with the scale set [2, 1, .5, 0, 1, 1, 3, 1, .25, 1, 1, 0]
     labelled_k10             within 3 of 114 labels (uniformly dealt)
     filtered_k10             one feature within [0, 0.1]: about 10 % of the rows pass
+    anyof_k1, _k10, _k32     the any-of request (engine.query_anyof: with out_member)
 
     python tools/playlist_ab.py --ab path/to/parent/libmi355rec.so [--kinds plain_k1,prior_k10] --out profiles/r16_playlist_cut_ab.json
 
@@ -34,7 +35,11 @@ PLAIN = ("plain_k1", "plain_k10")
 
 def kinds_of(eng, topn):
     """{kind: (K, call)}; a kind that needs side data loads it on first use."""
+    from spotify_recommender_amd.engine import query_anyof
     return {
+        "anyof_k1": (1, lambda rows: query_anyof(eng, topn, rows=rows)),
+        "anyof_k10": (10, lambda rows: query_anyof(eng, topn, rows=rows)),
+        "anyof_k32": (32, lambda rows: query_anyof(eng, topn, rows=rows)),
         "plain_k1": (1, lambda rows: eng.query_playlist_topn(rows, topn)),
         "plain_k10": (10, lambda rows: eng.query_playlist_topn(rows, topn)),
         "prior_k10": (10, lambda rows: eng.query_playlist_topn(rows, topn, prior_weight=0.25)),
