@@ -68,11 +68,15 @@ class PlaylistResult(ctypes.Structure):
                 ("out_pool_rows", POINTER(c_int))]
 
 
+# The three metric requests (distance, any-of, Manhattan) are one 64-byte layout under three names in the C-ABI: three classes here.
+_METRIC_QUERY_FIELDS = [("size", c_uint32), ("flags", c_uint32), ("members", c_void_p), ("rows", c_void_p), ("exclude_global", c_void_p),
+                        ("filter", POINTER(Filter)), ("labels", c_void_p), ("k", c_int32), ("n_exclude", c_int32), ("n_labels", c_int32),
+                        ("topn", c_int32)]
+
+
 class DistanceQuery(ctypes.Structure):
     """mi355rec_distance_query_t (include/mi355rec_diag.h, DISTANCE REQUESTS); `size` is sizeof of this struct, flags 0."""
-    _fields_ = [("size", c_uint32), ("flags", c_uint32), ("members", c_void_p), ("rows", c_void_p), ("exclude_global", c_void_p),
-                ("filter", POINTER(Filter)), ("labels", c_void_p), ("k", c_int32), ("n_exclude", c_int32), ("n_labels", c_int32),
-                ("topn", c_int32)]
+    _fields_ = _METRIC_QUERY_FIELDS
 
 
 class DistanceResult(ctypes.Structure):
@@ -82,9 +86,7 @@ class DistanceResult(ctypes.Structure):
 
 class AnyOfQuery(ctypes.Structure):
     """mi355rec_anyof_query_t (include/mi355rec_diag.h, ANY-OF REQUESTS); `size` is sizeof of this struct, flags 0."""
-    _fields_ = [("size", c_uint32), ("flags", c_uint32), ("members", c_void_p), ("rows", c_void_p), ("exclude_global", c_void_p),
-                ("filter", POINTER(Filter)), ("labels", c_void_p), ("k", c_int32), ("n_exclude", c_int32), ("n_labels", c_int32),
-                ("topn", c_int32)]
+    _fields_ = _METRIC_QUERY_FIELDS
 
 
 class AnyOfResult(ctypes.Structure):
@@ -94,9 +96,7 @@ class AnyOfResult(ctypes.Structure):
 
 class ManhattanQuery(ctypes.Structure):
     """mi355rec_manhattan_query_t (include/mi355rec_diag.h, MANHATTAN REQUESTS); `size` is sizeof of this struct, flags 0."""
-    _fields_ = [("size", c_uint32), ("flags", c_uint32), ("members", c_void_p), ("rows", c_void_p), ("exclude_global", c_void_p),
-                ("filter", POINTER(Filter)), ("labels", c_void_p), ("k", c_int32), ("n_exclude", c_int32), ("n_labels", c_int32),
-                ("topn", c_int32)]
+    _fields_ = _METRIC_QUERY_FIELDS
 
 
 class ManhattanResult(ctypes.Structure):

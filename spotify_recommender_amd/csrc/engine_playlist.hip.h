@@ -469,6 +469,31 @@ int score_request(mi355rec* h, Request r, const int64_t* candidates, int64_t n_c
     return sync_playlist_scores(h, r, {out_value, out_admissible});
 }
 
+// The ONE body of every exported entry point that takes a request struct (playlist_request.h: from_request converts whichever it
+// is): the null handle, the conversion, then the way down: score_request with `score` (its own checks), else the row set's owner,
+// the list's count (candidates.h; the ids are checked in playlist_launch's one pass over them) and sync_playlist_query.
+template <class Query, class Result>
+int request_entry(mi355rec* h, const Query* query, const mi355rec_request_ext_t* ext, const Result* result,
+                  const mi355playlist::CandidateList& list, const mi355playlist::ScoreOutputs* score = nullptr) {
+    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    Query full;
+    Request r;
+    Outputs out;
+    char why[160];
+    if (mi355playlist::from_request(query, ext, result, &full, &r, &out, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    if (score) return score_request(h, r, list.ids, list.n, score->value, score->admissible);
+    if (r.rowset && r.rowset->node) return fail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
+    if (list.given) {
+        if (mi355cand::invalid_count(list.ids, list.n, MI355REC_MAX_CANDIDATES, why, sizeof why))
+            return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+        r.candidates_id_end = kRowsetIdEnd;
+        r.listed = true;
+        r.candidates = list.ids;
+        r.n_candidates = list.n;
+    }
+    return sync_playlist_query(h, r, out);
+}
+
 }  // namespace
 
 namespace mi355node {
@@ -524,35 +549,16 @@ int mi355rec_query_playlist_topn_weighted(mi355rec_t* h, const int64_t* local_ro
 
 // "PLAYLIST REQUESTS": the family's one call; every entry point above (and engine_diverse.hip.h's) is a special case of it.
 // "ROW SETS": the request with its per-request extras; the plain and the _scaled entry points are special cases of THIS one path.
+// Every export from here to mi355rec_set_priors is request_entry (above) with its own structs.
 int mi355rec_query_playlist_request_ext(mi355rec_t* h, const mi355rec_playlist_query_t* query, const mi355rec_request_ext_t* ext,
                                         const mi355rec_playlist_result_t* result) {
-    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    mi355rec_playlist_query_t full;
-    Request r;
-    Outputs out;
-    char why[160];
-    if (mi355playlist::from_query_ext(query, ext, result, &full, &r, &out, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    if (r.rowset && r.rowset->node) return fail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
-    return sync_playlist_query(h, r, out);
+    return request_entry(h, query, ext, result, {});
 }
 
 // "CANDIDATE LISTS": the same request with its list; every check of the _ext call first, then the list's own (candidates.h).
 int mi355rec_query_playlist_request_candidates(mi355rec_t* h, const mi355rec_playlist_query_t* query, const mi355rec_request_ext_t* ext,
                                                const int64_t* candidates, int64_t n_candidates, const mi355rec_playlist_result_t* result) {
-    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    mi355rec_playlist_query_t full;
-    Request r;
-    Outputs out;
-    char why[160];
-    if (mi355playlist::from_query_ext(query, ext, result, &full, &r, &out, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    if (r.rowset && r.rowset->node) return fail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
-    if (mi355cand::invalid_count(candidates, n_candidates, MI355REC_MAX_CANDIDATES, why, sizeof why))
-        return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    r.candidates_id_end = kRowsetIdEnd;   // (the ids are checked in playlist_launch's one pass over them)
-    r.listed = true;
-    r.candidates = candidates;
-    r.n_candidates = n_candidates;
-    return sync_playlist_query(h, r, out);
+    return request_entry(h, query, ext, result, {true, candidates, n_candidates});
 }
 
 int mi355rec_query_playlist_request_scaled(mi355rec_t* h, const mi355rec_playlist_query_t* query, const float* feature_scales,
@@ -568,60 +574,27 @@ int mi355rec_query_playlist_request(mi355rec_t* h, const mi355rec_playlist_query
 // "DISTANCE REQUESTS": the same Request with metric = kDistance through the same path.
 int mi355rec_query_distance_request_ext(mi355rec_t* h, const mi355rec_distance_query_t* query, const mi355rec_request_ext_t* ext,
                                         const mi355rec_distance_result_t* result) {
-    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    mi355rec_distance_query_t full;
-    Request r;
-    Outputs out;
-    char why[160];
-    if (mi355playlist::from_distance_query_ext(query, ext, result, &full, &r, &out, why, sizeof why))
-        return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    if (r.rowset && r.rowset->node) return fail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
-    return sync_playlist_query(h, r, out);
+    return request_entry(h, query, ext, result, {});
 }
 
 int mi355rec_query_distance_request_candidates(mi355rec_t* h, const mi355rec_distance_query_t* query, const mi355rec_request_ext_t* ext,
                                                const int64_t* candidates, int64_t n_candidates, const mi355rec_distance_result_t* result) {
-    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    mi355rec_distance_query_t full;
-    Request r;
-    Outputs out;
-    char why[160];
-    if (mi355playlist::from_distance_query_ext(query, ext, result, &full, &r, &out, why, sizeof why))
-        return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    if (r.rowset && r.rowset->node) return fail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
-    if (mi355cand::invalid_count(candidates, n_candidates, MI355REC_MAX_CANDIDATES, why, sizeof why))
-        return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    r.candidates_id_end = kRowsetIdEnd;   // (the ids are checked in playlist_launch's one pass over them)
-    r.listed = true;
-    r.candidates = candidates;
-    r.n_candidates = n_candidates;
-    return sync_playlist_query(h, r, out);
+    return request_entry(h, query, ext, result, {true, candidates, n_candidates});
 }
 
-// "CANDIDATE SCORES": the _candidates calls' conversion and checks (there is no result struct: an empty one stands in), then score_request.
+// "CANDIDATE SCORES": the _candidates calls' conversion (there is no result struct: an empty one stands in), then score_request.
 int mi355rec_score_playlist_request_candidates(mi355rec_t* h, const mi355rec_playlist_query_t* query, const mi355rec_request_ext_t* ext,
                                                const int64_t* candidates, int64_t n_candidates, float* out_value, uint8_t* out_admissible) {
-    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    mi355rec_playlist_query_t full;
     const mi355rec_playlist_result_t none = {};
-    Request r;
-    Outputs out;
-    char why[160];
-    if (mi355playlist::from_query_ext(query, ext, &none, &full, &r, &out, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    return score_request(h, r, candidates, n_candidates, out_value, out_admissible);
+    const mi355playlist::ScoreOutputs score = {out_value, out_admissible};
+    return request_entry(h, query, ext, &none, {true, candidates, n_candidates}, &score);
 }
 
 int mi355rec_score_distance_request_candidates(mi355rec_t* h, const mi355rec_distance_query_t* query, const mi355rec_request_ext_t* ext,
                                                const int64_t* candidates, int64_t n_candidates, float* out_distance, uint8_t* out_admissible) {
-    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    mi355rec_distance_query_t full;
     const mi355rec_distance_result_t none = {};
-    Request r;
-    Outputs out;
-    char why[160];
-    if (mi355playlist::from_distance_query_ext(query, ext, &none, &full, &r, &out, why, sizeof why))
-        return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    return score_request(h, r, candidates, n_candidates, out_distance, out_admissible);
+    const mi355playlist::ScoreOutputs score = {out_distance, out_admissible};
+    return request_entry(h, query, ext, &none, {true, candidates, n_candidates}, &score);
 }
 
 int mi355rec_query_distance_request_scaled(mi355rec_t* h, const mi355rec_distance_query_t* query, const float* feature_scales,
@@ -637,27 +610,13 @@ int mi355rec_query_distance_request(mi355rec_t* h, const mi355rec_distance_query
 // "ANY-OF REQUESTS": the same Request with metric = kAnyOf through the same path; its scan is anyof_scan_kernel.
 int mi355rec_query_anyof_request(mi355rec_t* h, const mi355rec_anyof_query_t* query, const mi355rec_request_ext_t* ext,
                                  const mi355rec_anyof_result_t* result) {
-    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    mi355rec_anyof_query_t full;
-    Request r;
-    Outputs out;
-    char why[160];
-    if (mi355playlist::from_anyof_query(query, ext, result, &full, &r, &out, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    if (r.rowset && r.rowset->node) return fail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
-    return sync_playlist_query(h, r, out);
+    return request_entry(h, query, ext, result, {});
 }
 
 // "MANHATTAN REQUESTS": the same Request with metric = kManhattan through the same path; its scan is manhattan_scan_kernel.
 int mi355rec_query_manhattan_request(mi355rec_t* h, const mi355rec_manhattan_query_t* query, const mi355rec_request_ext_t* ext,
                                      const mi355rec_manhattan_result_t* result) {
-    if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    mi355rec_manhattan_query_t full;
-    Request r;
-    Outputs out;
-    char why[160];
-    if (mi355playlist::from_manhattan_query(query, ext, result, &full, &r, &out, why, sizeof why)) return fail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    if (r.rowset && r.rowset->node) return fail(h, MI355REC_ERR_INVALID_ARG, "row set of another handle");
-    return sync_playlist_query(h, r, out);
+    return request_entry(h, query, ext, result, {});
 }
 
 // "ROW PRIORS"

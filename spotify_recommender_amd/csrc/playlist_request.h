@@ -2,9 +2,11 @@
 // FILTERS", "WEIGHTED PLAYLISTS", "DIVERSIFIED TOP-N", "GROUP CAPS"), its outputs and its argument checks, shared by the single
 // handle (engine_playlist.hip.h), the node handle (sharded.hip) and the CPU backend.  Every exported entry point of the
 // family fills a Request and an Outputs and takes the one path of its handle type.  Neither struct is part of the C-ABI; the
-// C-ABI's own request ("PLAYLIST REQUESTS": mi355rec_playlist_query_t, the only call that takes a label set) is converted
-// to them by from_query below, and the distance request ("DISTANCE REQUESTS": mi355rec_distance_query_t, the same Request with
-// metric = kDistance) by from_distance_query, the Manhattan request ("MANHATTAN REQUESTS", metric = kManhattan) by from_manhattan_query.
+// C-ABI's own request structs are converted to them by from_request below, one overload per struct: the playlist request
+// ("PLAYLIST REQUESTS": mi355rec_playlist_query_t, with its flags) by its own body, the three 64-byte metric requests ("DISTANCE
+// REQUESTS", "ANY-OF REQUESTS", "MANHATTAN REQUESTS": the same Request with another `metric`) by ONE body, from_metric_query, over a
+// MetricKind row each.  Every self-sized struct (the four requests and the ext) is read by read_sized; every kind applies the ext
+// through from_ext then apply_ext.  A further metric request is a MetricKind row, an outputs_of mapping and an overload.
 #pragma once
 
 #include <cmath>
@@ -261,16 +263,32 @@ inline bool invalid_score_request(const Request& r, int64_t n_candidates, const 
     return false;
 }
 
-// The C-ABI's request (include/mi355rec_diag.h, "PLAYLIST REQUESTS") as the Request and Outputs every layer below takes.
-// q->size says how much of the struct the caller knows: a shorter one is read as "later fields zero"; 0, or more than this
-// library knows, is refused.  True when the structs cannot be used; then msg[0..cap) says why.
+// The size rule of every self-sized struct of the C-ABI (its first field is `uint32_t size`): in->size says how much of the
+// struct the caller knows.  It must be the end of a field (`ends`, the full size last: a struct that ends inside a field would hand
+// over half a pointer); a shorter one is read as "later fields zero"; 0, or more than this library knows, is refused.  True when
+// refused; then msg[0..cap) says why, naming the struct `what`.  Otherwise *full holds the struct as this library reads it.
+template <class T, size_t N>
+inline bool read_sized(const T* in, const char* what, const size_t (&ends)[N], T* full, char* msg, size_t cap) {
+    bool known = false;
+    for (size_t e : ends) known = known || in->size == e;
+    if (!known) {
+        std::snprintf(msg, cap, "%s of size %u: not the end of a field of the %u bytes this library reads", what,
+                      static_cast<unsigned>(in->size), static_cast<unsigned>(sizeof *full));
+        return true;
+    }
+    std::memset(full, 0, sizeof *full);
+    std::memcpy(full, in, in->size);
+    return false;
+}
+
+// The C-ABI's request (include/mi355rec_diag.h, "PLAYLIST REQUESTS") as the Request and Outputs every layer below takes, read by
+// read_sized' rule.  True when the structs cannot be used; then msg[0..cap) says why.
 inline bool from_query(const mi355rec_playlist_query_t* q, const mi355rec_playlist_result_t* res, mi355rec_playlist_query_t* full,
                        Request* r, Outputs* out, char* msg, size_t cap) {
     if (!q || !res) {
         std::snprintf(msg, cap, "null argument");
         return true;
     }
-    // (a struct that ends inside a field would hand over half a pointer: only sizes that end where a field ends)
     static const size_t ends[] = {offsetof(mi355rec_playlist_query_t, flags),          offsetof(mi355rec_playlist_query_t, members),
                                   offsetof(mi355rec_playlist_query_t, rows),           offsetof(mi355rec_playlist_query_t, weights),
                                   offsetof(mi355rec_playlist_query_t, exclude_global), offsetof(mi355rec_playlist_query_t, filter),
@@ -282,15 +300,7 @@ inline bool from_query(const mi355rec_playlist_query_t* q, const mi355rec_playli
     static_assert(offsetof(mi355rec_playlist_query_t, prior_weight) == offsetof(mi355rec_playlist_query_t, max_per_group) + sizeof(int32_t) &&
                       offsetof(mi355rec_playlist_query_t, prior_weight) == 84 && sizeof(mi355rec_playlist_query_t) == 88,
                   "prior_weight fills the tail padding: the struct ends where the field ends");
-    bool known = false;
-    for (size_t e : ends) known = known || q->size == e;
-    if (!known) {
-        std::snprintf(msg, cap, "playlist query of size %u: not the end of a field of the %u bytes this library reads",
-                      static_cast<unsigned>(q->size), static_cast<unsigned>(sizeof *full));
-        return true;
-    }
-    std::memset(full, 0, sizeof *full);
-    std::memcpy(full, q, q->size);
+    if (read_sized(q, "playlist query", ends, full, msg, cap)) return true;
     if (full->flags & ~static_cast<uint32_t>(MI355REC_PQ_DIVERSE | MI355REC_PQ_CAPPED | MI355REC_PQ_PRIOR)) {
         std::snprintf(msg, cap, "unknown flags 0x%x in a playlist query", static_cast<unsigned>(full->flags));
         return true;
@@ -348,23 +358,17 @@ inline const float* effective_scales(const float* a) {
     return nullptr;
 }
 
-// "ROW SETS": the per-request extras (mi355rec_request_ext_t) as this library reads them.  ext->size follows the size rules of
-// from_query: a shorter struct that ends where a field ends is read as "later fields zero"; 0, an end inside a field, or more than
-// this library knows is refused.  A null ext is the ext with every field zero.  True when it cannot be used; then msg says why.
+// "ROW SETS": the per-request extras (mi355rec_request_ext_t) as this library reads them, by read_sized' rule.  A null ext is the
+// ext with every field zero.  True when it cannot be used; then msg says why.
 inline bool from_ext(const mi355rec_request_ext_t* ext, mi355rec_request_ext_t* full, char* msg, size_t cap) {
-    std::memset(full, 0, sizeof *full);
-    if (!ext) return false;
+    if (!ext) {
+        std::memset(full, 0, sizeof *full);
+        return false;
+    }
     static const size_t ends[] = {offsetof(mi355rec_request_ext_t, rowset_mode), offsetof(mi355rec_request_ext_t, feature_scales),
                                   offsetof(mi355rec_request_ext_t, rowset), sizeof(mi355rec_request_ext_t)};
     static_assert(sizeof(mi355rec_request_ext_t) == 24 && offsetof(mi355rec_request_ext_t, rowset) == 16, "the struct ends where its last field ends");
-    bool known = false;
-    for (size_t e : ends) known = known || ext->size == e;
-    if (!known) {
-        std::snprintf(msg, cap, "request ext of size %u: not the end of a field of the %u bytes this library reads",
-                      static_cast<unsigned>(ext->size), static_cast<unsigned>(sizeof *full));
-        return true;
-    }
-    std::memcpy(full, ext, ext->size);
+    if (read_sized(ext, "request ext", ends, full, msg, cap)) return true;
     if (full->rowset && full->rowset_mode != MI355REC_ROWSET_EXCLUDE && full->rowset_mode != MI355REC_ROWSET_ONLY) {
         std::snprintf(msg, cap, "rowset_mode %u: MI355REC_ROWSET_EXCLUDE (0) or MI355REC_ROWSET_ONLY (1)", static_cast<unsigned>(full->rowset_mode));
         return true;
@@ -383,11 +387,11 @@ inline bool apply_ext(const mi355rec_request_ext_t& ext, Request* r, char* msg, 
     return false;
 }
 
-// from_query with the extras of the _ext entry points (the _scaled ones pass an ext that holds their scales): every check of
-// from_query first (its messages), then the ext's own; with scales, flags must be 0 and the scales usable.  A null ext, or one whose
-// pointers are null, is from_query itself.
-inline bool from_query_ext(const mi355rec_playlist_query_t* q, const mi355rec_request_ext_t* ext, const mi355rec_playlist_result_t* res,
-                           mi355rec_playlist_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
+// The playlist request with its extras, as every entry point that takes the struct converts it (the _scaled ones pass an ext that
+// holds their scales): every check of from_query first (its messages), then the ext's own; with scales, flags must be 0 and the
+// scales usable.  A null ext, or one whose pointers are null, is from_query itself.
+inline bool from_request(const mi355rec_playlist_query_t* q, const mi355rec_request_ext_t* ext, const mi355rec_playlist_result_t* res,
+                         mi355rec_playlist_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
     if (from_query(q, res, full, r, out, msg, cap)) return true;
     mi355rec_request_ext_t x;
     if (from_ext(ext, &x, msg, cap)) return true;
@@ -413,169 +417,89 @@ inline mi355rec_request_ext_t scales_only_ext(const float* scales) {
     return x;
 }
 
-// The C-ABI's distance request (include/mi355rec_diag.h, "DISTANCE REQUESTS") as the same Request (metric = kDistance) and
-// Outputs: the size rules of from_query, flags must be 0.  True when the structs cannot be used; then msg[0..cap) says why.
-inline bool from_distance_query(const mi355rec_distance_query_t* q, const mi355rec_distance_result_t* res, mi355rec_distance_query_t* full,
-                                Request* r, Outputs* out, char* msg, size_t cap) {
+// The three 64-byte metric requests of the C-ABI (include/mi355rec_diag.h: "DISTANCE REQUESTS", "ANY-OF REQUESTS", "MANHATTAN
+// REQUESTS") are one layout under three names; what tells them apart is a row of this table ...
+struct MetricKind {
+    const char* noun;        // the struct as the messages name it, with its article
+    int metric;
+    bool report_distance;    // the score output holds the distance (Request::report_distance)
+    const char* no_scales;   // null: feature scales are served; or the text that refuses them
+};
+constexpr MetricKind kDistanceQuery = {"a distance query", kDistance, true, nullptr};
+constexpr MetricKind kAnyOfQuery = {"an any-of query", kAnyOf, false, "any-of requests take no feature scales"};
+constexpr MetricKind kManhattanQuery = {"a manhattan query", kManhattan, true, "manhattan requests take no feature scales"};
+
+// ... and where its result struct's pointers go (any-of's carries out_member: the attribution is wanted when it is given).
+inline Outputs outputs_of(const mi355rec_distance_result_t& res) { return {res.out_idx, res.out_distance, nullptr, res.out_count, nullptr}; }
+inline Outputs outputs_of(const mi355rec_manhattan_result_t& res) { return {res.out_idx, res.out_distance, nullptr, res.out_count, nullptr}; }
+inline Outputs outputs_of(const mi355rec_anyof_result_t& res) {
+    return {res.out_idx, res.out_score, nullptr, res.out_count, nullptr, res.out_member};
+}
+
+// A metric request with its extras as the same Request (metric = kind.metric) and Outputs: read_sized' rule, flags must be 0,
+// members by value or by row, then the ext (a null one, or one whose pointers are null, adds nothing).  True when the structs
+// cannot be used; then msg[0..cap) says why.
+template <class Query, class Result>
+inline bool from_metric_query(const MetricKind& kind, const Query* q, const mi355rec_request_ext_t* ext, const Result* res, Query* full,
+                              Request* r, Outputs* out, char* msg, size_t cap) {
     if (!q || !res) {
         std::snprintf(msg, cap, "null argument");
         return true;
     }
-    static const size_t ends[] = {offsetof(mi355rec_distance_query_t, flags),          offsetof(mi355rec_distance_query_t, members),
-                                  offsetof(mi355rec_distance_query_t, rows),           offsetof(mi355rec_distance_query_t, exclude_global),
-                                  offsetof(mi355rec_distance_query_t, filter),         offsetof(mi355rec_distance_query_t, labels),
-                                  offsetof(mi355rec_distance_query_t, k),              offsetof(mi355rec_distance_query_t, n_exclude),
-                                  offsetof(mi355rec_distance_query_t, n_labels),       offsetof(mi355rec_distance_query_t, topn),
-                                  sizeof(mi355rec_distance_query_t)};
-    static_assert(sizeof(mi355rec_distance_query_t) == offsetof(mi355rec_distance_query_t, topn) + sizeof(int32_t) &&
-                      sizeof(mi355rec_distance_query_t) == 64,
+    static const size_t ends[] = {offsetof(Query, flags),  offsetof(Query, members), offsetof(Query, rows), offsetof(Query, exclude_global),
+                                  offsetof(Query, filter), offsetof(Query, labels),  offsetof(Query, k),    offsetof(Query, n_exclude),
+                                  offsetof(Query, n_labels), offsetof(Query, topn),  sizeof(Query)};
+    static_assert(sizeof(Query) == offsetof(Query, topn) + sizeof(int32_t) && sizeof(Query) == 64,
                   "no tail padding: the struct ends where its last field ends");
-    bool known = false;
-    for (size_t e : ends) known = known || q->size == e;
-    if (!known) {
-        std::snprintf(msg, cap, "distance query of size %u: not the end of a field of the %u bytes this library reads",
-                      static_cast<unsigned>(q->size), static_cast<unsigned>(sizeof *full));
-        return true;
-    }
-    std::memset(full, 0, sizeof *full);
-    std::memcpy(full, q, q->size);
+    const char* bare = std::strchr(kind.noun, ' ') + 1;   // the noun without its article
+    if (read_sized(q, bare, ends, full, msg, cap)) return true;
     if (full->flags != 0u) {
-        std::snprintf(msg, cap, "flags 0x%x in a distance query: must be 0 (weights, diversified and capped calls and priors are not served)",
-                      static_cast<unsigned>(full->flags));
+        std::snprintf(msg, cap, "flags 0x%x in %s: must be 0 (weights, diversified and capped calls and priors are not served)",
+                      static_cast<unsigned>(full->flags), kind.noun);
         return true;
     }
     if (full->members && full->rows) {
-        std::snprintf(msg, cap, "members by value and by row in one distance query");
+        std::snprintf(msg, cap, "members by value and by row in one %s", bare);
         return true;
     }
     if (!full->members && !full->rows) {
-        std::snprintf(msg, cap, "a distance query needs members by value or by row");
+        std::snprintf(msg, cap, "%s needs members by value or by row", kind.noun);
         return true;
     }
     *r = request(full->members, full->rows, nullptr, full->k, full->exclude_global, full->n_exclude, full->filter, full->topn);
     r->labels = full->labels;
     r->n_labels = full->n_labels;
-    r->metric = kDistance;
-    r->report_distance = true;
-    *out = {res->out_idx, res->out_distance, nullptr, res->out_count, nullptr};
-    return false;
-}
-
-// The C-ABI's Manhattan request (include/mi355rec_diag.h, "MANHATTAN REQUESTS") as the same Request (metric = kManhattan) and
-// Outputs: the size rules of from_query, flags must be 0, no feature scales.  True when the structs cannot be used; then
-// msg[0..cap) says why.
-inline bool from_manhattan_query(const mi355rec_manhattan_query_t* q, const mi355rec_request_ext_t* ext, const mi355rec_manhattan_result_t* res,
-                                 mi355rec_manhattan_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
-    if (!q || !res) {
-        std::snprintf(msg, cap, "null argument");
-        return true;
-    }
-    static const size_t ends[] = {offsetof(mi355rec_manhattan_query_t, flags),          offsetof(mi355rec_manhattan_query_t, members),
-                                  offsetof(mi355rec_manhattan_query_t, rows),           offsetof(mi355rec_manhattan_query_t, exclude_global),
-                                  offsetof(mi355rec_manhattan_query_t, filter),         offsetof(mi355rec_manhattan_query_t, labels),
-                                  offsetof(mi355rec_manhattan_query_t, k),              offsetof(mi355rec_manhattan_query_t, n_exclude),
-                                  offsetof(mi355rec_manhattan_query_t, n_labels),       offsetof(mi355rec_manhattan_query_t, topn),
-                                  sizeof(mi355rec_manhattan_query_t)};
-    static_assert(sizeof(mi355rec_manhattan_query_t) == offsetof(mi355rec_manhattan_query_t, topn) + sizeof(int32_t) &&
-                      sizeof(mi355rec_manhattan_query_t) == 64,
-                  "no tail padding: the struct ends where its last field ends");
-    bool known = false;
-    for (size_t e : ends) known = known || q->size == e;
-    if (!known) {
-        std::snprintf(msg, cap, "manhattan query of size %u: not the end of a field of the %u bytes this library reads",
-                      static_cast<unsigned>(q->size), static_cast<unsigned>(sizeof *full));
-        return true;
-    }
-    std::memset(full, 0, sizeof *full);
-    std::memcpy(full, q, q->size);
-    if (full->flags != 0u) {
-        std::snprintf(msg, cap, "flags 0x%x in a manhattan query: must be 0 (weights, diversified and capped calls and priors are not served)",
-                      static_cast<unsigned>(full->flags));
-        return true;
-    }
-    if (full->members && full->rows) {
-        std::snprintf(msg, cap, "members by value and by row in one manhattan query");
-        return true;
-    }
-    if (!full->members && !full->rows) {
-        std::snprintf(msg, cap, "a manhattan query needs members by value or by row");
-        return true;
-    }
-    *r = request(full->members, full->rows, nullptr, full->k, full->exclude_global, full->n_exclude, full->filter, full->topn);
-    r->labels = full->labels;
-    r->n_labels = full->n_labels;
-    r->metric = kManhattan;
-    r->report_distance = true;
-    *out = {res->out_idx, res->out_distance, nullptr, res->out_count, nullptr};
+    r->metric = kind.metric;
+    r->report_distance = kind.report_distance;
+    *out = outputs_of(*res);
+    r->attribute = out->member != nullptr;
     mi355rec_request_ext_t x;
     if (from_ext(ext, &x, msg, cap)) return true;
-    if (x.feature_scales) {
-        std::snprintf(msg, cap, "manhattan requests take no feature scales");
+    if (x.feature_scales && kind.no_scales) {
+        std::snprintf(msg, cap, "%s", kind.no_scales);
         return true;
     }
     return apply_ext(x, r, msg, cap);
 }
 
-// The C-ABI's any-of request (include/mi355rec_diag.h, "ANY-OF REQUESTS") as the same Request (metric = kAnyOf) and Outputs: the
-// size rules of from_query, flags must be 0, no feature scales.  True when the structs cannot be used; then msg[0..cap) says why.
-inline bool from_anyof_query(const mi355rec_anyof_query_t* q, const mi355rec_request_ext_t* ext, const mi355rec_anyof_result_t* res,
-                             mi355rec_anyof_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
-    if (!q || !res) {
-        std::snprintf(msg, cap, "null argument");
-        return true;
-    }
-    static const size_t ends[] = {offsetof(mi355rec_anyof_query_t, flags),          offsetof(mi355rec_anyof_query_t, members),
-                                  offsetof(mi355rec_anyof_query_t, rows),           offsetof(mi355rec_anyof_query_t, exclude_global),
-                                  offsetof(mi355rec_anyof_query_t, filter),         offsetof(mi355rec_anyof_query_t, labels),
-                                  offsetof(mi355rec_anyof_query_t, k),              offsetof(mi355rec_anyof_query_t, n_exclude),
-                                  offsetof(mi355rec_anyof_query_t, n_labels),       offsetof(mi355rec_anyof_query_t, topn),
-                                  sizeof(mi355rec_anyof_query_t)};
-    static_assert(sizeof(mi355rec_anyof_query_t) == offsetof(mi355rec_anyof_query_t, topn) + sizeof(int32_t) && sizeof(mi355rec_anyof_query_t) == 64,
-                  "no tail padding: the struct ends where its last field ends");
-    bool known = false;
-    for (size_t e : ends) known = known || q->size == e;
-    if (!known) {
-        std::snprintf(msg, cap, "any-of query of size %u: not the end of a field of the %u bytes this library reads",
-                      static_cast<unsigned>(q->size), static_cast<unsigned>(sizeof *full));
-        return true;
-    }
-    std::memset(full, 0, sizeof *full);
-    std::memcpy(full, q, q->size);
-    if (full->flags != 0u) {
-        std::snprintf(msg, cap, "flags 0x%x in an any-of query: must be 0 (weights, diversified and capped calls and priors are not served)",
-                      static_cast<unsigned>(full->flags));
-        return true;
-    }
-    if (full->members && full->rows) {
-        std::snprintf(msg, cap, "members by value and by row in one any-of query");
-        return true;
-    }
-    if (!full->members && !full->rows) {
-        std::snprintf(msg, cap, "an any-of query needs members by value or by row");
-        return true;
-    }
-    *r = request(full->members, full->rows, nullptr, full->k, full->exclude_global, full->n_exclude, full->filter, full->topn);
-    r->labels = full->labels;
-    r->n_labels = full->n_labels;
-    r->metric = kAnyOf;
-    r->attribute = res->out_member != nullptr;
-    *out = {res->out_idx, res->out_score, nullptr, res->out_count, nullptr, res->out_member};
-    mi355rec_request_ext_t x;
-    if (from_ext(ext, &x, msg, cap)) return true;
-    if (x.feature_scales) {
-        std::snprintf(msg, cap, "any-of requests take no feature scales");
-        return true;
-    }
-    return apply_ext(x, r, msg, cap);
+inline bool from_request(const mi355rec_distance_query_t* q, const mi355rec_request_ext_t* ext, const mi355rec_distance_result_t* res,
+                         mi355rec_distance_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
+    return from_metric_query(kDistanceQuery, q, ext, res, full, r, out, msg, cap);
+}
+inline bool from_request(const mi355rec_anyof_query_t* q, const mi355rec_request_ext_t* ext, const mi355rec_anyof_result_t* res,
+                         mi355rec_anyof_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
+    return from_metric_query(kAnyOfQuery, q, ext, res, full, r, out, msg, cap);
+}
+inline bool from_request(const mi355rec_manhattan_query_t* q, const mi355rec_request_ext_t* ext, const mi355rec_manhattan_result_t* res,
+                         mi355rec_manhattan_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
+    return from_metric_query(kManhattanQuery, q, ext, res, full, r, out, msg, cap);
 }
 
-// from_distance_query with the extras of the _ext entry points (null, or null pointers: from_distance_query itself).
-inline bool from_distance_query_ext(const mi355rec_distance_query_t* q, const mi355rec_request_ext_t* ext, const mi355rec_distance_result_t* res,
-                                    mi355rec_distance_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
-    if (from_distance_query(q, res, full, r, out, msg, cap)) return true;
-    mi355rec_request_ext_t x;
-    if (from_ext(ext, &x, msg, cap)) return true;
-    return apply_ext(x, r, msg, cap);
-}
+// "CANDIDATE LISTS": the list an entry point was handed beside its request, if it takes one (given; {} is "no list").
+struct CandidateList {
+    bool given = false;
+    const int64_t* ids = nullptr;
+    int64_t n = 0;
+};
 
 }  // namespace mi355playlist

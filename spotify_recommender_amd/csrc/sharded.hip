@@ -919,6 +919,27 @@ int sharded_scores(mi355rec_sharded_t* h, Request r, const mi355playlist::ScoreO
     }
     return MI355REC_OK;
 }
+
+// The ONE body of every exported entry point that takes a request struct (playlist_request.h: from_request converts whichever it
+// is): the null handle, the conversion, the list's own checks (CANDIDATE LISTS: its ids are rows of the catalogue), then
+// sharded_scores with `score`, else sharded_playlist.  (A template: C++ linkage inside this file's extern "C" block.)
+extern "C++" template <class Query, class Result>
+int node_request_entry(mi355rec_sharded_t* h, const Query* query, const mi355rec_request_ext_t* ext, const Result* result,
+                       const mi355playlist::CandidateList& list, const mi355playlist::ScoreOutputs* score = nullptr) {
+    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
+    Query full;
+    Request r;
+    Outputs out;
+    char why[160];
+    if (mi355playlist::from_request(query, ext, result, &full, &r, &out, why, sizeof why) ||
+        (list.given && mi355cand::invalid_list(list.ids, list.n, MI355REC_MAX_CANDIDATES, h->n, why, sizeof why)))
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
+    r.listed = list.given;
+    r.score = score != nullptr;
+    r.candidates = list.ids;
+    r.n_candidates = list.n;
+    return score ? sharded_scores(h, r, *score) : sharded_playlist(h, r, out);
+}
 }  // namespace
 
 int mi355rec_sharded_query_mean_topn(mi355rec_sharded_t* h, const float* queries, int k, const int64_t* exclude_global, int n_exclude,
@@ -1005,13 +1026,7 @@ int mi355rec_sharded_query_playlist_topn_capped(mi355rec_sharded_t* h, const int
 // own copy of the bitmap (engine_playlist.hip.h), the CPU backend tests the host bitmap.
 int mi355rec_sharded_query_playlist_request_ext(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
                                                 const mi355rec_request_ext_t* ext, const mi355rec_playlist_result_t* result) {
-    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    mi355rec_playlist_query_t full;
-    Request r;
-    Outputs out;
-    char why[160];
-    if (mi355playlist::from_query_ext(query, ext, result, &full, &r, &out, why, sizeof why)) return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    return sharded_playlist(h, r, out);
+    return node_request_entry(h, query, ext, result, {});
 }
 
 int mi355rec_sharded_query_playlist_request_scaled(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
@@ -1028,14 +1043,7 @@ int mi355rec_sharded_query_playlist_request(mi355rec_sharded_t* h, const mi355re
 // DISTANCE REQUESTS (include/mi355rec_diag.h): the same Request with metric = kDistance through sharded_playlist.
 int mi355rec_sharded_query_distance_request_ext(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
                                                 const mi355rec_request_ext_t* ext, const mi355rec_distance_result_t* result) {
-    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    mi355rec_distance_query_t full;
-    Request r;
-    Outputs out;
-    char why[160];
-    if (mi355playlist::from_distance_query_ext(query, ext, result, &full, &r, &out, why, sizeof why))
-        return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    return sharded_playlist(h, r, out);
+    return node_request_entry(h, query, ext, result, {});
 }
 
 int mi355rec_sharded_query_distance_request_scaled(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
@@ -1053,26 +1061,14 @@ int mi355rec_sharded_query_distance_request(mi355rec_sharded_t* h, const mi355re
 // carries each key's member index through its host merge (anyof_over_shards).
 int mi355rec_sharded_query_anyof_request(mi355rec_sharded_t* h, const mi355rec_anyof_query_t* query, const mi355rec_request_ext_t* ext,
                                          const mi355rec_anyof_result_t* result) {
-    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    mi355rec_anyof_query_t full;
-    Request r;
-    Outputs out;
-    char why[160];
-    if (mi355playlist::from_anyof_query(query, ext, result, &full, &r, &out, why, sizeof why)) return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    return sharded_playlist(h, r, out);
+    return node_request_entry(h, query, ext, result, {});
 }
 
 // MANHATTAN REQUESTS (include/mi355rec_diag.h): the same Request with metric = kManhattan through sharded_playlist, as the distance
 // request: the shards answer with -m, what the merge's keys compare, and m is taken from the merged list.
 int mi355rec_sharded_query_manhattan_request(mi355rec_sharded_t* h, const mi355rec_manhattan_query_t* query,
                                              const mi355rec_request_ext_t* ext, const mi355rec_manhattan_result_t* result) {
-    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    mi355rec_manhattan_query_t full;
-    Request r;
-    Outputs out;
-    char why[160];
-    if (mi355playlist::from_manhattan_query(query, ext, result, &full, &r, &out, why, sizeof why)) return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    return sharded_playlist(h, r, out);
+    return node_request_entry(h, query, ext, result, {});
 }
 
 // CANDIDATE LISTS (include/mi355rec_diag.h): the list travels in the Request; its ids are rows of the catalogue.  One handle takes it
@@ -1080,72 +1076,31 @@ int mi355rec_sharded_query_manhattan_request(mi355rec_sharded_t* h, const mi355r
 int mi355rec_sharded_query_playlist_request_candidates(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
                                                        const mi355rec_request_ext_t* ext, const int64_t* candidates, int64_t n_candidates,
                                                        const mi355rec_playlist_result_t* result) {
-    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    mi355rec_playlist_query_t full;
-    Request r;
-    Outputs out;
-    char why[160];
-    if (mi355playlist::from_query_ext(query, ext, result, &full, &r, &out, why, sizeof why) ||
-        mi355cand::invalid_list(candidates, n_candidates, MI355REC_MAX_CANDIDATES, h->n, why, sizeof why))
-        return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    r.listed = true;
-    r.candidates = candidates;
-    r.n_candidates = n_candidates;
-    return sharded_playlist(h, r, out);
+    return node_request_entry(h, query, ext, result, {true, candidates, n_candidates});
 }
 
 int mi355rec_sharded_query_distance_request_candidates(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
                                                        const mi355rec_request_ext_t* ext, const int64_t* candidates, int64_t n_candidates,
                                                        const mi355rec_distance_result_t* result) {
-    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    mi355rec_distance_query_t full;
-    Request r;
-    Outputs out;
-    char why[160];
-    if (mi355playlist::from_distance_query_ext(query, ext, result, &full, &r, &out, why, sizeof why) ||
-        mi355cand::invalid_list(candidates, n_candidates, MI355REC_MAX_CANDIDATES, h->n, why, sizeof why))
-        return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    r.listed = true;
-    r.candidates = candidates;
-    r.n_candidates = n_candidates;
-    return sharded_playlist(h, r, out);
+    return node_request_entry(h, query, ext, result, {true, candidates, n_candidates});
 }
 
-// CANDIDATE SCORES (include/mi355rec_diag.h): the _candidates calls' conversion and checks, then sharded_scores.
+// CANDIDATE SCORES (include/mi355rec_diag.h): the _candidates calls' conversion and checks (there is no result struct: an empty one
+// stands in), then sharded_scores.
 int mi355rec_sharded_score_playlist_request_candidates(mi355rec_sharded_t* h, const mi355rec_playlist_query_t* query,
                                                        const mi355rec_request_ext_t* ext, const int64_t* candidates, int64_t n_candidates,
                                                        float* out_value, uint8_t* out_admissible) {
-    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    mi355rec_playlist_query_t full;
     const mi355rec_playlist_result_t none = {};
-    Request r;
-    Outputs out;
-    char why[160];
-    if (mi355playlist::from_query_ext(query, ext, &none, &full, &r, &out, why, sizeof why) ||
-        mi355cand::invalid_list(candidates, n_candidates, MI355REC_MAX_CANDIDATES, h->n, why, sizeof why))
-        return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    r.listed = r.score = true;
-    r.candidates = candidates;
-    r.n_candidates = n_candidates;
-    return sharded_scores(h, r, {out_value, out_admissible});
+    const mi355playlist::ScoreOutputs score = {out_value, out_admissible};
+    return node_request_entry(h, query, ext, &none, {true, candidates, n_candidates}, &score);
 }
 
 int mi355rec_sharded_score_distance_request_candidates(mi355rec_sharded_t* h, const mi355rec_distance_query_t* query,
                                                        const mi355rec_request_ext_t* ext, const int64_t* candidates, int64_t n_candidates,
                                                        float* out_distance, uint8_t* out_admissible) {
-    if (!h) return sfail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    mi355rec_distance_query_t full;
     const mi355rec_distance_result_t none = {};
-    Request r;
-    Outputs out;
-    char why[160];
-    if (mi355playlist::from_distance_query_ext(query, ext, &none, &full, &r, &out, why, sizeof why) ||
-        mi355cand::invalid_list(candidates, n_candidates, MI355REC_MAX_CANDIDATES, h->n, why, sizeof why))
-        return sfail(h, MI355REC_ERR_INVALID_ARG, "%s", why);
-    r.listed = r.score = true;
-    r.candidates = candidates;
-    r.n_candidates = n_candidates;
-    return sharded_scores(h, r, {out_distance, out_admissible});
+    const mi355playlist::ScoreOutputs score = {out_distance, out_admissible};
+    return node_request_entry(h, query, ext, &none, {true, candidates, n_candidates}, &score);
 }
 
 // ROW SETS (include/mi355rec_diag.h): the global host bitmap, and a device copy beside every engine's rows: a row-sharded placement

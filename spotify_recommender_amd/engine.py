@@ -87,6 +87,51 @@ def make_scales(scales) -> np.ndarray:
     return a
 
 
+def _ptr(a):
+    """A numpy array's data as the void pointer the C-ABI takes."""
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _fill_query(q, members, topn: int, exclude, where, labels) -> tuple:
+    """Fills what the four request structs share (capi.PlaylistQuery, DistanceQuery, AnyOfQuery, ManhattanQuery): size, the members by
+    value (a (k, 12) float32 array) or by row (a 1-D int64 array), the exclusion list, the filter (make_filter), the label set, k and
+    topn.  Returns what the struct now points to: the caller holds it until the call has returned."""
+    flt = make_filter(where) if where is not None else None
+    ex = np.ascontiguousarray(np.asarray([] if exclude is None else list(exclude), dtype=np.int64).reshape(-1))
+    lab = _np_labels(labels) if labels is not None else None
+    q.size = ctypes.sizeof(type(q))
+    q.members, q.rows = (None, _ptr(members)) if members.dtype == np.int64 else (_ptr(members), None)
+    q.exclude_global, q.n_exclude = (_ptr(ex) if ex.size else None), int(ex.size)
+    q.filter = ctypes.pointer(flt) if flt is not None else None
+    if lab is not None:
+        q.labels, q.n_labels = _ptr(lab), int(lab.size)   # (an empty set stays a non-NULL pointer: the library refuses it)
+    q.k, q.topn = int(members.shape[0]), int(topn)
+    return members, flt, ex, lab
+
+
+def _call_request(lib, prefix: str, h, check, kind: str, q, res, scales=None, rowset=None, candidates=None) -> None:
+    """One top-N request of `kind` through the entry point its arguments need.  "playlist" and "distance": with `candidates` (a
+    sequence of global ids) `prefix`query_`kind`_request_candidates, else with `rowset` = (pointer, mode) ..._request_ext, else with
+    `scales` (checked: make_scales) ..._request_scaled, else ..._request.  "anyof" and "manhattan" have the one entry point
+    `prefix`query_`kind`_request, which takes the ext (NULL without a row set) and no scales or list."""
+    entry = f"{prefix}query_{kind}_request"
+    if kind in ("anyof", "manhattan"):
+        ext = _request_ext(None, rowset)
+        check(getattr(lib, entry)(h, ctypes.byref(q), ctypes.byref(ext) if rowset is not None else None, ctypes.byref(res)))
+    elif candidates is not None:
+        cand = _np_ids(candidates)
+        ext = _request_ext(scales, rowset)
+        check(getattr(lib, entry + "_candidates")(h, ctypes.byref(q), ctypes.byref(ext), _ptr(cand) if cand.size else None, int(cand.size),
+                                                  ctypes.byref(res)))
+    elif rowset is not None:
+        ext = _request_ext(scales, rowset)
+        check(getattr(lib, entry + "_ext")(h, ctypes.byref(q), ctypes.byref(ext), ctypes.byref(res)))
+    elif scales is not None:
+        check(getattr(lib, entry + "_scaled")(h, ctypes.byref(q), _ptr(scales), ctypes.byref(res)))
+    else:
+        check(getattr(lib, entry)(h, ctypes.byref(q), ctypes.byref(res)))
+
+
 _PLAYLIST_LEVELS = ("", "_where", "_weighted", "_diverse", "_capped")   # each level's entry point takes the previous one's arguments and its own
 
 
@@ -140,70 +185,45 @@ def _playlist_family(lib, prefix: str, h, check, members, topn: int, exclude=Non
         w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
         if w.size != k:
             raise ValueError(f"{w.size} weights for {k} songs: one weight per song")
-    flt = make_filter(where) if where is not None else None
-    ex = np.ascontiguousarray(np.asarray([] if exclude is None else list(exclude), dtype=np.int64).reshape(-1))
     n_out = max(int(topn), 1)
     idx = np.empty(n_out, dtype=np.int64)
     score = np.empty(n_out, dtype=np.float32)
     mmr = np.zeros(n_out, dtype=np.float32)
     count, pool_rows = ctypes.c_int(0), ctypes.c_int(0)
-
-    def ptr(a):
-        return a.ctypes.data_as(ctypes.c_void_p)
-
-    args = [h, ptr(members)]
-    if rank >= 2:
-        args.append(ptr(w) if w is not None else None)
-    args += [k, ptr(ex) if ex.size else None, int(ex.size)]
-    if rank >= 1:
-        args.append(ctypes.byref(flt) if flt is not None else None)
-    if diverse:
-        args += [ctypes.c_float(float(lam)), int(pool)]
-    if capped:
-        args.append(int(max_per_group))
-    args += [int(topn), ptr(idx), ptr(score)]
-    if diverse:
-        args.append(ptr(mmr))
-    args.append(ctypes.byref(count))
-    if capped:
-        args.append(ctypes.byref(pool_rows))
-    by = "playlist" if members.dtype == np.int64 else "mean"
-    a = make_scales(scales) if scales is not None else None
-    if labels is not None or prior_weight is not None or a is not None or rowset is not None or candidates is not None:
+    if labels is not None or prior_weight is not None or scales is not None or rowset is not None or candidates is not None:
         q = capi.PlaylistQuery()
-        q.size = ctypes.sizeof(capi.PlaylistQuery)
+        keep = _fill_query(q, members, topn, exclude, where, labels)   # noqa: F841  (alive until the call has returned)
         q.flags = (capi.PQ_DIVERSE if diverse else 0) | (capi.PQ_CAPPED if capped else 0)
         if prior_weight is not None:
             q.flags |= capi.PQ_PRIOR
             q.prior_weight = float(prior_weight)
-        q.members, q.rows = (None, ptr(members)) if by == "playlist" else (ptr(members), None)
-        q.weights = ptr(w) if w is not None else None
-        q.exclude_global, q.n_exclude = (ptr(ex) if ex.size else None), int(ex.size)
-        q.filter = ctypes.pointer(flt) if flt is not None else None
-        if labels is not None:
-            lab = _np_labels(labels)
-            q.labels, q.n_labels = ptr(lab), int(lab.size)   # (an empty set stays a non-NULL pointer: the library refuses it)
-        q.k, q.topn = k, int(topn)
+        q.weights = _ptr(w) if w is not None else None
         if diverse:
             q.lambda_, q.pool = float(lam), int(pool)
         if capped:
             q.max_per_group = int(max_per_group)
-        res = capi.PlaylistResult(ptr(idx), ptr(score), ptr(mmr) if diverse else None, ctypes.pointer(count),
-                                  ctypes.pointer(pool_rows))
-        if candidates is not None:
-            cand = _np_ids(candidates)
-            ext = _request_ext(a, rowset)
-            check(getattr(lib, f"{prefix}query_playlist_request_candidates")(
-                h, ctypes.byref(q), ctypes.byref(ext), ptr(cand) if cand.size else None, int(cand.size), ctypes.byref(res)))
-        elif rowset is not None:
-            ext = _request_ext(a, rowset)
-            check(getattr(lib, f"{prefix}query_playlist_request_ext")(h, ctypes.byref(q), ctypes.byref(ext), ctypes.byref(res)))
-        elif a is not None:
-            check(getattr(lib, f"{prefix}query_playlist_request_scaled")(h, ctypes.byref(q), ptr(a), ctypes.byref(res)))
-        else:
-            check(getattr(lib, f"{prefix}query_playlist_request")(h, ctypes.byref(q), ctypes.byref(res)))
+        res = capi.PlaylistResult(_ptr(idx), _ptr(score), _ptr(mmr) if diverse else None, ctypes.pointer(count), ctypes.pointer(pool_rows))
+        _call_request(lib, prefix, h, check, "playlist", q, res, make_scales(scales) if scales is not None else None, rowset, candidates)
     else:
-        check(getattr(lib, f"{prefix}query_{by}_topn{level}")(*args))
+        flt = make_filter(where) if where is not None else None
+        ex = np.ascontiguousarray(np.asarray([] if exclude is None else list(exclude), dtype=np.int64).reshape(-1))
+        args = [h, _ptr(members)]
+        if rank >= 2:
+            args.append(_ptr(w) if w is not None else None)
+        args += [k, _ptr(ex) if ex.size else None, int(ex.size)]
+        if rank >= 1:
+            args.append(ctypes.byref(flt) if flt is not None else None)
+        if diverse:
+            args += [ctypes.c_float(float(lam)), int(pool)]
+        if capped:
+            args.append(int(max_per_group))
+        args += [int(topn), _ptr(idx), _ptr(score)]
+        if diverse:
+            args.append(_ptr(mmr))
+        args.append(ctypes.byref(count))
+        if capped:
+            args.append(ctypes.byref(pool_rows))
+        check(getattr(lib, f"{prefix}query_{'playlist' if members.dtype == np.int64 else 'mean'}_topn{level}")(*args))
     out = (idx[:count.value].copy(), score[:count.value].copy())
     if return_mmr:
         out += (mmr[:count.value].copy(),)
@@ -216,7 +236,7 @@ def _request_ext(scales, rowset):
     """capi.RequestExt from checked scales (a float32 array or None) and rowset = (pointer, mode) or None.  (The arrays it points to
     are the caller's: they outlive the call.)"""
     return capi.RequestExt(ctypes.sizeof(capi.RequestExt), int(rowset[1]) if rowset is not None else 0,
-                           scales.ctypes.data_as(ctypes.c_void_p) if scales is not None else None,
+                           _ptr(scales) if scales is not None else None,
                            rowset[0] if rowset is not None else None)
 
 
@@ -228,41 +248,14 @@ def _distance_request(lib, prefix: str, h, check, members, topn: int, exclude=No
     root-mean-square distance to the members.  `scales` (make_scales): FEATURE SCALES, through `prefix`query_distance_request_scaled.
     `rowset` = (pointer, mode): ROW SETS, through `prefix`query_distance_request_ext.  `candidates`: CANDIDATE LISTS, a sequence of
     global ids, through `prefix`query_distance_request_candidates."""
-    flt = make_filter(where) if where is not None else None
-    ex = np.ascontiguousarray(np.asarray([] if exclude is None else list(exclude), dtype=np.int64).reshape(-1))
     n_out = max(int(topn), 1)
     idx = np.empty(n_out, dtype=np.int64)
     dist = np.empty(n_out, dtype=np.float32)
     count = ctypes.c_int(0)
-
-    def ptr(a):
-        return a.ctypes.data_as(ctypes.c_void_p)
-
     q = capi.DistanceQuery()
-    q.size = ctypes.sizeof(capi.DistanceQuery)
-    q.members, q.rows = (None, ptr(members)) if members.dtype == np.int64 else (ptr(members), None)
-    q.exclude_global, q.n_exclude = (ptr(ex) if ex.size else None), int(ex.size)
-    q.filter = ctypes.pointer(flt) if flt is not None else None
-    if labels is not None:
-        lab = _np_labels(labels)
-        q.labels, q.n_labels = ptr(lab), int(lab.size)   # (an empty set stays a non-NULL pointer: the library refuses it)
-    q.k, q.topn = int(members.shape[0]), int(topn)
-    res = capi.DistanceResult(ptr(idx), ptr(dist), ctypes.pointer(count))
-    if candidates is not None:
-        a = make_scales(scales) if scales is not None else None
-        cand = _np_ids(candidates)
-        ext = _request_ext(a, rowset)
-        check(getattr(lib, f"{prefix}query_distance_request_candidates")(
-            h, ctypes.byref(q), ctypes.byref(ext), ptr(cand) if cand.size else None, int(cand.size), ctypes.byref(res)))
-    elif rowset is not None:
-        a = make_scales(scales) if scales is not None else None
-        ext = _request_ext(a, rowset)
-        check(getattr(lib, f"{prefix}query_distance_request_ext")(h, ctypes.byref(q), ctypes.byref(ext), ctypes.byref(res)))
-    elif scales is not None:
-        a = make_scales(scales)
-        check(getattr(lib, f"{prefix}query_distance_request_scaled")(h, ctypes.byref(q), ptr(a), ctypes.byref(res)))
-    else:
-        check(getattr(lib, f"{prefix}query_distance_request")(h, ctypes.byref(q), ctypes.byref(res)))
+    keep = _fill_query(q, members, topn, exclude, where, labels)   # noqa: F841  (alive until the call has returned)
+    res = capi.DistanceResult(_ptr(idx), _ptr(dist), ctypes.pointer(count))
+    _call_request(lib, prefix, h, check, "distance", q, res, make_scales(scales) if scales is not None else None, rowset, candidates)
     return idx[:count.value].copy(), dist[:count.value].copy()
 
 
@@ -520,26 +513,13 @@ def candidate_scores(eng, candidates, *, queries=None, rows=None, metric="cosine
     cand = _np_ids(candidates)
     values = np.empty(cand.size, dtype=np.float32)
     flags = np.empty(cand.size, dtype=np.uint8)
-
-    def ptr(a):
-        return a.ctypes.data_as(ctypes.c_void_p)
-
-    flt = make_filter(where) if where is not None else None
-    ex = np.ascontiguousarray(np.asarray([] if exclude is None else list(exclude), dtype=np.int64).reshape(-1))
     q = capi.DistanceQuery() if dist else capi.PlaylistQuery()
-    q.size = ctypes.sizeof(type(q))
-    q.members, q.rows = (None, ptr(members)) if members.dtype == np.int64 else (ptr(members), None)
-    q.exclude_global, q.n_exclude = (ptr(ex) if ex.size else None), int(ex.size)
-    q.filter = ctypes.pointer(flt) if flt is not None else None
-    if labels is not None:
-        lab = _np_labels(labels)
-        q.labels, q.n_labels = ptr(lab), int(lab.size)
-    q.k, q.topn = k, 1   # (topn is checked and otherwise unused)
+    keep = _fill_query(q, members, 1, exclude, where, labels)   # noqa: F841  (topn is checked and otherwise unused)
     if weights is not None:
         w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
         if w.size != k:
             raise ValueError(f"{w.size} weights for {k} songs: one weight per song")
-        q.weights = ptr(w)
+        q.weights = _ptr(w)
     if prior_weight is not None:
         q.flags |= capi.PQ_PRIOR
         q.prior_weight = float(prior_weight)
@@ -548,8 +528,8 @@ def candidate_scores(eng, candidates, *, queries=None, rows=None, metric="cosine
 
     def call(rowset):
         ext = _request_ext(a, rowset)
-        eng._check(entry(eng._h, ctypes.byref(q), ctypes.byref(ext), ptr(cand) if cand.size else None, int(cand.size),
-                         ptr(values) if cand.size else None, ptr(flags) if cand.size else None))
+        eng._check(entry(eng._h, ctypes.byref(q), ctypes.byref(ext), _ptr(cand) if cand.size else None, int(cand.size),
+                         _ptr(values) if cand.size else None, _ptr(flags) if cand.size else None))
 
     eng._with_set(seen, only, call)
     return values, flags.astype(bool)
@@ -571,29 +551,10 @@ def query_anyof(eng, topn, members=None, rows=None, exclude=None, where=None, la
     score = np.empty(n_out, dtype=np.float32)
     member = np.empty(n_out, dtype=np.int32)
     count = ctypes.c_int(0)
-
-    def ptr(a):
-        return a.ctypes.data_as(ctypes.c_void_p)
-
-    flt = make_filter(where) if where is not None else None
-    ex = np.ascontiguousarray(np.asarray([] if exclude is None else list(exclude), dtype=np.int64).reshape(-1))
     q = capi.AnyOfQuery()
-    q.size = ctypes.sizeof(capi.AnyOfQuery)
-    q.members, q.rows = (None, ptr(m)) if m.dtype == np.int64 else (ptr(m), None)
-    q.exclude_global, q.n_exclude = (ptr(ex) if ex.size else None), int(ex.size)
-    q.filter = ctypes.pointer(flt) if flt is not None else None
-    if labels is not None:
-        lab = _np_labels(labels)
-        q.labels, q.n_labels = ptr(lab), int(lab.size)   # (an empty set stays a non-NULL pointer: the library refuses it)
-    q.k, q.topn = int(m.shape[0]), int(topn)
-    res = capi.AnyOfResult(ptr(idx), ptr(score), ptr(member), ctypes.pointer(count))
-    entry = getattr(eng._lib, f"{eng._prefix}query_anyof_request")
-
-    def call(rowset):
-        ext = _request_ext(None, rowset)
-        eng._check(entry(eng._h, ctypes.byref(q), ctypes.byref(ext) if rowset is not None else None, ctypes.byref(res)))
-
-    eng._with_set(seen, only, call)
+    keep = _fill_query(q, m, topn, exclude, where, labels)   # noqa: F841  (alive until the call has returned)
+    res = capi.AnyOfResult(_ptr(idx), _ptr(score), _ptr(member), ctypes.pointer(count))
+    eng._with_set(seen, only, lambda rowset: _call_request(eng._lib, eng._prefix, eng._h, eng._check, "anyof", q, res, rowset=rowset))
     c = count.value
     return idx[:c].copy(), score[:c].copy(), member[:c].copy()
 
@@ -612,29 +573,10 @@ def query_manhattan(eng, topn, members=None, rows=None, exclude=None, where=None
     idx = np.empty(n_out, dtype=np.int64)
     dist = np.empty(n_out, dtype=np.float32)
     count = ctypes.c_int(0)
-
-    def ptr(a):
-        return a.ctypes.data_as(ctypes.c_void_p)
-
-    flt = make_filter(where) if where is not None else None
-    ex = np.ascontiguousarray(np.asarray([] if exclude is None else list(exclude), dtype=np.int64).reshape(-1))
     q = capi.ManhattanQuery()
-    q.size = ctypes.sizeof(capi.ManhattanQuery)
-    q.members, q.rows = (None, ptr(m)) if m.dtype == np.int64 else (ptr(m), None)
-    q.exclude_global, q.n_exclude = (ptr(ex) if ex.size else None), int(ex.size)
-    q.filter = ctypes.pointer(flt) if flt is not None else None
-    if labels is not None:
-        lab = _np_labels(labels)
-        q.labels, q.n_labels = ptr(lab), int(lab.size)   # (an empty set stays a non-NULL pointer: the library refuses it)
-    q.k, q.topn = int(m.shape[0]), int(topn)
-    res = capi.ManhattanResult(ptr(idx), ptr(dist), ctypes.pointer(count))
-    entry = getattr(eng._lib, f"{eng._prefix}query_manhattan_request")
-
-    def call(rowset):
-        ext = _request_ext(None, rowset)
-        eng._check(entry(eng._h, ctypes.byref(q), ctypes.byref(ext) if rowset is not None else None, ctypes.byref(res)))
-
-    eng._with_set(seen, only, call)
+    keep = _fill_query(q, m, topn, exclude, where, labels)   # noqa: F841  (alive until the call has returned)
+    res = capi.ManhattanResult(_ptr(idx), _ptr(dist), ctypes.pointer(count))
+    eng._with_set(seen, only, lambda rowset: _call_request(eng._lib, eng._prefix, eng._h, eng._check, "manhattan", q, res, rowset=rowset))
     c = count.value
     return idx[:c].copy(), dist[:c].copy()
 
