@@ -179,7 +179,10 @@ int mi355rec_enqueue_query_keys(mi355rec_t* h, const float* query12,
  * MI355REC_PAIRING_AUTO_MIN_ROWS rows and more), two consecutive streamed queries over the 8-bit replica that
  * ask for the same topn <= 128 are served by ONE launch that scores every row against both, and the stream
  * runs up to THREE calls behind instead of one: call 2k + 1 completes pair k and launches pair k - 1, whose
- * launch merges pair k - 2.  The contract is the one above, stated without a call count: the keys of streamed
+ * launch merges pair k - 2.  Where the handle forms GROUPS of two pairs (MI355REC_PAIRING_GROUPS, or AUTO from
+ * MI355REC_GROUPS_AUTO_MIN_ROWS rows; include/mi355rec_diag.h) the stream runs up to SEVEN calls behind for
+ * queries by row and by value; a query by pointer (mi355rec_enqueue_ptr_keys_streamed) still has its memory
+ * read at most three calls after its own.  The contract is the one above, stated without a call count: the keys of streamed
  * queries are written in CALL ORDER (a buffer given to two queries ends with the later one's keys), and
  * everything enqueued is written once the work of mi355rec_enqueue_flush on the stream has completed.  A
  * streamed launch may thus serve two queued queries; each of them is still one full pass' worth of scores. */

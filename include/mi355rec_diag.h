@@ -91,8 +91,10 @@ typedef struct {
     int64_t route_mfma_two_pass; /* chunks (<= 1024 queries) of the two-pass batched matrix-core path              */
     int64_t route_exact_queue;   /* queries that path handed to the exact scan on the device (reading it synchronises) */
     int32_t device_bytes_per_row; /* what the handle keeps resident per row: 48 (fp32) + 24 (fp16 replica) + 12 (8-bit) */
-    int64_t stream_pair_launches; /* streamed launches that served TWO queued queries in one pass over the 8-bit replica
-                                     (mi355rec_set_stream_pairing); each of them still counts twice in route_q8 */
+    int64_t stream_pair_launches; /* PAIRS of queued queries served by one pass over the 8-bit replica
+                                     (mi355rec_set_stream_pairing); each pair still counts twice in route_q8, and a launch that
+                                     served two pairs (below) adds 2 here */
+    int64_t stream_group_launches; /* streamed launches that served TWO pairs (MI355REC_PAIRING_GROUPS) */
 } mi355rec_stats_t;
 
 /* What this build of the library was compiled with.  The product build returns 0.  The tools/ scripts build
@@ -194,14 +196,31 @@ int mi355rec_set_sample(mi355rec_t* h, int mode);
  * flush, another topn, a change of mi355rec_set_replica / _set_sample or a non-streamed call in between) takes the
  * one-query launch.  The two sample launches of the first pair of a stream take the sample a carried query would take under
  * mi355rec_set_sample(AUTO) (they are two calls ahead of the pair's launch, not on its critical path).
- *   AUTO (default): pairs on shards of at least MI355REC_PAIRING_AUTO_MIN_ROWS rows;
+ *   AUTO (default): pairs on shards of at least MI355REC_PAIRING_AUTO_MIN_ROWS rows, groups (below) on shards of at least
+ *                   MI355REC_GROUPS_AUTO_MIN_ROWS rows — there the first two pairs of a stream still go as pairs, and groups form
+ *                   once a launch of the stream is under way (a short stream gains nothing from waiting for four queries);
  *   OFF:            never;
- *   ON:             wherever the two queries qualify.
- * The mode belongs to the handle; a lane inherits its parent's when it is created.  The shards of a node handle do not pair. */
+ *   ON:             pairs wherever the two queries qualify, never groups;
+ *   GROUPS:         groups wherever four queries qualify, pairs otherwise.
+ * The mode belongs to the handle; a lane inherits its parent's when it is created.  The shards of a node handle do not pair.
+ *
+ * GROUPS.  Two consecutive complete pairs with the same topn, replica mode and sample mode form a GROUP, and one launch
+ * serves both pairs (scan_q8_kernel_pair, pairs == 2): every tile is scanned by two workgroups, one per pair, placed so that
+ * on this hardware they share an XCD and run at nearly the same time — the tile one of them fetches from the Infinity Cache
+ * the other finds in that XCD's L2.  Nothing but speed depends on the placement: no workgroup waits for another, and every
+ * key is what the pair launch (and the one-query launch) computes, bit for bit.  The stream then runs up to SEVEN calls
+ * behind for queries by row and by value: a waiting group of four and three queries of the group after it.  A query by
+ * POINTER never waits longer than under pairs: it may complete a pair but closes its group, and while one waits for its
+ * launch the group after it closes at one pair — its memory is read at most three calls later, as before.  A group with one
+ * pair is the pair launch; a lone query is the one-query launch. */
 #define MI355REC_PAIRING_AUTO 0
 #define MI355REC_PAIRING_OFF 1
 #define MI355REC_PAIRING_ON 2
+#define MI355REC_PAIRING_GROUPS 3
 #define MI355REC_PAIRING_AUTO_MIN_ROWS 2500000
+/* From how many rows AUTO forms groups: the smallest measured size from which groups were not slower than pairs at top-10 and
+ * top-100, for that size and every larger one measured (docs/LAB_NOTES.md, "two pairs per launch"): the smallest size measured. */
+#define MI355REC_GROUPS_AUTO_MIN_ROWS 2500000
 int mi355rec_set_stream_pairing(mi355rec_t* h, int mode);
 typedef struct {
     int64_t base_rows;        /* rows of the base (0: the handle has no bucketed sample)                          */
@@ -258,6 +277,8 @@ int mi355rec_enqueue_ptr_keys(mi355rec_t* h, const float* query12_dev, int64_t e
                               void* stream);
 int mi355rec_enqueue_ptr_keys_streamed(mi355rec_t* h, const float* query12_dev, int64_t exclude_global,
                                        int topn, mi355rec_key_t* out_keys_dev, void* stream);
+/* (The streamed form reads query12_dev when its launches run: by the work enqueued up to three streamed calls after this
+ * one, or by the flush — under pairs and under groups alike.  The memory must stay as it is until that work has completed.) */
 
 /* A batch whose queries are vectors (queries[i*12 ..], host) and / or POINTERS to 12 floats in
  * device-readable memory (query_ptrs_dev[i] != NULL wins; either array may be NULL when the other

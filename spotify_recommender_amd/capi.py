@@ -22,8 +22,9 @@ BATCH_AUTO, BATCH_MULTI, BATCH_MFMA, BATCH_HALF, BATCH_Q8, BATCH_MFMA_NOSKIP = 0
 REPLICA_AUTO, REPLICA_OFF, REPLICA_ON, REPLICA_FP16 = 0, 1, 2, 3
 SAMPLE_AUTO, SAMPLE_STRIDED, SAMPLE_BUCKETED = 0, 1, 2   # mi355rec_set_sample
 SAMPLE_AUTO_MIN_ROWS = 6_000_000
-PAIRING_AUTO, PAIRING_OFF, PAIRING_ON = 0, 1, 2   # mi355rec_set_stream_pairing
+PAIRING_AUTO, PAIRING_OFF, PAIRING_ON, PAIRING_GROUPS = 0, 1, 2, 3   # mi355rec_set_stream_pairing
 PAIRING_AUTO_MIN_ROWS = 2_500_000
+GROUPS_AUTO_MIN_ROWS = 2_500_000
 TRANSPORT_PEER, TRANSPORT_RCCL = 1, 2
 PLACEMENT_AUTO, PLACEMENT_SHARDED, PLACEMENT_REPLICATED, PLACEMENT_CPU = 0, 1, 2, 3
 CREATE_NO_REPLICA = 1
@@ -157,6 +158,7 @@ class Stats(ctypes.Structure):
         ("route_exact_queue", c_int64),
         ("device_bytes_per_row", c_int32),
         ("stream_pair_launches", c_int64),
+        ("stream_group_launches", c_int64),
     ]
 
 

@@ -2,7 +2,8 @@
 // launch in front of a query alone, the scan + merge (replaces calculateSimilarities + the host heap, Recommender.cu:184-254,
 // 293-315), rounds for topn > 1024, the completion word of a synchronous query, and the STREAM of single queries that runs
 // one call behind so that every launch carries the next query's seed riders — or, where two queued queries share one pass
-// over the 8-bit replica ("pairs"), up to three.  (Part of mi355rec.hip's translation unit.)
+// over the 8-bit replica ("pairs"), up to three, and up to seven where two pairs share one launch ("groups").  (Part of
+// mi355rec.hip's translation unit.)
 #pragma once
 
 #include "engine_state.hip.h"
@@ -560,17 +561,29 @@ int enqueue_streamed_single(mi355rec* h, const float* qptr, const float* query12
 // finds no partner — the odd tail at a flush, a change of topn, of the rows single queries stream, of mi355rec_set_replica
 // or mi355rec_set_sample between the two calls, a handle that does not pair — goes through the one-query path above,
 // unchanged.  The two paths are never open at once: whichever a query takes closes the other first, so keys are always
-// written in call order.  All per-QUERY books stay per query; a pair launch counts once in stream_pair_launches.
+// written in call order.  All per-QUERY books stay per query; a pair launch counts once in stream_pair_launches (a launch
+// that serves two pairs twice, and once in stream_group_launches).
+//
+// GROUPS.  Where the handle forms groups (MI355REC_PAIRING_GROUPS; AUTO from MI355REC_GROUPS_AUTO_MIN_ROWS rows), every stage
+// below holds up to TWO pairs and one launch serves both (scan_q8_kernel_pair, pairs == 2: twin workgroups, one per pair, read
+// every tile at nearly the same time on one XCD).  The group that forms closes at four queries — or at two where a query by
+// POINTER is among them or among the queries that wait for their launch (its memory is read at most three calls after its
+// call, as under pairs), and at whatever complete pairs it holds when the stream drains.  The stream then runs up to SEVEN
+// calls behind.  A group of one pair is the pair launch, bit for bit and launch for launch.
 bool pairing_on(const mi355rec* h) {
-    if (h->pairing == MI355REC_PAIRING_ON) return true;
+    if (h->pairing == MI355REC_PAIRING_ON || h->pairing == MI355REC_PAIRING_GROUPS) return true;
     if (h->pairing == MI355REC_PAIRING_OFF) return false;
     return h->n >= MI355REC_PAIRING_AUTO_MIN_ROWS;
 }
-bool pairs_open(const mi355rec* h) { return h->pairs.waiting || h->pairs.has_first || h->pairs.pending; }
+bool groups_on(const mi355rec* h) {
+    if (h->pairing == MI355REC_PAIRING_GROUPS) return true;
+    return h->pairing == MI355REC_PAIRING_AUTO && h->n >= MI355REC_GROUPS_AUTO_MIN_ROWS;
+}
+bool pairs_open(const mi355rec* h) { return h->pairs.n_wait > 0 || h->pairs.n_form > 0 || h->pairs.n_pending > 0; }
 
 void free_pairs(mi355rec* h) {
     auto& P = h->pairs;
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < 8; ++i) {
         if (P.lists[i]) (void)hipFree(P.lists[i]);
         if (P.seed[i]) (void)hipFree(P.seed[i]);
         P.lists[i] = nullptr;
@@ -584,13 +597,13 @@ void free_pairs(mi355rec* h) {
 int ensure_pairs_alloc(mi355rec* h) {
     auto& P = h->pairs;
     const size_t words = static_cast<size_t>(h->geom[kQ8].grid > 0 ? h->geom[kQ8].grid : 1) * kPairMaxTopk;
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < 8; ++i) {
         HIP_TRY(h, hipMalloc(&P.lists[i], sizeof(uint64_t) * words));
         HIP_TRY(h, hipMalloc(&P.seed[i], sizeof(unsigned long long) * kSampleSlots));
         HIP_TRY(h, hipMemset(P.seed[i], 0, sizeof(unsigned long long) * kSampleSlots));
     }
-    HIP_TRY(h, hipMalloc(&P.ctl, sizeof(SeedCtl) * 4));
-    HIP_TRY(h, hipMemset(P.ctl, 0, sizeof(SeedCtl) * 4));
+    HIP_TRY(h, hipMalloc(&P.ctl, sizeof(SeedCtl) * 8));
+    HIP_TRY(h, hipMemset(P.ctl, 0, sizeof(SeedCtl) * 8));
     return MI355REC_OK;
 }
 int ensure_pairs(mi355rec* h) {
@@ -605,103 +618,168 @@ int ensure_pairs(mi355rec* h) {
     return MI355REC_OK;
 }
 
-// The mergers of the pair launched last, in launches of their own and in call order.
+// The mergers of the pairs launched last, in launches of their own and in call order.
 int merge_pair_pending(mi355rec* h, hipStream_t s) {
     auto& P = h->pairs;
-    P.pending = false;
-    for (int x = 0; x < 2; ++x) {
-        const int rc = enqueue_merge(h, P.lists[2 * P.pending_set + x], P.pending_lists, P.pending_topn, P.pending_topn, P.pending_out[x],
+    const int count = P.n_pending;
+    P.n_pending = 0;
+    for (int x = 0; x < count; ++x) {
+        const int rc = enqueue_merge(h, P.lists[4 * P.pending_set + x], P.pending_lists, P.pending_topn, P.pending_topn, P.pending_out[x],
                                      nullptr, nullptr, s);
         if (rc) return rc;
     }
     return MI355REC_OK;
 }
 
-// Launches the waiting pair: scanners + the two riding mergers of the pair before + (next != null) the seed riders and the
-// neighbourhood workgroups of the two queries of the pair after, where the launch has them (ScanGeom: riders, nbhd, hoists).
-int launch_pair(mi355rec* h, hipStream_t s, const mi355rec::Stashed* next, bool next_bucketed) {
+// Launches the waiting pair, or the waiting group's two pairs: scanners + the riding mergers of the pairs before + (n_next > 0)
+// the seed riders and the neighbourhood workgroups of the n_next queries after, where the launch has them (ScanGeom: riders,
+// nbhd, hoists).  The launch has two slots for mergers and for queries after — four where it scans for two pairs, merges two or
+// carries two; a slot nobody fills costs its few workgroups an early return.
+int launch_pairs(mi355rec* h, hipStream_t s, const mi355rec::Stashed* next, int n_next, bool next_bucketed) {
     auto& P = h->pairs;
-    const mi355rec::Stashed& a = P.wait[0];
-    const mi355rec::Stashed& b = P.wait[1];
-    const int topn = a.topn;
-    // two mergers in one launch write their keys in no particular order: lists that share an output are merged one after the other
-    if (P.pending) {
-        const uint64_t* lo = P.pending_out[0] < P.pending_out[1] ? P.pending_out[0] : P.pending_out[1];
-        const uint64_t* hi = P.pending_out[0] < P.pending_out[1] ? P.pending_out[1] : P.pending_out[0];
-        if (hi < lo + P.pending_topn) {
+    const int n_scan = P.n_wait;   // queries this launch scans for: 2 or 4
+    const int pairs = n_scan / 2;
+    const int topn = P.wait[0].topn;
+    // mergers in one launch write their keys in no particular order: lists that share an output are merged one after the other
+    if (P.n_pending) {
+        bool shared = false;
+        for (int x = 0; x < P.n_pending; ++x)
+            for (int y = x + 1; y < P.n_pending; ++y) {
+                const uint64_t* lo = P.pending_out[x] < P.pending_out[y] ? P.pending_out[x] : P.pending_out[y];
+                const uint64_t* hi = P.pending_out[x] < P.pending_out[y] ? P.pending_out[y] : P.pending_out[x];
+                shared = shared || hi < lo + P.pending_topn;
+            }
+        if (shared) {
             const int rc = merge_pair_pending(h, s);
             if (rc) return rc;
         }
     }
-    const ScanGeom& g = stream_geom(h, kQ8, next != nullptr && next_bucketed);
-    const bool riders = next != nullptr && (g.riders > 0 || g.nbhd);
-    const int extra = 2 + (riders ? 2 * (g.riders + (g.nbhd ? 1 : 0)) : 0);
+    const int side_queries = (pairs == 2 || P.n_pending == 4 || n_next == 4) ? 4 : 2;
+    const ScanGeom& g = stream_geom(h, kQ8, n_next > 0 && next_bucketed);
+    const bool riders = n_next > 0 && (g.riders > 0 || g.nbhd);
+    const int extra = side_queries * (1 + (riders ? g.riders + (g.nbhd ? 1 : 0) : 0));
     const int64_t tiles = (h->n + Q8PairConfig::kTileRows - 1) / Q8PairConfig::kTileRows;
-    int64_t scanners = g.grid - extra;
-    if (scanners > kRideMaxLists - 1) scanners = kRideMaxLists - 1;
-    if (scanners > tiles) scanners = tiles;
-    if (scanners < 1) scanners = 1;
-    const int iters = static_cast<int>((tiles + scanners - 1) / scanners);
-    const int set = P.pending ? 1 - P.pending_set : 0;
+    // every pair gets `slots` scanning workgroups and as many lists per query; twins (one per pair) share a slot's tiles, so two
+    // pairs split what the chip holds at once, not what one pair would launch (a small shard's grid is its tile count)
+    int64_t slots = pairs == 2 ? (g.cap - extra) / 2 : g.grid - extra;
+    if (slots > kRideMaxLists - 1) slots = kRideMaxLists - 1;
+    if (slots > tiles) slots = tiles;
+    if (pairs == 2 && slots >= 8) slots &= ~static_cast<int64_t>(7);   // (scan_q8_kernel_pair: twins lie 8 block ids apart)
+    if (slots < 1) slots = 1;
+    const int64_t scanners = slots * pairs;
+    const int iters = static_cast<int>((tiles + slots - 1) / slots);
+    const int set = P.n_pending ? 1 - P.pending_set : 0;
     Q8PairSide side;
     std::memset(&side, 0, sizeof side);
-    side.prev[0] = side.prev[1] = no_prev_merge();
-    if (P.pending)
-        for (int x = 0; x < 2; ++x) side.prev[x] = PrevMerge{P.lists[2 * P.pending_set + x], P.pending_lists, P.pending_topn, P.pending_out[x]};
-    if (riders)
-        for (int x = 0; x < 2; ++x)
+    side.queries = side_queries;
+    for (int x = 0; x < 4; ++x) side.prev[x] = no_prev_merge();
+    for (int x = 0; x < P.n_pending; ++x)
+        side.prev[x] = PrevMerge{P.lists[4 * P.pending_set + x], P.pending_lists, P.pending_topn, P.pending_out[x]};
+    if (riders) {
+        for (int x = 0; x < n_next; ++x)
             side.next[x] = make_next_seed(h, kQ8, g.riders, g.nbhd, next[x].qptr, next[x].q, next[x].exclude, next[x].topn, next[x].epoch,
                                           P.seed[next[x].seed_buf], g.hoists ? P.ctl + next[x].seed_buf : nullptr,
                                           P.ctl_done[next[x].seed_buf], next_bucketed);
-    Q8PairArg arg[2];
-    const mi355rec::Stashed* const q[2] = {&a, &b};
-    for (int x = 0; x < 2; ++x) {
-        std::memset(&arg[x], 0, sizeof arg[x]);
-        arg[x].qarg = make_query_arg(h, q[x]->qptr, q[x]->q);
-        arg[x].query_ptr = q[x]->qptr;
-        arg[x].exclude_global = q[x]->exclude;
-        arg[x].block_lists = P.lists[2 * set + x];
-        arg[x].seed_vals = P.seed[q[x]->seed_buf];
-        arg[x].cutoff_ready = q[x]->cutoff_ready ? &P.ctl[q[x]->seed_buf].cutoff : nullptr;
-        arg[x].n_seed = q8_seed_count(h, q[x]->bucketed);   // (negative: exact values)
-        arg[x].epoch = q[x]->epoch;
+        // (the kernel reads the riders' geometry from slot 0, and an unfilled slot by its null `out`)
+        for (int x = n_next; x < side_queries; ++x) {
+            side.next[x].n_wgs = side.next[0].n_wgs;
+            side.next[x].nbhd = side.next[0].nbhd;
+        }
     }
-    const dim3 grid(static_cast<unsigned>(scanners + 2 + 2 * (side.next[0].n_wgs + side.next[0].nbhd)));
+    Q8PairArgs args;
+    std::memset(&args, 0, sizeof args);
+    for (int x = 0; x < n_scan; ++x) {
+        const mi355rec::Stashed& q = P.wait[x];
+        Q8PairArg& a = args.q[x];
+        a.qarg = make_query_arg(h, q.qptr, q.q);
+        a.query_ptr = q.qptr;
+        a.exclude_global = q.exclude;
+        a.block_lists = P.lists[4 * set + x];
+        a.seed_vals = P.seed[q.seed_buf];
+        a.cutoff_ready = q.cutoff_ready ? &P.ctl[q.seed_buf].cutoff : nullptr;
+        a.n_seed = q8_seed_count(h, q.bucketed);   // (negative: exact values)
+        a.epoch = q.epoch;
+    }
+    const dim3 grid(static_cast<unsigned>(scanners + side_queries * (1 + side.next[0].n_wgs + side.next[0].nbhd)));
     LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, scan_q8_kernel_pair<Q8PairConfig>, grid, dim3(Q8PairConfig::kBlock), s,
-                 h->d_feats, h->d_q8, h->n, iters, h->row_base, arg[0], arg[1], topn, h->d_half_rescored, side);
+                 h->d_feats, h->d_q8, h->n, iters, h->row_base, args, pairs, topn, h->d_half_rescored, side);
     HIP_TRY(h, hipGetLastError());
     // (the books move only once the launch is known to have been accepted: per QUERY, as on the one-query path)
-    h->half_scans += 2;
-    h->q8_scans += 2;
-    h->routes.q8 += 2;
-    ++h->stream_pair_launches;
-    for (int x = 0; x < 2; ++x)
+    h->half_scans += n_scan;
+    h->q8_scans += n_scan;
+    h->routes.q8 += n_scan;
+    h->stream_pair_launches += pairs;
+    if (pairs == 2) ++h->stream_group_launches;
+    for (int x = 0; x < n_next; ++x)
         if (side.next[x].ctl) P.ctl_done[next[x].seed_buf] += static_cast<unsigned>(side.next[x].n_wgs);
-    P.pending = true;
+    P.n_pending = n_scan;
     P.pending_set = set;
-    P.pending_lists = static_cast<int>(scanners);
+    P.pending_lists = static_cast<int>(slots);
     P.pending_topn = topn;
-    P.pending_out[0] = a.out;
-    P.pending_out[1] = b.out;
-    P.waiting = false;
+    for (int x = 0; x < n_scan; ++x) P.pending_out[x] = P.wait[x].out;
+    P.n_wait = 0;
     return MI355REC_OK;
 }
 
-// Everything the pairs still hold, in call order: the waiting pair, the mergers, and the first query of an unfinished
-// pair — which found no partner and takes the one-query path (left open: the caller flushes it or streams on).
-int drain_pairs(mi355rec* h, hipStream_t s) {
+// The first `count` (2 or 4) queries of the group that forms become the waiting stage: the pairs that waited are launched now,
+// and their launch takes the samples and the neighbourhoods of these.  The first pairs of a stream, and a shard too small to
+// spare riders, get sample launches of their own.  (Which sample: what use_bucket gives a CARRIED query — also for the first
+// pairs of a stream.  Their sample launches are not on the critical path as a query alone's is: the launch is calls away.)
+int close_forming(mi355rec* h, hipStream_t s, int count) {
     auto& P = h->pairs;
-    if (P.waiting) {
-        const int rc = launch_pair(h, s, nullptr, false);
+    const int topn = P.form[0].topn;
+    const int set = P.n_wait ? 1 - (P.wait[0].seed_buf >> 2) : 0;
+    const bool bucketed = use_bucket(h, kQ8, topn, h->geom_bucket.riders > 0);
+    const ScanGeom& ng = stream_geom(h, kQ8, bucketed);   // of the launch that carries THESE queries' samples
+    mi355rec::Stashed nx[4];
+    for (int i = 0; i < count; ++i) {
+        nx[i] = P.form[i];
+        nx[i].seed_buf = 4 * set + i;
+        nx[i].epoch = next_epoch(h);
+        nx[i].bucketed = bucketed;
+    }
+    h->last_sample = bucketed ? MI355REC_SAMPLE_BUCKETED : MI355REC_SAMPLE_STRIDED;
+    bool sampled = false;
+    if (P.n_wait) {
+        sampled = ng.riders > 0;
+        const int rc = launch_pairs(h, s, nx, count, bucketed);
         if (rc) return rc;
     }
-    if (P.pending) {
+    if (!sampled) {
+        for (int i = 0; i < count; ++i)
+            enqueue_half_seed(h, kQ8, nx[i].qptr, nx[i].q, nx[i].exclude, topn, P.seed[nx[i].seed_buf], nx[i].epoch, s, bucketed);
+        HIP_TRY(h, hipGetLastError());
+    }
+    for (int i = 0; i < count; ++i) {
+        nx[i].cutoff_ready = sampled && ng.hoists;
+        P.wait[i] = nx[i];
+    }
+    P.n_wait = count;
+    for (int i = count; i < P.n_form; ++i) P.form[i - count] = P.form[i];
+    P.n_form -= count;
+    return MI355REC_OK;
+}
+
+// Everything the pairs still hold, in call order: the complete pair among the queries of the group that forms (it closes
+// here), the waiting pairs, the mergers, and the one query left without a partner — which takes the one-query path (left
+// open: the caller flushes it or streams on).
+int drain_pairs(mi355rec* h, hipStream_t s) {
+    auto& P = h->pairs;
+    if (P.n_form >= 2) {
+        const int rc = close_forming(h, s, 2);
+        if (rc) return rc;
+    }
+    if (P.n_wait) {
+        const int rc = launch_pairs(h, s, nullptr, 0, false);
+        if (rc) return rc;
+    }
+    if (P.n_pending) {
         const int rc = merge_pair_pending(h, s);
         if (rc) return rc;
     }
-    if (P.has_first) {
-        const mi355rec::Stashed f = P.first;
-        P.has_first = false;
+    if (P.n_form) {
+        const mi355rec::Stashed f = P.form[0];
+        P.n_form = 0;
         return enqueue_streamed_single(h, f.qptr, f.q, f.exclude, f.topn, f.out, s, h->d_q8 ? f.kind : -1);
     }
     return MI355REC_OK;
@@ -719,8 +797,8 @@ int enqueue_streamed(mi355rec* h, const float* qptr, const float* query12, int64
         (void)hipGetLastError();
         pair = false;
     }
-    // a first query whose partner this one cannot be finds none
-    if (pair && P.has_first && (P.first.topn != topn || P.first_replica_mode != h->replica_mode || P.first_sample_mode != h->sample_mode)) {
+    // queries whose partner this one cannot be find none
+    if (pair && P.n_form && (P.form[0].topn != topn || P.first_replica_mode != h->replica_mode || P.first_sample_mode != h->sample_mode)) {
         rc = drain_pairs(h, s);
         if (rc) return rc;
     }
@@ -743,45 +821,32 @@ int enqueue_streamed(mi355rec* h, const float* qptr, const float* query12, int64
     x.topn = topn;
     x.out = out_keys;
     x.kind = kQ8;
-    if (!P.has_first) {   // the first of a pair: it waits for its partner without a sample
-        P.first = x;
-        P.has_first = true;
-        P.first_replica_mode = h->replica_mode;
-        P.first_sample_mode = h->sample_mode;
-        return MI355REC_OK;
-    }
-    // The pair is complete: the pair before it is launched now, and its launch takes the samples and the neighbourhoods of
-    // this one.  The first pair of a stream, and a shard too small to spare riders, get sample launches of their own.
-    // (Which sample: what use_bucket gives a CARRIED query — also for the first pair of a stream.  Its sample launches are
-    // not on the pair's critical path as a query alone's is: the pair is launched two calls from now, or by the flush.)
-    const int set = P.waiting ? 1 - (P.wait[0].seed_buf >> 1) : 0;
-    const bool bucketed = use_bucket(h, kQ8, topn, h->geom_bucket.riders > 0);
-    const ScanGeom& ng = stream_geom(h, kQ8, bucketed);   // of the launch that carries THIS pair's samples
-    mi355rec::Stashed nx[2] = {P.first, x};
-    for (int i = 0; i < 2; ++i) {
-        nx[i].seed_buf = 2 * set + i;
-        nx[i].epoch = next_epoch(h);
-        nx[i].bucketed = bucketed;
-    }
-    h->last_sample = bucketed ? MI355REC_SAMPLE_BUCKETED : MI355REC_SAMPLE_STRIDED;
-    bool sampled = false;
-    if (P.waiting) {
-        sampled = ng.riders > 0;
-        rc = launch_pair(h, s, nx, bucketed);
+    // (a pointer into the handle's own rows is a query by row; any other is the caller's memory, read when the launch runs)
+    x.by_pointer = qptr && !(qptr >= h->d_feats && qptr < h->d_feats + h->n * kDim);
+    if (P.n_form >= 2 && !groups_on(h)) {   // (the handle stopped forming groups while a pair waited for a second one)
+        rc = close_forming(h, s, 2);
         if (rc) return rc;
     }
-    if (!sampled) {
-        for (int i = 0; i < 2; ++i)
-            enqueue_half_seed(h, kQ8, nx[i].qptr, nx[i].q, nx[i].exclude, topn, P.seed[nx[i].seed_buf], nx[i].epoch, s, bucketed);
-        HIP_TRY(h, hipGetLastError());
+    if (!P.n_form) {
+        P.first_replica_mode = h->replica_mode;
+        P.first_sample_mode = h->sample_mode;
     }
-    for (int i = 0; i < 2; ++i) {
-        nx[i].cutoff_ready = sampled && ng.hoists;
-        P.wait[i] = nx[i];
-    }
-    P.waiting = true;
-    P.has_first = false;
-    return MI355REC_OK;
+    P.form[P.n_form++] = x;   // it waits for its partners without a sample
+    if (P.n_form & 1) return MI355REC_OK;
+    // (which sample a complete pair will take is known now, whenever its group closes — close_forming asks the same question,
+    // and a change of mi355rec_set_sample in between drains these queries — so mi355rec_bucket_sample_info answers at the call
+    // that completes a pair, as it does where the handle forms no groups)
+    h->last_sample = use_bucket(h, kQ8, topn, h->geom_bucket.riders > 0) ? MI355REC_SAMPLE_BUCKETED : MI355REC_SAMPLE_STRIDED;
+    // A complete pair.  Does the group close here?  At two pairs — or at one where the handle forms no groups, and where a query
+    // by pointer is in the group or waits for its launch: that launch is then two calls away at the most, as under pairs.
+    bool closes = P.n_form == 4 || !groups_on(h);
+    // AUTO: the head of a stream runs as pairs — the first pair takes its samples at once and the second one launches it, as
+    // where the handle forms no groups — and groups form once a launch of the stream is under way.  (A short stream gained
+    // nothing from groups otherwise: four sample launches and eight calls before its first scan.  GROUPS groups from the start.)
+    if (h->pairing == MI355REC_PAIRING_AUTO && P.n_pending == 0) closes = true;
+    for (int i = 0; i < P.n_form; ++i) closes = closes || P.form[i].by_pointer;
+    for (int i = 0; i < P.n_wait; ++i) closes = closes || P.wait[i].by_pointer;
+    return closes ? close_forming(h, s, P.n_form) : MI355REC_OK;
 }
 
 }  // namespace

@@ -76,6 +76,7 @@ const float* const kNoQueryPtr = nullptr;   // kernel argument of the variants t
 // regions of handoff.hip.h) and neighbourhood workgroup.
 struct ScanGeom {
     int grid = 0, iters = 0;            // plain launch
+    int cap = 0;                        // workgroups the chip holds at once (grid = min(tiles, cap))
     int sgrid = 0, siters = 0;          // streamed launch that carries nothing for the next query (one more workgroup is the merger)
     int seed_grid = 0;                  // sampled regions (0: the shard is too small to be worth a sample) ...
     int64_t seed_stride = 0;            // ... and the rows between their starts
@@ -223,6 +224,7 @@ struct mi355rec {
         int kind = 0;                   // which rows its scan streams — and its sample was taken over: kFp32, kFp16 (experiment builds), kQ8
         bool cutoff_ready = false;      // ... by riders, whose last one left the launch-wide cutoff / bound in d_stream_ctl
         bool bucketed = false;          // 8-bit replica: its sample is the bucketed one (replica_q8.hip.h)
+        bool by_pointer = false;        // pairs: qptr is the caller's memory, not a row of this handle (it closes its group)
     } stashed;
     unsigned long long* d_stream_seed[2] = {nullptr, nullptr};
     SeedCtl* d_stream_ctl = nullptr;    // [2]: rider count and finished cutoff beside each of d_stream_seed (8-bit replica)
@@ -230,23 +232,27 @@ struct mi355rec {
     // topn <= kPairMaxTopk share ONE pass over the replica (scan_q8_kernel_pair).  The stream then holds up to three queries
     // back: the pair that WAITS for its launch (its samples taken or in flight) and the FIRST of the pair after it, which has
     // no sample yet.  The waiting pair is launched when that next pair is complete, or by the flush; its launch carries the
-    // mergers of the pair before and the riders of the pair after.  Buffers come in two sets of two (set p: [2p], [2p + 1]).
-    int pairing = 0;                    // MI355REC_PAIRING_AUTO / _OFF / _ON (mi355rec_set_stream_pairing)
-    int64_t stream_pair_launches = 0;   // pair launches since create
+    // mergers of the pair before and the riders of the pair after.
+    // GROUPS (MI355REC_PAIRING_GROUPS): every stage holds up to TWO pairs, and one launch scans for both (scan_q8_kernel_pair,
+    // pairs == 2).  The stream then holds up to seven queries back: a waiting group of four and three of the group after it.
+    // Buffers come in two sets of four (set p: [4p] .. [4p + 3]); a stage with one pair uses the first two of its set.
+    int pairing = 0;                    // MI355REC_PAIRING_AUTO / _OFF / _ON / _GROUPS (mi355rec_set_stream_pairing)
+    int64_t stream_pair_launches = 0;   // pairs launched since create (a group launch counts two)
+    int64_t stream_group_launches = 0;  // of those launches, the ones that served two pairs
     struct Pairs {
         bool ready = false;             // the buffers below exist
-        uint64_t* lists[4] = {nullptr, nullptr, nullptr, nullptr};             // sgrid x kPairMaxTopk keys each
-        unsigned long long* seed[4] = {nullptr, nullptr, nullptr, nullptr};    // kSampleSlots tagged values each
-        SeedCtl* ctl = nullptr;         // [4] beside them ...
-        unsigned ctl_done[4] = {0u, 0u, 0u, 0u};   // ... and what their arrival counters hold
-        bool waiting = false;           // wait[0], wait[1]: a complete pair whose launch is due
-        Stashed wait[2];
-        bool has_first = false;         // first: the first query of the next pair (no sample yet) ...
-        Stashed first;
-        int first_replica_mode = 0, first_sample_mode = 0;   // ... and the modes it was accepted under
-        bool pending = false;           // the lists of the pair launched last wait for their mergers
+        uint64_t* lists[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};           // sgrid x kPairMaxTopk keys each
+        unsigned long long* seed[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // kSampleSlots tagged values each
+        SeedCtl* ctl = nullptr;         // [8] beside them ...
+        unsigned ctl_done[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};   // ... and what their arrival counters hold
+        int n_wait = 0;                 // 0, 2 or 4: wait[0 .. n_wait) are complete pairs whose launch is due
+        Stashed wait[4];
+        int n_form = 0;                 // 0 .. 3: form[0 .. n_form) are the queries of the group after it (no sample yet) ...
+        Stashed form[4];
+        int first_replica_mode = 0, first_sample_mode = 0;   // ... and the modes form[0] was accepted under
+        int n_pending = 0;              // 0, 2 or 4: the lists of the pairs launched last wait for their mergers
         int pending_set = 0, pending_lists = 0, pending_topn = 0;
-        uint64_t* pending_out[2] = {nullptr, nullptr};
+        uint64_t* pending_out[4] = {nullptr, nullptr, nullptr, nullptr};
     } pairs;
     // a STREAM of batches over the replica (mi355rec_enqueue_batch_keys_streamed)
     bool mstream_ready = false;
@@ -503,6 +509,7 @@ ScanGeom plan_replica(const mi355rec* h, int occ, int tile_rows, int align, doub
     if (max_blocks > kRideMaxLists) max_blocks = kRideMaxLists;
     MI355REC_EXP_INT(max_blocks, "MI355REC_EXP_REPLICA_GRID", 1, max_blocks - 1);
     const int64_t tiles = (h->n + tile_rows - 1) / tile_rows;
+    g.cap = static_cast<int>(max_blocks);
     g.grid = static_cast<int>(tiles < max_blocks ? tiles : max_blocks);
     g.iters = static_cast<int>((tiles + g.grid - 1) / g.grid);
     g.sgrid = g.grid > 1 ? g.grid - 1 : 1;

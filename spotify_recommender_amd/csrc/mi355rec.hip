@@ -369,6 +369,7 @@ int mi355rec_stats(const mi355rec_t* hc, mi355rec_stats_t* out) {
     }
     out->device_bytes_per_row = 48 + (h->d_half ? 24 : 0) + (h->d_q8 ? 12 : 0);
     out->stream_pair_launches = h->stream_pair_launches;
+    out->stream_group_launches = h->stream_group_launches;
     return MI355REC_OK;
 }
 
@@ -710,7 +711,7 @@ int mi355rec_set_sample(mi355rec_t* h, int mode) {
 
 int mi355rec_set_stream_pairing(mi355rec_t* h, int mode) {
     if (!h) return fail(nullptr, MI355REC_ERR_INVALID_ARG, "null handle");
-    if (mode != MI355REC_PAIRING_AUTO && mode != MI355REC_PAIRING_OFF && mode != MI355REC_PAIRING_ON)
+    if (mode != MI355REC_PAIRING_AUTO && mode != MI355REC_PAIRING_OFF && mode != MI355REC_PAIRING_ON && mode != MI355REC_PAIRING_GROUPS)
         return fail(h, MI355REC_ERR_INVALID_ARG, "unknown pairing mode %d", mode);
     h->pairing = mode;   // (from the next streamed query on: one that waits for a partner it can no longer get takes the one-query path)
     return MI355REC_OK;
@@ -777,16 +778,16 @@ int mi355rec_debug_handoff(mi355rec_t* h, int flags) {
             HIP_TRY(h, hipMemcpy(h->d_stream_ctl, ctl, sizeof ctl, hipMemcpyHostToDevice));
         }
         if (h->pairs.ready) {
-            // the pairs' buffers (engine_single.hip.h, "pairs"): TWO epochs are live while a pair waits for its launch (the
-            // last one handed out and the one before), so the stale values carry the three epochs before those
+            // the pairs' buffers (engine_single.hip.h, "pairs"): up to FOUR epochs are live while a group waits for its launch
+            // (the last four handed out), so the stale values carry the three epochs before those
             std::vector<unsigned long long> older(per);
             for (size_t i = 0; i < per; ++i)
-                older[i] = (static_cast<unsigned long long>(h->epoch_ctr - 2u - static_cast<uint32_t>(i % 3)) << 32) | one;
+                older[i] = (static_cast<unsigned long long>(h->epoch_ctr - 4u - static_cast<uint32_t>(i % 3)) << 32) | one;
             for (unsigned long long* b : h->pairs.seed)
                 if (b) HIP_TRY(h, hipMemcpy(b, older.data(), sizeof(unsigned long long) * per, hipMemcpyHostToDevice));
-            SeedCtl ctl[4];
+            SeedCtl ctl[8];
             HIP_TRY(h, hipMemcpy(ctl, h->pairs.ctl, sizeof ctl, hipMemcpyDeviceToHost));
-            for (SeedCtl& c : ctl) c.cutoff = (static_cast<unsigned long long>(h->epoch_ctr - 2u) << 32) | one_bits;
+            for (SeedCtl& c : ctl) c.cutoff = (static_cast<unsigned long long>(h->epoch_ctr - 4u) << 32) | one_bits;
             HIP_TRY(h, hipMemcpy(h->pairs.ctl, ctl, sizeof ctl, hipMemcpyHostToDevice));
         }
         if (h->d_lone_ctl) {

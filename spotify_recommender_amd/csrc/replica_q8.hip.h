@@ -921,10 +921,9 @@ __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel(
 // block_rank_and_store) is the single form's, so the keys are the single form's bit for bit.  Both queries ask for the same topk <= kPairMaxTopk: the
 // candidate lists are a quarter of the single form's (compaction starts at max(2 topk, 256) = 256 keys either way).
 //
-// Workgroups, by virtual id: [0, S) scan; S and S + 1 merge the lists of the pair BEFORE (prev[0], prev[1]); then
-// next[0].n_wgs and next[1].n_wgs seed riders and next[0].nbhd + next[1].nbhd neighbourhood workgroups for the two
-// queries of the pair AFTER, each with its own sample buffer, SeedCtl and epoch.  As in the single form they hold the
-// FIRST block ids.
+// Workgroups, by virtual id: [0, S) scan; the next Q = side.queries (2 or 4) merge the lists of the queries BEFORE
+// (prev[0 .. Q)); then Q x next[0].n_wgs seed riders and Q x next[0].nbhd neighbourhood workgroups for the queries AFTER, each
+// with its own sample buffer, SeedCtl and epoch.  As in the single form they hold the FIRST block ids.
 constexpr int kPairMaxTopk = 128;
 
 // A wave-uniform value the compiler holds in a vector register (whatever float arithmetic or an LDS read produced it), moved
@@ -987,21 +986,39 @@ struct Q8PairArg {
     uint32_t epoch;
 };
 
-// What the workgroups of a pair launch that do not scan are given: indexed by a run-time (uniform) 0 / 1, so that every role
-// exists once in the kernel's code and reads the arguments of ITS query from the kernel's argument block.
+// What the workgroups of a launch that do not scan are given: indexed by a run-time (uniform) index, so that every role
+// exists once in the kernel's code and reads the arguments of ITS query from the kernel's argument block.  `queries` is 2 or
+// 4: that many mergers, and that many queries after with `riders` seed riders and `nbhd` neighbourhood workgroups each (a
+// query slot nobody filled — prev.lists or next.out null — costs its workgroups an early return).
 struct Q8PairSide {
-    PrevMerge prev[2];   // the lists of the pair before
-    NextSeed next[2];    // the queries of the pair after: the same n_wgs and nbhd in both
+    PrevMerge prev[4];   // the lists of the pair (or the two pairs) before
+    NextSeed next[4];    // the queries of the pair (or the two pairs) after: the same n_wgs and nbhd in all
+    int queries;
+    int pad;
 };
 
+// The queries a launch scans for: pair g is q[2g], q[2g + 1].  A scanning workgroup picks its pair by a uniform run-time
+// index into the kernel's argument block, as the other roles pick theirs from Q8PairSide.
+struct Q8PairArgs {
+    Q8PairArg q[4];
+};
+
+// TWO PAIRS PER LAUNCH (pairs == 2).  The scanners split into two halves of H = S / 2, one per pair; every tile slot j < H is
+// scanned by two workgroups, one per pair ("twins").  Where H >= 8 (the host keeps it a multiple of 8 then) scanner s serves
+// pair (s >> 3) & 1 and slot ((s >> 4) << 3) | (s & 7): twins are scanners s and s ^ 8, whose block ids lie exactly 8 apart —
+// on the hardware this was written for they land on the same XCD at nearly the same time, so that the tile one of them
+// fetches is found in that XCD's L2 by the other.  Nothing but speed depends on that: no workgroup waits for another, and a
+// twin that runs alone or late computes the same keys.  A query's lists are block_lists[j], H of them; `rescored` stays per
+// scanning workgroup.  pairs == 1: H = S, slot = s — the launch of one pair as it always was.
 template <typename Cfg>
 __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel_pair(
-    const float* __restrict__ feats, const uint4* __restrict__ q8, int64_t n, int iters, int64_t row_base, Q8PairArg arg_a,
-    Q8PairArg arg_b, int topk, unsigned long long* __restrict__ rescored /* [scanning workgroups] */, Q8PairSide side) {
+    const float* __restrict__ feats, const uint4* __restrict__ q8, int64_t n, int iters, int64_t row_base, Q8PairArgs args,
+    int pairs /* 1 or 2 */, int topk, unsigned long long* __restrict__ rescored /* [scanning workgroups] */, Q8PairSide side) {
     constexpr int kBlock = Cfg::kBlock;
     __shared__ Q8PairOrMergeSmem<Cfg> s_mem;
     const unsigned riders = static_cast<unsigned>(side.next[0].n_wgs), nbhds = static_cast<unsigned>(side.next[0].nbhd);
-    const unsigned extra = 2u + 2u * (riders + nbhds);
+    const unsigned nq = static_cast<unsigned>(side.queries);
+    const unsigned extra = nq * (1u + riders + nbhds);
     const unsigned nblocks = gridDim.x - extra;   // scanning workgroups
     const unsigned vb = blockIdx.x >= extra ? blockIdx.x - extra : nblocks + blockIdx.x;
     if (vb >= nblocks) {
@@ -1009,14 +1026,16 @@ __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel_pa
                           sizeof(s_mem.scan.cand) >= sizeof(int) * Nbhd<kBlock>::kScratch, "the riders' geometry");
         int* const s_scratch = reinterpret_cast<int*>(s_mem.scan.cand);
         const unsigned e = vb - nblocks;   // uniform
-        if (e < 2u) {
+        if (e < nq) {
             q8_ride_merge(s_mem.merge, side.prev[e]);
-        } else if (e < 2u + 2u * riders) {
-            const unsigned which = e - 2u >= riders ? 1u : 0u;
-            q8_ride_sample<kBlock>(feats, q8, n, row_base, side.next[which], static_cast<int>(e - 2u - which * riders), s_scratch,
-                                   &s_mem.scan.count[0], &s_mem.scan.seeds[0], s_mem.scan.sel);
+        } else if (e < nq + nq * riders) {
+            const unsigned which = (e - nq) / riders;
+            if (side.next[which].out)
+                q8_ride_sample<kBlock>(feats, q8, n, row_base, side.next[which], static_cast<int>(e - nq - which * riders), s_scratch,
+                                       &s_mem.scan.count[0], &s_mem.scan.seeds[0], s_mem.scan.sel);
         } else {
-            q8_ride_nbhd<kBlock>(feats, n, row_base, side.next[e - 2u - 2u * riders], s_scratch);
+            const unsigned which = e - nq - nq * riders;
+            if (side.next[which].out) q8_ride_nbhd<kBlock>(feats, n, row_base, side.next[which], s_scratch);
         }
         __syncthreads();
         return;
@@ -1024,14 +1043,27 @@ __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel_pa
     Q8PairSmemT<Cfg>* const sm = &s_mem.scan;
     SelectSmem& s_sel = sm->sel;
 
-    const unsigned bid = vb;
+    // which pair this workgroup scans for, and which tile slot of that pair's `slots` it is (uniform)
+    unsigned group = 0u, bid = vb, slots = nblocks;
+    if (pairs == 2) {
+        slots = nblocks >> 1;
+        if (slots >= 8u) {
+            group = (vb >> 3) & 1u;
+            bid = ((vb >> 4) << 3) | (vb & 7u);
+        } else {   // (tiny shards: any mapping that gives each pair `slots` slots)
+            group = vb >= slots ? 1u : 0u;
+            bid = vb - group * slots;
+        }
+    }
+    const Q8PairArg& arg_a = args.q[2u * group];
+    const Q8PairArg& arg_b = args.q[2u * group + 1u];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
 
     const int64_t n_quads = (n + 3) >> 2;
     const int64_t last_quad = n_quads - 1;
     const int64_t quad_begin = static_cast<int64_t>(bid) * kBlock + tid;
-    const int64_t quad_stride = static_cast<int64_t>(nblocks) * kBlock;
+    const int64_t quad_stride = static_cast<int64_t>(slots) * kBlock;
 
     auto load_tile = [&](HalfTile& dst, int it) {
         int64_t quad = quad_begin + static_cast<int64_t>(it) * quad_stride;
@@ -1221,7 +1253,7 @@ __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel_pa
 
     if (lane == 0 && A.n_rescored + B.n_rescored) atomicAdd(&sm->rescored, A.n_rescored + B.n_rescored);
     __syncthreads();
-    if (tid == 0) rescored[bid] += static_cast<unsigned long long>(sm->rescored);   // launches of a handle are stream-ordered
+    if (tid == 0) rescored[vb] += static_cast<unsigned long long>(sm->rescored);   // launches of a handle are stream-ordered
     auto finish = [&](Mine& m, uint64_t* block_lists) {
         if (*m.s_count > kRankCountMax && *m.s_count > topk)  // uniform
             compact_candidates<kBlock, Cfg::kCandPerThread>(m.s_cand, m.s_count, topk, false, s_sel);

@@ -1249,15 +1249,21 @@ class NodeEngine(_RequestFamily):
 # ---- pairs of streamed queries -----------------------------------------------
 
 def set_stream_pairing(engine: "CosineEngine", mode: int) -> None:
-    """capi.PAIRING_AUTO / PAIRING_OFF / PAIRING_ON for `engine` (mi355rec_set_stream_pairing): whether two queued streamed
-    queries over the 8-bit replica that ask for the same topn <= 128 share ONE pass over it.  The stream then runs up to
-    three calls behind instead of one; results are unchanged.  A lane inherits the mode when it is created."""
+    """capi.PAIRING_AUTO / PAIRING_OFF / PAIRING_ON / PAIRING_GROUPS for `engine` (mi355rec_set_stream_pairing): whether two
+    queued streamed queries over the 8-bit replica that ask for the same topn <= 128 share ONE pass over it — and, under
+    GROUPS, whether two such pairs share one launch.  The stream then runs up to three calls behind instead of one (seven
+    under GROUPS for queries by row and by value); results are unchanged.  A lane inherits the mode when it is created."""
     capi.check(engine._lib.mi355rec_set_stream_pairing(engine._h, int(mode)), engine._h)
 
 
 def stream_pair_launches(engine: "CosineEngine") -> int:
-    """Pair launches of `engine` since create (mi355rec_stats_t::stream_pair_launches)."""
+    """Pairs launched by `engine` since create (mi355rec_stats_t::stream_pair_launches; a group launch adds two)."""
     return int(engine.stats().stream_pair_launches)
+
+
+def stream_group_launches(engine: "CosineEngine") -> int:
+    """Launches of `engine` that served two pairs, since create (mi355rec_stats_t::stream_group_launches)."""
+    return int(engine.stats().stream_group_launches)
 
 
 # ---- packed keys on the host (pure bit manipulation, mirrors kernels.hip.h) ----
