@@ -212,6 +212,11 @@ public:
     // manhattan (include/mi355rec_diag.h, "MANHATTAN REQUESTS"): songs rank by their mean L1 distance to `songs`, nearest first;
     // lastScores() holds the distances.  With manhattan, weights, diverse, maxPerArtist, priorWeight, scales, euclidean and anyOf are
     // refused with a message and {}, and so are a set candidate list (setCandidates) and scoreSongs.  The row set of setRowSet applies.
+    // atLeast / within (include/mi355rec_diag.h, "BOUNDED REQUESTS"): only songs that are good enough, and how many there are.
+    // query.atLeast(s) keeps the songs whose similarity (the plain mean) is >= s; query.within(r) sets euclidean and keeps the songs
+    // whose distance is <= r.  The results are the leading matches, at most topN of them (topN = 0 is allowed: count only), and
+    // lastMatchCount() holds the exact number of matching songs.  With a bound, weights, diverse, maxPerArtist, priorWeight, scales,
+    // anyOf and manhattan are refused with a message and {}, and so are a set candidate list and scoreSongs.  The row set applies.
     struct Query {
         std::vector<int> songs;            // 1 to 32
         std::vector<float> weights;        // one per song, or none
@@ -228,11 +233,18 @@ public:
         int topN = 10;
         bool anyOf = false;
         bool manhattan = false;
+        bool bounded = false;              // set by atLeast / within: `bound` is a score floor, or (euclidean) a radius
+        float bound = 0.0f;
+        Query& atLeast(float score) { bounded = true, euclidean = false, bound = score; return *this; }
+        Query& within(float radius) { bounded = true, euclidean = true, bound = radius; return *this; }
     };
     std::vector<int> recommendQuery(const Query& query);
     // Per result of the last recommendQuery with anyOf: the catalogue index of the matched song of query.songs (the first of them
     // that attains the result's score).  Empty after any other call.
     const std::vector<int>& lastMatchedSongs() const;
+    // The number of songs that matched the bound of the last recommendQuery with atLeast / within (whatever its topN); -1 after any
+    // other call and after one that failed.
+    long long lastMatchCount() const;
 
     // Extension: candidate scores (include/mi355rec_diag.h, "CANDIDATE SCORES").  scoreSongs gives what `query` is worth at every
     // song of songIndices, in their order (duplicates allowed, at most 1 048 576): the score (with euclidean the distance)

@@ -40,6 +40,8 @@
  *     (mi355rec_query_anyof_request and its node-handle twin);
  *   - MANHATTAN REQUESTS: the nearest rows by L1 distance to up to 32 members, with the playlist request's exclusion list,
  *     feature filter, label set and row set (mi355rec_query_manhattan_request and its node-handle twin);
+ *   - BOUNDED REQUESTS: only the rows at or above a score floor (or within a radius), and the exact number of such rows
+ *     (mi355rec_query_bounded_request and its node-handle twin);
  *   - test hooks, compiled in only with -DMI355REC_TEST_HOOKS (spotify_recommender_amd/build.py builds
  *     libmi355rec_testhooks.so for tests/; the product library does not export them).
  */
@@ -1155,6 +1157,83 @@ int mi355rec_query_manhattan_request(mi355rec_t* h, const mi355rec_manhattan_que
                                      const mi355rec_manhattan_result_t* result);
 int mi355rec_sharded_query_manhattan_request(mi355rec_sharded_t* h, const mi355rec_manhattan_query_t* query,
                                              const mi355rec_request_ext_t* ext, const mi355rec_manhattan_result_t* result);
+
+/* BOUNDED REQUESTS: "only rows that are good enough" and "how many such rows are there".  Every other request answers "which N
+ * rows are best"; topn is capped at MI355REC_MAX_TOPN_FAST, so a caller that cuts a returned list at a score cannot learn how many
+ * rows pass.  A bounded request takes a BOUND beside the fields of the distance request: a score floor for the cosine metric, a
+ * radius for the Euclidean one.  It returns the leading matching rows and the EXACT number of matching rows, whatever topn is.
+ * mi355rec_bounded_query_t has the field list of mi355rec_distance_query_t followed by `metric` and `bound`, and carries its own
+ * size under the same rules (every field end is a valid size; a shorter struct reads as "later fields zero").
+ *   members / rows   exactly one is non-NULL: k x 12 floats by value, or k rows of the handle (never returned, never counted);
+ *                    1 <= k <= MI355REC_MAX_PLAYLIST;
+ *   exclude_global / n_exclude, filter, labels / n_labels   as in the playlist request;
+ *   topn             in [0, MI355REC_MAX_TOPN_FAST]; 0: count only;       flags   must be 0;
+ *   metric           MI355REC_BOUNDED_COSINE or MI355REC_BOUNDED_EUCLIDEAN;
+ *   bound            cosine: the floor, any finite value; Euclidean: the radius, finite and >= 0.
+ * mi355rec_bounded_result_t: out_total is required; out_idx and out_score (topn slots each) may be NULL when topn == 0 (out_idx is
+ * required otherwise, out_score may always be NULL); out_count may be NULL.
+ * Admissibility is the playlist request's, unchanged: the row set of `ext`, the label set, the filter, not a member row, not excluded.
+ * RANKING VALUE AND KEY, per metric:
+ *   MI355REC_BOUNDED_COSINE     the playlist request's unweighted mean cosine: bit for bit the score mi355rec_query_playlist_request
+ *                               reports with flags 0;
+ *   MI355REC_BOUNDED_EUCLIDEAN  the distance request's m(x) ("DISTANCE REQUESTS"), keys of -m; the reported value is sqrtf(m).
+ * A row MATCHES iff it is admissible and its key exceeds floor_thr = (uint64(ordered image of b) << 32) - 1, the ordered image
+ * being the one keys carry (mi355rec_key_score's inverse; -0.0 and +0.0 share one):
+ *   cosine      b = bound: score >= bound.  Above 1 nothing matches; at -1 or below every admissible row does;
+ *   Euclidean   b = -m_max, m_max the largest float with sqrtf(m_max) <= bound (found on the host from fl(bound^2) by nextafterf
+ *               steps: sqrtf is monotone): a row matches exactly when the distance the call would report is <= the radius.  A
+ *               row whose m is not finite never matches.
+ * OUTPUT: *out_total = the number of matching rows, exact; count = min(topn, total); results [0, count) are the matching rows in
+ * key order: exactly the leading matching results of the unbounded playlist or distance request with the same fields (ids, order,
+ * score bits); past count the padding is -1 / +0.0f.
+ * INVALID_ARG (with a message): a NaN or infinite bound; a negative radius; an unknown metric; flags != 0; topn out of range; a
+ * non-NULL feature_scales in ext ("bounded requests take no feature scales"); both or neither of members and rows; a bad size;
+ * everything the playlist request refuses for the fields the two share (same limits, same messages).
+ * Device: no new kernel.  At most two launches of playlist_scan_kernel on the handle's stream: the COUNT launch, always (the scan
+ * with topk == 0: csrc/playlist.hip.h, "BOUNDED"), then, for topn > 0, the ordinary top-N launch of the same request and its
+ * merge; the host cuts the merged results at the floor.  The count launch starts at the floor, so the 8-bit pre-filter runs at
+ * its final cut from the first tile; a row the cut leaves takes the exact chains, and key > floor_thr then the exclusion lookup
+ * decide.  With the cosine metric and no feature filter the replica also proves rows IN (csrc/playlist_cut.hip.h, "BOUNDED": the
+ * bound is symmetric): such a row is counted without its fp32 row being read, and only the band between the two cuts takes the
+ * chains.  Replica on and off answer alike, bit for bit.  mi355rec_playlist_counters counts the call ONCE; its rows_exact moves
+ * for the top-N launch only, NOT for count launches (their counter word is the call's total).
+ * Measured (MI355X, 10 M uniform rows, K = 1 by row, p50 per call; profiles/r26_bounded.json, tools/run_bounded.py; the parent
+ * commit's plain top-100 playlist request: 95.4 us): count only at a floor about 1 000 rows pass 60.5 us; count only at the median
+ * floor (5.0 M matches) 95.3 us (152.2 us with the proven-in shortcut off: profiles/r26_bounded_shortcut_ab.json); topn = 100 with
+ * the tight floor 110.6 us, with the median floor 169.4 us.  The existing requests against the parent's library
+ * (profiles/r26_bounded_existing_ab.json): ratios 0.995 - 1.013, all but distance K = 10 (1.013 against 1.2 %) inside its spread.
+ * Node handle: one shard forwards; a replicated placement asks one replica; a row-sharded one fetches members given by row,
+ * forwards them by value to every shard, merges keys on the host, cuts at the floor and sums the shards' totals.  The CPU
+ * backend runs the same chain, floor and total.
+ * Not served (refused or absent): weights, diversified and capped calls, priors, feature scales, candidate lists, the any-of and
+ * Manhattan metrics; asynchronous, streamed and batched variants. */
+#define MI355REC_BOUNDED_COSINE 0
+#define MI355REC_BOUNDED_EUCLIDEAN 1
+typedef struct {
+    uint32_t size;                    /* sizeof(mi355rec_bounded_query_t) of the caller's header */
+    uint32_t flags;                   /* must be 0 */
+    const float* members;             /* k x 12 floats (host), or NULL with ... */
+    const int64_t* rows;              /* ... k rows of the handle */
+    const int64_t* exclude_global;    /* n_exclude global ids, or NULL */
+    const mi355rec_filter_t* filter;  /* NULL, or the feature filter */
+    const int32_t* labels;            /* NULL, or n_labels labels */
+    int32_t k;
+    int32_t n_exclude;
+    int32_t n_labels;
+    int32_t topn;                     /* 0: count only */
+    int32_t metric;                   /* MI355REC_BOUNDED_COSINE, MI355REC_BOUNDED_EUCLIDEAN */
+    float bound;                      /* the score floor, or the radius */
+} mi355rec_bounded_query_t;           /* 72 bytes */
+typedef struct {
+    int64_t* out_idx;                 /* topn slots; may be NULL when topn == 0 */
+    float* out_score;                 /* topn slots, or NULL: the score, or (Euclidean) the distance */
+    int* out_count;                   /* or NULL: min(topn, total) */
+    int64_t* out_total;               /* required: the number of matching rows */
+} mi355rec_bounded_result_t;
+int mi355rec_query_bounded_request(mi355rec_t* h, const mi355rec_bounded_query_t* query, const mi355rec_request_ext_t* ext,
+                                   const mi355rec_bounded_result_t* result);
+int mi355rec_sharded_query_bounded_request(mi355rec_sharded_t* h, const mi355rec_bounded_query_t* query,
+                                           const mi355rec_request_ext_t* ext, const mi355rec_bounded_result_t* result);
 
 /* ROW UPDATES (the reference lists "Real-time Updates: Incremental index updates" among its extensions): songs are re-analysed
  * and corrected every day, and a changed row should not cost a rebuild of everything the handle keeps beside the rows.

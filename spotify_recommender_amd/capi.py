@@ -105,6 +105,20 @@ class ManhattanResult(ctypes.Structure):
     _fields_ = [("out_idx", c_void_p), ("out_distance", c_void_p), ("out_count", POINTER(c_int))]
 
 
+BOUNDED_COSINE, BOUNDED_EUCLIDEAN = 0, 1   # mi355rec_bounded_query_t::metric
+
+
+class BoundedQuery(ctypes.Structure):
+    """mi355rec_bounded_query_t (include/mi355rec_diag.h, BOUNDED REQUESTS): the metric requests' 64 bytes, then `metric` and `bound`
+    (72 bytes); `size` is sizeof of this struct, flags 0, topn 0 counts only."""
+    _fields_ = _METRIC_QUERY_FIELDS + [("metric", c_int32), ("bound", c_float)]
+
+
+class BoundedResult(ctypes.Structure):
+    """mi355rec_bounded_result_t: out_total (int64) is required; out_idx and out_score may be NULL when topn == 0; out_count may be NULL."""
+    _fields_ = [("out_idx", c_void_p), ("out_score", c_void_p), ("out_count", POINTER(c_int)), ("out_total", POINTER(c_int64))]
+
+
 ROWSET_EXCLUDE, ROWSET_ONLY = 0, 1   # MI355REC_ROWSET_* (ROW SETS)
 MAX_CANDIDATES = 1 << 20             # MI355REC_MAX_CANDIDATES (CANDIDATE LISTS)
 
@@ -340,6 +354,9 @@ SIGNATURES = {
     # MANHATTAN REQUESTS: nearest-by-L1 top-N; one entry point takes the ext
     "mi355rec_query_manhattan_request": (c_int, [c_void_p, POINTER(ManhattanQuery), POINTER(RequestExt), POINTER(ManhattanResult)]),
     "mi355rec_sharded_query_manhattan_request": (c_int, [c_void_p, POINTER(ManhattanQuery), POINTER(RequestExt), POINTER(ManhattanResult)]),
+    # BOUNDED REQUESTS: the rows at or above a score floor (within a radius) and their exact number; one entry point takes the ext
+    "mi355rec_query_bounded_request": (c_int, [c_void_p, POINTER(BoundedQuery), POINTER(RequestExt), POINTER(BoundedResult)]),
+    "mi355rec_sharded_query_bounded_request": (c_int, [c_void_p, POINTER(BoundedQuery), POINTER(RequestExt), POINTER(BoundedResult)]),
     # ROW UPDATES: rows change in place, every route answers as a freshly created handle would
     "mi355rec_update_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "mi355rec_sharded_update_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

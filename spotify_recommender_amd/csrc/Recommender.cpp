@@ -56,6 +56,7 @@ struct Recommender::Impl {
     std::vector<float> scoreBuf;
     std::vector<float> lastScores;
     std::vector<int> lastMatched;   // Query::anyOf: the matched song of every result of the last such query
+    long long lastMatchCount = -1;  // Query::atLeast / within: the matching songs of the last such query
 };
 
 namespace {
@@ -438,6 +439,7 @@ struct ScoreSongs {
     bool ok = false;   // the engine has answered: values and admissible hold one entry per song
 };
 std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, bool rangesLast, ScoreSongs* score = nullptr) {
+    impl->lastMatchCount = -1;   // (whatever this call turns out to be: only a bounded query that succeeds leaves a count)
     if (!q.weights.empty() && q.weights.size() != q.songs.size()) {
         std::cerr << "Error: " << q.weights.size() << " weights for " << q.songs.size() << " songs (one weight per song, or none)" << std::endl;
         return {};
@@ -464,7 +466,7 @@ std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, 
                 return {};
             }
     int topN = score ? 1 : q.topN;   // (scoreSongs ignores topN)
-    if (topN <= 0) {
+    if (topN < 0 || (topN == 0 && !q.bounded)) {   // ("BOUNDED REQUESTS": topN = 0 counts only)
         std::cerr << "Error: topN must be positive" << std::endl;
         return {};
     }
@@ -488,6 +490,21 @@ std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, 
         return {};
     }
     impl->lastMatched.clear();
+    if (q.bounded) {   // "BOUNDED REQUESTS": what the request has no field for, and what is not served with it
+        if (!q.weights.empty() || rerank || withPrior || !q.scales.empty() || q.anyOf || q.manhattan) {
+            std::cerr << "Error: a bounded query takes no weights, diversity, cap, prior weight, feature scales, any-of matching or Manhattan distance"
+                      << std::endl;
+            return {};
+        }
+        if (impl->hasCandidates) {
+            std::cerr << "Error: a bounded query takes no candidate list (clearCandidates first)" << std::endl;
+            return {};
+        }
+        if (score) {
+            std::cerr << "Error: scoreSongs takes no bounded query" << std::endl;
+            return {};
+        }
+    }
     if (q.anyOf) {   // "ANY-OF REQUESTS": what the request has no field for, and what is not served with it
         if (!q.weights.empty() || rerank || withPrior || !q.scales.empty() || q.euclidean) {
             std::cerr << "Error: an any-of query takes no weights, diversity, cap, prior weight, feature scales or Euclidean metric" << std::endl;
@@ -553,7 +570,19 @@ std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, 
     const mi355rec_request_ext_t ext = requestExt(impl, q.scales.empty() ? nullptr : q.scales.data());
     int rc;
     std::vector<int32_t> member;
-    if (q.manhattan) {
+    int64_t matching = -1;
+    if (q.bounded) {
+        mi355rec_bounded_query_t b{};
+        shared(b);
+        b.metric = q.euclidean ? MI355REC_BOUNDED_EUCLIDEAN : MI355REC_BOUNDED_COSINE;
+        b.bound = q.bound;
+        mi355rec_bounded_result_t res{};
+        res.out_idx = impl->idxBuf.data();
+        res.out_score = impl->scoreBuf.data();
+        res.out_count = &count;
+        res.out_total = &matching;
+        rc = mi355rec_sharded_query_bounded_request(impl->engine, &b, &ext, &res);
+    } else if (q.manhattan) {
         mi355rec_manhattan_query_t m{};
         shared(m);
         mi355rec_manhattan_result_t res{};
@@ -617,6 +646,7 @@ std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, 
     std::vector<int> results(static_cast<size_t>(count));
     for (int i = 0; i < count; ++i) results[i] = static_cast<int>(impl->idxBuf[i]);
     impl->lastScores.assign(impl->scoreBuf.begin(), impl->scoreBuf.begin() + count);
+    impl->lastMatchCount = matching;
     if (q.anyOf)
         for (int i = 0; i < count; ++i) impl->lastMatched.push_back(q.songs[static_cast<size_t>(member[static_cast<size_t>(i)])]);
     return results;
@@ -783,6 +813,7 @@ int Recommender::getSongCount() const { return impl_->numSongs; }
 
 const std::vector<float>& Recommender::lastScores() const { return impl_->lastScores; }
 const std::vector<int>& Recommender::lastMatchedSongs() const { return impl_->lastMatched; }
+long long Recommender::lastMatchCount() const { return impl_->lastMatchCount; }
 
 bool Recommender::similarities(int songIndex, std::vector<float>& out) {  // Recommender.cu:184-254
     if (!impl_->initialized || songIndex < 0 || songIndex >= impl_->numSongs) {

@@ -586,6 +586,14 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
     int64_t avail = 0;
     const int rc = mean_keys(h, r, keys, &avail, why);
     if (rc) return rc;
+    if (r.bounded) {   // "BOUNDED REQUESTS": only the keys above the floor are left; their number is the total
+        avail = 0;
+        for (uint64_t& key : keys) {
+            if (key <= r.floor_thr) key = 0;
+            avail += key != 0;
+        }
+        *out.total = avail;
+    }
     const int count = static_cast<int>(topn_asked < avail ? topn_asked : avail);
     std::partial_sort(keys.begin(), keys.begin() + count, keys.end(), std::greater<uint64_t>());
     for (int i = 0; i < count; ++i) {
@@ -599,8 +607,9 @@ int node_query_mean(Node* h, const mi355playlist::Request& r, const mi355playlis
             out.member[i] = a;
         }
     }
-    mi355playlist::pad(out, count, topn_asked, count);
-    if (r.report_distance) mi355playlist::scores_to_distances(out, topn_asked, r.metric);
+    if (topn_asked > 0) mi355playlist::pad(out, count, topn_asked, count);
+    else if (out.count) *out.count = 0;   // ("BOUNDED REQUESTS", count only: out.idx may be null)
+    if (r.report_distance && topn_asked > 0) mi355playlist::scores_to_distances(out, topn_asked, r.metric);
     return MI355REC_OK;
 }
 

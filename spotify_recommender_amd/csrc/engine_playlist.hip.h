@@ -5,6 +5,8 @@
 // Every call of the family (filtered, weighted, diversified, capped; by value or by row) is one mi355playlist::Request
 // (playlist_request.h) through sync_playlist_query; the exported functions only fill it.  An ANY-OF request (metric kAnyOf) takes the
 // same path with anyof_scan_kernel (anyof.hip.h) at the launch and, where out_member is asked for, its attribution launch after the merge.
+// A BOUNDED request (Request::bounded) takes the same path with one more launch ahead of the scan: playlist_scan_kernel's count form
+// (topk == 0 without a list), whose total comes back through a pinned word; sync_playlist_query then cuts the merged results at the floor.
 // (Part of mi355rec.hip's translation unit, included after engine_labels.hip.h.)
 #pragma once
 
@@ -55,6 +57,11 @@ struct mi355rec_playlist {
     // the pinned h_member on the handle's stream.  kMaxTopK entries each, allocated with the buffers above.
     int32_t* d_member = nullptr;
     int32_t* h_member = nullptr;
+    // BOUNDED REQUESTS (playlist.hip.h, "BOUNDED"): the count launch's total word (its `rows_exact`): zeroed on the handle's stream
+    // ahead of the launch, copied into the pinned h_total behind it; the call's completion covers both.
+    unsigned long long* d_total = nullptr;
+    unsigned long long* h_total = nullptr;
+    bool counted = false;                       // the last playlist_launch enqueued a count launch: h_total is this call's
 };
 
 namespace {
@@ -109,6 +116,8 @@ void free_playlist(mi355rec_playlist* P) {
     if (P->d_cand_keys) (void)hipFree(P->d_cand_keys);
     if (P->d_member) (void)hipFree(P->d_member);
     if (P->h_member) (void)hipHostFree(P->h_member);
+    if (P->d_total) (void)hipFree(P->d_total);
+    if (P->h_total) (void)hipHostFree(P->h_total);
     delete P;
 }
 
@@ -127,6 +136,8 @@ int ensure_playlist(mi355rec* h) {
     if ((e = hipMemset(P->d_exact, 0, sizeof(unsigned long long))) != hipSuccess) return failed(e, "hipMemset(playlist counter)");
     if ((e = hipMalloc(&P->d_member, sizeof(int32_t) * kMaxTopK)) != hipSuccess) return failed(e, "hipMalloc(any-of members)");
     if ((e = hipHostMalloc(&P->h_member, sizeof(int32_t) * kMaxTopK, hipHostMallocDefault)) != hipSuccess) return failed(e, "hipHostMalloc(any-of members)");
+    if ((e = hipMalloc(&P->d_total, sizeof(unsigned long long))) != hipSuccess) return failed(e, "hipMalloc(bounded total)");
+    if ((e = hipHostMalloc(&P->h_total, sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess) return failed(e, "hipHostMalloc(bounded total)");
     int occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, playlist_scan_kernel, PlaylistCfg::kBlock, 0) != hipSuccess || occ < 1) occ = 1;
     (void)hipGetLastError();
@@ -196,6 +207,7 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     if (rc) return rc;
     mi355rec_playlist* P = h->playlist;
     PlaylistBuf* b = P->h_buf;
+    P->counted = false;
     // the excluded rows of this shard: sorted, distinct, as uint32 global ids
     int n_excl = 0;
     for (int i = 0; i < r.n_exclude; ++i)
@@ -259,7 +271,9 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     }
     ++h->playlist_queries;
     const int eff = static_cast<int64_t>(r.scan_topn()) < avail ? r.scan_topn() : static_cast<int>(avail);
-    if (eff <= 0) return MI355REC_OK;   // nothing left to return: nothing to launch
+    // "BOUNDED REQUESTS": the count launch goes whenever a row could be admissible, whatever topn is
+    const bool count_launch = r.bounded && avail > 0;
+    if (eff <= 0 && !count_launch) return MI355REC_OK;   // nothing left to return: nothing to launch
     // "CANDIDATE SCORES": the launch selects nothing (topk == 0 is the kernel's score mode) and needs no result slot
     const int topk = r.score ? 0 : eff;
     PlaylistArg arg;
@@ -311,7 +325,12 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     const bool anyof = r.metric == mi355playlist::kAnyOf;
     rc = sync_begin(h, topk, 1, !(anyof && r.attribute), ss);
     if (rc) return rc;
-    b->shared_thr = 0ull;
+    // "BOUNDED REQUESTS": the floor, where every other call stages 0.  The count launch starts from it and never moves it; the top-N
+    // launch behind it is SEEDED with it: every workgroup adopts the word after its first tile, which is sound (only keys above the
+    // floor are wanted; sync_playlist_query cuts whatever the first tiles let through) and costs nothing: one staging serves both.  Its
+    // lists may then hold fewer than `eff` keys, as a filtered call's already may: block_rank_and_store pads a short list with 0
+    // keys, the merge sorts them last and sync_finish counts the ids >= 0.
+    b->shared_thr = r.bounded ? r.floor_thr : 0ull;
     // (the staging buffer is free: the previous call on this handle has completed)
     const size_t bytes = offsetof(PlaylistBuf, excl) + sizeof(uint32_t) * static_cast<size_t>(n_excl);
     HIP_TRY(h, hipMemcpyAsync(P->d_buf, b, bytes, hipMemcpyHostToDevice, h->stream));
@@ -334,6 +353,22 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     if (want_grid > P->grid_cap) want_grid = P->grid_cap;
     if (want_grid < 1) want_grid = 1;
     const int grid = static_cast<int>(want_grid);
+    if (count_launch) {   // "BOUNDED REQUESTS": the count form: topk == 0 without a list, the total word as rows_exact; AHEAD of the
+        // top-N launch, which raises shared_thr above the floor
+        HIP_TRY(h, hipMemsetAsync(P->d_total, 0, sizeof(unsigned long long), h->stream));
+        PlaylistArg count_arg = arg;
+        // (experiments build only: tools/run_bounded.py's A/B of the proven-in shortcut; n_cand means nothing else without a list)
+        if (MI355REC_EXP_FLAG("MI355REC_EXP_NO_PROVEN_IN")) count_arg.n_cand = 1;
+        hipLaunchKernelGGL(playlist_scan_kernel, dim3(grid), dim3(PlaylistCfg::kBlock), 0, h->stream, h->d_feats, q8, h->n, h->row_base,
+                           static_cast<const PlaylistBuf*>(P->d_buf), count_arg, static_cast<const float*>(nullptr), 0, h->d_block_lists, P->d_total,
+                           reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr)),
+                           reinterpret_cast<const uint2*>(L ? L->d_row_labels : nullptr), reinterpret_cast<const float4*>(pri),
+                           reinterpret_cast<const float4*>(scan_norms ? P->d_norms : nullptr));
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(P->h_total, P->d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+        P->counted = true;
+        if (topk == 0) return MI355REC_OK;   // count only (or nothing to list): *grid_out stays 0
+    }
     if (manhattan) {   // "MANHATTAN REQUESTS": its own kernel (anyof.hip.h), this launch's geometry, inputs and lists
         const AnyofArg any = {k, n_excl, arg.by_row, arg.active, arg.labelled, arg.rowset, arg.rowset_flip, 0};
         LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, manhattan_scan_kernel, dim3(grid), dim3(PlaylistCfg::kBlock), h->stream,
@@ -391,7 +426,8 @@ int rerank_and_wait(mi355rec* h, const Request& r, const Outputs& out, SyncSlots
 
 // The one synchronous path of the family.  max_exclude: kMaxExclude for the exported calls, kPlExcludeCap for the node's.
 int sync_playlist_query(mi355rec* h, const Request& r, const Outputs& out, int max_exclude = kMaxExclude) {
-    if (!h || !(r.members || r.rows) || !out.idx) return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    if (!h || !(r.members || r.rows) || !(out.idx || (r.bounded && r.topn == 0)) || (r.bounded && !out.total))
+        return fail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     int rc = r.diverse ? check_diverse(h, r) : MI355REC_OK;
     if (rc) return rc;
     if (out.pool_rows) *out.pool_rows = 0;
@@ -401,6 +437,16 @@ int sync_playlist_query(mi355rec* h, const Request& r, const Outputs& out, int m
     rc = playlist_launch(h, r, max_exclude, &ss, &grid);
     if (rc) return rc;
     const int eff = ss.eff;
+    if (r.bounded && grid == 0) {   // "BOUNDED REQUESTS": no top-N launch: the count launch alone (wait for its total), or nothing at all
+        *out.total = 0;
+        if (h->playlist->counted) {
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            *out.total = static_cast<int64_t>(*h->playlist->h_total);
+        }
+        if (r.topn > 0) mi355playlist::pad(out, 0, r.topn, 0);
+        else if (out.count) *out.count = 0;
+        return MI355REC_OK;
+    }
     if (eff <= 0) {
         mi355playlist::pad(out, 0, r.topn, 0);
         return MI355REC_OK;
@@ -421,6 +467,11 @@ int sync_playlist_query(mi355rec* h, const Request& r, const Outputs& out, int m
         if (rc) return rc;
     }
     rc = sync_finish(h, ss, r.topn, out.idx, out.score, out.count);
+    if (rc == MI355REC_OK && r.bounded) {   // "BOUNDED REQUESTS": the total (copied ahead of the merge that was waited for), the cut at the floor
+        *out.total = static_cast<int64_t>(*h->playlist->h_total);
+        const int matched = mi355playlist::bounded_cut(r, h->h_idx, h->h_score, eff);
+        mi355playlist::pad(out, matched, r.topn, matched);
+    }
     if (rc == MI355REC_OK && out.member)   // (the stream has been waited for: ss.want == 0 with an attribution)
         for (int i = 0; i < r.topn; ++i) out.member[i] = i < eff && out.idx[i] >= 0 ? h->playlist->h_member[i] : -1;
     if (rc == MI355REC_OK && r.report_distance) mi355playlist::scores_to_distances(out, r.topn, r.metric);   // "DISTANCE REQUESTS": -m to sqrtf(m) ("MANHATTAN": to m)
@@ -616,6 +667,12 @@ int mi355rec_query_anyof_request(mi355rec_t* h, const mi355rec_anyof_query_t* qu
 // "MANHATTAN REQUESTS": the same Request with metric = kManhattan through the same path; its scan is manhattan_scan_kernel.
 int mi355rec_query_manhattan_request(mi355rec_t* h, const mi355rec_manhattan_query_t* query, const mi355rec_request_ext_t* ext,
                                      const mi355rec_manhattan_result_t* result) {
+    return request_entry(h, query, ext, result, {});
+}
+
+// "BOUNDED REQUESTS": the same Request with `bounded` through the same path: the count launch, then the top-N launch where topn > 0.
+int mi355rec_query_bounded_request(mi355rec_t* h, const mi355rec_bounded_query_t* query, const mi355rec_request_ext_t* ext,
+                                   const mi355rec_bounded_result_t* result) {
     return request_entry(h, query, ext, result, {});
 }
 

@@ -24,6 +24,9 @@
 //   ... --song, --id and --playlist with --distance manhattan: the NEAREST songs by Manhattan (L1) distance over the 12 features,
 //       for a playlist the mean of the distances to its songs (extension; with --genre, --where, --seen and --only and nothing else;
 //       distances are printed; --metric keeps its two names)
+//   ... --song, --id and --playlist with --min-score S: only the songs whose similarity is at least S, and "N of TOTAL matching":
+//       how many songs of the catalogue pass, whatever -n is; with --metric euclidean it is --within R: the songs within distance R
+//       (extension: BOUNDED REQUESTS; with --genre, --where, --seen and --only and nothing else; --count-only prints the number alone)
 //   ... --song, --id and --playlist with one or more --scale NAME=S: feature NAME counts S times (0: ignored) in the similarity or
 //       the distance (extension; under both metrics, with --genre and --where)
 //   ... the same modes with --candidates FILE (track ids, one per line, as for --only): only the listed songs are READ and ranked (a
@@ -632,6 +635,51 @@ static bool parseDistance(int argc, char* argv[], int first, bool& manhattan) {
     return true;
 }
 
+// --min-score S, --within R and --count-only from argv[first] (BOUNDED REQUESTS): bounded = true with `bound` = S or R.  false (the
+// return value), with a message, for a value that is no finite number, both options, --within without --metric euclidean,
+// --min-score with it, or --count-only without either.
+static bool parseBound(int argc, char* argv[], int first, bool euclidean, bool& bounded, float& bound, bool& countOnly) {
+    bounded = countOnly = false;
+    const char* which = nullptr;
+    for (int i = first; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--count-only") == 0) countOnly = true;
+        if (std::strcmp(argv[i], "--min-score") != 0 && std::strcmp(argv[i], "--within") != 0) continue;
+        const char* option = argv[i];
+        if (i + 1 >= argc) {
+            std::cerr << "Error: " << option << " needs a number" << std::endl;
+            return false;
+        }
+        if (which) {
+            std::cerr << "Error: " << option << " cannot be combined with " << which << " (one bound per request)" << std::endl;
+            return false;
+        }
+        char* end = nullptr;
+        const float v = std::strtof(argv[++i], &end);
+        if (end == argv[i] || *end != '\0' || !(v - v == 0.0f)) {
+            std::cerr << "Error: " << option << " '" << argv[i] << "': a finite number" << std::endl;
+            return false;
+        }
+        which = option;
+        bounded = true;
+        bound = v;
+    }
+    if (which && (std::strcmp(which, "--within") == 0) != euclidean) {
+        std::cerr << "Error: " << (euclidean ? "--min-score cannot be combined with --metric euclidean (a radius is --within R)"
+                                             : "--within goes with --metric euclidean (a score floor is --min-score S)")
+                  << std::endl;
+        return false;
+    }
+    if (bounded && euclidean && bound < 0.0f) {
+        std::cerr << "Error: --within '" << bound << "': a radius is >= 0" << std::endl;
+        return false;
+    }
+    if (countOnly && !bounded) {
+        std::cerr << "Error: --count-only goes with --min-score or --within" << std::endl;
+        return false;
+    }
+    return true;
+}
+
 // -n N: the first -n among argv[first .. argc-2] (the reference's rule, main.cpp:169-178: in last position it is not looked at).
 static bool parseTopN(int argc, char* argv[], int first, int& topN) {
     for (int i = first; i < argc - 1; ++i) {
@@ -673,12 +721,15 @@ struct Options {
     bool euclidean = false;
     bool anyOf = false;        // --match any
     bool manhattan = false;    // --distance manhattan
+    bool bounded = false;      // --min-score S, or --within R under --metric euclidean: `bound`
+    float bound = 0.0f;
+    bool countOnly = false;    // --count-only
     std::vector<float> scales;
     Taste taste;
     DiverseOpt dv;
     PriorOpt pr;
     // a distance or scaled request (its own banner; scores or distances are printed; --song / --id run as the one-song playlist)
-    bool nearest() const { return euclidean || manhattan || !scales.empty(); }
+    bool nearest() const { return euclidean || manhattan || bounded || !scales.empty(); }
 };
 
 // What does not combine: the option `given` stands for beside one of `beside` (the first of them in argv stands for %s in `text`).
@@ -692,6 +743,7 @@ enum class Given {
     GenreReranked,   // ... and beside a re-rank: --playlist <one id> and the distance and scaled requests serve those pairs
     MatchAny,        // --match any
     Manhattan,       // --distance manhattan
+    Bounded,         // --min-score, --within
 };
 struct Refusal {
     Given given;
@@ -711,12 +763,14 @@ static const Refusal kRefusals[] = {
     {Given::MatchAny, {"--scale", "--candidates", "--score"}, "--match any cannot be combined with %s (any-of requests take --genre, --where, --seen and --only only)"},
     {Given::Manhattan, kRequestOptions, "--distance manhattan cannot be combined with %s (Manhattan requests take --genre, --where, --seen and --only only)"},
     {Given::Manhattan, {"--scale", "--candidates", "--score"}, "--distance manhattan cannot be combined with %s (Manhattan requests take --genre, --where, --seen and --only only)"},
+    {Given::Bounded, kRequestOptions, "a bound (--min-score, --within) cannot be combined with %s (bounded requests take --genre, --where, --seen and --only only)"},
+    {Given::Bounded, {"--scale", "--candidates", "--score"},"a bound (--min-score, --within) cannot be combined with %s (bounded requests take --genre, --where, --seen and --only only)"},
 };
 
 // true, with the message, when `given` holds and the command line has an option that one of its rows refuses beside it.
 static bool refused(int argc, char* argv[], int first, const Options& o, Given given) {
     const bool genreAlone = !o.playlist && !o.nearest() && !o.genres.empty();
-    if (!(given == Given::Euclidean ? o.euclidean : given == Given::Scale ? !o.scales.empty() : given == Given::MatchAny ? o.anyOf : given == Given::Manhattan ? o.manhattan : genreAlone))
+    if (!(given == Given::Euclidean ? o.euclidean : given == Given::Scale ? !o.scales.empty() : given == Given::MatchAny ? o.anyOf : given == Given::Manhattan ? o.manhattan : given == Given::Bounded ? o.bounded : genreAlone))
         return false;
     for (const Refusal& r : kRefusals) {
         if (r.given != given) continue;
@@ -753,6 +807,12 @@ static bool parseOptions(int argc, char* argv[], Options& o) {
     if (o.manhattan && (o.euclidean || o.anyOf)) {
         std::cerr << "Error: --distance manhattan cannot be combined with " << (o.euclidean ? "--metric euclidean" : "--match any")
                   << " (Manhattan requests take --genre, --where, --seen and --only only)" << std::endl;
+        return false;
+    }
+    if (!parseBound(argc, argv, first, o.euclidean, o.bounded, o.bound, o.countOnly) || refused(argc, argv, first, o, Given::Bounded)) return false;
+    if (o.bounded && (o.anyOf || o.manhattan)) {
+        std::cerr << "Error: a bound (--min-score, --within) cannot be combined with " << (o.anyOf ? "--match any" : "--distance manhattan")
+                  << " (bounded requests take --genre, --where, --seen and --only only)" << std::endl;
         return false;
     }
     if (!parseScale(argc, argv, first, o.scales) || refused(argc, argv, first, o, Given::Scale)) return false;
@@ -840,7 +900,8 @@ static void printQuerySong(const DataManager::Catalogue& catalogue, std::map<int
 // and whatever goes wrong from there ends in "No recommendations found"), --playlist, and the distance or scaled request of any.
 static bool queryMode(const Options& o) {
     const bool nearest = o.nearest(), song = !o.playlist && !nearest;
-    std::cout << (nearest ? (o.manhattan   ? "=== NEAREST MODE (Manhattan distance) ==="
+    std::cout << (nearest ? (o.bounded     ? (o.euclidean ? "=== BOUNDED MODE (within a Euclidean distance) ===" : "=== BOUNDED MODE (similarity at least a score) ===")
+                             : o.manhattan ? "=== NEAREST MODE (Manhattan distance) ==="
                              : o.euclidean ? "=== NEAREST MODE (Euclidean distance) ==="
                                            : "=== SCALED MODE (cosine over scaled features) ===")
                   : song  ? "=== RECOMMENDATION MODE ==="
@@ -934,10 +995,16 @@ static bool queryMode(const Options& o) {
         q.euclidean = o.euclidean;
         q.anyOf = o.anyOf;
         q.manhattan = o.manhattan;
+        if (o.bounded) {   // BOUNDED REQUESTS: the leading matches and the number of matching songs; --count-only asks for no song
+            if (o.euclidean) q.within(o.bound);
+            else q.atLeast(o.bound);
+            if (o.countOnly) q.topN = 0;
+        }
         if (o.score.on) listedValues = recommender.scoreSongs(q, listed, &eligible);
-        else if (q.topN > 0) recs = recommender.recommendQuery(q);
+        else if (q.topN > 0 || o.bounded) recs = recommender.recommendQuery(q);
     }
-    if (o.score.on ? listedValues.size() != listed.size() || listed.empty() : recs.empty()) return noRecommendations();
+    const long long matching = o.bounded ? recommender.lastMatchCount() : -1;   // (a bounded request may match nothing: that is an answer)
+    if (o.score.on ? listedValues.size() != listed.size() || listed.empty() : recs.empty() && matching < 0) return noRecommendations();
 
     // 7. the query's block, then the recommendations (a distance or scaled request prints their values)
     const std::vector<float> values = recommender.lastScores();
@@ -966,6 +1033,14 @@ static bool queryMode(const Options& o) {
         }
         std::cout << "\nScoring complete!" << std::endl;
         return true;
+    }
+    if (o.bounded) {
+        std::cout << "\n" << recs.size() << " of " << matching << " matching (" << (o.euclidean ? "distance <= " : "score >= ") << o.bound << ")"
+                  << std::endl;
+        if (recs.empty()) {
+            std::cout << "\nRecommendation complete!" << std::endl;
+            return true;
+        }
     }
     std::cout << "\nTop " << recs.size() << " Recommendations:\n" << std::endl;
     for (size_t i = 0; i < recs.size(); ++i) {

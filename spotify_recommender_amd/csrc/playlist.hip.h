@@ -154,6 +154,21 @@
 // Entries past n_cand store nothing.  No kernel argument is added (the kernel sits on its register budget): the mode rides on topk,
 // the buffer on block_lists.
 //
+// BOUNDED (include/mi355rec_diag.h, "BOUNDED REQUESTS").  The scan (no candidate list) launched with topk == 0 (uniform): the
+// COUNT MODE.  PlaylistBuf::shared_thr holds the request's FLOOR, a key threshold the host derived from its bound, and the launch
+// counts the rows whose key exceeds it: the workgroup's threshold starts at the floor (the anchor bound is skipped: it needs a
+// topk) and never moves, so the cut is the final one from the first tile.  A row the cut leaves takes the exact chains as in
+// every other launch; key > thr, then the exclusion lookup, decides whether it MATCHES.  A match is counted where the other
+// launches count a chain (n_exact) and is not appended: sm.count stays 0, nothing compacts, nothing is published (the two
+// barriers and the shared_thr read remain: the word holds the floor and changes nothing).  The host passes a per-call total word
+// as `rows_exact`; the tail stores topk = 0 keys per workgroup and no merge follows.  No kernel argument is added: the mode rides
+// on topk as the gather's score mode does (with a candidate list topk == 0 is still that).  Filter, label set, row set, the
+// special rows and the exact path (no replica, the cut off) are untouched, so the count is exact under all of them.
+//   * PROVEN IN (playlist_cut.hip.h, "BOUNDED"): with the plain cut and no filter, a valid row whose D reaches cut_hi is proven to
+//     match by the replica alone: it goes through the exclusion lookup and is counted, and its fp32 row is never read.  The rows
+//     between the two cuts take the chains.  PlaylistArg::n_cand != 0 without a list turns the shortcut off (only the experiments
+//     build's host ever passes that: the A/B of tools/run_bounded.py); the count is the same either way.
+//
 // EXCLUSION.  The excluded global ids (members and the caller's list, sorted and deduplicated on the host, at most
 // kPlExcludeCap) sit in LDS as uint32; only a key that already beats the workgroup's threshold is looked up (binary
 // search), so the hot loop does not change.
@@ -507,11 +522,16 @@ __device__ __forceinline__ void playlist_load_tile(const PlaylistCtx& c, bool re
 }
 
 // ---- the scan: this workgroup's tiles, candidates into sm.cand (thr: the starting threshold key, or 0)
-__device__ __forceinline__ void playlist_scan_tiles(const PlaylistCtx& c, const PlaylistSmem& sm, const Q8Query& hq, PlaylistCut& cut, uint64_t thr, int& n_exact) {
+__device__ __forceinline__ void playlist_scan_tiles(const PlaylistCtx& c, const PlaylistSmem& sm, const Q8Query& hq, PlaylistCut& cut, uint64_t thr, int& n_exact,
+                                                    bool no_proof) {
     constexpr int kBlock = PlaylistCfg::kBlock;
     const int tid = c.tid, lane = c.lane;
     const int64_t n = c.n, n_quads = (n + 3) >> 2, tiles = (n_quads + kBlock - 1) / kBlock;
     playlist_cut_refresh(cut, thr);
+    const bool counting = c.topk == 0;   // (uniform) BOUNDED above: n_exact counts the matches, nothing is appended, thr never moves
+    // PROVEN IN (playlist_cut.hip.h, "BOUNDED"): the floor's own score is the image (thr + 1) >> 32; uniform, fixed for the launch
+    const bool proving = counting && cut.kind == kPlCutPlain && !c.active && !no_proof;
+    const int cut_hi = proving ? playlist_cut_proven(cut, ordered_to_score(static_cast<uint32_t>((thr + 1ull) >> 32))) : kPlCutNever;
     int compact_at = 2 * c.topk > 256 ? 2 * c.topk : 256;
     if (compact_at > kCandLimit) compact_at = kCandLimit;
     PlaylistTile cur = {};   // (zeros where nothing streams)
@@ -541,6 +561,14 @@ __device__ __forceinline__ void playlist_scan_tiles(const PlaylistCtx& c, const 
             bool special[4];
             q8_dot4(hq, cur.q8, a, special);
             playlist_cut_apply(cut, mask, a, special, cur.side, cur.q8, sm.abar);
+            if (proving) {   // (uniform) a row proven in matches unless it is excluded: counted here, its fp32 row never read
+#pragma unroll
+                for (int u4 = 0; u4 < 4; ++u4)
+                    if ((mask & (1u << u4)) && !special[u4] && a[u4] >= cut_hi) {
+                        mask &= ~(1u << u4);
+                        n_exact += c.n_excl > 0 && playlist_excluded(sm.excl, c.n_excl, static_cast<uint32_t>(c.row_base + r0 + u4)) ? 0 : 1;
+                    }
+            }
         }
         if (c.active && mask != 0u) {   // (active uniform) the filter on the fp32 rows left, before any chain
             // the quad's four rows are requested together (one memory round trip, not four); rows past n read row n - 1
@@ -550,7 +578,7 @@ __device__ __forceinline__ void playlist_scan_tiles(const PlaylistCtx& c, const 
 #pragma unroll
             for (int u4 = 0; u4 < 4; ++u4)
                 if (mask & (1u << u4)) {
-                    ++n_exact;
+                    n_exact += counting ? 0 : 1;
                     if (!filter_pass(x[u4], c.active, c.buf->lo, c.buf->hi)) mask &= ~(1u << u4);
                 }
         }
@@ -558,10 +586,11 @@ __device__ __forceinline__ void playlist_scan_tiles(const PlaylistCtx& c, const 
             const bool have = mask != 0u;
             const int64_t r = have ? r0 + __builtin_ctz(mask) : 0;
             const uint64_t row_key = playlist_row_key(c, sm, load_row(c.feats, r), r);
-            n_exact += (have && !c.active) ? 1 : 0;   // (with a filter every row read was counted above)
+            n_exact += (have && !c.active && !counting) ? 1 : 0;   // (with a filter every row read was counted above)
             const uint64_t key = have ? row_key : 0ull;
             bool pass = key > thr;
             if (pass && c.n_excl > 0) pass = !playlist_excluded(sm.excl, c.n_excl, static_cast<uint32_t>(c.row_base + r));
+            if (counting) n_exact += pass ? 1 : 0, pass = false;   // a match: counted, never listed
             const uint64_t ballot = __ballot(pass);
             if (ballot) {
                 int base = 0;
@@ -701,8 +730,9 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
         playlist_gather_rows(c, sm, arg.cand, arg.n_cand, block_lists, n_exact);
     } else {
         uint64_t thr = 0ull;
-        if (cut.kind != kPlCutOff) thr = playlist_anchor_bound(c, sm, u, un, n_exact);   // uniform
-        playlist_scan_tiles(c, sm, hq, cut, thr, n_exact);
+        if (topk == 0) thr = buf->shared_thr;   // (uniform) BOUNDED above: the count launch starts, and stays, at the floor
+        else if (cut.kind != kPlCutOff) thr = playlist_anchor_bound(c, sm, u, un, n_exact);   // uniform
+        playlist_scan_tiles(c, sm, hq, cut, thr, n_exact, arg.n_cand != 0);   // (n_cand without a list: BOUNDED above, the A/B knob)
     }
 
     const int wave_exact = wave_inclusive_scan(n_exact);

@@ -87,6 +87,41 @@ __device__ __forceinline__ int playlist_cut_int(float c) {
 // chains.  Dislikes shrink |u|: the cutoff (T - margin_mean) / |u| falls and more rows take the chains.
 __device__ __forceinline__ int playlist_cut_plain(const PlaylistCut& c, float t) { return q8_threshold((t - c.margin_mean) / c.un); }
 
+// BOUNDED (playlist.hip.h, "BOUNDED": the count launch; the threshold is the request's floor and never moves).  PROVEN IN: the bound
+// of PLAIN is symmetric, so the replica can also prove that a row MATCHES, and such a row is counted without its fp32 row being read.
+//   * every step of PLAIN's chain of inequalities is two-sided: |approx - v . x^| <= M is an absolute bound, |c_k - u^_k . x^| <=
+//     kPlChainErr / 2 is one (the clamp to [-1, 1] moves c_k TOWARDS the real cosine from either side), and every rounding it counts
+//     (the score's, u's, |u|'s, the quotient's, the excess of sum a_k) is a few ulp of a quantity of size <= 1 in either direction.  So
+//     for a valid row, members whose norms lie in [kBqMinNorm, kBqMaxNorm] and the unweighted call (W = K), beside
+//         score(x) <= |u| approx + margin_mean            also            score(x) >= |u| approx - margin_mean,
+//     and a row with |u| approx >= T + margin_mean scores at least T, for T of either sign.  T is the floor's own score b (the
+//     float whose image is (floor_thr + 1) >> 32, exactly: the launch's threshold key is floor_thr = (image(b) << 32) - 1), so
+//     score(x) >= b, image(score) >= image(b), and key(x) > floor_thr WHATEVER the row's id: the row matches, if it is not excluded.
+//   * the integer test is D >= cut_hi, cut_hi = ceil( fl( c kQ8DotScale ) ) + 1, c = max( fl( fl(T + margin_mean) / |u| ), -2 ):
+//       - the rounding of the sum and of the quotient: 2 ulp of a quantity of size <= 1.02 in units of the score (times |u| again),
+//         inside the 4 ulp PLAIN counts for "the fp32 quotient of the cutoff" (margin_mean is the same constant, used on both sides);
+//       - the product c kQ8DotScale is off by < 0.25 (|c| <= 2: 2^-24 relative of at most 8.2e6, q8_threshold's own figure): the
+//         ceiling and the + 1 put the cut at or ABOVE the real-number product, as floor and - 1 put q8_threshold's below it.  The
+//         conversion of an integral float below 2^24 is exact;
+//       - THE CLAMP AT +-2 (q8_threshold clamps its quotient there because |approx| <= 1 + M < 2 decides every compare beyond it).
+//         Above: a quotient >= 2, or one that is not a number, claims NOTHING: cut_hi = INT_MAX, no row is proven in (none could be:
+//         D <= 127 S (1 + M) < 2 * 127 S), every row the lower cut leaves takes the chains.  That is the safe side.  Below: c = -2 is
+//         sound, not merely safe-looking: a quotient <= -2 says T + margin_mean <= -2 |u|, and every valid row has
+//         score >= -|u| (1 + M) - margin_mean > -2 |u| - margin_mean >= T (M < 1), so every valid row does match; and a clamped c
+//         is LARGER than the quotient, so the cut only moves up, towards "not proven".
+//   * claimed only where PLAIN is: the kind is plain (cosine metric; no prior, no scales), the row is valid (its first byte is not
+//     0x80) and still admissible (row set, label set: its mask bit), and the launch has NO feature filter (the filter needs the fp32
+//     row; such a launch proves nothing in).  A row that is neither ruled out (D < cut_d) nor proven in (D >= cut_hi) takes the K
+//     chains, so the count is exact whatever the two cuts decide: they only choose who pays 48 B.
+//   * tests/test_bounded_margin.py checks both directions with tests/bounded_cut_model.py (a numpy mirror built on
+//     tests/playlist_cut_model.py) against the oracle, and that the undecided band is not vacuous.
+constexpr int kPlCutNever = 0x7fffffff;   // INT_MAX, the cut_hi that proves no row in
+__device__ __forceinline__ int playlist_cut_proven(const PlaylistCut& c, float t) {
+    const float q = (t + c.margin_mean) / c.un;
+    if (!(q < 2.0f)) return kPlCutNever;   // (NaN too)
+    return static_cast<int>(__builtin_ceilf(__builtin_fmaxf(q, -2.0f) * kQ8DotScale)) + 1;
+}
+
 // PRIOR (playlist.hip.h, "ROW PRIORS": the ranking value is v(x) = fl(score(x) + fl(beta p(x))), |p| <= 1, |beta| <= 4).
 //   * pre-filter: with its quad's four priors in hand (playlist_load_tile streams them with the replica) a row is ruled out iff
 //         |u| approx < T - margin_prior - fl(beta p(x)),       margin_prior = margin_mean + kPlPriorUlps kPlUlp,

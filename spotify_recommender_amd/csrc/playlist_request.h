@@ -7,6 +7,8 @@
 // REQUESTS", "ANY-OF REQUESTS", "MANHATTAN REQUESTS": the same Request with another `metric`) by ONE body, from_metric_query, over a
 // MetricKind row each.  Every self-sized struct (the four requests and the ext) is read by read_sized; every kind applies the ext
 // through from_ext then apply_ext.  A further metric request is a MetricKind row, an outputs_of mapping and an overload.
+// The bounded request ("BOUNDED REQUESTS": mi355rec_bounded_query_t, the metric requests' 64 bytes and then `metric` and `bound`) has
+// its own overload and its own refusal texts: the same Request with `bounded`, `floor_thr` and `floor_score`, and Outputs::total.
 #pragma once
 
 #include <cmath>
@@ -61,6 +63,9 @@ struct Request {
                                                 // ... by the pass that reduces the list (the single handle's own entry points)
     bool score = false;                         // "CANDIDATE SCORES" (listed only): the value of EVERY listed row is wanted, in list
                                                 // ... order, and nothing is selected: topn is checked and otherwise unused
+    bool bounded = false;                       // "BOUNDED REQUESTS" (kCosine, kDistance): only rows whose key exceeds floor_thr MATCH;
+    uint64_t floor_thr = 0;                     // ... their exact number is wanted (Outputs::total) and topn may be 0 (count only);
+    float floor_score = 0.0f;                   // ... b, the score floor_thr was made from (bounded_floor): a key's score s matches iff s >= b
 
     int scan_topn() const { return diverse ? pool : topn; }   // what the scan selects
     // The same call diversified, and (of a diversified one) capped: what the _diverse and _capped entry points add.
@@ -116,6 +121,7 @@ struct Outputs {
     int* count = nullptr;
     int* pool_rows = nullptr;   // capped only: P'
     int32_t* member = nullptr;  // "ANY-OF REQUESTS" only: a(x) of every result
+    int64_t* total = nullptr;   // "BOUNDED REQUESTS" only: the number of matching rows
 };
 
 // idx / score / mmr [from, topn) padded with -1 / 0.0f / 0.0f, and *count set.
@@ -160,7 +166,11 @@ inline bool invalid_playlist(const Request& r, int64_t n_rows, int64_t exclude_e
         std::snprintf(msg, cap, "playlist of %d songs: 1 to %d are supported", r.k, MI355REC_MAX_PLAYLIST);
         return true;
     }
-    if (topn <= 0 || topn > MI355REC_MAX_TOPN_FAST) {
+    if (r.bounded && (topn < 0 || topn > MI355REC_MAX_TOPN_FAST)) {
+        std::snprintf(msg, cap, "topn %d out of [0, %d] (a bounded query has one round; 0 counts only)", topn, MI355REC_MAX_TOPN_FAST);
+        return true;
+    }
+    if (!r.bounded && (topn <= 0 || topn > MI355REC_MAX_TOPN_FAST)) {
         std::snprintf(msg, cap, "topn %d out of [1, %d] (a playlist query has one round)", topn, MI355REC_MAX_TOPN_FAST);
         return true;
     }
@@ -493,6 +503,110 @@ inline bool from_request(const mi355rec_anyof_query_t* q, const mi355rec_request
 inline bool from_request(const mi355rec_manhattan_query_t* q, const mi355rec_request_ext_t* ext, const mi355rec_manhattan_result_t* res,
                          mi355rec_manhattan_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
     return from_metric_query(kManhattanQuery, q, ext, res, full, r, out, msg, cap);
+}
+
+// "BOUNDED REQUESTS": the ordered image of a score as keys carry it (core.hip.h, score_to_ordered: -0.0 and +0.0 share one).
+inline uint32_t ordered_image(float s) {
+    s = s + 0.0f;
+    uint32_t u;
+    std::memcpy(&u, &s, sizeof u);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// ... the floor of a bounded request: a key matches iff key > floor_thr, that is iff its score's image is at least b's (the row
+// half of a key is never negative).  b is finite, so its image is neither 0 nor ~0.
+inline uint64_t bounded_floor(float b) { return (static_cast<uint64_t>(ordered_image(b)) << 32) - 1ull; }
+
+// ... does a result whose key carries the score s match the floor made from b?
+inline bool bounded_match(float s, float b) { return ordered_image(s) >= ordered_image(b); }
+
+// ... the Euclidean metric's b = -m_max for a checked radius (finite, >= 0): m_max is the largest float with sqrtf(m_max) <= radius,
+// found from fl(radius^2) by nextafterf steps (sqrtf is correctly rounded and monotone; the steps are a handful at most).
+inline float bounded_radius_floor(float radius) {
+    float m = radius * radius;
+    const float top = 3.4028234663852886e38f;   // FLT_MAX: m_max is finite (a row whose m is not finite never matches)
+    if (!(m <= top)) m = top;
+    while (m > 0.0f && std::sqrt(m) > radius) m = std::nextafter(m, 0.0f);
+    while (m < top && std::sqrt(std::nextafter(m, top)) <= radius) m = std::nextafter(m, top);
+    return 0.0f - m;
+}
+
+// ... the bounded request with its extras as the same Request (metric kCosine or kDistance, bounded, floor_thr) and Outputs: read_sized'
+// rule, flags must be 0, members by value or by row, the metric and the bound, then the ext.  The refusal texts are this struct's
+// own.  True when the structs cannot be used; then msg[0..cap) says why.
+inline bool from_request(const mi355rec_bounded_query_t* q, const mi355rec_request_ext_t* ext, const mi355rec_bounded_result_t* res,
+                         mi355rec_bounded_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
+    using Query = mi355rec_bounded_query_t;
+    if (!q || !res) {
+        std::snprintf(msg, cap, "null argument");
+        return true;
+    }
+    static const size_t ends[] = {offsetof(Query, flags),  offsetof(Query, members), offsetof(Query, rows), offsetof(Query, exclude_global),
+                                  offsetof(Query, filter), offsetof(Query, labels),  offsetof(Query, k),    offsetof(Query, n_exclude),
+                                  offsetof(Query, n_labels), offsetof(Query, topn),  offsetof(Query, metric), offsetof(Query, bound),
+                                  sizeof(Query)};
+    static_assert(sizeof(Query) == offsetof(Query, bound) + sizeof(float) && sizeof(Query) == 72 && offsetof(Query, metric) == 64,
+                  "the distance query's 64 bytes, then metric and bound; no tail padding");
+    if (read_sized(q, "bounded query", ends, full, msg, cap)) return true;
+    if (full->flags != 0u) {
+        std::snprintf(msg, cap, "flags 0x%x in a bounded query: must be 0 (weights, diversified and capped calls and priors are not served)",
+                      static_cast<unsigned>(full->flags));
+        return true;
+    }
+    if (full->members && full->rows) {
+        std::snprintf(msg, cap, "members by value and by row in one bounded query");
+        return true;
+    }
+    if (!full->members && !full->rows) {
+        std::snprintf(msg, cap, "a bounded query needs members by value or by row");
+        return true;
+    }
+    if (full->metric != MI355REC_BOUNDED_COSINE && full->metric != MI355REC_BOUNDED_EUCLIDEAN) {
+        std::snprintf(msg, cap, "metric %d in a bounded query: MI355REC_BOUNDED_COSINE (0) or MI355REC_BOUNDED_EUCLIDEAN (1)",
+                      static_cast<int>(full->metric));
+        return true;
+    }
+    const bool euclid = full->metric == MI355REC_BOUNDED_EUCLIDEAN;
+    if (!std::isfinite(full->bound)) {
+        std::snprintf(msg, cap, "bound %g in a bounded query: a %s is finite", static_cast<double>(full->bound), euclid ? "radius" : "floor");
+        return true;
+    }
+    if (euclid && full->bound < 0.0f) {
+        std::snprintf(msg, cap, "radius %g in a bounded query: a radius is >= 0", static_cast<double>(full->bound));
+        return true;
+    }
+    if (!res->out_total) {
+        std::snprintf(msg, cap, "null out_total in a bounded result");
+        return true;
+    }
+    if (full->topn > 0 && !res->out_idx) {
+        std::snprintf(msg, cap, "null out_idx in a bounded result with topn %d", static_cast<int>(full->topn));
+        return true;
+    }
+    *r = request(full->members, full->rows, nullptr, full->k, full->exclude_global, full->n_exclude, full->filter, full->topn);
+    r->labels = full->labels;
+    r->n_labels = full->n_labels;
+    r->metric = euclid ? kDistance : kCosine;
+    r->report_distance = euclid;
+    r->bounded = true;
+    r->floor_score = euclid ? bounded_radius_floor(full->bound) : full->bound;
+    r->floor_thr = bounded_floor(r->floor_score);
+    *out = {res->out_idx, res->out_score, nullptr, res->out_count, nullptr, nullptr, res->out_total};
+    mi355rec_request_ext_t x;
+    if (from_ext(ext, &x, msg, cap)) return true;
+    if (x.feature_scales) {
+        std::snprintf(msg, cap, "bounded requests take no feature scales");
+        return true;
+    }
+    return apply_ext(x, r, msg, cap);
+}
+
+// ... the host's cut of `n` results in key order at the floor: how many of the leading ones match (scores as the keys carry them:
+// -m for the Euclidean metric, before scores_to_distances).
+inline int bounded_cut(const Request& r, const int64_t* idx, const float* score, int n) {
+    int c = 0;
+    while (c < n && idx[c] >= 0 && bounded_match(score[c], r.floor_score)) ++c;
+    return c;
 }
 
 // "CANDIDATE LISTS": the list an entry point was handed beside its request, if it takes one (given; {} is "no list").

@@ -820,11 +820,52 @@ int anyof_over_shards(mi355rec_sharded_t* h, const Request& r, const Outputs& ou
     return MI355REC_OK;
 }
 
+// "BOUNDED REQUESTS" on a ROW-SHARDED catalogue (members by value, the workers drained): every shard answers with its own leading
+// matches (already cut at the floor: keys of the score, or of -m) and its own total; the keys are merged on the host, the totals summed.
+int bounded_over_shards(mi355rec_sharded_t* h, Request r, const Outputs& out) {
+    const int topn = r.topn;
+    const bool report_distance = r.report_distance;
+    r.report_distance = false;   // (the shards answer with what the keys carry; the distances are taken from the merged list)
+    std::vector<mi355rec_key_t> keys;
+    std::vector<int64_t> idx;
+    std::vector<float> sc;
+    try {
+        idx.resize(static_cast<size_t>(topn));
+        sc.resize(static_cast<size_t>(topn));
+        keys.reserve(static_cast<size_t>(topn) * h->shards.size());
+    } catch (const std::bad_alloc&) {
+        return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for %d results per shard", topn);
+    }
+    int64_t total = 0;
+    for (Shard& s : h->shards) {
+        if (s.hi <= s.lo) continue;
+        S_HIP(h, hipSetDevice(s.device));
+        int c = 0;
+        int64_t part = 0;
+        const int rc = mi355node::query_playlist(s.engine, r, {idx.data(), sc.data(), nullptr, &c, nullptr, nullptr, &part});
+        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", s.device, mi355rec_last_error(s.engine));
+        total += part;
+        for (int i = 0; i < c; ++i) keys.push_back(mi355rec_pack_key(sc[static_cast<size_t>(i)], idx[static_cast<size_t>(i)]));
+    }
+    const size_t count = keys.size() < static_cast<size_t>(topn) ? keys.size() : static_cast<size_t>(topn);
+    std::partial_sort(keys.begin(), keys.begin() + count, keys.end(), [](mi355rec_key_t a, mi355rec_key_t b) { return a > b; });
+    for (size_t i = 0; i < count; ++i) {
+        out.idx[i] = mi355rec_key_row(keys[i]);
+        if (out.score) out.score[i] = mi355rec_key_score(keys[i]);
+    }
+    *out.total = total;
+    if (topn > 0) mi355playlist::pad(out, static_cast<int>(count), topn, static_cast<int>(count));
+    else if (out.count) *out.count = 0;
+    if (report_distance && topn > 0) mi355playlist::scores_to_distances(out, topn, r.metric);
+    return MI355REC_OK;
+}
+
 // Every call of the family on the node handle: the checks (the catalogue's global rows are known here), the members of a
 // by-row call by value where no single handle can read them, then the CPU backend, the one handle that holds the whole
 // catalogue, or every shard and a host merge.
 int sharded_playlist(mi355rec_sharded_t* h, Request r, const Outputs& out) {
-    if (!h || !(r.members || r.rows) || !out.idx) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    if (!h || !(r.members || r.rows) || !(out.idx || (r.bounded && r.topn == 0)) || (r.bounded && !out.total))
+        return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     char why[128];
     if ((r.diverse && mi355playlist::invalid_diverse(r, why, sizeof why)) ||
         mi355playlist::invalid_playlist(r, h->n, h->n, MI355REC_MAX_EXCLUDE, why, sizeof why))
@@ -851,6 +892,7 @@ int sharded_playlist(mi355rec_sharded_t* h, Request r, const Outputs& out) {
     // every shard gets the whole exclusion list and matches the ids of its own rows ("DISTANCE REQUESTS": the shards answer
     // with -m, what the merge's keys compare; the distances are taken from the merged list)
     if (r.metric == mi355playlist::kAnyOf && out.member) return anyof_over_shards(h, r, out);
+    if (r.bounded) return bounded_over_shards(h, r, out);
     const bool report_distance = r.report_distance;
     r.report_distance = false;
     ShardLists lists;
@@ -1068,6 +1110,13 @@ int mi355rec_sharded_query_anyof_request(mi355rec_sharded_t* h, const mi355rec_a
 // request: the shards answer with -m, what the merge's keys compare, and m is taken from the merged list.
 int mi355rec_sharded_query_manhattan_request(mi355rec_sharded_t* h, const mi355rec_manhattan_query_t* query,
                                              const mi355rec_request_ext_t* ext, const mi355rec_manhattan_result_t* result) {
+    return node_request_entry(h, query, ext, result, {});
+}
+
+// BOUNDED REQUESTS (include/mi355rec_diag.h): the same Request with `bounded` through sharded_playlist; a row-sharded catalogue merges
+// the shards' matches and sums their totals (bounded_over_shards).
+int mi355rec_sharded_query_bounded_request(mi355rec_sharded_t* h, const mi355rec_bounded_query_t* query, const mi355rec_request_ext_t* ext,
+                                           const mi355rec_bounded_result_t* result) {
     return node_request_entry(h, query, ext, result, {});
 }
 

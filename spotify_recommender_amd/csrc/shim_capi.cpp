@@ -268,6 +268,34 @@ int64_t shim_query_manhattan(void* h, const int* songs, int n_songs, const int* 
     if (refuse & 256) c->rec.clearCandidates();
     return n;
 }
+// Recommender::recommendQuery of the bounded Query {songs, alsoExclude = exclude, where = the one range on where_feature (< 0: none),
+// topN}.atLeast(bound) or, with `euclidean`, .within(bound), and — `refuse`, a bit each, to show the refusals — with weights (1),
+// diverse (2), maxPerArtist (4), priorWeight (8), scales (16), through scoreSongs (64), anyOf (128), with a candidate list set (256)
+// or manhattan (512).  scores: lastScores().  *match_count: lastMatchCount().  Returns how many songs came back.
+int64_t shim_query_bounded(void* h, const int* songs, int n_songs, const int* exclude, int n_exclude, int where_feature, float lo, float hi,
+                           int topn, int euclidean, float bound, int refuse, int* out, float* scores, long long* match_count, int64_t cap) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    Recommender::Query q;
+    q.songs.assign(songs, songs + (n_songs > 0 ? n_songs : 0));
+    q.alsoExclude.assign(exclude, exclude + (n_exclude > 0 ? n_exclude : 0));
+    if (where_feature >= 0) q.where.push_back({where_feature, lo, hi});
+    q.topN = topn;
+    if (euclidean) q.within(bound);
+    else q.atLeast(bound);
+    if (refuse & 1) q.weights.assign(q.songs.size(), 1.0f);
+    if (refuse & 2) q.diverse = true, q.lambda = 0.5f;
+    if (refuse & 4) q.maxPerArtist = 1;
+    if (refuse & 8) q.priorWeight = 0.5f;
+    if (refuse & 16) q.scales.assign(12, 2.0f);
+    if (refuse & 128) q.anyOf = true;
+    if (refuse & 512) q.manhattan = true;
+    if (refuse & 64) return static_cast<int64_t>(c->rec.scoreSongs(q, std::vector<int64_t>{0}).size());
+    if (refuse & 256) c->rec.setCandidates(std::vector<int64_t>{0, 1, 2});
+    const int64_t n = giveBack(c, c->rec.recommendQuery(q), out, scores, cap);
+    if (refuse & 256) c->rec.clearCandidates();
+    if (match_count) *match_count = c->rec.lastMatchCount();
+    return n;
+}
 // Recommender::updateSongs (n_features floats for n_songs songs: a length that differs is refused by the class).
 int shim_update_songs(void* h, const int* songs, int n_songs, const float* features, int64_t n_features) {
     Catalogue* c = static_cast<Catalogue*>(h);

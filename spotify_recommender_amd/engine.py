@@ -115,7 +115,7 @@ def _call_request(lib, prefix: str, h, check, kind: str, q, res, scales=None, ro
     `scales` (checked: make_scales) ..._request_scaled, else ..._request.  "anyof" and "manhattan" have the one entry point
     `prefix`query_`kind`_request, which takes the ext (NULL without a row set) and no scales or list."""
     entry = f"{prefix}query_{kind}_request"
-    if kind in ("anyof", "manhattan"):
+    if kind in ("anyof", "manhattan", "bounded"):
         ext = _request_ext(None, rowset)
         check(getattr(lib, entry)(h, ctypes.byref(q), ctypes.byref(ext) if rowset is not None else None, ctypes.byref(res)))
     elif candidates is not None:
@@ -579,6 +579,36 @@ def query_manhattan(eng, topn, members=None, rows=None, exclude=None, where=None
     eng._with_set(seen, only, lambda rowset: _call_request(eng._lib, eng._prefix, eng._h, eng._check, "manhattan", q, res, rowset=rowset))
     c = count.value
     return idx[:c].copy(), dist[:c].copy()
+
+
+def query_bounded(eng, topn, bound, metric="cosine", members=None, rows=None, exclude=None, where=None, labels=None, seen=None, only=None):
+    """BOUNDED REQUESTS (include/mi355rec_diag.h): only the rows that are good enough, and how many there are.  metric="cosine":
+    the rows whose unweighted mean cosine to the members is >= `bound`; metric="euclidean": the rows whose distance (what
+    query_nearest reports) is <= the radius `bound`.  `eng`: a CosineEngine, a lane or a NodeEngine; `members` k x 12 by value or
+    `rows` of the engine (never returned, never counted), one of them; `exclude`, `where`, `labels`, `seen` / `only` as in
+    query_playlist_topn.  `topn` may be 0: count only.
+    Returns (ids int64[c], scores float32[c], total): the leading c = min(topn, total) matching rows, best first (for the Euclidean
+    metric `scores` holds distances, nearest first), and the exact number of matching rows.
+        ids, scores, total = query_bounded(eng, 100, 0.9, rows=playlist_rows, seen=history)
+    (The engines' own methods keep their parameter lists: tests/test_engine_surface.py records them.)"""
+    if (members is None) == (rows is None):
+        raise ValueError("query_bounded takes members= (by value) or rows= (by row), one of them")
+    if metric not in ("cosine", "euclidean"):
+        raise ValueError(f"metric {metric!r}: 'cosine' or 'euclidean'")
+    m = _np_members(members) if members is not None else _np_rows(rows)
+    n_out = max(int(topn), 1)
+    idx = np.empty(n_out, dtype=np.int64)
+    score = np.empty(n_out, dtype=np.float32)
+    count = ctypes.c_int(0)
+    total = ctypes.c_int64(0)
+    q = capi.BoundedQuery()
+    keep = _fill_query(q, m, topn, exclude, where, labels)   # noqa: F841  (alive until the call has returned)
+    q.metric = capi.BOUNDED_EUCLIDEAN if metric == "euclidean" else capi.BOUNDED_COSINE
+    q.bound = float(bound)
+    res = capi.BoundedResult(_ptr(idx), _ptr(score), ctypes.pointer(count), ctypes.pointer(total))
+    eng._with_set(seen, only, lambda rowset: _call_request(eng._lib, eng._prefix, eng._h, eng._check, "bounded", q, res, rowset=rowset))
+    c = count.value
+    return idx[:c].copy(), score[:c].copy(), int(total.value)
 
 
 def candidates_counters(eng) -> dict:
