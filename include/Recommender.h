@@ -217,6 +217,10 @@ public:
     // whose distance is <= r.  The results are the leading matches, at most topN of them (topN = 0 is allowed: count only), and
     // lastMatchCount() holds the exact number of matching songs.  With a bound, weights, diverse, maxPerArtist, priorWeight, scales,
     // anyOf and manhattan are refused with a message and {}, and so are a set candidate list and scoreSongs.  The row set applies.
+    // jaccard (include/mi355rec_diag.h, "JACCARD REQUESTS"): songs rank by their mean weighted (Ruzicka) Jaccard similarity to `songs`,
+    // sum_j min(q_j, x_j) / sum_j max(q_j, x_j), most similar first; lastScores() holds the similarities.  With jaccard, weights,
+    // diverse, maxPerArtist, priorWeight, scales, euclidean, manhattan, anyOf and a bound are refused with a message and {}, and so
+    // are a set candidate list (setCandidates) and scoreSongs.  The row set of setRowSet applies.
     struct Query {
         std::vector<int> songs;            // 1 to 32
         std::vector<float> weights;        // one per song, or none
@@ -237,6 +241,7 @@ public:
         float bound = 0.0f;
         Query& atLeast(float score) { bounded = true, euclidean = false, bound = score; return *this; }
         Query& within(float radius) { bounded = true, euclidean = true, bound = radius; return *this; }
+        bool jaccard = false;
     };
     std::vector<int> recommendQuery(const Query& query);
     // Per result of the last recommendQuery with anyOf: the catalogue index of the matched song of query.songs (the first of them

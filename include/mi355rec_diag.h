@@ -42,6 +42,8 @@
  *     feature filter, label set and row set (mi355rec_query_manhattan_request and its node-handle twin);
  *   - BOUNDED REQUESTS: only the rows at or above a score floor (or within a radius), and the exact number of such rows
  *     (mi355rec_query_bounded_request and its node-handle twin);
+ *   - JACCARD REQUESTS: the top-N rows by weighted (Ruzicka) Jaccard similarity to up to 32 members, with the playlist request's
+ *     exclusion list, feature filter, label set and row set (mi355rec_query_jaccard_request and its node-handle twin);
  *   - test hooks, compiled in only with -DMI355REC_TEST_HOOKS (spotify_recommender_amd/build.py builds
  *     libmi355rec_testhooks.so for tests/; the product library does not export them).
  */
@@ -1234,6 +1236,71 @@ int mi355rec_query_bounded_request(mi355rec_t* h, const mi355rec_bounded_query_t
                                    const mi355rec_bounded_result_t* result);
 int mi355rec_sharded_query_bounded_request(mi355rec_sharded_t* h, const mi355rec_bounded_query_t* query,
                                            const mi355rec_request_ext_t* ext, const mi355rec_bounded_result_t* result);
+
+/* JACCARD REQUESTS (the reference's README names "additional similarity metrics (Euclidean, Jaccard)" among its extensions): the
+ * top-N rows by WEIGHTED JACCARD (Ruzicka) similarity to up to 32 members.  Unlike cosine it sees how large the features are, not
+ * only their direction.  mi355rec_jaccard_query_t has the field list of mi355rec_distance_query_t and carries its own size under
+ * the same rules.
+ *   members / rows   exactly one is non-NULL: k x 12 floats by value, or k rows of the handle (never returned);
+ *                    1 <= k <= MI355REC_MAX_PLAYLIST;
+ *   exclude_global / n_exclude, filter, labels / n_labels   as in the playlist request;
+ *   topn             in [1, MI355REC_MAX_TOPN_FAST];       flags   must be 0.
+ * mi355rec_jaccard_result_t: out_idx (topn slots) is required; out_similarity (topn slots) and out_count may be NULL.
+ * RANKING VALUE, per member k and row x, bit for bit in fp32, in this order, never fused:
+ *     num = den = 0.0f
+ *     for j = 0..11:  lt = x_j < q_kj;  lo = lt ? x_j : q_kj;  hi = lt ? q_kj : x_j;
+ *                     num = fl(num + lo);  den = fl(den + hi)
+ *     J_k  = fl(num / den)                                                             (one IEEE divide)
+ *     v(x) = fl( fl(...fl(J_0 + J_1) + ... + J_{K-1}) / (float)K )                     (members in order; K = 1 divides by 1.0f)
+ * min and max are ONE compare and two selects, not fminf / fmaxf (which drop a NaN): a NaN in the row reaches den, a NaN in a
+ * member reaches num.  Rows rank by v descending, then row ascending (keys are pack_key(v, global row));
+ * out_similarity[i] = v.  A row forms a key only if v is finite and every den_k is below +inf (a +inf feature would otherwise
+ * score a quiet 0): two all-zero vectors (0 / 0), NaN and infinite features are never returned, and the count says so.  The
+ * formula is applied as written whatever the signs; it is the Ruzicka similarity, in [0, 1], where row and members are
+ * non-negative, which a min-max normalised catalogue always is.  A copy of the single member scores exactly 1.0f.
+ * Admissibility is the playlist request's (the row set of `ext`, the label set, the filter, not a member row, not excluded);
+ * count = min(topn, |admissible rows that form a key|), past it the padding is -1 / +0.0f.
+ * ext: may be NULL; its row set is honoured with the _ext calls' ownership checks; a non-NULL feature_scales is INVALID_ARG
+ * ("jaccard requests take no feature scales").  There are no _ext or _scaled variants: this one entry point takes ext.
+ * INVALID_ARG (with a message): flags != 0; both or neither of members and rows; a bad size; everything the playlist request
+ * refuses for the fields the two share (same limits, same messages).
+ * Device: no new kernel.  playlist_scan_kernel (csrc/playlist.hip.h, "JACCARD") takes a third value of PlaylistArg::metric, a
+ * uniform branch of playlist_row_key: the K chains above in place of the cosine chains.  The kernel stays at 128 VGPRs, 40 128 B
+ * of LDS and no scratch; the library holds 60 kernels.
+ * NO PRE-FILTER: every row takes the chains, on a handle with the 8-bit replica as on one without (the launch is given no
+ * replica).  An 8-bit bound is proven (docs/LAB_NOTES.md) but the forms tried reserve scratch in a kernel that sits on its
+ * register budget, which the build refuses.  mi355rec_playlist_counters counts these calls; rows_exact grows by every row read.
+ * Node handle: one shard forwards; a replicated placement asks one replica; a row-sharded one fetches members given by row,
+ * forwards them by value to every shard and merges keys of v on the host.  The CPU backend runs the same chain.
+ * Measured (MI355X, 10 M uniform rows, top-100, members by row; profiles/r27_jaccard.json, tools/run_jaccard.py), p50 per call in
+ * us, on a handle with the replica / on one without (the same launch):
+ *     K = 1: 189.2 / 188.2      K = 3: 206.4 / 205.0      K = 10: 268.2 / 264.1      K = 32: 572.9 / 574.2
+ * (the cosine, distance and Manhattan requests on the handle without a replica, every row exact: 187.9, 184.2, 193.1 at K = 1 and
+ * 432.1, 338.6, 275.6 at K = 32).
+ * Not served: weights, priors, feature scales, MMR and caps; bounds; candidate lists and candidate scores; asynchronous,
+ * streamed and batched variants; the torch.distributed ShardedEngine. */
+typedef struct {
+    uint32_t size;                    /* sizeof(mi355rec_jaccard_query_t) of the caller's header */
+    uint32_t flags;                   /* must be 0 */
+    const float* members;             /* k x 12 floats (host), or NULL with ... */
+    const int64_t* rows;              /* ... k rows of the handle */
+    const int64_t* exclude_global;    /* n_exclude global ids, or NULL */
+    const mi355rec_filter_t* filter;  /* NULL, or the feature filter */
+    const int32_t* labels;            /* NULL, or n_labels labels */
+    int32_t k;
+    int32_t n_exclude;
+    int32_t n_labels;
+    int32_t topn;
+} mi355rec_jaccard_query_t;           /* 64 bytes */
+typedef struct {
+    int64_t* out_idx;                 /* topn slots; required */
+    float* out_similarity;            /* topn slots, or NULL: v(x) */
+    int* out_count;                   /* or NULL */
+} mi355rec_jaccard_result_t;
+int mi355rec_query_jaccard_request(mi355rec_t* h, const mi355rec_jaccard_query_t* query, const mi355rec_request_ext_t* ext,
+                                   const mi355rec_jaccard_result_t* result);
+int mi355rec_sharded_query_jaccard_request(mi355rec_sharded_t* h, const mi355rec_jaccard_query_t* query,
+                                           const mi355rec_request_ext_t* ext, const mi355rec_jaccard_result_t* result);
 
 /* ROW UPDATES (the reference lists "Real-time Updates: Incremental index updates" among its extensions): songs are re-analysed
  * and corrected every day, and a changed row should not cost a rebuild of everything the handle keeps beside the rows.

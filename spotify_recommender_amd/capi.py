@@ -69,7 +69,7 @@ class PlaylistResult(ctypes.Structure):
                 ("out_pool_rows", POINTER(c_int))]
 
 
-# The three metric requests (distance, any-of, Manhattan) are one 64-byte layout under three names in the C-ABI: three classes here.
+# The four metric requests (distance, any-of, Manhattan, Jaccard) are one 64-byte layout under four names in the C-ABI: four classes here.
 _METRIC_QUERY_FIELDS = [("size", c_uint32), ("flags", c_uint32), ("members", c_void_p), ("rows", c_void_p), ("exclude_global", c_void_p),
                         ("filter", POINTER(Filter)), ("labels", c_void_p), ("k", c_int32), ("n_exclude", c_int32), ("n_labels", c_int32),
                         ("topn", c_int32)]
@@ -105,7 +105,17 @@ class ManhattanResult(ctypes.Structure):
     _fields_ = [("out_idx", c_void_p), ("out_distance", c_void_p), ("out_count", POINTER(c_int))]
 
 
-BOUNDED_COSINE, BOUNDED_EUCLIDEAN = 0, 1   # mi355rec_bounded_query_t::metric
+class JaccardQuery(ctypes.Structure):
+    """mi355rec_jaccard_query_t (include/mi355rec_diag.h, JACCARD REQUESTS); `size` is sizeof of this struct, flags 0."""
+    _fields_ = _METRIC_QUERY_FIELDS
+
+
+class JaccardResult(ctypes.Structure):
+    """mi355rec_jaccard_result_t: every pointer but out_idx may be NULL; out_similarity holds v(x)."""
+    _fields_ = [("out_idx", c_void_p), ("out_similarity", c_void_p), ("out_count", POINTER(c_int))]
+
+
+BOUNDED_COSINE, BOUNDED_EUCLIDEAN = 0, 1  # mi355rec_bounded_query_t::metric
 
 
 class BoundedQuery(ctypes.Structure):
@@ -357,6 +367,9 @@ SIGNATURES = {
     # BOUNDED REQUESTS: the rows at or above a score floor (within a radius) and their exact number; one entry point takes the ext
     "mi355rec_query_bounded_request": (c_int, [c_void_p, POINTER(BoundedQuery), POINTER(RequestExt), POINTER(BoundedResult)]),
     "mi355rec_sharded_query_bounded_request": (c_int, [c_void_p, POINTER(BoundedQuery), POINTER(RequestExt), POINTER(BoundedResult)]),
+    # JACCARD REQUESTS: top-N by weighted (Ruzicka) Jaccard similarity; one entry point takes the ext
+    "mi355rec_query_jaccard_request": (c_int, [c_void_p, POINTER(JaccardQuery), POINTER(RequestExt), POINTER(JaccardResult)]),
+    "mi355rec_sharded_query_jaccard_request": (c_int, [c_void_p, POINTER(JaccardQuery), POINTER(RequestExt), POINTER(JaccardResult)]),
     # ROW UPDATES: rows change in place, every route answers as a freshly created handle would
     "mi355rec_update_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "mi355rec_sharded_update_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

@@ -490,6 +490,22 @@ std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, 
         return {};
     }
     impl->lastMatched.clear();
+    if (q.jaccard) {   // "JACCARD REQUESTS": what the request has no field for, and what is not served with it (ahead of the others' checks)
+        if (!q.weights.empty() || rerank || withPrior || !q.scales.empty() || q.euclidean || q.manhattan || q.anyOf || q.bounded) {
+            std::cerr << "Error: a Jaccard query takes no weights, diversity, cap, prior weight, feature scales, Euclidean or Manhattan metric, "
+                         "any-of matching or bound"
+                      << std::endl;
+            return {};
+        }
+        if (impl->hasCandidates) {
+            std::cerr << "Error: a Jaccard query takes no candidate list (clearCandidates first)" << std::endl;
+            return {};
+        }
+        if (score) {
+            std::cerr << "Error: scoreSongs takes no Jaccard query" << std::endl;
+            return {};
+        }
+    }
     if (q.bounded) {   // "BOUNDED REQUESTS": what the request has no field for, and what is not served with it
         if (!q.weights.empty() || rerank || withPrior || !q.scales.empty() || q.anyOf || q.manhattan) {
             std::cerr << "Error: a bounded query takes no weights, diversity, cap, prior weight, feature scales, any-of matching or Manhattan distance"
@@ -582,6 +598,14 @@ std::vector<int> runQuery(Recommender::Impl* impl, const Recommender::Query& q, 
         res.out_count = &count;
         res.out_total = &matching;
         rc = mi355rec_sharded_query_bounded_request(impl->engine, &b, &ext, &res);
+    } else if (q.jaccard) {
+        mi355rec_jaccard_query_t j{};
+        shared(j);
+        mi355rec_jaccard_result_t res{};
+        res.out_idx = impl->idxBuf.data();
+        res.out_similarity = impl->scoreBuf.data();
+        res.out_count = &count;
+        rc = mi355rec_sharded_query_jaccard_request(impl->engine, &j, &ext, &res);
     } else if (q.manhattan) {
         mi355rec_manhattan_query_t m{};
         shared(m);

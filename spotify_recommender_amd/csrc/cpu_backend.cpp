@@ -459,6 +459,10 @@ static int mean_keys(Node* h, const mi355playlist::Request& r, std::vector<uint6
     // "MANHATTAN REQUESTS": m(x) = fl(fl(d1_0 + ... + d1_{k-1}) / k), d1_k the sequential fp32 sum of fabsf(t), t = fl(q_kj - x_j);
     // keys carry -m, a row whose m is not finite gets no key (it is not admissible).
     const bool l1 = r.metric == mi355playlist::kManhattan;
+    // "JACCARD REQUESTS": v(x) = fl(fl(J_0 + ... + J_{k-1}) / k), J_k = fl(num / den), num and den the sequential fp32 sums of the
+    // smaller and the larger of q_kj and x_j (chosen by the one compare x_j < q_kj); keys carry v, a row whose v is not finite or
+    // one of whose den is not below +inf gets no key (it is not admissible).
+    const bool jaccard = r.metric == mi355playlist::kJaccard;
     // "FEATURE SCALES": two steps, as on the device: members and rows scaled with one fp32 multiply per feature, then the chains
     // above on the scaled values.  The filter below tests the stored rows f.
     const float* const a = r.scales;
@@ -512,6 +516,25 @@ static int mean_keys(Node* h, const mi355playlist::Request& r, std::vector<uint6
             keys[static_cast<size_t>(i)] = std::isfinite(mean) ? pack(-mean, static_cast<uint32_t>(i)) : 0;
             continue;
         }
+        if (jaccard) {
+            float sum = 0.0f;
+            bool bounded = true;
+            for (int m = 0; m < k; ++m) {
+                float num = 0.0f, den = 0.0f;
+                for (int j = 0; j < kDim; ++j) {
+                    const float q = members[m * kDim + j];
+                    const bool lt = x[j] < q;   // (one compare, two selects: a NaN goes where the contract says)
+                    num = num + (lt ? x[j] : q);
+                    den = den + (lt ? q : x[j]);
+                }
+                bounded = bounded && den < HUGE_VALF;   // (false for NaN)
+                const float jk = num / den;
+                sum = m == 0 ? jk : sum + jk;
+            }
+            const float v = sum / static_cast<float>(k);
+            keys[static_cast<size_t>(i)] = bounded && std::isfinite(v) ? pack(v, static_cast<uint32_t>(i)) : 0;
+            continue;
+        }
         if (anyof) {   // "ANY-OF REQUESTS": v = the best of the members' scores, in member order (the compare chain of anyof_best)
             int a;
             keys[static_cast<size_t>(i)] = pack(anyof_best(members, qn.data(), k, x, &a), static_cast<uint32_t>(i));
@@ -532,7 +555,7 @@ static int mean_keys(Node* h, const mi355playlist::Request& r, std::vector<uint6
     for (int64_t e : excl)
         if (e >= 0 && e < n) keys[static_cast<size_t>(e)] = 0;   // (a real key is never 0: its low half is ~row)
     int64_t avail = n - static_cast<int64_t>(std::count_if(excl.begin(), excl.end(), [n](int64_t e) { return e >= 0 && e < n; }));
-    if (dist || l1) avail = static_cast<int64_t>(std::count_if(keys.begin(), keys.end(), [](uint64_t key) { return key != 0; }));
+    if (dist || l1 || jaccard) avail =static_cast<int64_t>(std::count_if(keys.begin(), keys.end(), [](uint64_t key) { return key != 0; }));
     if (filter && filter->active) {   // the rows failing the filter go like excluded ones
         avail = 0;
         for (int64_t i = 0; i < n; ++i) {

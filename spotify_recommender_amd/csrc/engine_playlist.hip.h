@@ -285,7 +285,8 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     arg.labelled = L ? 1 : 0;
     arg.prior = pri ? 1 : 0;
     arg.prior_weight = pri ? r.prior_weight : 0.0f;
-    arg.metric = r.metric == mi355playlist::kDistance ? kPlDistance : kPlCosine;
+    const bool jaccard = r.metric == mi355playlist::kJaccard;
+    arg.metric = r.metric == mi355playlist::kDistance ? kPlDistance : jaccard ? kPlJaccard : kPlCosine;
     arg.rowset = set_bits;
     arg.rowset_flip = set_bits && !r.rowset_only ? 0xfu : 0u;   // EXCLUDE: a set bit clears the row; ONLY: a clear bit does
     arg.cand = r.listed ? P->d_cand : nullptr;   // (eff > 0: the list has an entry)
@@ -308,6 +309,8 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     int l1_cut_max_k = kL1CutMaxK;
     MI355REC_EXP_INT(l1_cut_max_k, "MI355REC_EXP_L1_CUT_MAX_K", 0, MI355REC_MAX_PLAYLIST);   // (experiments build only: tools/run_manhattan.py)
     if (manhattan && k > l1_cut_max_k) q8 = nullptr;
+    // "JACCARD REQUESTS": no pre-filter: every row takes the chains, whatever the handle holds (playlist.hip.h, JACCARD)
+    if (jaccard) q8 = nullptr;
     const int64_t n_quads4 = (h->n + 3) / 4 * 4;
     // (a scaled distance request takes the exact path: the norms are those of the unscaled rows, it is launched with null norms)
     const bool scan_norms = q8 && ((arg.metric == kPlDistance && !arg.scaled) || manhattan);
@@ -667,6 +670,13 @@ int mi355rec_query_anyof_request(mi355rec_t* h, const mi355rec_anyof_query_t* qu
 // "MANHATTAN REQUESTS": the same Request with metric = kManhattan through the same path; its scan is manhattan_scan_kernel.
 int mi355rec_query_manhattan_request(mi355rec_t* h, const mi355rec_manhattan_query_t* query, const mi355rec_request_ext_t* ext,
                                      const mi355rec_manhattan_result_t* result) {
+    return request_entry(h, query, ext, result, {});
+}
+
+// "JACCARD REQUESTS": the same Request with metric = kJaccard through the same path; its scan is playlist_scan_kernel's kPlJaccard
+// branch, with no replica (no pre-filter: every row takes the chains).
+int mi355rec_query_jaccard_request(mi355rec_t* h, const mi355rec_jaccard_query_t* query, const mi355rec_request_ext_t* ext,
+                                   const mi355rec_jaccard_result_t* result) {
     return request_entry(h, query, ext, result, {});
 }
 

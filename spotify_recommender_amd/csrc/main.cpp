@@ -27,6 +27,9 @@
 //   ... --song, --id and --playlist with --min-score S: only the songs whose similarity is at least S, and "N of TOTAL matching":
 //       how many songs of the catalogue pass, whatever -n is; with --metric euclidean it is --within R: the songs within distance R
 //       (extension: BOUNDED REQUESTS; with --genre, --where, --seen and --only and nothing else; --count-only prints the number alone)
+//   ... --song, --id and --playlist with --similarity jaccard: the MOST SIMILAR songs by weighted (Ruzicka) Jaccard similarity over the
+//       12 features, sum min / sum max, for a playlist the mean of the similarities to its songs (extension; with --genre, --where,
+//       --seen and --only and nothing else; similarities are printed; --metric and --distance keep their names)
 //   ... --song, --id and --playlist with one or more --scale NAME=S: feature NAME counts S times (0: ignored) in the similarity or
 //       the distance (extension; under both metrics, with --genre and --where)
 //   ... the same modes with --candidates FILE (track ids, one per line, as for --only): only the listed songs are READ and ranked (a
@@ -635,6 +638,26 @@ static bool parseDistance(int argc, char* argv[], int first, bool& manhattan) {
     return true;
 }
 
+// --similarity NAME from argv[first]: jaccard = true for "jaccard" (JACCARD REQUESTS: the most similar songs by weighted Jaccard
+// similarity), false without the option.  false (the return value), with a message, for another name.
+static bool parseSimilarity(int argc, char* argv[], int first, bool& jaccard) {
+    jaccard = false;
+    for (int i = first; i < argc; ++i) {
+        if (std::strcmp(argv[i], "--similarity") != 0) continue;
+        if (i + 1 >= argc) {
+            std::cerr << "Error: --similarity needs a name (jaccard)" << std::endl;
+            return false;
+        }
+        const std::string name = argv[++i];
+        if (name != "jaccard") {
+            std::cerr << "Error: --similarity '" << name << "': jaccard" << std::endl;
+            return false;
+        }
+        jaccard = true;
+    }
+    return true;
+}
+
 // --min-score S, --within R and --count-only from argv[first] (BOUNDED REQUESTS): bounded = true with `bound` = S or R.  false (the
 // return value), with a message, for a value that is no finite number, both options, --within without --metric euclidean,
 // --min-score with it, or --count-only without either.
@@ -721,6 +744,7 @@ struct Options {
     bool euclidean = false;
     bool anyOf = false;        // --match any
     bool manhattan = false;    // --distance manhattan
+    bool jaccard = false;      // --similarity jaccard
     bool bounded = false;      // --min-score S, or --within R under --metric euclidean: `bound`
     float bound = 0.0f;
     bool countOnly = false;    // --count-only
@@ -729,7 +753,7 @@ struct Options {
     DiverseOpt dv;
     PriorOpt pr;
     // a distance or scaled request (its own banner; scores or distances are printed; --song / --id run as the one-song playlist)
-    bool nearest() const { return euclidean || manhattan || bounded || !scales.empty(); }
+    bool nearest() const { return euclidean || manhattan || jaccard || bounded || !scales.empty(); }
 };
 
 // What does not combine: the option `given` stands for beside one of `beside` (the first of them in argv stands for %s in `text`).
@@ -744,6 +768,7 @@ enum class Given {
     MatchAny,        // --match any
     Manhattan,       // --distance manhattan
     Bounded,         // --min-score, --within
+    Jaccard,         // --similarity jaccard
 };
 struct Refusal {
     Given given;
@@ -765,12 +790,14 @@ static const Refusal kRefusals[] = {
     {Given::Manhattan, {"--scale", "--candidates", "--score"}, "--distance manhattan cannot be combined with %s (Manhattan requests take --genre, --where, --seen and --only only)"},
     {Given::Bounded, kRequestOptions, "a bound (--min-score, --within) cannot be combined with %s (bounded requests take --genre, --where, --seen and --only only)"},
     {Given::Bounded, {"--scale", "--candidates", "--score"},"a bound (--min-score, --within) cannot be combined with %s (bounded requests take --genre, --where, --seen and --only only)"},
+    {Given::Jaccard, kRequestOptions, "--similarity jaccard cannot be combined with %s (Jaccard requests take --genre, --where, --seen and --only only)"},
+    {Given::Jaccard, {"--scale", "--candidates", "--score", "--metric", "--distance", "--match", "--min-score", "--within", "--count-only"}, "--similarity jaccard cannot be combined with %s (Jaccard requests take --genre, --where, --seen and --only only)"},
 };
 
 // true, with the message, when `given` holds and the command line has an option that one of its rows refuses beside it.
 static bool refused(int argc, char* argv[], int first, const Options& o, Given given) {
     const bool genreAlone = !o.playlist && !o.nearest() && !o.genres.empty();
-    if (!(given == Given::Euclidean ? o.euclidean : given == Given::Scale ? !o.scales.empty() : given == Given::MatchAny ? o.anyOf : given == Given::Manhattan ? o.manhattan : given == Given::Bounded ? o.bounded : genreAlone))
+    if (!(given == Given::Euclidean ? o.euclidean : given == Given::Scale ? !o.scales.empty() : given == Given::MatchAny ? o.anyOf : given == Given::Manhattan ? o.manhattan : given == Given::Bounded ? o.bounded : given == Given::Jaccard ? o.jaccard : genreAlone))
         return false;
     for (const Refusal& r : kRefusals) {
         if (r.given != given) continue;
@@ -796,6 +823,7 @@ static bool parseOptions(int argc, char* argv[], Options& o) {
     if (!o.playlist && !parseGenres(argc, argv, first, o.genres)) return false;
     if (!parseWhere(argc, argv, first, o.ranges) || !parseRowSet(argc, argv, first, o.rowSet)) return false;
     if (!parseCandidates(argc, argv, first, o.candidates) || !parseScore(argc, argv, first, o.score)) return false;
+    if (!parseSimilarity(argc, argv, first, o.jaccard) || refused(argc, argv, first, o, Given::Jaccard)) return false;
     if (!parseMetric(argc, argv, first, o.euclidean) || refused(argc, argv, first, o, Given::Euclidean)) return false;
     if (!parseMatch(argc, argv, first, o.playlist, o.anyOf) || refused(argc, argv, first, o, Given::MatchAny)) return false;
     if (o.anyOf && o.euclidean) {
@@ -901,6 +929,7 @@ static void printQuerySong(const DataManager::Catalogue& catalogue, std::map<int
 static bool queryMode(const Options& o) {
     const bool nearest = o.nearest(), song = !o.playlist && !nearest;
     std::cout << (nearest ? (o.bounded     ? (o.euclidean ? "=== BOUNDED MODE (within a Euclidean distance) ===" : "=== BOUNDED MODE (similarity at least a score) ===")
+                             : o.jaccard   ? "=== RECOMMENDATION MODE (Jaccard similarity) ==="
                              : o.manhattan ? "=== NEAREST MODE (Manhattan distance) ==="
                              : o.euclidean ? "=== NEAREST MODE (Euclidean distance) ==="
                                            : "=== SCALED MODE (cosine over scaled features) ===")
@@ -995,6 +1024,7 @@ static bool queryMode(const Options& o) {
         q.euclidean = o.euclidean;
         q.anyOf = o.anyOf;
         q.manhattan = o.manhattan;
+        q.jaccard = o.jaccard;
         if (o.bounded) {   // BOUNDED REQUESTS: the leading matches and the number of matching songs; --count-only asks for no song
             if (o.euclidean) q.within(o.bound);
             else q.atLeast(o.bound);
@@ -1045,7 +1075,7 @@ static bool queryMode(const Options& o) {
     std::cout << "\nTop " << recs.size() << " Recommendations:\n" << std::endl;
     for (size_t i = 0; i < recs.size(); ++i) {
         std::ostringstream value;
-        if (nearest) value << "  (" << (o.euclidean || o.manhattan ? "distance " : "score ") << values[i] << ")";
+        if (nearest) value << "  (" << (o.jaccard ? "similarity " : o.euclidean || o.manhattan ? "distance " : "score ") << values[i] << ")";
         if (o.anyOf && i < matched.size()) value << "  (matches \"" << catalogue.trackNames[static_cast<size_t>(matched[i])] << "\")";
         if (!printEntry(catalogue, genreMap, recs[i], i + 1, "", value.str())) return false;
         if (i + 1 < recs.size()) std::cout << std::endl;

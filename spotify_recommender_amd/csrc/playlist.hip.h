@@ -169,6 +169,25 @@
 //     between the two cuts take the chains.  PlaylistArg::n_cand != 0 without a list turns the shortcut off (only the experiments
 //     build's host ever passes that: the A/B of tools/run_bounded.py); the count is the same either way.
 //
+// JACCARD (include/mi355rec_diag.h, "JACCARD REQUESTS").  PlaylistArg::metric == kPlJaccard (uniform): the ranking value of a row is
+// the MEAN WEIGHTED JACCARD (Ruzicka) SIMILARITY to the members, larger is better.  Everything fp32, in this order, never fused:
+//     num = den = 0.0f
+//     for j = 0..11:  lt = x_j < q_kj;  lo = lt ? x_j : q_kj;  hi = lt ? q_kj : x_j;  num = fl(num + lo);  den = fl(den + hi)
+//     J_k  = fl(num / den)                                                           (one IEEE divide)
+//     v(x) = fl( fl(...fl(J_0 + J_1) + ... + J_{K-1}) / (float)K )                   (member order; K = 1 divides by 1.0f: exact)
+// min and max are ONE compare and two selects, not fminf / fmaxf (which drop a NaN): a NaN in the row reaches den (x_j < q_kj is
+// false, hi = x_j) and a NaN in a member reaches num (lo = q_kj).  Keys are pack_key(v, global row): v descending, then row
+// ascending, as the cosine request's.  A row forms a key only if v is finite AND every den_k is below +inf (a +inf feature would
+// otherwise score a quiet 0: finite / inf): two all-zero vectors (0 / 0), NaN and infinite features are never returned.  The formula
+// is applied as written whatever the signs; it is the Ruzicka similarity, in [0, 1], where row and members are non-negative.
+//   * the K chains (playlist_jaccard) replace playlist_mean where a key is formed (playlist_row_key: the scan, the gather and the
+//     anchor rows read from the matrix all carry the same bits); exclusion lookup, filter, label test and row set are as above;
+//   * the weights (the prologue still copies the host's 1.0f each), W, u and the members' norms never enter a key; the priors are
+//     never read and `norms` is never passed;
+//   * NO PRE-FILTER: the host launches with a null replica, so the cut is off, the threshold starts at 0 and every admissible row
+//     takes the chains (docs/LAB_NOTES.md has the forms of an 8-bit bound that were tried and their register figures).
+// metric == kPlCosine takes none of these branches (uniform tests).
+//
 // EXCLUSION.  The excluded global ids (members and the caller's list, sorted and deduplicated on the host, at most
 // kPlExcludeCap) sit in LDS as uint32; only a key that already beats the workgroup's threshold is looked up (binary
 // search), so the hot loop does not change.
@@ -190,7 +209,7 @@ constexpr int kMaxPlaylist = 32;                            // MI355REC_MAX_PLAY
 constexpr int kMaxExclude = 1024;                           // MI355REC_MAX_EXCLUDE
 constexpr int kPlExcludeCap = kMaxExclude + kMaxPlaylist;   // the caller's ids and the members' rows
 constexpr int kPlBoundRows = 256;                           // anchor rows a workgroup scores for its starting threshold
-constexpr int kPlCosine = 0, kPlDistance = 1;               // PlaylistArg::metric (mi355playlist::Metric)
+constexpr int kPlCosine = 0, kPlDistance = 1, kPlJaccard = 2;   // PlaylistArg::metric
 using PlaylistCfg = Q8Cfg<512, 4, 1>;                       // kBlock, kMinWaves (two workgroups per CU); tiles of 2048 rows
 
 // One call's inputs on the device (written by the host before the launch).
@@ -215,7 +234,8 @@ struct PlaylistArg {
     int labelled;     // 1: only rows whose label is in PlaylistBuf::label_mask are admissible; 0: no label set
     float prior_weight;   // beta (read only where `prior`): v = fl(score + fl(beta p(x)))
     int prior;        // 1: rank by v, p from the kernel's `priors`; 0: rank by the score alone (`priors` is never read)
-    int metric;       // kPlCosine, or kPlDistance: rank by -m(x), the mean squared distance to the members (DISTANCE above)
+    int metric;       // kPlCosine, or kPlDistance: rank by -m(x), the mean squared distance to the members (DISTANCE above), or
+                      // kPlJaccard: rank by v(x), the mean weighted Jaccard similarity to the members (JACCARD above)
     int scaled;       // 1: rows and members are multiplied by PlaylistBuf::scales before the chains (FEATURE SCALES above); 0: never read
     const uint8_t* rowset;   // ROW SETS above: the shard's bitmap, bit i of byte i / 8 is local row i (padding bits 0); null: no set
     uint32_t rowset_flip;    // ... 0xf: rows IN the set are not admissible (EXCLUDE); 0: rows NOT in it are not (ONLY)
@@ -297,6 +317,29 @@ __device__ __forceinline__ float playlist_sqdist(const float (*__restrict__ mem)
     return sum / static_cast<float>(k);
 }
 
+// JACCARD: v(x), the contract's mean weighted Jaccard similarity of one row to the members (LDS) in order; *bounded: every den_k < +inf.
+__device__ __forceinline__ float playlist_jaccard(const float (*__restrict__ mem)[kDim], int k, const Row& r, bool* bounded) {
+    float f[kDim];
+    row_features(r, f);
+    float sum = 0.0f;
+    bool ok = true;
+    for (int m = 0; m < k; ++m) {
+        float num = 0.0f, den = 0.0f;
+#pragma unroll
+        for (int j = 0; j < kDim; ++j) {
+            const float q = mem[m][j];
+            const bool lt = f[j] < q;   // (one compare, two selects: a NaN goes where the contract says)
+            num = num + (lt ? f[j] : q);
+            den = den + (lt ? q : f[j]);
+        }
+        ok = ok && den < __builtin_inff();   // (false for NaN)
+        const float jk = num / den;
+        sum = m == 0 ? jk : sum + jk;
+    }
+    *bounded = ok;
+    return sum / static_cast<float>(k);
+}
+
 // ROW SETS: does the set admit local row `row`?  (bits: non-null)
 __device__ __forceinline__ bool rowset_admits(const uint8_t* __restrict__ bits, uint32_t flip, int64_t row) {
     return (((static_cast<uint32_t>(bits[row >> 3]) >> (row & 7)) ^ flip) & 1u) != 0u;
@@ -334,7 +377,7 @@ struct PlaylistCtx {
     int k, n_excl, topk;
     uint32_t active;
     float wsum, beta;
-    bool by_row, labelled, prior, dist, scaled;
+    bool by_row, labelled, prior, dist, scaled, jaccard;
     const int16_t* row_label;   // the rows' labels one by one, and four to a quad
     const uint2* labels4;
     const float* row_prior;     // the rows' priors one by one
@@ -356,6 +399,9 @@ __device__ __forceinline__ uint64_t playlist_row_key(const PlaylistCtx& c, const
         const float d = playlist_sqdist(sm.mem, c.k, x);
         finite = d < __builtin_inff();   // (false for NaN)
         m = -d;
+    } else if (c.jaccard) {   // (uniform) JACCARD: the key carries v; not finite, or a den_k that is not below +inf, forms no key
+        m = playlist_jaccard(sm.mem, c.k, x, &finite);
+        finite = finite && __builtin_fabsf(m) < __builtin_inff();   // (false for NaN)
     } else {
         m = playlist_mean(sm.mem, sm.qn, sm.w, c.wsum, c.k, x);
     }
@@ -718,7 +764,8 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     const bool dist = arg.metric == kPlDistance;
     const int tid = threadIdx.x;
     const PlaylistCtx c = {feats, anchors, n, row_base, buf, shared_thr, arg.k, arg.n_excl, topk, arg.active, arg.wsum, arg.prior_weight,
-                           arg.by_row != 0, arg.labelled != 0, arg.prior != 0, dist, arg.scaled != 0, reinterpret_cast<const int16_t*>(labels), labels,
+                           arg.by_row != 0, arg.labelled != 0, arg.prior != 0, dist, arg.scaled != 0, arg.metric == kPlJaccard,
+                           reinterpret_cast<const int16_t*>(labels), labels,
                            reinterpret_cast<const float*>(priors), dist ? norms : priors, q8, arg.rowset, arg.rowset_flip, tid, tid & 63};
     float u[kDim], un;
     PlaylistCut cut;

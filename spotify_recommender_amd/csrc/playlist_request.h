@@ -3,8 +3,8 @@
 // handle (engine_playlist.hip.h), the node handle (sharded.hip) and the CPU backend.  Every exported entry point of the
 // family fills a Request and an Outputs and takes the one path of its handle type.  Neither struct is part of the C-ABI; the
 // C-ABI's own request structs are converted to them by from_request below, one overload per struct: the playlist request
-// ("PLAYLIST REQUESTS": mi355rec_playlist_query_t, with its flags) by its own body, the three 64-byte metric requests ("DISTANCE
-// REQUESTS", "ANY-OF REQUESTS", "MANHATTAN REQUESTS": the same Request with another `metric`) by ONE body, from_metric_query, over a
+// ("PLAYLIST REQUESTS": mi355rec_playlist_query_t, with its flags) by its own body, the four 64-byte metric requests ("DISTANCE
+// REQUESTS", "ANY-OF REQUESTS", "MANHATTAN REQUESTS", "JACCARD REQUESTS": the same Request with another `metric`) by ONE body, from_metric_query, over a
 // MetricKind row each.  Every self-sized struct (the four requests and the ext) is read by read_sized; every kind applies the ext
 // through from_ext then apply_ext.  A further metric request is a MetricKind row, an outputs_of mapping and an overload.
 // The bounded request ("BOUNDED REQUESTS": mi355rec_bounded_query_t, the metric requests' 64 bytes and then `metric` and `bound`) has
@@ -23,7 +23,7 @@
 
 namespace mi355playlist {
 
-enum Metric { kCosine = 0, kDistance = 1, kAnyOf = 2, kManhattan = 3 };
+enum Metric { kCosine = 0, kDistance = 1, kAnyOf = 2, kManhattan = 3, kJaccard = 4 };
 
 struct Request {
     const float* members = nullptr;             // k x 12 floats by value, or null with ...
@@ -48,6 +48,8 @@ struct Request {
                                                 // kAnyOf ("ANY-OF REQUESTS"): rank by v(x), the best of the members' cosines
                                                 // kManhattan ("MANHATTAN REQUESTS"): rank by m(x), the mean L1 distance to the members,
                                                 // ... ascending; keys and scores carry -m
+                                                // kJaccard ("JACCARD REQUESTS"): rank by v(x), the mean weighted Jaccard similarity to
+                                                // ... the members, descending; keys and scores carry v
     bool attribute = false;                     // (kAnyOf) the member index a(x) of every result is wanted (Outputs::member)
     bool report_distance = false;               // (kDistance, kManhattan) the score output holds sqrtf(m) (kManhattan: m, no root);
                                                 // ... false: -m itself, what a node
@@ -427,8 +429,8 @@ inline mi355rec_request_ext_t scales_only_ext(const float* scales) {
     return x;
 }
 
-// The three 64-byte metric requests of the C-ABI (include/mi355rec_diag.h: "DISTANCE REQUESTS", "ANY-OF REQUESTS", "MANHATTAN
-// REQUESTS") are one layout under three names; what tells them apart is a row of this table ...
+// The four 64-byte metric requests of the C-ABI (include/mi355rec_diag.h: "DISTANCE REQUESTS", "ANY-OF REQUESTS", "MANHATTAN
+// REQUESTS", "JACCARD REQUESTS") are one layout under four names; what tells them apart is a row of this table ...
 struct MetricKind {
     const char* noun;        // the struct as the messages name it, with its article
     int metric;
@@ -438,10 +440,12 @@ struct MetricKind {
 constexpr MetricKind kDistanceQuery = {"a distance query", kDistance, true, nullptr};
 constexpr MetricKind kAnyOfQuery = {"an any-of query", kAnyOf, false, "any-of requests take no feature scales"};
 constexpr MetricKind kManhattanQuery = {"a manhattan query", kManhattan, true, "manhattan requests take no feature scales"};
+constexpr MetricKind kJaccardQuery = {"a jaccard query", kJaccard, false, "jaccard requests take no feature scales"};
 
 // ... and where its result struct's pointers go (any-of's carries out_member: the attribution is wanted when it is given).
 inline Outputs outputs_of(const mi355rec_distance_result_t& res) { return {res.out_idx, res.out_distance, nullptr, res.out_count, nullptr}; }
 inline Outputs outputs_of(const mi355rec_manhattan_result_t& res) { return {res.out_idx, res.out_distance, nullptr, res.out_count, nullptr}; }
+inline Outputs outputs_of(const mi355rec_jaccard_result_t& res) { return {res.out_idx, res.out_similarity, nullptr, res.out_count, nullptr}; }
 inline Outputs outputs_of(const mi355rec_anyof_result_t& res) {
     return {res.out_idx, res.out_score, nullptr, res.out_count, nullptr, res.out_member};
 }
@@ -503,6 +507,10 @@ inline bool from_request(const mi355rec_anyof_query_t* q, const mi355rec_request
 inline bool from_request(const mi355rec_manhattan_query_t* q, const mi355rec_request_ext_t* ext, const mi355rec_manhattan_result_t* res,
                          mi355rec_manhattan_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
     return from_metric_query(kManhattanQuery, q, ext, res, full, r, out, msg, cap);
+}
+inline bool from_request(const mi355rec_jaccard_query_t* q, const mi355rec_request_ext_t* ext, const mi355rec_jaccard_result_t* res,
+                         mi355rec_jaccard_query_t* full, Request* r, Outputs* out, char* msg, size_t cap) {
+    return from_metric_query(kJaccardQuery, q, ext, res, full, r, out, msg, cap);
 }
 
 // "BOUNDED REQUESTS": the ordered image of a score as keys carry it (core.hip.h, score_to_ordered: -0.0 and +0.0 share one).

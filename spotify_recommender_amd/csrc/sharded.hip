@@ -1113,6 +1113,13 @@ int mi355rec_sharded_query_manhattan_request(mi355rec_sharded_t* h, const mi355r
     return node_request_entry(h, query, ext, result, {});
 }
 
+// JACCARD REQUESTS (include/mi355rec_diag.h): the same Request with metric = kJaccard through sharded_playlist, as the playlist
+// request: the shards answer with v, what the merge's keys compare.
+int mi355rec_sharded_query_jaccard_request(mi355rec_sharded_t* h, const mi355rec_jaccard_query_t* query,
+                                           const mi355rec_request_ext_t* ext, const mi355rec_jaccard_result_t* result) {
+    return node_request_entry(h, query, ext, result, {});
+}
+
 // BOUNDED REQUESTS (include/mi355rec_diag.h): the same Request with `bounded` through sharded_playlist; a row-sharded catalogue merges
 // the shards' matches and sums their totals (bounded_over_shards).
 int mi355rec_sharded_query_bounded_request(mi355rec_sharded_t* h, const mi355rec_bounded_query_t* query, const mi355rec_request_ext_t* ext,

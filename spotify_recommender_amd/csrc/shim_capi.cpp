@@ -296,6 +296,34 @@ int64_t shim_query_bounded(void* h, const int* songs, int n_songs, const int* ex
     if (match_count) *match_count = c->rec.lastMatchCount();
     return n;
 }
+// Recommender::recommendQuery of the Jaccard Query {songs, alsoExclude = exclude, where = the one range on where_feature (< 0: none),
+// topN, jaccard}, and — `refuse`, a bit each, to show the refusals — with weights (1), diverse (2), maxPerArtist (4), priorWeight (8),
+// scales (16), euclidean (32), through scoreSongs (64), anyOf (128), with a candidate list set (256), manhattan (512) or a bound
+// (1024).  scores: lastScores(), the similarities.  Returns how many songs came back.
+int64_t shim_query_jaccard(void* h, const int* songs, int n_songs, const int* exclude, int n_exclude, int where_feature, float lo, float hi,
+                           int topn, int refuse, int* out, float* scores, int64_t cap) {
+    Catalogue* c = static_cast<Catalogue*>(h);
+    Recommender::Query q;
+    q.songs.assign(songs, songs + (n_songs > 0 ? n_songs : 0));
+    q.alsoExclude.assign(exclude, exclude + (n_exclude > 0 ? n_exclude : 0));
+    if (where_feature >= 0) q.where.push_back({where_feature, lo, hi});
+    q.topN = topn;
+    if (refuse & 1024) q.atLeast(0.5f);
+    q.jaccard = true;
+    if (refuse & 1) q.weights.assign(q.songs.size(), 1.0f);
+    if (refuse & 2) q.diverse = true, q.lambda = 0.5f;
+    if (refuse & 4) q.maxPerArtist = 1;
+    if (refuse & 8) q.priorWeight = 0.5f;
+    if (refuse & 16) q.scales.assign(12, 2.0f);
+    if (refuse & 32) q.euclidean = true;
+    if (refuse & 128) q.anyOf = true;
+    if (refuse & 512) q.manhattan = true;
+    if (refuse & 64) return static_cast<int64_t>(c->rec.scoreSongs(q, std::vector<int64_t>{0}).size());
+    if (refuse & 256) c->rec.setCandidates(std::vector<int64_t>{0, 1, 2});
+    const int64_t n = giveBack(c, c->rec.recommendQuery(q), out, scores, cap);
+    if (refuse & 256) c->rec.clearCandidates();
+    return n;
+}
 // Recommender::updateSongs (n_features floats for n_songs songs: a length that differs is refused by the class).
 int shim_update_songs(void* h, const int* songs, int n_songs, const float* features, int64_t n_features) {
     Catalogue* c = static_cast<Catalogue*>(h);

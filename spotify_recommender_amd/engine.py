@@ -93,7 +93,7 @@ def _ptr(a):
 
 
 def _fill_query(q, members, topn: int, exclude, where, labels) -> tuple:
-    """Fills what the four request structs share (capi.PlaylistQuery, DistanceQuery, AnyOfQuery, ManhattanQuery): size, the members by
+    """Fills what the request structs share (capi.PlaylistQuery, DistanceQuery, AnyOfQuery, ManhattanQuery, JaccardQuery): size, the members by
     value (a (k, 12) float32 array) or by row (a 1-D int64 array), the exclusion list, the filter (make_filter), the label set, k and
     topn.  Returns what the struct now points to: the caller holds it until the call has returned."""
     flt = make_filter(where) if where is not None else None
@@ -112,10 +112,10 @@ def _fill_query(q, members, topn: int, exclude, where, labels) -> tuple:
 def _call_request(lib, prefix: str, h, check, kind: str, q, res, scales=None, rowset=None, candidates=None) -> None:
     """One top-N request of `kind` through the entry point its arguments need.  "playlist" and "distance": with `candidates` (a
     sequence of global ids) `prefix`query_`kind`_request_candidates, else with `rowset` = (pointer, mode) ..._request_ext, else with
-    `scales` (checked: make_scales) ..._request_scaled, else ..._request.  "anyof" and "manhattan" have the one entry point
+    `scales` (checked: make_scales) ..._request_scaled, else ..._request.  "anyof", "manhattan", "bounded" and "jaccard" have the one entry point
     `prefix`query_`kind`_request, which takes the ext (NULL without a row set) and no scales or list."""
     entry = f"{prefix}query_{kind}_request"
-    if kind in ("anyof", "manhattan", "bounded"):
+    if kind in ("anyof", "manhattan", "bounded", "jaccard"):
         ext = _request_ext(None, rowset)
         check(getattr(lib, entry)(h, ctypes.byref(q), ctypes.byref(ext) if rowset is not None else None, ctypes.byref(res)))
     elif candidates is not None:
@@ -579,6 +579,29 @@ def query_manhattan(eng, topn, members=None, rows=None, exclude=None, where=None
     eng._with_set(seen, only, lambda rowset: _call_request(eng._lib, eng._prefix, eng._h, eng._check, "manhattan", q, res, rowset=rowset))
     c = count.value
     return idx[:c].copy(), dist[:c].copy()
+
+
+def query_jaccard(eng, topn, members=None, rows=None, exclude=None, where=None, labels=None, seen=None, only=None):
+    """JACCARD REQUESTS (include/mi355rec_diag.h): the `topn` rows most similar to the members by weighted (Ruzicka) Jaccard
+    similarity (the mean over the members of sum_j min(q_kj, x_j) / sum_j max(q_kj, x_j)).  `eng`: a CosineEngine, a lane or a
+    NodeEngine; `members` k x 12 by value or `rows` of the engine (never returned), one of them; `exclude`, `where`, `labels`,
+    `seen` / `only` as in query_playlist_topn.
+    Returns (ids int64[c], similarities float32[c]), most similar first, ties by id.
+        ids, similarities = query_jaccard(eng, 100, rows=playlist_rows, seen=history)
+    (The engines' own methods keep their parameter lists: tests/test_engine_surface.py records them.)"""
+    if (members is None) == (rows is None):
+        raise ValueError("query_jaccard takes members= (by value) or rows= (by row), one of them")
+    m = _np_members(members) if members is not None else _np_rows(rows)
+    n_out = max(int(topn), 1)
+    idx = np.empty(n_out, dtype=np.int64)
+    sim = np.empty(n_out, dtype=np.float32)
+    count = ctypes.c_int(0)
+    q = capi.JaccardQuery()
+    keep = _fill_query(q, m, topn, exclude, where, labels)   # noqa: F841  (alive until the call has returned)
+    res = capi.JaccardResult(_ptr(idx), _ptr(sim), ctypes.pointer(count))
+    eng._with_set(seen, only, lambda rowset: _call_request(eng._lib, eng._prefix, eng._h, eng._check, "jaccard", q, res, rowset=rowset))
+    c = count.value
+    return idx[:c].copy(), sim[:c].copy()
 
 
 def query_bounded(eng, topn, bound, metric="cosine", members=None, rows=None, exclude=None, where=None, labels=None, seen=None, only=None):

@@ -11,6 +11,7 @@ label and filter tests:
     labelled_k10             within 3 of 114 labels (uniformly dealt)
     filtered_k10             one feature within [0, 0.1]: about 10 % of the rows pass
     anyof_k1, _k10, _k32     the any-of request (engine.query_anyof: with out_member)
+    bounded_count_k1         the bounded request, count only (engine.query_bounded, topn = 0) at the cosine floor 0.97
 
     python tools/playlist_ab.py --ab path/to/parent/libmi355rec.so [--kinds plain_k1,prior_k10] --out profiles/r16_playlist_cut_ab.json
 
@@ -35,8 +36,9 @@ PLAIN = ("plain_k1", "plain_k10")
 
 def kinds_of(eng, topn):
     """{kind: (K, call)}; a kind that needs side data loads it on first use."""
-    from spotify_recommender_amd.engine import query_anyof
+    from spotify_recommender_amd.engine import query_anyof, query_bounded
     return {
+        "bounded_count_k1": (1, lambda rows: query_bounded(eng, 0, 0.97, rows=rows)),
         "anyof_k1": (1, lambda rows: query_anyof(eng, topn, rows=rows)),
         "anyof_k10": (10, lambda rows: query_anyof(eng, topn, rows=rows)),
         "anyof_k32": (32, lambda rows: query_anyof(eng, topn, rows=rows)),
