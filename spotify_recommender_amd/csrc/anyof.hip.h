@@ -11,10 +11,14 @@
 // OWN KERNEL, playlist_scan_kernel's launch: PlaylistCfg (512 threads, two workgroups per CU), tiles of 2048 rows dealt round-robin,
 // the next tile's replica load in flight, PlaylistBuf as the call's inputs (weights, scales: never read).  playlist_scan_kernel sits
 // at 128 VGPRs without scratch; a K-member loop inside its tile loop would have to be shown free for every other kind of request.
-// What is shared is included, not copied: label_selected, filter_pass, rowset_admits and the quad's nibble, playlist_excluded,
-// playlist_tile_quad, cosine_with_norm, compact_candidates, block_select_threshold, block_rank_and_store, the per-workgroup lists
-// and merge.hip.h's merge.  What a loop body is in playlist.hip.h and not a function (the ballot append, the two barriers and the
-// shared_thr exchange, the anchor bound's pick-and-score) is written out again here, in the same order.
+// What is shared is called, not copied: label_selected, filter_pass, rowset_admits, playlist_excluded, playlist_tile_quad,
+// cosine_with_norm, compact_candidates, block_select_threshold, block_rank_and_store, the per-workgroup lists and merge.hip.h's
+// merge; and the tile loop's pieces of playlist.hip.h ("THE SCAN'S SHARED PIECES"): scan_compact_at, scan_append (the ballot
+// append), scan_exchange (the two barriers, the compaction and the shared_thr exchange), scan_quad_filter, scan_anchor_threshold
+// (the anchor bound once the table is ranked: the pick, the rows read from the matrix and keyed by this file's anyof_row_key, the
+// threshold) and scan_finish (the kernel's tail).  One piece is written out here as it is in playlist_scan_tiles, in the same
+// order: the quad's admissible mask (tail mask, row-set nibble, four-label test), which as a function moved both kernels of this
+// file by 1 - 2 VGPRs.
 //
 // ADMISSIBILITY is the playlist request's and is tested in its order: the row set's nibble and the label first (no fp32 row is
 // read), then the pre-filter, then the feature filter on the fp32 rows left, then the K chains, and the exclusion list (LDS, binary
@@ -193,8 +197,7 @@ __device__ __forceinline__ bool anyof_prologue(const AnyofCtx& c, const AnyofSme
 template <bool kL1>
 __device__ __forceinline__ uint64_t anyof_anchor_bound(const AnyofCtx& c, const AnyofSmem& sm, int& n_exact) {
     constexpr int kBlock = PlaylistCfg::kBlock, kPer = kAnchorRows / kBlock;
-    static_assert(PlaylistCfg::kCandCap >= kAnchorRows / 2 && PlaylistCfg::kCandCap * 2 >= kPlBoundRows, "LDS reuse below");
-    const int tid = c.tid, lane = c.lane;
+    const int tid = c.tid;
     const int64_t n = c.n;
     const int n_anchor = n < kAnchorRows ? static_cast<int>(n) : kAnchorRows;   // (anchor i is row i below kAnchorRows rows)
     if (!(c.anchors && c.topk <= kPlBoundRows && n_anchor >= kPlBoundRows)) return 0ull;   // uniform
@@ -209,62 +212,8 @@ __device__ __forceinline__ uint64_t anyof_anchor_bound(const AnyofCtx& c, const 
         if (c.active && !filter_pass(a, c.active, c.buf->lo, c.buf->hi)) mine[r] = 0ull;   // (only chooses: re-checked on the matrix's row)
         if (c.labelled && i < n_anchor && !label_selected(sm.lmask, c.row_label[anchor_row(n, i)])) mine[r] = 0ull;
     }
-    int n_cand = kPlBoundRows;   // anchors left to choose from: all of them without a filter
-    if (c.active || c.labelled || kL1) {   // uniform
-#pragma unroll
-        for (int r = 0; r < kPer; ++r) {
-            const uint64_t have = __ballot(mine[r] != 0ull);
-            if (lane == 0 && have) atomicAdd(&sm.count, __popcll(have));
-        }
-        __syncthreads();
-        n_cand = sm.count;
-        __syncthreads();
-        if (tid == 0) sm.count = 0;
-        __syncthreads();
-    }
-    // (fewer than kPlBoundRows candidates: keep them all)
-    const uint64_t t = n_cand >= kPlBoundRows ? block_select_threshold<kBlock, kPer>(mine, kPlBoundRows, true, 0, sm.sel) : 1ull;
-    int* const s_pick = reinterpret_cast<int*>(sm.cand);
-#pragma unroll
-    for (int r = 0; r < kPer; ++r) {   // (uniform loop) exactly kPlBoundRows keys are >= t, or all n_cand < kPlBoundRows
-        const bool keep = mine[r] != 0ull && mine[r] >= t;
-        const uint64_t who = __ballot(keep);
-        int base = 0;
-        if (lane == 0 && who) base = atomicAdd(&sm.count, __popcll(who));
-        base = __builtin_amdgcn_readfirstlane(base);
-        if (keep) s_pick[base + lanes_below(who)] = r * kBlock + tid;
-    }
-    __syncthreads();
-    const int picked = sm.count;   // (<= kPlBoundRows <= kBlock)
-    uint64_t key = 0ull;
-    if (tid < picked) {
-        const int64_t row = anchor_row(n, s_pick[tid]);
-        const Row x = load_row(c.feats, row);   // from the matrix
-        const bool x_pass = !c.active || filter_pass(x, c.active, c.buf->lo, c.buf->hi);
-        const uint64_t row_key = anyof_row_key<kL1>(c, sm, x, row);
-        ++n_exact;
-        key = playlist_excluded(sm.excl, c.n_excl, static_cast<uint32_t>(c.row_base + row)) || !x_pass ||
-                      (c.labelled && !label_selected(sm.lmask, c.row_label[row])) || (c.rowset && !rowset_admits(c.rowset, c.flip, row))
-                  ? 0ull
-                  : row_key;
-    }
-    const uint64_t have = __ballot(key != 0ull);
-    __syncthreads();   // (every thread has read the count and s_pick)
-    if (tid == 0) sm.count = 0;
-    __syncthreads();
-    if (lane == 0 && have) atomicAdd(&sm.count, __popcll(have));
-    __syncthreads();
-    const int usable = sm.count;
-    __syncthreads();
-    if (tid == 0) sm.count = 0;
-    uint64_t thr = 0ull;
-    if (usable >= c.topk) {   // uniform
-        const uint64_t one[1] = {key};
-        thr = block_select_threshold<kBlock, 1>(one, c.topk, true, 0, sm.sel) - 1ull;   // keys >= the topk-th pass
-        if (tid == 0) atomicMax(c.shared_thr, static_cast<unsigned long long>(thr));
-    }
-    __syncthreads();
-    return thr;
+    return scan_anchor_threshold(c, sm, mine, c.active || c.labelled || kL1,
+                                 [&](const Row& x, int64_t row) { return anyof_row_key<kL1>(c, sm, x, row); }, n_exact);
 }
 
 // The workgroup's threshold key has moved: every member's cut, by the first K threads (the caller's barrier follows).
@@ -281,8 +230,7 @@ __device__ __forceinline__ void anyof_scan_tiles(const AnyofCtx& c, const AnyofS
     constexpr int kBlock = PlaylistCfg::kBlock;
     const int tid = c.tid, lane = c.lane;
     const int64_t n = c.n, n_quads = (n + 3) >> 2, tiles = (n_quads + kBlock - 1) / kBlock;
-    int compact_at = 2 * c.topk > 256 ? 2 * c.topk : 256;
-    if (compact_at > kCandLimit) compact_at = kCandLimit;
+    const int compact_at = scan_compact_at(c.topk);
     if (cut_on && thr != 0ull) {   // uniform
         anyof_cut_refresh<kL1>(c, sm, thr);
         __syncthreads();
@@ -302,6 +250,7 @@ __device__ __forceinline__ void anyof_scan_tiles(const AnyofCtx& c, const AnyofS
         if (c.labelled) nxt_labels = c.labels4[playlist_tile_quad(t + gridDim.x, tid, n_quads)];
         float4 nxt_norms = cur_norms;
         if (kL1 && cut_on) nxt_norms = c.norms4[playlist_tile_quad(t + gridDim.x, tid, n_quads)];
+        // (the quad's admissible mask stays written out here and in playlist_scan_tiles: as a function it moved anyof.hip.h's two kernels by 1 - 2 VGPRs)
         const int64_t quad = t * kBlock + tid;
         const int64_t r0 = quad * 4;
         const int64_t left = quad < n_quads ? n - r0 : 0;   // rows of the quad inside the shard
@@ -321,17 +270,7 @@ __device__ __forceinline__ void anyof_scan_tiles(const AnyofCtx& c, const AnyofS
             if constexpr (kL1) playlist_cut_l1_apply(mask, cur, cur_norms, sm.mem, c.k, sm.l1[0], sm.l1[1], sm.l1[2]);
             else playlist_cut_any_apply(mask, cur, sm.digits, sm.cut, c.k);
         }
-        if (c.active && mask != 0u) {   // (active uniform) the filter on the fp32 rows left, before any chain
-            Row x[4];
-#pragma unroll
-            for (int u4 = 0; u4 < 4; ++u4) x[u4] = load_row(c.feats, r0 + u4 < n ? r0 + u4 : n - 1);
-#pragma unroll
-            for (int u4 = 0; u4 < 4; ++u4)
-                if (mask & (1u << u4)) {
-                    ++n_exact;
-                    if (!filter_pass(x[u4], c.active, c.buf->lo, c.buf->hi)) mask &= ~(1u << u4);
-                }
-        }
+        scan_quad_filter(c, r0, false, mask, n_exact);
         while (__ballot(mask != 0u)) {   // uniform
             const bool have = mask != 0u;
             const int64_t r = have ? r0 + __builtin_ctz(mask) : 0;
@@ -340,28 +279,11 @@ __device__ __forceinline__ void anyof_scan_tiles(const AnyofCtx& c, const AnyofS
             const uint64_t key = have ? row_key : 0ull;
             bool pass = key > thr;
             if (pass && c.n_excl > 0) pass = !playlist_excluded(sm.excl, c.n_excl, static_cast<uint32_t>(c.row_base + r));
-            const uint64_t ballot = __ballot(pass);
-            if (ballot) {
-                int base = 0;
-                if (lane == 0) base = atomicAdd(&sm.count, __popcll(ballot));
-                base = __builtin_amdgcn_readfirstlane(base);
-                if (pass) sm.cand[base + lanes_below(ballot)] = key;
-            }
+            scan_append(sm, lane, pass, key);
             mask &= mask - 1u;
         }
-        // two barriers: every wave reads the count before any wave appends again (scan_kernel)
-        __syncthreads();
-        const int count = sm.count;
-        if (tid == 0) sm.shared = __hip_atomic_load(c.shared_thr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        const uint64_t published = sm.shared;
         const uint64_t before = thr;
-        if (count >= compact_at) {
-            const uint64_t local_thr = compact_candidates<kBlock, PlaylistCfg::kCandPerThread>(sm.cand, &sm.count, c.topk, false, sm.sel);
-            if (local_thr > thr && local_thr > published && tid == 0) atomicMax(c.shared_thr, static_cast<unsigned long long>(local_thr));
-            if (local_thr > thr) thr = local_thr;
-        }
-        if (published > thr) thr = published;
+        thr = scan_exchange(c, sm, compact_at, thr);
         if (cut_on && thr != before) {   // (uniform) every wave has left this tile's cut test: the barriers above
             anyof_cut_refresh<kL1>(c, sm, thr);
             __syncthreads();
@@ -376,20 +298,11 @@ __device__ __forceinline__ void anyof_scan_tiles(const AnyofCtx& c, const AnyofS
 template <bool kL1>
 __device__ __forceinline__ void anyof_scan_body(const AnyofCtx& c, const AnyofSmem& sm, bool cut_on, uint64_t* __restrict__ block_lists,
                                                 unsigned long long* __restrict__ rows_exact) {
-    constexpr int kBlock = PlaylistCfg::kBlock;
     int n_exact = 0;   // rows whose K chains this thread computed
     uint64_t thr = 0ull;
     if (cut_on) thr = anyof_anchor_bound<kL1>(c, sm, n_exact);   // uniform
     anyof_scan_tiles<kL1>(c, sm, cut_on, thr, n_exact);
-
-    const int wave_exact = wave_inclusive_scan(n_exact);
-    if (c.lane == 63 && wave_exact) atomicAdd(&sm.exact, wave_exact);
-    __syncthreads();
-    if (c.tid == 0 && rows_exact && sm.exact) atomicAdd(rows_exact, static_cast<unsigned long long>(sm.exact));
-    if (sm.count > kRankCountMax && sm.count > c.topk)   // uniform
-        compact_candidates<kBlock, PlaylistCfg::kCandPerThread>(sm.cand, &sm.count, c.topk, false, sm.sel);
-    __syncthreads();
-    block_rank_and_store<kBlock>(sm.cand, sm.count, block_lists + static_cast<int64_t>(blockIdx.x) * c.topk, c.topk);
+    scan_finish(c, sm, n_exact, block_lists, rows_exact);
 }
 
 // q8: the handle's 8-bit replica, or null (every row exact).  anchors: the anchor table, or null (no starting threshold).

@@ -356,51 +356,40 @@ int playlist_launch(mi355rec* h, const Request& r, int max_exclude, SyncSlots* s
     if (want_grid > P->grid_cap) want_grid = P->grid_cap;
     if (want_grid < 1) want_grid = 1;
     const int grid = static_cast<int>(want_grid);
+    // what every launch below passes: the call's staged inputs and the word inside them, the shard's labels, the rows' norms
+    const PlaylistBuf* const d_buf = P->d_buf;
+    unsigned long long* const shared_thr = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr));
+    const uint2* const labels = reinterpret_cast<const uint2*>(L ? L->d_row_labels : nullptr);
+    const float4* const norms = reinterpret_cast<const float4*>(scan_norms ? P->d_norms : nullptr);
+    const float* const anchors = h->d_anchor;
     if (count_launch) {   // "BOUNDED REQUESTS": the count form: topk == 0 without a list, the total word as rows_exact; AHEAD of the
         // top-N launch, which raises shared_thr above the floor
         HIP_TRY(h, hipMemsetAsync(P->d_total, 0, sizeof(unsigned long long), h->stream));
         PlaylistArg count_arg = arg;
         // (experiments build only: tools/run_bounded.py's A/B of the proven-in shortcut; n_cand means nothing else without a list)
         if (MI355REC_EXP_FLAG("MI355REC_EXP_NO_PROVEN_IN")) count_arg.n_cand = 1;
-        hipLaunchKernelGGL(playlist_scan_kernel, dim3(grid), dim3(PlaylistCfg::kBlock), 0, h->stream, h->d_feats, q8, h->n, h->row_base,
-                           static_cast<const PlaylistBuf*>(P->d_buf), count_arg, static_cast<const float*>(nullptr), 0, h->d_block_lists, P->d_total,
-                           reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr)),
-                           reinterpret_cast<const uint2*>(L ? L->d_row_labels : nullptr), reinterpret_cast<const float4*>(pri),
-                           reinterpret_cast<const float4*>(scan_norms ? P->d_norms : nullptr));
+        hipLaunchKernelGGL(playlist_scan_kernel, dim3(grid), dim3(PlaylistCfg::kBlock), 0, h->stream, h->d_feats, q8, h->n, h->row_base, d_buf,
+                           count_arg, static_cast<const float*>(nullptr), 0, h->d_block_lists, P->d_total, shared_thr, labels,
+                           reinterpret_cast<const float4*>(pri), norms);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipMemcpyAsync(P->h_total, P->d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
         P->counted = true;
         if (topk == 0) return MI355REC_OK;   // count only (or nothing to list): *grid_out stays 0
     }
-    if (manhattan) {   // "MANHATTAN REQUESTS": its own kernel (anyof.hip.h), this launch's geometry, inputs and lists
-        const AnyofArg any = {k, n_excl, arg.by_row, arg.active, arg.labelled, arg.rowset, arg.rowset_flip, 0};
+    // "MANHATTAN REQUESTS", "ANY-OF REQUESTS": their own kernels (anyof.hip.h), this launch's geometry, inputs and lists
+    const AnyofArg any = {k, n_excl, arg.by_row, arg.active, arg.labelled, arg.rowset, arg.rowset_flip, 0};
+    if (manhattan) {
         LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, manhattan_scan_kernel, dim3(grid), dim3(PlaylistCfg::kBlock), h->stream,
-                     h->d_feats, q8, h->n, h->row_base, static_cast<const PlaylistBuf*>(P->d_buf), any, static_cast<const float*>(h->d_anchor), topk,
-                     h->d_block_lists, P->d_exact,
-                     reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr)),
-                     reinterpret_cast<const uint2*>(L ? L->d_row_labels : nullptr), reinterpret_cast<const float4*>(scan_norms ? P->d_norms : nullptr));
-        HIP_TRY(h, hipGetLastError());
-        *grid_out = grid;
-        return MI355REC_OK;
-    }
-    if (anyof) {   // "ANY-OF REQUESTS": its own kernel (anyof.hip.h), this launch's geometry, inputs and lists
-        const AnyofArg any = {k, n_excl, arg.by_row, arg.active, arg.labelled, arg.rowset, arg.rowset_flip, 0};
+                     h->d_feats, q8, h->n, h->row_base, d_buf, any, anchors, topk, h->d_block_lists, P->d_exact, shared_thr, labels, norms);
+    } else if (anyof) {
         LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, anyof_scan_kernel, dim3(grid), dim3(PlaylistCfg::kBlock), h->stream,
-                     h->d_feats, q8, h->n, h->row_base, static_cast<const PlaylistBuf*>(P->d_buf), any, static_cast<const float*>(h->d_anchor), topk,
-                     h->d_block_lists, P->d_exact,
-                     reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr)),
-                     reinterpret_cast<const uint2*>(L ? L->d_row_labels : nullptr), static_cast<const uint64_t*>(nullptr),
-                     static_cast<int32_t*>(nullptr));
-        HIP_TRY(h, hipGetLastError());
-        *grid_out = grid;
-        return MI355REC_OK;
+                     h->d_feats, q8, h->n, h->row_base, d_buf, any, anchors, topk, h->d_block_lists, P->d_exact, shared_thr, labels,
+                     static_cast<const uint64_t*>(nullptr), static_cast<int32_t*>(nullptr));
+    } else {
+        LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, playlist_scan_kernel, dim3(grid), dim3(PlaylistCfg::kBlock), h->stream,
+                     h->d_feats, q8, h->n, h->row_base, d_buf, arg, r.listed ? nullptr : anchors, topk,
+                     r.score ? P->d_cand_keys : h->d_block_lists, P->d_exact, shared_thr, labels, reinterpret_cast<const float4*>(pri), norms);
     }
-    LAUNCH_TIMED(h, h->ev_scan, h->n_scan_pairs, h->scan_launches, playlist_scan_kernel, dim3(grid), dim3(PlaylistCfg::kBlock),
-                 h->stream, h->d_feats, q8, h->n, h->row_base, static_cast<const PlaylistBuf*>(P->d_buf), arg,
-                 static_cast<const float*>(r.listed ? nullptr : h->d_anchor), topk, r.score ? P->d_cand_keys : h->d_block_lists, P->d_exact,
-                 reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(P->d_buf) + offsetof(PlaylistBuf, shared_thr)),
-                 reinterpret_cast<const uint2*>(L ? L->d_row_labels : nullptr), reinterpret_cast<const float4*>(pri),
-                 reinterpret_cast<const float4*>(scan_norms ? P->d_norms : nullptr));
     HIP_TRY(h, hipGetLastError());
     *grid_out = grid;
     return MI355REC_OK;

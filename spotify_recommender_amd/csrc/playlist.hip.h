@@ -463,33 +463,76 @@ __device__ __forceinline__ Q8Query playlist_prologue(const PlaylistCtx& c, const
                               sm.abar, sm.qn, s_q2);
 }
 
-// ---- the starting threshold: the best kPlBoundRows anchors by u, scored exactly (STARTING THRESHOLD above).  Returns the
-// threshold key (published too), or 0.
-__device__ __forceinline__ uint64_t playlist_anchor_bound(const PlaylistCtx& c, const PlaylistSmem& sm, const float (&u)[kDim], float un, int& n_exact) {
+// ---- THE SCAN'S SHARED PIECES.  The family's three kernels (this file's, and anyof.hip.h's two) call them; Ctx / Smem are
+// PlaylistCtx / PlaylistSmem or AnyofCtx / AnyofSmem, which name what these pieces touch alike.  The starting threshold and the
+// shared atomicMax are valid only because every kernel applies the same rule in the same order: it is written here, once.
+
+// The candidate count at which a workgroup compacts its list: 2 topk, at least 256, at most kCandLimit.
+__device__ __forceinline__ int scan_compact_at(int topk) {
+    const int at = 2 * topk > 256 ? 2 * topk : 256;
+    return at > kCandLimit ? kCandLimit : at;
+}
+
+// The ballot append: the keys of the wave's passing lanes into sm.cand, one LDS atomic per wave.
+template <class Smem>
+__device__ __forceinline__ void scan_append(const Smem& sm, int lane, bool pass, uint64_t key) {
+    const uint64_t ballot = __ballot(pass);
+    if (ballot) {
+        int base = 0;
+        if (lane == 0) base = atomicAdd(&sm.count, __popcll(ballot));
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (pass) sm.cand[base + lanes_below(ballot)] = key;
+    }
+}
+
+// The end of a tile: two barriers (every wave reads the count before any wave appends again: scan_kernel), the published
+// threshold read once for the workgroup, the compaction at compact_at, and the exchange: a workgroup that raised its threshold
+// above the published one publishes it, and every workgroup adopts the published maximum.  Returns the new threshold.
+template <class Ctx, class Smem>
+__device__ __forceinline__ uint64_t scan_exchange(const Ctx& c, const Smem& sm, int compact_at, uint64_t thr) {
+    constexpr int kBlock = PlaylistCfg::kBlock;
+    __syncthreads();
+    const int count = sm.count;
+    if (c.tid == 0) sm.shared = __hip_atomic_load(c.shared_thr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    const uint64_t published = sm.shared;
+    if (count >= compact_at) {
+        const uint64_t local_thr = compact_candidates<kBlock, PlaylistCfg::kCandPerThread>(sm.cand, &sm.count, c.topk, false, sm.sel);
+        if (local_thr > thr && local_thr > published && c.tid == 0) atomicMax(c.shared_thr, static_cast<unsigned long long>(local_thr));
+        if (local_thr > thr) thr = local_thr;
+    }
+    return published > thr ? published : thr;
+}
+
+// The feature filter on the fp32 rows the quad at r0 still holds, before any chain.  The quad's four rows are requested together
+// (one memory round trip, not four); rows past n read row n - 1.  counting (BOUNDED): n_exact counts matches, not the rows read.
+template <class Ctx>
+__device__ __forceinline__ void scan_quad_filter(const Ctx& c, int64_t r0, bool counting, uint32_t& mask, int& n_exact) {
+    if (c.active && mask != 0u) {   // (active uniform)
+        Row x[4];
+#pragma unroll
+        for (int u4 = 0; u4 < 4; ++u4) x[u4] = load_row(c.feats, r0 + u4 < c.n ? r0 + u4 : c.n - 1);
+#pragma unroll
+        for (int u4 = 0; u4 < 4; ++u4)
+            if (mask & (1u << u4)) {
+                n_exact += counting ? 0 : 1;
+                if (!filter_pass(x[u4], c.active, c.buf->lo, c.buf->hi)) mask &= ~(1u << u4);
+            }
+    }
+}
+
+// The starting threshold once the anchor table is ranked (mine: a thread's keys of the table's copy, 0 for an anchor that is
+// no candidate): the best kPlBoundRows are picked, read FROM THE MATRIX, keyed by row_key(x, row) (the scan's own key of the
+// kernel), the inadmissible ones dropped, and the topk-th best of the rest is the threshold (published too), or 0.
+// count_first (uniform): some anchors may be no candidates, so fewer than kPlBoundRows may be left to choose from.
+template <class Ctx, class Smem, class RowKey>
+__device__ __forceinline__ uint64_t scan_anchor_threshold(const Ctx& c, const Smem& sm, const uint64_t (&mine)[kAnchorRows / PlaylistCfg::kBlock],
+                                                          bool count_first, RowKey row_key, int& n_exact) {
     constexpr int kBlock = PlaylistCfg::kBlock, kPer = kAnchorRows / kBlock;
     static_assert(PlaylistCfg::kCandCap >= kAnchorRows / 2 && PlaylistCfg::kCandCap * 2 >= kPlBoundRows, "LDS reuse below");
     const int tid = c.tid, lane = c.lane;
-    const int64_t n = c.n;
-    const int n_anchor = n < kAnchorRows ? static_cast<int>(n) : kAnchorRows;   // (anchor i is row i below kAnchorRows rows)
-    if (!(c.anchors && c.topk <= kPlBoundRows && n_anchor >= kPlBoundRows)) return 0ull;   // uniform
-    uint64_t mine[kPer];
-#pragma unroll
-    for (int r = 0; r < kPer; ++r) {
-        const int i = r * kBlock + tid;
-        Row a = load_row(c.anchors, static_cast<int64_t>(i));
-        const bool a_pass = !c.active || filter_pass(a, c.active, c.buf->lo, c.buf->hi);   // (the filter tests the stored values)
-        if (c.scaled) scale_row(a, sm.scale);   // (uniform)
-        if (c.dist) {   // (uniform) DISTANCE: the anchors nearest to the centroid; a distance that is not finite is no candidate
-            const float d = playlist_sqdist(&u, 1, a);   // (the chain's d2 against the centroid: K = 1 divides by 1.0f, exactly)
-            mine[r] = i < n_anchor && d < __builtin_inff() ? pack_key(-d, static_cast<uint32_t>(i)) : 0ull;
-        } else {
-            mine[r] = i < n_anchor ? pack_key(cosine_score(u, un, a), static_cast<uint32_t>(i)) : 0ull;
-        }
-        if (!a_pass) mine[r] = 0ull;   // (only chooses: re-checked on the matrix's row)
-        if (c.labelled && i < n_anchor && !label_selected(sm.lmask, c.row_label[anchor_row(n, i)])) mine[r] = 0ull;
-    }
     int n_cand = kPlBoundRows;   // anchors left to choose from: all of them without a filter
-    if (c.active || c.labelled || c.dist) {   // uniform
+    if (count_first) {   // uniform
 #pragma unroll
         for (int r = 0; r < kPer; ++r) {
             const uint64_t have = __ballot(mine[r] != 0ull);
@@ -514,18 +557,18 @@ __device__ __forceinline__ uint64_t playlist_anchor_bound(const PlaylistCtx& c, 
         if (keep) s_pick[base + lanes_below(who)] = r * kBlock + tid;
     }
     __syncthreads();
-    const int picked = sm.count;
+    const int picked = sm.count;   // (<= kPlBoundRows <= kBlock)
     uint64_t key = 0ull;
     if (tid < picked) {
-        const int64_t row = anchor_row(n, s_pick[tid]);
+        const int64_t row = anchor_row(c.n, s_pick[tid]);
         const Row x = load_row(c.feats, row);   // from the matrix
         const bool x_pass = !c.active || filter_pass(x, c.active, c.buf->lo, c.buf->hi);   // (the filter tests the stored row)
-        const uint64_t row_key = playlist_row_key(c, sm, x, row);
+        const uint64_t k = row_key(x, row);
         ++n_exact;
         key = playlist_excluded(sm.excl, c.n_excl, static_cast<uint32_t>(c.row_base + row)) || !x_pass ||
                       (c.labelled && !label_selected(sm.lmask, c.row_label[row])) || (c.rowset && !rowset_admits(c.rowset, c.flip, row))
                   ? 0ull
-                  : row_key;
+                  : k;
     }
     const uint64_t have = __ballot(key != 0ull);
     __syncthreads();   // (every thread has read the count and s_pick)
@@ -544,6 +587,49 @@ __device__ __forceinline__ uint64_t playlist_anchor_bound(const PlaylistCtx& c, 
     }
     __syncthreads();
     return thr;
+}
+
+// The kernel's tail: the workgroup's n_exact into rows_exact, the last compaction, the ranked list of topk keys.
+template <class Ctx, class Smem>
+__device__ __forceinline__ void scan_finish(const Ctx& c, const Smem& sm, int n_exact, uint64_t* __restrict__ block_lists,
+                                            unsigned long long* __restrict__ rows_exact) {
+    constexpr int kBlock = PlaylistCfg::kBlock;
+    const int wave_exact = wave_inclusive_scan(n_exact);
+    if (c.lane == 63 && wave_exact) atomicAdd(&sm.exact, wave_exact);
+    __syncthreads();
+    if (c.tid == 0 && rows_exact && sm.exact) atomicAdd(rows_exact, static_cast<unsigned long long>(sm.exact));
+    if (sm.count > kRankCountMax && sm.count > c.topk)   // uniform
+        compact_candidates<kBlock, PlaylistCfg::kCandPerThread>(sm.cand, &sm.count, c.topk, false, sm.sel);
+    __syncthreads();
+    block_rank_and_store<kBlock>(sm.cand, sm.count, block_lists + static_cast<int64_t>(blockIdx.x) * c.topk, c.topk);
+}
+
+// ---- the starting threshold: the best kPlBoundRows anchors by u, scored exactly (STARTING THRESHOLD above).  Returns the
+// threshold key (published too), or 0.
+__device__ __forceinline__ uint64_t playlist_anchor_bound(const PlaylistCtx& c, const PlaylistSmem& sm, const float (&u)[kDim], float un, int& n_exact) {
+    constexpr int kBlock = PlaylistCfg::kBlock, kPer = kAnchorRows / kBlock;
+    const int tid = c.tid;
+    const int64_t n = c.n;
+    const int n_anchor = n < kAnchorRows ? static_cast<int>(n) : kAnchorRows;   // (anchor i is row i below kAnchorRows rows)
+    if (!(c.anchors && c.topk <= kPlBoundRows && n_anchor >= kPlBoundRows)) return 0ull;   // uniform
+    uint64_t mine[kPer];
+#pragma unroll
+    for (int r = 0; r < kPer; ++r) {
+        const int i = r * kBlock + tid;
+        Row a = load_row(c.anchors, static_cast<int64_t>(i));
+        const bool a_pass = !c.active || filter_pass(a, c.active, c.buf->lo, c.buf->hi);   // (the filter tests the stored values)
+        if (c.scaled) scale_row(a, sm.scale);   // (uniform)
+        if (c.dist) {   // (uniform) DISTANCE: the anchors nearest to the centroid; a distance that is not finite is no candidate
+            const float d = playlist_sqdist(&u, 1, a);   // (the chain's d2 against the centroid: K = 1 divides by 1.0f, exactly)
+            mine[r] = i < n_anchor && d < __builtin_inff() ? pack_key(-d, static_cast<uint32_t>(i)) : 0ull;
+        } else {
+            mine[r] = i < n_anchor ? pack_key(cosine_score(u, un, a), static_cast<uint32_t>(i)) : 0ull;
+        }
+        if (!a_pass) mine[r] = 0ull;   // (only chooses: re-checked on the matrix's row)
+        if (c.labelled && i < n_anchor && !label_selected(sm.lmask, c.row_label[anchor_row(n, i)])) mine[r] = 0ull;
+    }
+    return scan_anchor_threshold(c, sm, mine, c.active || c.labelled || c.dist,
+                                 [&](const Row& x, int64_t row) { return playlist_row_key(c, sm, x, row); }, n_exact);
 }
 
 // One tile's streamed inputs of a lane: its quad of the replica, of the labels and of the side values.
@@ -578,8 +664,7 @@ __device__ __forceinline__ void playlist_scan_tiles(const PlaylistCtx& c, const 
     // PROVEN IN (playlist_cut.hip.h, "BOUNDED"): the floor's own score is the image (thr + 1) >> 32; uniform, fixed for the launch
     const bool proving = counting && cut.kind == kPlCutPlain && !c.active && !no_proof;
     const int cut_hi = proving ? playlist_cut_proven(cut, ordered_to_score(static_cast<uint32_t>((thr + 1ull) >> 32))) : kPlCutNever;
-    int compact_at = 2 * c.topk > 256 ? 2 * c.topk : 256;
-    if (compact_at > kCandLimit) compact_at = kCandLimit;
+    const int compact_at = scan_compact_at(c.topk);
     PlaylistTile cur = {};   // (zeros where nothing streams)
     const bool replica = cut.kind != kPlCutOff, side = cut.kind == kPlCutPrior || cut.kind == kPlCutDistance;   // what streams
     playlist_load_tile(c, replica, side, n_quads, blockIdx.x, cur);
@@ -587,6 +672,7 @@ __device__ __forceinline__ void playlist_scan_tiles(const PlaylistCtx& c, const 
     for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {   // uniform
         PlaylistTile nxt = cur;
         playlist_load_tile(c, replica, side, n_quads, t + gridDim.x, nxt);   // the next tile is in flight while this one is scored
+        // (the quad's admissible mask stays written out here and in anyof_scan_tiles: as a function it moved anyof.hip.h's two kernels by 1 - 2 VGPRs)
         const int64_t quad = t * kBlock + tid;
         const int64_t r0 = quad * 4;
         const int64_t left = quad < n_quads ? n - r0 : 0;   // rows of the quad inside the shard
@@ -616,18 +702,7 @@ __device__ __forceinline__ void playlist_scan_tiles(const PlaylistCtx& c, const 
                     }
             }
         }
-        if (c.active && mask != 0u) {   // (active uniform) the filter on the fp32 rows left, before any chain
-            // the quad's four rows are requested together (one memory round trip, not four); rows past n read row n - 1
-            Row x[4];
-#pragma unroll
-            for (int u4 = 0; u4 < 4; ++u4) x[u4] = load_row(c.feats, r0 + u4 < n ? r0 + u4 : n - 1);
-#pragma unroll
-            for (int u4 = 0; u4 < 4; ++u4)
-                if (mask & (1u << u4)) {
-                    n_exact += counting ? 0 : 1;
-                    if (!filter_pass(x[u4], c.active, c.buf->lo, c.buf->hi)) mask &= ~(1u << u4);
-                }
-        }
+        scan_quad_filter(c, r0, counting, mask, n_exact);
         while (__ballot(mask != 0u)) {   // uniform
             const bool have = mask != 0u;
             const int64_t r = have ? r0 + __builtin_ctz(mask) : 0;
@@ -637,27 +712,10 @@ __device__ __forceinline__ void playlist_scan_tiles(const PlaylistCtx& c, const 
             bool pass = key > thr;
             if (pass && c.n_excl > 0) pass = !playlist_excluded(sm.excl, c.n_excl, static_cast<uint32_t>(c.row_base + r));
             if (counting) n_exact += pass ? 1 : 0, pass = false;   // a match: counted, never listed
-            const uint64_t ballot = __ballot(pass);
-            if (ballot) {
-                int base = 0;
-                if (lane == 0) base = atomicAdd(&sm.count, __popcll(ballot));
-                base = __builtin_amdgcn_readfirstlane(base);
-                if (pass) sm.cand[base + lanes_below(ballot)] = key;
-            }
+            scan_append(sm, lane, pass, key);
             mask &= mask - 1u;
         }
-        // two barriers: every wave reads the count before any wave appends again (scan_kernel)
-        __syncthreads();
-        const int count = sm.count;
-        if (tid == 0) sm.shared = __hip_atomic_load(c.shared_thr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        const uint64_t published = sm.shared;
-        if (count >= compact_at) {
-            const uint64_t local_thr = compact_candidates<kBlock, PlaylistCfg::kCandPerThread>(sm.cand, &sm.count, c.topk, false, sm.sel);
-            if (local_thr > thr && local_thr > published && tid == 0) atomicMax(c.shared_thr, static_cast<unsigned long long>(local_thr));
-            if (local_thr > thr) thr = local_thr;
-        }
-        if (published > thr) thr = published;
+        thr = scan_exchange(c, sm, compact_at, thr);
         playlist_cut_refresh(cut, thr);
         cur = nxt;
     }
@@ -676,8 +734,7 @@ __device__ __forceinline__ void playlist_gather_rows(const PlaylistCtx& c, const
     const int64_t chunks = (n_cand + kBlock * kPer - 1) / (kBlock * kPer);
     const bool score = c.topk == 0;   // (uniform) CANDIDATE SCORES: every entry's key to entry_keys, nothing selected
     uint64_t thr = 0ull;
-    int compact_at = 2 * c.topk > 256 ? 2 * c.topk : 256;
-    if (compact_at > kCandLimit) compact_at = kCandLimit;
+    const int compact_at = scan_compact_at(c.topk);
 
     for (int64_t t = blockIdx.x; t < chunks; t += gridDim.x) {   // uniform
         const int64_t e0 = (t * kBlock + tid) * kPer;
@@ -717,27 +774,10 @@ __device__ __forceinline__ void playlist_gather_rows(const PlaylistCtx& c, const
                 if (e0 + v < n_cand) entry_keys[e0 + v] = pass ? key : 0ull;
                 continue;
             }
-            const uint64_t ballot = __ballot(pass);
-            if (ballot) {
-                int base = 0;
-                if (lane == 0) base = atomicAdd(&sm.count, __popcll(ballot));
-                base = __builtin_amdgcn_readfirstlane(base);
-                if (pass) sm.cand[base + lanes_below(ballot)] = key;
-            }
+            scan_append(sm, lane, pass, key);
         }
         if (score) continue;   // (uniform) nothing was appended: no barrier, no compaction, no threshold
-        // the scan's two barriers, compaction and threshold exchange
-        __syncthreads();
-        const int count = sm.count;
-        if (tid == 0) sm.shared = __hip_atomic_load(c.shared_thr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        const uint64_t published = sm.shared;
-        if (count >= compact_at) {
-            const uint64_t local_thr = compact_candidates<kBlock, PlaylistCfg::kCandPerThread>(sm.cand, &sm.count, c.topk, false, sm.sel);
-            if (local_thr > thr && local_thr > published && tid == 0) atomicMax(c.shared_thr, static_cast<unsigned long long>(local_thr));
-            if (local_thr > thr) thr = local_thr;
-        }
-        if (published > thr) thr = published;
+        thr = scan_exchange(c, sm, compact_at, thr);
     }
 }
 
@@ -751,7 +791,6 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
     PlaylistArg arg, const float* __restrict__ anchors, int topk, uint64_t* __restrict__ block_lists,
     unsigned long long* __restrict__ rows_exact, unsigned long long* __restrict__ shared_thr /* &buf->shared_thr */,
     const uint2* __restrict__ labels, const float4* __restrict__ priors, const float4* __restrict__ norms) {
-    constexpr int kBlock = PlaylistCfg::kBlock;
     __shared__ uint64_t s_cand[PlaylistCfg::kCandCap];
     __shared__ SelectSmem s_sel;
     __shared__ int s_count, s_ok, s_exact;
@@ -782,14 +821,7 @@ __global__ __launch_bounds__(PlaylistCfg::kBlock, PlaylistCfg::kMinWaves) void p
         playlist_scan_tiles(c, sm, hq, cut, thr, n_exact, arg.n_cand != 0);   // (n_cand without a list: BOUNDED above, the A/B knob)
     }
 
-    const int wave_exact = wave_inclusive_scan(n_exact);
-    if (c.lane == 63 && wave_exact) atomicAdd(&sm.exact, wave_exact);
-    __syncthreads();
-    if (tid == 0 && rows_exact && sm.exact) atomicAdd(rows_exact, static_cast<unsigned long long>(sm.exact));
-    if (sm.count > kRankCountMax && sm.count > topk)   // uniform
-        compact_candidates<kBlock, PlaylistCfg::kCandPerThread>(sm.cand, &sm.count, topk, false, sm.sel);
-    __syncthreads();
-    block_rank_and_store<kBlock>(sm.cand, sm.count, block_lists + static_cast<int64_t>(blockIdx.x) * topk, topk);
+    scan_finish(c, sm, n_exact, block_lists, rows_exact);
 }
 
 }  // namespace mi355

@@ -12,6 +12,9 @@ label and filter tests:
     filtered_k10             one feature within [0, 0.1]: about 10 % of the rows pass
     anyof_k1, _k10, _k32     the any-of request (engine.query_anyof: with out_member)
     bounded_count_k1         the bounded request, count only (engine.query_bounded, topn = 0) at the cosine floor 0.97
+    manhattan_k1, _k10       the Manhattan request (engine.query_manhattan: manhattan_scan_kernel)
+    jaccard_k1               the Jaccard request (engine.query_jaccard: no pre-filter, every row takes the chain)
+    candidates_k1            the cosine request within a fixed ascending list of 100 000 ids (engine.with_candidates: the gather)
 
     python tools/playlist_ab.py --ab path/to/parent/libmi355rec.so [--kinds plain_k1,prior_k10] --out profiles/r16_playlist_cut_ab.json
 
@@ -31,13 +34,19 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 
 GENERAL = [2, 1, .5, 0, 1, 1, 3, 1, .25, 1, 1, 0]
 N_LABELS = 114
+N_LISTED = 100_000
 PLAIN = ("plain_k1", "plain_k10")
 
 
 def kinds_of(eng, topn):
     """{kind: (K, call)}; a kind that needs side data loads it on first use."""
-    from spotify_recommender_amd.engine import query_anyof, query_bounded
+    from spotify_recommender_amd.engine import query_anyof, query_bounded, query_jaccard, query_manhattan, with_candidates
+    listed = np.arange(N_LISTED, dtype=np.int64) * ((eng.rows if eng else N_LISTED) // N_LISTED)   # ascending, spread over the catalogue
     return {
+        "manhattan_k1": (1, lambda rows: query_manhattan(eng, topn, rows=rows)),
+        "manhattan_k10": (10, lambda rows: query_manhattan(eng, topn, rows=rows)),
+        "jaccard_k1": (1, lambda rows: query_jaccard(eng, topn, rows=rows)),
+        "candidates_k1": (1, lambda rows: with_candidates(eng, listed).query_playlist_topn(rows, topn)),
         "bounded_count_k1": (1, lambda rows: query_bounded(eng, 0, 0.97, rows=rows)),
         "anyof_k1": (1, lambda rows: query_anyof(eng, topn, rows=rows)),
         "anyof_k10": (10, lambda rows: query_anyof(eng, topn, rows=rows)),
