@@ -949,6 +949,36 @@ __device__ __forceinline__ Q8Query q8_uniform(const Q8Query& q) {
 }
 constexpr int kPairCandLimit = 2 * kPairMaxTopk;   // a tile is never entered with more candidates of one query
 
+// The pair kernel's tile loop is bound by vector issue (docs/LAB_NOTES.md, "Streamed 8-bit scan: fewer vector instructions per
+// tile in the pair kernel"), and all it asks of a row's D is whether it reaches the query's cut_d.  So it computes the EXCESS
+// D - cut_d in one accumulator chain, eight instructions a row where q8_dot and its compare take ten: the low digits' chain
+// starts from 256 * hi - cut_d (one v_lshl_add_u32) instead of from a cleared register, and nothing is compared per row.  The
+// same integer sums as q8_dot: a row is a candidate where the excess is >= 0.  `neg_cut` is -cut_d, kept per query beside
+// cut_d; a cut of INT_MIN ("no bound") is clamped to -2^30, which no D comes near (|D| < 2^27).  (Plain builtins on purpose:
+// the dot instructions have issue hazards against other vector instructions on this chip that the compiler pads for, and it
+// cannot see into inline assembly.)
+__device__ __forceinline__ int q8_pair_neg_cut(int cut_d) { return -(cut_d > -(1 << 30) ? cut_d : -(1 << 30)); }
+__device__ __forceinline__ int q8_pair_excess(const Q8Query& q, int neg_cut, uint32_t d0, uint32_t d1, uint32_t d2) {
+    int hi = __builtin_amdgcn_sdot4(static_cast<int>(d0), q.hi[0], 0, false);
+    hi = __builtin_amdgcn_sdot4(static_cast<int>(d1), q.hi[1], hi, false);
+    hi = __builtin_amdgcn_sdot4(static_cast<int>(d2), q.hi[2], hi, false);
+    if constexpr (kQ8QueryBits == 16) {
+        int acc = static_cast<int>((static_cast<uint32_t>(hi) << 8) + static_cast<uint32_t>(neg_cut));
+        acc = __builtin_amdgcn_sdot4(static_cast<int>(d0), q.lo[0], acc, false);
+        acc = __builtin_amdgcn_sdot4(static_cast<int>(d1), q.lo[1], acc, false);
+        acc = __builtin_amdgcn_sdot4(static_cast<int>(d2), q.lo[2], acc, false);
+        return acc;
+    } else {
+        return hi + neg_cut;
+    }
+}
+__device__ __forceinline__ void q8_pair_excess4(const Q8Query& q, int neg_cut, const HalfTile& t, int (&e)[4]) {
+    e[0] = q8_pair_excess(q, neg_cut, t.t0.x, t.t0.y, t.t0.z);
+    e[1] = q8_pair_excess(q, neg_cut, t.t0.w, t.t1.x, t.t1.y);
+    e[2] = q8_pair_excess(q, neg_cut, t.t1.z, t.t1.w, t.t2.x);
+    e[3] = q8_pair_excess(q, neg_cut, t.t2.y, t.t2.z, t.t2.w);
+}
+
 template <int kBlockT, int kMinWavesT, int kDepthT>
 struct Q8PairCfg {
     static constexpr int kBlock = kBlockT;
@@ -1065,10 +1095,15 @@ __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel_pa
     const int64_t quad_begin = static_cast<int64_t>(bid) * kBlock + tid;
     const int64_t quad_stride = static_cast<int64_t>(slots) * kBlock;
 
-    auto load_tile = [&](HalfTile& dst, int it) {
-        int64_t quad = quad_begin + static_cast<int64_t>(it) * quad_stride;
-        quad = quad < n_quads ? quad : last_quad;   // unconditional prefetch (see scan_kernel)
-        const uint4* p = q8 + quad * 3;
+    // Tiles are asked for in order (it = 0, 1, 2, ...), so where the lane's next one starts (counted in uint4s) is where the last
+    // one did plus a uniform stride: five vector instructions a tile where quad_begin + it * quad_stride, the clamp and "times
+    // 48 plus the base" take ten.  The count runs on past the end and is clamped to the last quad's when it is used.
+    const int64_t last_at = last_quad * 3;
+    const int64_t stride_at = quad_stride * 3;
+    int64_t next_at = quad_begin * 3;
+    auto load_tile = [&](HalfTile& dst, int /* it: the next one */) {
+        const uint4* p = q8 + (next_at < last_at ? next_at : last_at);   // unconditional prefetch (see scan_kernel)
+        next_at += stride_at;
         dst.t0 = p[0];
         dst.t1 = p[1];
         dst.t2 = p[2];
@@ -1082,6 +1117,7 @@ __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel_pa
         float cutoff;
         uint64_t thr;
         int cut_d;
+        int neg_cut;      // -cut_d for q8_pair_excess, kept in step with cut_d
         int n_rescored;   // wave-uniform
         uint64_t* s_cand;
         int* s_count;
@@ -1139,6 +1175,7 @@ __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel_pa
         m.cutoff = q8_uniform(m.cutoff);
         m.thr = q8_uniform(m.thr);
         m.cut_d = q8_uniform(q8_threshold(m.cutoff));
+        m.neg_cut = q8_uniform(q8_pair_neg_cut(m.cut_d));
         m.n_rescored = 0;
     };
     start(A, arg_a, raw_a, n_sample_a, left_a, nbhd_raw_a, &sm->seeds[0]);
@@ -1209,6 +1246,7 @@ __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel_pa
                 const float local_cut = ordered_to_score(static_cast<uint32_t>(m.thr >> 32)) - m.hq.margin;
                 m.cutoff = q8_uniform(local_cut > m.cutoff ? local_cut : m.cutoff);
                 m.cut_d = q8_uniform(q8_threshold(m.cutoff));
+                m.neg_cut = q8_uniform(q8_pair_neg_cut(m.cut_d));
             }
         }
     };
@@ -1216,20 +1254,29 @@ __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel_pa
     auto process_tile = [&](const HalfTile& t, int it) {
         const int64_t quad = quad_begin + static_cast<int64_t>(it) * quad_stride;
         const int64_t r0 = quad * 4;
-        uint32_t hit_a = 0u, hit_b = 0u;   // which of the lane's four rows each query cannot rule out
-        {
-            int a[4];
-            bool special[4];
-            q8_dot4(A.hq, t, a, special);
+        // Most tiles hold no candidate of either query for a whole wave: all they pay for is the question "does any of the
+        // lane's four rows reach either cut" — the largest of the eight excesses — and which rows they are is worked out
+        // only where some lane answers yes.
+        int ea[4], eb[4];
+        q8_pair_excess4(A.hq, A.neg_cut, t, ea);
+        q8_pair_excess4(B.hq, B.neg_cut, t, eb);
+        const bool special[4] = {(t.t0.x & 0xffu) == kQ8Special, (t.t0.w & 0xffu) == kQ8Special, (t.t1.z & 0xffu) == kQ8Special,
+                                 (t.t2.y & 0xffu) == kQ8Special};
+        int top = ea[0] > eb[0] ? ea[0] : eb[0];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) hit_a |= (special[u] | (a[u] >= A.cut_d)) ? (1u << u) : 0u;
-            q8_dot4(B.hq, t, a, special);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) hit_b |= (special[u] | (a[u] >= B.cut_d)) ? (1u << u) : 0u;
+        for (int u = 1; u < 4; ++u) {
+            top = ea[u] > top ? ea[u] : top;
+            top = eb[u] > top ? eb[u] : top;
         }
-        const uint64_t maybe = __ballot((hit_a | hit_b) != 0u);
+        const uint64_t maybe = __ballot(top >= 0 || special[0] || special[1] || special[2] || special[3]);
         consume();   // the rows fetched while the previous tile was scanned
         if (maybe) {   // uniform
+            uint32_t hit_a = 0u, hit_b = 0u;   // which of the lane's four rows each query cannot rule out
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                hit_a |= (special[u] | (ea[u] >= 0)) ? (1u << u) : 0u;
+                hit_b |= (special[u] | (eb[u] >= 0)) ? (1u << u) : 0u;
+            }
             const int64_t left = n - r0;
             const int valid = quad < n_quads ? (left < 4 ? static_cast<int>(left) : 4) : 0;
             const uint32_t inside = (1u << valid) - 1u;   // (padding of the last quad, the clamped prefetch past the end)
@@ -1246,6 +1293,7 @@ __global__ __launch_bounds__(Cfg::kBlock, Cfg::kMinWaves) void scan_q8_kernel_pa
 #pragma unroll
         for (int sidx = 0; sidx < kDepth; ++sidx) {
             load_tile(ring[(sidx + kDepth - 1) % kDepth], it + sidx + kDepth - 1);
+            __builtin_amdgcn_sched_barrier(0);   // (the next tile is asked for before this one's first dot waits for it)
             if (it + sidx < iters) process_tile(ring[sidx], it + sidx);  // uniform
         }
     }
