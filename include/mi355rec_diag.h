@@ -1362,6 +1362,16 @@ int mi355rec_sharded_update_rows(mi355rec_sharded_t* h, const int64_t* global_ro
 int mi355rec_update_info(const mi355rec_t* h, mi355rec_update_info_t* out);
 int mi355rec_replica_entries(mi355rec_t* h, const int64_t* local_rows, int64_t count, void* out_half, void* out_q8, float* out_norms);
 
+/* WHAT A NODE HANDLE IS MADE OF, for a companion library that serves it shard by shard (libmi355rec_embed.so,
+ * include/mi355rec_embed.h).  Host-only accessors: nothing is launched or copied.
+ * mi355rec_sharded_shard_handle: the single-device handle of shard `shard` (a replica of a replicated placement), owned by
+ * the node handle and valid while it lives; the node's workers are drained first, and the caller must keep the node handle
+ * itself idle while it uses the shard's.  INVALID_ARG on the CPU placement and for a shard that does not exist.
+ * mi355rec_sharded_host_rows: the CPU placement's own row-major n x 12 host matrix — the LIVE one, which
+ * mi355rec_sharded_update_rows rewrites in place.  INVALID_ARG on every other placement. */
+int mi355rec_sharded_shard_handle(mi355rec_sharded_t* h, int shard, mi355rec_t** out);
+int mi355rec_sharded_host_rows(const mi355rec_sharded_t* h, const float** rows, int64_t* n);
+
 #ifdef MI355REC_TEST_HOOKS
 /* TEST HOOK for the cross-workgroup hand-offs of the streamed scans (csrc/replica.hip.h, "hand-offs that fail
  * safe": sample values and cutoffs carry the epoch of their query, arrival counters are never reset).  Simulates

@@ -23,7 +23,9 @@ HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc
 OFFLOAD_ARCH = "gfx950"
 
 ENGINE_SOURCES = [CSRC / "mi355rec.hip", CSRC / "sharded.hip"]
-ENGINE_DEPS = ENGINE_SOURCES + sorted(CSRC.glob("*.h")) + [INCLUDE / "mi355rec.h", INCLUDE / "mi355rec_diag.h"]
+# (embed*.h belong to the companion library, build_embed below: the engine includes none of them)
+ENGINE_DEPS = (ENGINE_SOURCES + sorted(p for p in CSRC.glob("*.h") if not p.name.startswith("embed"))
+               + [INCLUDE / "mi355rec.h", INCLUDE / "mi355rec_diag.h"])
 
 # -ffp-contract=off: the parity contract is sequential multiply-then-add with no
 # FMA contraction (Recommender.cu:264-269 compiled by the reference Makefile:9).
@@ -207,6 +209,31 @@ def build_testhooks(force: bool = False) -> Path:
     return build_engine_variant(LIB_TESTHOOKS, ["MI355REC_TEST_HOOKS"], force)
 
 
+# EMBEDDING TABLES: the companion library (include/mi355rec_embed.h).  Its own kernels, the engine's HIP_FLAGS, linked against
+# the product library beside it; the product library's device code is not touched by anything it adds.
+LIB_EMBED = PKG / "libmi355rec_embed.so"
+EMBED_CPU_SRC = CSRC / "embed_cpu.cpp"
+EMBED_CPU_OBJ = PKG / "embed_cpu.o"
+EMBED_DEPS = [CSRC / "embed.hip", CSRC / "embed.hip.h", CSRC / "embed_request.h", EMBED_CPU_SRC, CSRC / "core.hip.h", CSRC / "merge.hip.h",
+              CSRC / "experiments.hip.h", CSRC / "playlist_request.h", INCLUDE / "mi355rec_embed.h", INCLUDE / "mi355rec_diag.h",
+              INCLUDE / "mi355rec.h"]
+
+
+def build_embed(force: bool = False) -> Path:
+    """Compile libmi355rec_embed.so for gfx950; check_no_scratch applies to it exactly as to the product library."""
+    build_engine(force)
+    if force or _stale(LIB_EMBED, EMBED_DEPS + [LIB_ENGINE]):
+        _run(["g++", *CPU_BACKEND_FLAGS, "-c", EMBED_CPU_SRC, "-o", EMBED_CPU_OBJ])
+        _run([HIPCC, *HIP_FLAGS, "-o", LIB_EMBED, CSRC / "embed.hip", f"-Wl,{EMBED_CPU_OBJ}", "-lgomp",
+              f"-L{PKG}", "-lmi355rec", "-Wl,-rpath,$ORIGIN"])
+        try:
+            check_no_scratch(LIB_EMBED)
+        except Exception:
+            LIB_EMBED.unlink(missing_ok=True)
+            raise
+    return LIB_EMBED
+
+
 def shim_sources():
     return [CSRC / "Recommender.cpp", CSRC / "DataManager.cpp"]
 
@@ -247,6 +274,7 @@ def build_all(force: bool = False) -> None:
     build_engine(force)
     build_experiments(force)   # (a second library; nothing in the product loads it)
     build_testhooks(force)     # (a third: the product + the test hooks, for tests/ only)
+    build_embed(force)         # (the companion library: embedding tables over the product's C-ABI)
     build_shim(force)
     build_oracle(force)
 

@@ -375,6 +375,9 @@ SIGNATURES = {
     "mi355rec_sharded_update_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "mi355rec_update_info": (c_int, [c_void_p, POINTER(UpdateInfo)]),
     "mi355rec_replica_entries": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    # what a node handle is made of (host-only accessors for the companion library libmi355rec_embed.so)
+    "mi355rec_sharded_shard_handle": (c_int, [c_void_p, c_int, POINTER(c_void_p)]),
+    "mi355rec_sharded_host_rows": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int64)]),
     "mi355rec_pack_key": (c_uint64, [c_float, c_int64]),
     "mi355rec_key_score": (c_float, [c_uint64]),
     "mi355rec_key_row": (c_int64, [c_uint64]),
@@ -432,6 +435,64 @@ def has_experiments() -> bool:
     if not hasattr(L, "mi355rec_build_flags"):   # (a library of an earlier round, loaded leniently by a tool)
         return False
     return bool(L.mi355rec_build_flags() & BUILD_EXPERIMENTS)
+
+
+# ---- EMBEDDING TABLES: the companion library libmi355rec_embed.so (include/mi355rec_embed.h), a second table ----
+EMBED_LIB_PATH = PKG / "libmi355rec_embed.so"
+EMBED_COSINE, EMBED_DOT = 0, 1
+EMBED_DIMS = (16, 32, 64, 128)
+EMBED_MAX_MEMBERS = 32
+EMBED_MAX_EXCLUDE = 1024
+EMBED_MAX_WEIGHT = 4.0
+
+
+class EmbedQuery(ctypes.Structure):
+    """mi355rec_embed_query_t; `size` is sizeof of this struct (72)."""
+    _fields_ = [("size", c_uint32), ("flags", c_uint32), ("user", c_void_p), ("rows", c_void_p), ("audio", c_void_p),
+                ("exclude_global", c_void_p), ("audio_row", c_int64), ("k", c_int32), ("n_exclude", c_int32), ("topn", c_int32),
+                ("metric", c_int32), ("w_audio", c_float), ("w_embed", c_float)]
+
+
+class EmbedResult(ctypes.Structure):
+    """mi355rec_embed_result_t (32 bytes): out_score and out_count may be NULL."""
+    _fields_ = [("size", c_uint32), ("reserved", c_uint32), ("out_idx", c_void_p), ("out_score", c_void_p), ("out_count", POINTER(c_int))]
+
+
+class EmbedInfo(ctypes.Structure):
+    """mi355rec_embed_info_t (56 bytes)."""
+    _fields_ = [("size", c_uint32), ("dim", c_int32), ("rows", c_int64), ("device_bytes", c_int64), ("tile_rows", c_int32),
+                ("grid", c_int32), ("device", c_int32), ("shards", c_int32), ("queries", c_int64), ("scores_launches", c_int64)]
+
+
+EMBED_SIGNATURES = {
+    "mi355rec_embed_create": (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(c_void_p)]),
+    "mi355rec_embed_create_node": (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(c_void_p)]),
+    "mi355rec_embed_destroy": (None, [c_void_p]),
+    "mi355rec_embed_last_error": (c_char_p, [c_void_p]),
+    "mi355rec_embed_query": (c_int, [c_void_p, POINTER(EmbedQuery), POINTER(EmbedResult)]),
+    "mi355rec_embed_scores": (c_int, [c_void_p, POINTER(EmbedQuery), c_void_p, c_void_p]),
+    "mi355rec_embed_info": (c_int, [c_void_p, POINTER(EmbedInfo)]),
+    "mi355rec_embed_enqueue_probe": (c_int, [c_void_p, c_void_p, c_void_p]),
+}
+
+_embed_lib = None
+
+
+def embed_lib() -> ctypes.CDLL:
+    """Load libmi355rec_embed.so (it links against libmi355rec.so beside it; `lib()` is loaded first so that both share one
+    copy of it and of the HIP runtime).  A missing library is an error: the hybrid scan has no fallback."""
+    global _embed_lib
+    if _embed_lib is None:
+        lib()
+        if not EMBED_LIB_PATH.exists():
+            raise RuntimeError(f"{EMBED_LIB_PATH} is missing: build it with `python -m spotify_recommender_amd.build`")
+        handle = ctypes.CDLL(str(EMBED_LIB_PATH))
+        for name, (restype, argtypes) in EMBED_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _embed_lib = handle
+    return _embed_lib
 
 
 class Mi355Error(RuntimeError):

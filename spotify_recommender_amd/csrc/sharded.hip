@@ -1261,6 +1261,28 @@ int mi355rec_sharded_update_rows(mi355rec_sharded_t* h, const int64_t* global_ro
     return MI355REC_OK;
 }
 
+// What a node handle is made of (include/mi355rec_diag.h): host-only accessors for a companion library.
+int mi355rec_sharded_shard_handle(mi355rec_sharded_t* h, int shard, mi355rec_t** out) {
+    if (!h || !out) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (shard < 0 || shard >= static_cast<int>(h->shards.size()))
+        return sfail(h, MI355REC_ERR_INVALID_ARG, h->cpu ? "the CPU backend has no device shard %d" : "no shard %d", shard);
+    const int drc = drain_workers(h);
+    if (drc) return drc;
+    *out = h->shards[shard].engine;
+    return MI355REC_OK;
+}
+
+int mi355rec_sharded_host_rows(const mi355rec_sharded_t* hc, const float** rows, int64_t* n) {
+    mi355rec_sharded_t* h = const_cast<mi355rec_sharded_t*>(hc);
+    if (!h || !rows || !n) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
+    if (!h->cpu) return sfail(h, MI355REC_ERR_INVALID_ARG, "only the CPU placement keeps its rows on the host");
+    const mi355cpu::Catalogue* c = mi355cpu::node_catalogue(h->cpu);
+    *n = mi355cpu::rows(c);
+    *rows = *n > 0 ? mi355cpu::row(c, 0) : nullptr;
+    return MI355REC_OK;
+}
+
 int mi355rec_sharded_scores_row(mi355rec_sharded_t* h, int64_t global_row, float* out_host) {
     if (!h || !out_host) return sfail(h, MI355REC_ERR_INVALID_ARG, "null argument");
     if (global_row < 0 || global_row >= h->n)
