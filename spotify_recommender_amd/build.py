@@ -234,6 +234,31 @@ def build_embed(force: bool = False) -> Path:
     return LIB_EMBED
 
 
+# USER BATCHES: the second companion library (include/mi355rec_embed_batch.h).  Its own scan kernel over the first
+# companion's helpers (embed.hip.h is included, not edited), the engine's HIP_FLAGS, linked against the product library.
+LIB_EMBED_BATCH = PKG / "libmi355rec_embed_batch.so"
+EMBED_BATCH_DEPS = [CSRC / "embed_batch.hip", CSRC / "embed_batch.hip.h", CSRC / "embed_batch_request.h", CSRC / "embed.hip.h",
+                    CSRC / "embed_request.h", CSRC / "core.hip.h", CSRC / "merge.hip.h", CSRC / "experiments.hip.h", CSRC / "playlist_request.h",
+                    INCLUDE / "mi355rec_embed_batch.h", INCLUDE / "mi355rec_embed.h", INCLUDE / "mi355rec_diag.h", INCLUDE / "mi355rec.h"]
+
+
+def build_embed_batch(force: bool = False, pass_users: int = 0) -> Path:
+    """Compile libmi355rec_embed_batch.so for gfx950; check_no_scratch applies to it exactly as to the product library.
+    pass_users (2, 4 or 8; tools/run_embed_batch.py): a VARIANT beside it, libmi355rec_embed_batch_p<P>.so, whose passes take
+    P users at every dim — what the per-dim choice of the product build is measured from."""
+    build_engine(force)
+    out = PKG / f"libmi355rec_embed_batch_p{pass_users}.so" if pass_users else LIB_EMBED_BATCH
+    defines = [f"-DMI355REC_EMBED_BATCH_PASS_USERS={int(pass_users)}"] if pass_users else []
+    if force or _stale(out, EMBED_BATCH_DEPS + [LIB_ENGINE]):
+        _run([HIPCC, *HIP_FLAGS, *defines, "-o", out, CSRC / "embed_batch.hip", f"-L{PKG}", "-lmi355rec", "-Wl,-rpath,$ORIGIN"])
+        try:
+            check_no_scratch(out)
+        except Exception:
+            out.unlink(missing_ok=True)
+            raise
+    return out
+
+
 def shim_sources():
     return [CSRC / "Recommender.cpp", CSRC / "DataManager.cpp"]
 
@@ -275,6 +300,7 @@ def build_all(force: bool = False) -> None:
     build_experiments(force)   # (a second library; nothing in the product loads it)
     build_testhooks(force)     # (a third: the product + the test hooks, for tests/ only)
     build_embed(force)         # (the companion library: embedding tables over the product's C-ABI)
+    build_embed_batch(force)   # (the second companion: user batches over an embedding table)
     build_shim(force)
     build_oracle(force)
 

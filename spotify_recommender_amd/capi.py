@@ -495,6 +495,59 @@ def embed_lib() -> ctypes.CDLL:
     return _embed_lib
 
 
+# ---- USER BATCHES: the second companion library libmi355rec_embed_batch.so (include/mi355rec_embed_batch.h), a third table ----
+EMBED_BATCH_LIB_PATH = PKG / "libmi355rec_embed_batch.so"
+EMBED_BATCH_MAX_USERS = 1024
+EMBED_BATCH_MAX_TOPN = 128
+EMBED_BATCH_MAX_EXCLUDE = 65536
+
+
+class EmbedBatchQuery(ctypes.Structure):
+    """mi355rec_embed_batch_query_t; `size` is sizeof of this struct (48)."""
+    _fields_ = [("size", c_uint32), ("flags", c_uint32), ("users", c_void_p), ("exclude_global", c_void_p), ("exclude_offsets", c_void_p),
+                ("n_users", c_int32), ("topn", c_int32), ("metric", c_int32), ("w_embed", c_float)]
+
+
+class EmbedBatchResult(ctypes.Structure):
+    """mi355rec_embed_batch_result_t (32 bytes): out_score and out_count may be NULL."""
+    _fields_ = [("size", c_uint32), ("reserved", c_uint32), ("out_idx", c_void_p), ("out_score", c_void_p), ("out_count", c_void_p)]
+
+
+class EmbedBatchInfo(ctypes.Structure):
+    """mi355rec_embed_batch_info_t (56 bytes)."""
+    _fields_ = [("size", c_uint32), ("dim", c_int32), ("rows", c_int64), ("device_bytes", c_int64), ("tile_rows", c_int32),
+                ("grid", c_int32), ("device", c_int32), ("pass_users", c_int32), ("passes", c_int64), ("users_served", c_int64)]
+
+
+EMBED_BATCH_SIGNATURES = {
+    "mi355rec_embed_batch_create": (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(c_void_p)]),
+    "mi355rec_embed_batch_destroy": (None, [c_void_p]),
+    "mi355rec_embed_batch_last_error": (c_char_p, [c_void_p]),
+    "mi355rec_embed_batch_query": (c_int, [c_void_p, POINTER(EmbedBatchQuery), POINTER(EmbedBatchResult)]),
+    "mi355rec_embed_batch_info": (c_int, [c_void_p, POINTER(EmbedBatchInfo)]),
+}
+
+_embed_batch_libs = {}
+
+
+def embed_batch_lib(path=None) -> ctypes.CDLL:
+    """Load libmi355rec_embed_batch.so (it links against libmi355rec.so beside it; `lib()` is loaded first so that both share
+    one copy of it and of the HIP runtime).  A missing library is an error: the batch scan has no fallback.  `path`: a
+    variant built by build.build_embed_batch(pass_users=P) (tools/run_embed_batch.py measures them)."""
+    path = Path(path) if path else EMBED_BATCH_LIB_PATH
+    if path not in _embed_batch_libs:
+        lib()
+        if not path.exists():
+            raise RuntimeError(f"{path} is missing: build it with `python -m spotify_recommender_amd.build`")
+        handle = ctypes.CDLL(str(path))
+        for name, (restype, argtypes) in EMBED_BATCH_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _embed_batch_libs[path] = handle
+    return _embed_batch_libs[path]
+
+
 class Mi355Error(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"mi355rec error {code}: {message}")
