@@ -259,6 +259,28 @@ def build_embed_batch(force: bool = False, pass_users: int = 0) -> Path:
     return out
 
 
+# HALF-PRECISION EMBEDDING TABLES: the third companion library (include/mi355rec_embed_half.h).  Its own scan kernel over
+# the first companion's helpers (embed.hip.h is included, not edited), the engine's HIP_FLAGS, linked against the product
+# library and against neither companion.
+LIB_EMBED_HALF = PKG / "libmi355rec_embed_half.so"
+EMBED_HALF_DEPS = [CSRC / "embed_half.hip", CSRC / "embed_half.hip.h", CSRC / "embed_half_request.h", CSRC / "embed.hip.h",
+                   CSRC / "embed_request.h", CSRC / "core.hip.h", CSRC / "merge.hip.h", CSRC / "experiments.hip.h", CSRC / "playlist_request.h",
+                   INCLUDE / "mi355rec_embed_half.h", INCLUDE / "mi355rec_embed.h", INCLUDE / "mi355rec_diag.h", INCLUDE / "mi355rec.h"]
+
+
+def build_embed_half(force: bool = False) -> Path:
+    """Compile libmi355rec_embed_half.so for gfx950; check_no_scratch applies to it exactly as to the product library."""
+    build_engine(force)
+    if force or _stale(LIB_EMBED_HALF, EMBED_HALF_DEPS + [LIB_ENGINE]):
+        _run([HIPCC, *HIP_FLAGS, "-o", LIB_EMBED_HALF, CSRC / "embed_half.hip", f"-L{PKG}", "-lmi355rec", "-Wl,-rpath,$ORIGIN"])
+        try:
+            check_no_scratch(LIB_EMBED_HALF)
+        except Exception:
+            LIB_EMBED_HALF.unlink(missing_ok=True)
+            raise
+    return LIB_EMBED_HALF
+
+
 def shim_sources():
     return [CSRC / "Recommender.cpp", CSRC / "DataManager.cpp"]
 
@@ -301,6 +323,7 @@ def build_all(force: bool = False) -> None:
     build_testhooks(force)     # (a third: the product + the test hooks, for tests/ only)
     build_embed(force)         # (the companion library: embedding tables over the product's C-ABI)
     build_embed_batch(force)   # (the second companion: user batches over an embedding table)
+    build_embed_half(force)    # (the third companion: fp16 / bf16 embedding tables)
     build_shim(force)
     build_oracle(force)
 

@@ -560,3 +560,44 @@ def check(rc: int, handle=None) -> None:
     L = lib()
     msg = L.mi355rec_last_error(handle) if handle else L.mi355rec_last_global_error()
     raise Mi355Error(rc, (msg or b"").decode("utf-8", "replace"))
+
+
+# ---- HALF-PRECISION EMBEDDING TABLES: the third companion library libmi355rec_embed_half.so
+# (include/mi355rec_embed_half.h), a fourth table.  Queries and results are EmbedQuery / EmbedResult. ----
+EMBED_HALF_LIB_PATH = PKG / "libmi355rec_embed_half.so"
+EMBED_HALF_FP16, EMBED_HALF_BF16 = 0, 1
+
+
+class EmbedHalfInfo(ctypes.Structure):
+    """mi355rec_embed_half_info_t (64 bytes): EmbedInfo's fields, then the storage."""
+    _fields_ = EmbedInfo._fields_ + [("storage", c_int32), ("reserved", c_int32)]
+
+
+EMBED_HALF_SIGNATURES = {
+    "mi355rec_embed_half_create": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, POINTER(c_void_p)]),
+    "mi355rec_embed_half_destroy": (None, [c_void_p]),
+    "mi355rec_embed_half_last_error": (c_char_p, [c_void_p]),
+    "mi355rec_embed_half_query": (c_int, [c_void_p, POINTER(EmbedQuery), POINTER(EmbedResult)]),
+    "mi355rec_embed_half_scores": (c_int, [c_void_p, POINTER(EmbedQuery), c_void_p, c_void_p]),
+    "mi355rec_embed_half_info": (c_int, [c_void_p, POINTER(EmbedHalfInfo)]),
+    "mi355rec_embed_half_enqueue_probe": (c_int, [c_void_p, c_void_p, c_void_p]),
+}
+
+_embed_half_lib = None
+
+
+def embed_half_lib() -> ctypes.CDLL:
+    """Load libmi355rec_embed_half.so (it links against libmi355rec.so beside it; `lib()` is loaded first so that both share
+    one copy of it and of the HIP runtime).  A missing library is an error: the half scan has no fallback."""
+    global _embed_half_lib
+    if _embed_half_lib is None:
+        lib()
+        if not EMBED_HALF_LIB_PATH.exists():
+            raise RuntimeError(f"{EMBED_HALF_LIB_PATH} is missing: build it with `python -m spotify_recommender_amd.build`")
+        handle = ctypes.CDLL(str(EMBED_HALF_LIB_PATH))
+        for name, (restype, argtypes) in EMBED_HALF_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _embed_half_lib = handle
+    return _embed_half_lib

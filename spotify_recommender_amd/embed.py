@@ -36,6 +36,12 @@ class EmbeddingTable:
     """A per-row embedding table over a CosineEngine or a NodeEngine (one row of `table` per row of the engine).  The table
     must be closed before its engine; one call at a time; a node engine must have no call of its own in flight."""
 
+    _PREFIX = "mi355rec_embed_"   # (the entry points and the info struct of the library that serves this class)
+    _INFO = capi.EmbedInfo
+
+    def _fn(self, name):
+        return getattr(self._lib, self._PREFIX + name)
+
     def __init__(self, engine, table):
         self._lib = capi.embed_lib()
         self._e = ctypes.c_void_p()
@@ -55,11 +61,11 @@ class EmbeddingTable:
 
     def _check(self, rc: int) -> None:
         if rc != capi.OK:
-            raise capi.Mi355Error(rc, (self._lib.mi355rec_embed_last_error(self._e) or b"").decode("utf-8", "replace"))
+            raise capi.Mi355Error(rc, (self._fn("last_error")(self._e) or b"").decode("utf-8", "replace"))
 
     def close(self) -> None:
         if getattr(self, "_e", None) is not None and self._e:
-            self._lib.mi355rec_embed_destroy(self._e)
+            self._fn("destroy")(self._e)
             self._e = ctypes.c_void_p()
         self._engine = None
 
@@ -132,7 +138,7 @@ class EmbeddingTable:
         res.out_idx = idx.ctypes.data
         res.out_score = score.ctypes.data
         res.out_count = ctypes.pointer(count)
-        self._check(self._lib.mi355rec_embed_query(self._e, ctypes.byref(q), ctypes.byref(res)))
+        self._check(self._fn("query")(self._e, ctypes.byref(q), ctypes.byref(res)))
         del keep
         assert np.all(idx[count.value:] == -1) and np.all(score[count.value:] == 0)
         return idx[: count.value], score[: count.value]
@@ -142,18 +148,17 @@ class EmbeddingTable:
         q, keep = self._query_struct(user, rows, audio_row, audio, embed_weight, audio_weight, metric, None, 0, False)
         v = np.empty(self.rows, dtype=np.float32)
         c = np.empty(self.rows, dtype=np.float32)
-        self._check(self._lib.mi355rec_embed_scores(self._e, ctypes.byref(q), v.ctypes.data_as(ctypes.c_void_p),
-                                                    c.ctypes.data_as(ctypes.c_void_p)))
+        self._check(self._fn("scores")(self._e, ctypes.byref(q), v.ctypes.data_as(ctypes.c_void_p), c.ctypes.data_as(ctypes.c_void_p)))
         del keep
         return v, c
 
     def info(self) -> dict:
-        out = capi.EmbedInfo()
-        out.size = ctypes.sizeof(capi.EmbedInfo)
-        self._check(self._lib.mi355rec_embed_info(self._e, ctypes.byref(out)))
-        return {name: getattr(out, name) for name, _ in capi.EmbedInfo._fields_ if name != "size"}
+        out = self._INFO()
+        out.size = ctypes.sizeof(self._INFO)
+        self._check(self._fn("info")(self._e, ctypes.byref(out)))
+        return {name: getattr(out, name) for name, _ in self._INFO._fields_ if name not in ("size", "reserved")}
 
     def enqueue_probe(self, sink, stream=None) -> None:
         """A plain read of the table on `stream` (a torch stream or None); sink: a uint32 device tensor of >= 1024 words."""
         s = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-        self._check(self._lib.mi355rec_embed_enqueue_probe(self._e, ctypes.c_void_p(sink.data_ptr()), s))
+        self._check(self._fn("enqueue_probe")(self._e, ctypes.c_void_p(sink.data_ptr()), s))
