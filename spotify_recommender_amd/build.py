@@ -215,7 +215,7 @@ LIB_EMBED = PKG / "libmi355rec_embed.so"
 EMBED_CPU_SRC = CSRC / "embed_cpu.cpp"
 EMBED_CPU_OBJ = PKG / "embed_cpu.o"
 EMBED_DEPS = [CSRC / "embed.hip", CSRC / "embed.hip.h", CSRC / "embed_request.h", EMBED_CPU_SRC, CSRC / "core.hip.h", CSRC / "merge.hip.h",
-              CSRC / "experiments.hip.h", CSRC / "playlist_request.h", INCLUDE / "mi355rec_embed.h", INCLUDE / "mi355rec_diag.h",
+              CSRC / "embed_device.hip.h", CSRC / "experiments.hip.h", CSRC / "playlist_request.h", INCLUDE / "mi355rec_embed.h", INCLUDE / "mi355rec_diag.h",
               INCLUDE / "mi355rec.h"]
 
 
@@ -234,10 +234,11 @@ def build_embed(force: bool = False) -> Path:
     return LIB_EMBED
 
 
-# USER BATCHES: the second companion library (include/mi355rec_embed_batch.h).  Its own scan kernel over the first
-# companion's helpers (embed.hip.h is included, not edited), the engine's HIP_FLAGS, linked against the product library.
+# USER BATCHES: the second companion library (include/mi355rec_embed_batch.h).  Its own scan kernel over the embedding
+# libraries' shared helpers (embed.hip.h, embed_device.hip.h), the engine's HIP_FLAGS, linked against the product library.
 LIB_EMBED_BATCH = PKG / "libmi355rec_embed_batch.so"
 EMBED_BATCH_DEPS = [CSRC / "embed_batch.hip", CSRC / "embed_batch.hip.h", CSRC / "embed_batch_request.h", CSRC / "embed.hip.h",
+                    CSRC / "embed_device.hip.h",
                     CSRC / "embed_request.h", CSRC / "core.hip.h", CSRC / "merge.hip.h", CSRC / "experiments.hip.h", CSRC / "playlist_request.h",
                     INCLUDE / "mi355rec_embed_batch.h", INCLUDE / "mi355rec_embed.h", INCLUDE / "mi355rec_diag.h", INCLUDE / "mi355rec.h"]
 
@@ -259,11 +260,12 @@ def build_embed_batch(force: bool = False, pass_users: int = 0) -> Path:
     return out
 
 
-# HALF-PRECISION EMBEDDING TABLES: the third companion library (include/mi355rec_embed_half.h).  Its own scan kernel over
-# the first companion's helpers (embed.hip.h is included, not edited), the engine's HIP_FLAGS, linked against the product
-# library and against neither companion.
+# HALF-PRECISION EMBEDDING TABLES: the third companion library (include/mi355rec_embed_half.h).  Its row layout under the
+# one scan body and host path of the embedding libraries (embed.hip.h, embed_device.hip.h), the engine's HIP_FLAGS, linked
+# against the product library and against neither companion.
 LIB_EMBED_HALF = PKG / "libmi355rec_embed_half.so"
 EMBED_HALF_DEPS = [CSRC / "embed_half.hip", CSRC / "embed_half.hip.h", CSRC / "embed_half_request.h", CSRC / "embed.hip.h",
+                   CSRC / "embed_device.hip.h",
                    CSRC / "embed_request.h", CSRC / "core.hip.h", CSRC / "merge.hip.h", CSRC / "experiments.hip.h", CSRC / "playlist_request.h",
                    INCLUDE / "mi355rec_embed_half.h", INCLUDE / "mi355rec_embed.h", INCLUDE / "mi355rec_diag.h", INCLUDE / "mi355rec.h"]
 

@@ -3,68 +3,26 @@
 // The companion library owns its kernels (embed.hip.h) and its device buffers and reaches the catalogue only through the
 // product library's C-ABI: mi355rec_stats (rows, row_base, device), mi355rec_enqueue_scores (s(x) of every row into this
 // library's buffer, on this table's stream), mi355rec_fetch_row (an audio row of another shard) and the node handle's
-// accessors.  One mi355rec_embed is one of: a table on one device handle; the host table of a CPU placement
+// accessors.  One mi355rec_embed is one of: a table on one device handle (embed_device.hip.h); the host table of a CPU placement
 // (embed_cpu.cpp); or the parent of one device table per shard of a row-sharded node handle, whose keys it merges on the
 // host (a replicated placement, and a node handle of one shard, are a device table over the first handle).
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstdarg>
 #include <functional>
 #include <memory>
 #include <new>
-#include <string>
-#include <vector>
 
-#include "embed.hip.h"
-#include "embed_request.h"
+#include "embed_device.hip.h"
 
 using namespace mi355;
 
 namespace {
 
-thread_local std::string t_create_error;
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int device) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != device) (void)hipSetDevice(device);
-        else prev = -1;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 enum Kind { kDevice, kCpu, kSharded };
 
 }  // namespace
 
-struct mi355rec_embed {
+struct mi355rec_embed : EmbedDeviceTable {   // (the device table is used by kDevice alone)
     int kind = kDevice;
-    std::string err;
-    int64_t n = 0;
-    int dim = 0;
     int64_t queries = 0;
-    int64_t scores_launches = 0;
-
-    // ---- a table on one device handle ----
-    mi355rec_t* h = nullptr;
-    int device = -1;
-    int cus = 0;
-    int grid = 0;
-    int64_t row_base = 0;
-    hipStream_t stream = nullptr;
-    float* d_table = nullptr;
-    float* d_user = nullptr;
-    float* d_s = nullptr;          // s(x) of every row (allocated by the first call with w_audio != 0)
-    float* d_v = nullptr;          // the parity hook's outputs (allocated by the first _scores call)
-    float* d_c = nullptr;
-    uint32_t* d_excl = nullptr;
-    uint64_t* d_lists = nullptr;   // [grid][MI355REC_MAX_TOPN_FAST]
-    uint64_t* d_keys = nullptr;    // [MI355REC_MAX_TOPN_FAST]
-    int64_t device_bytes = 0;
 
     // ---- the CPU placement ----
     std::vector<float> host_table;
@@ -74,85 +32,17 @@ struct mi355rec_embed {
     mi355rec_sharded_t* node = nullptr;
     std::vector<std::unique_ptr<mi355rec_embed>> shards;   // one per shard that has rows, in row order
     std::vector<mi355rec_t*> shard_handles;
-
-    ~mi355rec_embed() {
-        if (kind != kDevice || device < 0) return;
-        DeviceGuard guard(device);
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (void* p : {static_cast<void*>(d_table), static_cast<void*>(d_user), static_cast<void*>(d_s), static_cast<void*>(d_v),
-                        static_cast<void*>(d_c), static_cast<void*>(d_excl), static_cast<void*>(d_lists), static_cast<void*>(d_keys)})
-            if (p) (void)hipFree(p);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 namespace {
 
-int efail(mi355rec_embed* e, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (e) e->err = buf;
-    else t_create_error = buf;
-    return code;
-}
-
-#define EMBED_HIP_TRY(e, expr)                                                                              \
-    do {                                                                                                    \
-        const hipError_t err_ = (expr);                                                                     \
-        if (err_ != hipSuccess)                                                                             \
-            return efail((e), err_ == hipErrorOutOfMemory ? MI355REC_ERR_OUT_OF_MEMORY : MI355REC_ERR_HIP, \
-                         "%s: %s", #expr, hipGetErrorString(err_));                                         \
-    } while (0)
-
-template <class T>
-int dev_alloc(mi355rec_embed* e, T** p, size_t count) {
-    EMBED_HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * count));
-    e->device_bytes += static_cast<int64_t>(sizeof(T) * count);
-    return MI355REC_OK;
-}
-
-int tile_rows_of(int dim) { return kEmbedTileVecs / (dim / 4); }
-
-// Fills a fresh kDevice table over `h` (its rows are table[0 .. n)).
-int init_device(mi355rec_embed* e, mi355rec_t* h, const float* table, int64_t n, int dim) {
-    mi355rec_stats_t st;
-    if (mi355rec_stats(h, &st) != MI355REC_OK) return efail(e, MI355REC_ERR_INVALID_ARG, "mi355rec_stats: %s", mi355rec_last_error(h));
-    char msg[256];
-    if (mi355embed::invalid_table(table, n, dim, st.rows, msg, sizeof msg)) return efail(e, MI355REC_ERR_INVALID_ARG, "%s", msg);
-    e->kind = kDevice;
-    e->h = h;
-    e->n = n;
-    e->dim = dim;
-    e->device = st.device;
-    e->cus = st.compute_units > 0 ? st.compute_units : 256;
-    e->row_base = st.row_base;
-    DeviceGuard guard(e->device);
-    const int64_t n_tiles = (n * (dim / 4) + kEmbedTileVecs - 1) / kEmbedTileVecs;
-    // two workgroups per CU, tiles dealt round-robin; at most kMergeMaxLists lists reach the merge
-    int64_t grid = std::min<int64_t>(n_tiles, 2 * e->cus);
-    grid = std::min<int64_t>(grid, kMergeMaxLists);
-    e->grid = static_cast<int>(std::max<int64_t>(grid, 1));
-    EMBED_HIP_TRY(e, hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    int rc = MI355REC_OK;
-    if (n > 0 && (rc = dev_alloc(e, &e->d_table, static_cast<size_t>(n) * dim))) return rc;
-    if ((rc = dev_alloc(e, &e->d_user, MI355REC_EMBED_MAX_DIM))) return rc;
-    if ((rc = dev_alloc(e, &e->d_excl, kEmbedMaxExclude))) return rc;
-    if ((rc = dev_alloc(e, &e->d_lists, static_cast<size_t>(e->grid) * MI355REC_MAX_TOPN_FAST))) return rc;
-    if ((rc = dev_alloc(e, &e->d_keys, MI355REC_MAX_TOPN_FAST))) return rc;
-    if (n > 0) EMBED_HIP_TRY(e, hipMemcpy(e->d_table, table, sizeof(float) * static_cast<size_t>(n) * dim, hipMemcpyHostToDevice));
-    return MI355REC_OK;
-}
-
 template <int kDimT>
-void launch_scan_dim(mi355rec_embed* e, const EmbedArgs& a, const float* d_s, float* out_v, float* out_c) {
-    hipLaunchKernelGGL((embed_scan_kernel<kDimT>), dim3(e->grid), dim3(kEmbedBlock), 0, e->stream, e->d_table, e->n, e->row_base,
-                       e->d_user, d_s, e->d_excl, a, e->d_lists, out_v, out_c);
+void launch_scan_dim(EmbedDeviceTable* e, const EmbedArgs& a, const float* d_s, float* out_v, float* out_c) {
+    hipLaunchKernelGGL((embed_scan_kernel<kDimT>), dim3(e->grid), dim3(kEmbedBlock), 0, e->stream, static_cast<const float*>(e->d_table), e->n,
+                       e->row_base, e->d_user, d_s, e->d_excl, a, e->d_lists, out_v, out_c);
 }
 
-void launch_scan(mi355rec_embed* e, const EmbedArgs& a, const float* d_s, float* out_v, float* out_c) {
+void launch_scan(EmbedDeviceTable* e, const EmbedArgs& a, const float* d_s, float* out_v, float* out_c) {
     switch (e->dim) {
         case 16: launch_scan_dim<16>(e, a, d_s, out_v, out_c); break;
         case 32: launch_scan_dim<32>(e, a, d_s, out_v, out_c); break;
@@ -161,88 +51,20 @@ void launch_scan(mi355rec_embed* e, const EmbedArgs& a, const float* d_s, float*
     }
 }
 
-// What both kinds of call enqueue ahead of the scan: the user vector in d_user and, with w_audio != 0, s(x) in d_s.
-int enqueue_inputs(mi355rec_embed* e, const mi355embed::Request& r) {
-    if (r.user) {
-        EMBED_HIP_TRY(e, hipMemcpyAsync(e->d_user, r.user, sizeof(float) * static_cast<size_t>(e->dim), hipMemcpyHostToDevice, e->stream));
-    } else {
-        EmbedMembers m;
-        for (int i = 0; i < kEmbedMaxMembers; ++i) m.rows[i] = i < r.k ? r.rows[i] : 0;
-        m.k = r.k;
-        hipLaunchKernelGGL(embed_user_kernel, dim3(1), dim3(128), 0, e->stream, e->d_table, e->dim, m, e->d_user);
-        EMBED_HIP_TRY(e, hipGetLastError());
-    }
-    if (r.use_audio) {
-        if (!e->d_s) {
-            const int rc = dev_alloc(e, &e->d_s, static_cast<size_t>(e->n));
-            if (rc) return rc;
-        }
-        const int rc = mi355rec_enqueue_scores(e->h, r.audio ? -1 : r.audio_row, r.audio, e->d_s, e->stream);
-        if (rc != MI355REC_OK) return efail(e, rc, "mi355rec_enqueue_scores: %s", mi355rec_last_error(e->h));
-        ++e->scores_launches;
-    }
-    return MI355REC_OK;
+void launch_user(EmbedDeviceTable* e, const EmbedMembers& m) {
+    hipLaunchKernelGGL(embed_user_kernel, dim3(1), dim3(128), 0, e->stream, static_cast<const float*>(e->d_table), e->dim, m, e->d_user);
 }
 
-EmbedArgs args_of(const mi355embed::Request& r, int n_exclude, int topk) {
-    EmbedArgs a;
-    a.w_audio = r.w_audio;
-    a.w_embed = r.w_embed;
-    a.metric = r.metric;
-    a.use_audio = r.use_audio ? 1 : 0;
-    a.n_exclude = n_exclude;
-    a.topk = topk;
-    return a;
-}
+constexpr EmbedTableKind kF32Table = {sizeof(float), 4, launch_scan, launch_user};
 
-// The request's best keys of this device table (sorted descending) into keys_out[0 .. topn), *count of them non-empty.
-int device_keys(mi355rec_embed* e, const mi355embed::Request& r, uint64_t* keys_out, int* count) {
-    *count = 0;
-    if (e->n == 0) return MI355REC_OK;
-    DeviceGuard guard(e->device);
-    const int eff = static_cast<int64_t>(r.topn) < e->n ? r.topn : static_cast<int>(e->n);
-    // the exclusion list as the kernel wants it: local rows of this table, sorted, distinct
-    std::vector<uint32_t> excl;
-    for (int i = 0; i < r.n_exclude; ++i) {
-        const int64_t local = r.exclude[i] - e->row_base;
-        if (local >= 0 && local < e->n) excl.push_back(static_cast<uint32_t>(local));
-    }
-    std::sort(excl.begin(), excl.end());
-    excl.erase(std::unique(excl.begin(), excl.end()), excl.end());
-    if (!excl.empty())
-        EMBED_HIP_TRY(e, hipMemcpyAsync(e->d_excl, excl.data(), sizeof(uint32_t) * excl.size(), hipMemcpyHostToDevice, e->stream));
-    int rc = enqueue_inputs(e, r);
-    if (rc) return rc;
-    launch_scan(e, args_of(r, static_cast<int>(excl.size()), eff), e->d_s, nullptr, nullptr);
-    EMBED_HIP_TRY(e, hipGetLastError());
-    hipLaunchKernelGGL(merge_kernel, dim3(1), dim3(kMergeBlock), 0, e->stream, e->d_lists, e->grid, eff, static_cast<int64_t>(eff),
-                       static_cast<int64_t>(0), eff, e->d_keys, static_cast<int64_t*>(nullptr), static_cast<float*>(nullptr),
-                       static_cast<int64_t>(0), static_cast<uint32_t*>(nullptr), 0u);
-    EMBED_HIP_TRY(e, hipGetLastError());
-    EMBED_HIP_TRY(e, hipMemcpyAsync(keys_out, e->d_keys, sizeof(uint64_t) * static_cast<size_t>(eff), hipMemcpyDeviceToHost, e->stream));
-    EMBED_HIP_TRY(e, hipStreamSynchronize(e->stream));
-    int c = 0;
-    while (c < eff && keys_out[c] != 0ull) ++c;
-    *count = c;
-    return MI355REC_OK;
-}
-
-// v and c of every row of this device table.
-int device_scores(mi355rec_embed* e, const mi355embed::Request& r, float* out_v, float* out_c) {
-    if (e->n == 0) return MI355REC_OK;
-    DeviceGuard guard(e->device);
-    int rc = MI355REC_OK;
-    if (!e->d_v && (rc = dev_alloc(e, &e->d_v, static_cast<size_t>(e->n)))) return rc;
-    if (!e->d_c && (rc = dev_alloc(e, &e->d_c, static_cast<size_t>(e->n)))) return rc;
-    rc = enqueue_inputs(e, r);
-    if (rc) return rc;
-    launch_scan(e, args_of(r, 0, 1), e->d_s, e->d_v, e->d_c);
-    EMBED_HIP_TRY(e, hipGetLastError());
-    const size_t bytes = sizeof(float) * static_cast<size_t>(e->n);
-    EMBED_HIP_TRY(e, hipMemcpyAsync(out_v, e->d_v, bytes, hipMemcpyDeviceToHost, e->stream));
-    if (out_c) EMBED_HIP_TRY(e, hipMemcpyAsync(out_c, e->d_c, bytes, hipMemcpyDeviceToHost, e->stream));
-    EMBED_HIP_TRY(e, hipStreamSynchronize(e->stream));
-    return MI355REC_OK;
+// Fills a fresh kDevice table over `h` (its rows are table[0 .. n)).
+int init_f32(mi355rec_embed* e, mi355rec_t* h, const float* table, int64_t n, int dim) {
+    mi355rec_stats_t st;
+    if (mi355rec_stats(h, &st) != MI355REC_OK) return efail(e, MI355REC_ERR_INVALID_ARG, "mi355rec_stats: %s", mi355rec_last_error(h));
+    char msg[256];
+    if (mi355embed::invalid_table(table, n, dim, st.rows, msg, sizeof msg)) return efail(e, MI355REC_ERR_INVALID_ARG, "%s", msg);
+    e->kind = kDevice;
+    return init_device(e, &kF32Table, h, st, table, n, dim);
 }
 
 // ---- the row-sharded parent: what a shard's table is asked is by VALUE (u and the audio query are formed here) ----
@@ -275,8 +97,8 @@ int sharded_by_value(mi355rec_embed* e, const mi355embed::Request& r, ByValue* b
                                     int64_t local = 0;
                                     mi355rec_embed* s = owner_of(e, row, &local, nullptr);
                                     DeviceGuard guard(s->device);
-                                    if (hipMemcpy(out, s->d_table + local * e->dim, sizeof(float) * static_cast<size_t>(e->dim), hipMemcpyDeviceToHost) !=
-                                        hipSuccess)
+                                    const float* const src = static_cast<const float*>(s->d_table) + local * e->dim;
+                                    if (hipMemcpy(out, src, sizeof(float) * static_cast<size_t>(e->dim), hipMemcpyDeviceToHost) != hipSuccess)
                                         rc = MI355REC_ERR_HIP;
                                 },
                                 bv->u);
@@ -313,7 +135,7 @@ int mi355rec_embed_create(mi355rec_t* h, const float* table_host, int64_t n, int
     if (rc) return rc;
     std::unique_ptr<mi355rec_embed> e(new (std::nothrow) mi355rec_embed());
     if (!e) return efail(nullptr, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory");
-    rc = init_device(e.get(), h, table_host, n, dim);
+    rc = init_f32(e.get(), h, table_host, n, dim);
     if (rc) {
         t_create_error = e->err;
         return rc;
@@ -360,7 +182,7 @@ int mi355rec_embed_create_node(mi355rec_sharded_t* h, const float* table_host, i
         mi355rec_t* first = nullptr;
         if (mi355rec_sharded_shard_handle(h, 0, &first) != MI355REC_OK)
             return efail(nullptr, MI355REC_ERR_INVALID_ARG, "mi355rec_sharded_shard_handle: %s", mi355rec_sharded_last_error(h));
-        rc = init_device(e.get(), first, table_host, n, dim);
+        rc = init_f32(e.get(), first, table_host, n, dim);
         if (rc) {
             t_create_error = e->err;
             return rc;
@@ -381,7 +203,7 @@ int mi355rec_embed_create_node(mi355rec_sharded_t* h, const float* table_host, i
                 return efail(nullptr, MI355REC_ERR_INVALID_ARG, "mi355rec_sharded_shard_handle: %s", mi355rec_sharded_last_error(h));
             std::unique_ptr<mi355rec_embed> child(new (std::nothrow) mi355rec_embed());
             if (!child) return efail(nullptr, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory");
-            rc = init_device(child.get(), sh, table_host + lo * dim, rows, dim);
+            rc = init_f32(child.get(), sh, table_host + lo * dim, rows, dim);
             if (rc == MI355REC_OK && child->row_base != lo) rc = efail(child.get(), MI355REC_ERR_INVALID_ARG, "shard %d starts at row %lld, not %lld", s,
                                                                        static_cast<long long>(child->row_base), static_cast<long long>(lo));
             if (rc) {
@@ -478,7 +300,7 @@ int mi355rec_embed_info(const mi355rec_embed_t* e, mi355rec_embed_info_t* out) {
     out->rows = e->n;
     out->device_bytes = e->device_bytes;
     for (const auto& s : e->shards) out->device_bytes += s->device_bytes;
-    out->tile_rows = e->kind == kCpu ? 0 : tile_rows_of(e->dim);
+    out->tile_rows = e->kind == kCpu ? 0 : embed_tile_rows(e->dim, 4);
     out->grid = e->kind == kCpu ? 0 : first->grid;
     out->device = e->kind == kCpu ? -1 : first->device;
     out->shards = e->kind == kSharded ? static_cast<int32_t>(e->shards.size()) : 1;
@@ -490,14 +312,7 @@ int mi355rec_embed_info(const mi355rec_embed_t* e, mi355rec_embed_info_t* out) {
 int mi355rec_embed_enqueue_probe(mi355rec_embed_t* e, uint32_t* sink_dev, void* stream) {
     if (!e || !sink_dev) return efail(e, MI355REC_ERR_INVALID_ARG, "null argument");
     if (e->kind != kDevice) return efail(e, MI355REC_ERR_INVALID_ARG, "the probe reads a table over one device handle");
-    if (e->n == 0) return MI355REC_OK;
-    DeviceGuard guard(e->device);
-    const int64_t n_vec = e->n * (e->dim / 4);
-    const int grid = static_cast<int>(std::min<int64_t>(2 * e->cus, (n_vec + kEmbedBlock - 1) / kEmbedBlock));
-    hipLaunchKernelGGL(embed_probe_kernel, dim3(grid), dim3(kEmbedBlock), 0, static_cast<hipStream_t>(stream),
-                       reinterpret_cast<const float4*>(e->d_table), n_vec, sink_dev);
-    EMBED_HIP_TRY(e, hipGetLastError());
-    return MI355REC_OK;
+    return enqueue_probe(e, sink_dev, stream);
 }
 
 }  // extern "C"

@@ -2,13 +2,20 @@
 // (include/mi355rec_embed.h has the arithmetic contract), the kernel that forms a user vector from member rows, and the
 // plain read of the table that the scan is measured against.
 //
-// embed_scan_kernel<kDimT> streams the table (n x d fp32, row-major) with 16-byte loads: thread t of a workgroup loads the
-// float4 at vector index tile * kTileVecs + j * kBlock + t, so every wave instruction reads 1 KiB of consecutive bytes.
-// G = d / 4 consecutive lanes hold one row (G divides 64 and kBlock, so a lane's group index g = t % G never changes and
-// its four user values stay in registers): each lane forms its group partial p_g of the dot product and of the row's squared
+// embed_scan_body<Rows, kDimT> is the scan, written once: embed_scan_kernel<kDimT> here and embed_half_scan_kernel
+// (embed_half.hip.h) are one call of it each.  Rows is the layout of a stored row: Word (the table's element), Vec (the
+// 16-byte load), kVals (stored values per load), Row (the widened values a lane holds), widen(Vec) -> Row,
+// user(u, g) -> Row (lane g's values of the user vector) and partial(Row, Row) -> float (the lane's part of the contract's
+// tree).  EmbedRowsF32 below is the fp32 layout (kVals = 4, one group of four per lane); the body derives its lanes per row,
+// its widest tile and its candidate list's capacity from kVals.
+//
+// The body streams the table (n x d, row-major) with 16-byte loads: thread t of a workgroup loads the
+// Vec at vector index tile * kTileVecs + j * kBlock + t, so every wave instruction reads 1 KiB of consecutive bytes.
+// G = d / kVals consecutive lanes hold one row (G divides 64 and kBlock, so a lane's group index g = t % G never changes and
+// its user values stay in registers): each lane forms its partial p_g of the dot product and of the row's squared
 // norm, and log2(G) xor-butterfly steps leave the contract's tree sum in EVERY lane of the group — fl(a + b) is symmetric,
-// so the butterfly's t(l+1) = fl(t_g + t_(g xor 2^l)) is the contract's fl(t_(2g) + t_(2g+1)).  One wave instruction thus
-// covers 16, 8, 4 or 2 rows.  Steps 1 and 2 are quad permutes, 4 and 8 the half-row and row mirrors of DPP (after the
+// so the butterfly's t(l+1) = fl(t_g + t_(g xor 2^l)) is the contract's fl(t_(2g) + t_(2g+1)).  One fp32 wave instruction
+// thus covers 16, 8, 4 or 2 rows.  Steps 1 and 2 are quad permutes, 4 and 8 the half-row and row mirrors of DPP (after the
 // steps before them all lanes they could pick hold one value), 16 a ds_bpermute.
 // s(x), the audio cosine, is read at 4 B per row from the vector mi355rec_enqueue_scores wrote (w_audio != 0 only).
 // Two tiles of kEmbedVecsPerThread loads each are in flight per lane (the tile being scored and the next one, in registers:
@@ -28,9 +35,6 @@ namespace mi355 {
 constexpr int kEmbedBlock = 512;
 constexpr int kEmbedVecsPerThread = 4;                            // 16-byte loads per lane per tile
 constexpr int kEmbedTileVecs = kEmbedBlock * kEmbedVecsPerThread;   // 32 KiB per tile
-constexpr int kEmbedMaxTileRows = kEmbedTileVecs / 4;             // d = 16
-constexpr int kEmbedCandCap = kCandLimit + kEmbedMaxTileRows;
-constexpr int kEmbedCandPerThread = (kEmbedCandCap + kEmbedBlock - 1) / kEmbedBlock;
 constexpr int kEmbedMaxExclude = 1024;
 constexpr int kEmbedMaxMembers = 32;
 
@@ -61,11 +65,11 @@ __device__ __forceinline__ float embed_dpp_mirror(float x) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x140, 0xf, 0xf, true));   // row_mirror
 }
 
-// The levels of the contract's tree over the kGroup lanes of a row; the sum ends in every lane of the group.
+// The levels of the contract's tree over the kGroup lanes of a row (2 to 32); the sum ends in every lane of the group.
 template <int kGroup>
 __device__ __forceinline__ float embed_tree_levels(float p) {
     p = p + embed_dpp_xor1(p);
-    p = p + embed_dpp_xor2(p);
+    if constexpr (kGroup >= 4) p = p + embed_dpp_xor2(p);
     if constexpr (kGroup >= 8) p = p + embed_dpp_half_mirror(p);
     if constexpr (kGroup >= 16) p = p + embed_dpp_mirror(p);
     if constexpr (kGroup >= 32) p = p + __shfl_xor(p, 16, 64);
@@ -114,17 +118,36 @@ __global__ __launch_bounds__(kEmbedBlock) void embed_probe_kernel(const float4* 
     if (threadIdx.x == 0) sink[blockIdx.x] = s_acc;
 }
 
-// table: n x kDimT floats; user: kDimT floats (device); audio_s: n floats or null (use_audio == 0); exclude: n_exclude sorted
-// local rows.  Selecting form (out_v == null): block_lists[gridDim.x][topk].  Scoring form: out_v[n], out_c[n] or null.
-template <int kDimT>
-__global__ __launch_bounds__(kEmbedBlock, 4) void embed_scan_kernel(
-    const float* __restrict__ table, int64_t n, int64_t row_base, const float* __restrict__ user, const float* __restrict__ audio_s,
-    const uint32_t* __restrict__ exclude, EmbedArgs a, uint64_t* __restrict__ block_lists, float* __restrict__ out_v, float* __restrict__ out_c) {
-    constexpr int kGroup = kDimT / 4;                        // lanes per row
+// The fp32 row layout: four stored values per 16-byte load, one group of four per lane.
+struct EmbedRowsF32 {
+    using Word = float;
+    using Vec = float4;
+    using Row = float4;
+    static constexpr int kVals = 4;
+    static __device__ __forceinline__ Row widen(const Vec& w) { return w; }
+    static __device__ __forceinline__ Row user(const float* u, int g) { return reinterpret_cast<const float4*>(u)[g]; }
+    static __device__ __forceinline__ float partial(const Row& a, const Row& b) { return embed_partial(a, b); }
+};
+
+// The scan over a table of n x kDimT Rows::Word (the one body of embed_scan_kernel and embed_half_scan_kernel).
+// user: kDimT floats (device); audio_s: n floats or null (use_audio == 0); exclude: n_exclude sorted local rows.
+// Selecting form (out_v == null): block_lists[gridDim.x][topk].  Scoring form: out_v[n], out_c[n] or null.
+template <class Rows, int kDimT>
+__device__ __forceinline__ void embed_scan_body(const typename Rows::Word* __restrict__ table, int64_t n, int64_t row_base,
+                                                const float* __restrict__ user, const float* __restrict__ audio_s,
+                                                const uint32_t* __restrict__ exclude, EmbedArgs a, uint64_t* __restrict__ block_lists,
+                                                float* __restrict__ out_v, float* __restrict__ out_c) {
+    using Vec = typename Rows::Vec;
+    using Row = typename Rows::Row;
+    constexpr int kGroup = kDimT / Rows::kVals;                        // lanes per row
     constexpr int kTileRows = kEmbedTileVecs / kGroup;
-    static_assert(kGroup >= 4 && kGroup <= 32 && 64 % kGroup == 0, "a row lies inside one wave");
-    static_assert(kTileRows <= kEmbedMaxTileRows, "a tile appends at most kEmbedMaxTileRows candidates");
-    __shared__ uint64_t s_cand[kEmbedCandCap];
+    constexpr int kMaxTileRows = kEmbedTileVecs / (16 / Rows::kVals);   // d = 16
+    constexpr int kCandCap = kCandLimit + kMaxTileRows;
+    constexpr int kCandPerThread = (kCandCap + kEmbedBlock - 1) / kEmbedBlock;
+    static_assert(kGroup >= 2 && kGroup <= 32 && 64 % kGroup == 0, "a row lies inside one wave");
+    static_assert(kTileRows <= kMaxTileRows, "a tile appends at most kMaxTileRows candidates");
+    static_assert(kCandPerThread * kEmbedBlock >= kCandCap, "compact_candidates reads the whole list");
+    __shared__ uint64_t s_cand[kCandCap];
     __shared__ SelectSmem s_sel;
     __shared__ int s_count;
     __shared__ uint32_t s_excl[kEmbedMaxExclude];
@@ -134,10 +157,10 @@ __global__ __launch_bounds__(kEmbedBlock, 4) void embed_scan_kernel(
     const int g = tid & (kGroup - 1);
     const bool selecting = out_v == nullptr;   // uniform
     const int64_t n_vec = n * kGroup;          // n >= 1 (the host launches nothing for an empty table)
-    const float4* const tab4 = reinterpret_cast<const float4*>(table);
+    const Vec* const tab4 = reinterpret_cast<const Vec*>(table);
     const int64_t n_tiles = (n_vec + kEmbedTileVecs - 1) / kEmbedTileVecs;
 
-    auto load_tile = [&](int64_t tile, float4 (&e)[kEmbedVecsPerThread], float (&s)[kEmbedVecsPerThread]) {
+    auto load_tile = [&](int64_t tile, Vec (&e)[kEmbedVecsPerThread], float (&s)[kEmbedVecsPerThread]) {
 #pragma unroll
         for (int j = 0; j < kEmbedVecsPerThread; ++j) {
             int64_t v = tile * kEmbedTileVecs + j * kEmbedBlock + tid;
@@ -146,16 +169,17 @@ __global__ __launch_bounds__(kEmbedBlock, 4) void embed_scan_kernel(
             s[j] = a.use_audio ? audio_s[v / kGroup] : 0.0f;
         }
     };
+    auto tree = [](const Row& x, const Row& y) { return embed_tree_levels<kGroup>(Rows::partial(x, y)); };
 
     int64_t tile = blockIdx.x;
-    float4 cur_e[kEmbedVecsPerThread];
+    Vec cur_e[kEmbedVecsPerThread];
     float cur_s[kEmbedVecsPerThread];
     if (tile < n_tiles) load_tile(tile, cur_e, cur_s);   // requested before the user vector is
 
     if (tid == 0) s_count = 0;
     for (int i = tid; i < a.n_exclude; i += kEmbedBlock) s_excl[i] = exclude[i];
-    const float4 u4 = reinterpret_cast<const float4*>(user)[g];
-    const float nu = sqrtf(embed_tree_levels<kGroup>(embed_partial(u4, u4)));
+    const Row u = Rows::user(user, g);
+    const float nu = sqrtf(tree(u, u));
     __syncthreads();
 
     uint64_t thr = 0;
@@ -164,7 +188,7 @@ __global__ __launch_bounds__(kEmbedBlock, 4) void embed_scan_kernel(
 
     for (; tile < n_tiles; tile += gridDim.x) {   // uniform
         const int64_t next_tile = tile + gridDim.x;
-        float4 next_e[kEmbedVecsPerThread];
+        Vec next_e[kEmbedVecsPerThread];
         float next_s[kEmbedVecsPerThread];
         load_tile(next_tile < n_tiles ? next_tile : tile, next_e, next_s);   // the next tile is in flight while this one is scored
 
@@ -172,10 +196,11 @@ __global__ __launch_bounds__(kEmbedBlock, 4) void embed_scan_kernel(
         for (int j = 0; j < kEmbedVecsPerThread; ++j) {
             const int64_t vec = tile * kEmbedTileVecs + j * kEmbedBlock + tid;
             const int64_t row = vec / kGroup;
-            const float dot = embed_tree_levels<kGroup>(embed_partial(cur_e[j], u4));
+            const Row e = Rows::widen(cur_e[j]);
+            const float dot = tree(e, u);
             float c = dot;
             if (a.metric == 0) {   // uniform
-                const float nn = embed_tree_levels<kGroup>(embed_partial(cur_e[j], cur_e[j]));
+                const float nn = tree(e, e);
                 const float den = sqrtf(nn) * nu;
                 c = 0.0f;
                 if (den > 1e-8f) {
@@ -224,7 +249,7 @@ __global__ __launch_bounds__(kEmbedBlock, 4) void embed_scan_kernel(
             const int c = s_count;
             __syncthreads();
             if (c >= compact_at) {
-                const uint64_t local_thr = compact_candidates<kEmbedBlock, kEmbedCandPerThread>(s_cand, &s_count, a.topk, false, s_sel);
+                const uint64_t local_thr = compact_candidates<kEmbedBlock, kCandPerThread>(s_cand, &s_count, a.topk, false, s_sel);
                 if (local_thr > thr) thr = local_thr;
             }
         }
@@ -238,9 +263,17 @@ __global__ __launch_bounds__(kEmbedBlock, 4) void embed_scan_kernel(
 
     __syncthreads();
     if (s_count > kRankCountMax && s_count > a.topk)   // uniform
-        compact_candidates<kEmbedBlock, kEmbedCandPerThread>(s_cand, &s_count, a.topk, false, s_sel);
+        compact_candidates<kEmbedBlock, kCandPerThread>(s_cand, &s_count, a.topk, false, s_sel);
     __syncthreads();
     block_rank_and_store<kEmbedBlock>(s_cand, s_count, block_lists + static_cast<int64_t>(blockIdx.x) * a.topk, a.topk);
+}
+
+// table: n x kDimT floats; the other arguments and both forms are embed_scan_body's.
+template <int kDimT>
+__global__ __launch_bounds__(kEmbedBlock, 4) void embed_scan_kernel(
+    const float* __restrict__ table, int64_t n, int64_t row_base, const float* __restrict__ user, const float* __restrict__ audio_s,
+    const uint32_t* __restrict__ exclude, EmbedArgs a, uint64_t* __restrict__ block_lists, float* __restrict__ out_v, float* __restrict__ out_c) {
+    embed_scan_body<EmbedRowsF32, kDimT>(table, n, row_base, user, audio_s, exclude, a, block_lists, out_v, out_c);
 }
 
 }  // namespace mi355

@@ -4,16 +4,12 @@
 // reaches the catalogue only through mi355rec_stats (rows, row_base, device).  A call serves its users in groups of
 // pass_users: per group one scan launch and one merge launch (merge_kernel, one workgroup per user of the group), all on
 // the table's stream, one synchronise at the end of the call.
-#include <hip/hip_runtime.h>
-
-#include <cstdarg>
 #include <memory>
 #include <new>
-#include <string>
-#include <vector>
 
 #include "embed_batch.hip.h"
 #include "embed_batch_request.h"
+#include "embed_device.hip.h"
 
 using namespace mi355;
 
@@ -29,20 +25,6 @@ constexpr int kPassUsers = 8;
 
 namespace {
 
-thread_local std::string t_create_error;
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int device) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != device) (void)hipSetDevice(device);
-        else prev = -1;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 int pass_users_of(int dim) {
     switch (dim) {
         case 16: return kPassUsers<16>;
@@ -54,8 +36,7 @@ int pass_users_of(int dim) {
 
 }  // namespace
 
-struct mi355rec_embed_batch {
-    std::string err;
+struct mi355rec_embed_batch : EmbedHandle {
     int64_t n = 0;
     int dim = 0;
     int pass_users = 0;
@@ -73,7 +54,6 @@ struct mi355rec_embed_batch {
     int64_t* d_excl_off = nullptr; // [MAX_USERS + 1]
     uint32_t* d_excl = nullptr;    // the call's exclusion lists (grown on demand)
     size_t excl_cap = 0;
-    int64_t device_bytes = 0;
 
     ~mi355rec_embed_batch() {
         if (device < 0) return;
@@ -88,38 +68,12 @@ struct mi355rec_embed_batch {
 
 namespace {
 
-int bfail(mi355rec_embed_batch* e, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (e) e->err = buf;
-    else t_create_error = buf;
-    return code;
-}
-
-#define EMBED_BATCH_HIP_TRY(e, expr)                                                                        \
-    do {                                                                                                    \
-        const hipError_t err_ = (expr);                                                                     \
-        if (err_ != hipSuccess)                                                                             \
-            return bfail((e), err_ == hipErrorOutOfMemory ? MI355REC_ERR_OUT_OF_MEMORY : MI355REC_ERR_HIP, \
-                         "%s: %s", #expr, hipGetErrorString(err_));                                         \
-    } while (0)
-
-template <class T>
-int dev_alloc(mi355rec_embed_batch* e, T** p, size_t count) {
-    EMBED_BATCH_HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * count));
-    e->device_bytes += static_cast<int64_t>(sizeof(T) * count);
-    return MI355REC_OK;
-}
-
 int init_device(mi355rec_embed_batch* e, mi355rec_t* h, const float* table, int64_t n, int dim) {
     mi355rec_stats_t st;
-    if (mi355rec_stats(h, &st) != MI355REC_OK) return bfail(e, MI355REC_ERR_INVALID_ARG, "mi355rec_stats: %s", mi355rec_last_error(h));
+    if (mi355rec_stats(h, &st) != MI355REC_OK) return efail(e, MI355REC_ERR_INVALID_ARG, "mi355rec_stats: %s", mi355rec_last_error(h));
     char msg[256];
-    if (mi355embed::invalid_table(table, n, dim, st.rows, msg, sizeof msg)) return bfail(e, MI355REC_ERR_INVALID_ARG, "%s", msg);
-    if (st.device < 0) return bfail(e, MI355REC_ERR_INVALID_ARG, "user batches need a handle on a HIP device");
+    if (mi355embed::invalid_table(table, n, dim, st.rows, msg, sizeof msg)) return efail(e, MI355REC_ERR_INVALID_ARG, "%s", msg);
+    if (st.device < 0) return efail(e, MI355REC_ERR_INVALID_ARG, "user batches need a handle on a HIP device");
     e->n = n;
     e->dim = dim;
     e->pass_users = pass_users_of(dim);
@@ -127,12 +81,8 @@ int init_device(mi355rec_embed_batch* e, mi355rec_t* h, const float* table, int6
     e->cus = st.compute_units > 0 ? st.compute_units : 256;
     e->row_base = st.row_base;
     DeviceGuard guard(e->device);
-    const int64_t n_tiles = (n * (dim / 4) + kEmbedTileVecs - 1) / kEmbedTileVecs;
-    // two workgroups per CU, tiles dealt round-robin; at most kMergeMaxLists lists per user reach the merge
-    int64_t grid = std::min<int64_t>(n_tiles, 2 * e->cus);
-    grid = std::min<int64_t>(grid, kMergeMaxLists);
-    e->grid = static_cast<int>(std::max<int64_t>(grid, 1));
-    EMBED_BATCH_HIP_TRY(e, hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+    e->grid = embed_grid(n, dim, 4, e->cus);
+    EMBED_HIP_TRY(e, hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     const size_t max_users = (MI355REC_EMBED_BATCH_MAX_USERS + e->pass_users - 1) / e->pass_users * static_cast<size_t>(e->pass_users);
     int rc = MI355REC_OK;
     if (n > 0 && (rc = dev_alloc(e, &e->d_table, static_cast<size_t>(n) * dim))) return rc;
@@ -140,7 +90,7 @@ int init_device(mi355rec_embed_batch* e, mi355rec_t* h, const float* table, int6
     if ((rc = dev_alloc(e, &e->d_lists, static_cast<size_t>(e->pass_users) * e->grid * MI355REC_EMBED_BATCH_MAX_TOPN))) return rc;
     if ((rc = dev_alloc(e, &e->d_keys, static_cast<size_t>(MI355REC_EMBED_BATCH_MAX_USERS) * MI355REC_EMBED_BATCH_MAX_TOPN))) return rc;
     if ((rc = dev_alloc(e, &e->d_excl_off, MI355REC_EMBED_BATCH_MAX_USERS + 1))) return rc;
-    if (n > 0) EMBED_BATCH_HIP_TRY(e, hipMemcpy(e->d_table, table, sizeof(float) * static_cast<size_t>(n) * dim, hipMemcpyHostToDevice));
+    if (n > 0) EMBED_HIP_TRY(e, hipMemcpy(e->d_table, table, sizeof(float) * static_cast<size_t>(n) * dim, hipMemcpyHostToDevice));
     return MI355REC_OK;
 }
 
@@ -171,7 +121,7 @@ int device_keys(mi355rec_embed_batch* e, const mi355embed::BatchRequest& r, int 
     if (excluding) {
         if (excl.size() > e->excl_cap) {
             if (e->d_excl) {
-                EMBED_BATCH_HIP_TRY(e, hipFree(e->d_excl));
+                EMBED_HIP_TRY(e, hipFree(e->d_excl));
                 e->device_bytes -= static_cast<int64_t>(sizeof(uint32_t) * e->excl_cap);
                 e->d_excl = nullptr;
                 e->excl_cap = 0;
@@ -180,13 +130,13 @@ int device_keys(mi355rec_embed_batch* e, const mi355embed::BatchRequest& r, int 
             if (rc) return rc;
             e->excl_cap = excl.size();
         }
-        EMBED_BATCH_HIP_TRY(e, hipMemcpyAsync(e->d_excl, excl.data(), sizeof(uint32_t) * excl.size(), hipMemcpyHostToDevice, e->stream));
-        EMBED_BATCH_HIP_TRY(e, hipMemcpyAsync(e->d_excl_off, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, e->stream));
+        EMBED_HIP_TRY(e, hipMemcpyAsync(e->d_excl, excl.data(), sizeof(uint32_t) * excl.size(), hipMemcpyHostToDevice, e->stream));
+        EMBED_HIP_TRY(e, hipMemcpyAsync(e->d_excl_off, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, e->stream));
     }
     // the users, padded with zero vectors to whole passes
     std::vector<float> users(static_cast<size_t>(n_pass) * P * e->dim, 0.0f);
     std::copy(r.users, r.users + static_cast<size_t>(r.n_users) * e->dim, users.begin());
-    EMBED_BATCH_HIP_TRY(e, hipMemcpyAsync(e->d_users, users.data(), sizeof(float) * users.size(), hipMemcpyHostToDevice, e->stream));
+    EMBED_HIP_TRY(e, hipMemcpyAsync(e->d_users, users.data(), sizeof(float) * users.size(), hipMemcpyHostToDevice, e->stream));
     for (int pass = 0; pass < n_pass; ++pass) {
         const int user0 = pass * P;
         EmbedBatchArgs a;
@@ -195,17 +145,17 @@ int device_keys(mi355rec_embed_batch* e, const mi355embed::BatchRequest& r, int 
         a.topk = eff;
         a.users = std::min(P, r.n_users - user0);
         launch_scan(e, e->d_users + static_cast<size_t>(user0) * e->dim, excluding ? e->d_excl_off + user0 : nullptr, a);
-        EMBED_BATCH_HIP_TRY(e, hipGetLastError());
+        EMBED_HIP_TRY(e, hipGetLastError());
         ++e->passes;
         // one merge launch for the pass: workgroup b merges the gridDim lists of the pass's user b
         hipLaunchKernelGGL(merge_kernel, dim3(a.users), dim3(kMergeBlock), 0, e->stream, e->d_lists, e->grid, eff, static_cast<int64_t>(eff),
                            static_cast<int64_t>(e->grid) * eff, eff, e->d_keys + static_cast<size_t>(user0) * eff, static_cast<int64_t*>(nullptr),
                            static_cast<float*>(nullptr), static_cast<int64_t>(eff), static_cast<uint32_t*>(nullptr), 0u);
-        EMBED_BATCH_HIP_TRY(e, hipGetLastError());
+        EMBED_HIP_TRY(e, hipGetLastError());
     }
     keys->assign(static_cast<size_t>(r.n_users) * eff, 0ull);
-    EMBED_BATCH_HIP_TRY(e, hipMemcpyAsync(keys->data(), e->d_keys, sizeof(uint64_t) * keys->size(), hipMemcpyDeviceToHost, e->stream));
-    EMBED_BATCH_HIP_TRY(e, hipStreamSynchronize(e->stream));
+    EMBED_HIP_TRY(e, hipMemcpyAsync(keys->data(), e->d_keys, sizeof(uint64_t) * keys->size(), hipMemcpyDeviceToHost, e->stream));
+    EMBED_HIP_TRY(e, hipStreamSynchronize(e->stream));
     return MI355REC_OK;
 }
 
@@ -215,10 +165,10 @@ extern "C" {
 
 int mi355rec_embed_batch_create(mi355rec_t* h, const float* table_host, int64_t n, int dim, mi355rec_embed_batch_t** out) {
     if (out) *out = nullptr;
-    if (!h || !out) return bfail(nullptr, MI355REC_ERR_INVALID_ARG, "null argument");
-    if (n < 0 || (n > 0 && !table_host)) return bfail(nullptr, MI355REC_ERR_INVALID_ARG, "null table or negative n");
+    if (!h || !out) return efail(nullptr, MI355REC_ERR_INVALID_ARG, "null argument");
+    if (n < 0 || (n > 0 && !table_host)) return efail(nullptr, MI355REC_ERR_INVALID_ARG, "null table or negative n");
     std::unique_ptr<mi355rec_embed_batch> e(new (std::nothrow) mi355rec_embed_batch());
-    if (!e) return bfail(nullptr, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory");
+    if (!e) return efail(nullptr, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory");
     const int rc = init_device(e.get(), h, table_host, n, dim);
     if (rc) {
         t_create_error = e->err;
@@ -233,12 +183,12 @@ void mi355rec_embed_batch_destroy(mi355rec_embed_batch_t* e) { delete e; }
 const char* mi355rec_embed_batch_last_error(const mi355rec_embed_batch_t* e) { return e ? e->err.c_str() : t_create_error.c_str(); }
 
 int mi355rec_embed_batch_query(mi355rec_embed_batch_t* e, const mi355rec_embed_batch_query_t* q, const mi355rec_embed_batch_result_t* res) {
-    if (!e) return bfail(nullptr, MI355REC_ERR_INVALID_ARG, "null table");
+    if (!e) return efail(nullptr, MI355REC_ERR_INVALID_ARG, "null table");
     mi355rec_embed_batch_query_t full;
     mi355rec_embed_batch_result_t fres;
     mi355embed::BatchRequest r;
     char msg[256];
-    if (mi355embed::from_batch_query(q, res, &full, &fres, &r, msg, sizeof msg)) return bfail(e, MI355REC_ERR_INVALID_ARG, "%s", msg);
+    if (mi355embed::from_batch_query(q, res, &full, &fres, &r, msg, sizeof msg)) return efail(e, MI355REC_ERR_INVALID_ARG, "%s", msg);
     const int eff = static_cast<int64_t>(r.topn) < e->n ? r.topn : static_cast<int>(e->n);
     std::vector<uint64_t> keys;
     try {
@@ -247,7 +197,7 @@ int mi355rec_embed_batch_query(mi355rec_embed_batch_t* e, const mi355rec_embed_b
             if (rc) return rc;
         }
     } catch (const std::bad_alloc&) {
-        return bfail(e, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory");
+        return efail(e, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory");
     }
     for (int b = 0; b < r.n_users; ++b) {
         const uint64_t* mine = keys.empty() ? nullptr : keys.data() + static_cast<size_t>(b) * eff;
@@ -260,14 +210,14 @@ int mi355rec_embed_batch_query(mi355rec_embed_batch_t* e, const mi355rec_embed_b
 }
 
 int mi355rec_embed_batch_info(const mi355rec_embed_batch_t* e, mi355rec_embed_batch_info_t* out) {
-    if (!e || !out) return bfail(const_cast<mi355rec_embed_batch_t*>(e), MI355REC_ERR_INVALID_ARG, "null argument");
+    if (!e || !out) return efail(const_cast<mi355rec_embed_batch_t*>(e), MI355REC_ERR_INVALID_ARG, "null argument");
     if (out->size != sizeof(mi355rec_embed_batch_info_t))
-        return bfail(const_cast<mi355rec_embed_batch_t*>(e), MI355REC_ERR_INVALID_ARG, "embed batch info of size %u: this library writes %u bytes",
+        return efail(const_cast<mi355rec_embed_batch_t*>(e), MI355REC_ERR_INVALID_ARG, "embed batch info of size %u: this library writes %u bytes",
                      static_cast<unsigned>(out->size), static_cast<unsigned>(sizeof(mi355rec_embed_batch_info_t)));
     out->dim = e->dim;
     out->rows = e->n;
     out->device_bytes = e->device_bytes;
-    out->tile_rows = kEmbedTileVecs / (e->dim / 4);
+    out->tile_rows = embed_tile_rows(e->dim, 4);
     out->grid = e->grid;
     out->device = e->device;
     out->pass_users = e->pass_users;
