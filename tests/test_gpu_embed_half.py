@@ -2,7 +2,8 @@
 embed_half_scan_kernel's answers, both storages, bit for bit against tests/embed_oracle.py over the WIDENED table — v and
 c of every row through the parity hook and the top-N — at the sizes where the kernel can go wrong: the
 rows-per-wave-instruction edges of every dim (32 / 16 / 8 / 4), one tile more or less (1024 rows at d = 16: the candidate
-list's widest append), several workgroups, many tiles per workgroup (compaction), a full grid of lists in the merge; rows
+list's widest append), several workgroups, a full grid of lists in the merge (no workgroup sees more than two tiles
+here; many tiles per workgroup, repeated compaction and a list at its last slot are tests/test_gpu_embed_steady.py's); rows
 that only half storage makes hostile (the largest fp16, the first value that rounds to inf, the smallest fp16 subnormal —
 a flushing kernel scores it as zero — and 3e38); the fp32 library on the widened table; the CPU placement's recorded
 answers; a row base; updated audio rows; two tables of different storage on one handle.  Hostile means values, never
