@@ -25,6 +25,7 @@
 #include "playlist_request.h"
 #include "rows_update.h"
 #include "rowset.h"
+#include "shard_merge.h"
 
 namespace mi355node {
 // mi355rec_set_labels for a handle whose group of lanes the caller has to itself (engine_labels.hip.h): the replicas of a
@@ -98,6 +99,8 @@ Rccl g_rccl;
 struct Shard {
     int device = 0;
     int64_t lo = 0, hi = 0;
+    bool lane = false;                  // a replica on a device that already holds one: a lane of that one (create_on), which
+                                        // shares its rows, replicas and side data
     mi355rec_t* engine = nullptr;
     hipStream_t stream = nullptr;       // the engine's own stream (mi355rec_own_stream): not this struct's to destroy
     bool owns_stream = false;
@@ -696,12 +699,10 @@ int locate_row(mi355rec_sharded* h, int64_t global_row, const float** qptr, floa
     if (!own) return sfail(h, MI355REC_ERR_INVALID_ARG, "Invalid song index: %lld", (long long)global_row);
     *qptr = nullptr;
     if (h->peer_rows) {
-        const int rc = mi355rec_row_ptr(own->engine, global_row - own->lo, qptr);
-        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
-        return MI355REC_OK;
+        S_ENG(h, *own, mi355rec_row_ptr(own->engine, global_row - own->lo, qptr));
+    } else {
+        S_ENG(h, *own, mi355rec_fetch_row(own->engine, global_row - own->lo, q_host));
     }
-    const int rc = mi355rec_fetch_row(own->engine, global_row - own->lo, q_host);
-    if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
     return MI355REC_OK;
 }
 
@@ -732,35 +733,41 @@ int on_whole_catalogue(mi355rec_sharded_t* h, Call&& call) {
     return rc == MI355REC_OK ? rc : sfail(h, rc, "%s", mi355rec_last_error(s->engine));
 }
 
-// A query on a ROW-SHARDED catalogue (the workers drained): call(engine, idx, score, count) asks a shard for its top-`topn`,
-// the per-shard lists are merged on the host by key — exact, since every shard's list holds its best min(topn, rows) keys.
+// A query on a ROW-SHARDED catalogue (the workers drained): call(shard, answer) asks a shard for its top-`topn` — `answer` has what
+// `out` has of idx, score, count, member ("ANY-OF REQUESTS") and total ("BOUNDED REQUESTS": topn may be 0) — and the per-shard
+// lists are merged on the host by key (shard_merge.h: each key's member travels with it, the totals are summed) — exact, since
+// every shard's list holds its best min(topn, rows) keys.  `out` is padded behind the merged list.
 template <class Call>
 int merge_over_shards(mi355rec_sharded_t* h, int topn, const mi355playlist::Outputs& out, Call&& call) {
-    std::vector<mi355rec_key_t> keys;
-    std::vector<int64_t> idx;
-    std::vector<float> sc;
     try {
-        idx.resize(static_cast<size_t>(topn));
-        sc.resize(static_cast<size_t>(topn));
-        keys.reserve(static_cast<size_t>(topn) * h->shards.size());
+        std::vector<mi355rec_key_t> keys(static_cast<size_t>(topn));
+        std::vector<int64_t> idx(static_cast<size_t>(topn));
+        std::vector<float> sc(static_cast<size_t>(topn));
+        std::vector<int32_t> member(out.member ? static_cast<size_t>(topn) : 0);
+        int32_t* const mem = out.member ? member.data() : nullptr;
+        mi355merge::TopKeys merge;
+        merge.reserve(static_cast<size_t>(topn) * h->shards.size());
+        for (Shard& s : h->shards) {
+            if (s.hi <= s.lo) continue;
+            S_HIP(h, hipSetDevice(s.device));
+            int c = 0;
+            int64_t part = 0;
+            S_ENG(h, s, call(s, mi355playlist::Outputs{idx.data(), sc.data(), nullptr, &c, nullptr, mem, out.total ? &part : nullptr}));
+            for (int i = 0; i < c; ++i) keys[static_cast<size_t>(i)] = mi355rec_pack_key(sc[static_cast<size_t>(i)], idx[static_cast<size_t>(i)]);
+            merge.add(keys.data(), mem, c, part);
+        }
+        const int count = merge.finish(topn, keys.data(), mem);
+        for (int i = 0; i < count; ++i) {
+            out.idx[i] = mi355rec_key_row(keys[static_cast<size_t>(i)]);
+            if (out.score) out.score[i] = mi355rec_key_score(keys[static_cast<size_t>(i)]);
+            if (mem) out.member[i] = mem[i];
+        }
+        if (out.total) *out.total = merge.total;
+        if (topn > 0) mi355playlist::pad(out, count, topn, count);
+        else if (out.count) *out.count = 0;
     } catch (const std::bad_alloc&) {
         return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for %d results per shard", topn);
     }
-    for (Shard& s : h->shards) {
-        if (s.hi <= s.lo) continue;
-        S_HIP(h, hipSetDevice(s.device));
-        int c = 0;
-        const int rc = call(s.engine, idx.data(), sc.data(), &c);
-        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", s.device, mi355rec_last_error(s.engine));
-        for (int i = 0; i < c; ++i) keys.push_back(mi355rec_pack_key(sc[static_cast<size_t>(i)], idx[static_cast<size_t>(i)]));
-    }
-    const size_t count = keys.size() < static_cast<size_t>(topn) ? keys.size() : static_cast<size_t>(topn);
-    std::partial_sort(keys.begin(), keys.begin() + count, keys.end(), std::greater<mi355rec_key_t>());
-    for (size_t i = 0; i < count; ++i) {
-        out.idx[i] = mi355rec_key_row(keys[i]);
-        if (out.score) out.score[i] = mi355rec_key_score(keys[i]);
-    }
-    mi355playlist::pad(out, static_cast<int>(count), topn, static_cast<int>(count));
     return MI355REC_OK;
 }
 

@@ -78,26 +78,41 @@ int wait_window(mi355rec_sharded* h, int w) {
     return MI355REC_OK;
 }
 
-// Buffers for (topn, window); a change of geometry closes the stream first.  All or nothing.
-int ensure_stream(mi355rec_sharded* h, int topn) {
-    if (h->s_topn == topn && h->s_alloc_window == h->s_window) return MI355REC_OK;
-    if (h->s_topn) {
-        int rc = stream_flush(h);
-        if (rc) return rc;
-        rc = drain_workers(h);
-        if (rc) return rc;
-        for (Shard& s : h->shards) {
-            S_HIP(h, hipSetDevice(s.device));
-            S_HIP(h, hipStreamSynchronize(s.stream));
-        }
-        free_stream(h);
+// STOP THE STREAM BEFORE THE HANDLE CHANGES.  quiesce: the open window is closed as the handle stands (its geometry, its
+// transport, its rows), the workers have issued everything they were handed, and every shard's stream has run dry (the workers
+// only ENQUEUE a window's scans).  Tickets handed out so far stay readable: their results are in host memory.
+int quiesce(mi355rec_sharded* h) {
+    int rc = stream_flush(h);
+    if (rc) return rc;
+    rc = drain_workers(h);
+    if (rc) return rc;
+    for (Shard& s : h->shards) {
+        S_HIP(h, hipSetDevice(s.device));
+        S_HIP(h, hipStreamSynchronize(s.stream));
     }
+    return MI355REC_OK;
+}
+
+// ... reset_stream, behind it: the stream's buffers are gone and its ring is empty — the next enqueue makes them again
+// (ensure_stream) for whatever geometry and window mode the handle has by then; no earlier ticket can be waited for any more.
+void reset_stream(mi355rec_sharded* h) {
+    free_stream(h);
     for (Window& w : h->win) {
         w.abs = -1;
         w.count = 0;
         w.handed = false;
         w.issued = false;
     }
+}
+
+// Buffers for (topn, window); a change of geometry closes the stream first.  All or nothing.
+int ensure_stream(mi355rec_sharded* h, int topn) {
+    if (h->s_topn == topn && h->s_alloc_window == h->s_window) return MI355REC_OK;
+    if (h->s_topn) {
+        const int rc = quiesce(h);
+        if (rc) return rc;
+    }
+    reset_stream(h);
     // tickets keep growing across a change of geometry, window-aligned in the new one
     h->next_ticket = (h->next_ticket + h->s_window - 1) / h->s_window * h->s_window;
     h->issued_upto = h->next_ticket;

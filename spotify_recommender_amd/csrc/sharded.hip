@@ -40,6 +40,13 @@
 // A query by ROW never comes back to the host: every shard's kernels read its 48 bytes from
 // the owning shard's memory through the peer mapping (checked once at create time against
 // the by-value path; without all-pairs peer access the row is fetched once per query).
+// REQUESTS (the playlist family of include/mi355rec_diag.h) on a row-sharded catalogue are driven by the caller's thread: every shard
+// answers with its own leading keys and ONE host merge makes the node's answer of them (merge_over_shards in node_state.hip.h, over
+// the accumulator of shard_merge.h): an any-of request's member indices and a bounded request's totals travel through that merge.
+// Whatever changes the handle under the stream (window, window mode, topn, rows) goes through ONE pair in node_stream.hip.h:
+// quiesce() closes the open window, drains the workers and waits for every shard's stream; reset_stream() drops the stream's
+// buffers and empties its ring.  Shard::lane, set at create time, marks a replica that shares a device — and so its rows and side
+// data — with an earlier one.
 //
 // PLACEMENT (mi355rec_create_placed).  Row sharding is what north_star specifies and the only way to a lower
 // latency once a scan is longer than its launches; but a shard below ~4 M rows is launch-bound (measured on one
@@ -150,6 +157,7 @@ int create_on(const float* feats_host, int64_t n, int dim, const int* devices, i
         int same = -1;
         for (int p = 0; p < r && replicated && same < 0; ++p)
             if (h->shards[p].device == s.device) same = p;
+        s.lane = same >= 0;
         const int rc = same >= 0 ? mi355rec_create_lane(h->shards[same].engine, &s.engine)
                                  : mi355rec_create(s.hi > s.lo ? feats_host + s.lo * MI355REC_DIM : nullptr, s.hi - s.lo, dim, s.device,
                                                    s.lo, &s.engine);
@@ -249,11 +257,8 @@ int set_on_every_shard(mi355rec_sharded_t* h, const char* noun, SetShard set_sha
     DeviceRestore restore;
     int rc = drain_workers(h);
     if (rc) return rc;
-    for (size_t r = 0; r < h->shards.size(); ++r) {
-        Shard& s = h->shards[r];
-        bool lane = false;
-        for (size_t p = 0; p < r && h->replicated && !lane; ++p) lane = h->shards[p].device == s.device;
-        if (lane) continue;
+    for (Shard& s : h->shards) {
+        if (s.lane) continue;
         S_HIP(h, hipSetDevice(s.device));
         rc = set_shard(s.engine, &s);
         if (rc != MI355REC_OK) {
@@ -526,8 +531,7 @@ int mi355rec_sharded_query_row_topn(mi355rec_sharded_t* h, int64_t global_row, i
     if (eff > MI355REC_MAX_TOPN_FAST) {
         if (qptr) {   // cold path: by value
             const Shard* own = owner_of(h, global_row);
-            rc = mi355rec_fetch_row(own->engine, global_row - own->lo, q);
-            if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
+            S_ENG(h, *own, mi355rec_fetch_row(own->engine, global_row - own->lo, q));
         }
         return run_queries_large(h, q, &global_row, 1, eff, topn, out_idx, out_score, out_count);
     }
@@ -613,8 +617,9 @@ namespace {
 int sharded_labels_by_value(mi355rec_sharded_t* h, const float* q, int64_t exclude_global, const int32_t* labels, int n_labels,
                             int topn, int64_t* out_idx, float* out_score, int* out_count) {
     return merge_over_shards(h, topn, {out_idx, out_score, nullptr, out_count, nullptr},
-                             [&](mi355rec_t* e, int64_t* idx, float* sc, int* c) {
-                                 return mi355rec_query_topn_labels(e, q, exclude_global, labels, n_labels, topn, idx, sc, c);
+                             [&](const Shard& s, const mi355playlist::Outputs& mine) {
+                                 return mi355rec_query_topn_labels(s.engine, q, exclude_global, labels, n_labels, topn, mine.idx, mine.score,
+                                                                   mine.count);
                              });
 }
 }  // namespace
@@ -654,13 +659,12 @@ int mi355rec_sharded_query_row_topn_labels(mi355rec_sharded_t* h, int64_t global
         return on_whole_catalogue(h, [&](mi355rec_t* e) {
             return mi355rec_query_row_topn_labels(e, global_row, labels, n_labels, topn, out_idx, out_score, out_count);
         });
-    int rc = drain_workers(h);
+    const int rc = drain_workers(h);
     if (rc) return rc;
     const Shard* own = owner_of(h, global_row);
     float q[MI355REC_DIM];
     S_HIP(h, hipSetDevice(own->device));
-    rc = mi355rec_fetch_row(own->engine, global_row - own->lo, q);
-    if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
+    S_ENG(h, *own, mi355rec_fetch_row(own->engine, global_row - own->lo, q));
     return sharded_labels_by_value(h, q, global_row, labels, n_labels, topn, out_idx, out_score, out_count);
 }
 
@@ -670,23 +674,21 @@ using mi355playlist::Outputs;
 using mi355playlist::Request;
 using mi355playlist::request;
 
-// CANDIDATE LISTS on a ROW-SHARDED catalogue: the request as the shard of engine `e` takes it, its list cut down to the ids of that
-// shard's range (candidates.h).  A shard with none gets an empty list: its call launches nothing, as one with nothing left to return.
+// CANDIDATE LISTS on a ROW-SHARDED catalogue: the request as the shard of rows [lo, hi) takes it, its list cut down to the ids of
+// that range (candidates.h); a request without a list as it is.  A shard with none gets an empty list: its call launches nothing,
+// as one with nothing left to return.
 struct ShardLists {
     std::vector<int64_t> ids;   // the list of the shard asked for last (the shards are asked one after the other)
-    Request of(const mi355rec_sharded_t* h, const Request& r, const mi355rec_t* e) {
+    Request of(const Request& r, int64_t lo, int64_t hi) {
         if (!r.listed) return r;
+        try {
+            mi355cand::split(r.candidates, r.n_candidates, lo, hi, &ids);
+        } catch (const std::bad_alloc&) {
+            return r;   // (the whole list: the shard matches the ids of its own rows itself)
+        }
         Request mine = r;
-        for (const Shard& s : h->shards)
-            if (s.engine == e) {
-                try {
-                    mi355cand::split(r.candidates, r.n_candidates, s.lo, s.hi, &ids);
-                } catch (const std::bad_alloc&) {
-                    return r;   // (the whole list: the shard matches the ids of its own rows itself)
-                }
-                mine.candidates = ids.data();
-                mine.n_candidates = static_cast<int64_t>(ids.size());
-            }
+        mine.candidates = ids.data();
+        mine.n_candidates = static_cast<int64_t>(ids.size());
         return mine;
     }
 };
@@ -718,8 +720,8 @@ int diverse_over_shards(mi355rec_sharded_t* h, const Request& r, const Outputs& 
     const Request mean = r.pool_call();
     ShardLists lists;
     rc = merge_over_shards(h, pool, {pidx.data(), prel.data(), nullptr, &p_eff, nullptr},
-                           [&](mi355rec_t* e, int64_t* idx, float* sc, int* c) {
-                               return mi355node::query_playlist(e, lists.of(h, mean, e), {idx, sc, nullptr, c, nullptr});
+                           [&](const Shard& s, const Outputs& mine) {
+                               return mi355node::query_playlist(s.engine, lists.of(mean, s.lo, s.hi), mine);
                            });
     if (rc) return rc;
     if (p_eff <= 0) {
@@ -737,8 +739,7 @@ int diverse_over_shards(mi355rec_sharded_t* h, const Request& r, const Outputs& 
             }
         if (local.empty()) continue;
         S_HIP(h, hipSetDevice(s.device));
-        rc = mi355rec_fetch_rows(s.engine, local.data(), static_cast<int64_t>(local.size()), part.data());
-        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", s.device, mi355rec_last_error(s.engine));
+        S_ENG(h, s, mi355rec_fetch_rows(s.engine, local.data(), static_cast<int64_t>(local.size()), part.data()));
         for (size_t j = 0; j < where.size(); ++j)
             std::memcpy(rows.data() + static_cast<size_t>(where[j]) * MI355REC_DIM, part.data() + j * MI355REC_DIM, sizeof(float) * MI355REC_DIM);
     }
@@ -750,9 +751,9 @@ int diverse_over_shards(mi355rec_sharded_t* h, const Request& r, const Outputs& 
         }
     S_HIP(h, hipSetDevice(first->device));
     for (int i = 0; r.capped && i < p_eff; ++i) pgroups[static_cast<size_t>(i)] = h->groups[static_cast<size_t>(pidx[static_cast<size_t>(i)])];
-    rc = mi355node::rerank_pool(first->engine, pidx.data(), prel.data(), rows.data(), p_eff, r.lambda, r.topn, out.idx, out.score, out.mmr,
-                                out.count, r.capped ? pgroups.data() : nullptr, r.max_per_group, out.pool_rows);
-    return rc == MI355REC_OK ? rc : sfail(h, rc, "shard on device %d: %s", first->device, mi355rec_last_error(first->engine));
+    S_ENG(h, *first, mi355node::rerank_pool(first->engine, pidx.data(), prel.data(), rows.data(), p_eff, r.lambda, r.topn, out.idx, out.score,
+                                            out.mmr, out.count, r.capped ? pgroups.data() : nullptr, r.max_per_group, out.pool_rows));
+    return MI355REC_OK;
 }
 
 // By row, one handle (row_base 0) takes its own by-row call: the members stay on the device.  Otherwise the members go by value
@@ -773,90 +774,12 @@ int members_by_value(mi355rec_sharded_t* h, Request& r, float* members, int64_t*
         DeviceRestore restore;
         const Shard* own = owner_of(h, r.rows[m]);
         S_HIP(h, hipSetDevice(own->device));
-        const int rc = mi355rec_fetch_row(own->engine, r.rows[m] - own->lo, members + m * MI355REC_DIM);
-        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
+        S_ENG(h, *own, mi355rec_fetch_row(own->engine, r.rows[m] - own->lo, members + m * MI355REC_DIM));
     }
     r.members = members;
     r.rows = nullptr;
     r.exclude = excl;
     r.n_exclude += r.k;
-    return MI355REC_OK;
-}
-
-// "ANY-OF REQUESTS" with out_member on a ROW-SHARDED catalogue (members by value, the workers drained): merge_over_shards' merge with
-// each key's member index carried through it (rows are distinct across shards, so the keys are).
-int anyof_over_shards(mi355rec_sharded_t* h, const Request& r, const Outputs& out) {
-    const int topn = r.topn;
-    std::vector<std::pair<mi355rec_key_t, int32_t>> keys;
-    std::vector<int64_t> idx;
-    std::vector<float> sc;
-    std::vector<int32_t> mem;
-    try {
-        idx.resize(static_cast<size_t>(topn));
-        sc.resize(static_cast<size_t>(topn));
-        mem.resize(static_cast<size_t>(topn));
-        keys.reserve(static_cast<size_t>(topn) * h->shards.size());
-    } catch (const std::bad_alloc&) {
-        return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for %d results per shard", topn);
-    }
-    for (Shard& s : h->shards) {
-        if (s.hi <= s.lo) continue;
-        S_HIP(h, hipSetDevice(s.device));
-        int c = 0;
-        const int rc = mi355node::query_playlist(s.engine, r, {idx.data(), sc.data(), nullptr, &c, nullptr, mem.data()});
-        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", s.device, mi355rec_last_error(s.engine));
-        for (int i = 0; i < c; ++i)
-            keys.emplace_back(mi355rec_pack_key(sc[static_cast<size_t>(i)], idx[static_cast<size_t>(i)]), mem[static_cast<size_t>(i)]);
-    }
-    const size_t count = keys.size() < static_cast<size_t>(topn) ? keys.size() : static_cast<size_t>(topn);
-    std::partial_sort(keys.begin(), keys.begin() + count, keys.end(),
-                      [](const std::pair<mi355rec_key_t, int32_t>& a, const std::pair<mi355rec_key_t, int32_t>& b) { return a.first > b.first; });
-    for (size_t i = 0; i < count; ++i) {
-        out.idx[i] = mi355rec_key_row(keys[i].first);
-        if (out.score) out.score[i] = mi355rec_key_score(keys[i].first);
-        out.member[i] = keys[i].second;
-    }
-    mi355playlist::pad(out, static_cast<int>(count), topn, static_cast<int>(count));
-    return MI355REC_OK;
-}
-
-// "BOUNDED REQUESTS" on a ROW-SHARDED catalogue (members by value, the workers drained): every shard answers with its own leading
-// matches (already cut at the floor: keys of the score, or of -m) and its own total; the keys are merged on the host, the totals summed.
-int bounded_over_shards(mi355rec_sharded_t* h, Request r, const Outputs& out) {
-    const int topn = r.topn;
-    const bool report_distance = r.report_distance;
-    r.report_distance = false;   // (the shards answer with what the keys carry; the distances are taken from the merged list)
-    std::vector<mi355rec_key_t> keys;
-    std::vector<int64_t> idx;
-    std::vector<float> sc;
-    try {
-        idx.resize(static_cast<size_t>(topn));
-        sc.resize(static_cast<size_t>(topn));
-        keys.reserve(static_cast<size_t>(topn) * h->shards.size());
-    } catch (const std::bad_alloc&) {
-        return sfail(h, MI355REC_ERR_OUT_OF_MEMORY, "out of host memory for %d results per shard", topn);
-    }
-    int64_t total = 0;
-    for (Shard& s : h->shards) {
-        if (s.hi <= s.lo) continue;
-        S_HIP(h, hipSetDevice(s.device));
-        int c = 0;
-        int64_t part = 0;
-        const int rc = mi355node::query_playlist(s.engine, r, {idx.data(), sc.data(), nullptr, &c, nullptr, nullptr, &part});
-        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", s.device, mi355rec_last_error(s.engine));
-        total += part;
-        for (int i = 0; i < c; ++i) keys.push_back(mi355rec_pack_key(sc[static_cast<size_t>(i)], idx[static_cast<size_t>(i)]));
-    }
-    const size_t count = keys.size() < static_cast<size_t>(topn) ? keys.size() : static_cast<size_t>(topn);
-    std::partial_sort(keys.begin(), keys.begin() + count, keys.end(), [](mi355rec_key_t a, mi355rec_key_t b) { return a > b; });
-    for (size_t i = 0; i < count; ++i) {
-        out.idx[i] = mi355rec_key_row(keys[i]);
-        if (out.score) out.score[i] = mi355rec_key_score(keys[i]);
-    }
-    *out.total = total;
-    if (topn > 0) mi355playlist::pad(out, static_cast<int>(count), topn, static_cast<int>(count));
-    else if (out.count) *out.count = 0;
-    if (report_distance && topn > 0) mi355playlist::scores_to_distances(out, topn, r.metric);
     return MI355REC_OK;
 }
 
@@ -889,15 +812,15 @@ int sharded_playlist(mi355rec_sharded_t* h, Request r, const Outputs& out) {
     if (r.diverse) return diverse_over_shards(h, r, out);
     const int rc = drain_workers(h);
     if (rc) return rc;
-    // every shard gets the whole exclusion list and matches the ids of its own rows ("DISTANCE REQUESTS": the shards answer
-    // with -m, what the merge's keys compare; the distances are taken from the merged list)
-    if (r.metric == mi355playlist::kAnyOf && out.member) return anyof_over_shards(h, r, out);
-    if (r.bounded) return bounded_over_shards(h, r, out);
+    // every shard gets the whole exclusion list and matches the ids of its own rows, and its own cut of a candidate list; it
+    // answers with its leading keys, each with its member where `out` has members ("ANY-OF REQUESTS"), and its own total where
+    // `out` has one ("BOUNDED REQUESTS": the keys are cut at the floor already).  "DISTANCE REQUESTS": the shards answer with -m,
+    // what the merge's keys compare; the distances are taken from the merged list.
     const bool report_distance = r.report_distance;
     r.report_distance = false;
     ShardLists lists;
-    const int merged = merge_over_shards(h, r.topn, out, [&](mi355rec_t* e, int64_t* idx, float* sc, int* c) {
-        return mi355node::query_playlist(e, lists.of(h, r, e), {idx, sc, nullptr, c, nullptr});
+    const int merged = merge_over_shards(h, r.topn, out, [&](const Shard& s, const Outputs& mine) {
+        return mi355node::query_playlist(s.engine, lists.of(r, s.lo, s.hi), mine);
     });
     if (merged == MI355REC_OK && report_distance) mi355playlist::scores_to_distances(out, r.topn, r.metric);
     return merged;
@@ -952,8 +875,7 @@ int sharded_scores(mi355rec_sharded_t* h, Request r, const mi355playlist::ScoreO
         mine.candidates = ids.data();
         mine.n_candidates = static_cast<int64_t>(ids.size());
         S_HIP(h, hipSetDevice(s.device));
-        rc = mi355node::score_playlist(s.engine, mine, {value.data(), admissible.data()});
-        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", s.device, mi355rec_last_error(s.engine));
+        S_ENG(h, s, mi355node::score_playlist(s.engine, mine, {value.data(), admissible.data()}));
         for (size_t j = 0; j < where.size(); ++j) {
             out.value[where[j]] = value[j];
             if (out.admissible) out.admissible[where[j]] = admissible[j];
@@ -1100,7 +1022,7 @@ int mi355rec_sharded_query_distance_request(mi355rec_sharded_t* h, const mi355re
 }
 
 // ANY-OF REQUESTS (include/mi355rec_diag.h): the same Request with metric = kAnyOf through sharded_playlist; a row-sharded catalogue
-// carries each key's member index through its host merge (anyof_over_shards).
+// carries each key's member index through its host merge (merge_over_shards).
 int mi355rec_sharded_query_anyof_request(mi355rec_sharded_t* h, const mi355rec_anyof_query_t* query, const mi355rec_request_ext_t* ext,
                                          const mi355rec_anyof_result_t* result) {
     return node_request_entry(h, query, ext, result, {});
@@ -1121,7 +1043,7 @@ int mi355rec_sharded_query_jaccard_request(mi355rec_sharded_t* h, const mi355rec
 }
 
 // BOUNDED REQUESTS (include/mi355rec_diag.h): the same Request with `bounded` through sharded_playlist; a row-sharded catalogue merges
-// the shards' matches and sums their totals (bounded_over_shards).
+// the shards' matches and sums their totals (merge_over_shards).
 int mi355rec_sharded_query_bounded_request(mi355rec_sharded_t* h, const mi355rec_bounded_query_t* query, const mi355rec_request_ext_t* ext,
                                            const mi355rec_bounded_result_t* result) {
     return node_request_entry(h, query, ext, result, {});
@@ -1224,16 +1146,10 @@ int mi355rec_sharded_update_rows(mi355rec_sharded_t* h, const int64_t* global_ro
         return cpu_result(h, mi355cpu::node_update_rows(h->cpu, global_rows, count, feats_host, &why), why);
     }
     DeviceRestore restore;
-    int rc = stream_flush(h);
-    if (rc) return rc;
-    rc = drain_workers(h);
-    if (rc) return rc;
     // (the workers have only ENQUEUED the window's scans: every shard's stream is drained before a row is written, as ensure_stream
     // does before it replaces the stream's buffers — the engines wait for their lanes' streams again themselves)
-    for (Shard& s : h->shards) {
-        S_HIP(h, hipSetDevice(s.device));
-        S_HIP(h, hipStreamSynchronize(s.stream));
-    }
+    const int rc = quiesce(h);
+    if (rc) return rc;
     // A failure on one shard leaves the shards before it updated: the update may have been applied in part, and repeating it
     // (the same rows, the same features) is safe.
     for (size_t r = 0; r < h->shards.size(); ++r) {
@@ -1241,9 +1157,7 @@ int mi355rec_sharded_update_rows(mi355rec_sharded_t* h, const int64_t* global_ro
         if (s.hi == s.lo) continue;
         S_HIP(h, hipSetDevice(s.device));
         if (parts.empty()) {   // one shard, or replicas: the whole list, once per device
-            bool lane = false;
-            for (size_t p = 0; p < r && !lane; ++p) lane = h->shards[p].device == s.device;
-            if (lane) continue;
+            if (s.lane) continue;
             S_ENG(h, s, mi355rec_update_rows(s.engine, global_rows, count, feats_host));
             continue;
         }
@@ -1304,12 +1218,10 @@ int mi355rec_sharded_scores_row(mi355rec_sharded_t* h, int64_t global_row, float
     const Shard* own = owner_of(h, global_row);
     int rc = drain_workers(h);   // cold path: the caller's thread drives every shard itself
     if (rc) return rc;
-    rc = mi355rec_fetch_row(own->engine, global_row - own->lo, q);
-    if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", own->device, mi355rec_last_error(own->engine));
+    S_ENG(h, *own, mi355rec_fetch_row(own->engine, global_row - own->lo, q));
     for (const Shard& s : h->shards) {
         if (s.hi == s.lo) continue;
-        rc = mi355rec_scores(s.engine, q, out_host + s.lo);
-        if (rc != MI355REC_OK) return sfail(h, rc, "shard on device %d: %s", s.device, mi355rec_last_error(s.engine));
+        S_ENG(h, s, mi355rec_scores(s.engine, q, out_host + s.lo));
     }
     return MI355REC_OK;
 }
@@ -1325,24 +1237,13 @@ int mi355rec_sharded_set_window(mi355rec_sharded_t* h, int window) {
     }
     if (window == h->s_window) return MI355REC_OK;
     DeviceRestore restore;
-    int rc = stream_flush(h);   // the open window is closed in the old geometry
+    const int rc = quiesce(h);   // the open window is closed in the old geometry
     if (rc) return rc;
-    rc = drain_workers(h);
-    if (rc) return rc;
-    // buffers are re-made by the next enqueue (ensure_stream sees s_alloc_window != s_window)
+    // buffers are re-made by the next enqueue (ensure_stream sees s_alloc_window != s_window); tickets keep growing, aligned to
+    // the NEW window before s_window changes
     h->next_ticket = (h->next_ticket + window - 1) / window * window;
     h->issued_upto = h->next_ticket;
-    for (Shard& s : h->shards) {
-        S_HIP(h, hipSetDevice(s.device));
-        S_HIP(h, hipStreamSynchronize(s.stream));
-    }
-    free_stream(h);
-    for (Window& w : h->win) {
-        w.abs = -1;
-        w.count = 0;
-        w.handed = false;
-        w.issued = false;
-    }
+    reset_stream(h);
     h->s_window = window;
     return MI355REC_OK;
 }
@@ -1352,21 +1253,9 @@ int mi355rec_sharded_set_window_mode(mi355rec_sharded_t* h, int batched) {
     if (h->cpu) return MI355REC_OK;   // (a query is computed when it is enqueued, either way)
     if ((batched != 0) == h->batched_windows) return MI355REC_OK;
     DeviceRestore restore;
-    int rc = stream_flush(h);
+    const int rc = quiesce(h);
     if (rc) return rc;
-    rc = drain_workers(h);
-    if (rc) return rc;
-    for (Shard& s : h->shards) {
-        S_HIP(h, hipSetDevice(s.device));
-        S_HIP(h, hipStreamSynchronize(s.stream));
-    }
-    free_stream(h);   // the next enqueue re-makes the buffers and decides the mode again
-    for (Window& w : h->win) {
-        w.abs = -1;
-        w.count = 0;
-        w.handed = false;
-        w.issued = false;
-    }
+    reset_stream(h);   // the next enqueue re-makes the buffers and decides the mode again
     h->batched_windows = batched != 0;
     return MI355REC_OK;
 }

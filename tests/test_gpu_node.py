@@ -334,3 +334,83 @@ def test_replicated_stream_ring_and_bad_tickets(Node):
         assert_topn_matches(idx, sc, oracle.scores(f, f[7]), 7, 33)
     with pytest.raises(capi.Mi355Error):
         Node(f, devices=[0], placement=7)
+
+
+# ---- a change of the handle while a stream window is open (quiesce / reset_stream, csrc/node_stream.hip.h) --------------
+
+ANSWER, GONE = "the answer as it was before the change", "ERR_INVALID_ARG"
+# What each change does to the tickets of the window that was open when it came.  Recorded on the commit before quiesce() and
+# reset_stream() replaced the hand-written copies of those steps (docs/LAB_NOTES.md); the same on both placements.
+RECORDED = {"set_window": GONE, "set_window_mode": GONE, "set_replica": ANSWER, "set_transport": ANSWER, "update_rows": ANSWER}
+
+
+def _served(node, f, ticket, row, topn):
+    idx, sc = node.wait(ticket, topn)
+    want = oracle.scores(f, f[row])
+    assert_topn_matches(idx, sc, want, row, topn, ref_idx=oracle.topn_heap(want, row, topn))
+
+
+def _changes_under_an_open_window(Node, replicated):
+    """name of the change -> what became of the tickets of the window it found open.  Everything else is asserted here."""
+    from spotify_recommender_amd import capi
+    rng = np.random.default_rng(41 + replicated)
+    n, topn = 259, 10
+    f = rng.random((n, 12), dtype=np.float32)
+    kw = dict(devices=[0, 0], placement=capi.PLACEMENT_REPLICATED) if replicated else dict(devices=[0, 0, 0])
+    edge = np.asarray([85, 86, 87, 88, 172, 173], np.int64)        # both sides of both shard edges of [0, 87) [87, 173) [173, 259)
+    got, seen = {}, []
+    with Node(f, **kw) as node:
+        if not replicated:
+            assert node.info()["shard_rows"] == [87, 86, 86]
+        node.set_window(4)
+
+        def open_window():
+            """A partial window of fresh tickets, not waited for."""
+            rows = [int(edge[len(seen) % edge.size])] + rng.integers(0, n, size=1).tolist()
+            tickets = [node.enqueue_row(r, topn) for r in rows]
+            assert tickets == sorted(tickets) and (not seen or tickets[0] > max(seen))
+            seen.extend(tickets)
+            return list(zip(tickets, rows))
+
+        def update():
+            f[edge] = rng.random((edge.size, 12), dtype=np.float32)
+            node.update_rows(edge, f[edge])
+
+        for name, change in (("set_window", lambda: node.set_window(3)),
+                             ("set_window_mode", lambda: node.set_window_mode(False)),
+                             ("set_replica", lambda: node.set_replica(capi.REPLICA_ON)),
+                             ("set_transport", lambda: node.set_transport(capi.TRANSPORT_RCCL)),
+                             ("update_rows", update)):
+            old, before = open_window(), f.copy()
+            change()
+            outcomes = set()
+            for t, r in old:
+                try:
+                    _served(node, before, t, r, topn)
+                    outcomes.add(ANSWER)
+                except capi.Mi355Error as e:
+                    assert e.code == capi.ERR_INVALID_ARG, e
+                    outcomes.add(GONE)
+            assert len(outcomes) == 1, (name, outcomes)
+            got[name] = outcomes.pop()
+            if name == "set_transport" and not replicated:
+                # one device holds all three shards: the RCCL transport takes the change (the open window was closed under the
+                # peer transport) and refuses the next query, handing out no ticket; the peer transport serves the stream again
+                with pytest.raises(capi.Mi355Error, match="one device per shard") as refused:
+                    node.enqueue_row(0, topn)
+                assert refused.value.code == capi.ERR_INVALID_ARG
+                node.set_transport(capi.TRANSPORT_PEER)
+            for t, r in open_window():                             # (larger than every ticket before them: open_window)
+                _served(node, f, t, r, topn)
+    return got
+
+
+@pytest.mark.parametrize("replicated", [False, True])
+def test_a_change_of_the_handle_under_an_open_window(Node, replicated):
+    """259 rows, window 4, top-10, on devices [0, 0, 0] row-sharded and on [0, 0] replicated.  A partial window is enqueued and not
+    waited for; then the handle changes: set_window(3), set_window_mode(False), set_replica(ON), set_transport(RCCL), update_rows
+    on rows either side of both shard edges — each with fresh tickets.  The old tickets give the oracle's answer of before the change
+    or ERR_INVALID_ARG, whichever was recorded; new tickets are larger than every old one and give the oracle's answer (after
+    update_rows: over the updated rows).  Three shards on one device cannot use the RCCL transport: there the enqueue after
+    set_transport(RCCL) is refused, as recorded, and the new tickets are taken after the return to PEER."""
+    assert _changes_under_an_open_window(Node, replicated) == RECORDED

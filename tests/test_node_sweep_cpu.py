@@ -5,8 +5,8 @@ a quarter of the cases expect nothing, and that every case's expectation is what
 
 The CPU backend (csrc/cpu_backend.cpp) does NOT shard: it holds the whole catalogue behind the node handle.  So the last test
 validates the cases and the oracles' composition (one exclusion list per request), and says nothing about the node layer itself:
-merge_over_shards, anyof_over_shards, bounded_over_shards, diverse_over_shards, ShardLists and the per-shard slices run only on
-the MI355X."""
+merge_over_shards, diverse_over_shards, ShardLists and the per-shard slices run only on the MI355X (the merge's own arithmetic,
+csrc/shard_merge.h, is checked without one by tests/test_shard_merge_cpu.py)."""
 import numpy as np
 import pytest
 
