@@ -283,6 +283,30 @@ def build_embed_half(force: bool = False) -> Path:
     return LIB_EMBED_HALF
 
 
+# RESTRICTED EMBEDDING REQUESTS: the fourth companion library (include/mi355rec_embed_sets.h).  The one scan body under a
+# restriction policy, its own bitmaps and the embedding libraries' host path, the engine's HIP_FLAGS, linked against the
+# product library and against no other companion.
+LIB_EMBED_SETS = PKG / "libmi355rec_embed_sets.so"
+EMBED_SETS_DEPS = [CSRC / "embed_sets.hip", CSRC / "embed_sets.hip.h", CSRC / "embed_sets_request.h", CSRC / "embed_half.hip.h",
+                   CSRC / "embed_half_request.h", CSRC / "embed.hip.h", CSRC / "embed_device.hip.h",
+                   CSRC / "embed_request.h", CSRC / "core.hip.h", CSRC / "merge.hip.h", CSRC / "experiments.hip.h", CSRC / "playlist_request.h",
+                   INCLUDE / "mi355rec_embed_sets.h", INCLUDE / "mi355rec_embed_half.h", INCLUDE / "mi355rec_embed.h", INCLUDE / "mi355rec_diag.h",
+                   INCLUDE / "mi355rec.h"]
+
+
+def build_embed_sets(force: bool = False) -> Path:
+    """Compile libmi355rec_embed_sets.so for gfx950; check_no_scratch applies to it exactly as to the product library."""
+    build_engine(force)
+    if force or _stale(LIB_EMBED_SETS, EMBED_SETS_DEPS + [LIB_ENGINE]):
+        _run([HIPCC, *HIP_FLAGS, "-o", LIB_EMBED_SETS, CSRC / "embed_sets.hip", f"-L{PKG}", "-lmi355rec", "-Wl,-rpath,$ORIGIN"])
+        try:
+            check_no_scratch(LIB_EMBED_SETS)
+        except Exception:
+            LIB_EMBED_SETS.unlink(missing_ok=True)
+            raise
+    return LIB_EMBED_SETS
+
+
 def shim_sources():
     return [CSRC / "Recommender.cpp", CSRC / "DataManager.cpp"]
 
@@ -326,6 +350,7 @@ def build_all(force: bool = False) -> None:
     build_embed(force)         # (the companion library: embedding tables over the product's C-ABI)
     build_embed_batch(force)   # (the second companion: user batches over an embedding table)
     build_embed_half(force)    # (the third companion: fp16 / bf16 embedding tables)
+    build_embed_sets(force)    # (the fourth companion: hybrid requests restricted by row sets)
     build_shim(force)
     build_oracle(force)
 

@@ -601,3 +601,53 @@ def embed_half_lib() -> ctypes.CDLL:
             fn.argtypes = argtypes
         _embed_half_lib = handle
     return _embed_half_lib
+
+
+# ---- RESTRICTED EMBEDDING REQUESTS: the fourth companion library libmi355rec_embed_sets.so
+# (include/mi355rec_embed_sets.h), a fifth table.  Queries and results are EmbedQuery / EmbedResult. ----
+EMBED_SETS_LIB_PATH = PKG / "libmi355rec_embed_sets.so"
+EMBED_SETS_FP32 = -1   # `storage` of an fp32 table in EmbedSetsInfo
+
+
+class EmbedSetsExt(ctypes.Structure):
+    """mi355rec_embed_sets_ext_t (24 bytes): either set may be NULL."""
+    _fields_ = [("size", c_uint32), ("flags", c_uint32), ("seen", c_void_p), ("only", c_void_p)]
+
+
+class EmbedSetsInfo(ctypes.Structure):
+    """mi355rec_embed_sets_info_t (88 bytes): EmbedHalfInfo's fields, then the cumulative counters."""
+    _fields_ = EmbedHalfInfo._fields_ + [("tiles_total", c_int64), ("tiles_scored", c_int64), ("launches_skipped", c_int64)]
+
+
+EMBED_SETS_SIGNATURES = {
+    "mi355rec_embed_sets_create": (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(c_void_p)]),
+    "mi355rec_embed_sets_create_half": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, POINTER(c_void_p)]),
+    "mi355rec_embed_sets_destroy": (None, [c_void_p]),
+    "mi355rec_embed_sets_last_error": (c_char_p, [c_void_p]),
+    "mi355rec_embed_sets_info": (c_int, [c_void_p, POINTER(EmbedSetsInfo)]),
+    "mi355rec_embed_sets_rowset_create": (c_int, [c_void_p, c_void_p, c_int64, POINTER(c_void_p)]),
+    "mi355rec_embed_sets_rowset_create_mask": (c_int, [c_void_p, c_void_p, c_int64, POINTER(c_void_p)]),
+    "mi355rec_embed_sets_rowset_add": (c_int, [c_void_p, c_void_p, c_int64]),
+    "mi355rec_embed_sets_rowset_count": (c_int64, [c_void_p]),
+    "mi355rec_embed_sets_rowset_destroy": (None, [c_void_p]),
+    "mi355rec_embed_sets_query": (c_int, [c_void_p, POINTER(EmbedQuery), POINTER(EmbedSetsExt), POINTER(EmbedResult)]),
+}
+
+_embed_sets_lib = None
+
+
+def embed_sets_lib() -> ctypes.CDLL:
+    """Load libmi355rec_embed_sets.so (it links against libmi355rec.so beside it; `lib()` is loaded first so that both share
+    one copy of it and of the HIP runtime).  A missing library is an error: the restricted scan has no fallback."""
+    global _embed_sets_lib
+    if _embed_sets_lib is None:
+        lib()
+        if not EMBED_SETS_LIB_PATH.exists():
+            raise RuntimeError(f"{EMBED_SETS_LIB_PATH} is missing: build it with `python -m spotify_recommender_amd.build`")
+        handle = ctypes.CDLL(str(EMBED_SETS_LIB_PATH))
+        for name, (restype, argtypes) in EMBED_SETS_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _embed_sets_lib = handle
+    return _embed_sets_lib

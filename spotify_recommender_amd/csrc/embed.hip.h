@@ -23,6 +23,10 @@
 // The lane with g == 0 forms the key; candidates, thresholds and the per-workgroup lists are core.hip.h's pieces used as
 // label_scan_kernel uses them (no launch-wide bound, no pre-filter: DESIGN.md §5.4.21); merge_kernel (merge.hip.h) follows.
 // With out_v the launch is the parity hook instead: v (and c) of every row are stored and nothing is selected.
+//
+// The body takes a compile-time RESTRICTION POLICY (default EmbedNoRestriction: the plain scan, which reads and holds
+// nothing more).  A restricting policy (embed_sets.hip.h) names the tiles the workgroup scores (next_live), the bitmap
+// words a tile's rows are tested against (loaded with the tile, one tile ahead) and the row test that joins `owner`.
 #pragma once
 
 #include "core.hip.h"
@@ -129,14 +133,21 @@ struct EmbedRowsF32 {
     static __device__ __forceinline__ float partial(const Row& a, const Row& b) { return embed_partial(a, b); }
 };
 
+// The policy of the plain scan: every tile of the workgroup's stride is live and every row passes.
+struct EmbedNoRestriction {
+    static constexpr bool kRestricted = false;
+    template <int kTileWords>
+    __device__ __forceinline__ int64_t next_live(int64_t from, int64_t, int) const { return from; }
+};
+
 // The scan over a table of n x kDimT Rows::Word (the one body of embed_scan_kernel and embed_half_scan_kernel).
 // user: kDimT floats (device); audio_s: n floats or null (use_audio == 0); exclude: n_exclude sorted local rows.
 // Selecting form (out_v == null): block_lists[gridDim.x][topk].  Scoring form: out_v[n], out_c[n] or null.
-template <class Rows, int kDimT>
+template <class Rows, int kDimT, class Restrict = EmbedNoRestriction>
 __device__ __forceinline__ void embed_scan_body(const typename Rows::Word* __restrict__ table, int64_t n, int64_t row_base,
                                                 const float* __restrict__ user, const float* __restrict__ audio_s,
                                                 const uint32_t* __restrict__ exclude, EmbedArgs a, uint64_t* __restrict__ block_lists,
-                                                float* __restrict__ out_v, float* __restrict__ out_c) {
+                                                float* __restrict__ out_v, float* __restrict__ out_c, const Restrict rs = Restrict{}) {
     using Vec = typename Rows::Vec;
     using Row = typename Rows::Row;
     constexpr int kGroup = kDimT / Rows::kVals;                        // lanes per row
@@ -144,6 +155,9 @@ __device__ __forceinline__ void embed_scan_body(const typename Rows::Word* __res
     constexpr int kMaxTileRows = kEmbedTileVecs / (16 / Rows::kVals);   // d = 16
     constexpr int kCandCap = kCandLimit + kMaxTileRows;
     constexpr int kCandPerThread = (kCandCap + kEmbedBlock - 1) / kEmbedBlock;
+    constexpr int kTileWords = kTileRows / 32;                         // bitmap words of a tile (a restricting policy's)
+    constexpr int kSetWords = Restrict::kRestricted ? kEmbedVecsPerThread : 1;
+    static_assert(kTileRows % 32 == 0 && kTileWords >= 2, "a tile owns whole bitmap words");
     static_assert(kGroup >= 2 && kGroup <= 32 && 64 % kGroup == 0, "a row lies inside one wave");
     static_assert(kTileRows <= kMaxTileRows, "a tile appends at most kMaxTileRows candidates");
     static_assert(kCandPerThread * kEmbedBlock >= kCandCap, "compact_candidates reads the whole list");
@@ -160,21 +174,24 @@ __device__ __forceinline__ void embed_scan_body(const typename Rows::Word* __res
     const Vec* const tab4 = reinterpret_cast<const Vec*>(table);
     const int64_t n_tiles = (n_vec + kEmbedTileVecs - 1) / kEmbedTileVecs;
 
-    auto load_tile = [&](int64_t tile, Vec (&e)[kEmbedVecsPerThread], float (&s)[kEmbedVecsPerThread]) {
+    auto load_tile = [&](int64_t tile, Vec (&e)[kEmbedVecsPerThread], float (&s)[kEmbedVecsPerThread], uint32_t (&wo)[kSetWords],
+                         uint32_t (&ws)[kSetWords]) {
 #pragma unroll
         for (int j = 0; j < kEmbedVecsPerThread; ++j) {
             int64_t v = tile * kEmbedTileVecs + j * kEmbedBlock + tid;
             v = v < n_vec ? v : n_vec - 1;   // (a clamped lane's row is never used: rows are whole groups of lanes)
+            if constexpr (Restrict::kRestricted) rs.load_words((v / kGroup) >> 5, wo[j], ws[j]);   // (ahead of the 16-byte load)
             e[j] = tab4[v];
             s[j] = a.use_audio ? audio_s[v / kGroup] : 0.0f;
         }
     };
     auto tree = [](const Row& x, const Row& y) { return embed_tree_levels<kGroup>(Rows::partial(x, y)); };
 
-    int64_t tile = blockIdx.x;
+    int64_t tile = rs.template next_live<kTileWords>(blockIdx.x, n_tiles, lane);   // uniform
     Vec cur_e[kEmbedVecsPerThread];
     float cur_s[kEmbedVecsPerThread];
-    if (tile < n_tiles) load_tile(tile, cur_e, cur_s);   // requested before the user vector is
+    uint32_t cur_wo[kSetWords], cur_ws[kSetWords];
+    if (tile < n_tiles) load_tile(tile, cur_e, cur_s, cur_wo, cur_ws);   // requested before the user vector is
 
     if (tid == 0) s_count = 0;
     for (int i = tid; i < a.n_exclude; i += kEmbedBlock) s_excl[i] = exclude[i];
@@ -186,16 +203,26 @@ __device__ __forceinline__ void embed_scan_body(const typename Rows::Word* __res
     int compact_at = 2 * a.topk > 256 ? 2 * a.topk : 256;
     if (compact_at > kCandLimit) compact_at = kCandLimit;
 
-    for (; tile < n_tiles; tile += gridDim.x) {   // uniform
-        const int64_t next_tile = tile + gridDim.x;
+    int scored = 0;
+    int64_t next_tile;
+    for (; tile < n_tiles; tile = next_tile) {   // uniform
+        next_tile = rs.template next_live<kTileWords>(tile + gridDim.x, n_tiles, lane);   // (the plain scan: tile + gridDim.x)
         Vec next_e[kEmbedVecsPerThread];
         float next_s[kEmbedVecsPerThread];
-        load_tile(next_tile < n_tiles ? next_tile : tile, next_e, next_s);   // the next tile is in flight while this one is scored
+        uint32_t next_wo[kSetWords], next_ws[kSetWords];
+        load_tile(next_tile < n_tiles ? next_tile : tile, next_e, next_s, next_wo, next_ws);   // the next tile is in flight while this one is scored
+        if constexpr (Restrict::kRestricted) ++scored;
 
 #pragma unroll
         for (int j = 0; j < kEmbedVecsPerThread; ++j) {
             const int64_t vec = tile * kEmbedTileVecs + j * kEmbedBlock + tid;
             const int64_t row = vec / kGroup;
+            bool admitted = true;
+            if constexpr (Restrict::kRestricted) {
+                // the row's bit joins owner: a rejected row forms no key; a load with no admissible row in the wave is not scored
+                admitted = (((cur_wo[j] & ~cur_ws[j]) >> (static_cast<uint32_t>(row) & 31u)) & 1u) != 0u;
+                if (!__ballot(admitted && g == 0 && vec < n_vec)) continue;   // (wave-uniform: the butterflies stay inside the wave)
+            }
             const Row e = Rows::widen(cur_e[j]);
             const float dot = tree(e, u);
             float c = dot;
@@ -214,7 +241,7 @@ __device__ __forceinline__ void embed_scan_body(const typename Rows::Word* __res
                 const float wa = a.w_audio * cur_s[j];
                 v = wa + v;
             }
-            const bool owner = g == 0 && vec < n_vec;
+            const bool owner = g == 0 && vec < n_vec && admitted;
             if (!selecting) {
                 if (owner) {
                     out_v[row] = v;
@@ -257,9 +284,14 @@ __device__ __forceinline__ void embed_scan_body(const typename Rows::Word* __res
         for (int j = 0; j < kEmbedVecsPerThread; ++j) {
             cur_e[j] = next_e[j];
             cur_s[j] = next_s[j];
+            if constexpr (Restrict::kRestricted) {
+                cur_wo[j] = next_wo[j];
+                cur_ws[j] = next_ws[j];
+            }
         }
     }
     if (!selecting) return;   // uniform
+    if constexpr (Restrict::kRestricted) rs.count_scored(scored);   // once per workgroup
 
     __syncthreads();
     if (s_count > kRankCountMax && s_count > a.topk)   // uniform

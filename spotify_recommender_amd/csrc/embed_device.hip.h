@@ -84,6 +84,8 @@ struct EmbedTableKind {
     int vals;            // stored values per 16-byte load
     void (*launch_scan)(EmbedDeviceTable* e, const EmbedArgs& a, const float* d_s, float* out_v, float* out_c);
     void (*launch_user)(EmbedDeviceTable* e, const EmbedMembers& m);   // d_user from member rows
+    // uint64 words a library keeps on the device in front of d_keys: one copy brings them back with the keys, to keys_out[-keys_lead ..)
+    int keys_lead = 0;
 };
 
 // A table on one device handle (its rows are the handle's, from row_base on).
@@ -105,14 +107,14 @@ struct EmbedDeviceTable : EmbedHandle {
     float* d_c = nullptr;
     uint32_t* d_excl = nullptr;
     uint64_t* d_lists = nullptr;   // [grid][MI355REC_MAX_TOPN_FAST]
-    uint64_t* d_keys = nullptr;    // [MI355REC_MAX_TOPN_FAST]
+    uint64_t* d_keys = nullptr;    // [MI355REC_MAX_TOPN_FAST], behind the kind's keys_lead words
 
     ~EmbedDeviceTable() {
         if (device < 0) return;
         DeviceGuard guard(device);
         if (stream) (void)hipStreamSynchronize(stream);
         for (void* p : {d_table, static_cast<void*>(d_user), static_cast<void*>(d_s), static_cast<void*>(d_v), static_cast<void*>(d_c),
-                        static_cast<void*>(d_excl), static_cast<void*>(d_lists), static_cast<void*>(d_keys)})
+                        static_cast<void*>(d_excl), static_cast<void*>(d_lists), static_cast<void*>(d_keys ? d_keys - table_kind->keys_lead : nullptr)})
             if (p) (void)hipFree(p);
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -136,7 +138,8 @@ int init_device(EmbedDeviceTable* e, const EmbedTableKind* kind, mi355rec_t* h, 
     if ((rc = dev_alloc(e, &e->d_user, MI355REC_EMBED_MAX_DIM))) return rc;
     if ((rc = dev_alloc(e, &e->d_excl, kEmbedMaxExclude))) return rc;
     if ((rc = dev_alloc(e, &e->d_lists, static_cast<size_t>(e->grid) * MI355REC_MAX_TOPN_FAST))) return rc;
-    if ((rc = dev_alloc(e, &e->d_keys, MI355REC_MAX_TOPN_FAST))) return rc;
+    if ((rc = dev_alloc(e, &e->d_keys, static_cast<size_t>(kind->keys_lead) + MI355REC_MAX_TOPN_FAST))) return rc;
+    e->d_keys += kind->keys_lead;
     if (n > 0) EMBED_HIP_TRY(e, hipMemcpy(e->d_table, table, table_bytes, hipMemcpyHostToDevice));
     return MI355REC_OK;
 }
@@ -175,7 +178,8 @@ EmbedArgs args_of(const mi355embed::Request& r, int n_exclude, int topk) {
     return a;
 }
 
-// The request's best keys of this table (sorted descending) into keys_out[0 .. topn), *count of them non-empty.
+// The request's best keys of this table (sorted descending) into keys_out[0 .. topn), *count of them non-empty; the kind's
+// keys_lead words into keys_out[-keys_lead .. 0).
 int device_keys(EmbedDeviceTable* e, const mi355embed::Request& r, uint64_t* keys_out, int* count) {
     *count = 0;
     if (e->n == 0) return MI355REC_OK;
@@ -199,7 +203,8 @@ int device_keys(EmbedDeviceTable* e, const mi355embed::Request& r, uint64_t* key
                        static_cast<int64_t>(0), eff, e->d_keys, static_cast<int64_t*>(nullptr), static_cast<float*>(nullptr),
                        static_cast<int64_t>(0), static_cast<uint32_t*>(nullptr), 0u);
     EMBED_HIP_TRY(e, hipGetLastError());
-    EMBED_HIP_TRY(e, hipMemcpyAsync(keys_out, e->d_keys, sizeof(uint64_t) * static_cast<size_t>(eff), hipMemcpyDeviceToHost, e->stream));
+    const int lead = e->table_kind->keys_lead;
+    EMBED_HIP_TRY(e, hipMemcpyAsync(keys_out - lead, e->d_keys - lead, sizeof(uint64_t) * static_cast<size_t>(lead + eff), hipMemcpyDeviceToHost, e->stream));
     EMBED_HIP_TRY(e, hipStreamSynchronize(e->stream));
     int c = 0;
     while (c < eff && keys_out[c] != 0ull) ++c;
