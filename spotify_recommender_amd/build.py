@@ -307,6 +307,30 @@ def build_embed_sets(force: bool = False) -> Path:
     return LIB_EMBED_SETS
 
 
+# STREAMED EMBEDDING REQUESTS: the fifth companion library (include/mi355rec_embed_stream.h).  The scan bodies of the
+# embedding libraries and merge_kernel, instantiated here, its own prepare and finish kernels (embed_stream.hip.h), the
+# engine's HIP_FLAGS, linked against the product library and against no other companion.
+LIB_EMBED_STREAM = PKG / "libmi355rec_embed_stream.so"
+EMBED_STREAM_DEPS = [CSRC / "embed_stream.hip", CSRC / "embed_stream.hip.h", CSRC / "embed_stream_request.h", CSRC / "embed_batch.hip.h",
+                     CSRC / "embed_half.hip.h", CSRC / "embed_half_request.h", CSRC / "embed.hip.h", CSRC / "embed_device.hip.h",
+                     CSRC / "embed_request.h", CSRC / "core.hip.h", CSRC / "merge.hip.h", CSRC / "experiments.hip.h", CSRC / "playlist_request.h",
+                     INCLUDE / "mi355rec_embed_stream.h", INCLUDE / "mi355rec_embed_half.h", INCLUDE / "mi355rec_embed.h", INCLUDE / "mi355rec_diag.h",
+                     INCLUDE / "mi355rec.h"]
+
+
+def build_embed_stream(force: bool = False) -> Path:
+    """Compile libmi355rec_embed_stream.so for gfx950; check_no_scratch applies to it exactly as to the product library."""
+    build_engine(force)
+    if force or _stale(LIB_EMBED_STREAM, EMBED_STREAM_DEPS + [LIB_ENGINE]):
+        _run([HIPCC, *HIP_FLAGS, "-o", LIB_EMBED_STREAM, CSRC / "embed_stream.hip", f"-L{PKG}", "-lmi355rec", "-Wl,-rpath,$ORIGIN"])
+        try:
+            check_no_scratch(LIB_EMBED_STREAM)
+        except Exception:
+            LIB_EMBED_STREAM.unlink(missing_ok=True)
+            raise
+    return LIB_EMBED_STREAM
+
+
 def shim_sources():
     return [CSRC / "Recommender.cpp", CSRC / "DataManager.cpp"]
 
@@ -351,6 +375,7 @@ def build_all(force: bool = False) -> None:
     build_embed_batch(force)   # (the second companion: user batches over an embedding table)
     build_embed_half(force)    # (the third companion: fp16 / bf16 embedding tables)
     build_embed_sets(force)    # (the fourth companion: hybrid requests restricted by row sets)
+    build_embed_stream(force)  # (the fifth companion: device tensors in and out on the caller's stream)
     build_shim(force)
     build_oracle(force)
 

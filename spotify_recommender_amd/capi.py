@@ -651,3 +651,67 @@ def embed_sets_lib() -> ctypes.CDLL:
             fn.argtypes = argtypes
         _embed_sets_lib = handle
     return _embed_sets_lib
+
+
+# ---- STREAMED EMBEDDING REQUESTS: the fifth companion library libmi355rec_embed_stream.so
+# (include/mi355rec_embed_stream.h), a sixth table.  Every pointer named *_dev is device memory. ----
+EMBED_STREAM_LIB_PATH = PKG / "libmi355rec_embed_stream.so"
+EMBED_STREAM_FP32 = -1   # `storage` of an fp32 table; else EMBED_HALF_FP16 / EMBED_HALF_BF16
+EMBED_STREAM_MAX_EXCLUDE = 1024
+EMBED_STREAM_MAX_USERS = 1024
+EMBED_STREAM_MAX_USERS_TOPN = 128
+
+
+class EmbedStreamQuery(ctypes.Structure):
+    """mi355rec_embed_stream_query_t; `size` is sizeof of this struct (64).  `audio` is 12 HOST floats."""
+    _fields_ = [("size", c_uint32), ("flags", c_uint32), ("user_dev", c_void_p), ("audio", c_void_p), ("exclude_dev", c_void_p),
+                ("audio_row", c_int64), ("n_exclude", c_int32), ("topn", c_int32), ("metric", c_int32), ("w_audio", c_float),
+                ("w_embed", c_float), ("reserved", c_uint32)]
+
+
+class EmbedStreamUsers(ctypes.Structure):
+    """mi355rec_embed_stream_users_t; `size` is sizeof of this struct (48)."""
+    _fields_ = [("size", c_uint32), ("flags", c_uint32), ("users_dev", c_void_p), ("exclude_dev", c_void_p), ("n_users", c_int32),
+                ("topn", c_int32), ("exclude_len", c_int32), ("metric", c_int32), ("w_embed", c_float), ("reserved", c_uint32)]
+
+
+class EmbedStreamResult(ctypes.Structure):
+    """mi355rec_embed_stream_result_t (32 bytes): out_score_dev and out_count_dev may be NULL."""
+    _fields_ = [("size", c_uint32), ("reserved", c_uint32), ("out_idx_dev", c_void_p), ("out_score_dev", c_void_p), ("out_count_dev", c_void_p)]
+
+
+class EmbedStreamInfo(ctypes.Structure):
+    """mi355rec_embed_stream_info_t (80 bytes)."""
+    _fields_ = [("size", c_uint32), ("dim", c_int32), ("rows", c_int64), ("device_bytes", c_int64), ("tile_rows", c_int32),
+                ("grid", c_int32), ("device", c_int32), ("storage", c_int32), ("table_dev", c_void_p), ("launches", c_int64),
+                ("enqueues", c_int64), ("scores_launches", c_int64), ("pass_users", c_int32), ("borrowed", c_int32)]
+
+
+EMBED_STREAM_SIGNATURES = {
+    "mi355rec_embed_stream_create_device": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, POINTER(c_void_p)]),
+    "mi355rec_embed_stream_create": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, POINTER(c_void_p)]),
+    "mi355rec_embed_stream_destroy": (None, [c_void_p]),
+    "mi355rec_embed_stream_last_error": (c_char_p, [c_void_p]),
+    "mi355rec_embed_stream_info": (c_int, [c_void_p, POINTER(EmbedStreamInfo)]),
+    "mi355rec_embed_stream_enqueue_query": (c_int, [c_void_p, POINTER(EmbedStreamQuery), POINTER(EmbedStreamResult), c_void_p]),
+    "mi355rec_embed_stream_enqueue_users": (c_int, [c_void_p, POINTER(EmbedStreamUsers), POINTER(EmbedStreamResult), c_void_p]),
+}
+
+_embed_stream_lib = None
+
+
+def embed_stream_lib() -> ctypes.CDLL:
+    """Load libmi355rec_embed_stream.so (it links against libmi355rec.so beside it; `lib()` is loaded first so that both share
+    one copy of it and of the HIP runtime).  A missing library is an error: the streamed requests have no fallback."""
+    global _embed_stream_lib
+    if _embed_stream_lib is None:
+        lib()
+        if not EMBED_STREAM_LIB_PATH.exists():
+            raise RuntimeError(f"{EMBED_STREAM_LIB_PATH} is missing: build it with `python -m spotify_recommender_amd.build`")
+        handle = ctypes.CDLL(str(EMBED_STREAM_LIB_PATH))
+        for name, (restype, argtypes) in EMBED_STREAM_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _embed_stream_lib = handle
+    return _embed_stream_lib

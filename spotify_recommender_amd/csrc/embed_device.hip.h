@@ -1,4 +1,5 @@
-// embed_device.hip.h — the host path the embedding libraries share (embed.hip, embed_half.hip, embed_batch.hip; host code
+// embed_device.hip.h — the host path the embedding libraries share (embed.hip, embed_half.hip, embed_batch.hip,
+// embed_sets.hip; embed_stream.hip takes the table from it and enqueues on the caller's stream itself; host code
 // over the HIP runtime, so no header that the CPU-only programs compile includes it): the device guard, the error function,
 // EMBED_HIP_TRY, dev_alloc and the grid rule, and EmbedDeviceTable, a table on one device handle, with its one host path.
 // What a library adds to a table is an EmbedTableKind: the size of a stored value, the values per 16-byte load and the two
@@ -101,6 +102,7 @@ struct EmbedDeviceTable : EmbedHandle {
     int64_t row_base = 0;
     hipStream_t stream = nullptr;
     void* d_table = nullptr;
+    bool borrowed_table = false;   // d_table is the caller's device memory: never copied into, never freed (embed_stream.hip)
     float* d_user = nullptr;
     float* d_s = nullptr;          // s(x) of every row (allocated by the first call with w_audio != 0)
     float* d_v = nullptr;          // the parity hook's outputs (allocated by the first _scores call)
@@ -113,7 +115,7 @@ struct EmbedDeviceTable : EmbedHandle {
         if (device < 0) return;
         DeviceGuard guard(device);
         if (stream) (void)hipStreamSynchronize(stream);
-        for (void* p : {d_table, static_cast<void*>(d_user), static_cast<void*>(d_s), static_cast<void*>(d_v), static_cast<void*>(d_c),
+        for (void* p : {borrowed_table ? nullptr : d_table, static_cast<void*>(d_user), static_cast<void*>(d_s), static_cast<void*>(d_v), static_cast<void*>(d_c),
                         static_cast<void*>(d_excl), static_cast<void*>(d_lists), static_cast<void*>(d_keys ? d_keys - table_kind->keys_lead : nullptr)})
             if (p) (void)hipFree(p);
         if (stream) (void)hipStreamDestroy(stream);
@@ -121,6 +123,7 @@ struct EmbedDeviceTable : EmbedHandle {
 };
 
 // Fills a fresh table over `h` (st: its mi355rec_stats) with table[0 .. n); the caller has checked the table against st.rows.
+// With borrowed_table set, `table` is device memory of the handle's device and becomes d_table as it is.
 int init_device(EmbedDeviceTable* e, const EmbedTableKind* kind, mi355rec_t* h, const mi355rec_stats_t& st, const void* table, int64_t n, int dim) {
     e->table_kind = kind;
     e->h = h;
@@ -134,13 +137,14 @@ int init_device(EmbedDeviceTable* e, const EmbedTableKind* kind, mi355rec_t* h, 
     EMBED_HIP_TRY(e, hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     const size_t table_bytes = kind->word_bytes * static_cast<size_t>(n) * dim;
     int rc = MI355REC_OK;
-    if (n > 0 && (rc = dev_alloc(e, reinterpret_cast<char**>(&e->d_table), table_bytes))) return rc;
+    if (e->borrowed_table) e->d_table = const_cast<void*>(table);
+    else if (n > 0 && (rc = dev_alloc(e, reinterpret_cast<char**>(&e->d_table), table_bytes))) return rc;
     if ((rc = dev_alloc(e, &e->d_user, MI355REC_EMBED_MAX_DIM))) return rc;
     if ((rc = dev_alloc(e, &e->d_excl, kEmbedMaxExclude))) return rc;
     if ((rc = dev_alloc(e, &e->d_lists, static_cast<size_t>(e->grid) * MI355REC_MAX_TOPN_FAST))) return rc;
     if ((rc = dev_alloc(e, &e->d_keys, static_cast<size_t>(kind->keys_lead) + MI355REC_MAX_TOPN_FAST))) return rc;
     e->d_keys += kind->keys_lead;
-    if (n > 0) EMBED_HIP_TRY(e, hipMemcpy(e->d_table, table, table_bytes, hipMemcpyHostToDevice));
+    if (n > 0 && !e->borrowed_table) EMBED_HIP_TRY(e, hipMemcpy(e->d_table, table, table_bytes, hipMemcpyHostToDevice));
     return MI355REC_OK;
 }
 
