@@ -331,6 +331,27 @@ def build_embed_stream(force: bool = False) -> Path:
     return LIB_EMBED_STREAM
 
 
+# EMBEDDING CANDIDATE LISTS: the sixth companion library (include/mi355rec_embed_cand.h).  Its own gather and claim kernels
+# (embed_cand.hip.h) over the row layouts of the embedding libraries, the stream library's prepare and finish kernels and
+# merge_kernel, instantiated here, the engine's HIP_FLAGS, linked against the product library and against no other companion.
+LIB_EMBED_CAND = PKG / "libmi355rec_embed_cand.so"
+EMBED_CAND_DEPS = ([CSRC / "embed_cand.hip", CSRC / "embed_cand.hip.h", CSRC / "embed_cand_request.h", INCLUDE / "mi355rec_embed_cand.h"]
+                   + [d for d in EMBED_STREAM_DEPS if d.name != "embed_stream.hip"])   # (every header of the stream library is included)
+
+
+def build_embed_cand(force: bool = False) -> Path:
+    """Compile libmi355rec_embed_cand.so for gfx950; check_no_scratch applies to it exactly as to the product library."""
+    build_engine(force)
+    if force or _stale(LIB_EMBED_CAND, EMBED_CAND_DEPS + [LIB_ENGINE]):
+        _run([HIPCC, *HIP_FLAGS, "-o", LIB_EMBED_CAND, CSRC / "embed_cand.hip", f"-L{PKG}", "-lmi355rec", "-Wl,-rpath,$ORIGIN"])
+        try:
+            check_no_scratch(LIB_EMBED_CAND)
+        except Exception:
+            LIB_EMBED_CAND.unlink(missing_ok=True)
+            raise
+    return LIB_EMBED_CAND
+
+
 def shim_sources():
     return [CSRC / "Recommender.cpp", CSRC / "DataManager.cpp"]
 
@@ -376,6 +397,7 @@ def build_all(force: bool = False) -> None:
     build_embed_half(force)    # (the third companion: fp16 / bf16 embedding tables)
     build_embed_sets(force)    # (the fourth companion: hybrid requests restricted by row sets)
     build_embed_stream(force)  # (the fifth companion: device tensors in and out on the caller's stream)
+    build_embed_cand(force)    # (the sixth companion: rank or score the listed rows of an embedding table by gather)
     build_shim(force)
     build_oracle(force)
 

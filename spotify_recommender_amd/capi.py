@@ -715,3 +715,59 @@ def embed_stream_lib() -> ctypes.CDLL:
             fn.argtypes = argtypes
         _embed_stream_lib = handle
     return _embed_stream_lib
+
+
+# ---- EMBEDDING CANDIDATE LISTS: the sixth companion library libmi355rec_embed_cand.so
+# (include/mi355rec_embed_cand.h), a seventh table.  Every pointer named *_dev is device memory; a rank call's result is
+# EmbedStreamResult. ----
+EMBED_CAND_LIB_PATH = PKG / "libmi355rec_embed_cand.so"
+EMBED_CAND_MAX = 1 << 20
+EMBED_CAND_MAX_EXCLUDE = 1024
+
+
+class EmbedCandQuery(ctypes.Structure):
+    """mi355rec_embed_cand_query_t; `size` is sizeof of this struct (80).  `audio` is 12 HOST floats."""
+    _fields_ = [("size", c_uint32), ("flags", c_uint32), ("user_dev", c_void_p), ("audio", c_void_p), ("candidates_dev", c_void_p),
+                ("exclude_dev", c_void_p), ("audio_row", c_int64), ("n_candidates", c_int64), ("n_exclude", c_int32), ("topn", c_int32),
+                ("metric", c_int32), ("w_audio", c_float), ("w_embed", c_float), ("reserved", c_uint32)]
+
+
+class EmbedCandScores(ctypes.Structure):
+    """mi355rec_embed_cand_scores_t (32 bytes): out_c_dev and out_flag_dev may be NULL."""
+    _fields_ = [("size", c_uint32), ("reserved", c_uint32), ("out_v_dev", c_void_p), ("out_c_dev", c_void_p), ("out_flag_dev", c_void_p)]
+
+
+class EmbedCandInfo(ctypes.Structure):
+    """mi355rec_embed_cand_info_t (96 bytes): EmbedStreamInfo's fields, then the list's limit and the launches per call."""
+    _fields_ = EmbedStreamInfo._fields_ + [("max_candidates", c_int32), ("rank_launches", c_int32), ("scores_call_launches", c_int32),
+                                           ("reserved", c_int32)]
+
+
+EMBED_CAND_SIGNATURES = {
+    "mi355rec_embed_cand_create_device": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, POINTER(c_void_p)]),
+    "mi355rec_embed_cand_create": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, POINTER(c_void_p)]),
+    "mi355rec_embed_cand_destroy": (None, [c_void_p]),
+    "mi355rec_embed_cand_last_error": (c_char_p, [c_void_p]),
+    "mi355rec_embed_cand_info": (c_int, [c_void_p, POINTER(EmbedCandInfo)]),
+    "mi355rec_embed_cand_enqueue_rank": (c_int, [c_void_p, POINTER(EmbedCandQuery), POINTER(EmbedStreamResult), c_void_p]),
+    "mi355rec_embed_cand_enqueue_scores": (c_int, [c_void_p, POINTER(EmbedCandQuery), POINTER(EmbedCandScores), c_void_p]),
+}
+
+_embed_cand_lib = None
+
+
+def embed_cand_lib() -> ctypes.CDLL:
+    """Load libmi355rec_embed_cand.so (it links against libmi355rec.so beside it; `lib()` is loaded first so that both share
+    one copy of it and of the HIP runtime).  A missing library is an error: the candidate lists have no fallback."""
+    global _embed_cand_lib
+    if _embed_cand_lib is None:
+        lib()
+        if not EMBED_CAND_LIB_PATH.exists():
+            raise RuntimeError(f"{EMBED_CAND_LIB_PATH} is missing: build it with `python -m spotify_recommender_amd.build`")
+        handle = ctypes.CDLL(str(EMBED_CAND_LIB_PATH))
+        for name, (restype, argtypes) in EMBED_CAND_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _embed_cand_lib = handle
+    return _embed_cand_lib

@@ -30,11 +30,20 @@ class StreamedEmbeddingTable:
     (float32, or float16 attached as it is) is copied, zero-padded to a served width.
     The table must be closed before its engine; calls come from one host thread at a time, on any streams."""
 
+    # (the library of a table and what its entry points and refusals call it: CandidateEmbeddingTable attaches its table
+    # the same way to another library)
+    _load = staticmethod(capi.embed_stream_lib)
+    _prefix = "mi355rec_embed_stream_"
+    _what = "streamed embedding requests"
+
+    def _fn(self, name):
+        return getattr(self._lib, self._prefix + name)
+
     def __init__(self, engine, table):
         self._e = ctypes.c_void_p()
         if getattr(engine, "_prefix", "") == "mi355rec_sharded_":
-            raise ValueError("streamed embedding requests are served over a CosineEngine, not a node engine")
-        self._lib = capi.embed_stream_lib()
+            raise ValueError(f"{self._what} are served over a CosineEngine, not a node engine")
+        self._lib = self._load()
         self._engine = engine   # (kept alive: the table reads the engine's rows)
         self._table = None
         if _is_torch(table):
@@ -58,7 +67,7 @@ class StreamedEmbeddingTable:
             self.user_dim = self.dim = int(table.shape[1])
             self.rows = int(table.shape[0])
             self._table = table   # (the reference that keeps the borrowed memory alive)
-            rc = self._lib.mi355rec_embed_stream_create_device(engine._h, ctypes.c_void_p(table.data_ptr()), self.rows, self.dim, self.storage,
+            rc = self._fn("create_device")(engine._h, ctypes.c_void_p(table.data_ptr()), self.rows, self.dim, self.storage,
                                                                ctypes.byref(self._e))
         else:
             half = isinstance(table, np.ndarray) and table.dtype == np.float16
@@ -75,19 +84,19 @@ class StreamedEmbeddingTable:
             elif not half:
                 arr = _pad(arr, self.dim)
             self.rows = int(arr.shape[0])
-            rc = self._lib.mi355rec_embed_stream_create(engine._h, arr.ctypes.data_as(ctypes.c_void_p), self.rows, self.dim, self.storage,
+            rc = self._fn("create")(engine._h, arr.ctypes.data_as(ctypes.c_void_p), self.rows, self.dim, self.storage,
                                                         ctypes.byref(self._e))
         if rc != capi.OK:
-            raise capi.Mi355Error(rc, (self._lib.mi355rec_embed_stream_last_error(None) or b"").decode("utf-8", "replace"))
+            raise capi.Mi355Error(rc, (self._fn("last_error")(None) or b"").decode("utf-8", "replace"))
 
     def _check(self, rc: int) -> None:
         if rc != capi.OK:
-            raise capi.Mi355Error(rc, (self._lib.mi355rec_embed_stream_last_error(self._e) or b"").decode("utf-8", "replace"))
+            raise capi.Mi355Error(rc, (self._fn("last_error")(self._e) or b"").decode("utf-8", "replace"))
 
     def close(self) -> None:
         """Destroys the native table (it waits for the device); a borrowed tensor is left as it is."""
         if getattr(self, "_e", None) is not None and self._e:
-            self._lib.mi355rec_embed_stream_destroy(self._e)
+            self._fn("destroy")(self._e)
             self._e = ctypes.c_void_p()
         self._engine = None
         self._table = None
@@ -163,7 +172,7 @@ class StreamedEmbeddingTable:
             q = capi.EmbedStreamUsers(size=ctypes.sizeof(capi.EmbedStreamUsers), users_dev=user.data_ptr(),
                                       exclude_dev=exclude.data_ptr() if L else None, n_users=n_users, topn=int(topn), exclude_len=L,
                                       metric=_METRICS[metric], w_embed=float(embed_weight))
-            self._check(self._lib.mi355rec_embed_stream_enqueue_users(self._e, ctypes.byref(q), ctypes.byref(res), handle))
+            self._check(self._fn("enqueue_users")(self._e, ctypes.byref(q), ctypes.byref(res), handle))
         else:
             q = capi.EmbedStreamQuery(size=ctypes.sizeof(capi.EmbedStreamQuery), user_dev=user.data_ptr(), exclude_dev=exclude.data_ptr() if L else None,
                                       audio_row=-1, n_exclude=L, topn=int(topn), metric=_METRICS[metric], w_audio=float(audio_weight),
@@ -176,14 +185,14 @@ class StreamedEmbeddingTable:
                 q.audio = a.ctypes.data
             elif audio_row is not None:
                 q.audio_row = int(audio_row)
-            self._check(self._lib.mi355rec_embed_stream_enqueue_query(self._e, ctypes.byref(q), ctypes.byref(res), handle))
+            self._check(self._fn("enqueue_query")(self._e, ctypes.byref(q), ctypes.byref(res), handle))
             del a   # (read before the call returned)
         return idx, score, count
 
     def info(self) -> dict:
         out = capi.EmbedStreamInfo()
         out.size = ctypes.sizeof(capi.EmbedStreamInfo)
-        self._check(self._lib.mi355rec_embed_stream_info(self._e, ctypes.byref(out)))
+        self._check(self._fn("info")(self._e, ctypes.byref(out)))
         d = {name: getattr(out, name) for name, _ in capi.EmbedStreamInfo._fields_ if name != "size"}
         d["table_dev"] = int(d["table_dev"] or 0)
         d["storage_name"] = _NAMES[d["storage"]]
