@@ -6,6 +6,7 @@
 // integers on purpose.
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <random>
@@ -310,9 +311,38 @@ void check_claims() {
     }
 }
 
+// `embed_cand_check claim IDS N ROW_BASE OUT`: claim_list over the int64 ids of the file IDS (a table of N rows from
+// ROW_BASE on), its rows_out written to OUT as uint32 words; the bitmap must be all zero behind clear_claims.  The buffers
+// are heap blocks of exactly their size, as in check_one_list.  (tests/test_embed_cand_steady_cpu.py holds its own
+// statement of what a workgroup meets against this one.)
+int claim_file(const char* ids_path, int64_t n, int64_t base, const char* out_path) {
+    std::FILE* f = std::fopen(ids_path, "rb");
+    if (!f) return 2;
+    std::fseek(f, 0, SEEK_END);
+    const long bytes = std::ftell(f);
+    std::fseek(f, 0, SEEK_SET);
+    const int64_t m = bytes / static_cast<long>(sizeof(int64_t));
+    std::unique_ptr<int64_t[]> ids(new int64_t[m ? m : 1]);
+    const size_t got = std::fread(ids.get(), sizeof(int64_t), static_cast<size_t>(m), f);
+    std::fclose(f);
+    if (got != static_cast<size_t>(m) || n < 0) return 2;
+    const size_t words = static_cast<size_t>(claim_words(n));
+    std::unique_ptr<uint32_t[]> bitmap(new uint32_t[words ? words : 1]());
+    std::unique_ptr<uint32_t[]> rows(new uint32_t[m ? m : 1]);
+    claim_list(ids.get(), m, base, n, bitmap.get(), rows.get());
+    clear_claims(rows.get(), m, bitmap.get());
+    for (size_t w = 0; w < words; ++w) EXPECT(bitmap[w] == 0u);
+    std::FILE* out = std::fopen(out_path, "wb");
+    if (!out) return 2;
+    const size_t put = std::fwrite(rows.get(), sizeof(uint32_t), static_cast<size_t>(m), out);
+    std::fclose(out);
+    return (put == static_cast<size_t>(m) && failures == 0) ? 0 : 1;
+}
+
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc == 6 && std::strcmp(argv[1], "claim") == 0) return claim_file(argv[2], std::atoll(argv[3]), std::atoll(argv[4]), argv[5]);
     check_layout();
     check_refusals();
     check_claims();
