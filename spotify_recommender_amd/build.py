@@ -352,6 +352,27 @@ def build_embed_cand(force: bool = False) -> Path:
     return LIB_EMBED_CAND
 
 
+# MULTI-INTEREST EMBEDDING REQUESTS: the seventh companion library (include/mi355rec_embed_multi.h).  Its own scan and finish
+# kernels (embed_multi.hip.h) over the row layouts of the embedding libraries, the stream library's prepare kernel and
+# merge_kernel, instantiated here, the engine's HIP_FLAGS, linked against the product library and against no other companion.
+LIB_EMBED_MULTI = PKG / "libmi355rec_embed_multi.so"
+EMBED_MULTI_DEPS = ([CSRC / "embed_multi.hip", CSRC / "embed_multi.hip.h", CSRC / "embed_multi_request.h", INCLUDE / "mi355rec_embed_multi.h"]
+                    + [d for d in EMBED_STREAM_DEPS if d.name != "embed_stream.hip"])   # (every header of the stream library is included)
+
+
+def build_embed_multi(force: bool = False) -> Path:
+    """Compile libmi355rec_embed_multi.so for gfx950; check_no_scratch applies to it exactly as to the product library."""
+    build_engine(force)
+    if force or _stale(LIB_EMBED_MULTI, EMBED_MULTI_DEPS + [LIB_ENGINE]):
+        _run([HIPCC, *HIP_FLAGS, "-o", LIB_EMBED_MULTI, CSRC / "embed_multi.hip", f"-L{PKG}", "-lmi355rec", "-Wl,-rpath,$ORIGIN"])
+        try:
+            check_no_scratch(LIB_EMBED_MULTI)
+        except Exception:
+            LIB_EMBED_MULTI.unlink(missing_ok=True)
+            raise
+    return LIB_EMBED_MULTI
+
+
 def shim_sources():
     return [CSRC / "Recommender.cpp", CSRC / "DataManager.cpp"]
 
@@ -398,6 +419,7 @@ def build_all(force: bool = False) -> None:
     build_embed_sets(force)    # (the fourth companion: hybrid requests restricted by row sets)
     build_embed_stream(force)  # (the fifth companion: device tensors in and out on the caller's stream)
     build_embed_cand(force)    # (the sixth companion: rank or score the listed rows of an embedding table by gather)
+    build_embed_multi(force)   # (the seventh companion: one pass for the K interests of one user, with attribution)
     build_shim(force)
     build_oracle(force)
 

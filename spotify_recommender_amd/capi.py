@@ -771,3 +771,58 @@ def embed_cand_lib() -> ctypes.CDLL:
             fn.argtypes = argtypes
         _embed_cand_lib = handle
     return _embed_cand_lib
+
+
+# ---- MULTI-INTEREST EMBEDDING REQUESTS: the seventh companion library libmi355rec_embed_multi.so
+# (include/mi355rec_embed_multi.h), an eighth table.  Every pointer named *_dev is device memory. ----
+EMBED_MULTI_LIB_PATH = PKG / "libmi355rec_embed_multi.so"
+EMBED_MULTI_MAX_INTERESTS = 32
+EMBED_MULTI_MAX_EXCLUDE = 1024
+
+
+class EmbedMultiQuery(ctypes.Structure):
+    """mi355rec_embed_multi_query_t; `size` is sizeof of this struct (72).  `audio` is 12 HOST floats."""
+    _fields_ = [("size", c_uint32), ("flags", c_uint32), ("interests_dev", c_void_p), ("audio", c_void_p), ("exclude_dev", c_void_p),
+                ("audio_row", c_int64), ("n_interests", c_int32), ("n_exclude", c_int32), ("topn", c_int32), ("metric", c_int32),
+                ("w_audio", c_float), ("w_embed", c_float), ("reserved", c_uint64)]
+
+
+class EmbedMultiResult(ctypes.Structure):
+    """mi355rec_embed_multi_result_t (40 bytes): EmbedStreamResult's fields, then out_interest_dev; the last three may be NULL."""
+    _fields_ = EmbedStreamResult._fields_ + [("out_interest_dev", c_void_p)]
+
+
+class EmbedMultiInfo(ctypes.Structure):
+    """mi355rec_embed_multi_info_t (96 bytes): EmbedStreamInfo's fields, then the interests' limit, the chunk width and the
+    launches per call."""
+    _fields_ = EmbedStreamInfo._fields_ + [("max_interests", c_int32), ("pass_interests", c_int32), ("query_launches", c_int32),
+                                           ("reserved", c_int32)]
+
+
+EMBED_MULTI_SIGNATURES = {
+    "mi355rec_embed_multi_create_device": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, POINTER(c_void_p)]),
+    "mi355rec_embed_multi_create": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, POINTER(c_void_p)]),
+    "mi355rec_embed_multi_destroy": (None, [c_void_p]),
+    "mi355rec_embed_multi_last_error": (c_char_p, [c_void_p]),
+    "mi355rec_embed_multi_info": (c_int, [c_void_p, POINTER(EmbedMultiInfo)]),
+    "mi355rec_embed_multi_enqueue_query": (c_int, [c_void_p, POINTER(EmbedMultiQuery), POINTER(EmbedMultiResult), c_void_p]),
+}
+
+_embed_multi_lib = None
+
+
+def embed_multi_lib() -> ctypes.CDLL:
+    """Load libmi355rec_embed_multi.so (it links against libmi355rec.so beside it; `lib()` is loaded first so that both share
+    one copy of it and of the HIP runtime).  A missing library is an error: the multi-interest requests have no fallback."""
+    global _embed_multi_lib
+    if _embed_multi_lib is None:
+        lib()
+        if not EMBED_MULTI_LIB_PATH.exists():
+            raise RuntimeError(f"{EMBED_MULTI_LIB_PATH} is missing: build it with `python -m spotify_recommender_amd.build`")
+        handle = ctypes.CDLL(str(EMBED_MULTI_LIB_PATH))
+        for name, (restype, argtypes) in EMBED_MULTI_SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _embed_multi_lib = handle
+    return _embed_multi_lib
